@@ -13,12 +13,19 @@ already resident in HBM.  Rank 0 prints ONE JSON line.
     python bench.py --workload base_b64_f16           # BASELINE config 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W        # BASELINE config 4 at N=8
+    python bench.py --full                            # the headline plus every other leg listed below
+    python bench.py --dump-outputs DIR                # also write the last timed step's ids to DIR/token_ids.npy
 
 Protocol of the timed region: K full passes of 64 clips per GPU, issued in groups of `config.pipeline_depth` = 8 through the
 library's pipeline slots (submit the group, collect the group, all-gather the group when N > 1); with `--coalesce 2` (default) the
 library pairs consecutive submits into one 128-row decode state — every submit still is B = 64 and receives exactly its own ids.
 
-Besides the contract's keys the line carries (all timed in this same run, N = 1 only):
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the optional output dump, the line.
+`--dump-outputs DIR` writes what the last timed step returned to its caller, the gathered ids of all utterances (prompt +
+generated, [utterances, 4 + 1 + 99]), as DIR/token_ids.npy in float32 (exact for ids below 2^24).  Weights (seed 0) and mels
+(utterance u: seed 1000 + u) are synthetic, so the same arguments give the same inputs in every run.
+
+With --full the line also carries (all timed in this same run, N = 1 only):
   value_uncoalesced  the same passes with one decode state per submit, four in flight (round 2's protocol) and the ratio
   value_with_h2d     the same K steps with the 61 MB of mels uploaded from pinned host memory INSIDE the timed region
                      (SURVEY §8d's literal timed region; `value` keeps the mels resident, as the bench contract asks)
@@ -348,6 +355,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="override utterances per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the other legs: unpipelined, kernel timings / roofline, H2D-inclusive, natural stop, "
+                         "uncoalesced, precision ladder, CPU baseline (--no-extras, --no-cpu-baseline, --no-x4 trim them)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the last timed step's gathered ids to DIR/token_ids.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-x4", action="store_true", help="skip the four-chains-in-flight decode step timing (profiler runs: keeps every launch of the dominant kernel alone on the chip)")
     ap.add_argument("--no-pipeline", action="store_true", help="run the steps strictly one after another")
@@ -359,6 +371,8 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the value_with_h2d / natural / precision_ladder legs (profiler and test runs)")
     ap.add_argument("--dump-ids", default="", help="rank 0 writes the gathered ids of the last timed step to this .npy file (tests)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     from whisper_mojo_amd import dist as wdist
@@ -394,19 +408,22 @@ def main():
     log(f"timed region done: {dt:.3f} s")
     if args.dump_ids and rank == 0:
         np.save(args.dump_ids, np.asarray(out, np.int32))
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "token_ids.npy"), np.asarray(out, np.float32))
 
     extras = {}
-    if depth > 1:  # the same K steps strictly one after another (no overlap between steps), for reference
+    if args.full and depth > 1:  # the same K steps strictly one after another (no overlap between steps), for reference
         b.run_steps(1, 1)
         seq_dt, _ = b.timed(args.steps, 1)
         extras["unpipelined"] = {"ms_per_step": round(seq_dt / args.steps * 1e3, 3), "value": round(b.rates(seq_dt, args.steps, 1)[0], 1)}
-    if world == 1:
+    if args.full and world == 1:
         # the decode step as a pass really runs it (cache length growing 4 .. 103): synchronous passes with and without the loop
         b.run_steps(1, 1, max_loop=0)
         t_full, _ = b.timed(3, 1, gather=False)
         t_none, _ = b.timed(3, 1, max_loop=0, gather=False)
         extras["_in_pass_step_us"] = (t_full - t_none) / 3 / DECODE_STEPS * 1e6
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         log("H2D-inclusive leg")
         b.run_steps(min(depth, args.steps), depth, mel=b.mel_host)
         h_dt, _ = b.timed(args.steps, depth, mel=b.mel_host)  # pinned host mels: every pass uploads its 61 MB inside the timed region
@@ -442,8 +459,6 @@ def main():
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         rtf, tok_s = b.rates(dt, args.steps, DECODE_STEPS + 1)
-        log("kernel timings (cross-attention, decode step, encoder)")
-        k = b.kernel_timings(x4=not args.no_x4)
         dtype, prec = precision_of(args.workload, b.cdt, b.kdt)
         res = {
             "metric": "real-time-factor (audio-sec/wall-sec)", "value": round(rtf, 1), "unit": "x real-time",
@@ -459,41 +474,44 @@ def main():
                                     f"{depth} submits in flight = {depth // 2} passes of 128 rows; every submit is B = 64 and receives its own ids, "
                                     "bit-identical to the uncoalesced run (tests/test_gpu_edges.py)") if args.coalesce == 2 else "off"},
         }
-        in_pass = extras.pop("_in_pass_step_us", None)
-        res.update(extras)
-        res.update(k)
-        if in_pass is not None:  # next to the replayed step (cache length held at 50): the average over a real pass's 99 steps
-            sb = res["decode_step"]["algorithmic_bytes"]
-            res["decode_step"]["cache_len"] = 50
-            res["decode_step"]["in_pass_avg_us"] = round(in_pass, 1)
-            res["decode_step"]["in_pass_frac_of_hbm_peak"] = round(sb / (in_pass * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
-        if world == 1 and not args.no_extras:
-            if args.coalesce == 2:  # the same workload with one decode state per submit, four in flight (round 2's protocol)
-                log("uncoalesced comparison")
-                b.model.close()
-                u = Bench(args.workload, args.batch, rank, world, local, weights_cache, coalesce=0)
-                try:
-                    u.setup_slots(4)
-                    u.run_steps(4, 4)
-                    u_dt, _ = u.timed(12, 4)
-                    res["value_uncoalesced"] = {"value": round(u.rates(u_dt, 12, 1)[0], 1), "ms_per_step": round(u_dt / 12 * 1e3, 3), "steps": 12,
-                                                "pipeline_depth": 4, "ratio": round(res["value"] / u.rates(u_dt, 12, 1)[0], 4)}
-                finally:
-                    u.close()
-            res["precision_ladder"] = []
-            for name in LADDER:
-                if name == args.workload:
-                    continue
-                log(f"precision ladder: {name}")
-                b.model.close()  # one model resident at a time
-                res["precision_ladder"].append(ladder_entry(name, rank, world, local, weights_cache, depth))
-                if name == "tiny_b64_bf16":  # round 2's headline, kept as a named extra: NOT config 3 (decoder and KV narrowed too)
-                    e = res["precision_ladder"][-1]
-                    res["value_all_16bit"] = {"value": e["value"], "ms_per_step": e["ms_per_step"], "steps": e["steps"], "coalesced": e["coalesced"],
-                                              "note": "bf16 operands in the decoder too + bf16 KV cache: narrower than BASELINE config 3"}
-        if not args.no_cpu_baseline and world == 1:
-            log("cpu baseline (oracle) ...")
-            res["cpu_baseline"] = cpu_baseline(b.cfg, b.weights, b.mel_host[0], DECODE_STEPS)
+        if args.full:
+            log("kernel timings (cross-attention, decode step, encoder)")
+            k = b.kernel_timings(x4=not args.no_x4)
+            in_pass = extras.pop("_in_pass_step_us", None)
+            res.update(extras)
+            res.update(k)
+            if in_pass is not None:  # next to the replayed step (cache length held at 50): the average over a real pass's 99 steps
+                sb = res["decode_step"]["algorithmic_bytes"]
+                res["decode_step"]["cache_len"] = 50
+                res["decode_step"]["in_pass_avg_us"] = round(in_pass, 1)
+                res["decode_step"]["in_pass_frac_of_hbm_peak"] = round(sb / (in_pass * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
+            if world == 1 and not args.no_extras:
+                if args.coalesce == 2:  # the same workload with one decode state per submit, four in flight (round 2's protocol)
+                    log("uncoalesced comparison")
+                    b.model.close()
+                    u = Bench(args.workload, args.batch, rank, world, local, weights_cache, coalesce=0)
+                    try:
+                        u.setup_slots(4)
+                        u.run_steps(4, 4)
+                        u_dt, _ = u.timed(12, 4)
+                        res["value_uncoalesced"] = {"value": round(u.rates(u_dt, 12, 1)[0], 1), "ms_per_step": round(u_dt / 12 * 1e3, 3), "steps": 12,
+                                                    "pipeline_depth": 4, "ratio": round(res["value"] / u.rates(u_dt, 12, 1)[0], 4)}
+                    finally:
+                        u.close()
+                res["precision_ladder"] = []
+                for name in LADDER:
+                    if name == args.workload:
+                        continue
+                    log(f"precision ladder: {name}")
+                    b.model.close()  # one model resident at a time
+                    res["precision_ladder"].append(ladder_entry(name, rank, world, local, weights_cache, depth))
+                    if name == "tiny_b64_bf16":  # round 2's headline, kept as a named extra: NOT config 3 (decoder and KV narrowed too)
+                        e = res["precision_ladder"][-1]
+                        res["value_all_16bit"] = {"value": e["value"], "ms_per_step": e["ms_per_step"], "steps": e["steps"], "coalesced": e["coalesced"],
+                                                  "note": "bf16 operands in the decoder too + bf16 KV cache: narrower than BASELINE config 3"}
+            if not args.no_cpu_baseline and world == 1:
+                log("cpu baseline (oracle) ...")
+                res["cpu_baseline"] = cpu_baseline(b.cfg, b.weights, b.mel_host[0], DECODE_STEPS)
         print(json.dumps(res), flush=True)
     b.close()
     if world > 1 or torch.distributed.is_initialized():

@@ -52,10 +52,18 @@ def test_product_never_imports_the_oracle():
 
 def test_package_import_sets_hw_queue_default():
     """Pipelined passes need one hardware queue per slot stream: the package sets GPU_MAX_HW_QUEUES before HIP
-    initialises unless the user already chose a value."""
-    import os
-    import whisper_mojo_amd  # noqa: F401
-    assert int(os.environ.get("GPU_MAX_HW_QUEUES", "0")) >= 8
+    initialises unless the user already chose a value.  A fresh child process each time: this process's environment may
+    carry a value of its own."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
+
+    def queues_after_import(**extra):
+        code = "import os, whisper_mojo_amd; print(os.environ.get('GPU_MAX_HW_QUEUES', '0'))"
+        return int(subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=dict(env, **extra), capture_output=True, text=True,
+                                  check=True).stdout)
+    assert queues_after_import() >= 8
+    assert queues_after_import(GPU_MAX_HW_QUEUES="12") == 12
 
 
 def test_op_wrappers_validate_shapes_before_calling_the_library():

@@ -31,10 +31,10 @@ def hip():
     return True
 
 
-def _bench(n, batch, dump, extra_env):
+def _bench(n, batch, dump, extra_env, outputs=None):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     args = ["bench.py", "--gpus", str(n), "--steps", "4", "--warmup", "0", "--no-cpu-baseline", "--no-x4", "--no-extras", "--batch", str(batch),
-            "--dump-ids", dump]
+            "--dump-ids", dump] + (["--dump-outputs", outputs] if outputs else [])
     if n == 1:
         cmd = [sys.executable] + args
     else:
@@ -50,11 +50,14 @@ def _bench(n, batch, dump, extra_env):
 def test_bench_two_ranks_equal_one_rank(hip, tmp_path):
     one, two = str(tmp_path / "one.npy"), str(tmp_path / "two.npy")
     r2 = _bench(2, 8, two, {"WM_BENCH_BACKEND": "gloo", "WM_BENCH_SINGLE_DEVICE": "1"})
-    r1 = _bench(1, 16, one, {})
+    r1 = _bench(1, 16, one, {}, outputs=str(tmp_path / "outputs"))
     assert r2["n_gpus"] == 2 and r2["scaling"] == "weak" and r2["config"]["parallelism"] == "dp2"
     a, b = np.load(one), np.load(two)
     assert a.shape == b.shape == (16, 4 + 1 + 99)
     assert np.array_equal(a, b)
+    assert r1["steps"] == 4 and r1["ms_per_step"] > 0
+    c = np.load(tmp_path / "outputs" / "token_ids.npy")  # --dump-outputs: the same ids as float32
+    assert c.dtype == np.float32 and np.array_equal(c, a)
 
 
 def _sharded_worker(rank, world, port, total, q):

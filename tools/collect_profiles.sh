@@ -7,9 +7,9 @@ cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 O=gpurun_out/prof; rm -rf $O; mkdir -p $O
 say() { echo "[$(date +%T)] $*" | tee -a $O/progress.log; }
 say solo stats
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/solo -- python3 bench.py --no-pipeline --no-cpu-baseline --no-x4 --no-extras > $O/bench_solo.json 2> $O/bench_solo.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/solo -- python3 bench.py --full --no-pipeline --no-cpu-baseline --no-x4 --no-extras > $O/bench_solo.json 2> $O/bench_solo.err
 say pipelined stats
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/pipe -- python3 bench.py --no-cpu-baseline --no-x4 --no-extras > $O/bench_pipe.json 2> $O/bench_pipe.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/pipe -- python3 bench.py --full --no-cpu-baseline --no-x4 --no-extras > $O/bench_pipe.json 2> $O/bench_pipe.err
 say mfma busy
 rocprofv3 --kernel-trace --output-format csv --pmc SQ_VALU_MFMA_BUSY_CYCLES -d $O/busy -- python3 tools/enc_bench.py 2 > /dev/null 2>&1
 say grbm

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Reduce two rocprofv3 PMC passes (--pmc FETCH_SIZE and --pmc WRITE_SIZE, each with --kernel-trace only) of
-`python bench.py --steps 1 --warmup 0 --no-cpu-baseline` into profiles/<name>.json: HBM bytes per launch of the
+`python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline` into profiles/<name>.json: HBM bytes per launch of the
 cross-attention and logits kernels, with the gfx950 correction of MI355X_MICROARCH.md §HBM (FETCH_SIZE reports half of a
 wide coalesced 16 B/lane streaming read; WRITE_SIZE is exact; both in KB).
 Usage: pmc_traffic.py <fetch_dir> <write_dir> <out.json> <algorithmic_bytes_cross_attn> [workload]
@@ -16,7 +16,7 @@ def collect(d, counter):
     return vals
 
 fetch, write = collect(sys.argv[1], "FETCH_SIZE"), collect(sys.argv[2], "WRITE_SIZE")
-out = {"note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) of `python bench.py --steps 1 "
+out = {"note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) of `python bench.py --full --steps 1 "
                "--warmup 0 --no-cpu-baseline` (tiny_b64_bf16). Units: counter value = KB.  gfx950 correction (MI355X_MICROARCH.md "
                "§HBM): FETCH_SIZE reports 1/2 of a wide coalesced 16 B/lane streaming read -> fetch_bytes = 2 * FETCH_SIZE * 1024; "
                "WRITE_SIZE is exact.  Reduced by tools/pmc_traffic.py.", "kernels": {}}

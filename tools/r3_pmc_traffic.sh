@@ -4,7 +4,7 @@
 set -e
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 O=gpurun_out/r3_pmc; rm -rf $O; mkdir -p $O
-CMD="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-x4 --no-extras --no-pipeline"
+CMD="python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-x4 --no-extras --no-pipeline"
 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $O/fetch -- $CMD > $O/fetch.json 2> $O/fetch.err
 echo "[$(date +%T)] fetch pass done"
 rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d $O/write -- $CMD > $O/write.json 2> $O/write.err
