@@ -1428,6 +1428,339 @@ void launch_attn_combine(const float* part_o, const float* part_ml, void* out, i
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Cross-attention over the encoder output X (bf16 encoder operands, fp32 K/V): the K/V projections are absorbed into the
+// query and the output instead of being materialised as an fp32 cache.  For head h (Wk has no bias; bv is added after the
+// softmax average because the weights sum to one):
+//     s_hj = (scale·q_h)·(Wk_h·X_j) = q'_h·X_j,   q'_h = (scale·q_h)·Wk_h            (a d-vector per head)
+//     o_h  = Σ_j p_hj (Wv_h·X_j + bv_h) / l_h = ((Σ_j p_hj X_j) / l_h)·Wv_hᵀ + bv_h
+// X is the projection's own bf16 operand, so the step streams n_keys·d·2 bytes per utterance and layer instead of
+// 2·n_keys·d·4: a quarter of the bytes.  Every product is still an exact product of a bf16 value with an fp32 value
+// (the fp32 factor carried as three bf16 terms, h + m + l, which reproduce it exactly in the normal range); only the
+// order of the fp32 roundings differs from the cached form.
+
+// fp32 -> three bf16 by truncation: x = h + m + l exactly (8 + 8 + 8 significant bits; as split3 above)
+__device__ __forceinline__ void split3_1(float x, unsigned short& h, unsigned short& m, unsigned short& l) {
+    const unsigned uh = __float_as_uint(x) & 0xffff0000u;
+    const float r1 = x - __uint_as_float(uh);
+    const unsigned um = __float_as_uint(r1) & 0xffff0000u;
+    const float r2 = r1 - __uint_as_float(um);
+    h = (unsigned short)(uh >> 16);
+    m = (unsigned short)(um >> 16);
+    l = (unsigned short)(__float_as_uint(r2) >> 16);
+}
+
+// q'[row][h][c] = Σ_e (scale·q[row][h*64+e])·Wk[h*64+e][c], written once per row as three bf16 images [row][3][H][d].
+// grid (ceil(rows / 4), H), d/2 threads: thread t owns columns 2t, 2t+1 of four rows (one coalesced Wk row read per e).
+__global__ __launch_bounds__(256) void xattn_absorb_kernel(XAttnParams p) {
+    constexpr int R = 4;
+    __shared__ float sq[R][64];
+    const int r0 = blockIdx.x * R, h = blockIdx.y, t = threadIdx.x;
+    for (int i = t; i < R * 64; i += blockDim.x) {
+        const int r = r0 + i / 64;
+        sq[i / 64][i % 64] = r < p.rows ? p.q[(size_t)r * p.d + h * 64 + i % 64] * p.scale : 0.f;
+    }
+    __syncthreads();
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+    const bf16* w = (const bf16*)p.Wk + (size_t)h * 64 * p.d + 2 * t;
+    float acc[R][2];
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r][0] = acc[r][1] = 0.f;
+#pragma unroll 16
+    for (int e = 0; e < 64; ++e) {
+        const bf16x2 wv = *reinterpret_cast<const bf16x2*>(w + (size_t)e * p.d);
+        const float w0 = (float)wv[0], w1 = (float)wv[1];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            acc[r][0] = fmaf(sq[r][e], w0, acc[r][0]);
+            acc[r][1] = fmaf(sq[r][e], w1, acc[r][1]);
+        }
+    }
+    unsigned short* qs = (unsigned short*)p.qs;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (r0 + r >= p.rows) break;
+        unsigned short hh[2], mm[2], ll[2];
+        split3_1(acc[r][0], hh[0], mm[0], ll[0]);
+        split3_1(acc[r][1], hh[1], mm[1], ll[1]);
+        const size_t img = (size_t)p.H * p.d, base = (size_t)(r0 + r) * 3 * img + (size_t)h * p.d + 2 * t;
+        *reinterpret_cast<unsigned*>(qs + base) = hh[0] | ((unsigned)hh[1] << 16);
+        *reinterpret_cast<unsigned*>(qs + base + img) = mm[0] | ((unsigned)mm[1] << 16);
+        *reinterpret_cast<unsigned*>(qs + base + 2 * img) = ll[0] | ((unsigned)ll[1] << 16);
+    }
+}
+
+// The X sweep.  grid (nsplit key chunks, rows), 4 waves; each wave takes every 4th 16-key tile of the chunk.
+//   S (16 keys x 16 columns = heads, columns >= H read a zero row) = X_tile · q'ᵀ: per 32-dim k-step three
+//     v_mfma_f32_16x16x32_bf16 (q' = h + m + l) into one accumulator; A = X rows straight from global memory (16 B per lane).
+//   online softmax per head as attn_decode_kernel: running max from -1e10, scale already inside q', expf.
+//   Yᵀ (d x heads) += X_tileᵀ · P: the tile is parked row-major in the wave's LDS slice and read back transposed with
+//     ds_read_b64_tr_b16 (lane (dim r16, group g) gets keys 4g..4g+3 — exactly the keys its P fragment holds, the C map of S);
+//     P = h + m + l as three v_mfma_f32_16x16x16_bf16.
+// The four waves' (Y, m, l) are merged through LDS and leave as one un-normalised partial per chunk.
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+__device__ __forceinline__ f32x4 mma16_bf16(const bf16x4& a, const bf16x4& b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
+}
+__device__ __forceinline__ bf16x4 lds_tr16_bf16(const bf16* p) {
+    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)p);
+}
+__device__ __forceinline__ void wave_lds_fence() {  // this wave's LDS writes / reads are ordered against its next ones
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+template <int H, bool NT>
+__global__ __launch_bounds__(256, 2) void xattn_kernel(XAttnParams p) {
+    constexpr int D = 64 * H, NKS = D / 32, NDB = D / 16;
+    constexpr int XP = D + 16;  // row pitch (elements): 32·H + 8 dwords, so the 8 rows of one transposed read hit disjoint banks
+    __shared__ __attribute__((aligned(16))) bf16 sQ[3 * (H + 1) * XP];  // q' images; row H of each image is zero
+    __shared__ __attribute__((aligned(16))) bf16 sX[4 * 16 * XP];        // per wave: the parked 16-key tile; at the end: Y of 4 waves
+    __shared__ float sML[4][H][2];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r16 = lane & 15, g = lane >> 4;
+    const int split = blockIdx.x, row = blockIdx.y;
+    const int utt = p.q_B > 0 ? row % p.q_B : row;
+    const int len = p.n_keys, chunk = (len + p.nsplit - 1) / p.nsplit;
+    const int j0 = split * chunk, j1 = min(len, j0 + chunk);
+    {
+        const bf16x8* src = (const bf16x8*)((const bf16*)p.qs + (size_t)row * 3 * H * D);
+        for (int i = threadIdx.x; i < 3 * (H + 1) * (D / 8); i += 256) {
+            const int img = i / ((H + 1) * (D / 8)), rem = i % ((H + 1) * (D / 8)), hh = rem / (D / 8), c8 = rem % (D / 8);
+            bf16x8 v = {};
+            if (hh < H) v = src[(img * H + hh) * (D / 8) + c8];
+            *reinterpret_cast<bf16x8*>(&sQ[(img * (H + 1) + hh) * XP + c8 * 8]) = v;
+        }
+    }
+    __syncthreads();
+    const int hq = r16 < H ? r16 : H;
+    const bf16* X = (const bf16*)p.X + (size_t)utt * p.x_stride;
+    bf16* park = sX + w * 16 * XP;
+    f32x4 y[NDB];
+#pragma unroll
+    for (int db = 0; db < NDB; ++db) y[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run = -1e10f, l_run = 0.f;
+    const int ntile = j1 > j0 ? (j1 - j0 + 15) / 16 : 0;
+
+    auto load = [&](bf16x8 (&xr)[NKS], int t) {
+        const int key = max(min(j0 + 16 * t + r16, j1 - 1), 0);
+        const bf16* src = X + (size_t)key * D + g * 8;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            if (NT)
+                xr[ks] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(src + ks * 32));
+            else
+                xr[ks] = *reinterpret_cast<const bf16x8*>(src + ks * 32);
+        }
+    };
+    auto consume = [&](const bf16x8 (&xr)[NKS], int t) {
+        // one accumulator per q' term: three independent MFMA chains of NKS instead of one dependent chain of 3·NKS
+        f32x4 sk[3] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const bf16x8 qf = *reinterpret_cast<const bf16x8*>(&sQ[(k * (H + 1) + hq) * XP + ks * 32 + g * 8]);
+                sk[k] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xr[ks], qf, sk[k], 0, 0, 0);
+            }
+        const f32x4 s = (sk[0] + sk[1]) + sk[2];
+        // lane (head r16, group g) holds the scores of keys 4g..4g+3 of the tile
+        const int kb = j0 + 16 * t + 4 * g;
+        float sc[4], bm = -1e30f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            sc[r] = kb + r < j1 ? s[r] : -1e30f;
+            bm = fmaxf(bm, sc[r]);
+        }
+        bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
+        bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+        const float m_new = fmaxf(m_run, bm);
+        const float alpha = expf(m_run - m_new);
+        float pe[4], ps = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            pe[r] = expf(sc[r] - m_new);
+            ps += pe[r];
+        }
+        ps += __shfl_xor(ps, 16, 64);
+        ps += __shfl_xor(ps, 32, 64);
+        l_run = l_run * alpha + ps;
+        m_run = m_new;
+        typedef __attribute__((ext_vector_type(4))) unsigned short u16x4;
+        u16x4 ph, pm, pl;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            unsigned short a, b, c;
+            split3_1(pe[r], a, b, c);
+            ph[r] = a;
+            pm[r] = b;
+            pl[r] = c;
+        }
+        const bf16x4 fh = __builtin_bit_cast(bf16x4, ph), fm = __builtin_bit_cast(bf16x4, pm), fl = __builtin_bit_cast(bf16x4, pl);
+        wave_lds_fence();  // the previous tile's transposed reads are done
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) *reinterpret_cast<bf16x8*>(&park[r16 * XP + ks * 32 + g * 8]) = xr[ks];
+        wave_lds_fence();
+#pragma unroll
+        for (int db = 0; db < NDB; ++db) {
+            const bf16x4 xt = lds_tr16_bf16(&park[(4 * g + (r16 >> 2)) * XP + db * 16 + (r16 & 3) * 4]);
+            f32x4 a = y[db] * alpha;
+            a = mma16_bf16(xt, fh, a);
+            a = mma16_bf16(xt, fm, a);
+            y[db] = mma16_bf16(xt, fl, a);
+        }
+    };
+
+    if (w < ntile) {
+        bf16x8 xa[NKS], xb[NKS];
+        int t = w;
+        load(xa, t);
+        while (true) {
+            const bool more1 = t + 4 < ntile;
+            if (more1) load(xb, t + 4);
+            consume(xa, t);
+            t += 4;
+            if (!more1) break;
+            const bool more2 = t + 4 < ntile;
+            if (more2) load(xa, t + 4);
+            consume(xb, t);
+            t += 4;
+            if (!more2) break;
+        }
+    }
+    // merge the four waves (as attn_decode_kernel merges its row slots), write the chunk's partial
+    __syncthreads();
+    float* sY = reinterpret_cast<float*>(sX);  // [4][H][D]
+    if (r16 < H) {
+#pragma unroll
+        for (int db = 0; db < NDB; ++db)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sY[(w * H + r16) * D + db * 16 + 4 * g + r] = y[db][r];
+        if (g == 0) {
+            sML[w][r16][0] = m_run;
+            sML[w][r16][1] = l_run;
+        }
+    }
+    __syncthreads();
+    const size_t prow = (size_t)row * p.nsplit + split;
+    for (int i = threadIdx.x; i < H * D; i += 256) {
+        const int h = i / D;
+        float M = -1e10f;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) M = fmaxf(M, sML[v][h][0]);
+        float L = 0.f, o = 0.f;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const float wgt = sML[v][h][1] > 0.f ? expf(sML[v][h][0] - M) : 0.f;
+            L += wgt * sML[v][h][1];
+            o += wgt * sY[v * H * D + i];
+        }
+        p.part_y[prow * H * D + i] = o;
+        if (i % D == 0) {
+            p.part_ml[(prow * H + h) * 2] = M;
+            p.part_ml[(prow * H + h) * 2 + 1] = L;
+        }
+    }
+}
+
+// Merge the chunk partials of one head (exactly attn_combine_kernel's weights) and apply Wv_h: out[row][h*64+e] =
+// y_h·Wv[h*64+e]ᵀ + bv[h*64+e].  grid (ceil(rows / 4), H), 256 threads: four rows per workgroup share each Wv row read.
+__global__ __launch_bounds__(256) void xattn_merge_kernel(XAttnParams p) {
+    constexpr int R = 4, DMAX = 512;
+    __shared__ __attribute__((aligned(16))) float sy[R][DMAX];
+    __shared__ float sw[R][64], sL[R];
+    const int r0 = blockIdx.x * R, h = blockIdx.y, t = threadIdx.x, D = p.d, H = p.H, ns = p.nsplit;
+    if (t < R * 64) {  // chunk weights of row r0 + t/64, one wave per row
+        const int r = t >> 6, lane = t & 63, row = r0 + r;
+        float m = -1e30f, l = 0.f;
+        if (row < p.rows && lane < ns) {
+            const float* ml = p.part_ml + (((size_t)row * ns + lane) * H + h) * 2;
+            m = ml[0];
+            l = ml[1];
+        }
+        const float M = wave_max(l > 0.f ? m : -1e30f);
+        const float wgt = l > 0.f ? expf(m - M) : 0.f;
+        const float L = wave_sum(wgt * l);
+        if (lane < 64) sw[r][lane] = wgt;
+        if (lane == 0) sL[r] = L;
+    }
+    __syncthreads();
+    for (int i = t; i < R * D; i += blockDim.x) {
+        const int r = i / D, c = i % D, row = r0 + r;
+        float o = 0.f;
+        if (row < p.rows) {
+            const float* py = p.part_y + ((size_t)row * ns * H + h) * D + c;
+            for (int s = 0; s < ns; ++s) o += sw[r][s] * py[(size_t)s * H * D];
+            o *= 1.0f / sL[r];
+        }
+        sy[r][c] = o;
+    }
+    __syncthreads();
+    // V-apply: four lanes per output feature e, interleaved over c so that they read 64 contiguous bytes of the Wv row per load
+    // (one lane per whole Wv row, 64 rows per load, measured 14.4 us per launch at 128 rows)
+    const int e = t >> 2, q = t & 3;
+    const bf16* wv = (const bf16*)p.Wv + (size_t)(h * 64 + e) * D;
+    float acc[R] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int it = 0; it < D / 32; ++it) {
+        const int c = (it * 4 + q) * 8;
+        const bf16x8 wf = *reinterpret_cast<const bf16x8*>(wv + c);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const f32x4 ya = *reinterpret_cast<const f32x4*>(&sy[r][c]), yb = *reinterpret_cast<const f32x4*>(&sy[r][c + 4]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[r] = fmaf(ya[k], (float)wf[k], acc[r]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[r] = fmaf(yb[k], (float)wf[4 + k], acc[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        acc[r] += __shfl_xor(acc[r], 1, 64);
+        acc[r] += __shfl_xor(acc[r], 2, 64);
+        if (q == 0 && r0 + r < p.rows) store_as(p.out, (size_t)(r0 + r) * D + h * 64 + e, acc[r] + p.bv[h * 64 + e], p.out_dtype);
+    }
+}
+
+static int xattn_check(const XAttnParams& p) {
+    if (p.H < 1 || p.H > 8 || p.d != 64 * p.H || p.rows <= 0 || p.nsplit < 1 || p.nsplit > 64 || p.n_keys < 1)
+        return launch_refuse("xattn: needs 1 <= heads <= 8 of 64 dims, rows > 0, 1 <= nsplit <= 64");
+    return WM_LAUNCH_OK;
+}
+int launch_xattn_absorb(const XAttnParams& p, hipStream_t st) {
+    if (const int rc = xattn_check(p)) return rc;
+    hipLaunchKernelGGL(xattn_absorb_kernel, dim3((p.rows + 3) / 4, p.H), dim3(p.d / 2), 0, st, p);
+    return WM_LAUNCH_OK;
+}
+template <int H> static void launch_xattn_h(const XAttnParams& p, hipStream_t st) {
+    // X is re-read by every layer of the step (147 MB for 128 rows: inside the 256 MB Infinity Cache).  WM_XATTN_NT (developer
+    // build): non-temporal loads for A/B.
+    static const bool nt = wm_env("WM_XATTN_NT") != nullptr;
+    const dim3 grid(p.nsplit, p.rows), block(256);
+    if (nt)
+        hipLaunchKernelGGL((xattn_kernel<H, true>), grid, block, 0, st, p);
+    else
+        hipLaunchKernelGGL((xattn_kernel<H, false>), grid, block, 0, st, p);
+}
+int launch_xattn(const XAttnParams& p, hipStream_t st) {
+    if (const int rc = xattn_check(p)) return rc;
+    switch (p.H) {
+        case 1: launch_xattn_h<1>(p, st); break;
+        case 2: launch_xattn_h<2>(p, st); break;
+        case 3: launch_xattn_h<3>(p, st); break;
+        case 4: launch_xattn_h<4>(p, st); break;
+        case 5: launch_xattn_h<5>(p, st); break;
+        case 6: launch_xattn_h<6>(p, st); break;
+        case 7: launch_xattn_h<7>(p, st); break;
+        default: launch_xattn_h<8>(p, st); break;
+    }
+    return WM_LAUNCH_OK;
+}
+int launch_xattn_merge(const XAttnParams& p, hipStream_t st) {
+    if (const int rc = xattn_check(p)) return rc;
+    hipLaunchKernelGGL(xattn_merge_kernel, dim3((p.rows + 3) / 4, p.H), dim3(256), 0, st, p);
+    return WM_LAUNCH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // argmax with the reference's tie rule (strict '>' scanning upward => lowest index wins, whisper_tensor.mojo:436)
 // + the greedy loop's bookkeeping (whisper.mojo:200-221): append the id, stop an utterance after its eot.
 // block-wide (value, index) argmax of row[0..V): 16-byte loads (row 16-byte aligned, V rounded up inside the padded

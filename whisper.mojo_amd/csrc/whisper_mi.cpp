@@ -191,6 +191,10 @@ struct wm_model {
     std::vector<DecLayer> dec;
     DevBuf dec_ln_g, dec_ln_b;
     DevBuf cross_kv_w, cross_kv_b;  // [L*2*d][d] rows: layer-major, K then V
+    // Cross-attention over the bf16 encoder output with the K/V projections absorbed (bf16 encoder operands + fp32 K/V, d = 64·H,
+    // H <= 8): states keep X = ln_post rows in bf16 instead of an fp32 cross K/V cache, a quarter of the bytes per decode step
+    // (DESIGN §3).  Chosen at load time and used by every entry point of the model; WM_XATTN_OFF (developer build) keeps the cache.
+    bool xattn = false;
     DevBuf ts_buf;     // developer timeline (WM_TRACE_EVENTS=<file>): count + (tag, clock) pairs
     // log-mel front end (lazy): constants + scratch sized for max_batch utterances
     struct Frontend {
@@ -279,7 +283,9 @@ struct wm_state {
     // encoder arena (sized for Bc utterances)
     DevBuf mel_dev, mel_t, h1, x, xn, qkv, ao, hid, enc_t;
     DevBuf enc_f;            // [B*n_ctx][d] fp32
-    DevBuf cross_kv;         // [L][2][B][n_ctx][d] kv dtype
+    DevBuf cross_kv;         // [L][2][B][n_ctx][d] kv dtype (not allocated when m->xattn)
+    DevBuf enc_x;            // m->xattn: [B][n_ctx][d] bf16 ln_post rows, what the cross-attention streams
+    DevBuf xq, part_y;       // m->xattn: q' images [rows][3][H][d] bf16; chunk partials [rows][nsplit][H][d] fp32
     DevBuf self_kv;          // [L][2][B][n_text_ctx][d]
     // decode arena
     DevBuf mask_steady, mask_begin;  // [Vpad] additive logit masks (0 / -inf) for the fused argmax
@@ -560,6 +566,8 @@ extern "C" int wm_model_load_memory(const float* weights, size_t n_floats, const
     m->cfg = *cfg;
     m->device = device;
     if (const char* e = wm_env("WM_ENC_CHUNK")) m->enc_chunk = std::max(1, atoi(e));
+    m->xattn = cfg->compute_dtype == WM_BF16 && cfg->kv_dtype == WM_F32 && cfg->dims.n_heads <= 8 &&
+               cfg->dims.d_model == 64 * cfg->dims.n_heads && !wm_env("WM_XATTN_OFF");
     hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete m;
@@ -759,7 +767,7 @@ extern "C" void wm_state_free(wm_state* s) {
         if (ev) (void)hipEventDestroy(ev);
     if (s->h_prog) (void)hipHostFree((void*)s->h_prog);
     DevBuf* bs[] = {&s->mel_dev, &s->mel_t, &s->h1, &s->x, &s->xn, &s->qkv, &s->ao, &s->hid, &s->enc_t, &s->enc_f,
-                    &s->cross_kv, &s->self_kv, &s->dx, &s->dq, &s->dattn, &s->dhid, &s->part_o, &s->part_ml, &s->logits, &s->amax_val, &s->amax_idx, &s->ts_state, &s->ts_val, &s->ts_idx, &s->ts_m, &s->ts_s, &s->mask_steady, &s->mask_begin,
+                    &s->cross_kv, &s->enc_x, &s->xq, &s->part_y, &s->self_kv, &s->dx, &s->dq, &s->dattn, &s->dhid, &s->part_o, &s->part_ml, &s->logits, &s->amax_val, &s->amax_idx, &s->ts_state, &s->ts_val, &s->ts_idx, &s->ts_m, &s->ts_s, &s->mask_steady, &s->mask_begin,
                     &s->tok, &s->pos, &s->tok_rows, &s->pos_rows, &s->ctl, &s->out_tokens, &s->n_tokens, &s->finished};
     for (DevBuf* b : bs) b->release();
     delete s;
@@ -799,7 +807,15 @@ static int state_new(wm_model* m, int B, wm_state** out, bool pair) {
         int ns = (target + m->cfg.max_batch - 1) / m->cfg.max_batch;
         ns = std::max(ks == 4 ? 8 : 12, std::min(48, ns));
         ns = std::max(min_split, std::min(ns, (int)((T + 31) / 32)));
-        if (const char* e = wm_env("WM_NSPLIT")) ns = std::max(min_split, std::min(64, atoi(e)));
+        if (m->xattn) {
+            // absorbed cross-attention: a chunk carries fixed costs the K/V stream did not have (q' images into LDS, an H·d partial,
+            // its share of the merge), so fewer, longer chunks: ~128 per max_batch rows, at least 64 keys (one tile per wave).
+            // Measured, headline (128-row states), ms per 64-clip pass: 32 chunks 32.1, 24: 28.3, 16: 26.0, 8: 23.5, 6: 23.5,
+            // 4: 22.3-22.5, 3: 21.8, 2: 21.4
+            ns = (128 + m->cfg.max_batch - 1) / m->cfg.max_batch;
+            ns = std::max(1, std::min({ns, 48, (int)T / 64}));
+        }
+        if (const char* e = wm_env("WM_NSPLIT")) ns = std::max(m->xattn ? 1 : min_split, std::min(64, atoi(e)));
         s->nsplit = ns;
     }
     s->out_stride = OUT_STRIDE_MAX;
@@ -817,9 +833,13 @@ static int state_new(wm_model* m, int B, wm_state** out, bool pair) {
     A(s->qkv, Mp * 3 * d * ts, true);
     A(s->ao, Mp * d * ts, true);
     A(s->hid, Mp * c.ffn * ts, true);
-    A(s->enc_t, Mp * d * ts, true);
     A(s->enc_f, (size_t)B * T * d * 4);
-    A(s->cross_kv, (size_t)c.n_layers * 2 * B * T * d * ks);
+    if (m->xattn) {  // X rows are written in place by the encoder's last LayerNorm: no chunk-sized operand buffer, no cross cache
+        A(s->enc_x, (size_t)B * T * d * 2);
+    } else {
+        A(s->enc_t, Mp * d * ts, true);
+        A(s->cross_kv, (size_t)c.n_layers * 2 * B * T * d * ks);
+    }
     A(s->self_kv, (size_t)c.n_layers * 2 * B * c.n_text_ctx * d * ks, true);
     // decode activations: rows for one token per utterance, or — prompt prefill — for up to PREFILL_MAX positions at once
     const size_t R = (size_t)B * wm_state::PREFILL_MAX;
@@ -827,7 +847,12 @@ static int state_new(wm_model* m, int B, wm_state** out, bool pair) {
     A(s->dq, R * d * 4);
     A(s->dattn, R * d * 4);
     A(s->dhid, R * c.ffn * 4);
-    A(s->part_o, R * s->nsplit * d * 4);
+    if (m->xattn) {
+        A(s->xq, R * 3 * c.n_heads * d * 2);
+        A(s->part_y, R * s->nsplit * c.n_heads * d * 4);
+    } else {
+        A(s->part_o, R * s->nsplit * d * 4);
+    }
     A(s->part_ml, R * s->nsplit * c.n_heads * 2 * 4);
     A(s->tok_rows, R * 4, true);
     A(s->pos_rows, R * 4, true);
@@ -955,6 +980,9 @@ static int run_encoder(wm_model* m, wm_state* s, const float* mel_dev, int B, hi
         const int opb = T == WM_F32 ? 4 : 2;
         bool xn_is_ln1 = false;  // xn holds LN1(x) of the coming block, written by the epilogue of the GEMM that produced x
         bool post_fused = false;  // enc_t was written by the last fc2's epilogue
+        // operand rows of ln_post: the chunk-sized enc_t that the cross-K/V projection consumes, or (m->xattn) this chunk's rows
+        // of the state's X, which the decoder's cross-attention streams itself
+        void* post_rows = m->xattn ? off_bytes(s->enc_x, (size_t)c0 * NT * d * 2) : s->enc_t.p;
         const float* mel_c = (mel2 && c0 >= split_at) ? mel2 + (size_t)(c0 - split_at) * c.n_mels * L : mel_dev + (size_t)c0 * c.n_mels * L;
         DISPATCH_DT(T, TT, launch_mel_transpose_pad<TT>(mel_c, s->mel_t.p, bc, c.n_mels, (int)L, m->Cp, st));
         {  // conv1 + GELU -> h1 rows 1..L (token-major)   whisper.mojo:73-75
@@ -1077,17 +1105,17 @@ static int run_encoder(wm_model* m, wm_state* s, const float* mel_dev, int B, hi
             } else if (fuse_out) {  // last block: ln_post (whisper.mojo:97-98) as operand rows for the cross-K/V projection
                 f2.lno_g = m->enc_ln_g.as<float>();
                 f2.lno_b = m->enc_ln_b.as<float>();
-                f2.lno_out = s->enc_t.p;
+                f2.lno_out = post_rows;
                 post_fused = true;
             }
             WMCHK(gemm_dispatch(T, WM_F32, f2, 1, st));
         }
         float* encf = s->enc_f.as<float>() + (size_t)c0 * NT * d;
         if (!post_fused)  // operand rows (and the fp32 copy) from the LayerNorm kernel
-            DISPATCH_DT(T, TT, launch_layernorm_rows<TT>(s->x.as<float>(), m->enc_ln_g.as<float>(), m->enc_ln_b.as<float>(), s->enc_t.p, want_f32 ? encf : nullptr, M, c.d_model, 1e-5f, st));
+            DISPATCH_DT(T, TT, launch_layernorm_rows<TT>(s->x.as<float>(), m->enc_ln_g.as<float>(), m->enc_ln_b.as<float>(), post_rows, want_f32 ? encf : nullptr, M, c.d_model, 1e-5f, st));
         else if (want_f32)  // the fp32 copy only
             DISPATCH_DT(T, TT, launch_layernorm_rows<TT>(s->x.as<float>(), m->enc_ln_g.as<float>(), m->enc_ln_b.as<float>(), nullptr, encf, M, c.d_model, 1e-5f, st));
-        WMCHK(cross_kv_chunk(m, s, c0, bc, st));
+        if (!m->xattn) WMCHK(cross_kv_chunk(m, s, c0, bc, st));
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -1131,6 +1159,10 @@ extern "C" int wm_state_set_encoder_output(wm_model* m, wm_state* s, const float
     HIPCHK(hipMemcpyAsync(s->enc_f.p, enc_out, (size_t)B * NT * d * 4, hipMemcpyHostToDevice, m->stream));
     for (int c0 = 0; c0 < B; c0 += s->Bc) {
         const int bc = std::min(s->Bc, B - c0);
+        if (m->xattn) {  // the cross-attention reads the bf16 rows themselves
+            launch_convert<bf16>(s->enc_f.as<float>() + (size_t)c0 * NT * d, off_bytes(s->enc_x, (size_t)c0 * NT * d * 2), (size_t)bc * NT * d, m->stream);
+            continue;
+        }
         DISPATCH_DT(m->cfg.compute_dtype, TT, launch_convert<TT>(s->enc_f.as<float>() + (size_t)c0 * NT * d, s->enc_t.p, (size_t)bc * NT * d, m->stream));
         WMCHK(cross_kv_chunk(m, s, c0, bc, m->stream));
     }
@@ -1159,7 +1191,43 @@ struct DecView {
 };
 static DecView whole_batch(wm_model* m, wm_state* s) { return DecView{0, s->B, m->stream, s->ctl.as<StepCtl>()}; }
 
+// m->xattn: the cross-attention of layer l over X for the rows of view v (P positions each): absorb + X sweep (launch_cross_attn),
+// then merge + V-apply into out (cross_attn_merge).  Rows are position-major as everywhere in decode_core.
+static XAttnParams xattn_params(wm_model* m, wm_state* s, int l, const DecView& v, int P) {
+    const wm_dims& c = m->cfg.dims;
+    const size_t d = c.d_model;
+    XAttnParams x{};
+    x.q = s->dq.as<float>() + (size_t)v.b0 * d;
+    x.Wk = off_bytes(m->cross_kv_w, (size_t)(2 * l) * d * d * 2);
+    x.Wv = off_bytes(m->cross_kv_w, (size_t)(2 * l + 1) * d * d * 2);
+    x.bv = m->cross_kv_b.as<float>() + (size_t)(2 * l + 1) * d;
+    x.X = off_bytes(s->enc_x, (size_t)v.b0 * c.n_audio_ctx * d * 2);
+    x.x_stride = (long)((size_t)c.n_audio_ctx * d);
+    x.n_keys = c.n_audio_ctx;
+    x.nsplit = s->nsplit;
+    x.H = c.n_heads;
+    x.d = c.d_model;
+    x.rows = v.nb * P;
+    x.q_B = P > 1 ? v.nb : 0;
+    x.scale = 1.0f / sqrtf(64.0f);
+    x.qs = off_bytes(s->xq, (size_t)v.b0 * 3 * c.n_heads * d * 2);
+    x.part_y = s->part_y.as<float>() + (size_t)v.b0 * s->nsplit * c.n_heads * d;
+    x.part_ml = s->part_ml.as<float>() + (size_t)v.b0 * s->nsplit * c.n_heads * 2;
+    return x;
+}
+static int cross_attn_merge(wm_model* m, wm_state* s, int l, const DecView& v, int P, void* out, int out_dtype) {
+    XAttnParams x = xattn_params(m, s, l, v, P);
+    x.out = out;
+    x.out_dtype = out_dtype;
+    return launch_rc(launch_xattn_merge(x, v.st));
+}
+
 static int launch_cross_attn(wm_model* m, wm_state* s, int l, const DecView& v, int P = 1) {
+    if (m->xattn) {
+        const XAttnParams x = xattn_params(m, s, l, v, P);
+        WMCHK(launch_rc(launch_xattn_absorb(x, v.st)));
+        return launch_rc(launch_xattn(x, v.st));
+    }
     const wm_dims& c = m->cfg.dims;
     const size_t d = c.d_model, ks = dt_size(m->cfg.kv_dtype);
     const size_t cross_l = (size_t)s->B * c.n_audio_ctx * d;
@@ -1296,7 +1364,10 @@ static int decode_core(wm_model* m, wm_state* s, const DecView& v, bool want_log
         WMCHK(launch_cross_attn(m, s, l, v, P));
         // (merging the chunk partials inside the projection's prologue was measured 14 us per layer SLOWER than this
         // 3 us launch: 96 workgroups each re-reading 295 KB of partials)
-        launch_attn_combine(s->part_o.as<float>() + (size_t)v.b0 * s->nsplit * d, s->part_ml.as<float>() + (size_t)v.b0 * s->nsplit * c.n_heads * 2,
+        if (m->xattn)
+            WMCHK(cross_attn_merge(m, s, l, v, P, dattn, T));
+        else
+            launch_attn_combine(s->part_o.as<float>() + (size_t)v.b0 * s->nsplit * d, s->part_ml.as<float>() + (size_t)v.b0 * s->nsplit * c.n_heads * 2,
                             dattn, T, B, s->nsplit, c.n_heads, c.d_model, st, (long long*)m->ts_buf.p, s->trace_id);
         WMCHK(proj_residual(dattn, c.d_model, w.co_w, w.co_b));
         {  // LN2 -> fc1 + GELU
@@ -2079,9 +2150,13 @@ extern "C" int wm_bench_bytes(wm_model* m, wm_state* s, int which, double* bytes
     const wm_dims& c = m->cfg.dims;
     const double d = c.d_model, H = c.n_heads, B = s->B;
     const double ks = dt_size(m->cfg.kv_dtype), ws = dt_size(dec_dtype(m->cfg));
+    // m->xattn: the cross-attention of one layer (absorb + sweep + merge, as wm_bench_kernel times it) reads X (bf16) once per
+    // utterance, Wk and Wv (bf16) once, q' (three bf16 images) per row (written and read), and writes / re-reads H·d partials per key chunk
+    const double x_layer = B * (double)c.n_audio_ctx * d * 2 + 2 * d * d * 2 + B * d * 4 + B * 3 * H * d * 2 * 2 +
+                           B * s->nsplit * (H * d + 2 * H) * 4 * 2 + B * d * ws;
     if (which == WM_KERNEL_CROSS_ATTN) {
         // one layer: K and V rows of every utterance once + q in + partials out
-        *bytes = B * 2.0 * c.n_audio_ctx * d * ks + B * d * 4 + B * s->nsplit * (d + 2 * H) * 4;
+        *bytes = m->xattn ? x_layer : B * 2.0 * c.n_audio_ctx * d * ks + B * d * 4 + B * s->nsplit * (d + 2 * H) * 4;
     } else if (which == WM_KERNEL_DECODE_STEP || which == WM_KERNEL_DECODE_STEP_SHARED) {
         // every weight once per step, KV once per utterance, KV write; logits are NOT materialised
         // (fused argmax: only B x ceil(V/128) (value, index) partials are written and re-read)
@@ -2090,6 +2165,8 @@ extern "C" int wm_bench_bytes(wm_model* m, wm_state* s, int which, double* bytes
         const double t = s->host_len > 0 ? s->host_len : BENCH_STEP_LEN;
         *bytes = ws * (L * (8 * d * d + 2 * f * d) + V * d) + 4 * (L * (p_blk - 8 * d * d - 2 * f * d) + 2 * d) +
                  B * L * 2 * d * ks * (c.n_audio_ctx + t) + B * L * 2 * d * ks + B * s->npart * 8.0 * 2 + B * 4;
+        if (m->xattn)  // X and the bf16 Wk / Wv in place of the cross K/V cache (and the decoder-dtype Wk / Wv counted above)
+            *bytes += L * (x_layer - B * 2.0 * c.n_audio_ctx * d * ks - 2 * d * d * ws);
     } else if (which == WM_KERNEL_ENCODER) {
         *bytes = 0;  // MFMA-bound: see wm_bench_flops in DESIGN.md
     } else {
@@ -2109,10 +2186,18 @@ extern "C" int wm_bench_kernel(wm_model* m, wm_state* s, int which, int reps, fl
     HIPCHK(hipEventCreate(&e1));
     const int L = m->cfg.dims.n_layers;
     if (which == WM_KERNEL_CROSS_ATTN) {
+        // m->xattn: absorb + X sweep + merge / V-apply, everything that replaces attn_decode + attn_combine (wm_bench_bytes prices
+        // the same three launches).  Every layer reads the SAME X (73.7 MB at B = 64), so after the first launch the stream is
+        // served from the 256 MB Infinity Cache — as it is inside a decode step, where the four layers re-read it.
         const DecView v = whole_batch(m, s);
-        for (int i = 0; i < L; ++i) WMCHK(launch_cross_attn(m, s, i, v));  // warm-up
+        const int TD = dec_dtype(m->cfg);
+        auto one = [&](int l) -> int {
+            WMCHK(launch_cross_attn(m, s, l, v));
+            return m->xattn ? cross_attn_merge(m, s, l, v, 1, s->dattn.p, TD) : 0;
+        };
+        for (int i = 0; i < L; ++i) WMCHK(one(i));  // warm-up
         HIPCHK(hipEventRecord(e0, st));
-        for (int i = 0; i < reps; ++i) WMCHK(launch_cross_attn(m, s, i % L, v));  // cycles the layers: 4 x 295 MB > 256 MB L3
+        for (int i = 0; i < reps; ++i) WMCHK(one(i % L));  // fp32 K/V: cycles the layers, 4 x 295 MB > 256 MB L3
         HIPCHK(hipEventRecord(e1, st));
     } else if (which == WM_KERNEL_DECODE_STEP || which == WM_KERNEL_DECODE_STEP_SHARED) {
         s->shares_chip = which == WM_KERNEL_DECODE_STEP_SHARED;  // the K/V stream as pipelined passes launch it

@@ -205,6 +205,30 @@ template <typename TKV> int launch_attn_decode(const AttnDecParams& p, hipStream
 void launch_attn_combine(const float* part_o, const float* part_ml, void* out, int out_dtype, int B, int nsplit, int H, int d,
                          hipStream_t st, long long* ts = nullptr, int ts_id = 0);
 
+// Cross-attention over the bf16 encoder output X with the K/V projections absorbed (bf16 encoder operands, fp32 K/V models):
+//   s_hj = (scale·q_h·Wk_h)·X_j      o_h = ((Σ_j p_hj X_j) / l_h)·Wv_hᵀ + bv_h
+// three launches: absorb (q' once per row, split into three bf16 images), the X sweep (un-normalised partials per key chunk),
+// merge + V-apply (writes the attention output in out_dtype).  d = 64·H, H <= 8.
+struct XAttnParams {
+    const float* q;      // [rows][d] cross-Q output (fp32, unscaled)
+    const void* Wk;      // [d][d] bf16, this layer's K projection (row = output feature h*64+e)
+    const void* Wv;      // [d][d] bf16
+    const float* bv;     // [d]
+    const void* X;       // [utterances][n_keys][d] bf16 encoder output (ln_post)
+    long x_stride;       // elements per utterance
+    int n_keys, nsplit, H, d, rows;
+    int q_B;             // > 0: prompt prefill, row r reads utterance r % q_B (position-major rows); else row = utterance
+    float scale;
+    void* qs;            // [rows][3][H][d] bf16: q' = hi + mid + lo
+    float* part_y;       // [rows][nsplit][H][d]
+    float* part_ml;      // [rows][nsplit][H][2]
+    void* out;           // [rows][d] in out_dtype
+    int out_dtype;
+};
+int launch_xattn_absorb(const XAttnParams& p, hipStream_t st);  // WM_LAUNCH_*
+int launch_xattn(const XAttnParams& p, hipStream_t st);
+int launch_xattn_merge(const XAttnParams& p, hipStream_t st);
+
 void launch_dec_embed(const float* tok_emb, const float* pos_emb, const int* tok, const int* pos, float* x, int B, int d,
                       hipStream_t st);
 // argmax over logits rows (lowest index wins) + greedy-loop bookkeeping
