@@ -157,6 +157,35 @@ int wm_transcribe_wait_device(wm_model* m, int slot, int32_t* dev_packed, int ro
  * the pass ran to its bound, less when the early exit cut it.  -1: no pass yet / bad slot.  Diagnostics and tests. */
 int wm_transcribe_steps(wm_model* m, int slot);
 
+/* ---- token-level timestamps ---------------------------------------------------------------------------------
+ * When each id was spoken, with the semantics of HF generate(..., return_token_timestamps=True)
+ * (WhisperGenerationMixin._extract_token_timestamps, time_precision 0.02, median_filter_width 7, num_input_ids = n_prompt): the
+ * cross-attention probabilities of a fixed set of alignment heads for the R = n_tokens[b] - n_prompt - 1 ids that were fed back,
+ * cropped to the first n_frames[b] / 2 encoder positions (no renormalisation), z-scored over the rows (population std), median-filtered
+ * (width 7, reflect) along the positions, averaged over the heads, then DTW against the positions.  token_times: host
+ * [B, n_prompt + 1 + max_loop] fp32 in the layout of tokens_out: 0 for the prompt, the R jump times, the last id repeats the last one
+ * (all 0 when R = 0).  Runs on the GPU after the greedy loop; a call without _tt enqueues exactly what it did before.
+ *
+ * wm_set_alignment_heads: (layer, head) pairs, HF generation_config.alignment_heads; at most 32, no duplicates; 0 pairs = off (the
+ * default).  A _tt call on a model without alignment heads returns WM_E_STATE; n_frames[b] outside [2, 2·n_audio_ctx] WM_E_ARG.
+ * n_frames NULL = the whole window.  The _tt submits pair under coalesce = 2 only with other _tt submits. */
+int wm_set_alignment_heads(wm_model* m, const int32_t* layer_head_pairs, int n_pairs);
+int wm_transcribe_tt(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* opts, const int32_t* n_frames,
+                     int32_t* tokens_out, int32_t* n_tokens, float* token_times);
+int wm_transcribe_submit_tt(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* opts,
+                            const int32_t* n_frames);
+/* WM_E_STATE when the slot's pass was submitted without timestamps */
+int wm_transcribe_wait_tt(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_times);
+/* n_frames[b] = min(2·n_audio_ctx, ceil(n_samples[b] / 160)): WhisperFeatureExtractor's attention mask */
+int wm_transcribe_pcm_tt(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* opts,
+                         int32_t* tokens_out, int32_t* n_tokens, float* token_times);
+/* Diagnostics / tests: the alignment heads' probabilities of the slot's last completed _tt pass (slot 0 = wm_transcribe_tt),
+ * out [B][n_sel][max_loop][n_audio_ctx] over ALL positions (before the crop); rows past R_b are 0.  WM_E_STATE once that pass's
+ * state has run another pass. */
+int wm_alignment_weights(wm_model* m, int slot, float* out);
+/* Known-answer test of the normalisation + DTW stage: weights [n_sel][R][F] -> times [n_prompt + R + 1].  R <= 447. */
+int wm_op_token_times(float* times, const float* weights, int n_sel, int R, int F, int n_prompt);
+
 /* ---- log-mel front end --------------------------------------------------------------------------
  * Replaces the reference's call to HF WhisperProcessor (export_weights.py:100-116): 16 kHz mono PCM -> pad / trim to the
  * 30 s window -> 400-point Hann STFT (hop 160, reflect padding) -> 80 slaney mel bands -> log10 -> clamp to max-8 ->

@@ -138,6 +138,26 @@ public:
         check(wm_transcribe_wait(model_, slot, toks.data(), n.data()));
         return unpack(toks, n, B, stride);
     }
+    // token-level timestamps (HF return_token_timestamps): (layer, head) alignment heads; none = off
+    void set_alignment_heads(const std::vector<std::pair<int, int>>& pairs) {
+        need_model();
+        std::vector<int32_t> flat;
+        for (const auto& [l, h] : pairs) flat.insert(flat.end(), {l, h});
+        check(wm_set_alignment_heads(model_, flat.data(), (int)pairs.size()));
+    }
+    // ids and, per id, the time it was spoken (seconds); n_frames: mel frames of real audio per utterance, empty = whole window
+    std::vector<std::vector<int>> transcribe_batch_tt(const float* mels, int B, std::vector<std::vector<float>>& times, int max_loop = MAX_LOOP,
+                                                      const std::vector<int32_t>& n_frames = {}) const {
+        need_model();
+        wm_decode_opts o = opts(max_loop, false);
+        const int stride = o.n_prompt + 1 + max_loop;
+        std::vector<int32_t> toks((size_t)B * stride), n(B);
+        std::vector<float> t((size_t)B * stride);
+        check(wm_transcribe_tt(model_, mels, 0, B, &o, n_frames.empty() ? nullptr : n_frames.data(), toks.data(), n.data(), t.data()));
+        times.assign(B, {});
+        for (int b = 0; b < B; ++b) times[b].assign(t.begin() + (size_t)b * stride, t.begin() + (size_t)b * stride + n[b]);
+        return unpack(toks, n, B, stride);
+    }
     // other prompts / stop ids (reduced test models have small vocabularies); defaults are the reference's
     void set_prompt(const std::vector<int32_t>& prompt, int32_t eot) {
         prompt_ = prompt;

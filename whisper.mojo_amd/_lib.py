@@ -19,6 +19,8 @@ SYMBOLS = [
     "wm_state_reset", "wm_state_free", "wm_state_len", "wm_encode", "wm_state_set_encoder_output", "wm_decode_step",
     "wm_transcribe", "wm_transcribe_submit", "wm_transcribe_wait", "wm_transcribe_wait_device", "wm_transcribe_steps", "wm_log_mel", "wm_transcribe_pcm", "wm_op_matmul_nt", "wm_op_ln_matmul_nt", "wm_op_mlp_block", "wm_op_attention", "wm_op_attention_cached", "wm_op_layer_norm", "wm_op_gelu", "wm_op_softmax_rows", "wm_op_conv1d_k3",
     "wm_op_argmax", "wm_bench_kernel", "wm_bench_bytes", "wm_synth_weights", "wm_synth_mel_host",
+    "wm_set_alignment_heads", "wm_transcribe_tt", "wm_transcribe_submit_tt", "wm_transcribe_wait_tt", "wm_transcribe_pcm_tt",
+    "wm_alignment_weights", "wm_op_token_times",
 ]
 
 ABI_VERSION = 4  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -82,6 +84,13 @@ def lib():
     L.wm_transcribe_wait_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
     L.wm_log_mel.argtypes = [vp, fp, ip, C.c_int, C.c_int, fp]
     L.wm_transcribe_pcm.argtypes = [vp, fp, ip, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip]
+    L.wm_set_alignment_heads.argtypes = [vp, ip, C.c_int]
+    L.wm_transcribe_tt.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip, ip, fp]
+    L.wm_transcribe_submit_tt.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip]
+    L.wm_transcribe_wait_tt.argtypes = [vp, C.c_int, ip, ip, fp]
+    L.wm_transcribe_pcm_tt.argtypes = [vp, fp, ip, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip, fp]
+    L.wm_alignment_weights.argtypes = [vp, C.c_int, fp]
+    L.wm_op_token_times.argtypes = [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int]
     L.wm_op_matmul_nt.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int]
     L.wm_op_mlp_block.argtypes = [fp] * 10 + [C.c_int] * 5
     L.wm_op_ln_matmul_nt.argtypes = [fp] * 6 + [C.c_int] * 5

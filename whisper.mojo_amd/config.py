@@ -20,6 +20,9 @@ DTYPE_NAMES = {DT_F32: "f32", DT_BF16: "bf16", DT_F16: "f16"}
 PROMPT = (50258, 50259, 50359, 50363)  # whisper.mojo:187-191
 EOT = 50257                            # whisper.mojo:206
 MAX_LOOP = 195                         # whisper.mojo:205
+# Alignment heads (layer, head) of the published openai/whisper-tiny checkpoint (its generation_config.alignment_heads), for
+# Whisper.set_alignment_heads.  Quoted, not verified: the checkpoint cannot be read offline here, and no test depends on this list.
+ALIGNMENT_HEADS_TINY = ((2, 2), (3, 0), (3, 2), (3, 3), (3, 4), (3, 5))
 
 
 class WmDims(ctypes.Structure):

@@ -141,6 +141,18 @@ struct DevBuf {
     template <typename T> T* as() const { return (T*)p; }
 };
 
+// scratch of an op-level entry point, released on return
+struct TmpDev {
+    std::vector<DevBuf> bufs;
+    ~TmpDev() {
+        for (auto& b : bufs) b.release();
+    }
+    DevBuf& add() {
+        bufs.emplace_back();
+        return bufs.back();
+    }
+};
+
 // host fp32 -> device buffer in dtype dt
 static int upload(DevBuf& b, const float* h, size_t n, int dt) {
     WMCHK(b.alloc(n * dt_size(dt)));
@@ -216,11 +228,14 @@ struct wm_model {
         const float* mel = nullptr;
         wm_decode_opts o{};
         std::vector<int32_t> prompt, sup, bsup;  // deep copies: the caller's option arrays need not outlive the call
+        bool tt = false;                          // token timestamps asked for; cols = columns kept per row
+        std::vector<int32_t> cols;
     } held;
     struct SlotRef {  // where a submitted slot's rows live
         bool pending = false;
         wm_state* st = nullptr;  // null while the slot is only held
         int row0 = 0, rows = 0, total = 0;
+        bool tt = false;
     } slot_ref[8];
     wm_state* pairs[4] = {};  // 2·B-row states of coalesced pairs
     int last_steps[8] = {-1, -1, -1, -1, -1, -1, -1, -1};  // loop iterations enqueued for each slot's last collected pass
@@ -231,6 +246,12 @@ struct wm_model {
     std::condition_variable pump_cv;
     std::vector<wm_state*> pump_work;  // passes whose loop is not fully enqueued yet
     bool pump_quit = false;
+    // token-level timestamps: HF generation_config.alignment_heads, (layer, head) pairs in the caller's order; empty = off
+    std::vector<int32_t> align_pairs;
+    struct AlignRef {  // where a slot's last timestamp pass left its alignment weights (wm_alignment_weights)
+        wm_state* st = nullptr;
+        int row0 = 0, rows = 0, gen = 0;
+    } align_ref[8];
 };
 
 struct wm_state {
@@ -297,6 +318,21 @@ struct wm_state {
     int no_ts_cached = -1;
     DevBuf dx, dq, dattn, dhid, part_o, part_ml, logits, amax_val, amax_idx, tok, pos, tok_rows, pos_rows, ctl, out_tokens, n_tokens, finished;
     int npart = 0;  // fused-argmax partials per utterance = workgroups per row block of the logits kernel
+    // token-level timestamps of the pending pass (on = asked for): the loop's cross-q launches of the alignment layers also store the
+    // selected heads' query rows (cap), the post-loop kernels (kernels_align.hip) turn them into times.  Buffers grow on demand.
+    struct Align {
+        bool on = false;
+        int L = 0, n_prompt = 0, gen = 0;         // rows per utterance (= max_loop), prompt length, pass counter
+        std::vector<int32_t> pairs;               // (layer, head) pairs of the pass
+        std::vector<int32_t> cols;                // [B] columns kept per utterance (n_frames // 2, or n_audio_ctx)
+        DevBuf cap, kh, probs, mean, stdv, M, trace, times, ncols;
+    } al;
+    struct CapKey {  // the capture baked into the captured step graph
+        const void* cap = nullptr;
+        int L = 0, n_prompt = 0;
+        std::vector<int32_t> pairs;
+        bool operator!=(const CapKey& o) const { return cap != o.cap || L != o.L || n_prompt != o.n_prompt || pairs != o.pairs; }
+    } graph_cap;
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -750,6 +786,8 @@ extern "C" void wm_state_free(wm_state* s) {
         if (pr == s) pr = nullptr;
     for (auto& r : s->m->slot_ref)
         if (r.st == s) r = wm_model::SlotRef{};
+    for (auto& r : s->m->align_ref)
+        if (r.st == s) r = wm_model::AlignRef{};
     (void)hipSetDevice(s->m->device);
     // nothing of this state may still be running when its graphs, streams and arenas go away (a submitted pass that was
     // never waited for, or the model stream's last wm_decode_step)
@@ -768,7 +806,8 @@ extern "C" void wm_state_free(wm_state* s) {
     if (s->h_prog) (void)hipHostFree((void*)s->h_prog);
     DevBuf* bs[] = {&s->mel_dev, &s->mel_t, &s->h1, &s->x, &s->xn, &s->qkv, &s->ao, &s->hid, &s->enc_t, &s->enc_f,
                     &s->cross_kv, &s->enc_x, &s->xq, &s->part_y, &s->self_kv, &s->dx, &s->dq, &s->dattn, &s->dhid, &s->part_o, &s->part_ml, &s->logits, &s->amax_val, &s->amax_idx, &s->ts_state, &s->ts_val, &s->ts_idx, &s->ts_m, &s->ts_s, &s->mask_steady, &s->mask_begin,
-                    &s->tok, &s->pos, &s->tok_rows, &s->pos_rows, &s->ctl, &s->out_tokens, &s->n_tokens, &s->finished};
+                    &s->tok, &s->pos, &s->tok_rows, &s->pos_rows, &s->ctl, &s->out_tokens, &s->n_tokens, &s->finished,
+                    &s->al.cap, &s->al.kh, &s->al.probs, &s->al.mean, &s->al.stdv, &s->al.M, &s->al.trace, &s->al.times, &s->al.ncols};
     for (DevBuf* b : bs) b->release();
     delete s;
 }
@@ -1265,7 +1304,7 @@ static int launch_cross_attn(wm_model* m, wm_state* s, int l, const DecView& v, 
 // self-attention of position t sees keys 0..len+t (the causal mask of layers.mojo:309-318), logits only for the last
 // position.  Every row's arithmetic is what the single-position pass does for it, so the ids are the same bit for bit.
 static int decode_core(wm_model* m, wm_state* s, const DecView& v, bool want_logits, bool full_logits = false,
-                       const float* mask = nullptr, int P = 1, bool embed = true, const TsRules* rules = nullptr) {
+                       const float* mask = nullptr, int P = 1, bool embed = true, const TsRules* rules = nullptr, bool capture = false) {
     const wm_dims& c = m->cfg.dims;
     const int T = dec_dtype(m->cfg), KV = m->cfg.kv_dtype;  // T: the decoder's operand dtype
     const int B = v.nb * P;          // activation rows of this pass
@@ -1359,6 +1398,24 @@ static int decode_core(wm_model* m, wm_state* s, const DecView& v, bool want_log
             p.bias = w.cq_b.as<float>();
             p.out = dq;
             p.ldo = c.d_model;
+            if (capture && s->al.on) {  // token timestamps: this step's query rows of the alignment heads of layer l
+                bool any = false;
+                for (int h = 0; h < 32; ++h) p.cap_sel[h] = -1;
+                const int n_sel = (int)s->al.pairs.size() / 2;
+                for (int k = 0; k < n_sel; ++k)
+                    if (s->al.pairs[2 * k] == l) {
+                        p.cap_sel[s->al.pairs[2 * k + 1]] = (signed char)k;
+                        any = true;
+                    }
+                if (any) {
+                    p.cap_row_stride = (long)s->al.L * n_sel * 64;
+                    p.cap = s->al.cap.as<float>() + (size_t)v.b0 * p.cap_row_stride;
+                    p.cap_step0 = s->al.n_prompt;
+                    p.cap_steps = s->al.L;
+                    p.cap_nsel = n_sel;
+                    p.ctl = ctl;
+                }
+            }
             WMCHK(dec_linear_dispatch(T, p, st));
         }
         WMCHK(launch_cross_attn(m, s, l, v, P));
@@ -1538,7 +1595,7 @@ static int enqueue_loop_steps(wm_model* m, wm_state* s, int n) {
                 if (e != hipSuccess) return fail(WM_E_HIP, "hipGraphLaunch: %s", hipGetErrorString(e));
             } else {
                 const DecView v{ln.b0, ln.nb, ln.st, ln.ctl};
-                WMCHK(decode_core(m, s, v, true, false, s->mask_steady.as<float>(), 1, false, rp));
+                WMCHK(decode_core(m, s, v, true, false, s->mask_steady.as<float>(), 1, false, rp, true));
                 launch_argmax_step(argmax_params(m, s, v, true, s->loop_opts.eot, s->loop_opts.ignore_eot, true, true, rp), v.st);
             }
         }
@@ -1546,9 +1603,17 @@ static int enqueue_loop_steps(wm_model* m, wm_state* s, int n) {
     return 0;
 }
 // the pending pass is fully enqueued: its completion events go behind the last step
+static int enqueue_align(wm_model* m, wm_state* s);
 static int finish_enqueue(wm_model* m, wm_state* s) {
-    (void)m;
     int rc = 0;
+    if (s->al.on) {  // token timestamps: the post-loop kernels go behind the last step, before the pass's completion events
+        for (size_t i = 1; i < s->lanes.size() && !rc; ++i) {
+            hipError_t e = hipEventRecord(s->lanes[i].done, s->lanes[i].st);
+            if (e == hipSuccess) e = hipStreamWaitEvent(s->lanes[0].st, s->lanes[i].done, 0);
+            if (e != hipSuccess) rc = fail(WM_E_HIP, "align wait: %s", hipGetErrorString(e));
+        }
+        if (!rc) rc = enqueue_align(m, s);
+    }
     for (auto& ln : s->lanes) {
         trace_mark(ln.st, "state %p lane %d decode end", (void*)s, ln.b0);
         const hipError_t e = hipEventRecord(ln.done, ln.st);
@@ -1635,8 +1700,10 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
     const TsRules* rp = rules.tb > 0 ? &rules : nullptr;
     const int no_ts = rp ? o->no_timestamps_token : -1;
     s->shares_chip = !allow_poll;  // the pipelined entry (wm_transcribe_submit): other passes are, or will be, in flight
+    wm_state::CapKey cap_key;
+    if (s->al.on) cap_key = wm_state::CapKey{s->al.cap.p, s->al.L, s->al.n_prompt, s->al.pairs};
     const bool recapture = !s->graphs_valid || s->graph_eot != o->eot || s->graph_ignore != o->ignore_eot ||
-                           s->graph_shares != s->shares_chip || memcmp(&s->graph_rules, &rules, sizeof rules) != 0;
+                           s->graph_shares != s->shares_chip || memcmp(&s->graph_rules, &rules, sizeof rules) != 0 || s->graph_cap != cap_key;
     const int first_pos = o->pos_mode == WM_POS_REF ? o->n_prompt - 1 : o->n_prompt;
     // logit masks (§8f rank 4): rebuilt only when the id lists change; always passed (all-zero = the reference's raw argmax)
     {
@@ -1702,7 +1769,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
             }
             hipGraph_t g = nullptr;
             HIPCHK(hipStreamBeginCapture(v.st, hipStreamCaptureModeThreadLocal));
-            const int crc = decode_core(m, s, v, true, false, s->mask_steady.as<float>(), 1, false, rp);
+            const int crc = decode_core(m, s, v, true, false, s->mask_steady.as<float>(), 1, false, rp, true);
             launch_argmax_step(argmax_params(m, s, v, true, o->eot, o->ignore_eot, true, true, rp), v.st);
             const hipError_t cap = hipStreamEndCapture(v.st, &g);  // always closed, also when a launcher refused
             if (crc) {
@@ -1721,6 +1788,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
     s->graph_ignore = o->ignore_eot;
     s->graph_rules = rules;
     s->graph_shares = s->shares_chip;
+    s->graph_cap = cap_key;
     if (trace_phase) {
         for (auto& ln : s->lanes) (void)hipStreamSynchronize(ln.st);
         fprintf(stderr, "[wm] encoder wait + prefill (+graph capture if any): %.3f ms\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count() * 1e3);
@@ -1782,8 +1850,10 @@ static int check_opts(wm_model* m, const wm_decode_opts* o, int B) {
 
 // Enqueues one whole pass (encoder, prefill, greedy loop) for B utterances on state *slot (created / re-created on demand).
 // mel2 != null: a coalesced pair — *slot is a 2·(B/2)-row pair state, utterances [B/2, B) come from mel2.
+static int align_setup(wm_model* m, wm_state* s, const wm_decode_opts* o, const std::vector<int32_t>* cols);
+// cols != null: token timestamps for this pass, cols[b] = columns kept for row b (n_frames[b] // 2, or n_audio_ctx)
 static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, bool allow_poll,
-                     const float* mel2 = nullptr, int mel2_on_device = 0) {
+                     const float* mel2 = nullptr, int mel2_on_device = 0, const std::vector<int32_t>* cols = nullptr) {
     const wm_dims& c = m->cfg.dims;
     HIPCHK(hipSetDevice(m->device));
     const bool pair = mel2 != nullptr;
@@ -1835,6 +1905,7 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
         fprintf(stderr, "[wm] encoder: enqueue %.3f ms, done after %.3f ms\n", std::chrono::duration<double>(tt1 - tt0).count() * 1e3,
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - tt0).count() * 1e3);
     }
+    WMCHK(align_setup(m, s, o, cols));
     WMCHK(transcribe_decode(m, s, o, allow_poll));
     s->pending = true;
     s->synced = false;
@@ -1847,7 +1918,7 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
 // Blocks until the state's pending pass is complete, then copies `rows` utterances starting at row0 out.  The pass stays pending
 // until every slot that shares the state (one, or the two of a coalesced pair) has collected its rows.
 static int wait_on(wm_model* m, wm_state* s, int32_t* tokens_out, int32_t* n_tokens, int row0 = 0, int rows = -1, int32_t* dev_packed = nullptr,
-                   int rows_cap = 0, int pack_stride = 0) {
+                   int rows_cap = 0, int pack_stride = 0, float* token_times = nullptr) {
     if (!s || !s->pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
     HIPCHK(hipSetDevice(m->device));
     if (rows < 0) rows = s->B;
@@ -1874,6 +1945,9 @@ static int wait_on(wm_model* m, wm_state* s, int32_t* tokens_out, int32_t* n_tok
         HIPCHK(hipMemcpy2D(tokens_out, (size_t)total * 4, s->out_tokens.as<int>() + (size_t)row0 * s->out_stride, (size_t)s->out_stride * 4, (size_t)total * 4, rows,
                            hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(n_tokens, s->n_tokens.as<int>() + row0, (size_t)rows * 4, hipMemcpyDeviceToHost));
+        if (token_times)
+            HIPCHK(hipMemcpy2D(token_times, (size_t)total * 4, s->al.times.as<float>() + (size_t)row0 * s->out_stride, (size_t)s->out_stride * 4,
+                               (size_t)total * 4, rows, hipMemcpyDeviceToHost));
     }
     if (--s->halves_left <= 0) {
         s->pending = false;
@@ -1895,8 +1969,10 @@ static bool same_opts(const wm_model::Held& h, const wm_decode_opts* o) {
     return std::equal(h.prompt.begin(), h.prompt.end(), o->prompt) && std::equal(h.sup.begin(), h.sup.end(), o->suppress_tokens) &&
            std::equal(h.bsup.begin(), h.bsup.end(), o->begin_suppress_tokens);
 }
-static void hold(wm_model* m, int slot, const float* mel, int on_dev, int B, const wm_decode_opts* o) {
+static void hold(wm_model* m, int slot, const float* mel, int on_dev, int B, const wm_decode_opts* o, const std::vector<int32_t>* cols) {
     wm_model::Held& h = m->held;
+    h.tt = cols != nullptr;
+    h.cols = cols ? *cols : std::vector<int32_t>();
     h.active = true;
     h.slot = slot;
     h.B = B;
@@ -1911,7 +1987,7 @@ static void hold(wm_model* m, int slot, const float* mel, int on_dev, int B, con
     h.o.n_suppress = (int)h.sup.size();
     h.o.begin_suppress_tokens = h.bsup.empty() ? nullptr : h.bsup.data();
     h.o.n_begin_suppress = (int)h.bsup.size();
-    m->slot_ref[slot] = wm_model::SlotRef{true, nullptr, 0, B, o->n_prompt + 1 + o->max_loop};
+    m->slot_ref[slot] = wm_model::SlotRef{true, nullptr, 0, B, o->n_prompt + 1 + o->max_loop, h.tt};
 }
 // the held submit runs alone, on its own slot's state (no partner came, or the partner did not match)
 static int flush_held(wm_model* m) {
@@ -1919,7 +1995,7 @@ static int flush_held(wm_model* m) {
     if (!h.active) return 0;
     h.active = false;
     wm_model::SlotRef& r = m->slot_ref[h.slot];
-    const int rc = submit_on(m, slot_state(m, h.slot), h.mel, h.on_dev, h.B, &h.o, false);
+    const int rc = submit_on(m, slot_state(m, h.slot), h.mel, h.on_dev, h.B, &h.o, false, nullptr, 0, h.tt ? &h.cols : nullptr);
     if (rc) {
         r = wm_model::SlotRef{};
         return rc;
@@ -1929,28 +2005,56 @@ static int flush_held(wm_model* m) {
     return 0;
 }
 
+// n_frames -> columns kept per row (HF crops the attentions to n_frames // 2 encoder positions); null = every column
+static int align_cols(wm_model* m, const int32_t* n_frames, int B, std::vector<int32_t>& cols) {
+    const int T = m->cfg.dims.n_audio_ctx;
+    if (m->align_pairs.empty()) return fail(WM_E_STATE, "token timestamps need alignment heads (wm_set_alignment_heads)");
+    cols.assign(B, T);
+    if (n_frames)
+        for (int b = 0; b < B; ++b) {
+            if (n_frames[b] < 2 || n_frames[b] > 2 * T)
+                return fail(WM_E_ARG, "n_frames[%d] = %d: must lie in [2, %d] (mel frames of real audio)", b, n_frames[b], 2 * T);
+            cols[b] = n_frames[b] / 2;
+        }
+    return 0;
+}
+
+static int transcribe_impl(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const std::vector<int32_t>* cols,
+                           int32_t* tokens_out, int32_t* n_tokens, float* token_times) {
+    WMCHK(flush_held(m));  // a held submit goes first: this call may use its mel buffers' stream order, and slot 0
+    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, o, true, nullptr, 0, cols));
+    WMCHK(wait_on(m, m->cached, tokens_out, n_tokens, 0, -1, nullptr, 0, 0, token_times));
+    m->last_steps[0] = m->cached->last_steps;
+    m->align_ref[0] = cols ? wm_model::AlignRef{m->cached, 0, B, m->cached->al.gen} : wm_model::AlignRef{};
+    return 0;
+}
+
 extern "C" int wm_transcribe(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* o,
                              int32_t* tokens_out, int32_t* n_tokens) {
     if (!m || !mel || !tokens_out || !n_tokens) return fail(WM_E_ARG, "bad argument");
     WMCHK(check_opts(m, o, B));
-    WMCHK(flush_held(m));  // a held submit goes first: this call may use its mel buffers' stream order, and slot 0
-    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, o, true));
-    WMCHK(wait_on(m, m->cached, tokens_out, n_tokens));
-    m->last_steps[0] = m->cached->last_steps;
-    return 0;
+    return transcribe_impl(m, mel, mel_on_device, B, o, nullptr, tokens_out, n_tokens, nullptr);
+}
+
+extern "C" int wm_transcribe_tt(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const int32_t* n_frames,
+                                int32_t* tokens_out, int32_t* n_tokens, float* token_times) {
+    if (!m || !mel || !tokens_out || !n_tokens || !token_times) return fail(WM_E_ARG, "bad argument");
+    WMCHK(check_opts(m, o, B));
+    std::vector<int32_t> cols;
+    WMCHK(align_cols(m, n_frames, B, cols));
+    return transcribe_impl(m, mel, mel_on_device, B, o, &cols, tokens_out, n_tokens, token_times);
 }
 
 // Pipelined form of Whisper.transcribe for back-to-back batches: submit enqueues the encoder and the greedy loop on the slot's
 // stream and returns; wait blocks until that slot's tokens are ready.
-extern "C" int wm_transcribe_submit(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o) {
-    if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
-    WMCHK(check_opts(m, o, B));
+static int submit_impl(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const std::vector<int32_t>* cols) {
     wm_model::SlotRef& r = m->slot_ref[slot];
     if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
     const int total = o->n_prompt + 1 + o->max_loop;
+    const bool tt = cols != nullptr;
     const bool can_pair = m->cfg.coalesce == 2 && B <= m->cfg.max_batch && (B <= m->enc_chunk || B % m->enc_chunk == 0);
-    if (can_pair && m->held.active && m->held.B == B && same_opts(m->held, o)) {
+    if (can_pair && m->held.active && m->held.B == B && m->held.tt == tt && same_opts(m->held, o)) {
         // the partner of the held submit: both batches go out as ONE pass on a 2·B-row state
         wm_state** ps = nullptr;
         for (auto& pr : m->pairs)
@@ -1963,40 +2067,230 @@ extern "C" int wm_transcribe_submit(wm_model* m, int slot, const float* mel, int
             wm_model::Held& h = m->held;
             h.active = false;
             wm_model::SlotRef& r0 = m->slot_ref[h.slot];
-            const int rc = submit_on(m, ps, h.mel, h.on_dev, 2 * B, &h.o, false, mel, mel_on_device);
+            std::vector<int32_t> pair_cols;
+            if (tt) {  // rows [0, B) are the held batch's, [B, 2B) this one's
+                pair_cols = h.cols;
+                pair_cols.insert(pair_cols.end(), cols->begin(), cols->end());
+            }
+            const int rc = submit_on(m, ps, h.mel, h.on_dev, 2 * B, &h.o, false, mel, mel_on_device, tt ? &pair_cols : nullptr);
             if (rc) {
                 r0 = wm_model::SlotRef{};
                 return rc;
             }
             r0.st = *ps;
             r0.row0 = 0;
-            r = wm_model::SlotRef{true, *ps, B, B, total};
+            r = wm_model::SlotRef{true, *ps, B, B, total, tt};
             return 0;
         }
     }
     WMCHK(flush_held(m));
     if (can_pair) {  // wait for a partner (or for this slot's wm_transcribe_wait)
-        hold(m, slot, mel, mel_on_device, B, o);
+        hold(m, slot, mel, mel_on_device, B, o, cols);
         return 0;
     }
-    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, o, false));
-    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, total};
+    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, o, false, nullptr, 0, cols));
+    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, total, tt};
     return 0;
 }
-extern "C" int wm_transcribe_wait(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens) {
-    if (!m || !tokens_out || !n_tokens || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
+extern "C" int wm_transcribe_submit(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o) {
+    if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
+    WMCHK(check_opts(m, o, B));
+    return submit_impl(m, slot, mel, mel_on_device, B, o, nullptr);
+}
+extern "C" int wm_transcribe_submit_tt(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o,
+                                       const int32_t* n_frames) {
+    if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
+    WMCHK(check_opts(m, o, B));
+    std::vector<int32_t> cols;
+    WMCHK(align_cols(m, n_frames, B, cols));
+    return submit_impl(m, slot, mel, mel_on_device, B, o, &cols);
+}
+static int wait_impl(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_times) {
     wm_model::SlotRef& r = m->slot_ref[slot];
     if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
+    if (token_times && !r.tt) return fail(WM_E_STATE, "this slot's pass was submitted without token timestamps (wm_transcribe_submit_tt)");
     if (m->held.active && m->held.slot == slot) {  // no partner came: the held batch runs alone now
         const int rc = flush_held(m);
         if (rc) return rc;
     }
     wm_state* s = r.st;
-    const int rc = wait_on(m, s, tokens_out, n_tokens, r.row0, r.rows);
-    if (!rc) m->last_steps[slot] = s->last_steps;
+    const int rc = wait_on(m, s, tokens_out, n_tokens, r.row0, r.rows, nullptr, 0, 0, token_times);
+    if (!rc) {
+        m->last_steps[slot] = s->last_steps;
+        m->align_ref[slot] = r.tt ? wm_model::AlignRef{s, r.row0, r.rows, s->al.gen} : wm_model::AlignRef{};
+    }
     r = wm_model::SlotRef{};
     return rc;
 }
+extern "C" int wm_transcribe_wait(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens) {
+    if (!m || !tokens_out || !n_tokens || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
+    return wait_impl(m, slot, tokens_out, n_tokens, nullptr);
+}
+extern "C" int wm_transcribe_wait_tt(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_times) {
+    if (!m || !tokens_out || !n_tokens || !token_times || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
+    return wait_impl(m, slot, tokens_out, n_tokens, token_times);
+}
+// ---- token-level timestamps ------------------------------------------------------------------------------------
+extern "C" int wm_set_alignment_heads(wm_model* m, const int32_t* layer_head_pairs, int n_pairs) {
+    if (!m || n_pairs < 0 || (n_pairs > 0 && !layer_head_pairs)) return fail(WM_E_ARG, "bad argument");
+    if (n_pairs > ALIGN_MAX_HEADS) return fail(WM_E_ARG, "at most %d alignment heads (got %d)", ALIGN_MAX_HEADS, n_pairs);
+    const wm_dims& c = m->cfg.dims;
+    std::vector<int32_t> pairs(layer_head_pairs, layer_head_pairs + 2 * n_pairs);
+    for (int k = 0; k < n_pairs; ++k) {
+        const int l = pairs[2 * k], h = pairs[2 * k + 1];
+        if (l < 0 || l >= c.n_layers || h < 0 || h >= c.n_heads || h >= 32)
+            return fail(WM_E_ARG, "alignment head %d = (%d, %d) outside %d layers x %d heads", k, l, h, c.n_layers, c.n_heads);
+        for (int q = 0; q < k; ++q)
+            if (pairs[2 * q] == l && pairs[2 * q + 1] == h) return fail(WM_E_ARG, "alignment head (%d, %d) listed twice", l, h);
+    }
+    m->align_pairs = pairs;
+    return 0;
+}
+
+static int grow(DevBuf& b, size_t bytes) { return b.p && b.bytes >= bytes ? 0 : b.alloc(bytes); }
+
+// Before the pass's graphs are (re)captured: size the timestamp buffers of state s and record what the pass asked for.
+static int align_setup(wm_model* m, wm_state* s, const wm_decode_opts* o, const std::vector<int32_t>* cols) {
+    wm_state::Align& a = s->al;
+    a.on = cols != nullptr;
+    if (!a.on) return 0;
+    const wm_dims& c = m->cfg.dims;
+    const size_t B = s->B, T = c.n_audio_ctx, L = o->max_loop;
+    a.pairs = m->align_pairs;
+    const size_t n_sel = a.pairs.size() / 2;
+    a.L = o->max_loop;
+    a.n_prompt = o->n_prompt;
+    a.cols = *cols;
+    ++a.gen;
+    const size_t Lr = std::max<size_t>(L, 1);
+    WMCHK(grow(a.cap, B * Lr * n_sel * 64 * 4));
+    if (m->xattn) WMCHK(grow(a.kh, B * n_sel * T * 64 * 4));
+    WMCHK(grow(a.probs, B * n_sel * Lr * T * 4));
+    WMCHK(grow(a.mean, B * n_sel * T * 4));
+    WMCHK(grow(a.stdv, B * n_sel * T * 4));
+    WMCHK(grow(a.M, B * Lr * T * 4));
+    if (align_dtw_lds_bytes((int)Lr, (int)T) == 0) WMCHK(grow(a.trace, B * Lr * ((T + 15) / 16) * 4));
+    WMCHK(grow(a.times, B * s->out_stride * 4));
+    WMCHK(grow(a.ncols, B * 4));
+    // (a.cols outlives the copy: the state is not reused before this pass is waited for)
+    HIPCHK(hipMemcpyAsync(a.ncols.p, a.cols.data(), B * 4, hipMemcpyHostToDevice, s->lanes[0].st));
+    return 0;
+}
+
+static AlignParams align_params(wm_model* m, wm_state* s) {
+    const wm_dims& c = m->cfg.dims;
+    const wm_state::Align& a = s->al;
+    AlignParams p{};
+    p.cap = a.cap.as<float>();
+    p.B = s->B;
+    p.L = a.L;
+    p.n_sel = (int)a.pairs.size() / 2;
+    p.n_prompt = a.n_prompt;
+    p.T = c.n_audio_ctx;
+    p.d = c.d_model;
+    p.n_tokens = s->n_tokens.as<int>();
+    p.n_frames = a.ncols.as<int>();
+    if (m->xattn) {
+        p.X = s->enc_x.p;
+        p.Wk = m->cross_kv_w.p;
+        p.kh = a.kh.as<float>();
+    } else {
+        p.kv = s->cross_kv.p;
+        p.kv_dtype = m->cfg.kv_dtype;
+        p.kv_layer_stride = (long)((size_t)s->B * c.n_audio_ctx * c.d_model);
+    }
+    for (int k = 0; k < p.n_sel; ++k) {
+        p.layer[k] = a.pairs[2 * k];
+        p.head[k] = a.pairs[2 * k + 1];
+    }
+    p.probs = a.probs.as<float>();
+    p.mean = a.mean.as<float>();
+    p.stdv = a.stdv.as<float>();
+    p.M = a.M.as<float>();
+    p.trace = align_dtw_lds_bytes(a.L, c.n_audio_ctx) ? nullptr : a.trace.as<unsigned>();
+    p.times = a.times.as<float>();
+    p.out_stride = s->out_stride;
+    return p;
+}
+
+// the post-loop kernels of a timestamp pass, on lane 0's stream behind the last step
+static int enqueue_align(wm_model* m, wm_state* s) {
+    hipStream_t st = s->lanes[0].st;
+    if (s->al.L == 0) {  // max_loop 0: no row ever, every time is 0 (HF's early return)
+        HIPCHK(hipMemsetAsync(s->al.times.p, 0, (size_t)s->B * s->out_stride * 4, st));
+        return 0;
+    }
+    const AlignParams p = align_params(m, s);
+    LCHK(launch_align_probs(p, st));
+    LCHK(launch_align_norm(p, st));
+    LCHK(launch_align_dtw(p, st));
+    return 0;
+}
+
+extern "C" int wm_transcribe_pcm_tt(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o,
+                                    int32_t* tokens_out, int32_t* n_tokens, float* token_times);
+
+extern "C" int wm_alignment_weights(wm_model* m, int slot, float* out) {
+    if (!m || !out || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
+    const wm_model::AlignRef& r = m->align_ref[slot];
+    if (!r.st || !state_is_live(r.st) || r.st->al.gen != r.gen || r.st->pending)
+        return fail(WM_E_STATE, "no completed timestamp pass on this slot (or its state has run another pass since)");
+    wm_state* s = r.st;
+    const size_t T = m->cfg.dims.n_audio_ctx, L = s->al.L, n_sel = s->al.pairs.size() / 2;
+    HIPCHK(hipSetDevice(m->device));
+    const size_t per_row = n_sel * L * T;
+    HIPCHK(hipMemcpy(out, s->al.probs.as<float>() + (size_t)r.row0 * per_row, (size_t)r.rows * per_row * 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> n(r.rows);
+    HIPCHK(hipMemcpy(n.data(), s->n_tokens.as<int>() + r.row0, (size_t)r.rows * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < r.rows; ++b) {  // rows past R_b were never computed
+        const size_t R = (size_t)std::max(0, std::min<int>((int)L, n[b] - s->al.n_prompt - 1));
+        for (size_t k = 0; k < n_sel; ++k) std::fill(out + b * per_row + (k * L + R) * T, out + b * per_row + (k + 1) * L * T, 0.f);
+    }
+    return 0;
+}
+
+extern "C" int wm_op_token_times(float* times, const float* weights, int n_sel, int R, int F, int n_prompt) {
+    if (!times || n_sel <= 0 || n_sel > ALIGN_MAX_HEADS || R < 0 || R > ALIGN_MAX_ROWS || F <= 0 || n_prompt < 0 || (R > 0 && !weights))
+        return fail(WM_E_ARG, "bad argument (1 <= n_sel <= %d, 0 <= R <= %d, F >= 1)", ALIGN_MAX_HEADS, ALIGN_MAX_ROWS);
+    const int total = n_prompt + R + 1;
+    if (R == 0) {
+        std::fill(times, times + total, 0.f);
+        return 0;
+    }
+    TmpDev t;
+    t.bufs.reserve(8);
+    DevBuf &probs = t.add(), &mean = t.add(), &sd = t.add(), &M = t.add(), &tr = t.add(), &tm = t.add(), &nt = t.add();
+    WMCHK(upload(probs, weights, (size_t)n_sel * R * F, WM_F32));
+    WMCHK(mean.alloc((size_t)n_sel * F * 4));
+    WMCHK(sd.alloc((size_t)n_sel * F * 4));
+    WMCHK(M.alloc((size_t)R * F * 4));
+    WMCHK(tm.alloc((size_t)total * 4));
+    WMCHK(nt.alloc(4));
+    HIPCHK(hipMemcpy(nt.p, &total, 4, hipMemcpyHostToDevice));
+    AlignParams p{};
+    p.B = 1;
+    p.L = R;
+    p.n_sel = n_sel;
+    p.n_prompt = n_prompt;
+    p.T = F;
+    p.n_tokens = nt.as<int>();
+    p.probs = probs.as<float>();
+    p.mean = mean.as<float>();
+    p.stdv = sd.as<float>();
+    p.M = M.as<float>();
+    if (align_dtw_lds_bytes(R, F) == 0) {
+        WMCHK(tr.alloc((size_t)R * ((F + 15) / 16) * 4));
+        p.trace = tr.as<unsigned>();
+    }
+    p.times = tm.as<float>();
+    p.out_stride = total;
+    LCHK(launch_align_norm(p, nullptr));
+    LCHK(launch_align_dtw(p, nullptr));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(times, tm.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // wm_transcribe_wait with the result left ON THE DEVICE as the gather buffer of the multi-GPU path: dev_packed
 // [rows_cap, 1 + stride] int32 in the caller's device memory (e.g. a torch tensor), row r = [length, ids zero-padded]; rows past the
 // batch are zeroed.  stride >= n_prompt + 1 + max_loop of the pass.
@@ -2138,6 +2432,19 @@ extern "C" int wm_transcribe_pcm(wm_model* m, const float* pcm, const int32_t* n
     WMCHK(wait_on(m, m->cached, tokens_out, n_tokens));
     m->last_steps[0] = m->cached->last_steps;
     return 0;
+}
+
+// n_frames[b] = min(2·n_audio_ctx, ceil(n_samples[b] / 160)): the attention mask of WhisperFeatureExtractor
+extern "C" int wm_transcribe_pcm_tt(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o,
+                                    int32_t* tokens_out, int32_t* n_tokens, float* token_times) {
+    if (!m || !tokens_out || !n_tokens || !token_times || !n_samples || B <= 0) return fail(WM_E_ARG, "bad argument");
+    WMCHK(check_opts(m, o, B));
+    std::vector<int32_t> nf(B);
+    for (int b = 0; b < B; ++b) nf[b] = (int32_t)std::min<long>(2L * m->cfg.dims.n_audio_ctx, ((long)n_samples[b] + FE_HOP - 1) / FE_HOP);
+    std::vector<int32_t> cols;
+    WMCHK(align_cols(m, nf.data(), B, cols));
+    WMCHK(frontend_run(m, pcm, n_samples, B, stride));
+    return transcribe_impl(m, m->fe.mel.as<float>(), 1, B, o, &cols, tokens_out, n_tokens, token_times);
 }
 
 // ---- measurement helpers ------------------------------------------------------------------------------------------------
@@ -2369,16 +2676,6 @@ extern "C" int wm_bench_kernel(wm_model* m, wm_state* s, int which, int reps, fl
 }
 
 // ---- op-level entry points (whisper_tensor.mojo) --------------------------------------------------------------------------
-struct TmpDev {
-    std::vector<DevBuf> bufs;
-    ~TmpDev() {
-        for (auto& b : bufs) b.release();
-    }
-    DevBuf& add() {
-        bufs.emplace_back();
-        return bufs.back();
-    }
-};
 
 extern "C" int wm_op_matmul_nt(float* C, const float* A, const float* Bm, const float* bias, int M, int N, int K, int dtype) {
     if (!C || !A || !Bm || M <= 0 || N <= 0 || K <= 0) return fail(WM_E_ARG, "bad argument");

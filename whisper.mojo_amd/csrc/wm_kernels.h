@@ -168,6 +168,13 @@ struct DecLinearParams {
     long long* ts;  // developer timeline (dec_logits only)
     int ts_id;
     long long* dbg;  // developer build: per-(workgroup, wave) phase stamps of dec_logits (100 MHz clock), null = off
+    // alignment-head capture (token timestamps; cap null = off): the output columns of every head h with cap_sel[h] >= 0 are also
+    // stored, fp32, to cap[row * cap_row_stride + (step * cap_nsel + cap_sel[h]) * 64 + (column % 64)], step = ctl->len - cap_step0;
+    // steps outside [0, cap_steps) are not stored
+    float* cap;
+    long cap_row_stride;
+    int cap_step0, cap_steps, cap_nsel;
+    signed char cap_sel[32];
 };
 template <typename TW> int launch_dec_linear(const DecLinearParams& p, hipStream_t st);  // WM_LAUNCH_*
 bool dec_linear_supports_k(int K);  // K/32 k-steps must split into NW <= 16 waves x KPW <= 4 steps (checked at model load)
@@ -287,6 +294,40 @@ void launch_init_tokens(const InitTokensParams& p, hipStream_t st);
 void launch_pack_tokens(const int* out_tokens, const int* n_tokens, int out_stride, int rows, int rows_cap, int stride, int* dst, hipStream_t st);
 void launch_set_step(StepCtl* ctl, int len, int set_len, int* pos, int pos_value, int* tok, int tok_value, int B,
                      hipStream_t st);
+
+// ---- token-level timestamps (kernels_align.hip) ------------------------------------------------------------------------
+// After a greedy loop that captured the cross-attention queries of the alignment heads (DecLinearParams.cap), per utterance b with
+// R_b = n_tokens[b] - n_prompt - 1 fed-back rows and F_b kept columns: probabilities of every head over all keys (align_probs), their
+// z-score over rows, width-7 median over columns and mean over heads (align_norm), DTW over the negated matrix and the token times
+// (align_dtw) — HF WhisperGenerationMixin._extract_token_timestamps.
+static const int ALIGN_MAX_HEADS = 32;
+static const int ALIGN_MAX_ROWS = 447;  // max_loop bound (n_text_ctx - 1)
+struct AlignParams {
+    const float* cap;     // [B][L][n_sel][64] captured cross-q rows (unscaled)
+    int B, L, n_sel, n_prompt, T, d;  // utterances, rows per utterance (max_loop), heads, prompt length, n_audio_ctx, d_model
+    const int* n_tokens;  // [B] ids per utterance
+    const int* n_frames;  // [B] columns kept (F_b <= T), or null = T
+    // keys of selected head k, K/V path (X null): kv_dtype rows kv + layer_k*kv_layer_stride + b*T*d + head_k*64, stride d
+    const void* kv;
+    int kv_dtype;
+    long kv_layer_stride;
+    // xattn path: K_h = X·Wk_hᵀ from the bf16 encoder rows X [B][T][d] and the bf16 K projection Wk (cross_kv_w, [n_layers][2][d][d]) into kh
+    const void* X;
+    const void* Wk;
+    float* kh;            // [B][n_sel][T][64]
+    int layer[ALIGN_MAX_HEADS], head[ALIGN_MAX_HEADS];
+    float* probs;         // [B][n_sel][L][T]
+    float* mean;          // [B][n_sel][T]
+    float* stdv;          // [B][n_sel][T]
+    float* M;             // [B][L][T] normalised, filtered, head-averaged matrix
+    unsigned* trace;      // [B][L][ceil(T/16)] 2-bit DTW trace in global memory, or null: in LDS (the launcher decides)
+    float* times;         // [B][out_stride]
+    int out_stride;
+};
+int launch_align_probs(const AlignParams& p, hipStream_t st);  // WM_LAUNCH_*
+int launch_align_norm(const AlignParams& p, hipStream_t st);
+int launch_align_dtw(const AlignParams& p, hipStream_t st);
+size_t align_dtw_lds_bytes(int L, int T);  // dynamic LDS of align_dtw with the trace in LDS (0: does not fit, trace goes to global)
 
 // ---- log-mel front end (kernels_frontend.hip) ------------------------------------------------------------------------
 void launch_zero_tails(float* pcm, const int* len, int B, int N, hipStream_t st);

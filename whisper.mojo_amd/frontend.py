@@ -35,8 +35,9 @@ def log_mel(model, audios: Sequence[np.ndarray]) -> np.ndarray:
 
 
 def transcribe_audio(model, audios: Sequence[np.ndarray], prompt: Sequence[int] = PROMPT, eot: int = EOT,
-                     max_loop: int = MAX_LOOP, ignore_eot: bool = False) -> List[List[int]]:
-    """PCM in, token ids out (the mel never leaves the GPU)."""
+                     max_loop: int = MAX_LOOP, ignore_eot: bool = False, return_token_timestamps: bool = False):
+    """PCM in, token ids out (the mel never leaves the GPU).  return_token_timestamps: (ids, times) with the time in seconds
+    each id was spoken (needs model.set_alignment_heads); the attention columns are cropped to each clip's real audio."""
     buf, n, stride = _pack(audios)
     p = np.asarray(prompt, np.int32)
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
@@ -44,6 +45,11 @@ def transcribe_audio(model, audios: Sequence[np.ndarray], prompt: Sequence[int] 
     total = len(p) + 1 + max_loop
     toks = np.zeros((len(audios), total), np.int32)
     cnt = np.zeros(len(audios), np.int32)
+    if return_token_timestamps:
+        times = np.zeros((len(audios), total), np.float32)
+        _lib.check(_lib.lib().wm_transcribe_pcm_tt(model._h, buf.ctypes.data_as(fp), n.ctypes.data_as(ip), len(audios), stride,
+                                                   C.byref(opts), toks.ctypes.data_as(ip), cnt.ctypes.data_as(ip), times.ctypes.data_as(fp)))
+        return ([toks[b, :cnt[b]].tolist() for b in range(len(audios))], [times[b, :cnt[b]].tolist() for b in range(len(audios))])
     _lib.check(_lib.lib().wm_transcribe_pcm(model._h, buf.ctypes.data_as(fp), n.ctypes.data_as(ip), len(audios), stride,
                                             C.byref(opts), toks.ctypes.data_as(ip), cnt.ctypes.data_as(ip)))
     return [toks[b, :cnt[b]].tolist() for b in range(len(audios))]

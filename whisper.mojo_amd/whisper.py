@@ -149,6 +149,7 @@ class Whisper:
         self.coalesce = coalesce  # 2: consecutive transcribe_submit calls of equal batch size / options share one 2·B-row decode state
         self._h = None
         self._caches = weakref.WeakSet()  # live KVCaches of the loaded model
+        self._n_align = 0  # alignment heads set on the loaded model (set_alignment_heads)
         self.encoder = WhisperEncoder(self)
         self.decoder = WhisperDecoder(self)
 
@@ -164,6 +165,7 @@ class Whisper:
         w = loader.raw_data
         _lib.check(_lib.lib().wm_model_load_memory(_fp(w), w.size, C.byref(cfg), self.device, C.byref(h)))
         self._h = h
+        self._n_align = 0
 
     def load_file(self, path: str):
         self.close()
@@ -171,6 +173,7 @@ class Whisper:
         cfg = self._cfg()
         _lib.check(_lib.lib().wm_model_load(path.encode(), C.byref(cfg), self.device, C.byref(h)))
         self._h = h
+        self._n_align = 0
 
     def close(self):
         h, self._h = self._h, None
@@ -200,10 +203,38 @@ class Whisper:
                                  tb, no_ts, max_init)
         return opts, (p, sup, bsup)
 
+    def set_alignment_heads(self, pairs: Sequence[Sequence[int]]):
+        """(layer, head) pairs whose cross-attention aligns ids with audio (HF generation_config.alignment_heads, e.g.
+        config.ALIGNMENT_HEADS_TINY); needed by return_token_timestamps.  An empty list switches the feature off."""
+        if self._h is None:
+            raise _lib.WhisperMiError("model not loaded")
+        flat = np.asarray([int(v) for pr in pairs for v in pr], np.int32)
+        if flat.size != 2 * len(pairs):
+            raise ValueError("alignment heads are (layer, head) pairs")
+        _lib.check(_lib.lib().wm_set_alignment_heads(self._h, _ip(flat) if flat.size else None, len(pairs)))
+        self._n_align = len(pairs)
+
+    @staticmethod
+    def _frames_arg(n_frames, B):
+        if n_frames is None:
+            return None
+        nf = np.ascontiguousarray(np.asarray(n_frames, np.int32).reshape(-1))
+        if nf.size != B:
+            raise ValueError(f"n_frames needs one entry per utterance ({B}), got {nf.size}")
+        return nf
+
+    @staticmethod
+    def _split_times(times, n, B):
+        return [times[b, :n[b]].tolist() for b in range(B)]
+
     def transcribe_batch(self, mel, prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP,
                          ignore_eot: bool = False, suppress_tokens: Sequence[int] = (),
-                         begin_suppress_tokens: Sequence[int] = (), timestamps=None) -> List[List[int]]:
-        """Batched Whisper.transcribe: one List[int] per utterance = prompt + generated ids (+ eot when hit)."""
+                         begin_suppress_tokens: Sequence[int] = (), timestamps=None, return_token_timestamps: bool = False,
+                         n_frames=None):
+        """Batched Whisper.transcribe: one List[int] per utterance = prompt + generated ids (+ eot when hit).
+        return_token_timestamps: also return, per utterance, the time in seconds each id was spoken (HF generate's
+        return_token_timestamps; needs set_alignment_heads) as (ids, times); n_frames: mel frames of real audio per utterance
+        (HF's attention_mask.sum(-1)), None = the whole window."""
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
@@ -212,37 +243,71 @@ class Whisper:
         total = len(p) + 1 + max_loop
         toks = np.zeros((B, total), np.int32)
         n = np.zeros(B, np.int32)
-        _lib.check(_lib.lib().wm_transcribe(self._h, ptr, on_dev, B, C.byref(opts), _ip(toks), _ip(n)))
+        if return_token_timestamps:
+            nf = self._frames_arg(n_frames, B)
+            times = np.zeros((B, total), np.float32)
+            _lib.check(_lib.lib().wm_transcribe_tt(self._h, ptr, on_dev, B, C.byref(opts), _ip(nf) if nf is not None else None,
+                                                   _ip(toks), _ip(n), _fp(times)))
+        else:
+            _lib.check(_lib.lib().wm_transcribe(self._h, ptr, on_dev, B, C.byref(opts), _ip(toks), _ip(n)))
         self.last_tokens, self.last_counts = toks, n
-        return [toks[b, :n[b]].tolist() for b in range(B)]
+        ids = [toks[b, :n[b]].tolist() for b in range(B)]
+        if return_token_timestamps:
+            self._align_shape = getattr(self, "_align_shape", {})
+            self._align_shape[0] = (B, max_loop, self._n_align)
+            return ids, self._split_times(times, n, B)
+        return ids
+
+    def alignment_weights(self, slot: int = 0) -> np.ndarray:
+        """The alignment heads' cross-attention probabilities of the slot's last timestamp pass (slot 0: transcribe_batch),
+        [B, n_heads_selected, max_loop, n_audio_ctx] over all positions; rows past an utterance's last fed-back id are 0."""
+        B, L, n_sel = self._align_shape[slot]
+        out = np.zeros((B, n_sel, L, self.config.n_audio_ctx), np.float32)
+        _lib.check(_lib.lib().wm_alignment_weights(self._h, slot, _fp(out)))
+        return out
 
     def transcribe_submit(self, mel, slot: int = 0, prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP,
                           ignore_eot: bool = False, suppress_tokens: Sequence[int] = (), begin_suppress_tokens: Sequence[int] = (),
-                          timestamps=None):
+                          timestamps=None, return_token_timestamps: bool = False, n_frames=None):
         """Pipelined form (wm_transcribe_submit): enqueue encoder + greedy loop for this batch on pipeline slot 0..7 and
         return at once; `transcribe_wait(slot)` collects the ids.  Submitting batch i+1 before waiting for batch i lets
-        its encoder overlap batch i's decode."""
+        its encoder overlap batch i's decode.  return_token_timestamps / n_frames: as transcribe_batch; the matching
+        transcribe_wait then returns (ids, times)."""
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]
-        _lib.check(_lib.lib().wm_transcribe_submit(self._h, slot, ptr, on_dev, B, C.byref(opts)))
+        if return_token_timestamps:
+            nf = self._frames_arg(n_frames, B)
+            _lib.check(_lib.lib().wm_transcribe_submit_tt(self._h, slot, ptr, on_dev, B, C.byref(opts),
+                                                          _ip(nf) if nf is not None else None))
+        else:
+            _lib.check(_lib.lib().wm_transcribe_submit(self._h, slot, ptr, on_dev, B, C.byref(opts)))
         self._pending = getattr(self, "_pending", {})
-        self._pending[slot] = (B, len(p) + 1 + max_loop, keep)
+        self._pending[slot] = (B, len(p) + 1 + max_loop, keep, (max_loop, self._n_align) if return_token_timestamps else None)
 
-    def transcribe_wait(self, slot: int = 0) -> List[List[int]]:
-        B, total, _keep = self._pending.pop(slot)
+    def transcribe_wait(self, slot: int = 0):
+        B, total, _keep, tt = self._pending.pop(slot)
         toks = np.zeros((B, total), np.int32)
         n = np.zeros(B, np.int32)
-        _lib.check(_lib.lib().wm_transcribe_wait(self._h, slot, _ip(toks), _ip(n)))
+        if tt is not None:
+            times = np.zeros((B, total), np.float32)
+            _lib.check(_lib.lib().wm_transcribe_wait_tt(self._h, slot, _ip(toks), _ip(n), _fp(times)))
+        else:
+            _lib.check(_lib.lib().wm_transcribe_wait(self._h, slot, _ip(toks), _ip(n)))
         self.last_tokens, self.last_counts = toks, n
-        return [toks[b, :n[b]].tolist() for b in range(B)]
+        ids = [toks[b, :n[b]].tolist() for b in range(B)]
+        if tt is not None:
+            self._align_shape = getattr(self, "_align_shape", {})
+            self._align_shape[slot] = (B, tt[0], tt[1])
+            return ids, self._split_times(times, n, B)
+        return ids
 
     def transcribe_wait_device(self, slot: int, packed) -> None:
         """transcribe_wait with the ids left on the GPU as the multi-GPU gather buffer: `packed` is a torch int32 CUDA tensor
         [rows, 1 + stride] on this model's device; row r becomes [length, ids zero-padded] (dist.gather_tokens_device)."""
-        B, total, _keep = self._pending.pop(slot)
+        B, total, _keep, _tt = self._pending.pop(slot)
         rows, width = int(packed.shape[0]), int(packed.shape[1])
         if not packed.is_cuda or packed.dtype.itemsize != 4 or not packed.is_contiguous():
             raise ValueError("packed must be a contiguous int32 CUDA tensor")
