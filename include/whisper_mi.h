@@ -7,7 +7,9 @@
  *
  * Conventions: every function returns 0 on success or a negative WM_E_* code and never throws;
  * wm_last_error() gives the message (thread-local).  Opaque handles own all device memory; every host
- * buffer is caller-owned and caller-sized.  One wm_model lives on one GPU; calls on one handle must be
+ * buffer is caller-owned and caller-sized, except the result of long-form transcription (wm_long_result): its per-utterance
+ * id lists and segment lists have lengths nobody knows before the run, so it is an opaque handle that the caller sizes its
+ * buffers from (wm_long_result_sizes) and frees (wm_long_result_free).  One wm_model lives on one GPU; calls on one handle must be
  * serialised by the caller (the reference is single-caller too: whisper.mojo:184 takes self immutably and
  * builds its cache locally).  Different handles (other GPUs / processes) are independent.
  */
@@ -195,6 +197,52 @@ int wm_log_mel(wm_model* m, const float* pcm, const int32_t* n_samples, int B, i
 /* PCM in, token ids out: front end + wm_transcribe without the mel ever leaving the GPU. */
 int wm_transcribe_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* opts,
                       int32_t* tokens_out, int32_t* n_tokens);
+
+/* ---- sequential long-form transcription ------------------------------------------------------------------
+ * Audio of any length, with the semantics of HF WhisperGenerationMixin.generate on its long-form path (greedy,
+ * condition_on_prev_tokens=False, no prompt_ids, no temperature fallback / no-speech / log-prob / compression thresholds,
+ * return_timestamps=True, return_segments=True): per utterance seek = 0; while seek < n_frames[b] the window
+ * mel[:, seek : seek + min(n_frames[b] - seek, 2·n_audio_ctx)] zero-padded to 2·n_audio_ctx is decoded with opts (prompt as the
+ * initial ids, timestamp rules from the first generated id), the trailing eot is dropped, the ids are split into segments at
+ * timestamp pairs (HF _retrieve_segment, = wm_op_long_segments) and seek advances as HF's does.  The utterance's sequence is the
+ * concatenation of its segments' ids.  One deliberate deviation: a window whose ids do not advance seek (e.g. <|0.00|><|0.00|>
+ * and no later pair), on which HF and openai-whisper decode the same window forever, advances by its own length instead; its
+ * segments are kept once and the window is counted (wm_long_result_stats).
+ * Any B: utterances queue for rows of passes of R = min(max_batch, ceil(B / 2)) rows (spare rows repeat a real item), up to two
+ * passes in flight on two internal decode states, never on the caller's slots 0..7.  An utterance is in at most one pass at a
+ * time, so a single recording runs its windows one pass after another, and once one state runs out of ready utterances the
+ * other's tail does too.  The two states (R rows each) stay allocated until the model is freed or B changes their size; the
+ * long-form scratch that grows with the audio (PCM, long mel, windows) is released before each call returns.  WM_E_STATE while a coalesce = 2 submit is held.  WM_E_ARG: timestamp_begin <= 0,
+ * ignore_eot != 0, n_frames[b] outside [0, T], n_prompt + 1 + max_loop > n_text_ctx.  An utterance of 0 frames has an empty
+ * result.  The sequences assume eot is also generate's pad id. */
+typedef struct wm_long_result wm_long_result;
+typedef struct {
+    int32_t first, count; /* the segment's ids are [first, first + count) of the utterance's sequence */
+    double start, end;    /* seconds, float64 as HF computes them */
+} wm_segment;
+/* Log-mel of long audio, HF WhisperFeatureExtractor(truncation=False, padding="longest", return_attention_mask=True) with the
+ * recordings zero-padded to `stride` samples (stride = the longest n_samples is HF's "longest"): F = stride / 160 frames, one
+ * clamp max per utterance over its whole spectrogram.  pcm: host [B][stride]; n_samples[b] <= stride; stride > 200.  mel_out:
+ * NULL or host [B][n_mels][F]; n_frames_out: NULL or [B], min(ceil(n_samples[b] / 160), F) (the ones of HF's attention mask).
+ * The device copies of the PCM and the mel are released before the call returns. */
+int wm_log_mel_long(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, float* mel_out, int32_t* n_frames_out);
+/* mel: [B][n_mels][T] fp32, host or (mel_on_device) device; n_frames[b] frames of real audio in row b (NULL = T). */
+int wm_transcribe_long(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames, const wm_decode_opts* opts,
+                       wm_long_result** out);
+/* wm_log_mel_long + wm_transcribe_long without the mel leaving the GPU */
+int wm_transcribe_long_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* opts,
+                           wm_long_result** out);
+int wm_long_result_sizes(const wm_long_result* r, int b, int32_t* n_tokens, int32_t* n_segments);
+/* tokens: [n_tokens] (may be NULL when 0), segs: [n_segments] */
+int wm_long_result_get(const wm_long_result* r, int b, int32_t* tokens, wm_segment* segs);
+/* windows decoded in all, how many of them did not advance seek (the deviation above), passes run, and rows those passes decoded
+ * (passes · R: rows - windows were spare rows) */
+int wm_long_result_stats(const wm_long_result* r, int32_t* windows, int32_t* stalled, int32_t* passes, int32_t* rows);
+void wm_long_result_free(wm_long_result* r);
+/* Host-only: HF _retrieve_segment on one window's generated ids (eot already dropped).  segs: room for max(1, n) entries;
+ * advance: the seek advance in frames exactly as HF computes it (0 in the zero-advance case). */
+int wm_op_long_segments(const int32_t* ids, int n, int timestamp_begin, int64_t seek, int seek_num_frames, wm_segment* segs,
+                        int32_t* n_segs, int32_t* advance);
 
 /* ---- op-level entry points (host pointers; known-answer tests only) ------------------------------------------
  * Same argument meaning as the reference ops: out-param first, caller-allocated. */

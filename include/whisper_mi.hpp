@@ -158,6 +158,37 @@ public:
         for (int b = 0; b < B; ++b) times[b].assign(t.begin() + (size_t)b * stride, t.begin() + (size_t)b * stride + n[b]);
         return unpack(toks, n, B, stride);
     }
+    // sequential long-form transcription (HF generate's long-form path; needs set_timestamps): host mels
+    // [B][n_mels][T], n_frames per utterance (empty = T) -> per utterance the sequence and its segments
+    struct LongSegment {
+        double start, end;
+        std::vector<int> tokens;
+    };
+    struct LongResult {
+        std::vector<int> sequence;
+        std::vector<LongSegment> segments;
+    };
+    std::vector<LongResult> transcribe_long(const float* mels, int B, int T, const std::vector<int32_t>& n_frames = {}, int max_loop = MAX_LOOP) const {
+        need_model();
+        wm_decode_opts o = opts(max_loop, false);
+        wm_long_result* r = nullptr;
+        check(wm_transcribe_long(model_, mels, 0, B, T, n_frames.empty() ? nullptr : n_frames.data(), &o, &r));
+        std::vector<LongResult> out(B);
+        int rc = 0;
+        for (int b = 0; b < B && !rc; ++b) {
+            int32_t nt = 0, ns = 0;
+            rc = wm_long_result_sizes(r, b, &nt, &ns);
+            std::vector<int32_t> ids(nt);
+            std::vector<wm_segment> segs(ns);
+            if (!rc) rc = wm_long_result_get(r, b, ids.data(), segs.data());
+            out[b].sequence.assign(ids.begin(), ids.end());
+            for (const wm_segment& sg : segs)
+                out[b].segments.push_back({sg.start, sg.end, std::vector<int>(ids.begin() + sg.first, ids.begin() + sg.first + sg.count)});
+        }
+        wm_long_result_free(r);
+        check(rc);
+        return out;
+    }
     // other prompts / stop ids (reduced test models have small vocabularies); defaults are the reference's
     void set_prompt(const std::vector<int32_t>& prompt, int32_t eot) {
         prompt_ = prompt;

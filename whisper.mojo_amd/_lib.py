@@ -21,6 +21,8 @@ SYMBOLS = [
     "wm_op_argmax", "wm_bench_kernel", "wm_bench_bytes", "wm_synth_weights", "wm_synth_mel_host",
     "wm_set_alignment_heads", "wm_transcribe_tt", "wm_transcribe_submit_tt", "wm_transcribe_wait_tt", "wm_transcribe_pcm_tt",
     "wm_alignment_weights", "wm_op_token_times",
+    "wm_log_mel_long", "wm_transcribe_long", "wm_transcribe_long_pcm", "wm_long_result_sizes", "wm_long_result_get",
+    "wm_long_result_stats", "wm_long_result_free", "wm_op_long_segments",
 ]
 
 ABI_VERSION = 4  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -38,6 +40,10 @@ class WmDecodeOpts(C.Structure):
                 ("suppress_tokens", C.POINTER(C.c_int32)), ("n_suppress", C.c_int),
                 ("begin_suppress_tokens", C.POINTER(C.c_int32)), ("n_begin_suppress", C.c_int),
                 ("timestamp_begin", C.c_int), ("no_timestamps_token", C.c_int), ("max_initial_timestamp_index", C.c_int)]
+
+
+class WmSegment(C.Structure):
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("start", C.c_double), ("end", C.c_double)]
 
 
 class WhisperMiError(RuntimeError):
@@ -91,6 +97,15 @@ def lib():
     L.wm_transcribe_pcm_tt.argtypes = [vp, fp, ip, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip, fp]
     L.wm_alignment_weights.argtypes = [vp, C.c_int, fp]
     L.wm_op_token_times.argtypes = [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.wm_log_mel_long.argtypes = [vp, fp, ip, C.c_int, C.c_int, fp, ip]
+    L.wm_transcribe_long.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, C.POINTER(WmDecodeOpts), C.POINTER(vp)]
+    L.wm_transcribe_long_pcm.argtypes = [vp, fp, ip, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), C.POINTER(vp)]
+    L.wm_long_result_sizes.argtypes = [vp, C.c_int, ip, ip]
+    L.wm_long_result_get.argtypes = [vp, C.c_int, ip, C.POINTER(WmSegment)]
+    L.wm_long_result_stats.argtypes = [vp, ip, ip, ip, ip]
+    L.wm_long_result_free.argtypes = [vp]
+    L.wm_long_result_free.restype = None
+    L.wm_op_long_segments.argtypes = [ip, C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(WmSegment), ip, ip]
     L.wm_op_matmul_nt.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int]
     L.wm_op_mlp_block.argtypes = [fp] * 10 + [C.c_int] * 5
     L.wm_op_ln_matmul_nt.argtypes = [fp] * 6 + [C.c_int] * 5
@@ -109,6 +124,40 @@ def lib():
     L.wm_synth_mel_host.restype = None
     _lib = L
     return L
+
+
+def long_result(h, B: int):
+    """Reads and frees a wm_long_result handle of B utterances -> (per utterance {"sequence": [...], "segments": [{"start",
+    "end", "tokens"}]}, {"windows", "stalled", "passes", "rows"}: windows decoded, windows that did not advance seek, passes
+    run and rows those passes decoded)."""
+    L = lib()
+    try:
+        out = []
+        n_tok, n_seg = C.c_int32(), C.c_int32()
+        for b in range(B):
+            check(L.wm_long_result_sizes(h, b, C.byref(n_tok), C.byref(n_seg)))
+            toks = (C.c_int32 * max(1, n_tok.value))()
+            segs = (WmSegment * max(1, n_seg.value))()
+            check(L.wm_long_result_get(h, b, toks, segs))
+            seq = list(toks[:n_tok.value])
+            out.append({"sequence": seq, "segments": [{"start": s.start, "end": s.end, "tokens": seq[s.first:s.first + s.count]}
+                                                      for s in segs[:n_seg.value]]})
+        st = [C.c_int32() for _ in range(4)]
+        check(L.wm_long_result_stats(h, *[C.byref(v) for v in st]))
+        return out, dict(zip(("windows", "stalled", "passes", "rows"), (v.value for v in st)))
+    finally:
+        L.wm_long_result_free(h)
+
+
+def long_segments(ids, timestamp_begin: int, seek: int, seek_num_frames: int):
+    """wm_op_long_segments (host-only HF _retrieve_segment): ([(first, count, start, end)], advance)."""
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
+    segs = (WmSegment * max(1, a.size))()
+    n, adv = C.c_int32(), C.c_int32()
+    check(lib().wm_op_long_segments(a.ctypes.data_as(C.POINTER(C.c_int32)), a.size, timestamp_begin, seek, seek_num_frames, segs,
+                                    C.byref(n), C.byref(adv)))
+    return [(s.first, s.count, s.start, s.end) for s in segs[:n.value]], adv.value
 
 
 def check(rc: int):

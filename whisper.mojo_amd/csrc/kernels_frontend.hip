@@ -5,19 +5,22 @@
 //   gemm_nt<float>     real DFT as an exact-fp32 MFMA GEMM against a [512, 416] cos / -sin basis (re at k, im at 256+k)
 //   mel_log_kernel     |X|^2 -> sparse triangular mel filters -> log10(max(., 1e-10))
 //   mel_norm_kernel    per-utterance max, clamp to max-8, (x+4)/4, channel-major output (what the encoder consumes)
+// Long audio (wm_log_mel_long) runs the first three over chunks of frames at a frame offset t0 into a
+// [B][n_mels][F] log-mel, then mel_max_partial_kernel + mel_norm_long_kernel: a two-stage per-utterance max over the whole
+// spectrogram (no atomics) and a wide clamp / rescale pass.  window_gather_kernel cuts the encoder windows out of it.
 #include "wm_kernels.h"
 
 namespace wm {
 
 __global__ __launch_bounds__(128) void frames_kernel(const float* __restrict__ pcm, float* __restrict__ F,
-                                                     const float* __restrict__ window, int N, int n_frames, int hop) {
+                                                     const float* __restrict__ window, int N, int n_frames, int hop, int t0) {
     const int t = blockIdx.x, b = blockIdx.y;
     const float* x = pcm + (size_t)b * N;
     float* row = F + ((size_t)b * n_frames + t) * 416;
     for (int n = threadIdx.x; n < 416; n += 128) {
         float v = 0.f;
         if (n < 400) {
-            int i = hop * t + n - 200;
+            int i = hop * (t0 + t) + n - 200;
             if (i < 0) i = -i;                    // numpy 'reflect': edge sample not repeated
             if (i >= N) i = 2 * (N - 1) - i;
             v = x[i] * window[n];
@@ -34,15 +37,15 @@ __global__ void zero_tails_kernel(float* __restrict__ pcm, const int* __restrict
 void launch_zero_tails(float* pcm, const int* len, int B, int N, hipStream_t st) {
     hipLaunchKernelGGL(zero_tails_kernel, dim3((N + 255) / 256, B), dim3(256), 0, st, pcm, len, N);
 }
-void launch_frames(const float* pcm, float* F, const float* window, int B, int N, int n_frames, int hop, hipStream_t st) {
-    hipLaunchKernelGGL(frames_kernel, dim3(n_frames, B), dim3(128), 0, st, pcm, F, window, N, n_frames, hop);
+void launch_frames(const float* pcm, float* F, const float* window, int B, int N, int n_frames, int hop, hipStream_t st, int t0) {
+    hipLaunchKernelGGL(frames_kernel, dim3(n_frames, B), dim3(128), 0, st, pcm, F, window, N, n_frames, hop, t0);
 }
 
 // spec [rows][512] (re at k, im at 256+k) -> logmel[b][m][t].  One workgroup = 32 frames; power spectrum in LDS; thread
 // (f, m-group) walks only the non-zero band [lo[m], hi[m]) of each triangular filter.
 __global__ __launch_bounds__(256) void mel_log_kernel(const float* __restrict__ spec, const float* __restrict__ fb /*[201][n_mels]*/,
                                                       const int* __restrict__ band /*[n_mels][2]*/, float* __restrict__ logmel,
-                                                      int n_frames, int n_mels) {
+                                                      int n_frames, int n_mels, int out_frames, int t_out) {
     __shared__ float P[32][204];
     const int b = blockIdx.y, t0 = blockIdx.x * 32;
     for (int i = threadIdx.x; i < 32 * 201; i += 256) {
@@ -62,11 +65,14 @@ __global__ __launch_bounds__(256) void mel_log_kernel(const float* __restrict__ 
         const int lo = band[2 * m], hi = band[2 * m + 1];
         float s = 0.f;
         for (int k = lo; k < hi; ++k) s += fb[k * n_mels + m] * P[f][k];
-        logmel[((size_t)b * n_mels + m) * n_frames + t0 + f] = log10f(fmaxf(s, 1e-10f));
+        logmel[((size_t)b * n_mels + m) * out_frames + t_out + t0 + f] = log10f(fmaxf(s, 1e-10f));
     }
 }
-void launch_mel_log(const float* spec, const float* fb, const int* band, float* logmel, int B, int n_frames, int n_mels, hipStream_t st) {
-    hipLaunchKernelGGL(mel_log_kernel, dim3((n_frames + 31) / 32, B), dim3(256), 0, st, spec, fb, band, logmel, n_frames, n_mels);
+// out_frames / t_out: row length of the output and frame offset of this chunk in it (0 / n_frames: one whole window)
+void launch_mel_log(const float* spec, const float* fb, const int* band, float* logmel, int B, int n_frames, int n_mels, hipStream_t st,
+                    int out_frames, int t_out) {
+    hipLaunchKernelGGL(mel_log_kernel, dim3((n_frames + 31) / 32, B), dim3(256), 0, st, spec, fb, band, logmel, n_frames, n_mels,
+                       out_frames > 0 ? out_frames : n_frames, t_out);
 }
 
 __global__ __launch_bounds__(1024) void mel_norm_kernel(const float* __restrict__ logmel, float* __restrict__ out, int n) {
@@ -85,6 +91,53 @@ __global__ __launch_bounds__(1024) void mel_norm_kernel(const float* __restrict_
 }
 void launch_mel_norm(const float* logmel, float* out, int B, int n, hipStream_t st) {
     hipLaunchKernelGGL(mel_norm_kernel, dim3(B), dim3(1024), 0, st, logmel, out, n);
+}
+
+// Stage 1 of the long-audio max: block (p, b) reduces elements p·256 + i·P·256 + tid of utterance b's n values -> part[b][p].
+// fmaxf is exact, so the result does not depend on the order; no atomics either way.
+__global__ __launch_bounds__(256) void mel_max_partial_kernel(const float* __restrict__ x, float* __restrict__ part, size_t n) {
+    __shared__ float s_m[4];
+    const int P = gridDim.x;
+    const float* xb = x + (size_t)blockIdx.y * n;
+    float mx = -INFINITY;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)P * 256) mx = fmaxf(mx, xb[i]);
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) part[(size_t)blockIdx.y * P + blockIdx.x] = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
+}
+// Stage 2 + the wide pass: every block re-reduces utterance b's P partials (P <= 256, the same values in the same order in every
+// block), then clamps / rescales its slice in place: y = (max(x, max - 8) + 4) / 4.
+__global__ __launch_bounds__(256) void mel_norm_long_kernel(float* __restrict__ x, const float* __restrict__ part, int P, size_t n) {
+    __shared__ float s_m[4];
+    float mx = threadIdx.x < P ? part[(size_t)blockIdx.y * P + threadIdx.x] : -INFINITY;
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    const float floor_v = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3])) - 8.0f;
+    float* xb = x + (size_t)blockIdx.y * n;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) xb[i] = (fmaxf(xb[i], floor_v) + 4.0f) / 4.0f;
+}
+void launch_mel_norm_long(float* logmel, float* part, int B, size_t n, hipStream_t st) {
+    const int P = (int)std::min<size_t>(256, (n + 4095) / 4096);
+    hipLaunchKernelGGL(mel_max_partial_kernel, dim3(P, B), dim3(256), 0, st, logmel, part, n);
+    const int G = (int)std::min<size_t>(2048, (n + 1023) / 1024);
+    hipLaunchKernelGGL(mel_norm_long_kernel, dim3(G, B), dim3(256), 0, st, logmel, part, P, n);
+}
+
+// Encoder windows of sequential long-form decoding: out[r][m][t] = mel[b][m][seek + t] for t < len, 0 beyond (HF's
+// _get_input_segment pads with 0.0), for items[r] = (b, seek, len).  The host guarantees seek + len <= F.
+__global__ __launch_bounds__(256) void window_gather_kernel(const float* __restrict__ mel, const int* __restrict__ items, float* __restrict__ out,
+                                                            int n_mels, int F, int W) {
+    const int t = blockIdx.x * 256 + threadIdx.x, m = blockIdx.y, r = blockIdx.z;
+    if (t >= W) return;
+    const int b = items[3 * r], seek = items[3 * r + 1], len = items[3 * r + 2];
+    float v = 0.f;
+    if (t < len && seek + t < F) v = mel[((size_t)b * n_mels + m) * F + seek + t];
+    out[((size_t)r * n_mels + m) * W + t] = v;
+}
+void launch_window_gather(const float* mel, const int* items, float* out, int rows, int n_mels, int F, int W, hipStream_t st) {
+    hipLaunchKernelGGL(window_gather_kernel, dim3((W + 255) / 256, n_mels, rows), dim3(256), 0, st, mel, items, out, n_mels, F, W);
 }
 
 }  // namespace wm

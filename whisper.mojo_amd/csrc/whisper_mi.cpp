@@ -252,6 +252,15 @@ struct wm_model {
         wm_state* st = nullptr;
         int row0 = 0, rows = 0, gen = 0;
     } align_ref[8];
+    // sequential long-form decoding: the long log-mel and its scratch (frames / spec hold one chunk of frames, the
+    // rest grows with the audio), and two internal decode states, apart from the caller's slots, with each one's gathered
+    // windows and work items
+    struct LongForm {
+        DevBuf pcm, lens, frames, spec, part, mel, in_mel;
+        wm_state* st[2] = {nullptr, nullptr};
+        DevBuf win[2], items[2];
+        std::vector<int32_t> h_items[2];
+    } lf;
 };
 
 struct wm_state {
@@ -475,6 +484,9 @@ extern "C" void wm_model_free(wm_model* m) {
     {
         DevBuf* fb[] = {&m->fe.window, &m->fe.dft, &m->fe.fb, &m->fe.band, &m->fe.pcm, &m->fe.lens, &m->fe.frames, &m->fe.spec, &m->fe.logtmp, &m->fe.mel};
         for (DevBuf* b : fb) b->release();
+        DevBuf* lb[] = {&m->lf.pcm, &m->lf.lens, &m->lf.frames, &m->lf.spec, &m->lf.part, &m->lf.mel, &m->lf.in_mel,
+                        &m->lf.win[0], &m->lf.win[1], &m->lf.items[0], &m->lf.items[1]};
+        for (DevBuf* b : lb) b->release();
     }
     DevBuf* top[] = {&m->conv1_w, &m->conv1_b, &m->conv2_w, &m->conv2_b, &m->enc_pos, &m->enc_ln_g, &m->enc_ln_b,
                      &m->tok_emb_f, &m->tok_emb_t, &m->dec_pos, &m->dec_ln_g, &m->dec_ln_b, &m->cross_kv_w, &m->cross_kv_b};
@@ -784,6 +796,8 @@ extern "C" void wm_state_free(wm_state* s) {
         if (sl == s) sl = nullptr;
     for (auto& pr : s->m->pairs)
         if (pr == s) pr = nullptr;
+    for (auto& ls : s->m->lf.st)
+        if (ls == s) ls = nullptr;
     for (auto& r : s->m->slot_ref)
         if (r.st == s) r = wm_model::SlotRef{};
     for (auto& r : s->m->align_ref)
@@ -1866,7 +1880,8 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
         WMCHK(state_new(m, B, slot, pair));
     }
     wm_state* s = *slot;
-    s->trace_id = slot == &m->cached ? 1 : (slot >= m->slots && slot < m->slots + (wm_model::NSLOT - 1)) ? 2 + (int)(slot - m->slots) : 10 + (int)(slot - m->pairs);
+    s->trace_id = slot == &m->cached ? 1 : (slot >= m->slots && slot < m->slots + (wm_model::NSLOT - 1)) ? 2 + (int)(slot - m->slots)
+                : (slot == &m->lf.st[0] || slot == &m->lf.st[1]) ? 20 + (int)(slot - m->lf.st) : 10 + (int)(slot - m->pairs);
     // The whole pass — encoder, prefill, greedy loop — goes on the slot's own stream: four slots are then four hardware
     // queues, which is what the chip runs concurrently (a fifth queue, e.g. a shared encoder stream, lands on a pipe that
     // already serves one of them and the two take turns: 22.3 vs 20.8 ms per pass at four passes in flight).
@@ -2446,6 +2461,309 @@ extern "C" int wm_transcribe_pcm_tt(wm_model* m, const float* pcm, const int32_t
     WMCHK(frontend_run(m, pcm, n_samples, B, stride));
     return transcribe_impl(m, m->fe.mel.as<float>(), 1, B, o, &cols, tokens_out, n_tokens, token_times);
 }
+
+// ---- sequential long-form transcription --------------------------------------------------------------------------
+struct wm_long_result {
+    std::vector<std::vector<int32_t>> tokens;  // per utterance: the concatenation of its segments' ids
+    std::vector<std::vector<wm_segment>> segs;
+    int windows = 0, stalled = 0, passes = 0, rows = 0;
+};
+
+// HF WhisperGenerationMixin._retrieve_segment (time_precision 0.02, time_precision_features 0.01, input_stride 2) on one window's
+// generated ids without the trailing eot.  Returns the seek advance in frames exactly as HF computes it (possibly 0).
+static int long_segments(const int32_t* ids, int n, int tb, int64_t seek, int snf, std::vector<wm_segment>& out) {
+#pragma clang fp contract(off)
+    out.clear();
+    const double off = (double)seek * 0.02 / 2;  // time_offset: float64(seek) * time_precision / input_stride
+    auto ts = [&](int i) { return ids[i] >= tb; };
+    const bool single_end = n >= 2 && !ts(n - 2) && ts(n - 1);  // timestamp_tokens[-2:] == [False, True]
+    std::vector<int> slices;
+    for (int i = 1; i < n; ++i)
+        if (ts(i - 1) && ts(i)) slices.push_back(i);  // consecutive timestamps end a segment
+    if (!slices.empty()) {
+        if (single_end) slices.push_back(n);
+        else slices.back() += 1;  // the last pair stays in the last segment
+        int last = 0;
+        for (size_t k = 0; k < slices.size(); ++k) {
+            const int cur = slices[k];
+            const bool is_last = k + 1 == slices.size();
+            const int end_i = (!is_last || single_end) ? cur - 1 : cur - 2;
+            out.push_back(wm_segment{last, cur - last, off + (double)(ids[last] - tb) * 0.02, off + (double)(ids[end_i] - tb) * 0.02});
+            last = cur;
+        }
+        return single_end ? snf : (ids[last - 2] - tb) * 2;
+    }
+    // no pair: the whole window is one segment, ending at the last timestamp (other than <|0.00|>) or at the window's end — the
+    // latter as HF computes it, int(seek_num_frames * 0.01 / 0.02) in float32 (a long tensor times a Python float)
+    int last_ts = -1;
+    for (int i = 0; i < n; ++i)
+        if (ts(i)) last_ts = ids[i];
+    const double end_pos = (last_ts >= 0 && last_ts != tb) ? (double)(last_ts - tb) : (double)(int)((float)snf * 0.01f / 0.02f);
+    out.push_back(wm_segment{0, n, off, off + end_pos * 0.02});
+    return snf;
+}
+
+extern "C" int wm_op_long_segments(const int32_t* ids, int n, int timestamp_begin, int64_t seek, int seek_num_frames, wm_segment* segs,
+                                   int32_t* n_segs, int32_t* advance) {
+    if (n < 0 || (n > 0 && !ids) || !segs || !n_segs || !advance || timestamp_begin <= 0 || seek < 0 || seek_num_frames < 0)
+        return fail(WM_E_ARG, "bad argument");
+    std::vector<wm_segment> out;
+    *advance = long_segments(ids, n, timestamp_begin, seek, seek_num_frames, out);
+    *n_segs = (int32_t)out.size();
+    std::copy(out.begin(), out.end(), segs);
+    return 0;
+}
+
+// The long-form scratch that grows with the audio goes back to the device once a call is done (the two decode states stay, like the
+// slots').  hipFree waits for the device, and every pass of the call has been waited for.
+static void long_release(wm_model* m) {
+    wm_model::LongForm& L = m->lf;
+    DevBuf* bs[] = {&L.pcm, &L.lens, &L.frames, &L.spec, &L.part, &L.mel, &L.in_mel, &L.win[0], &L.win[1], &L.items[0], &L.items[1]};
+    for (DevBuf* b : bs) b->release();
+}
+
+// Log-mel of long audio into m->lf.mel [B][n_mels][stride / 160] (device): the 30 s path's kernels over chunks of frames of all
+// utterances at once, so frames / spec stay one chunk however long the audio; then the two-stage max and the clamp / rescale.
+static const int LONG_FE_ROWS = 16 * 3000;  // frames per DFT GEMM (the 30 s path's largest chunk)
+static int frontend_long_run(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, int32_t* n_frames_out) {
+    if (!pcm || !n_samples || B <= 0 || stride <= 200) return fail(WM_E_ARG, "bad argument (B >= 1, stride > 200 samples)");
+    for (int b = 0; b < B; ++b)
+        if (n_samples[b] < 0 || n_samples[b] > stride) return fail(WM_E_ARG, "n_samples[%d]=%d out of range", b, n_samples[b]);
+    HIPCHK(hipSetDevice(m->device));
+    WMCHK(frontend_init(m));
+    const int n_mels = m->cfg.dims.n_mels, F = stride / FE_HOP;
+    hipStream_t st = m->stream;
+    wm_model::LongForm& L = m->lf;
+    const int nt = std::max(32, std::min((F + 31) / 32 * 32, LONG_FE_ROWS / B / 32 * 32));  // frames per chunk and utterance
+    const size_t rows = ((size_t)B * nt + 255) / 256 * 256 + 256;
+    if (!L.frames.p || L.frames.bytes < rows * 416 * 4) WMCHK(L.frames.alloc(rows * 416 * 4, true));
+    if (!L.spec.p || L.spec.bytes < rows * 512 * 4) WMCHK(L.spec.alloc(rows * 512 * 4, true));
+    WMCHK(grow(L.pcm, (size_t)B * stride * 4));
+    WMCHK(grow(L.lens, (size_t)B * 4));
+    WMCHK(grow(L.part, (size_t)B * 256 * 4));
+    WMCHK(grow(L.mel, (size_t)B * n_mels * F * 4));
+    HIPCHK(hipMemcpyAsync(L.pcm.p, pcm, (size_t)B * stride * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(L.lens.p, n_samples, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    launch_zero_tails(L.pcm.as<float>(), L.lens.as<int>(), B, stride, st);  // HF pads with zeros to the longest recording
+    for (int t0 = 0; t0 < F; t0 += nt) {
+        const int n = std::min(nt, F - t0);
+        launch_frames(L.pcm.as<float>(), L.frames.as<float>(), m->fe.window.as<float>(), B, stride, n, FE_HOP, st, t0);
+        GemmParams p{};
+        p.A = L.frames.p;
+        p.W = m->fe.dft.p;
+        p.C = L.spec.p;
+        p.M = B * n;
+        p.N = 512;
+        p.K = 416;
+        p.lda = 416;
+        p.ldw = 416;
+        p.ldc = 512;
+        LCHK((launch_gemm_nt<float, float>(p, 1, st)));
+        launch_mel_log(L.spec.as<float>(), m->fe.fb.as<float>(), m->fe.band.as<int>(), L.mel.as<float>(), B, n, n_mels, st, F, t0);
+    }
+    launch_mel_norm_long(L.mel.as<float>(), L.part.as<float>(), B, (size_t)n_mels * F, st);
+    HIPCHK(hipGetLastError());
+    if (n_frames_out)
+        for (int b = 0; b < B; ++b) n_frames_out[b] = std::min((n_samples[b] + FE_HOP - 1) / FE_HOP, F);
+    return 0;
+}
+
+extern "C" int wm_log_mel_long(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, float* mel_out, int32_t* n_frames_out) {
+    if (!m) return fail(WM_E_ARG, "null model");
+    const int rc = frontend_long_run(m, pcm, n_samples, B, stride, n_frames_out);
+    if (rc) {
+        (void)hipStreamSynchronize(m->stream);
+        long_release(m);
+        return rc;
+    }
+    hipError_t e = hipSuccess;
+    if (mel_out)
+        e = hipMemcpyAsync(mel_out, m->lf.mel.p, (size_t)B * m->cfg.dims.n_mels * (stride / FE_HOP) * 4, hipMemcpyDeviceToHost, m->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+    long_release(m);
+    if (e != hipSuccess) return fail(WM_E_HIP, "wm_log_mel_long: %s", hipGetErrorString(e));
+    return 0;
+}
+
+static int long_check(wm_model* m, const wm_decode_opts* o, int B) {
+    WMCHK(check_opts(m, o, B));
+    if (o->timestamp_begin <= 0) return fail(WM_E_ARG, "long-form transcription needs the timestamp rules (timestamp_begin > 0)");
+    if (o->ignore_eot) return fail(WM_E_ARG, "long-form transcription stops each window at eot (ignore_eot must be 0)");
+    if (o->n_prompt + 1 + o->max_loop > m->cfg.dims.n_text_ctx)
+        return fail(WM_E_ARG, "n_prompt + 1 + max_loop = %d exceeds the decoder context %d", o->n_prompt + 1 + o->max_loop, m->cfg.dims.n_text_ctx);
+    if (m->held.active) return fail(WM_E_STATE, "a coalesced submit is held: wait for it before long-form transcription");
+    return 0;
+}
+
+// The window scheduler.  Without condition_on_prev_tokens an utterance carries nothing but seek from one window to the next, so a
+// pass may take ANY pending (utterance, seek) items: passes of R = min(ceil(B / 2), max_batch) rows (short passes repeat their first
+// item, so neither state is re-created within a call and the repeat finishes with its original), two in flight on m->lf.st[0..1]
+// — one pass's gather + encoder and the host's segment bookkeeping overlap the other's decode.  An utterance rides one pass at a
+// time: with B <= 2R the two states keep the utterances they started with, and when one state runs dry the other's tail runs
+// one pass at a time.  mel: device [B][n_mels][T].
+static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int B, const wm_decode_opts* o, wm_long_result* res) {
+    const wm_dims& c = m->cfg.dims;
+    // half the batch per state (when it fits), so that two passes are in flight whenever two utterances are pending
+    const int W = 2 * c.n_audio_ctx, R = std::min((B + 1) / 2, m->cfg.max_batch), total = o->n_prompt + 1 + o->max_loop;
+    wm_model::LongForm& L = m->lf;
+    std::vector<int64_t> seek(B, 0);
+    std::vector<char> busy(B, 0);
+    std::vector<int> snf(B, 0);
+    int n_items[2] = {0, 0}, order[2] = {0, 0}, ticket = 0;
+    for (int k = 0; k < 2; ++k) {
+        WMCHK(grow(L.win[k], (size_t)R * c.n_mels * W * 4));
+        WMCHK(grow(L.items[k], (size_t)R * 3 * 4));
+    }
+    std::vector<int32_t> toks((size_t)R * total), cnt(R);
+    std::vector<wm_segment> segs;
+    auto drain = [&]() {  // an error mid-run: let the other pass finish before returning
+        for (int k = 0; k < 2; ++k)
+            if (n_items[k] && L.st[k] && L.st[k]->pending) (void)wait_on(m, L.st[k], toks.data(), cnt.data());
+    };
+    int cursor = 0;
+    for (;;) {
+        for (int k = 0; k < 2; ++k) {  // fill idle states with ready utterances
+            if (n_items[k]) continue;
+            std::vector<int32_t>& h = L.h_items[k];
+            h.clear();
+            for (int i = 0; i < B && (int)h.size() < 3 * R; ++i) {
+                const int b = (cursor + i) % B;
+                if (busy[b] || seek[b] >= nf[b]) continue;
+                snf[b] = (int)std::min<int64_t>(nf[b] - seek[b], W);
+                h.insert(h.end(), {b, (int32_t)seek[b], snf[b]});
+                busy[b] = 1;
+            }
+            if (h.empty()) continue;
+            n_items[k] = (int)h.size() / 3;
+            cursor = (h[3 * (n_items[k] - 1)] + 1) % B;
+            for (int r = n_items[k]; r < R; ++r) h.insert(h.end(), {h[0], h[1], h[2]});
+            int rc = hipMemcpyAsync(L.items[k].p, h.data(), (size_t)R * 3 * 4, hipMemcpyHostToDevice, m->stream) == hipSuccess ? 0
+                     : fail(WM_E_HIP, "items upload failed");
+            if (!rc) {
+                launch_window_gather(mel, L.items[k].as<int>(), L.win[k].as<float>(), R, c.n_mels, T, W, m->stream);
+                rc = hipGetLastError() == hipSuccess ? 0 : fail(WM_E_HIP, "window gather launch failed");
+            }
+            if (!rc) rc = submit_on(m, &L.st[k], L.win[k].as<float>(), 1, R, o, false);
+            if (rc) {
+                n_items[k] = 0;
+                drain();
+                return rc;
+            }
+            order[k] = ++ticket;
+            ++res->passes;
+            res->rows += R;
+        }
+        int k = -1;  // the older pass in flight
+        for (int j = 0; j < 2; ++j)
+            if (n_items[j] && (k < 0 || order[j] < order[k])) k = j;
+        if (k < 0) break;
+        const int rc = wait_on(m, L.st[k], toks.data(), cnt.data());
+        const int n = n_items[k];
+        n_items[k] = 0;
+        if (rc) {
+            drain();
+            return rc;
+        }
+        for (int r = 0; r < n; ++r) {
+            const int b = L.h_items[k][3 * r];
+            const int32_t* row = toks.data() + (size_t)r * total;
+            int g1 = cnt[r];
+            if (g1 > o->n_prompt && row[g1 - 1] == o->eot) --g1;  // HF drops the trailing eos
+            const int g0 = std::min(o->n_prompt, g1);
+            int adv = long_segments(row + g0, g1 - g0, o->timestamp_begin, seek[b], snf[b], segs);
+            if (adv == 0) {  // the deviation: HF would decode this window again, forever
+                adv = snf[b];
+                ++res->stalled;
+            }
+            std::vector<int32_t>& seq = res->tokens[b];
+            for (wm_segment sg : segs) {
+                const int32_t first = (int32_t)seq.size();
+                seq.insert(seq.end(), row + g0 + sg.first, row + g0 + sg.first + sg.count);
+                sg.first = first;
+                res->segs[b].push_back(sg);
+            }
+            seek[b] += adv;
+            busy[b] = 0;
+            ++res->windows;
+        }
+    }
+    return 0;
+}
+
+static int transcribe_long_impl(wm_model* m, const float* mel_dev, int T, const int32_t* nf, int B, const wm_decode_opts* o, wm_long_result** out) {
+    wm_long_result* r = new wm_long_result();
+    r->tokens.resize(B);
+    r->segs.resize(B);
+    const int rc = long_run(m, mel_dev, T, nf, B, o, r);
+    (void)hipStreamSynchronize(m->stream);
+    long_release(m);
+    if (rc) {
+        delete r;
+        return rc;
+    }
+    *out = r;
+    return 0;
+}
+
+extern "C" int wm_transcribe_long(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames, const wm_decode_opts* o,
+                                  wm_long_result** out) {
+    if (!m || !mel || !out || T <= 0) return fail(WM_E_ARG, "bad argument");
+    *out = nullptr;
+    WMCHK(long_check(m, o, B));
+    std::vector<int32_t> nf(B, T);
+    if (n_frames)
+        for (int b = 0; b < B; ++b) {
+            if (n_frames[b] < 0 || n_frames[b] > T) return fail(WM_E_ARG, "n_frames[%d] = %d outside [0, %d]", b, n_frames[b], T);
+            nf[b] = n_frames[b];
+        }
+    HIPCHK(hipSetDevice(m->device));
+    const float* dev = mel;
+    if (!mel_on_device) {
+        const size_t bytes = (size_t)B * m->cfg.dims.n_mels * T * 4;
+        WMCHK(grow(m->lf.in_mel, bytes));
+        HIPCHK(hipMemcpyAsync(m->lf.in_mel.p, mel, bytes, hipMemcpyHostToDevice, m->stream));
+        dev = m->lf.in_mel.as<float>();
+    }
+    return transcribe_long_impl(m, dev, T, nf.data(), B, o, out);
+}
+
+extern "C" int wm_transcribe_long_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o,
+                                      wm_long_result** out) {
+    if (!m || !out) return fail(WM_E_ARG, "bad argument");
+    *out = nullptr;
+    WMCHK(long_check(m, o, B));
+    std::vector<int32_t> nf(std::max(B, 0));
+    const int rc = frontend_long_run(m, pcm, n_samples, B, stride, nf.data());  // same stream as the gathers: ordered, no host sync
+    if (rc) {
+        (void)hipStreamSynchronize(m->stream);
+        long_release(m);
+        return rc;
+    }
+    return transcribe_long_impl(m, m->lf.mel.as<float>(), stride / FE_HOP, nf.data(), B, o, out);
+}
+
+extern "C" int wm_long_result_sizes(const wm_long_result* r, int b, int32_t* n_tokens, int32_t* n_segments) {
+    if (!r || b < 0 || b >= (int)r->tokens.size() || !n_tokens || !n_segments) return fail(WM_E_ARG, "bad argument");
+    *n_tokens = (int32_t)r->tokens[b].size();
+    *n_segments = (int32_t)r->segs[b].size();
+    return 0;
+}
+extern "C" int wm_long_result_get(const wm_long_result* r, int b, int32_t* tokens, wm_segment* segs) {
+    if (!r || b < 0 || b >= (int)r->tokens.size() || (!tokens && !r->tokens[b].empty()) || (!segs && !r->segs[b].empty()))
+        return fail(WM_E_ARG, "bad argument");
+    std::copy(r->tokens[b].begin(), r->tokens[b].end(), tokens);
+    std::copy(r->segs[b].begin(), r->segs[b].end(), segs);
+    return 0;
+}
+extern "C" int wm_long_result_stats(const wm_long_result* r, int32_t* windows, int32_t* stalled, int32_t* passes, int32_t* rows) {
+    if (!r || !windows || !stalled || !passes || !rows) return fail(WM_E_ARG, "bad argument");
+    *windows = r->windows;
+    *stalled = r->stalled;
+    *passes = r->passes;
+    *rows = r->rows;
+    return 0;
+}
+extern "C" void wm_long_result_free(wm_long_result* r) { delete r; }
 
 // ---- measurement helpers ------------------------------------------------------------------------------------------------
 // A freshly encoded state has an empty self-attention cache; the decode step is priced AND timed mid-sequence, at this many

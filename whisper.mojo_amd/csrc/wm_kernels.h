@@ -331,8 +331,12 @@ size_t align_dtw_lds_bytes(int L, int T);  // dynamic LDS of align_dtw with the 
 
 // ---- log-mel front end (kernels_frontend.hip) ------------------------------------------------------------------------
 void launch_zero_tails(float* pcm, const int* len, int B, int N, hipStream_t st);
-void launch_frames(const float* pcm, float* F, const float* window, int B, int N, int n_frames, int hop, hipStream_t st);
-void launch_mel_log(const float* spec, const float* fb, const int* band, float* logmel, int B, int n_frames, int n_mels, hipStream_t st);
+void launch_frames(const float* pcm, float* F, const float* window, int B, int N, int n_frames, int hop, hipStream_t st, int t0 = 0);
+void launch_mel_log(const float* spec, const float* fb, const int* band, float* logmel, int B, int n_frames, int n_mels, hipStream_t st,
+                    int out_frames = 0, int t_out = 0);
+// long-audio front end and window gather (kernels_frontend.hip); part: >= 256·B floats of scratch
+void launch_mel_norm_long(float* logmel, float* part, int B, size_t n, hipStream_t st);
+void launch_window_gather(const float* mel, const int* items, float* out, int rows, int n_mels, int F, int W, hipStream_t st);
 void launch_mel_norm(const float* logmel, float* out, int B, int n, hipStream_t st);
 
 // ---- small ops for the op-level C-ABI ----------------------------------------------------------------------------

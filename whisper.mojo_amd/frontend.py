@@ -55,6 +55,41 @@ def transcribe_audio(model, audios: Sequence[np.ndarray], prompt: Sequence[int] 
     return [toks[b, :cnt[b]].tolist() for b in range(len(audios))]
 
 
+def log_mel_long(model, audios: Sequence[np.ndarray]):
+    """Log-mel of audio of any length, HF WhisperFeatureExtractor(truncation=False, padding="longest",
+    return_attention_mask=True): (features [B, n_mels, longest // 160] float32, n_frames [B] = the mask's ones)."""
+    buf, n, stride = _pack(audios)
+    stride = max(stride, 201)
+    if buf.shape[1] < stride:
+        buf = np.pad(buf, ((0, 0), (0, stride - buf.shape[1])))
+    out = np.empty((len(audios), model.config.n_mels, stride // HOP), np.float32)
+    nf = np.zeros(len(audios), np.int32)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    _lib.check(_lib.lib().wm_log_mel_long(model._h, buf.ctypes.data_as(fp), n.ctypes.data_as(ip), len(audios), stride,
+                                          out.ctypes.data_as(fp), nf.ctypes.data_as(ip)))
+    return out, nf
+
+
+def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequence[int] = PROMPT, eot: int = EOT,
+                               max_loop: int = MAX_LOOP, suppress_tokens: Sequence[int] = (), begin_suppress_tokens: Sequence[int] = (),
+                               timestamps=(50364, 50363, 50), return_stats: bool = False):
+    """Sequential long-form transcription of 16 kHz PCM of any length (HF generate's long-form path), the long
+    log-mel never leaving the GPU.  Returns per recording {"sequence": ids, "segments": [{"start", "end", "tokens"}]}."""
+    if timestamps is None:
+        raise ValueError("long-form transcription needs the timestamp rules")
+    buf, n, stride = _pack(audios)
+    stride = max(stride, 201)
+    if buf.shape[1] < stride:
+        buf = np.pad(buf, ((0, 0), (0, stride - buf.shape[1])))
+    opts, _keep = model._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    h = C.c_void_p()
+    _lib.check(_lib.lib().wm_transcribe_long_pcm(model._h, buf.ctypes.data_as(fp), n.ctypes.data_as(ip), len(audios), stride,
+                                                 C.byref(opts), C.byref(h)))
+    out, stats = _lib.long_result(h, len(audios))
+    return (out, stats) if return_stats else out
+
+
 # ---- decoding features the reference lacks (SURVEY §8f rank 4), host-level over the same C-ABI -----------------------
 HOP = 160  # samples per mel frame (WhisperFeatureExtractor hop_length)
 

@@ -98,3 +98,9 @@ def synth_mel(cfg: WhisperConfig, seed: int) -> np.ndarray:
 def synth_mels(cfg: WhisperConfig, first_utt: int, count: int) -> np.ndarray:
     """[count, n_mels, n_frames]; utterance i uses seed 1000+i."""
     return np.stack([synth_mel(cfg, 1000 + first_utt + i) for i in range(count)])
+
+
+def synth_long_mel(cfg: WhisperConfig, seed: int, n_frames: int) -> np.ndarray:
+    """[n_mels, n_frames] fp32 of any length: consecutive synth_mel windows of seeds 1000·seed + k, cropped (long-form tests)."""
+    k = max(1, -(-n_frames // cfg.n_frames))
+    return np.concatenate([synth_mel(cfg, 1000 * seed + i) for i in range(k)], axis=1)[:, :n_frames].copy()

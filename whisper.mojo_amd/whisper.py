@@ -258,6 +258,60 @@ class Whisper:
             return ids, self._split_times(times, n, B)
         return ids
 
+    def transcribe_long_form(self, features, n_frames=None, prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP,
+                             suppress_tokens: Sequence[int] = (), begin_suppress_tokens: Sequence[int] = (),
+                             timestamps=(50364, 50363, 50), return_stats: bool = False):
+        """Sequential long-form transcription (HF generate's long-form path, greedy, condition_on_prev_tokens=False).
+        features: [B, n_mels, T] log-mel of any length T (numpy, or a CUDA tensor on this model's device), or a list of
+        [n_mels, T_b] arrays; n_frames: frames of real audio per utterance (HF's attention_mask.sum(-1)), None = T (or each
+        array's length).  timestamps: (timestamp_begin, no_timestamps_id, max_initial_timestamp_index | None), required.
+        Returns per utterance {"sequence": ids, "segments": [{"start", "end", "tokens"}]} — HF's return_segments output with
+        the padding-free sequences row; return_stats also returns {"windows", "stalled"}."""
+        if self._h is None:
+            raise _lib.WhisperMiError("model not loaded")
+        if timestamps is None:
+            raise ValueError("long-form transcription needs the timestamp rules")
+        n_mels = self.config.n_mels
+        if isinstance(features, (list, tuple)):
+            arrs = [np.asarray(f, np.float32) for f in features]
+            for f in arrs:
+                if f.ndim != 2 or f.shape[0] != n_mels:
+                    raise ValueError(f"each feature array must be [{n_mels}, T_b], got {f.shape}")
+            lens = [f.shape[1] for f in arrs]
+            feats = np.zeros((len(arrs), n_mels, max([1] + lens)), np.float32)
+            for b, f in enumerate(arrs):
+                feats[b, :, :lens[b]] = f
+            n_frames = lens if n_frames is None else n_frames
+            features = feats
+        if isinstance(features, np.ndarray):
+            keep = np.ascontiguousarray(features, np.float32)
+            if keep.ndim == 2:
+                keep = keep[None]
+            if keep.ndim != 3 or keep.shape[1] != n_mels or keep.shape[0] < 1 or keep.shape[2] < 1:
+                raise ValueError(f"features must be [B, {n_mels}, T], got {features.shape}")
+            ptr, on_dev = C.c_void_p(keep.ctypes.data), 0
+        else:
+            import torch
+            if not isinstance(features, torch.Tensor):
+                raise TypeError("features must be a numpy array, a list of [n_mels, T_b] arrays or a torch tensor")
+            t = features if features.dim() == 3 else features[None]
+            if t.dim() != 3 or t.shape[1] != n_mels or t.shape[0] < 1 or t.shape[2] < 1:
+                raise ValueError(f"features must be [B, {n_mels}, T], got {tuple(features.shape)}")
+            if not t.is_cuda:
+                return self.transcribe_long_form(t.float().numpy(), n_frames, prompt, eot, max_loop, suppress_tokens,
+                                                 begin_suppress_tokens, timestamps, return_stats)
+            keep = t.contiguous().float()
+            torch.cuda.current_stream(keep.device).synchronize()  # the library reads it on its own HIP stream
+            ptr, on_dev = C.c_void_p(keep.data_ptr()), 1
+        B, T = int(keep.shape[0]), int(keep.shape[2])
+        nf = self._frames_arg(n_frames, B)
+        opts, _keep2 = self._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().wm_transcribe_long(self._h, ptr, on_dev, B, T, _ip(nf) if nf is not None else None, C.byref(opts),
+                                                 C.byref(h)))
+        out, stats = _lib.long_result(h, B)
+        return (out, stats) if return_stats else out
+
     def alignment_weights(self, slot: int = 0) -> np.ndarray:
         """The alignment heads' cross-attention probabilities of the slot's last timestamp pass (slot 0: transcribe_batch),
         [B, n_heads_selected, max_loop, n_audio_ctx] over all positions; rows past an utterance's last fed-back id are 0."""
