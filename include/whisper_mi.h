@@ -267,6 +267,25 @@ int wm_op_layer_norm(float* out, const float* inp, const float* gamma, const flo
  * control block (the self-attention form).  Known-answer tests. */
 int wm_op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
                            int n_chunks);
+/* The decode step's final LayerNorm + tied-embedding logits and fused argmax (whisper.mojo:156-166, whisper_tensor.mojo:431-439):
+ * logits[B, N] = layer_norm(x, ln_g, ln_b, 1e-5)·emb[N, K]ᵀ on the decode step's logits kernel, emb rounded to dtype on upload (the
+ * kernel variant follows from dtype, K and B as in a decode step), and ids[B] = the fused argmax of those logits (stage 1 in the
+ * logits kernel, stage 2 the step's argmax) with the lowest-index rule; an all -inf candidate set gives id 0.  mask [N]: additive
+ * 0 / -inf applied to the argmax candidates only, or NULL.  ranges [B][4] = (text_lo, text_hi, ts_lo, ts_hi), or NULL: with
+ * 0 < timestamp_begin < N the timestamp decision is on — the best admissible text id in [text_lo, text_hi) unless
+ * logsumexp of the admissible timestamps in [ts_lo, ts_hi) exceeds its logit, then the best admissible timestamp.
+ * x [B, K] fp32, K in {128, 384, 512}.  Known-answer tests. */
+int wm_op_logits(float* logits, int32_t* ids, const float* x, const float* ln_g, const float* ln_b, const float* emb, const float* mask,
+                 const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype);
+/* The absorbed cross-attention of bf16-encoder / fp32-K/V models: per row r and head h, with X = x[utt(r)] and
+ * utt(r) = r % q_B when q_B > 0 (prefill rows, position-major; rows = P·q_B) else r,
+ *   out[r, h] = Σ_j softmax_j(0.125·q_h[r]·(Wk_h X_j)) (Wv_h X_j) + bv_h,
+ * computed as the decode step does: q' = 0.125·q_h·Wk_h once per row, the X sweep in nsplit key chunks, merge + Wv apply.
+ * q [rows, 64·n_heads] and bv [64·n_heads] fp32; Wk, Wv [64·n_heads, 64·n_heads] and x [n_utt, n_keys, 64·n_heads] rounded to bf16
+ * on upload.  out [rows, 64·n_heads] in out_dtype WM_F32 or WM_BF16, returned widened to fp32.  1 <= n_heads <= 8,
+ * 1 <= nsplit <= 64 (chunks of ceil(n_keys / nsplit) keys; trailing chunks may be empty).  Known-answer tests. */
+int wm_op_xattn(float* out, const float* q, const float* Wk, const float* Wv, const float* bv, const float* x, int rows, int q_B,
+                int n_utt, int n_keys, int n_heads, int nsplit, int out_dtype);
 /* The MLP half of ResidualAttentionBlock.forward  layers.mojo:489-517 :  x += fc2(gelu(fc1(layer_norm(x, ln_g, ln_b)))),
  * x [M, d] in place; fc1_w [ffn, d], fc2_w [d, ffn] (HF [out, in]).  With next_g / next_b / xn_out non-NULL also returns
  * layer_norm(x_new, next_g, next_b) rounded to the operand dtype (what the next projection is fed) in xn_out [M, d].

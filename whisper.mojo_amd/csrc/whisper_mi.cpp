@@ -3293,6 +3293,153 @@ extern "C" int wm_op_attention_cached(float* out, const float* q, const float* k
     return 0;
 }
 
+// The decode step's final LayerNorm + tied-embedding logits and its fused argmax, wired as decode_core (want_logits) and
+// argmax_params wire them: launch_dec_logits picks the kernel variant from (dtype, K, B), argmax_step reduces its partials.
+extern "C" int wm_op_logits(float* logits, int32_t* ids, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                            const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
+    if (!logits || !ids || !x || !ln_g || !ln_b || !emb || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
+    if (K != 128 && K != 384 && K != 512) return fail(WM_E_ARG, "K must be 128, 384 or 512 (the logits kernels' d_model)");
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    if (ranges && (timestamp_begin <= 0 || timestamp_begin >= N)) return fail(WM_E_ARG, "ranges need 0 < timestamp_begin < N");
+    TmpDev t;
+    t.bufs.reserve(16);
+    hipStream_t st = nullptr;
+    const int ldo = (N + 3) / 4 * 4, npart = dec_logits_parts(N);  // the kernel stores whole float4 groups below ldo
+    DevBuf &dx = t.add(), &g = t.add(), &be = t.add(), &w = t.add(), &mk = t.add(), &o = t.add(), &av = t.add(), &ai = t.add(),
+           &tst = t.add(), &tv = t.add(), &ti = t.add(), &tm = t.add(), &ts = t.add(), &nx = t.add();
+    WMCHK(upload(dx, x, (size_t)B * K, WM_F32));
+    WMCHK(upload(g, ln_g, K, WM_F32));
+    WMCHK(upload(be, ln_b, K, WM_F32));
+    WMCHK(upload(w, emb, (size_t)N * K, dtype));
+    if (mask) WMCHK(upload(mk, mask, N, WM_F32));
+    WMCHK(o.alloc((size_t)B * ldo * 4, true));
+    WMCHK(av.alloc((size_t)B * npart * 4, true));
+    WMCHK(ai.alloc((size_t)B * npart * 4, true));
+    WMCHK(nx.alloc((size_t)B * 4, true));
+    TsRules rules{};
+    if (ranges) {
+        std::vector<TsState> h(B);
+        for (int b = 0; b < B; ++b) {
+            h[b] = TsState{};
+            h[b].n_gen = 1;
+            h[b].t_last = -1;
+            h[b].text_lo = ranges[4 * b];
+            h[b].text_hi = ranges[4 * b + 1];
+            h[b].ts_lo = ranges[4 * b + 2];
+            h[b].ts_hi = ranges[4 * b + 3];
+        }
+        WMCHK(tst.alloc((size_t)B * sizeof(TsState)));
+        HIPCHK(hipMemcpy(tst.p, h.data(), (size_t)B * sizeof(TsState), hipMemcpyHostToDevice));
+        for (DevBuf* d : {&tv, &ti, &tm, &ts}) WMCHK(d->alloc((size_t)B * npart * 4, true));
+        rules.tb = timestamp_begin;
+        rules.eos = timestamp_begin;
+        rules.max_init = -1;
+        rules.vocab = N;
+    }
+    DecLinearParams p{};
+    p.x = dx.as<float>();
+    p.ldx = K;
+    p.ln_g = g.as<float>();
+    p.ln_b = be.as<float>();
+    p.W = w.p;
+    p.N = N;
+    p.K = K;
+    p.B = B;
+    p.out = o.as<float>();
+    p.ldo = ldo;
+    p.amax_val = av.as<float>();
+    p.amax_idx = ai.as<int>();
+    p.amax_stride = npart;
+    p.amax_mask = mask ? mk.as<float>() : nullptr;
+    if (ranges) {
+        p.ts_state = tst.as<TsState>();
+        p.ts_begin = timestamp_begin;
+        p.ts_val = tv.as<float>();
+        p.ts_idx = ti.as<int>();
+        p.ts_m = tm.as<float>();
+        p.ts_s = ts.as<float>();
+    }
+    int lrc = 0;
+    DISPATCH_DT(dtype, TT, lrc = launch_dec_logits<TT>(p, st));
+    LCHK(lrc);
+    ArgmaxParams a{};
+    if (ranges) {
+        a.ts_state = tst.as<TsState>();
+        a.rules = rules;
+        a.ts_val = tv.as<float>();
+        a.ts_idx = ti.as<int>();
+        a.ts_m = tm.as<float>();
+        a.ts_s = ts.as<float>();
+        a.ts_part0 = timestamp_begin / dec_logits_ids_per_part(N);
+    }
+    a.logits = o.as<float>();
+    a.ldl = ldo;
+    a.V = N;
+    a.B = B;
+    a.pval = av.as<float>();
+    a.pidx = ai.as<int>();
+    a.npart = npart;
+    a.next = nx.as<int>();
+    launch_argmax_step(a, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy2D(logits, (size_t)N * 4, o.p, (size_t)ldo * 4, (size_t)N * 4, B, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ids, nx.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The absorbed cross-attention of m->xattn models, wired as launch_cross_attn + cross_attn_merge wire it: absorb, X sweep, merge.
+extern "C" int wm_op_xattn(float* out, const float* q, const float* Wk, const float* Wv, const float* bv, const float* X, int rows,
+                           int q_B, int n_utt, int n_keys, int n_heads, int nsplit, int out_dtype) {
+    if (!out || !q || !Wk || !Wv || !bv || !X || rows <= 0 || n_utt <= 0 || n_keys <= 0) return fail(WM_E_ARG, "bad argument");
+    if (n_heads < 1 || n_heads > 8 || nsplit < 1 || nsplit > 64) return fail(WM_E_ARG, "needs 1 <= n_heads <= 8, 1 <= nsplit <= 64");
+    if (out_dtype != WM_F32 && out_dtype != WM_BF16) return fail(WM_E_ARG, "out_dtype must be WM_F32 or WM_BF16");
+    if (q_B < 0 || (q_B > 0 ? (q_B > n_utt || rows % q_B) : rows > n_utt))
+        return fail(WM_E_ARG, "rows must be P * q_B with q_B <= n_utt (prefill), or <= n_utt (q_B == 0)");
+    const size_t d = (size_t)n_heads * 64;
+    TmpDev t;
+    t.bufs.reserve(12);
+    hipStream_t st = nullptr;
+    DevBuf &dq = t.add(), &wk = t.add(), &wv = t.add(), &b = t.add(), &dx = t.add(), &qs = t.add(), &py = t.add(), &pml = t.add(),
+           &o = t.add();
+    WMCHK(upload(dq, q, (size_t)rows * d, WM_F32));
+    WMCHK(upload(wk, Wk, d * d, WM_BF16));
+    WMCHK(upload(wv, Wv, d * d, WM_BF16));
+    WMCHK(upload(b, bv, d, WM_F32));
+    WMCHK(upload(dx, X, (size_t)n_utt * n_keys * d, WM_BF16));
+    WMCHK(qs.alloc((size_t)rows * 3 * n_heads * d * 2, true));
+    WMCHK(py.alloc((size_t)rows * nsplit * n_heads * d * 4, true));
+    WMCHK(pml.alloc((size_t)rows * nsplit * n_heads * 2 * 4, true));
+    WMCHK(o.alloc((size_t)rows * d * dt_size(out_dtype), true));
+    XAttnParams x{};
+    x.q = dq.as<float>();
+    x.Wk = wk.p;
+    x.Wv = wv.p;
+    x.bv = b.as<float>();
+    x.X = dx.p;
+    x.x_stride = (long)((size_t)n_keys * d);
+    x.n_keys = n_keys;
+    x.nsplit = nsplit;
+    x.H = n_heads;
+    x.d = (int)d;
+    x.rows = rows;
+    x.q_B = q_B;
+    x.scale = 1.0f / sqrtf(64.0f);
+    x.qs = qs.p;
+    x.part_y = py.as<float>();
+    x.part_ml = pml.as<float>();
+    x.out = o.p;
+    x.out_dtype = out_dtype;
+    LCHK(launch_xattn_absorb(x, st));
+    LCHK(launch_xattn(x, st));
+    LCHK(launch_xattn_merge(x, st));
+    HIPCHK(hipGetLastError());
+    const size_t n = (size_t)rows * d;
+    std::vector<unsigned char> h(n * dt_size(out_dtype));
+    HIPCHK(hipMemcpy(h.data(), o.p, h.size(), hipMemcpyDeviceToHost));
+    widen_to_f32(h.data(), out_dtype, n, out);
+    return 0;
+}
+
 extern "C" int wm_op_gelu(float* tt, size_t n, int mode) {
     if (!tt || (mode != 0 && mode != 1)) return fail(WM_E_ARG, "bad argument");
     if (n == 0) return 0;

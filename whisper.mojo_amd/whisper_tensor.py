@@ -129,3 +129,42 @@ def argmax(t) -> int:
     idx = C.c_int32(0)
     _lib.check(_lib.lib().wm_op_argmax(_fp(x), x.size, C.byref(idx)))
     return int(idx.value)
+
+
+def logits_argmax(x, ln_g, ln_b, emb, dtype=DT_F32, mask=None, ranges=None, timestamp_begin: int = 0):
+    """whisper.mojo:156-166 + the greedy argmax: (logits [B, N] = layer_norm(x)·embᵀ, ids [B]) on the decode step's logits kernel
+    and fused argmax.  mask [N] additive (0 / -inf) on the argmax candidates; ranges [B, 4] = (text_lo, text_hi, ts_lo, ts_hi)
+    with timestamp_begin > 0: the timestamp decision (wm_op_logits)."""
+    f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    x, emb, mask = f(x), f(emb), f(mask)
+    g, b = f(ln_g).ravel(), f(ln_b).ravel()
+    if x.ndim != 2 or emb.ndim != 2 or emb.shape[1] != x.shape[1] or g.size != x.shape[1] or b.size != x.shape[1]:
+        raise ValueError("x must be [B, K], emb [N, K], ln_g / ln_b [K]")
+    B, K = x.shape
+    N = emb.shape[0]
+    if mask is not None and mask.size != N:
+        raise ValueError("mask must have N elements")
+    rg = None
+    if ranges is not None:
+        rg = np.ascontiguousarray(ranges, np.int32)
+        if rg.shape != (B, 4):
+            raise ValueError("ranges must be [B, 4]")
+    logits = np.zeros((B, N), np.float32)
+    ids = np.zeros(B, np.int32)
+    ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    _lib.check(_lib.lib().wm_op_logits(_fp(logits), ip(ids), _fp(x), _fp(g), _fp(b), _fp(emb), _fp(mask.ravel() if mask is not None else None),
+                                       ip(rg), int(timestamp_begin), B, N, K, dtype))
+    return logits, ids
+
+
+def xattn(out: np.ndarray, q, Wk, Wv, bv, x, n_heads: int, nsplit: int, q_B: int = 0, out_dtype=DT_F32):
+    """The absorbed cross-attention (wm_op_xattn): q [rows, d], Wk / Wv [d, d], bv [d], x [n_utt, n_keys, d], d = 64·n_heads;
+    row r attends over x[r % q_B] (q_B > 0, prefill) or x[r] -> out [rows, d]."""
+    f = lambda a: np.ascontiguousarray(a, np.float32)
+    q, Wk, Wv, bv, x = f(q), f(Wk), f(Wv), f(bv).ravel(), f(x)
+    d = 64 * n_heads
+    if q.ndim != 2 or q.shape[1] != d or Wk.shape != (d, d) or Wv.shape != (d, d) or bv.size != d or x.ndim != 3 or x.shape[2] != d:
+        raise ValueError("q must be [rows, 64 * n_heads], Wk / Wv [d, d], bv [d], x [n_utt, n_keys, d]")
+    _chk_out(out, q.shape)
+    _lib.check(_lib.lib().wm_op_xattn(_fp(out), _fp(q), _fp(Wk), _fp(Wv), _fp(bv), _fp(x), q.shape[0], q_B, x.shape[0], x.shape[1],
+                                      n_heads, nsplit, out_dtype))
