@@ -264,9 +264,31 @@ int wm_op_layer_norm(float* out, const float* inp, const float* gamma, const flo
  * q, out [B, 64·n_heads] fp32; k, v [B, t, 64·n_heads] fp32 host rows, rounded to kv_dtype as the cache holds them.
  * n_chunks > 1: the keys of an utterance are swept by n_chunks workgroups and merged (the cross-attention form; needs
  * t/512 <= n_chunks <= t/32 rounded up);  n_chunks == 1: one workgroup per utterance, the key count read from the decode
- * control block (the self-attention form).  Known-answer tests. */
+ * control block (the self-attention form).  out_dtype: element type of the kernels' output (the single-workgroup form's direct
+ * store, the merge's store), returned widened to fp32.  len >= 0 (single-workgroup form): the control block's length — a row sweeps
+ * len + 1 of the t cache rows (len < 0: t - 1, all of them).  q_B > 0: prefill rows, position-major (B = P·q_B; k, v hold q_B
+ * utterances): row p·q_B + b attends over utterance b — len + 1 + p keys in the single-workgroup (causal) form, needs len + P <= t.
+ * nq = 4 (chunked form, B = 4·q_B): one K/V sweep per (utterance, chunk) serves the four positions; else 0.  1 <= n_heads <= 16,
+ * n_chunks <= 64.  Known-answer tests. */
 int wm_op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
-                           int n_chunks);
+                           int n_chunks, int out_dtype, int q_B, int len, int nq);
+/* One launch of the decode step's skinny linear, out[B, N] = epi(pro(x)[B, K]·W[N, K]ᵀ + bias), wired as a decode step wires its six
+ * per-layer launches.  W is rounded to dtype on upload.  pro: ln_g / ln_b [K] non-NULL: LayerNorm (eps 1e-5) of the fp32 rows x;
+ * x_is_t != 0 (no LayerNorm): x is uploaded in dtype, as the producer kernel leaves it.  epi: + bias [N] (or NULL); act != 0: GELU
+ * (gelu_mode); + residual [B, N] (or NULL; residual == out: in place, out holds the residual on entry); out_is_t != 0 (no residual,
+ * no cache): the kernel stores dtype, returned widened.
+ * QKV mode (kcache, vcache non-NULL; N = 3·d): out is [B, d] (q); columns [d, 2d) / [2d, 3d) are appended to kcache / vcache
+ * [n_utt][cap_rows][d] — uploaded in kv_dtype from the caller's values, returned after the launch — at row len of utterance r
+ * (kv_B == 0, B <= n_utt), or, kv_B > 0 (prefill, B = P·kv_B position-major rows, len + P <= cap_rows), row len + r / kv_B of
+ * utterance r % kv_B.
+ * Capture (cap non-NULL, no cache; N = 64·heads): cap [B][cap_steps][cap_nsel][64], caller-initialised and returned; the 64 output
+ * columns of every head h with cap_sel[h] >= 0 (cap_sel [32], values < cap_nsel) also go to cap[r][len - cap_step0][cap_sel[h]] when
+ * 0 <= len - cap_step0 < cap_steps.
+ * K must split over the kernel's waves (a multiple of 32, K/32 = waves·steps with waves <= 16, steps <= 4).  Known-answer tests. */
+int wm_op_dec_linear(float* out, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
+                     const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
+                     float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
+                     const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel);
 /* The decode step's final LayerNorm + tied-embedding logits and fused argmax (whisper.mojo:156-166, whisper_tensor.mojo:431-439):
  * logits[B, N] = layer_norm(x, ln_g, ln_b, 1e-5)·emb[N, K]ᵀ on the decode step's logits kernel, emb rounded to dtype on upload (the
  * kernel variant follows from dtype, K and B as in a decode step), and ids[B] = the fused argmax of those logits (stage 1 in the

@@ -89,3 +89,22 @@ def test_op_wrappers_validate_shapes_before_calling_the_library():
         wt.attention_cached(np.zeros_like(q), q, q, q, 2)
     with pytest.raises(ValueError):  # another batch size in the cache
         wt.attention_cached(np.zeros_like(q), q, np.zeros((9, 5, 128), np.float32), np.zeros((9, 5, 128), np.float32), 2)
+    with pytest.raises(ValueError):  # prefill rows: k holds q_B utterances, not one per row
+        wt.attention_cached(np.zeros_like(q), q, np.zeros((10, 5, 128), np.float32), np.zeros((10, 5, 128), np.float32), 2, q_B=5, len=0)
+    with pytest.raises(ValueError):  # prefill rows are P * q_B
+        wt.attention_cached(np.zeros_like(q), q, np.zeros((3, 5, 128), np.float32), np.zeros((3, 5, 128), np.float32), 2, q_B=3, len=0)
+    W = np.zeros((384, 128), np.float32)
+    with pytest.raises(ValueError):  # W must be [N, K]
+        wt.dec_linear(x, np.zeros((384, 64), np.float32))
+    with pytest.raises(ValueError):  # bias of another width
+        wt.dec_linear(x, W, bias=np.zeros(128, np.float32))
+    with pytest.raises(ValueError):  # LayerNorm gamma / beta have K elements
+        wt.dec_linear(x, W, ln=(np.ones(384, np.float32), np.zeros(384, np.float32)))
+    with pytest.raises(ValueError):  # residual must be [B, N]
+        wt.dec_linear(x, W, residual=np.zeros((4, 128), np.float32))
+    with pytest.raises(ValueError):  # QKV mode: the caches are [n_utt, cap_rows, N / 3]
+        wt.dec_linear(x, W, kv=(np.zeros((4, 8, 384), np.float32), np.zeros((4, 8, 384), np.float32)))
+    with pytest.raises(ValueError):  # capture: one row per activation row, 64 columns per head, 32 selectors
+        wt.dec_linear(x, W[:128], cap=np.zeros((3, 2, 1, 64), np.float32), cap_sel=np.full(32, -1, np.int8))
+    with pytest.raises(ValueError):
+        wt.dec_linear(x, W[:128], cap=np.zeros((4, 2, 1, 64), np.float32), cap_sel=np.full(16, -1, np.int8))

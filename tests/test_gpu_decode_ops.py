@@ -1,5 +1,6 @@
-"""Op-level tests (-m gpu) of the two decoder kernel families that run on every decode step, against float64 on the operands
-exactly as the kernels receive them:
+"""Op-level tests (-m gpu) of two of the four decoder kernel families that run on every decode step, against float64 on the
+operands exactly as the kernels receive them (the other two — the per-layer skinny linears and the cached attention — are in
+tests/test_gpu_decode_layer.py):
 
   * the final LayerNorm + tied-embedding logits with the fused argmax (wm_op_logits: launch_dec_logits + argmax_step), over every
     kernel variant the release dispatch reaches, ties and masks at the reduction boundaries, and the timestamp decision;
@@ -47,13 +48,14 @@ def _ln64(x, g, b):
     return (x - mean) / np.sqrt(var + 1e-5) * g.astype(np.float64) + b.astype(np.float64)
 
 
-def _ln_err(x, g, b):
+def _ln_err(x, g, b, n=None):
     """First-order bound on |fp32 LayerNorm - float64 LayerNorm| per element, for the logits kernels' fp32 LayerNorm: each of 8
     threads per row sums K/8 elements (and their squares) in sequence, three butterfly adds join them (γ_n, n = K/8 + 3); then
-    mean = s/K, var = q/K - mean², rstd = 1/sqrtf(var + eps), y = ((x - mean)·rstd)·g + b, every operation rounded once."""
+    mean = s/K, var = q/K - mean², rstd = 1/sqrtf(var + eps), y = ((x - mean)·rstd)·g + b, every operation rounded once.
+    n: the summation depth of another kernel's statistics (default: the logits kernels')."""
     x = x.astype(np.float64)
     K = x.shape[1]
-    gam = (K // 8 + 3) * U
+    gam = (K // 8 + 3 if n is None else n) * U
     mu = x.mean(1, keepdims=True)
     m2 = (x * x).mean(1, keepdims=True)
     var = m2 - mu * mu

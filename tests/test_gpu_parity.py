@@ -261,17 +261,31 @@ def test_op_attention_fp32(hip):
         assert np.abs(out - ref).max() < 2e-5 * max(1.0, np.abs(ref).max())
 
 
-def _attention_cached_ref(q, k, v, n_heads, rnd):
-    """layers.mojo:186-272 in float64: per utterance and head s_j = (q·K_j)·0.125, softmax over the cached rows, o = Σ p_j V_j."""
+def _attention_cached_ref(q, k, v, n_heads, rnd=None, counts=None, q_B=0):
+    """layers.mojo:186-272 in float64: per utterance and head s_j = (q·K_j)·0.125, softmax over the cached rows, o = Σ p_j V_j.
+    rnd: the cache's rounding of k, v (None: they already hold the cache's values).  counts / q_B (tests/test_gpu_decode_layer.py):
+    row r attends over the first counts[r] rows (None: all) of utterance r % q_B (q_B > 0: position-major prefill rows) or r."""
     q = q.astype(np.float64)
-    k, v = rnd(k).astype(np.float64), rnd(v).astype(np.float64)
+    if rnd is not None:
+        k, v = rnd(k), rnd(v)
     out = np.empty_like(q)
-    for h in range(n_heads):
-        sl = slice(64 * h, 64 * h + 64)
-        s_ = np.einsum("bd,btd->bt", q[:, sl], k[:, :, sl]) * 0.125
-        s_ -= s_.max(axis=1, keepdims=True)
-        p = np.exp(s_)
-        out[:, sl] = np.einsum("bt,btd->bd", p / p.sum(axis=1, keepdims=True), v[:, :, sl])
+    if counts is None and q_B == 0:
+        k, v = k.astype(np.float64), v.astype(np.float64)
+        for h in range(n_heads):
+            sl = slice(64 * h, 64 * h + 64)
+            s_ = np.einsum("bd,btd->bt", q[:, sl], k[:, :, sl]) * 0.125
+            s_ -= s_.max(axis=1, keepdims=True)
+            p = np.exp(s_)
+            out[:, sl] = np.einsum("bt,btd->bd", p / p.sum(axis=1, keepdims=True), v[:, :, sl])
+        return out
+    for r in range(q.shape[0]):
+        u = r % q_B if q_B > 0 else r
+        n = k.shape[1] if counts is None else counts[r]
+        for h in range(n_heads):
+            sl = slice(64 * h, 64 * h + 64)
+            s_ = 0.125 * (k[u, :n, sl].astype(np.float64) @ q[r, sl])
+            p = np.exp(s_ - s_.max())
+            out[r, sl] = (p / p.sum()) @ v[u, :n, sl].astype(np.float64)
     return out
 
 

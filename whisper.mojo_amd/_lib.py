@@ -18,7 +18,7 @@ SYMBOLS = [
     "wm_last_error", "wm_abi_version", "wm_model_load", "wm_model_load_memory", "wm_model_free", "wm_weight_count", "wm_weights_convert_v2", "wm_weights_read", "wm_state_new",
     "wm_state_reset", "wm_state_free", "wm_state_len", "wm_encode", "wm_state_set_encoder_output", "wm_decode_step",
     "wm_transcribe", "wm_transcribe_submit", "wm_transcribe_wait", "wm_transcribe_wait_device", "wm_transcribe_steps", "wm_log_mel", "wm_transcribe_pcm", "wm_op_matmul_nt", "wm_op_ln_matmul_nt", "wm_op_mlp_block", "wm_op_attention", "wm_op_attention_cached", "wm_op_layer_norm", "wm_op_gelu", "wm_op_softmax_rows", "wm_op_conv1d_k3",
-    "wm_op_argmax", "wm_op_logits", "wm_op_xattn", "wm_bench_kernel", "wm_bench_bytes", "wm_synth_weights", "wm_synth_mel_host",
+    "wm_op_argmax", "wm_op_logits", "wm_op_xattn", "wm_op_dec_linear", "wm_bench_kernel", "wm_bench_bytes", "wm_synth_weights", "wm_synth_mel_host",
     "wm_set_alignment_heads", "wm_transcribe_tt", "wm_transcribe_submit_tt", "wm_transcribe_wait_tt", "wm_transcribe_pcm_tt",
     "wm_alignment_weights", "wm_op_token_times",
     "wm_log_mel_long", "wm_transcribe_long", "wm_transcribe_long_pcm", "wm_long_result_sizes", "wm_long_result_get",
@@ -110,7 +110,8 @@ def lib():
     L.wm_op_mlp_block.argtypes = [fp] * 10 + [C.c_int] * 5
     L.wm_op_ln_matmul_nt.argtypes = [fp] * 6 + [C.c_int] * 5
     L.wm_op_attention.argtypes = [fp] * 4 + [C.c_int] * 3
-    L.wm_op_attention_cached.argtypes = [fp] * 4 + [C.c_int] * 5
+    L.wm_op_attention_cached.argtypes = [fp] * 4 + [C.c_int] * 9
+    L.wm_op_dec_linear.argtypes = [fp] * 7 + [C.c_int] * 8 + [fp, fp] + [C.c_int] * 5 + [fp, C.POINTER(C.c_int8)] + [C.c_int] * 3
     L.wm_op_layer_norm.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_float]
     L.wm_op_gelu.argtypes = [fp, C.c_size_t, C.c_int]
     L.wm_op_softmax_rows.argtypes = [fp, C.c_int, C.c_int]

@@ -3244,20 +3244,28 @@ extern "C" int wm_op_attention(float* out, const float* q, const float* k, const
 }
 
 extern "C" int wm_op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
-                                      int n_chunks) {
+                                      int n_chunks, int out_dtype, int q_B, int len, int nq) {
     if (!out || !q || !k || !v || B <= 0 || t <= 0 || n_heads <= 0 || n_heads > 16) return fail(WM_E_ARG, "bad argument");
-    if (kv_dtype < 0 || kv_dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    if (kv_dtype < 0 || kv_dtype > 2 || out_dtype < 0 || out_dtype > 2) return fail(WM_E_ARG, "bad dtype");
     if (n_chunks < 1 || (n_chunks > 1 && (n_chunks < (t + 511) / 512 || n_chunks > (t + 31) / 32)))
         return fail(WM_E_ARG, "n_chunks must be 1, or between ceil(t/512) and ceil(t/32)");
     if (n_chunks == 1 && t > 512) return fail(WM_E_ARG, "the single-workgroup form serves up to 512 keys (the text context)");
-    const size_t d = (size_t)n_heads * 64;
+    if (n_chunks > 64) return fail(WM_E_ARG, "the merge takes up to 64 chunks");
+    if (q_B < 0 || (q_B > 0 && B % q_B)) return fail(WM_E_ARG, "prefill rows are position-major: B must be P * q_B");
+    if (nq != 0 && (nq != 4 || n_chunks == 1 || q_B == 0 || B != 4 * q_B))
+        return fail(WM_E_ARG, "nq must be 0, or 4 with the chunked form and B = 4 * q_B rows");
+    const int P = q_B > 0 ? B / q_B : 1, n_utt = q_B > 0 ? q_B : B;  // k, v hold n_utt utterances of t rows
+    if (n_chunks > 1 && len >= 0) return fail(WM_E_ARG, "len belongs to the single-workgroup form (the chunked form sweeps all t rows)");
+    if (n_chunks == 1 && len < 0 && P > 1) return fail(WM_E_ARG, "the causal prefill form needs len >= 0");
+    if (n_chunks == 1 && len >= 0 && len + P > t) return fail(WM_E_ARG, "the cache must hold len + P rows");
+    const size_t d = (size_t)n_heads * 64, n = (size_t)B * d;
     TmpDev tmp;
     tmp.bufs.reserve(8);
     DevBuf &dq = tmp.add(), &dk = tmp.add(), &dv = tmp.add(), &po = tmp.add(), &pml = tmp.add(), &o = tmp.add(), &ctl = tmp.add();
-    WMCHK(upload(dq, q, (size_t)B * d, WM_F32));
-    WMCHK(upload(dk, k, (size_t)B * t * d, kv_dtype));
-    WMCHK(upload(dv, v, (size_t)B * t * d, kv_dtype));
-    WMCHK(o.alloc((size_t)B * d * 4, true));
+    WMCHK(upload(dq, q, n, WM_F32));
+    WMCHK(upload(dk, k, (size_t)n_utt * t * d, kv_dtype));
+    WMCHK(upload(dv, v, (size_t)n_utt * t * d, kv_dtype));
+    WMCHK(o.alloc(n * dt_size(out_dtype), true));
     AttnDecParams a{};
     a.q = dq.as<float>();
     a.K = dk.p;
@@ -3267,6 +3275,8 @@ extern "C" int wm_op_attention_cached(float* out, const float* q, const float* k
     a.H = n_heads;
     a.d = (int)d;
     a.B = B;
+    a.q_B = q_B;
+    a.nq = nq;
     if (n_chunks > 1) {
         WMCHK(po.alloc((size_t)B * n_chunks * d * 4, true));
         WMCHK(pml.alloc((size_t)B * n_chunks * n_heads * 2 * 4, true));
@@ -3275,21 +3285,137 @@ extern "C" int wm_op_attention_cached(float* out, const float* q, const float* k
         a.part_o = po.as<float>();
         a.part_ml = pml.as<float>();
         WMCHK(attn_decode_dispatch(kv_dtype, a, nullptr));
-        launch_attn_combine(po.as<float>(), pml.as<float>(), o.p, WM_F32, B, n_chunks, n_heads, (int)d, nullptr);
+        launch_attn_combine(po.as<float>(), pml.as<float>(), o.p, out_dtype, B, n_chunks, n_heads, (int)d, nullptr);
     } else {
         StepCtl h{};
-        h.len = t - 1;  // the kernel sweeps len + 1 rows: the cache as it stands after this step's row was appended
+        // the kernel sweeps len + 1 rows (position p of a prefill: len + 1 + p): the cache as it stands after this step's row was appended
+        h.len = len >= 0 ? len : t - 1;
         WMCHK(ctl.alloc(sizeof(StepCtl)));
         HIPCHK(hipMemcpy(ctl.p, &h, sizeof h, hipMemcpyHostToDevice));
         a.n_keys = -1;
         a.ctl = ctl.as<StepCtl>();
         a.nsplit = 1;
         a.direct_out = o.as<float>();
-        a.out_dtype = WM_F32;
+        a.out_dtype = out_dtype;
         WMCHK(attn_decode_dispatch(kv_dtype, a, nullptr));
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out, o.p, (size_t)B * d * 4, hipMemcpyDeviceToHost));
+    std::vector<unsigned char> h(n * dt_size(out_dtype));
+    HIPCHK(hipMemcpy(h.data(), o.p, h.size(), hipMemcpyDeviceToHost));
+    widen_to_f32(h.data(), out_dtype, n, out);
+    return 0;
+}
+
+// One launch_dec_linear as decode_core wires it: LN1 -> QKV with the cache append, the XT out-projections with the residual in place,
+// LNx -> cross q with the alignment-head capture, LN2 -> fc1 + GELU stored in operand dtype, fc2.
+extern "C" int wm_op_dec_linear(float* out, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
+                                const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
+                                float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
+                                const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel) {
+    if (!out || !x || !W || B <= 0 || N <= 0 || K <= 0) return fail(WM_E_ARG, "bad argument");
+    if (dtype < 0 || dtype > 2 || (gelu_mode != 0 && gelu_mode != 1)) return fail(WM_E_ARG, "bad dtype / gelu_mode");
+    if (!dec_linear_supports_k(K)) return fail(WM_E_ARG, "K must be a multiple of 32 whose k-steps split over <= 16 waves x <= 4 steps (K <= 2048)");
+    if (!ln_g != !ln_b) return fail(WM_E_ARG, "ln_g and ln_b go together");
+    if (ln_g && x_is_t) return fail(WM_E_ARG, "the LayerNorm prologue reads fp32 rows (no x_is_t)");
+    if (!kcache != !vcache) return fail(WM_E_ARG, "kcache and vcache go together");
+    if (out_is_t && (residual || kcache)) return fail(WM_E_ARG, "out_is_t is the plain store (no residual, no cache append)");
+    const int d = N / 3;
+    if (kcache) {
+        if (N % 3 || d % 64 || kv_dtype < 0 || kv_dtype > 2 || n_utt <= 0 || cap_rows <= 0 || len < 0)
+            return fail(WM_E_ARG, "QKV mode needs N = 3 * d_model (d_model % 64 == 0), a kv_dtype and a cache [n_utt][cap_rows][d_model]");
+        if (residual) return fail(WM_E_ARG, "QKV mode has no residual");
+        if (kv_B < 0 || (kv_B > 0 ? (kv_B > n_utt || B % kv_B || len + B / kv_B > cap_rows) : (B > n_utt || len + 1 > cap_rows)))
+            return fail(WM_E_ARG, "rows must be P * kv_B with kv_B <= n_utt and len + P <= cap_rows, or <= n_utt with len < cap_rows");
+    }
+    if (cap) {
+        if (!cap_sel || len < 0 || cap_steps <= 0 || cap_nsel <= 0 || cap_nsel > 32 || N % 64 || N > 2048 || (kcache && cap))
+            return fail(WM_E_ARG, "capture needs cap_sel, len >= 0, N = 64 * heads <= 2048, 1 <= cap_nsel <= 32, cap_steps > 0 (and no cache)");
+        for (int h = 0; h < 32; ++h)
+            if (cap_sel[h] >= cap_nsel || (cap_sel[h] >= 0 && h >= N / 64)) return fail(WM_E_ARG, "cap_sel names a slot >= cap_nsel or a head >= N / 64");
+    }
+    TmpDev t;
+    t.bufs.reserve(12);
+    hipStream_t st = nullptr;
+    // the kernel stores whole 16-column tiles (and loads the residual the same way): rows padded to 16 columns
+    const int wout = kcache ? d : N, ldo = (wout + 15) / 16 * 16;
+    const int odt = out_is_t ? dtype : WM_F32;
+    const size_t ncache = kcache ? (size_t)n_utt * cap_rows * d : 0, ncap = cap ? (size_t)B * cap_steps * cap_nsel * 64 : 0;
+    DevBuf &dx = t.add(), &w = t.add(), &b = t.add(), &g = t.add(), &be = t.add(), &o = t.add(), &r = t.add(), &kc = t.add(), &vc = t.add(),
+           &ctl = t.add(), &cp = t.add();
+    WMCHK(upload(dx, x, (size_t)B * K, x_is_t ? dtype : WM_F32));
+    WMCHK(upload(w, W, (size_t)N * K, dtype));
+    if (bias) WMCHK(upload(b, bias, N, WM_F32));
+    if (ln_g) {
+        WMCHK(upload(g, ln_g, K, WM_F32));
+        WMCHK(upload(be, ln_b, K, WM_F32));
+    }
+    WMCHK(o.alloc((size_t)B * ldo * dt_size(odt), true));
+    const bool in_place = residual == out;
+    if (residual) {
+        DevBuf& dst = in_place ? o : r;
+        if (!in_place) WMCHK(r.alloc((size_t)B * ldo * 4, true));
+        HIPCHK(hipMemcpy2D(dst.p, (size_t)ldo * 4, residual, (size_t)N * 4, (size_t)N * 4, B, hipMemcpyHostToDevice));
+    }
+    DecLinearParams p{};
+    p.x = dx.as<float>();
+    p.ldx = K;
+    p.x_is_t = x_is_t;
+    p.out_is_t = out_is_t;
+    p.ln_g = ln_g ? g.as<float>() : nullptr;
+    p.ln_b = ln_g ? be.as<float>() : nullptr;
+    p.W = w.p;
+    p.N = N;
+    p.K = K;
+    p.B = B;
+    p.bias = bias ? b.as<float>() : nullptr;
+    p.act = act != 0;
+    p.gelu_mode = gelu_mode;
+    p.residual = residual ? (in_place ? o.as<float>() : r.as<float>()) : nullptr;
+    p.ldr = ldo;
+    p.out = o.as<float>();
+    p.ldo = ldo;
+    if (kcache || cap) {
+        StepCtl h{};
+        h.len = len;
+        WMCHK(ctl.alloc(sizeof(StepCtl)));
+        HIPCHK(hipMemcpy(ctl.p, &h, sizeof h, hipMemcpyHostToDevice));
+        p.ctl = ctl.as<StepCtl>();
+    }
+    if (kcache) {
+        WMCHK(upload(kc, kcache, ncache, kv_dtype));
+        WMCHK(upload(vc, vcache, ncache, kv_dtype));
+        p.kcache = kc.p;
+        p.vcache = vc.p;
+        p.kv_batch_stride = (long)((size_t)cap_rows * d);
+        p.d_model = d;
+        p.kv_dtype = kv_dtype;
+        p.kv_B = kv_B;
+    }
+    if (cap) {
+        WMCHK(upload(cp, cap, ncap, WM_F32));
+        p.cap = cp.as<float>();
+        p.cap_row_stride = (long)cap_steps * cap_nsel * 64;
+        p.cap_step0 = cap_step0;
+        p.cap_steps = cap_steps;
+        p.cap_nsel = cap_nsel;
+        memcpy(p.cap_sel, cap_sel, 32);
+    }
+    WMCHK(dec_linear_dispatch(dtype, p, st));
+    HIPCHK(hipGetLastError());
+    {
+        const size_t es = dt_size(odt);
+        std::vector<unsigned char> h((size_t)B * wout * es);
+        HIPCHK(hipMemcpy2D(h.data(), (size_t)wout * es, o.p, (size_t)ldo * es, (size_t)wout * es, B, hipMemcpyDeviceToHost));
+        widen_to_f32(h.data(), odt, (size_t)B * wout, out);
+    }
+    if (kcache) {
+        std::vector<unsigned char> h(ncache * dt_size(kv_dtype));
+        HIPCHK(hipMemcpy(h.data(), kc.p, h.size(), hipMemcpyDeviceToHost));
+        widen_to_f32(h.data(), kv_dtype, ncache, kcache);
+        HIPCHK(hipMemcpy(h.data(), vc.p, h.size(), hipMemcpyDeviceToHost));
+        widen_to_f32(h.data(), kv_dtype, ncache, vcache);
+    }
+    if (cap) HIPCHK(hipMemcpy(cap, cp.p, ncap * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

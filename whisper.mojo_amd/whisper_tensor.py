@@ -77,16 +77,79 @@ def attention(out: np.ndarray, q, k, v, n_heads: int, dtype=DT_F32):
     _lib.check(_lib.lib().wm_op_attention(_fp(out), _fp(q), _fp(k), _fp(v), n_ctx, n_heads, dtype))
 
 
-def attention_cached(out: np.ndarray, q, k, v, n_heads: int, kv_dtype=DT_F32, n_chunks: int = 1):
+def attention_cached(out: np.ndarray, q, k, v, n_heads: int, kv_dtype=DT_F32, n_chunks: int = 1, out_dtype=DT_F32, q_B: int = 0,
+                     len: int = -1, nq: int = 0):
     """layers.mojo:186-272, the q_len == 1 path over cached rows: q [B, d], k / v [B, t, d] -> out [B, d].
-    n_chunks > 1: the cross-attention form (keys swept by several workgroups and merged)."""
+    n_chunks > 1: the cross-attention form (keys swept by several workgroups and merged).  out_dtype: what the kernels store
+    (returned widened).  len >= 0 (n_chunks == 1): a row sweeps len + 1 of the t rows.  q_B > 0: prefill, q [P·q_B, d] position-major,
+    k / v [q_B, t, d]: row p·q_B + b attends over utterance b (n_chunks == 1: its first len + 1 + p rows).  nq = 4: the chunked
+    prefill form that serves four positions from one sweep."""
     f = lambda a: np.ascontiguousarray(a, np.float32)
     q, k, v = f(q), f(k), f(v)
     B, d = q.shape
-    if d != 64 * n_heads or k.ndim != 3 or k.shape[0] != B or k.shape[2] != d or v.shape != k.shape:
-        raise ValueError("q must be [B, 64 * n_heads], k and v [B, t, 64 * n_heads]")
+    n_utt = q_B if q_B > 0 else B
+    if d != 64 * n_heads or k.ndim != 3 or k.shape[0] != n_utt or k.shape[2] != d or v.shape != k.shape:
+        raise ValueError("q must be [B, 64 * n_heads], k and v [B (or q_B), t, 64 * n_heads]")
+    if q_B > 0 and B % q_B:
+        raise ValueError("prefill rows are position-major: q must be [P * q_B, d]")
     _chk_out(out, q.shape)
-    _lib.check(_lib.lib().wm_op_attention_cached(_fp(out), _fp(q), _fp(k), _fp(v), B, k.shape[1], n_heads, kv_dtype, n_chunks))
+    _lib.check(_lib.lib().wm_op_attention_cached(_fp(out), _fp(q), _fp(k), _fp(v), B, k.shape[1], n_heads, kv_dtype, n_chunks, out_dtype,
+                                                 q_B, len, nq))
+
+
+def dec_linear(x, W, bias=None, ln=None, residual=None, in_place: bool = False, dtype=DT_F32, x_is_t: bool = False, out_is_t: bool = False,
+               act: bool = False, gelu_mode: int = GELU_TANH, kv=None, kv_dtype=DT_F32, kv_B: int = 0, len: int = 0, cap=None,
+               cap_sel=None, cap_step0: int = 0):
+    """One launch of the decode step's skinny linear (wm_op_dec_linear): epi(pro(x)·Wᵀ + bias) -> out [B, N] fp32.
+    ln = (gamma, beta): LayerNorm prologue; x_is_t: x goes up in operand dtype; act: GELU; residual [B, N] is added (in_place: through
+    the aliasing form, out = residual buffer); out_is_t: the kernel stores operand dtype.  kv = (kcache, vcache) [n_utt, cap_rows, d]
+    with N = 3·d: QKV mode, returns (q [B, d], kcache, vcache) — the caches as they stand after the append at row len (kv_B > 0:
+    prefill rows, position-major).  cap [B, cap_steps, cap_nsel, 64] with cap_sel [32]: alignment-head capture, returns (out, cap)."""
+    f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    x, W, bias, residual = f(x), f(W), f(bias), f(residual)
+    if x.ndim != 2 or W.ndim != 2 or W.shape[1] != x.shape[1]:
+        raise ValueError("x must be [B, K] and W [N, K]")
+    B, K = x.shape
+    N = W.shape[0]
+    if bias is not None and bias.size != N:
+        raise ValueError("bias must have N elements")
+    g = b = None
+    if ln is not None:
+        g, b = f(ln[0]).ravel(), f(ln[1]).ravel()
+        if g.size != K or b.size != K:
+            raise ValueError("ln gamma / beta must have K elements")
+    if residual is not None and residual.shape != (B, N):
+        raise ValueError("residual must be [B, N]")
+    kc = vc = None
+    n_utt = cap_rows = 0
+    wout = N
+    if kv is not None:
+        kc, vc = f(kv[0]).copy(), f(kv[1]).copy()
+        if N % 3 or kc.ndim != 3 or kc.shape[2] != N // 3 or vc.shape != kc.shape:
+            raise ValueError("QKV mode: W must be [3 * d, K] and kcache / vcache [n_utt, cap_rows, d]")
+        n_utt, cap_rows, wout = kc.shape
+    cp = sel = None
+    steps = nsel = 0
+    if cap is not None:
+        cp = f(cap).copy()
+        sel = np.ascontiguousarray(cap_sel, np.int8)
+        if cp.ndim != 4 or cp.shape[0] != B or cp.shape[3] != 64 or sel.shape != (32,):
+            raise ValueError("cap must be [B, cap_steps, cap_nsel, 64] and cap_sel [32]")
+        steps, nsel = cp.shape[1], cp.shape[2]
+    out = np.zeros((B, wout), np.float32)
+    res = residual
+    if residual is not None and in_place:
+        out[:] = residual
+        res = out
+    _lib.check(_lib.lib().wm_op_dec_linear(_fp(out), _fp(x), _fp(W), _fp(bias), _fp(g), _fp(b), _fp(res), B, N, K, dtype, int(x_is_t),
+                                           int(out_is_t), int(act), gelu_mode, _fp(kc), _fp(vc), n_utt, cap_rows, kv_dtype, kv_B, len,
+                                           _fp(cp), None if sel is None else sel.ctypes.data_as(C.POINTER(C.c_int8)), cap_step0, steps,
+                                           nsel))
+    if kv is not None:
+        return out, kc, vc
+    if cap is not None:
+        return out, cp
+    return out
 
 
 def layer_norm(out: np.ndarray, inp, gamma, beta, eps: float = 1e-5):
