@@ -159,6 +159,21 @@ int wm_transcribe_wait_device(wm_model* m, int slot, int32_t* dev_packed, int ro
  * the pass ran to its bound, less when the early exit cut it.  -1: no pass yet / bad slot.  Diagnostics and tests. */
 int wm_transcribe_steps(wm_model* m, int slot);
 
+/* ---- per-row prompts -------------------------------------------------------------------------------------------
+ * wm_transcribe / wm_transcribe_submit with a decoder prompt that differs from row to row, in content and in length: row b decodes
+ * exactly as if it were decoded alone with its own prompt (HF generate's left-padded batch with decoder_attention_mask).
+ * prompts: host [B][prompt_stride], row b holds prompt_len[b] ids; opts->prompt / n_prompt are ignored.  With Lmax the longest
+ * prompt_len: tokens_out host [B][Lmax + 1 + max_loop], row b = its own prompt (unpadded) + generated ids; n_tokens[b] its length.
+ * The timestamp rules and the suppress masks start at the first generated id as always.  The prefill runs in chunks of 16
+ * positions.  WM_E_ARG, nothing launched: prompt_len[b] < 1 or > prompt_stride, an id outside the vocabulary,
+ * Lmax + 1 + max_loop > n_text_ctx.  Not supported: per-row prompts with token timestamps (there is no _tt form), pairing under
+ * coalesce = 2 (such a submit always runs alone), multi-lane decode states (WM_E_ARG, also up front).  Collected with wm_transcribe_wait (out
+ * stride Lmax + 1 + max_loop). */
+int wm_transcribe_rows(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* opts, const int32_t* prompts,
+                       const int32_t* prompt_len, int prompt_stride, int32_t* tokens_out, int32_t* n_tokens);
+int wm_transcribe_submit_rows(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* opts,
+                              const int32_t* prompts, const int32_t* prompt_len, int prompt_stride);
+
 /* ---- token-level timestamps ---------------------------------------------------------------------------------
  * When each id was spoken, with the semantics of HF generate(..., return_token_timestamps=True)
  * (WhisperGenerationMixin._extract_token_timestamps, time_precision 0.02, median_filter_width 7, num_input_ids = n_prompt): the
@@ -200,7 +215,7 @@ int wm_transcribe_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, i
 
 /* ---- sequential long-form transcription ------------------------------------------------------------------
  * Audio of any length, with the semantics of HF WhisperGenerationMixin.generate on its long-form path (greedy,
- * condition_on_prev_tokens=False, no prompt_ids, no temperature fallback / no-speech / log-prob / compression thresholds,
+ * condition_on_prev_tokens and prompt_ids through the _ex forms below, no temperature fallback / no-speech / log-prob / compression thresholds,
  * return_timestamps=True, return_segments=True): per utterance seek = 0; while seek < n_frames[b] the window
  * mel[:, seek : seek + min(n_frames[b] - seek, 2·n_audio_ctx)] zero-padded to 2·n_audio_ctx is decoded with opts (prompt as the
  * initial ids, timestamp rules from the first generated id), the trailing eot is dropped, the ids are split into segments at
@@ -232,12 +247,37 @@ int wm_transcribe_long(wm_model* m, const float* mel, int mel_on_device, int B, 
 /* wm_log_mel_long + wm_transcribe_long without the mel leaving the GPU */
 int wm_transcribe_long_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* opts,
                            wm_long_result** out);
+/* Long-form with HF's condition_on_prev_tokens / prompt_ids / prompt_condition_type.  Every window's decoder prompt is
+ * what HF's _prepare_decoder_input_ids builds for that utterance alone (= wm_op_long_prompt): with conditioning, <|startofprev|> (or,
+ * all-segments, the whole prompt_ids) + the last n_text_ctx / 2 - 1 ids of the utterance's segments so far (a segment of more than
+ * two ids that ends in a timestamp pair loses its last id) + opts->prompt; first-segment: prompt_ids without its leading
+ * <|startofprev|> counts as a segment before the first window and never appears in the result; prompt_ids without conditioning:
+ * prompt_ids + opts->prompt for every window.  Passes whose rows all carry opts->prompt run as wm_transcribe_long's do, the others as
+ * per-row passes.  NULL / zero wm_long_opts = wm_transcribe_long.  Checked before the first window (WM_E_ARG): the longest possible
+ * prompt + 1 + max_loop <= n_text_ctx, n_prompt_ids <= n_text_ctx / 2, ids in range, all-segments without conditioning. */
+typedef struct {
+    int condition_on_prev_tokens;   /* 0 / 1 */
+    int prev_sot_token;             /* <|startofprev|> (50361); required when conditioning or prompt_ids are used */
+    const int32_t* prompt_ids;      /* NULL / 0 = none; as WhisperProcessor.get_prompt_ids returns them */
+    int n_prompt_ids;
+    int prompt_condition_type;      /* 0 first-segment, 1 all-segments (needs condition_on_prev_tokens) */
+} wm_long_opts;
+int wm_transcribe_long_ex(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames, const wm_decode_opts* opts,
+                          const wm_long_opts* lopts, wm_long_result** out);
+int wm_transcribe_long_pcm_ex(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* opts,
+                              const wm_long_opts* lopts, wm_long_result** out);
+/* Host-only, the counterpart of wm_op_long_segments: the decoder prompt of ONE utterance's next window.  seq / segs: the utterance's
+ * segments so far (first, count into seq; n_segs may be 0); init: opts->prompt.  out: room for n_text_ctx ids. */
+int wm_op_long_prompt(const int32_t* seq, const wm_segment* segs, int n_segs, const int32_t* init, int n_init, const wm_long_opts* lopts,
+                      int timestamp_begin, int n_text_ctx, int32_t* out, int32_t* n_out);
 int wm_long_result_sizes(const wm_long_result* r, int b, int32_t* n_tokens, int32_t* n_segments);
 /* tokens: [n_tokens] (may be NULL when 0), segs: [n_segments] */
 int wm_long_result_get(const wm_long_result* r, int b, int32_t* tokens, wm_segment* segs);
 /* windows decoded in all, how many of them did not advance seek (the deviation above), passes run, and rows those passes decoded
  * (passes · R: rows - windows were spare rows) */
 int wm_long_result_stats(const wm_long_result* r, int32_t* windows, int32_t* stalled, int32_t* passes, int32_t* rows);
+/* the longest decoder prompt (ids) any pass of the run carried, and how many of its passes went out as per-row passes */
+int wm_long_result_prompt_stats(const wm_long_result* r, int32_t* longest_prompt, int32_t* row_passes);
 void wm_long_result_free(wm_long_result* r);
 /* Host-only: HF _retrieve_segment on one window's generated ids (eot already dropped).  segs: room for max(1, n) entries;
  * advance: the seek advance in frames exactly as HF computes it (0 in the zero-advance case). */
@@ -272,6 +312,11 @@ int wm_op_layer_norm(float* out, const float* inp, const float* gamma, const flo
  * n_chunks <= 64.  Known-answer tests. */
 int wm_op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
                            int n_chunks, int out_dtype, int q_B, int len, int nq);
+/* wm_op_attention_cached's single-workgroup forms (n_chunks = 1, nq = 0) with a key window: utterance u sweeps the cache rows
+ * [key_lo[u], len + 1 (+ p)) — key_lo [n_utt], 0 <= key_lo[u] <= t.  An empty window gives zeros.  key_lo = 0 is wm_op_attention_cached
+ * bit for bit. */
+int wm_op_attention_cached_lo(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
+                              int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo);
 /* One launch of the decode step's skinny linear, out[B, N] = epi(pro(x)[B, K]·W[N, K]ᵀ + bias), wired as a decode step wires its six
  * per-layer launches.  W is rounded to dtype on upload.  pro: ln_g / ln_b [K] non-NULL: LayerNorm (eps 1e-5) of the fp32 rows x;
  * x_is_t != 0 (no LayerNorm): x is uploaded in dtype, as the producer kernel leaves it.  epi: + bias [N] (or NULL); act != 0: GELU

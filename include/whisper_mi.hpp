@@ -168,11 +168,17 @@ public:
         std::vector<int> sequence;
         std::vector<LongSegment> segments;
     };
-    std::vector<LongResult> transcribe_long(const float* mels, int B, int T, const std::vector<int32_t>& n_frames = {}, int max_loop = MAX_LOOP) const {
+    // condition_on_prev_tokens / prompt_ids (as WhisperProcessor.get_prompt_ids returns them) / all_segments: HF generate's options of
+    // the same names; the defaults are wm_transcribe_long
+    std::vector<LongResult> transcribe_long(const float* mels, int B, int T, const std::vector<int32_t>& n_frames = {}, int max_loop = MAX_LOOP,
+                                            bool condition_on_prev_tokens = false, const std::vector<int32_t>& prompt_ids = {},
+                                            bool all_segments = false, int32_t prev_sot_token = 50361) const {
         need_model();
         wm_decode_opts o = opts(max_loop, false);
         wm_long_result* r = nullptr;
-        check(wm_transcribe_long(model_, mels, 0, B, T, n_frames.empty() ? nullptr : n_frames.data(), &o, &r));
+        const wm_long_opts lo{condition_on_prev_tokens ? 1 : 0, prev_sot_token, prompt_ids.empty() ? nullptr : prompt_ids.data(),
+                              (int)prompt_ids.size(), all_segments ? 1 : 0};
+        check(wm_transcribe_long_ex(model_, mels, 0, B, T, n_frames.empty() ? nullptr : n_frames.data(), &o, &lo, &r));
         std::vector<LongResult> out(B);
         int rc = 0;
         for (int b = 0; b < B && !rc; ++b) {

@@ -23,6 +23,8 @@ SYMBOLS = [
     "wm_alignment_weights", "wm_op_token_times",
     "wm_log_mel_long", "wm_transcribe_long", "wm_transcribe_long_pcm", "wm_long_result_sizes", "wm_long_result_get",
     "wm_long_result_stats", "wm_long_result_free", "wm_op_long_segments",
+    "wm_transcribe_rows", "wm_transcribe_submit_rows", "wm_transcribe_long_ex", "wm_transcribe_long_pcm_ex", "wm_op_long_prompt",
+    "wm_op_attention_cached_lo", "wm_long_result_prompt_stats",
 ]
 
 ABI_VERSION = 4  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -44,6 +46,25 @@ class WmDecodeOpts(C.Structure):
 
 class WmSegment(C.Structure):
     _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("start", C.c_double), ("end", C.c_double)]
+
+
+class WmLongOpts(C.Structure):
+    _fields_ = [("condition_on_prev_tokens", C.c_int), ("prev_sot_token", C.c_int), ("prompt_ids", C.POINTER(C.c_int32)),
+                ("n_prompt_ids", C.c_int), ("prompt_condition_type", C.c_int)]
+
+
+PROMPT_CONDITION_TYPES = {"first-segment": 0, "all-segments": 1}
+
+
+def long_opts(prompt_ids=None, condition_on_prev_tokens=False, prompt_condition_type="first-segment", prev_sot_token=50361):
+    """-> (WmLongOpts, keep-alive array).  prompt_condition_type: a name of PROMPT_CONDITION_TYPES."""
+    import numpy as np
+    if (prompt_condition_type or "first-segment") not in PROMPT_CONDITION_TYPES:
+        raise ValueError(f"prompt_condition_type must be one of {sorted(PROMPT_CONDITION_TYPES)}")
+    p = np.ascontiguousarray(np.asarray([] if prompt_ids is None else prompt_ids, np.int32).reshape(-1))
+    o = WmLongOpts(int(bool(condition_on_prev_tokens)), int(prev_sot_token), p.ctypes.data_as(C.POINTER(C.c_int32)) if p.size else None,
+                   int(p.size), PROMPT_CONDITION_TYPES[prompt_condition_type or "first-segment"])
+    return o, p
 
 
 class WhisperMiError(RuntimeError):
@@ -103,9 +124,16 @@ def lib():
     L.wm_long_result_sizes.argtypes = [vp, C.c_int, ip, ip]
     L.wm_long_result_get.argtypes = [vp, C.c_int, ip, C.POINTER(WmSegment)]
     L.wm_long_result_stats.argtypes = [vp, ip, ip, ip, ip]
+    L.wm_long_result_prompt_stats.argtypes = [vp, ip, ip]
     L.wm_long_result_free.argtypes = [vp]
     L.wm_long_result_free.restype = None
     L.wm_op_long_segments.argtypes = [ip, C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(WmSegment), ip, ip]
+    L.wm_transcribe_rows.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip, C.c_int, ip, ip]
+    L.wm_transcribe_submit_rows.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip, C.c_int]
+    L.wm_transcribe_long_ex.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, C.POINTER(WmDecodeOpts), C.POINTER(WmLongOpts), C.POINTER(vp)]
+    L.wm_transcribe_long_pcm_ex.argtypes = [vp, fp, ip, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), C.POINTER(WmLongOpts), C.POINTER(vp)]
+    L.wm_op_long_prompt.argtypes = [ip, C.POINTER(WmSegment), C.c_int, ip, C.c_int, C.POINTER(WmLongOpts), C.c_int, C.c_int, ip, ip]
+    L.wm_op_attention_cached_lo.argtypes = [fp] * 4 + [C.c_int] * 9 + [ip]
     L.wm_op_matmul_nt.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int]
     L.wm_op_mlp_block.argtypes = [fp] * 10 + [C.c_int] * 5
     L.wm_op_ln_matmul_nt.argtypes = [fp] * 6 + [C.c_int] * 5
@@ -132,7 +160,8 @@ def lib():
 def long_result(h, B: int):
     """Reads and frees a wm_long_result handle of B utterances -> (per utterance {"sequence": [...], "segments": [{"start",
     "end", "tokens"}]}, {"windows", "stalled", "passes", "rows"}: windows decoded, windows that did not advance seek, passes
-    run and rows those passes decoded)."""
+    run and rows those passes decoded; "longest_prompt", "row_passes": the longest decoder prompt a pass carried and how many
+    passes went out as per-row passes)."""
     L = lib()
     try:
         out = []
@@ -147,7 +176,11 @@ def long_result(h, B: int):
                                                       for s in segs[:n_seg.value]]})
         st = [C.c_int32() for _ in range(4)]
         check(L.wm_long_result_stats(h, *[C.byref(v) for v in st]))
-        return out, dict(zip(("windows", "stalled", "passes", "rows"), (v.value for v in st)))
+        stats = dict(zip(("windows", "stalled", "passes", "rows"), (v.value for v in st)))
+        lp, rp = C.c_int32(), C.c_int32()
+        check(L.wm_long_result_prompt_stats(h, C.byref(lp), C.byref(rp)))
+        stats.update(longest_prompt=lp.value, row_passes=rp.value)
+        return out, stats
     finally:
         L.wm_long_result_free(h)
 
@@ -161,6 +194,27 @@ def long_segments(ids, timestamp_begin: int, seek: int, seek_num_frames: int):
     check(lib().wm_op_long_segments(a.ctypes.data_as(C.POINTER(C.c_int32)), a.size, timestamp_begin, seek, seek_num_frames, segs,
                                     C.byref(n), C.byref(adv)))
     return [(s.first, s.count, s.start, s.end) for s in segs[:n.value]], adv.value
+
+
+def long_prompt(segments, init, timestamp_begin: int, n_text_ctx: int, prompt_ids=None, condition_on_prev_tokens=False,
+                prompt_condition_type="first-segment", prev_sot_token=50361):
+    """wm_op_long_prompt (host-only HF _prepare_decoder_input_ids for one utterance): segments = the utterance's segments so
+    far (a list of id lists) -> the decoder prompt of its next window."""
+    import numpy as np
+    ip = C.POINTER(C.c_int32)
+    seq = np.ascontiguousarray(np.asarray([t for sg in segments for t in sg], np.int32))
+    segs = (WmSegment * max(1, len(segments)))()
+    first = 0
+    for i, sg in enumerate(segments):
+        segs[i] = WmSegment(first, len(sg), 0.0, 0.0)
+        first += len(sg)
+    ini = np.ascontiguousarray(np.asarray(init, np.int32).reshape(-1))
+    lo, _keep = long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token)
+    out = np.zeros(max(1, n_text_ctx), np.int32)
+    n = C.c_int32()
+    check(lib().wm_op_long_prompt(seq.ctypes.data_as(ip) if seq.size else None, segs, len(segments), ini.ctypes.data_as(ip), ini.size,
+                                  C.byref(lo), timestamp_begin, n_text_ctx, out.ctypes.data_as(ip), C.byref(n)))
+    return out[:n.value].tolist()
 
 
 def check(rc: int):

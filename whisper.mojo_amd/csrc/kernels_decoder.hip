@@ -1195,8 +1195,12 @@ template int launch_dec_logits<f16>(const DecLinearParams&, hipStream_t);
 // attn_combine, or the normalised output directly when the chunk is the whole sequence.
 // Scale after the dot product and max initialised to -1e10 follow layers.mojo:196,212 (the mask branch at :213 is a
 // no-op for j <= len-1 and is omitted).
-template <typename TKV, int LPH, bool FAST, bool NT, int U, int NQ = 1>
-__global__ __launch_bounds__(512) void attn_decode_kernel(AttnDecParams p) {
+// LO (per-row prompts, self-attention forms only): utterance bk sweeps keys [key_lo[bk], len) instead of [0, len) — the rows of a pass
+// are aligned at the END of the longest prompt, so a shorter prompt has dead cache rows in front.  The sweep starts AT key_lo (row
+// slot r takes keys key_lo + r, key_lo + r + RPS, ...): a row's arithmetic is what it would be alone with its own unpadded prompt.
+// An empty window (a dead prefill slot) stores zeros.  LO = false is the kernel as it always was.
+template <typename TKV, int LPH, bool FAST, bool NT, int U, int NQ, bool LO>
+__device__ __forceinline__ void attn_decode_body(const AttnDecParams& p, const int* __restrict__ key_lo) {
     // NQ > 1 (prompt prefill, cross-attention): the workgroup of utterance b serves the NQ query rows t * B + b from ONE
     // sweep of that utterance's K/V chunk — each cache row is read once for all prompt positions.
     constexpr int EPL = 64 / LPH;  // elements per lane
@@ -1209,8 +1213,9 @@ __global__ __launch_bounds__(512) void attn_decode_kernel(AttnDecParams p) {
     const int bk = (NQ == 1 && p.q_B > 0) ? b % p.q_B : b;  // utterance whose K/V this workgroup reads
     const int len = p.n_keys >= 0 ? p.n_keys : p.ctl->len + 1 + ((NQ == 1 && p.q_B > 0) ? b / p.q_B : 0);  // (scalar chain kernarg -> ctl -> len: the loop bounds need it before any K/V row is requested)
     const int qstride = NQ > 1 ? p.q_B : 0;  // query / output row of position t: b + t * qstride
-    const int chunk = (len + p.nsplit - 1) / p.nsplit;
-    const int j0 = split * chunk;
+    const int lo = LO ? key_lo[bk] : 0;
+    const int chunk = LO ? max(len - lo, 0) : (len + p.nsplit - 1) / p.nsplit;  // (LO: nsplit == 1)
+    const int j0 = lo + split * chunk;
     const int j1 = min(len, j0 + chunk);
     const int rslot = threadIdx.x / LPR, c = threadIdx.x % LPR;
     const int h = c / LPH, e0 = (c % LPH) * EPL;
@@ -1323,7 +1328,7 @@ __global__ __launch_bounds__(512) void attn_decode_kernel(AttnDecParams p) {
             }
             const size_t orow = (size_t)b + (size_t)t * qstride;
             if (p.direct_out) {
-                const float norm = 1.0f / L;
+                const float norm = (LO && !(L > 0.f)) ? 0.f : 1.0f / L;
 #pragma unroll
                 for (int e = 0; e < EPL; ++e) store_as(p.direct_out, orow * p.d + h * 64 + e0 + e, o[e] * norm, p.out_dtype);
             } else {
@@ -1339,7 +1344,15 @@ __global__ __launch_bounds__(512) void attn_decode_kernel(AttnDecParams p) {
         }
     }
 }
-template <typename TKV> int launch_attn_decode(const AttnDecParams& p, hipStream_t st) {
+template <typename TKV, int LPH, bool FAST, bool NT, int U, int NQ = 1>
+__global__ __launch_bounds__(512) void attn_decode_kernel(AttnDecParams p) {
+    attn_decode_body<TKV, LPH, FAST, NT, U, NQ, false>(p, nullptr);
+}
+template <typename TKV, int LPH, bool FAST, int U>
+__global__ __launch_bounds__(512) void attn_decode_lo_kernel(AttnDecParams p, const int* __restrict__ key_lo) {
+    attn_decode_body<TKV, LPH, FAST, false, U, 1, true>(p, key_lo);
+}
+template <typename TKV> int launch_attn_decode(const AttnDecParams& p, hipStream_t st, const int* key_lo) {
     constexpr int LPH = sizeof(TKV) == 4 ? 16 : 8;
     constexpr bool FAST = sizeof(TKV) == 2;
     const int LPR = p.H * LPH;
@@ -1357,6 +1370,11 @@ template <typename TKV> int launch_attn_decode(const AttnDecParams& p, hipStream
     if (thr_cross && p.n_keys >= 0) q.rps = std::max(1, std::min(512, thr_cross) / LPR);
     // block rounded up to whole waves: the spare lanes take no rows (rslot >= RPS) but stay in the DPP groups
     const dim3 grid(p.nsplit, p.B), block((q.rps * LPR + 63) / 64 * 64);
+    if (key_lo) {  // per-row prompts: the self-attention forms with a key window
+        if (p.n_keys >= 0 || !p.direct_out || p.nq > 1) return launch_refuse("attn_decode: key_lo belongs to the single-workgroup self-attention forms");
+        hipLaunchKernelGGL((attn_decode_lo_kernel<TKV, LPH, FAST, 4>), grid, block, 0, st, q, key_lo);
+        return WM_LAUNCH_OK;
+    }
     static const bool nt_off = wm_env("WM_NO_NT") != nullptr;
     static const int u_cross = wm_env("WM_ATTN_U") ? atoi(wm_env("WM_ATTN_U")) : 4;
     if (p.n_keys >= 0 && p.nq == 4) {  // prompt prefill, four positions per utterance from one K/V sweep (q_B = utterances)
@@ -1396,9 +1414,9 @@ template <typename TKV> int launch_attn_decode(const AttnDecParams& p, hipStream
     }
     return WM_LAUNCH_OK;
 }
-template int launch_attn_decode<float>(const AttnDecParams&, hipStream_t);
-template int launch_attn_decode<bf16>(const AttnDecParams&, hipStream_t);
-template int launch_attn_decode<f16>(const AttnDecParams&, hipStream_t);
+template int launch_attn_decode<float>(const AttnDecParams&, hipStream_t, const int*);
+template int launch_attn_decode<bf16>(const AttnDecParams&, hipStream_t, const int*);
+template int launch_attn_decode<f16>(const AttnDecParams&, hipStream_t, const int*);
 
 // merge the key-chunk partials: out[b][h*64+e] = Σ_s w_s·o_s / Σ_s w_s·l_s,  w_s = exp(m_s − max m).
 // One wave per (utterance, head): lane s owns chunk s's (m, l) — one exp per chunk, not per element — and the
@@ -1982,6 +2000,49 @@ __global__ void init_tokens_kernel(InitTokensParams p) {
 }
 void launch_init_tokens(const InitTokensParams& p, hipStream_t st) {
     hipLaunchKernelGGL(init_tokens_kernel, dim3((p.B + 255) / 256), dim3(256), 0, st, p);
+}
+// per-row prompts: row b's prompt is table[b][0 .. len[b]) (p.prompt / p.n_prompt unused).  The rows of the pass end together at
+// position Lmax: row b has pad = Lmax - len[b] dead slots in front — (the row's first id, position 0) in the prefill rows, never attended to
+// (key_lo[b] = pad).  out_tokens gets the row's own prompt, unpadded.
+__global__ void init_tokens_rows_kernel(InitTokensParams p, RowPromptParams r) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < p.B) {
+        const int Lb = r.len[b], pad = r.Lmax - Lb;
+        const int* row = r.table + (size_t)b * r.stride;
+        for (int i = 0; i < Lb; ++i) p.out_tokens[(size_t)b * p.out_stride + i] = row[i];
+        p.n_tokens[b] = Lb;
+        p.finished[b] = 0;
+        r.key_lo[b] = pad;
+        for (int t = 0; t < r.Lmax; ++t) {
+            p.tok_rows[(size_t)t * p.B + b] = t < pad ? row[0] : row[t - pad];
+            p.pos_rows[(size_t)t * p.B + b] = t < pad ? 0 : t - pad;
+        }
+        if (p.ts_state) {
+            TsState st;
+            st.n_gen = 0;
+            st.last_ts = 0;
+            st.pen_ts = 1;
+            st.t_last = -1;
+            ts_next_ranges(st, p.rules);
+            p.ts_state[b] = st;
+        }
+    }
+    if (b == 0) {
+        p.ctl->len = 0;
+        p.ctl->n_finished = 0;
+    }
+}
+void launch_init_tokens_rows(const InitTokensParams& p, const RowPromptParams& r, hipStream_t st) {
+    hipLaunchKernelGGL(init_tokens_rows_kernel, dim3((p.B + 255) / 256), dim3(256), 0, st, p, r);
+}
+// end of a per-row prefill: cache length Lmax for all, position len[b] + pos_delta per row
+__global__ void set_rows_step_kernel(StepCtl* ctl, int Lmax, int* pos, const int* len, int pos_delta, int B) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < B) pos[i] = len[i] + pos_delta;
+    if (i == 0) ctl->len = Lmax;
+}
+void launch_set_rows_step(StepCtl* ctl, int Lmax, int* pos, const int* len, int pos_delta, int B, hipStream_t st) {
+    hipLaunchKernelGGL(set_rows_step_kernel, dim3((B + 255) / 256), dim3(256), 0, st, ctl, Lmax, pos, len, pos_delta, B);
 }
 
 __global__ void pack_tokens_kernel(const int* __restrict__ out_tokens, const int* __restrict__ n_tokens, int out_stride, int rows, int stride,

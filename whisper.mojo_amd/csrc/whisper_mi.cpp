@@ -141,6 +141,8 @@ struct DevBuf {
     template <typename T> T* as() const { return (T*)p; }
 };
 
+static int grow(DevBuf& b, size_t bytes) { return b.p && b.bytes >= bytes ? 0 : b.alloc(bytes); }
+
 // scratch of an op-level entry point, released on return
 struct TmpDev {
     std::vector<DevBuf> bufs;
@@ -342,6 +344,15 @@ struct wm_state {
         std::vector<int32_t> pairs;
         bool operator!=(const CapKey& o) const { return cap != o.cap || L != o.L || n_prompt != o.n_prompt || pairs != o.pairs; }
     } graph_cap;
+    // per-row prompts of the pending pass (on = wm_transcribe_rows and its kin).  Buffers are allocated by the first such
+    // pass: table [B][n_text_ctx] ids, len [B], key_lo [B] (first cache row of each utterance's own keys).
+    struct Rows {
+        bool on = false;
+        int Lmax = 0, stride = 0;
+        DevBuf table, len, key_lo;
+        std::vector<int32_t> h_table, h_len;
+    } rw;
+    bool graph_rows = false;  // the captured step graph's self-attention is the key-window form
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -821,7 +832,8 @@ extern "C" void wm_state_free(wm_state* s) {
     DevBuf* bs[] = {&s->mel_dev, &s->mel_t, &s->h1, &s->x, &s->xn, &s->qkv, &s->ao, &s->hid, &s->enc_t, &s->enc_f,
                     &s->cross_kv, &s->enc_x, &s->xq, &s->part_y, &s->self_kv, &s->dx, &s->dq, &s->dattn, &s->dhid, &s->part_o, &s->part_ml, &s->logits, &s->amax_val, &s->amax_idx, &s->ts_state, &s->ts_val, &s->ts_idx, &s->ts_m, &s->ts_s, &s->mask_steady, &s->mask_begin,
                     &s->tok, &s->pos, &s->tok_rows, &s->pos_rows, &s->ctl, &s->out_tokens, &s->n_tokens, &s->finished,
-                    &s->al.cap, &s->al.kh, &s->al.probs, &s->al.mean, &s->al.stdv, &s->al.M, &s->al.trace, &s->al.times, &s->al.ncols};
+                    &s->al.cap, &s->al.kh, &s->al.probs, &s->al.mean, &s->al.stdv, &s->al.M, &s->al.trace, &s->al.times, &s->al.ncols,
+                    &s->rw.table, &s->rw.len, &s->rw.key_lo};
     for (DevBuf* b : bs) b->release();
     delete s;
 }
@@ -829,6 +841,12 @@ extern "C" void wm_state_free(wm_state* s) {
 static const int OUT_STRIDE_MAX = 1024;
 
 static int state_new(wm_model* m, int B, wm_state** out, bool pair);
+// decode lanes a state of B utterances gets (1 unless the developer build's WM_DEC_LANES asks for more)
+static int dec_lanes_for(int B) {
+    int nl = 1;
+    if (const char* e = wm_env("WM_DEC_LANES")) nl = std::max(1, std::min(4, atoi(e)));
+    return std::min(nl, (B + 15) / 16);
+}
 extern "C" int wm_state_new(wm_model* m, int B, wm_state** out) { return state_new(m, B, out, false); }
 // pair: the 2·B-row state of a coalesced pair of submits (B <= max_batch each)
 static int state_new(wm_model* m, int B, wm_state** out, bool pair) {
@@ -935,9 +953,7 @@ static int state_new(wm_model* m, int B, wm_state** out, bool pair) {
     {  // decode lanes
         // measured on MI355X (round 1): 2 lanes 49.1 ms vs 1 lane 47.4 ms per 64-clip pass — kernel boundaries of one
         // queue also stall the other queue's kernels, so extra lanes stay opt-in (WM_DEC_LANES)
-        int nl = 1;
-        if (const char* e = wm_env("WM_DEC_LANES")) nl = std::max(1, std::min(4, atoi(e)));
-        nl = std::min(nl, (B + 15) / 16);
+        const int nl = dec_lanes_for(B);
         s->lanes.resize(nl);
         const int per = ((B + nl - 1) / nl + 15) / 16 * 16;  // whole MFMA row blocks per lane
         int b0 = 0;
@@ -1230,9 +1246,9 @@ static int dec_linear_dispatch(int dt, const DecLinearParams& p, hipStream_t st)
     DISPATCH_DT(dt, TT, rc = launch_dec_linear<TT>(p, st));
     return launch_rc(rc);
 }
-static int attn_decode_dispatch(int dt, const AttnDecParams& p, hipStream_t st) {
+static int attn_decode_dispatch(int dt, const AttnDecParams& p, hipStream_t st, const int* key_lo = nullptr) {
     int rc = 0;
-    DISPATCH_DT(dt, TT, rc = launch_attn_decode<TT>(p, st));
+    DISPATCH_DT(dt, TT, rc = launch_attn_decode<TT>(p, st, key_lo));
     return launch_rc(rc);
 }
 
@@ -1318,7 +1334,8 @@ static int launch_cross_attn(wm_model* m, wm_state* s, int l, const DecView& v, 
 // self-attention of position t sees keys 0..len+t (the causal mask of layers.mojo:309-318), logits only for the last
 // position.  Every row's arithmetic is what the single-position pass does for it, so the ids are the same bit for bit.
 static int decode_core(wm_model* m, wm_state* s, const DecView& v, bool want_logits, bool full_logits = false,
-                       const float* mask = nullptr, int P = 1, bool embed = true, const TsRules* rules = nullptr, bool capture = false) {
+                       const float* mask = nullptr, int P = 1, bool embed = true, const TsRules* rules = nullptr, bool capture = false,
+                       int t0 = -1) {  // t0 >= 0: a chunk of a per-row prefill — tokens / positions are rows [t0, t0 + P) of tok_rows / pos_rows
     const wm_dims& c = m->cfg.dims;
     const int T = dec_dtype(m->cfg), KV = m->cfg.kv_dtype;  // T: the decoder's operand dtype
     const int B = v.nb * P;          // activation rows of this pass
@@ -1335,8 +1352,9 @@ static int decode_core(wm_model* m, wm_state* s, const DecView& v, bool want_log
     float* dattn = (float*)off_bytes(s->dattn, (size_t)v.b0 * d * dt_size(T));
     float* dhid = (float*)off_bytes(s->dhid, (size_t)v.b0 * c.ffn * dt_size(T));
     if (embed)  // (the greedy loop's steps get their input row from the previous step's argmax launch instead)
-        launch_dec_embed(m->tok_emb_f.as<float>(), m->dec_pos.as<float>(), P > 1 ? s->tok_rows.as<int>() : s->tok.as<int>() + v.b0,
-                     P > 1 ? s->pos_rows.as<int>() : s->pos.as<int>() + v.b0, dx, B, c.d_model, st);
+        launch_dec_embed(m->tok_emb_f.as<float>(), m->dec_pos.as<float>(),
+                     t0 >= 0 ? s->tok_rows.as<int>() + (size_t)t0 * v.nb : P > 1 ? s->tok_rows.as<int>() : s->tok.as<int>() + v.b0,
+                     t0 >= 0 ? s->pos_rows.as<int>() + (size_t)t0 * v.nb : P > 1 ? s->pos_rows.as<int>() : s->pos.as<int>() + v.b0, dx, B, c.d_model, st);
     for (int l = 0; l < c.n_layers; ++l) {
         DecLayer& w = m->dec[l];
         void* sk = off_bytes(s->self_kv, ((size_t)(2 * l) * self_l + self_b) * ks);
@@ -1379,7 +1397,8 @@ static int decode_core(wm_model* m, wm_state* s, const DecView& v, bool want_log
             a.H = c.n_heads;
             a.d = c.d_model;
             a.B = B;
-            WMCHK(attn_decode_dispatch(KV, a, st));
+            // per-row prompts: every utterance sweeps its own key window [key_lo, len + 1 (+ t))
+            WMCHK(attn_decode_dispatch(KV, a, st, s->rw.on ? s->rw.key_lo.as<int>() + v.b0 : nullptr));
         }
         // the attention outputs and the MLP hidden rows are handed over in operand dtype T (what the next MFMA consumes)
         auto proj_residual = [&](const float* in, int K, const DevBuf& W, const DevBuf& bias) -> int {  // x += in·Wᵀ + b
@@ -1696,6 +1715,29 @@ static void pump_main(wm_model* m) {
     }
 }
 
+// Per-row prompts, the start of a pass on a single-lane state: prompt table and lengths to the device, tokens /
+// key windows / prefill rows from them, the prefill in chunks of PREFILL_MAX positions through the position-major pass (the rows
+// end together at position Lmax; logits for the last chunk only: every row's last position is real), the first id, and the per-row
+// positions of the first loop step.  ip: the pass's InitTokensParams without the prompt.
+static int prefill_rows(wm_model* m, wm_state* s, const DecView& v, InitTokensParams ip, const wm_decode_opts* o, const TsRules* rp) {
+    wm_state::Rows& rw = s->rw;
+    const int Lmax = rw.Lmax;
+    HIPCHK(hipMemcpyAsync(rw.table.p, rw.h_table.data(), rw.h_table.size() * 4, hipMemcpyHostToDevice, v.st));
+    HIPCHK(hipMemcpyAsync(rw.len.p, rw.h_len.data(), rw.h_len.size() * 4, hipMemcpyHostToDevice, v.st));
+    ip.tok_rows = s->tok_rows.as<int>();
+    ip.pos_rows = s->pos_rows.as<int>();
+    launch_init_tokens_rows(ip, RowPromptParams{rw.table.as<int>(), rw.len.as<int>(), rw.stride, Lmax, rw.key_lo.as<int>()}, v.st);
+    for (int t0 = 0; t0 < Lmax; t0 += wm_state::PREFILL_MAX) {
+        const int P = std::min<int>(wm_state::PREFILL_MAX, Lmax - t0);
+        if (t0) launch_set_step(v.ctl, t0, 1, nullptr, 0, nullptr, 0, v.nb, v.st);
+        WMCHK(decode_core(m, s, v, t0 + P == Lmax, false, s->mask_begin.as<float>(), P, true, rp, false, t0));
+    }
+    launch_argmax_step(argmax_params(m, s, v, true, o->eot, o->ignore_eot, false, false, rp), v.st);
+    trace_mark(v.st, "state %p lane %d prefill end", (void*)s, v.b0);
+    launch_set_rows_step(v.ctl, Lmax, s->pos.as<int>() + v.b0, rw.len.as<int>(), o->pos_mode == WM_POS_REF ? -1 : 0, v.nb, v.st);
+    return 0;
+}
+
 // ---- Whisper.transcribe: whisper.mojo:184-223 ------------------------------------------------------------------------
 // Enqueues the prompt prefill and the greedy loop for state s on its decode lane streams; returns without waiting.  The lanes
 // first wait for the encoder (recorded on the stream it ran on).  Both entry points stop once every utterance has emitted eot
@@ -1717,7 +1759,8 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
     wm_state::CapKey cap_key;
     if (s->al.on) cap_key = wm_state::CapKey{s->al.cap.p, s->al.L, s->al.n_prompt, s->al.pairs};
     const bool recapture = !s->graphs_valid || s->graph_eot != o->eot || s->graph_ignore != o->ignore_eot ||
-                           s->graph_shares != s->shares_chip || memcmp(&s->graph_rules, &rules, sizeof rules) != 0 || s->graph_cap != cap_key;
+                           s->graph_shares != s->shares_chip || memcmp(&s->graph_rules, &rules, sizeof rules) != 0 || s->graph_cap != cap_key ||
+                           s->graph_rows != s->rw.on;
     const int first_pos = o->pos_mode == WM_POS_REF ? o->n_prompt - 1 : o->n_prompt;
     // logit masks (§8f rank 4): rebuilt only when the id lists change; always passed (all-zero = the reference's raw argmax)
     {
@@ -1740,7 +1783,8 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
     }
     InitTokensParams ip{};
     ip.n_prompt = o->n_prompt;
-    for (int i = 0; i < o->n_prompt; ++i) ip.prompt[i] = o->prompt[i];
+    if (!s->rw.on)  // (per-row prompts: o->n_prompt is the longest row's length, the ids come from the device table)
+        for (int i = 0; i < o->n_prompt; ++i) ip.prompt[i] = o->prompt[i];
     for (auto& ln : s->lanes) {
         const DecView v{ln.b0, ln.nb, ln.st, ln.ctl};
         HIPCHK(hipStreamWaitEvent(v.st, s->enc_done, 0));
@@ -1756,21 +1800,25 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
         ip.pos_rows = s->pos_rows.as<int>();
         ip.ts_state = rp ? s->ts_state.as<TsState>() + v.b0 : nullptr;
         ip.rules = rules;
-        launch_init_tokens(ip, v.st);
-        // prefill (whisper.mojo:195, start_pos=0): the q_len = n_prompt causal block equals n_prompt single-token steps
-        static const bool seq_prefill = wm_env("WM_SEQ_PREFILL") != nullptr;  // A/B: one pass per prompt position
-        if (!seq_prefill && s->lanes.size() == 1 && o->n_prompt > 1 && o->n_prompt <= wm_state::PREFILL_MAX) {
-            WMCHK(decode_core(m, s, v, true, false, s->mask_begin.as<float>(), o->n_prompt, true, rp));  // init_tokens filled tok_rows / pos_rows
+        if (s->rw.on) {
+            WMCHK(prefill_rows(m, s, v, ip, o, rp));
         } else {
-            for (int i = 0; i < o->n_prompt; ++i) {
-                launch_set_step(v.ctl, i, 1, s->pos.as<int>() + v.b0, i, s->tok.as<int>() + v.b0, o->prompt[i], v.nb, v.st);
-                WMCHK(decode_core(m, s, v, i == o->n_prompt - 1, false, s->mask_begin.as<float>(), 1, true, rp));
+            launch_init_tokens(ip, v.st);
+            // prefill (whisper.mojo:195, start_pos=0): the q_len = n_prompt causal block equals n_prompt single-token steps
+            static const bool seq_prefill = wm_env("WM_SEQ_PREFILL") != nullptr;  // A/B: one pass per prompt position
+            if (!seq_prefill && s->lanes.size() == 1 && o->n_prompt > 1 && o->n_prompt <= wm_state::PREFILL_MAX) {
+                WMCHK(decode_core(m, s, v, true, false, s->mask_begin.as<float>(), o->n_prompt, true, rp));  // init_tokens filled tok_rows / pos_rows
+            } else {
+                for (int i = 0; i < o->n_prompt; ++i) {
+                    launch_set_step(v.ctl, i, 1, s->pos.as<int>() + v.b0, i, s->tok.as<int>() + v.b0, o->prompt[i], v.nb, v.st);
+                    WMCHK(decode_core(m, s, v, i == o->n_prompt - 1, false, s->mask_begin.as<float>(), 1, true, rp));
+                }
             }
+            launch_argmax_step(argmax_params(m, s, v, true, o->eot, o->ignore_eot, false, false, rp), v.st);  // :198-203
+            trace_mark(v.st, "state %p lane %d prefill end", (void*)s, v.b0);
+            // incremental steps: start_pos = current_len - 1 (reference, :217) or current_len (HF)
+            launch_set_step(v.ctl, o->n_prompt, 1, s->pos.as<int>() + v.b0, first_pos, nullptr, 0, v.nb, v.st);
         }
-        launch_argmax_step(argmax_params(m, s, v, true, o->eot, o->ignore_eot, false, false, rp), v.st);  // :198-203
-        trace_mark(v.st, "state %p lane %d prefill end", (void*)s, v.b0);
-        // incremental steps: start_pos = current_len - 1 (reference, :217) or current_len (HF)
-        launch_set_step(v.ctl, o->n_prompt, 1, s->pos.as<int>() + v.b0, first_pos, nullptr, 0, v.nb, v.st);
         // input row of the first loop step; every later step's row is written by the preceding step's argmax launch
         launch_dec_embed(m->tok_emb_f.as<float>(), m->dec_pos.as<float>(), s->tok.as<int>() + v.b0, s->pos.as<int>() + v.b0,
                          s->dx.as<float>() + (size_t)v.b0 * m->cfg.dims.d_model, v.nb, m->cfg.dims.d_model, v.st);
@@ -1803,6 +1851,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
     s->graph_rules = rules;
     s->graph_shares = s->shares_chip;
     s->graph_cap = cap_key;
+    s->graph_rows = s->rw.on;
     if (trace_phase) {
         for (auto& ln : s->lanes) (void)hipStreamSynchronize(ln.st);
         fprintf(stderr, "[wm] encoder wait + prefill (+graph capture if any): %.3f ms\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count() * 1e3);
@@ -1866,8 +1915,36 @@ static int check_opts(wm_model* m, const wm_decode_opts* o, int B) {
 // mel2 != null: a coalesced pair — *slot is a 2·(B/2)-row pair state, utterances [B/2, B) come from mel2.
 static int align_setup(wm_model* m, wm_state* s, const wm_decode_opts* o, const std::vector<int32_t>* cols);
 // cols != null: token timestamps for this pass, cols[b] = columns kept for row b (n_frames[b] // 2, or n_audio_ctx)
+// rows != null: per-row prompts (o->n_prompt = rows->Lmax, o->prompt unused)
+struct RowPrompts {
+    const int32_t* ids;  // host [B][stride]
+    const int32_t* len;  // host [B]
+    int stride, Lmax;
+};
+static int rows_setup(wm_model* m, wm_state* s, const RowPrompts* rows) {
+    wm_state::Rows& rw = s->rw;
+    rw.on = rows != nullptr;
+    if (!rw.on) return 0;
+    if (s->lanes.size() != 1) {
+        rw.on = false;
+        return fail(WM_E_ARG, "per-row prompts need a single-lane decode state");
+    }
+    const size_t B = s->B, ctx = m->cfg.dims.n_text_ctx;
+    WMCHK(grow(rw.table, B * ctx * 4));
+    WMCHK(grow(rw.len, B * 4));
+    WMCHK(grow(rw.key_lo, B * 4));
+    WMCHK(grow(s->tok_rows, B * ctx * 4));  // the whole prompt's position-major rows [Lmax][B], consumed chunk by chunk
+    WMCHK(grow(s->pos_rows, B * ctx * 4));
+    rw.Lmax = rows->Lmax;
+    rw.stride = rows->Lmax;
+    rw.h_table.assign(B * (size_t)rw.stride, 0);
+    rw.h_len.assign(rows->len, rows->len + B);
+    for (size_t b = 0; b < B; ++b) std::copy(rows->ids + b * rows->stride, rows->ids + b * rows->stride + rows->len[b], rw.h_table.begin() + b * rw.stride);
+    return 0;
+}
 static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, bool allow_poll,
-                     const float* mel2 = nullptr, int mel2_on_device = 0, const std::vector<int32_t>* cols = nullptr) {
+                     const float* mel2 = nullptr, int mel2_on_device = 0, const std::vector<int32_t>* cols = nullptr,
+                     const RowPrompts* rows = nullptr) {
     const wm_dims& c = m->cfg.dims;
     HIPCHK(hipSetDevice(m->device));
     const bool pair = mel2 != nullptr;
@@ -1880,6 +1957,7 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
         WMCHK(state_new(m, B, slot, pair));
     }
     wm_state* s = *slot;
+    WMCHK(rows_setup(m, s, rows));
     s->trace_id = slot == &m->cached ? 1 : (slot >= m->slots && slot < m->slots + (wm_model::NSLOT - 1)) ? 2 + (int)(slot - m->slots)
                 : (slot == &m->lf.st[0] || slot == &m->lf.st[1]) ? 20 + (int)(slot - m->lf.st) : 10 + (int)(slot - m->pairs);
     // The whole pass — encoder, prefill, greedy loop — goes on the slot's own stream: four slots are then four hardware
@@ -2120,6 +2198,61 @@ extern "C" int wm_transcribe_submit_tt(wm_model* m, int slot, const float* mel, 
     WMCHK(align_cols(m, n_frames, B, cols));
     return submit_impl(m, slot, mel, mel_on_device, B, o, &cols);
 }
+// ---- per-row prompts -----------------------------------------------------------------------------------------------
+// Everything is checked before anything is launched.  o2: the options the pass runs with (n_prompt = the longest row).
+static int rows_check(wm_model* m, const wm_decode_opts* o, int B, const int32_t* prompts, const int32_t* prompt_len, int prompt_stride,
+                      wm_decode_opts& o2, RowPrompts& rows) {
+    if (!o || B <= 0 || !prompts || !prompt_len || prompt_stride <= 0) return fail(WM_E_ARG, "bad argument");
+    o2 = *o;
+    o2.prompt = prompts;  // (ignored by a per-row pass; the generic checks want one valid id)
+    o2.n_prompt = 1;
+    const wm_dims& c = m->cfg.dims;
+    int Lmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const int L = prompt_len[b];
+        if (L < 1 || L > prompt_stride) return fail(WM_E_ARG, "prompt_len[%d] = %d outside [1, prompt_stride = %d]", b, L, prompt_stride);
+        for (int i = 0; i < L; ++i) {
+            const int32_t id = prompts[(size_t)b * prompt_stride + i];
+            if (id < 0 || id >= c.vocab) return fail(WM_E_ARG, "prompt id %d of row %d out of range", id, b);
+        }
+        Lmax = std::max(Lmax, L);
+    }
+    WMCHK(check_opts(m, &o2, B));
+    if (dec_lanes_for(B) != 1) return fail(WM_E_ARG, "per-row prompts need a single-lane decode state");
+    if (o->max_loop < 0 || Lmax + 1 + o->max_loop > c.n_text_ctx)
+        return fail(WM_E_ARG, "longest prompt %d + 1 + max_loop %d exceeds the decoder context %d", Lmax, o->max_loop, c.n_text_ctx);
+    o2.n_prompt = Lmax;
+    rows = RowPrompts{prompts, prompt_len, prompt_stride, Lmax};
+    return 0;
+}
+extern "C" int wm_transcribe_rows(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const int32_t* prompts,
+                                  const int32_t* prompt_len, int prompt_stride, int32_t* tokens_out, int32_t* n_tokens) {
+    if (!m || !mel || !tokens_out || !n_tokens) return fail(WM_E_ARG, "bad argument");
+    wm_decode_opts o2;
+    RowPrompts rows;
+    WMCHK(rows_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));
+    WMCHK(flush_held(m));
+    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, &o2, true, nullptr, 0, nullptr, &rows));
+    WMCHK(wait_on(m, m->cached, tokens_out, n_tokens));
+    m->last_steps[0] = m->cached->last_steps;
+    m->align_ref[0] = wm_model::AlignRef{};
+    return 0;
+}
+// (never held for a coalesce = 2 partner: a per-row pass runs alone)
+extern "C" int wm_transcribe_submit_rows(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o,
+                                         const int32_t* prompts, const int32_t* prompt_len, int prompt_stride) {
+    if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
+    wm_decode_opts o2;
+    RowPrompts rows;
+    WMCHK(rows_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));
+    wm_model::SlotRef& r = m->slot_ref[slot];
+    if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    WMCHK(flush_held(m));
+    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, &o2, false, nullptr, 0, nullptr, &rows));
+    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, o2.n_prompt + 1 + o2.max_loop, false};
+    return 0;
+}
 static int wait_impl(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_times) {
     wm_model::SlotRef& r = m->slot_ref[slot];
     if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
@@ -2161,8 +2294,6 @@ extern "C" int wm_set_alignment_heads(wm_model* m, const int32_t* layer_head_pai
     m->align_pairs = pairs;
     return 0;
 }
-
-static int grow(DevBuf& b, size_t bytes) { return b.p && b.bytes >= bytes ? 0 : b.alloc(bytes); }
 
 // Before the pass's graphs are (re)captured: size the timestamp buffers of state s and record what the pass asked for.
 static int align_setup(wm_model* m, wm_state* s, const wm_decode_opts* o, const std::vector<int32_t>* cols) {
@@ -2467,6 +2598,7 @@ struct wm_long_result {
     std::vector<std::vector<int32_t>> tokens;  // per utterance: the concatenation of its segments' ids
     std::vector<std::vector<wm_segment>> segs;
     int windows = 0, stalled = 0, passes = 0, rows = 0;
+    int longest_prompt = 0, row_passes = 0;  // longest decoder prompt a window of a real utterance carried; passes that went per row
 };
 
 // HF WhisperGenerationMixin._retrieve_segment (time_precision 0.02, time_precision_features 0.01, input_stride 2) on one window's
@@ -2585,6 +2717,79 @@ extern "C" int wm_log_mel_long(wm_model* m, const float* pcm, const int32_t* n_s
     return 0;
 }
 
+// HF WhisperGenerationMixin._prepare_decoder_input_ids for ONE utterance (wm_op_long_prompt).  seq / segs: the utterance's segments
+// so far; the first-segment pseudo-segment (prompt_ids minus a leading <|startofprev|>) is entered in front of them here.
+static bool long_opts_plain(const wm_long_opts* lo) { return !lo || (!lo->condition_on_prev_tokens && (!lo->prompt_ids || lo->n_prompt_ids <= 0)); }
+static void long_prompt(const int32_t* seq, const wm_segment* segs, int n_segs, const int32_t* init, int n_init, const wm_long_opts* lo, int tb,
+                        int n_text_ctx, std::vector<int32_t>& out) {
+    out.clear();
+    const bool have_prompt = lo && lo->prompt_ids && lo->n_prompt_ids > 0;
+    const bool cond = lo && lo->condition_on_prev_tokens;
+    const bool all_segments = lo && lo->prompt_condition_type == 1;
+    const int pseudo0 = have_prompt && lo->prompt_ids[0] == lo->prev_sot_token ? 1 : 0;
+    const bool pseudo = have_prompt && !all_segments;
+    if (cond && (n_segs > 0 || pseudo)) {
+        const int cut = n_text_ctx / 2 - 1;
+        std::vector<int32_t> prev;
+        auto add = [&](const int32_t* t, int n) {  // skip_ending_double_timestamps
+            if (n > 2 && t[n - 2] >= tb) --n;
+            prev.insert(prev.end(), t, t + n);
+        };
+        if (pseudo) add(lo->prompt_ids + pseudo0, lo->n_prompt_ids - pseudo0);
+        for (int i = 0; i < n_segs; ++i) add(seq + segs[i].first, segs[i].count);
+        if ((int)prev.size() > cut) prev.erase(prev.begin(), prev.end() - cut);
+        if (have_prompt && all_segments)
+            out.assign(lo->prompt_ids, lo->prompt_ids + lo->n_prompt_ids);
+        else
+            out.push_back(lo->prev_sot_token);
+        out.insert(out.end(), prev.begin(), prev.end());
+    } else if (have_prompt) {
+        out.assign(lo->prompt_ids, lo->prompt_ids + lo->n_prompt_ids);
+    }
+    out.insert(out.end(), init, init + n_init);
+}
+static int long_opts_check(const wm_long_opts* lo, const int32_t* init, int n_init, int max_loop, int vocab, int n_text_ctx, int pass_rows) {
+    if (long_opts_plain(lo)) {
+        if (lo && lo->prompt_condition_type == 1) return fail(WM_E_ARG, "prompt_condition_type all-segments needs condition_on_prev_tokens");
+        return 0;
+    }
+    (void)init;
+    if (dec_lanes_for(pass_rows) != 1) return fail(WM_E_ARG, "per-row prompts need a single-lane decode state");
+    const int cut = n_text_ctx / 2 - 1;
+    const int np = lo->prompt_ids ? std::max(lo->n_prompt_ids, 0) : 0;
+    if (lo->n_prompt_ids < 0 || (lo->n_prompt_ids > 0 && !lo->prompt_ids)) return fail(WM_E_ARG, "bad prompt_ids");
+    if (lo->prompt_condition_type != 0 && lo->prompt_condition_type != 1) return fail(WM_E_ARG, "prompt_condition_type must be 0 (first-segment) or 1 (all-segments)");
+    if (lo->prompt_condition_type == 1 && !lo->condition_on_prev_tokens) return fail(WM_E_ARG, "prompt_condition_type all-segments needs condition_on_prev_tokens");
+    if (lo->prev_sot_token < 0 || lo->prev_sot_token >= vocab) return fail(WM_E_ARG, "prev_sot_token %d is not a vocabulary id", lo->prev_sot_token);
+    for (int i = 0; i < np; ++i)
+        if (lo->prompt_ids[i] < 0 || lo->prompt_ids[i] >= vocab) return fail(WM_E_ARG, "prompt id out of range");
+    if (np > cut + 1) return fail(WM_E_ARG, "n_prompt_ids %d exceeds %d (half the decoder context)", np, cut + 1);
+    const int worst = lo->condition_on_prev_tokens ? ((lo->prompt_condition_type == 1 && np > 0 ? np : 1) + cut + n_init) : np + n_init;
+    if (worst + 1 + max_loop > n_text_ctx)
+        return fail(WM_E_ARG, "longest decoder prompt %d + 1 + max_loop %d exceeds the decoder context %d", worst, max_loop, n_text_ctx);
+    return 0;
+}
+extern "C" int wm_op_long_prompt(const int32_t* seq, const wm_segment* segs, int n_segs, const int32_t* init, int n_init, const wm_long_opts* lo,
+                                 int timestamp_begin, int n_text_ctx, int32_t* out, int32_t* n_out) {
+    if (n_segs < 0 || (n_segs > 0 && (!seq || !segs)) || !init || n_init <= 0 || !out || !n_out || n_text_ctx < 4 || timestamp_begin <= 0)
+        return fail(WM_E_ARG, "bad argument");
+    if (lo) {
+        if (lo->n_prompt_ids < 0 || (lo->n_prompt_ids > 0 && !lo->prompt_ids)) return fail(WM_E_ARG, "bad prompt_ids");
+        if (lo->prompt_condition_type != 0 && lo->prompt_condition_type != 1) return fail(WM_E_ARG, "prompt_condition_type must be 0 (first-segment) or 1 (all-segments)");
+        if (lo->prompt_condition_type == 1 && !lo->condition_on_prev_tokens) return fail(WM_E_ARG, "prompt_condition_type all-segments needs condition_on_prev_tokens");
+        if (!long_opts_plain(lo) && lo->prev_sot_token < 0) return fail(WM_E_ARG, "prev_sot_token is required with conditioning or prompt_ids");
+        if (lo->prompt_ids && lo->n_prompt_ids > n_text_ctx / 2) return fail(WM_E_ARG, "n_prompt_ids %d exceeds %d (half the decoder context)", lo->n_prompt_ids, n_text_ctx / 2);
+    }
+    for (int i = 0; i < n_segs; ++i)
+        if (segs[i].first < 0 || segs[i].count < 0) return fail(WM_E_ARG, "bad segment %d", i);
+    std::vector<int32_t> v;
+    long_prompt(seq, segs, n_segs, init, n_init, lo, timestamp_begin, n_text_ctx, v);
+    if ((int)v.size() > n_text_ctx) return fail(WM_E_ARG, "the prompt (%d ids) exceeds the decoder context %d", (int)v.size(), n_text_ctx);
+    std::copy(v.begin(), v.end(), out);
+    *n_out = (int32_t)v.size();
+    return 0;
+}
+
 static int long_check(wm_model* m, const wm_decode_opts* o, int B) {
     WMCHK(check_opts(m, o, B));
     if (o->timestamp_begin <= 0) return fail(WM_E_ARG, "long-form transcription needs the timestamp rules (timestamp_begin > 0)");
@@ -2601,10 +2806,17 @@ static int long_check(wm_model* m, const wm_decode_opts* o, int B) {
 // — one pass's gather + encoder and the host's segment bookkeeping overlap the other's decode.  An utterance rides one pass at a
 // time: with B <= 2R the two states keep the utterances they started with, and when one state runs dry the other's tail runs
 // one pass at a time.  mel: device [B][n_mels][T].
-static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int B, const wm_decode_opts* o, wm_long_result* res) {
+// lo (conditioning / prompt_ids): a row's decoder prompt is built from its utterance's own segments when the row is
+// assigned to a pass; a pass whose rows all carry opts->prompt goes out exactly as before, any other as a per-row pass.
+static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int B, const wm_decode_opts* o, wm_long_result* res,
+                    const wm_long_opts* lo) {
     const wm_dims& c = m->cfg.dims;
+    const bool plain = long_opts_plain(lo);
     // half the batch per state (when it fits), so that two passes are in flight whenever two utterances are pending
-    const int W = 2 * c.n_audio_ctx, R = std::min((B + 1) / 2, m->cfg.max_batch), total = o->n_prompt + 1 + o->max_loop;
+    const int W = 2 * c.n_audio_ctx, R = std::min((B + 1) / 2, m->cfg.max_batch), total = plain ? o->n_prompt + 1 + o->max_loop : c.n_text_ctx;
+    std::vector<int32_t> row_prompts[2], row_len[2];  // per state: the pass's prompts [R][n_text_ctx] and their lengths
+    int pass_total[2] = {total, total};
+    std::vector<int32_t> pr;
     wm_model::LongForm& L = m->lf;
     std::vector<int64_t> seek(B, 0);
     std::vector<char> busy(B, 0);
@@ -2643,7 +2855,36 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
                 launch_window_gather(mel, L.items[k].as<int>(), L.win[k].as<float>(), R, c.n_mels, T, W, m->stream);
                 rc = hipGetLastError() == hipSuccess ? 0 : fail(WM_E_HIP, "window gather launch failed");
             }
-            if (!rc) rc = submit_on(m, &L.st[k], L.win[k].as<float>(), 1, R, o, false);
+            bool per_row = false;
+            if (!plain) {
+                row_prompts[k].assign((size_t)R * c.n_text_ctx, 0);
+                row_len[k].assign(R, 0);
+                for (int r = 0; r < R; ++r) {  // (spare rows repeat row 0 with its prompt)
+                    const int b = h[3 * r];
+                    long_prompt(res->tokens[b].data(), res->segs[b].data(), (int)res->segs[b].size(), o->prompt, o->n_prompt, lo, o->timestamp_begin,
+                                c.n_text_ctx, pr);
+                    std::copy(pr.begin(), pr.end(), row_prompts[k].begin() + (size_t)r * c.n_text_ctx);
+                    row_len[k][r] = (int32_t)pr.size();
+                    per_row = per_row || (int)pr.size() != o->n_prompt || !std::equal(pr.begin(), pr.end(), o->prompt);
+                }
+            }
+            row_len[k].resize(R, o->n_prompt);
+            if (!per_row) {
+                res->longest_prompt = std::max(res->longest_prompt, o->n_prompt);
+                std::fill(row_len[k].begin(), row_len[k].end(), o->n_prompt);
+                pass_total[k] = o->n_prompt + 1 + o->max_loop;
+                if (!rc) rc = submit_on(m, &L.st[k], L.win[k].as<float>(), 1, R, o, false);
+            } else if (!rc) {
+                wm_decode_opts o2;
+                RowPrompts rows;
+                rc = rows_check(m, o, R, row_prompts[k].data(), row_len[k].data(), c.n_text_ctx, o2, rows);
+                pass_total[k] = o2.n_prompt + 1 + o2.max_loop;
+                if (!rc) {
+                    res->longest_prompt = std::max(res->longest_prompt, o2.n_prompt);
+                    ++res->row_passes;
+                }
+                if (!rc) rc = submit_on(m, &L.st[k], L.win[k].as<float>(), 1, R, &o2, false, nullptr, 0, nullptr, &rows);
+            }
             if (rc) {
                 n_items[k] = 0;
                 drain();
@@ -2666,10 +2907,11 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
         }
         for (int r = 0; r < n; ++r) {
             const int b = L.h_items[k][3 * r];
-            const int32_t* row = toks.data() + (size_t)r * total;
+            const int32_t* row = toks.data() + (size_t)r * pass_total[k];
+            const int n_prompt = row_len[k][r];
             int g1 = cnt[r];
-            if (g1 > o->n_prompt && row[g1 - 1] == o->eot) --g1;  // HF drops the trailing eos
-            const int g0 = std::min(o->n_prompt, g1);
+            if (g1 > n_prompt && row[g1 - 1] == o->eot) --g1;  // HF drops the trailing eos
+            const int g0 = std::min(n_prompt, g1);
             int adv = long_segments(row + g0, g1 - g0, o->timestamp_begin, seek[b], snf[b], segs);
             if (adv == 0) {  // the deviation: HF would decode this window again, forever
                 adv = snf[b];
@@ -2690,11 +2932,12 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
     return 0;
 }
 
-static int transcribe_long_impl(wm_model* m, const float* mel_dev, int T, const int32_t* nf, int B, const wm_decode_opts* o, wm_long_result** out) {
+static int transcribe_long_impl(wm_model* m, const float* mel_dev, int T, const int32_t* nf, int B, const wm_decode_opts* o, wm_long_result** out,
+                                const wm_long_opts* lo) {
     wm_long_result* r = new wm_long_result();
     r->tokens.resize(B);
     r->segs.resize(B);
-    const int rc = long_run(m, mel_dev, T, nf, B, o, r);
+    const int rc = long_run(m, mel_dev, T, nf, B, o, r, lo);
     (void)hipStreamSynchronize(m->stream);
     long_release(m);
     if (rc) {
@@ -2705,11 +2948,12 @@ static int transcribe_long_impl(wm_model* m, const float* mel_dev, int T, const 
     return 0;
 }
 
-extern "C" int wm_transcribe_long(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames, const wm_decode_opts* o,
-                                  wm_long_result** out) {
+extern "C" int wm_transcribe_long_ex(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames,
+                                     const wm_decode_opts* o, const wm_long_opts* lo, wm_long_result** out) {
     if (!m || !mel || !out || T <= 0) return fail(WM_E_ARG, "bad argument");
     *out = nullptr;
     WMCHK(long_check(m, o, B));
+    WMCHK(long_opts_check(lo, o->prompt, o->n_prompt, o->max_loop, m->cfg.dims.vocab, m->cfg.dims.n_text_ctx, std::min((B + 1) / 2, m->cfg.max_batch)));
     std::vector<int32_t> nf(B, T);
     if (n_frames)
         for (int b = 0; b < B; ++b) {
@@ -2724,14 +2968,23 @@ extern "C" int wm_transcribe_long(wm_model* m, const float* mel, int mel_on_devi
         HIPCHK(hipMemcpyAsync(m->lf.in_mel.p, mel, bytes, hipMemcpyHostToDevice, m->stream));
         dev = m->lf.in_mel.as<float>();
     }
-    return transcribe_long_impl(m, dev, T, nf.data(), B, o, out);
+    return transcribe_long_impl(m, dev, T, nf.data(), B, o, out, lo);
+}
+extern "C" int wm_transcribe_long(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames, const wm_decode_opts* o,
+                                  wm_long_result** out) {
+    return wm_transcribe_long_ex(m, mel, mel_on_device, B, T, n_frames, o, nullptr, out);
 }
 
 extern "C" int wm_transcribe_long_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o,
                                       wm_long_result** out) {
+    return wm_transcribe_long_pcm_ex(m, pcm, n_samples, B, stride, o, nullptr, out);
+}
+extern "C" int wm_transcribe_long_pcm_ex(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o,
+                                         const wm_long_opts* lo, wm_long_result** out) {
     if (!m || !out) return fail(WM_E_ARG, "bad argument");
     *out = nullptr;
     WMCHK(long_check(m, o, B));
+    WMCHK(long_opts_check(lo, o->prompt, o->n_prompt, o->max_loop, m->cfg.dims.vocab, m->cfg.dims.n_text_ctx, std::min((B + 1) / 2, m->cfg.max_batch)));
     std::vector<int32_t> nf(std::max(B, 0));
     const int rc = frontend_long_run(m, pcm, n_samples, B, stride, nf.data());  // same stream as the gathers: ordered, no host sync
     if (rc) {
@@ -2739,7 +2992,7 @@ extern "C" int wm_transcribe_long_pcm(wm_model* m, const float* pcm, const int32
         long_release(m);
         return rc;
     }
-    return transcribe_long_impl(m, m->lf.mel.as<float>(), stride / FE_HOP, nf.data(), B, o, out);
+    return transcribe_long_impl(m, m->lf.mel.as<float>(), stride / FE_HOP, nf.data(), B, o, out, lo);
 }
 
 extern "C" int wm_long_result_sizes(const wm_long_result* r, int b, int32_t* n_tokens, int32_t* n_segments) {
@@ -2761,6 +3014,12 @@ extern "C" int wm_long_result_stats(const wm_long_result* r, int32_t* windows, i
     *stalled = r->stalled;
     *passes = r->passes;
     *rows = r->rows;
+    return 0;
+}
+extern "C" int wm_long_result_prompt_stats(const wm_long_result* r, int32_t* longest_prompt, int32_t* row_passes) {
+    if (!r || !longest_prompt || !row_passes) return fail(WM_E_ARG, "bad argument");
+    *longest_prompt = r->longest_prompt;
+    *row_passes = r->row_passes;
     return 0;
 }
 extern "C" void wm_long_result_free(wm_long_result* r) { delete r; }
@@ -3243,8 +3502,19 @@ extern "C" int wm_op_attention(float* out, const float* q, const float* k, const
     return 0;
 }
 
+static int op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
+                               int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo, bool with_lo);
 extern "C" int wm_op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
                                       int n_chunks, int out_dtype, int q_B, int len, int nq) {
+    return op_attention_cached(out, q, k, v, B, t, n_heads, kv_dtype, n_chunks, out_dtype, q_B, len, nq, nullptr, false);
+}
+extern "C" int wm_op_attention_cached_lo(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
+                                         int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo) {
+    return op_attention_cached(out, q, k, v, B, t, n_heads, kv_dtype, n_chunks, out_dtype, q_B, len, nq, key_lo, true);
+}
+static int op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
+                               int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo, bool with_lo) {
+    if (with_lo && (!key_lo || n_chunks != 1 || nq != 0)) return fail(WM_E_ARG, "key_lo belongs to the single-workgroup forms (n_chunks = 1, nq = 0)");
     if (!out || !q || !k || !v || B <= 0 || t <= 0 || n_heads <= 0 || n_heads > 16) return fail(WM_E_ARG, "bad argument");
     if (kv_dtype < 0 || kv_dtype > 2 || out_dtype < 0 || out_dtype > 2) return fail(WM_E_ARG, "bad dtype");
     if (n_chunks < 1 || (n_chunks > 1 && (n_chunks < (t + 511) / 512 || n_chunks > (t + 31) / 32)))
@@ -3261,7 +3531,13 @@ extern "C" int wm_op_attention_cached(float* out, const float* q, const float* k
     const size_t d = (size_t)n_heads * 64, n = (size_t)B * d;
     TmpDev tmp;
     tmp.bufs.reserve(8);
-    DevBuf &dq = tmp.add(), &dk = tmp.add(), &dv = tmp.add(), &po = tmp.add(), &pml = tmp.add(), &o = tmp.add(), &ctl = tmp.add();
+    DevBuf &dq = tmp.add(), &dk = tmp.add(), &dv = tmp.add(), &po = tmp.add(), &pml = tmp.add(), &o = tmp.add(), &ctl = tmp.add(), &dlo = tmp.add();
+    if (with_lo) {
+        for (int u = 0; u < n_utt; ++u)
+            if (key_lo[u] < 0 || key_lo[u] > t) return fail(WM_E_ARG, "key_lo[%d] = %d outside [0, %d]", u, key_lo[u], t);
+        WMCHK(dlo.alloc((size_t)n_utt * 4));
+        HIPCHK(hipMemcpy(dlo.p, key_lo, (size_t)n_utt * 4, hipMemcpyHostToDevice));
+    }
     WMCHK(upload(dq, q, n, WM_F32));
     WMCHK(upload(dk, k, (size_t)n_utt * t * d, kv_dtype));
     WMCHK(upload(dv, v, (size_t)n_utt * t * d, kv_dtype));
@@ -3297,7 +3573,7 @@ extern "C" int wm_op_attention_cached(float* out, const float* q, const float* k
         a.nsplit = 1;
         a.direct_out = o.as<float>();
         a.out_dtype = out_dtype;
-        WMCHK(attn_decode_dispatch(kv_dtype, a, nullptr));
+        WMCHK(attn_decode_dispatch(kv_dtype, a, nullptr, with_lo ? dlo.as<int>() : nullptr));
     }
     HIPCHK(hipGetLastError());
     std::vector<unsigned char> h(n * dt_size(out_dtype));

@@ -208,7 +208,9 @@ struct AttnDecParams {
     long long* ts;  // developer timeline (null = off): see ts_put in kernels_decoder.hip
     int ts_id;
 };
-template <typename TKV> int launch_attn_decode(const AttnDecParams& p, hipStream_t st);  // WM_LAUNCH_*
+// key_lo non-null (per-row prompts; single-workgroup self-attention forms only): [utterances], utterance u sweeps the keys
+// [key_lo[u], len + 1 (+ t)) — a separate kernel; with key_lo null exactly the launch it always was
+template <typename TKV> int launch_attn_decode(const AttnDecParams& p, hipStream_t st, const int* key_lo = nullptr);  // WM_LAUNCH_*
 void launch_attn_combine(const float* part_o, const float* part_ml, void* out, int out_dtype, int B, int nsplit, int H, int d,
                          hipStream_t st, long long* ts = nullptr, int ts_id = 0);
 
@@ -289,6 +291,16 @@ struct InitTokensParams {
     TsRules rules;
 };
 void launch_init_tokens(const InitTokensParams& p, hipStream_t st);
+// Per-row prompts: the prompt of row b is table[b * stride .. + len[b]); the rows end together at position Lmax.
+struct RowPromptParams {
+    const int* table;  // [B][stride]
+    const int* len;    // [B], 1 <= len[b] <= Lmax; the dead slots in front of a shorter prompt embed its first id (never attended to)
+    int stride, Lmax;
+    int* key_lo;       // [B] out: Lmax - len[b], first cache row of the utterance's own keys
+};
+// as launch_init_tokens, tok_rows / pos_rows [Lmax][B] required; also writes key_lo
+void launch_init_tokens_rows(const InitTokensParams& p, const RowPromptParams& r, hipStream_t st);
+void launch_set_rows_step(StepCtl* ctl, int Lmax, int* pos, const int* len, int pos_delta, int B, hipStream_t st);
 // rows of the gather buffer of SURVEY §8e: dst[r] = [n_tokens[r], ids of row r zero-padded to `stride`] for r < rows; rows in
 // [rows, rows_cap) are zeroed (ragged shards gather a fixed row count per rank)
 void launch_pack_tokens(const int* out_tokens, const int* n_tokens, int out_stride, int rows, int rows_cap, int stride, int* dst, hipStream_t st);

@@ -224,14 +224,28 @@ class Whisper:
         return nf
 
     @staticmethod
+    def _prompt_rows(prompts, B):
+        """per-utterance prompts -> ([B, Lmax] int32 table, [B] lengths)"""
+        rows = [np.asarray(r, np.int32).reshape(-1) for r in prompts]
+        if len(rows) != B:
+            raise ValueError(f"prompts needs one id list per utterance ({B}), got {len(rows)}")
+        lens = np.asarray([r.size for r in rows], np.int32)
+        tab = np.zeros((B, max(1, int(lens.max()))), np.int32)
+        for b, r in enumerate(rows):
+            tab[b, :r.size] = r
+        return tab, lens
+
+    @staticmethod
     def _split_times(times, n, B):
         return [times[b, :n[b]].tolist() for b in range(B)]
 
     def transcribe_batch(self, mel, prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP,
                          ignore_eot: bool = False, suppress_tokens: Sequence[int] = (),
                          begin_suppress_tokens: Sequence[int] = (), timestamps=None, return_token_timestamps: bool = False,
-                         n_frames=None):
+                         n_frames=None, prompts: Optional[Sequence[Sequence[int]]] = None):
         """Batched Whisper.transcribe: one List[int] per utterance = prompt + generated ids (+ eot when hit).
+        prompts: one decoder prompt per utterance, of any lengths (`prompt` is then ignored); every row decodes as if it were
+        alone with its own prompt and comes back as its own prompt + generated ids.  Not with return_token_timestamps.
         return_token_timestamps: also return, per utterance, the time in seconds each id was spoken (HF generate's
         return_token_timestamps; needs set_alignment_heads) as (ids, times); n_frames: mel frames of real audio per utterance
         (HF's attention_mask.sum(-1)), None = the whole window."""
@@ -240,6 +254,16 @@ class Whisper:
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]
+        if prompts is not None:
+            if return_token_timestamps:
+                raise ValueError("per-utterance prompts do not combine with return_token_timestamps")
+            tab, lens = self._prompt_rows(prompts, B)
+            toks = np.zeros((B, tab.shape[1] + 1 + max_loop), np.int32)
+            n = np.zeros(B, np.int32)
+            _lib.check(_lib.lib().wm_transcribe_rows(self._h, ptr, on_dev, B, C.byref(opts), _ip(tab), _ip(lens), tab.shape[1],
+                                                     _ip(toks), _ip(n)))
+            self.last_tokens, self.last_counts = toks, n
+            return [toks[b, :n[b]].tolist() for b in range(B)]
         total = len(p) + 1 + max_loop
         toks = np.zeros((B, total), np.int32)
         n = np.zeros(B, np.int32)
@@ -260,8 +284,13 @@ class Whisper:
 
     def transcribe_long_form(self, features, n_frames=None, prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP,
                              suppress_tokens: Sequence[int] = (), begin_suppress_tokens: Sequence[int] = (),
-                             timestamps=(50364, 50363, 50), return_stats: bool = False):
-        """Sequential long-form transcription (HF generate's long-form path, greedy, condition_on_prev_tokens=False).
+                             timestamps=(50364, 50363, 50), return_stats: bool = False, prompt_ids: Optional[Sequence[int]] = None,
+                             condition_on_prev_tokens: bool = False, prompt_condition_type: str = "first-segment",
+                             prev_sot_token: int = 50361):
+        """Sequential long-form transcription (HF generate's long-form path, greedy).
+        condition_on_prev_tokens / prompt_ids / prompt_condition_type: HF generate's options of the same names — every window's
+        decoder prompt carries the utterance's previous text (up to half the decoder context) and / or prompt_ids (as
+        WhisperProcessor.get_prompt_ids returns them, leading <|startofprev|> = prev_sot_token included).
         features: [B, n_mels, T] log-mel of any length T (numpy, or a CUDA tensor on this model's device), or a list of
         [n_mels, T_b] arrays; n_frames: frames of real audio per utterance (HF's attention_mask.sum(-1)), None = T (or each
         array's length).  timestamps: (timestamp_begin, no_timestamps_id, max_initial_timestamp_index | None), required.
@@ -299,7 +328,8 @@ class Whisper:
                 raise ValueError(f"features must be [B, {n_mels}, T], got {tuple(features.shape)}")
             if not t.is_cuda:
                 return self.transcribe_long_form(t.float().numpy(), n_frames, prompt, eot, max_loop, suppress_tokens,
-                                                 begin_suppress_tokens, timestamps, return_stats)
+                                                 begin_suppress_tokens, timestamps, return_stats, prompt_ids, condition_on_prev_tokens,
+                                                 prompt_condition_type, prev_sot_token)
             keep = t.contiguous().float()
             torch.cuda.current_stream(keep.device).synchronize()  # the library reads it on its own HIP stream
             ptr, on_dev = C.c_void_p(keep.data_ptr()), 1
@@ -307,8 +337,9 @@ class Whisper:
         nf = self._frames_arg(n_frames, B)
         opts, _keep2 = self._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
         h = C.c_void_p()
-        _lib.check(_lib.lib().wm_transcribe_long(self._h, ptr, on_dev, B, T, _ip(nf) if nf is not None else None, C.byref(opts),
-                                                 C.byref(h)))
+        lo, _keep3 = _lib.long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token)
+        _lib.check(_lib.lib().wm_transcribe_long_ex(self._h, ptr, on_dev, B, T, _ip(nf) if nf is not None else None, C.byref(opts),
+                                                    C.byref(lo), C.byref(h)))
         out, stats = _lib.long_result(h, B)
         return (out, stats) if return_stats else out
 
@@ -322,7 +353,8 @@ class Whisper:
 
     def transcribe_submit(self, mel, slot: int = 0, prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP,
                           ignore_eot: bool = False, suppress_tokens: Sequence[int] = (), begin_suppress_tokens: Sequence[int] = (),
-                          timestamps=None, return_token_timestamps: bool = False, n_frames=None):
+                          timestamps=None, return_token_timestamps: bool = False, n_frames=None,
+                          prompts: Optional[Sequence[Sequence[int]]] = None):
         """Pipelined form (wm_transcribe_submit): enqueue encoder + greedy loop for this batch on pipeline slot 0..7 and
         return at once; `transcribe_wait(slot)` collects the ids.  Submitting batch i+1 before waiting for batch i lets
         its encoder overlap batch i's decode.  return_token_timestamps / n_frames: as transcribe_batch; the matching
@@ -332,6 +364,14 @@ class Whisper:
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]
+        if prompts is not None:  # per-utterance prompts, as transcribe_batch
+            if return_token_timestamps:
+                raise ValueError("per-utterance prompts do not combine with return_token_timestamps")
+            tab, lens = self._prompt_rows(prompts, B)
+            _lib.check(_lib.lib().wm_transcribe_submit_rows(self._h, slot, ptr, on_dev, B, C.byref(opts), _ip(tab), _ip(lens), tab.shape[1]))
+            self._pending = getattr(self, "_pending", {})
+            self._pending[slot] = (B, tab.shape[1] + 1 + max_loop, keep, None)
+            return
         if return_token_timestamps:
             nf = self._frames_arg(n_frames, B)
             _lib.check(_lib.lib().wm_transcribe_submit_tt(self._h, slot, ptr, on_dev, B, C.byref(opts),

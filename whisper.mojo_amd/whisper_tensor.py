@@ -78,8 +78,10 @@ def attention(out: np.ndarray, q, k, v, n_heads: int, dtype=DT_F32):
 
 
 def attention_cached(out: np.ndarray, q, k, v, n_heads: int, kv_dtype=DT_F32, n_chunks: int = 1, out_dtype=DT_F32, q_B: int = 0,
-                     len: int = -1, nq: int = 0):
+                     len: int = -1, nq: int = 0, key_lo=None):
     """layers.mojo:186-272, the q_len == 1 path over cached rows: q [B, d], k / v [B, t, d] -> out [B, d].
+    key_lo [B (or q_B)] (n_chunks == 1; wm_op_attention_cached_lo): utterance u sweeps rows [key_lo[u], len + 1 (+ p)) only; an empty
+    window gives zeros.
     n_chunks > 1: the cross-attention form (keys swept by several workgroups and merged).  out_dtype: what the kernels store
     (returned widened).  len >= 0 (n_chunks == 1): a row sweeps len + 1 of the t rows.  q_B > 0: prefill, q [P·q_B, d] position-major,
     k / v [q_B, t, d]: row p·q_B + b attends over utterance b (n_chunks == 1: its first len + 1 + p rows).  nq = 4: the chunked
@@ -93,6 +95,13 @@ def attention_cached(out: np.ndarray, q, k, v, n_heads: int, kv_dtype=DT_F32, n_
     if q_B > 0 and B % q_B:
         raise ValueError("prefill rows are position-major: q must be [P * q_B, d]")
     _chk_out(out, q.shape)
+    if key_lo is not None:
+        lo = np.ascontiguousarray(np.asarray(key_lo, np.int32).reshape(-1))
+        if lo.size != n_utt:
+            raise ValueError(f"key_lo needs one entry per utterance ({n_utt})")
+        _lib.check(_lib.lib().wm_op_attention_cached_lo(_fp(out), _fp(q), _fp(k), _fp(v), B, k.shape[1], n_heads, kv_dtype, n_chunks,
+                                                        out_dtype, q_B, len, nq, lo.ctypes.data_as(C.POINTER(C.c_int32))))
+        return
     _lib.check(_lib.lib().wm_op_attention_cached(_fp(out), _fp(q), _fp(k), _fp(v), B, k.shape[1], n_heads, kv_dtype, n_chunks, out_dtype,
                                                  q_B, len, nq))
 
