@@ -174,6 +174,29 @@ int wm_transcribe_rows(wm_model* m, const float* mel, int mel_on_device, int B, 
 int wm_transcribe_submit_rows(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* opts,
                               const int32_t* prompts, const int32_t* prompt_len, int prompt_stride);
 
+/* ---- log-probabilities -------------------------------------------------------------------------------------------
+ * wm_transcribe / wm_transcribe_submit / wm_transcribe_rows with the log-probability of every generated id (the ids after the prompt,
+ * a trailing eot included) and their mean per row: openai-whisper's avg_logprob, HF generate(output_scores=True) followed by
+ * WhisperGenerationMixin._retrieve_avg_logprobs(scores, ids, 0.0).  logprob = s[id] - logsumexp_j s[j], s the logits row after the
+ * processors this library applies: ids removed by suppress_tokens, by begin_suppress_tokens (first generated id only) or by the
+ * timestamp rules are -inf; when the timestamp rule forces a timestamp every text id is -inf and the normaliser runs over the
+ * admissible timestamps alone; with the rules off it runs over everything the mask leaves.  Computed by the fused argmax on the
+ * captured-graph path (stage 1 adds one exp per logit, stage 2 one merge); a pass without _lp launches exactly what it did before.
+ * prompts NULL: the shared prompt opts->prompt (prompt_len, prompt_stride ignored; the wm_transcribe_submit path, pairs under
+ * coalesce = 2 only with other _lp submits of the same shape and options); non-NULL: per-row prompts as wm_transcribe_rows (runs alone).
+ * token_logprobs: host fp32 in the layout of tokens_out; prompt positions and positions at and past n_tokens[b] are 0.
+ * avg_logprob: host [B], sum of the row's generated log-probs / their count; 0 when nothing was generated.
+ * A step whose candidates are all -inf (a mask over the whole vocabulary) emits id 0, as always; its log-prob is -inf, never NaN.
+ * WM_E_ARG, nothing launched: multi-lane decode states.  Log-probs together with token timestamps are not supported (there is no
+ * entry that asks for both).  wm_transcribe_wait_lp on a slot submitted without log-probs returns WM_E_STATE; wm_transcribe_wait on
+ * an _lp slot returns the ids. */
+int wm_transcribe_lp(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* opts, const int32_t* prompts,
+                     const int32_t* prompt_len, int prompt_stride, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs,
+                     float* avg_logprob);
+int wm_transcribe_submit_lp(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* opts,
+                            const int32_t* prompts, const int32_t* prompt_len, int prompt_stride);
+int wm_transcribe_wait_lp(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob);
+
 /* ---- token-level timestamps ---------------------------------------------------------------------------------
  * When each id was spoken, with the semantics of HF generate(..., return_token_timestamps=True)
  * (WhisperGenerationMixin._extract_token_timestamps, time_precision 0.02, median_filter_width 7, num_input_ids = n_prompt): the
@@ -344,6 +367,11 @@ int wm_op_dec_linear(float* out, const float* x, const float* W, const float* bi
  * x [B, K] fp32, K in {128, 384, 512}.  Known-answer tests. */
 int wm_op_logits(float* logits, int32_t* ids, const float* x, const float* ln_g, const float* ln_b, const float* emb, const float* mask,
                  const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype);
+/* wm_op_logits on the log-prob instantiation of the same kernel variant, plus logprob[B] = logits[id] - logsumexp over the candidates
+ * the processors leave (the rule of wm_transcribe_lp; all candidates -inf: id 0, logprob -inf).  logits and ids equal wm_op_logits's
+ * bit for bit. */
+int wm_op_logits_lp(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                    const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype);
 /* The absorbed cross-attention of bf16-encoder / fp32-K/V models: per row r and head h, with X = x[utt(r)] and
  * utt(r) = r % q_B when q_B > 0 (prefill rows, position-major; rows = P·q_B) else r,
  *   out[r, h] = Σ_j softmax_j(0.125·q_h[r]·(Wk_h X_j)) (Wv_h X_j) + bv_h,

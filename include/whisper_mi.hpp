@@ -11,6 +11,7 @@
 // wm_last_error().  examples/main.cpp is main.mojo:11-45 written against this header.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -156,6 +157,31 @@ public:
         check(wm_transcribe_tt(model_, mels, 0, B, &o, n_frames.empty() ? nullptr : n_frames.data(), toks.data(), n.data(), t.data()));
         times.assign(B, {});
         for (int b = 0; b < B; ++b) times[b].assign(t.begin() + (size_t)b * stride, t.begin() + (size_t)b * stride + n[b]);
+        return unpack(toks, n, B, stride);
+    }
+    // ids and, per id, its log-probability (0 at the prompt positions); avg_logprob per utterance.  prompts: one decoder
+    // prompt per utterance (empty = the model's shared prompt)
+    std::vector<std::vector<int>> transcribe_batch_lp(const float* mels, int B, std::vector<std::vector<float>>& token_logprobs,
+                                                      std::vector<float>& avg_logprob, int max_loop = MAX_LOOP,
+                                                      const std::vector<std::vector<int32_t>>& prompts = {}) const {
+        need_model();
+        wm_decode_opts o = opts(max_loop, false);
+        int lmax = 0;
+        for (const auto& r : prompts) lmax = std::max(lmax, (int)r.size());
+        std::vector<int32_t> tab((size_t)B * std::max(lmax, 1)), len(B);
+        for (size_t b = 0; b < prompts.size() && b < (size_t)B; ++b) {
+            len[b] = (int32_t)prompts[b].size();
+            std::copy(prompts[b].begin(), prompts[b].end(), tab.begin() + b * lmax);
+        }
+        const bool rows = !prompts.empty();
+        const int stride = (rows ? lmax : o.n_prompt) + 1 + max_loop;
+        std::vector<int32_t> toks((size_t)B * stride), n(B);
+        std::vector<float> lp((size_t)B * stride);
+        avg_logprob.assign(B, 0.f);
+        check(wm_transcribe_lp(model_, mels, 0, B, &o, rows ? tab.data() : nullptr, rows ? len.data() : nullptr, lmax, toks.data(), n.data(),
+                               lp.data(), avg_logprob.data()));
+        token_logprobs.assign(B, {});
+        for (int b = 0; b < B; ++b) token_logprobs[b].assign(lp.begin() + (size_t)b * stride, lp.begin() + (size_t)b * stride + n[b]);
         return unpack(toks, n, B, stride);
     }
     // sequential long-form transcription (HF generate's long-form path; needs set_timestamps): host mels

@@ -25,6 +25,7 @@ SYMBOLS = [
     "wm_long_result_stats", "wm_long_result_free", "wm_op_long_segments",
     "wm_transcribe_rows", "wm_transcribe_submit_rows", "wm_transcribe_long_ex", "wm_transcribe_long_pcm_ex", "wm_op_long_prompt",
     "wm_op_attention_cached_lo", "wm_long_result_prompt_stats",
+    "wm_transcribe_lp", "wm_transcribe_submit_lp", "wm_transcribe_wait_lp", "wm_op_logits_lp",
 ]
 
 ABI_VERSION = 4  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -146,6 +147,10 @@ def lib():
     L.wm_op_conv1d_k3.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.wm_op_argmax.argtypes = [fp, C.c_int, ip]
     L.wm_op_logits.argtypes = [fp, ip, fp, fp, fp, fp, fp, ip] + [C.c_int] * 5
+    L.wm_op_logits_lp.argtypes = [fp, ip, fp, fp, fp, fp, fp, fp, ip] + [C.c_int] * 5
+    L.wm_transcribe_lp.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip, C.c_int, ip, ip, fp, fp]
+    L.wm_transcribe_submit_lp.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip, C.c_int]
+    L.wm_transcribe_wait_lp.argtypes = [vp, C.c_int, ip, ip, fp, fp]
     L.wm_op_xattn.argtypes = [fp] * 6 + [C.c_int] * 7
     L.wm_bench_kernel.argtypes = [vp, vp, C.c_int, C.c_int, fp]
     L.wm_bench_bytes.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double)]

@@ -327,7 +327,9 @@ template <int NRB> struct LogitsScratch {
     float (*tm)[NRB * 16];
     float (*ts)[NRB * 16];
     int (*ti)[NRB * 16];
+    float (*ls)[NRB * 16];  // [8 waves][row], log-prob kernels only: sum of exp(v - wave max) over the wave's admissible text candidates
     static constexpr size_t bytes = (size_t)(2 * 32 + 4 * 8) * NRB * 16 * 4;
+    static constexpr size_t bytes_lp = bytes + (size_t)8 * NRB * 16 * 4;
     __device__ static LogitsScratch carve(unsigned char* base) {
         LogitsScratch s;
         float* f = reinterpret_cast<float*>(base);
@@ -337,12 +339,16 @@ template <int NRB> struct LogitsScratch {
         s.tm = reinterpret_cast<float (*)[NRB * 16]>(f + 72 * NRB * 16);
         s.ts = reinterpret_cast<float (*)[NRB * 16]>(f + 80 * NRB * 16);
         s.ti = reinterpret_cast<int (*)[NRB * 16]>(f + 88 * NRB * 16);
+        s.ls = reinterpret_cast<float (*)[NRB * 16]>(f + 96 * NRB * 16);  // past `bytes`: touched by the log-prob kernels only
         return s;
     }
 };
 // Shared tail of the logits kernels.  acc[nb][rb][r] = logits[row0 + 16 rb + r16][n0[nb] + 4 g + r]: optional store of the
 // logits, then the fused argmax's stage 1 (and the timestamp-side partials when the rules are on).
-template <int NRB>
+// LP (log-probabilities): also the text side of the softmax normaliser — per part the sum of exp(v - amax_val) over the
+// candidates the argmax admits (same mask, same [text_lo, text_hi) test), amax_val being their maximum: every term is <= 1, so a
+// logits row offset by 1e4 cannot overflow.  LP = false compiles to exactly the kernel without it.
+template <int NRB, bool LP>
 __device__ __forceinline__ void logits_epilogue(const DecLinearParams& p, int CT, const f32x4 (&acc)[2][NRB], const int (&n0)[2],
                                                 const bool (&have)[2], const float (&mk)[2][4], int row0, int nrows, int lane, int w,
                                                 const LogitsScratch<NRB>& sc) {
@@ -398,6 +404,24 @@ __device__ __forceinline__ void logits_epilogue(const DecLinearParams& p, int CT
                         bi = n;
                     }
                 }
+            if constexpr (LP) {
+                float ls = 0.f, lm = bv;  // the lane's maximum IS its best value
+#pragma unroll
+                for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int n = n0[nb] + g * 4 + r;
+                        if (have[nb] && n < p.N && n >= t_lo && n < t_hi && cand[nb][r] > -INFINITY) ls += expf(cand[nb][r] - lm);
+                    }
+#pragma unroll
+                for (int o = 16; o <= 32; o <<= 1) {  // the 4 lanes of a row (lane group 0 holds the value that is kept)
+                    const float m2 = __shfl_xor(lm, o, 64), s2 = __shfl_xor(ls, o, 64);
+                    const float mn = fmaxf(lm, m2);
+                    ls = (ls > 0.f ? ls * expf(lm - mn) : 0.f) + (s2 > 0.f ? s2 * expf(m2 - mn) : 0.f);
+                    lm = mn;
+                }
+                if (g == 0) sc.ls[w][rb * 16 + r16] = ls;  // relative to the wave's maximum = max of its four s_av entries
+            }
             if (wg_ts) {
                 float tv = -INFINITY, tsum = 0.f;
                 int ti = 0x7fffffff;
@@ -457,6 +481,17 @@ __device__ __forceinline__ void logits_epilogue(const DecLinearParams& p, int CT
             const size_t o = (size_t)(row0 + threadIdx.x) * p.amax_stride + blockIdx.x;
             p.amax_val[o] = bv;
             p.amax_idx[o] = bi;
+            if constexpr (LP) {  // the 8 waves' sums in wave order, rescaled to the part's maximum bv
+                float tot = 0.f;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const float wm = fmaxf(fmaxf(s_av[4 * k][threadIdx.x], s_av[4 * k + 1][threadIdx.x]),
+                                           fmaxf(s_av[4 * k + 2][threadIdx.x], s_av[4 * k + 3][threadIdx.x]));
+                    const float s2 = sc.ls[k][threadIdx.x];
+                    if (s2 > 0.f) tot += s2 * expf(wm - bv);
+                }
+                p.lp_s[o] = tot;
+            }
             if (wg_ts) {  // the 8 waves' timestamp partials, in wave order (deterministic)
                 float tv = s_tv[0][threadIdx.x], tm = s_tm[0][threadIdx.x], tsum = s_ts[0][threadIdx.x];
                 int ti = s_ti[0][threadIdx.x];
@@ -488,7 +523,7 @@ __device__ __forceinline__ void logits_epilogue(const DecLinearParams& p, int CT
 // workgroup (LN statistics from a 4-thread-per-row sweep, everything in flight at once) and parked in LDS as MFMA
 // operands, so L2 sees x once per 128 columns; each wave then streams its 32 embedding rows straight from HBM into
 // registers (all k-steps in flight) and needs no cross-wave reduction.
-template <typename TW, int KD /* d_model/128 */, int NRB>
+template <typename TW, int KD /* d_model/128 */, int NRB, bool LP = false>
 __global__ __launch_bounds__(512) void dec_logits_kernel(DecLinearParams p, int CT) {
     // One workgroup = 8 waves = CT <= 16 column tiles of 16 vocabulary rows (wave w owns tiles w and w+8), all NRB*16
     // utterance rows.  CT is chosen by the launcher so that the whole vocabulary is ONE round of <= 256 workgroups
@@ -658,11 +693,17 @@ __global__ __launch_bounds__(512) void dec_logits_kernel(DecLinearParams p, int 
         sc.tm = s_tm;
         sc.ts = s_ts;
         sc.ti = s_ti;
-        logits_epilogue<NRB>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, sc);
+        sc.ls = nullptr;
+        if constexpr (LP) {
+            __shared__ float s_ls[8][NRB * 16];
+            sc.ls = s_ls;
+        }
+        logits_epilogue<NRB, LP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, sc);
     } else {  // 128 rows: the 48 KB of scratch do not fit beside the activation image — overlay it once every wave is done reading
         __syncthreads();
-        static_assert(LogitsScratch<NRB>::bytes <= (size_t)NRB * 16 * PITCH * sizeof(TW), "epilogue scratch must fit the activation image");
-        logits_epilogue<NRB>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
+        static_assert((LP ? LogitsScratch<NRB>::bytes_lp : LogitsScratch<NRB>::bytes) <= (size_t)NRB * 16 * PITCH * sizeof(TW),
+                      "epilogue scratch must fit the activation image");
+        logits_epilogue<NRB, LP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
     }
     WM_LG_STAMP(4);
 }
@@ -710,7 +751,7 @@ __device__ __forceinline__ f32x4 mma_bf16(const bf16x8& a, const bf16x8& b, f32x
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-template <int KD /* d_model/128 */, int NRB>
+template <int KD /* d_model/128 */, int NRB, bool LP = false>
 __global__ __launch_bounds__(512) void dec_logits_split_kernel(DecLinearParams p, int CT) {
     // Geometry as dec_logits_kernel: 8 waves, wave w owns column tiles w and w + 8 of the workgroup's CT <= 16, all NRB*16 rows.
     constexpr int K = KD * 128;
@@ -876,8 +917,9 @@ __global__ __launch_bounds__(512) void dec_logits_split_kernel(DecLinearParams p
         body(std::integral_constant<int, 1>{});
     WM_LG_STAMP(3);
     __syncthreads();  // every wave is past its last fragment read: the epilogue's scratch overlays the activation images
-    static_assert(LogitsScratch<NRB>::bytes <= (size_t)3 * IMG * sizeof(bf16), "epilogue scratch must fit the activation images");
-    logits_epilogue<NRB>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
+    static_assert((LP ? LogitsScratch<NRB>::bytes_lp : LogitsScratch<NRB>::bytes) <= (size_t)3 * IMG * sizeof(bf16),
+                  "epilogue scratch must fit the activation images");
+    logits_epilogue<NRB, LP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
     WM_LG_STAMP(4);
 }
 #undef WM_LG_STAMP
@@ -889,7 +931,7 @@ __global__ __launch_bounds__(512) void dec_logits_split_kernel(DecLinearParams p
 // LayerNorm statistics are summed in the same order (a thread carries the two partial sums of the two "virtual" threads the
 // 8-threads-per-row scheme gives its elements to), the k-steps accumulate in the same order — so the ids of a coalesced pass equal
 // the uncoalesced ones bit for bit.
-template <int KD /* d_model/128 */>
+template <int KD /* d_model/128 */, bool LP = false>
 __global__ __launch_bounds__(512) void dec_logits_split128_kernel(DecLinearParams p, int CT) {
     constexpr int NRB = 8, ROWS = 128;
     constexpr int K = KD * 128, KH = K / 2;  // columns per pass
@@ -1087,29 +1129,30 @@ __global__ __launch_bounds__(512) void dec_logits_split128_kernel(DecLinearParam
         run(std::integral_constant<int, 0>{});
     WM_LG_STAMP(3);
     __syncthreads();  // the epilogue's scratch overlays the activation images
-    static_assert(LogitsScratch<NRB>::bytes <= (size_t)3 * IMG * sizeof(bf16), "epilogue scratch must fit the activation images");
-    logits_epilogue<NRB>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
+    static_assert((LP ? LogitsScratch<NRB>::bytes_lp : LogitsScratch<NRB>::bytes) <= (size_t)3 * IMG * sizeof(bf16),
+                  "epilogue scratch must fit the activation images");
+    logits_epilogue<NRB, LP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
     WM_LG_STAMP(4);
 }
 #undef WM_LG_STAMP
-template <int KD> static int launch_dec_logits_split128_t(const DecLinearParams& p, hipStream_t st) {
+template <int KD, bool LP = false> static int launch_dec_logits_split128_t(const DecLinearParams& p, hipStream_t st) {
     const size_t lds = (size_t)3 * 128 * (KD * 64 + 16) * sizeof(bf16) + (size_t)2 * KD * 128 * sizeof(float);
     if (lds > 48 * 1024)
-        if (const hipError_t e = ensure_dyn_lds<&dec_logits_split128_kernel<KD>>((int)lds); e != hipSuccess)
+        if (const hipError_t e = ensure_dyn_lds<&dec_logits_split128_kernel<KD, LP>>((int)lds); e != hipSuccess)
             return launch_hip_failed("logits kernel (split fp32, 128 rows): dynamic LDS attribute", e);
     const int ct = dec_logits_tiles_per_wg(p.N);
     dim3 grid(dec_logits_parts(p.N), (p.B + 127) / 128);
-    hipLaunchKernelGGL((dec_logits_split128_kernel<KD>), grid, dim3(512), lds, st, p, ct);
+    hipLaunchKernelGGL((dec_logits_split128_kernel<KD, LP>), grid, dim3(512), lds, st, p, ct);
     return WM_LAUNCH_OK;
 }
-template <int KD, int NRB> static int launch_dec_logits_split_t(const DecLinearParams& p, hipStream_t st) {
+template <int KD, int NRB, bool LP = false> static int launch_dec_logits_split_t(const DecLinearParams& p, hipStream_t st) {
     const size_t lds = (size_t)3 * NRB * 16 * (KD * 128 + 16) * sizeof(bf16) + (size_t)2 * KD * 128 * sizeof(float);
     if (lds > 48 * 1024)
-        if (const hipError_t e = ensure_dyn_lds<&dec_logits_split_kernel<KD, NRB>>((int)lds); e != hipSuccess)
+        if (const hipError_t e = ensure_dyn_lds<&dec_logits_split_kernel<KD, NRB, LP>>((int)lds); e != hipSuccess)
             return launch_hip_failed("logits kernel (split fp32): dynamic LDS attribute", e);
     const int ct = dec_logits_tiles_per_wg(p.N);
     dim3 grid(dec_logits_parts(p.N), (p.B + NRB * 16 - 1) / (NRB * 16));
-    hipLaunchKernelGGL((dec_logits_split_kernel<KD, NRB>), grid, dim3(512), lds, st, p, ct);
+    hipLaunchKernelGGL((dec_logits_split_kernel<KD, NRB, LP>), grid, dim3(512), lds, st, p, ct);
     return WM_LAUNCH_OK;
 }
 
@@ -1127,39 +1170,40 @@ int dec_logits_parts(int N) {
     const int tiles = (N + 15) / 16, ct = dec_logits_tiles_per_wg(N);
     return (tiles + ct - 1) / ct;
 }
-template <typename TW, int KD, int NRB> static int launch_dec_logits_t(const DecLinearParams& p, hipStream_t st) {
+template <typename TW, int KD, int NRB, bool LP = false> static int launch_dec_logits_t(const DecLinearParams& p, hipStream_t st) {
     const size_t lds = (size_t)NRB * 16 * (KD * 128 + (sizeof(TW) == 2 ? 80 : 16 / sizeof(TW))) * sizeof(TW);
     if (lds > 48 * 1024)
-        if (const hipError_t e = ensure_dyn_lds<&dec_logits_kernel<TW, KD, NRB>>((int)lds); e != hipSuccess)
+        if (const hipError_t e = ensure_dyn_lds<&dec_logits_kernel<TW, KD, NRB, LP>>((int)lds); e != hipSuccess)
             return launch_hip_failed("logits kernel: dynamic LDS attribute", e);
     const int ct = dec_logits_tiles_per_wg(p.N);
     dim3 grid(dec_logits_parts(p.N), (p.B + NRB * 16 - 1) / (NRB * 16));
-    hipLaunchKernelGGL((dec_logits_kernel<TW, KD, NRB>), grid, dim3(512), lds, st, p, ct);
+    hipLaunchKernelGGL((dec_logits_kernel<TW, KD, NRB, LP>), grid, dim3(512), lds, st, p, ct);
     return WM_LAUNCH_OK;
 }
 // requires ln_g/ln_b, no bias/act/residual, K in {128, 384, 512}, ldo % 4 == 0; amax_stride >= dec_logits_parts(N)
-template <typename TW> int launch_dec_logits(const DecLinearParams& p, hipStream_t st) {
+template <typename TW, bool LP> static int launch_dec_logits_lp(const DecLinearParams& p, hipStream_t st) {
     const int kd = p.K >> 7;
     if (p.B <= 0 || p.N <= 0) return launch_refuse("dec_logits: empty problem");
     if ((p.K & 127) != 0 || (kd != 1 && kd != 3 && kd != 4)) return launch_refuse("dec_logits: d_model must be 128, 384 or 512");
     if (!p.ln_g || !p.ln_b) return launch_refuse("dec_logits: the final LayerNorm's gamma / beta are required");
     if (p.amax_val && p.amax_stride < dec_logits_parts(p.N)) return launch_refuse("dec_logits: amax_stride is smaller than the partials per utterance");
+    if (LP && !p.amax_val) return launch_refuse("dec_logits: log-probabilities need the fused argmax (amax_val)");
     if constexpr (sizeof(TW) == 4) {
         // fp32 weights: the three-way bf16 split (d_model 128 / 384: three activation images fit the 160 KB of LDS); d_model 512
         // keeps the exact-fp32 MFMA kernel.  WM_LOGITS_EXACT (developer build) forces the exact kernel for A/B runs.
         static const bool exact = wm_env("WM_LOGITS_EXACT") != nullptr;
         if (!exact && (kd == 1 || kd == 3)) {
-            if (p.B <= 16) return kd == 1 ? launch_dec_logits_split_t<1, 1>(p, st) : launch_dec_logits_split_t<3, 1>(p, st);
+            if (p.B <= 16) return kd == 1 ? launch_dec_logits_split_t<1, 1, LP>(p, st) : launch_dec_logits_split_t<3, 1, LP>(p, st);
             // more than 64 rows (coalesced batches): 128 rows per workgroup, the embedding streamed once per 128 (WM_LOGITS_NO128: A/B)
             static const bool no128 = wm_env("WM_LOGITS_NO128") != nullptr;
-            if (p.B > 64 && !no128) return kd == 1 ? launch_dec_logits_split128_t<1>(p, st) : launch_dec_logits_split128_t<3>(p, st);
-            return kd == 1 ? launch_dec_logits_split_t<1, 4>(p, st) : launch_dec_logits_split_t<3, 4>(p, st);
+            if (p.B > 64 && !no128) return kd == 1 ? launch_dec_logits_split128_t<1, LP>(p, st) : launch_dec_logits_split128_t<3, LP>(p, st);
+            return kd == 1 ? launch_dec_logits_split_t<1, 4, LP>(p, st) : launch_dec_logits_split_t<3, 4, LP>(p, st);
         }
     }
     if (p.B <= 16) {
-        if (kd == 1) return launch_dec_logits_t<TW, 1, 1>(p, st);
-        if (kd == 3) return launch_dec_logits_t<TW, 3, 1>(p, st);
-        return launch_dec_logits_t<TW, 4, 1>(p, st);
+        if (kd == 1) return launch_dec_logits_t<TW, 1, 1, LP>(p, st);
+        if (kd == 3) return launch_dec_logits_t<TW, 3, 1, LP>(p, st);
+        return launch_dec_logits_t<TW, 4, 1, LP>(p, st);
     }
 #ifdef WM_DEV
     if constexpr (sizeof(TW) == 2) {
@@ -1169,15 +1213,19 @@ template <typename TW> int launch_dec_logits(const DecLinearParams& p, hipStream
         // the rows behind one stream.  The fp32 form (80 MB per stream, MFMA-heavy) does gain: dec_logits_split128_kernel.
         static const bool on128 = wm_env("WM_LOGITS_128_16BIT") != nullptr;
         if (p.B > 64 && on128) {
-            if (kd == 1) return launch_dec_logits_t<TW, 1, 8>(p, st);
-            if (kd == 3) return launch_dec_logits_t<TW, 3, 8>(p, st);
-            return launch_dec_logits_t<TW, 4, 8>(p, st);
+            if (kd == 1) return launch_dec_logits_t<TW, 1, 8, LP>(p, st);
+            if (kd == 3) return launch_dec_logits_t<TW, 3, 8, LP>(p, st);
+            return launch_dec_logits_t<TW, 4, 8, LP>(p, st);
         }
     }
 #endif
-    if (kd == 1) return launch_dec_logits_t<TW, 1, 4>(p, st);
-    if (kd == 3) return launch_dec_logits_t<TW, 3, 4>(p, st);
-    return launch_dec_logits_t<TW, 4, 4>(p, st);
+    if (kd == 1) return launch_dec_logits_t<TW, 1, 4, LP>(p, st);
+    if (kd == 3) return launch_dec_logits_t<TW, 3, 4, LP>(p, st);
+    return launch_dec_logits_t<TW, 4, 4, LP>(p, st);
+}
+// p.lp_s null: exactly the kernels, grids and LDS of a pass without log-probabilities; non-null: the LP instantiation of the same variant
+template <typename TW> int launch_dec_logits(const DecLinearParams& p, hipStream_t st) {
+    return p.lp_s ? launch_dec_logits_lp<TW, true>(p, st) : launch_dec_logits_lp<TW, false>(p, st);
 }
 template int launch_dec_logits<float>(const DecLinearParams&, hipStream_t);
 template int launch_dec_logits<bf16>(const DecLinearParams&, hipStream_t);
@@ -1876,6 +1924,8 @@ __device__ __forceinline__ void argmax_partials(const float* pv, const int* pi, 
     best = mv;
     bidx = mi;
 }
+// LP: the log-probability instantiation (p.lp_s non-null); LP = false is the kernel without it, static LDS included
+template <bool LP>
 __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
     const int b = blockIdx.x;
     if (p.ts && b == 0 && threadIdx.x == 0) ts_put(p.ts, p.ts_id, 3);
@@ -1893,6 +1943,25 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
         argmax_partials(p.pval + (size_t)b * p.npart, p.pidx + (size_t)b * p.npart, p.npart, best, idx);
     else
         argmax_block(p.logits + (size_t)b * p.ldl, p.V, best, idx);
+    // Log-probabilities (lp_s null = off): lp = s[id] - logsumexp(s) over what the processors leave.  Text side: part k
+    // contributes lp_s[k] * exp(pval[k] - best) — the exp terms by all threads, the sum by thread 0 in ascending part order, so a
+    // row's value does not depend on the batch it sits in.
+    float txt_s = 0.f, lp = -INFINITY;  // thread 0: sum of exp(text - best); the chosen id's log-probability
+    if constexpr (LP) {
+        __shared__ float s_term[256];
+        for (int k0 = 0; k0 < p.npart; k0 += 256) {
+            const int k = k0 + (int)threadIdx.x;
+            if (threadIdx.x < 256 && k < p.npart) {
+                const float s2 = p.lp_s[(size_t)b * p.npart + k];
+                s_term[threadIdx.x] = s2 > 0.f ? s2 * expf(p.pval[(size_t)b * p.npart + k] - best) : 0.f;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0)
+                for (int j = 0; j < min(256, p.npart - k0); ++j) txt_s += s_term[j];
+            __syncthreads();
+        }
+        if (!p.ts_state && txt_s > 0.f) lp = -logf(txt_s);  // best - (best + log sum); every candidate -inf: stays -inf, never NaN
+    }
     if (p.ts_state) {
         // Timestamp rules, the decision (HF WhisperTimeStampLogitsProcessor rule 5 + the final argmax): (best, idx) is the best
         // admissible text id; if the admissible timestamps' probability mass exceeds it — logsumexp(ts) > best, the softmax
@@ -1916,7 +1985,18 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
             }
             int pick = idx;
             const bool have_text = (unsigned)idx < (unsigned)p.V;
-            if (tsum > 0.f && (!have_text || tm + logf(tsum) > best)) pick = ti;
+            const bool forced = tsum > 0.f && (!have_text || tm + logf(tsum) > best);
+            if (forced) pick = ti;
+            if constexpr (LP) {
+                // forced timestamp: HF sets every text id to -inf, the normaliser is the admissible timestamps' alone; else text ∪ timestamps
+                if (forced) {
+                    lp = (tv - tm) - logf(tsum);  // differences first: a row offset by 1e4 keeps its low bits
+                } else if (have_text) {
+                    const float mn = fmaxf(best, tm);
+                    const float tot = (txt_s > 0.f ? txt_s * expf(best - mn) : 0.f) + (tsum > 0.f ? tsum * expf(tm - mn) : 0.f);
+                    if (tot > 0.f) lp = (best - mn) - logf(tot);
+                }
+            }
             if ((unsigned)pick >= (unsigned)p.V) pick = 0;
             TsState st = p.ts_state[b];
             const int is_ts = pick >= p.rules.tb;
@@ -1937,12 +2017,17 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
     if ((unsigned)idx >= (unsigned)p.V) idx = 0;
     if (threadIdx.x == 0) {
         p.next[b] = idx;
+        if (LP && p.lp_next) p.lp_next[b] = lp;
         if (p.advance) {  // current_len += 1 (layers.mojo:143), position += 1: nothing else in this launch reads them
             p.pos[b] += 1;
             if (b == 0) p.ctl->len += 1;
         }
         if (p.out_tokens && !p.finished[b]) {
             p.out_tokens[(size_t)b * p.out_stride + p.n_tokens[b]] = idx;
+            if (LP && p.logprobs) {
+                p.logprobs[(size_t)b * p.out_stride + p.n_tokens[b]] = lp;
+                p.lp_sum[b] += lp;
+            }
             p.n_tokens[b] += 1;
             if (!p.ignore_eot && idx == p.eot) {
                 p.finished[b] = 1;
@@ -1957,7 +2042,10 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
     }
 }
 void launch_argmax_step(const ArgmaxParams& p, hipStream_t st) {
-    hipLaunchKernelGGL(argmax_step_kernel, dim3(p.B), dim3(p.pval ? 256 : 1024), 0, st, p);
+    if (p.lp_s && p.pval)
+        hipLaunchKernelGGL(argmax_step_kernel<true>, dim3(p.B), dim3(256), 0, st, p);
+    else
+        hipLaunchKernelGGL(argmax_step_kernel<false>, dim3(p.B), dim3(p.pval ? 256 : 1024), 0, st, p);
 }
 __global__ __launch_bounds__(1024) void argmax_plain_kernel(const float* t, int n, int* idx) {
     float best;
@@ -1977,6 +2065,10 @@ __global__ void init_tokens_kernel(InitTokensParams p) {
         for (int i = 0; i < p.n_prompt; ++i) p.out_tokens[(size_t)b * p.out_stride + i] = p.prompt[i];
         p.n_tokens[b] = p.n_prompt;
         p.finished[b] = 0;
+        if (p.logprobs) {  // prompt and tail positions of the log-prob table stay 0
+            for (int i = 0; i < p.out_stride; ++i) p.logprobs[(size_t)b * p.out_stride + i] = 0.f;
+            p.lp_sum[b] = 0.f;
+        }
         if (p.tok_rows) {
             for (int i = 0; i < p.n_prompt; ++i) {
                 p.tok_rows[i * p.B + b] = p.prompt[i];
@@ -2012,6 +2104,10 @@ __global__ void init_tokens_rows_kernel(InitTokensParams p, RowPromptParams r) {
         for (int i = 0; i < Lb; ++i) p.out_tokens[(size_t)b * p.out_stride + i] = row[i];
         p.n_tokens[b] = Lb;
         p.finished[b] = 0;
+        if (p.logprobs) {
+            for (int i = 0; i < p.out_stride; ++i) p.logprobs[(size_t)b * p.out_stride + i] = 0.f;
+            p.lp_sum[b] = 0.f;
+        }
         r.key_lo[b] = pad;
         for (int t = 0; t < r.Lmax; ++t) {
             p.tok_rows[(size_t)t * p.B + b] = t < pad ? row[0] : row[t - pad];

@@ -232,12 +232,14 @@ struct wm_model {
         std::vector<int32_t> prompt, sup, bsup;  // deep copies: the caller's option arrays need not outlive the call
         bool tt = false;                          // token timestamps asked for; cols = columns kept per row
         std::vector<int32_t> cols;
+        bool lp = false;                          // log-probabilities asked for: pairs only with another such submit
     } held;
     struct SlotRef {  // where a submitted slot's rows live
         bool pending = false;
         wm_state* st = nullptr;  // null while the slot is only held
         int row0 = 0, rows = 0, total = 0;
         bool tt = false;
+        bool lp = false;  // the pass computes log-probabilities (wm_transcribe_wait_lp may collect them)
     } slot_ref[8];
     wm_state* pairs[4] = {};  // 2·B-row states of coalesced pairs
     int last_steps[8] = {-1, -1, -1, -1, -1, -1, -1, -1};  // loop iterations enqueued for each slot's last collected pass
@@ -353,6 +355,14 @@ struct wm_state {
         std::vector<int32_t> h_table, h_len;
     } rw;
     bool graph_rows = false;  // the captured step graph's self-attention is the key-window form
+    // log-probabilities of the pending pass (on = wm_transcribe_lp and its kin): stage 1's text-side sums [B][npart], the
+    // table [B][out_stride] that mirrors out_tokens (zeroed by the init-tokens launch) and the per-row sums.  Part of the arena.
+    struct Lp {
+        bool on = false;
+        DevBuf part_s, table, sum;
+        std::vector<int32_t> n_prompt;  // [B] prompt length of each row of the pending pass
+    } lp;
+    bool graph_lp = false;  // the captured step graph computes log-probabilities
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -833,7 +843,7 @@ extern "C" void wm_state_free(wm_state* s) {
                     &s->cross_kv, &s->enc_x, &s->xq, &s->part_y, &s->self_kv, &s->dx, &s->dq, &s->dattn, &s->dhid, &s->part_o, &s->part_ml, &s->logits, &s->amax_val, &s->amax_idx, &s->ts_state, &s->ts_val, &s->ts_idx, &s->ts_m, &s->ts_s, &s->mask_steady, &s->mask_begin,
                     &s->tok, &s->pos, &s->tok_rows, &s->pos_rows, &s->ctl, &s->out_tokens, &s->n_tokens, &s->finished,
                     &s->al.cap, &s->al.kh, &s->al.probs, &s->al.mean, &s->al.stdv, &s->al.M, &s->al.trace, &s->al.times, &s->al.ncols,
-                    &s->rw.table, &s->rw.len, &s->rw.key_lo};
+                    &s->rw.table, &s->rw.len, &s->rw.key_lo, &s->lp.part_s, &s->lp.table, &s->lp.sum};
     for (DevBuf* b : bs) b->release();
     delete s;
 }
@@ -944,6 +954,9 @@ static int state_new(wm_model* m, int B, wm_state** out, bool pair) {
     A(s->out_tokens, (size_t)B * s->out_stride * 4, true);
     A(s->n_tokens, (size_t)B * 4, true);
     A(s->finished, (size_t)B * 4, true);
+    A(s->lp.part_s, (size_t)B * s->npart * 4, true);
+    A(s->lp.table, (size_t)B * s->out_stride * 4, true);
+    A(s->lp.sum, (size_t)B * 4, true);
     if (rc) {
         std::string keep = g_err;
         wm_state_free(s);
@@ -1504,6 +1517,7 @@ static int decode_core(wm_model* m, wm_state* s, const DecView& v, bool want_log
             p.ts_m = s->ts_m.as<float>() + (size_t)v.b0 * s->npart;
             p.ts_s = s->ts_s.as<float>() + (size_t)v.b0 * s->npart;
         }
+        if (s->lp.on) p.lp_s = s->lp.part_s.as<float>() + (size_t)v.b0 * s->npart;
         p.ts = (long long*)m->ts_buf.p;
         p.ts_id = s->trace_id;
         int lrc = 0;
@@ -1537,6 +1551,11 @@ static ArgmaxParams argmax_params(wm_model* m, wm_state* s, const DecView& v, bo
     a.out_stride = s->out_stride;
     a.n_tokens = s->n_tokens.as<int>() + v.b0;
     a.finished = s->finished.as<int>() + v.b0;
+    if (s->lp.on && record) {
+        a.lp_s = s->lp.part_s.as<float>() + (size_t)v.b0 * s->npart;
+        a.logprobs = s->lp.table.as<float>() + (size_t)v.b0 * s->out_stride;
+        a.lp_sum = s->lp.sum.as<float>() + v.b0;
+    }
     a.ctl = v.ctl;
     a.eot = eot;
     a.ignore_eot = ignore_eot;
@@ -1760,7 +1779,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
     if (s->al.on) cap_key = wm_state::CapKey{s->al.cap.p, s->al.L, s->al.n_prompt, s->al.pairs};
     const bool recapture = !s->graphs_valid || s->graph_eot != o->eot || s->graph_ignore != o->ignore_eot ||
                            s->graph_shares != s->shares_chip || memcmp(&s->graph_rules, &rules, sizeof rules) != 0 || s->graph_cap != cap_key ||
-                           s->graph_rows != s->rw.on;
+                           s->graph_rows != s->rw.on || s->graph_lp != s->lp.on;
     const int first_pos = o->pos_mode == WM_POS_REF ? o->n_prompt - 1 : o->n_prompt;
     // logit masks (§8f rank 4): rebuilt only when the id lists change; always passed (all-zero = the reference's raw argmax)
     {
@@ -1800,6 +1819,8 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
         ip.pos_rows = s->pos_rows.as<int>();
         ip.ts_state = rp ? s->ts_state.as<TsState>() + v.b0 : nullptr;
         ip.rules = rules;
+        ip.logprobs = s->lp.on ? s->lp.table.as<float>() + (size_t)v.b0 * s->out_stride : nullptr;
+        ip.lp_sum = s->lp.on ? s->lp.sum.as<float>() + v.b0 : nullptr;
         if (s->rw.on) {
             WMCHK(prefill_rows(m, s, v, ip, o, rp));
         } else {
@@ -1852,6 +1873,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
     s->graph_shares = s->shares_chip;
     s->graph_cap = cap_key;
     s->graph_rows = s->rw.on;
+    s->graph_lp = s->lp.on;
     if (trace_phase) {
         for (auto& ln : s->lanes) (void)hipStreamSynchronize(ln.st);
         fprintf(stderr, "[wm] encoder wait + prefill (+graph capture if any): %.3f ms\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count() * 1e3);
@@ -1944,8 +1966,10 @@ static int rows_setup(wm_model* m, wm_state* s, const RowPrompts* rows) {
 }
 static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, bool allow_poll,
                      const float* mel2 = nullptr, int mel2_on_device = 0, const std::vector<int32_t>* cols = nullptr,
-                     const RowPrompts* rows = nullptr) {
+                     const RowPrompts* rows = nullptr, bool lp = false) {
     const wm_dims& c = m->cfg.dims;
+    if (lp && (cols || dec_lanes_for(B) != 1))  // (the entry points refuse both before anything is touched; kept for internal callers)
+        return fail(WM_E_ARG, "log-probabilities need a single-lane decode state and a pass without token timestamps");
     HIPCHK(hipSetDevice(m->device));
     const bool pair = mel2 != nullptr;
     // a pass that was submitted and not yet waited for owns the slot's state: refuse BEFORE touching it (re-creating the
@@ -1958,6 +1982,13 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
     }
     wm_state* s = *slot;
     WMCHK(rows_setup(m, s, rows));
+    s->lp.on = lp;
+    if (lp) {
+        if (rows)
+            s->lp.n_prompt.assign(rows->len, rows->len + B);
+        else
+            s->lp.n_prompt.assign(B, o->n_prompt);
+    }
     s->trace_id = slot == &m->cached ? 1 : (slot >= m->slots && slot < m->slots + (wm_model::NSLOT - 1)) ? 2 + (int)(slot - m->slots)
                 : (slot == &m->lf.st[0] || slot == &m->lf.st[1]) ? 20 + (int)(slot - m->lf.st) : 10 + (int)(slot - m->pairs);
     // The whole pass — encoder, prefill, greedy loop — goes on the slot's own stream: four slots are then four hardware
@@ -2011,7 +2042,7 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
 // Blocks until the state's pending pass is complete, then copies `rows` utterances starting at row0 out.  The pass stays pending
 // until every slot that shares the state (one, or the two of a coalesced pair) has collected its rows.
 static int wait_on(wm_model* m, wm_state* s, int32_t* tokens_out, int32_t* n_tokens, int row0 = 0, int rows = -1, int32_t* dev_packed = nullptr,
-                   int rows_cap = 0, int pack_stride = 0, float* token_times = nullptr) {
+                   int rows_cap = 0, int pack_stride = 0, float* token_times = nullptr, float* token_logprobs = nullptr, float* avg_logprob = nullptr) {
     if (!s || !s->pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
     HIPCHK(hipSetDevice(m->device));
     if (rows < 0) rows = s->B;
@@ -2041,6 +2072,15 @@ static int wait_on(wm_model* m, wm_state* s, int32_t* tokens_out, int32_t* n_tok
         if (token_times)
             HIPCHK(hipMemcpy2D(token_times, (size_t)total * 4, s->al.times.as<float>() + (size_t)row0 * s->out_stride, (size_t)s->out_stride * 4,
                                (size_t)total * 4, rows, hipMemcpyDeviceToHost));
+        if (token_logprobs) {  // (the callers checked that the pass computed them)
+            HIPCHK(hipMemcpy2D(token_logprobs, (size_t)total * 4, s->lp.table.as<float>() + (size_t)row0 * s->out_stride, (size_t)s->out_stride * 4,
+                               (size_t)total * 4, rows, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(avg_logprob, s->lp.sum.as<float>() + row0, (size_t)rows * 4, hipMemcpyDeviceToHost));
+            for (int b = 0; b < rows; ++b) {  // HF _retrieve_avg_logprobs: sum / generated ids (eot included); nothing generated: 0
+                const int gen = n_tokens[b] - s->lp.n_prompt[row0 + b];
+                avg_logprob[b] = gen > 0 ? avg_logprob[b] / (float)gen : 0.f;
+            }
+        }
     }
     if (--s->halves_left <= 0) {
         s->pending = false;
@@ -2062,8 +2102,9 @@ static bool same_opts(const wm_model::Held& h, const wm_decode_opts* o) {
     return std::equal(h.prompt.begin(), h.prompt.end(), o->prompt) && std::equal(h.sup.begin(), h.sup.end(), o->suppress_tokens) &&
            std::equal(h.bsup.begin(), h.bsup.end(), o->begin_suppress_tokens);
 }
-static void hold(wm_model* m, int slot, const float* mel, int on_dev, int B, const wm_decode_opts* o, const std::vector<int32_t>* cols) {
+static void hold(wm_model* m, int slot, const float* mel, int on_dev, int B, const wm_decode_opts* o, const std::vector<int32_t>* cols, bool lp) {
     wm_model::Held& h = m->held;
+    h.lp = lp;
     h.tt = cols != nullptr;
     h.cols = cols ? *cols : std::vector<int32_t>();
     h.active = true;
@@ -2080,7 +2121,7 @@ static void hold(wm_model* m, int slot, const float* mel, int on_dev, int B, con
     h.o.n_suppress = (int)h.sup.size();
     h.o.begin_suppress_tokens = h.bsup.empty() ? nullptr : h.bsup.data();
     h.o.n_begin_suppress = (int)h.bsup.size();
-    m->slot_ref[slot] = wm_model::SlotRef{true, nullptr, 0, B, o->n_prompt + 1 + o->max_loop, h.tt};
+    m->slot_ref[slot] = wm_model::SlotRef{true, nullptr, 0, B, o->n_prompt + 1 + o->max_loop, h.tt, lp};
 }
 // the held submit runs alone, on its own slot's state (no partner came, or the partner did not match)
 static int flush_held(wm_model* m) {
@@ -2088,7 +2129,7 @@ static int flush_held(wm_model* m) {
     if (!h.active) return 0;
     h.active = false;
     wm_model::SlotRef& r = m->slot_ref[h.slot];
-    const int rc = submit_on(m, slot_state(m, h.slot), h.mel, h.on_dev, h.B, &h.o, false, nullptr, 0, h.tt ? &h.cols : nullptr);
+    const int rc = submit_on(m, slot_state(m, h.slot), h.mel, h.on_dev, h.B, &h.o, false, nullptr, 0, h.tt ? &h.cols : nullptr, nullptr, h.lp);
     if (rc) {
         r = wm_model::SlotRef{};
         return rc;
@@ -2141,13 +2182,14 @@ extern "C" int wm_transcribe_tt(wm_model* m, const float* mel, int mel_on_device
 
 // Pipelined form of Whisper.transcribe for back-to-back batches: submit enqueues the encoder and the greedy loop on the slot's
 // stream and returns; wait blocks until that slot's tokens are ready.
-static int submit_impl(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const std::vector<int32_t>* cols) {
+static int submit_impl(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const std::vector<int32_t>* cols,
+                       bool lp = false) {
     wm_model::SlotRef& r = m->slot_ref[slot];
     if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
     const int total = o->n_prompt + 1 + o->max_loop;
     const bool tt = cols != nullptr;
     const bool can_pair = m->cfg.coalesce == 2 && B <= m->cfg.max_batch && (B <= m->enc_chunk || B % m->enc_chunk == 0);
-    if (can_pair && m->held.active && m->held.B == B && m->held.tt == tt && same_opts(m->held, o)) {
+    if (can_pair && m->held.active && m->held.B == B && m->held.tt == tt && m->held.lp == lp && same_opts(m->held, o)) {
         // the partner of the held submit: both batches go out as ONE pass on a 2·B-row state
         wm_state** ps = nullptr;
         for (auto& pr : m->pairs)
@@ -2165,24 +2207,24 @@ static int submit_impl(wm_model* m, int slot, const float* mel, int mel_on_devic
                 pair_cols = h.cols;
                 pair_cols.insert(pair_cols.end(), cols->begin(), cols->end());
             }
-            const int rc = submit_on(m, ps, h.mel, h.on_dev, 2 * B, &h.o, false, mel, mel_on_device, tt ? &pair_cols : nullptr);
+            const int rc = submit_on(m, ps, h.mel, h.on_dev, 2 * B, &h.o, false, mel, mel_on_device, tt ? &pair_cols : nullptr, nullptr, lp);
             if (rc) {
                 r0 = wm_model::SlotRef{};
                 return rc;
             }
             r0.st = *ps;
             r0.row0 = 0;
-            r = wm_model::SlotRef{true, *ps, B, B, total, tt};
+            r = wm_model::SlotRef{true, *ps, B, B, total, tt, lp};
             return 0;
         }
     }
     WMCHK(flush_held(m));
     if (can_pair) {  // wait for a partner (or for this slot's wm_transcribe_wait)
-        hold(m, slot, mel, mel_on_device, B, o, cols);
+        hold(m, slot, mel, mel_on_device, B, o, cols, lp);
         return 0;
     }
-    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, o, false, nullptr, 0, cols));
-    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, total, tt};
+    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, o, false, nullptr, 0, cols, nullptr, lp));
+    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, total, tt, lp};
     return 0;
 }
 extern "C" int wm_transcribe_submit(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o) {
@@ -2253,16 +2295,18 @@ extern "C" int wm_transcribe_submit_rows(wm_model* m, int slot, const float* mel
     r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, o2.n_prompt + 1 + o2.max_loop, false};
     return 0;
 }
-static int wait_impl(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_times) {
+static int wait_impl(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_times, float* token_logprobs = nullptr,
+                     float* avg_logprob = nullptr) {
     wm_model::SlotRef& r = m->slot_ref[slot];
     if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
+    if (token_logprobs && !r.lp) return fail(WM_E_STATE, "this slot's pass was submitted without log-probabilities (wm_transcribe_submit_lp)");
     if (token_times && !r.tt) return fail(WM_E_STATE, "this slot's pass was submitted without token timestamps (wm_transcribe_submit_tt)");
     if (m->held.active && m->held.slot == slot) {  // no partner came: the held batch runs alone now
         const int rc = flush_held(m);
         if (rc) return rc;
     }
     wm_state* s = r.st;
-    const int rc = wait_on(m, s, tokens_out, n_tokens, r.row0, r.rows, nullptr, 0, 0, token_times);
+    const int rc = wait_on(m, s, tokens_out, n_tokens, r.row0, r.rows, nullptr, 0, 0, token_times, token_logprobs, avg_logprob);
     if (!rc) {
         m->last_steps[slot] = s->last_steps;
         m->align_ref[slot] = r.tt ? wm_model::AlignRef{s, r.row0, r.rows, s->al.gen} : wm_model::AlignRef{};
@@ -2277,6 +2321,53 @@ extern "C" int wm_transcribe_wait(wm_model* m, int slot, int32_t* tokens_out, in
 extern "C" int wm_transcribe_wait_tt(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_times) {
     if (!m || !tokens_out || !n_tokens || !token_times || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
     return wait_impl(m, slot, tokens_out, n_tokens, token_times);
+}
+// ---- log-probabilities -----------------------------------------------------------------------------------------------
+// One family for shared (prompts == NULL: opts->prompt) and per-row prompts.  Everything is refused before anything is launched.
+static int lp_check(wm_model* m, const wm_decode_opts* o, int B, const int32_t* prompts, const int32_t* prompt_len, int prompt_stride,
+                    wm_decode_opts& o2, RowPrompts& rows) {
+    if (prompts) {
+        WMCHK(rows_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));
+    } else {
+        if (prompt_len) return fail(WM_E_ARG, "prompt_len without prompts");
+        WMCHK(check_opts(m, o, B));
+        o2 = *o;
+    }
+    if (dec_lanes_for(B) != 1) return fail(WM_E_ARG, "log-probabilities need a single-lane decode state");
+    return 0;
+}
+extern "C" int wm_transcribe_lp(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const int32_t* prompts,
+                                const int32_t* prompt_len, int prompt_stride, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs,
+                                float* avg_logprob) {
+    if (!m || !mel || !tokens_out || !n_tokens || !token_logprobs || !avg_logprob) return fail(WM_E_ARG, "bad argument");
+    wm_decode_opts o2;
+    RowPrompts rows;
+    WMCHK(lp_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));
+    WMCHK(flush_held(m));
+    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, &o2, true, nullptr, 0, nullptr, prompts ? &rows : nullptr, true));
+    WMCHK(wait_on(m, m->cached, tokens_out, n_tokens, 0, -1, nullptr, 0, 0, nullptr, token_logprobs, avg_logprob));
+    m->last_steps[0] = m->cached->last_steps;
+    m->align_ref[0] = wm_model::AlignRef{};
+    return 0;
+}
+extern "C" int wm_transcribe_submit_lp(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o,
+                                       const int32_t* prompts, const int32_t* prompt_len, int prompt_stride) {
+    if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
+    wm_decode_opts o2;
+    RowPrompts rows;
+    WMCHK(lp_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));
+    if (!prompts) return submit_impl(m, slot, mel, mel_on_device, B, &o2, nullptr, true);
+    wm_model::SlotRef& r = m->slot_ref[slot];  // (a per-row pass is never held for a coalesce = 2 partner)
+    if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    WMCHK(flush_held(m));
+    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, &o2, false, nullptr, 0, nullptr, &rows, true));
+    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, o2.n_prompt + 1 + o2.max_loop, false, true};
+    return 0;
+}
+extern "C" int wm_transcribe_wait_lp(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob) {
+    if (!m || !tokens_out || !n_tokens || !token_logprobs || !avg_logprob || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
+    return wait_impl(m, slot, tokens_out, n_tokens, nullptr, token_logprobs, avg_logprob);
 }
 // ---- token-level timestamps ------------------------------------------------------------------------------------
 extern "C" int wm_set_alignment_heads(wm_model* m, const int32_t* layer_head_pairs, int n_pairs) {
@@ -3697,18 +3788,19 @@ extern "C" int wm_op_dec_linear(float* out, const float* x, const float* W, cons
 
 // The decode step's final LayerNorm + tied-embedding logits and its fused argmax, wired as decode_core (want_logits) and
 // argmax_params wire them: launch_dec_logits picks the kernel variant from (dtype, K, B), argmax_step reduces its partials.
-extern "C" int wm_op_logits(float* logits, int32_t* ids, const float* x, const float* ln_g, const float* ln_b, const float* emb,
-                            const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
+// logprob non-null: the LP instantiation of the same kernel variant, and the chosen ids' log-probabilities [B] (wm_op_logits_lp)
+static int op_logits(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                     const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
     if (!logits || !ids || !x || !ln_g || !ln_b || !emb || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
     if (K != 128 && K != 384 && K != 512) return fail(WM_E_ARG, "K must be 128, 384 or 512 (the logits kernels' d_model)");
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
     if (ranges && (timestamp_begin <= 0 || timestamp_begin >= N)) return fail(WM_E_ARG, "ranges need 0 < timestamp_begin < N");
     TmpDev t;
-    t.bufs.reserve(16);
+    t.bufs.reserve(20);
     hipStream_t st = nullptr;
     const int ldo = (N + 3) / 4 * 4, npart = dec_logits_parts(N);  // the kernel stores whole float4 groups below ldo
     DevBuf &dx = t.add(), &g = t.add(), &be = t.add(), &w = t.add(), &mk = t.add(), &o = t.add(), &av = t.add(), &ai = t.add(),
-           &tst = t.add(), &tv = t.add(), &ti = t.add(), &tm = t.add(), &ts = t.add(), &nx = t.add();
+           &tst = t.add(), &tv = t.add(), &ti = t.add(), &tm = t.add(), &ts = t.add(), &nx = t.add(), &ls = t.add(), &ln = t.add();
     WMCHK(upload(dx, x, (size_t)B * K, WM_F32));
     WMCHK(upload(g, ln_g, K, WM_F32));
     WMCHK(upload(be, ln_b, K, WM_F32));
@@ -3718,6 +3810,10 @@ extern "C" int wm_op_logits(float* logits, int32_t* ids, const float* x, const f
     WMCHK(av.alloc((size_t)B * npart * 4, true));
     WMCHK(ai.alloc((size_t)B * npart * 4, true));
     WMCHK(nx.alloc((size_t)B * 4, true));
+    if (logprob) {
+        WMCHK(ls.alloc((size_t)B * npart * 4, true));
+        WMCHK(ln.alloc((size_t)B * 4, true));
+    }
     TsRules rules{};
     if (ranges) {
         std::vector<TsState> h(B);
@@ -3761,10 +3857,15 @@ extern "C" int wm_op_logits(float* logits, int32_t* ids, const float* x, const f
         p.ts_m = tm.as<float>();
         p.ts_s = ts.as<float>();
     }
+    if (logprob) p.lp_s = ls.as<float>();
     int lrc = 0;
     DISPATCH_DT(dtype, TT, lrc = launch_dec_logits<TT>(p, st));
     LCHK(lrc);
     ArgmaxParams a{};
+    if (logprob) {
+        a.lp_s = ls.as<float>();
+        a.lp_next = ln.as<float>();
+    }
     if (ranges) {
         a.ts_state = tst.as<TsState>();
         a.rules = rules;
@@ -3786,7 +3887,17 @@ extern "C" int wm_op_logits(float* logits, int32_t* ids, const float* x, const f
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy2D(logits, (size_t)N * 4, o.p, (size_t)ldo * 4, (size_t)N * 4, B, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(ids, nx.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    if (logprob) HIPCHK(hipMemcpy(logprob, ln.p, (size_t)B * 4, hipMemcpyDeviceToHost));
     return 0;
+}
+extern "C" int wm_op_logits(float* logits, int32_t* ids, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                            const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
+    return op_logits(logits, ids, nullptr, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype);
+}
+extern "C" int wm_op_logits_lp(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                               const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
+    if (!logprob) return fail(WM_E_ARG, "bad argument");
+    return op_logits(logits, ids, logprob, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype);
 }
 
 // The absorbed cross-attention of m->xattn models, wired as launch_cross_attn + cross_attn_merge wire it: absorb, X sweep, merge.

@@ -165,6 +165,10 @@ struct DecLinearParams {
     int* ts_idx;
     float* ts_m;
     float* ts_s;
+    // log-probabilities (null = off, needs amax_val): per part the sum of exp(v - amax_val) over the admissible text candidates —
+    // with amax_val their (max, sum exp) pair, the text side of the softmax normaliser; the timestamp side is (ts_m, ts_s).  Non-null
+    // selects the LP instantiation of the same kernel variant; null launches exactly the kernel, grid and LDS without it.
+    float* lp_s;  // [B][amax_stride]
     long long* ts;  // developer timeline (dec_logits only)
     int ts_id;
     long long* dbg;  // developer build: per-(workgroup, wave) phase stamps of dec_logits (100 MHz clock), null = off
@@ -275,6 +279,13 @@ struct ArgmaxParams {
     const float* ts_m;
     const float* ts_s;
     int ts_part0;  // first part that covers timestamp ids
+    // log-probabilities (lp_s null = off; needs pval): lp = s[id] - logsumexp(s) over the candidates the processors leave — admissible
+    // text ∪ admissible timestamps, the timestamps alone when the rule forces one, everything the mask leaves with the rules off.  A step
+    // whose candidates are all -inf emits id 0 with lp = -inf (never NaN).
+    const float* lp_s;  // [B][npart] stage 1's text-side sums (DecLinearParams.lp_s)
+    float* logprobs;    // [B][out_stride] or null: lp goes where the id goes in out_tokens (same guard: a finished row does not store)
+    float* lp_sum;      // [B], with logprobs: running sum of the row's stored values
+    float* lp_next;     // [B] or null: lp of next[b], stored unconditionally (op-level entry)
 };
 void launch_argmax_step(const ArgmaxParams& p, hipStream_t st);
 struct InitTokensParams {
@@ -289,6 +300,8 @@ struct InitTokensParams {
     int* pos_rows;
     TsState* ts_state;  // non-null: start state of the timestamp rules
     TsRules rules;
+    float* logprobs;  // non-null: zero the utterance's row of the log-prob table [B][out_stride] and its sum lp_sum[b]
+    float* lp_sum;
 };
 void launch_init_tokens(const InitTokensParams& p, hipStream_t st);
 // Per-row prompts: the prompt of row b is table[b * stride .. + len[b]); the rows end together at position Lmax.

@@ -242,8 +242,12 @@ class Whisper:
     def transcribe_batch(self, mel, prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP,
                          ignore_eot: bool = False, suppress_tokens: Sequence[int] = (),
                          begin_suppress_tokens: Sequence[int] = (), timestamps=None, return_token_timestamps: bool = False,
-                         n_frames=None, prompts: Optional[Sequence[Sequence[int]]] = None):
+                         n_frames=None, prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False):
         """Batched Whisper.transcribe: one List[int] per utterance = prompt + generated ids (+ eot when hit).
+        return_logprobs: also return (token_logprobs, avg_logprob) as (ids, (token_logprobs, avg_logprob)): per utterance the
+        log-probability of every id in the layout of its id list (0 at the prompt positions), HF's log_softmax of the processed
+        scores at the chosen id, and avg_logprob [B] = their mean over the generated ids (openai-whisper's avg_logprob, HF's
+        _retrieve_avg_logprobs).  Works with and without prompts=; not with return_token_timestamps.
         prompts: one decoder prompt per utterance, of any lengths (`prompt` is then ignored); every row decodes as if it were
         alone with its own prompt and comes back as its own prompt + generated ids.  Not with return_token_timestamps.
         return_token_timestamps: also return, per utterance, the time in seconds each id was spoken (HF generate's
@@ -254,6 +258,20 @@ class Whisper:
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]
+        if return_logprobs:
+            if return_token_timestamps:
+                raise ValueError("return_logprobs does not combine with return_token_timestamps")
+            tab, lens = self._prompt_rows(prompts, B) if prompts is not None else (None, None)
+            total = (tab.shape[1] if tab is not None else len(p)) + 1 + max_loop
+            toks = np.zeros((B, total), np.int32)
+            n = np.zeros(B, np.int32)
+            lps = np.zeros((B, total), np.float32)
+            avg = np.zeros(B, np.float32)
+            _lib.check(_lib.lib().wm_transcribe_lp(self._h, ptr, on_dev, B, C.byref(opts), _ip(tab) if tab is not None else None,
+                                                   _ip(lens) if tab is not None else None, tab.shape[1] if tab is not None else 0,
+                                                   _ip(toks), _ip(n), _fp(lps), _fp(avg)))
+            self.last_tokens, self.last_counts, self.last_logprobs = toks, n, lps
+            return [toks[b, :n[b]].tolist() for b in range(B)], (self._split_times(lps, n, B), avg)
         if prompts is not None:
             if return_token_timestamps:
                 raise ValueError("per-utterance prompts do not combine with return_token_timestamps")
@@ -354,16 +372,26 @@ class Whisper:
     def transcribe_submit(self, mel, slot: int = 0, prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP,
                           ignore_eot: bool = False, suppress_tokens: Sequence[int] = (), begin_suppress_tokens: Sequence[int] = (),
                           timestamps=None, return_token_timestamps: bool = False, n_frames=None,
-                          prompts: Optional[Sequence[Sequence[int]]] = None):
+                          prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False):
         """Pipelined form (wm_transcribe_submit): enqueue encoder + greedy loop for this batch on pipeline slot 0..7 and
         return at once; `transcribe_wait(slot)` collects the ids.  Submitting batch i+1 before waiting for batch i lets
         its encoder overlap batch i's decode.  return_token_timestamps / n_frames: as transcribe_batch; the matching
-        transcribe_wait then returns (ids, times)."""
+        transcribe_wait then returns (ids, times).  return_logprobs: as transcribe_batch; the matching transcribe_wait returns
+        (ids, (token_logprobs, avg_logprob))."""
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]
+        if return_logprobs:
+            if return_token_timestamps:
+                raise ValueError("return_logprobs does not combine with return_token_timestamps")
+            tab, lens = self._prompt_rows(prompts, B) if prompts is not None else (None, None)
+            _lib.check(_lib.lib().wm_transcribe_submit_lp(self._h, slot, ptr, on_dev, B, C.byref(opts), _ip(tab) if tab is not None else None,
+                                                          _ip(lens) if tab is not None else None, tab.shape[1] if tab is not None else 0))
+            self._pending = getattr(self, "_pending", {})
+            self._pending[slot] = (B, (tab.shape[1] if tab is not None else len(p)) + 1 + max_loop, keep, "lp")
+            return
         if prompts is not None:  # per-utterance prompts, as transcribe_batch
             if return_token_timestamps:
                 raise ValueError("per-utterance prompts do not combine with return_token_timestamps")
@@ -385,6 +413,12 @@ class Whisper:
         B, total, _keep, tt = self._pending.pop(slot)
         toks = np.zeros((B, total), np.int32)
         n = np.zeros(B, np.int32)
+        if tt == "lp":
+            lps = np.zeros((B, total), np.float32)
+            avg = np.zeros(B, np.float32)
+            _lib.check(_lib.lib().wm_transcribe_wait_lp(self._h, slot, _ip(toks), _ip(n), _fp(lps), _fp(avg)))
+            self.last_tokens, self.last_counts, self.last_logprobs = toks, n, lps
+            return [toks[b, :n[b]].tolist() for b in range(B)], (self._split_times(lps, n, B), avg)
         if tt is not None:
             times = np.zeros((B, total), np.float32)
             _lib.check(_lib.lib().wm_transcribe_wait_tt(self._h, slot, _ip(toks), _ip(n), _fp(times)))

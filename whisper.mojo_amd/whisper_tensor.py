@@ -203,10 +203,11 @@ def argmax(t) -> int:
     return int(idx.value)
 
 
-def logits_argmax(x, ln_g, ln_b, emb, dtype=DT_F32, mask=None, ranges=None, timestamp_begin: int = 0):
+def logits_argmax(x, ln_g, ln_b, emb, dtype=DT_F32, mask=None, ranges=None, timestamp_begin: int = 0, return_logprobs: bool = False):
     """whisper.mojo:156-166 + the greedy argmax: (logits [B, N] = layer_norm(x)·embᵀ, ids [B]) on the decode step's logits kernel
     and fused argmax.  mask [N] additive (0 / -inf) on the argmax candidates; ranges [B, 4] = (text_lo, text_hi, ts_lo, ts_hi)
-    with timestamp_begin > 0: the timestamp decision (wm_op_logits)."""
+    with timestamp_begin > 0: the timestamp decision (wm_op_logits).  return_logprobs: (logits, ids, logprob [B]) from the log-prob
+    instantiation of the same kernels (wm_op_logits_lp): logits[id] - logsumexp over the candidates the mask and the ranges leave."""
     f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
     x, emb, mask = f(x), f(emb), f(mask)
     g, b = f(ln_g).ravel(), f(ln_b).ravel()
@@ -224,6 +225,11 @@ def logits_argmax(x, ln_g, ln_b, emb, dtype=DT_F32, mask=None, ranges=None, time
     logits = np.zeros((B, N), np.float32)
     ids = np.zeros(B, np.int32)
     ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    if return_logprobs:
+        lp = np.zeros(B, np.float32)
+        _lib.check(_lib.lib().wm_op_logits_lp(_fp(logits), ip(ids), _fp(lp), _fp(x), _fp(g), _fp(b), _fp(emb),
+                                              _fp(mask.ravel() if mask is not None else None), ip(rg), int(timestamp_begin), B, N, K, dtype))
+        return logits, ids, lp
     _lib.check(_lib.lib().wm_op_logits(_fp(logits), ip(ids), _fp(x), _fp(g), _fp(b), _fp(emb), _fp(mask.ravel() if mask is not None else None),
                                        ip(rg), int(timestamp_begin), B, N, K, dtype))
     return logits, ids
