@@ -84,7 +84,7 @@ const char* wm_last_error(void);
  * built against an older header would hand the library structs whose tail it never wrote.  WM_ABI_VERSION is bumped with every
  * such change; a host binding compares it with wm_abi_version() once after loading the library and refuses a mismatch (the
  * Python and C++ mirrors do). */
-#define WM_ABI_VERSION 4
+#define WM_ABI_VERSION 5
 int wm_abi_version(void);
 
 /* ---- WeightLoader(filename) + Whisper() + Whisper.load(loader)   loader.mojo:10-27, whisper.mojo:175-182 ----
@@ -197,6 +197,26 @@ int wm_transcribe_submit_lp(wm_model* m, int slot, const float* mel, int mel_on_
                             const int32_t* prompts, const int32_t* prompt_len, int prompt_stride);
 int wm_transcribe_wait_lp(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob);
 
+/* ---- no-speech probability ------------------------------------------------------------------------------------
+ * The _lp trio plus openai-whisper's no_speech_prob, HF WhisperNoSpeechDetection: per row the softmax, in fp32 over the whole
+ * vocabulary, of the RAW decoder logits (no suppress mask, no begin-suppress, no timestamp rules) at the position of
+ * <|startoftranscript|> in the row's decoder input, read at no_speech_token (HF: no_timestamps_token_id - 1; here the caller names
+ * it).  That position is prompt_len[b] - n_init (opts->n_prompt - n_init with the shared prompt), n_init the number of initial ids
+ * (<|startoftranscript|> first); previous-text conditioning and prompt_ids come before them.  The prefill keeps the position's last
+ * hidden row, one extra vocabulary sweep (the log-prob logits kernel, unmasked, into buffers of its own) and one small kernel run
+ * between the prefill and the greedy loop; ids, token log-probs and avg_logprob are bit for bit those of the _lp call, and a pass
+ * without _ns launches exactly what it did before.  no_speech_prob: host [B].
+ * WM_E_ARG, nothing launched: what _lp refuses; no_speech_token outside [0, vocab); n_init < 1; n_init larger than a row's prompt.
+ * Under coalesce = 2 such a submit pairs only with another of the same shape, options, token and n_init.  wm_transcribe_wait_lp_ns on
+ * a slot submitted without the probe returns WM_E_STATE; the older waits on a probe slot return what they always return. */
+int wm_transcribe_lp_ns(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* opts, const int32_t* prompts,
+                        const int32_t* prompt_len, int prompt_stride, int no_speech_token, int n_init, int32_t* tokens_out, int32_t* n_tokens,
+                        float* token_logprobs, float* avg_logprob, float* no_speech_prob);
+int wm_transcribe_submit_lp_ns(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* opts,
+                               const int32_t* prompts, const int32_t* prompt_len, int prompt_stride, int no_speech_token, int n_init);
+int wm_transcribe_wait_lp_ns(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob,
+                             float* no_speech_prob);
+
 /* ---- token-level timestamps ---------------------------------------------------------------------------------
  * When each id was spoken, with the semantics of HF generate(..., return_token_timestamps=True)
  * (WhisperGenerationMixin._extract_token_timestamps, time_precision 0.02, median_filter_width 7, num_input_ids = n_prompt): the
@@ -238,7 +258,8 @@ int wm_transcribe_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, i
 
 /* ---- sequential long-form transcription ------------------------------------------------------------------
  * Audio of any length, with the semantics of HF WhisperGenerationMixin.generate on its long-form path (greedy,
- * condition_on_prev_tokens and prompt_ids through the _ex forms below, no temperature fallback / no-speech / log-prob / compression thresholds,
+ * condition_on_prev_tokens, prompt_ids, logprob_threshold and no_speech_threshold through the _ex forms below, no temperature fallback,
+ * no compression_ratio_threshold,
  * return_timestamps=True, return_segments=True): per utterance seek = 0; while seek < n_frames[b] the window
  * mel[:, seek : seek + min(n_frames[b] - seek, 2·n_audio_ctx)] zero-padded to 2·n_audio_ctx is decoded with opts (prompt as the
  * initial ids, timestamp rules from the first generated id), the trailing eot is dropped, the ids are split into segments at
@@ -284,6 +305,19 @@ typedef struct {
     const int32_t* prompt_ids;      /* NULL / 0 = none; as WhisperProcessor.get_prompt_ids returns them */
     int n_prompt_ids;
     int prompt_condition_type;      /* 0 first-segment, 1 all-segments (needs condition_on_prev_tokens) */
+    /* Thresholds (a zero tail keeps everything off).  When either use_* flag is set every pass of the run is a log-prob
+     * pass (wm_transcribe_lp) and, unless no_speech_token is -1, carries the no-speech probe at the first of opts->prompt's
+     * ids.  HF _need_fallback at the single temperature 0: a window is skipped iff avg_logprob < logprob_threshold and
+     * no_speech_prob > no_speech_threshold; it then contributes no segments and no ids, seek advances by the window's own frame
+     * count, and a conditioned prompt is built from the segments without it.  logprob_threshold alone changes no ids and only makes
+     * the quality values available; with it alone no_speech_token may be -1 (no probe: no_speech_prob is reported as NaN).  WM_E_ARG
+     * before anything is launched: use_no_speech_threshold without use_logprob_threshold (HF dereferences it) or without a vocabulary
+     * id; with either flag, a no_speech_token that is neither -1 nor a vocabulary id. */
+    int use_logprob_threshold;
+    float logprob_threshold;
+    int use_no_speech_threshold;
+    float no_speech_threshold;
+    int no_speech_token;
 } wm_long_opts;
 int wm_transcribe_long_ex(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames, const wm_decode_opts* opts,
                           const wm_long_opts* lopts, wm_long_result** out);
@@ -301,6 +335,13 @@ int wm_long_result_get(const wm_long_result* r, int b, int32_t* tokens, wm_segme
 int wm_long_result_stats(const wm_long_result* r, int32_t* windows, int32_t* stalled, int32_t* passes, int32_t* rows);
 /* the longest decoder prompt (ids) any pass of the run carried, and how many of its passes went out as per-row passes */
 int wm_long_result_prompt_stats(const wm_long_result* r, int32_t* longest_prompt, int32_t* row_passes);
+/* Thresholds only (WM_E_STATE for a run without): each segment's window values, openai-whisper's segment fields; [n_segments] */
+int wm_long_result_quality(const wm_long_result* r, int b, float* seg_avg_logprob, float* seg_no_speech_prob);
+/* Thresholds only: utterance b's window log in decode order, skipped windows included.  Call with NULL arrays for the count. */
+int wm_long_result_windows(const wm_long_result* r, int b, int32_t* n_windows, int64_t* seek, float* avg_logprob, float* no_speech_prob,
+                           int32_t* skipped);
+/* windows the skip rule dropped (they are counted in wm_long_result_stats' windows) */
+int wm_long_result_skip_stats(const wm_long_result* r, int32_t* skipped_windows);
 void wm_long_result_free(wm_long_result* r);
 /* Host-only: HF _retrieve_segment on one window's generated ids (eot already dropped).  segs: room for max(1, n) entries;
  * advance: the seek advance in frames exactly as HF computes it (0 in the zero-advance case). */
@@ -372,6 +413,10 @@ int wm_op_logits(float* logits, int32_t* ids, const float* x, const float* ln_g,
  * bit for bit. */
 int wm_op_logits_lp(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                     const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype);
+/* The no-speech probe's launches on the kernel variant wm_op_logits_lp picks for (dtype, K, B): prob[b] = softmax(LN(x[b])·embᵀ)[token]
+ * over all N columns, lse[b] the row's logsumexp.  prob, lse: [B]. */
+int wm_op_no_speech(float* prob, float* lse, const float* x, const float* ln_g, const float* ln_b, const float* emb, int B, int N, int K,
+                    int dtype, int token);
 /* The absorbed cross-attention of bf16-encoder / fp32-K/V models: per row r and head h, with X = x[utt(r)] and
  * utt(r) = r % q_B when q_B > 0 (prefill rows, position-major; rows = P·q_B) else r,
  *   out[r, h] = Σ_j softmax_j(0.125·q_h[r]·(Wk_h X_j)) (Wv_h X_j) + bv_h,

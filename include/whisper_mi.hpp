@@ -184,26 +184,72 @@ public:
         for (int b = 0; b < B; ++b) token_logprobs[b].assign(lp.begin() + (size_t)b * stride, lp.begin() + (size_t)b * stride + n[b]);
         return unpack(toks, n, B, stride);
     }
+    // transcribe_batch_lp plus openai-whisper's no_speech_prob per utterance: the probability of no_speech_token under the
+    // raw logits at each row's <|startoftranscript|> position, prompt length - n_init (n_init <= 0: the shared prompt's length)
+    std::vector<std::vector<int>> transcribe_batch_lp_ns(const float* mels, int B, int32_t no_speech_token, std::vector<std::vector<float>>& token_logprobs,
+                                                         std::vector<float>& avg_logprob, std::vector<float>& no_speech_prob, int max_loop = MAX_LOOP,
+                                                         const std::vector<std::vector<int32_t>>& prompts = {}, int n_init = 0) const {
+        need_model();
+        wm_decode_opts o = opts(max_loop, false);
+        int lmax = 0;
+        for (const auto& r : prompts) lmax = std::max(lmax, (int)r.size());
+        std::vector<int32_t> tab((size_t)B * std::max(lmax, 1)), len(B);
+        for (size_t b = 0; b < prompts.size() && b < (size_t)B; ++b) {
+            len[b] = (int32_t)prompts[b].size();
+            std::copy(prompts[b].begin(), prompts[b].end(), tab.begin() + b * lmax);
+        }
+        const bool rows = !prompts.empty();
+        const int stride = (rows ? lmax : o.n_prompt) + 1 + max_loop;
+        std::vector<int32_t> toks((size_t)B * stride), n(B);
+        std::vector<float> lp((size_t)B * stride);
+        avg_logprob.assign(B, 0.f);
+        no_speech_prob.assign(B, 0.f);
+        check(wm_transcribe_lp_ns(model_, mels, 0, B, &o, rows ? tab.data() : nullptr, rows ? len.data() : nullptr, lmax, no_speech_token,
+                                  n_init > 0 ? n_init : o.n_prompt, toks.data(), n.data(), lp.data(), avg_logprob.data(), no_speech_prob.data()));
+        token_logprobs.assign(B, {});
+        for (int b = 0; b < B; ++b) token_logprobs[b].assign(lp.begin() + (size_t)b * stride, lp.begin() + (size_t)b * stride + n[b]);
+        return unpack(toks, n, B, stride);
+    }
     // sequential long-form transcription (HF generate's long-form path; needs set_timestamps): host mels
     // [B][n_mels][T], n_frames per utterance (empty = T) -> per utterance the sequence and its segments
     struct LongSegment {
         double start, end;
         std::vector<int> tokens;
+        float avg_logprob = 0.f, no_speech_prob = 0.f;  // the segment's window values; filled with LongThresholds only
+    };
+    struct LongWindow {  // one decoded window of an utterance, skipped ones included (LongThresholds only)
+        int64_t seek;
+        float avg_logprob, no_speech_prob;
+        bool skipped;
     };
     struct LongResult {
         std::vector<int> sequence;
         std::vector<LongSegment> segments;
+        std::vector<LongWindow> windows;
+    };
+    // HF generate's logprob_threshold / no_speech_threshold at temperature 0: a window with avg_logprob < logprob_threshold
+    // and no_speech_prob > no_speech_threshold is skipped.  no_speech_threshold needs logprob_threshold and the <|nospeech|> id.
+    struct LongThresholds {
+        bool use_logprob_threshold = false;
+        float logprob_threshold = 0.f;
+        bool use_no_speech_threshold = false;
+        float no_speech_threshold = 0.f;
+        int32_t no_speech_token = -1;
     };
     // condition_on_prev_tokens / prompt_ids (as WhisperProcessor.get_prompt_ids returns them) / all_segments: HF generate's options of
     // the same names; the defaults are wm_transcribe_long
     std::vector<LongResult> transcribe_long(const float* mels, int B, int T, const std::vector<int32_t>& n_frames = {}, int max_loop = MAX_LOOP,
                                             bool condition_on_prev_tokens = false, const std::vector<int32_t>& prompt_ids = {},
-                                            bool all_segments = false, int32_t prev_sot_token = 50361) const {
+                                            bool all_segments = false, int32_t prev_sot_token = 50361, const LongThresholds* thresholds = nullptr) const {
         need_model();
         wm_decode_opts o = opts(max_loop, false);
         wm_long_result* r = nullptr;
+        LongThresholds th;
+        if (thresholds) th = *thresholds;
         const wm_long_opts lo{condition_on_prev_tokens ? 1 : 0, prev_sot_token, prompt_ids.empty() ? nullptr : prompt_ids.data(),
-                              (int)prompt_ids.size(), all_segments ? 1 : 0};
+                              (int)prompt_ids.size(), all_segments ? 1 : 0, th.use_logprob_threshold ? 1 : 0, th.logprob_threshold,
+                              th.use_no_speech_threshold ? 1 : 0, th.no_speech_threshold, th.no_speech_token};
+        const bool quality = th.use_logprob_threshold || th.use_no_speech_threshold;
         check(wm_transcribe_long_ex(model_, mels, 0, B, T, n_frames.empty() ? nullptr : n_frames.data(), &o, &lo, &r));
         std::vector<LongResult> out(B);
         int rc = 0;
@@ -216,6 +262,21 @@ public:
             out[b].sequence.assign(ids.begin(), ids.end());
             for (const wm_segment& sg : segs)
                 out[b].segments.push_back({sg.start, sg.end, std::vector<int>(ids.begin() + sg.first, ids.begin() + sg.first + sg.count)});
+            if (quality && !rc) {
+                std::vector<float> qa(ns), qn(ns);
+                rc = wm_long_result_quality(r, b, qa.data(), qn.data());
+                for (int i = 0; i < ns && !rc; ++i) {
+                    out[b].segments[i].avg_logprob = qa[i];
+                    out[b].segments[i].no_speech_prob = qn[i];
+                }
+                int32_t nw = 0;
+                if (!rc) rc = wm_long_result_windows(r, b, &nw, nullptr, nullptr, nullptr, nullptr);
+                std::vector<int64_t> ws(nw);
+                std::vector<float> wa(nw), wn(nw);
+                std::vector<int32_t> wk(nw);
+                if (!rc) rc = wm_long_result_windows(r, b, &nw, ws.data(), wa.data(), wn.data(), wk.data());
+                for (int i = 0; i < nw && !rc; ++i) out[b].windows.push_back({ws[i], wa[i], wn[i], wk[i] != 0});
+            }
         }
         wm_long_result_free(r);
         check(rc);

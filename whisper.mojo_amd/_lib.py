@@ -26,9 +26,11 @@ SYMBOLS = [
     "wm_transcribe_rows", "wm_transcribe_submit_rows", "wm_transcribe_long_ex", "wm_transcribe_long_pcm_ex", "wm_op_long_prompt",
     "wm_op_attention_cached_lo", "wm_long_result_prompt_stats",
     "wm_transcribe_lp", "wm_transcribe_submit_lp", "wm_transcribe_wait_lp", "wm_op_logits_lp",
+    "wm_transcribe_lp_ns", "wm_transcribe_submit_lp_ns", "wm_transcribe_wait_lp_ns", "wm_op_no_speech",
+    "wm_long_result_quality", "wm_long_result_windows", "wm_long_result_skip_stats",
 ]
 
-ABI_VERSION = 4  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
+ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
 KERNEL_CROSS_ATTN, KERNEL_DECODE_STEP, KERNEL_ENCODER, KERNEL_DECODE_STEP_SHARED = 0, 1, 2, 3
 
 
@@ -51,21 +53,53 @@ class WmSegment(C.Structure):
 
 class WmLongOpts(C.Structure):
     _fields_ = [("condition_on_prev_tokens", C.c_int), ("prev_sot_token", C.c_int), ("prompt_ids", C.POINTER(C.c_int32)),
-                ("n_prompt_ids", C.c_int), ("prompt_condition_type", C.c_int)]
+                ("n_prompt_ids", C.c_int), ("prompt_condition_type", C.c_int),
+                ("use_logprob_threshold", C.c_int), ("logprob_threshold", C.c_float),
+                ("use_no_speech_threshold", C.c_int), ("no_speech_threshold", C.c_float), ("no_speech_token", C.c_int)]
 
 
 PROMPT_CONDITION_TYPES = {"first-segment": 0, "all-segments": 1}
 
 
-def long_opts(prompt_ids=None, condition_on_prev_tokens=False, prompt_condition_type="first-segment", prev_sot_token=50361):
-    """-> (WmLongOpts, keep-alive array).  prompt_condition_type: a name of PROMPT_CONDITION_TYPES."""
+def long_opts(prompt_ids=None, condition_on_prev_tokens=False, prompt_condition_type="first-segment", prev_sot_token=50361,
+              logprob_threshold=None, no_speech_threshold=None, no_speech_token=None):
+    """-> (WmLongOpts, keep-alive array).  prompt_condition_type: a name of PROMPT_CONDITION_TYPES.
+    logprob_threshold / no_speech_threshold / no_speech_token: HF generate's thresholds; ValueError for a
+    no_speech_threshold without logprob_threshold (HF dereferences it) or without the <|nospeech|> id."""
     import numpy as np
+    if no_speech_threshold is not None:
+        if logprob_threshold is None:
+            raise ValueError("no_speech_threshold needs logprob_threshold")
+        if no_speech_token is None:
+            raise ValueError("no_speech_threshold needs no_speech_token (the <|nospeech|> id, HF: no_timestamps_token_id - 1)")
+    if no_speech_token is not None and int(no_speech_token) < 0:
+        raise ValueError("no_speech_token must be a vocabulary id")
     if (prompt_condition_type or "first-segment") not in PROMPT_CONDITION_TYPES:
         raise ValueError(f"prompt_condition_type must be one of {sorted(PROMPT_CONDITION_TYPES)}")
     p = np.ascontiguousarray(np.asarray([] if prompt_ids is None else prompt_ids, np.int32).reshape(-1))
     o = WmLongOpts(int(bool(condition_on_prev_tokens)), int(prev_sot_token), p.ctypes.data_as(C.POINTER(C.c_int32)) if p.size else None,
-                   int(p.size), PROMPT_CONDITION_TYPES[prompt_condition_type or "first-segment"])
+                   int(p.size), PROMPT_CONDITION_TYPES[prompt_condition_type or "first-segment"],
+                   int(logprob_threshold is not None), float(logprob_threshold or 0.0),
+                   int(no_speech_threshold is not None), float(no_speech_threshold or 0.0),
+                   -1 if no_speech_token is None else int(no_speech_token))
     return o, p
+
+
+def no_speech_args(no_speech_token, n_init, prompt_lens, vocab):
+    """Checks the no-speech probe's arguments on the host (the library refuses the same with WM_E_ARG) -> (token, n_init).
+    n_init None: the shared prompt's length (prompt_lens one number); required with per-row prompts (a list of lengths)."""
+    shared = isinstance(prompt_lens, int)
+    if n_init is None:
+        if not shared:
+            raise ValueError("n_init is required with per-row prompts (the number of initial ids, <|startoftranscript|> first)")
+        n_init = prompt_lens
+    token, n_init = int(no_speech_token), int(n_init)
+    if token < 0 or token >= vocab:
+        raise ValueError(f"no_speech_token {token} is not a vocabulary id")
+    shortest = prompt_lens if shared else min(int(v) for v in prompt_lens)
+    if n_init < 1 or n_init > shortest:
+        raise ValueError(f"n_init {n_init} outside [1, shortest prompt = {shortest}]")
+    return token, n_init
 
 
 class WhisperMiError(RuntimeError):
@@ -151,6 +185,13 @@ def lib():
     L.wm_transcribe_lp.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip, C.c_int, ip, ip, fp, fp]
     L.wm_transcribe_submit_lp.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip, C.c_int]
     L.wm_transcribe_wait_lp.argtypes = [vp, C.c_int, ip, ip, fp, fp]
+    L.wm_transcribe_lp_ns.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip, C.c_int, C.c_int, C.c_int, ip, ip, fp, fp, fp]
+    L.wm_transcribe_submit_lp_ns.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip, C.c_int, C.c_int, C.c_int]
+    L.wm_transcribe_wait_lp_ns.argtypes = [vp, C.c_int, ip, ip, fp, fp, fp]
+    L.wm_op_no_speech.argtypes = [fp] * 6 + [C.c_int] * 5
+    L.wm_long_result_quality.argtypes = [vp, C.c_int, fp, fp]
+    L.wm_long_result_windows.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_int64), fp, fp, ip]
+    L.wm_long_result_skip_stats.argtypes = [vp, ip]
     L.wm_op_xattn.argtypes = [fp] * 6 + [C.c_int] * 7
     L.wm_bench_kernel.argtypes = [vp, vp, C.c_int, C.c_int, fp]
     L.wm_bench_bytes.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double)]
@@ -162,11 +203,14 @@ def lib():
     return L
 
 
-def long_result(h, B: int):
+def long_result(h, B: int, quality: bool = False):
     """Reads and frees a wm_long_result handle of B utterances -> (per utterance {"sequence": [...], "segments": [{"start",
     "end", "tokens"}]}, {"windows", "stalled", "passes", "rows"}: windows decoded, windows that did not advance seek, passes
     run and rows those passes decoded; "longest_prompt", "row_passes": the longest decoder prompt a pass carried and how many
-    passes went out as per-row passes)."""
+    passes went out as per-row passes).
+    quality (a run with thresholds): every segment also carries its window's "avg_logprob" / "no_speech_prob", every
+    utterance its window log "windows": [{"seek", "avg_logprob", "no_speech_prob", "skipped"}] in decode order, and the stats
+    "skipped_windows"."""
     L = lib()
     try:
         out = []
@@ -179,12 +223,28 @@ def long_result(h, B: int):
             seq = list(toks[:n_tok.value])
             out.append({"sequence": seq, "segments": [{"start": s.start, "end": s.end, "tokens": seq[s.first:s.first + s.count]}
                                                       for s in segs[:n_seg.value]]})
+            if quality:
+                qa, qn = (C.c_float * max(1, n_seg.value))(), (C.c_float * max(1, n_seg.value))()
+                check(L.wm_long_result_quality(h, b, qa, qn))
+                for i, sg in enumerate(out[-1]["segments"]):
+                    sg["avg_logprob"], sg["no_speech_prob"] = float(qa[i]), float(qn[i])
+                nw = C.c_int32()
+                check(L.wm_long_result_windows(h, b, C.byref(nw), None, None, None, None))
+                k = max(1, nw.value)
+                ws, wa, wn, wk = (C.c_int64 * k)(), (C.c_float * k)(), (C.c_float * k)(), (C.c_int32 * k)()
+                check(L.wm_long_result_windows(h, b, C.byref(nw), ws, wa, wn, wk))
+                out[-1]["windows"] = [{"seek": int(ws[i]), "avg_logprob": float(wa[i]), "no_speech_prob": float(wn[i]),
+                                       "skipped": bool(wk[i])} for i in range(nw.value)]
         st = [C.c_int32() for _ in range(4)]
         check(L.wm_long_result_stats(h, *[C.byref(v) for v in st]))
         stats = dict(zip(("windows", "stalled", "passes", "rows"), (v.value for v in st)))
         lp, rp = C.c_int32(), C.c_int32()
         check(L.wm_long_result_prompt_stats(h, C.byref(lp), C.byref(rp)))
         stats.update(longest_prompt=lp.value, row_passes=rp.value)
+        if quality:
+            sk = C.c_int32()
+            check(L.wm_long_result_skip_stats(h, C.byref(sk)))
+            stats["skipped_windows"] = sk.value
         return out, stats
     finally:
         L.wm_long_result_free(h)

@@ -2168,6 +2168,89 @@ void launch_set_step(StepCtl* ctl, int len, int set_len, int* pos, int pos_value
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// No-speech probe: HF WhisperNoSpeechDetection — softmax over the RAW logits at the <|startoftranscript|> position,
+// read at no_speech_token.  The prefill keeps each row's last-layer residual row of that position (capture); after the prefill the
+// LP instantiation of the logits kernel sweeps the vocabulary once over those rows with no mask and no ranges, into the probe's own
+// partials: per part (max, Σ exp(v − max)); the finish kernel merges them and reads the token's probability.
+__global__ void no_speech_capture_kernel(const float* __restrict__ rows, float* __restrict__ out, int n4) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n4) reinterpret_cast<f32x4*>(out)[i] = reinterpret_cast<const f32x4*>(rows)[i];
+}
+void launch_no_speech_capture(const float* rows, float* out, int B, int d, hipStream_t st) {
+    const int n4 = B * d / 4;  // d is a multiple of 128
+    hipLaunchKernelGGL(no_speech_capture_kernel, dim3((n4 + 255) / 256), dim3(256), 0, st, rows, out, n4);
+}
+// One workgroup per row.  M = the parts' largest maximum (exact in any order); thread k forms psum[k]·exp(pmax[k] − M), thread 0 adds
+// the terms in ascending part order (a fixed order: a row's value does not depend on the batch it rides in).  Wave 0 recomputes the
+// token's logit as the logits kernel forms it: fp32 LayerNorm of the row (one-pass statistics, eps 1e-5), rounded to the operand
+// dtype TW, times the token's embedding row, summed in fp32.  log p = (logit − M) − log S: the maxima are subtracted first, so every
+// exponent is <= 0 and an offset of the whole row costs nothing.
+template <typename TW>
+__global__ __launch_bounds__(256) void no_speech_finish_kernel(NoSpeechParams p) {
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    __shared__ float s_red[4];
+    __shared__ float s_term[256];
+    __shared__ float s_logit;
+    const float* pm = p.pmax + (size_t)b * p.stride;
+    const float* ps = p.psum + (size_t)b * p.stride;
+    float mx = -INFINITY;
+    for (int k = tid; k < p.npart; k += 256) mx = fmaxf(mx, pm[k]);
+    mx = wave_max(mx);
+    if (lane == 0) s_red[w] = mx;
+    if (w == 0) {
+        const float* xr = p.x + (size_t)b * p.ldx;
+        float sm = 0.f, sq = 0.f;
+        for (int k = lane; k < p.K; k += 64) {
+            const float v = xr[k];
+            sm += v;
+            sq += v * v;
+        }
+        sm = wave_sum(sm);
+        sq = wave_sum(sq);
+        const float mean = sm / (float)p.K;
+        const float var = (sq / (float)p.K) - (mean * mean);
+        const float rstd = 1.0f / sqrtf(var + 1e-5f);
+        const TW* er = (const TW*)p.emb + (size_t)p.token * p.K;
+        float acc = 0.f;
+        for (int k = lane; k < p.K; k += 64) {
+            const TW a = from_f32<TW>((xr[k] - mean) * rstd * p.ln_g[k] + p.ln_b[k]);
+            acc += (float)a * (float)er[k];
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) s_logit = acc;
+    }
+    __syncthreads();
+    const float M = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+    float S = 0.f;
+    for (int k0 = 0; k0 < p.npart; k0 += 256) {
+        const int k = k0 + tid;
+        float t = 0.f;
+        if (k < p.npart) {
+            const float s2 = ps[k];
+            if (s2 > 0.f) t = s2 * expf(pm[k] - M);
+        }
+        s_term[tid] = t;
+        __syncthreads();
+        if (tid == 0) {
+            const int n = min(256, p.npart - k0);
+            for (int j = 0; j < n; ++j) S += s_term[j];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float ls = logf(S);  // S >= 1: the part that holds M contributes a term exp(0)
+        p.lse[b] = M + ls;
+        p.prob[b] = expf(fminf((s_logit - M) - ls, 0.f));
+    }
+}
+template <typename TW> void launch_no_speech_finish(const NoSpeechParams& p, hipStream_t st) {
+    hipLaunchKernelGGL(no_speech_finish_kernel<TW>, dim3(p.B), dim3(256), 0, st, p);
+}
+template void launch_no_speech_finish<float>(const NoSpeechParams&, hipStream_t);
+template void launch_no_speech_finish<bf16>(const NoSpeechParams&, hipStream_t);
+template void launch_no_speech_finish<f16>(const NoSpeechParams&, hipStream_t);
+
+// ------------------------------------------------------------------------------------------------------------
 // op-level helpers (known-answer tests of the C-ABI)
 __global__ void gelu_kernel(float* t, size_t n, int mode) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

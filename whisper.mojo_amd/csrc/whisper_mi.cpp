@@ -233,6 +233,7 @@ struct wm_model {
         bool tt = false;                          // token timestamps asked for; cols = columns kept per row
         std::vector<int32_t> cols;
         bool lp = false;                          // log-probabilities asked for: pairs only with another such submit
+        int ns_token = -1, ns_init = 0;           // no-speech probe (ns_token >= 0): pairs only with the same token and n_init
     } held;
     struct SlotRef {  // where a submitted slot's rows live
         bool pending = false;
@@ -240,6 +241,7 @@ struct wm_model {
         int row0 = 0, rows = 0, total = 0;
         bool tt = false;
         bool lp = false;  // the pass computes log-probabilities (wm_transcribe_wait_lp may collect them)
+        bool ns = false;  // the pass carries the no-speech probe (wm_transcribe_wait_lp_ns may collect it)
     } slot_ref[8];
     wm_state* pairs[4] = {};  // 2·B-row states of coalesced pairs
     int last_steps[8] = {-1, -1, -1, -1, -1, -1, -1, -1};  // loop iterations enqueued for each slot's last collected pass
@@ -363,6 +365,14 @@ struct wm_state {
         std::vector<int32_t> n_prompt;  // [B] prompt length of each row of the pending pass
     } lp;
     bool graph_lp = false;  // the captured step graph computes log-probabilities
+    // no-speech probe of the pending pass (on = wm_transcribe_lp_ns and its kin, always with lp.on): the residual rows
+    // of the <|startoftranscript|> position [B][d], the probe's OWN sweep partials [B][npart] (the step's amax / lp_s partials and
+    // the control block are not touched) and the results [B].  Part of the arena; runs outside the captured step graph.
+    struct Ns {
+        bool on = false;
+        int token = -1, n_init = 0;
+        DevBuf x, pmax, pidx, psum, prob, lse;
+    } ns;
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -843,7 +853,8 @@ extern "C" void wm_state_free(wm_state* s) {
                     &s->cross_kv, &s->enc_x, &s->xq, &s->part_y, &s->self_kv, &s->dx, &s->dq, &s->dattn, &s->dhid, &s->part_o, &s->part_ml, &s->logits, &s->amax_val, &s->amax_idx, &s->ts_state, &s->ts_val, &s->ts_idx, &s->ts_m, &s->ts_s, &s->mask_steady, &s->mask_begin,
                     &s->tok, &s->pos, &s->tok_rows, &s->pos_rows, &s->ctl, &s->out_tokens, &s->n_tokens, &s->finished,
                     &s->al.cap, &s->al.kh, &s->al.probs, &s->al.mean, &s->al.stdv, &s->al.M, &s->al.trace, &s->al.times, &s->al.ncols,
-                    &s->rw.table, &s->rw.len, &s->rw.key_lo, &s->lp.part_s, &s->lp.table, &s->lp.sum};
+                    &s->rw.table, &s->rw.len, &s->rw.key_lo, &s->lp.part_s, &s->lp.table, &s->lp.sum,
+                    &s->ns.x, &s->ns.pmax, &s->ns.pidx, &s->ns.psum, &s->ns.prob, &s->ns.lse};
     for (DevBuf* b : bs) b->release();
     delete s;
 }
@@ -957,6 +968,12 @@ static int state_new(wm_model* m, int B, wm_state** out, bool pair) {
     A(s->lp.part_s, (size_t)B * s->npart * 4, true);
     A(s->lp.table, (size_t)B * s->out_stride * 4, true);
     A(s->lp.sum, (size_t)B * 4, true);
+    A(s->ns.x, (size_t)B * d * 4, true);
+    A(s->ns.pmax, (size_t)B * s->npart * 4, true);
+    A(s->ns.pidx, (size_t)B * s->npart * 4, true);
+    A(s->ns.psum, (size_t)B * s->npart * 4, true);
+    A(s->ns.prob, (size_t)B * 4, true);
+    A(s->ns.lse, (size_t)B * 4, true);
     if (rc) {
         std::string keep = g_err;
         wm_state_free(s);
@@ -1734,6 +1751,61 @@ static void pump_main(wm_model* m) {
     }
 }
 
+// No-speech probe.  capture: after the prefill pass that holds the <|startoftranscript|> position, keep that position's
+// residual rows (row_off: its first row in the pass's position-major activations).  probe: after the prefill, one vocabulary sweep
+// over the kept rows — the log-prob instantiation of the logits kernel a decode step of this state picks, no mask, no ranges, its
+// partials in the probe's own buffers — and the finish kernel.  Both go on the lane's stream, outside the captured step graph.
+static void ns_capture(wm_model* m, wm_state* s, const DecView& v, size_t row_off) {
+    const size_t d = m->cfg.dims.d_model;
+    launch_no_speech_capture(s->dx.as<float>() + ((size_t)v.b0 + row_off) * d, s->ns.x.as<float>() + (size_t)v.b0 * d, v.nb, (int)d, v.st);
+}
+static int ns_sweep(int T, const float* x, const float* ln_g, const float* ln_b, const void* emb, int N, int K, int B, int npart, float* pmax,
+                    int* pidx, float* psum, int token, float* prob, float* lse, hipStream_t st) {
+    DecLinearParams p{};
+    p.x = x;
+    p.ldx = K;
+    p.ln_g = ln_g;
+    p.ln_b = ln_b;
+    p.W = emb;
+    p.N = N;
+    p.K = K;
+    p.B = B;
+    p.ldo = (N + 3) / 4 * 4;
+    p.amax_val = pmax;
+    p.amax_idx = pidx;
+    p.amax_stride = npart;
+    p.lp_s = psum;
+    int lrc = 0;
+    DISPATCH_DT(T, TT, lrc = launch_dec_logits<TT>(p, st));
+    LCHK(lrc);
+    NoSpeechParams q{};
+    q.x = x;
+    q.ldx = K;
+    q.ln_g = ln_g;
+    q.ln_b = ln_b;
+    q.emb = emb;
+    q.K = K;
+    q.token = token;
+    q.B = B;
+    q.pmax = pmax;
+    q.psum = psum;
+    q.npart = npart;
+    q.stride = npart;
+    q.prob = prob;
+    q.lse = lse;
+    DISPATCH_DT(T, TT, launch_no_speech_finish<TT>(q, st));
+    return 0;
+}
+static int ns_probe(wm_model* m, wm_state* s, const DecView& v) {
+    const wm_dims& c = m->cfg.dims;
+    const int T = dec_dtype(m->cfg);
+    const size_t np = (size_t)v.b0 * s->npart;
+    return ns_sweep(T, s->ns.x.as<float>() + (size_t)v.b0 * c.d_model, m->dec_ln_g.as<float>(), m->dec_ln_b.as<float>(),
+                    T == WM_F32 ? m->tok_emb_f.p : m->tok_emb_t.p, c.vocab, c.d_model, v.nb, s->npart, s->ns.pmax.as<float>() + np,
+                    s->ns.pidx.as<int>() + np, s->ns.psum.as<float>() + np, s->ns.token, s->ns.prob.as<float>() + v.b0,
+                    s->ns.lse.as<float>() + v.b0, v.st);
+}
+
 // Per-row prompts, the start of a pass on a single-lane state: prompt table and lengths to the device, tokens /
 // key windows / prefill rows from them, the prefill in chunks of PREFILL_MAX positions through the position-major pass (the rows
 // end together at position Lmax; logits for the last chunk only: every row's last position is real), the first id, and the per-row
@@ -1750,6 +1822,9 @@ static int prefill_rows(wm_model* m, wm_state* s, const DecView& v, InitTokensPa
         const int P = std::min<int>(wm_state::PREFILL_MAX, Lmax - t0);
         if (t0) launch_set_step(v.ctl, t0, 1, nullptr, 0, nullptr, 0, v.nb, v.st);
         WMCHK(decode_core(m, s, v, t0 + P == Lmax, false, s->mask_begin.as<float>(), P, true, rp, false, t0));
+        // the rows end together, so every row's <|startoftranscript|> sits in cache slot Lmax - n_init, whatever its own length
+        const int t_sot = Lmax - s->ns.n_init;
+        if (s->ns.on && t_sot >= t0 && t_sot < t0 + P) ns_capture(m, s, v, (size_t)(t_sot - t0) * v.nb);
     }
     launch_argmax_step(argmax_params(m, s, v, true, o->eot, o->ignore_eot, false, false, rp), v.st);
     trace_mark(v.st, "state %p lane %d prefill end", (void*)s, v.b0);
@@ -1829,10 +1904,12 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
             static const bool seq_prefill = wm_env("WM_SEQ_PREFILL") != nullptr;  // A/B: one pass per prompt position
             if (!seq_prefill && s->lanes.size() == 1 && o->n_prompt > 1 && o->n_prompt <= wm_state::PREFILL_MAX) {
                 WMCHK(decode_core(m, s, v, true, false, s->mask_begin.as<float>(), o->n_prompt, true, rp));  // init_tokens filled tok_rows / pos_rows
+                if (s->ns.on) ns_capture(m, s, v, (size_t)(o->n_prompt - s->ns.n_init) * v.nb);
             } else {
                 for (int i = 0; i < o->n_prompt; ++i) {
                     launch_set_step(v.ctl, i, 1, s->pos.as<int>() + v.b0, i, s->tok.as<int>() + v.b0, o->prompt[i], v.nb, v.st);
                     WMCHK(decode_core(m, s, v, i == o->n_prompt - 1, false, s->mask_begin.as<float>(), 1, true, rp));
+                    if (s->ns.on && i == o->n_prompt - s->ns.n_init) ns_capture(m, s, v, 0);
                 }
             }
             launch_argmax_step(argmax_params(m, s, v, true, o->eot, o->ignore_eot, false, false, rp), v.st);  // :198-203
@@ -1843,6 +1920,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
         // input row of the first loop step; every later step's row is written by the preceding step's argmax launch
         launch_dec_embed(m->tok_emb_f.as<float>(), m->dec_pos.as<float>(), s->tok.as<int>() + v.b0, s->pos.as<int>() + v.b0,
                          s->dx.as<float>() + (size_t)v.b0 * m->cfg.dims.d_model, v.nb, m->cfg.dims.d_model, v.st);
+        if (s->ns.on) WMCHK(ns_probe(m, s, v));  // between prefill and loop, outside the captured step
         // steady state: one captured graph per lane = [37 decode-step launches + argmax/bookkeeping]; every per-step
         // quantity (token, position, cache length) lives in HBM, so the same graph is replayed for every token
         if (!no_graph && (recapture || !ln.graph[0])) {
@@ -1938,6 +2016,9 @@ static int check_opts(wm_model* m, const wm_decode_opts* o, int B) {
 static int align_setup(wm_model* m, wm_state* s, const wm_decode_opts* o, const std::vector<int32_t>* cols);
 // cols != null: token timestamps for this pass, cols[b] = columns kept for row b (n_frames[b] // 2, or n_audio_ctx)
 // rows != null: per-row prompts (o->n_prompt = rows->Lmax, o->prompt unused)
+struct NsAsk {  // the no-speech probe a pass carries; token < 0: none
+    int token = -1, n_init = 0;
+};
 struct RowPrompts {
     const int32_t* ids;  // host [B][stride]
     const int32_t* len;  // host [B]
@@ -1966,8 +2047,10 @@ static int rows_setup(wm_model* m, wm_state* s, const RowPrompts* rows) {
 }
 static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, bool allow_poll,
                      const float* mel2 = nullptr, int mel2_on_device = 0, const std::vector<int32_t>* cols = nullptr,
-                     const RowPrompts* rows = nullptr, bool lp = false) {
+                     const RowPrompts* rows = nullptr, bool lp = false, NsAsk ns = NsAsk()) {
     const wm_dims& c = m->cfg.dims;
+    if (ns.token >= 0 && (!lp || ns.token >= c.vocab || ns.n_init < 1 || ns.n_init > o->n_prompt))  // (refused by the entry points first)
+        return fail(WM_E_ARG, "the no-speech probe needs a log-prob pass, a vocabulary id and 1 <= n_init <= prompt length");
     if (lp && (cols || dec_lanes_for(B) != 1))  // (the entry points refuse both before anything is touched; kept for internal callers)
         return fail(WM_E_ARG, "log-probabilities need a single-lane decode state and a pass without token timestamps");
     HIPCHK(hipSetDevice(m->device));
@@ -1982,6 +2065,9 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
     }
     wm_state* s = *slot;
     WMCHK(rows_setup(m, s, rows));
+    s->ns.on = ns.token >= 0;
+    s->ns.token = ns.token;
+    s->ns.n_init = ns.n_init;
     s->lp.on = lp;
     if (lp) {
         if (rows)
@@ -2042,7 +2128,8 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
 // Blocks until the state's pending pass is complete, then copies `rows` utterances starting at row0 out.  The pass stays pending
 // until every slot that shares the state (one, or the two of a coalesced pair) has collected its rows.
 static int wait_on(wm_model* m, wm_state* s, int32_t* tokens_out, int32_t* n_tokens, int row0 = 0, int rows = -1, int32_t* dev_packed = nullptr,
-                   int rows_cap = 0, int pack_stride = 0, float* token_times = nullptr, float* token_logprobs = nullptr, float* avg_logprob = nullptr) {
+                   int rows_cap = 0, int pack_stride = 0, float* token_times = nullptr, float* token_logprobs = nullptr, float* avg_logprob = nullptr,
+                   float* no_speech_prob = nullptr) {
     if (!s || !s->pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
     HIPCHK(hipSetDevice(m->device));
     if (rows < 0) rows = s->B;
@@ -2081,6 +2168,7 @@ static int wait_on(wm_model* m, wm_state* s, int32_t* tokens_out, int32_t* n_tok
                 avg_logprob[b] = gen > 0 ? avg_logprob[b] / (float)gen : 0.f;
             }
         }
+        if (no_speech_prob) HIPCHK(hipMemcpy(no_speech_prob, s->ns.prob.as<float>() + row0, (size_t)rows * 4, hipMemcpyDeviceToHost));
     }
     if (--s->halves_left <= 0) {
         s->pending = false;
@@ -2102,9 +2190,12 @@ static bool same_opts(const wm_model::Held& h, const wm_decode_opts* o) {
     return std::equal(h.prompt.begin(), h.prompt.end(), o->prompt) && std::equal(h.sup.begin(), h.sup.end(), o->suppress_tokens) &&
            std::equal(h.bsup.begin(), h.bsup.end(), o->begin_suppress_tokens);
 }
-static void hold(wm_model* m, int slot, const float* mel, int on_dev, int B, const wm_decode_opts* o, const std::vector<int32_t>* cols, bool lp) {
+static void hold(wm_model* m, int slot, const float* mel, int on_dev, int B, const wm_decode_opts* o, const std::vector<int32_t>* cols, bool lp,
+                 NsAsk ns) {
     wm_model::Held& h = m->held;
     h.lp = lp;
+    h.ns_token = ns.token;
+    h.ns_init = ns.n_init;
     h.tt = cols != nullptr;
     h.cols = cols ? *cols : std::vector<int32_t>();
     h.active = true;
@@ -2121,7 +2212,7 @@ static void hold(wm_model* m, int slot, const float* mel, int on_dev, int B, con
     h.o.n_suppress = (int)h.sup.size();
     h.o.begin_suppress_tokens = h.bsup.empty() ? nullptr : h.bsup.data();
     h.o.n_begin_suppress = (int)h.bsup.size();
-    m->slot_ref[slot] = wm_model::SlotRef{true, nullptr, 0, B, o->n_prompt + 1 + o->max_loop, h.tt, lp};
+    m->slot_ref[slot] = wm_model::SlotRef{true, nullptr, 0, B, o->n_prompt + 1 + o->max_loop, h.tt, lp, ns.token >= 0};
 }
 // the held submit runs alone, on its own slot's state (no partner came, or the partner did not match)
 static int flush_held(wm_model* m) {
@@ -2129,7 +2220,8 @@ static int flush_held(wm_model* m) {
     if (!h.active) return 0;
     h.active = false;
     wm_model::SlotRef& r = m->slot_ref[h.slot];
-    const int rc = submit_on(m, slot_state(m, h.slot), h.mel, h.on_dev, h.B, &h.o, false, nullptr, 0, h.tt ? &h.cols : nullptr, nullptr, h.lp);
+    const int rc = submit_on(m, slot_state(m, h.slot), h.mel, h.on_dev, h.B, &h.o, false, nullptr, 0, h.tt ? &h.cols : nullptr, nullptr, h.lp,
+                             NsAsk{h.ns_token, h.ns_init});
     if (rc) {
         r = wm_model::SlotRef{};
         return rc;
@@ -2183,13 +2275,14 @@ extern "C" int wm_transcribe_tt(wm_model* m, const float* mel, int mel_on_device
 // Pipelined form of Whisper.transcribe for back-to-back batches: submit enqueues the encoder and the greedy loop on the slot's
 // stream and returns; wait blocks until that slot's tokens are ready.
 static int submit_impl(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const std::vector<int32_t>* cols,
-                       bool lp = false) {
+                       bool lp = false, NsAsk ns = NsAsk()) {
     wm_model::SlotRef& r = m->slot_ref[slot];
     if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
     const int total = o->n_prompt + 1 + o->max_loop;
     const bool tt = cols != nullptr;
     const bool can_pair = m->cfg.coalesce == 2 && B <= m->cfg.max_batch && (B <= m->enc_chunk || B % m->enc_chunk == 0);
-    if (can_pair && m->held.active && m->held.B == B && m->held.tt == tt && m->held.lp == lp && same_opts(m->held, o)) {
+    if (can_pair && m->held.active && m->held.B == B && m->held.tt == tt && m->held.lp == lp && m->held.ns_token == ns.token &&
+        m->held.ns_init == ns.n_init && same_opts(m->held, o)) {
         // the partner of the held submit: both batches go out as ONE pass on a 2·B-row state
         wm_state** ps = nullptr;
         for (auto& pr : m->pairs)
@@ -2207,24 +2300,24 @@ static int submit_impl(wm_model* m, int slot, const float* mel, int mel_on_devic
                 pair_cols = h.cols;
                 pair_cols.insert(pair_cols.end(), cols->begin(), cols->end());
             }
-            const int rc = submit_on(m, ps, h.mel, h.on_dev, 2 * B, &h.o, false, mel, mel_on_device, tt ? &pair_cols : nullptr, nullptr, lp);
+            const int rc = submit_on(m, ps, h.mel, h.on_dev, 2 * B, &h.o, false, mel, mel_on_device, tt ? &pair_cols : nullptr, nullptr, lp, ns);
             if (rc) {
                 r0 = wm_model::SlotRef{};
                 return rc;
             }
             r0.st = *ps;
             r0.row0 = 0;
-            r = wm_model::SlotRef{true, *ps, B, B, total, tt, lp};
+            r = wm_model::SlotRef{true, *ps, B, B, total, tt, lp, ns.token >= 0};
             return 0;
         }
     }
     WMCHK(flush_held(m));
     if (can_pair) {  // wait for a partner (or for this slot's wm_transcribe_wait)
-        hold(m, slot, mel, mel_on_device, B, o, cols, lp);
+        hold(m, slot, mel, mel_on_device, B, o, cols, lp, ns);
         return 0;
     }
-    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, o, false, nullptr, 0, cols, nullptr, lp));
-    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, total, tt, lp};
+    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, o, false, nullptr, 0, cols, nullptr, lp, ns));
+    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, total, tt, lp, ns.token >= 0};
     return 0;
 }
 extern "C" int wm_transcribe_submit(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o) {
@@ -2296,9 +2389,10 @@ extern "C" int wm_transcribe_submit_rows(wm_model* m, int slot, const float* mel
     return 0;
 }
 static int wait_impl(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_times, float* token_logprobs = nullptr,
-                     float* avg_logprob = nullptr) {
+                     float* avg_logprob = nullptr, float* no_speech_prob = nullptr) {
     wm_model::SlotRef& r = m->slot_ref[slot];
     if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
+    if (no_speech_prob && !r.ns) return fail(WM_E_STATE, "this slot's pass was submitted without the no-speech probe (wm_transcribe_submit_lp_ns)");
     if (token_logprobs && !r.lp) return fail(WM_E_STATE, "this slot's pass was submitted without log-probabilities (wm_transcribe_submit_lp)");
     if (token_times && !r.tt) return fail(WM_E_STATE, "this slot's pass was submitted without token timestamps (wm_transcribe_submit_tt)");
     if (m->held.active && m->held.slot == slot) {  // no partner came: the held batch runs alone now
@@ -2306,7 +2400,7 @@ static int wait_impl(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_toke
         if (rc) return rc;
     }
     wm_state* s = r.st;
-    const int rc = wait_on(m, s, tokens_out, n_tokens, r.row0, r.rows, nullptr, 0, 0, token_times, token_logprobs, avg_logprob);
+    const int rc = wait_on(m, s, tokens_out, n_tokens, r.row0, r.rows, nullptr, 0, 0, token_times, token_logprobs, avg_logprob, no_speech_prob);
     if (!rc) {
         m->last_steps[slot] = s->last_steps;
         m->align_ref[slot] = r.tt ? wm_model::AlignRef{s, r.row0, r.rows, s->al.gen} : wm_model::AlignRef{};
@@ -2368,6 +2462,57 @@ extern "C" int wm_transcribe_submit_lp(wm_model* m, int slot, const float* mel, 
 extern "C" int wm_transcribe_wait_lp(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob) {
     if (!m || !tokens_out || !n_tokens || !token_logprobs || !avg_logprob || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
     return wait_impl(m, slot, tokens_out, n_tokens, nullptr, token_logprobs, avg_logprob);
+}
+// ---- no-speech probe: the _lp trio plus the probability of no_speech_token at each row's <|startoftranscript|>
+// position, prompt length - n_init.  Everything is refused before anything is launched.
+static int ns_check(wm_model* m, const wm_decode_opts& o2, int B, const int32_t* prompts, const int32_t* prompt_len, int no_speech_token, int n_init) {
+    if (no_speech_token < 0 || no_speech_token >= m->cfg.dims.vocab) return fail(WM_E_ARG, "no_speech_token %d is not a vocabulary id", no_speech_token);
+    if (n_init < 1) return fail(WM_E_ARG, "n_init must be >= 1 (the initial ids start at <|startoftranscript|>)");
+    if (prompts) {
+        for (int b = 0; b < B; ++b)
+            if (n_init > prompt_len[b]) return fail(WM_E_ARG, "n_init %d exceeds prompt_len[%d] = %d", n_init, b, prompt_len[b]);
+    } else if (n_init > o2.n_prompt) {
+        return fail(WM_E_ARG, "n_init %d exceeds the prompt length %d", n_init, o2.n_prompt);
+    }
+    return 0;
+}
+extern "C" int wm_transcribe_lp_ns(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const int32_t* prompts,
+                                   const int32_t* prompt_len, int prompt_stride, int no_speech_token, int n_init, int32_t* tokens_out,
+                                   int32_t* n_tokens, float* token_logprobs, float* avg_logprob, float* no_speech_prob) {
+    if (!m || !mel || !tokens_out || !n_tokens || !token_logprobs || !avg_logprob || !no_speech_prob) return fail(WM_E_ARG, "bad argument");
+    wm_decode_opts o2;
+    RowPrompts rows;
+    WMCHK(lp_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));
+    WMCHK(ns_check(m, o2, B, prompts, prompt_len, no_speech_token, n_init));
+    WMCHK(flush_held(m));
+    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, &o2, true, nullptr, 0, nullptr, prompts ? &rows : nullptr, true, NsAsk{no_speech_token, n_init}));
+    WMCHK(wait_on(m, m->cached, tokens_out, n_tokens, 0, -1, nullptr, 0, 0, nullptr, token_logprobs, avg_logprob, no_speech_prob));
+    m->last_steps[0] = m->cached->last_steps;
+    m->align_ref[0] = wm_model::AlignRef{};
+    return 0;
+}
+extern "C" int wm_transcribe_submit_lp_ns(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o,
+                                          const int32_t* prompts, const int32_t* prompt_len, int prompt_stride, int no_speech_token, int n_init) {
+    if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
+    wm_decode_opts o2;
+    RowPrompts rows;
+    WMCHK(lp_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));
+    WMCHK(ns_check(m, o2, B, prompts, prompt_len, no_speech_token, n_init));
+    const NsAsk ns{no_speech_token, n_init};
+    if (!prompts) return submit_impl(m, slot, mel, mel_on_device, B, &o2, nullptr, true, ns);
+    wm_model::SlotRef& r = m->slot_ref[slot];  // (a per-row pass is never held for a coalesce = 2 partner)
+    if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    WMCHK(flush_held(m));
+    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, &o2, false, nullptr, 0, nullptr, &rows, true, ns));
+    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, o2.n_prompt + 1 + o2.max_loop, false, true, true};
+    return 0;
+}
+extern "C" int wm_transcribe_wait_lp_ns(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob,
+                                        float* no_speech_prob) {
+    if (!m || !tokens_out || !n_tokens || !token_logprobs || !avg_logprob || !no_speech_prob || slot < 0 || slot >= wm_model::NSLOT)
+        return fail(WM_E_ARG, "bad argument");
+    return wait_impl(m, slot, tokens_out, n_tokens, nullptr, token_logprobs, avg_logprob, no_speech_prob);
 }
 // ---- token-level timestamps ------------------------------------------------------------------------------------
 extern "C" int wm_set_alignment_heads(wm_model* m, const int32_t* layer_head_pairs, int n_pairs) {
@@ -2684,12 +2829,23 @@ extern "C" int wm_transcribe_pcm_tt(wm_model* m, const float* pcm, const int32_t
     return transcribe_impl(m, m->fe.mel.as<float>(), 1, B, o, &cols, tokens_out, n_tokens, token_times);
 }
 
-// ---- sequential long-form transcription --------------------------------------------------------------------------
+// ---- sequential long-form transcription (thresholds and no-speech window skipping: §18) -----------------------------
 struct wm_long_result {
     std::vector<std::vector<int32_t>> tokens;  // per utterance: the concatenation of its segments' ids
     std::vector<std::vector<wm_segment>> segs;
     int windows = 0, stalled = 0, passes = 0, rows = 0;
     int longest_prompt = 0, row_passes = 0;  // longest decoder prompt a window of a real utterance carried; passes that went per row
+    // thresholds (quality = either use_* flag of wm_long_opts was set): per utterance the window log in decode order,
+    // skipped windows included, and each segment's window values
+    struct Window {
+        int64_t seek;
+        float avg_logprob, no_speech_prob;
+        int32_t skipped;
+    };
+    bool quality = false;
+    int skipped = 0;
+    std::vector<std::vector<Window>> wins;
+    std::vector<std::vector<float>> seg_avg, seg_nsp;
 };
 
 // HF WhisperGenerationMixin._retrieve_segment (time_precision 0.02, time_precision_features 0.01, input_stride 2) on one window's
@@ -2840,6 +2996,15 @@ static void long_prompt(const int32_t* seq, const wm_segment* segs, int n_segs, 
     out.insert(out.end(), init, init + n_init);
 }
 static int long_opts_check(const wm_long_opts* lo, const int32_t* init, int n_init, int max_loop, int vocab, int n_text_ctx, int pass_rows) {
+    if (lo && lo->use_no_speech_threshold) {  // HF dereferences logprob_threshold whenever no_speech_threshold is set
+        if (!lo->use_logprob_threshold) return fail(WM_E_ARG, "no_speech_threshold needs logprob_threshold");
+        if (lo->no_speech_token < 0 || lo->no_speech_token >= vocab) return fail(WM_E_ARG, "no_speech_token %d is not a vocabulary id", lo->no_speech_token);
+    }
+    if (lo && (lo->use_logprob_threshold || lo->use_no_speech_threshold) && lo->no_speech_token != -1 &&
+        (lo->no_speech_token < 0 || lo->no_speech_token >= vocab))  // (-1 with logprob_threshold alone: no probe, no_speech_prob is NaN)
+        return fail(WM_E_ARG, "no_speech_token %d is neither -1 nor a vocabulary id", lo->no_speech_token);
+    if (lo && (lo->use_logprob_threshold || lo->use_no_speech_threshold) && dec_lanes_for(pass_rows) != 1)
+        return fail(WM_E_ARG, "log-probabilities need a single-lane decode state");
     if (long_opts_plain(lo)) {
         if (lo && lo->prompt_condition_type == 1) return fail(WM_E_ARG, "prompt_condition_type all-segments needs condition_on_prev_tokens");
         return 0;
@@ -2903,6 +3068,11 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
                     const wm_long_opts* lo) {
     const wm_dims& c = m->cfg.dims;
     const bool plain = long_opts_plain(lo);
+    // thresholds: every pass is a log-prob pass; with a no_speech_token it also carries the probe at the first of the
+    // o->n_prompt initial ids.  A window is skipped iff avg_logprob < logprob_threshold and no_speech_prob > no_speech_threshold.
+    const bool quality = lo && (lo->use_logprob_threshold || lo->use_no_speech_threshold);
+    const NsAsk ns = quality && lo->no_speech_token >= 0 ? NsAsk{lo->no_speech_token, o->n_prompt} : NsAsk();  // (range checked up front)
+    res->quality = quality;
     // half the batch per state (when it fits), so that two passes are in flight whenever two utterances are pending
     const int W = 2 * c.n_audio_ctx, R = std::min((B + 1) / 2, m->cfg.max_batch), total = plain ? o->n_prompt + 1 + o->max_loop : c.n_text_ctx;
     std::vector<int32_t> row_prompts[2], row_len[2];  // per state: the pass's prompts [R][n_text_ctx] and their lengths
@@ -2918,10 +3088,15 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
         WMCHK(grow(L.items[k], (size_t)R * 3 * 4));
     }
     std::vector<int32_t> toks((size_t)R * total), cnt(R);
+    std::vector<float> lps(quality ? (size_t)R * total : 0), avg(R, 0.f), nsp(R, NAN);
     std::vector<wm_segment> segs;
+    auto collect = [&](int k) {
+        return wait_on(m, L.st[k], toks.data(), cnt.data(), 0, -1, nullptr, 0, 0, nullptr, quality ? lps.data() : nullptr, quality ? avg.data() : nullptr,
+                       ns.token >= 0 ? nsp.data() : nullptr);
+    };
     auto drain = [&]() {  // an error mid-run: let the other pass finish before returning
         for (int k = 0; k < 2; ++k)
-            if (n_items[k] && L.st[k] && L.st[k]->pending) (void)wait_on(m, L.st[k], toks.data(), cnt.data());
+            if (n_items[k] && L.st[k] && L.st[k]->pending) (void)collect(k);
     };
     int cursor = 0;
     for (;;) {
@@ -2964,7 +3139,7 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
                 res->longest_prompt = std::max(res->longest_prompt, o->n_prompt);
                 std::fill(row_len[k].begin(), row_len[k].end(), o->n_prompt);
                 pass_total[k] = o->n_prompt + 1 + o->max_loop;
-                if (!rc) rc = submit_on(m, &L.st[k], L.win[k].as<float>(), 1, R, o, false);
+                if (!rc) rc = submit_on(m, &L.st[k], L.win[k].as<float>(), 1, R, o, false, nullptr, 0, nullptr, nullptr, quality, ns);
             } else if (!rc) {
                 wm_decode_opts o2;
                 RowPrompts rows;
@@ -2974,7 +3149,7 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
                     res->longest_prompt = std::max(res->longest_prompt, o2.n_prompt);
                     ++res->row_passes;
                 }
-                if (!rc) rc = submit_on(m, &L.st[k], L.win[k].as<float>(), 1, R, &o2, false, nullptr, 0, nullptr, &rows);
+                if (!rc) rc = submit_on(m, &L.st[k], L.win[k].as<float>(), 1, R, &o2, false, nullptr, 0, nullptr, &rows, quality, ns);
             }
             if (rc) {
                 n_items[k] = 0;
@@ -2989,7 +3164,7 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
         for (int j = 0; j < 2; ++j)
             if (n_items[j] && (k < 0 || order[j] < order[k])) k = j;
         if (k < 0) break;
-        const int rc = wait_on(m, L.st[k], toks.data(), cnt.data());
+        const int rc = collect(k);
         const int n = n_items[k];
         n_items[k] = 0;
         if (rc) {
@@ -3003,6 +3178,17 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
             int g1 = cnt[r];
             if (g1 > n_prompt && row[g1 - 1] == o->eot) --g1;  // HF drops the trailing eos
             const int g0 = std::min(n_prompt, g1);
+            if (quality) {
+                const bool skip = lo->use_no_speech_threshold && avg[r] < lo->logprob_threshold && nsp[r] > lo->no_speech_threshold;
+                res->wins[b].push_back(wm_long_result::Window{seek[b], avg[r], nsp[r], skip ? 1 : 0});
+                if (skip) {  // HF: no segments, no ids, seek += seek_num_frames (not _retrieve_segment's advance)
+                    seek[b] += snf[b];
+                    busy[b] = 0;
+                    ++res->windows;
+                    ++res->skipped;
+                    continue;
+                }
+            }
             int adv = long_segments(row + g0, g1 - g0, o->timestamp_begin, seek[b], snf[b], segs);
             if (adv == 0) {  // the deviation: HF would decode this window again, forever
                 adv = snf[b];
@@ -3014,6 +3200,10 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
                 seq.insert(seq.end(), row + g0 + sg.first, row + g0 + sg.first + sg.count);
                 sg.first = first;
                 res->segs[b].push_back(sg);
+                if (quality) {
+                    res->seg_avg[b].push_back(avg[r]);
+                    res->seg_nsp[b].push_back(nsp[r]);
+                }
             }
             seek[b] += adv;
             busy[b] = 0;
@@ -3028,6 +3218,9 @@ static int transcribe_long_impl(wm_model* m, const float* mel_dev, int T, const 
     wm_long_result* r = new wm_long_result();
     r->tokens.resize(B);
     r->segs.resize(B);
+    r->wins.resize(B);
+    r->seg_avg.resize(B);
+    r->seg_nsp.resize(B);
     const int rc = long_run(m, mel_dev, T, nf, B, o, r, lo);
     (void)hipStreamSynchronize(m->stream);
     long_release(m);
@@ -3111,6 +3304,33 @@ extern "C" int wm_long_result_prompt_stats(const wm_long_result* r, int32_t* lon
     if (!r || !longest_prompt || !row_passes) return fail(WM_E_ARG, "bad argument");
     *longest_prompt = r->longest_prompt;
     *row_passes = r->row_passes;
+    return 0;
+}
+extern "C" int wm_long_result_quality(const wm_long_result* r, int b, float* seg_avg_logprob, float* seg_no_speech_prob) {
+    if (!r || b < 0 || b >= (int)r->tokens.size()) return fail(WM_E_ARG, "bad argument");
+    if (!r->quality) return fail(WM_E_STATE, "this run had no thresholds (wm_long_opts.use_logprob_threshold / use_no_speech_threshold)");
+    if ((!seg_avg_logprob || !seg_no_speech_prob) && !r->segs[b].empty()) return fail(WM_E_ARG, "bad argument");
+    std::copy(r->seg_avg[b].begin(), r->seg_avg[b].end(), seg_avg_logprob);
+    std::copy(r->seg_nsp[b].begin(), r->seg_nsp[b].end(), seg_no_speech_prob);
+    return 0;
+}
+extern "C" int wm_long_result_windows(const wm_long_result* r, int b, int32_t* n_windows, int64_t* seek, float* avg_logprob, float* no_speech_prob,
+                                      int32_t* skipped) {
+    if (!r || b < 0 || b >= (int)r->tokens.size() || !n_windows) return fail(WM_E_ARG, "bad argument");
+    if (!r->quality) return fail(WM_E_STATE, "this run had no thresholds (wm_long_opts.use_logprob_threshold / use_no_speech_threshold)");
+    const std::vector<wm_long_result::Window>& w = r->wins[b];
+    *n_windows = (int32_t)w.size();
+    for (size_t i = 0; i < w.size(); ++i) {
+        if (seek) seek[i] = w[i].seek;
+        if (avg_logprob) avg_logprob[i] = w[i].avg_logprob;
+        if (no_speech_prob) no_speech_prob[i] = w[i].no_speech_prob;
+        if (skipped) skipped[i] = w[i].skipped;
+    }
+    return 0;
+}
+extern "C" int wm_long_result_skip_stats(const wm_long_result* r, int32_t* skipped_windows) {
+    if (!r || !skipped_windows) return fail(WM_E_ARG, "bad argument");
+    *skipped_windows = r->skipped;
     return 0;
 }
 extern "C" void wm_long_result_free(wm_long_result* r) { delete r; }
@@ -3898,6 +4118,33 @@ extern "C" int wm_op_logits_lp(float* logits, int32_t* ids, float* logprob, cons
                                const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
     if (!logprob) return fail(WM_E_ARG, "bad argument");
     return op_logits(logits, ids, logprob, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype);
+}
+
+// The no-speech probe's launches on the kernel variant wm_op_logits_lp would pick for (dtype, K, B): the LP sweep with
+// no mask and no ranges, then no_speech_finish_kernel.  prob[b] = softmax(logits[b])[token], lse[b] = logsumexp(logits[b]).
+extern "C" int wm_op_no_speech(float* prob, float* lse, const float* x, const float* ln_g, const float* ln_b, const float* emb, int B, int N, int K,
+                               int dtype, int token) {
+    if (!prob || !lse || !x || !ln_g || !ln_b || !emb || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
+    if (K != 128 && K != 384 && K != 512) return fail(WM_E_ARG, "K must be 128, 384 or 512 (the logits kernels' d_model)");
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    if (token < 0 || token >= N) return fail(WM_E_ARG, "token %d is not a vocabulary id", token);
+    TmpDev t;
+    t.bufs.reserve(12);
+    const int npart = dec_logits_parts(N);
+    DevBuf &dx = t.add(), &g = t.add(), &be = t.add(), &w = t.add(), &pm = t.add(), &pi = t.add(), &ps = t.add(), &pr = t.add(), &ls = t.add();
+    WMCHK(upload(dx, x, (size_t)B * K, WM_F32));
+    WMCHK(upload(g, ln_g, K, WM_F32));
+    WMCHK(upload(be, ln_b, K, WM_F32));
+    WMCHK(upload(w, emb, (size_t)N * K, dtype));
+    for (DevBuf* d : {&pm, &pi, &ps}) WMCHK(d->alloc((size_t)B * npart * 4, true));
+    WMCHK(pr.alloc((size_t)B * 4, true));
+    WMCHK(ls.alloc((size_t)B * 4, true));
+    WMCHK(ns_sweep(dtype, dx.as<float>(), g.as<float>(), be.as<float>(), w.p, N, K, B, npart, pm.as<float>(), pi.as<int>(), ps.as<float>(), token,
+                   pr.as<float>(), ls.as<float>(), nullptr));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(prob, pr.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lse, ls.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // The absorbed cross-attention of m->xattn models, wired as launch_cross_attn + cross_attn_merge wire it: absorb, X sweep, merge.

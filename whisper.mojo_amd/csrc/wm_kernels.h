@@ -314,6 +314,25 @@ struct RowPromptParams {
 // as launch_init_tokens, tok_rows / pos_rows [Lmax][B] required; also writes key_lo
 void launch_init_tokens_rows(const InitTokensParams& p, const RowPromptParams& r, hipStream_t st);
 void launch_set_rows_step(StepCtl* ctl, int Lmax, int* pos, const int* len, int pos_delta, int B, hipStream_t st);
+// No-speech probe.  capture: copies B rows of d floats (the residual rows of one prefill position, contiguous in the
+// position-major activations) into the probe's [B][d] buffer.  finish: per row, the probability of `token` under the softmax whose
+// per-part (max, Σ exp(v − max)) pairs the LP logits kernel left in pmax / psum (its amax_val / lp_s outputs, launched without mask
+// and ranges on the captured rows), merged in ascending part order; the token's logit is recomputed from the row.
+struct NoSpeechParams {
+    const float* x;  // [B][ldx] captured residual rows (before the final LayerNorm)
+    int ldx;
+    const float* ln_g;
+    const float* ln_b;
+    const void* emb;  // [N][K] token embedding in the logits kernel's operand dtype
+    int K, token, B;
+    const float* pmax;  // [B][stride]
+    const float* psum;
+    int npart, stride;
+    float* prob;  // [B] out: exp(logit − lse)
+    float* lse;   // [B] out: log Σ exp over the whole vocabulary
+};
+void launch_no_speech_capture(const float* rows, float* out, int B, int d, hipStream_t st);
+template <typename TW> void launch_no_speech_finish(const NoSpeechParams& p, hipStream_t st);
 // rows of the gather buffer of SURVEY §8e: dst[r] = [n_tokens[r], ids of row r zero-padded to `stride`] for r < rows; rows in
 // [rows, rows_cap) are zeroed (ragged shards gather a fixed row count per rank)
 void launch_pack_tokens(const int* out_tokens, const int* n_tokens, int out_stride, int rows, int rows_cap, int stride, int* dst, hipStream_t st);

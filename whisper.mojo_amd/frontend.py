@@ -74,9 +74,14 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
                                max_loop: int = MAX_LOOP, suppress_tokens: Sequence[int] = (), begin_suppress_tokens: Sequence[int] = (),
                                timestamps=(50364, 50363, 50), return_stats: bool = False, prompt_ids=None,
                                condition_on_prev_tokens: bool = False, prompt_condition_type: str = "first-segment",
-                               prev_sot_token: int = 50361):
+                               prev_sot_token: int = 50361, logprob_threshold=None, no_speech_threshold=None, no_speech_token=None):
     """Sequential long-form transcription of 16 kHz PCM of any length (HF generate's long-form path), the long
-    log-mel never leaving the GPU.  prompt_ids / condition_on_prev_tokens / prompt_condition_type: as Whisper.transcribe_long_form.  Returns per recording {"sequence": ids, "segments": [{"start", "end", "tokens"}]}."""
+    log-mel never leaving the GPU.  prompt_ids / condition_on_prev_tokens / prompt_condition_type / logprob_threshold /
+    no_speech_threshold / no_speech_token: as Whisper.transcribe_long_form.  Returns per recording {"sequence": ids, "segments": [{"start", "end", "tokens"}]}."""
+    lo, _keep2 = _lib.long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token, logprob_threshold,
+                                no_speech_threshold, no_speech_token)
+    if no_speech_token is not None and int(no_speech_token) >= model.config.vocab_size:
+        raise ValueError(f"no_speech_token {no_speech_token} is not a vocabulary id")
     if timestamps is None:
         raise ValueError("long-form transcription needs the timestamp rules")
     buf, n, stride = _pack(audios)
@@ -86,10 +91,9 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
     opts, _keep = model._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
     h = C.c_void_p()
-    lo, _keep2 = _lib.long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token)
     _lib.check(_lib.lib().wm_transcribe_long_pcm_ex(model._h, buf.ctypes.data_as(fp), n.ctypes.data_as(ip), len(audios), stride,
                                                     C.byref(opts), C.byref(lo), C.byref(h)))
-    out, stats = _lib.long_result(h, len(audios))
+    out, stats = _lib.long_result(h, len(audios), logprob_threshold is not None or no_speech_threshold is not None)
     return (out, stats) if return_stats else out
 
 

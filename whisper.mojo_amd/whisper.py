@@ -235,6 +235,17 @@ class Whisper:
             tab[b, :r.size] = r
         return tab, lens
 
+    def _ns_args(self, no_speech_token, n_init, prompt, prompts, return_logprobs):
+        """-> None or (token, n_init), checked on the host (ValueError) before anything else"""
+        if no_speech_token is None:
+            if n_init is not None:
+                raise ValueError("n_init without no_speech_token")
+            return None
+        if not return_logprobs:
+            raise ValueError("no_speech_token needs return_logprobs=True")
+        lens = len(prompt) if prompts is None else [len(r) for r in prompts]
+        return _lib.no_speech_args(no_speech_token, n_init, lens, self.config.vocab_size)
+
     @staticmethod
     def _split_times(times, n, B):
         return [times[b, :n[b]].tolist() for b in range(B)]
@@ -242,7 +253,8 @@ class Whisper:
     def transcribe_batch(self, mel, prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP,
                          ignore_eot: bool = False, suppress_tokens: Sequence[int] = (),
                          begin_suppress_tokens: Sequence[int] = (), timestamps=None, return_token_timestamps: bool = False,
-                         n_frames=None, prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False):
+                         n_frames=None, prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False,
+                         no_speech_token: Optional[int] = None, n_init: Optional[int] = None):
         """Batched Whisper.transcribe: one List[int] per utterance = prompt + generated ids (+ eot when hit).
         return_logprobs: also return (token_logprobs, avg_logprob) as (ids, (token_logprobs, avg_logprob)): per utterance the
         log-probability of every id in the layout of its id list (0 at the prompt positions), HF's log_softmax of the processed
@@ -252,7 +264,12 @@ class Whisper:
         alone with its own prompt and comes back as its own prompt + generated ids.  Not with return_token_timestamps.
         return_token_timestamps: also return, per utterance, the time in seconds each id was spoken (HF generate's
         return_token_timestamps; needs set_alignment_heads) as (ids, times); n_frames: mel frames of real audio per utterance
-        (HF's attention_mask.sum(-1)), None = the whole window."""
+        (HF's attention_mask.sum(-1)), None = the whole window.
+        no_speech_token (needs return_logprobs): also openai-whisper's no_speech_prob [B], HF WhisperNoSpeechDetection — the
+        probability of that id under the raw logits at each row's <|startoftranscript|> position, prompt length - n_init; the second
+        element becomes (token_logprobs, avg_logprob, no_speech_prob).  n_init: the number of initial ids (<|startoftranscript|>
+        first); defaults to the shared prompt's length, required with prompts=."""
+        ns = self._ns_args(no_speech_token, n_init, prompt, prompts, return_logprobs)
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
@@ -267,9 +284,14 @@ class Whisper:
             n = np.zeros(B, np.int32)
             lps = np.zeros((B, total), np.float32)
             avg = np.zeros(B, np.float32)
-            _lib.check(_lib.lib().wm_transcribe_lp(self._h, ptr, on_dev, B, C.byref(opts), _ip(tab) if tab is not None else None,
-                                                   _ip(lens) if tab is not None else None, tab.shape[1] if tab is not None else 0,
-                                                   _ip(toks), _ip(n), _fp(lps), _fp(avg)))
+            rows = (_ip(tab) if tab is not None else None, _ip(lens) if tab is not None else None, tab.shape[1] if tab is not None else 0)
+            if ns is not None:
+                nsp = np.zeros(B, np.float32)
+                _lib.check(_lib.lib().wm_transcribe_lp_ns(self._h, ptr, on_dev, B, C.byref(opts), *rows, ns[0], ns[1], _ip(toks), _ip(n),
+                                                          _fp(lps), _fp(avg), _fp(nsp)))
+                self.last_tokens, self.last_counts, self.last_logprobs = toks, n, lps
+                return [toks[b, :n[b]].tolist() for b in range(B)], (self._split_times(lps, n, B), avg, nsp)
+            _lib.check(_lib.lib().wm_transcribe_lp(self._h, ptr, on_dev, B, C.byref(opts), *rows, _ip(toks), _ip(n), _fp(lps), _fp(avg)))
             self.last_tokens, self.last_counts, self.last_logprobs = toks, n, lps
             return [toks[b, :n[b]].tolist() for b in range(B)], (self._split_times(lps, n, B), avg)
         if prompts is not None:
@@ -304,8 +326,14 @@ class Whisper:
                              suppress_tokens: Sequence[int] = (), begin_suppress_tokens: Sequence[int] = (),
                              timestamps=(50364, 50363, 50), return_stats: bool = False, prompt_ids: Optional[Sequence[int]] = None,
                              condition_on_prev_tokens: bool = False, prompt_condition_type: str = "first-segment",
-                             prev_sot_token: int = 50361):
-        """Sequential long-form transcription (HF generate's long-form path, greedy; DESIGN §15, §16).
+                             prev_sot_token: int = 50361, logprob_threshold: Optional[float] = None,
+                             no_speech_threshold: Optional[float] = None, no_speech_token: Optional[int] = None):
+        """Sequential long-form transcription (HF generate's long-form path, greedy; DESIGN §15, §16, §18).
+        logprob_threshold / no_speech_threshold (HF generate's options, temperature 0 only; no_speech_token: the <|nospeech|> id,
+        HF's no_timestamps_token_id - 1): a window with avg_logprob < logprob_threshold and no_speech_prob > no_speech_threshold is
+        skipped — no segments, no ids, seek advances by the window's frames.  With either threshold every segment carries its window's
+        "avg_logprob" / "no_speech_prob", every utterance its window log "windows" (skipped windows included), the stats
+        "skipped_windows".  logprob_threshold alone changes no ids.  ValueError: no_speech_threshold without logprob_threshold or token.
         condition_on_prev_tokens / prompt_ids / prompt_condition_type: HF generate's options of the same names — every window's
         decoder prompt carries the utterance's previous text (up to half the decoder context) and / or prompt_ids (as
         WhisperProcessor.get_prompt_ids returns them, leading <|startofprev|> = prev_sot_token included).
@@ -314,6 +342,11 @@ class Whisper:
         array's length).  timestamps: (timestamp_begin, no_timestamps_id, max_initial_timestamp_index | None), required.
         Returns per utterance {"sequence": ids, "segments": [{"start", "end", "tokens"}]} — HF's return_segments output with
         the padding-free sequences row; return_stats also returns {"windows", "stalled"}."""
+        lo, _keep3 = _lib.long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token, logprob_threshold,
+                                    no_speech_threshold, no_speech_token)
+        if no_speech_token is not None and int(no_speech_token) >= self.config.vocab_size:
+            raise ValueError(f"no_speech_token {no_speech_token} is not a vocabulary id")
+        quality = logprob_threshold is not None or no_speech_threshold is not None
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
         if timestamps is None:
@@ -347,7 +380,7 @@ class Whisper:
             if not t.is_cuda:
                 return self.transcribe_long_form(t.float().numpy(), n_frames, prompt, eot, max_loop, suppress_tokens,
                                                  begin_suppress_tokens, timestamps, return_stats, prompt_ids, condition_on_prev_tokens,
-                                                 prompt_condition_type, prev_sot_token)
+                                                 prompt_condition_type, prev_sot_token, logprob_threshold, no_speech_threshold, no_speech_token)
             keep = t.contiguous().float()
             torch.cuda.current_stream(keep.device).synchronize()  # the library reads it on its own HIP stream
             ptr, on_dev = C.c_void_p(keep.data_ptr()), 1
@@ -355,10 +388,9 @@ class Whisper:
         nf = self._frames_arg(n_frames, B)
         opts, _keep2 = self._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
         h = C.c_void_p()
-        lo, _keep3 = _lib.long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token)
         _lib.check(_lib.lib().wm_transcribe_long_ex(self._h, ptr, on_dev, B, T, _ip(nf) if nf is not None else None, C.byref(opts),
                                                     C.byref(lo), C.byref(h)))
-        out, stats = _lib.long_result(h, B)
+        out, stats = _lib.long_result(h, B, quality)
         return (out, stats) if return_stats else out
 
     def alignment_weights(self, slot: int = 0) -> np.ndarray:
@@ -372,12 +404,15 @@ class Whisper:
     def transcribe_submit(self, mel, slot: int = 0, prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP,
                           ignore_eot: bool = False, suppress_tokens: Sequence[int] = (), begin_suppress_tokens: Sequence[int] = (),
                           timestamps=None, return_token_timestamps: bool = False, n_frames=None,
-                          prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False):
+                          prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False,
+                          no_speech_token: Optional[int] = None, n_init: Optional[int] = None):
         """Pipelined form (wm_transcribe_submit): enqueue encoder + greedy loop for this batch on pipeline slot 0..7 and
         return at once; `transcribe_wait(slot)` collects the ids.  Submitting batch i+1 before waiting for batch i lets
         its encoder overlap batch i's decode.  return_token_timestamps / n_frames: as transcribe_batch; the matching
         transcribe_wait then returns (ids, times).  return_logprobs: as transcribe_batch; the matching transcribe_wait returns
-        (ids, (token_logprobs, avg_logprob))."""
+        (ids, (token_logprobs, avg_logprob)).  no_speech_token / n_init: as transcribe_batch; the matching transcribe_wait returns
+        (ids, (token_logprobs, avg_logprob, no_speech_prob))."""
+        ns = self._ns_args(no_speech_token, n_init, prompt, prompts, return_logprobs)
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
@@ -387,10 +422,13 @@ class Whisper:
             if return_token_timestamps:
                 raise ValueError("return_logprobs does not combine with return_token_timestamps")
             tab, lens = self._prompt_rows(prompts, B) if prompts is not None else (None, None)
-            _lib.check(_lib.lib().wm_transcribe_submit_lp(self._h, slot, ptr, on_dev, B, C.byref(opts), _ip(tab) if tab is not None else None,
-                                                          _ip(lens) if tab is not None else None, tab.shape[1] if tab is not None else 0))
+            rows = (_ip(tab) if tab is not None else None, _ip(lens) if tab is not None else None, tab.shape[1] if tab is not None else 0)
+            if ns is not None:
+                _lib.check(_lib.lib().wm_transcribe_submit_lp_ns(self._h, slot, ptr, on_dev, B, C.byref(opts), *rows, ns[0], ns[1]))
+            else:
+                _lib.check(_lib.lib().wm_transcribe_submit_lp(self._h, slot, ptr, on_dev, B, C.byref(opts), *rows))
             self._pending = getattr(self, "_pending", {})
-            self._pending[slot] = (B, (tab.shape[1] if tab is not None else len(p)) + 1 + max_loop, keep, "lp")
+            self._pending[slot] = (B, (tab.shape[1] if tab is not None else len(p)) + 1 + max_loop, keep, "lp_ns" if ns is not None else "lp")
             return
         if prompts is not None:  # per-utterance prompts, as transcribe_batch
             if return_token_timestamps:
@@ -413,6 +451,13 @@ class Whisper:
         B, total, _keep, tt = self._pending.pop(slot)
         toks = np.zeros((B, total), np.int32)
         n = np.zeros(B, np.int32)
+        if tt == "lp_ns":
+            lps = np.zeros((B, total), np.float32)
+            avg = np.zeros(B, np.float32)
+            nsp = np.zeros(B, np.float32)
+            _lib.check(_lib.lib().wm_transcribe_wait_lp_ns(self._h, slot, _ip(toks), _ip(n), _fp(lps), _fp(avg), _fp(nsp)))
+            self.last_tokens, self.last_counts, self.last_logprobs = toks, n, lps
+            return [toks[b, :n[b]].tolist() for b in range(B)], (self._split_times(lps, n, B), avg, nsp)
         if tt == "lp":
             lps = np.zeros((B, total), np.float32)
             avg = np.zeros(B, np.float32)

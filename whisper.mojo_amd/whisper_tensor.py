@@ -235,6 +235,20 @@ def logits_argmax(x, ln_g, ln_b, emb, dtype=DT_F32, mask=None, ranges=None, time
     return logits, ids
 
 
+def no_speech(x, ln_g, ln_b, emb, token: int, dtype=DT_F32):
+    """The no-speech probe's launches (wm_op_no_speech): (prob [B], lse [B]) — softmax(layer_norm(x)·embᵀ)[token] over
+    all N columns (no mask, no ranges) and the row's logsumexp, on the kernel variant logits_argmax(return_logprobs=True) picks."""
+    f = lambda a: np.ascontiguousarray(a, np.float32)
+    x, emb = f(x), f(emb)
+    g, b = f(ln_g).ravel(), f(ln_b).ravel()
+    if x.ndim != 2 or emb.ndim != 2 or emb.shape[1] != x.shape[1] or g.size != x.shape[1] or b.size != x.shape[1]:
+        raise ValueError("x must be [B, K], emb [N, K], ln_g / ln_b [K]")
+    B, K = x.shape
+    prob, lse = np.zeros(B, np.float32), np.zeros(B, np.float32)
+    _lib.check(_lib.lib().wm_op_no_speech(_fp(prob), _fp(lse), _fp(x), _fp(g), _fp(b), _fp(emb), B, emb.shape[0], K, dtype, int(token)))
+    return prob, lse
+
+
 def xattn(out: np.ndarray, q, Wk, Wv, bv, x, n_heads: int, nsplit: int, q_B: int = 0, out_dtype=DT_F32):
     """The absorbed cross-attention (wm_op_xattn): q [rows, d], Wk / Wv [d, d], bv [d], x [n_utt, n_keys, d], d = 64·n_heads;
     row r attends over x[r % q_B] (q_B > 0, prefill) or x[r] -> out [rows, d]."""
