@@ -1594,23 +1594,9 @@ __global__ __launch_bounds__(256, 2) void xattn_kernel(XAttnParams p) {
     const int utt = p.q_B > 0 ? row % p.q_B : row;
     const int len = p.n_keys, chunk = (len + p.nsplit - 1) / p.nsplit;
     const int j0 = split * chunk, j1 = min(len, j0 + chunk);
-    {
-        const bf16x8* src = (const bf16x8*)((const bf16*)p.qs + (size_t)row * 3 * H * D);
-        for (int i = threadIdx.x; i < 3 * (H + 1) * (D / 8); i += 256) {
-            const int img = i / ((H + 1) * (D / 8)), rem = i % ((H + 1) * (D / 8)), hh = rem / (D / 8), c8 = rem % (D / 8);
-            bf16x8 v = {};
-            if (hh < H) v = src[(img * H + hh) * (D / 8) + c8];
-            *reinterpret_cast<bf16x8*>(&sQ[(img * (H + 1) + hh) * XP + c8 * 8]) = v;
-        }
-    }
-    __syncthreads();
     const int hq = r16 < H ? r16 : H;
     const bf16* X = (const bf16*)p.X + (size_t)utt * p.x_stride;
     bf16* park = sX + w * 16 * XP;
-    f32x4 y[NDB];
-#pragma unroll
-    for (int db = 0; db < NDB; ++db) y[db] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run = -1e10f, l_run = 0.f;
     const int ntile = j1 > j0 ? (j1 - j0 + 15) / 16 : 0;
 
     auto load = [&](bf16x8 (&xr)[NKS], int t) {
@@ -1624,6 +1610,28 @@ __global__ __launch_bounds__(256, 2) void xattn_kernel(XAttnParams p) {
                 xr[ks] = *reinterpret_cast<const bf16x8*>(src + ks * 32);
         }
     };
+    // the wave's first X tile is requested before anything else: the q' staging and its barrier run under that round trip
+    bf16x8 xa[NKS], xb[NKS];
+    if (w < ntile) load(xa, w);
+    {  // q' images -> sQ: a thread owns one 16-byte column of every RPP-th (image, head) row, so its index split is done once
+        constexpr int C8 = D / 8, RPP = 256 / C8;
+        static_assert(RPP >= 3, "the three zero rows are filled by the first three row slots");
+        const bf16x8* src = (const bf16x8*)((const bf16*)p.qs + (size_t)row * 3 * H * D);
+        const int sr = threadIdx.x / C8, sc = threadIdx.x % C8;
+        if (sr < RPP) {
+#pragma unroll
+            for (int rr = sr; rr < 3 * H; rr += RPP) {
+                const int img = rr / H, hh = rr - img * H;
+                *reinterpret_cast<bf16x8*>(&sQ[(img * (H + 1) + hh) * XP + sc * 8]) = src[rr * C8 + sc];
+            }
+            if (sr < 3) *reinterpret_cast<bf16x8*>(&sQ[(sr * (H + 1) + H) * XP + sc * 8]) = bf16x8{};
+        }
+    }
+    __syncthreads();
+    f32x4 y[NDB];
+#pragma unroll
+    for (int db = 0; db < NDB; ++db) y[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run = -1e10f, l_run = 0.f;
     auto consume = [&](const bf16x8 (&xr)[NKS], int t) {
         // one accumulator per q' term: three independent MFMA chains of NKS instead of one dependent chain of 3·NKS
         f32x4 sk[3] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -1683,9 +1691,7 @@ __global__ __launch_bounds__(256, 2) void xattn_kernel(XAttnParams p) {
     };
 
     if (w < ntile) {
-        bf16x8 xa[NKS], xb[NKS];
         int t = w;
-        load(xa, t);
         while (true) {
             const bool more1 = t + 4 < ntile;
             if (more1) load(xb, t + 4);
@@ -1714,75 +1720,118 @@ __global__ __launch_bounds__(256, 2) void xattn_kernel(XAttnParams p) {
     }
     __syncthreads();
     const size_t prow = (size_t)row * p.nsplit + split;
-    for (int i = threadIdx.x; i < H * D; i += 256) {
-        const int h = i / D;
+    // the four waves' weights of a head: once per head (they were one expf per wave and output element), then 16-byte combines
+    __shared__ float sWg[4][H];
+    if (threadIdx.x < H) {
+        const int h = threadIdx.x;
         float M = -1e10f;
 #pragma unroll
         for (int v = 0; v < 4; ++v) M = fmaxf(M, sML[v][h][0]);
-        float L = 0.f, o = 0.f;
+        float L = 0.f;
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
             const float wgt = sML[v][h][1] > 0.f ? expf(sML[v][h][0] - M) : 0.f;
             L += wgt * sML[v][h][1];
-            o += wgt * sY[v * H * D + i];
+            sWg[v][h] = wgt;
         }
-        p.part_y[prow * H * D + i] = o;
-        if (i % D == 0) {
-            p.part_ml[(prow * H + h) * 2] = M;
-            p.part_ml[(prow * H + h) * 2 + 1] = L;
+        p.part_ml[(prow * H + h) * 2] = M;
+        p.part_ml[(prow * H + h) * 2 + 1] = L;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x * 4; i < H * D; i += 256 * 4) {
+        const int h = i / D;
+        f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const float wgt = sWg[v][h];
+            const f32x4 yv = *reinterpret_cast<const f32x4*>(&sY[v * H * D + i]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] += wgt * yv[k];
         }
+        *reinterpret_cast<f32x4*>(p.part_y + prow * H * D + i) = o;
     }
 }
 
 // Merge the chunk partials of one head (exactly attn_combine_kernel's weights) and apply Wv_h: out[row][h*64+e] =
 // y_h·Wv[h*64+e]ᵀ + bv[h*64+e].  grid (ceil(rows / 4), H), 256 threads: four rows per workgroup share each Wv row read.
 __global__ __launch_bounds__(256) void xattn_merge_kernel(XAttnParams p) {
-    constexpr int R = 4, DMAX = 512;
+    constexpr int R = 4, DMAX = 512, NSP = 2, NI = R * DMAX / 4 / 256;
     __shared__ __attribute__((aligned(16))) float sy[R][DMAX];
     __shared__ float sw[R][64], sL[R];
     const int r0 = blockIdx.x * R, h = blockIdx.y, t = threadIdx.x, D = p.d, H = p.H, ns = p.nsplit;
-    if (t < R * 64) {  // chunk weights of row r0 + t/64, one wave per row
-        const int r = t >> 6, lane = t & 63, row = r0 + r;
-        float m = -1e30f, l = 0.f;
-        if (row < p.rows && lane < ns) {
-            const float* ml = p.part_ml + (((size_t)row * ns + lane) * H + h) * 2;
-            m = ml[0];
-            l = ml[1];
-        }
-        const float M = wave_max(l > 0.f ? m : -1e30f);
-        const float wgt = l > 0.f ? expf(m - M) : 0.f;
-        const float L = wave_sum(wgt * l);
-        if (lane < 64) sw[r][lane] = wgt;
-        if (lane == 0) sL[r] = L;
+    // Everything is requested before anything is waited for (no address depends on loaded data): the (m, l) pairs, the partials
+    // of the first NSP chunks (all of them at the model paths' 1-2 chunks) and this thread's Wv fragments — one memory round trip
+    // where the reduce -> barrier -> combine -> barrier -> V-apply order made three.
+    const int wr = t >> 6, lane = t & 63;  // chunk weights of row r0 + wr, one wave per row
+    float m = -1e30f, l = 0.f;
+    if (r0 + wr < p.rows && lane < ns) {
+        const float* ml = p.part_ml + (((size_t)(r0 + wr) * ns + lane) * H + h) * 2;
+        m = ml[0];
+        l = ml[1];
     }
-    __syncthreads();
-    for (int i = t; i < R * D; i += blockDim.x) {
-        const int r = i / D, c = i % D, row = r0 + r;
-        float o = 0.f;
-        if (row < p.rows) {
-            const float* py = p.part_y + ((size_t)row * ns * H + h) * D + c;
-            for (int s = 0; s < ns; ++s) o += sw[r][s] * py[(size_t)s * H * D];
-            o *= 1.0f / sL[r];
+    f32x4 yv[NI][NSP];
+#pragma unroll
+    for (int k = 0; k < NI; ++k) {
+        const int j = t + 256 * k, r = j / (D / 4), c = (j % (D / 4)) * 4;
+        if (j < R * (D / 4) && r0 + r < p.rows) {
+            const float* py = p.part_y + ((size_t)(r0 + r) * ns * H + h) * D + c;
+#pragma unroll
+            for (int s = 0; s < NSP; ++s)
+                if (s < ns) yv[k][s] = *reinterpret_cast<const f32x4*>(py + (size_t)s * H * D);
         }
-        sy[r][c] = o;
     }
-    __syncthreads();
     // V-apply: four lanes per output feature e, interleaved over c so that they read 64 contiguous bytes of the Wv row per load
     // (one lane per whole Wv row, 64 rows per load, measured 14.4 us per launch at 128 rows)
     const int e = t >> 2, q = t & 3;
     const bf16* wv = (const bf16*)p.Wv + (size_t)(h * 64 + e) * D;
+    bf16x8 wf[DMAX / 32];
+#pragma unroll
+    for (int it = 0; it < DMAX / 32; ++it)
+        if (it < D / 32) wf[it] = *reinterpret_cast<const bf16x8*>(wv + (it * 4 + q) * 8);
+    {
+        const float M = wave_max(l > 0.f ? m : -1e30f);
+        const float wgt = l > 0.f ? expf(m - M) : 0.f;
+        const float L = wave_sum(wgt * l);
+        sw[wr][lane] = wgt;
+        if (lane == 0) sL[wr] = L;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NI; ++k) {
+        const int j = t + 256 * k, r = j / (D / 4), c = (j % (D / 4)) * 4;
+        if (j >= R * (D / 4)) continue;
+        f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (r0 + r < p.rows) {
+            const float* py = p.part_y + ((size_t)(r0 + r) * ns * H + h) * D + c;
+#pragma unroll
+            for (int s = 0; s < NSP; ++s)
+                if (s < ns) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) o[i] += sw[r][s] * yv[k][s][i];
+                }
+            for (int s = NSP; s < ns; ++s) {
+                const f32x4 y = *reinterpret_cast<const f32x4*>(py + (size_t)s * H * D);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) o[i] += sw[r][s] * y[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] *= 1.0f / sL[r];
+        }
+        *reinterpret_cast<f32x4*>(&sy[r][c]) = o;
+    }
+    __syncthreads();
     float acc[R] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int it = 0; it < D / 32; ++it) {
+#pragma unroll
+    for (int it = 0; it < DMAX / 32; ++it) {
+        if (it >= D / 32) continue;
         const int c = (it * 4 + q) * 8;
-        const bf16x8 wf = *reinterpret_cast<const bf16x8*>(wv + c);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const f32x4 ya = *reinterpret_cast<const f32x4*>(&sy[r][c]), yb = *reinterpret_cast<const f32x4*>(&sy[r][c + 4]);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) acc[r] = fmaf(ya[k], (float)wf[k], acc[r]);
+            for (int k = 0; k < 4; ++k) acc[r] = fmaf(ya[k], (float)wf[it][k], acc[r]);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) acc[r] = fmaf(yb[k], (float)wf[4 + k], acc[r]);
+            for (int k = 0; k < 4; ++k) acc[r] = fmaf(yb[k], (float)wf[it][4 + k], acc[r]);
         }
     }
 #pragma unroll
