@@ -217,6 +217,40 @@ int wm_transcribe_submit_lp_ns(wm_model* m, int slot, const float* mel, int mel_
 int wm_transcribe_wait_lp_ns(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob,
                              float* no_speech_prob);
 
+/* ---- language detection ---------------------------------------------------------------------------------------
+ * HF WhisperGenerationMixin.detect_language / openai-whisper detect_language: one decoder pass over [sot_token] alone at position 0,
+ * the logits of the n_lang candidate ids only, their arg-max (ties: the smaller token id, as an arg-max over the vocabulary row with
+ * the rest at -inf) and their softmax.  lang_ids: host [n_lang], 1 <= n_lang <= 128, any order, no duplicates.
+ *
+ * wm_detect_language: the encoder, the [sot] pass and the kernel.  lang_out: [B] token ids; probs_out: [B][n_lang] in list order, or
+ * NULL.  Uses slot 0's state, like wm_transcribe: afterwards that state holds no usable encoder output or K/V (its cache slot 0 was
+ * written by the [sot] pass), exactly as after wm_transcribe.  States of wm_state_new (wm_encode / wm_decode_step) are not touched.
+ *
+ * The _lang trio: the arguments of the _lp_ns trio plus the list, n_init (required, >= 2: the initial ids are the last n_init ids of
+ * every row, the language is the second of them) and the outputs lang_out [B], lang_probs [B][n_lang] (or NULL).  The language is
+ * detected on the device between the encoder and the prefill and written into each row's slot of the prompt table; nothing is read
+ * back before the wait and the audio is encoded once.  The id given at the language slot is a placeholder.  prompts == NULL:
+ * opts->prompt for every row.  token_logprobs == NULL and avg_logprob == NULL: a plain pass; no_speech_token < 0: no probe (then
+ * no_speech_prob is not written; a probe needs the log-prob outputs).  Always a per-row-prompt pass on a single-lane state; under
+ * coalesce = 2 it runs alone.  With everything on, ids, log-probs and no_speech_prob are those of _lp_ns called with the detected
+ * prompts.  The returned ids carry the detected language.
+ * WM_E_ARG, nothing launched: n_lang outside [1, 128]; an id outside the vocabulary or a duplicate; n_init < 2 or larger than a
+ * row's prompt; sot_token outside the vocabulary; a multi-lane decode state; rows whose initial ids do not start with the same id
+ * (one [sot] pass serves all rows); a probe without the log-prob outputs; what _rows / _lp / _lp_ns refuse.
+ * wm_transcribe_wait_lang on a slot submitted without detection returns WM_E_STATE; the older waits on a _lang slot return what
+ * they always return.  There is no token-timestamp form. */
+int wm_detect_language(wm_model* m, const float* mel, int mel_on_device, int B, int sot_token, const int32_t* lang_ids, int n_lang,
+                       int32_t* lang_out, float* probs_out);
+int wm_transcribe_lang(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* opts, const int32_t* prompts,
+                       const int32_t* prompt_len, int prompt_stride, int no_speech_token, int n_init, const int32_t* lang_ids, int n_lang,
+                       int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob, float* no_speech_prob,
+                       int32_t* lang_out, float* lang_probs);
+int wm_transcribe_submit_lang(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* opts,
+                              const int32_t* prompts, const int32_t* prompt_len, int prompt_stride, int no_speech_token, int n_init,
+                              const int32_t* lang_ids, int n_lang, int want_logprobs);
+int wm_transcribe_wait_lang(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob,
+                            float* no_speech_prob, int32_t* lang_out, float* lang_probs);
+
 /* ---- token-level timestamps ---------------------------------------------------------------------------------
  * When each id was spoken, with the semantics of HF generate(..., return_token_timestamps=True)
  * (WhisperGenerationMixin._extract_token_timestamps, time_precision 0.02, median_filter_width 7, num_input_ids = n_prompt): the
@@ -323,6 +357,16 @@ int wm_transcribe_long_ex(wm_model* m, const float* mel, int mel_on_device, int 
                           const wm_long_opts* lopts, wm_long_result** out);
 int wm_transcribe_long_pcm_ex(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* opts,
                               const wm_long_opts* lopts, wm_long_result** out);
+/* Long-form with language detection: the arguments of the _ex pair plus the language list and lang_out [B].  HF detects
+ * once per recording, on its first window: before the scheduler loop every recording's window at seek 0 is gathered, in groups of at
+ * most the pass's rows, and run through wm_detect_language's device path (one extra encoder run over the first windows, as in HF);
+ * the ids are read back once per group.  From then on recording b's initial ids are opts->prompt with the second id replaced by
+ * lang_out[b], and every pass is a per-row-prompt pass.  Thresholds, prompt_ids and condition_on_prev_tokens work unchanged on top.
+ * WM_E_ARG, nothing launched: what the _ex pair and wm_detect_language refuse; opts->n_prompt < 2; multi-lane decode states. */
+int wm_transcribe_long_lang(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames, const wm_decode_opts* opts,
+                            const wm_long_opts* lopts, const int32_t* lang_ids, int n_lang, int32_t* lang_out, wm_long_result** out);
+int wm_transcribe_long_pcm_lang(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* opts,
+                                const wm_long_opts* lopts, const int32_t* lang_ids, int n_lang, int32_t* lang_out, wm_long_result** out);
 /* Host-only, the counterpart of wm_op_long_segments: the decoder prompt of ONE utterance's next window.  seq / segs: the utterance's
  * segments so far (first, count into seq; n_segs may be 0); init: opts->prompt.  out: room for n_text_ctx ids. */
 int wm_op_long_prompt(const int32_t* seq, const wm_segment* segs, int n_segs, const int32_t* init, int n_init, const wm_long_opts* lopts,
@@ -417,6 +461,11 @@ int wm_op_logits_lp(float* logits, int32_t* ids, float* logprob, const float* x,
  * over all N columns, lse[b] the row's logsumexp.  prob, lse: [B]. */
 int wm_op_no_speech(float* prob, float* lse, const float* x, const float* ln_g, const float* ln_b, const float* emb, int B, int N, int K,
                     int dtype, int token);
+/* lang_detect_kernel alone: lang_out[b] = the id among lang_ids with the largest LN(x[b])·emb[id] (ties: the smaller id),
+ * probs[b][i] = the softmax over the n_lang candidates at list position i.  emb [N][K] is rounded to dtype on upload.
+ * 1 <= n_lang <= 128, ids distinct and inside [0, N), K 128, 384 or 512.  probs may be NULL. */
+int wm_op_lang_detect(int32_t* lang_out, float* probs, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                      const int32_t* lang_ids, int n_lang, int B, int N, int K, int dtype);
 /* The absorbed cross-attention of bf16-encoder / fp32-K/V models: per row r and head h, with X = x[utt(r)] and
  * utt(r) = r % q_B when q_B > 0 (prefill rows, position-major; rows = P·q_B) else r,
  *   out[r, h] = Σ_j softmax_j(0.125·q_h[r]·(Wk_h X_j)) (Wv_h X_j) + bv_h,

@@ -210,6 +210,61 @@ public:
         for (int b = 0; b < B; ++b) token_logprobs[b].assign(lp.begin() + (size_t)b * stride, lp.begin() + (size_t)b * stride + n[b]);
         return unpack(toks, n, B, stride);
     }
+    // openai-whisper's detect_language: per utterance the id of lang_ids with the largest logit after a decoder pass over
+    // [sot] alone; probs (optional): [B][lang_ids.size()] softmax over the list, in list order
+    std::vector<int32_t> detect_language(const float* mels, int B, const std::vector<int32_t>& lang_ids, int32_t sot,
+                                         std::vector<float>* probs = nullptr) const {
+        need_model();
+        std::vector<int32_t> out(B);
+        if (probs) probs->assign((size_t)B * lang_ids.size(), 0.f);
+        check(wm_detect_language(model_, mels, 0, B, sot, lang_ids.data(), (int)lang_ids.size(), out.data(), probs ? probs->data() : nullptr));
+        return out;
+    }
+    // transcribe_batch with the language detected on the device inside the same pass (HF generate's language = None): the
+    // second of every row's n_init initial ids is overwritten with the row's detected id (returned in res.lang and in the id lists).
+    // prompts: one decoder prompt per utterance (empty = the model's shared prompt; n_init <= 0: its length).  want_logprobs and
+    // no_speech_token >= 0 (needs want_logprobs) add §17's and §18's values.
+    struct LangResult {
+        std::vector<std::vector<int>> ids;
+        std::vector<int32_t> lang;                       // [B]
+        std::vector<float> lang_probs;                   // [B][n_lang], list order
+        std::vector<std::vector<float>> token_logprobs;  // want_logprobs
+        std::vector<float> avg_logprob, no_speech_prob;
+    };
+    LangResult transcribe_batch_lang(const float* mels, int B, const std::vector<int32_t>& lang_ids, int max_loop = MAX_LOOP,
+                                     const std::vector<std::vector<int32_t>>& prompts = {}, int n_init = 0, bool want_logprobs = false,
+                                     int32_t no_speech_token = -1) const {
+        need_model();
+        wm_decode_opts o = opts(max_loop, false);
+        std::vector<int32_t> tab, len;
+        const int lmax = prompt_table(prompts, B, tab, len);
+        const bool rows = !prompts.empty();
+        const int stride = (rows ? lmax : o.n_prompt) + 1 + max_loop;
+        LangSlot q{B, stride, (int)lang_ids.size(), want_logprobs, no_speech_token >= 0};
+        return lang_collect(q, [&](int32_t* t, int32_t* n, float* lp, float* avg, float* nsp, int32_t* lo, float* pr) {
+            return wm_transcribe_lang(model_, mels, 0, B, &o, rows ? tab.data() : nullptr, rows ? len.data() : nullptr, lmax, no_speech_token,
+                                      n_init > 0 ? n_init : o.n_prompt, lang_ids.data(), (int)lang_ids.size(), t, n, lp, avg, nsp, lo, pr);
+        });
+    }
+    // pipelined form of transcribe_batch_lang: submit on slot 0..7, collect with transcribe_wait_lang
+    void transcribe_submit_lang(const float* mels, int B, int slot, const std::vector<int32_t>& lang_ids, int max_loop = MAX_LOOP,
+                                const std::vector<std::vector<int32_t>>& prompts = {}, int n_init = 0, bool want_logprobs = false,
+                                int32_t no_speech_token = -1) {
+        need_model();
+        wm_decode_opts o = opts(max_loop, false);
+        std::vector<int32_t> tab, len;
+        const int lmax = prompt_table(prompts, B, tab, len);
+        const bool rows = !prompts.empty();
+        check(wm_transcribe_submit_lang(model_, slot, mels, 0, B, &o, rows ? tab.data() : nullptr, rows ? len.data() : nullptr, lmax, no_speech_token,
+                                        n_init > 0 ? n_init : o.n_prompt, lang_ids.data(), (int)lang_ids.size(), want_logprobs ? 1 : 0));
+        lang_pend_[slot] = LangSlot{B, (rows ? lmax : o.n_prompt) + 1 + max_loop, (int)lang_ids.size(), want_logprobs, no_speech_token >= 0};
+    }
+    LangResult transcribe_wait_lang(int slot) {
+        need_model();
+        return lang_collect(lang_pend_[slot], [&](int32_t* t, int32_t* n, float* lp, float* avg, float* nsp, int32_t* lo, float* pr) {
+            return wm_transcribe_wait_lang(model_, slot, t, n, lp, avg, nsp, lo, pr);
+        });
+    }
     // sequential long-form transcription (HF generate's long-form path; needs set_timestamps): host mels
     // [B][n_mels][T], n_frames per utterance (empty = T) -> per utterance the sequence and its segments
     struct LongSegment {
@@ -240,7 +295,8 @@ public:
     // the same names; the defaults are wm_transcribe_long
     std::vector<LongResult> transcribe_long(const float* mels, int B, int T, const std::vector<int32_t>& n_frames = {}, int max_loop = MAX_LOOP,
                                             bool condition_on_prev_tokens = false, const std::vector<int32_t>& prompt_ids = {},
-                                            bool all_segments = false, int32_t prev_sot_token = 50361, const LongThresholds* thresholds = nullptr) const {
+                                            bool all_segments = false, int32_t prev_sot_token = 50361, const LongThresholds* thresholds = nullptr,
+                                            const std::vector<int32_t>& lang_ids = {}, std::vector<int32_t>* lang_out = nullptr) const {
         need_model();
         wm_decode_opts o = opts(max_loop, false);
         wm_long_result* r = nullptr;
@@ -250,7 +306,14 @@ public:
                               (int)prompt_ids.size(), all_segments ? 1 : 0, th.use_logprob_threshold ? 1 : 0, th.logprob_threshold,
                               th.use_no_speech_threshold ? 1 : 0, th.no_speech_threshold, th.no_speech_token};
         const bool quality = th.use_logprob_threshold || th.use_no_speech_threshold;
-        check(wm_transcribe_long_ex(model_, mels, 0, B, T, n_frames.empty() ? nullptr : n_frames.data(), &o, &lo, &r));
+        if (!lang_ids.empty()) {  // HF generate's language = None: each recording's language, detected on its first window
+            std::vector<int32_t> lang(B);
+            check(wm_transcribe_long_lang(model_, mels, 0, B, T, n_frames.empty() ? nullptr : n_frames.data(), &o, &lo, lang_ids.data(),
+                                          (int)lang_ids.size(), lang.data(), &r));
+            if (lang_out) *lang_out = lang;
+        } else {
+            check(wm_transcribe_long_ex(model_, mels, 0, B, T, n_frames.empty() ? nullptr : n_frames.data(), &o, &lo, &r));
+        }
         std::vector<LongResult> out(B);
         int rc = 0;
         for (int b = 0; b < B && !rc; ++b) {
@@ -319,6 +382,40 @@ private:
         for (int b = 0; b < B; ++b) out[b].assign(toks.begin() + (size_t)b * stride, toks.begin() + (size_t)b * stride + n[b]);
         return out;
     }
+    // [B][lmax] table and lengths of per-utterance prompts -> lmax (0 without prompts)
+    static int prompt_table(const std::vector<std::vector<int32_t>>& prompts, int B, std::vector<int32_t>& tab, std::vector<int32_t>& len) {
+        int lmax = 0;
+        for (const auto& r : prompts) lmax = std::max(lmax, (int)r.size());
+        tab.assign((size_t)B * std::max(lmax, 1), 0);
+        len.assign(B, 0);
+        for (size_t b = 0; b < prompts.size() && b < (size_t)B; ++b) {
+            len[b] = (int32_t)prompts[b].size();
+            std::copy(prompts[b].begin(), prompts[b].end(), tab.begin() + b * lmax);
+        }
+        return lmax;
+    }
+    struct LangSlot {
+        int B = 0, stride = 0, n_lang = 0;
+        bool lp = false, ns = false;
+    };
+    template <typename Call> static LangResult lang_collect(const LangSlot& q, Call call) {
+        LangResult r;
+        std::vector<int32_t> toks((size_t)q.B * q.stride), n(q.B);
+        std::vector<float> lp(q.lp ? (size_t)q.B * q.stride : 0);
+        r.lang.assign(q.B, 0);
+        r.lang_probs.assign((size_t)q.B * q.n_lang, 0.f);
+        if (q.lp) r.avg_logprob.assign(q.B, 0.f);
+        if (q.ns) r.no_speech_prob.assign(q.B, 0.f);
+        check(call(toks.data(), n.data(), q.lp ? lp.data() : nullptr, q.lp ? r.avg_logprob.data() : nullptr,
+                   q.ns ? r.no_speech_prob.data() : nullptr, r.lang.data(), r.lang_probs.data()));
+        r.ids = unpack(toks, n, q.B, q.stride);
+        if (q.lp) {
+            r.token_logprobs.assign(q.B, {});
+            for (int b = 0; b < q.B; ++b) r.token_logprobs[b].assign(lp.begin() + (size_t)b * q.stride, lp.begin() + (size_t)b * q.stride + n[b]);
+        }
+        return r;
+    }
+    LangSlot lang_pend_[8] = {};
     WhisperConfig cfg_;
     std::vector<int32_t> prompt_{PROMPT, PROMPT + 4};
     int32_t eot_ = EOT;

@@ -28,6 +28,8 @@ SYMBOLS = [
     "wm_transcribe_lp", "wm_transcribe_submit_lp", "wm_transcribe_wait_lp", "wm_op_logits_lp",
     "wm_transcribe_lp_ns", "wm_transcribe_submit_lp_ns", "wm_transcribe_wait_lp_ns", "wm_op_no_speech",
     "wm_long_result_quality", "wm_long_result_windows", "wm_long_result_skip_stats",
+    "wm_detect_language", "wm_transcribe_lang", "wm_transcribe_submit_lang", "wm_transcribe_wait_lang", "wm_op_lang_detect",
+    "wm_transcribe_long_lang", "wm_transcribe_long_pcm_lang",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -100,6 +102,22 @@ def no_speech_args(no_speech_token, n_init, prompt_lens, vocab):
     if n_init < 1 or n_init > shortest:
         raise ValueError(f"n_init {n_init} outside [1, shortest prompt = {shortest}]")
     return token, n_init
+
+
+LANG_DETECT_MAX = 128  # csrc/wm_kernels.h LANG_DETECT_MAX
+
+
+def lang_args(lang_ids, vocab):
+    """Checks a language list on the host (the library refuses the same with WM_E_ARG) -> contiguous int32 array."""
+    import numpy as np
+    ids = np.ascontiguousarray(np.asarray(lang_ids, np.int64).reshape(-1))
+    if ids.size < 1 or ids.size > LANG_DETECT_MAX:
+        raise ValueError(f"the language list needs 1..{LANG_DETECT_MAX} ids, got {ids.size}")
+    if ids.min() < 0 or ids.max() >= vocab:
+        raise ValueError(f"language ids must be vocabulary ids [0, {vocab})")
+    if np.unique(ids).size != ids.size:
+        raise ValueError("a language id is listed twice")
+    return ids.astype(np.int32)
 
 
 class WhisperMiError(RuntimeError):
@@ -189,6 +207,17 @@ def lib():
     L.wm_transcribe_submit_lp_ns.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip, C.c_int, C.c_int, C.c_int]
     L.wm_transcribe_wait_lp_ns.argtypes = [vp, C.c_int, ip, ip, fp, fp, fp]
     L.wm_op_no_speech.argtypes = [fp] * 6 + [C.c_int] * 5
+    L.wm_detect_language.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, fp]
+    L.wm_transcribe_lang.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip, C.c_int, C.c_int, C.c_int, ip, C.c_int,
+                                     ip, ip, fp, fp, fp, ip, fp]
+    L.wm_transcribe_submit_lang.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), ip, ip, C.c_int, C.c_int, C.c_int,
+                                            ip, C.c_int, C.c_int]
+    L.wm_transcribe_wait_lang.argtypes = [vp, C.c_int, ip, ip, fp, fp, fp, ip, fp]
+    L.wm_transcribe_long_lang.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, C.POINTER(WmDecodeOpts), C.POINTER(WmLongOpts), ip, C.c_int, ip,
+                                          C.POINTER(vp)]
+    L.wm_transcribe_long_pcm_lang.argtypes = [vp, fp, ip, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), C.POINTER(WmLongOpts), ip, C.c_int, ip,
+                                              C.POINTER(vp)]
+    L.wm_op_lang_detect.argtypes = [ip, fp, fp, fp, fp, fp, ip] + [C.c_int] * 5
     L.wm_long_result_quality.argtypes = [vp, C.c_int, fp, fp]
     L.wm_long_result_windows.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_int64), fp, fp, ip]
     L.wm_long_result_skip_stats.argtypes = [vp, ip]

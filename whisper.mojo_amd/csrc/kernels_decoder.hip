@@ -2300,6 +2300,90 @@ template void launch_no_speech_finish<bf16>(const NoSpeechParams&, hipStream_t);
 template void launch_no_speech_finish<f16>(const NoSpeechParams&, hipStream_t);
 
 // ------------------------------------------------------------------------------------------------------------
+// Language detection: HF WhisperGenerationMixin.detect_language — the logits of a decoder pass over
+// [<|startoftranscript|>] alone, everything outside the language ids at -inf, arg-max; openai-whisper also returns the softmax over
+// the languages.  Only the n_lang candidate columns are formed (n_lang·K embedding elements, not the vocabulary's N·K).
+// One workgroup per row.  The LayerNorm is the one of no_speech_finish_kernel (every wave forms the same one-pass statistics, eps
+// 1e-5); the normalised row, rounded to the operand dtype TW, is parked in LDS.  Wave w takes candidates w, w + 4, …: lanes split K,
+// fp32 products, butterfly add, logit to LDS.  Wave 0 takes the arg-max (ties: the smaller TOKEN ID, what an arg-max over the
+// vocabulary row returns, whatever the list's order).  Softmax in fp32: the maximum is subtracted first (every exponent <= 0, an
+// offset of the whole row costs nothing) and thread 0 adds the terms in list order, so a row's values do not depend on its batch.
+template <typename TW>
+__global__ __launch_bounds__(256) void lang_detect_kernel(LangDetectParams p) {
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    __shared__ float s_a[LANG_DETECT_MAX_K];
+    __shared__ float s_logit[LANG_DETECT_MAX];
+    __shared__ float s_term[LANG_DETECT_MAX];
+    __shared__ float s_max, s_sum;
+    const float* xr = p.x + (size_t)b * p.ldx;
+    float sm = 0.f, sq = 0.f;
+    for (int k = lane; k < p.K; k += 64) {
+        const float v = xr[k];
+        sm += v;
+        sq += v * v;
+    }
+    sm = wave_sum(sm);
+    sq = wave_sum(sq);
+    const float mean = sm / (float)p.K;
+    const float var = (sq / (float)p.K) - (mean * mean);
+    const float rstd = 1.0f / sqrtf(var + 1e-5f);
+    for (int k = tid; k < p.K; k += 256) s_a[k] = (float)from_f32<TW>((xr[k] - mean) * rstd * p.ln_g[k] + p.ln_b[k]);
+    __syncthreads();
+    for (int c = w; c < p.n_lang; c += 4) {
+        const TW* er = (const TW*)p.emb + (size_t)p.lang_ids[c] * p.K;
+        float acc = 0.f;
+        for (int k = lane; k < p.K; k += 64) acc += s_a[k] * (float)er[k];
+        acc = wave_sum(acc);
+        if (lane == 0) s_logit[c] = acc;
+    }
+    __syncthreads();
+    if (w == 0) {
+        // (starts at a list member: with NaN logits no comparison holds, and the id written to the prompt table must still be a
+        //  vocabulary id)
+        float bv = -INFINITY;
+        int bi = p.lang_ids[0];
+        for (int c = lane; c < p.n_lang; c += 64) {
+            const float v = s_logit[c];
+            const int id = p.lang_ids[c];
+            if (v > bv || (v == bv && id < bi)) {
+                bv = v;
+                bi = id;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float v2 = __shfl_xor(bv, o, 64);
+            const int i2 = __shfl_xor(bi, o, 64);
+            if (v2 > bv || (v2 == bv && i2 < bi)) {
+                bv = v2;
+                bi = i2;
+            }
+        }
+        if (lane == 0) {
+            s_max = bv;
+            p.lang_out[b] = bi;
+            if (p.patch) p.patch[(size_t)b * p.patch_stride + p.patch_col[b]] = bi;
+        }
+    }
+    __syncthreads();
+    if (tid < p.n_lang) s_term[tid] = expf(s_logit[tid] - s_max);
+    __syncthreads();
+    if (tid == 0) {
+        float S = 0.f;
+        for (int c = 0; c < p.n_lang; ++c) S += s_term[c];  // finite logits: S >= 1, the winner's term is exp(0) (NaN logits give NaN probabilities)
+        s_sum = S;
+    }
+    __syncthreads();
+    if (p.probs && tid < p.n_lang) p.probs[(size_t)b * p.n_lang + tid] = s_term[tid] / s_sum;
+}
+template <typename TW> void launch_lang_detect(const LangDetectParams& p, hipStream_t st) {
+    hipLaunchKernelGGL(lang_detect_kernel<TW>, dim3(p.B), dim3(256), 0, st, p);
+}
+template void launch_lang_detect<float>(const LangDetectParams&, hipStream_t);
+template void launch_lang_detect<bf16>(const LangDetectParams&, hipStream_t);
+template void launch_lang_detect<f16>(const LangDetectParams&, hipStream_t);
+
+// ------------------------------------------------------------------------------------------------------------
 // op-level helpers (known-answer tests of the C-ABI)
 __global__ void gelu_kernel(float* t, size_t n, int mode) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

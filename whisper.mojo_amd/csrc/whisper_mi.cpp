@@ -242,6 +242,7 @@ struct wm_model {
         bool tt = false;
         bool lp = false;  // the pass computes log-probabilities (wm_transcribe_wait_lp may collect them)
         bool ns = false;  // the pass carries the no-speech probe (wm_transcribe_wait_lp_ns may collect it)
+        bool lang = false;  // the pass detects the language (wm_transcribe_wait_lang may collect it)
     } slot_ref[8];
     wm_state* pairs[4] = {};  // 2·B-row states of coalesced pairs
     int last_steps[8] = {-1, -1, -1, -1, -1, -1, -1, -1};  // loop iterations enqueued for each slot's last collected pass
@@ -373,6 +374,16 @@ struct wm_state {
         int token = -1, n_init = 0;
         DevBuf x, pmax, pidx, psum, prob, lse;
     } ns;
+    // language detection of the pending pass (on = wm_transcribe_lang and its kin, always with rw.on; wm_detect_language
+    // uses the buffers without a pass): the residual rows of the [<|startoftranscript|>] pass [B][d] (NOT ns.x: the probe's row of the
+    // same pass comes from the real prefill, behind any previous text), the candidate ids, each row's language slot in the prompt
+    // table and the results.  Part of the arena; runs outside the captured step graph.
+    struct Lang {
+        bool on = false;
+        int n = 0, n_init = 0, sot = -1;
+        DevBuf x, ids, col, out, probs;  // [B][d] fp32, [LANG_DETECT_MAX], [B], [B], [B][LANG_DETECT_MAX] (used as [B][n])
+        std::vector<int32_t> h_ids, h_col;
+    } lg;
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -854,7 +865,8 @@ extern "C" void wm_state_free(wm_state* s) {
                     &s->tok, &s->pos, &s->tok_rows, &s->pos_rows, &s->ctl, &s->out_tokens, &s->n_tokens, &s->finished,
                     &s->al.cap, &s->al.kh, &s->al.probs, &s->al.mean, &s->al.stdv, &s->al.M, &s->al.trace, &s->al.times, &s->al.ncols,
                     &s->rw.table, &s->rw.len, &s->rw.key_lo, &s->lp.part_s, &s->lp.table, &s->lp.sum,
-                    &s->ns.x, &s->ns.pmax, &s->ns.pidx, &s->ns.psum, &s->ns.prob, &s->ns.lse};
+                    &s->ns.x, &s->ns.pmax, &s->ns.pidx, &s->ns.psum, &s->ns.prob, &s->ns.lse,
+                    &s->lg.x, &s->lg.ids, &s->lg.col, &s->lg.out, &s->lg.probs};
     for (DevBuf* b : bs) b->release();
     delete s;
 }
@@ -974,6 +986,11 @@ static int state_new(wm_model* m, int B, wm_state** out, bool pair) {
     A(s->ns.psum, (size_t)B * s->npart * 4, true);
     A(s->ns.prob, (size_t)B * 4, true);
     A(s->ns.lse, (size_t)B * 4, true);
+    A(s->lg.x, (size_t)B * d * 4, true);
+    A(s->lg.ids, (size_t)LANG_DETECT_MAX * 4, true);
+    A(s->lg.col, (size_t)B * 4, true);
+    A(s->lg.out, (size_t)B * 4, true);
+    A(s->lg.probs, (size_t)B * LANG_DETECT_MAX * 4, true);
     if (rc) {
         std::string keep = g_err;
         wm_state_free(s);
@@ -1365,7 +1382,8 @@ static int launch_cross_attn(wm_model* m, wm_state* s, int l, const DecView& v, 
 // position.  Every row's arithmetic is what the single-position pass does for it, so the ids are the same bit for bit.
 static int decode_core(wm_model* m, wm_state* s, const DecView& v, bool want_logits, bool full_logits = false,
                        const float* mask = nullptr, int P = 1, bool embed = true, const TsRules* rules = nullptr, bool capture = false,
-                       int t0 = -1) {  // t0 >= 0: a chunk of a per-row prefill — tokens / positions are rows [t0, t0 + P) of tok_rows / pos_rows
+                       int t0 = -1,  // t0 >= 0: a chunk of a per-row prefill — tokens / positions are rows [t0, t0 + P) of tok_rows / pos_rows
+                       bool key_window = true) {  // false: no per-row key windows even on a per-row pass (the language pass, §19)
     const wm_dims& c = m->cfg.dims;
     const int T = dec_dtype(m->cfg), KV = m->cfg.kv_dtype;  // T: the decoder's operand dtype
     const int B = v.nb * P;          // activation rows of this pass
@@ -1428,7 +1446,7 @@ static int decode_core(wm_model* m, wm_state* s, const DecView& v, bool want_log
             a.d = c.d_model;
             a.B = B;
             // per-row prompts: every utterance sweeps its own key window [key_lo, len + 1 (+ t))
-            WMCHK(attn_decode_dispatch(KV, a, st, s->rw.on ? s->rw.key_lo.as<int>() + v.b0 : nullptr));
+            WMCHK(attn_decode_dispatch(KV, a, st, s->rw.on && key_window ? s->rw.key_lo.as<int>() + v.b0 : nullptr));
         }
         // the attention outputs and the MLP hidden rows are handed over in operand dtype T (what the next MFMA consumes)
         auto proj_residual = [&](const float* in, int K, const DevBuf& W, const DevBuf& bias) -> int {  // x += in·Wᵀ + b
@@ -1806,6 +1824,38 @@ static int ns_probe(wm_model* m, wm_state* s, const DecView& v) {
                     s->ns.lse.as<float>() + v.b0, v.st);
 }
 
+// Language detection, after the encoder on a single-lane state: one decoder pass over [sot] at position 0 for all rows
+// (cache length 0, every row attends only to itself, no key window, no logits; its K/V rows in cache slot 0 are overwritten by the
+// prefill that follows), its residual rows kept in lg.x, then lang_detect_kernel.  patch: the device prompt table whose language
+// slots (lg.col) receive the ids, or null.  All on the lane's stream; nothing is read back.
+static int lang_pass(wm_model* m, wm_state* s, const DecView& v, int* patch, int patch_stride) {
+    const wm_dims& c = m->cfg.dims;
+    const int T = dec_dtype(m->cfg);
+    wm_state::Lang& lg = s->lg;
+    HIPCHK(hipMemcpyAsync(lg.ids.p, lg.h_ids.data(), (size_t)lg.n * 4, hipMemcpyHostToDevice, v.st));
+    if (patch) HIPCHK(hipMemcpyAsync(lg.col.as<int>() + v.b0, lg.h_col.data() + v.b0, (size_t)v.nb * 4, hipMemcpyHostToDevice, v.st));
+    launch_set_step(v.ctl, 0, 1, s->pos.as<int>() + v.b0, 0, s->tok.as<int>() + v.b0, lg.sot, v.nb, v.st);
+    WMCHK(decode_core(m, s, v, false, false, nullptr, 1, true, nullptr, false, -1, false));
+    launch_no_speech_capture(s->dx.as<float>() + (size_t)v.b0 * c.d_model, lg.x.as<float>() + (size_t)v.b0 * c.d_model, v.nb, c.d_model, v.st);
+    LangDetectParams q{};
+    q.x = lg.x.as<float>() + (size_t)v.b0 * c.d_model;
+    q.ldx = c.d_model;
+    q.ln_g = m->dec_ln_g.as<float>();
+    q.ln_b = m->dec_ln_b.as<float>();
+    q.emb = T == WM_F32 ? m->tok_emb_f.p : m->tok_emb_t.p;
+    q.lang_ids = lg.ids.as<int>();
+    q.n_lang = lg.n;
+    q.K = c.d_model;
+    q.B = v.nb;
+    q.lang_out = lg.out.as<int>() + v.b0;
+    q.probs = lg.probs.as<float>() + (size_t)v.b0 * lg.n;
+    q.patch = patch ? patch + (size_t)v.b0 * patch_stride : nullptr;
+    q.patch_stride = patch_stride;
+    q.patch_col = lg.col.as<int>() + v.b0;
+    DISPATCH_DT(T, TT, launch_lang_detect<TT>(q, v.st));
+    return 0;
+}
+
 // Per-row prompts, the start of a pass on a single-lane state: prompt table and lengths to the device, tokens /
 // key windows / prefill rows from them, the prefill in chunks of PREFILL_MAX positions through the position-major pass (the rows
 // end together at position Lmax; logits for the last chunk only: every row's last position is real), the first id, and the per-row
@@ -1815,6 +1865,7 @@ static int prefill_rows(wm_model* m, wm_state* s, const DecView& v, InitTokensPa
     const int Lmax = rw.Lmax;
     HIPCHK(hipMemcpyAsync(rw.table.p, rw.h_table.data(), rw.h_table.size() * 4, hipMemcpyHostToDevice, v.st));
     HIPCHK(hipMemcpyAsync(rw.len.p, rw.h_len.data(), rw.h_len.size() * 4, hipMemcpyHostToDevice, v.st));
+    if (s->lg.on) WMCHK(lang_pass(m, s, v, rw.table.as<int>(), rw.stride));  // the table's language slots come from the device (§19)
     ip.tok_rows = s->tok_rows.as<int>();
     ip.pos_rows = s->pos_rows.as<int>();
     launch_init_tokens_rows(ip, RowPromptParams{rw.table.as<int>(), rw.len.as<int>(), rw.stride, Lmax, rw.key_lo.as<int>()}, v.st);
@@ -2019,6 +2070,11 @@ static int align_setup(wm_model* m, wm_state* s, const wm_decode_opts* o, const 
 struct NsAsk {  // the no-speech probe a pass carries; token < 0: none
     int token = -1, n_init = 0;
 };
+struct LangAsk {  // language detection a pass carries; ids == null: none.  only: no transcription (wm_detect_language)
+    const int32_t* ids = nullptr;  // host [n]
+    int n = 0, n_init = 0, sot = -1;
+    bool only = false;
+};
 struct RowPrompts {
     const int32_t* ids;  // host [B][stride]
     const int32_t* len;  // host [B]
@@ -2047,8 +2103,10 @@ static int rows_setup(wm_model* m, wm_state* s, const RowPrompts* rows) {
 }
 static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, bool allow_poll,
                      const float* mel2 = nullptr, int mel2_on_device = 0, const std::vector<int32_t>* cols = nullptr,
-                     const RowPrompts* rows = nullptr, bool lp = false, NsAsk ns = NsAsk()) {
+                     const RowPrompts* rows = nullptr, bool lp = false, NsAsk ns = NsAsk(), LangAsk lang = LangAsk()) {
     const wm_dims& c = m->cfg.dims;
+    if (lang.ids && (mel2 || cols || dec_lanes_for(B) != 1 || (!lang.only && !rows)))  // (refused by the entry points first)
+        return fail(WM_E_ARG, "language detection needs a single-lane decode state and a per-row-prompt pass without token timestamps");
     if (ns.token >= 0 && (!lp || ns.token >= c.vocab || ns.n_init < 1 || ns.n_init > o->n_prompt))  // (refused by the entry points first)
         return fail(WM_E_ARG, "the no-speech probe needs a log-prob pass, a vocabulary id and 1 <= n_init <= prompt length");
     if (lp && (cols || dec_lanes_for(B) != 1))  // (the entry points refuse both before anything is touched; kept for internal callers)
@@ -2068,6 +2126,15 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
     s->ns.on = ns.token >= 0;
     s->ns.token = ns.token;
     s->ns.n_init = ns.n_init;
+    s->lg.on = lang.ids != nullptr && !lang.only;
+    if (lang.ids) {
+        s->lg.n = lang.n;
+        s->lg.n_init = lang.n_init;
+        s->lg.sot = lang.sot;
+        s->lg.h_ids.assign(lang.ids, lang.ids + lang.n);
+        s->lg.h_col.resize(B);
+        for (int b = 0; b < B; ++b) s->lg.h_col[b] = rows ? rows->len[b] - lang.n_init + 1 : 0;
+    }
     s->lp.on = lp;
     if (lp) {
         if (rows)
@@ -2115,6 +2182,15 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
         fprintf(stderr, "[wm] encoder: enqueue %.3f ms, done after %.3f ms\n", std::chrono::duration<double>(tt1 - tt0).count() * 1e3,
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - tt0).count() * 1e3);
     }
+    if (lang.only) {  // wm_detect_language: the [sot] pass and the kernel behind the encoder, no transcription
+        const wm_state::Lane& ln = s->lanes[0];
+        HIPCHK(hipEventRecord(s->enc_done, est));
+        HIPCHK(hipStreamWaitEvent(ln.st, s->enc_done, 0));
+        WMCHK(lang_pass(m, s, DecView{ln.b0, ln.nb, ln.st, ln.ctl}, nullptr, 0));
+        HIPCHK(hipGetLastError());
+        s->has_enc = false;  // cache slot 0 holds the [sot] pass: a new wm_encode is needed before wm_decode_step
+        return 0;
+    }
     WMCHK(align_setup(m, s, o, cols));
     WMCHK(transcribe_decode(m, s, o, allow_poll));
     s->pending = true;
@@ -2129,7 +2205,7 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
 // until every slot that shares the state (one, or the two of a coalesced pair) has collected its rows.
 static int wait_on(wm_model* m, wm_state* s, int32_t* tokens_out, int32_t* n_tokens, int row0 = 0, int rows = -1, int32_t* dev_packed = nullptr,
                    int rows_cap = 0, int pack_stride = 0, float* token_times = nullptr, float* token_logprobs = nullptr, float* avg_logprob = nullptr,
-                   float* no_speech_prob = nullptr) {
+                   float* no_speech_prob = nullptr, int32_t* lang_out = nullptr, float* lang_probs = nullptr) {
     if (!s || !s->pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
     HIPCHK(hipSetDevice(m->device));
     if (rows < 0) rows = s->B;
@@ -2169,6 +2245,9 @@ static int wait_on(wm_model* m, wm_state* s, int32_t* tokens_out, int32_t* n_tok
             }
         }
         if (no_speech_prob) HIPCHK(hipMemcpy(no_speech_prob, s->ns.prob.as<float>() + row0, (size_t)rows * 4, hipMemcpyDeviceToHost));
+        if (lang_out) HIPCHK(hipMemcpy(lang_out, s->lg.out.as<int>() + row0, (size_t)rows * 4, hipMemcpyDeviceToHost));
+        if (lang_probs)
+            HIPCHK(hipMemcpy(lang_probs, s->lg.probs.as<float>() + (size_t)row0 * s->lg.n, (size_t)rows * s->lg.n * 4, hipMemcpyDeviceToHost));
     }
     if (--s->halves_left <= 0) {
         s->pending = false;
@@ -2389,9 +2468,10 @@ extern "C" int wm_transcribe_submit_rows(wm_model* m, int slot, const float* mel
     return 0;
 }
 static int wait_impl(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_times, float* token_logprobs = nullptr,
-                     float* avg_logprob = nullptr, float* no_speech_prob = nullptr) {
+                     float* avg_logprob = nullptr, float* no_speech_prob = nullptr, int32_t* lang_out = nullptr, float* lang_probs = nullptr) {
     wm_model::SlotRef& r = m->slot_ref[slot];
     if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
+    if (lang_out && !r.lang) return fail(WM_E_STATE, "this slot's pass was submitted without language detection (wm_transcribe_submit_lang)");
     if (no_speech_prob && !r.ns) return fail(WM_E_STATE, "this slot's pass was submitted without the no-speech probe (wm_transcribe_submit_lp_ns)");
     if (token_logprobs && !r.lp) return fail(WM_E_STATE, "this slot's pass was submitted without log-probabilities (wm_transcribe_submit_lp)");
     if (token_times && !r.tt) return fail(WM_E_STATE, "this slot's pass was submitted without token timestamps (wm_transcribe_submit_tt)");
@@ -2400,7 +2480,8 @@ static int wait_impl(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_toke
         if (rc) return rc;
     }
     wm_state* s = r.st;
-    const int rc = wait_on(m, s, tokens_out, n_tokens, r.row0, r.rows, nullptr, 0, 0, token_times, token_logprobs, avg_logprob, no_speech_prob);
+    const int rc = wait_on(m, s, tokens_out, n_tokens, r.row0, r.rows, nullptr, 0, 0, token_times, token_logprobs, avg_logprob, no_speech_prob,
+                           lang_out, lang_probs);
     if (!rc) {
         m->last_steps[slot] = s->last_steps;
         m->align_ref[slot] = r.tt ? wm_model::AlignRef{s, r.row0, r.rows, s->al.gen} : wm_model::AlignRef{};
@@ -2513,6 +2594,121 @@ extern "C" int wm_transcribe_wait_lp_ns(wm_model* m, int slot, int32_t* tokens_o
     if (!m || !tokens_out || !n_tokens || !token_logprobs || !avg_logprob || !no_speech_prob || slot < 0 || slot >= wm_model::NSLOT)
         return fail(WM_E_ARG, "bad argument");
     return wait_impl(m, slot, tokens_out, n_tokens, nullptr, token_logprobs, avg_logprob, no_speech_prob);
+}
+// ---- language detection ----------------------------------------------------------------------------------------------
+// Everything is refused before anything is launched.
+static int lang_list_check(int vocab, const int32_t* lang_ids, int n_lang) {
+    if (n_lang < 1 || n_lang > LANG_DETECT_MAX) return fail(WM_E_ARG, "n_lang = %d outside [1, %d]", n_lang, LANG_DETECT_MAX);
+    if (!lang_ids) return fail(WM_E_ARG, "bad argument");
+    for (int i = 0; i < n_lang; ++i) {
+        if (lang_ids[i] < 0 || lang_ids[i] >= vocab) return fail(WM_E_ARG, "language id %d is not a vocabulary id", lang_ids[i]);
+        for (int j = 0; j < i; ++j)
+            if (lang_ids[j] == lang_ids[i]) return fail(WM_E_ARG, "language id %d is listed twice", lang_ids[i]);
+    }
+    return 0;
+}
+extern "C" int wm_detect_language(wm_model* m, const float* mel, int mel_on_device, int B, int sot_token, const int32_t* lang_ids, int n_lang,
+                                  int32_t* lang_out, float* probs_out) {
+    if (!m || !mel || !lang_out || B <= 0) return fail(WM_E_ARG, "bad argument");
+    if (B > m->cfg.max_batch) return fail(WM_E_ARG, "B = %d exceeds max_batch %d", B, m->cfg.max_batch);
+    if (sot_token < 0 || sot_token >= m->cfg.dims.vocab) return fail(WM_E_ARG, "sot_token %d is not a vocabulary id", sot_token);
+    WMCHK(lang_list_check(m->cfg.dims.vocab, lang_ids, n_lang));
+    if (dec_lanes_for(B) != 1) return fail(WM_E_ARG, "language detection needs a single-lane decode state");
+    WMCHK(flush_held(m));
+    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    LangAsk lang;
+    lang.ids = lang_ids;
+    lang.n = n_lang;
+    lang.sot = sot_token;
+    lang.only = true;
+    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, nullptr, true, nullptr, 0, nullptr, nullptr, false, NsAsk(), lang));
+    wm_state* s = m->cached;
+    HIPCHK(hipStreamSynchronize(s->lanes[0].st));
+    HIPCHK(hipMemcpy(lang_out, s->lg.out.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    if (probs_out) HIPCHK(hipMemcpy(probs_out, s->lg.probs.p, (size_t)B * n_lang * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+// The checks of a _lang pass.  tab / len: the per-row table built from opts->prompt when prompts == NULL.
+static int lang_check(wm_model* m, const wm_decode_opts* o, int B, const int32_t*& prompts, const int32_t*& prompt_len, int& prompt_stride,
+                      bool lp, int no_speech_token, int n_init, const int32_t* lang_ids, int n_lang, std::vector<int32_t>& tab,
+                      std::vector<int32_t>& len, wm_decode_opts& o2, RowPrompts& rows, LangAsk& lang) {
+    if (!prompts) {
+        if (prompt_len) return fail(WM_E_ARG, "prompt_len without prompts");
+        WMCHK(check_opts(m, o, B));
+        tab.resize((size_t)B * o->n_prompt);
+        for (int b = 0; b < B; ++b) std::copy(o->prompt, o->prompt + o->n_prompt, tab.begin() + (size_t)b * o->n_prompt);
+        len.assign(B, o->n_prompt);
+        prompts = tab.data();
+        prompt_len = len.data();
+        prompt_stride = o->n_prompt;
+    }
+    WMCHK(rows_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));  // (single lane included)
+    if (no_speech_token >= 0) {
+        if (!lp) return fail(WM_E_ARG, "the no-speech probe needs the log-prob outputs");
+        WMCHK(ns_check(m, o2, B, prompts, prompt_len, no_speech_token, n_init));
+    }
+    WMCHK(lang_list_check(m->cfg.dims.vocab, lang_ids, n_lang));
+    if (n_init < 2) return fail(WM_E_ARG, "n_init must be >= 2 (<|startoftranscript|> and the language slot)");
+    const int32_t sot = prompts[prompt_len[0] - n_init >= 0 ? prompt_len[0] - n_init : 0];
+    for (int b = 0; b < B; ++b) {
+        if (n_init > prompt_len[b]) return fail(WM_E_ARG, "n_init %d exceeds prompt_len[%d] = %d", n_init, b, prompt_len[b]);
+        if (prompts[(size_t)b * prompt_stride + prompt_len[b] - n_init] != sot)
+            return fail(WM_E_ARG, "row %d starts its initial ids with %d, row 0 with %d: one <|startoftranscript|> per pass", b,
+                        prompts[(size_t)b * prompt_stride + prompt_len[b] - n_init], sot);
+    }
+    lang.ids = lang_ids;
+    lang.n = n_lang;
+    lang.n_init = n_init;
+    lang.sot = sot;
+    return 0;
+}
+extern "C" int wm_transcribe_lang(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const int32_t* prompts,
+                                  const int32_t* prompt_len, int prompt_stride, int no_speech_token, int n_init, const int32_t* lang_ids, int n_lang,
+                                  int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob, float* no_speech_prob,
+                                  int32_t* lang_out, float* lang_probs) {
+    if (!m || !mel || !tokens_out || !n_tokens || !lang_out || !o || B <= 0) return fail(WM_E_ARG, "bad argument");
+    if (!token_logprobs != !avg_logprob) return fail(WM_E_ARG, "token_logprobs and avg_logprob go together");
+    const bool lp = token_logprobs != nullptr;
+    if (no_speech_token >= 0 && !no_speech_prob) return fail(WM_E_ARG, "bad argument");
+    std::vector<int32_t> tab, len;
+    wm_decode_opts o2;
+    RowPrompts rows;
+    LangAsk lang;
+    WMCHK(lang_check(m, o, B, prompts, prompt_len, prompt_stride, lp, no_speech_token, n_init, lang_ids, n_lang, tab, len, o2, rows, lang));
+    WMCHK(flush_held(m));
+    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    const NsAsk ns = no_speech_token >= 0 ? NsAsk{no_speech_token, n_init} : NsAsk();
+    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, &o2, true, nullptr, 0, nullptr, &rows, lp, ns, lang));
+    WMCHK(wait_on(m, m->cached, tokens_out, n_tokens, 0, -1, nullptr, 0, 0, nullptr, token_logprobs, avg_logprob,
+                  no_speech_token >= 0 ? no_speech_prob : nullptr, lang_out, lang_probs));
+    m->last_steps[0] = m->cached->last_steps;
+    m->align_ref[0] = wm_model::AlignRef{};
+    return 0;
+}
+// (never held for a coalesce = 2 partner: a per-row pass runs alone)
+extern "C" int wm_transcribe_submit_lang(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o,
+                                         const int32_t* prompts, const int32_t* prompt_len, int prompt_stride, int no_speech_token, int n_init,
+                                         const int32_t* lang_ids, int n_lang, int want_logprobs) {
+    if (!m || !mel || !o || B <= 0 || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
+    const bool lp = want_logprobs != 0;
+    std::vector<int32_t> tab, len;
+    wm_decode_opts o2;
+    RowPrompts rows;
+    LangAsk lang;
+    WMCHK(lang_check(m, o, B, prompts, prompt_len, prompt_stride, lp, no_speech_token, n_init, lang_ids, n_lang, tab, len, o2, rows, lang));
+    wm_model::SlotRef& r = m->slot_ref[slot];
+    if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    WMCHK(flush_held(m));
+    const NsAsk ns = no_speech_token >= 0 ? NsAsk{no_speech_token, n_init} : NsAsk();
+    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, &o2, false, nullptr, 0, nullptr, &rows, lp, ns, lang));
+    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, o2.n_prompt + 1 + o2.max_loop, false, lp, ns.token >= 0, true};
+    return 0;
+}
+extern "C" int wm_transcribe_wait_lang(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob,
+                                       float* no_speech_prob, int32_t* lang_out, float* lang_probs) {
+    if (!m || !tokens_out || !n_tokens || !lang_out || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
+    if (!token_logprobs != !avg_logprob) return fail(WM_E_ARG, "token_logprobs and avg_logprob go together");
+    return wait_impl(m, slot, tokens_out, n_tokens, nullptr, token_logprobs, avg_logprob, no_speech_prob, lang_out, lang_probs);
 }
 // ---- token-level timestamps ------------------------------------------------------------------------------------
 extern "C" int wm_set_alignment_heads(wm_model* m, const int32_t* layer_head_pairs, int n_pairs) {
@@ -3064,10 +3260,13 @@ static int long_check(wm_model* m, const wm_decode_opts* o, int B) {
 // one pass at a time.  mel: device [B][n_mels][T].
 // lo (conditioning / prompt_ids): a row's decoder prompt is built from its utterance's own segments when the row is
 // assigned to a pass; a pass whose rows all carry opts->prompt goes out exactly as before, any other as a per-row pass.
+// lang_ids != null: HF detects once per recording, on its first window — before the loop every recording's window at
+// seek 0 is gathered in groups of R rows and run through wm_detect_language's device path on state 0, the ids are read back once per
+// group, and from then on recording b's initial ids are opts->prompt with slot 1 replaced by its language: every pass is a per-row pass.
 static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int B, const wm_decode_opts* o, wm_long_result* res,
-                    const wm_long_opts* lo) {
+                    const wm_long_opts* lo, const int32_t* lang_ids = nullptr, int n_lang = 0, int32_t* lang_out = nullptr) {
     const wm_dims& c = m->cfg.dims;
-    const bool plain = long_opts_plain(lo);
+    const bool plain = long_opts_plain(lo) && !lang_ids;
     // thresholds: every pass is a log-prob pass; with a no_speech_token it also carries the probe at the first of the
     // o->n_prompt initial ids.  A window is skipped iff avg_logprob < logprob_threshold and no_speech_prob > no_speech_threshold.
     const bool quality = lo && (lo->use_logprob_threshold || lo->use_no_speech_threshold);
@@ -3098,6 +3297,34 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
         for (int k = 0; k < 2; ++k)
             if (n_items[k] && L.st[k] && L.st[k]->pending) (void)collect(k);
     };
+    std::vector<int32_t> inits;  // language detection: [B][n_prompt] each recording's own initial ids
+    if (lang_ids) {
+        std::vector<int32_t>& h = L.h_items[0];
+        for (int b0 = 0; b0 < B; b0 += R) {
+            const int nb = std::min(R, B - b0);
+            h.clear();
+            for (int r = 0; r < R; ++r) {  // (spare rows repeat the group's first recording)
+                const int b = b0 + (r < nb ? r : 0);
+                h.insert(h.end(), {b, 0, (int32_t)std::min<int64_t>(nf[b], W)});
+            }
+            HIPCHK(hipMemcpyAsync(L.items[0].p, h.data(), (size_t)R * 3 * 4, hipMemcpyHostToDevice, m->stream));
+            launch_window_gather(mel, L.items[0].as<int>(), L.win[0].as<float>(), R, c.n_mels, T, W, m->stream);
+            HIPCHK(hipGetLastError());
+            LangAsk lang;
+            lang.ids = lang_ids;
+            lang.n = n_lang;
+            lang.sot = o->prompt[0];
+            lang.only = true;
+            WMCHK(submit_on(m, &L.st[0], L.win[0].as<float>(), 1, R, nullptr, false, nullptr, 0, nullptr, nullptr, false, NsAsk(), lang));
+            HIPCHK(hipStreamSynchronize(L.st[0]->lanes[0].st));
+            HIPCHK(hipMemcpy(lang_out + b0, L.st[0]->lg.out.p, (size_t)nb * 4, hipMemcpyDeviceToHost));
+        }
+        inits.resize((size_t)B * o->n_prompt);
+        for (int b = 0; b < B; ++b) {
+            std::copy(o->prompt, o->prompt + o->n_prompt, inits.begin() + (size_t)b * o->n_prompt);
+            inits[(size_t)b * o->n_prompt + 1] = lang_out[b];
+        }
+    }
     int cursor = 0;
     for (;;) {
         for (int k = 0; k < 2; ++k) {  // fill idle states with ready utterances
@@ -3127,11 +3354,12 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
                 row_len[k].assign(R, 0);
                 for (int r = 0; r < R; ++r) {  // (spare rows repeat row 0 with its prompt)
                     const int b = h[3 * r];
-                    long_prompt(res->tokens[b].data(), res->segs[b].data(), (int)res->segs[b].size(), o->prompt, o->n_prompt, lo, o->timestamp_begin,
+                    const int32_t* init = lang_ids ? inits.data() + (size_t)b * o->n_prompt : o->prompt;  // the row's own initial ids
+                    long_prompt(res->tokens[b].data(), res->segs[b].data(), (int)res->segs[b].size(), init, o->n_prompt, lo, o->timestamp_begin,
                                 c.n_text_ctx, pr);
                     std::copy(pr.begin(), pr.end(), row_prompts[k].begin() + (size_t)r * c.n_text_ctx);
                     row_len[k][r] = (int32_t)pr.size();
-                    per_row = per_row || (int)pr.size() != o->n_prompt || !std::equal(pr.begin(), pr.end(), o->prompt);
+                    per_row = per_row || lang_ids || (int)pr.size() != o->n_prompt || !std::equal(pr.begin(), pr.end(), init);
                 }
             }
             row_len[k].resize(R, o->n_prompt);
@@ -3214,14 +3442,14 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
 }
 
 static int transcribe_long_impl(wm_model* m, const float* mel_dev, int T, const int32_t* nf, int B, const wm_decode_opts* o, wm_long_result** out,
-                                const wm_long_opts* lo) {
+                                const wm_long_opts* lo, const int32_t* lang_ids = nullptr, int n_lang = 0, int32_t* lang_out = nullptr) {
     wm_long_result* r = new wm_long_result();
     r->tokens.resize(B);
     r->segs.resize(B);
     r->wins.resize(B);
     r->seg_avg.resize(B);
     r->seg_nsp.resize(B);
-    const int rc = long_run(m, mel_dev, T, nf, B, o, r, lo);
+    const int rc = long_run(m, mel_dev, T, nf, B, o, r, lo, lang_ids, n_lang, lang_out);
     (void)hipStreamSynchronize(m->stream);
     long_release(m);
     if (rc) {
@@ -3232,12 +3460,22 @@ static int transcribe_long_impl(wm_model* m, const float* mel_dev, int T, const 
     return 0;
 }
 
-extern "C" int wm_transcribe_long_ex(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames,
-                                     const wm_decode_opts* o, const wm_long_opts* lo, wm_long_result** out) {
+// the extra refusals of a long-form run with language detection; everything is refused before anything is launched
+static int long_lang_check(wm_model* m, const wm_decode_opts* o, int B, const int32_t* lang_ids, int n_lang, const int32_t* lang_out) {
+    if (!lang_out) return fail(WM_E_ARG, "bad argument");
+    WMCHK(lang_list_check(m->cfg.dims.vocab, lang_ids, n_lang));
+    if (o->n_prompt < 2) return fail(WM_E_ARG, "language detection needs at least two initial ids (<|startoftranscript|> and the language slot)");
+    if (dec_lanes_for(std::min((B + 1) / 2, m->cfg.max_batch)) != 1) return fail(WM_E_ARG, "language detection needs a single-lane decode state");
+    if (m->cfg.dims.n_text_ctx < o->n_prompt + 1 + o->max_loop) return fail(WM_E_ARG, "the decoder context is too short");
+    return 0;
+}
+static int long_mel_impl(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames, const wm_decode_opts* o,
+                         const wm_long_opts* lo, const int32_t* lang_ids, int n_lang, int32_t* lang_out, bool want_lang, wm_long_result** out) {
     if (!m || !mel || !out || T <= 0) return fail(WM_E_ARG, "bad argument");
     *out = nullptr;
     WMCHK(long_check(m, o, B));
     WMCHK(long_opts_check(lo, o->prompt, o->n_prompt, o->max_loop, m->cfg.dims.vocab, m->cfg.dims.n_text_ctx, std::min((B + 1) / 2, m->cfg.max_batch)));
+    if (want_lang) WMCHK(long_lang_check(m, o, B, lang_ids, n_lang, lang_out));
     std::vector<int32_t> nf(B, T);
     if (n_frames)
         for (int b = 0; b < B; ++b) {
@@ -3252,7 +3490,16 @@ extern "C" int wm_transcribe_long_ex(wm_model* m, const float* mel, int mel_on_d
         HIPCHK(hipMemcpyAsync(m->lf.in_mel.p, mel, bytes, hipMemcpyHostToDevice, m->stream));
         dev = m->lf.in_mel.as<float>();
     }
-    return transcribe_long_impl(m, dev, T, nf.data(), B, o, out, lo);
+    return transcribe_long_impl(m, dev, T, nf.data(), B, o, out, lo, want_lang ? lang_ids : nullptr, n_lang, lang_out);
+}
+extern "C" int wm_transcribe_long_ex(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames,
+                                     const wm_decode_opts* o, const wm_long_opts* lo, wm_long_result** out) {
+    return long_mel_impl(m, mel, mel_on_device, B, T, n_frames, o, lo, nullptr, 0, nullptr, false, out);
+}
+extern "C" int wm_transcribe_long_lang(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames,
+                                       const wm_decode_opts* o, const wm_long_opts* lo, const int32_t* lang_ids, int n_lang, int32_t* lang_out,
+                                       wm_long_result** out) {
+    return long_mel_impl(m, mel, mel_on_device, B, T, n_frames, o, lo, lang_ids, n_lang, lang_out, true, out);
 }
 extern "C" int wm_transcribe_long(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames, const wm_decode_opts* o,
                                   wm_long_result** out) {
@@ -3263,12 +3510,13 @@ extern "C" int wm_transcribe_long_pcm(wm_model* m, const float* pcm, const int32
                                       wm_long_result** out) {
     return wm_transcribe_long_pcm_ex(m, pcm, n_samples, B, stride, o, nullptr, out);
 }
-extern "C" int wm_transcribe_long_pcm_ex(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o,
-                                         const wm_long_opts* lo, wm_long_result** out) {
+static int long_pcm_impl(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o, const wm_long_opts* lo,
+                         const int32_t* lang_ids, int n_lang, int32_t* lang_out, bool want_lang, wm_long_result** out) {
     if (!m || !out) return fail(WM_E_ARG, "bad argument");
     *out = nullptr;
     WMCHK(long_check(m, o, B));
     WMCHK(long_opts_check(lo, o->prompt, o->n_prompt, o->max_loop, m->cfg.dims.vocab, m->cfg.dims.n_text_ctx, std::min((B + 1) / 2, m->cfg.max_batch)));
+    if (want_lang) WMCHK(long_lang_check(m, o, B, lang_ids, n_lang, lang_out));
     std::vector<int32_t> nf(std::max(B, 0));
     const int rc = frontend_long_run(m, pcm, n_samples, B, stride, nf.data());  // same stream as the gathers: ordered, no host sync
     if (rc) {
@@ -3276,7 +3524,15 @@ extern "C" int wm_transcribe_long_pcm_ex(wm_model* m, const float* pcm, const in
         long_release(m);
         return rc;
     }
-    return transcribe_long_impl(m, m->lf.mel.as<float>(), stride / FE_HOP, nf.data(), B, o, out, lo);
+    return transcribe_long_impl(m, m->lf.mel.as<float>(), stride / FE_HOP, nf.data(), B, o, out, lo, want_lang ? lang_ids : nullptr, n_lang, lang_out);
+}
+extern "C" int wm_transcribe_long_pcm_ex(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o,
+                                         const wm_long_opts* lo, wm_long_result** out) {
+    return long_pcm_impl(m, pcm, n_samples, B, stride, o, lo, nullptr, 0, nullptr, false, out);
+}
+extern "C" int wm_transcribe_long_pcm_lang(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o,
+                                           const wm_long_opts* lo, const int32_t* lang_ids, int n_lang, int32_t* lang_out, wm_long_result** out) {
+    return long_pcm_impl(m, pcm, n_samples, B, stride, o, lo, lang_ids, n_lang, lang_out, true, out);
 }
 
 extern "C" int wm_long_result_sizes(const wm_long_result* r, int b, int32_t* n_tokens, int32_t* n_segments) {
@@ -4144,6 +4400,43 @@ extern "C" int wm_op_no_speech(float* prob, float* lse, const float* x, const fl
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(prob, pr.p, (size_t)B * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(lse, ls.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// lang_detect_kernel alone, launched as the language pass launches it (no patch).
+extern "C" int wm_op_lang_detect(int32_t* lang_out, float* probs, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                                 const int32_t* lang_ids, int n_lang, int B, int N, int K, int dtype) {
+    if (!lang_out || !x || !ln_g || !ln_b || !emb || !lang_ids || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
+    if (K != 128 && K != 384 && K != 512) return fail(WM_E_ARG, "K must be 128, 384 or 512 (the logits kernels' d_model)");
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    WMCHK(lang_list_check(N, lang_ids, n_lang));
+    TmpDev t;
+    t.bufs.reserve(8);
+    DevBuf &dx = t.add(), &g = t.add(), &be = t.add(), &w = t.add(), &li = t.add(), &lo = t.add(), &pr = t.add();
+    WMCHK(upload(dx, x, (size_t)B * K, WM_F32));
+    WMCHK(upload(g, ln_g, K, WM_F32));
+    WMCHK(upload(be, ln_b, K, WM_F32));
+    WMCHK(upload(w, emb, (size_t)N * K, dtype));
+    WMCHK(li.alloc((size_t)n_lang * 4));
+    HIPCHK(hipMemcpy(li.p, lang_ids, (size_t)n_lang * 4, hipMemcpyHostToDevice));
+    WMCHK(lo.alloc((size_t)B * 4, true));
+    WMCHK(pr.alloc((size_t)B * n_lang * 4, true));
+    LangDetectParams q{};
+    q.x = dx.as<float>();
+    q.ldx = K;
+    q.ln_g = g.as<float>();
+    q.ln_b = be.as<float>();
+    q.emb = w.p;
+    q.lang_ids = li.as<int>();
+    q.n_lang = n_lang;
+    q.K = K;
+    q.B = B;
+    q.lang_out = lo.as<int>();
+    q.probs = pr.as<float>();
+    DISPATCH_DT(dtype, TT, launch_lang_detect<TT>(q, nullptr));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(lang_out, lo.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    if (probs) HIPCHK(hipMemcpy(probs, pr.p, (size_t)B * n_lang * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

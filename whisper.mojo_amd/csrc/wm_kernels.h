@@ -333,6 +333,27 @@ struct NoSpeechParams {
 };
 void launch_no_speech_capture(const float* rows, float* out, int B, int d, hipStream_t st);
 template <typename TW> void launch_no_speech_finish(const NoSpeechParams& p, hipStream_t st);
+// Language detection: per row, the logits of the n_lang candidate ids only (LayerNorm of the captured [SOT]-pass row as
+// the no-speech finish forms it, rounded to TW, times each candidate's embedding row, fp32 sums), their arg-max (ties: the smaller
+// token id) and their softmax in list order.  The callers check 1 <= n_lang <= LANG_DETECT_MAX, 1 <= K <= LANG_DETECT_MAX_K and
+// that every id is a vocabulary id.
+static const int LANG_DETECT_MAX = 128;
+static const int LANG_DETECT_MAX_K = 1280;
+struct LangDetectParams {
+    const float* x;  // [B][ldx] residual rows of the [SOT] pass (before the final LayerNorm)
+    int ldx;
+    const float* ln_g;
+    const float* ln_b;
+    const void* emb;      // [N][K] token embedding in the decoder's operand dtype
+    const int* lang_ids;  // [n_lang] device list, any order
+    int n_lang, K, B;
+    int* lang_out;  // [B] out: the winning token id
+    float* probs;   // [B][n_lang] out, list order; or null
+    int* patch;     // non-null: the id is also written to patch[b * patch_stride + patch_col[b]] (the row's prompt-table slot)
+    int patch_stride;
+    const int* patch_col;  // [B]
+};
+template <typename TW> void launch_lang_detect(const LangDetectParams& p, hipStream_t st);
 // rows of the gather buffer of SURVEY §8e: dst[r] = [n_tokens[r], ids of row r zero-padded to `stride`] for r < rows; rows in
 // [rows, rows_cap) are zeroed (ragged shards gather a fixed row count per rank)
 void launch_pack_tokens(const int* out_tokens, const int* n_tokens, int out_stride, int rows, int rows_cap, int stride, int* dst, hipStream_t st);

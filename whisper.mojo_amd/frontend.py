@@ -74,16 +74,23 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
                                max_loop: int = MAX_LOOP, suppress_tokens: Sequence[int] = (), begin_suppress_tokens: Sequence[int] = (),
                                timestamps=(50364, 50363, 50), return_stats: bool = False, prompt_ids=None,
                                condition_on_prev_tokens: bool = False, prompt_condition_type: str = "first-segment",
-                               prev_sot_token: int = 50361, logprob_threshold=None, no_speech_threshold=None, no_speech_token=None):
+                               prev_sot_token: int = 50361, logprob_threshold=None, no_speech_threshold=None, no_speech_token=None,
+                               detect_language=None):
     """Sequential long-form transcription of 16 kHz PCM of any length (HF generate's long-form path), the long
     log-mel never leaving the GPU.  prompt_ids / condition_on_prev_tokens / prompt_condition_type / logprob_threshold /
-    no_speech_threshold / no_speech_token: as Whisper.transcribe_long_form.  Returns per recording {"sequence": ids, "segments": [{"start", "end", "tokens"}]}."""
+    no_speech_threshold / no_speech_token / detect_language (then the detected ids [B] are returned as the last element): as
+    Whisper.transcribe_long_form.  Returns per recording {"sequence": ids, "segments": [{"start", "end", "tokens"}]}."""
     lo, _keep2 = _lib.long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token, logprob_threshold,
                                 no_speech_threshold, no_speech_token)
     if no_speech_token is not None and int(no_speech_token) >= model.config.vocab_size:
         raise ValueError(f"no_speech_token {no_speech_token} is not a vocabulary id")
     if timestamps is None:
         raise ValueError("long-form transcription needs the timestamp rules")
+    lang_list = None
+    if detect_language is not None:
+        lang_list = _lib.lang_args(detect_language, model.config.vocab_size)
+        if len(prompt) < 2:
+            raise ValueError("detect_language needs at least two initial ids (<|startoftranscript|> and the language slot)")
     buf, n, stride = _pack(audios)
     stride = max(stride, 201)
     if buf.shape[1] < stride:
@@ -91,6 +98,13 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
     opts, _keep = model._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
     h = C.c_void_p()
+    if lang_list is not None:
+        lang = np.zeros(len(audios), np.int32)
+        _lib.check(_lib.lib().wm_transcribe_long_pcm_lang(model._h, buf.ctypes.data_as(fp), n.ctypes.data_as(ip), len(audios), stride,
+                                                          C.byref(opts), C.byref(lo), lang_list.ctypes.data_as(ip), lang_list.size,
+                                                          lang.ctypes.data_as(ip), C.byref(h)))
+        out, stats = _lib.long_result(h, len(audios), logprob_threshold is not None or no_speech_threshold is not None)
+        return (out, stats, lang) if return_stats else (out, lang)
     _lib.check(_lib.lib().wm_transcribe_long_pcm_ex(model._h, buf.ctypes.data_as(fp), n.ctypes.data_as(ip), len(audios), stride,
                                                     C.byref(opts), C.byref(lo), C.byref(h)))
     out, stats = _lib.long_result(h, len(audios), logprob_threshold is not None or no_speech_threshold is not None)

@@ -69,3 +69,38 @@ class Tokenizer:
                 else:
                     data.append(b)
         return data.decode("utf-8", errors="replace")
+
+
+# The multilingual checkpoints' language tokens, in id order from <|startoftranscript|> + 1 (openai-whisper's LANGUAGES order;
+# the 51865-entry vocabulary has these 99, ids 50259 … 50357).
+LANGUAGE_CODES = (
+    "en zh de es ru ko fr ja pt tr pl ca nl ar sv it id hi fi vi he uk el ms cs ro da hu ta no th ur hr bg lt la mi ml cy sk te fa lv bn "
+    "sr az sl kn et mk br eu is hy ne mn bs kk sq sw gl mr pa si km sn yo so af oc ka be tg sd gu am yi lo uz fo ht ps tk nn mt sa lb my "
+    "bo tl mg as tt haw ln ha ba jw su").split()
+LANGUAGE_ID0 = 50259
+
+
+def language_ids(tokenizer: "Tokenizer" = None):
+    """The language ids of the multilingual vocabulary, for detect_language: (ids, {id: code}, from_vocab).
+    With a tokenizer whose vocabulary holds the `<|xx|>` entries behind <|startoftranscript|>, ids and codes are read from it
+    (from_vocab True); without one, or when the vocabulary file lacks those entries, the published range 50259 … 50357 and
+    openai-whisper's code order are returned and from_vocab is False."""
+    if tokenizer is not None:
+        ids, codes = [], {}
+        i = LANGUAGE_ID0
+        while True:
+            tok = tokenizer._token(i)
+            if tok is None or not Tokenizer._is_special(tok) or not (2 <= len(tok) - 4 <= 3) or not tok[2:-2].isalpha():
+                break
+            ids.append(i)
+            codes[i] = tok[2:-2]
+            i += 1
+        if ids and tokenizer._token(LANGUAGE_ID0 - 1) == "<|startoftranscript|>":
+            return ids, codes, True
+    ids = list(range(LANGUAGE_ID0, LANGUAGE_ID0 + len(LANGUAGE_CODES)))
+    return ids, dict(zip(ids, LANGUAGE_CODES)), False
+
+
+def language_code(token_id: int, tokenizer: "Tokenizer" = None) -> str:
+    """<|xx|> id -> "xx"; KeyError for an id that is no language token."""
+    return language_ids(tokenizer)[1][int(token_id)]

@@ -246,6 +246,71 @@ class Whisper:
         lens = len(prompt) if prompts is None else [len(r) for r in prompts]
         return _lib.no_speech_args(no_speech_token, n_init, lens, self.config.vocab_size)
 
+    def _lang_args(self, detect_language, n_init, prompt, prompts, return_token_timestamps, no_speech_token, return_logprobs):
+        """-> (int32 language list, n_init), checked on the host (ValueError) before anything else"""
+        if return_token_timestamps:
+            raise ValueError("detect_language does not combine with return_token_timestamps")
+        ids = _lib.lang_args(detect_language, self.config.vocab_size)
+        if n_init is None:
+            if prompts is not None:
+                raise ValueError("n_init is required with per-row prompts (the number of initial ids, <|startoftranscript|> first)")
+            n_init = len(prompt)
+        n_init = int(n_init)
+        shortest = len(prompt) if prompts is None else min(len(r) for r in prompts)
+        if n_init < 2 or n_init > shortest:
+            raise ValueError(f"n_init {n_init} outside [2, shortest prompt = {shortest}]")
+        if no_speech_token is not None:
+            if not return_logprobs:
+                raise ValueError("no_speech_token needs return_logprobs=True")
+            if int(no_speech_token) < 0 or int(no_speech_token) >= self.config.vocab_size:
+                raise ValueError(f"no_speech_token {no_speech_token} is not a vocabulary id")
+        return ids, n_init
+
+    def detect_language(self, mel, lang_ids: Sequence[int], sot: int = PROMPT[0]):
+        """openai-whisper's detect_language / HF WhisperGenerationMixin.detect_language: the encoder, one decoder pass
+        over [sot] and the language kernel -> (ids [B] int32: per utterance the id of lang_ids with the largest logit, probs
+        [B, n_lang] float32: the softmax over lang_ids, in list order).  lang_ids: 1..128 distinct vocabulary ids, any order
+        (tokenizer.language_ids)."""
+        ids = _lib.lang_args(lang_ids, self.config.vocab_size)
+        if int(sot) < 0 or int(sot) >= self.config.vocab_size:
+            raise ValueError(f"sot {sot} is not a vocabulary id")
+        if self._h is None:
+            raise _lib.WhisperMiError("model not loaded")
+        ptr, on_dev, B, keep = _mel_arg(mel, self.config)
+        out = np.zeros(B, np.int32)
+        probs = np.zeros((B, ids.size), np.float32)
+        _lib.check(_lib.lib().wm_detect_language(self._h, ptr, on_dev, B, int(sot), _ip(ids), ids.size, _ip(out), _fp(probs)))
+        return out, probs
+
+    def _lang_call(self, slot, ptr, on_dev, B, opts, p, prompts, max_loop, lang, return_logprobs, no_speech_token):
+        """submit (slot is not None) or run a _lang pass; -> what transcribe_wait needs / the result"""
+        ids, n_init = lang
+        tab, lens = self._prompt_rows(prompts, B) if prompts is not None else (None, None)
+        rows = (_ip(tab) if tab is not None else None, _ip(lens) if tab is not None else None, tab.shape[1] if tab is not None else 0)
+        total = (tab.shape[1] if tab is not None else len(p)) + 1 + max_loop
+        ns_tok = -1 if no_speech_token is None else int(no_speech_token)
+        if slot is not None:
+            _lib.check(_lib.lib().wm_transcribe_submit_lang(self._h, slot, ptr, on_dev, B, C.byref(opts), *rows, ns_tok, n_init, _ip(ids),
+                                                            ids.size, int(return_logprobs)))
+            return total, ("lang", ids.size, bool(return_logprobs), ns_tok >= 0)
+        return self._lang_collect(None, B, total, ids.size, return_logprobs, ns_tok >= 0,
+                                  lambda *a: _lib.lib().wm_transcribe_lang(self._h, ptr, on_dev, B, C.byref(opts), *rows, ns_tok, n_init,
+                                                                           _ip(ids), ids.size, *a))
+
+    def _lang_collect(self, slot, B, total, n_lang, lp, ns, call):
+        toks, n = np.zeros((B, total), np.int32), np.zeros(B, np.int32)
+        lps, avg, nsp = np.zeros((B, total), np.float32), np.zeros(B, np.float32), np.zeros(B, np.float32)
+        lang_out, lang_probs = np.zeros(B, np.int32), np.zeros((B, n_lang), np.float32)
+        _lib.check(call(_ip(toks), _ip(n), _fp(lps) if lp else None, _fp(avg) if lp else None, _fp(nsp) if ns else None, _ip(lang_out),
+                        _fp(lang_probs)))
+        self.last_tokens, self.last_counts = toks, n
+        out = [toks[b, :n[b]].tolist() for b in range(B)]
+        lang = (lang_out, lang_probs)
+        if not lp:
+            return out, lang
+        self.last_logprobs = lps
+        return out, (self._split_times(lps, n, B), avg, nsp) if ns else (self._split_times(lps, n, B), avg), lang
+
     @staticmethod
     def _split_times(times, n, B):
         return [times[b, :n[b]].tolist() for b in range(B)]
@@ -254,8 +319,13 @@ class Whisper:
                          ignore_eot: bool = False, suppress_tokens: Sequence[int] = (),
                          begin_suppress_tokens: Sequence[int] = (), timestamps=None, return_token_timestamps: bool = False,
                          n_frames=None, prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False,
-                         no_speech_token: Optional[int] = None, n_init: Optional[int] = None):
+                         no_speech_token: Optional[int] = None, n_init: Optional[int] = None,
+                         detect_language: Optional[Sequence[int]] = None):
         """Batched Whisper.transcribe: one List[int] per utterance = prompt + generated ids (+ eot when hit).
+        detect_language: a list of language ids (tokenizer.language_ids) — HF generate's language=None: every utterance's
+        language is detected on the device in the same pass and written over the second of its n_init initial ids (n_init: default
+        the shared prompt's length, required with prompts=, >= 2); returns (ids, lang) or, with return_logprobs, (ids, (…the tuple
+        below…), lang) with lang = (lang_ids [B], lang_probs [B, n_lang]).  Not with return_token_timestamps.
         return_logprobs: also return (token_logprobs, avg_logprob) as (ids, (token_logprobs, avg_logprob)): per utterance the
         log-probability of every id in the layout of its id list (0 at the prompt positions), HF's log_softmax of the processed
         scores at the chosen id, and avg_logprob [B] = their mean over the generated ids (openai-whisper's avg_logprob, HF's
@@ -269,12 +339,17 @@ class Whisper:
         probability of that id under the raw logits at each row's <|startoftranscript|> position, prompt length - n_init; the second
         element becomes (token_logprobs, avg_logprob, no_speech_prob).  n_init: the number of initial ids (<|startoftranscript|>
         first); defaults to the shared prompt's length, required with prompts=."""
-        ns = self._ns_args(no_speech_token, n_init, prompt, prompts, return_logprobs)
+        lang = None
+        if detect_language is not None:
+            lang = self._lang_args(detect_language, n_init, prompt, prompts, return_token_timestamps, no_speech_token, return_logprobs)
+        ns = None if lang else self._ns_args(no_speech_token, n_init, prompt, prompts, return_logprobs)
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]
+        if lang:
+            return self._lang_call(None, ptr, on_dev, B, opts, p, prompts, max_loop, lang, return_logprobs, no_speech_token)
         if return_logprobs:
             if return_token_timestamps:
                 raise ValueError("return_logprobs does not combine with return_token_timestamps")
@@ -327,8 +402,12 @@ class Whisper:
                              timestamps=(50364, 50363, 50), return_stats: bool = False, prompt_ids: Optional[Sequence[int]] = None,
                              condition_on_prev_tokens: bool = False, prompt_condition_type: str = "first-segment",
                              prev_sot_token: int = 50361, logprob_threshold: Optional[float] = None,
-                             no_speech_threshold: Optional[float] = None, no_speech_token: Optional[int] = None):
+                             no_speech_threshold: Optional[float] = None, no_speech_token: Optional[int] = None,
+                             detect_language: Optional[Sequence[int]] = None):
         """Sequential long-form transcription (HF generate's long-form path, greedy).
+        detect_language: a list of language ids (HF generate's language=None) — every recording's language is detected on
+        its first window and replaces the second id of `prompt` for that recording; the call then also returns the detected ids
+        [B] as its last element: (out, lang) or (out, stats, lang).
         logprob_threshold / no_speech_threshold (HF generate's options, temperature 0 only; no_speech_token: the <|nospeech|> id,
         HF's no_timestamps_token_id - 1): a window with avg_logprob < logprob_threshold and no_speech_prob > no_speech_threshold is
         skipped — no segments, no ids, seek advances by the window's frames.  With either threshold every segment carries its window's
@@ -347,6 +426,11 @@ class Whisper:
         if no_speech_token is not None and int(no_speech_token) >= self.config.vocab_size:
             raise ValueError(f"no_speech_token {no_speech_token} is not a vocabulary id")
         quality = logprob_threshold is not None or no_speech_threshold is not None
+        lang_list = None
+        if detect_language is not None:
+            lang_list = _lib.lang_args(detect_language, self.config.vocab_size)
+            if len(prompt) < 2:
+                raise ValueError("detect_language needs at least two initial ids (<|startoftranscript|> and the language slot)")
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
         if timestamps is None:
@@ -380,7 +464,8 @@ class Whisper:
             if not t.is_cuda:
                 return self.transcribe_long_form(t.float().numpy(), n_frames, prompt, eot, max_loop, suppress_tokens,
                                                  begin_suppress_tokens, timestamps, return_stats, prompt_ids, condition_on_prev_tokens,
-                                                 prompt_condition_type, prev_sot_token, logprob_threshold, no_speech_threshold, no_speech_token)
+                                                 prompt_condition_type, prev_sot_token, logprob_threshold, no_speech_threshold, no_speech_token,
+                                                 detect_language)
             keep = t.contiguous().float()
             torch.cuda.current_stream(keep.device).synchronize()  # the library reads it on its own HIP stream
             ptr, on_dev = C.c_void_p(keep.data_ptr()), 1
@@ -388,6 +473,12 @@ class Whisper:
         nf = self._frames_arg(n_frames, B)
         opts, _keep2 = self._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
         h = C.c_void_p()
+        if lang_list is not None:
+            lang = np.zeros(B, np.int32)
+            _lib.check(_lib.lib().wm_transcribe_long_lang(self._h, ptr, on_dev, B, T, _ip(nf) if nf is not None else None, C.byref(opts),
+                                                          C.byref(lo), _ip(lang_list), lang_list.size, _ip(lang), C.byref(h)))
+            out, stats = _lib.long_result(h, B, quality)
+            return (out, stats, lang) if return_stats else (out, lang)
         _lib.check(_lib.lib().wm_transcribe_long_ex(self._h, ptr, on_dev, B, T, _ip(nf) if nf is not None else None, C.byref(opts),
                                                     C.byref(lo), C.byref(h)))
         out, stats = _lib.long_result(h, B, quality)
@@ -405,19 +496,29 @@ class Whisper:
                           ignore_eot: bool = False, suppress_tokens: Sequence[int] = (), begin_suppress_tokens: Sequence[int] = (),
                           timestamps=None, return_token_timestamps: bool = False, n_frames=None,
                           prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False,
-                          no_speech_token: Optional[int] = None, n_init: Optional[int] = None):
+                          no_speech_token: Optional[int] = None, n_init: Optional[int] = None,
+                          detect_language: Optional[Sequence[int]] = None):
         """Pipelined form (wm_transcribe_submit): enqueue encoder + greedy loop for this batch on pipeline slot 0..7 and
         return at once; `transcribe_wait(slot)` collects the ids.  Submitting batch i+1 before waiting for batch i lets
         its encoder overlap batch i's decode.  return_token_timestamps / n_frames: as transcribe_batch; the matching
         transcribe_wait then returns (ids, times).  return_logprobs: as transcribe_batch; the matching transcribe_wait returns
         (ids, (token_logprobs, avg_logprob)).  no_speech_token / n_init: as transcribe_batch; the matching transcribe_wait returns
-        (ids, (token_logprobs, avg_logprob, no_speech_prob))."""
-        ns = self._ns_args(no_speech_token, n_init, prompt, prompts, return_logprobs)
+        (ids, (token_logprobs, avg_logprob, no_speech_prob)).  detect_language: as transcribe_batch; the matching transcribe_wait
+        returns what transcribe_batch returns."""
+        lang = None
+        if detect_language is not None:
+            lang = self._lang_args(detect_language, n_init, prompt, prompts, return_token_timestamps, no_speech_token, return_logprobs)
+        ns = None if lang else self._ns_args(no_speech_token, n_init, prompt, prompts, return_logprobs)
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]
+        if lang:
+            total, tag = self._lang_call(slot, ptr, on_dev, B, opts, p, prompts, max_loop, lang, return_logprobs, no_speech_token)
+            self._pending = getattr(self, "_pending", {})
+            self._pending[slot] = (B, total, keep, tag)
+            return
         if return_logprobs:
             if return_token_timestamps:
                 raise ValueError("return_logprobs does not combine with return_token_timestamps")
@@ -449,6 +550,9 @@ class Whisper:
 
     def transcribe_wait(self, slot: int = 0):
         B, total, _keep, tt = self._pending.pop(slot)
+        if isinstance(tt, tuple) and tt and tt[0] == "lang":
+            return self._lang_collect(slot, B, total, tt[1], tt[2], tt[3],
+                                      lambda *a: _lib.lib().wm_transcribe_wait_lang(self._h, slot, *a))
         toks = np.zeros((B, total), np.int32)
         n = np.zeros(B, np.int32)
         if tt == "lp_ns":

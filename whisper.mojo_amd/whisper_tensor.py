@@ -249,6 +249,24 @@ def no_speech(x, ln_g, ln_b, emb, token: int, dtype=DT_F32):
     return prob, lse
 
 
+def lang_detect(x, ln_g, ln_b, emb, lang_ids, dtype=DT_F32):
+    """lang_detect_kernel alone (wm_op_lang_detect): (ids [B], probs [B, n_lang]) — among lang_ids the id with the largest
+    layer_norm(x)·emb[id] (ties: the smaller id) and the softmax over those candidates, in list order."""
+    f = lambda a: np.ascontiguousarray(a, np.float32)
+    x, emb = f(x), f(emb)
+    g, b = f(ln_g).ravel(), f(ln_b).ravel()
+    if x.ndim != 2 or emb.ndim != 2 or emb.shape[1] != x.shape[1] or g.size != x.shape[1] or b.size != x.shape[1]:
+        raise ValueError("x must be [B, K], emb [N, K], ln_g / ln_b [K]")
+    if x.shape[1] not in (128, 384, 512):
+        raise ValueError("K must be 128, 384 or 512")
+    ids = _lib.lang_args(lang_ids, emb.shape[0])
+    B, K = x.shape
+    out, probs = np.zeros(B, np.int32), np.zeros((B, ids.size), np.float32)
+    _lib.check(_lib.lib().wm_op_lang_detect(out.ctypes.data_as(C.POINTER(C.c_int32)), _fp(probs), _fp(x), _fp(g), _fp(b), _fp(emb),
+                                            ids.ctypes.data_as(C.POINTER(C.c_int32)), ids.size, B, emb.shape[0], K, dtype))
+    return out, probs
+
+
 def xattn(out: np.ndarray, q, Wk, Wv, bv, x, n_heads: int, nsplit: int, q_B: int = 0, out_dtype=DT_F32):
     """The absorbed cross-attention (wm_op_xattn): q [rows, d], Wk / Wv [d, d], bv [d], x [n_utt, n_keys, d], d = 64·n_heads;
     row r attends over x[r % q_B] (q_B > 0, prefill) or x[r] -> out [rows, d]."""
