@@ -251,6 +251,42 @@ int wm_transcribe_submit_lang(wm_model* m, int slot, const float* mel, int mel_o
 int wm_transcribe_wait_lang(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob,
                             float* no_speech_prob, int32_t* lang_out, float* lang_probs);
 
+/* ---- transcript scoring ---------------------------------------------------------------------------------------
+ * How likely is THIS transcript for THIS audio: teacher-forced log-probabilities, HF
+ * model(input_features, decoder_input_ids=y[:, :-1]).logits.float().log_softmax(-1) gathered at y[:, 1:].  Row b holds the ids
+ * y[0 .. ids_len[b]) — the decoder prompt followed by the hypothesis, a trailing eot included if it is to be scored — at
+ * ids[b * ids_stride]; context_len[b] in [1, ids_len[b] - 1] of them are context (NULL: 1 for every row).  For t in [1, ids_len[b]):
+ *   token_logprobs[b][t] = z[t-1][y[t]] - logsumexp_j z[t-1][j]      top_ids[b][t] = argmax_j z[t-1][j]  (lowest id on ties)
+ * z the RAW decoder logits after input t-1 (no suppress masks, no timestamp rules), fp32 normaliser over the whole vocabulary.
+ * token_logprobs[b][0] = 0, top_ids[b][0] = -1; positions at and past ids_len[b] are 0 / -1.  sum_logprob[b] = the sum over
+ * t >= context_len[b] (positions 1 .. context_len - 1 are reported, not summed); avg_logprob[b] = that sum / (ids_len[b] -
+ * context_len[b]) = -HF loss of the row with labels = -100 on the context.  token_logprobs, top_ids (or NULL): host [B][ids_stride];
+ * sum_logprob, avg_logprob: host [B].
+ * pos_mode: WM_POS_HF — input t sits at position t; WM_POS_REF — position t for t < context_len[b] and t - 1 from there on (the
+ * current_len - 1 of whisper.mojo:217), so that scoring the ids a WM_POS_REF transcription returned, with context_len = its prompt
+ * length, reproduces that pass's own hidden rows.
+ * One encoder run, the per-row prefill of wm_transcribe_rows over y[0 .. len - 1) (chunks of 16 positions, no logits launch), then one
+ * LayerNorm launch, one vocabulary sweep for all sum(ids_len[b] - 1) rows and a merge: no loop, no captured graph, and no logits
+ * matrix.  Rows are independent: a row scored in any batch gives the same bits.  Single-lane decode states only; under coalesce = 2 a
+ * score submit always runs alone.  wm_score uses slot 0's state like wm_transcribe; afterwards the slot's state holds no usable pass.
+ * WM_E_ARG, nothing launched: ids_len[b] < 2 or > min(ids_stride, n_text_ctx); context_len[b] outside [1, ids_len[b] - 1]; an id
+ * outside the vocabulary; B over max_batch; a bad pos_mode; a multi-lane decode state.  wm_score_wait on a slot that holds a
+ * transcribe pass returns WM_E_STATE, and so do the wm_transcribe_wait family on a score slot (the pass stays pending).
+ * The id arrays are copied at submit; mel must stay valid until the matching wait when it is a device pointer. */
+int wm_score(wm_model* m, const float* mel, int mel_on_device, int B, int pos_mode, const int32_t* ids, const int32_t* ids_len, int ids_stride,
+             const int32_t* context_len, float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob);
+int wm_score_submit(wm_model* m, int slot, const float* mel, int mel_on_device, int B, int pos_mode, const int32_t* ids, const int32_t* ids_len,
+                    int ids_stride, const int32_t* context_len);
+int wm_score_wait(wm_model* m, int slot, float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob);
+/* Diagnostics (tools/score_cost.py): GPU time of the phases of the slot's last collected score pass (slot 0 also serves wm_score), from
+ * HIP events on the pass's stream, milliseconds: ms[0] encoder, [1] prefill chunks + row collection, [2] final LayerNorm, [3] vocabulary
+ * sweep, [4] merge + sums.  WM_E_STATE: no completed score pass on the slot's state, or it has started another pass since. */
+int wm_score_phases(wm_model* m, int slot, float* ms);
+/* PCM in (the layout of wm_log_mel): front end + wm_score without the mel leaving the GPU */
+int wm_score_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, int pos_mode, const int32_t* ids,
+                 const int32_t* ids_len, int ids_stride, const int32_t* context_len, float* token_logprobs, int32_t* top_ids, float* sum_logprob,
+                 float* avg_logprob);
+
 /* ---- token-level timestamps ---------------------------------------------------------------------------------
  * When each id was spoken, with the semantics of HF generate(..., return_token_timestamps=True)
  * (WhisperGenerationMixin._extract_token_timestamps, time_precision 0.02, median_filter_width 7, num_input_ids = n_prompt): the
@@ -466,6 +502,13 @@ int wm_op_no_speech(float* prob, float* lse, const float* x, const float* ln_g, 
  * 1 <= n_lang <= 128, ids distinct and inside [0, N), K 128, 384 or 512.  probs may be NULL. */
 int wm_op_lang_detect(int32_t* lang_out, float* probs, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                       const int32_t* lang_ids, int n_lang, int B, int N, int K, int dtype);
+/* The score pass's vocabulary side alone: the final LayerNorm once per row into the sweep's operand form, the MFMA-tiled
+ * sweep with the fused log-sum-exp / target gather / arg-max, and the merge.  With z = layer_norm(x, ln_g, ln_b, 1e-5)·emb[N, K]ᵀ (emb
+ * rounded to dtype on upload; the arithmetic class per dtype and K is wm_op_logits's): logprob[r] = z[r][target[r]] - logsumexp_j z[r][j]
+ * and top_id[r] = argmax_j z[r][j], lowest id on ties.  target[r] < 0: the row is not scored — logprob[r] = 0, top_id[r] is still
+ * written; target[r] >= N: WM_E_ARG.  x [M, K] fp32, K in {128, 384, 512}; logprob, top_id, target: [M].  Known-answer tests. */
+int wm_op_score_logits(float* logprob, int32_t* top_id, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                       const int32_t* target, int M, int N, int K, int dtype);
 /* The absorbed cross-attention of bf16-encoder / fp32-K/V models: per row r and head h, with X = x[utt(r)] and
  * utt(r) = r % q_B when q_B > 0 (prefill rows, position-major; rows = P·q_B) else r,
  *   out[r, h] = Σ_j softmax_j(0.125·q_h[r]·(Wk_h X_j)) (Wv_h X_j) + bv_h,

@@ -210,6 +210,41 @@ public:
         for (int b = 0; b < B; ++b) token_logprobs[b].assign(lp.begin() + (size_t)b * stride, lp.begin() + (size_t)b * stride + n[b]);
         return unpack(toks, n, B, stride);
     }
+    // How likely is this transcript for this audio (wm_score): ids[b] = the decoder prompt followed by the hypothesis (a
+    // trailing eot included if it is to be scored); context_len: per row (empty = 1) how many leading ids are context — reported, not
+    // summed.  Returns per row the log-probability of every id (0 at t = 0) over the raw logits; sum_logprob / avg_logprob [B] over
+    // t >= context_len (avg = -HF loss with labels = -100 on the context); top_ids (optional): the arg-max id per position, lowest id
+    // on ties, -1 at t = 0.  Positions as this mirror's passes (WM_POS_REF).
+    struct ScoreResult {
+        std::vector<std::vector<float>> token_logprobs;
+        std::vector<float> sum_logprob, avg_logprob;
+        std::vector<std::vector<int32_t>> top_ids;  // want_top_ids
+    };
+    ScoreResult score(const float* mels, int B, const std::vector<std::vector<int32_t>>& ids, const std::vector<int32_t>& context_len = {},
+                      bool want_top_ids = false) const {
+        need_model();
+        if ((int)ids.size() != B || (!context_len.empty() && (int)context_len.size() != B)) throw std::runtime_error("score: one id row (and context_len) per clip");
+        int stride = 2;
+        for (const auto& r : ids) stride = std::max(stride, (int)r.size());
+        std::vector<int32_t> tab((size_t)B * stride), len(B), top((size_t)B * stride);
+        for (int b = 0; b < B; ++b) {
+            len[b] = (int32_t)ids[b].size();
+            std::copy(ids[b].begin(), ids[b].end(), tab.begin() + (size_t)b * stride);
+        }
+        std::vector<float> lp((size_t)B * stride);
+        ScoreResult r;
+        r.sum_logprob.assign(B, 0.f);
+        r.avg_logprob.assign(B, 0.f);
+        check(wm_score(model_, mels, 0, B, WM_POS_REF, tab.data(), len.data(), stride, context_len.empty() ? nullptr : context_len.data(), lp.data(),
+                       want_top_ids ? top.data() : nullptr, r.sum_logprob.data(), r.avg_logprob.data()));
+        r.token_logprobs.assign(B, {});
+        if (want_top_ids) r.top_ids.assign(B, {});
+        for (int b = 0; b < B; ++b) {
+            r.token_logprobs[b].assign(lp.begin() + (size_t)b * stride, lp.begin() + (size_t)b * stride + len[b]);
+            if (want_top_ids) r.top_ids[b].assign(top.begin() + (size_t)b * stride, top.begin() + (size_t)b * stride + len[b]);
+        }
+        return r;
+    }
     // openai-whisper's detect_language: per utterance the id of lang_ids with the largest logit after a decoder pass over
     // [sot] alone; probs (optional): [B][lang_ids.size()] softmax over the list, in list order
     std::vector<int32_t> detect_language(const float* mels, int B, const std::vector<int32_t>& lang_ids, int32_t sot,

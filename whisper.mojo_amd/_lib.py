@@ -30,6 +30,7 @@ SYMBOLS = [
     "wm_long_result_quality", "wm_long_result_windows", "wm_long_result_skip_stats",
     "wm_detect_language", "wm_transcribe_lang", "wm_transcribe_submit_lang", "wm_transcribe_wait_lang", "wm_op_lang_detect",
     "wm_transcribe_long_lang", "wm_transcribe_long_pcm_lang",
+    "wm_score", "wm_score_submit", "wm_score_wait", "wm_score_pcm", "wm_op_score_logits", "wm_score_phases",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -118,6 +119,30 @@ def lang_args(lang_ids, vocab):
     if np.unique(ids).size != ids.size:
         raise ValueError("a language id is listed twice")
     return ids.astype(np.int32)
+
+
+def score_args(ids, context_len, B, vocab, n_text_ctx, max_batch):
+    """Checks a score call's arguments on the host (the library refuses the same with WM_E_ARG) -> (table [B, stride] int32,
+    lengths [B], context lengths [B]).  ids: one id list per row (the decoder prompt followed by the hypothesis); context_len: None
+    (= 1), one number, or one per row."""
+    import numpy as np
+    rows = [np.asarray(r, np.int64).reshape(-1) for r in ids]
+    if len(rows) != B:
+        raise ValueError(f"{len(rows)} id rows for {B} clips")
+    if B < 1 or B > max_batch:
+        raise ValueError(f"batch {B} outside [1, max_batch = {max_batch}]")
+    lens = np.asarray([r.size for r in rows], np.int32)
+    if lens.min() < 2 or lens.max() > n_text_ctx:
+        raise ValueError(f"every row needs 2..{n_text_ctx} ids")
+    ctx = np.full(B, 1, np.int32) if context_len is None else np.broadcast_to(np.asarray(context_len, np.int32), (B,)).copy()
+    if (ctx < 1).any() or (ctx > lens - 1).any():
+        raise ValueError("context_len must lie in [1, len - 1] for every row")
+    tab = np.zeros((B, int(lens.max())), np.int32)
+    for b, r in enumerate(rows):
+        if r.min() < 0 or r.max() >= vocab:
+            raise ValueError(f"row {b} holds an id outside the vocabulary [0, {vocab})")
+        tab[b, :r.size] = r
+    return tab, lens, ctx
 
 
 class WhisperMiError(RuntimeError):
@@ -218,6 +243,12 @@ def lib():
     L.wm_transcribe_long_pcm_lang.argtypes = [vp, fp, ip, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), C.POINTER(WmLongOpts), ip, C.c_int, ip,
                                               C.POINTER(vp)]
     L.wm_op_lang_detect.argtypes = [ip, fp, fp, fp, fp, fp, ip] + [C.c_int] * 5
+    L.wm_score.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip, fp, ip, fp, fp]
+    L.wm_score_submit.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip]
+    L.wm_score_wait.argtypes = [vp, C.c_int, fp, ip, fp, fp]
+    L.wm_score_pcm.argtypes = [vp, fp, ip, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip, fp, ip, fp, fp]
+    L.wm_score_phases.argtypes = [vp, C.c_int, fp]
+    L.wm_op_score_logits.argtypes = [fp, ip, fp, fp, fp, fp, ip] + [C.c_int] * 4
     L.wm_long_result_quality.argtypes = [vp, C.c_int, fp, fp]
     L.wm_long_result_windows.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_int64), fp, fp, ip]
     L.wm_long_result_skip_stats.argtypes = [vp, ip]

@@ -243,6 +243,7 @@ struct wm_model {
         bool lp = false;  // the pass computes log-probabilities (wm_transcribe_wait_lp may collect them)
         bool ns = false;  // the pass carries the no-speech probe (wm_transcribe_wait_lp_ns may collect it)
         bool lang = false;  // the pass detects the language (wm_transcribe_wait_lang may collect it)
+        bool score = false;  // a score pass: only wm_score_wait collects it; total = the caller's ids_stride
     } slot_ref[8];
     wm_state* pairs[4] = {};  // 2·B-row states of coalesced pairs
     int last_steps[8] = {-1, -1, -1, -1, -1, -1, -1, -1};  // loop iterations enqueued for each slot's last collected pass
@@ -384,6 +385,21 @@ struct wm_state {
         DevBuf x, ids, col, out, probs;  // [B][d] fp32, [LANG_DETECT_MAX], [B], [B], [B][LANG_DETECT_MAX] (used as [B][n])
         std::vector<int32_t> h_ids, h_col;
     } lg;
+    // transcript scoring (on = the pending pass is a score pass).  Everything here is allocated by the first score pass of
+    // the state and grows on demand, never in state_new: the arenas of a state that is never scored are what they always were.
+    // rows [M][d]: the last layer's residual rows of the real inputs, utterance-major; a: their LayerNorm in the sweep's operand
+    // form; the sweep's partials [M][parts]; per row the target id and the slot of its results in the [B][stride] tables; dst
+    // [Lmax][B]: where a position-major prefill row goes in `rows` (-1: left padding).
+    struct Score {
+        bool on = false;
+        int M = 0, stride = 0, Lmax = 0;
+        DevBuf rows, a, pmax, psum, pidx, ztgt, target, slot, dst, len, ctx, lp, top, sum, avg;
+        std::vector<int32_t> h_tok, h_pos, h_key_lo, h_dst, h_target, h_slot, h_len, h_ctx;
+        // phase marks of the last score pass (wm_score_phases): before the encoder, behind it, behind the prefill chunks, the
+        // LayerNorm, the sweep, the merge + sums.  Created by the first score pass.
+        hipEvent_t ev[6] = {};
+        bool timed = false;  // a completed pass's marks are all recorded
+    } sc;
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -857,6 +873,8 @@ extern "C" void wm_state_free(wm_state* s) {
         if (ln.done) (void)hipEventDestroy(ln.done);
     }
     if (s->enc_done) (void)hipEventDestroy(s->enc_done);
+    for (auto& ev : s->sc.ev)
+        if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : s->chunk_ev)
         if (ev) (void)hipEventDestroy(ev);
     if (s->h_prog) (void)hipHostFree((void*)s->h_prog);
@@ -2080,6 +2098,13 @@ struct RowPrompts {
     const int32_t* len;  // host [B]
     int stride, Lmax;
 };
+struct ScoreAsk {  // a score pass, already validated by score_check
+    const int32_t* ids;  // host [B][stride]
+    const int32_t* len;  // host [B]
+    const int32_t* ctx;  // host [B] or null (= 1)
+    int stride, pos_mode;
+};
+static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a);
 static int rows_setup(wm_model* m, wm_state* s, const RowPrompts* rows) {
     wm_state::Rows& rw = s->rw;
     rw.on = rows != nullptr;
@@ -2103,8 +2128,10 @@ static int rows_setup(wm_model* m, wm_state* s, const RowPrompts* rows) {
 }
 static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, bool allow_poll,
                      const float* mel2 = nullptr, int mel2_on_device = 0, const std::vector<int32_t>* cols = nullptr,
-                     const RowPrompts* rows = nullptr, bool lp = false, NsAsk ns = NsAsk(), LangAsk lang = LangAsk()) {
+                     const RowPrompts* rows = nullptr, bool lp = false, NsAsk ns = NsAsk(), LangAsk lang = LangAsk(), const ScoreAsk* score = nullptr) {
     const wm_dims& c = m->cfg.dims;
+    if (score && (mel2 || cols || rows || lp || ns.token >= 0 || lang.ids || dec_lanes_for(B) != 1))  // (refused by the entry points first)
+        return fail(WM_E_ARG, "a score pass runs alone on a single-lane decode state");
     if (lang.ids && (mel2 || cols || dec_lanes_for(B) != 1 || (!lang.only && !rows)))  // (refused by the entry points first)
         return fail(WM_E_ARG, "language detection needs a single-lane decode state and a per-row-prompt pass without token timestamps");
     if (ns.token >= 0 && (!lp || ns.token >= c.vocab || ns.n_init < 1 || ns.n_init > o->n_prompt))  // (refused by the entry points first)
@@ -2135,6 +2162,8 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
         s->lg.h_col.resize(B);
         for (int b = 0; b < B; ++b) s->lg.h_col[b] = rows ? rows->len[b] - lang.n_init + 1 : 0;
     }
+    s->sc.on = false;
+    s->sc.timed = false;
     s->lp.on = lp;
     if (lp) {
         if (rows)
@@ -2169,6 +2198,12 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
         HIPCHK(hipMemcpyAsync(dst, mel2, (size_t)B1 * mel_floats * 4, hipMemcpyHostToDevice, est));
         mel2_dev = dst;
     }
+    if (score) {
+        for (auto& e : s->sc.ev)
+            if (!e) HIPCHK(hipEventCreate(&e));
+        s->sc.timed = false;
+        HIPCHK(hipEventRecord(s->sc.ev[0], est));
+    }
     const auto tt0 = std::chrono::steady_clock::now();
     trace_mark(est, "state %p encoder start", (void*)s);
     WMCHK(run_encoder(m, s, mel_dev, B, est, mel2_dev, B1, false));
@@ -2189,6 +2224,16 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
         WMCHK(lang_pass(m, s, DecView{ln.b0, ln.nb, ln.st, ln.ctl}, nullptr, 0));
         HIPCHK(hipGetLastError());
         s->has_enc = false;  // cache slot 0 holds the [sot] pass: a new wm_encode is needed before wm_decode_step
+        return 0;
+    }
+    if (score) {  // teacher-forced prefill + the vocabulary side on the lane's stream: no loop, no graph, no pump
+        s->al.on = false;
+        s->shares_chip = !allow_poll;
+        WMCHK(score_pass(m, s, *score));
+        s->pending = true;
+        s->synced = false;
+        s->halves_left = 1;
+        s->pend_total = score->stride;
         return 0;
     }
     WMCHK(align_setup(m, s, o, cols));
@@ -2471,6 +2516,7 @@ static int wait_impl(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_toke
                      float* avg_logprob = nullptr, float* no_speech_prob = nullptr, int32_t* lang_out = nullptr, float* lang_probs = nullptr) {
     wm_model::SlotRef& r = m->slot_ref[slot];
     if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
+    if (r.score) return fail(WM_E_STATE, "this slot holds a score pass (collect it with wm_score_wait)");
     if (lang_out && !r.lang) return fail(WM_E_STATE, "this slot's pass was submitted without language detection (wm_transcribe_submit_lang)");
     if (no_speech_prob && !r.ns) return fail(WM_E_STATE, "this slot's pass was submitted without the no-speech probe (wm_transcribe_submit_lp_ns)");
     if (token_logprobs && !r.lp) return fail(WM_E_STATE, "this slot's pass was submitted without log-probabilities (wm_transcribe_submit_lp)");
@@ -2876,6 +2922,7 @@ extern "C" int wm_transcribe_wait_device(wm_model* m, int slot, int32_t* dev_pac
     if (!m || !dev_packed || slot < 0 || slot >= wm_model::NSLOT || stride <= 0) return fail(WM_E_ARG, "bad argument");
     wm_model::SlotRef& r = m->slot_ref[slot];
     if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
+    if (r.score) return fail(WM_E_STATE, "this slot holds a score pass (collect it with wm_score_wait)");
     if (rows_cap < r.rows) return fail(WM_E_ARG, "rows_cap %d is smaller than the batch (%d)", rows_cap, r.rows);
     if (stride < r.total) return fail(WM_E_ARG, "stride %d is smaller than the pass's ids per utterance (%d)", stride, r.total);
     if (m->held.active && m->held.slot == slot) {
@@ -3023,6 +3070,261 @@ extern "C" int wm_transcribe_pcm_tt(wm_model* m, const float* pcm, const int32_t
     WMCHK(align_cols(m, nf.data(), B, cols));
     WMCHK(frontend_run(m, pcm, n_samples, B, stride));
     return transcribe_impl(m, m->fe.mel.as<float>(), 1, B, o, &cols, tokens_out, n_tokens, token_times);
+}
+
+// ---- transcript scoring --------------------------------------------------------------------------------------------
+// Row b holds ids y[0 .. len_b); its decoder input is y[0 .. len_b - 1), run through the per-row prefill's position-major chunks
+// (left-padded so that the rows end together, key windows as in §16) with no logits launch; after every chunk the real rows of the
+// last layer's residual stream are copied out, utterance-major; then one LayerNorm launch, one vocabulary sweep and the merge.
+// Everything is refused before anything is launched.
+static int score_check(wm_model* m, int B, int pos_mode, const int32_t* ids, const int32_t* ids_len, int ids_stride, const int32_t* context_len) {
+    if (!m || !ids || !ids_len || B <= 0 || ids_stride < 2) return fail(WM_E_ARG, "bad argument");
+    if (pos_mode != WM_POS_REF && pos_mode != WM_POS_HF) return fail(WM_E_ARG, "bad pos_mode");
+    const wm_dims& c = m->cfg.dims;
+    if (B > m->cfg.max_batch) return fail(WM_E_ARG, "batch %d exceeds max_batch %d", B, m->cfg.max_batch);
+    if (dec_lanes_for(B) != 1) return fail(WM_E_ARG, "scoring needs a single-lane decode state");
+    const int cap = std::min(ids_stride, c.n_text_ctx);
+    for (int b = 0; b < B; ++b) {
+        const int L = ids_len[b], cl = context_len ? context_len[b] : 1;
+        if (L < 2 || L > cap) return fail(WM_E_ARG, "ids_len[%d] = %d outside [2, min(ids_stride, n_text_ctx) = %d]", b, L, cap);
+        if (cl < 1 || cl > L - 1) return fail(WM_E_ARG, "context_len[%d] = %d outside [1, ids_len - 1 = %d]", b, cl, L - 1);
+        for (int i = 0; i < L; ++i) {
+            const int32_t id = ids[(size_t)b * ids_stride + i];
+            if (id < 0 || id >= c.vocab) return fail(WM_E_ARG, "id %d of row %d out of range", id, b);
+        }
+    }
+    return 0;
+}
+static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
+    const wm_dims& c = m->cfg.dims;
+    const int B = s->B, T = dec_dtype(m->cfg);
+    const size_t d = c.d_model;
+    wm_state::Score& sc = s->sc;
+    int Lmax = 0, M = 0;
+    for (int b = 0; b < B; ++b) {
+        Lmax = std::max(Lmax, a.len[b] - 1);
+        M += a.len[b] - 1;
+    }
+    sc.M = M;
+    sc.Lmax = Lmax;
+    sc.stride = a.stride;
+    sc.h_tok.assign((size_t)Lmax * B, 0);
+    sc.h_pos.assign((size_t)Lmax * B, 0);
+    sc.h_dst.assign((size_t)Lmax * B, -1);
+    sc.h_key_lo.assign(B, 0);
+    sc.h_target.assign(M, -1);
+    sc.h_slot.assign(M, 0);
+    sc.h_len.assign(a.len, a.len + B);
+    sc.h_ctx.assign(B, 1);
+    for (int b = 0, base = 0; b < B; ++b) {
+        const int n_in = a.len[b] - 1, pad = Lmax - n_in, cl = a.ctx ? a.ctx[b] : 1;
+        const int32_t* y = a.ids + (size_t)b * a.stride;
+        sc.h_ctx[b] = cl;
+        sc.h_key_lo[b] = pad;
+        for (int t = 0; t < Lmax; ++t) {
+            const size_t o = (size_t)t * B + b;
+            if (t < pad) {  // a dead slot in front of a shorter row: the row's first id at position 0, never attended to (§16)
+                sc.h_tok[o] = y[0];
+                continue;
+            }
+            const int i = t - pad;
+            sc.h_tok[o] = y[i];
+            // WM_POS_REF: the reference's loop feeds position current_len - 1 (whisper.mojo:217), as set_rows_step_kernel applies it
+            sc.h_pos[o] = a.pos_mode == WM_POS_REF && i >= cl ? i - 1 : i;
+            sc.h_dst[o] = base + i;
+            sc.h_target[base + i] = y[i + 1];
+            sc.h_slot[base + i] = b * a.stride + i + 1;
+        }
+        base += n_in;
+    }
+    int spp = 0;
+    const size_t parts = score_parts(c.vocab, T, &spp), ctx = c.n_text_ctx;
+    WMCHK(grow(s->rw.key_lo, (size_t)B * 4));
+    WMCHK(grow(s->tok_rows, (size_t)B * ctx * 4));
+    WMCHK(grow(s->pos_rows, (size_t)B * ctx * 4));
+    WMCHK(grow(sc.rows, (size_t)M * d * 4));
+    WMCHK(grow(sc.a, score_operand_bytes(M, c.d_model, T)));
+    for (DevBuf* p : {&sc.pmax, &sc.psum, &sc.pidx}) WMCHK(grow(*p, (size_t)M * parts * 4));
+    for (DevBuf* p : {&sc.ztgt, &sc.target, &sc.slot}) WMCHK(grow(*p, (size_t)M * 4));
+    WMCHK(grow(sc.dst, (size_t)B * ctx * 4));
+    for (DevBuf* p : {&sc.len, &sc.ctx, &sc.sum, &sc.avg}) WMCHK(grow(*p, (size_t)B * 4));
+    for (DevBuf* p : {&sc.lp, &sc.top}) WMCHK(grow(*p, (size_t)B * a.stride * 4));
+    s->rw.on = true;  // the prefill's self-attention sweeps each row's own key window
+    s->rw.Lmax = Lmax;
+    sc.on = true;
+    const wm_state::Lane& ln = s->lanes[0];
+    const DecView v{ln.b0, ln.nb, ln.st, ln.ctl};
+    HIPCHK(hipEventRecord(s->enc_done, s->enc_stream ? s->enc_stream : m->stream));
+    HIPCHK(hipStreamWaitEvent(v.st, s->enc_done, 0));
+    auto up = [&](DevBuf& dst, const std::vector<int32_t>& h) { return hipMemcpyAsync(dst.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, v.st); };
+    HIPCHK(up(s->tok_rows, sc.h_tok));
+    HIPCHK(up(s->pos_rows, sc.h_pos));
+    HIPCHK(up(s->rw.key_lo, sc.h_key_lo));
+    HIPCHK(up(sc.dst, sc.h_dst));
+    HIPCHK(up(sc.target, sc.h_target));
+    HIPCHK(up(sc.slot, sc.h_slot));
+    HIPCHK(up(sc.len, sc.h_len));
+    HIPCHK(up(sc.ctx, sc.h_ctx));
+    HIPCHK(hipMemsetAsync(sc.lp.p, 0, (size_t)B * a.stride * 4, v.st));     // logprob[b][0] and the tails: 0
+    HIPCHK(hipMemsetAsync(sc.top.p, 0xff, (size_t)B * a.stride * 4, v.st));  // top_id[b][0] and the tails: -1
+    HIPCHK(hipEventRecord(sc.ev[1], v.st));
+    trace_mark(v.st, "state %p score prefill start", (void*)s);
+    for (int t0 = 0; t0 < Lmax; t0 += wm_state::PREFILL_MAX) {
+        const int P = std::min<int>(wm_state::PREFILL_MAX, Lmax - t0);
+        launch_set_step(v.ctl, t0, 1, nullptr, 0, nullptr, 0, v.nb, v.st);
+        WMCHK(decode_core(m, s, v, false, false, nullptr, P, true, nullptr, false, t0));
+        launch_score_collect(s->dx.as<float>(), sc.rows.as<float>(), sc.dst.as<int>() + (size_t)t0 * B, P * B, c.d_model, v.st);
+    }
+    HIPCHK(hipEventRecord(sc.ev[2], v.st));
+    trace_mark(v.st, "state %p score prefill end", (void*)s);
+    ScoreParams q{};
+    q.x = sc.rows.as<float>();
+    q.ln_g = m->dec_ln_g.as<float>();
+    q.ln_b = m->dec_ln_b.as<float>();
+    q.emb = T == WM_F32 ? m->tok_emb_f.p : m->tok_emb_t.p;
+    q.a = sc.a.p;
+    q.target = sc.target.as<int>();
+    q.slot = sc.slot.as<int>();
+    q.M = M;
+    q.N = c.vocab;
+    q.K = c.d_model;
+    q.pmax = sc.pmax.as<float>();
+    q.psum = sc.psum.as<float>();
+    q.pidx = sc.pidx.as<int>();
+    q.ztgt = sc.ztgt.as<float>();
+    q.logprob = sc.lp.as<float>();
+    q.top_id = sc.top.as<int>();
+    int lrc = 0;
+    DISPATCH_DT(T, TT, lrc = launch_score<TT>(q, v.st, sc.ev + 3));
+    LCHK(lrc);
+    launch_score_sums(sc.lp.as<float>(), a.stride, sc.len.as<int>(), sc.ctx.as<int>(), sc.sum.as<float>(), sc.avg.as<float>(), B, v.st);
+    HIPCHK(hipEventRecord(sc.ev[5], v.st));
+    trace_mark(v.st, "state %p score end", (void*)s);
+    HIPCHK(hipEventRecord(ln.done, ln.st));
+    HIPCHK(hipGetLastError());
+    s->enq_rc = 0;
+    s->enq_done.store(true);
+    return 0;
+}
+static int score_collect(wm_model* m, wm_state* s, float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob) {
+    if (!s || !s->pending || !s->sc.on) return fail(WM_E_STATE, "no score pass was submitted on this slot");
+    HIPCHK(hipSetDevice(m->device));
+    const hipError_t e = hipEventSynchronize(s->lanes[0].done);
+    s->pending = false;  // afterwards the state holds no usable pass, exactly as after wm_transcribe
+    s->has_enc = false;
+    s->sc.on = false;
+    s->rw.on = false;
+    HIPCHK(e);
+    s->sc.timed = true;
+    const size_t n = (size_t)s->B * s->sc.stride * 4;
+    HIPCHK(hipMemcpy(token_logprobs, s->sc.lp.p, n, hipMemcpyDeviceToHost));
+    if (top_ids) HIPCHK(hipMemcpy(top_ids, s->sc.top.p, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sum_logprob, s->sc.sum.p, (size_t)s->B * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(avg_logprob, s->sc.avg.p, (size_t)s->B * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+static int score_impl(wm_model* m, const float* mel, int mel_on_device, int B, const ScoreAsk& a, float* token_logprobs, int32_t* top_ids,
+                      float* sum_logprob, float* avg_logprob) {
+    WMCHK(flush_held(m));
+    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, nullptr, true, nullptr, 0, nullptr, nullptr, false, NsAsk(), LangAsk(), &a));
+    m->align_ref[0] = wm_model::AlignRef{};
+    return score_collect(m, m->cached, token_logprobs, top_ids, sum_logprob, avg_logprob);
+}
+extern "C" int wm_score(wm_model* m, const float* mel, int mel_on_device, int B, int pos_mode, const int32_t* ids, const int32_t* ids_len,
+                        int ids_stride, const int32_t* context_len, float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob) {
+    if (!m || !mel || !token_logprobs || !sum_logprob || !avg_logprob) return fail(WM_E_ARG, "bad argument");
+    WMCHK(score_check(m, B, pos_mode, ids, ids_len, ids_stride, context_len));
+    return score_impl(m, mel, mel_on_device, B, ScoreAsk{ids, ids_len, context_len, ids_stride, pos_mode}, token_logprobs, top_ids, sum_logprob,
+                      avg_logprob);
+}
+// (never held for a coalesce = 2 partner: a score pass runs alone)
+extern "C" int wm_score_submit(wm_model* m, int slot, const float* mel, int mel_on_device, int B, int pos_mode, const int32_t* ids,
+                               const int32_t* ids_len, int ids_stride, const int32_t* context_len) {
+    if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
+    WMCHK(score_check(m, B, pos_mode, ids, ids_len, ids_stride, context_len));
+    wm_model::SlotRef& r = m->slot_ref[slot];
+    if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    WMCHK(flush_held(m));
+    const ScoreAsk a{ids, ids_len, context_len, ids_stride, pos_mode};
+    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, nullptr, false, nullptr, 0, nullptr, nullptr, false, NsAsk(), LangAsk(), &a));
+    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, ids_stride, false};
+    r.score = true;
+    return 0;
+}
+extern "C" int wm_score_wait(wm_model* m, int slot, float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob) {
+    if (!m || !token_logprobs || !sum_logprob || !avg_logprob || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
+    wm_model::SlotRef& r = m->slot_ref[slot];
+    if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
+    if (!r.score) return fail(WM_E_STATE, "this slot holds a transcribe pass (collect it with wm_transcribe_wait)");
+    if (m->held.active && m->held.slot == slot) WMCHK(flush_held(m));
+    const int rc = score_collect(m, r.st, token_logprobs, top_ids, sum_logprob, avg_logprob);
+    m->align_ref[slot] = wm_model::AlignRef{};
+    r = wm_model::SlotRef{};
+    return rc;
+}
+extern "C" int wm_score_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, int pos_mode, const int32_t* ids,
+                            const int32_t* ids_len, int ids_stride, const int32_t* context_len, float* token_logprobs, int32_t* top_ids,
+                            float* sum_logprob, float* avg_logprob) {
+    if (!m || !token_logprobs || !sum_logprob || !avg_logprob) return fail(WM_E_ARG, "bad argument");
+    WMCHK(score_check(m, B, pos_mode, ids, ids_len, ids_stride, context_len));
+    WMCHK(frontend_run(m, pcm, n_samples, B, stride));  // same stream order as the encoder: no host sync
+    return score_impl(m, m->fe.mel.as<float>(), 1, B, ScoreAsk{ids, ids_len, context_len, ids_stride, pos_mode}, token_logprobs, top_ids,
+                      sum_logprob, avg_logprob);
+}
+extern "C" int wm_score_phases(wm_model* m, int slot, float* ms) {
+    if (!m || !ms || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
+    wm_state* s = *slot_state(m, slot);
+    if (!s || !state_is_live(s) || s->pending || !s->sc.timed) return fail(WM_E_STATE, "no completed score pass on this slot's state");
+    HIPCHK(hipSetDevice(m->device));
+    for (int k = 0; k < 5; ++k) HIPCHK(hipEventElapsedTime(ms + k, s->sc.ev[k], s->sc.ev[k + 1]));
+    return 0;
+}
+// The score pass's vocabulary side alone (LayerNorm, sweep, merge) on host operands: known-answer tests.
+extern "C" int wm_op_score_logits(float* logprob, int32_t* top_id, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                                  const int32_t* target, int M, int N, int K, int dtype) {
+    if (!logprob || !top_id || !x || !ln_g || !ln_b || !emb || !target || M <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
+    if (K != 128 && K != 384 && K != 512) return fail(WM_E_ARG, "K must be 128, 384 or 512 (the logits kernels' d_model)");
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    for (int r = 0; r < M; ++r)
+        if (target[r] >= N) return fail(WM_E_ARG, "target[%d] = %d is not a vocabulary id", r, target[r]);
+    TmpDev t;
+    t.bufs.reserve(16);
+    const size_t parts = score_parts(N, dtype);
+    DevBuf &dx = t.add(), &g = t.add(), &be = t.add(), &w = t.add(), &a = t.add(), &pm = t.add(), &ps = t.add(), &pi = t.add(), &zt = t.add(),
+           &tg = t.add(), &lp = t.add(), &top = t.add();
+    WMCHK(upload(dx, x, (size_t)M * K, WM_F32));
+    WMCHK(upload(g, ln_g, K, WM_F32));
+    WMCHK(upload(be, ln_b, K, WM_F32));
+    WMCHK(upload(w, emb, (size_t)N * K, dtype));
+    WMCHK(a.alloc(score_operand_bytes(M, K, dtype)));
+    for (DevBuf* p : {&pm, &ps, &pi}) WMCHK(p->alloc((size_t)M * parts * 4, true));
+    for (DevBuf* p : {&zt, &lp, &top}) WMCHK(p->alloc((size_t)M * 4, true));
+    WMCHK(tg.alloc((size_t)M * 4));
+    HIPCHK(hipMemcpy(tg.p, target, (size_t)M * 4, hipMemcpyHostToDevice));
+    ScoreParams q{};
+    q.x = dx.as<float>();
+    q.ln_g = g.as<float>();
+    q.ln_b = be.as<float>();
+    q.emb = w.p;
+    q.a = a.p;
+    q.target = tg.as<int>();
+    q.M = M;
+    q.N = N;
+    q.K = K;
+    q.pmax = pm.as<float>();
+    q.psum = ps.as<float>();
+    q.pidx = pi.as<int>();
+    q.ztgt = zt.as<float>();
+    q.logprob = lp.as<float>();
+    q.top_id = top.as<int>();
+    int lrc = 0;
+    DISPATCH_DT(dtype, TT, lrc = launch_score<TT>(q, nullptr));
+    LCHK(lrc);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(logprob, lp.p, (size_t)M * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(top_id, top.p, (size_t)M * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // ---- sequential long-form transcription (thresholds and no-speech window skipping: §18) -----------------------------

@@ -354,6 +354,33 @@ struct LangDetectParams {
     const int* patch_col;  // [B]
 };
 template <typename TW> void launch_lang_detect(const LangDetectParams& p, hipStream_t st);
+// ---- transcript scoring (kernels_score.hip) ------------------------------------------------------------------
+// The vocabulary side of a teacher-forced pass over M hidden rows: final LayerNorm once per row into the sweep's operand form (a),
+// the sweep (per (row, part): max, Σ exp(v − max), arg-max; the target's logit), the merge.  logprob[slot[r]] =
+// logit[r][target[r]] − logsumexp(logit[r]) (0 when target[r] < 0), top_id[slot[r]] = the row's arg-max, lowest id on ties.
+struct ScoreParams {
+    const float* x;  // [M][K] residual rows (before the final LayerNorm)
+    const float* ln_g;
+    const float* ln_b;
+    const void* emb;    // [N][K] token embedding in the decoder's operand dtype
+    void* a;            // score_operand_bytes(M, K, dtype) of scratch
+    const int* target;  // [M]
+    const int* slot;    // [M] or null (= the row index)
+    int M, N, K;
+    float* pmax;  // [M][score_parts(N, dtype)] each
+    float* psum;
+    int* pidx;
+    float* ztgt;  // [M]
+    float* logprob;
+    int* top_id;  // or null
+};
+int score_parts(int N, int dtype, int* stages_per_part = nullptr);  // dtype: WM_F32 = 0 / 16-bit; never a function of M
+size_t score_operand_bytes(int M, int K, int dtype);
+// WM_LAUNCH_*: LayerNorm, sweep, merge.  ev non-null: ev[0] is recorded behind the LayerNorm, ev[1] behind the sweep (phase timing)
+template <typename TW> int launch_score(const ScoreParams& p, hipStream_t st, hipEvent_t* ev = nullptr);
+// rows[r] -> out[dst[r]] for the n_rows rows of a prefill chunk whose dst[r] >= 0 (d floats each)
+void launch_score_collect(const float* rows, float* out, const int* dst, int n_rows, int d, hipStream_t st);
+void launch_score_sums(const float* logprob, int stride, const int* len, const int* ctx, float* sum, float* avg, int B, hipStream_t st);
 // rows of the gather buffer of SURVEY §8e: dst[r] = [n_tokens[r], ids of row r zero-padded to `stride`] for r < rows; rows in
 // [rows, rows_cap) are zeroed (ragged shards gather a fixed row count per rank)
 void launch_pack_tokens(const int* out_tokens, const int* n_tokens, int out_stride, int rows, int rows_cap, int stride, int* dst, hipStream_t st);

@@ -55,6 +55,21 @@ def transcribe_audio(model, audios: Sequence[np.ndarray], prompt: Sequence[int] 
     return [toks[b, :cnt[b]].tolist() for b in range(len(audios))]
 
 
+def score_audio(model, audios: Sequence[np.ndarray], ids, context_len=None, return_top_ids: bool = False):
+    """PCM in, Whisper.score out (wm_score_pcm: the mel never leaves the GPU).  Arguments and result as Whisper.score."""
+    buf, n, stride = _pack(audios)
+    B = len(audios)
+    tab, lens, ctx = _lib.score_args(ids, context_len, B, model.config.vocab_size, model.config.n_text_ctx, model.max_batch)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    lps, top = np.zeros(tab.shape, np.float32), np.full(tab.shape, -1, np.int32)
+    sm, avg = np.zeros(B, np.float32), np.zeros(B, np.float32)
+    _lib.check(_lib.lib().wm_score_pcm(model._h, buf.ctypes.data_as(fp), n.ctypes.data_as(ip), B, stride, model.pos_mode,
+                                       tab.ctypes.data_as(ip), lens.ctypes.data_as(ip), tab.shape[1], ctx.ctypes.data_as(ip),
+                                       lps.ctypes.data_as(fp), top.ctypes.data_as(ip) if return_top_ids else None,
+                                       sm.ctypes.data_as(fp), avg.ctypes.data_as(fp)))
+    return model._score_out(tab, lens, lps, top, sm, avg, return_top_ids)
+
+
 def log_mel_long(model, audios: Sequence[np.ndarray]):
     """Log-mel of audio of any length, HF WhisperFeatureExtractor(truncation=False, padding="longest",
     return_attention_mask=True): (features [B, n_mels, longest // 160] float32, n_frames [B] = the mask's ones)."""

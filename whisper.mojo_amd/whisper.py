@@ -150,6 +150,7 @@ class Whisper:
         self._h = None
         self._caches = weakref.WeakSet()  # live KVCaches of the loaded model
         self._n_align = 0  # alignment heads set on the loaded model (set_alignment_heads)
+        self._score_pending = {}  # slot -> (id table, lengths, mel keep-alive) of a submitted score pass (score_submit / score_wait)
         self.encoder = WhisperEncoder(self)
         self.decoder = WhisperDecoder(self)
 
@@ -182,6 +183,7 @@ class Whisper:
                 c._invalidate()
             self._caches.clear()
             self._pending = {}
+            self._score_pending = {}
             _lib.lib().wm_model_free(h)  # also frees every state (KVCache arena, pipeline slot) created on it
 
     def __del__(self):
@@ -580,6 +582,60 @@ class Whisper:
             self._align_shape[slot] = (B, tt[0], tt[1])
             return ids, self._split_times(times, n, B)
         return ids
+
+    # ---- transcript scoring -------------------------------------------------------------------------------------
+    def _score_out(self, tab, lens, lps, top, sm, avg, return_top_ids):
+        B = len(lens)
+        out = ([lps[b, :lens[b]].tolist() for b in range(B)], (sm, avg))
+        return out + ([top[b, :lens[b]].tolist() for b in range(B)],) if return_top_ids else out
+
+    def score(self, mel, ids, context_len=None, return_top_ids: bool = False):
+        """How likely is this transcript for this audio: teacher-forced log-probabilities of the given ids (wm_score).
+        ids: one list per clip, the decoder prompt followed by the hypothesis (a trailing eot included if it is to be scored);
+        context_len: how many leading ids are context — reported but not summed — None = 1, a number, or one per row.
+        -> (token_logprobs, (sum_logprob [B], avg_logprob [B])) (+ top_ids when asked): token_logprobs[b][t] = log p(ids[b][t] |
+        ids[b][:t], audio) over the raw logits (HF model(..., decoder_input_ids=ids[:, :-1]).logits.float().log_softmax(-1)), 0 at
+        t = 0; top_ids[b][t] the arg-max id at that position (lowest id on ties, -1 at t = 0); avg_logprob = -HF loss of the row with
+        labels = -100 on the context.  Positions follow self.pos_mode."""
+        ptr, on_dev, B, keep = _mel_arg(mel, self.config)
+        tab, lens, ctx = _lib.score_args(ids, context_len, B, self.config.vocab_size, self.config.n_text_ctx, self.max_batch)
+        if self._h is None:
+            raise _lib.WhisperMiError("model not loaded")
+        lps, top = np.zeros(tab.shape, np.float32), np.full(tab.shape, -1, np.int32)
+        sm, avg = np.zeros(B, np.float32), np.zeros(B, np.float32)
+        _lib.check(_lib.lib().wm_score(self._h, ptr, on_dev, B, self.pos_mode, _ip(tab), _ip(lens), tab.shape[1], _ip(ctx), _fp(lps),
+                                       _ip(top) if return_top_ids else None, _fp(sm), _fp(avg)))
+        return self._score_out(tab, lens, lps, top, sm, avg, return_top_ids)
+
+    def score_submit(self, mel, ids, slot: int = 0, context_len=None):
+        """Pipelined Whisper.score on one of the eight slots; collect with score_wait.  Everything is validated before the call and
+        the slot's record is written only once the library accepted the pass."""
+        ptr, on_dev, B, keep = _mel_arg(mel, self.config)
+        tab, lens, ctx = _lib.score_args(ids, context_len, B, self.config.vocab_size, self.config.n_text_ctx, self.max_batch)
+        if self._h is None:
+            raise _lib.WhisperMiError("model not loaded")
+        if not 0 <= int(slot) < 8:
+            raise ValueError("slot must be 0..7")
+        _lib.check(_lib.lib().wm_score_submit(self._h, slot, ptr, on_dev, B, self.pos_mode, _ip(tab), _ip(lens), tab.shape[1], _ip(ctx)))
+        self._score_pending[slot] = (tab, lens, keep)
+
+    def score_wait(self, slot: int = 0, return_top_ids: bool = False):
+        pend = self._score_pending
+        if slot not in pend:
+            raise _lib.WhisperMiError(f"no score pass was submitted on slot {slot}")
+        tab, lens, _keep = pend[slot]
+        B = len(lens)
+        lps, top = np.zeros(tab.shape, np.float32), np.full(tab.shape, -1, np.int32)
+        sm, avg = np.zeros(B, np.float32), np.zeros(B, np.float32)
+        _lib.check(_lib.lib().wm_score_wait(self._h, slot, _fp(lps), _ip(top) if return_top_ids else None, _fp(sm), _fp(avg)))
+        del pend[slot]  # only a collected pass leaves the table
+        return self._score_out(tab, lens, lps, top, sm, avg, return_top_ids)
+
+    def score_phases(self, slot: int = 0) -> dict:
+        """GPU milliseconds of the phases of the slot's last collected score pass (wm_score_phases; slot 0 also serves score)."""
+        ms = np.zeros(5, np.float32)
+        _lib.check(_lib.lib().wm_score_phases(self._h, slot, _fp(ms)))
+        return dict(zip(("encoder", "prefill", "ln", "sweep", "merge"), (float(v) for v in ms)))
 
     def transcribe_wait_device(self, slot: int, packed) -> None:
         """transcribe_wait with the ids left on the GPU as the multi-GPU gather buffer: `packed` is a torch int32 CUDA tensor

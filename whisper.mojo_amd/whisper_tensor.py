@@ -235,6 +235,25 @@ def logits_argmax(x, ln_g, ln_b, emb, dtype=DT_F32, mask=None, ranges=None, time
     return logits, ids
 
 
+def score_logits(x, ln_g, ln_b, emb, target, dtype=DT_F32):
+    """The score pass's vocabulary side alone (wm_op_score_logits): (logprob [M], top_id [M]) with logprob[r] =
+    z[r][target[r]] - logsumexp(z[r]) over z = layer_norm(x)·embᵀ (0 where target[r] < 0) and top_id[r] = argmax z[r], lowest id on
+    ties.  No logits matrix is formed."""
+    f = lambda a: np.ascontiguousarray(a, np.float32)
+    x, emb = f(x), f(emb)
+    g, b = f(ln_g).ravel(), f(ln_b).ravel()
+    tg = np.ascontiguousarray(target, np.int32).ravel()
+    if x.ndim != 2 or emb.ndim != 2 or emb.shape[1] != x.shape[1] or g.size != x.shape[1] or b.size != x.shape[1] or tg.size != x.shape[0]:
+        raise ValueError("x must be [M, K], emb [N, K], ln_g / ln_b [K], target [M]")
+    if tg.max() >= emb.shape[0]:
+        raise ValueError("a target is not a vocabulary id")
+    M, K = x.shape
+    lp, top = np.zeros(M, np.float32), np.zeros(M, np.int32)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    _lib.check(_lib.lib().wm_op_score_logits(_fp(lp), ip(top), _fp(x), _fp(g), _fp(b), _fp(emb), ip(tg), M, emb.shape[0], K, dtype))
+    return lp, top
+
+
 def no_speech(x, ln_g, ln_b, emb, token: int, dtype=DT_F32):
     """The no-speech probe's launches (wm_op_no_speech): (prob [B], lse [B]) — softmax(layer_norm(x)·embᵀ)[token] over
     all N columns (no mask, no ranges) and the row's logsumexp, on the kernel variant logits_argmax(return_logprobs=True) picks."""
