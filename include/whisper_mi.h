@@ -316,6 +316,41 @@ int wm_alignment_weights(wm_model* m, int slot, float* out);
 /* Known-answer test of the normalisation + DTW stage: weights [n_sel][R][F] -> times [n_prompt + R + 1].  R <= 447. */
 int wm_op_token_times(float* times, const float* weights, int n_sel, int R, int F, int n_prompt);
 
+/* ---- forced alignment -----------------------------------------------------------------------------------------
+ * When each id of a GIVEN transcript was spoken.  Rows, ids, context_len and pos_mode exactly as wm_score takes and validates them.
+ * The decoder input of row b is y[0 .. len_b - 1); the cross-attention rows that count are the inputs t in [context_len[b], len_b - 1),
+ * R_b = len_b - context_len[b] - 1 of them (0 is allowed); n_frames as the _tt calls (NULL = every column).  token_times: host
+ * [B, ids_stride] fp32, what HF's _extract_token_timestamps gives for the cross-attentions of model(input_features,
+ * decoder_input_ids = y[:, :-1]) with sequences = y and num_input_ids = context_len[b]: 0 for the context, the R_b jump times, the
+ * last id repeats the last one, 0 past len_b.  Aligning the ids of a greedy _tt pass with context_len = its prompt length gives that
+ * pass's own times.  token_logprobs / sum_logprob / avg_logprob: NULL as a group, or what wm_score writes for the same inputs, bit for
+ * bit (the vocabulary side then runs as well).  State rules as wm_score: single-lane states, never coalesced, the slot's wait families
+ * refuse each other's passes with WM_E_STATE (the pass stays pending).  WM_E_STATE without alignment heads; WM_E_ARG as wm_score and
+ * as the _tt calls for n_frames; all before anything is launched.  wm_alignment_weights serves the slot's last align pass with
+ * out [B][n_sel][L][n_audio_ctx], L = max_b R_b. */
+int wm_align(wm_model* m, const float* mel, int mel_on_device, int B, int pos_mode, const int32_t* ids, const int32_t* ids_len, int ids_stride,
+             const int32_t* context_len, const int32_t* n_frames, float* token_times, float* token_logprobs, float* sum_logprob,
+             float* avg_logprob);
+int wm_align_submit(wm_model* m, int slot, const float* mel, int mel_on_device, int B, int pos_mode, const int32_t* ids, const int32_t* ids_len,
+                    int ids_stride, const int32_t* context_len, const int32_t* n_frames, int want_logprobs);
+/* token_logprobs non-NULL on a pass submitted with want_logprobs = 0: WM_E_STATE, the pass stays pending */
+int wm_align_wait(wm_model* m, int slot, float* token_times, float* token_logprobs, float* sum_logprob, float* avg_logprob);
+/* PCM in: front end + wm_align, n_frames[b] = min(2·n_audio_ctx, ceil(n_samples[b] / 160)) as wm_transcribe_pcm_tt */
+int wm_align_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, int pos_mode, const int32_t* ids,
+                 const int32_t* ids_len, int ids_stride, const int32_t* context_len, float* token_times, float* token_logprobs,
+                 float* sum_logprob, float* avg_logprob);
+/* Diagnostics (tools/align_cost.py): ms[6] = wm_score_phases' five phases of the slot's last collected align pass (LayerNorm, sweep and
+ * merge are 0 when it ran without log-probs) and [5] the align chain. */
+int wm_align_phases(wm_model* m, int slot, float* ms);
+/* Known-answer tests.  wm_op_dec_linear_capmap: LNx -> cross q with the capture by row map — B input rows, cap [cap_dst][cap_nsel][64]
+ * in and out, cap_map [B] in [-1, cap_dst): row r's selected heads go to cap row cap_map[r], -1 stores nothing.
+ * wm_op_token_times_rows: n_tab weight tables [n_tab][n_sel][L][T] (table b uses its R[b] x F[b] corner) through the normalisation and the
+ * DTW in one launch each -> times [n_tab][out_stride], table b's times starting at id row0[b]. */
+int wm_op_dec_linear_capmap(float* out, float* cap, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
+                            int B, int N, int K, int dtype, const int8_t* cap_sel, int cap_nsel, const int32_t* cap_map, int cap_dst);
+int wm_op_token_times_rows(float* times, const float* weights, int n_tab, int n_sel, int L, int T, const int32_t* R, const int32_t* F,
+                           const int32_t* row0, int out_stride);
+
 /* ---- log-mel front end --------------------------------------------------------------------------
  * Replaces the reference's call to HF WhisperProcessor (export_weights.py:100-116): 16 kHz mono PCM -> pad / trim to the
  * 30 s window -> 400-point Hann STFT (hop 160, reflect padding) -> 80 slaney mel bands -> log10 -> clamp to max-8 ->

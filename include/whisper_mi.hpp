@@ -245,6 +245,38 @@ public:
         }
         return r;
     }
+    // When each id of a given transcript was spoken (wm_align): ids / context_len as score(); n_frames: per row the mel frames
+    // of real audio (empty = the whole window).  Returns per row one time per id: 0 for the context, then HF's _extract_token_timestamps
+    // over the teacher-forced cross-attentions.  scores (optional): what score() returns for the same inputs, from the same pass.
+    std::vector<std::vector<float>> align(const float* mels, int B, const std::vector<std::vector<int32_t>>& ids,
+                                          const std::vector<int32_t>& context_len = {}, const std::vector<int32_t>& n_frames = {},
+                                          ScoreResult* scores = nullptr) const {
+        need_model();
+        if ((int)ids.size() != B || (!context_len.empty() && (int)context_len.size() != B) || (!n_frames.empty() && (int)n_frames.size() != B))
+            throw std::runtime_error("align: one id row (and context_len, n_frames) per clip");
+        int stride = 2;
+        for (const auto& r : ids) stride = std::max(stride, (int)r.size());
+        std::vector<int32_t> tab((size_t)B * stride), len(B);
+        for (int b = 0; b < B; ++b) {
+            len[b] = (int32_t)ids[b].size();
+            std::copy(ids[b].begin(), ids[b].end(), tab.begin() + (size_t)b * stride);
+        }
+        std::vector<float> tm((size_t)B * stride), lp(scores ? (size_t)B * stride : 0);
+        if (scores) {
+            scores->sum_logprob.assign(B, 0.f);
+            scores->avg_logprob.assign(B, 0.f);
+        }
+        check(wm_align(model_, mels, 0, B, WM_POS_REF, tab.data(), len.data(), stride, context_len.empty() ? nullptr : context_len.data(),
+                       n_frames.empty() ? nullptr : n_frames.data(), tm.data(), scores ? lp.data() : nullptr,
+                       scores ? scores->sum_logprob.data() : nullptr, scores ? scores->avg_logprob.data() : nullptr));
+        std::vector<std::vector<float>> times(B);
+        if (scores) scores->token_logprobs.assign(B, {});
+        for (int b = 0; b < B; ++b) {
+            times[b].assign(tm.begin() + (size_t)b * stride, tm.begin() + (size_t)b * stride + len[b]);
+            if (scores) scores->token_logprobs[b].assign(lp.begin() + (size_t)b * stride, lp.begin() + (size_t)b * stride + len[b]);
+        }
+        return times;
+    }
     // openai-whisper's detect_language: per utterance the id of lang_ids with the largest logit after a decoder pass over
     // [sot] alone; probs (optional): [B][lang_ids.size()] softmax over the list, in list order
     std::vector<int32_t> detect_language(const float* mels, int B, const std::vector<int32_t>& lang_ids, int32_t sot,

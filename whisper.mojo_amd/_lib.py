@@ -31,6 +31,7 @@ SYMBOLS = [
     "wm_detect_language", "wm_transcribe_lang", "wm_transcribe_submit_lang", "wm_transcribe_wait_lang", "wm_op_lang_detect",
     "wm_transcribe_long_lang", "wm_transcribe_long_pcm_lang",
     "wm_score", "wm_score_submit", "wm_score_wait", "wm_score_pcm", "wm_op_score_logits", "wm_score_phases",
+    "wm_align", "wm_align_submit", "wm_align_wait", "wm_align_pcm", "wm_align_phases", "wm_op_dec_linear_capmap", "wm_op_token_times_rows",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -145,6 +146,23 @@ def score_args(ids, context_len, B, vocab, n_text_ctx, max_batch):
     return tab, lens, ctx
 
 
+def align_args(ids, context_len, n_frames, B, vocab, n_text_ctx, max_batch, n_audio_ctx):
+    """Checks an align call's arguments on the host (the library refuses the same with WM_E_ARG) -> (table, lengths, context
+    lengths, n_frames [B] int32 or None).  ids / context_len: as score_args; n_frames: None (every column) or one count of real mel
+    frames per row in [2, 2 * n_audio_ctx].  (Missing alignment heads are the library's to refuse: WM_E_STATE.)"""
+    import numpy as np
+    tab, lens, ctx = score_args(ids, context_len, B, vocab, n_text_ctx, max_batch)
+    nf = None
+    if n_frames is not None:
+        nf = np.ascontiguousarray(np.asarray(n_frames, np.int64).reshape(-1))
+        if nf.size != B:
+            raise ValueError(f"n_frames needs one entry per row ({B}), got {nf.size}")
+        if nf.min() < 2 or nf.max() > 2 * n_audio_ctx:
+            raise ValueError(f"n_frames must lie in [2, {2 * n_audio_ctx}]")
+        nf = nf.astype(np.int32)
+    return tab, lens, ctx, nf
+
+
 class WhisperMiError(RuntimeError):
     pass
 
@@ -249,6 +267,13 @@ def lib():
     L.wm_score_pcm.argtypes = [vp, fp, ip, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip, fp, ip, fp, fp]
     L.wm_score_phases.argtypes = [vp, C.c_int, fp]
     L.wm_op_score_logits.argtypes = [fp, ip, fp, fp, fp, fp, ip] + [C.c_int] * 4
+    L.wm_align.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip, ip, fp, fp, fp, fp]
+    L.wm_align_submit.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip, ip, C.c_int]
+    L.wm_align_wait.argtypes = [vp, C.c_int, fp, fp, fp, fp]
+    L.wm_align_pcm.argtypes = [vp, fp, ip, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip, fp, fp, fp, fp]
+    L.wm_align_phases.argtypes = [vp, C.c_int, fp]
+    L.wm_op_dec_linear_capmap.argtypes = [fp] * 7 + [C.c_int] * 4 + [C.POINTER(C.c_int8), C.c_int, ip, C.c_int]
+    L.wm_op_token_times_rows.argtypes = [fp, fp] + [C.c_int] * 4 + [ip, ip, ip, C.c_int]
     L.wm_long_result_quality.argtypes = [vp, C.c_int, fp, fp]
     L.wm_long_result_windows.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_int64), fp, fp, ip]
     L.wm_long_result_skip_stats.argtypes = [vp, ip]

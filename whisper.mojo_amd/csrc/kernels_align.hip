@@ -7,7 +7,8 @@
 //   align_dtw  : DTW over -M (one workgroup per utterance, anti-diagonal sweep, 2-bit trace), backtrace, jump times -> times
 //
 // Rows of an utterance: R_b = n_tokens[b] - n_prompt - 1 (the ids that were fed back; the last id has no row).  Nothing here reads
-// anything the host computed after the loop: n_tokens stays on the device.
+// anything the host computed after the loop: n_tokens stays on the device.  Forced alignment gives every utterance its
+// own row count and output offset instead (AlignParams::rows / row0); the arithmetic is the same.
 #include "wm_kernels.h"
 
 #include <cmath>
@@ -15,7 +16,7 @@
 namespace wm {
 
 __device__ __forceinline__ int align_rows(const AlignParams& p, int b) {
-    const int r = p.n_tokens[b] - p.n_prompt - 1;
+    const int r = p.rows ? p.rows[b] : p.n_tokens[b] - p.n_prompt - 1;
     return r < 0 ? 0 : (r > p.L ? p.L : r);
 }
 __device__ __forceinline__ int align_cols(const AlignParams& p, int b) {
@@ -218,7 +219,9 @@ __global__ __launch_bounds__(512) void align_dtw_kernel(AlignParams p) {
     unsigned* tr = p.trace ? p.trace + (size_t)b * p.L * wpr : reinterpret_cast<unsigned*>(dtw_smem + (size_t)3 * L1 * 4);
     int* jt = reinterpret_cast<int*>(dtw_smem);  // after the sweep: jump column of each text row (reuses the diagonals)
     float* times = p.times + (size_t)b * p.out_stride;
-    const int n = p.n_tokens[b];
+    // ids [t_lo, n) carry a time; ragged rows: each utterance's own offset, and the id behind its last row is the last one
+    const int t_lo = p.row0 ? p.row0[b] : p.n_prompt;
+    const int n = p.rows ? t_lo + R + 1 : p.n_tokens[b];
     if (R > 0) {
         const float* Mrow = p.M + ((size_t)b * p.L + (i > 0 ? i - 1 : 0)) * p.T;
         const bool own = i >= 1 && i <= R;
@@ -308,8 +311,8 @@ __global__ __launch_bounds__(512) void align_dtw_kernel(AlignParams p) {
     // token times: 0 for the prompt, the R jump times (time index · 0.02 in double, stored fp32), the last id repeats the last one
     for (int t = i; t < p.out_stride; t += blockDim.x) {
         float v = 0.f;
-        if (R > 0 && t >= p.n_prompt && t < n) {
-            const int r = t - p.n_prompt < R ? t - p.n_prompt : R - 1;
+        if (R > 0 && t >= t_lo && t < n) {
+            const int r = t - t_lo < R ? t - t_lo : R - 1;
             v = (float)((double)jt[r] * 0.02);
         }
         times[t] = v;
@@ -349,7 +352,9 @@ size_t align_dtw_lds_bytes(int L, int T) {
 }
 
 int launch_align_dtw(const AlignParams& p, hipStream_t st) {
-    if (p.L <= 0 || p.L > ALIGN_MAX_ROWS || p.T <= 0 || p.out_stride < p.n_prompt + p.L + 1) return launch_refuse("align_dtw: bad shape");
+    if (!p.rows != !p.row0) return launch_refuse("align_dtw: rows and row0 go together");
+    if (p.L <= 0 || p.L > ALIGN_MAX_ROWS || p.T <= 0 || p.out_stride < (p.rows ? p.out_need : p.n_prompt + p.L + 1))
+        return launch_refuse("align_dtw: bad shape");
     size_t lds = p.trace ? (size_t)3 * (p.L + 1) * 4 : align_dtw_lds_bytes(p.L, p.T);
     if (lds == 0) return launch_refuse("align_dtw: the trace does not fit in LDS and no global trace buffer was given");
     const hipError_t e = ensure_dyn_lds<align_dtw_kernel>((int)lds);

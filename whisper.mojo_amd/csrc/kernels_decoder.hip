@@ -111,7 +111,7 @@ __global__ __launch_bounds__(1024) void dec_linear_kernel(DecLinearParams p) {
         // (the address is uniform, so hipcc emits a scalar load whatever the source says — kernarg -> ctl -> len is one more
         //  scalar round trip in the prologue; in-kernel stamps showed the prologue's scalar stages are not what delays the loads)
         if (p.kcache) cache_row = __builtin_nontemporal_load(&p.ctl->len);
-        if (p.cap) cache_row = __builtin_nontemporal_load(&p.ctl->len);
+        if (p.cap && !p.cap_map) cache_row = __builtin_nontemporal_load(&p.ctl->len);
     }
     Frag<TW> wf[NT][KPW];
     Frag<TW> xft[XT ? KPW : 1];
@@ -241,7 +241,14 @@ __global__ __launch_bounds__(1024) void dec_linear_kernel(DecLinearParams p) {
         if (p.cap) {  // alignment-head capture: this lane's 4 columns lie in one head
             const int h = en >> 6, step = cache_row - p.cap_step0;
             const int k = h < 32 ? p.cap_sel[h] : -1;
-            if (k >= 0 && step >= 0 && step < p.cap_steps)
+            if (p.cap_map) {  // by row map: the position-major rows of a teacher-forced pass go to their utterance's row
+                // (the empty asm pins the map's address arithmetic to this branch: hoisted to the prologue it cost every instantiation
+                //  with one column tile two VGPRs, and two of them a wave of occupancy)
+                int idx = eb;
+                asm volatile("" : "+v"(idx));
+                const int dr = k >= 0 ? p.cap_map[idx] : -1;
+                if (dr >= 0) *reinterpret_cast<f32x4*>(p.cap + ((size_t)dr * p.cap_nsel + k) * 64 + (en & 63)) = v;
+            } else if (k >= 0 && step >= 0 && step < p.cap_steps)
                 *reinterpret_cast<f32x4*>(p.cap + (size_t)eb * p.cap_row_stride + ((size_t)step * p.cap_nsel + k) * 64 + (en & 63)) = v;
         }
     }

@@ -244,6 +244,7 @@ struct wm_model {
         bool ns = false;  // the pass carries the no-speech probe (wm_transcribe_wait_lp_ns may collect it)
         bool lang = false;  // the pass detects the language (wm_transcribe_wait_lang may collect it)
         bool score = false;  // a score pass: only wm_score_wait collects it; total = the caller's ids_stride
+        bool align = false;  // an align pass: only wm_align_wait collects it; lp = it also computes the log-probs
     } slot_ref[8];
     wm_state* pairs[4] = {};  // 2·B-row states of coalesced pairs
     int last_steps[8] = {-1, -1, -1, -1, -1, -1, -1, -1};  // loop iterations enqueued for each slot's last collected pass
@@ -343,6 +344,13 @@ struct wm_state {
         std::vector<int32_t> pairs;               // (layer, head) pairs of the pass
         std::vector<int32_t> cols;                // [B] columns kept per utterance (n_frames // 2, or n_audio_ctx)
         DevBuf cap, kh, probs, mean, stdv, M, trace, times, ncols;
+        // forced alignment (ragged = the pending or last pass was an align pass): every utterance has its own row count
+        // R_b and first timed id; L = max R_b; map [Lmax][B]: where a position-major prefill row's query rows go in cap, as a row of
+        // [B][L] (-1: left padding or context); times is [B][stride] with the caller's ids_stride
+        bool ragged = false;
+        int stride = 0;
+        std::vector<int32_t> h_rows, h_row0, h_map;
+        DevBuf rows, row0, map;
     } al;
     struct CapKey {  // the capture baked into the captured step graph
         const void* cap = nullptr;
@@ -397,8 +405,10 @@ struct wm_state {
         std::vector<int32_t> h_tok, h_pos, h_key_lo, h_dst, h_target, h_slot, h_len, h_ctx;
         // phase marks of the last score pass (wm_score_phases): before the encoder, behind it, behind the prefill chunks, the
         // LayerNorm, the sweep, the merge + sums.  Created by the first score pass.
-        hipEvent_t ev[6] = {};
+        // An align pass adds ev[6] behind its align chain (wm_align_phases).
+        hipEvent_t ev[7] = {};
         bool timed = false;  // a completed pass's marks are all recorded
+        bool timed_al = false;  // ... and it was an align pass: ev[6] too
     } sc;
 };
 
@@ -882,6 +892,8 @@ extern "C" void wm_state_free(wm_state* s) {
                     &s->cross_kv, &s->enc_x, &s->xq, &s->part_y, &s->self_kv, &s->dx, &s->dq, &s->dattn, &s->dhid, &s->part_o, &s->part_ml, &s->logits, &s->amax_val, &s->amax_idx, &s->ts_state, &s->ts_val, &s->ts_idx, &s->ts_m, &s->ts_s, &s->mask_steady, &s->mask_begin,
                     &s->tok, &s->pos, &s->tok_rows, &s->pos_rows, &s->ctl, &s->out_tokens, &s->n_tokens, &s->finished,
                     &s->al.cap, &s->al.kh, &s->al.probs, &s->al.mean, &s->al.stdv, &s->al.M, &s->al.trace, &s->al.times, &s->al.ncols,
+                    &s->al.rows, &s->al.row0, &s->al.map, &s->sc.rows, &s->sc.a, &s->sc.pmax, &s->sc.psum, &s->sc.pidx, &s->sc.ztgt, &s->sc.target,
+                    &s->sc.slot, &s->sc.dst, &s->sc.len, &s->sc.ctx, &s->sc.lp, &s->sc.top, &s->sc.sum, &s->sc.avg,
                     &s->rw.table, &s->rw.len, &s->rw.key_lo, &s->lp.part_s, &s->lp.table, &s->lp.sum,
                     &s->ns.x, &s->ns.pmax, &s->ns.pidx, &s->ns.psum, &s->ns.prob, &s->ns.lse,
                     &s->lg.x, &s->lg.ids, &s->lg.col, &s->lg.out, &s->lg.probs};
@@ -1506,7 +1518,11 @@ static int decode_core(wm_model* m, wm_state* s, const DecView& v, bool want_log
                         p.cap_sel[s->al.pairs[2 * k + 1]] = (signed char)k;
                         any = true;
                     }
-                if (any) {
+                if (any && s->al.ragged) {  // an align pass's chunk: rows [t0, t0 + P) of the row map (single-lane: b0 = 0)
+                    p.cap = s->al.cap.as<float>();
+                    p.cap_map = s->al.map.as<int>() + (size_t)std::max(t0, 0) * v.nb;
+                    p.cap_nsel = n_sel;
+                } else if (any) {
                     p.cap_row_stride = (long)s->al.L * n_sel * 64;
                     p.cap = s->al.cap.as<float>() + (size_t)v.b0 * p.cap_row_stride;
                     p.cap_step0 = s->al.n_prompt;
@@ -2103,6 +2119,9 @@ struct ScoreAsk {  // a score pass, already validated by score_che
     const int32_t* len;  // host [B]
     const int32_t* ctx;  // host [B] or null (= 1)
     int stride, pos_mode;
+    // an align pass: cols non-null = the columns kept per row (align_cols); lp = the vocabulary side runs too
+    const std::vector<int32_t>* cols = nullptr;
+    bool lp = true;
 };
 static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a);
 static int rows_setup(wm_model* m, wm_state* s, const RowPrompts* rows) {
@@ -2163,7 +2182,7 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
         for (int b = 0; b < B; ++b) s->lg.h_col[b] = rows ? rows->len[b] - lang.n_init + 1 : 0;
     }
     s->sc.on = false;
-    s->sc.timed = false;
+    s->sc.timed = s->sc.timed_al = false;
     s->lp.on = lp;
     if (lp) {
         if (rows)
@@ -2236,6 +2255,7 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
         s->pend_total = score->stride;
         return 0;
     }
+    s->al.ragged = false;
     WMCHK(align_setup(m, s, o, cols));
     WMCHK(transcribe_decode(m, s, o, allow_poll));
     s->pending = true;
@@ -2517,6 +2537,7 @@ static int wait_impl(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_toke
     wm_model::SlotRef& r = m->slot_ref[slot];
     if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
     if (r.score) return fail(WM_E_STATE, "this slot holds a score pass (collect it with wm_score_wait)");
+    if (r.align) return fail(WM_E_STATE, "this slot holds an align pass (collect it with wm_align_wait)");
     if (lang_out && !r.lang) return fail(WM_E_STATE, "this slot's pass was submitted without language detection (wm_transcribe_submit_lang)");
     if (no_speech_prob && !r.ns) return fail(WM_E_STATE, "this slot's pass was submitted without the no-speech probe (wm_transcribe_submit_lp_ns)");
     if (token_logprobs && !r.lp) return fail(WM_E_STATE, "this slot's pass was submitted without log-probabilities (wm_transcribe_submit_lp)");
@@ -2834,6 +2855,14 @@ static AlignParams align_params(wm_model* m, wm_state* s) {
     p.trace = align_dtw_lds_bytes(a.L, c.n_audio_ctx) ? nullptr : a.trace.as<unsigned>();
     p.times = a.times.as<float>();
     p.out_stride = s->out_stride;
+    if (a.ragged) {  // an align pass: per-row row counts and offsets, the caller's table width
+        p.n_tokens = nullptr;
+        p.n_prompt = 0;
+        p.rows = a.rows.as<int>();
+        p.row0 = a.row0.as<int>();
+        p.out_stride = a.stride;
+        for (int b = 0; b < s->B; ++b) p.out_need = std::max(p.out_need, a.h_row0[b] + a.h_rows[b] + 1);
+    }
     return p;
 }
 
@@ -2841,7 +2870,7 @@ static AlignParams align_params(wm_model* m, wm_state* s) {
 static int enqueue_align(wm_model* m, wm_state* s) {
     hipStream_t st = s->lanes[0].st;
     if (s->al.L == 0) {  // max_loop 0: no row ever, every time is 0 (HF's early return)
-        HIPCHK(hipMemsetAsync(s->al.times.p, 0, (size_t)s->B * s->out_stride * 4, st));
+        HIPCHK(hipMemsetAsync(s->al.times.p, 0, (size_t)s->B * (s->al.ragged ? s->al.stride : s->out_stride) * 4, st));
         return 0;
     }
     const AlignParams p = align_params(m, s);
@@ -2867,7 +2896,7 @@ extern "C" int wm_alignment_weights(wm_model* m, int slot, float* out) {
     std::vector<int32_t> n(r.rows);
     HIPCHK(hipMemcpy(n.data(), s->n_tokens.as<int>() + r.row0, (size_t)r.rows * 4, hipMemcpyDeviceToHost));
     for (int b = 0; b < r.rows; ++b) {  // rows past R_b were never computed
-        const size_t R = (size_t)std::max(0, std::min<int>((int)L, n[b] - s->al.n_prompt - 1));
+        const size_t R = s->al.ragged ? (size_t)s->al.h_rows[r.row0 + b] : (size_t)std::max(0, std::min<int>((int)L, n[b] - s->al.n_prompt - 1));
         for (size_t k = 0; k < n_sel; ++k) std::fill(out + b * per_row + (k * L + R) * T, out + b * per_row + (k + 1) * L * T, 0.f);
     }
     return 0;
@@ -2915,6 +2944,57 @@ extern "C" int wm_op_token_times(float* times, const float* weights, int n_sel, 
     return 0;
 }
 
+// Several weight tables through align_norm and align_dtw in ONE launch each, with per-table row counts and offsets (the ragged chain of
+// an align pass): weights [n_tab][n_sel][L][T] with L >= max R and T >= max F, table b's R[b] x F[b] corner used;
+// times [n_tab][out_stride], out_stride >= max(row0[b] + R[b] + 1).
+extern "C" int wm_op_token_times_rows(float* times, const float* weights, int n_tab, int n_sel, int L, int T, const int32_t* R, const int32_t* F,
+                                      const int32_t* row0, int out_stride) {
+    if (!times || !weights || !R || !F || !row0 || n_tab <= 0 || n_sel <= 0 || n_sel > ALIGN_MAX_HEADS || L <= 0 || L > ALIGN_MAX_ROWS || T <= 0)
+        return fail(WM_E_ARG, "bad argument (1 <= n_sel <= %d, 1 <= L <= %d, T >= 1)", ALIGN_MAX_HEADS, ALIGN_MAX_ROWS);
+    int need = 0;
+    for (int b = 0; b < n_tab; ++b) {
+        if (R[b] < 0 || R[b] > L || F[b] < 1 || F[b] > T || row0[b] < 0) return fail(WM_E_ARG, "table %d: R in [0, L], F in [1, T], row0 >= 0", b);
+        need = std::max(need, row0[b] + R[b] + 1);
+    }
+    if (out_stride < need) return fail(WM_E_ARG, "out_stride %d is smaller than max(row0 + R + 1) = %d", out_stride, need);
+    TmpDev t;
+    t.bufs.reserve(10);
+    DevBuf &probs = t.add(), &mean = t.add(), &sd = t.add(), &M = t.add(), &tr = t.add(), &tm = t.add(), &dr = t.add(), &df = t.add(), &d0 = t.add();
+    WMCHK(upload(probs, weights, (size_t)n_tab * n_sel * L * T, WM_F32));
+    WMCHK(mean.alloc((size_t)n_tab * n_sel * T * 4));
+    WMCHK(sd.alloc((size_t)n_tab * n_sel * T * 4));
+    WMCHK(M.alloc((size_t)n_tab * L * T * 4));
+    WMCHK(tm.alloc((size_t)n_tab * out_stride * 4));
+    for (auto pr : {std::make_pair(&dr, R), std::make_pair(&df, F), std::make_pair(&d0, row0)}) {
+        WMCHK(pr.first->alloc((size_t)n_tab * 4));
+        HIPCHK(hipMemcpy(pr.first->p, pr.second, (size_t)n_tab * 4, hipMemcpyHostToDevice));
+    }
+    AlignParams p{};
+    p.B = n_tab;
+    p.L = L;
+    p.n_sel = n_sel;
+    p.T = T;
+    p.n_frames = df.as<int>();
+    p.rows = dr.as<int>();
+    p.row0 = d0.as<int>();
+    p.out_need = need;
+    p.probs = probs.as<float>();
+    p.mean = mean.as<float>();
+    p.stdv = sd.as<float>();
+    p.M = M.as<float>();
+    if (align_dtw_lds_bytes(L, T) == 0) {
+        WMCHK(tr.alloc((size_t)n_tab * L * ((T + 15) / 16) * 4));
+        p.trace = tr.as<unsigned>();
+    }
+    p.times = tm.as<float>();
+    p.out_stride = out_stride;
+    LCHK(launch_align_norm(p, nullptr));
+    LCHK(launch_align_dtw(p, nullptr));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(times, tm.p, (size_t)n_tab * out_stride * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // wm_transcribe_wait with the result left ON THE DEVICE as the gather buffer of the multi-GPU path: dev_packed
 // [rows_cap, 1 + stride] int32 in the caller's device memory (e.g. a torch tensor), row r = [length, ids zero-padded]; rows past the
 // batch are zeroed.  stride >= n_prompt + 1 + max_loop of the pass.
@@ -2923,6 +3003,7 @@ extern "C" int wm_transcribe_wait_device(wm_model* m, int slot, int32_t* dev_pac
     wm_model::SlotRef& r = m->slot_ref[slot];
     if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
     if (r.score) return fail(WM_E_STATE, "this slot holds a score pass (collect it with wm_score_wait)");
+    if (r.align) return fail(WM_E_STATE, "this slot holds an align pass (collect it with wm_align_wait)");
     if (rows_cap < r.rows) return fail(WM_E_ARG, "rows_cap %d is smaller than the batch (%d)", rows_cap, r.rows);
     if (stride < r.total) return fail(WM_E_ARG, "stride %d is smaller than the pass's ids per utterance (%d)", stride, r.total);
     if (m->held.active && m->held.slot == slot) {
@@ -3116,6 +3197,20 @@ static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
     sc.h_slot.assign(M, 0);
     sc.h_len.assign(a.len, a.len + B);
     sc.h_ctx.assign(B, 1);
+    // an align pass: the cross-q rows of inputs t in [context_len, len - 1) are captured, R_b = len_b - context_len_b - 1
+    const bool align = a.cols != nullptr, want_lp = !align || a.lp;
+    wm_state::Align& al = s->al;
+    int Lal = 0;
+    if (align) {
+        al.h_rows.assign(B, 0);
+        al.h_row0.assign(B, 1);
+        for (int b = 0; b < B; ++b) {
+            al.h_row0[b] = a.ctx ? a.ctx[b] : 1;
+            al.h_rows[b] = a.len[b] - al.h_row0[b] - 1;
+            Lal = std::max(Lal, al.h_rows[b]);
+        }
+        al.h_map.assign((size_t)Lmax * B, -1);
+    }
     for (int b = 0, base = 0; b < B; ++b) {
         const int n_in = a.len[b] - 1, pad = Lmax - n_in, cl = a.ctx ? a.ctx[b] : 1;
         const int32_t* y = a.ids + (size_t)b * a.stride;
@@ -3132,6 +3227,7 @@ static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
             // WM_POS_REF: the reference's loop feeds position current_len - 1 (whisper.mojo:217), as set_rows_step_kernel applies it
             sc.h_pos[o] = a.pos_mode == WM_POS_REF && i >= cl ? i - 1 : i;
             sc.h_dst[o] = base + i;
+            if (align && i >= cl) al.h_map[o] = b * Lal + (i - cl);
             sc.h_target[base + i] = y[i + 1];
             sc.h_slot[base + i] = b * a.stride + i + 1;
         }
@@ -3142,13 +3238,37 @@ static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
     WMCHK(grow(s->rw.key_lo, (size_t)B * 4));
     WMCHK(grow(s->tok_rows, (size_t)B * ctx * 4));
     WMCHK(grow(s->pos_rows, (size_t)B * ctx * 4));
-    WMCHK(grow(sc.rows, (size_t)M * d * 4));
-    WMCHK(grow(sc.a, score_operand_bytes(M, c.d_model, T)));
-    for (DevBuf* p : {&sc.pmax, &sc.psum, &sc.pidx}) WMCHK(grow(*p, (size_t)M * parts * 4));
-    for (DevBuf* p : {&sc.ztgt, &sc.target, &sc.slot}) WMCHK(grow(*p, (size_t)M * 4));
-    WMCHK(grow(sc.dst, (size_t)B * ctx * 4));
-    for (DevBuf* p : {&sc.len, &sc.ctx, &sc.sum, &sc.avg}) WMCHK(grow(*p, (size_t)B * 4));
-    for (DevBuf* p : {&sc.lp, &sc.top}) WMCHK(grow(*p, (size_t)B * a.stride * 4));
+    if (want_lp) {
+        WMCHK(grow(sc.rows, (size_t)M * d * 4));
+        WMCHK(grow(sc.a, score_operand_bytes(M, c.d_model, T)));
+        for (DevBuf* p : {&sc.pmax, &sc.psum, &sc.pidx}) WMCHK(grow(*p, (size_t)M * parts * 4));
+        for (DevBuf* p : {&sc.ztgt, &sc.target, &sc.slot}) WMCHK(grow(*p, (size_t)M * 4));
+        WMCHK(grow(sc.dst, (size_t)B * ctx * 4));
+        for (DevBuf* p : {&sc.len, &sc.ctx, &sc.sum, &sc.avg}) WMCHK(grow(*p, (size_t)B * 4));
+        for (DevBuf* p : {&sc.lp, &sc.top}) WMCHK(grow(*p, (size_t)B * a.stride * 4));
+    }
+    al.on = al.ragged = align;
+    if (align) {  // the buffers of align_setup, sized by the longest row of THIS pass (they grow, as there)
+        const size_t Ta = c.n_audio_ctx, n_sel = m->align_pairs.size() / 2, Lr = std::max(Lal, 1);
+        al.pairs = m->align_pairs;
+        al.L = Lal;
+        al.n_prompt = 0;
+        al.stride = a.stride;
+        al.cols = *a.cols;
+        ++al.gen;
+        s->graph_cap.L = -1;  // the captured step graph may hold a capture into a buffer that is re-sized here: the next pass recaptures
+        WMCHK(grow(al.cap, (size_t)B * Lr * n_sel * 64 * 4));
+        if (m->xattn) WMCHK(grow(al.kh, (size_t)B * n_sel * Ta * 64 * 4));
+        WMCHK(grow(al.probs, (size_t)B * n_sel * Lr * Ta * 4));
+        WMCHK(grow(al.mean, (size_t)B * n_sel * Ta * 4));
+        WMCHK(grow(al.stdv, (size_t)B * n_sel * Ta * 4));
+        WMCHK(grow(al.M, (size_t)B * Lr * Ta * 4));
+        // rows past ~400 at n_audio_ctx = 1500: the 2-bit trace leaves LDS for global memory
+        if (align_dtw_lds_bytes((int)Lr, (int)Ta) == 0) WMCHK(grow(al.trace, (size_t)B * Lr * ((Ta + 15) / 16) * 4));
+        WMCHK(grow(al.times, (size_t)B * a.stride * 4));
+        for (DevBuf* p : {&al.ncols, &al.rows, &al.row0}) WMCHK(grow(*p, (size_t)B * 4));
+        WMCHK(grow(al.map, (size_t)B * ctx * 4));
+    }
     s->rw.on = true;  // the prefill's self-attention sweeps each row's own key window
     s->rw.Lmax = Lmax;
     sc.on = true;
@@ -3160,23 +3280,34 @@ static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
     HIPCHK(up(s->tok_rows, sc.h_tok));
     HIPCHK(up(s->pos_rows, sc.h_pos));
     HIPCHK(up(s->rw.key_lo, sc.h_key_lo));
-    HIPCHK(up(sc.dst, sc.h_dst));
-    HIPCHK(up(sc.target, sc.h_target));
-    HIPCHK(up(sc.slot, sc.h_slot));
-    HIPCHK(up(sc.len, sc.h_len));
-    HIPCHK(up(sc.ctx, sc.h_ctx));
-    HIPCHK(hipMemsetAsync(sc.lp.p, 0, (size_t)B * a.stride * 4, v.st));     // logprob[b][0] and the tails: 0
-    HIPCHK(hipMemsetAsync(sc.top.p, 0xff, (size_t)B * a.stride * 4, v.st));  // top_id[b][0] and the tails: -1
+    if (want_lp) {
+        HIPCHK(up(sc.dst, sc.h_dst));
+        HIPCHK(up(sc.target, sc.h_target));
+        HIPCHK(up(sc.slot, sc.h_slot));
+        HIPCHK(up(sc.len, sc.h_len));
+        HIPCHK(up(sc.ctx, sc.h_ctx));
+        HIPCHK(hipMemsetAsync(sc.lp.p, 0, (size_t)B * a.stride * 4, v.st));     // logprob[b][0] and the tails: 0
+        HIPCHK(hipMemsetAsync(sc.top.p, 0xff, (size_t)B * a.stride * 4, v.st));  // top_id[b][0] and the tails: -1
+    }
+    if (align) {  // (the host vectors outlive the copies: the state is not reused before this pass is waited for)
+        HIPCHK(up(al.map, al.h_map));
+        HIPCHK(up(al.rows, al.h_rows));
+        HIPCHK(up(al.row0, al.h_row0));
+        HIPCHK(up(al.ncols, al.cols));
+    }
     HIPCHK(hipEventRecord(sc.ev[1], v.st));
     trace_mark(v.st, "state %p score prefill start", (void*)s);
     for (int t0 = 0; t0 < Lmax; t0 += wm_state::PREFILL_MAX) {
         const int P = std::min<int>(wm_state::PREFILL_MAX, Lmax - t0);
         launch_set_step(v.ctl, t0, 1, nullptr, 0, nullptr, 0, v.nb, v.st);
-        WMCHK(decode_core(m, s, v, false, false, nullptr, P, true, nullptr, false, t0));
-        launch_score_collect(s->dx.as<float>(), sc.rows.as<float>(), sc.dst.as<int>() + (size_t)t0 * B, P * B, c.d_model, v.st);
+        WMCHK(decode_core(m, s, v, false, false, nullptr, P, true, nullptr, align && Lal > 0, t0));
+        if (want_lp) launch_score_collect(s->dx.as<float>(), sc.rows.as<float>(), sc.dst.as<int>() + (size_t)t0 * B, P * B, c.d_model, v.st);
     }
     HIPCHK(hipEventRecord(sc.ev[2], v.st));
     trace_mark(v.st, "state %p score prefill end", (void*)s);
+    if (!want_lp) {  // times only: no LayerNorm, sweep, merge or sums
+        for (int k = 3; k <= 5; ++k) HIPCHK(hipEventRecord(sc.ev[k], v.st));
+    } else {
     ScoreParams q{};
     q.x = sc.rows.as<float>();
     q.ln_g = m->dec_ln_g.as<float>();
@@ -3199,6 +3330,11 @@ static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
     LCHK(lrc);
     launch_score_sums(sc.lp.as<float>(), a.stride, sc.len.as<int>(), sc.ctx.as<int>(), sc.sum.as<float>(), sc.avg.as<float>(), B, v.st);
     HIPCHK(hipEventRecord(sc.ev[5], v.st));
+    }
+    if (align) {  // the align chain on the lane's stream, before the pass's completion event
+        WMCHK(enqueue_align(m, s));
+        HIPCHK(hipEventRecord(sc.ev[6], v.st));
+    }
     trace_mark(v.st, "state %p score end", (void*)s);
     HIPCHK(hipEventRecord(ln.done, ln.st));
     HIPCHK(hipGetLastError());
@@ -3206,17 +3342,23 @@ static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
     s->enq_done.store(true);
     return 0;
 }
-static int score_collect(wm_model* m, wm_state* s, float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob) {
+static int score_collect(wm_model* m, wm_state* s, float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob,
+                         float* token_times = nullptr) {
     if (!s || !s->pending || !s->sc.on) return fail(WM_E_STATE, "no score pass was submitted on this slot");
     HIPCHK(hipSetDevice(m->device));
+    const bool align = s->al.on;  // an align pass: token_times [B][stride] too, the log-probs only if it computed them
     const hipError_t e = hipEventSynchronize(s->lanes[0].done);
     s->pending = false;  // afterwards the state holds no usable pass, exactly as after wm_transcribe
     s->has_enc = false;
     s->sc.on = false;
     s->rw.on = false;
+    s->al.on = false;
     HIPCHK(e);
     s->sc.timed = true;
+    s->sc.timed_al = align;
     const size_t n = (size_t)s->B * s->sc.stride * 4;
+    if (token_times) HIPCHK(hipMemcpy(token_times, s->al.times.p, n, hipMemcpyDeviceToHost));
+    if (!token_logprobs) return 0;
     HIPCHK(hipMemcpy(token_logprobs, s->sc.lp.p, n, hipMemcpyDeviceToHost));
     if (top_ids) HIPCHK(hipMemcpy(top_ids, s->sc.top.p, n, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(sum_logprob, s->sc.sum.p, (size_t)s->B * 4, hipMemcpyDeviceToHost));
@@ -3256,6 +3398,7 @@ extern "C" int wm_score_wait(wm_model* m, int slot, float* token_logprobs, int32
     if (!m || !token_logprobs || !sum_logprob || !avg_logprob || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
     wm_model::SlotRef& r = m->slot_ref[slot];
     if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
+    if (r.align) return fail(WM_E_STATE, "this slot holds an align pass (collect it with wm_align_wait)");
     if (!r.score) return fail(WM_E_STATE, "this slot holds a transcribe pass (collect it with wm_transcribe_wait)");
     if (m->held.active && m->held.slot == slot) WMCHK(flush_held(m));
     const int rc = score_collect(m, r.st, token_logprobs, top_ids, sum_logprob, avg_logprob);
@@ -3278,6 +3421,89 @@ extern "C" int wm_score_phases(wm_model* m, int slot, float* ms) {
     if (!s || !state_is_live(s) || s->pending || !s->sc.timed) return fail(WM_E_STATE, "no completed score pass on this slot's state");
     HIPCHK(hipSetDevice(m->device));
     for (int k = 0; k < 5; ++k) HIPCHK(hipEventElapsedTime(ms + k, s->sc.ev[k], s->sc.ev[k + 1]));
+    return 0;
+}
+
+// ---- forced alignment ------------------------------------------------------------------------------------------------
+// Token timestamps of a GIVEN transcript: the score pass with the alignment layers' cross-q rows captured by row map, then the align
+// chain with per-row row counts and offsets.  token_logprobs / sum_logprob / avg_logprob are nullable as a group: without them the
+// vocabulary side is not launched.  Everything is refused before anything is launched.
+static int align_check(wm_model* m, int B, int pos_mode, const int32_t* ids, const int32_t* ids_len, int ids_stride, const int32_t* context_len,
+                       const int32_t* n_frames, const float* token_logprobs, const float* sum_logprob, const float* avg_logprob,
+                       std::vector<int32_t>& cols) {
+    if ((token_logprobs != nullptr) != (sum_logprob != nullptr) || (token_logprobs != nullptr) != (avg_logprob != nullptr))
+        return fail(WM_E_ARG, "token_logprobs, sum_logprob and avg_logprob go together");
+    WMCHK(score_check(m, B, pos_mode, ids, ids_len, ids_stride, context_len));
+    return align_cols(m, n_frames, B, cols);
+}
+static int align_impl(wm_model* m, const float* mel, int mel_on_device, int B, const ScoreAsk& a, float* token_times, float* token_logprobs,
+                      float* sum_logprob, float* avg_logprob) {
+    WMCHK(flush_held(m));
+    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, nullptr, true, nullptr, 0, nullptr, nullptr, false, NsAsk(), LangAsk(), &a));
+    const int rc = score_collect(m, m->cached, token_logprobs, nullptr, sum_logprob, avg_logprob, token_times);
+    m->align_ref[0] = rc ? wm_model::AlignRef{} : wm_model::AlignRef{m->cached, 0, B, m->cached->al.gen};
+    return rc;
+}
+extern "C" int wm_align(wm_model* m, const float* mel, int mel_on_device, int B, int pos_mode, const int32_t* ids, const int32_t* ids_len,
+                        int ids_stride, const int32_t* context_len, const int32_t* n_frames, float* token_times, float* token_logprobs,
+                        float* sum_logprob, float* avg_logprob) {
+    if (!m || !mel || !token_times) return fail(WM_E_ARG, "bad argument");
+    std::vector<int32_t> cols;
+    WMCHK(align_check(m, B, pos_mode, ids, ids_len, ids_stride, context_len, n_frames, token_logprobs, sum_logprob, avg_logprob, cols));
+    return align_impl(m, mel, mel_on_device, B, ScoreAsk{ids, ids_len, context_len, ids_stride, pos_mode, &cols, token_logprobs != nullptr},
+                      token_times, token_logprobs, sum_logprob, avg_logprob);
+}
+// (never held for a coalesce = 2 partner: an align pass runs alone)
+extern "C" int wm_align_submit(wm_model* m, int slot, const float* mel, int mel_on_device, int B, int pos_mode, const int32_t* ids,
+                               const int32_t* ids_len, int ids_stride, const int32_t* context_len, const int32_t* n_frames, int want_logprobs) {
+    if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
+    std::vector<int32_t> cols;
+    WMCHK(align_check(m, B, pos_mode, ids, ids_len, ids_stride, context_len, n_frames, nullptr, nullptr, nullptr, cols));
+    wm_model::SlotRef& r = m->slot_ref[slot];
+    if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    WMCHK(flush_held(m));
+    const ScoreAsk a{ids, ids_len, context_len, ids_stride, pos_mode, &cols, want_logprobs != 0};
+    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, nullptr, false, nullptr, 0, nullptr, nullptr, false, NsAsk(), LangAsk(), &a));
+    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, ids_stride, false, want_logprobs != 0};
+    r.align = true;
+    return 0;
+}
+extern "C" int wm_align_wait(wm_model* m, int slot, float* token_times, float* token_logprobs, float* sum_logprob, float* avg_logprob) {
+    if (!m || !token_times || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
+    if ((token_logprobs != nullptr) != (sum_logprob != nullptr) || (token_logprobs != nullptr) != (avg_logprob != nullptr))
+        return fail(WM_E_ARG, "token_logprobs, sum_logprob and avg_logprob go together");
+    wm_model::SlotRef& r = m->slot_ref[slot];
+    if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
+    if (r.score) return fail(WM_E_STATE, "this slot holds a score pass (collect it with wm_score_wait)");
+    if (!r.align) return fail(WM_E_STATE, "this slot holds a transcribe pass (collect it with wm_transcribe_wait)");
+    if (token_logprobs && !r.lp) return fail(WM_E_STATE, "this slot's align pass was submitted without log-probabilities");
+    wm_state* s = r.st;
+    const int rc = score_collect(m, s, token_logprobs, nullptr, sum_logprob, avg_logprob, token_times);
+    m->align_ref[slot] = rc ? wm_model::AlignRef{} : wm_model::AlignRef{s, 0, r.rows, s->al.gen};
+    r = wm_model::SlotRef{};
+    return rc;
+}
+// n_frames from the sample counts, as wm_transcribe_pcm_tt
+extern "C" int wm_align_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, int pos_mode, const int32_t* ids,
+                            const int32_t* ids_len, int ids_stride, const int32_t* context_len, float* token_times, float* token_logprobs,
+                            float* sum_logprob, float* avg_logprob) {
+    if (!m || !token_times || !n_samples || B <= 0) return fail(WM_E_ARG, "bad argument");
+    std::vector<int32_t> nf(B);
+    for (int b = 0; b < B; ++b) nf[b] = (int32_t)std::min<long>(2L * m->cfg.dims.n_audio_ctx, ((long)n_samples[b] + FE_HOP - 1) / FE_HOP);
+    std::vector<int32_t> cols;
+    WMCHK(align_check(m, B, pos_mode, ids, ids_len, ids_stride, context_len, nf.data(), token_logprobs, sum_logprob, avg_logprob, cols));
+    WMCHK(frontend_run(m, pcm, n_samples, B, stride));  // same stream order as the encoder: no host sync
+    return align_impl(m, m->fe.mel.as<float>(), 1, B, ScoreAsk{ids, ids_len, context_len, ids_stride, pos_mode, &cols, token_logprobs != nullptr},
+                      token_times, token_logprobs, sum_logprob, avg_logprob);
+}
+// ms[6]: wm_score_phases' five (LayerNorm, sweep and merge are 0 for a pass without log-probs) and the align chain
+extern "C" int wm_align_phases(wm_model* m, int slot, float* ms) {
+    if (!m || !ms || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
+    wm_state* s = *slot_state(m, slot);
+    if (!s || !state_is_live(s) || s->pending || !s->sc.timed_al) return fail(WM_E_STATE, "no completed align pass on this slot's state");
+    HIPCHK(hipSetDevice(m->device));
+    for (int k = 0; k < 6; ++k) HIPCHK(hipEventElapsedTime(ms + k, s->sc.ev[k], s->sc.ev[k + 1]));
     return 0;
 }
 // The score pass's vocabulary side alone (LayerNorm, sweep, merge) on host operands: known-answer tests.
@@ -4453,10 +4679,11 @@ static int op_attention_cached(float* out, const float* q, const float* k, const
 
 // One launch_dec_linear as decode_core wires it: LN1 -> QKV with the cache append, the XT out-projections with the residual in place,
 // LNx -> cross q with the alignment-head capture, LN2 -> fc1 + GELU stored in operand dtype, fc2.
-extern "C" int wm_op_dec_linear(float* out, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
-                                const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
-                                float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
-                                const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel) {
+// cap_map non-null: the capture by row map, cap is [cap_dst][cap_nsel][64] and len / cap_step0 / cap_steps are not used
+static int op_dec_linear(float* out, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
+                         const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
+                         float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
+                         const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel, const int32_t* cap_map = nullptr, int cap_dst = 0) {
     if (!out || !x || !W || B <= 0 || N <= 0 || K <= 0) return fail(WM_E_ARG, "bad argument");
     if (dtype < 0 || dtype > 2 || (gelu_mode != 0 && gelu_mode != 1)) return fail(WM_E_ARG, "bad dtype / gelu_mode");
     if (!dec_linear_supports_k(K)) return fail(WM_E_ARG, "K must be a multiple of 32 whose k-steps split over <= 16 waves x <= 4 steps (K <= 2048)");
@@ -4472,7 +4699,14 @@ extern "C" int wm_op_dec_linear(float* out, const float* x, const float* W, cons
         if (kv_B < 0 || (kv_B > 0 ? (kv_B > n_utt || B % kv_B || len + B / kv_B > cap_rows) : (B > n_utt || len + 1 > cap_rows)))
             return fail(WM_E_ARG, "rows must be P * kv_B with kv_B <= n_utt and len + P <= cap_rows, or <= n_utt with len < cap_rows");
     }
-    if (cap) {
+    if (cap && cap_map) {
+        if (!cap_sel || cap_dst <= 0 || cap_nsel <= 0 || cap_nsel > 32 || N % 64 || N > 2048 || kcache)
+            return fail(WM_E_ARG, "capture by row map needs cap_sel, cap_dst > 0, N = 64 * heads <= 2048, 1 <= cap_nsel <= 32 (and no cache)");
+        for (int h = 0; h < 32; ++h)
+            if (cap_sel[h] >= cap_nsel || (cap_sel[h] >= 0 && h >= N / 64)) return fail(WM_E_ARG, "cap_sel names a slot >= cap_nsel or a head >= N / 64");
+        for (int r = 0; r < B; ++r)
+            if (cap_map[r] < -1 || cap_map[r] >= cap_dst) return fail(WM_E_ARG, "cap_map[%d] = %d outside [-1, cap_dst = %d)", r, cap_map[r], cap_dst);
+    } else if (cap) {
         if (!cap_sel || len < 0 || cap_steps <= 0 || cap_nsel <= 0 || cap_nsel > 32 || N % 64 || N > 2048 || (kcache && cap))
             return fail(WM_E_ARG, "capture needs cap_sel, len >= 0, N = 64 * heads <= 2048, 1 <= cap_nsel <= 32, cap_steps > 0 (and no cache)");
         for (int h = 0; h < 32; ++h)
@@ -4484,9 +4718,10 @@ extern "C" int wm_op_dec_linear(float* out, const float* x, const float* W, cons
     // the kernel stores whole 16-column tiles (and loads the residual the same way): rows padded to 16 columns
     const int wout = kcache ? d : N, ldo = (wout + 15) / 16 * 16;
     const int odt = out_is_t ? dtype : WM_F32;
-    const size_t ncache = kcache ? (size_t)n_utt * cap_rows * d : 0, ncap = cap ? (size_t)B * cap_steps * cap_nsel * 64 : 0;
+    const size_t ncache = kcache ? (size_t)n_utt * cap_rows * d : 0;
+    const size_t ncap = !cap ? 0 : cap_map ? (size_t)cap_dst * cap_nsel * 64 : (size_t)B * cap_steps * cap_nsel * 64;
     DevBuf &dx = t.add(), &w = t.add(), &b = t.add(), &g = t.add(), &be = t.add(), &o = t.add(), &r = t.add(), &kc = t.add(), &vc = t.add(),
-           &ctl = t.add(), &cp = t.add();
+           &ctl = t.add(), &cp = t.add(), &cm = t.add();
     WMCHK(upload(dx, x, (size_t)B * K, x_is_t ? dtype : WM_F32));
     WMCHK(upload(w, W, (size_t)N * K, dtype));
     if (bias) WMCHK(upload(b, bias, N, WM_F32));
@@ -4519,7 +4754,7 @@ extern "C" int wm_op_dec_linear(float* out, const float* x, const float* W, cons
     p.ldr = ldo;
     p.out = o.as<float>();
     p.ldo = ldo;
-    if (kcache || cap) {
+    if (kcache || (cap && !cap_map)) {
         StepCtl h{};
         h.len = len;
         WMCHK(ctl.alloc(sizeof(StepCtl)));
@@ -4544,6 +4779,11 @@ extern "C" int wm_op_dec_linear(float* out, const float* x, const float* W, cons
         p.cap_steps = cap_steps;
         p.cap_nsel = cap_nsel;
         memcpy(p.cap_sel, cap_sel, 32);
+        if (cap_map) {
+            WMCHK(cm.alloc((size_t)B * 4));
+            HIPCHK(hipMemcpy(cm.p, cap_map, (size_t)B * 4, hipMemcpyHostToDevice));
+            p.cap_map = cm.as<int>();
+        }
     }
     WMCHK(dec_linear_dispatch(dtype, p, st));
     HIPCHK(hipGetLastError());
@@ -4562,6 +4802,21 @@ extern "C" int wm_op_dec_linear(float* out, const float* x, const float* W, cons
     }
     if (cap) HIPCHK(hipMemcpy(cap, cp.p, ncap * 4, hipMemcpyDeviceToHost));
     return 0;
+}
+extern "C" int wm_op_dec_linear(float* out, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
+                                const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
+                                float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
+                                const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel) {
+    return op_dec_linear(out, x, W, bias, ln_g, ln_b, residual, B, N, K, dtype, x_is_t, out_is_t, act, gelu_mode, kcache, vcache, n_utt, cap_rows,
+                         kv_dtype, kv_B, len, cap, cap_sel, cap_step0, cap_steps, cap_nsel);
+}
+// LNx -> cross q as an align pass wires it: B input rows, cap [cap_dst][cap_nsel][64] in and out, cap_map [B] in [-1, cap_dst)
+extern "C" int wm_op_dec_linear_capmap(float* out, float* cap, const float* x, const float* W, const float* bias, const float* ln_g,
+                                       const float* ln_b, int B, int N, int K, int dtype, const int8_t* cap_sel, int cap_nsel,
+                                       const int32_t* cap_map, int cap_dst) {
+    if (!cap || !cap_map) return fail(WM_E_ARG, "bad argument");
+    return op_dec_linear(out, x, W, bias, ln_g, ln_b, nullptr, B, N, K, dtype, 0, 0, 0, 0, nullptr, nullptr, 0, 0, 0, 0, 0, cap, cap_sel, 0, 0,
+                         cap_nsel, cap_map, cap_dst);
 }
 
 // The decode step's final LayerNorm + tied-embedding logits and its fused argmax, wired as decode_core (want_logits) and

@@ -179,6 +179,10 @@ struct DecLinearParams {
     long cap_row_stride;
     int cap_step0, cap_steps, cap_nsel;
     signed char cap_sel[32];
+    // capture by row map (forced alignment; null = the addressing above): [B] destination row of each input row, -1 = none.
+    // Row r stores to cap[(cap_map[r] * cap_nsel + cap_sel[h]) * 64 + (column % 64)]; ctl->len, cap_row_stride, cap_step0 and
+    // cap_steps are not read
+    const int* cap_map;
 };
 template <typename TW> int launch_dec_linear(const DecLinearParams& p, hipStream_t st);  // WM_LAUNCH_*
 bool dec_linear_supports_k(int K);  // K/32 k-steps must split into NW <= 16 waves x KPW <= 4 steps (checked at model load)
@@ -415,6 +419,12 @@ struct AlignParams {
     unsigned* trace;      // [B][L][ceil(T/16)] 2-bit DTW trace in global memory, or null: in LDS (the launcher decides)
     float* times;         // [B][out_stride]
     int out_stride;
+    // ragged rows (forced alignment; both null = the n_tokens / n_prompt form above, both set = n_tokens is not read):
+    // rows[b] = R_b rows of utterance b (clamped to [0, L]), row0[b] = the first id that has a row (times[b][0 .. row0[b]) = 0, the
+    // id row0[b] + R_b repeats the last time, everything behind it is 0).  out_need: the host's max_b(row0[b] + rows[b] + 1)
+    const int* rows;
+    const int* row0;
+    int out_need;
 };
 int launch_align_probs(const AlignParams& p, hipStream_t st);  // WM_LAUNCH_*
 int launch_align_norm(const AlignParams& p, hipStream_t st);

@@ -70,6 +70,22 @@ def score_audio(model, audios: Sequence[np.ndarray], ids, context_len=None, retu
     return model._score_out(tab, lens, lps, top, sm, avg, return_top_ids)
 
 
+def align_audio(model, audios: Sequence[np.ndarray], ids, context_len=None, return_logprobs: bool = False):
+    """PCM in, Whisper.align out (wm_align_pcm: the mel never leaves the GPU; n_frames from the clip lengths, as
+    transcribe_audio(return_token_timestamps=True)).  Arguments and result as Whisper.align."""
+    buf, n, stride = _pack(audios)
+    B = len(audios)
+    tab, lens, ctx, _ = _lib.align_args(ids, context_len, None, B, model.config.vocab_size, model.config.n_text_ctx, model.max_batch,
+                                        model.config.n_audio_ctx)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    times = np.zeros(tab.shape, np.float32)
+    lp = (np.zeros(tab.shape, np.float32), np.zeros(B, np.float32), np.zeros(B, np.float32)) if return_logprobs else None
+    _lib.check(_lib.lib().wm_align_pcm(model._h, buf.ctypes.data_as(fp), n.ctypes.data_as(ip), B, stride, model.pos_mode,
+                                       tab.ctypes.data_as(ip), lens.ctypes.data_as(ip), tab.shape[1], ctx.ctypes.data_as(ip),
+                                       times.ctypes.data_as(fp), *([a.ctypes.data_as(fp) for a in lp] if lp else [None] * 3)))
+    return model._align_out(0, tab, lens, ctx, times, lp)
+
+
 def log_mel_long(model, audios: Sequence[np.ndarray]):
     """Log-mel of audio of any length, HF WhisperFeatureExtractor(truncation=False, padding="longest",
     return_attention_mask=True): (features [B, n_mels, longest // 160] float32, n_frames [B] = the mask's ones)."""

@@ -151,6 +151,7 @@ class Whisper:
         self._caches = weakref.WeakSet()  # live KVCaches of the loaded model
         self._n_align = 0  # alignment heads set on the loaded model (set_alignment_heads)
         self._score_pending = {}  # slot -> (id table, lengths, mel keep-alive) of a submitted score pass (score_submit / score_wait)
+        self._align_pending = {}  # slot -> (id table, lengths, context lengths, logprobs asked, keep-alives) of a submitted align pass
         self.encoder = WhisperEncoder(self)
         self.decoder = WhisperDecoder(self)
 
@@ -184,6 +185,7 @@ class Whisper:
             self._caches.clear()
             self._pending = {}
             self._score_pending = {}
+            self._align_pending = {}
             _lib.lib().wm_model_free(h)  # also frees every state (KVCache arena, pipeline slot) created on it
 
     def __del__(self):
@@ -630,6 +632,64 @@ class Whisper:
         _lib.check(_lib.lib().wm_score_wait(self._h, slot, _fp(lps), _ip(top) if return_top_ids else None, _fp(sm), _fp(avg)))
         del pend[slot]  # only a collected pass leaves the table
         return self._score_out(tab, lens, lps, top, sm, avg, return_top_ids)
+
+    # ---- forced alignment ---------------------------------------------------------------------------------------
+    def _align_args(self, mel, ids, context_len, n_frames):
+        ptr, on_dev, B, keep = _mel_arg(mel, self.config)
+        tab, lens, ctx, nf = _lib.align_args(ids, context_len, n_frames, B, self.config.vocab_size, self.config.n_text_ctx, self.max_batch,
+                                             self.config.n_audio_ctx)
+        if self._h is None:
+            raise _lib.WhisperMiError("model not loaded")
+        return ptr, on_dev, B, keep, tab, lens, ctx, nf
+
+    def _align_out(self, slot, tab, lens, ctx, times, lp):
+        B = len(lens)
+        self._align_shape = getattr(self, "_align_shape", {})
+        self._align_shape[slot] = (B, int((lens - ctx - 1).max()), self._n_align)
+        out = [times[b, :lens[b]].tolist() for b in range(B)]
+        return (out, self._score_out(tab, lens, lp[0], None, lp[1], lp[2], False)) if lp is not None else out
+
+    def align(self, mel, ids, context_len=None, n_frames=None, return_logprobs: bool = False):
+        """When was each id of this transcript spoken (wm_align): token timestamps of GIVEN ids, HF's _extract_token_timestamps over
+        the cross-attentions of the teacher-forced pass model(features, decoder_input_ids=ids[:, :-1]) with num_input_ids =
+        context_len.  ids / context_len: as score() (context ids get time 0); n_frames: as transcribe_batch.  Needs
+        set_alignment_heads.  -> times, one list per row with one time per id; return_logprobs: (times, what score() returns for the
+        same inputs, computed by the same pass).  alignment_weights() then serves this pass: [B, heads, max_b R_b, n_audio_ctx] with
+        R_b = len_b - context_len_b - 1."""
+        ptr, on_dev, B, keep, tab, lens, ctx, nf = self._align_args(mel, ids, context_len, n_frames)
+        times = np.zeros(tab.shape, np.float32)
+        lp = (np.zeros(tab.shape, np.float32), np.zeros(B, np.float32), np.zeros(B, np.float32)) if return_logprobs else None
+        _lib.check(_lib.lib().wm_align(self._h, ptr, on_dev, B, self.pos_mode, _ip(tab), _ip(lens), tab.shape[1], _ip(ctx),
+                                       _ip(nf) if nf is not None else None, _fp(times), *([_fp(a) for a in lp] if lp else [None] * 3)))
+        return self._align_out(0, tab, lens, ctx, times, lp)
+
+    def align_submit(self, mel, ids, slot: int = 0, context_len=None, n_frames=None, return_logprobs: bool = False):
+        """Pipelined Whisper.align on one of the eight slots; collect with align_wait.  Everything is validated before the call and
+        the slot's record is written only once the library accepted the pass."""
+        ptr, on_dev, B, keep, tab, lens, ctx, nf = self._align_args(mel, ids, context_len, n_frames)
+        if not 0 <= int(slot) < 8:
+            raise ValueError("slot must be 0..7")
+        _lib.check(_lib.lib().wm_align_submit(self._h, slot, ptr, on_dev, B, self.pos_mode, _ip(tab), _ip(lens), tab.shape[1], _ip(ctx),
+                                              _ip(nf) if nf is not None else None, int(bool(return_logprobs))))
+        self._align_pending[slot] = (tab, lens, ctx, bool(return_logprobs), keep)
+
+    def align_wait(self, slot: int = 0):
+        pend = self._align_pending
+        if slot not in pend:
+            raise _lib.WhisperMiError(f"no align pass was submitted on slot {slot}")
+        tab, lens, ctx, want_lp, _keep = pend[slot]
+        B = len(lens)
+        times = np.zeros(tab.shape, np.float32)
+        lp = (np.zeros(tab.shape, np.float32), np.zeros(B, np.float32), np.zeros(B, np.float32)) if want_lp else None
+        _lib.check(_lib.lib().wm_align_wait(self._h, slot, _fp(times), *([_fp(a) for a in lp] if lp else [None] * 3)))
+        del pend[slot]  # only a collected pass leaves the table
+        return self._align_out(slot, tab, lens, ctx, times, lp)
+
+    def align_phases(self, slot: int = 0) -> dict:
+        """GPU milliseconds of the phases of the slot's last collected align pass (wm_align_phases)."""
+        ms = np.zeros(6, np.float32)
+        _lib.check(_lib.lib().wm_align_phases(self._h, slot, _fp(ms)))
+        return dict(zip(("encoder", "prefill", "ln", "sweep", "merge", "align"), (float(v) for v in ms)))
 
     def score_phases(self, slot: int = 0) -> dict:
         """GPU milliseconds of the phases of the slot's last collected score pass (wm_score_phases; slot 0 also serves score)."""
