@@ -188,6 +188,65 @@ struct DecLayer {
         ln2_b;
 };
 
+// ---- what a pass is asked to do, and where its results go -------------------------------------------------------------
+struct NsAsk {  // the no-speech probe a pass carries (DESIGN §18); token < 0: none
+    int token = -1, n_init = 0;
+};
+struct LangAsk {  // language detection a pass carries (DESIGN §19); ids == null: none.  only: no transcription (wm_detect_language)
+    const int32_t* ids = nullptr;  // host [n]
+    int n = 0, n_init = 0, sot = -1;
+    bool only = false;
+};
+struct RowPrompts {
+    const int32_t* ids;  // host [B][stride]
+    const int32_t* len;  // host [B]
+    int stride, Lmax;
+};
+struct ScoreAsk {  // a score pass (DESIGN §20), already validated by score_check
+    const int32_t* ids;  // host [B][stride]
+    const int32_t* len;  // host [B]
+    const int32_t* ctx;  // host [B] or null (= 1)
+    int stride, pos_mode;
+    // an align pass (DESIGN §21): cols non-null = the columns kept per row (align_cols); lp = the vocabulary side runs too
+    const std::vector<int32_t>* cols = nullptr;
+    bool lp = true;
+};
+// One pass: encoder, prefill, greedy loop (or the teacher-forced pass of `score`) for B utterances.  The entry points validate, fill
+// one of these and hand it to a driver (run_now / submit_slot); nothing in it is owned, it lives on the caller's stack.
+struct PassAsk {
+    const float* mel = nullptr;
+    int mel_on_device = 0, B = 0;
+    const wm_decode_opts* opts = nullptr;  // null for a score / align pass and for lang.only
+    bool allow_poll = false;               // the synchronous entries pump their own loop (run_now sets it, nobody else)
+    const float* mel2 = nullptr;           // a coalesced pair: utterances [B/2, B) come from mel2
+    int mel2_on_device = 0;
+    const std::vector<int32_t>* cols = nullptr;  // token timestamps: cols[b] = columns kept for row b (n_frames[b] // 2, or n_audio_ctx)
+    const RowPrompts* rows = nullptr;            // per-row prompts (opts->n_prompt = rows->Lmax, opts->prompt unused)
+    bool lp = false;                             // per-token log-probabilities
+    NsAsk ns;
+    LangAsk lang;
+    const ScoreAsk* score = nullptr;
+};
+static PassAsk lang_only_ask(const float* mel, int mel_on_device, int B, const int32_t* lang_ids, int n_lang, int sot) {
+    PassAsk ask{mel, mel_on_device, B};
+    ask.lang.ids = lang_ids;
+    ask.lang.n = n_lang;
+    ask.lang.sot = sot;
+    ask.lang.only = true;
+    return ask;
+}
+struct PassOut {  // where a pass's results go: the caller's buffers, null = not asked for
+    int32_t *tokens = nullptr, *n_tokens = nullptr;
+    float *token_times = nullptr, *token_logprobs = nullptr, *avg_logprob = nullptr, *no_speech_prob = nullptr;
+    int32_t* lang_out = nullptr;
+    float* lang_probs = nullptr;
+    int32_t* dev_packed = nullptr;  // wm_transcribe_wait_device: the ids stay on the device, [rows_cap][1 + pack_stride]
+    int rows_cap = 0, pack_stride = 0;
+    int32_t* top_ids = nullptr;  // score / align passes
+    float* sum_logprob = nullptr;
+};
+enum class PassKind { transcribe, score, align };  // which wait family collects a slot's pass
+
 struct wm_model {
     wm_config cfg;
     int device = 0;
@@ -226,25 +285,21 @@ struct wm_model {
     // returns exactly its own ids.
     struct Held {
         bool active = false;
-        int slot = 0, B = 0, on_dev = 0;
-        const float* mel = nullptr;
+        int slot = 0;
+        PassAsk ask;  // the held request; ask.opts = &o and ask.cols = &cols (when asked for): the only owning copy of a request
         wm_decode_opts o{};
-        std::vector<int32_t> prompt, sup, bsup;  // deep copies: the caller's option arrays need not outlive the call
-        bool tt = false;                          // token timestamps asked for; cols = columns kept per row
-        std::vector<int32_t> cols;
-        bool lp = false;                          // log-probabilities asked for: pairs only with another such submit
-        int ns_token = -1, ns_init = 0;           // no-speech probe (ns_token >= 0): pairs only with the same token and n_init
+        std::vector<int32_t> prompt, sup, bsup, cols;  // deep copies: the caller's arrays need not outlive the call
     } held;
-    struct SlotRef {  // where a submitted slot's rows live
+    struct SlotRef {  // what a submitted slot holds and where its rows live (filled by record_pass alone)
         bool pending = false;
         wm_state* st = nullptr;  // null while the slot is only held
-        int row0 = 0, rows = 0, total = 0;
-        bool tt = false;
-        bool lp = false;  // the pass computes log-probabilities (wm_transcribe_wait_lp may collect them)
-        bool ns = false;  // the pass carries the no-speech probe (wm_transcribe_wait_lp_ns may collect it)
-        bool lang = false;  // the pass detects the language (wm_transcribe_wait_lang may collect it)
-        bool score = false;  // a score pass: only wm_score_wait collects it; total = the caller's ids_stride
-        bool align = false;  // an align pass: only wm_align_wait collects it; lp = it also computes the log-probs
+        int row0 = 0, rows = 0;
+        int total = 0;  // ids per utterance; a score / align pass: the caller's ids_stride
+        PassKind kind = PassKind::transcribe;
+        bool tt = false;    // the pass computes token timestamps (wm_transcribe_wait_tt may collect them)
+        bool lp = false;    // ... log-probabilities (wm_transcribe_wait_lp; an align pass: wm_align_wait's log-prob outputs)
+        bool ns = false;    // ... the no-speech probe (wm_transcribe_wait_lp_ns)
+        bool lang = false;  // ... the language (wm_transcribe_wait_lang)
     } slot_ref[8];
     wm_state* pairs[4] = {};  // 2·B-row states of coalesced pairs
     int last_steps[8] = {-1, -1, -1, -1, -1, -1, -1, -1};  // loop iterations enqueued for each slot's last collected pass
@@ -2096,33 +2151,7 @@ static int check_opts(wm_model* m, const wm_decode_opts* o, int B) {
     return 0;
 }
 
-// Enqueues one whole pass (encoder, prefill, greedy loop) for B utterances on state *slot (created / re-created on demand).
-// mel2 != null: a coalesced pair — *slot is a 2·(B/2)-row pair state, utterances [B/2, B) come from mel2.
 static int align_setup(wm_model* m, wm_state* s, const wm_decode_opts* o, const std::vector<int32_t>* cols);
-// cols != null: token timestamps for this pass, cols[b] = columns kept for row b (n_frames[b] // 2, or n_audio_ctx)
-// rows != null: per-row prompts (o->n_prompt = rows->Lmax, o->prompt unused)
-struct NsAsk {  // the no-speech probe a pass carries (DESIGN §18); token < 0: none
-    int token = -1, n_init = 0;
-};
-struct LangAsk {  // language detection a pass carries (DESIGN §19); ids == null: none.  only: no transcription (wm_detect_language)
-    const int32_t* ids = nullptr;  // host [n]
-    int n = 0, n_init = 0, sot = -1;
-    bool only = false;
-};
-struct RowPrompts {
-    const int32_t* ids;  // host [B][stride]
-    const int32_t* len;  // host [B]
-    int stride, Lmax;
-};
-struct ScoreAsk {  // a score pass (DESIGN §20), already validated by score_check
-    const int32_t* ids;  // host [B][stride]
-    const int32_t* len;  // host [B]
-    const int32_t* ctx;  // host [B] or null (= 1)
-    int stride, pos_mode;
-    // an align pass (DESIGN §21): cols non-null = the columns kept per row (align_cols); lp = the vocabulary side runs too
-    const std::vector<int32_t>* cols = nullptr;
-    bool lp = true;
-};
 static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a);
 static int rows_setup(wm_model* m, wm_state* s, const RowPrompts* rows) {
     wm_state::Rows& rw = s->rw;
@@ -2145,20 +2174,28 @@ static int rows_setup(wm_model* m, wm_state* s, const RowPrompts* rows) {
     for (size_t b = 0; b < B; ++b) std::copy(rows->ids + b * rows->stride, rows->ids + b * rows->stride + rows->len[b], rw.h_table.begin() + b * rw.stride);
     return 0;
 }
-static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, bool allow_poll,
-                     const float* mel2 = nullptr, int mel2_on_device = 0, const std::vector<int32_t>* cols = nullptr,
-                     const RowPrompts* rows = nullptr, bool lp = false, NsAsk ns = NsAsk(), LangAsk lang = LangAsk(), const ScoreAsk* score = nullptr) {
+// Enqueues one whole pass (encoder, prefill, greedy loop) for ask.B utterances on state *slot (created / re-created on demand).
+// ask.mel2 != null: a coalesced pair — *slot is a 2·(B/2)-row pair state.
+static int submit_on(wm_model* m, wm_state** slot, const PassAsk& ask) {
     const wm_dims& c = m->cfg.dims;
-    if (score && (mel2 || cols || rows || lp || ns.token >= 0 || lang.ids || dec_lanes_for(B) != 1))  // (refused by the entry points first)
+    const int B = ask.B;
+    const wm_decode_opts* o = ask.opts;
+    const bool lp = ask.lp;
+    const std::vector<int32_t>* cols = ask.cols;
+    const RowPrompts* rows = ask.rows;
+    const NsAsk& ns = ask.ns;
+    const LangAsk& lang = ask.lang;
+    const ScoreAsk* score = ask.score;
+    if (score && (ask.mel2 || cols || rows || lp || ns.token >= 0 || lang.ids || dec_lanes_for(B) != 1))  // (refused by the entry points first)
         return fail(WM_E_ARG, "a score pass runs alone on a single-lane decode state");
-    if (lang.ids && (mel2 || cols || dec_lanes_for(B) != 1 || (!lang.only && !rows)))  // (refused by the entry points first)
+    if (lang.ids && (ask.mel2 || cols || dec_lanes_for(B) != 1 || (!lang.only && !rows)))  // (refused by the entry points first)
         return fail(WM_E_ARG, "language detection needs a single-lane decode state and a per-row-prompt pass without token timestamps");
     if (ns.token >= 0 && (!lp || ns.token >= c.vocab || ns.n_init < 1 || ns.n_init > o->n_prompt))  // (refused by the entry points first)
         return fail(WM_E_ARG, "the no-speech probe needs a log-prob pass, a vocabulary id and 1 <= n_init <= prompt length");
     if (lp && (cols || dec_lanes_for(B) != 1))  // (the entry points refuse both before anything is touched; kept for internal callers)
         return fail(WM_E_ARG, "log-probabilities need a single-lane decode state and a pass without token timestamps");
     HIPCHK(hipSetDevice(m->device));
-    const bool pair = mel2 != nullptr;
+    const bool pair = ask.mel2 != nullptr;
     // a pass that was submitted and not yet waited for owns the slot's state: refuse BEFORE touching it (re-creating the
     // state for another batch size would destroy graphs, streams and arenas under its running kernels)
     if (*slot && (*slot)->pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
@@ -2206,15 +2243,15 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
     }
     const size_t mel_floats = (size_t)c.n_mels * 2 * c.n_audio_ctx;  // per utterance
     const int B1 = pair ? B / 2 : B;
-    const float* mel_dev = mel;
-    if (!mel_on_device) {
-        HIPCHK(hipMemcpyAsync(s->mel_dev.p, mel, (size_t)B1 * mel_floats * 4, hipMemcpyHostToDevice, est));
+    const float* mel_dev = ask.mel;
+    if (!ask.mel_on_device) {
+        HIPCHK(hipMemcpyAsync(s->mel_dev.p, ask.mel, (size_t)B1 * mel_floats * 4, hipMemcpyHostToDevice, est));
         mel_dev = s->mel_dev.as<float>();
     }
-    const float* mel2_dev = mel2;
-    if (pair && !mel2_on_device) {
+    const float* mel2_dev = ask.mel2;
+    if (pair && !ask.mel2_on_device) {
         float* dst = s->mel_dev.as<float>() + (size_t)B1 * mel_floats;
-        HIPCHK(hipMemcpyAsync(dst, mel2, (size_t)B1 * mel_floats * 4, hipMemcpyHostToDevice, est));
+        HIPCHK(hipMemcpyAsync(dst, ask.mel2, (size_t)B1 * mel_floats * 4, hipMemcpyHostToDevice, est));
         mel2_dev = dst;
     }
     if (score) {
@@ -2247,7 +2284,7 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
     }
     if (score) {  // teacher-forced prefill + the vocabulary side on the lane's stream: no loop, no graph, no pump
         s->al.on = false;
-        s->shares_chip = !allow_poll;
+        s->shares_chip = !ask.allow_poll;
         WMCHK(score_pass(m, s, *score));
         s->pending = true;
         s->synced = false;
@@ -2257,7 +2294,7 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
     }
     s->al.ragged = false;
     WMCHK(align_setup(m, s, o, cols));
-    WMCHK(transcribe_decode(m, s, o, allow_poll));
+    WMCHK(transcribe_decode(m, s, o, ask.allow_poll));
     s->pending = true;
     s->synced = false;
     s->halves_left = pair ? 2 : 1;
@@ -2268,9 +2305,7 @@ static int submit_on(wm_model* m, wm_state** slot, const float* mel, int mel_on_
 
 // Blocks until the state's pending pass is complete, then copies `rows` utterances starting at row0 out.  The pass stays pending
 // until every slot that shares the state (one, or the two of a coalesced pair) has collected its rows.
-static int wait_on(wm_model* m, wm_state* s, int32_t* tokens_out, int32_t* n_tokens, int row0 = 0, int rows = -1, int32_t* dev_packed = nullptr,
-                   int rows_cap = 0, int pack_stride = 0, float* token_times = nullptr, float* token_logprobs = nullptr, float* avg_logprob = nullptr,
-                   float* no_speech_prob = nullptr, int32_t* lang_out = nullptr, float* lang_probs = nullptr) {
+static int wait_on(wm_model* m, wm_state* s, int row0, int rows, const PassOut& out) {
     if (!s || !s->pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
     HIPCHK(hipSetDevice(m->device));
     if (rows < 0) rows = s->B;
@@ -2288,31 +2323,31 @@ static int wait_on(wm_model* m, wm_state* s, int32_t* tokens_out, int32_t* n_tok
         s->synced = true;
     }
     const int total = s->pend_total;
-    if (dev_packed) {  // the gather buffer, built on the device in the caller's DEVICE memory (no host round trip before the collective)
-        launch_pack_tokens(s->out_tokens.as<int>() + (size_t)row0 * s->out_stride, s->n_tokens.as<int>() + row0, s->out_stride, rows, rows_cap,
-                           pack_stride, dev_packed, s->lanes[0].st);
+    if (out.dev_packed) {  // the gather buffer, built on the device in the caller's DEVICE memory (no host round trip before the collective)
+        launch_pack_tokens(s->out_tokens.as<int>() + (size_t)row0 * s->out_stride, s->n_tokens.as<int>() + row0, s->out_stride, rows, out.rows_cap,
+                           out.pack_stride, out.dev_packed, s->lanes[0].st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s->lanes[0].st));  // the caller's collective runs on another stream
     } else {
-        HIPCHK(hipMemcpy2D(tokens_out, (size_t)total * 4, s->out_tokens.as<int>() + (size_t)row0 * s->out_stride, (size_t)s->out_stride * 4, (size_t)total * 4, rows,
+        HIPCHK(hipMemcpy2D(out.tokens, (size_t)total * 4, s->out_tokens.as<int>() + (size_t)row0 * s->out_stride, (size_t)s->out_stride * 4, (size_t)total * 4, rows,
                            hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(n_tokens, s->n_tokens.as<int>() + row0, (size_t)rows * 4, hipMemcpyDeviceToHost));
-        if (token_times)
-            HIPCHK(hipMemcpy2D(token_times, (size_t)total * 4, s->al.times.as<float>() + (size_t)row0 * s->out_stride, (size_t)s->out_stride * 4,
+        HIPCHK(hipMemcpy(out.n_tokens, s->n_tokens.as<int>() + row0, (size_t)rows * 4, hipMemcpyDeviceToHost));
+        if (out.token_times)
+            HIPCHK(hipMemcpy2D(out.token_times, (size_t)total * 4, s->al.times.as<float>() + (size_t)row0 * s->out_stride, (size_t)s->out_stride * 4,
                                (size_t)total * 4, rows, hipMemcpyDeviceToHost));
-        if (token_logprobs) {  // (the callers checked that the pass computed them)
-            HIPCHK(hipMemcpy2D(token_logprobs, (size_t)total * 4, s->lp.table.as<float>() + (size_t)row0 * s->out_stride, (size_t)s->out_stride * 4,
+        if (out.token_logprobs) {  // (the callers checked that the pass computed them)
+            HIPCHK(hipMemcpy2D(out.token_logprobs, (size_t)total * 4, s->lp.table.as<float>() + (size_t)row0 * s->out_stride, (size_t)s->out_stride * 4,
                                (size_t)total * 4, rows, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(avg_logprob, s->lp.sum.as<float>() + row0, (size_t)rows * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(out.avg_logprob, s->lp.sum.as<float>() + row0, (size_t)rows * 4, hipMemcpyDeviceToHost));
             for (int b = 0; b < rows; ++b) {  // HF _retrieve_avg_logprobs: sum / generated ids (eot included); nothing generated: 0
-                const int gen = n_tokens[b] - s->lp.n_prompt[row0 + b];
-                avg_logprob[b] = gen > 0 ? avg_logprob[b] / (float)gen : 0.f;
+                const int gen = out.n_tokens[b] - s->lp.n_prompt[row0 + b];
+                out.avg_logprob[b] = gen > 0 ? out.avg_logprob[b] / (float)gen : 0.f;
             }
         }
-        if (no_speech_prob) HIPCHK(hipMemcpy(no_speech_prob, s->ns.prob.as<float>() + row0, (size_t)rows * 4, hipMemcpyDeviceToHost));
-        if (lang_out) HIPCHK(hipMemcpy(lang_out, s->lg.out.as<int>() + row0, (size_t)rows * 4, hipMemcpyDeviceToHost));
-        if (lang_probs)
-            HIPCHK(hipMemcpy(lang_probs, s->lg.probs.as<float>() + (size_t)row0 * s->lg.n, (size_t)rows * s->lg.n * 4, hipMemcpyDeviceToHost));
+        if (out.no_speech_prob) HIPCHK(hipMemcpy(out.no_speech_prob, s->ns.prob.as<float>() + row0, (size_t)rows * 4, hipMemcpyDeviceToHost));
+        if (out.lang_out) HIPCHK(hipMemcpy(out.lang_out, s->lg.out.as<int>() + row0, (size_t)rows * 4, hipMemcpyDeviceToHost));
+        if (out.lang_probs)
+            HIPCHK(hipMemcpy(out.lang_probs, s->lg.probs.as<float>() + (size_t)row0 * s->lg.n, (size_t)rows * s->lg.n * 4, hipMemcpyDeviceToHost));
     }
     if (--s->halves_left <= 0) {
         s->pending = false;
@@ -2323,56 +2358,173 @@ static int wait_on(wm_model* m, wm_state* s, int32_t* tokens_out, int32_t* n_tok
 
 static wm_state** slot_state(wm_model* m, int slot) { return slot == 0 ? &m->cached : &m->slots[slot - 1]; }
 
+// ---- the slot protocol: what a slot holds, and the three drivers every entry point ends in -----------------------------
+// The one place a SlotRef is filled: the slot holds rows [row0, row0 + rows) of the pass `a`, on state st (null: only held so far).
+static void record_pass(wm_model* m, int slot, const PassAsk& a, wm_state* st, int row0, int rows) {
+    wm_model::SlotRef& r = m->slot_ref[slot];
+    r = wm_model::SlotRef();
+    r.pending = true;
+    r.st = st;
+    r.row0 = row0;
+    r.rows = rows;
+    r.kind = !a.score ? PassKind::transcribe : a.score->cols ? PassKind::align : PassKind::score;
+    r.total = a.score ? a.score->stride : a.opts->n_prompt + 1 + a.opts->max_loop;
+    r.tt = a.cols != nullptr;
+    r.lp = a.score ? a.score->lp : a.lp;
+    r.ns = a.ns.token >= 0;
+    r.lang = a.lang.ids != nullptr;
+}
+static int score_collect(wm_model* m, wm_state* s, const PassOut& out);
+// Collects the slot's rows and releases the slot.  The one place that says what the slot remembers of a collected pass: the loop
+// steps of a transcribe pass, and a reference to the alignment weights of a pass that computed some (token timestamps, or an align
+// pass that succeeded) — every other pass clears that reference, for its state's weights are no longer this slot's last pass's.
+static int collect_pass(wm_model* m, int slot, const PassOut& out) {
+    wm_model::SlotRef& r = m->slot_ref[slot];
+    wm_state* s = r.st;
+    const bool transcribe = r.kind == PassKind::transcribe;
+    const int rc = transcribe ? wait_on(m, s, r.row0, r.rows, out) : score_collect(m, s, out);
+    if (!rc && transcribe) m->last_steps[slot] = s->last_steps;
+    const bool weights = !rc && (r.tt || r.kind == PassKind::align);
+    m->align_ref[slot] = weights ? wm_model::AlignRef{s, r.row0, r.rows, s->al.gen} : wm_model::AlignRef();
+    r = wm_model::SlotRef();
+    return rc;
+}
+
 // ---- coalescing of consecutive submits (wm_config.coalesce == 2) ------------------------------------------------------------------
-static bool same_opts(const wm_model::Held& h, const wm_decode_opts* o) {
-    const wm_decode_opts& a = h.o;
-    if (a.n_prompt != o->n_prompt || a.eot != o->eot || a.max_loop != o->max_loop || a.pos_mode != o->pos_mode || a.ignore_eot != o->ignore_eot ||
-        a.n_suppress != (o->suppress_tokens ? o->n_suppress : 0) || a.n_begin_suppress != (o->begin_suppress_tokens ? o->n_begin_suppress : 0) ||
-        a.timestamp_begin != o->timestamp_begin || a.no_timestamps_token != o->no_timestamps_token ||
-        a.max_initial_timestamp_index != o->max_initial_timestamp_index)
+// May this submit share a pass with the held one: the same batch size, outputs asked for and options.
+static bool pairs_with(const wm_model::Held& h, const PassAsk& b) {
+    const PassAsk& a = h.ask;
+    const wm_decode_opts &x = h.o, *o = b.opts;
+    if (a.B != b.B || (a.cols != nullptr) != (b.cols != nullptr) || a.lp != b.lp || a.ns.token != b.ns.token || a.ns.n_init != b.ns.n_init)
+        return false;
+    if (x.n_prompt != o->n_prompt || x.eot != o->eot || x.max_loop != o->max_loop || x.pos_mode != o->pos_mode || x.ignore_eot != o->ignore_eot ||
+        x.n_suppress != (o->suppress_tokens ? o->n_suppress : 0) || x.n_begin_suppress != (o->begin_suppress_tokens ? o->n_begin_suppress : 0) ||
+        x.timestamp_begin != o->timestamp_begin || x.no_timestamps_token != o->no_timestamps_token ||
+        x.max_initial_timestamp_index != o->max_initial_timestamp_index)
         return false;
     return std::equal(h.prompt.begin(), h.prompt.end(), o->prompt) && std::equal(h.sup.begin(), h.sup.end(), o->suppress_tokens) &&
            std::equal(h.bsup.begin(), h.bsup.end(), o->begin_suppress_tokens);
 }
-static void hold(wm_model* m, int slot, const float* mel, int on_dev, int B, const wm_decode_opts* o, const std::vector<int32_t>* cols, bool lp,
-                 NsAsk ns) {
+static void hold(wm_model* m, int slot, const PassAsk& a) {
     wm_model::Held& h = m->held;
-    h.lp = lp;
-    h.ns_token = ns.token;
-    h.ns_init = ns.n_init;
-    h.tt = cols != nullptr;
-    h.cols = cols ? *cols : std::vector<int32_t>();
+    const wm_decode_opts* o = a.opts;
     h.active = true;
     h.slot = slot;
-    h.B = B;
-    h.on_dev = on_dev;
-    h.mel = mel;
     h.prompt.assign(o->prompt, o->prompt + o->n_prompt);
     h.sup.assign(o->suppress_tokens, o->suppress_tokens + (o->suppress_tokens ? o->n_suppress : 0));
     h.bsup.assign(o->begin_suppress_tokens, o->begin_suppress_tokens + (o->begin_suppress_tokens ? o->n_begin_suppress : 0));
+    h.cols = a.cols ? *a.cols : std::vector<int32_t>();
     h.o = *o;
     h.o.prompt = h.prompt.data();
     h.o.suppress_tokens = h.sup.empty() ? nullptr : h.sup.data();
     h.o.n_suppress = (int)h.sup.size();
     h.o.begin_suppress_tokens = h.bsup.empty() ? nullptr : h.bsup.data();
     h.o.n_begin_suppress = (int)h.bsup.size();
-    m->slot_ref[slot] = wm_model::SlotRef{true, nullptr, 0, B, o->n_prompt + 1 + o->max_loop, h.tt, lp, ns.token >= 0};
+    h.ask = a;
+    h.ask.opts = &h.o;
+    h.ask.cols = a.cols ? &h.cols : nullptr;
+    record_pass(m, slot, h.ask, nullptr, 0, a.B);
 }
 // the held submit runs alone, on its own slot's state (no partner came, or the partner did not match)
 static int flush_held(wm_model* m) {
     wm_model::Held& h = m->held;
     if (!h.active) return 0;
     h.active = false;
-    wm_model::SlotRef& r = m->slot_ref[h.slot];
-    const int rc = submit_on(m, slot_state(m, h.slot), h.mel, h.on_dev, h.B, &h.o, false, nullptr, 0, h.tt ? &h.cols : nullptr, nullptr, h.lp,
-                             NsAsk{h.ns_token, h.ns_init});
+    const int rc = submit_on(m, slot_state(m, h.slot), h.ask);
     if (rc) {
-        r = wm_model::SlotRef{};
+        m->slot_ref[h.slot] = wm_model::SlotRef();
         return rc;
     }
-    r.st = *slot_state(m, h.slot);
-    r.row0 = 0;
+    record_pass(m, h.slot, h.ask, *slot_state(m, h.slot), 0, h.ask.B);
     return 0;
+}
+
+// ---- the drivers --------------------------------------------------------------------------------------------------------------------
+// The synchronous entries run on slot 0.  A held submit goes first: this call may use its mel buffers' stream order, and slot 0.
+static int slot0_ready(wm_model* m) {
+    WMCHK(flush_held(m));
+    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    return 0;
+}
+static int run_now(wm_model* m, PassAsk ask, const PassOut& out) {
+    WMCHK(slot0_ready(m));
+    ask.allow_poll = true;
+    WMCHK(submit_on(m, &m->cached, ask));
+    record_pass(m, 0, ask, m->cached, 0, ask.B);
+    return collect_pass(m, 0, out);
+}
+// Pipelined form of Whisper.transcribe for back-to-back batches: submit enqueues the encoder and the greedy loop on the slot's
+// stream and returns; the slot's wait blocks until its results are ready.  A pending slot is refused BEFORE a held submit is flushed.
+static int submit_slot(wm_model* m, int slot, const PassAsk& ask) {
+    if (m->slot_ref[slot].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    const int B = ask.B;
+    // (a per-row, language or score / align pass is never held for a coalesce = 2 partner: it runs alone)
+    const bool can_pair = !ask.rows && !ask.lang.ids && !ask.score && m->cfg.coalesce == 2 && B <= m->cfg.max_batch &&
+                          (B <= m->enc_chunk || B % m->enc_chunk == 0);
+    if (can_pair && m->held.active && pairs_with(m->held, ask)) {
+        // the partner of the held submit: both batches go out as ONE pass on a 2·B-row state
+        wm_state** ps = nullptr;
+        for (auto& pr : m->pairs)
+            if (pr && !pr->pending && pr->B == 2 * B) ps = &pr;
+        for (auto& pr : m->pairs)
+            if (!ps && !pr) ps = &pr;
+        for (auto& pr : m->pairs)
+            if (!ps && !pr->pending) ps = &pr;  // another batch size: re-created
+        if (ps) {
+            wm_model::Held& h = m->held;
+            h.active = false;
+            PassAsk both = h.ask;
+            both.B = 2 * B;
+            both.mel2 = ask.mel;
+            both.mel2_on_device = ask.mel_on_device;
+            std::vector<int32_t> pair_cols;
+            if (ask.cols) {  // rows [0, B) are the held batch's, [B, 2B) this one's
+                pair_cols = h.cols;
+                pair_cols.insert(pair_cols.end(), ask.cols->begin(), ask.cols->end());
+                both.cols = &pair_cols;
+            }
+            const int rc = submit_on(m, ps, both);
+            if (rc) {
+                m->slot_ref[h.slot] = wm_model::SlotRef();
+                return rc;
+            }
+            record_pass(m, h.slot, h.ask, *ps, 0, B);
+            record_pass(m, slot, ask, *ps, B, B);
+            return 0;
+        }
+    }
+    WMCHK(flush_held(m));
+    if (can_pair) {  // wait for a partner (or for this slot's wait)
+        hold(m, slot, ask);
+        return 0;
+    }
+    WMCHK(submit_on(m, slot_state(m, slot), ask));
+    record_pass(m, slot, ask, *slot_state(m, slot), 0, B);
+    return 0;
+}
+// A wait of the `kind` family on a slot: refused (the pass stays pending, collectable by the right wait) when the slot holds another
+// kind of pass or one submitted without something `out` asks for.
+static int collect_slot(wm_model* m, int slot, PassKind kind, const PassOut& out) {
+    const wm_model::SlotRef& r = m->slot_ref[slot];
+    if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
+    if (r.kind != kind) {
+        if (r.kind == PassKind::score) return fail(WM_E_STATE, "this slot holds a score pass (collect it with wm_score_wait)");
+        if (r.kind == PassKind::align) return fail(WM_E_STATE, "this slot holds an align pass (collect it with wm_align_wait)");
+        return fail(WM_E_STATE, "this slot holds a transcribe pass (collect it with wm_transcribe_wait)");
+    }
+    if (kind == PassKind::align) {
+        if (out.token_logprobs && !r.lp) return fail(WM_E_STATE, "this slot's align pass was submitted without log-probabilities");
+    } else if (kind == PassKind::transcribe) {
+        if (out.lang_out && !r.lang) return fail(WM_E_STATE, "this slot's pass was submitted without language detection (wm_transcribe_submit_lang)");
+        if (out.no_speech_prob && !r.ns) return fail(WM_E_STATE, "this slot's pass was submitted without the no-speech probe (wm_transcribe_submit_lp_ns)");
+        if (out.token_logprobs && !r.lp) return fail(WM_E_STATE, "this slot's pass was submitted without log-probabilities (wm_transcribe_submit_lp)");
+        if (out.token_times && !r.tt) return fail(WM_E_STATE, "this slot's pass was submitted without token timestamps (wm_transcribe_submit_tt)");
+        if (out.dev_packed && out.rows_cap < r.rows) return fail(WM_E_ARG, "rows_cap %d is smaller than the batch (%d)", out.rows_cap, r.rows);
+        if (out.dev_packed && out.pack_stride < r.total)
+            return fail(WM_E_ARG, "stride %d is smaller than the pass's ids per utterance (%d)", out.pack_stride, r.total);
+    }
+    if (m->held.active && m->held.slot == slot) WMCHK(flush_held(m));  // no partner came: the held batch runs alone now
+    return collect_pass(m, slot, out);
 }
 
 // n_frames -> columns kept per row (HF crops the attentions to n_frames // 2 encoder positions); null = every column
@@ -2389,22 +2541,11 @@ static int align_cols(wm_model* m, const int32_t* n_frames, int B, std::vector<i
     return 0;
 }
 
-static int transcribe_impl(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const std::vector<int32_t>* cols,
-                           int32_t* tokens_out, int32_t* n_tokens, float* token_times) {
-    WMCHK(flush_held(m));  // a held submit goes first: this call may use its mel buffers' stream order, and slot 0
-    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, o, true, nullptr, 0, cols));
-    WMCHK(wait_on(m, m->cached, tokens_out, n_tokens, 0, -1, nullptr, 0, 0, token_times));
-    m->last_steps[0] = m->cached->last_steps;
-    m->align_ref[0] = cols ? wm_model::AlignRef{m->cached, 0, B, m->cached->al.gen} : wm_model::AlignRef{};
-    return 0;
-}
-
 extern "C" int wm_transcribe(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* o,
                              int32_t* tokens_out, int32_t* n_tokens) {
     if (!m || !mel || !tokens_out || !n_tokens) return fail(WM_E_ARG, "bad argument");
     WMCHK(check_opts(m, o, B));
-    return transcribe_impl(m, mel, mel_on_device, B, o, nullptr, tokens_out, n_tokens, nullptr);
+    return run_now(m, PassAsk{mel, mel_on_device, B, o}, PassOut{tokens_out, n_tokens});
 }
 
 extern "C" int wm_transcribe_tt(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const int32_t* n_frames,
@@ -2413,61 +2554,15 @@ extern "C" int wm_transcribe_tt(wm_model* m, const float* mel, int mel_on_device
     WMCHK(check_opts(m, o, B));
     std::vector<int32_t> cols;
     WMCHK(align_cols(m, n_frames, B, cols));
-    return transcribe_impl(m, mel, mel_on_device, B, o, &cols, tokens_out, n_tokens, token_times);
+    PassAsk ask{mel, mel_on_device, B, o};
+    ask.cols = &cols;
+    return run_now(m, ask, PassOut{tokens_out, n_tokens, token_times});
 }
 
-// Pipelined form of Whisper.transcribe for back-to-back batches: submit enqueues the encoder and the greedy loop on the slot's
-// stream and returns; wait blocks until that slot's tokens are ready.
-static int submit_impl(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const std::vector<int32_t>* cols,
-                       bool lp = false, NsAsk ns = NsAsk()) {
-    wm_model::SlotRef& r = m->slot_ref[slot];
-    if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    const int total = o->n_prompt + 1 + o->max_loop;
-    const bool tt = cols != nullptr;
-    const bool can_pair = m->cfg.coalesce == 2 && B <= m->cfg.max_batch && (B <= m->enc_chunk || B % m->enc_chunk == 0);
-    if (can_pair && m->held.active && m->held.B == B && m->held.tt == tt && m->held.lp == lp && m->held.ns_token == ns.token &&
-        m->held.ns_init == ns.n_init && same_opts(m->held, o)) {
-        // the partner of the held submit: both batches go out as ONE pass on a 2·B-row state
-        wm_state** ps = nullptr;
-        for (auto& pr : m->pairs)
-            if (pr && !pr->pending && pr->B == 2 * B) ps = &pr;
-        for (auto& pr : m->pairs)
-            if (!ps && !pr) ps = &pr;
-        for (auto& pr : m->pairs)
-            if (!ps && !pr->pending) ps = &pr;  // another batch size: re-created
-        if (ps) {
-            wm_model::Held& h = m->held;
-            h.active = false;
-            wm_model::SlotRef& r0 = m->slot_ref[h.slot];
-            std::vector<int32_t> pair_cols;
-            if (tt) {  // rows [0, B) are the held batch's, [B, 2B) this one's
-                pair_cols = h.cols;
-                pair_cols.insert(pair_cols.end(), cols->begin(), cols->end());
-            }
-            const int rc = submit_on(m, ps, h.mel, h.on_dev, 2 * B, &h.o, false, mel, mel_on_device, tt ? &pair_cols : nullptr, nullptr, lp, ns);
-            if (rc) {
-                r0 = wm_model::SlotRef{};
-                return rc;
-            }
-            r0.st = *ps;
-            r0.row0 = 0;
-            r = wm_model::SlotRef{true, *ps, B, B, total, tt, lp, ns.token >= 0};
-            return 0;
-        }
-    }
-    WMCHK(flush_held(m));
-    if (can_pair) {  // wait for a partner (or for this slot's wm_transcribe_wait)
-        hold(m, slot, mel, mel_on_device, B, o, cols, lp, ns);
-        return 0;
-    }
-    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, o, false, nullptr, 0, cols, nullptr, lp, ns));
-    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, total, tt, lp, ns.token >= 0};
-    return 0;
-}
 extern "C" int wm_transcribe_submit(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o) {
     if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
     WMCHK(check_opts(m, o, B));
-    return submit_impl(m, slot, mel, mel_on_device, B, o, nullptr);
+    return submit_slot(m, slot, PassAsk{mel, mel_on_device, B, o});
 }
 extern "C" int wm_transcribe_submit_tt(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o,
                                        const int32_t* n_frames) {
@@ -2475,7 +2570,9 @@ extern "C" int wm_transcribe_submit_tt(wm_model* m, int slot, const float* mel, 
     WMCHK(check_opts(m, o, B));
     std::vector<int32_t> cols;
     WMCHK(align_cols(m, n_frames, B, cols));
-    return submit_impl(m, slot, mel, mel_on_device, B, o, &cols);
+    PassAsk ask{mel, mel_on_device, B, o};
+    ask.cols = &cols;
+    return submit_slot(m, slot, ask);
 }
 // ---- per-row prompts -----------------------------------------------------------------------------------------------
 // Everything is checked before anything is launched.  o2: the options the pass runs with (n_prompt = the longest row).
@@ -2510,59 +2607,27 @@ extern "C" int wm_transcribe_rows(wm_model* m, const float* mel, int mel_on_devi
     wm_decode_opts o2;
     RowPrompts rows;
     WMCHK(rows_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));
-    WMCHK(flush_held(m));
-    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, &o2, true, nullptr, 0, nullptr, &rows));
-    WMCHK(wait_on(m, m->cached, tokens_out, n_tokens));
-    m->last_steps[0] = m->cached->last_steps;
-    m->align_ref[0] = wm_model::AlignRef{};
-    return 0;
+    PassAsk ask{mel, mel_on_device, B, &o2};
+    ask.rows = &rows;
+    return run_now(m, ask, PassOut{tokens_out, n_tokens});
 }
-// (never held for a coalesce = 2 partner: a per-row pass runs alone)
 extern "C" int wm_transcribe_submit_rows(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o,
                                          const int32_t* prompts, const int32_t* prompt_len, int prompt_stride) {
     if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
     wm_decode_opts o2;
     RowPrompts rows;
     WMCHK(rows_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));
-    wm_model::SlotRef& r = m->slot_ref[slot];
-    if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    WMCHK(flush_held(m));
-    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, &o2, false, nullptr, 0, nullptr, &rows));
-    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, o2.n_prompt + 1 + o2.max_loop, false};
-    return 0;
-}
-static int wait_impl(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_times, float* token_logprobs = nullptr,
-                     float* avg_logprob = nullptr, float* no_speech_prob = nullptr, int32_t* lang_out = nullptr, float* lang_probs = nullptr) {
-    wm_model::SlotRef& r = m->slot_ref[slot];
-    if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
-    if (r.score) return fail(WM_E_STATE, "this slot holds a score pass (collect it with wm_score_wait)");
-    if (r.align) return fail(WM_E_STATE, "this slot holds an align pass (collect it with wm_align_wait)");
-    if (lang_out && !r.lang) return fail(WM_E_STATE, "this slot's pass was submitted without language detection (wm_transcribe_submit_lang)");
-    if (no_speech_prob && !r.ns) return fail(WM_E_STATE, "this slot's pass was submitted without the no-speech probe (wm_transcribe_submit_lp_ns)");
-    if (token_logprobs && !r.lp) return fail(WM_E_STATE, "this slot's pass was submitted without log-probabilities (wm_transcribe_submit_lp)");
-    if (token_times && !r.tt) return fail(WM_E_STATE, "this slot's pass was submitted without token timestamps (wm_transcribe_submit_tt)");
-    if (m->held.active && m->held.slot == slot) {  // no partner came: the held batch runs alone now
-        const int rc = flush_held(m);
-        if (rc) return rc;
-    }
-    wm_state* s = r.st;
-    const int rc = wait_on(m, s, tokens_out, n_tokens, r.row0, r.rows, nullptr, 0, 0, token_times, token_logprobs, avg_logprob, no_speech_prob,
-                           lang_out, lang_probs);
-    if (!rc) {
-        m->last_steps[slot] = s->last_steps;
-        m->align_ref[slot] = r.tt ? wm_model::AlignRef{s, r.row0, r.rows, s->al.gen} : wm_model::AlignRef{};
-    }
-    r = wm_model::SlotRef{};
-    return rc;
+    PassAsk ask{mel, mel_on_device, B, &o2};
+    ask.rows = &rows;
+    return submit_slot(m, slot, ask);
 }
 extern "C" int wm_transcribe_wait(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens) {
     if (!m || !tokens_out || !n_tokens || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
-    return wait_impl(m, slot, tokens_out, n_tokens, nullptr);
+    return collect_slot(m, slot, PassKind::transcribe, PassOut{tokens_out, n_tokens});
 }
 extern "C" int wm_transcribe_wait_tt(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_times) {
     if (!m || !tokens_out || !n_tokens || !token_times || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
-    return wait_impl(m, slot, tokens_out, n_tokens, token_times);
+    return collect_slot(m, slot, PassKind::transcribe, PassOut{tokens_out, n_tokens, token_times});
 }
 // ---- log-probabilities -----------------------------------------------------------------------------------------------
 // One family for shared (prompts == NULL: opts->prompt) and per-row prompts.  Everything is refused before anything is launched.
@@ -2578,38 +2643,42 @@ static int lp_check(wm_model* m, const wm_decode_opts* o, int B, const int32_t* 
     if (dec_lanes_for(B) != 1) return fail(WM_E_ARG, "log-probabilities need a single-lane decode state");
     return 0;
 }
+static int ns_check(wm_model* m, const wm_decode_opts& o2, int B, const int32_t* prompts, const int32_t* prompt_len, int no_speech_token, int n_init);
+// The _lp and _lp_ns entries behind their null checks: slot < 0 runs the pass now, on slot 0; ns: the _lp_ns probe, as given.
+static int lp_entry(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const int32_t* prompts,
+                    const int32_t* prompt_len, int prompt_stride, const NsAsk* ns, const PassOut& out) {
+    wm_decode_opts o2;
+    RowPrompts rows;
+    WMCHK(lp_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));
+    if (ns) WMCHK(ns_check(m, o2, B, prompts, prompt_len, ns->token, ns->n_init));
+    PassAsk ask{mel, mel_on_device, B, &o2};
+    ask.rows = prompts ? &rows : nullptr;
+    ask.lp = true;
+    if (ns) ask.ns = *ns;
+    return slot < 0 ? run_now(m, ask, out) : submit_slot(m, slot, ask);
+}
+static PassOut lp_out(int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob, float* no_speech_prob) {
+    PassOut out{tokens_out, n_tokens};
+    out.token_logprobs = token_logprobs;
+    out.avg_logprob = avg_logprob;
+    out.no_speech_prob = no_speech_prob;
+    return out;
+}
 extern "C" int wm_transcribe_lp(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const int32_t* prompts,
                                 const int32_t* prompt_len, int prompt_stride, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs,
                                 float* avg_logprob) {
     if (!m || !mel || !tokens_out || !n_tokens || !token_logprobs || !avg_logprob) return fail(WM_E_ARG, "bad argument");
-    wm_decode_opts o2;
-    RowPrompts rows;
-    WMCHK(lp_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));
-    WMCHK(flush_held(m));
-    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, &o2, true, nullptr, 0, nullptr, prompts ? &rows : nullptr, true));
-    WMCHK(wait_on(m, m->cached, tokens_out, n_tokens, 0, -1, nullptr, 0, 0, nullptr, token_logprobs, avg_logprob));
-    m->last_steps[0] = m->cached->last_steps;
-    m->align_ref[0] = wm_model::AlignRef{};
-    return 0;
+    return lp_entry(m, -1, mel, mel_on_device, B, o, prompts, prompt_len, prompt_stride, nullptr,
+                    lp_out(tokens_out, n_tokens, token_logprobs, avg_logprob, nullptr));
 }
 extern "C" int wm_transcribe_submit_lp(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o,
                                        const int32_t* prompts, const int32_t* prompt_len, int prompt_stride) {
     if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
-    wm_decode_opts o2;
-    RowPrompts rows;
-    WMCHK(lp_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));
-    if (!prompts) return submit_impl(m, slot, mel, mel_on_device, B, &o2, nullptr, true);
-    wm_model::SlotRef& r = m->slot_ref[slot];  // (a per-row pass is never held for a coalesce = 2 partner)
-    if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    WMCHK(flush_held(m));
-    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, &o2, false, nullptr, 0, nullptr, &rows, true));
-    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, o2.n_prompt + 1 + o2.max_loop, false, true};
-    return 0;
+    return lp_entry(m, slot, mel, mel_on_device, B, o, prompts, prompt_len, prompt_stride, nullptr, PassOut());
 }
 extern "C" int wm_transcribe_wait_lp(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob) {
     if (!m || !tokens_out || !n_tokens || !token_logprobs || !avg_logprob || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
-    return wait_impl(m, slot, tokens_out, n_tokens, nullptr, token_logprobs, avg_logprob);
+    return collect_slot(m, slot, PassKind::transcribe, lp_out(tokens_out, n_tokens, token_logprobs, avg_logprob, nullptr));
 }
 // ---- no-speech probe: the _lp trio plus the probability of no_speech_token at each row's <|startoftranscript|>
 // position, prompt length - n_init.  Everything is refused before anything is launched.
@@ -2628,39 +2697,21 @@ extern "C" int wm_transcribe_lp_ns(wm_model* m, const float* mel, int mel_on_dev
                                    const int32_t* prompt_len, int prompt_stride, int no_speech_token, int n_init, int32_t* tokens_out,
                                    int32_t* n_tokens, float* token_logprobs, float* avg_logprob, float* no_speech_prob) {
     if (!m || !mel || !tokens_out || !n_tokens || !token_logprobs || !avg_logprob || !no_speech_prob) return fail(WM_E_ARG, "bad argument");
-    wm_decode_opts o2;
-    RowPrompts rows;
-    WMCHK(lp_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));
-    WMCHK(ns_check(m, o2, B, prompts, prompt_len, no_speech_token, n_init));
-    WMCHK(flush_held(m));
-    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, &o2, true, nullptr, 0, nullptr, prompts ? &rows : nullptr, true, NsAsk{no_speech_token, n_init}));
-    WMCHK(wait_on(m, m->cached, tokens_out, n_tokens, 0, -1, nullptr, 0, 0, nullptr, token_logprobs, avg_logprob, no_speech_prob));
-    m->last_steps[0] = m->cached->last_steps;
-    m->align_ref[0] = wm_model::AlignRef{};
-    return 0;
+    const NsAsk ns{no_speech_token, n_init};
+    return lp_entry(m, -1, mel, mel_on_device, B, o, prompts, prompt_len, prompt_stride, &ns,
+                    lp_out(tokens_out, n_tokens, token_logprobs, avg_logprob, no_speech_prob));
 }
 extern "C" int wm_transcribe_submit_lp_ns(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o,
                                           const int32_t* prompts, const int32_t* prompt_len, int prompt_stride, int no_speech_token, int n_init) {
     if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
-    wm_decode_opts o2;
-    RowPrompts rows;
-    WMCHK(lp_check(m, o, B, prompts, prompt_len, prompt_stride, o2, rows));
-    WMCHK(ns_check(m, o2, B, prompts, prompt_len, no_speech_token, n_init));
     const NsAsk ns{no_speech_token, n_init};
-    if (!prompts) return submit_impl(m, slot, mel, mel_on_device, B, &o2, nullptr, true, ns);
-    wm_model::SlotRef& r = m->slot_ref[slot];  // (a per-row pass is never held for a coalesce = 2 partner)
-    if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    WMCHK(flush_held(m));
-    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, &o2, false, nullptr, 0, nullptr, &rows, true, ns));
-    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, o2.n_prompt + 1 + o2.max_loop, false, true, true};
-    return 0;
+    return lp_entry(m, slot, mel, mel_on_device, B, o, prompts, prompt_len, prompt_stride, &ns, PassOut());
 }
 extern "C" int wm_transcribe_wait_lp_ns(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob,
                                         float* no_speech_prob) {
     if (!m || !tokens_out || !n_tokens || !token_logprobs || !avg_logprob || !no_speech_prob || slot < 0 || slot >= wm_model::NSLOT)
         return fail(WM_E_ARG, "bad argument");
-    return wait_impl(m, slot, tokens_out, n_tokens, nullptr, token_logprobs, avg_logprob, no_speech_prob);
+    return collect_slot(m, slot, PassKind::transcribe, lp_out(tokens_out, n_tokens, token_logprobs, avg_logprob, no_speech_prob));
 }
 // ---- language detection ----------------------------------------------------------------------------------------------
 // Everything is refused before anything is launched.
@@ -2674,6 +2725,7 @@ static int lang_list_check(int vocab, const int32_t* lang_ids, int n_lang) {
     }
     return 0;
 }
+// (the synchronous sequence up to the submit; the collect is its own: no ids, and the pass leaves no pending state behind)
 extern "C" int wm_detect_language(wm_model* m, const float* mel, int mel_on_device, int B, int sot_token, const int32_t* lang_ids, int n_lang,
                                   int32_t* lang_out, float* probs_out) {
     if (!m || !mel || !lang_out || B <= 0) return fail(WM_E_ARG, "bad argument");
@@ -2681,24 +2733,21 @@ extern "C" int wm_detect_language(wm_model* m, const float* mel, int mel_on_devi
     if (sot_token < 0 || sot_token >= m->cfg.dims.vocab) return fail(WM_E_ARG, "sot_token %d is not a vocabulary id", sot_token);
     WMCHK(lang_list_check(m->cfg.dims.vocab, lang_ids, n_lang));
     if (dec_lanes_for(B) != 1) return fail(WM_E_ARG, "language detection needs a single-lane decode state");
-    WMCHK(flush_held(m));
-    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    LangAsk lang;
-    lang.ids = lang_ids;
-    lang.n = n_lang;
-    lang.sot = sot_token;
-    lang.only = true;
-    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, nullptr, true, nullptr, 0, nullptr, nullptr, false, NsAsk(), lang));
+    WMCHK(slot0_ready(m));
+    WMCHK(submit_on(m, &m->cached, lang_only_ask(mel, mel_on_device, B, lang_ids, n_lang, sot_token)));
     wm_state* s = m->cached;
     HIPCHK(hipStreamSynchronize(s->lanes[0].st));
     HIPCHK(hipMemcpy(lang_out, s->lg.out.p, (size_t)B * 4, hipMemcpyDeviceToHost));
     if (probs_out) HIPCHK(hipMemcpy(probs_out, s->lg.probs.p, (size_t)B * n_lang * 4, hipMemcpyDeviceToHost));
     return 0;
 }
-// The checks of a _lang pass.  tab / len: the per-row table built from opts->prompt when prompts == NULL.
-static int lang_check(wm_model* m, const wm_decode_opts* o, int B, const int32_t*& prompts, const int32_t*& prompt_len, int& prompt_stride,
-                      bool lp, int no_speech_token, int n_init, const int32_t* lang_ids, int n_lang, std::vector<int32_t>& tab,
-                      std::vector<int32_t>& len, wm_decode_opts& o2, RowPrompts& rows, LangAsk& lang) {
+// The _lang entries behind their null checks: the checks of a _lang pass, then slot < 0 runs it now, on slot 0.
+static int lang_entry(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const int32_t* prompts,
+                      const int32_t* prompt_len, int prompt_stride, bool lp, int no_speech_token, int n_init, const int32_t* lang_ids, int n_lang,
+                      const PassOut& out) {
+    std::vector<int32_t> tab, len;  // the per-row table built from opts->prompt when prompts == NULL
+    wm_decode_opts o2;
+    RowPrompts rows;
     if (!prompts) {
         if (prompt_len) return fail(WM_E_ARG, "prompt_len without prompts");
         WMCHK(check_opts(m, o, B));
@@ -2723,11 +2772,15 @@ static int lang_check(wm_model* m, const wm_decode_opts* o, int B, const int32_t
             return fail(WM_E_ARG, "row %d starts its initial ids with %d, row 0 with %d: one <|startoftranscript|> per pass", b,
                         prompts[(size_t)b * prompt_stride + prompt_len[b] - n_init], sot);
     }
-    lang.ids = lang_ids;
-    lang.n = n_lang;
-    lang.n_init = n_init;
-    lang.sot = sot;
-    return 0;
+    PassAsk ask{mel, mel_on_device, B, &o2};
+    ask.rows = &rows;
+    ask.lp = lp;
+    if (no_speech_token >= 0) ask.ns = NsAsk{no_speech_token, n_init};
+    ask.lang.ids = lang_ids;
+    ask.lang.n = n_lang;
+    ask.lang.n_init = n_init;
+    ask.lang.sot = sot;
+    return slot < 0 ? run_now(m, ask, out) : submit_slot(m, slot, ask);
 }
 extern "C" int wm_transcribe_lang(wm_model* m, const float* mel, int mel_on_device, int B, const wm_decode_opts* o, const int32_t* prompts,
                                   const int32_t* prompt_len, int prompt_stride, int no_speech_token, int n_init, const int32_t* lang_ids, int n_lang,
@@ -2735,47 +2788,28 @@ extern "C" int wm_transcribe_lang(wm_model* m, const float* mel, int mel_on_devi
                                   int32_t* lang_out, float* lang_probs) {
     if (!m || !mel || !tokens_out || !n_tokens || !lang_out || !o || B <= 0) return fail(WM_E_ARG, "bad argument");
     if (!token_logprobs != !avg_logprob) return fail(WM_E_ARG, "token_logprobs and avg_logprob go together");
-    const bool lp = token_logprobs != nullptr;
     if (no_speech_token >= 0 && !no_speech_prob) return fail(WM_E_ARG, "bad argument");
-    std::vector<int32_t> tab, len;
-    wm_decode_opts o2;
-    RowPrompts rows;
-    LangAsk lang;
-    WMCHK(lang_check(m, o, B, prompts, prompt_len, prompt_stride, lp, no_speech_token, n_init, lang_ids, n_lang, tab, len, o2, rows, lang));
-    WMCHK(flush_held(m));
-    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    const NsAsk ns = no_speech_token >= 0 ? NsAsk{no_speech_token, n_init} : NsAsk();
-    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, &o2, true, nullptr, 0, nullptr, &rows, lp, ns, lang));
-    WMCHK(wait_on(m, m->cached, tokens_out, n_tokens, 0, -1, nullptr, 0, 0, nullptr, token_logprobs, avg_logprob,
-                  no_speech_token >= 0 ? no_speech_prob : nullptr, lang_out, lang_probs));
-    m->last_steps[0] = m->cached->last_steps;
-    m->align_ref[0] = wm_model::AlignRef{};
-    return 0;
+    PassOut out = lp_out(tokens_out, n_tokens, token_logprobs, avg_logprob, no_speech_token >= 0 ? no_speech_prob : nullptr);
+    out.lang_out = lang_out;
+    out.lang_probs = lang_probs;
+    return lang_entry(m, -1, mel, mel_on_device, B, o, prompts, prompt_len, prompt_stride, token_logprobs != nullptr, no_speech_token, n_init, lang_ids,
+                      n_lang, out);
 }
-// (never held for a coalesce = 2 partner: a per-row pass runs alone)
 extern "C" int wm_transcribe_submit_lang(wm_model* m, int slot, const float* mel, int mel_on_device, int B, const wm_decode_opts* o,
                                          const int32_t* prompts, const int32_t* prompt_len, int prompt_stride, int no_speech_token, int n_init,
                                          const int32_t* lang_ids, int n_lang, int want_logprobs) {
     if (!m || !mel || !o || B <= 0 || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
-    const bool lp = want_logprobs != 0;
-    std::vector<int32_t> tab, len;
-    wm_decode_opts o2;
-    RowPrompts rows;
-    LangAsk lang;
-    WMCHK(lang_check(m, o, B, prompts, prompt_len, prompt_stride, lp, no_speech_token, n_init, lang_ids, n_lang, tab, len, o2, rows, lang));
-    wm_model::SlotRef& r = m->slot_ref[slot];
-    if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    WMCHK(flush_held(m));
-    const NsAsk ns = no_speech_token >= 0 ? NsAsk{no_speech_token, n_init} : NsAsk();
-    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, &o2, false, nullptr, 0, nullptr, &rows, lp, ns, lang));
-    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, o2.n_prompt + 1 + o2.max_loop, false, lp, ns.token >= 0, true};
-    return 0;
+    return lang_entry(m, slot, mel, mel_on_device, B, o, prompts, prompt_len, prompt_stride, want_logprobs != 0, no_speech_token, n_init, lang_ids,
+                      n_lang, PassOut());
 }
 extern "C" int wm_transcribe_wait_lang(wm_model* m, int slot, int32_t* tokens_out, int32_t* n_tokens, float* token_logprobs, float* avg_logprob,
                                        float* no_speech_prob, int32_t* lang_out, float* lang_probs) {
     if (!m || !tokens_out || !n_tokens || !lang_out || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
     if (!token_logprobs != !avg_logprob) return fail(WM_E_ARG, "token_logprobs and avg_logprob go together");
-    return wait_impl(m, slot, tokens_out, n_tokens, nullptr, token_logprobs, avg_logprob, no_speech_prob, lang_out, lang_probs);
+    PassOut out = lp_out(tokens_out, n_tokens, token_logprobs, avg_logprob, no_speech_prob);
+    out.lang_out = lang_out;
+    out.lang_probs = lang_probs;
+    return collect_slot(m, slot, PassKind::transcribe, out);
 }
 // ---- token-level timestamps ------------------------------------------------------------------------------------
 extern "C" int wm_set_alignment_heads(wm_model* m, const int32_t* layer_head_pairs, int n_pairs) {
@@ -2879,9 +2913,6 @@ static int enqueue_align(wm_model* m, wm_state* s) {
     LCHK(launch_align_dtw(p, st));
     return 0;
 }
-
-extern "C" int wm_transcribe_pcm_tt(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o,
-                                    int32_t* tokens_out, int32_t* n_tokens, float* token_times);
 
 extern "C" int wm_alignment_weights(wm_model* m, int slot, float* out) {
     if (!m || !out || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
@@ -3000,21 +3031,11 @@ extern "C" int wm_op_token_times_rows(float* times, const float* weights, int n_
 // batch are zeroed.  stride >= n_prompt + 1 + max_loop of the pass.
 extern "C" int wm_transcribe_wait_device(wm_model* m, int slot, int32_t* dev_packed, int rows_cap, int stride) {
     if (!m || !dev_packed || slot < 0 || slot >= wm_model::NSLOT || stride <= 0) return fail(WM_E_ARG, "bad argument");
-    wm_model::SlotRef& r = m->slot_ref[slot];
-    if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
-    if (r.score) return fail(WM_E_STATE, "this slot holds a score pass (collect it with wm_score_wait)");
-    if (r.align) return fail(WM_E_STATE, "this slot holds an align pass (collect it with wm_align_wait)");
-    if (rows_cap < r.rows) return fail(WM_E_ARG, "rows_cap %d is smaller than the batch (%d)", rows_cap, r.rows);
-    if (stride < r.total) return fail(WM_E_ARG, "stride %d is smaller than the pass's ids per utterance (%d)", stride, r.total);
-    if (m->held.active && m->held.slot == slot) {
-        const int rc = flush_held(m);
-        if (rc) return rc;
-    }
-    wm_state* s = r.st;
-    const int rc = wait_on(m, s, nullptr, nullptr, r.row0, r.rows, dev_packed, rows_cap, stride);
-    if (!rc) m->last_steps[slot] = s->last_steps;
-    r = wm_model::SlotRef{};
-    return rc;
+    PassOut out;
+    out.dev_packed = dev_packed;
+    out.rows_cap = rows_cap;
+    out.pack_stride = stride;
+    return collect_slot(m, slot, PassKind::transcribe, out);
 }
 extern "C" int wm_transcribe_steps(wm_model* m, int slot) {
     if (!m || slot < 0 || slot >= wm_model::NSLOT) return -1;
@@ -3132,12 +3153,7 @@ extern "C" int wm_transcribe_pcm(wm_model* m, const float* pcm, const int32_t* n
     if (!m || !tokens_out || !n_tokens) return fail(WM_E_ARG, "bad argument");
     WMCHK(check_opts(m, o, B));
     WMCHK(frontend_run(m, pcm, n_samples, B, stride));  // same stream as the encoder: ordered, no host sync
-    WMCHK(flush_held(m));
-    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    WMCHK(submit_on(m, &m->cached, m->fe.mel.as<float>(), 1, B, o, true));
-    WMCHK(wait_on(m, m->cached, tokens_out, n_tokens));
-    m->last_steps[0] = m->cached->last_steps;
-    return 0;
+    return run_now(m, PassAsk{m->fe.mel.as<float>(), 1, B, o}, PassOut{tokens_out, n_tokens});
 }
 
 // n_frames[b] = min(2·n_audio_ctx, ceil(n_samples[b] / 160)): the attention mask of WhisperFeatureExtractor
@@ -3150,7 +3166,9 @@ extern "C" int wm_transcribe_pcm_tt(wm_model* m, const float* pcm, const int32_t
     std::vector<int32_t> cols;
     WMCHK(align_cols(m, nf.data(), B, cols));
     WMCHK(frontend_run(m, pcm, n_samples, B, stride));
-    return transcribe_impl(m, m->fe.mel.as<float>(), 1, B, o, &cols, tokens_out, n_tokens, token_times);
+    PassAsk ask{m->fe.mel.as<float>(), 1, B, o};
+    ask.cols = &cols;
+    return run_now(m, ask, PassOut{tokens_out, n_tokens, token_times});
 }
 
 // ---- transcript scoring --------------------------------------------------------------------------------------------
@@ -3342,11 +3360,10 @@ static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
     s->enq_done.store(true);
     return 0;
 }
-static int score_collect(wm_model* m, wm_state* s, float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob,
-                         float* token_times = nullptr) {
+static int score_collect(wm_model* m, wm_state* s, const PassOut& out) {
     if (!s || !s->pending || !s->sc.on) return fail(WM_E_STATE, "no score pass was submitted on this slot");
     HIPCHK(hipSetDevice(m->device));
-    const bool align = s->al.on;  // an align pass: token_times [B][stride] too, the log-probs only if it computed them
+    const bool align = s->al.on;  // an align pass: out.token_times [B][stride] too, the log-probs only if it computed them
     const hipError_t e = hipEventSynchronize(s->lanes[0].done);
     s->pending = false;  // afterwards the state holds no usable pass, exactly as after wm_transcribe
     s->has_enc = false;
@@ -3357,54 +3374,46 @@ static int score_collect(wm_model* m, wm_state* s, float* token_logprobs, int32_
     s->sc.timed = true;
     s->sc.timed_al = align;
     const size_t n = (size_t)s->B * s->sc.stride * 4;
-    if (token_times) HIPCHK(hipMemcpy(token_times, s->al.times.p, n, hipMemcpyDeviceToHost));
-    if (!token_logprobs) return 0;
-    HIPCHK(hipMemcpy(token_logprobs, s->sc.lp.p, n, hipMemcpyDeviceToHost));
-    if (top_ids) HIPCHK(hipMemcpy(top_ids, s->sc.top.p, n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(sum_logprob, s->sc.sum.p, (size_t)s->B * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(avg_logprob, s->sc.avg.p, (size_t)s->B * 4, hipMemcpyDeviceToHost));
+    if (out.token_times) HIPCHK(hipMemcpy(out.token_times, s->al.times.p, n, hipMemcpyDeviceToHost));
+    if (!out.token_logprobs) return 0;
+    HIPCHK(hipMemcpy(out.token_logprobs, s->sc.lp.p, n, hipMemcpyDeviceToHost));
+    if (out.top_ids) HIPCHK(hipMemcpy(out.top_ids, s->sc.top.p, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out.sum_logprob, s->sc.sum.p, (size_t)s->B * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out.avg_logprob, s->sc.avg.p, (size_t)s->B * 4, hipMemcpyDeviceToHost));
     return 0;
 }
-static int score_impl(wm_model* m, const float* mel, int mel_on_device, int B, const ScoreAsk& a, float* token_logprobs, int32_t* top_ids,
-                      float* sum_logprob, float* avg_logprob) {
-    WMCHK(flush_held(m));
-    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, nullptr, true, nullptr, 0, nullptr, nullptr, false, NsAsk(), LangAsk(), &a));
-    m->align_ref[0] = wm_model::AlignRef{};
-    return score_collect(m, m->cached, token_logprobs, top_ids, sum_logprob, avg_logprob);
+// the request and the outputs of a checked score / align call (a: the caller's ScoreAsk, alive for the call)
+static PassAsk score_ask(const float* mel, int mel_on_device, int B, const ScoreAsk& a) {
+    PassAsk ask{mel, mel_on_device, B};
+    ask.score = &a;
+    return ask;
+}
+static PassOut score_out(float* token_times, float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob) {
+    PassOut out;
+    out.token_times = token_times;
+    out.token_logprobs = token_logprobs;
+    out.top_ids = top_ids;
+    out.sum_logprob = sum_logprob;
+    out.avg_logprob = avg_logprob;
+    return out;
 }
 extern "C" int wm_score(wm_model* m, const float* mel, int mel_on_device, int B, int pos_mode, const int32_t* ids, const int32_t* ids_len,
                         int ids_stride, const int32_t* context_len, float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob) {
     if (!m || !mel || !token_logprobs || !sum_logprob || !avg_logprob) return fail(WM_E_ARG, "bad argument");
     WMCHK(score_check(m, B, pos_mode, ids, ids_len, ids_stride, context_len));
-    return score_impl(m, mel, mel_on_device, B, ScoreAsk{ids, ids_len, context_len, ids_stride, pos_mode}, token_logprobs, top_ids, sum_logprob,
-                      avg_logprob);
+    const ScoreAsk a{ids, ids_len, context_len, ids_stride, pos_mode};
+    return run_now(m, score_ask(mel, mel_on_device, B, a), score_out(nullptr, token_logprobs, top_ids, sum_logprob, avg_logprob));
 }
-// (never held for a coalesce = 2 partner: a score pass runs alone)
 extern "C" int wm_score_submit(wm_model* m, int slot, const float* mel, int mel_on_device, int B, int pos_mode, const int32_t* ids,
                                const int32_t* ids_len, int ids_stride, const int32_t* context_len) {
     if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
     WMCHK(score_check(m, B, pos_mode, ids, ids_len, ids_stride, context_len));
-    wm_model::SlotRef& r = m->slot_ref[slot];
-    if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    WMCHK(flush_held(m));
     const ScoreAsk a{ids, ids_len, context_len, ids_stride, pos_mode};
-    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, nullptr, false, nullptr, 0, nullptr, nullptr, false, NsAsk(), LangAsk(), &a));
-    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, ids_stride, false};
-    r.score = true;
-    return 0;
+    return submit_slot(m, slot, score_ask(mel, mel_on_device, B, a));
 }
 extern "C" int wm_score_wait(wm_model* m, int slot, float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob) {
     if (!m || !token_logprobs || !sum_logprob || !avg_logprob || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
-    wm_model::SlotRef& r = m->slot_ref[slot];
-    if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
-    if (r.align) return fail(WM_E_STATE, "this slot holds an align pass (collect it with wm_align_wait)");
-    if (!r.score) return fail(WM_E_STATE, "this slot holds a transcribe pass (collect it with wm_transcribe_wait)");
-    if (m->held.active && m->held.slot == slot) WMCHK(flush_held(m));
-    const int rc = score_collect(m, r.st, token_logprobs, top_ids, sum_logprob, avg_logprob);
-    m->align_ref[slot] = wm_model::AlignRef{};
-    r = wm_model::SlotRef{};
-    return rc;
+    return collect_slot(m, slot, PassKind::score, score_out(nullptr, token_logprobs, top_ids, sum_logprob, avg_logprob));
 }
 extern "C" int wm_score_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, int pos_mode, const int32_t* ids,
                             const int32_t* ids_len, int ids_stride, const int32_t* context_len, float* token_logprobs, int32_t* top_ids,
@@ -3412,8 +3421,8 @@ extern "C" int wm_score_pcm(wm_model* m, const float* pcm, const int32_t* n_samp
     if (!m || !token_logprobs || !sum_logprob || !avg_logprob) return fail(WM_E_ARG, "bad argument");
     WMCHK(score_check(m, B, pos_mode, ids, ids_len, ids_stride, context_len));
     WMCHK(frontend_run(m, pcm, n_samples, B, stride));  // same stream order as the encoder: no host sync
-    return score_impl(m, m->fe.mel.as<float>(), 1, B, ScoreAsk{ids, ids_len, context_len, ids_stride, pos_mode}, token_logprobs, top_ids,
-                      sum_logprob, avg_logprob);
+    const ScoreAsk a{ids, ids_len, context_len, ids_stride, pos_mode};
+    return run_now(m, score_ask(m->fe.mel.as<float>(), 1, B, a), score_out(nullptr, token_logprobs, top_ids, sum_logprob, avg_logprob));
 }
 extern "C" int wm_score_phases(wm_model* m, int slot, float* ms) {
     if (!m || !ms || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
@@ -3436,53 +3445,28 @@ static int align_check(wm_model* m, int B, int pos_mode, const int32_t* ids, con
     WMCHK(score_check(m, B, pos_mode, ids, ids_len, ids_stride, context_len));
     return align_cols(m, n_frames, B, cols);
 }
-static int align_impl(wm_model* m, const float* mel, int mel_on_device, int B, const ScoreAsk& a, float* token_times, float* token_logprobs,
-                      float* sum_logprob, float* avg_logprob) {
-    WMCHK(flush_held(m));
-    if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    WMCHK(submit_on(m, &m->cached, mel, mel_on_device, B, nullptr, true, nullptr, 0, nullptr, nullptr, false, NsAsk(), LangAsk(), &a));
-    const int rc = score_collect(m, m->cached, token_logprobs, nullptr, sum_logprob, avg_logprob, token_times);
-    m->align_ref[0] = rc ? wm_model::AlignRef{} : wm_model::AlignRef{m->cached, 0, B, m->cached->al.gen};
-    return rc;
-}
 extern "C" int wm_align(wm_model* m, const float* mel, int mel_on_device, int B, int pos_mode, const int32_t* ids, const int32_t* ids_len,
                         int ids_stride, const int32_t* context_len, const int32_t* n_frames, float* token_times, float* token_logprobs,
                         float* sum_logprob, float* avg_logprob) {
     if (!m || !mel || !token_times) return fail(WM_E_ARG, "bad argument");
     std::vector<int32_t> cols;
     WMCHK(align_check(m, B, pos_mode, ids, ids_len, ids_stride, context_len, n_frames, token_logprobs, sum_logprob, avg_logprob, cols));
-    return align_impl(m, mel, mel_on_device, B, ScoreAsk{ids, ids_len, context_len, ids_stride, pos_mode, &cols, token_logprobs != nullptr},
-                      token_times, token_logprobs, sum_logprob, avg_logprob);
+    const ScoreAsk a{ids, ids_len, context_len, ids_stride, pos_mode, &cols, token_logprobs != nullptr};
+    return run_now(m, score_ask(mel, mel_on_device, B, a), score_out(token_times, token_logprobs, nullptr, sum_logprob, avg_logprob));
 }
-// (never held for a coalesce = 2 partner: an align pass runs alone)
 extern "C" int wm_align_submit(wm_model* m, int slot, const float* mel, int mel_on_device, int B, int pos_mode, const int32_t* ids,
                                const int32_t* ids_len, int ids_stride, const int32_t* context_len, const int32_t* n_frames, int want_logprobs) {
     if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
     std::vector<int32_t> cols;
     WMCHK(align_check(m, B, pos_mode, ids, ids_len, ids_stride, context_len, n_frames, nullptr, nullptr, nullptr, cols));
-    wm_model::SlotRef& r = m->slot_ref[slot];
-    if (r.pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
-    WMCHK(flush_held(m));
     const ScoreAsk a{ids, ids_len, context_len, ids_stride, pos_mode, &cols, want_logprobs != 0};
-    WMCHK(submit_on(m, slot_state(m, slot), mel, mel_on_device, B, nullptr, false, nullptr, 0, nullptr, nullptr, false, NsAsk(), LangAsk(), &a));
-    r = wm_model::SlotRef{true, *slot_state(m, slot), 0, B, ids_stride, false, want_logprobs != 0};
-    r.align = true;
-    return 0;
+    return submit_slot(m, slot, score_ask(mel, mel_on_device, B, a));
 }
 extern "C" int wm_align_wait(wm_model* m, int slot, float* token_times, float* token_logprobs, float* sum_logprob, float* avg_logprob) {
     if (!m || !token_times || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
     if ((token_logprobs != nullptr) != (sum_logprob != nullptr) || (token_logprobs != nullptr) != (avg_logprob != nullptr))
         return fail(WM_E_ARG, "token_logprobs, sum_logprob and avg_logprob go together");
-    wm_model::SlotRef& r = m->slot_ref[slot];
-    if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
-    if (r.score) return fail(WM_E_STATE, "this slot holds a score pass (collect it with wm_score_wait)");
-    if (!r.align) return fail(WM_E_STATE, "this slot holds a transcribe pass (collect it with wm_transcribe_wait)");
-    if (token_logprobs && !r.lp) return fail(WM_E_STATE, "this slot's align pass was submitted without log-probabilities");
-    wm_state* s = r.st;
-    const int rc = score_collect(m, s, token_logprobs, nullptr, sum_logprob, avg_logprob, token_times);
-    m->align_ref[slot] = rc ? wm_model::AlignRef{} : wm_model::AlignRef{s, 0, r.rows, s->al.gen};
-    r = wm_model::SlotRef{};
-    return rc;
+    return collect_slot(m, slot, PassKind::align, score_out(token_times, token_logprobs, nullptr, sum_logprob, avg_logprob));
 }
 // n_frames from the sample counts, as wm_transcribe_pcm_tt
 extern "C" int wm_align_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, int pos_mode, const int32_t* ids,
@@ -3494,8 +3478,8 @@ extern "C" int wm_align_pcm(wm_model* m, const float* pcm, const int32_t* n_samp
     std::vector<int32_t> cols;
     WMCHK(align_check(m, B, pos_mode, ids, ids_len, ids_stride, context_len, nf.data(), token_logprobs, sum_logprob, avg_logprob, cols));
     WMCHK(frontend_run(m, pcm, n_samples, B, stride));  // same stream order as the encoder: no host sync
-    return align_impl(m, m->fe.mel.as<float>(), 1, B, ScoreAsk{ids, ids_len, context_len, ids_stride, pos_mode, &cols, token_logprobs != nullptr},
-                      token_times, token_logprobs, sum_logprob, avg_logprob);
+    const ScoreAsk a{ids, ids_len, context_len, ids_stride, pos_mode, &cols, token_logprobs != nullptr};
+    return run_now(m, score_ask(m->fe.mel.as<float>(), 1, B, a), score_out(token_times, token_logprobs, nullptr, sum_logprob, avg_logprob));
 }
 // ms[6]: wm_score_phases' five (LayerNorm, sweep and merge are 0 for a pass without log-probs) and the align chain
 extern "C" int wm_align_phases(wm_model* m, int slot, float* ms) {
@@ -3817,9 +3801,16 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
     std::vector<int32_t> toks((size_t)R * total), cnt(R);
     std::vector<float> lps(quality ? (size_t)R * total : 0), avg(R, 0.f), nsp(R, NAN);
     std::vector<wm_segment> segs;
-    auto collect = [&](int k) {
-        return wait_on(m, L.st[k], toks.data(), cnt.data(), 0, -1, nullptr, 0, 0, nullptr, quality ? lps.data() : nullptr, quality ? avg.data() : nullptr,
-                       ns.token >= 0 ? nsp.data() : nullptr);
+    PassOut out{toks.data(), cnt.data()};
+    out.token_logprobs = quality ? lps.data() : nullptr;
+    out.avg_logprob = quality ? avg.data() : nullptr;
+    out.no_speech_prob = ns.token >= 0 ? nsp.data() : nullptr;
+    auto collect = [&](int k) { return wait_on(m, L.st[k], 0, -1, out); };
+    auto window_ask = [&](int k, const wm_decode_opts* opts) {  // a pass over state k's gathered windows
+        PassAsk ask{L.win[k].as<float>(), 1, R, opts};
+        ask.lp = quality;
+        ask.ns = ns;
+        return ask;
     };
     auto drain = [&]() {  // an error mid-run: let the other pass finish before returning
         for (int k = 0; k < 2; ++k)
@@ -3838,12 +3829,7 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
             HIPCHK(hipMemcpyAsync(L.items[0].p, h.data(), (size_t)R * 3 * 4, hipMemcpyHostToDevice, m->stream));
             launch_window_gather(mel, L.items[0].as<int>(), L.win[0].as<float>(), R, c.n_mels, T, W, m->stream);
             HIPCHK(hipGetLastError());
-            LangAsk lang;
-            lang.ids = lang_ids;
-            lang.n = n_lang;
-            lang.sot = o->prompt[0];
-            lang.only = true;
-            WMCHK(submit_on(m, &L.st[0], L.win[0].as<float>(), 1, R, nullptr, false, nullptr, 0, nullptr, nullptr, false, NsAsk(), lang));
+            WMCHK(submit_on(m, &L.st[0], lang_only_ask(L.win[0].as<float>(), 1, R, lang_ids, n_lang, o->prompt[0])));
             HIPCHK(hipStreamSynchronize(L.st[0]->lanes[0].st));
             HIPCHK(hipMemcpy(lang_out + b0, L.st[0]->lg.out.p, (size_t)nb * 4, hipMemcpyDeviceToHost));
         }
@@ -3895,7 +3881,7 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
                 res->longest_prompt = std::max(res->longest_prompt, o->n_prompt);
                 std::fill(row_len[k].begin(), row_len[k].end(), o->n_prompt);
                 pass_total[k] = o->n_prompt + 1 + o->max_loop;
-                if (!rc) rc = submit_on(m, &L.st[k], L.win[k].as<float>(), 1, R, o, false, nullptr, 0, nullptr, nullptr, quality, ns);
+                if (!rc) rc = submit_on(m, &L.st[k], window_ask(k, o));
             } else if (!rc) {
                 wm_decode_opts o2;
                 RowPrompts rows;
@@ -3905,7 +3891,11 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
                     res->longest_prompt = std::max(res->longest_prompt, o2.n_prompt);
                     ++res->row_passes;
                 }
-                if (!rc) rc = submit_on(m, &L.st[k], L.win[k].as<float>(), 1, R, &o2, false, nullptr, 0, nullptr, &rows, quality, ns);
+                if (!rc) {
+                    PassAsk ask = window_ask(k, &o2);
+                    ask.rows = &rows;
+                    rc = submit_on(m, &L.st[k], ask);
+                }
             }
             if (rc) {
                 n_items[k] = 0;
