@@ -350,6 +350,16 @@ int wm_op_dec_linear_capmap(float* out, float* cap, const float* x, const float*
                             int B, int N, int K, int dtype, const int8_t* cap_sel, int cap_nsel, const int32_t* cap_map, int cap_dst);
 int wm_op_token_times_rows(float* times, const float* weights, int n_tab, int n_sel, int L, int T, const int32_t* R, const int32_t* F,
                            const int32_t* row0, int out_stride);
+/* The align chain's first two stages alone.  wm_op_align_probs: the probabilities of n_sel (layer, head) pairs (layer_head_pairs
+ * [n_sel][2]) over all T keys for the cross-q rows q [B][L][n_sel][64] (fp32, unscaled), utterance b's first rows[b] <= L rows.  Keys, one
+ * of: kv, a host fp32 K/V cache [n_layers][2][B][T][d] (K halves read, V halves present as in the model) uploaded as kv_dtype (WM_F32 /
+ * WM_BF16 / WM_F16), with X and Wk NULL; or the absorbed form, kv NULL, X [B][T][d] and Wk [n_layers][2][d][d] both uploaded as bf16,
+ * K_h = X·Wk_hᵀ formed on the device.  probs [B][n_sel][L][T] in and out: rows >= rows[b] keep the caller's values.
+ * wm_op_align_norm: wm_op_token_times_rows' tables through the normalisation only -> M [n_tab][L][T], in and out: cells outside table
+ * b's R[b] x F[b] corner keep the caller's values.  Both refuse with WM_E_ARG before anything is launched. */
+int wm_op_align_probs(float* probs, const float* q, const float* kv, int kv_dtype, const float* X, const float* Wk,
+                      const int32_t* layer_head_pairs, int n_sel, const int32_t* rows, int B, int L, int T, int d, int n_layers);
+int wm_op_align_norm(float* M, const float* weights, int n_tab, int n_sel, int L, int T, const int32_t* R, const int32_t* F);
 
 /* ---- log-mel front end --------------------------------------------------------------------------
  * Replaces the reference's call to HF WhisperProcessor (export_weights.py:100-116): 16 kHz mono PCM -> pad / trim to the

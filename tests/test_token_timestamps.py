@@ -1,7 +1,8 @@
 """CPU: a numpy restatement of the token-timestamp stage (normalise, median filter, head mean, DTW, jump times) equals HF's own
 times on every table of tests/golden/token_timestamps_tables.npz (made by tools/make_golden_token_timestamps.py from
 WhisperGenerationMixin._extract_token_timestamps).  The GPU tests lean on this restatement for the 16-bit configurations: its
-arithmetic is the kernels' (csrc/kernels_align.hip) operation for operation, so on the same weights the two agree bit for bit."""
+arithmetic is the kernels' (csrc/kernels_align.hip) operation for operation, so on the same weights the two agree bit for bit
+(tests/test_gpu_align_chain_op.py holds the kernels to that: the matrix `normalise` returns, and the times at the DTW's edges)."""
 import numpy as np
 import pytest
 
@@ -33,9 +34,11 @@ def normalise(w):
     return acc / np.float32(n_sel)
 
 
-def dtw_jumps(m):
+def dtw_jumps(m, stats=None):
     """HF _dynamic_time_warping on -m: fp32 cost, fp32(double(x) + double(c)), strict-comparison tie order; returns, per text row,
-    the time index where the path enters it."""
+    the time index where the path enters it.  stats (a dict): stats["ties"] counts the cells whose smallest finite predecessor cost
+    is held by more than one predecessor, where only the strictness of the comparisons decides."""
+    ties = 0
     x = -m.astype(np.float64)
     R, F = x.shape
     cost = np.full((R + 1, F + 1), np.inf, np.float32)
@@ -44,6 +47,9 @@ def dtw_jumps(m):
     for j in range(1, F + 1):
         for i in range(1, R + 1):
             c0, c1, c2 = cost[i - 1, j - 1], cost[i - 1, j], cost[i, j - 1]
+            if stats is not None:
+                lo = min(c0, c1, c2)
+                ties += bool(lo < np.inf) and int(c0 == lo) + int(c1 == lo) + int(c2 == lo) > 1
             if c0 < c1 and c0 < c2:
                 c, t = c0, 0
             elif c1 < c0 and c1 < c2:
@@ -66,6 +72,8 @@ def dtw_jumps(m):
             i -= 1
         else:
             j -= 1
+    if stats is not None:
+        stats["ties"] = int(ties)
     return jt
 
 

@@ -32,6 +32,7 @@ SYMBOLS = [
     "wm_transcribe_long_lang", "wm_transcribe_long_pcm_lang",
     "wm_score", "wm_score_submit", "wm_score_wait", "wm_score_pcm", "wm_op_score_logits", "wm_score_phases",
     "wm_align", "wm_align_submit", "wm_align_wait", "wm_align_pcm", "wm_align_phases", "wm_op_dec_linear_capmap", "wm_op_token_times_rows",
+    "wm_op_align_probs", "wm_op_align_norm",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -274,6 +275,8 @@ def lib():
     L.wm_align_phases.argtypes = [vp, C.c_int, fp]
     L.wm_op_dec_linear_capmap.argtypes = [fp] * 7 + [C.c_int] * 4 + [C.POINTER(C.c_int8), C.c_int, ip, C.c_int]
     L.wm_op_token_times_rows.argtypes = [fp, fp] + [C.c_int] * 4 + [ip, ip, ip, C.c_int]
+    L.wm_op_align_probs.argtypes = [fp, fp, fp, C.c_int, fp, fp, ip, C.c_int, ip] + [C.c_int] * 5
+    L.wm_op_align_norm.argtypes = [fp, fp] + [C.c_int] * 4 + [ip, ip]
     L.wm_long_result_quality.argtypes = [vp, C.c_int, fp, fp]
     L.wm_long_result_windows.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_int64), fp, fp, ip]
     L.wm_long_result_skip_stats.argtypes = [vp, ip]

@@ -3026,6 +3026,96 @@ extern "C" int wm_op_token_times_rows(float* times, const float* weights, int n_
     return 0;
 }
 
+// launch_align_probs alone.  Keys: kv (host fp32 [n_layers][2][B][T][d], the model's K/V cache with its V halves, uploaded as
+// kv_dtype) or the absorbed form X [B][T][d] + Wk [n_layers][2][d][d] (both uploaded as bf16, K_h built in a scratch buffer).
+// probs [B][n_sel][L][T] goes up before the launch and comes back after it: rows >= rows[b] keep what the caller put there.
+extern "C" int wm_op_align_probs(float* probs, const float* q, const float* kv, int kv_dtype, const float* X, const float* Wk,
+                                 const int32_t* layer_head_pairs, int n_sel, const int32_t* rows, int B, int L, int T, int d, int n_layers) {
+    if (!probs || !q || !layer_head_pairs || !rows) return fail(WM_E_ARG, "probs, q, layer_head_pairs and rows are required");
+    if (kv ? (X || Wk) : (!X || !Wk)) return fail(WM_E_ARG, "keys: either kv, or X and Wk");
+    if (kv && kv_dtype != WM_F32 && kv_dtype != WM_BF16 && kv_dtype != WM_F16) return fail(WM_E_ARG, "kv_dtype %d", kv_dtype);
+    if (B <= 0 || n_sel <= 0 || n_sel > ALIGN_MAX_HEADS || L <= 0 || L > ALIGN_MAX_ROWS || T <= 0 || d <= 0 || d % 64 || n_layers <= 0)
+        return fail(WM_E_ARG, "bad argument (B >= 1, 1 <= n_sel <= %d, 1 <= L <= %d, T >= 1, d a multiple of 64, n_layers >= 1)", ALIGN_MAX_HEADS,
+                    ALIGN_MAX_ROWS);
+    for (int b = 0; b < B; ++b)
+        if (rows[b] < 0 || rows[b] > L) return fail(WM_E_ARG, "utterance %d: rows in [0, L]", b);
+    for (int k = 0; k < n_sel; ++k)
+        if (layer_head_pairs[2 * k] < 0 || layer_head_pairs[2 * k] >= n_layers || layer_head_pairs[2 * k + 1] < 0 || layer_head_pairs[2 * k + 1] >= d / 64)
+            return fail(WM_E_ARG, "pair %d: layer in [0, %d), head in [0, %d)", k, n_layers, d / 64);
+    TmpDev t;
+    t.bufs.reserve(8);
+    DevBuf &cap = t.add(), &keys = t.add(), &wk = t.add(), &kh = t.add(), &pr = t.add(), &dr = t.add();
+    WMCHK(upload(cap, q, (size_t)B * L * n_sel * 64, WM_F32));
+    WMCHK(upload(pr, probs, (size_t)B * n_sel * L * T, WM_F32));
+    WMCHK(dr.alloc((size_t)B * 4));
+    HIPCHK(hipMemcpy(dr.p, rows, (size_t)B * 4, hipMemcpyHostToDevice));
+    AlignParams p{};
+    p.cap = cap.as<float>();
+    p.B = B;
+    p.L = L;
+    p.n_sel = n_sel;
+    p.T = T;
+    p.d = d;
+    p.rows = dr.as<int>();
+    if (kv) {
+        WMCHK(upload(keys, kv, (size_t)n_layers * 2 * B * T * d, kv_dtype));
+        p.kv = keys.p;
+        p.kv_dtype = kv_dtype;
+        p.kv_layer_stride = (long)((size_t)B * T * d);
+    } else {
+        WMCHK(upload(keys, X, (size_t)B * T * d, WM_BF16));
+        WMCHK(upload(wk, Wk, (size_t)n_layers * 2 * d * d, WM_BF16));
+        WMCHK(kh.alloc((size_t)B * n_sel * T * 64 * 4));
+        p.X = keys.p;
+        p.Wk = wk.p;
+        p.kh = kh.as<float>();
+    }
+    for (int k = 0; k < n_sel; ++k) {
+        p.layer[k] = layer_head_pairs[2 * k];
+        p.head[k] = layer_head_pairs[2 * k + 1];
+    }
+    p.probs = pr.as<float>();
+    LCHK(launch_align_probs(p, nullptr));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(probs, pr.p, (size_t)B * n_sel * L * T * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// launch_align_norm alone: wm_op_token_times_rows' tables -> M [n_tab][L][T], uploaded first (cells outside a table's R x F corner keep
+// what the caller put there).
+extern "C" int wm_op_align_norm(float* M, const float* weights, int n_tab, int n_sel, int L, int T, const int32_t* R, const int32_t* F) {
+    if (!M || !weights || !R || !F || n_tab <= 0 || n_sel <= 0 || n_sel > ALIGN_MAX_HEADS || L <= 0 || L > ALIGN_MAX_ROWS || T <= 0)
+        return fail(WM_E_ARG, "bad argument (1 <= n_sel <= %d, 1 <= L <= %d, T >= 1)", ALIGN_MAX_HEADS, ALIGN_MAX_ROWS);
+    for (int b = 0; b < n_tab; ++b)
+        if (R[b] < 0 || R[b] > L || F[b] < 1 || F[b] > T) return fail(WM_E_ARG, "table %d: R in [0, L], F in [1, T]", b);
+    TmpDev t;
+    t.bufs.reserve(8);
+    DevBuf &probs = t.add(), &mean = t.add(), &sd = t.add(), &dm = t.add(), &dr = t.add(), &df = t.add();
+    WMCHK(upload(probs, weights, (size_t)n_tab * n_sel * L * T, WM_F32));
+    WMCHK(upload(dm, M, (size_t)n_tab * L * T, WM_F32));
+    WMCHK(mean.alloc((size_t)n_tab * n_sel * T * 4));
+    WMCHK(sd.alloc((size_t)n_tab * n_sel * T * 4));
+    for (auto pr : {std::make_pair(&dr, R), std::make_pair(&df, F)}) {
+        WMCHK(pr.first->alloc((size_t)n_tab * 4));
+        HIPCHK(hipMemcpy(pr.first->p, pr.second, (size_t)n_tab * 4, hipMemcpyHostToDevice));
+    }
+    AlignParams p{};
+    p.B = n_tab;
+    p.L = L;
+    p.n_sel = n_sel;
+    p.T = T;
+    p.n_frames = df.as<int>();
+    p.rows = dr.as<int>();
+    p.probs = probs.as<float>();
+    p.mean = mean.as<float>();
+    p.stdv = sd.as<float>();
+    p.M = dm.as<float>();
+    LCHK(launch_align_norm(p, nullptr));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(M, dm.p, (size_t)n_tab * L * T * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // wm_transcribe_wait with the result left ON THE DEVICE as the gather buffer of the multi-GPU path: dev_packed
 // [rows_cap, 1 + stride] int32 in the caller's device memory (e.g. a torch tensor), row r = [length, ids zero-padded]; rows past the
 // batch are zeroed.  stride >= n_prompt + 1 + max_loop of the pass.

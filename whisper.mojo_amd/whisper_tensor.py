@@ -297,3 +297,53 @@ def xattn(out: np.ndarray, q, Wk, Wv, bv, x, n_heads: int, nsplit: int, q_B: int
     _chk_out(out, q.shape)
     _lib.check(_lib.lib().wm_op_xattn(_fp(out), _fp(q), _fp(Wk), _fp(Wv), _fp(bv), _fp(x), q.shape[0], q_B, x.shape[0], x.shape[1],
                                       n_heads, nsplit, out_dtype))
+
+
+def align_probs(q, layer_head_pairs, rows, n_layers: int, kv=None, kv_dtype=DT_F32, X=None, Wk=None, probs=None):
+    """launch_align_probs alone (wm_op_align_probs): q [B, L, n_sel, 64] unscaled cross-q rows, layer_head_pairs [n_sel, 2], rows [B]
+    (utterance b's first rows[b] <= L rows count).  Keys: kv [n_layers, 2, B, T, d] (the K/V cache, uploaded as kv_dtype) or the
+    absorbed form X [B, T, d] + Wk [n_layers, 2, d, d] (uploaded as bf16).  probs [B, n_sel, L, T] in and out (None: zeros):
+    softmax_j(0.125·q_r·K_j) in rows < rows[b], untouched elsewhere."""
+    f = lambda a: np.ascontiguousarray(a, np.float32)
+    q = f(q)
+    pairs = np.ascontiguousarray(layer_head_pairs, np.int32)
+    rows = np.ascontiguousarray(rows, np.int32).ravel()
+    if q.ndim != 4 or q.shape[3] != 64 or pairs.ndim != 2 or pairs.shape != (q.shape[2], 2) or rows.size != q.shape[0]:
+        raise ValueError("q must be [B, L, n_sel, 64], layer_head_pairs [n_sel, 2], rows [B]")
+    B, L, n_sel, _ = q.shape
+    if (kv is None) == (X is None and Wk is None) or (X is None) != (Wk is None):
+        raise ValueError("keys: either kv, or X and Wk")
+    if kv is not None:
+        kv = f(kv)
+        if kv.ndim != 5 or kv.shape[:3] != (n_layers, 2, B):
+            raise ValueError("kv must be [n_layers, 2, B, T, d]")
+        T, d = kv.shape[3:]
+    else:
+        X, Wk = f(X), f(Wk)
+        if X.ndim != 3 or X.shape[0] != B or Wk.shape != (n_layers, 2, X.shape[2], X.shape[2]):
+            raise ValueError("X must be [B, T, d], Wk [n_layers, 2, d, d]")
+        T, d = X.shape[1:]
+    if probs is None:
+        probs = np.zeros((B, n_sel, L, T), np.float32)
+    _chk_out(probs, (B, n_sel, L, T))
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    _lib.check(_lib.lib().wm_op_align_probs(_fp(probs), _fp(q), _fp(kv), int(kv_dtype), _fp(X), _fp(Wk), ip(pairs), n_sel, ip(rows), B, L, T, d,
+                                            int(n_layers)))
+    return probs
+
+
+def align_norm(weights, R, F, M=None):
+    """launch_align_norm alone (wm_op_align_norm): weights [n_tab, n_sel, L, T], table b's R[b] x F[b] corner -> M [n_tab, L, T], in
+    and out (None: zeros): z-score over the rows, width-7 reflect median over the columns, mean over the heads inside the corner,
+    untouched elsewhere."""
+    w = np.ascontiguousarray(weights, np.float32)
+    R, F = np.ascontiguousarray(R, np.int32).ravel(), np.ascontiguousarray(F, np.int32).ravel()
+    if w.ndim != 4 or R.size != w.shape[0] or F.size != w.shape[0]:
+        raise ValueError("weights must be [n_tab, n_sel, L, T], R and F [n_tab]")
+    n_tab, n_sel, L, T = w.shape
+    if M is None:
+        M = np.zeros((n_tab, L, T), np.float32)
+    _chk_out(M, (n_tab, L, T))
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    _lib.check(_lib.lib().wm_op_align_norm(_fp(M), _fp(w), n_tab, n_sel, L, T, ip(R), ip(F)))
+    return M
