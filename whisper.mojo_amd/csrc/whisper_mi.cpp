@@ -348,13 +348,11 @@ struct wm_state {
     std::vector<Lane> lanes;
     hipEvent_t enc_done = nullptr;
     hipStream_t enc_stream = nullptr;  // stream the pending pass's encoder was enqueued on
-    int graph_eot = 0, graph_ignore = 0;
-    bool graphs_valid = false;
+    bool graphs_valid = false;  // the lanes' graphs hold graph_step (false also after invalidate_step_graphs)
     bool pending = false;   // a submitted pass has not been waited for yet
     int halves_left = 0;    // coalesced pair: slots that have not collected their rows yet
     bool synced = false;    // the pending pass's completion has been waited for (second half of a pair does not wait again)
     bool shares_chip = false;  // this state's passes run beside other passes (pipelined entry): K/V stream at two workgroups per CU
-    bool graph_shares = false;
     int trace_id = 1;       // slot + 1: tags this state's entries in the developer timeline
     int pend_total = 0;     // ids per utterance of the pending pass
     // Greedy loop of the pending pass, enqueued in sub-chunks of LOOP_CHUNK steps with at most two sub-chunks queued ahead of the GPU
@@ -369,10 +367,26 @@ struct wm_state {
     int enq_rc = 0;                    // status of the pump's enqueues
     std::string enq_err;
     int last_steps = -1;               // loop steps enqueued for the most recent completed pass (wm_transcribe_steps)
-    struct LoopOpts {
+    // Everything a step of the greedy loop depends on beside the device buffers: loop_step runs `step`, the lanes' graphs
+    // hold `graph_step`, a pass recaptures when they differ.  Whatever loop_step reads from the state must be a field here.
+    struct StepKey {
         int eot = 0, ignore_eot = 0;
-        TsRules rules{};
-    } loop_opts;
+        TsRules rules{};           // timestamp rules (tb <= 0: off)
+        bool shares_chip = false;  // K/V stream at two workgroups per CU
+        struct Cap {               // the alignment-head capture: al.cap.p, al.L, al.n_prompt, al.pairs of a timestamp pass, else empty
+            const void* buf = nullptr;
+            int L = 0, n_prompt = 0;
+            std::vector<int32_t> pairs;
+            bool operator==(const Cap& o) const { return buf == o.buf && L == o.L && n_prompt == o.n_prompt && pairs == o.pairs; }
+        } cap;
+        bool rows = false, lp = false;  // self-attention in the key-window form (rw.on); log-probabilities (lp.on)
+        bool operator==(const StepKey& o) const {
+            return eot == o.eot && ignore_eot == o.ignore_eot && rules.tb == o.rules.tb && rules.eos == o.rules.eos &&
+                   rules.max_init == o.rules.max_init && rules.vocab == o.rules.vocab && shares_chip == o.shares_chip && cap == o.cap &&
+                   rows == o.rows && lp == o.lp;
+        }
+    };
+    StepKey step, graph_step;
     const float* last_mel = nullptr;  // device pointer of the last encoded batch (bench replays the encoder on it)
     // encoder arena (sized for Bc utterances)
     DevBuf mel_dev, mel_t, h1, x, xn, qkv, ao, hid, enc_t;
@@ -387,7 +401,6 @@ struct wm_state {
     bool masks_valid = false;
     static const int PREFILL_MAX = 16;  // prompt positions decoded in one pass (= the n_prompt bound of wm_decode_opts)
     DevBuf ts_state, ts_val, ts_idx, ts_m, ts_s;  // timestamp rules: per-utterance history / ranges, per-part timestamp partials
-    TsRules graph_rules{};                         // rules baked into the captured step graph
     int no_ts_cached = -1;
     DevBuf dx, dq, dattn, dhid, part_o, part_ml, logits, amax_val, amax_idx, tok, pos, tok_rows, pos_rows, ctl, out_tokens, n_tokens, finished;
     int npart = 0;  // fused-argmax partials per utterance = workgroups per row block of the logits kernel
@@ -407,12 +420,6 @@ struct wm_state {
         std::vector<int32_t> h_rows, h_row0, h_map;
         DevBuf rows, row0, map;
     } al;
-    struct CapKey {  // the capture baked into the captured step graph
-        const void* cap = nullptr;
-        int L = 0, n_prompt = 0;
-        std::vector<int32_t> pairs;
-        bool operator!=(const CapKey& o) const { return cap != o.cap || L != o.L || n_prompt != o.n_prompt || pairs != o.pairs; }
-    } graph_cap;
     // per-row prompts of the pending pass (on = wm_transcribe_rows and its kin).  Buffers are allocated by the first such
     // pass: table [B][n_text_ctx] ids, len [B], key_lo [B] (first cache row of each utterance's own keys).
     struct Rows {
@@ -421,7 +428,6 @@ struct wm_state {
         DevBuf table, len, key_lo;
         std::vector<int32_t> h_table, h_len;
     } rw;
-    bool graph_rows = false;  // the captured step graph's self-attention is the key-window form
     // log-probabilities of the pending pass (on = wm_transcribe_lp and its kin): stage 1's text-side sums [B][npart], the
     // table [B][out_stride] that mirrors out_tokens (zeroed by the init-tokens launch) and the per-row sums.  Part of the arena.
     struct Lp {
@@ -429,7 +435,6 @@ struct wm_state {
         DevBuf part_s, table, sum;
         std::vector<int32_t> n_prompt;  // [B] prompt length of each row of the pending pass
     } lp;
-    bool graph_lp = false;  // the captured step graph computes log-probabilities
     // no-speech probe of the pending pass (on = wm_transcribe_lp_ns and its kin, always with lp.on): the residual rows
     // of the <|startoftranscript|> position [B][d], the probe's OWN sweep partials [B][npart] (the step's amax / lp_s partials and
     // the control block are not touched) and the results [B].  Part of the arena; runs outside the captured step graph.
@@ -1142,6 +1147,7 @@ extern "C" int wm_state_len(const wm_state* s) { return state_is_live(s) ? s->ho
 
 // ---- encoder: whisper.mojo:71-99 ------------------------------------------------------------------------------------
 static void* off_bytes(const DevBuf& b, size_t bytes) { return (char*)b.p + bytes; }
+static const float ATTN_SCALE = 1.0f / sqrtf(64.0f);  // every attention here has heads of 64 columns
 
 static int cross_kv_chunk(wm_model* m, wm_state* s, int c0, int bc, hipStream_t st) {
     // cross K/V for utterances [c0, c0+bc) from enc_t (rows 0..bc*T): layers.mojo:150-154, all layers in one GEMM
@@ -1169,12 +1175,11 @@ static int cross_kv_chunk(wm_model* m, wm_state* s, int c0, int bc, hipStream_t 
 // LayerNorm in its epilogue (16-bit operands, d = 384) `ln_post` rides there: no LayerNorm launch, no 147 MB fp32 write per pass.
 // BOTH kinds of caller take the operand rows from the same epilogue, so wm_encode + wm_decode_step and wm_transcribe see
 // bit-identical cross-K/V (round 2 had fused it for the transcribe paths only and reverted: the two entry points parted at a near-tie).
-static int run_encoder(wm_model* m, wm_state* s, const float* mel_dev, int B, hipStream_t st, const float* mel2 = nullptr, int split_at = 0,
-                       bool want_f32 = true) {
+static int run_encoder(wm_model* m, wm_state* s, const float* mel_dev, int B, hipStream_t st, const float* mel2, int split_at,
+                       bool want_f32) {
     const wm_dims& c = m->cfg.dims;
     const int T = m->cfg.compute_dtype;
     const size_t d = c.d_model, L = 2 * (size_t)c.n_audio_ctx, NT = c.n_audio_ctx, ts = dt_size(T);
-    const float scale = 1.0f / sqrtf(64.0f);
     for (int c0 = 0; c0 < B; c0 += s->Bc) {
         const int bc = std::min(s->Bc, B - c0);
         const int M = (int)(bc * NT);
@@ -1246,7 +1251,7 @@ static int run_encoder(wm_model* m, wm_state* s, const float* mel_dev, int B, hi
                 WMCHK(gemm_dispatch(T, T, p, 1, st));
             else
                 WMCHK(ln_then_gemm(T, T, p, s->x.as<float>(), w.ln1_g.as<float>(), w.ln1_b.as<float>(), st));
-            DISPATCH_DT(T, TT, launch_flash_attn_enc<TT>(s->qkv.p, s->ao.p, bc, c.n_heads, c.n_audio_ctx, scale, st));
+            DISPATCH_DT(T, TT, launch_flash_attn_enc<TT>(s->qkv.p, s->ao.p, bc, c.n_heads, c.n_audio_ctx, ATTN_SCALE, st));
             GemmParams o{};
             o.A = s->ao.p;
             o.W = w.o_w.p;
@@ -1391,6 +1396,18 @@ struct DecView {
     StepCtl* ctl;
 };
 static DecView whole_batch(wm_model* m, wm_state* s) { return DecView{0, s->B, m->stream, s->ctl.as<StepCtl>()}; }
+template <typename T> static T* lane_ptr(const DevBuf& buf, const DecView& v, size_t stride) { return buf.as<T>() + (size_t)v.b0 * stride; }  // view v's rows
+
+// What a sweep over the tied embedding reads: the final LayerNorm and the embedding in the decoder's operand dtype
+struct VocabHead {
+    const float *ln_g, *ln_b;
+    const void* emb;
+    int vocab, d_model;
+};
+static VocabHead vocab_head(const wm_model* m) {
+    return VocabHead{m->dec_ln_g.as<float>(), m->dec_ln_b.as<float>(), dec_dtype(m->cfg) == WM_F32 ? m->tok_emb_f.p : m->tok_emb_t.p,
+                     m->cfg.dims.vocab, m->cfg.dims.d_model};
+}
 
 // m->xattn: the cross-attention of layer l over X for the rows of view v (P positions each): absorb + X sweep (launch_cross_attn),
 // then merge + V-apply into out (cross_attn_merge).  Rows are position-major as everywhere in decode_core.
@@ -1398,7 +1415,7 @@ static XAttnParams xattn_params(wm_model* m, wm_state* s, int l, const DecView& 
     const wm_dims& c = m->cfg.dims;
     const size_t d = c.d_model;
     XAttnParams x{};
-    x.q = s->dq.as<float>() + (size_t)v.b0 * d;
+    x.q = lane_ptr<float>(s->dq, v, d);
     x.Wk = off_bytes(m->cross_kv_w, (size_t)(2 * l) * d * d * 2);
     x.Wv = off_bytes(m->cross_kv_w, (size_t)(2 * l + 1) * d * d * 2);
     x.bv = m->cross_kv_b.as<float>() + (size_t)(2 * l + 1) * d;
@@ -1410,10 +1427,10 @@ static XAttnParams xattn_params(wm_model* m, wm_state* s, int l, const DecView& 
     x.d = c.d_model;
     x.rows = v.nb * P;
     x.q_B = P > 1 ? v.nb : 0;
-    x.scale = 1.0f / sqrtf(64.0f);
+    x.scale = ATTN_SCALE;
     x.qs = off_bytes(s->xq, (size_t)v.b0 * 3 * c.n_heads * d * 2);
-    x.part_y = s->part_y.as<float>() + (size_t)v.b0 * s->nsplit * c.n_heads * d;
-    x.part_ml = s->part_ml.as<float>() + (size_t)v.b0 * s->nsplit * c.n_heads * 2;
+    x.part_y = lane_ptr<float>(s->part_y, v, s->nsplit * c.n_heads * d);
+    x.part_ml = lane_ptr<float>(s->part_ml, v, (size_t)s->nsplit * c.n_heads * 2);
     return x;
 }
 static int cross_attn_merge(wm_model* m, wm_state* s, int l, const DecView& v, int P, void* out, int out_dtype) {
@@ -1423,7 +1440,7 @@ static int cross_attn_merge(wm_model* m, wm_state* s, int l, const DecView& v, i
     return launch_rc(launch_xattn_merge(x, v.st));
 }
 
-static int launch_cross_attn(wm_model* m, wm_state* s, int l, const DecView& v, int P = 1) {
+static int launch_cross_attn(wm_model* m, wm_state* s, int l, const DecView& v, int P) {
     if (m->xattn) {
         const XAttnParams x = xattn_params(m, s, l, v, P);
         WMCHK(launch_rc(launch_xattn_absorb(x, v.st)));
@@ -1434,16 +1451,16 @@ static int launch_cross_attn(wm_model* m, wm_state* s, int l, const DecView& v, 
     const size_t cross_l = (size_t)s->B * c.n_audio_ctx * d;
     const size_t boff = (size_t)v.b0 * c.n_audio_ctx * d;
     AttnDecParams a{};
-    a.q = s->dq.as<float>() + (size_t)v.b0 * d;
+    a.q = lane_ptr<float>(s->dq, v, d);
     a.K = off_bytes(s->cross_kv, ((size_t)(2 * l) * cross_l + boff) * ks);
     a.V = off_bytes(s->cross_kv, ((size_t)(2 * l + 1) * cross_l + boff) * ks);
     a.batch_stride = (long)((size_t)c.n_audio_ctx * d);
     a.n_keys = c.n_audio_ctx;
     a.ctl = v.ctl;
     a.nsplit = s->nsplit;
-    a.scale = 1.0f / sqrtf(64.0f);
-    a.part_o = s->part_o.as<float>() + (size_t)v.b0 * s->nsplit * d;
-    a.part_ml = s->part_ml.as<float>() + (size_t)v.b0 * s->nsplit * c.n_heads * 2;
+    a.scale = ATTN_SCALE;
+    a.part_o = lane_ptr<float>(s->part_o, v, s->nsplit * d);
+    a.part_ml = lane_ptr<float>(s->part_ml, v, (size_t)s->nsplit * c.n_heads * 2);
     a.H = c.n_heads;
     a.d = c.d_model;
     a.B = v.nb * P;
@@ -1459,133 +1476,159 @@ static int launch_cross_attn(wm_model* m, wm_state* s, int l, const DecView& v, 
     return attn_decode_dispatch(m->cfg.kv_dtype, a, v.st);
 }
 
-// want_logits: run the final LN + vocabulary projection.  full_logits: also materialise [B, vocab] fp32 (stage tests,
-// wm_decode_step); the greedy loop only needs the fused-argmax partials.
-// P > 1: prompt prefill — P positions of every utterance in ONE pass (whisper.mojo:195: the q_len = n_prompt block).  Rows are
-// position-major (row = t * B + b), tokens / positions come from tok_rows / pos_rows, K/V rows go to cache rows len + t, the
-// self-attention of position t sees keys 0..len+t (the causal mask of layers.mojo:309-318), logits only for the last
-// position.  Every row's arithmetic is what the single-position pass does for it, so the ids are the same bit for bit.
-static int decode_core(wm_model* m, wm_state* s, const DecView& v, bool want_logits, bool full_logits = false,
-                       const float* mask = nullptr, int P = 1, bool embed = true, const TsRules* rules = nullptr, bool capture = false,
-                       int t0 = -1,  // t0 >= 0: a chunk of a per-row prefill — tokens / positions are rows [t0, t0 + P) of tok_rows / pos_rows
-                       bool key_window = true) {  // false: no per-row key windows even on a per-row pass (the language pass, §19)
+// What one decode_core call does: by default a single-position step that embeds its input and produces no logits.
+enum class Logits { none, partials, full };  // partials: the fused-argmax partials only (the greedy loop); full: also [B, vocab] fp32
+struct DecPass {
+    // P > 1: prompt prefill — P positions of every utterance in ONE pass (whisper.mojo:195: the q_len = n_prompt block).  Rows are
+    // position-major (row = t * B + b), tokens / positions come from tok_rows / pos_rows, K/V rows go to cache rows len + t, position
+    // t sees keys 0..len+t (the causal mask of layers.mojo:309-318), logits only for the last position.  Every row's arithmetic is
+    // what the single-position pass does for it, so the ids are the same bit for bit.
+    int P = 1;
+    int t0 = -1;        // t0 >= 0: a chunk of a per-row prefill — tokens / positions are rows [t0, t0 + P) of tok_rows / pos_rows
+    bool embed = true;  // false: the input rows are in dx already (the greedy loop: written by the previous step's argmax launch)
+    Logits logits = Logits::none;   // the final LN + vocabulary projection
+    const float* mask = nullptr;    // additive logit mask of the fused argmax
+    const TsRules* rules = nullptr;  // timestamp rules (null or tb <= 0: off)
+    bool capture = false;           // a timestamp pass (al.on) also stores the alignment heads' cross-q rows
+    bool key_window = true;         // false: no per-row key windows even on a per-row pass (the language pass, §19)
+};
+// What every linear launch of a decoder pass sets (ln_g null: no LayerNorm prologue); each block's special part is added by name below
+static DecLinearParams linear_block(const float* x, const float* ln_g, const float* ln_b, const void* W, const float* bias, int N, int K, int B,
+                                 float* out, int ldo) {
+    DecLinearParams p{};
+    p.x = x;
+    p.ldx = K;
+    p.ln_g = ln_g;
+    p.ln_b = ln_b;
+    p.W = W;
+    p.N = N;
+    p.K = K;
+    p.B = B;
+    p.bias = bias;
+    p.out = out;
+    p.ldo = ldo;
+    return p;
+}
+static void* self_kv_rows(wm_model* m, wm_state* s, const DecView& v, int l, int k_or_v) {  // layer l's cached K (0) / V (1) rows of view v
+    const size_t per_utt = (size_t)m->cfg.dims.n_text_ctx * m->cfg.dims.d_model;
+    return off_bytes(s->self_kv, ((size_t)(2 * l + k_or_v) * s->B + v.b0) * per_utt * dt_size(m->cfg.kv_dtype));
+}
+static void add_cache_append(DecLinearParams& p, wm_model* m, wm_state* s, const DecView& v, int l, int P) {  // k, v to cache row len (+ t)
+    const wm_dims& c = m->cfg.dims;
+    p.kcache = self_kv_rows(m, s, v, l, 0);
+    p.vcache = self_kv_rows(m, s, v, l, 1);
+    p.kv_batch_stride = (long)((size_t)c.n_text_ctx * c.d_model);
+    p.d_model = c.d_model;
+    p.kv_dtype = m->cfg.kv_dtype;
+    p.kv_B = P > 1 ? v.nb : 0;
+    p.ctl = v.ctl;
+}
+static void add_align_capture(DecLinearParams& p, const wm_state::Align& al, int l, const DecView& v, int t0) {  // layer l's alignment heads
+    for (int h = 0; h < 32; ++h) p.cap_sel[h] = -1;
+    const int n_sel = (int)al.pairs.size() / 2;
+    bool any = false;
+    for (int k = 0; k < n_sel; ++k)
+        if (al.pairs[2 * k] == l) {
+            p.cap_sel[al.pairs[2 * k + 1]] = (signed char)k;
+            any = true;
+        }
+    if (any && al.ragged) {  // an align pass's chunk: rows [t0, t0 + P) of the row map (single-lane: b0 = 0)
+        p.cap = al.cap.as<float>();
+        p.cap_map = al.map.as<int>() + (size_t)std::max(t0, 0) * v.nb;
+        p.cap_nsel = n_sel;
+    } else if (any) {
+        p.cap_row_stride = (long)al.L * n_sel * 64;
+        p.cap = al.cap.as<float>() + (size_t)v.b0 * p.cap_row_stride;
+        p.cap_step0 = al.n_prompt;
+        p.cap_steps = al.L;
+        p.cap_nsel = n_sel;
+        p.ctl = v.ctl;  // the step index comes from the cache length (the row map needs none)
+    }
+}
+static void add_gelu_t(DecLinearParams& p, int gelu_mode) {  // GELU, stored in the operand dtype for the next MFMA
+    p.act = 1;
+    p.gelu_mode = gelu_mode;
+    p.out_is_t = 1;
+}
+static void add_argmax_partials(DecLinearParams& p, wm_state* s, const DecView& v, const float* mask, const TsRules* rules) {
+    p.amax_val = lane_ptr<float>(s->amax_val, v, s->npart);
+    p.amax_idx = lane_ptr<int>(s->amax_idx, v, s->npart);
+    p.amax_stride = s->npart;
+    p.amax_mask = mask;
+    if (rules && rules->tb > 0) {  // timestamp rules: split the candidates by the utterances' admissible ranges
+        p.ts_state = lane_ptr<TsState>(s->ts_state, v, 1);
+        p.ts_begin = rules->tb;
+        p.ts_val = lane_ptr<float>(s->ts_val, v, s->npart);
+        p.ts_idx = lane_ptr<int>(s->ts_idx, v, s->npart);
+        p.ts_m = lane_ptr<float>(s->ts_m, v, s->npart);
+        p.ts_s = lane_ptr<float>(s->ts_s, v, s->npart);
+    }
+    if (s->lp.on) p.lp_s = lane_ptr<float>(s->lp.part_s, v, s->npart);
+}
+// LN1 -> q | k,v appended to the cache   (layers.mojo:118-147)
+static DecLinearParams qkv_block(wm_model* m, wm_state* s, const DecView& v, int l, int P) {
+    const wm_dims& c = m->cfg.dims;
+    const DecLayer& w = m->dec[l];
+    DecLinearParams p = linear_block(lane_ptr<float>(s->dx, v, c.d_model), w.ln1_g.as<float>(), w.ln1_b.as<float>(), w.sqkv_w.p, w.sqkv_b.as<float>(),
+                                  3 * c.d_model, c.d_model, v.nb * P, lane_ptr<float>(s->dq, v, c.d_model), c.d_model);
+    add_cache_append(p, m, s, v, l, P);
+    return p;
+}
+// x += in·Wᵀ + b, `in` in operand dtype (what the attention / fc1 launches hand over)
+static DecLinearParams proj_residual_block(wm_model* m, wm_state* s, const DecView& v, int P, const float* in, int K, const DevBuf& W, const DevBuf& bias) {
+    const wm_dims& c = m->cfg.dims;
+    float* dx = lane_ptr<float>(s->dx, v, c.d_model);
+    DecLinearParams p = linear_block(in, nullptr, nullptr, W.p, bias.as<float>(), c.d_model, K, v.nb * P, dx, c.d_model);
+    p.x_is_t = 1;
+    p.residual = dx;
+    p.ldr = c.d_model;
+    return p;
+}
+
+static int decode_core(wm_model* m, wm_state* s, const DecView& v, const DecPass& a) {
     const wm_dims& c = m->cfg.dims;
     const int T = dec_dtype(m->cfg), KV = m->cfg.kv_dtype;  // T: the decoder's operand dtype
-    const int B = v.nb * P;          // activation rows of this pass
+    const int P = a.P, B = v.nb * P;  // B: activation rows of this pass
     const int qB = P > 1 ? v.nb : 0;  // position-major row mapping on
-    const size_t d = c.d_model, ks = dt_size(KV);
+    const size_t d = c.d_model;
     hipStream_t st = v.st;
-    const StepCtl* ctl = v.ctl;
-    const float scale = 1.0f / sqrtf(64.0f);
-    const size_t self_l = (size_t)s->B * c.n_text_ctx * d;  // elements per (layer, K|V)
-    const size_t self_b = (size_t)v.b0 * c.n_text_ctx * d;
-    float* dx = s->dx.as<float>() + (size_t)v.b0 * d;
-    float* dq = s->dq.as<float>() + (size_t)v.b0 * d;
+    float* dx = lane_ptr<float>(s->dx, v, d);
+    float* dq = lane_ptr<float>(s->dq, v, d);
     // attention output / MLP hidden rows: operand dtype T (fp32 buffers, used at T's width)
     float* dattn = (float*)off_bytes(s->dattn, (size_t)v.b0 * d * dt_size(T));
     float* dhid = (float*)off_bytes(s->dhid, (size_t)v.b0 * c.ffn * dt_size(T));
-    if (embed)  // (the greedy loop's steps get their input row from the previous step's argmax launch instead)
-        launch_dec_embed(m->tok_emb_f.as<float>(), m->dec_pos.as<float>(),
-                     t0 >= 0 ? s->tok_rows.as<int>() + (size_t)t0 * v.nb : P > 1 ? s->tok_rows.as<int>() : s->tok.as<int>() + v.b0,
-                     t0 >= 0 ? s->pos_rows.as<int>() + (size_t)t0 * v.nb : P > 1 ? s->pos_rows.as<int>() : s->pos.as<int>() + v.b0, dx, B, c.d_model, st);
+    if (a.embed) {
+        const size_t row0 = a.t0 >= 0 ? (size_t)a.t0 * v.nb : 0;  // the pass's first row of tok_rows / pos_rows
+        const bool rows = a.t0 >= 0 || P > 1;
+        launch_dec_embed(m->tok_emb_f.as<float>(), m->dec_pos.as<float>(), rows ? s->tok_rows.as<int>() + row0 : lane_ptr<int>(s->tok, v, 1),
+                         rows ? s->pos_rows.as<int>() + row0 : lane_ptr<int>(s->pos, v, 1), dx, B, c.d_model, st);
+    }
     for (int l = 0; l < c.n_layers; ++l) {
         DecLayer& w = m->dec[l];
-        void* sk = off_bytes(s->self_kv, ((size_t)(2 * l) * self_l + self_b) * ks);
-        void* sv = off_bytes(s->self_kv, ((size_t)(2 * l + 1) * self_l + self_b) * ks);
-        {  // LN1 -> q | k,v appended to the cache at row current_len   (layers.mojo:118-147)
-            DecLinearParams p{};
-            p.x = dx;
-            p.ldx = c.d_model;
-            p.ln_g = w.ln1_g.as<float>();
-            p.ln_b = w.ln1_b.as<float>();
-            p.W = w.sqkv_w.p;
-            p.N = 3 * c.d_model;
-            p.K = c.d_model;
-            p.B = B;
-            p.bias = w.sqkv_b.as<float>();
-            p.out = dq;
-            p.ldo = c.d_model;
-            p.kcache = sk;
-            p.vcache = sv;
-            p.kv_batch_stride = (long)((size_t)c.n_text_ctx * d);
-            p.d_model = c.d_model;
-            p.kv_dtype = KV;
-            p.kv_B = qB;
-            p.ctl = ctl;
-            WMCHK(dec_linear_dispatch(T, p, st));
-        }
+        WMCHK(dec_linear_dispatch(T, qkv_block(m, s, v, l, P), st));
         {  // self-attention over current_len+1 cached rows   (layers.mojo:186-272)
-            AttnDecParams a{};
-            a.q = dq;
-            a.K = sk;
-            a.V = sv;
-            a.batch_stride = (long)((size_t)c.n_text_ctx * d);
-            a.n_keys = -1;
-            a.q_B = qB;
-            a.ctl = ctl;
-            a.nsplit = 1;
-            a.scale = scale;
-            a.direct_out = dattn;
-            a.out_dtype = T;
-            a.H = c.n_heads;
-            a.d = c.d_model;
-            a.B = B;
+            AttnDecParams q{};
+            q.q = dq;
+            q.K = self_kv_rows(m, s, v, l, 0);
+            q.V = self_kv_rows(m, s, v, l, 1);
+            q.batch_stride = (long)((size_t)c.n_text_ctx * d);
+            q.n_keys = -1;
+            q.q_B = qB;
+            q.ctl = v.ctl;
+            q.nsplit = 1;
+            q.scale = ATTN_SCALE;
+            q.direct_out = dattn;
+            q.out_dtype = T;
+            q.H = c.n_heads;
+            q.d = c.d_model;
+            q.B = B;
             // per-row prompts: every utterance sweeps its own key window [key_lo, len + 1 (+ t))
-            WMCHK(attn_decode_dispatch(KV, a, st, s->rw.on && key_window ? s->rw.key_lo.as<int>() + v.b0 : nullptr));
+            WMCHK(attn_decode_dispatch(KV, q, st, s->rw.on && a.key_window ? lane_ptr<int>(s->rw.key_lo, v, 1) : nullptr));
         }
-        // the attention outputs and the MLP hidden rows are handed over in operand dtype T (what the next MFMA consumes)
-        auto proj_residual = [&](const float* in, int K, const DevBuf& W, const DevBuf& bias) -> int {  // x += in·Wᵀ + b
-            DecLinearParams p{};
-            p.x = in;
-            p.ldx = K;
-            p.x_is_t = 1;
-            p.W = W.p;
-            p.N = c.d_model;
-            p.K = K;
-            p.B = B;
-            p.bias = bias.as<float>();
-            p.residual = dx;
-            p.ldr = c.d_model;
-            p.out = dx;
-            p.ldo = c.d_model;
-            return dec_linear_dispatch(T, p, st);
-        };
-        WMCHK(proj_residual(dattn, c.d_model, w.so_w, w.so_b));
+        WMCHK(dec_linear_dispatch(T, proj_residual_block(m, s, v, P, dattn, c.d_model, w.so_w, w.so_b), st));
         {  // LNx -> cross q
-            DecLinearParams p{};
-            p.x = dx;
-            p.ldx = c.d_model;
-            p.ln_g = w.lnx_g.as<float>();
-            p.ln_b = w.lnx_b.as<float>();
-            p.W = w.cq_w.p;
-            p.N = c.d_model;
-            p.K = c.d_model;
-            p.B = B;
-            p.bias = w.cq_b.as<float>();
-            p.out = dq;
-            p.ldo = c.d_model;
-            if (capture && s->al.on) {  // token timestamps: this step's query rows of the alignment heads of layer l
-                bool any = false;
-                for (int h = 0; h < 32; ++h) p.cap_sel[h] = -1;
-                const int n_sel = (int)s->al.pairs.size() / 2;
-                for (int k = 0; k < n_sel; ++k)
-                    if (s->al.pairs[2 * k] == l) {
-                        p.cap_sel[s->al.pairs[2 * k + 1]] = (signed char)k;
-                        any = true;
-                    }
-                if (any && s->al.ragged) {  // an align pass's chunk: rows [t0, t0 + P) of the row map (single-lane: b0 = 0)
-                    p.cap = s->al.cap.as<float>();
-                    p.cap_map = s->al.map.as<int>() + (size_t)std::max(t0, 0) * v.nb;
-                    p.cap_nsel = n_sel;
-                } else if (any) {
-                    p.cap_row_stride = (long)s->al.L * n_sel * 64;
-                    p.cap = s->al.cap.as<float>() + (size_t)v.b0 * p.cap_row_stride;
-                    p.cap_step0 = s->al.n_prompt;
-                    p.cap_steps = s->al.L;
-                    p.cap_nsel = n_sel;
-                    p.ctl = ctl;
-                }
-            }
+            DecLinearParams p = linear_block(dx, w.lnx_g.as<float>(), w.lnx_b.as<float>(), w.cq_w.p, w.cq_b.as<float>(), c.d_model, c.d_model, B, dq, c.d_model);
+            if (a.capture && s->al.on) add_align_capture(p, s->al, l, v, a.t0);
             WMCHK(dec_linear_dispatch(T, p, st));
         }
         WMCHK(launch_cross_attn(m, s, l, v, P));
@@ -1594,54 +1637,21 @@ static int decode_core(wm_model* m, wm_state* s, const DecView& v, bool want_log
         if (m->xattn)
             WMCHK(cross_attn_merge(m, s, l, v, P, dattn, T));
         else
-            launch_attn_combine(s->part_o.as<float>() + (size_t)v.b0 * s->nsplit * d, s->part_ml.as<float>() + (size_t)v.b0 * s->nsplit * c.n_heads * 2,
-                            dattn, T, B, s->nsplit, c.n_heads, c.d_model, st, (long long*)m->ts_buf.p, s->trace_id);
-        WMCHK(proj_residual(dattn, c.d_model, w.co_w, w.co_b));
+            launch_attn_combine(lane_ptr<float>(s->part_o, v, s->nsplit * d), lane_ptr<float>(s->part_ml, v, (size_t)s->nsplit * c.n_heads * 2), dattn, T, B,
+                                s->nsplit, c.n_heads, c.d_model, st, (long long*)m->ts_buf.p, s->trace_id);
+        WMCHK(dec_linear_dispatch(T, proj_residual_block(m, s, v, P, dattn, c.d_model, w.co_w, w.co_b), st));
         {  // LN2 -> fc1 + GELU
-            DecLinearParams p{};
-            p.x = dx;
-            p.ldx = c.d_model;
-            p.ln_g = w.ln2_g.as<float>();
-            p.ln_b = w.ln2_b.as<float>();
-            p.W = w.fc1_w.p;
-            p.N = c.ffn;
-            p.K = c.d_model;
-            p.B = B;
-            p.bias = w.fc1_b.as<float>();
-            p.act = 1;
-            p.gelu_mode = m->cfg.gelu_mode;
-            p.out = dhid;
-            p.out_is_t = 1;
-            p.ldo = c.ffn;
+            DecLinearParams p = linear_block(dx, w.ln2_g.as<float>(), w.ln2_b.as<float>(), w.fc1_w.p, w.fc1_b.as<float>(), c.ffn, c.d_model, B, dhid, c.ffn);
+            add_gelu_t(p, m->cfg.gelu_mode);
             WMCHK(dec_linear_dispatch(T, p, st));
         }
-        WMCHK(proj_residual(dhid, c.ffn, w.fc2_w, w.fc2_b));
+        WMCHK(dec_linear_dispatch(T, proj_residual_block(m, s, v, P, dhid, c.ffn, w.fc2_w, w.fc2_b), st));
     }
-    if (want_logits) {  // final LN + tied-embedding logits (whisper.mojo:156-166), no bias
-        DecLinearParams p{};
-        p.x = dx + (size_t)(P - 1) * v.nb * d;  // rows of the last position
-        p.ldx = c.d_model;
-        p.ln_g = m->dec_ln_g.as<float>();
-        p.ln_b = m->dec_ln_b.as<float>();
-        p.W = T == WM_F32 ? m->tok_emb_f.p : m->tok_emb_t.p;
-        p.N = c.vocab;
-        p.K = c.d_model;
-        p.B = v.nb;
-        p.out = full_logits ? s->logits.as<float>() + (size_t)v.b0 * m->Vpad : nullptr;
-        p.ldo = m->Vpad;
-        p.amax_val = s->amax_val.as<float>() + (size_t)v.b0 * s->npart;
-        p.amax_idx = s->amax_idx.as<int>() + (size_t)v.b0 * s->npart;
-        p.amax_stride = s->npart;
-        p.amax_mask = mask;
-        if (rules && rules->tb > 0) {  // timestamp rules: split the candidates by the utterances' admissible ranges
-            p.ts_state = s->ts_state.as<TsState>() + v.b0;
-            p.ts_begin = rules->tb;
-            p.ts_val = s->ts_val.as<float>() + (size_t)v.b0 * s->npart;
-            p.ts_idx = s->ts_idx.as<int>() + (size_t)v.b0 * s->npart;
-            p.ts_m = s->ts_m.as<float>() + (size_t)v.b0 * s->npart;
-            p.ts_s = s->ts_s.as<float>() + (size_t)v.b0 * s->npart;
-        }
-        if (s->lp.on) p.lp_s = s->lp.part_s.as<float>() + (size_t)v.b0 * s->npart;
+    if (a.logits != Logits::none) {  // final LN + tied-embedding logits (whisper.mojo:156-166), no bias, rows of the last position
+        const VocabHead h = vocab_head(m);
+        DecLinearParams p = linear_block(dx + (size_t)(P - 1) * v.nb * d, h.ln_g, h.ln_b, h.emb, nullptr, h.vocab, h.d_model, v.nb,
+                                      a.logits == Logits::full ? lane_ptr<float>(s->logits, v, m->Vpad) : nullptr, m->Vpad);
+        add_argmax_partials(p, s, v, a.mask, a.rules);
         p.ts = (long long*)m->ts_buf.p;
         p.ts_id = s->trace_id;
         int lrc = 0;
@@ -1651,50 +1661,60 @@ static int decode_core(wm_model* m, wm_state* s, const DecView& v, bool want_log
     return 0;
 }
 
-static ArgmaxParams argmax_params(wm_model* m, wm_state* s, const DecView& v, bool record, int eot, int ignore_eot,
-                                  bool advance = false, bool embed_next = false, const TsRules* rules = nullptr) {
+// The fused argmax's second stage, in its three uses.  wm_decode_step: the next id of every row, nothing recorded, no stop rule
+static ArgmaxParams argmax_peek(wm_model* m, wm_state* s, const DecView& v) {
     ArgmaxParams a{};
-    if (rules && rules->tb > 0) {
-        a.ts_state = s->ts_state.as<TsState>() + v.b0;
-        a.rules = *rules;
-        a.ts_val = s->ts_val.as<float>() + (size_t)v.b0 * s->npart;
-        a.ts_idx = s->ts_idx.as<int>() + (size_t)v.b0 * s->npart;
-        a.ts_m = s->ts_m.as<float>() + (size_t)v.b0 * s->npart;
-        a.ts_s = s->ts_s.as<float>() + (size_t)v.b0 * s->npart;
-        a.ts_part0 = rules->tb / dec_logits_ids_per_part(m->cfg.dims.vocab);
-    }
-    a.logits = s->logits.as<float>() + (size_t)v.b0 * m->Vpad;
-    a.pval = s->amax_val.as<float>() + (size_t)v.b0 * s->npart;
-    a.pidx = s->amax_idx.as<int>() + (size_t)v.b0 * s->npart;
+    a.logits = lane_ptr<float>(s->logits, v, m->Vpad);
+    a.pval = lane_ptr<float>(s->amax_val, v, s->npart);
+    a.pidx = lane_ptr<int>(s->amax_idx, v, s->npart);
     a.npart = s->npart;
     a.ldl = m->Vpad;
     a.V = m->cfg.dims.vocab;
     a.B = v.nb;
-    a.next = s->tok.as<int>() + v.b0;
-    a.out_tokens = record ? s->out_tokens.as<int>() + (size_t)v.b0 * s->out_stride : nullptr;
+    a.next = lane_ptr<int>(s->tok, v, 1);
     a.out_stride = s->out_stride;
-    a.n_tokens = s->n_tokens.as<int>() + v.b0;
-    a.finished = s->finished.as<int>() + v.b0;
-    if (s->lp.on && record) {
-        a.lp_s = s->lp.part_s.as<float>() + (size_t)v.b0 * s->npart;
-        a.logprobs = s->lp.table.as<float>() + (size_t)v.b0 * s->out_stride;
-        a.lp_sum = s->lp.sum.as<float>() + v.b0;
-    }
+    a.n_tokens = lane_ptr<int>(s->n_tokens, v, 1);
+    a.finished = lane_ptr<int>(s->finished, v, 1);
     a.ctl = v.ctl;
-    a.eot = eot;
-    a.ignore_eot = ignore_eot;
-    a.advance = advance ? 1 : 0;
-    a.pos = s->pos.as<int>() + v.b0;
+    a.pos = lane_ptr<int>(s->pos, v, 1);
     a.ts = (long long*)m->ts_buf.p;
     a.ts_id = s->trace_id;
-    if (advance) a.host_progress = s->d_prog;  // the greedy loop's steps report (finished, cache length) to the host
-    if (embed_next) {
-        a.emb_tok = m->tok_emb_f.as<float>();
-        a.emb_pos = m->dec_pos.as<float>();
-        a.emb_out = s->dx.as<float>() + (size_t)v.b0 * m->cfg.dims.d_model;
-        a.d = m->cfg.dims.d_model;
-        a.max_pos = m->cfg.dims.n_text_ctx - 1;
+    a.eot = -1;
+    a.ignore_eot = 1;
+    return a;
+}
+// the end of a prefill: the first id goes into the pass's outputs (ids, log-probs, timestamp history); the cache length stays
+static ArgmaxParams argmax_first_id(wm_model* m, wm_state* s, const DecView& v, int eot, int ignore_eot, const TsRules* rules) {
+    ArgmaxParams a = argmax_peek(m, s, v);
+    if (rules && rules->tb > 0) {
+        a.ts_state = lane_ptr<TsState>(s->ts_state, v, 1);
+        a.rules = *rules;
+        a.ts_val = lane_ptr<float>(s->ts_val, v, s->npart);
+        a.ts_idx = lane_ptr<int>(s->ts_idx, v, s->npart);
+        a.ts_m = lane_ptr<float>(s->ts_m, v, s->npart);
+        a.ts_s = lane_ptr<float>(s->ts_s, v, s->npart);
+        a.ts_part0 = rules->tb / dec_logits_ids_per_part(m->cfg.dims.vocab);
     }
+    a.out_tokens = lane_ptr<int>(s->out_tokens, v, s->out_stride);
+    if (s->lp.on) {
+        a.lp_s = lane_ptr<float>(s->lp.part_s, v, s->npart);
+        a.logprobs = lane_ptr<float>(s->lp.table, v, s->out_stride);
+        a.lp_sum = lane_ptr<float>(s->lp.sum, v, 1);
+    }
+    a.eot = eot;
+    a.ignore_eot = ignore_eot;
+    return a;
+}
+// a step of the greedy loop: also advances the cache length, reports progress to the host and writes the next step's input row
+static ArgmaxParams argmax_loop_step(wm_model* m, wm_state* s, const DecView& v, int eot, int ignore_eot, const TsRules* rules) {
+    ArgmaxParams a = argmax_first_id(m, s, v, eot, ignore_eot, rules);
+    a.advance = 1;
+    a.host_progress = s->d_prog;
+    a.emb_tok = m->tok_emb_f.as<float>();
+    a.emb_pos = m->dec_pos.as<float>();
+    a.emb_out = lane_ptr<float>(s->dx, v, m->cfg.dims.d_model);
+    a.d = m->cfg.dims.d_model;
+    a.max_pos = m->cfg.dims.n_text_ctx - 1;
     return a;
 }
 
@@ -1715,6 +1735,8 @@ extern "C" int wm_decode_step(wm_model* m, wm_state* s, const int32_t* tokens, i
     hipStream_t st = m->stream;
     const DecView v = whole_batch(m, s);
     std::vector<int32_t> col(B), pos(B);
+    DecPass pass;
+    pass.logits = Logits::full;  // for the caller, of the last position
     if (q_len > 1 && q_len <= wm_state::PREFILL_MAX) {  // the q_len block of whisper.mojo:195 as ONE position-major pass
         std::vector<int32_t> trow((size_t)q_len * B), prow((size_t)q_len * B);
         for (int i = 0; i < q_len; ++i)
@@ -1725,7 +1747,8 @@ extern "C" int wm_decode_step(wm_model* m, wm_state* s, const int32_t* tokens, i
         HIPCHK(hipMemcpyAsync(s->tok_rows.p, trow.data(), trow.size() * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(s->pos_rows.p, prow.data(), prow.size() * 4, hipMemcpyHostToDevice, st));
         launch_set_step(v.ctl, s->host_len, 1, nullptr, 0, nullptr, 0, B, st);
-        WMCHK(decode_core(m, s, v, true, true, nullptr, q_len));
+        pass.P = q_len;
+        WMCHK(decode_core(m, s, v, pass));
         HIPCHK(hipGetLastError());         // a launch that failed (bad configuration, LDS attribute) is reported here
         HIPCHK(hipStreamSynchronize(st));  // trow / prow go out of scope
         s->host_len += q_len;
@@ -1739,14 +1762,15 @@ extern "C" int wm_decode_step(wm_model* m, wm_state* s, const int32_t* tokens, i
         HIPCHK(hipMemcpyAsync(s->tok.p, col.data(), B * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(s->pos.p, pos.data(), B * 4, hipMemcpyHostToDevice, st));
         launch_set_step(v.ctl, s->host_len, 1, nullptr, 0, nullptr, 0, B, st);
-        WMCHK(decode_core(m, s, v, i == q_len - 1, true));
+        pass.logits = i == q_len - 1 ? Logits::full : Logits::none;
+        WMCHK(decode_core(m, s, v, pass));
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));  // col/pos are reused next iteration
         s->host_len += 1;
     }
     launch_set_step(v.ctl, s->host_len, 1, nullptr, 0, nullptr, 0, B, st);
     if (next) {
-        launch_argmax_step(argmax_params(m, s, v, false, -1, 1), st);
+        launch_argmax_step(argmax_peek(m, s, v), st);
         HIPCHK(hipMemcpyAsync(next, s->tok.p, B * 4, hipMemcpyDeviceToHost, st));
     }
     if (logits)
@@ -1759,9 +1783,24 @@ extern "C" int wm_decode_step(wm_model* m, wm_state* s, const int32_t* tokens, i
 // ---- greedy-loop enqueue machinery (used by transcribe_decode and the loop pump) -----------------------------------------------
 static const int LOOP_CHUNK = 8;  // graph replays per sub-chunk; two sub-chunks (16 steps) are queued ahead of the GPU
 
+// One step of the greedy loop for view v as s->step describes it: the decoder pass and its argmax.  The only place that pairs
+// them — transcribe_decode captures this into the lanes' graphs, enqueue_loop_steps launches it where there is no graph.
+static int loop_step(wm_model* m, wm_state* s, const DecView& v) {
+    const wm_state::StepKey& k = s->step;
+    DecPass step;
+    step.embed = false;
+    step.logits = Logits::partials;
+    step.mask = s->mask_steady.as<float>();
+    step.rules = &k.rules;  // (tb <= 0: off, as every reader of the rules checks)
+    step.capture = true;
+    WMCHK(decode_core(m, s, v, step));
+    launch_argmax_step(argmax_loop_step(m, s, v, k.eot, k.ignore_eot, &k.rules), v.st);
+    return 0;
+}
+static void invalidate_step_graphs(wm_state* s) { s->graphs_valid = false; }  // the next greedy pass captures its step anew
+
 // n more steps of the pending pass's loop on the state's lane streams (captured graph, or eager launches in the developer build)
 static int enqueue_loop_steps(wm_model* m, wm_state* s, int n) {
-    const TsRules* rp = s->loop_opts.rules.tb > 0 ? &s->loop_opts.rules : nullptr;
     for (int k = 0; k < n; ++k, ++s->loop_enq) {
         const int it = s->loop_enq;
         for (auto& ln : s->lanes) {
@@ -1770,9 +1809,7 @@ static int enqueue_loop_steps(wm_model* m, wm_state* s, int n) {
                 const hipError_t e = hipGraphLaunch(ln.graph[it % wm_state::Lane::NEXEC], ln.st);
                 if (e != hipSuccess) return fail(WM_E_HIP, "hipGraphLaunch: %s", hipGetErrorString(e));
             } else {
-                const DecView v{ln.b0, ln.nb, ln.st, ln.ctl};
-                WMCHK(decode_core(m, s, v, true, false, s->mask_steady.as<float>(), 1, false, rp, true));
-                launch_argmax_step(argmax_params(m, s, v, true, s->loop_opts.eot, s->loop_opts.ignore_eot, true, true, rp), v.st);
+                WMCHK(loop_step(m, s, DecView{ln.b0, ln.nb, ln.st, ln.ctl}));
             }
         }
     }
@@ -1864,20 +1901,11 @@ static void pump_main(wm_model* m) {
 // partials in the probe's own buffers — and the finish kernel.  Both go on the lane's stream, outside the captured step graph.
 static void ns_capture(wm_model* m, wm_state* s, const DecView& v, size_t row_off) {
     const size_t d = m->cfg.dims.d_model;
-    launch_no_speech_capture(s->dx.as<float>() + ((size_t)v.b0 + row_off) * d, s->ns.x.as<float>() + (size_t)v.b0 * d, v.nb, (int)d, v.st);
+    launch_no_speech_capture(lane_ptr<float>(s->dx, v, d) + row_off * d, lane_ptr<float>(s->ns.x, v, d), v.nb, (int)d, v.st);
 }
-static int ns_sweep(int T, const float* x, const float* ln_g, const float* ln_b, const void* emb, int N, int K, int B, int npart, float* pmax,
-                    int* pidx, float* psum, int token, float* prob, float* lse, hipStream_t st) {
-    DecLinearParams p{};
-    p.x = x;
-    p.ldx = K;
-    p.ln_g = ln_g;
-    p.ln_b = ln_b;
-    p.W = emb;
-    p.N = N;
-    p.K = K;
-    p.B = B;
-    p.ldo = (N + 3) / 4 * 4;
+static int ns_sweep(int T, const float* x, const VocabHead& h, int B, int npart, float* pmax, int* pidx, float* psum, int token, float* prob,
+                    float* lse, hipStream_t st) {
+    DecLinearParams p = linear_block(x, h.ln_g, h.ln_b, h.emb, nullptr, h.vocab, h.d_model, B, nullptr, (h.vocab + 3) / 4 * 4);
     p.amax_val = pmax;
     p.amax_idx = pidx;
     p.amax_stride = npart;
@@ -1887,11 +1915,11 @@ static int ns_sweep(int T, const float* x, const float* ln_g, const float* ln_b,
     LCHK(lrc);
     NoSpeechParams q{};
     q.x = x;
-    q.ldx = K;
-    q.ln_g = ln_g;
-    q.ln_b = ln_b;
-    q.emb = emb;
-    q.K = K;
+    q.ldx = h.d_model;
+    q.ln_g = h.ln_g;
+    q.ln_b = h.ln_b;
+    q.emb = h.emb;
+    q.K = h.d_model;
     q.token = token;
     q.B = B;
     q.pmax = pmax;
@@ -1904,13 +1932,10 @@ static int ns_sweep(int T, const float* x, const float* ln_g, const float* ln_b,
     return 0;
 }
 static int ns_probe(wm_model* m, wm_state* s, const DecView& v) {
-    const wm_dims& c = m->cfg.dims;
-    const int T = dec_dtype(m->cfg);
-    const size_t np = (size_t)v.b0 * s->npart;
-    return ns_sweep(T, s->ns.x.as<float>() + (size_t)v.b0 * c.d_model, m->dec_ln_g.as<float>(), m->dec_ln_b.as<float>(),
-                    T == WM_F32 ? m->tok_emb_f.p : m->tok_emb_t.p, c.vocab, c.d_model, v.nb, s->npart, s->ns.pmax.as<float>() + np,
-                    s->ns.pidx.as<int>() + np, s->ns.psum.as<float>() + np, s->ns.token, s->ns.prob.as<float>() + v.b0,
-                    s->ns.lse.as<float>() + v.b0, v.st);
+    const wm_state::Ns& ns = s->ns;
+    return ns_sweep(dec_dtype(m->cfg), lane_ptr<float>(ns.x, v, m->cfg.dims.d_model), vocab_head(m), v.nb, s->npart, lane_ptr<float>(ns.pmax, v, s->npart),
+                    lane_ptr<int>(ns.pidx, v, s->npart), lane_ptr<float>(ns.psum, v, s->npart), ns.token, lane_ptr<float>(ns.prob, v, 1),
+                    lane_ptr<float>(ns.lse, v, 1), v.st);
 }
 
 // Language detection, after the encoder on a single-lane state: one decoder pass over [sot] at position 0 for all rows
@@ -1922,25 +1947,28 @@ static int lang_pass(wm_model* m, wm_state* s, const DecView& v, int* patch, int
     const int T = dec_dtype(m->cfg);
     wm_state::Lang& lg = s->lg;
     HIPCHK(hipMemcpyAsync(lg.ids.p, lg.h_ids.data(), (size_t)lg.n * 4, hipMemcpyHostToDevice, v.st));
-    if (patch) HIPCHK(hipMemcpyAsync(lg.col.as<int>() + v.b0, lg.h_col.data() + v.b0, (size_t)v.nb * 4, hipMemcpyHostToDevice, v.st));
-    launch_set_step(v.ctl, 0, 1, s->pos.as<int>() + v.b0, 0, s->tok.as<int>() + v.b0, lg.sot, v.nb, v.st);
-    WMCHK(decode_core(m, s, v, false, false, nullptr, 1, true, nullptr, false, -1, false));
-    launch_no_speech_capture(s->dx.as<float>() + (size_t)v.b0 * c.d_model, lg.x.as<float>() + (size_t)v.b0 * c.d_model, v.nb, c.d_model, v.st);
+    if (patch) HIPCHK(hipMemcpyAsync(lane_ptr<int>(lg.col, v, 1), lg.h_col.data() + v.b0, (size_t)v.nb * 4, hipMemcpyHostToDevice, v.st));
+    launch_set_step(v.ctl, 0, 1, lane_ptr<int>(s->pos, v, 1), 0, lane_ptr<int>(s->tok, v, 1), lg.sot, v.nb, v.st);
+    DecPass sot;
+    sot.key_window = false;
+    WMCHK(decode_core(m, s, v, sot));
+    launch_no_speech_capture(lane_ptr<float>(s->dx, v, c.d_model), lane_ptr<float>(lg.x, v, c.d_model), v.nb, c.d_model, v.st);
+    const VocabHead h = vocab_head(m);
     LangDetectParams q{};
-    q.x = lg.x.as<float>() + (size_t)v.b0 * c.d_model;
+    q.x = lane_ptr<float>(lg.x, v, c.d_model);
     q.ldx = c.d_model;
-    q.ln_g = m->dec_ln_g.as<float>();
-    q.ln_b = m->dec_ln_b.as<float>();
-    q.emb = T == WM_F32 ? m->tok_emb_f.p : m->tok_emb_t.p;
+    q.ln_g = h.ln_g;
+    q.ln_b = h.ln_b;
+    q.emb = h.emb;
     q.lang_ids = lg.ids.as<int>();
     q.n_lang = lg.n;
-    q.K = c.d_model;
+    q.K = h.d_model;
     q.B = v.nb;
-    q.lang_out = lg.out.as<int>() + v.b0;
-    q.probs = lg.probs.as<float>() + (size_t)v.b0 * lg.n;
+    q.lang_out = lane_ptr<int>(lg.out, v, 1);
+    q.probs = lane_ptr<float>(lg.probs, v, lg.n);
     q.patch = patch ? patch + (size_t)v.b0 * patch_stride : nullptr;
     q.patch_stride = patch_stride;
-    q.patch_col = lg.col.as<int>() + v.b0;
+    q.patch_col = lane_ptr<int>(lg.col, v, 1);
     DISPATCH_DT(T, TT, launch_lang_detect<TT>(q, v.st));
     return 0;
 }
@@ -1961,14 +1989,20 @@ static int prefill_rows(wm_model* m, wm_state* s, const DecView& v, InitTokensPa
     for (int t0 = 0; t0 < Lmax; t0 += wm_state::PREFILL_MAX) {
         const int P = std::min<int>(wm_state::PREFILL_MAX, Lmax - t0);
         if (t0) launch_set_step(v.ctl, t0, 1, nullptr, 0, nullptr, 0, v.nb, v.st);
-        WMCHK(decode_core(m, s, v, t0 + P == Lmax, false, s->mask_begin.as<float>(), P, true, rp, false, t0));
+        DecPass chunk;
+        chunk.P = P;
+        chunk.t0 = t0;
+        chunk.logits = t0 + P == Lmax ? Logits::partials : Logits::none;
+        chunk.mask = s->mask_begin.as<float>();
+        chunk.rules = rp;
+        WMCHK(decode_core(m, s, v, chunk));
         // the rows end together, so every row's <|startoftranscript|> sits in cache slot Lmax - n_init, whatever its own length
         const int t_sot = Lmax - s->ns.n_init;
         if (s->ns.on && t_sot >= t0 && t_sot < t0 + P) ns_capture(m, s, v, (size_t)(t_sot - t0) * v.nb);
     }
-    launch_argmax_step(argmax_params(m, s, v, true, o->eot, o->ignore_eot, false, false, rp), v.st);
+    launch_argmax_step(argmax_first_id(m, s, v, o->eot, o->ignore_eot, rp), v.st);
     trace_mark(v.st, "state %p lane %d prefill end", (void*)s, v.b0);
-    launch_set_rows_step(v.ctl, Lmax, s->pos.as<int>() + v.b0, rw.len.as<int>(), o->pos_mode == WM_POS_REF ? -1 : 0, v.nb, v.st);
+    launch_set_rows_step(v.ctl, Lmax, lane_ptr<int>(s->pos, v, 1), rw.len.as<int>(), o->pos_mode == WM_POS_REF ? -1 : 0, v.nb, v.st);
     return 0;
 }
 
@@ -1982,7 +2016,8 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
     static const bool trace_phase = wm_env("WM_TRACE_HOST") != nullptr;
     const auto tp0 = std::chrono::steady_clock::now();
     static const bool no_graph = wm_env("WM_NO_GRAPH") != nullptr;
-    TsRules rules{};  // timestamp rules of this pass (tb <= 0: off)
+    s->step = wm_state::StepKey{};      // the loop step of this pass
+    TsRules& rules = s->step.rules;  // timestamp rules of this pass (tb <= 0: off)
     rules.tb = o->timestamp_begin > 0 ? o->timestamp_begin : 0;
     rules.eos = o->eot;
     rules.max_init = o->max_initial_timestamp_index;
@@ -1990,11 +2025,13 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
     const TsRules* rp = rules.tb > 0 ? &rules : nullptr;
     const int no_ts = rp ? o->no_timestamps_token : -1;
     s->shares_chip = !allow_poll;  // the pipelined entry (wm_transcribe_submit): other passes are, or will be, in flight
-    wm_state::CapKey cap_key;
-    if (s->al.on) cap_key = wm_state::CapKey{s->al.cap.p, s->al.L, s->al.n_prompt, s->al.pairs};
-    const bool recapture = !s->graphs_valid || s->graph_eot != o->eot || s->graph_ignore != o->ignore_eot ||
-                           s->graph_shares != s->shares_chip || memcmp(&s->graph_rules, &rules, sizeof rules) != 0 || s->graph_cap != cap_key ||
-                           s->graph_rows != s->rw.on || s->graph_lp != s->lp.on;
+    s->step.eot = o->eot;
+    s->step.ignore_eot = o->ignore_eot;
+    s->step.shares_chip = s->shares_chip;
+    if (s->al.on) s->step.cap = wm_state::StepKey::Cap{s->al.cap.p, s->al.L, s->al.n_prompt, s->al.pairs};
+    s->step.rows = s->rw.on;
+    s->step.lp = s->lp.on;
+    const bool recapture = !s->graphs_valid || !(s->graph_step == s->step);
     const int first_pos = o->pos_mode == WM_POS_REF ? o->n_prompt - 1 : o->n_prompt;
     // logit masks (§8f rank 4): rebuilt only when the id lists change; always passed (all-zero = the reference's raw argmax)
     {
@@ -2024,42 +2061,48 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
         HIPCHK(hipStreamWaitEvent(v.st, s->enc_done, 0));
         trace_mark(v.st, "state %p lane %d decode start", (void*)s, v.b0);
         // tokens = prompt (whisper.mojo:187-191, 200-202); finished = 0; control block = 0
-        ip.out_tokens = s->out_tokens.as<int>() + (size_t)v.b0 * s->out_stride;
+        ip.out_tokens = lane_ptr<int>(s->out_tokens, v, s->out_stride);
         ip.out_stride = s->out_stride;
-        ip.n_tokens = s->n_tokens.as<int>() + v.b0;
-        ip.finished = s->finished.as<int>() + v.b0;
+        ip.n_tokens = lane_ptr<int>(s->n_tokens, v, 1);
+        ip.finished = lane_ptr<int>(s->finished, v, 1);
         ip.ctl = v.ctl;
         ip.B = v.nb;
         ip.tok_rows = s->lanes.size() == 1 ? s->tok_rows.as<int>() : nullptr;
         ip.pos_rows = s->pos_rows.as<int>();
-        ip.ts_state = rp ? s->ts_state.as<TsState>() + v.b0 : nullptr;
+        ip.ts_state = rp ? lane_ptr<TsState>(s->ts_state, v, 1) : nullptr;
         ip.rules = rules;
-        ip.logprobs = s->lp.on ? s->lp.table.as<float>() + (size_t)v.b0 * s->out_stride : nullptr;
-        ip.lp_sum = s->lp.on ? s->lp.sum.as<float>() + v.b0 : nullptr;
+        ip.logprobs = s->lp.on ? lane_ptr<float>(s->lp.table, v, s->out_stride) : nullptr;
+        ip.lp_sum = s->lp.on ? lane_ptr<float>(s->lp.sum, v, 1) : nullptr;
         if (s->rw.on) {
             WMCHK(prefill_rows(m, s, v, ip, o, rp));
         } else {
             launch_init_tokens(ip, v.st);
             // prefill (whisper.mojo:195, start_pos=0): the q_len = n_prompt causal block equals n_prompt single-token steps
             static const bool seq_prefill = wm_env("WM_SEQ_PREFILL") != nullptr;  // A/B: one pass per prompt position
+            DecPass prompt;  // the last prompt position's logits, under the begin mask
+            prompt.logits = Logits::partials;
+            prompt.mask = s->mask_begin.as<float>();
+            prompt.rules = rp;
             if (!seq_prefill && s->lanes.size() == 1 && o->n_prompt > 1 && o->n_prompt <= wm_state::PREFILL_MAX) {
-                WMCHK(decode_core(m, s, v, true, false, s->mask_begin.as<float>(), o->n_prompt, true, rp));  // init_tokens filled tok_rows / pos_rows
+                prompt.P = o->n_prompt;  // init_tokens filled tok_rows / pos_rows
+                WMCHK(decode_core(m, s, v, prompt));
                 if (s->ns.on) ns_capture(m, s, v, (size_t)(o->n_prompt - s->ns.n_init) * v.nb);
             } else {
                 for (int i = 0; i < o->n_prompt; ++i) {
-                    launch_set_step(v.ctl, i, 1, s->pos.as<int>() + v.b0, i, s->tok.as<int>() + v.b0, o->prompt[i], v.nb, v.st);
-                    WMCHK(decode_core(m, s, v, i == o->n_prompt - 1, false, s->mask_begin.as<float>(), 1, true, rp));
+                    launch_set_step(v.ctl, i, 1, lane_ptr<int>(s->pos, v, 1), i, lane_ptr<int>(s->tok, v, 1), o->prompt[i], v.nb, v.st);
+                    prompt.logits = i == o->n_prompt - 1 ? Logits::partials : Logits::none;
+                    WMCHK(decode_core(m, s, v, prompt));
                     if (s->ns.on && i == o->n_prompt - s->ns.n_init) ns_capture(m, s, v, 0);
                 }
             }
-            launch_argmax_step(argmax_params(m, s, v, true, o->eot, o->ignore_eot, false, false, rp), v.st);  // :198-203
+            launch_argmax_step(argmax_first_id(m, s, v, o->eot, o->ignore_eot, rp), v.st);  // :198-203
             trace_mark(v.st, "state %p lane %d prefill end", (void*)s, v.b0);
             // incremental steps: start_pos = current_len - 1 (reference, :217) or current_len (HF)
-            launch_set_step(v.ctl, o->n_prompt, 1, s->pos.as<int>() + v.b0, first_pos, nullptr, 0, v.nb, v.st);
+            launch_set_step(v.ctl, o->n_prompt, 1, lane_ptr<int>(s->pos, v, 1), first_pos, nullptr, 0, v.nb, v.st);
         }
         // input row of the first loop step; every later step's row is written by the preceding step's argmax launch
-        launch_dec_embed(m->tok_emb_f.as<float>(), m->dec_pos.as<float>(), s->tok.as<int>() + v.b0, s->pos.as<int>() + v.b0,
-                         s->dx.as<float>() + (size_t)v.b0 * m->cfg.dims.d_model, v.nb, m->cfg.dims.d_model, v.st);
+        launch_dec_embed(m->tok_emb_f.as<float>(), m->dec_pos.as<float>(), lane_ptr<int>(s->tok, v, 1), lane_ptr<int>(s->pos, v, 1),
+                         lane_ptr<float>(s->dx, v, m->cfg.dims.d_model), v.nb, m->cfg.dims.d_model, v.st);
         if (s->ns.on) WMCHK(ns_probe(m, s, v));  // between prefill and loop, outside the captured step
         // steady state: one captured graph per lane = [37 decode-step launches + argmax/bookkeeping]; every per-step
         // quantity (token, position, cache length) lives in HBM, so the same graph is replayed for every token
@@ -2070,8 +2113,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
             }
             hipGraph_t g = nullptr;
             HIPCHK(hipStreamBeginCapture(v.st, hipStreamCaptureModeThreadLocal));
-            const int crc = decode_core(m, s, v, true, false, s->mask_steady.as<float>(), 1, false, rp, true);
-            launch_argmax_step(argmax_params(m, s, v, true, o->eot, o->ignore_eot, true, true, rp), v.st);
+            const int crc = loop_step(m, s, v);
             const hipError_t cap = hipStreamEndCapture(v.st, &g);  // always closed, also when a launcher refused
             if (crc) {
                 if (g) (void)hipGraphDestroy(g);
@@ -2085,13 +2127,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
         }
     }
     s->graphs_valid = !no_graph;
-    s->graph_eot = o->eot;
-    s->graph_ignore = o->ignore_eot;
-    s->graph_rules = rules;
-    s->graph_shares = s->shares_chip;
-    s->graph_cap = cap_key;
-    s->graph_rows = s->rw.on;
-    s->graph_lp = s->lp.on;
+    s->graph_step = s->step;
     if (trace_phase) {
         for (auto& ln : s->lanes) (void)hipStreamSynchronize(ln.st);
         fprintf(stderr, "[wm] encoder wait + prefill (+graph capture if any): %.3f ms\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count() * 1e3);
@@ -2104,9 +2140,6 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
     s->loop_total = o->max_loop;
     s->loop_enq = 0;
     s->chunk_k = 0;
-    s->loop_opts.eot = o->eot;
-    s->loop_opts.ignore_eot = o->ignore_eot;
-    s->loop_opts.rules = rules;
     s->enq_rc = 0;
     s->enq_err.clear();
     s->h_prog[0] = 0;
@@ -2828,31 +2861,35 @@ extern "C" int wm_set_alignment_heads(wm_model* m, const int32_t* layer_head_pai
     return 0;
 }
 
-// Before the pass's graphs are (re)captured: size the timestamp buffers of state s and record what the pass asked for.
-static int align_setup(wm_model* m, wm_state* s, const wm_decode_opts* o, const std::vector<int32_t>* cols) {
+// The buffers of a timestamp or align pass (they only grow) for al.pairs: Lr >= 1 rows per utterance, times_stride time columns
+static int align_buffers(wm_model* m, wm_state* s, size_t Lr, size_t times_stride) {
     wm_state::Align& a = s->al;
-    a.on = cols != nullptr;
-    if (!a.on) return 0;
-    const wm_dims& c = m->cfg.dims;
-    const size_t B = s->B, T = c.n_audio_ctx, L = o->max_loop;
-    a.pairs = m->align_pairs;
-    const size_t n_sel = a.pairs.size() / 2;
-    a.L = o->max_loop;
-    a.n_prompt = o->n_prompt;
-    a.cols = *cols;
-    ++a.gen;
-    const size_t Lr = std::max<size_t>(L, 1);
+    const size_t B = s->B, T = m->cfg.dims.n_audio_ctx, n_sel = a.pairs.size() / 2;
     WMCHK(grow(a.cap, B * Lr * n_sel * 64 * 4));
     if (m->xattn) WMCHK(grow(a.kh, B * n_sel * T * 64 * 4));
     WMCHK(grow(a.probs, B * n_sel * Lr * T * 4));
     WMCHK(grow(a.mean, B * n_sel * T * 4));
     WMCHK(grow(a.stdv, B * n_sel * T * 4));
     WMCHK(grow(a.M, B * Lr * T * 4));
+    // rows past ~400 at n_audio_ctx = 1500: the 2-bit trace leaves LDS for global memory
     if (align_dtw_lds_bytes((int)Lr, (int)T) == 0) WMCHK(grow(a.trace, B * Lr * ((T + 15) / 16) * 4));
-    WMCHK(grow(a.times, B * s->out_stride * 4));
+    WMCHK(grow(a.times, B * times_stride * 4));
     WMCHK(grow(a.ncols, B * 4));
+    return 0;
+}
+// Before the pass's graphs are (re)captured: size the timestamp buffers of state s and record what the pass asked for.
+static int align_setup(wm_model* m, wm_state* s, const wm_decode_opts* o, const std::vector<int32_t>* cols) {
+    wm_state::Align& a = s->al;
+    a.on = cols != nullptr;
+    if (!a.on) return 0;
+    a.pairs = m->align_pairs;
+    a.L = o->max_loop;
+    a.n_prompt = o->n_prompt;
+    a.cols = *cols;
+    ++a.gen;
+    WMCHK(align_buffers(m, s, std::max<size_t>(o->max_loop, 1), s->out_stride));
     // (a.cols outlives the copy: the state is not reused before this pass is waited for)
-    HIPCHK(hipMemcpyAsync(a.ncols.p, a.cols.data(), B * 4, hipMemcpyHostToDevice, s->lanes[0].st));
+    HIPCHK(hipMemcpyAsync(a.ncols.p, a.cols.data(), (size_t)s->B * 4, hipMemcpyHostToDevice, s->lanes[0].st));
     return 0;
 }
 
@@ -3356,25 +3393,16 @@ static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
         for (DevBuf* p : {&sc.lp, &sc.top}) WMCHK(grow(*p, (size_t)B * a.stride * 4));
     }
     al.on = al.ragged = align;
-    if (align) {  // the buffers of align_setup, sized by the longest row of THIS pass (they grow, as there)
-        const size_t Ta = c.n_audio_ctx, n_sel = m->align_pairs.size() / 2, Lr = std::max(Lal, 1);
+    if (align) {  // the buffers of a timestamp pass, sized by the longest row of THIS pass
         al.pairs = m->align_pairs;
         al.L = Lal;
         al.n_prompt = 0;
         al.stride = a.stride;
         al.cols = *a.cols;
         ++al.gen;
-        s->graph_cap.L = -1;  // the captured step graph may hold a capture into a buffer that is re-sized here: the next pass recaptures
-        WMCHK(grow(al.cap, (size_t)B * Lr * n_sel * 64 * 4));
-        if (m->xattn) WMCHK(grow(al.kh, (size_t)B * n_sel * Ta * 64 * 4));
-        WMCHK(grow(al.probs, (size_t)B * n_sel * Lr * Ta * 4));
-        WMCHK(grow(al.mean, (size_t)B * n_sel * Ta * 4));
-        WMCHK(grow(al.stdv, (size_t)B * n_sel * Ta * 4));
-        WMCHK(grow(al.M, (size_t)B * Lr * Ta * 4));
-        // rows past ~400 at n_audio_ctx = 1500: the 2-bit trace leaves LDS for global memory
-        if (align_dtw_lds_bytes((int)Lr, (int)Ta) == 0) WMCHK(grow(al.trace, (size_t)B * Lr * ((Ta + 15) / 16) * 4));
-        WMCHK(grow(al.times, (size_t)B * a.stride * 4));
-        for (DevBuf* p : {&al.ncols, &al.rows, &al.row0}) WMCHK(grow(*p, (size_t)B * 4));
+        invalidate_step_graphs(s);  // the captured step graph may hold a capture into a buffer that is re-sized here
+        WMCHK(align_buffers(m, s, std::max(Lal, 1), a.stride));
+        for (DevBuf* p : {&al.rows, &al.row0}) WMCHK(grow(*p, (size_t)B * 4));
         WMCHK(grow(al.map, (size_t)B * ctx * 4));
     }
     s->rw.on = true;  // the prefill's self-attention sweeps each row's own key window
@@ -3408,7 +3436,11 @@ static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
     for (int t0 = 0; t0 < Lmax; t0 += wm_state::PREFILL_MAX) {
         const int P = std::min<int>(wm_state::PREFILL_MAX, Lmax - t0);
         launch_set_step(v.ctl, t0, 1, nullptr, 0, nullptr, 0, v.nb, v.st);
-        WMCHK(decode_core(m, s, v, false, false, nullptr, P, true, nullptr, align && Lal > 0, t0));
+        DecPass chunk;
+        chunk.P = P;
+        chunk.t0 = t0;
+        chunk.capture = align && Lal > 0;
+        WMCHK(decode_core(m, s, v, chunk));
         if (want_lp) launch_score_collect(s->dx.as<float>(), sc.rows.as<float>(), sc.dst.as<int>() + (size_t)t0 * B, P * B, c.d_model, v.st);
     }
     HIPCHK(hipEventRecord(sc.ev[2], v.st));
@@ -3416,17 +3448,18 @@ static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
     if (!want_lp) {  // times only: no LayerNorm, sweep, merge or sums
         for (int k = 3; k <= 5; ++k) HIPCHK(hipEventRecord(sc.ev[k], v.st));
     } else {
+    const VocabHead h = vocab_head(m);
     ScoreParams q{};
     q.x = sc.rows.as<float>();
-    q.ln_g = m->dec_ln_g.as<float>();
-    q.ln_b = m->dec_ln_b.as<float>();
-    q.emb = T == WM_F32 ? m->tok_emb_f.p : m->tok_emb_t.p;
+    q.ln_g = h.ln_g;
+    q.ln_b = h.ln_b;
+    q.emb = h.emb;
     q.a = sc.a.p;
     q.target = sc.target.as<int>();
     q.slot = sc.slot.as<int>();
     q.M = M;
-    q.N = c.vocab;
-    q.K = c.d_model;
+    q.N = h.vocab;
+    q.K = h.d_model;
     q.pmax = sc.pmax.as<float>();
     q.psum = sc.psum.as<float>();
     q.pidx = sc.pidx.as<int>();
@@ -4244,6 +4277,24 @@ extern "C" int wm_bench_kernel(wm_model* m, wm_state* s, int which, int reps, fl
     HIPCHK(hipEventCreate(&e0));
     HIPCHK(hipEventCreate(&e1));
     const int L = m->cfg.dims.n_layers;
+#ifdef WM_DEV
+    // phase stamps in groups of 8 (100 MHz clock): per phase the sum / max of the us after the first group's entry; returns the groups seen
+    auto phase_stats = [](const std::vector<long long>& h, int nphase, double* av, double* mx) {
+        long long t0 = -1;
+        for (size_t g = 0; g < h.size() / 8; ++g) if (h[g * 8] > 0 && (t0 < 0 || h[g * 8] < t0)) t0 = h[g * 8];
+        int n = 0;
+        for (size_t g = 0; g < h.size() / 8; ++g) {
+            if (h[g * 8] <= 0) continue;
+            ++n;
+            for (int k = 0; k < nphase; ++k) {
+                const double us = (double)(h[g * 8 + k] - t0) / 100.0;
+                av[k] += us;
+                mx[k] = std::max(mx[k], us);
+            }
+        }
+        return n;
+    };
+#endif
     if (which == WM_KERNEL_CROSS_ATTN) {
         // m->xattn: absorb + X sweep + merge / V-apply, everything that replaces attn_decode + attn_combine (wm_bench_bytes prices
         // the same three launches).  Every layer reads the SAME X (73.7 MB at B = 64), so after the first launch the stream is
@@ -4251,7 +4302,7 @@ extern "C" int wm_bench_kernel(wm_model* m, wm_state* s, int which, int reps, fl
         const DecView v = whole_batch(m, s);
         const int TD = dec_dtype(m->cfg);
         auto one = [&](int l) -> int {
-            WMCHK(launch_cross_attn(m, s, l, v));
+            WMCHK(launch_cross_attn(m, s, l, v, 1));
             return m->xattn ? cross_attn_merge(m, s, l, v, 1, s->dattn.p, TD) : 0;
         };
         for (int i = 0; i < L; ++i) WMCHK(one(i));  // warm-up
@@ -4268,12 +4319,14 @@ extern "C" int wm_bench_kernel(wm_model* m, wm_state* s, int which, int reps, fl
         if (own) st = s->lanes[0].st;
         const DecView v{0, s->B, st, own ? s->lanes[0].ctl : s->ctl.as<StepCtl>()};
         launch_set_step(v.ctl, len0, 1, nullptr, 0, nullptr, 0, s->B, st);
-        WMCHK(decode_core(m, s, v, true));
+        DecPass step;  // the bare step: embeds its input, logits partials with no mask
+        step.logits = Logits::partials;
+        WMCHK(decode_core(m, s, v, step));
         // timed as the transcribe loop runs it: a captured graph of the step, replayed (cache length held constant)
         hipGraph_t g = nullptr;
         hipGraphExec_t ge = nullptr;
         HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        const int crc = decode_core(m, s, v, true);
+        const int crc = decode_core(m, s, v, step);
         const hipError_t cap = hipStreamEndCapture(st, &g);
         if (crc) {
             if (g) (void)hipGraphDestroy(g);
@@ -4296,19 +4349,10 @@ extern "C" int wm_bench_kernel(wm_model* m, wm_state* s, int which, int reps, fl
         DecLayer& w0 = m->dec[0];
         DevBuf dbg;
         WMCHK(dbg.alloc((size_t)4096 * 16 * 8 * 8, true));
-        DecLinearParams p{};
-        p.B = s->B;
-        if (which == 41) {
-            p.x = s->dx.as<float>(); p.ldx = c.d_model; p.ln_g = w0.ln1_g.as<float>(); p.ln_b = w0.ln1_b.as<float>();
-            p.W = w0.sqkv_w.p; p.N = 3 * c.d_model; p.K = c.d_model; p.bias = w0.sqkv_b.as<float>(); p.out = s->dq.as<float>();
-            p.ldo = c.d_model; p.kcache = s->self_kv.p; p.vcache = off_bytes(s->self_kv, (size_t)s->B * c.n_text_ctx * c.d_model * dt_size(m->cfg.kv_dtype));
-            p.kv_batch_stride = (long)((size_t)c.n_text_ctx * c.d_model); p.d_model = c.d_model; p.kv_dtype = m->cfg.kv_dtype; p.ctl = s->ctl.as<StepCtl>();
-        } else {
-            p.x = s->dattn.as<float>(); p.ldx = c.d_model; p.x_is_t = 1; p.W = w0.so_w.p; p.N = c.d_model; p.K = c.d_model; p.bias = w0.so_b.as<float>();
-            p.residual = s->dx.as<float>(); p.ldr = c.d_model; p.out = s->dx.as<float>(); p.ldo = c.d_model;
-        }
+        const DecView v = whole_batch(m, s);  // layer 0's launch as a single-position pass over the whole batch wires it
+        DecLinearParams p = which == 41 ? qkv_block(m, s, v, 0, 1) : proj_residual_block(m, s, v, 1, s->dattn.as<float>(), c.d_model, w0.so_w, w0.so_b);
         launch_set_step(s->ctl.as<StepCtl>(), 10, 1, nullptr, 0, nullptr, 0, s->B, st);
-        for (int i = 0; i < 3; ++i) { WMCHK(dec_linear_dispatch(T, p, st)); if (!wm_env("WM_STAMP_NO_STREAM")) WMCHK(launch_cross_attn(m, s, i, whole_batch(m, s))); }
+        for (int i = 0; i < 3; ++i) { WMCHK(dec_linear_dispatch(T, p, st)); if (!wm_env("WM_STAMP_NO_STREAM")) WMCHK(launch_cross_attn(m, s, i, whole_batch(m, s), 1)); }
         p.dbg = dbg.as<long long>();
         HIPCHK(hipEventRecord(e0, st));
         WMCHK(dec_linear_dispatch(T, p, st));
@@ -4316,19 +4360,8 @@ extern "C" int wm_bench_kernel(wm_model* m, wm_state* s, int which, int reps, fl
         HIPCHK(hipEventSynchronize(e1));
         std::vector<long long> h((size_t)4096 * 16 * 8);
         HIPCHK(hipMemcpy(h.data(), dbg.p, h.size() * 8, hipMemcpyDeviceToHost));
-        long long t0 = -1;
-        for (size_t g = 0; g < h.size() / 8; ++g) if (h[g * 8] > 0 && (t0 < 0 || h[g * 8] < t0)) t0 = h[g * 8];
         double mx[6] = {0}, av[6] = {0};
-        int n = 0;
-        for (size_t g = 0; g < h.size() / 8; ++g) {
-            if (h[g * 8] <= 0) continue;
-            ++n;
-            for (int k = 0; k < 6; ++k) {
-                const double us = (double)(h[g * 8 + k] - t0) / 100.0;
-                av[k] += us;
-                mx[k] = std::max(mx[k], us);
-            }
-        }
+        const int n = phase_stats(h, 6, av, mx);
         fprintf(stderr, "[wm] dec_linear %s phases (us after the first wave's entry; mean / max over %d waves): entry %.2f/%.2f  loads issued %.2f/%.2f  operands ready %.2f/%.2f  MFMA + partial stored %.2f/%.2f  after barrier %.2f/%.2f  end %.2f/%.2f\n",
                 which == 41 ? "LN1+QKV" : "O-proj", n, av[0] / n, mx[0], av[1] / n, mx[1], av[2] / n, mx[2], av[3] / n, mx[3], av[4] / n, mx[4], av[5] / n, mx[5]);
         dbg.release();
@@ -4374,16 +4407,14 @@ extern "C" int wm_bench_kernel(wm_model* m, wm_state* s, int which, int reps, fl
                     wait / ns * 10, issue / ns * 10, comp / ns * 10, ng ? gap / ng * 10 : 0.0, epi / nu * 10, unit / nu * 10, ns, nu);
         dbg.release();
     } else if (which == 40) {  // developer: phase stamps of one logits launch (after a few warm ones), printed to stderr
-        const wm_dims& c = m->cfg.dims;
         const int T = dec_dtype(m->cfg);
         DevBuf dbg;
         const int nwg = s->npart;
         WMCHK(dbg.alloc((size_t)nwg * 8 * 8 * 8, true));
-        DecLinearParams p{};
-        p.x = s->dx.as<float>(); p.ldx = c.d_model; p.ln_g = m->dec_ln_g.as<float>(); p.ln_b = m->dec_ln_b.as<float>();
-        p.W = T == WM_F32 ? m->tok_emb_f.p : m->tok_emb_t.p; p.N = c.vocab; p.K = c.d_model; p.B = s->B; p.ldo = m->Vpad;
+        const VocabHead vh = vocab_head(m);
+        DecLinearParams p = linear_block(s->dx.as<float>(), vh.ln_g, vh.ln_b, vh.emb, nullptr, vh.vocab, vh.d_model, s->B, nullptr, m->Vpad);
         p.amax_val = s->amax_val.as<float>(); p.amax_idx = s->amax_idx.as<int>(); p.amax_stride = s->npart;
-        for (int i = 0; i < 3; ++i) { DISPATCH_DT(T, TT, (void)launch_dec_logits<TT>(p, st)); WMCHK(launch_cross_attn(m, s, i, whole_batch(m, s))); }
+        for (int i = 0; i < 3; ++i) { DISPATCH_DT(T, TT, (void)launch_dec_logits<TT>(p, st)); WMCHK(launch_cross_attn(m, s, i, whole_batch(m, s), 1)); }
         p.dbg = dbg.as<long long>();
         HIPCHK(hipEventRecord(e0, st));
         DISPATCH_DT(T, TT, (void)launch_dec_logits<TT>(p, st));
@@ -4391,19 +4422,8 @@ extern "C" int wm_bench_kernel(wm_model* m, wm_state* s, int which, int reps, fl
         HIPCHK(hipEventSynchronize(e1));
         std::vector<long long> h((size_t)nwg * 64);
         HIPCHK(hipMemcpy(h.data(), dbg.p, h.size() * 8, hipMemcpyDeviceToHost));
-        long long t0 = -1;
-        for (int g = 0; g < nwg * 8; ++g) if (h[(size_t)g * 8] > 0 && (t0 < 0 || h[(size_t)g * 8] < t0)) t0 = h[(size_t)g * 8];
         double mx[8] = {0, 0, 0, 0, 0, 0, 0, 0}, av[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        int n = 0;
-        for (int g = 0; g < nwg * 8; ++g) {
-            if (h[(size_t)g * 8] <= 0) continue;
-            ++n;
-            for (int k = 0; k < 7; ++k) {
-                const double us = (double)(h[(size_t)g * 8 + k] - t0) / 100.0;
-                av[k] += us;
-                mx[k] = std::max(mx[k], us);
-            }
-        }
+        const int n = phase_stats(h, 7, av, mx);
         fprintf(stderr, "[wm] logits phases (us after the first wave's entry; mean / max over %d waves): entry %.2f/%.2f  loads issued + staged %.2f/%.2f  after barrier %.2f/%.2f  MFMA done %.2f/%.2f  end %.2f/%.2f\n",
                 n, av[0] / n, mx[0], av[1] / n, mx[1], av[2] / n, mx[2], av[3] / n, mx[3], av[4] / n, mx[4]);
         fprintf(stderr, "[wm]   gamma/beta + activations arrived (own wave) %.2f/%.2f  all waves of the workgroup %.2f/%.2f\n", av[5] / n, mx[5], av[6] / n, mx[6]);
@@ -4816,24 +4836,14 @@ static int op_dec_linear(float* out, const float* x, const float* W, const float
         if (!in_place) WMCHK(r.alloc((size_t)B * ldo * 4, true));
         HIPCHK(hipMemcpy2D(dst.p, (size_t)ldo * 4, residual, (size_t)N * 4, (size_t)N * 4, B, hipMemcpyHostToDevice));
     }
-    DecLinearParams p{};
-    p.x = dx.as<float>();
-    p.ldx = K;
+    DecLinearParams p = linear_block(dx.as<float>(), ln_g ? g.as<float>() : nullptr, ln_g ? be.as<float>() : nullptr, w.p, bias ? b.as<float>() : nullptr,
+                                     N, K, B, o.as<float>(), ldo);
     p.x_is_t = x_is_t;
     p.out_is_t = out_is_t;
-    p.ln_g = ln_g ? g.as<float>() : nullptr;
-    p.ln_b = ln_g ? be.as<float>() : nullptr;
-    p.W = w.p;
-    p.N = N;
-    p.K = K;
-    p.B = B;
-    p.bias = bias ? b.as<float>() : nullptr;
     p.act = act != 0;
     p.gelu_mode = gelu_mode;
     p.residual = residual ? (in_place ? o.as<float>() : r.as<float>()) : nullptr;
     p.ldr = ldo;
-    p.out = o.as<float>();
-    p.ldo = ldo;
     if (kcache || (cap && !cap_map)) {
         StepCtl h{};
         h.len = len;
@@ -4899,8 +4909,8 @@ extern "C" int wm_op_dec_linear_capmap(float* out, float* cap, const float* x, c
                          cap_nsel, cap_map, cap_dst);
 }
 
-// The decode step's final LayerNorm + tied-embedding logits and its fused argmax, wired as decode_core (want_logits) and
-// argmax_params wire them: launch_dec_logits picks the kernel variant from (dtype, K, B), argmax_step reduces its partials.
+// The decode step's final LayerNorm + tied-embedding logits and its fused argmax, wired as decode_core (Logits::full) and
+// argmax_peek wire them: launch_dec_logits picks the kernel variant from (dtype, K, B), argmax_step reduces its partials.
 // logprob non-null: the LP instantiation of the same kernel variant, and the chosen ids' log-probabilities [B] (wm_op_logits_lp)
 static int op_logits(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                      const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
@@ -4947,17 +4957,7 @@ static int op_logits(float* logits, int32_t* ids, float* logprob, const float* x
         rules.max_init = -1;
         rules.vocab = N;
     }
-    DecLinearParams p{};
-    p.x = dx.as<float>();
-    p.ldx = K;
-    p.ln_g = g.as<float>();
-    p.ln_b = be.as<float>();
-    p.W = w.p;
-    p.N = N;
-    p.K = K;
-    p.B = B;
-    p.out = o.as<float>();
-    p.ldo = ldo;
+    DecLinearParams p = linear_block(dx.as<float>(), g.as<float>(), be.as<float>(), w.p, nullptr, N, K, B, o.as<float>(), ldo);
     p.amax_val = av.as<float>();
     p.amax_idx = ai.as<int>();
     p.amax_stride = npart;
@@ -5032,8 +5032,8 @@ extern "C" int wm_op_no_speech(float* prob, float* lse, const float* x, const fl
     for (DevBuf* d : {&pm, &pi, &ps}) WMCHK(d->alloc((size_t)B * npart * 4, true));
     WMCHK(pr.alloc((size_t)B * 4, true));
     WMCHK(ls.alloc((size_t)B * 4, true));
-    WMCHK(ns_sweep(dtype, dx.as<float>(), g.as<float>(), be.as<float>(), w.p, N, K, B, npart, pm.as<float>(), pi.as<int>(), ps.as<float>(), token,
-                   pr.as<float>(), ls.as<float>(), nullptr));
+    WMCHK(ns_sweep(dtype, dx.as<float>(), VocabHead{g.as<float>(), be.as<float>(), w.p, N, K}, B, npart, pm.as<float>(), pi.as<int>(), ps.as<float>(),
+                   token, pr.as<float>(), ls.as<float>(), nullptr));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(prob, pr.p, (size_t)B * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(lse, ls.p, (size_t)B * 4, hipMemcpyDeviceToHost));
@@ -5113,7 +5113,7 @@ extern "C" int wm_op_xattn(float* out, const float* q, const float* Wk, const fl
     x.d = (int)d;
     x.rows = rows;
     x.q_B = q_B;
-    x.scale = 1.0f / sqrtf(64.0f);
+    x.scale = ATTN_SCALE;
     x.qs = qs.p;
     x.part_y = py.as<float>();
     x.part_ml = pml.as<float>();
