@@ -29,7 +29,9 @@ enum { WM_GELU_TANH = 0 /* whisper_tensor.mojo:288-308 */, WM_GELU_ERF = 1 /* HF
 enum { WM_POS_REF = 0 /* start_pos = current_len-1, whisper.mojo:217 */, WM_POS_HF = 1 /* = current_len */ };
 
 /* Replaces WhisperConfig (whisper.mojo:15-31) + config.mojo:4-17.  dims.d_model / dims.n_heads must be 64
- * (layers.mojo:190-198 hard-codes a 64-wide head). */
+ * (layers.mojo:190-198 hard-codes a 64-wide head).  Shapes the kernels are instantiated for: d_model 128, 384 (tiny) or 512
+ * (base) with ffn <= 2048 whose ffn/32 splits into <= 16 x <= 4, and d_model 768 with 12 heads and ffn 3072 (small).  Anything else
+ * is refused at load with WM_E_ARG and a message that names the field. */
 typedef struct {
     wm_dims dims;
     int gelu_mode;     /* WM_GELU_* */

@@ -53,6 +53,11 @@ class WhisperConfig:
         return WhisperConfig(512, 8, 6, 51865, 2048, 80, 1500, 448)
 
     @staticmethod
+    def small() -> "WhisperConfig":
+        """openai/whisper-small: 12 heads of 64, 12 layers (cross-attention on the K/V cache)."""
+        return WhisperConfig(768, 12, 12, 51865, 3072, 80, 1500, 448)
+
+    @staticmethod
     def micro() -> "WhisperConfig":
         """Reduced test model: same structure, runs in seconds on a CPU."""
         return WhisperConfig(128, 2, 2, 1000, 512, 16, 100, 64)

@@ -63,9 +63,14 @@ __device__ __forceinline__ void store_as(void* base, size_t idx, float v, int dt
         ((f16*)base)[idx] = (f16)v;
 }
 
-template <typename TW, int KPW, bool LN, int NT, bool XT = false>
+// KG > 1 (K = 3072, fc2 of d_model 768: 96 k-steps = 16 waves x KG = 2 groups x KPW = 3): a wave walks KG groups of KPW k-steps, k-step
+// w + NW·(kg·KPW + i), into the same accumulators; one LDS exchange at the end, as ever.  The loop is NOT unrolled: group kg + 1's
+// fragments reuse group kg's registers (fp32, two column tiles: 48 + 24 fragment VGPRs instead of 96 + 48 — 144 do not fit the 128 a
+// 1024-thread workgroup leaves a wave), at the price of one memory round trip per group.  KG = 1 is the kernel as it always was.
+template <typename TW, int KPW, bool LN, int NT, bool XT = false, int KG = 1>
 __global__ __launch_bounds__(1024) void dec_linear_kernel(DecLinearParams p) {
     static_assert(!(LN && XT), "the LayerNorm prologue reads the fp32 residual stream");
+    static_assert(!(LN && KG > 1), "the LayerNorm statistics need the whole row before the first MFMA");
 #ifdef WM_DEV
 #define WM_DL_STAMP(k) do { if (p.dbg && (threadIdx.x & 63) == 0) p.dbg[(((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + (threadIdx.x >> 6)) * 8 + (k)] = (long long)wall_clock64(); } while (0)
 #else
@@ -113,6 +118,11 @@ __global__ __launch_bounds__(1024) void dec_linear_kernel(DecLinearParams p) {
         if (p.kcache) cache_row = __builtin_nontemporal_load(&p.ctl->len);
         if (p.cap && !p.cap_map) cache_row = __builtin_nontemporal_load(&p.ctl->len);
     }
+    f32x4 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int kg = 0; kg < KG; ++kg) {
     Frag<TW> wf[NT][KPW];
     Frag<TW> xft[XT ? KPW : 1];
     f32x4 xa[XT ? 1 : KPW][2];
@@ -121,13 +131,13 @@ __global__ __launch_bounds__(1024) void dec_linear_kernel(DecLinearParams p) {
     // and a wave issues loads only as fast as the CU's address path takes them (24 x 1 KB per wave here)
 #pragma unroll
     for (int i = 0; i < KPW; ++i) {
-        const int k = (w + nw * i) * 32;
+        const int k = (w + nw * (kg * KPW + i)) * 32;
 #pragma unroll
         for (int t = 0; t < NT; ++t) wf[t][i] = load_frag<TW>(wp[t] + k);
     }
 #pragma unroll
     for (int i = 0; i < KPW; ++i) {
-        const int k = (w + nw * i) * 32;
+        const int k = (w + nw * (kg * KPW + i)) * 32;
         if constexpr (XT) {
             xft[i] = load_frag<TW>(xpt + k);
         } else {
@@ -172,9 +182,6 @@ __global__ __launch_bounds__(1024) void dec_linear_kernel(DecLinearParams p) {
         rstd = 1.0f / sqrtf(var + 1e-5f);
     }
     WM_DL_STAMP(2);
-    f32x4 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < KPW; ++i) {
         Frag<TW> xf;
@@ -201,6 +208,7 @@ __global__ __launch_bounds__(1024) void dec_linear_kernel(DecLinearParams p) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) acc[t] = mma32(wf[t][i], xf, acc[t]);
     }
+    }  // kg
 #pragma unroll
     for (int t = 0; t < NT; ++t) s_red[w][t][lane] = acc[t];
     WM_DL_STAMP(3);
@@ -255,6 +263,29 @@ __global__ __launch_bounds__(1024) void dec_linear_kernel(DecLinearParams p) {
     WM_DL_STAMP(5);
 }
 #undef WM_DL_STAMP
+// K = 3072 (the only K past 2048 the kernel takes): 16 waves, two groups of three k-steps each.  No LayerNorm form: a row of 3072
+// columns is an MLP hidden row, never the residual stream.
+static const int DEC_LINEAR_K_LONG = 3072;
+template <typename TW> static int launch_dec_linear_long(const DecLinearParams& p, hipStream_t st) {
+    if (p.ln_g) return launch_refuse("dec_linear: no LayerNorm prologue at K = 3072");
+    constexpr int NW = 16, KPW = 3, KG = 2;
+    static_assert(NW * KPW * KG * 32 == DEC_LINEAR_K_LONG, "the groups cover K exactly");
+    const bool wide = p.N >= 1024;
+    const dim3 grid((p.N + (wide ? 31 : 15)) / (wide ? 32 : 16), (p.B + 15) / 16), block(NW * 64);
+    const size_t smem = (size_t)NW * (wide ? 2 : 1) * 64 * sizeof(f32x4) + (size_t)NW * 16 * 2 * sizeof(float);
+    if (sizeof(TW) == 2 && p.x_is_t) {
+        if (wide)
+            hipLaunchKernelGGL((dec_linear_kernel<TW, KPW, false, 2, true, KG>), grid, block, smem, st, p);
+        else
+            hipLaunchKernelGGL((dec_linear_kernel<TW, KPW, false, 1, true, KG>), grid, block, smem, st, p);
+    } else {
+        if (wide)
+            hipLaunchKernelGGL((dec_linear_kernel<TW, KPW, false, 2, false, KG>), grid, block, smem, st, p);
+        else
+            hipLaunchKernelGGL((dec_linear_kernel<TW, KPW, false, 1, false, KG>), grid, block, smem, st, p);
+    }
+    return WM_LAUNCH_OK;
+}
 template <typename TW, int KPW> static int launch_dec_linear_t(const DecLinearParams& p, int nw, hipStream_t st) {
     // two column tiles per workgroup for the wide projections (QKV, fc1): half the workgroups, one activation
     // fragment (and one LayerNorm) feeding two MFMAs
@@ -307,13 +338,14 @@ static int dec_linear_waves(int K, int elem_bytes = 2) {
             if (ksteps % c == 0 && ksteps / c <= lim) return c;
     return 0;
 }
-bool dec_linear_supports_k(int K) { return dec_linear_waves(K) > 0; }
+bool dec_linear_supports_k(int K) { return dec_linear_waves(K) > 0 || K == DEC_LINEAR_K_LONG; }
 template <typename TW> int launch_dec_linear(const DecLinearParams& p, hipStream_t st) {
     if (p.B <= 0 || p.N <= 0) return launch_refuse("dec_linear: empty problem");
+    if (p.K == DEC_LINEAR_K_LONG) return launch_dec_linear_long<TW>(p, st);
     const int ksteps = p.K >> 5;
     const int nw = dec_linear_waves(p.K, (int)sizeof(TW));
     if (nw == 0)  // refuse rather than drop k-steps (check_cfg / wm_op_matmul_nt keep model paths away from here)
-        return launch_refuse("dec_linear: K must be a multiple of 32 whose k-steps split over <= 16 waves x <= 4 steps (K <= 2048)");
+        return launch_refuse("dec_linear: K must be a multiple of 32 whose k-steps split over <= 16 waves x <= 4 steps (K <= 2048), or 3072");
     switch (ksteps / nw) {
         case 1: return launch_dec_linear_t<TW, 1>(p, nw, st);
         case 2: return launch_dec_linear_t<TW, 2>(p, nw, st);
@@ -543,7 +575,12 @@ __global__ __launch_bounds__(512) void dec_logits_kernel(DecLinearParams p, int 
     constexpr int PAD = sizeof(TW) == 2 ? 80 - (K % 128) : 16 / sizeof(TW);
     constexpr int PITCH = K + PAD;
     constexpr int KS = KD * 4;                         // k-steps of 32
-    constexpr int CHK = sizeof(TW) == 2 ? KS : KS / 2;  // k-steps whose weight fragments are in flight together
+    // k-steps whose weight fragments are in flight together: every panel of a tile for 16-bit operands and half of them for fp32 up to
+    // d_model 512 (128 fragment VGPRs for the two tiles); at d_model 768 (24 k-steps) half of that again — 96 VGPRs, not 192 — rather
+    // than spill.  Chunk c > 0 is loaded at the head of chunk c into the registers chunk c - 1 just multiplied from: there is no
+    // explicit prefetch here (the split kernel below has one), any overlap is the scheduler's and the other wave's of the SIMD
+    constexpr int CHK = (sizeof(TW) == 2 ? KS : KS / 2) / (KD > 4 ? 2 : 1);
+    static_assert(KS % CHK == 0, "whole chunks");
 #ifndef WM_LOGITS_PRE
 #define WM_LOGITS_PRE 4
 #endif
@@ -1187,17 +1224,22 @@ template <typename TW, int KD, int NRB, bool LP = false> static int launch_dec_l
     hipLaunchKernelGGL((dec_logits_kernel<TW, KD, NRB, LP>), grid, dim3(512), lds, st, p, ct);
     return WM_LAUNCH_OK;
 }
-// requires ln_g/ln_b, no bias/act/residual, K in {128, 384, 512}, ldo % 4 == 0; amax_stride >= dec_logits_parts(N)
+// requires ln_g/ln_b, no bias/act/residual, K in {128, 384, 512, 768}, ldo % 4 == 0; amax_stride >= dec_logits_parts(N)
 template <typename TW, bool LP> static int launch_dec_logits_lp(const DecLinearParams& p, hipStream_t st) {
     const int kd = p.K >> 7;
     if (p.B <= 0 || p.N <= 0) return launch_refuse("dec_logits: empty problem");
-    if ((p.K & 127) != 0 || (kd != 1 && kd != 3 && kd != 4)) return launch_refuse("dec_logits: d_model must be 128, 384 or 512");
+    if ((p.K & 127) != 0 || (kd != 1 && kd != 3 && kd != 4 && kd != 6)) return launch_refuse("dec_logits: d_model must be 128, 384, 512 or 768");
     if (!p.ln_g || !p.ln_b) return launch_refuse("dec_logits: the final LayerNorm's gamma / beta are required");
     if (p.amax_val && p.amax_stride < dec_logits_parts(p.N)) return launch_refuse("dec_logits: amax_stride is smaller than the partials per utterance");
     if (LP && !p.amax_val) return launch_refuse("dec_logits: log-probabilities need the fused argmax (amax_val)");
     if constexpr (sizeof(TW) == 4) {
         // fp32 weights: the three-way bf16 split (d_model 128 / 384: three activation images fit the 160 KB of LDS); d_model 512
-        // keeps the exact-fp32 MFMA kernel.  WM_LOGITS_EXACT (developer build) forces the exact kernel for A/B runs.
+        // keeps the exact-fp32 MFMA kernel, and so does d_model 768 — NOT the split: three bf16 images of 64 x 768 are 301 KB.  At 768
+        // even one fp32 image of 64 rows (64 x 772 x 4 = 198 KB) is past the LDS, so the exact kernel runs 32 rows per workgroup there
+        // (99 KB) and a 64- or 128-row state is 2 or 4 row blocks in grid.y: the kernel is MFMA-bound with fp32 operands (see the note
+        // at dec_logits_split_kernel), the MFMA count is the same, and the embedding's second read comes from the Infinity Cache.  A
+        // row's arithmetic does not depend on the rows beside it, so ids stay bitwise equal across batch sizes and coalescing.
+        // WM_LOGITS_EXACT (developer build) forces the exact kernel for A/B runs.
         static const bool exact = wm_env("WM_LOGITS_EXACT") != nullptr;
         if (!exact && (kd == 1 || kd == 3)) {
             if (p.B <= 16) return kd == 1 ? launch_dec_logits_split_t<1, 1, LP>(p, st) : launch_dec_logits_split_t<3, 1, LP>(p, st);
@@ -1210,8 +1252,10 @@ template <typename TW, bool LP> static int launch_dec_logits_lp(const DecLinearP
     if (p.B <= 16) {
         if (kd == 1) return launch_dec_logits_t<TW, 1, 1, LP>(p, st);
         if (kd == 3) return launch_dec_logits_t<TW, 3, 1, LP>(p, st);
+        if (kd == 6) return launch_dec_logits_t<TW, 6, 1, LP>(p, st);
         return launch_dec_logits_t<TW, 4, 1, LP>(p, st);
     }
+    if (kd == 6) return launch_dec_logits_t<TW, 6, sizeof(TW) == 4 ? 2 : 4, LP>(p, st);  // (16-bit, 64 rows: 106 KB image + 30 KB static)
 #ifdef WM_DEV
     if constexpr (sizeof(TW) == 2) {
         // Developer A/B (WM_LOGITS_128_16BIT): 128 rows per workgroup for 16-bit weights too.  Measured SLOWER than two 64-row

@@ -3,7 +3,7 @@
 //
 //   score_collect   the real rows of a position-major prefill chunk -> the pass's row buffer [M][d]
 //   score_ln        the final LayerNorm of the M rows, ONCE, written in the operand form the sweep multiplies: TW rows for 16-bit
-//                   decoders and for fp32 at d = 512, the three bf16 images (x = h + m + l by truncation, dec_logits_split_kernel's
+//                   decoders and for fp32 at d = 512 / 768, the three bf16 images (x = h + m + l by truncation, dec_logits_split_kernel's
 //                   split) for fp32 at d = 128 / 384.  Statistics and rounding are those of the decode step's logits kernels
 //                   (8 threads per row, thread q sums the float4 groups q + 8·i in order, three butterfly adds).
 //   score_logits    grid (vocabulary parts, row blocks of 128).  Wave w of a workgroup keeps the operand fragments of its 16 rows in
@@ -103,7 +103,15 @@ template <typename TW, int KD, bool SPLIT> struct ScoreCfg {
     static constexpr int K = KD * 128;
     static constexpr int KS = KD * 4;                          // k-steps of 32
     static constexpr int CS = sizeof(TW) == 2 ? 4 : 2;         // column tiles (of 16) per stage
-    static constexpr int COLS = CS * 16;
+    // column tiles staged (and held in flight as `pre`) together.  fp32 rows of d_model 768 keep 24 fragments = 192 VGPRs per lane for
+    // the whole kernel: a stage goes through LDS one tile at a time there, in the same tile order — stages, parts and every row's
+    // arithmetic are what two tiles at once would give — and a tile is fetched when it is parked, not a tile ahead: 24 VGPRs of
+    // prefetch held across the MFMAs were 15 more than the 256 a 512-thread workgroup leaves a wave (60 bytes of scratch).  The
+    // sweep issues 192 MFMAs of 32 cycles per tile and wave with fp32 operands, so the exposed round trip is expected to be the smaller
+    // part; that has not been measured
+    static constexpr int CSU = (sizeof(TW) == 4 && !SPLIT && KD > 4) ? 1 : CS;
+    static constexpr int SUB = CS / CSU;                       // staged units per stage
+    static constexpr int COLS = CSU * 16;
     static constexpr int ESZ = SPLIT ? 2 : (int)sizeof(TW);    // bytes per LDS element
     // LDS row pitch in elements: 16-bit images ≡ 8 dwords (mod 64), as dec_logits_split_kernel's; fp32 rows + 16 bytes
     static constexpr int PITCH = ESZ == 2 ? K + 16 : K + 4;
@@ -163,12 +171,12 @@ __global__ __launch_bounds__(512) void score_logits_kernel(ScoreSweepParams p) {
 
     // one stage of embedding rows: global -> registers (in flight during the previous stage's MFMAs) -> LDS
     f32x4 pre[C::NCH];
-    auto fetch = [&](int stage) {
+    auto fetch = [&](int unit) {
 #pragma unroll
         for (int i = 0; i < C::NCH; ++i) {
             const int c = threadIdx.x + i * 512;
             const int col = c / C::CPR, off = c % C::CPR;
-            const int n = min(stage * C::COLS + col, p.N - 1);  // columns past N re-read the last row; the epilogue drops them
+            const int n = min(unit * C::COLS + col, p.N - 1);  // columns past N re-read the last row; the epilogue drops them
             pre[i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const unsigned char*>(p.W) + ((size_t)n * C::CPR + off) * 16);
         }
     };
@@ -205,15 +213,19 @@ __global__ __launch_bounds__(512) void score_logits_kernel(ScoreSweepParams p) {
     float m = -INFINITY, s = 0.f, zt = 0.f;  // running max = the best value so far, Σ exp(v − m), target logit
     int bi = INT_MAX;
     bool got = false;
-    if (st_lo < st_hi) fetch(st_lo);
-    for (int stg = st_lo; stg < st_hi; ++stg) {
-        __syncthreads();  // every wave is past the previous stage's fragment reads
+    // staged units of CSU tiles: SUB per stage (1 everywhere but fp32 at d_model 768), none past the vocabulary's last tile
+    const int u_lo = st_lo * C::SUB, u_hi = min(st_hi * C::SUB, (tiles + C::CSU - 1) / C::CSU);
+    constexpr bool AHEAD = C::SUB == 1;  // the next unit's rows in flight during this unit's MFMAs
+    if (AHEAD && u_lo < u_hi) fetch(u_lo);
+    for (int stg = u_lo; stg < u_hi; ++stg) {
+        if (!AHEAD) fetch(stg);
+        __syncthreads();  // every wave is past the previous unit's fragment reads
         park();
         __syncthreads();
-        if (stg + 1 < st_hi) fetch(stg + 1);
+        if (AHEAD && stg + 1 < u_hi) fetch(stg + 1);
 #pragma unroll
-        for (int t = 0; t < C::CS; ++t) {
-            const int n0 = (stg * C::CS + t) * 16;
+        for (int t = 0; t < C::CSU; ++t) {
+            const int n0 = (stg * C::CSU + t) * 16;
             if (n0 >= p.N) break;  // workgroup-uniform
             f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
             if constexpr (SPLIT) {
@@ -372,18 +384,20 @@ template <typename TW, int KD, bool SPLIT> static int score_run(const ScoreParam
     hipLaunchKernelGGL(score_merge_kernel, dim3((q.M + 127) / 128), dim3(128), 0, st, mp);
     return WM_LAUNCH_OK;
 }
-size_t score_operand_bytes(int M, int K, int dtype) { return (size_t)M * K * (dtype == 0 ? (K == 512 ? 4 : 6) : 2); }
+size_t score_operand_bytes(int M, int K, int dtype) { return (size_t)M * K * (dtype == 0 ? (K >= 512 ? 4 : 6) : 2); }
 template <typename TW> int launch_score(const ScoreParams& q, hipStream_t st, hipEvent_t* ev) {
     const int kd = q.K >> 7;
     if (q.M <= 0 || q.N <= 0) return launch_refuse("score: empty problem");
-    if ((q.K & 127) != 0 || (kd != 1 && kd != 3 && kd != 4)) return launch_refuse("score: d_model must be 128, 384 or 512");
+    if ((q.K & 127) != 0 || (kd != 1 && kd != 3 && kd != 4 && kd != 6)) return launch_refuse("score: d_model must be 128, 384, 512 or 768");
     if constexpr (sizeof(TW) == 4) {
         if (kd == 1) return score_run<float, 1, true>(q, st, ev);
         if (kd == 3) return score_run<float, 3, true>(q, st, ev);
+        if (kd == 6) return score_run<float, 6, false>(q, st, ev);  // exact fp32, as d_model 512 and as the decode step's logits at 768
         return score_run<float, 4, false>(q, st, ev);
     } else {
         if (kd == 1) return score_run<TW, 1, false>(q, st, ev);
         if (kd == 3) return score_run<TW, 3, false>(q, st, ev);
+        if (kd == 6) return score_run<TW, 6, false>(q, st, ev);
         return score_run<TW, 4, false>(q, st, ev);
     }
 }

@@ -523,14 +523,18 @@ static int check_cfg(const wm_config* c) {
     const wm_dims& d = c->dims;
     if (d.d_model <= 0 || d.n_heads <= 0 || d.d_model != d.n_heads * 64)
         return fail(WM_E_ARG, "d_model must equal n_heads*64 (got %d, %d)", d.d_model, d.n_heads);
-    if (d.n_heads > 8) return fail(WM_E_ARG, "n_heads > 8 not supported");
+    // Whisper-small (d_model 768, 12 heads, ffn 3072) is the one shape past 8 heads: its cross-attention runs on the K/V cache
+    // (m->xattn stays <= 8 heads), its fc2 on the two-group form of the skinny linear (launch_dec_linear_long)
+    const bool small = d.d_model == 768 && d.n_heads == 12;
+    if (d.n_heads > 8 && !small) return fail(WM_E_ARG, "n_heads > 8 not supported (except 12 heads at d_model 768)");
     if (d.d_model % 128 || d.ffn % 128) return fail(WM_E_ARG, "d_model and ffn must be multiples of 128");
-    // what the decode kernels are instantiated for: the logits kernel keeps d_model/128 in {1, 3, 4} k-panels
+    // what the decode kernels are instantiated for: the logits kernel keeps d_model/128 in {1, 3, 4, 6} k-panels
     // (kernels_decoder.hip launch_dec_logits), the skinny linears split K/32 k-steps over <= 16 waves x <= 4 steps
-    if (d.d_model != 128 && d.d_model != 384 && d.d_model != 512)
-        return fail(WM_E_ARG, "d_model %d not supported (128, 384 or 512)", d.d_model);
-    if (!dec_linear_supports_k(d.d_model) || !dec_linear_supports_k(d.ffn))
-        return fail(WM_E_ARG, "ffn %d not supported (ffn/32 must split into <= 16 waves x <= 4 k-steps, ffn <= 2048)", d.ffn);
+    if (d.d_model != 128 && d.d_model != 384 && d.d_model != 512 && !small)
+        return fail(WM_E_ARG, "d_model %d not supported (128, 384, 512 or 768)", d.d_model);
+    if (small && d.ffn != 3072) return fail(WM_E_ARG, "ffn %d not supported (d_model 768 takes ffn 3072 only)", d.ffn);
+    if (!small && (d.ffn > 2048 || !dec_linear_supports_k(d.ffn)))
+        return fail(WM_E_ARG, "ffn %d not supported (ffn/32 must split into <= 16 waves x <= 4 k-steps, ffn <= 2048; 3072 with d_model 768)", d.ffn);
     if ((d.n_layers * 2 * d.d_model) % 128) return fail(WM_E_ARG, "n_layers*2*d_model must be a multiple of 128");
     if (d.n_text_ctx > 512) return fail(WM_E_ARG, "n_text_ctx > 512 not supported");
     if (d.n_mels <= 0 || d.n_audio_ctx <= 0 || d.vocab <= 0 || d.n_layers <= 0) return fail(WM_E_ARG, "bad dims");
@@ -3617,7 +3621,7 @@ extern "C" int wm_align_phases(wm_model* m, int slot, float* ms) {
 extern "C" int wm_op_score_logits(float* logprob, int32_t* top_id, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                                   const int32_t* target, int M, int N, int K, int dtype) {
     if (!logprob || !top_id || !x || !ln_g || !ln_b || !emb || !target || M <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
-    if (K != 128 && K != 384 && K != 512) return fail(WM_E_ARG, "K must be 128, 384 or 512 (the logits kernels' d_model)");
+    if (K != 128 && K != 384 && K != 512 && K != 768) return fail(WM_E_ARG, "K must be 128, 384, 512 or 768 (the logits kernels' d_model)");
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
     for (int r = 0; r < M; ++r)
         if (target[r] >= N) return fail(WM_E_ARG, "target[%d] = %d is not a vocabulary id", r, target[r]);
@@ -4786,7 +4790,7 @@ static int op_dec_linear(float* out, const float* x, const float* W, const float
                          const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel, const int32_t* cap_map = nullptr, int cap_dst = 0) {
     if (!out || !x || !W || B <= 0 || N <= 0 || K <= 0) return fail(WM_E_ARG, "bad argument");
     if (dtype < 0 || dtype > 2 || (gelu_mode != 0 && gelu_mode != 1)) return fail(WM_E_ARG, "bad dtype / gelu_mode");
-    if (!dec_linear_supports_k(K)) return fail(WM_E_ARG, "K must be a multiple of 32 whose k-steps split over <= 16 waves x <= 4 steps (K <= 2048)");
+    if (!dec_linear_supports_k(K)) return fail(WM_E_ARG, "K must be a multiple of 32 whose k-steps split over <= 16 waves x <= 4 steps (K <= 2048), or 3072");
     if (!ln_g != !ln_b) return fail(WM_E_ARG, "ln_g and ln_b go together");
     if (ln_g && x_is_t) return fail(WM_E_ARG, "the LayerNorm prologue reads fp32 rows (no x_is_t)");
     if (!kcache != !vcache) return fail(WM_E_ARG, "kcache and vcache go together");
@@ -4915,7 +4919,7 @@ extern "C" int wm_op_dec_linear_capmap(float* out, float* cap, const float* x, c
 static int op_logits(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                      const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
     if (!logits || !ids || !x || !ln_g || !ln_b || !emb || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
-    if (K != 128 && K != 384 && K != 512) return fail(WM_E_ARG, "K must be 128, 384 or 512 (the logits kernels' d_model)");
+    if (K != 128 && K != 384 && K != 512 && K != 768) return fail(WM_E_ARG, "K must be 128, 384, 512 or 768 (the logits kernels' d_model)");
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
     if (ranges && (timestamp_begin <= 0 || timestamp_begin >= N)) return fail(WM_E_ARG, "ranges need 0 < timestamp_begin < N");
     TmpDev t;
@@ -5018,7 +5022,7 @@ extern "C" int wm_op_logits_lp(float* logits, int32_t* ids, float* logprob, cons
 extern "C" int wm_op_no_speech(float* prob, float* lse, const float* x, const float* ln_g, const float* ln_b, const float* emb, int B, int N, int K,
                                int dtype, int token) {
     if (!prob || !lse || !x || !ln_g || !ln_b || !emb || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
-    if (K != 128 && K != 384 && K != 512) return fail(WM_E_ARG, "K must be 128, 384 or 512 (the logits kernels' d_model)");
+    if (K != 128 && K != 384 && K != 512 && K != 768) return fail(WM_E_ARG, "K must be 128, 384, 512 or 768 (the logits kernels' d_model)");
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
     if (token < 0 || token >= N) return fail(WM_E_ARG, "token %d is not a vocabulary id", token);
     TmpDev t;
@@ -5044,7 +5048,7 @@ extern "C" int wm_op_no_speech(float* prob, float* lse, const float* x, const fl
 extern "C" int wm_op_lang_detect(int32_t* lang_out, float* probs, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                                  const int32_t* lang_ids, int n_lang, int B, int N, int K, int dtype) {
     if (!lang_out || !x || !ln_g || !ln_b || !emb || !lang_ids || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
-    if (K != 128 && K != 384 && K != 512) return fail(WM_E_ARG, "K must be 128, 384 or 512 (the logits kernels' d_model)");
+    if (K != 128 && K != 384 && K != 512 && K != 768) return fail(WM_E_ARG, "K must be 128, 384, 512 or 768 (the logits kernels' d_model)");
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
     WMCHK(lang_list_check(N, lang_ids, n_lang));
     TmpDev t;

@@ -276,8 +276,8 @@ def lang_detect(x, ln_g, ln_b, emb, lang_ids, dtype=DT_F32):
     g, b = f(ln_g).ravel(), f(ln_b).ravel()
     if x.ndim != 2 or emb.ndim != 2 or emb.shape[1] != x.shape[1] or g.size != x.shape[1] or b.size != x.shape[1]:
         raise ValueError("x must be [B, K], emb [N, K], ln_g / ln_b [K]")
-    if x.shape[1] not in (128, 384, 512):
-        raise ValueError("K must be 128, 384 or 512")
+    if x.shape[1] not in (128, 384, 512, 768):
+        raise ValueError("K must be 128, 384, 512 or 768")
     ids = _lib.lang_args(lang_ids, emb.shape[0])
     B, K = x.shape
     out, probs = np.zeros(B, np.int32), np.zeros((B, ids.size), np.float32)
