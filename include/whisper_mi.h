@@ -490,6 +490,12 @@ int wm_op_ln_matmul_nt(float* C, const float* A, const float* ln_g, const float*
 /* layer_norm(out, inp, gamma, beta, eps)  whisper_tensor.mojo:249-285 (one-pass variance). cols % 128 == 0, <= 1024 */
 int wm_op_layer_norm(float* out, const float* inp, const float* gamma, const float* beta, int rows, int cols,
                      float eps);
+/* The LayerNorm launch of the base / small encoder as it is made before a projection: launch_layernorm_rows<dtype> storing the
+ * operand-dtype rows (out_t, returned widened to fp32), the fp32 rows (out_f), or both from one launch.  Either of out_t / out_f may be
+ * NULL, not both.  Both hold rows + 1 rows, in and out: the device buffers start from the caller's values (out_t's rounded to dtype),
+ * so the guard row after the last comes back as it went in unless the kernel wrote it.  cols as wm_op_layer_norm.  Known-answer tests. */
+int wm_op_layer_norm_t(float* out_t, float* out_f, const float* inp, const float* gamma, const float* beta, int rows, int cols,
+                       float eps, int dtype);
 /* The q_len == 1 path of MultiHeadAttention.forward over cached keys / values (layers.mojo:186-272): per utterance and head
  * s_j = (q·K_j)·0.125 (scale AFTER the dot product), running max from -1e10, p = exp(s - max), o = Σ p_j V_j / Σ p_j.
  * q, out [B, 64·n_heads] fp32; k, v [B, t, 64·n_heads] fp32 host rows, rounded to kv_dtype as the cache holds them.
@@ -578,6 +584,9 @@ int wm_op_mlp_block(float* x, const float* ln_g, const float* ln_b, const float*
  * fp32 host rows; dtype = operand rounding of q, k, v and of the probabilities (WM_F32: exact).  Runs the encoder's fused
  * attention kernel (never materialises S).  Known-answer tests. */
 int wm_op_attention(float* out, const float* q, const float* k, const float* v, int n_ctx, int n_heads, int dtype);
+/* wm_op_attention over B utterances in ONE launch, as an encoder pass makes it: q, k, v, out [B, n_ctx, 64·n_heads].  B = 1 is
+ * wm_op_attention.  B <= 0, n_heads outside 1..64 or a bad dtype: WM_E_ARG, nothing launched, out untouched. */
+int wm_op_attention_batch(float* out, const float* q, const float* k, const float* v, int B, int n_ctx, int n_heads, int dtype);
 /* gelu(t) in place  whisper_tensor.mojo:288-308 (mode WM_GELU_TANH) */
 int wm_op_gelu(float* t, size_t n, int mode);
 /* softmax(t) rows in place  whisper_tensor.mojo:311-355 */

@@ -17,7 +17,8 @@ def declared_symbols():
 def test_header_declares_the_boundary():
     syms = declared_symbols()
     for s in ("wm_model_load", "wm_transcribe", "wm_encode", "wm_decode_step", "wm_state_new", "wm_op_matmul_nt",
-              "wm_op_layer_norm", "wm_op_gelu", "wm_op_softmax_rows", "wm_op_conv1d_k3", "wm_op_argmax"):
+              "wm_op_layer_norm", "wm_op_gelu", "wm_op_softmax_rows", "wm_op_conv1d_k3", "wm_op_argmax",
+              "wm_op_attention_batch", "wm_op_layer_norm_t"):
         assert s in syms
 
 
@@ -85,6 +86,10 @@ def test_op_wrappers_validate_shapes_before_calling_the_library():
         wt.attention(np.zeros_like(q), q, np.zeros((9, 128), np.float32), q, 2)
     with pytest.raises(ValueError):  # out of the wrong shape
         wt.attention(np.zeros((10, 64), np.float32), q, q, q, 2)
+    with pytest.raises(ValueError):  # the batched form takes [B, n_ctx, d]
+        wt.attention_batch(np.zeros_like(q), q, q, q, 2)
+    with pytest.raises(ValueError):  # LayerNorm with neither store asked for
+        wt.layer_norm_t(x, np.ones(128), np.zeros(128))
     with pytest.raises(ValueError):  # cached keys must be [B, t, d]
         wt.attention_cached(np.zeros_like(q), q, q, q, 2)
     with pytest.raises(ValueError):  # another batch size in the cache

@@ -33,6 +33,7 @@ SYMBOLS = [
     "wm_score", "wm_score_submit", "wm_score_wait", "wm_score_pcm", "wm_op_score_logits", "wm_score_phases",
     "wm_align", "wm_align_submit", "wm_align_wait", "wm_align_pcm", "wm_align_phases", "wm_op_dec_linear_capmap", "wm_op_token_times_rows",
     "wm_op_align_probs", "wm_op_align_norm",
+    "wm_op_attention_batch", "wm_op_layer_norm_t",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -238,6 +239,8 @@ def lib():
     L.wm_op_attention_cached.argtypes = [fp] * 4 + [C.c_int] * 9
     L.wm_op_dec_linear.argtypes = [fp] * 7 + [C.c_int] * 8 + [fp, fp] + [C.c_int] * 5 + [fp, C.POINTER(C.c_int8)] + [C.c_int] * 3
     L.wm_op_layer_norm.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_float]
+    L.wm_op_layer_norm_t.argtypes = [fp] * 5 + [C.c_int, C.c_int, C.c_float, C.c_int]
+    L.wm_op_attention_batch.argtypes = [fp] * 4 + [C.c_int] * 4
     L.wm_op_gelu.argtypes = [fp, C.c_size_t, C.c_int]
     L.wm_op_softmax_rows.argtypes = [fp, C.c_int, C.c_int]
     L.wm_op_conv1d_k3.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]

@@ -958,7 +958,9 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __rest
         q += __shfl_xor(q, o, 64);
     }
     const float mean = s / (float)cols;
-    const float var = (q / (float)cols) - (mean * mean);
+    // The one-pass variance cancels on rows whose mean is large against their spread and can come out below -eps (a constant row of
+    // 13.7 gave NaN): clamp at 0.  fmaxf returns var itself wherever var >= 0, so every other row keeps its bits.
+    const float var = fmaxf((q / (float)cols) - (mean * mean), 0.f);
     const float inv_std = 1.0f / sqrtf(var + eps);
     if (!ok) return;
 #pragma unroll

@@ -4582,6 +4582,35 @@ extern "C" int wm_op_layer_norm(float* out, const float* inp, const float* gamma
 }
 
 static void widen_to_f32(const void* src, int dtype, size_t n, float* dst);
+// launch_layernorm_rows<T> with the operand-dtype store (out_t, returned widened), the fp32 store (out_f), or both — the launches the
+// base / small encoder makes before every projection.  out_t / out_f hold rows + 1 rows, in and out: the device buffers start from the
+// caller's values, so the guard row (and anything else the kernel did not write) comes back as it went in.  Known-answer tests.
+extern "C" int wm_op_layer_norm_t(float* out_t, float* out_f, const float* inp, const float* gamma, const float* beta, int rows, int cols,
+                                  float eps, int dtype) {
+    if ((!out_t && !out_f) || !inp || !gamma || !beta || rows <= 0 || cols <= 0) return fail(WM_E_ARG, "bad argument");
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    if (cols % 128 || cols > 1024) return fail(WM_E_ARG, "cols must be a multiple of 128 and <= 1024");
+    const size_t n = (size_t)rows * cols, ng = n + cols;
+    TmpDev t;
+    t.bufs.reserve(8);
+    DevBuf &x = t.add(), &g = t.add(), &b = t.add(), &ot = t.add(), &of = t.add();
+    WMCHK(upload(x, inp, n, WM_F32));
+    WMCHK(upload(g, gamma, cols, WM_F32));
+    WMCHK(upload(b, beta, cols, WM_F32));
+    if (out_t) WMCHK(upload(ot, out_t, ng, dtype));
+    if (out_f) WMCHK(upload(of, out_f, ng, WM_F32));
+    DISPATCH_DT(dtype, TT, launch_layernorm_rows<TT>(x.as<float>(), g.as<float>(), b.as<float>(), out_t ? ot.p : nullptr,
+                                                     out_f ? of.as<float>() : nullptr, rows, cols, eps, nullptr));
+    HIPCHK(hipGetLastError());
+    if (out_t) {
+        std::vector<unsigned char> h(ng * dt_size(dtype));
+        HIPCHK(hipMemcpy(h.data(), ot.p, h.size(), hipMemcpyDeviceToHost));
+        widen_to_f32(h.data(), dtype, ng, out_t);
+    }
+    if (out_f) HIPCHK(hipMemcpy(out_f, of.p, ng * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int wm_op_mlp_block(float* x, const float* ln_g, const float* ln_b, const float* fc1_w, const float* fc1_b, const float* fc2_w,
                                const float* fc2_b, const float* next_g, const float* next_b, float* xn_out, int M, int d, int ffn,
                                int dtype, int gelu_mode) {
@@ -4678,27 +4707,30 @@ static void widen_to_f32(const void* src, int dtype, size_t n, float* dst) {
     }
 }
 
-extern "C" int wm_op_attention(float* out, const float* q, const float* k, const float* v, int n_ctx, int n_heads, int dtype) {
-    if (!out || !q || !k || !v || n_ctx <= 0 || n_heads <= 0 || n_heads > 64) return fail(WM_E_ARG, "bad argument");
+extern "C" int wm_op_attention_batch(float* out, const float* q, const float* k, const float* v, int B, int n_ctx, int n_heads, int dtype) {
+    if (!out || !q || !k || !v || B <= 0 || n_ctx <= 0 || n_heads <= 0 || n_heads > 64) return fail(WM_E_ARG, "bad argument");
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
-    const size_t d = (size_t)n_heads * 64, n = (size_t)n_ctx * d;
-    std::vector<float> packed(3 * n);  // the fused projection layout the kernel reads: row = [q | k | v]
-    for (int t = 0; t < n_ctx; ++t) {
-        memcpy(&packed[(size_t)t * 3 * d], q + (size_t)t * d, d * 4);
-        memcpy(&packed[(size_t)t * 3 * d + d], k + (size_t)t * d, d * 4);
-        memcpy(&packed[(size_t)t * 3 * d + 2 * d], v + (size_t)t * d, d * 4);
+    const size_t d = (size_t)n_heads * 64, rows = (size_t)B * n_ctx, n = rows * d;
+    std::vector<float> packed(3 * n);  // the fused projection layout the kernel reads: row = [q | k | v], utterances back to back
+    for (size_t t = 0; t < rows; ++t) {
+        memcpy(&packed[t * 3 * d], q + t * d, d * 4);
+        memcpy(&packed[t * 3 * d + d], k + t * d, d * 4);
+        memcpy(&packed[t * 3 * d + 2 * d], v + t * d, d * 4);
     }
     TmpDev t;
     t.bufs.reserve(4);
     DevBuf &qkv = t.add(), &o = t.add();
     WMCHK(upload(qkv, packed.data(), packed.size(), dtype));
     WMCHK(o.alloc(n * dt_size(dtype), true));
-    DISPATCH_DT(dtype, TT, launch_flash_attn_enc<TT>(qkv.p, o.p, 1, n_heads, n_ctx, 0.125f, nullptr));
+    DISPATCH_DT(dtype, TT, launch_flash_attn_enc<TT>(qkv.p, o.p, B, n_heads, n_ctx, 0.125f, nullptr));
     HIPCHK(hipGetLastError());
     std::vector<unsigned char> h(n * dt_size(dtype));
     HIPCHK(hipMemcpy(h.data(), o.p, h.size(), hipMemcpyDeviceToHost));
     widen_to_f32(h.data(), dtype, n, out);
     return 0;
+}
+extern "C" int wm_op_attention(float* out, const float* q, const float* k, const float* v, int n_ctx, int n_heads, int dtype) {
+    return wm_op_attention_batch(out, q, k, v, 1, n_ctx, n_heads, dtype);
 }
 
 static int op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,

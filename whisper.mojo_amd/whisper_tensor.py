@@ -77,6 +77,16 @@ def attention(out: np.ndarray, q, k, v, n_heads: int, dtype=DT_F32):
     _lib.check(_lib.lib().wm_op_attention(_fp(out), _fp(q), _fp(k), _fp(v), n_ctx, n_heads, dtype))
 
 
+def attention_batch(out: np.ndarray, q, k, v, n_heads: int, dtype=DT_F32):
+    """attention over B utterances in one launch (wm_op_attention_batch): q, k, v, out [B, n_ctx, 64 * n_heads]."""
+    f = lambda a: np.ascontiguousarray(a, np.float32)
+    q, k, v = f(q), f(k), f(v)
+    if q.ndim != 3 or q.shape[2] != 64 * n_heads or k.shape != q.shape or v.shape != q.shape:
+        raise ValueError("q, k, v must be [B, n_ctx, 64 * n_heads]")
+    _chk_out(out, q.shape)
+    _lib.check(_lib.lib().wm_op_attention_batch(_fp(out), _fp(q), _fp(k), _fp(v), q.shape[0], q.shape[1], n_heads, dtype))
+
+
 def attention_cached(out: np.ndarray, q, k, v, n_heads: int, kv_dtype=DT_F32, n_chunks: int = 1, out_dtype=DT_F32, q_B: int = 0,
                      len: int = -1, nq: int = 0, key_lo=None):
     """layers.mojo:186-272, the q_len == 1 path over cached rows: q [B, d], k / v [B, t, d] -> out [B, d].
@@ -167,6 +177,20 @@ def layer_norm(out: np.ndarray, inp, gamma, beta, eps: float = 1e-5):
     g, b = np.ascontiguousarray(gamma, np.float32).ravel(), np.ascontiguousarray(beta, np.float32).ravel()
     _chk_out(out, x.shape)
     _lib.check(_lib.lib().wm_op_layer_norm(_fp(out), _fp(x), _fp(g), _fp(b), x.shape[0], x.shape[1], eps))
+
+
+def layer_norm_t(inp, gamma, beta, eps: float = 1e-5, dtype=DT_F32, out_t=None, out_f=None):
+    """One launch of the LayerNorm kernel with its operand-dtype store (out_t, returned widened to fp32), its fp32 store (out_f), or
+    both (wm_op_layer_norm_t).  out_t / out_f: caller's [rows + 1, cols] float32 arrays, at least one, in and out: rows the kernel does not
+    write (the guard row after the last) keep the caller's values."""
+    x = np.ascontiguousarray(inp, np.float32)
+    g, b = np.ascontiguousarray(gamma, np.float32).ravel(), np.ascontiguousarray(beta, np.float32).ravel()
+    if out_t is None and out_f is None:
+        raise ValueError("out_t, out_f or both")
+    for o in (out_t, out_f):
+        if o is not None:
+            _chk_out(o, (x.shape[0] + 1, x.shape[1]))
+    _lib.check(_lib.lib().wm_op_layer_norm_t(_fp(out_t), _fp(out_f), _fp(x), _fp(g), _fp(b), x.shape[0], x.shape[1], eps, dtype))
 
 
 def gelu(t: np.ndarray, mode: int = GELU_TANH):
