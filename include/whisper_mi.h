@@ -571,6 +571,11 @@ int wm_op_score_logits(float* logprob, int32_t* top_id, const float* x, const fl
  * 1 <= nsplit <= 64 (chunks of ceil(n_keys / nsplit) keys; trailing chunks may be empty).  Known-answer tests. */
 int wm_op_xattn(float* out, const float* q, const float* Wk, const float* Wv, const float* bv, const float* x, int rows, int q_B,
                 int n_utt, int n_keys, int n_heads, int nsplit, int out_dtype);
+/* The first launch of wm_op_xattn alone: q'[r, h] = (0.125·q_h[r])·Wk_h as the X sweep reads it, three bf16 images whose sum is the
+ * fp32 product (x = hi + mid + lo by truncation).  images [rows, 3, n_heads, 64·n_heads], widened to fp32; q [rows, 64·n_heads] fp32;
+ * Wk [64·n_heads, 64·n_heads] rounded to bf16 on upload.  late_loads != 0: the loop that requests its Wk rows after q is staged
+ * (the default requests all of them first); the images are equal bit for bit.  1 <= n_heads <= 8.  Known-answer tests. */
+int wm_op_xattn_absorb(float* images, const float* q, const float* Wk, int rows, int n_heads, int late_loads);
 /* The MLP half of ResidualAttentionBlock.forward  layers.mojo:489-517 :  x += fc2(gelu(fc1(layer_norm(x, ln_g, ln_b)))),
  * x [M, d] in place; fc1_w [ffn, d], fc2_w [d, ffn] (HF [out, in]).  With next_g / next_b / xn_out non-NULL also returns
  * layer_norm(x_new, next_g, next_b) rounded to the operand dtype (what the next projection is fed) in xn_out [M, d].

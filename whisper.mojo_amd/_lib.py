@@ -34,6 +34,7 @@ SYMBOLS = [
     "wm_align", "wm_align_submit", "wm_align_wait", "wm_align_pcm", "wm_align_phases", "wm_op_dec_linear_capmap", "wm_op_token_times_rows",
     "wm_op_align_probs", "wm_op_align_norm",
     "wm_op_attention_batch", "wm_op_layer_norm_t",
+    "wm_op_xattn_absorb",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -284,6 +285,7 @@ def lib():
     L.wm_long_result_windows.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_int64), fp, fp, ip]
     L.wm_long_result_skip_stats.argtypes = [vp, ip]
     L.wm_op_xattn.argtypes = [fp] * 6 + [C.c_int] * 7
+    L.wm_op_xattn_absorb.argtypes = [fp] * 3 + [C.c_int] * 3
     L.wm_bench_kernel.argtypes = [vp, vp, C.c_int, C.c_int, fp]
     L.wm_bench_bytes.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double)]
     L.wm_synth_weights.argtypes = [C.POINTER(WmDims), C.c_uint64, fp]

@@ -1575,28 +1575,49 @@ __device__ __forceinline__ void split3_1(float x, unsigned short& h, unsigned sh
 
 // q'[row][h][c] = Σ_e (scale·q[row][h*64+e])·Wk[h*64+e][c], written once per row as three bf16 images [row][3][H][d].
 // grid (ceil(rows / 4), H), d/2 threads: thread t owns columns 2t, 2t+1 of four rows (one coalesced Wk row read per e).
+// EARLY: the thread's 64 Wk loads depend on nothing loaded, so all of them are requested before q is loaded, staged and the barrier
+// passed — one memory round trip under the staging instead of four batches of 16 after it.  The e loop then runs on the registers:
+// same order, same fmafs, bitwise the same images.  EARLY = false is the loop as it was (op tests, A/B).
+template <bool EARLY>
 __global__ __launch_bounds__(256) void xattn_absorb_kernel(XAttnParams p) {
     constexpr int R = 4;
     __shared__ float sq[R][64];
     const int r0 = blockIdx.x * R, h = blockIdx.y, t = threadIdx.x;
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+    const bf16* w = (const bf16*)p.Wk + (size_t)h * 64 * p.d + 2 * t;
+    bf16x2 wr[EARLY ? 64 : 1];
+    if constexpr (EARLY) {
+#pragma unroll
+        for (int e = 0; e < 64; ++e) wr[e] = *reinterpret_cast<const bf16x2*>(w + (size_t)e * p.d);
+    }
     for (int i = t; i < R * 64; i += blockDim.x) {
         const int r = r0 + i / 64;
         sq[i / 64][i % 64] = r < p.rows ? p.q[(size_t)r * p.d + h * 64 + i % 64] * p.scale : 0.f;
     }
     __syncthreads();
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    const bf16* w = (const bf16*)p.Wk + (size_t)h * 64 * p.d + 2 * t;
     float acc[R][2];
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[r][0] = acc[r][1] = 0.f;
-#pragma unroll 16
-    for (int e = 0; e < 64; ++e) {
-        const bf16x2 wv = *reinterpret_cast<const bf16x2*>(w + (size_t)e * p.d);
-        const float w0 = (float)wv[0], w1 = (float)wv[1];
+    if constexpr (EARLY) {
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            acc[r][0] = fmaf(sq[r][e], w0, acc[r][0]);
-            acc[r][1] = fmaf(sq[r][e], w1, acc[r][1]);
+        for (int e = 0; e < 64; ++e) {
+            const float w0 = (float)wr[e][0], w1 = (float)wr[e][1];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                acc[r][0] = fmaf(sq[r][e], w0, acc[r][0]);
+                acc[r][1] = fmaf(sq[r][e], w1, acc[r][1]);
+            }
+        }
+    } else {
+#pragma unroll 16
+        for (int e = 0; e < 64; ++e) {
+            const bf16x2 wv = *reinterpret_cast<const bf16x2*>(w + (size_t)e * p.d);
+            const float w0 = (float)wv[0], w1 = (float)wv[1];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                acc[r][0] = fmaf(sq[r][e], w0, acc[r][0]);
+                acc[r][1] = fmaf(sq[r][e], w1, acc[r][1]);
+            }
         }
     }
     unsigned short* qs = (unsigned short*)p.qs;
@@ -1898,9 +1919,14 @@ static int xattn_check(const XAttnParams& p) {
         return launch_refuse("xattn: needs 1 <= heads <= 8 of 64 dims, rows > 0, 1 <= nsplit <= 64");
     return WM_LAUNCH_OK;
 }
-int launch_xattn_absorb(const XAttnParams& p, hipStream_t st) {
+int launch_xattn_absorb(const XAttnParams& p, hipStream_t st, bool late_loads) {
     if (const int rc = xattn_check(p)) return rc;
-    hipLaunchKernelGGL(xattn_absorb_kernel, dim3((p.rows + 3) / 4, p.H), dim3(p.d / 2), 0, st, p);
+    static const bool late_env = wm_env("WM_ABSORB_LATE") != nullptr;  // developer build A/B: the loop that loads Wk after the barrier
+    const dim3 grid((p.rows + 3) / 4, p.H), block(p.d / 2);
+    if (late_loads || late_env)
+        hipLaunchKernelGGL(xattn_absorb_kernel<false>, grid, block, 0, st, p);
+    else
+        hipLaunchKernelGGL(xattn_absorb_kernel<true>, grid, block, 0, st, p);
     return WM_LAUNCH_OK;
 }
 template <int H> static void launch_xattn_h(const XAttnParams& p, hipStream_t st) {

@@ -5166,6 +5166,35 @@ extern "C" int wm_op_xattn(float* out, const float* q, const float* Wk, const fl
     return 0;
 }
 
+// xattn_absorb_kernel alone: the three bf16 images of q' as the X sweep reads them
+extern "C" int wm_op_xattn_absorb(float* images, const float* q, const float* Wk, int rows, int n_heads, int late_loads) {
+    if (!images || !q || !Wk || rows <= 0) return fail(WM_E_ARG, "bad argument");
+    if (n_heads < 1 || n_heads > 8) return fail(WM_E_ARG, "needs 1 <= n_heads <= 8");
+    const size_t d = (size_t)n_heads * 64, n = (size_t)rows * 3 * n_heads * d;
+    TmpDev t;
+    t.bufs.reserve(4);
+    DevBuf &dq = t.add(), &wk = t.add(), &qs = t.add();
+    WMCHK(upload(dq, q, (size_t)rows * d, WM_F32));
+    WMCHK(upload(wk, Wk, d * d, WM_BF16));
+    WMCHK(qs.alloc(n * 2, true));
+    XAttnParams x{};
+    x.q = dq.as<float>();
+    x.Wk = wk.p;
+    x.n_keys = 1;  // (not read by the absorb; the launch check wants a key)
+    x.nsplit = 1;
+    x.H = n_heads;
+    x.d = (int)d;
+    x.rows = rows;
+    x.scale = ATTN_SCALE;
+    x.qs = qs.p;
+    LCHK(launch_xattn_absorb(x, nullptr, late_loads != 0));
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned char> h(n * 2);
+    HIPCHK(hipMemcpy(h.data(), qs.p, h.size(), hipMemcpyDeviceToHost));
+    widen_to_f32(h.data(), WM_BF16, n, images);
+    return 0;
+}
+
 extern "C" int wm_op_gelu(float* tt, size_t n, int mode) {
     if (!tt || (mode != 0 && mode != 1)) return fail(WM_E_ARG, "bad argument");
     if (n == 0) return 0;

@@ -242,7 +242,8 @@ struct XAttnParams {
     void* out;           // [rows][d] in out_dtype
     int out_dtype;
 };
-int launch_xattn_absorb(const XAttnParams& p, hipStream_t st);  // WM_LAUNCH_*
+// late_loads: the absorb loop that requests its Wk rows after the q staging, as it was; same images bit for bit (op tests, A/B)
+int launch_xattn_absorb(const XAttnParams& p, hipStream_t st, bool late_loads = false);  // WM_LAUNCH_*
 int launch_xattn(const XAttnParams& p, hipStream_t st);
 int launch_xattn_merge(const XAttnParams& p, hipStream_t st);
 

@@ -323,6 +323,19 @@ def xattn(out: np.ndarray, q, Wk, Wv, bv, x, n_heads: int, nsplit: int, q_B: int
                                       n_heads, nsplit, out_dtype))
 
 
+def xattn_absorb(q, Wk, n_heads: int, late_loads: bool = False) -> np.ndarray:
+    """The absorb launch alone (wm_op_xattn_absorb): q [rows, d], Wk [d, d] -> the three bf16 images of q' [rows, 3, n_heads, d],
+    widened to fp32.  late_loads: the loop that requests Wk after staging q; the same images bit for bit."""
+    f = lambda a: np.ascontiguousarray(a, np.float32)
+    q, Wk = f(q), f(Wk)
+    d = 64 * n_heads
+    if q.ndim != 2 or q.shape[1] != d or Wk.shape != (d, d):
+        raise ValueError("q must be [rows, 64 * n_heads], Wk [d, d]")
+    images = np.zeros((q.shape[0], 3, n_heads, d), np.float32)
+    _lib.check(_lib.lib().wm_op_xattn_absorb(_fp(images), _fp(q), _fp(Wk), q.shape[0], n_heads, int(late_loads)))
+    return images
+
+
 def align_probs(q, layer_head_pairs, rows, n_layers: int, kv=None, kv_dtype=DT_F32, X=None, Wk=None, probs=None):
     """launch_align_probs alone (wm_op_align_probs): q [B, L, n_sel, 64] unscaled cross-q rows, layer_head_pairs [n_sel, 2], rows [B]
     (utterance b's first rows[b] <= L rows count).  Keys: kv [n_layers, 2, B, T, d] (the K/V cache, uploaded as kv_dtype) or the
