@@ -30,7 +30,7 @@ enum { WM_POS_REF = 0 /* start_pos = current_len-1, whisper.mojo:217 */, WM_POS_
 
 /* Replaces WhisperConfig (whisper.mojo:15-31) + config.mojo:4-17.  dims.d_model / dims.n_heads must be 64
  * (layers.mojo:190-198 hard-codes a 64-wide head).  Shapes the kernels are instantiated for: d_model 128, 384 (tiny) or 512
- * (base) with ffn <= 2048 whose ffn/32 splits into <= 16 x <= 4, and d_model 768 with 12 heads and ffn 3072 (small).  Anything else
+ * (base) with ffn <= 2048 whose ffn/32 splits into <= 16 x <= 4, d_model 768 with 12 heads and ffn 3072 (small), and d_model 1024 with 16 heads and ffn 4096 (medium).  Anything else
  * is refused at load with WM_E_ARG and a message that names the field. */
 typedef struct {
     wm_dims dims;
@@ -531,6 +531,13 @@ int wm_op_dec_linear(float* out, const float* x, const float* W, const float* bi
                      const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
                      float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
                      const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel);
+/* wm_op_dec_linear on the K-long form of the kernel, the one fc2 of d_model 768 / 1024 runs: 16 waves walking groups of k-steps into
+ * the same accumulators.  Same arguments and results; K must be 3072 or 4096 and ln_g / ln_b NULL (the form has no LayerNorm
+ * prologue).  K = 3072 gives wm_op_dec_linear's bits; K = 4096 is refused by wm_op_dec_linear and taken here.  Known-answer tests. */
+int wm_op_dec_linear_long(float* out, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
+                          const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
+                          float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
+                          const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel);
 /* The decode step's final LayerNorm + tied-embedding logits and fused argmax (whisper.mojo:156-166, whisper_tensor.mojo:431-439):
  * logits[B, N] = layer_norm(x, ln_g, ln_b, 1e-5)·emb[N, K]ᵀ on the decode step's logits kernel, emb rounded to dtype on upload (the
  * kernel variant follows from dtype, K and B as in a decode step), and ids[B] = the fused argmax of those logits (stage 1 in the
@@ -538,7 +545,7 @@ int wm_op_dec_linear(float* out, const float* x, const float* W, const float* bi
  * 0 / -inf applied to the argmax candidates only, or NULL.  ranges [B][4] = (text_lo, text_hi, ts_lo, ts_hi), or NULL: with
  * 0 < timestamp_begin < N the timestamp decision is on — the best admissible text id in [text_lo, text_hi) unless
  * logsumexp of the admissible timestamps in [ts_lo, ts_hi) exceeds its logit, then the best admissible timestamp.
- * x [B, K] fp32, K in {128, 384, 512}.  Known-answer tests. */
+ * x [B, K] fp32, K in {128, 384, 512, 768, 1024}.  Known-answer tests. */
 int wm_op_logits(float* logits, int32_t* ids, const float* x, const float* ln_g, const float* ln_b, const float* emb, const float* mask,
                  const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype);
 /* wm_op_logits on the log-prob instantiation of the same kernel variant, plus logprob[B] = logits[id] - logsumexp over the candidates
@@ -559,7 +566,7 @@ int wm_op_lang_detect(int32_t* lang_out, float* probs, const float* x, const flo
  * sweep with the fused log-sum-exp / target gather / arg-max, and the merge.  With z = layer_norm(x, ln_g, ln_b, 1e-5)·emb[N, K]ᵀ (emb
  * rounded to dtype on upload; the arithmetic class per dtype and K is wm_op_logits's): logprob[r] = z[r][target[r]] - logsumexp_j z[r][j]
  * and top_id[r] = argmax_j z[r][j], lowest id on ties.  target[r] < 0: the row is not scored — logprob[r] = 0, top_id[r] is still
- * written; target[r] >= N: WM_E_ARG.  x [M, K] fp32, K in {128, 384, 512}; logprob, top_id, target: [M].  Known-answer tests. */
+ * written; target[r] >= N: WM_E_ARG.  x [M, K] fp32, K in {128, 384, 512, 768, 1024}; logprob, top_id, target: [M].  Known-answer tests. */
 int wm_op_score_logits(float* logprob, int32_t* top_id, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                        const int32_t* target, int M, int N, int K, int dtype);
 /* The absorbed cross-attention of bf16-encoder / fp32-K/V models: per row r and head h, with X = x[utt(r)] and

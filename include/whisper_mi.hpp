@@ -42,6 +42,7 @@ struct WhisperConfig {
     static WhisperConfig tiny() { return WhisperConfig{}; }
     static WhisperConfig base() { return WhisperConfig{512, 8, 6, 2048, 80, 1500, 448, 51865}; }
     static WhisperConfig small() { return WhisperConfig{768, 12, 12, 3072, 80, 1500, 448, 51865}; }
+    static WhisperConfig medium() { return WhisperConfig{1024, 16, 24, 4096, 80, 1500, 448, 51865}; }
     static WhisperConfig micro() { return WhisperConfig{128, 2, 2, 512, 16, 100, 64, 1000}; }  // test-size model
     wm_dims dims() const { return wm_dims{d_model, n_heads, n_layers, ffn, n_mels, n_audio_ctx, n_text_ctx, vocab_size}; }
     int n_frames() const { return 2 * n_audio_ctx; }

@@ -35,6 +35,7 @@ SYMBOLS = [
     "wm_op_align_probs", "wm_op_align_norm",
     "wm_op_attention_batch", "wm_op_layer_norm_t",
     "wm_op_xattn_absorb",
+    "wm_op_dec_linear_long",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -239,6 +240,7 @@ def lib():
     L.wm_op_attention.argtypes = [fp] * 4 + [C.c_int] * 3
     L.wm_op_attention_cached.argtypes = [fp] * 4 + [C.c_int] * 9
     L.wm_op_dec_linear.argtypes = [fp] * 7 + [C.c_int] * 8 + [fp, fp] + [C.c_int] * 5 + [fp, C.POINTER(C.c_int8)] + [C.c_int] * 3
+    L.wm_op_dec_linear_long.argtypes = L.wm_op_dec_linear.argtypes
     L.wm_op_layer_norm.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_float]
     L.wm_op_layer_norm_t.argtypes = [fp] * 5 + [C.c_int, C.c_int, C.c_float, C.c_int]
     L.wm_op_attention_batch.argtypes = [fp] * 4 + [C.c_int] * 4

@@ -58,6 +58,11 @@ class WhisperConfig:
         return WhisperConfig(768, 12, 12, 51865, 3072, 80, 1500, 448)
 
     @staticmethod
+    def medium() -> "WhisperConfig":
+        """openai/whisper-medium: 16 heads of 64, 24 layers (cross-attention on the K/V cache)."""
+        return WhisperConfig(1024, 16, 24, 51865, 4096, 80, 1500, 448)
+
+    @staticmethod
     def micro() -> "WhisperConfig":
         """Reduced test model: same structure, runs in seconds on a CPU."""
         return WhisperConfig(128, 2, 2, 1000, 512, 16, 100, 64)

@@ -63,7 +63,7 @@ __device__ __forceinline__ void store_as(void* base, size_t idx, float v, int dt
         ((f16*)base)[idx] = (f16)v;
 }
 
-// KG > 1 (K = 3072, fc2 of d_model 768: 96 k-steps = 16 waves x KG = 2 groups x KPW = 3): a wave walks KG groups of KPW k-steps, k-step
+// KG > 1 (K = 3072, fc2 of d_model 768: 96 k-steps = 16 waves x KG = 2 groups x KPW = 3; K = 4096, fc2 of d_model 1024: 2 x 4): a wave walks KG groups of KPW k-steps, k-step
 // w + NW·(kg·KPW + i), into the same accumulators; one LDS exchange at the end, as ever.  The loop is NOT unrolled: group kg + 1's
 // fragments reuse group kg's registers (fp32, two column tiles: 48 + 24 fragment VGPRs instead of 96 + 48 — 144 do not fit the 128 a
 // 1024-thread workgroup leaves a wave), at the price of one memory round trip per group.  KG = 1 is the kernel as it always was.
@@ -263,13 +263,14 @@ __global__ __launch_bounds__(1024) void dec_linear_kernel(DecLinearParams p) {
     WM_DL_STAMP(5);
 }
 #undef WM_DL_STAMP
-// K = 3072 (the only K past 2048 the kernel takes): 16 waves, two groups of three k-steps each.  No LayerNorm form: a row of 3072
-// columns is an MLP hidden row, never the residual stream.
-static const int DEC_LINEAR_K_LONG = 3072;
-template <typename TW> static int launch_dec_linear_long(const DecLinearParams& p, hipStream_t st) {
-    if (p.ln_g) return launch_refuse("dec_linear: no LayerNorm prologue at K = 3072");
-    constexpr int NW = 16, KPW = 3, KG = 2;
-    static_assert(NW * KPW * KG * 32 == DEC_LINEAR_K_LONG, "the groups cover K exactly");
+// K past 2048, the K-long form: 16 waves walking KG groups of KPW k-steps.  K = 3072 (fc2 of d_model 768) is 2 groups of 3, K = 4096
+// (fc2 of d_model 1024, 128 k-steps) 2 groups of 4: fp32 with two column tiles holds wf[2][4] + xa[4][2] = 64 + 32 fragment VGPRs of
+// the 128 a 1024-thread workgroup leaves a wave, and 4 groups of 2 would pay two more memory round trips for registers nobody needs.
+// No LayerNorm form: a row of 3072 / 4096 columns is an MLP hidden row, never the residual stream.
+static const int DEC_LINEAR_K_LONG = 3072, DEC_LINEAR_K_LONG2 = 4096;
+template <typename TW, int KPW, int KG> static int launch_dec_linear_long_t(const DecLinearParams& p, hipStream_t st) {
+    constexpr int NW = 16;
+    if (p.K != NW * KPW * KG * 32) return launch_refuse("dec_linear: the k-step groups do not cover K");
     const bool wide = p.N >= 1024;
     const dim3 grid((p.N + (wide ? 31 : 15)) / (wide ? 32 : 16), (p.B + 15) / 16), block(NW * 64);
     const size_t smem = (size_t)NW * (wide ? 2 : 1) * 64 * sizeof(f32x4) + (size_t)NW * 16 * 2 * sizeof(float);
@@ -285,6 +286,11 @@ template <typename TW> static int launch_dec_linear_long(const DecLinearParams& 
             hipLaunchKernelGGL((dec_linear_kernel<TW, KPW, false, 1, false, KG>), grid, block, smem, st, p);
     }
     return WM_LAUNCH_OK;
+}
+template <typename TW> static int launch_dec_linear_long(const DecLinearParams& p, hipStream_t st) {
+    if (p.ln_g) return launch_refuse("dec_linear: no LayerNorm prologue at K = 3072 / 4096");
+    if (p.K == DEC_LINEAR_K_LONG2) return launch_dec_linear_long_t<TW, 4, 2>(p, st);
+    return launch_dec_linear_long_t<TW, 3, 2>(p, st);
 }
 template <typename TW, int KPW> static int launch_dec_linear_t(const DecLinearParams& p, int nw, hipStream_t st) {
     // two column tiles per workgroup for the wide projections (QKV, fc1): half the workgroups, one activation
@@ -339,13 +345,17 @@ static int dec_linear_waves(int K, int elem_bytes = 2) {
     return 0;
 }
 bool dec_linear_supports_k(int K) { return dec_linear_waves(K) > 0 || K == DEC_LINEAR_K_LONG; }
+// what a model's ffn and wm_op_dec_linear_long may be: the above and K = 4096.  (wm_op_dec_linear and wm_op_matmul_nt keep the
+// narrower answer: their refusal of K = 4096 is part of their contract.)
+bool dec_linear_long_supports_k(int K) { return K == DEC_LINEAR_K_LONG || K == DEC_LINEAR_K_LONG2; }
+bool dec_linear_model_supports_k(int K) { return dec_linear_supports_k(K) || K == DEC_LINEAR_K_LONG2; }
 template <typename TW> int launch_dec_linear(const DecLinearParams& p, hipStream_t st) {
     if (p.B <= 0 || p.N <= 0) return launch_refuse("dec_linear: empty problem");
-    if (p.K == DEC_LINEAR_K_LONG) return launch_dec_linear_long<TW>(p, st);
+    if (dec_linear_long_supports_k(p.K)) return launch_dec_linear_long<TW>(p, st);
     const int ksteps = p.K >> 5;
     const int nw = dec_linear_waves(p.K, (int)sizeof(TW));
     if (nw == 0)  // refuse rather than drop k-steps (check_cfg / wm_op_matmul_nt keep model paths away from here)
-        return launch_refuse("dec_linear: K must be a multiple of 32 whose k-steps split over <= 16 waves x <= 4 steps (K <= 2048), or 3072");
+        return launch_refuse("dec_linear: K must be a multiple of 32 whose k-steps split over <= 16 waves x <= 4 steps (K <= 2048), or 3072 / 4096");
     switch (ksteps / nw) {
         case 1: return launch_dec_linear_t<TW, 1>(p, nw, st);
         case 2: return launch_dec_linear_t<TW, 2>(p, nw, st);
@@ -579,8 +589,11 @@ __global__ __launch_bounds__(512) void dec_logits_kernel(DecLinearParams p, int 
     // d_model 512 (128 fragment VGPRs for the two tiles); at d_model 768 (24 k-steps) half of that again — 96 VGPRs, not 192 — rather
     // than spill.  Chunk c > 0 is loaded at the head of chunk c into the registers chunk c - 1 just multiplied from: there is no
     // explicit prefetch here (the split kernel below has one), any overlap is the scheduler's and the other wave's of the SIMD
-    constexpr int CHK = (sizeof(TW) == 2 ? KS : KS / 2) / (KD > 4 ? 2 : 1);
+    // At d_model 1024 (32 k-steps) a quarter: 8 k-steps for 16-bit, 4 for fp32 — 64 VGPRs for the two tiles (a third, 10.67, is no whole
+    // chunk, and a half would be 128 VGPRs, past the 96 that d_model 768 holds)
+    constexpr int CHK = (sizeof(TW) == 2 ? KS : KS / 2) / (KD > 6 ? 4 : KD > 4 ? 2 : 1);
     static_assert(KS % CHK == 0, "whole chunks");
+    static_assert(2 * K <= 4 * 512, "gamma | beta are fetched as one float4 per thread");
 #ifndef WM_LOGITS_PRE
 #define WM_LOGITS_PRE 4
 #endif
@@ -1215,7 +1228,11 @@ int dec_logits_parts(int N) {
     return (tiles + ct - 1) / ct;
 }
 template <typename TW, int KD, int NRB, bool LP = false> static int launch_dec_logits_t(const DecLinearParams& p, hipStream_t st) {
-    const size_t lds = (size_t)NRB * 16 * (KD * 128 + (sizeof(TW) == 2 ? 80 : 16 / sizeof(TW))) * sizeof(TW);
+    constexpr size_t lds = (size_t)NRB * 16 * (KD * 128 + (sizeof(TW) == 2 ? 80 : 16 / sizeof(TW))) * sizeof(TW);
+    // beside the image: gamma | beta (8·K bytes) and, up to 64 rows, the epilogue's scratch: 2 x 32 + 4 x 8 (+ 8 with log-probs)
+    // floats / ints per row.  At 128 rows the scratch overlays the image.
+    static_assert(lds + (size_t)8 * KD * 128 + (NRB <= 4 ? (size_t)NRB * 16 * 4 * (LP ? 104 : 96) : 0) <= 160 * 1024,
+                  "activation image + static LDS must fit the 160 KB of a CU");
     if (lds > 48 * 1024)
         if (const hipError_t e = ensure_dyn_lds<&dec_logits_kernel<TW, KD, NRB, LP>>((int)lds); e != hipSuccess)
             return launch_hip_failed("logits kernel: dynamic LDS attribute", e);
@@ -1224,11 +1241,11 @@ template <typename TW, int KD, int NRB, bool LP = false> static int launch_dec_l
     hipLaunchKernelGGL((dec_logits_kernel<TW, KD, NRB, LP>), grid, dim3(512), lds, st, p, ct);
     return WM_LAUNCH_OK;
 }
-// requires ln_g/ln_b, no bias/act/residual, K in {128, 384, 512, 768}, ldo % 4 == 0; amax_stride >= dec_logits_parts(N)
+// requires ln_g/ln_b, no bias/act/residual, K in {128, 384, 512, 768, 1024}, ldo % 4 == 0; amax_stride >= dec_logits_parts(N)
 template <typename TW, bool LP> static int launch_dec_logits_lp(const DecLinearParams& p, hipStream_t st) {
     const int kd = p.K >> 7;
     if (p.B <= 0 || p.N <= 0) return launch_refuse("dec_logits: empty problem");
-    if ((p.K & 127) != 0 || (kd != 1 && kd != 3 && kd != 4 && kd != 6)) return launch_refuse("dec_logits: d_model must be 128, 384, 512 or 768");
+    if ((p.K & 127) != 0 || (kd != 1 && kd != 3 && kd != 4 && kd != 6 && kd != 8)) return launch_refuse("dec_logits: d_model must be 128, 384, 512, 768 or 1024");
     if (!p.ln_g || !p.ln_b) return launch_refuse("dec_logits: the final LayerNorm's gamma / beta are required");
     if (p.amax_val && p.amax_stride < dec_logits_parts(p.N)) return launch_refuse("dec_logits: amax_stride is smaller than the partials per utterance");
     if (LP && !p.amax_val) return launch_refuse("dec_logits: log-probabilities need the fused argmax (amax_val)");
@@ -1253,8 +1270,12 @@ template <typename TW, bool LP> static int launch_dec_logits_lp(const DecLinearP
         if (kd == 1) return launch_dec_logits_t<TW, 1, 1, LP>(p, st);
         if (kd == 3) return launch_dec_logits_t<TW, 3, 1, LP>(p, st);
         if (kd == 6) return launch_dec_logits_t<TW, 6, 1, LP>(p, st);
+        if (kd == 8) return launch_dec_logits_t<TW, 8, 1, LP>(p, st);
         return launch_dec_logits_t<TW, 4, 1, LP>(p, st);
     }
+    // d_model 1024: 32 rows per workgroup for every operand type (16-bit: 32 x 1104 x 2 = 69 KB image + 21 KB static; fp32:
+    // 32 x 1028 x 4 = 129 KB + 21 KB; 64 rows of 16-bit would be 138 + 34 KB, past the 160).  More rows are more row blocks in grid.y.
+    if (kd == 8) return launch_dec_logits_t<TW, 8, 2, LP>(p, st);
     if (kd == 6) return launch_dec_logits_t<TW, 6, sizeof(TW) == 4 ? 2 : 4, LP>(p, st);  // (16-bit, 64 rows: 106 KB image + 30 KB static)
 #ifdef WM_DEV
     if constexpr (sizeof(TW) == 2) {

@@ -3,11 +3,11 @@
 //
 //   score_collect   the real rows of a position-major prefill chunk -> the pass's row buffer [M][d]
 //   score_ln        the final LayerNorm of the M rows, ONCE, written in the operand form the sweep multiplies: TW rows for 16-bit
-//                   decoders and for fp32 at d = 512 / 768, the three bf16 images (x = h + m + l by truncation, dec_logits_split_kernel's
+//                   decoders and for fp32 at d >= 512, the three bf16 images (x = h + m + l by truncation, dec_logits_split_kernel's
 //                   split) for fp32 at d = 128 / 384.  Statistics and rounding are those of the decode step's logits kernels
 //                   (8 threads per row, thread q sums the float4 groups q + 8·i in order, three butterfly adds).
 //   score_logits    grid (vocabulary parts, row blocks of 128).  Wave w of a workgroup keeps the operand fragments of its 16 rows in
-//                   registers for the whole kernel; the workgroup stages the embedding 64 (16-bit) / 32 (fp32) columns at a time
+//                   registers for the whole kernel (d = 1024: half a row at a time, re-read per staged unit; ScoreCfg::NP); the workgroup stages the embedding 64 (16-bit) / 32 (fp32) columns at a time
 //                   into LDS — fp32 weights on the split path are split once while they are staged — and every wave multiplies the
 //                   staged columns with its rows, so each embedding byte that arrives from HBM or the Infinity Cache serves 128 rows.
 //                   Per lane a running (max, Σ exp(v − max), arg-max, target logit) over its 4 columns of every tile; the four lanes
@@ -110,6 +110,14 @@ template <typename TW, int KD, bool SPLIT> struct ScoreCfg {
     // sweep issues 192 MFMAs of 32 cycles per tile and wave with fp32 operands, so the exposed round trip is expected to be the smaller
     // part; that has not been measured
     static constexpr int CSU = (sizeof(TW) == 4 && !SPLIT && KD > 4) ? 1 : CS;
+    // d_model 1024 (32 k-steps): a row is 32 fragments — 256 VGPRs in fp32, 128 in 16-bit next to 64 of prefetch and the ~100 the rest
+    // of the sweep takes — so it is NOT held.  K is walked in NP = 2 halves: for each staged unit a wave fetches the first half of its
+    // 16 rows (16 fragments, from L2: score_ln wrote them just before), multiplies every tile of the unit by it, fetches the second half
+    // into the same registers and carries each tile's accumulator on.  A tile's k-steps still enter its accumulator in the order
+    // 0, 1, ..., 31, so the bits are those of a held row.  (Rows in LDS instead: 128 x 1024 is 256 KB in 16-bit — no room.)
+    static constexpr int NP = KD > 6 ? 2 : 1;
+    static constexpr int KSP = KS / NP;                        // k-steps of a wave's rows in registers together
+    static_assert(!(SPLIT && NP > 1), "the split images are held whole");
     static constexpr int SUB = CS / CSU;                       // staged units per stage
     static constexpr int COLS = CSU * 16;
     static constexpr int ESZ = SPLIT ? 2 : (int)sizeof(TW);    // bytes per LDS element
@@ -135,6 +143,31 @@ struct ScoreSweepParams {
     float* ztgt;        // [M]
 };
 
+// one tile into a lane's running (max, Σ exp, arg-max, target logit): acc[r] = logit[row][n0 + 4 g + r].  Text, not a function: both forms
+// of the sweep below expand it, and the held-row form compiles to what it was before the second form existed.
+#define WM_SCORE_FOLD(n0, acc)                                                                                                   \
+    do {                                                                                                                         \
+        float v[4];                                                                                                              \
+        float mt = m; /* the maximum after this tile */                                                                          \
+        _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                                          \
+            const int n = (n0) + 4 * g + r;                                                                                      \
+            v[r] = n < p.N ? (acc)[r] : -INFINITY;                                                                               \
+            if (n == tgt) {                                                                                                      \
+                zt = (acc)[r];                                                                                                   \
+                got = true;                                                                                                      \
+            }                                                                                                                    \
+            if (v[r] > mt) { /* n grows along the loop: strict '>' keeps the lowest id */                                        \
+                mt = v[r];                                                                                                       \
+                bi = n;                                                                                                          \
+            }                                                                                                                    \
+        }                                                                                                                        \
+        if (mt > m) { /* the sum follows the maximum once per tile.  (the s > 0 guards here and in the merges keep */            \
+            s = s > 0.f ? s * expf(m - mt) : 0.f; /* expf(-inf - -inf) = NaN out while nothing has been summed yet) */           \
+            m = mt;                                                                                                              \
+        }                                                                                                                        \
+        _Pragma("unroll") for (int r = 0; r < 4; ++r) if (v[r] > -INFINITY) s += expf(v[r] - m);                                 \
+    } while (0)
+
 template <typename TW, int KD, bool SPLIT>
 __global__ __launch_bounds__(512) void score_logits_kernel(ScoreSweepParams p) {
     using C = ScoreCfg<TW, KD, SPLIT>;
@@ -151,7 +184,7 @@ __global__ __launch_bounds__(512) void score_logits_kernel(ScoreSweepParams p) {
     const int st_lo = blockIdx.x * p.spp, st_hi = min(stages, st_lo + p.spp);
 
     // this wave's rows as MFMA operand fragments, for the whole kernel
-    Frag<TW> af[SPLIT ? 1 : KS];
+    Frag<TW> af[SPLIT ? 1 : C::KSP];
     bf16x8 ah[SPLIT ? KS : 1], am[SPLIT ? KS : 1], al[SPLIT ? KS : 1];
     if constexpr (SPLIT) {
         const bf16* a = reinterpret_cast<const bf16*>(p.a) + (size_t)rr * K + g * 8;
@@ -162,7 +195,7 @@ __global__ __launch_bounds__(512) void score_logits_kernel(ScoreSweepParams p) {
             am[ks] = *reinterpret_cast<const bf16x8*>(a + img + ks * 32);
             al[ks] = *reinterpret_cast<const bf16x8*>(a + 2 * img + ks * 32);
         }
-    } else {
+    } else if constexpr (C::NP == 1) {
         const TW* a = reinterpret_cast<const TW*>(p.a) + (size_t)rr * K + g * 8;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) af[ks] = load_frag<TW>(a + ks * 32);
@@ -223,6 +256,30 @@ __global__ __launch_bounds__(512) void score_logits_kernel(ScoreSweepParams p) {
         park();
         __syncthreads();
         if (AHEAD && stg + 1 < u_hi) fetch(stg + 1);
+        if constexpr (C::NP > 1) {  // K in halves: this wave's rows, half by half, through every tile of the unit
+            const TW* a = reinterpret_cast<const TW*>(p.a) + (size_t)rr * K + g * 8;
+            f32x4 accs[C::CSU];
+#pragma unroll
+            for (int t = 0; t < C::CSU; ++t) accs[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int h = 0; h < C::NP; ++h) {
+#pragma unroll
+                for (int ks = 0; ks < C::KSP; ++ks) af[ks] = load_frag<TW>(a + (h * C::KSP + ks) * 32);
+#pragma unroll
+                for (int t = 0; t < C::CSU; ++t) {
+                    if ((stg * C::CSU + t) * 16 >= p.N) break;  // workgroup-uniform: no MFMAs for a tile past the vocabulary
+                    const TW* xs = reinterpret_cast<const TW*>(smem_raw) + (t * 16 + r16) * PITCH + g * 8 + h * C::KSP * 32;
+#pragma unroll
+                    for (int ks = 0; ks < C::KSP; ++ks) accs[t] = mma32(load_frag<TW>(xs + ks * 32), af[ks], accs[t]);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < C::CSU; ++t) {
+                const int n0 = (stg * C::CSU + t) * 16;
+                if (n0 >= p.N) break;  // workgroup-uniform
+                WM_SCORE_FOLD(n0, accs[t]);
+            }
+        } else {
 #pragma unroll
         for (int t = 0; t < C::CSU; ++t) {
             const int n0 = (stg * C::CSU + t) * 16;
@@ -247,29 +304,8 @@ __global__ __launch_bounds__(512) void score_logits_kernel(ScoreSweepParams p) {
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) acc = mma32(load_frag<TW>(xs + ks * 32), af[ks], acc);
             }
-            // acc[r] = logit[row][n0 + 4 g + r]
-            float v[4];
-            float mt = m;  // the maximum after this tile
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = n0 + 4 * g + r;
-                v[r] = n < p.N ? acc[r] : -INFINITY;
-                if (n == tgt) {
-                    zt = acc[r];
-                    got = true;
-                }
-                if (v[r] > mt) {  // n grows along the loop: strict '>' keeps the lowest id
-                    mt = v[r];
-                    bi = n;
-                }
-            }
-            if (mt > m) {  // the sum follows the maximum once per tile.  (the s > 0 guards here and in the merges keep
-                s = s > 0.f ? s * expf(m - mt) : 0.f;  //  expf(-inf - -inf) = NaN out while nothing has been summed yet)
-                m = mt;
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (v[r] > -INFINITY) s += expf(v[r] - m);
+            WM_SCORE_FOLD(n0, acc);
+        }
         }
     }
     // the four lanes of a row (symmetric, so all four end with the same values)
@@ -294,6 +330,7 @@ __global__ __launch_bounds__(512) void score_logits_kernel(ScoreSweepParams p) {
     }
 }
 
+#undef WM_SCORE_FOLD
 int score_parts(int N, int dtype, int* spp_out) {
     const int cs = dtype == 0 ? 2 : 4;
     const int tiles = (N + 15) / 16, stages = (tiles + cs - 1) / cs;
@@ -388,16 +425,18 @@ size_t score_operand_bytes(int M, int K, int dtype) { return (size_t)M * K * (dt
 template <typename TW> int launch_score(const ScoreParams& q, hipStream_t st, hipEvent_t* ev) {
     const int kd = q.K >> 7;
     if (q.M <= 0 || q.N <= 0) return launch_refuse("score: empty problem");
-    if ((q.K & 127) != 0 || (kd != 1 && kd != 3 && kd != 4 && kd != 6)) return launch_refuse("score: d_model must be 128, 384, 512 or 768");
+    if ((q.K & 127) != 0 || (kd != 1 && kd != 3 && kd != 4 && kd != 6 && kd != 8)) return launch_refuse("score: d_model must be 128, 384, 512, 768 or 1024");
     if constexpr (sizeof(TW) == 4) {
         if (kd == 1) return score_run<float, 1, true>(q, st, ev);
         if (kd == 3) return score_run<float, 3, true>(q, st, ev);
         if (kd == 6) return score_run<float, 6, false>(q, st, ev);  // exact fp32, as d_model 512 and as the decode step's logits at 768
+        if (kd == 8) return score_run<float, 8, false>(q, st, ev);  // exact fp32 too, K in two halves
         return score_run<float, 4, false>(q, st, ev);
     } else {
         if (kd == 1) return score_run<TW, 1, false>(q, st, ev);
         if (kd == 3) return score_run<TW, 3, false>(q, st, ev);
         if (kd == 6) return score_run<TW, 6, false>(q, st, ev);
+        if (kd == 8) return score_run<TW, 8, false>(q, st, ev);
         return score_run<TW, 4, false>(q, st, ev);
     }
 }

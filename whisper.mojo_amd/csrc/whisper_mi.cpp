@@ -523,18 +523,22 @@ static int check_cfg(const wm_config* c) {
     const wm_dims& d = c->dims;
     if (d.d_model <= 0 || d.n_heads <= 0 || d.d_model != d.n_heads * 64)
         return fail(WM_E_ARG, "d_model must equal n_heads*64 (got %d, %d)", d.d_model, d.n_heads);
-    // Whisper-small (d_model 768, 12 heads, ffn 3072) is the one shape past 8 heads: its cross-attention runs on the K/V cache
-    // (m->xattn stays <= 8 heads), its fc2 on the two-group form of the skinny linear (launch_dec_linear_long)
-    const bool small = d.d_model == 768 && d.n_heads == 12;
-    if (d.n_heads > 8 && !small) return fail(WM_E_ARG, "n_heads > 8 not supported (except 12 heads at d_model 768)");
+    // Whisper-small (d_model 768, 12 heads, ffn 3072) and Whisper-medium (d_model 1024, 16 heads, ffn 4096) are the two shapes past 8
+    // heads: their cross-attention runs on the K/V cache (m->xattn stays <= 8 heads), their fc2 on the K-long form of the skinny linear
+    // (launch_dec_linear_long)
+    const bool small = d.d_model == 768 && d.n_heads == 12, medium = d.d_model == 1024 && d.n_heads == 16;
+    if (d.n_heads > 8 && !small && !medium)
+        return fail(WM_E_ARG, "n_heads > 8 not supported (except 12 heads at d_model 768 and 16 heads at d_model 1024)");
     if (d.d_model % 128 || d.ffn % 128) return fail(WM_E_ARG, "d_model and ffn must be multiples of 128");
-    // what the decode kernels are instantiated for: the logits kernel keeps d_model/128 in {1, 3, 4, 6} k-panels
+    // what the decode kernels are instantiated for: the logits kernel keeps d_model/128 in {1, 3, 4, 6, 8} k-panels
     // (kernels_decoder.hip launch_dec_logits), the skinny linears split K/32 k-steps over <= 16 waves x <= 4 steps
-    if (d.d_model != 128 && d.d_model != 384 && d.d_model != 512 && !small)
-        return fail(WM_E_ARG, "d_model %d not supported (128, 384, 512 or 768)", d.d_model);
+    if (d.d_model != 128 && d.d_model != 384 && d.d_model != 512 && !small && !medium)
+        return fail(WM_E_ARG, "d_model %d not supported (128, 384, 512, 768 or 1024)", d.d_model);
     if (small && d.ffn != 3072) return fail(WM_E_ARG, "ffn %d not supported (d_model 768 takes ffn 3072 only)", d.ffn);
-    if (!small && (d.ffn > 2048 || !dec_linear_supports_k(d.ffn)))
-        return fail(WM_E_ARG, "ffn %d not supported (ffn/32 must split into <= 16 waves x <= 4 k-steps, ffn <= 2048; 3072 with d_model 768)", d.ffn);
+    if (medium && d.ffn != 4096) return fail(WM_E_ARG, "ffn %d not supported (d_model 1024 takes ffn 4096 only)", d.ffn);
+    // dec_linear_model_supports_k is what admits 3072 and 4096 (the K-long form of fc2); below d_model 768 the K-long form stays closed
+    if (!dec_linear_model_supports_k(d.ffn) || (!small && !medium && d.ffn > 2048))
+        return fail(WM_E_ARG, "ffn %d not supported (ffn/32 must split into <= 16 waves x <= 4 k-steps, ffn <= 2048; 3072 with d_model 768, 4096 with d_model 1024)", d.ffn);
     if ((d.n_layers * 2 * d.d_model) % 128) return fail(WM_E_ARG, "n_layers*2*d_model must be a multiple of 128");
     if (d.n_text_ctx > 512) return fail(WM_E_ARG, "n_text_ctx > 512 not supported");
     if (d.n_mels <= 0 || d.n_audio_ctx <= 0 || d.vocab <= 0 || d.n_layers <= 0) return fail(WM_E_ARG, "bad dims");
@@ -3621,7 +3625,7 @@ extern "C" int wm_align_phases(wm_model* m, int slot, float* ms) {
 extern "C" int wm_op_score_logits(float* logprob, int32_t* top_id, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                                   const int32_t* target, int M, int N, int K, int dtype) {
     if (!logprob || !top_id || !x || !ln_g || !ln_b || !emb || !target || M <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
-    if (K != 128 && K != 384 && K != 512 && K != 768) return fail(WM_E_ARG, "K must be 128, 384, 512 or 768 (the logits kernels' d_model)");
+    if (K != 128 && K != 384 && K != 512 && K != 768 && K != 1024) return fail(WM_E_ARG, "K must be 128, 384, 512, 768 or 1024 (the logits kernels' d_model)");
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
     for (int r = 0; r < M; ++r)
         if (target[r] >= N) return fail(WM_E_ARG, "target[%d] = %d is not a vocabulary id", r, target[r]);
@@ -4819,10 +4823,14 @@ static int op_attention_cached(float* out, const float* q, const float* k, const
 static int op_dec_linear(float* out, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
                          const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
                          float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
-                         const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel, const int32_t* cap_map = nullptr, int cap_dst = 0) {
+                         const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel, const int32_t* cap_map = nullptr, int cap_dst = 0,
+                         bool k_long = false) {
     if (!out || !x || !W || B <= 0 || N <= 0 || K <= 0) return fail(WM_E_ARG, "bad argument");
     if (dtype < 0 || dtype > 2 || (gelu_mode != 0 && gelu_mode != 1)) return fail(WM_E_ARG, "bad dtype / gelu_mode");
-    if (!dec_linear_supports_k(K)) return fail(WM_E_ARG, "K must be a multiple of 32 whose k-steps split over <= 16 waves x <= 4 steps (K <= 2048), or 3072");
+    if (k_long) {  // wm_op_dec_linear_long: the K-long form alone (16 waves walking groups of k-steps), which has no LayerNorm prologue
+        if (!dec_linear_long_supports_k(K)) return fail(WM_E_ARG, "K must be 3072 or 4096 (the K-long form of the skinny linear)");
+        if (ln_g || ln_b) return fail(WM_E_ARG, "the K-long form has no LayerNorm prologue");
+    } else if (!dec_linear_supports_k(K)) return fail(WM_E_ARG, "K must be a multiple of 32 whose k-steps split over <= 16 waves x <= 4 steps (K <= 2048), or 3072");
     if (!ln_g != !ln_b) return fail(WM_E_ARG, "ln_g and ln_b go together");
     if (ln_g && x_is_t) return fail(WM_E_ARG, "the LayerNorm prologue reads fp32 rows (no x_is_t)");
     if (!kcache != !vcache) return fail(WM_E_ARG, "kcache and vcache go together");
@@ -4936,6 +4944,15 @@ extern "C" int wm_op_dec_linear(float* out, const float* x, const float* W, cons
     return op_dec_linear(out, x, W, bias, ln_g, ln_b, residual, B, N, K, dtype, x_is_t, out_is_t, act, gelu_mode, kcache, vcache, n_utt, cap_rows,
                          kv_dtype, kv_B, len, cap, cap_sel, cap_step0, cap_steps, cap_nsel);
 }
+// The K-long form of the same launch (fc2 of d_model 768 / 1024): K = 3072 or 4096, no LayerNorm prologue.  wm_op_dec_linear keeps
+// refusing K = 4096; K = 3072 runs the same kernel through either hook.
+extern "C" int wm_op_dec_linear_long(float* out, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
+                                     const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
+                                     float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
+                                     const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel) {
+    return op_dec_linear(out, x, W, bias, ln_g, ln_b, residual, B, N, K, dtype, x_is_t, out_is_t, act, gelu_mode, kcache, vcache, n_utt, cap_rows,
+                         kv_dtype, kv_B, len, cap, cap_sel, cap_step0, cap_steps, cap_nsel, nullptr, 0, true);
+}
 // LNx -> cross q as an align pass wires it: B input rows, cap [cap_dst][cap_nsel][64] in and out, cap_map [B] in [-1, cap_dst)
 extern "C" int wm_op_dec_linear_capmap(float* out, float* cap, const float* x, const float* W, const float* bias, const float* ln_g,
                                        const float* ln_b, int B, int N, int K, int dtype, const int8_t* cap_sel, int cap_nsel,
@@ -4951,7 +4968,7 @@ extern "C" int wm_op_dec_linear_capmap(float* out, float* cap, const float* x, c
 static int op_logits(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                      const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
     if (!logits || !ids || !x || !ln_g || !ln_b || !emb || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
-    if (K != 128 && K != 384 && K != 512 && K != 768) return fail(WM_E_ARG, "K must be 128, 384, 512 or 768 (the logits kernels' d_model)");
+    if (K != 128 && K != 384 && K != 512 && K != 768 && K != 1024) return fail(WM_E_ARG, "K must be 128, 384, 512, 768 or 1024 (the logits kernels' d_model)");
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
     if (ranges && (timestamp_begin <= 0 || timestamp_begin >= N)) return fail(WM_E_ARG, "ranges need 0 < timestamp_begin < N");
     TmpDev t;
@@ -5054,7 +5071,7 @@ extern "C" int wm_op_logits_lp(float* logits, int32_t* ids, float* logprob, cons
 extern "C" int wm_op_no_speech(float* prob, float* lse, const float* x, const float* ln_g, const float* ln_b, const float* emb, int B, int N, int K,
                                int dtype, int token) {
     if (!prob || !lse || !x || !ln_g || !ln_b || !emb || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
-    if (K != 128 && K != 384 && K != 512 && K != 768) return fail(WM_E_ARG, "K must be 128, 384, 512 or 768 (the logits kernels' d_model)");
+    if (K != 128 && K != 384 && K != 512 && K != 768 && K != 1024) return fail(WM_E_ARG, "K must be 128, 384, 512, 768 or 1024 (the logits kernels' d_model)");
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
     if (token < 0 || token >= N) return fail(WM_E_ARG, "token %d is not a vocabulary id", token);
     TmpDev t;
@@ -5080,7 +5097,7 @@ extern "C" int wm_op_no_speech(float* prob, float* lse, const float* x, const fl
 extern "C" int wm_op_lang_detect(int32_t* lang_out, float* probs, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                                  const int32_t* lang_ids, int n_lang, int B, int N, int K, int dtype) {
     if (!lang_out || !x || !ln_g || !ln_b || !emb || !lang_ids || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
-    if (K != 128 && K != 384 && K != 512 && K != 768) return fail(WM_E_ARG, "K must be 128, 384, 512 or 768 (the logits kernels' d_model)");
+    if (K != 128 && K != 384 && K != 512 && K != 768 && K != 1024) return fail(WM_E_ARG, "K must be 128, 384, 512, 768 or 1024 (the logits kernels' d_model)");
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
     WMCHK(lang_list_check(N, lang_ids, n_lang));
     TmpDev t;

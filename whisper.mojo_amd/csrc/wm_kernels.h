@@ -185,7 +185,9 @@ struct DecLinearParams {
     const int* cap_map;
 };
 template <typename TW> int launch_dec_linear(const DecLinearParams& p, hipStream_t st);  // WM_LAUNCH_*
-bool dec_linear_supports_k(int K);  // K/32 k-steps must split into NW <= 16 waves x KPW <= 4 steps (checked at model load)
+bool dec_linear_supports_k(int K);  // K/32 k-steps must split into NW <= 16 waves x KPW <= 4 steps, or K = 3072 (the op hooks' answer)
+bool dec_linear_long_supports_k(int K);   // K = 3072 or 4096: the K-long form (wm_op_dec_linear_long)
+bool dec_linear_model_supports_k(int K);  // either of the two (checked at model load)
 template <typename TW> int launch_dec_logits(const DecLinearParams& p, hipStream_t st);  // WM_LAUNCH_*
 int dec_logits_parts(int N);  // fused-argmax partials per utterance that launch_dec_logits writes (amax_stride must cover them)
 int dec_logits_ids_per_part(int N);  // vocabulary ids one part covers

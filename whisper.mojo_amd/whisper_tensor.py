@@ -118,7 +118,7 @@ def attention_cached(out: np.ndarray, q, k, v, n_heads: int, kv_dtype=DT_F32, n_
 
 def dec_linear(x, W, bias=None, ln=None, residual=None, in_place: bool = False, dtype=DT_F32, x_is_t: bool = False, out_is_t: bool = False,
                act: bool = False, gelu_mode: int = GELU_TANH, kv=None, kv_dtype=DT_F32, kv_B: int = 0, len: int = 0, cap=None,
-               cap_sel=None, cap_step0: int = 0):
+               cap_sel=None, cap_step0: int = 0, _hook: str = "wm_op_dec_linear"):
     """One launch of the decode step's skinny linear (wm_op_dec_linear): epi(pro(x)·Wᵀ + bias) -> out [B, N] fp32.
     ln = (gamma, beta): LayerNorm prologue; x_is_t: x goes up in operand dtype; act: GELU; residual [B, N] is added (in_place: through
     the aliasing form, out = residual buffer); out_is_t: the kernel stores operand dtype.  kv = (kcache, vcache) [n_utt, cap_rows, d]
@@ -160,15 +160,21 @@ def dec_linear(x, W, bias=None, ln=None, residual=None, in_place: bool = False, 
     if residual is not None and in_place:
         out[:] = residual
         res = out
-    _lib.check(_lib.lib().wm_op_dec_linear(_fp(out), _fp(x), _fp(W), _fp(bias), _fp(g), _fp(b), _fp(res), B, N, K, dtype, int(x_is_t),
-                                           int(out_is_t), int(act), gelu_mode, _fp(kc), _fp(vc), n_utt, cap_rows, kv_dtype, kv_B, len,
-                                           _fp(cp), None if sel is None else sel.ctypes.data_as(C.POINTER(C.c_int8)), cap_step0, steps,
-                                           nsel))
+    _lib.check(getattr(_lib.lib(), _hook)(_fp(out), _fp(x), _fp(W), _fp(bias), _fp(g), _fp(b), _fp(res), B, N, K, dtype, int(x_is_t),
+                                          int(out_is_t), int(act), gelu_mode, _fp(kc), _fp(vc), n_utt, cap_rows, kv_dtype, kv_B, len,
+                                          _fp(cp), None if sel is None else sel.ctypes.data_as(C.POINTER(C.c_int8)), cap_step0, steps,
+                                          nsel))
     if kv is not None:
         return out, kc, vc
     if cap is not None:
         return out, cp
     return out
+
+
+def dec_linear_long(x, W, bias=None, **kw):
+    """dec_linear on the K-long form of the kernel (wm_op_dec_linear_long): 16 waves walking groups of k-steps, K = 3072 or 4096 (fc2
+    of d_model 768 / 1024), no LayerNorm prologue.  Arguments and results as dec_linear's."""
+    return dec_linear(x, W, bias, _hook="wm_op_dec_linear_long", **kw)
 
 
 def layer_norm(out: np.ndarray, inp, gamma, beta, eps: float = 1e-5):
@@ -300,8 +306,8 @@ def lang_detect(x, ln_g, ln_b, emb, lang_ids, dtype=DT_F32):
     g, b = f(ln_g).ravel(), f(ln_b).ravel()
     if x.ndim != 2 or emb.ndim != 2 or emb.shape[1] != x.shape[1] or g.size != x.shape[1] or b.size != x.shape[1]:
         raise ValueError("x must be [B, K], emb [N, K], ln_g / ln_b [K]")
-    if x.shape[1] not in (128, 384, 512, 768):
-        raise ValueError("K must be 128, 384, 512 or 768")
+    if x.shape[1] not in (128, 384, 512, 768, 1024):
+        raise ValueError("K must be 128, 384, 512, 768 or 1024")
     ids = _lib.lang_args(lang_ids, emb.shape[0])
     B, K = x.shape
     out, probs = np.zeros(B, np.int32), np.zeros((B, ids.size), np.float32)
