@@ -48,11 +48,9 @@ def _ln64(x, g, b):
     return (x - mean) / np.sqrt(var + 1e-5) * g.astype(np.float64) + b.astype(np.float64)
 
 
-def _ln_err(x, g, b, n=None):
-    """First-order bound on |fp32 LayerNorm - float64 LayerNorm| per element, for the logits kernels' fp32 LayerNorm: each of 8
-    threads per row sums K/8 elements (and their squares) in sequence, three butterfly adds join them (γ_n, n = K/8 + 3); then
-    mean = s/K, var = q/K - mean², rstd = 1/sqrtf(var + eps), y = ((x - mean)·rstd)·g + b, every operation rounded once.
-    n: the summation depth of another kernel's statistics (default: the logits kernels')."""
+def _ln_stats(x, n=None):
+    """The row statistics of _ln_err and their fp32 error: (x float64, mean, var, Δmean, Δvar), each [rows, 1], for statistics summed
+    n deep (default: the logits kernels' K/8 + 3).  tests/test_fused_ln_ref.py builds its interval bound from the same terms."""
     x = x.astype(np.float64)
     K = x.shape[1]
     gam = (K // 8 + 3 if n is None else n) * U
@@ -62,6 +60,15 @@ def _ln_err(x, g, b, n=None):
     d_mu = gam * np.abs(x).mean(1, keepdims=True) + U * np.abs(mu)
     d_m2 = (gam + 2 * U) * m2
     d_var = d_m2 + 2 * np.abs(mu) * d_mu + U * mu * mu + U * (np.abs(var) + 1e-5)
+    return x, mu, var, d_mu, d_var
+
+
+def _ln_err(x, g, b, n=None):
+    """First-order bound on |fp32 LayerNorm - float64 LayerNorm| per element, for the logits kernels' fp32 LayerNorm: each of 8
+    threads per row sums K/8 elements (and their squares) in sequence, three butterfly adds join them (γ_n, n = K/8 + 3); then
+    mean = s/K, var = q/K - mean², rstd = 1/sqrtf(var + eps), y = ((x - mean)·rstd)·g + b, every operation rounded once.
+    n: the summation depth of another kernel's statistics (default: the logits kernels')."""
+    x, mu, var, d_mu, d_var = _ln_stats(x, n)
     r = 1.0 / np.sqrt(var + 1e-5)
     rho = 0.5 * d_var / (var + 1e-5) + 2 * U
     y = (x - mu) * r * g + b

@@ -75,7 +75,11 @@ def _data(dt, K, B, N, n_lang, seed):
 
 def _ref(x, g, b, emb, ids, dt):
     """-> (log p float64 [B, n], bound [B, n], float64 arg-max ids [B], top-2 gap [B], e [B])"""
-    ref, bound = _logits_ref(x, g, b, emb[ids], dt)
+    return _ref_from(*_logits_ref(x, g, b, emb[ids], dt), ids)
+
+
+def _ref_from(ref, bound, ids):
+    """the same from the candidates' float64 logits and their per-logit bound (tests/test_gpu_fused_ln_op.py brings its own)"""
     n = len(ids)
     M = ref.max(1, keepdims=True)
     w = np.exp(ref - M)
@@ -129,8 +133,8 @@ def _run(x, g, b, emb, ids, dt):
     return wt.lang_detect(x, g, b, emb, ids, dtype=dt)
 
 
-def _check(tag, got, probs, x, g, b, emb, ids, dt, need_all=True):
-    lp, bnd, want, gap, e = _ref(x, g, b, emb, ids, dt)
+def _check(tag, got, probs, x, g, b, emb, ids, dt, need_all=True, refs=None):
+    lp, bnd, want, gap, e = _ref(x, g, b, emb, ids, dt) if refs is None else _ref_from(*refs, ids)
     assert np.isfinite(probs).all() and (probs > 0).all() and (probs <= 1).all(), tag
     ratio = np.abs(np.log(probs.astype(np.float64)) - lp) / bnd
     print(f"{tag}: worst err/bound {ratio.max():.3g}, max |err| {np.abs(np.log(probs.astype(np.float64)) - lp).max():.3g}, "

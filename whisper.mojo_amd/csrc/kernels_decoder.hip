@@ -179,7 +179,7 @@ __global__ __launch_bounds__(1024) void dec_linear_kernel(DecLinearParams p) {
         }
         mean = sm / (float)p.K;
         const float var = (sq / (float)p.K) - (mean * mean);
-        rstd = 1.0f / sqrtf(var + 1e-5f);
+        rstd = 1.0f / sqrtf(fmaxf(var, 0.f) + 1e-5f);
     }
     WM_DL_STAMP(2);
 #pragma unroll
@@ -680,7 +680,7 @@ __global__ __launch_bounds__(512) void dec_logits_kernel(DecLinearParams p, int 
                 }
                 const float mean = sm / (float)K;
                 const float var = (sq / (float)K) - (mean * mean);
-                const float rstd = 1.0f / sqrtf(var + 1e-5f);
+                const float rstd = 1.0f / sqrtf(fmaxf(var, 0.f) + 1e-5f);
 #pragma unroll
                 for (int i = 0; i < KD * 4; ++i) {
                     const int k = 4 * (q + 8 * i);
@@ -896,7 +896,7 @@ __global__ __launch_bounds__(512) void dec_logits_split_kernel(DecLinearParams p
                 }
                 const float mean = sm / (float)K;
                 const float var = (sq / (float)K) - (mean * mean);
-                const float rstd = 1.0f / sqrtf(var + 1e-5f);
+                const float rstd = 1.0f / sqrtf(fmaxf(var, 0.f) + 1e-5f);
 #pragma unroll
                 for (int i = 0; i < KD * 4; ++i) {
                     const int k = 4 * (q + 8 * i);
@@ -1108,7 +1108,7 @@ __global__ __launch_bounds__(512) void dec_logits_split128_kernel(DecLinearParam
         const float sm = sa + sb, sq = qa + qb;  // its last level
         mean = sm / (float)K;
         const float var = (sq / (float)K) - (mean * mean);
-        rstd = 1.0f / sqrtf(var + 1e-5f);
+        rstd = 1.0f / sqrtf(fmaxf(var, 0.f) + 1e-5f);
         stage(v0, 0);
     }
     WM_LG_STAMP(1);
@@ -2356,7 +2356,7 @@ __global__ __launch_bounds__(256) void no_speech_finish_kernel(NoSpeechParams p)
         sq = wave_sum(sq);
         const float mean = sm / (float)p.K;
         const float var = (sq / (float)p.K) - (mean * mean);
-        const float rstd = 1.0f / sqrtf(var + 1e-5f);
+        const float rstd = 1.0f / sqrtf(fmaxf(var, 0.f) + 1e-5f);
         const TW* er = (const TW*)p.emb + (size_t)p.token * p.K;
         float acc = 0.f;
         for (int k = lane; k < p.K; k += 64) {
@@ -2424,7 +2424,7 @@ __global__ __launch_bounds__(256) void lang_detect_kernel(LangDetectParams p) {
     sq = wave_sum(sq);
     const float mean = sm / (float)p.K;
     const float var = (sq / (float)p.K) - (mean * mean);
-    const float rstd = 1.0f / sqrtf(var + 1e-5f);
+    const float rstd = 1.0f / sqrtf(fmaxf(var, 0.f) + 1e-5f);
     for (int k = tid; k < p.K; k += 256) s_a[k] = (float)from_f32<TW>((xr[k] - mean) * rstd * p.ln_g[k] + p.ln_b[k]);
     __syncthreads();
     for (int c = w; c < p.n_lang; c += 4) {

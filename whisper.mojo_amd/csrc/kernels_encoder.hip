@@ -379,7 +379,7 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_nt_rowpanel_kernel(GemmParams
                     sq += __shfl_xor(sq, 32, 64);
                     const float mean = sm / (float)(KS * 32);
                     const float var = (sq / (float)(KS * 32)) - (mean * mean);
-                    const float inv_std = 1.0f / sqrtf(var + 1e-5f);
+                    const float inv_std = 1.0f / sqrtf(fmaxf(var, 0.f) + 1e-5f);
 #pragma unroll
                     for (int k = 0; k < KS; ++k) {
                         float y[8];
@@ -852,7 +852,7 @@ __global__ __launch_bounds__(512) void gemm_nt_fullrow_kernel(GemmParams p) {
             const float s1 = (s01[0] + s01[2]) + (s23[0] + s23[2]), s2 = (s01[1] + s01[3]) + (s23[1] + s23[3]);
             const float mean = s1 / 384.0f;
             const float var = (s2 / 384.0f) - (mean * mean);
-            const float inv_std = 1.0f / sqrtf(var + 1e-5f);
+            const float inv_std = 1.0f / sqrtf(fmaxf(var, 0.f) + 1e-5f);
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
                 const f32x4 v = acc[j][i];

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void score_ln_kernel(const float* __restrict__
     }
     const float mean = sm / (float)K;
     const float var = (sq / (float)K) - (mean * mean);
-    const float rstd = 1.0f / sqrtf(var + 1e-5f);
+    const float rstd = 1.0f / sqrtf(fmaxf(var, 0.f) + 1e-5f);
     if (row >= M) return;
 #pragma unroll
     for (int i = 0; i < KD * 4; ++i) {
