@@ -402,7 +402,8 @@ typedef struct {
  * NULL or host [B][n_mels][F]; n_frames_out: NULL or [B], min(ceil(n_samples[b] / 160), F) (the ones of HF's attention mask).
  * The device copies of the PCM and the mel are released before the call returns. */
 int wm_log_mel_long(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, float* mel_out, int32_t* n_frames_out);
-/* mel: [B][n_mels][T] fp32, host or (mel_on_device) device; n_frames[b] frames of real audio in row b (NULL = T). */
+/* mel: [B][n_mels][T] fp32, host or (mel_on_device) device; n_frames[b] frames of real audio in row b (NULL = T).
+ * Word-level times on top of the segments: wm_transcribe_long_tt below. */
 int wm_transcribe_long(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames, const wm_decode_opts* opts,
                        wm_long_result** out);
 /* wm_log_mel_long + wm_transcribe_long without the mel leaving the GPU */
@@ -450,6 +451,24 @@ int wm_transcribe_long_lang(wm_model* m, const float* mel, int mel_on_device, in
                             const wm_long_opts* lopts, const int32_t* lang_ids, int n_lang, int32_t* lang_out, wm_long_result** out);
 int wm_transcribe_long_pcm_lang(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* opts,
                                 const wm_long_opts* lopts, const int32_t* lang_ids, int n_lang, int32_t* lang_out, wm_long_result** out);
+/* Long-form with token timestamps: the arguments of the _lang pair plus a flag; lang_ids NULL = no language detection
+ * (lang_out is then not written).  token_timestamps != 0: every window pass also carries the alignment-head capture and the chain of
+ * wm_transcribe_tt, with num_input_ids = the row's own decoder prompt length (previous text and prompt_ids included) and num_frames =
+ * the window's real frames; an id's time is its window-relative fp32 time plus the window's time_offset, summed in float64.
+ * wm_long_result_token_times then serves one time per id of the utterance's sequence.  One encoder run per window; no align pass.
+ * WM_E_STATE: no alignment heads set.  WM_E_ARG: thresholds set in wm_long_opts together with the flag (log-probabilities and token
+ * timestamps do not share a pass, as in wm_transcribe_lp; out of scope here).  token_timestamps = 0: exactly the _lang / _ex pair. */
+int wm_transcribe_long_tt(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames, const wm_decode_opts* opts,
+                          const wm_long_opts* lopts, const int32_t* lang_ids, int n_lang, int32_t* lang_out, int token_timestamps,
+                          wm_long_result** out);
+int wm_transcribe_long_pcm_tt(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* opts,
+                              const wm_long_opts* lopts, const int32_t* lang_ids, int n_lang, int32_t* lang_out, int token_timestamps,
+                              wm_long_result** out);
+/* times: [n_tokens] seconds, parallel to wm_long_result_get's tokens (may be NULL when 0).  WM_E_STATE for a run without the flag. */
+int wm_long_result_token_times(const wm_long_result* r, int b, double* times);
+/* Host-only: one window's share of that array.  rel: the window-relative fp32 times of its n generated ids (eot already dropped),
+ * segs: wm_op_long_segments' segments of those ids; times: room for n entries, one per id a segment keeps. */
+int wm_op_long_token_times(const float* rel, int n, int64_t seek, const wm_segment* segs, int n_segs, double* times, int32_t* n_times);
 /* Host-only, the counterpart of wm_op_long_segments: the decoder prompt of ONE utterance's next window.  seq / segs: the utterance's
  * segments so far (first, count into seq; n_segs may be 0); init: opts->prompt.  out: room for n_text_ctx ids. */
 int wm_op_long_prompt(const int32_t* seq, const wm_segment* segs, int n_segs, const int32_t* init, int n_init, const wm_long_opts* lopts,

@@ -340,6 +340,7 @@ public:
         double start, end;
         std::vector<int> tokens;
         float avg_logprob = 0.f, no_speech_prob = 0.f;  // the segment's window values; filled with LongThresholds only
+        std::vector<double> token_timestamps{};         // seconds, one per id of `tokens`; filled with token_timestamps only
     };
     struct LongWindow {  // one decoded window of an utterance, skipped ones included (LongThresholds only)
         int64_t seek;
@@ -350,6 +351,7 @@ public:
         std::vector<int> sequence;
         std::vector<LongSegment> segments;
         std::vector<LongWindow> windows;
+        std::vector<double> token_times;  // seconds, one per id of `sequence`; filled with token_timestamps only
     };
     // HF generate's logprob_threshold / no_speech_threshold at temperature 0: a window with avg_logprob < logprob_threshold
     // and no_speech_prob > no_speech_threshold is skipped.  no_speech_threshold needs logprob_threshold and the <|nospeech|> id.
@@ -361,11 +363,13 @@ public:
         int32_t no_speech_token = -1;
     };
     // condition_on_prev_tokens / prompt_ids (as WhisperProcessor.get_prompt_ids returns them) / all_segments: HF generate's options of
-    // the same names; the defaults are wm_transcribe_long
+    // the same names; the defaults are wm_transcribe_long.  token_timestamps (needs set_alignment_heads, not
+    // with thresholds): the time of every id, per utterance and per segment
     std::vector<LongResult> transcribe_long(const float* mels, int B, int T, const std::vector<int32_t>& n_frames = {}, int max_loop = MAX_LOOP,
                                             bool condition_on_prev_tokens = false, const std::vector<int32_t>& prompt_ids = {},
                                             bool all_segments = false, int32_t prev_sot_token = 50361, const LongThresholds* thresholds = nullptr,
-                                            const std::vector<int32_t>& lang_ids = {}, std::vector<int32_t>* lang_out = nullptr) const {
+                                            const std::vector<int32_t>& lang_ids = {}, std::vector<int32_t>* lang_out = nullptr,
+                                            bool token_timestamps = false) const {
         need_model();
         wm_decode_opts o = opts(max_loop, false);
         wm_long_result* r = nullptr;
@@ -375,7 +379,12 @@ public:
                               (int)prompt_ids.size(), all_segments ? 1 : 0, th.use_logprob_threshold ? 1 : 0, th.logprob_threshold,
                               th.use_no_speech_threshold ? 1 : 0, th.no_speech_threshold, th.no_speech_token};
         const bool quality = th.use_logprob_threshold || th.use_no_speech_threshold;
-        if (!lang_ids.empty()) {  // HF generate's language = None: each recording's language, detected on its first window
+        if (token_timestamps) {
+            std::vector<int32_t> lang(B);
+            check(wm_transcribe_long_tt(model_, mels, 0, B, T, n_frames.empty() ? nullptr : n_frames.data(), &o, &lo,
+                                        lang_ids.empty() ? nullptr : lang_ids.data(), (int)lang_ids.size(), lang.data(), 1, &r));
+            if (lang_out && !lang_ids.empty()) *lang_out = lang;
+        } else if (!lang_ids.empty()) {  // HF generate's language = None: each recording's language, detected on its first window
             std::vector<int32_t> lang(B);
             check(wm_transcribe_long_lang(model_, mels, 0, B, T, n_frames.empty() ? nullptr : n_frames.data(), &o, &lo, lang_ids.data(),
                                           (int)lang_ids.size(), lang.data(), &r));
@@ -394,6 +403,13 @@ public:
             out[b].sequence.assign(ids.begin(), ids.end());
             for (const wm_segment& sg : segs)
                 out[b].segments.push_back({sg.start, sg.end, std::vector<int>(ids.begin() + sg.first, ids.begin() + sg.first + sg.count)});
+            if (token_timestamps && !rc) {
+                out[b].token_times.resize(nt);
+                rc = wm_long_result_token_times(r, b, out[b].token_times.data());
+                for (int i = 0; i < ns && !rc; ++i)
+                    out[b].segments[i].token_timestamps.assign(out[b].token_times.begin() + segs[i].first,
+                                                               out[b].token_times.begin() + segs[i].first + segs[i].count);
+            }
             if (quality && !rc) {
                 std::vector<float> qa(ns), qn(ns);
                 rc = wm_long_result_quality(r, b, qa.data(), qn.data());

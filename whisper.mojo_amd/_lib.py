@@ -36,6 +36,7 @@ SYMBOLS = [
     "wm_op_attention_batch", "wm_op_layer_norm_t",
     "wm_op_xattn_absorb",
     "wm_op_dec_linear_long",
+    "wm_transcribe_long_tt", "wm_transcribe_long_pcm_tt", "wm_long_result_token_times", "wm_op_long_token_times",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -267,6 +268,12 @@ def lib():
                                           C.POINTER(vp)]
     L.wm_transcribe_long_pcm_lang.argtypes = [vp, fp, ip, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), C.POINTER(WmLongOpts), ip, C.c_int, ip,
                                               C.POINTER(vp)]
+    L.wm_transcribe_long_tt.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, C.POINTER(WmDecodeOpts), C.POINTER(WmLongOpts), ip, C.c_int, ip,
+                                        C.c_int, C.POINTER(vp)]
+    L.wm_transcribe_long_pcm_tt.argtypes = [vp, fp, ip, C.c_int, C.c_int, C.POINTER(WmDecodeOpts), C.POINTER(WmLongOpts), ip, C.c_int, ip,
+                                            C.c_int, C.POINTER(vp)]
+    L.wm_long_result_token_times.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
+    L.wm_op_long_token_times.argtypes = [fp, C.c_int, C.c_int64, C.POINTER(WmSegment), C.c_int, C.POINTER(C.c_double), ip]
     L.wm_op_lang_detect.argtypes = [ip, fp, fp, fp, fp, fp, ip] + [C.c_int] * 5
     L.wm_score.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip, fp, ip, fp, fp]
     L.wm_score_submit.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip]
@@ -298,14 +305,38 @@ def lib():
     return L
 
 
-def long_result(h, B: int, quality: bool = False):
+def long_tt_args(return_token_timestamps, logprob_threshold, no_speech_threshold):
+    """Checks the long-form token-timestamp flag on the host (the library refuses the same with WM_E_ARG) -> bool."""
+    tt = bool(return_token_timestamps)
+    if tt and (logprob_threshold is not None or no_speech_threshold is not None):
+        raise ValueError("return_token_timestamps does not combine with logprob_threshold / no_speech_threshold")
+    return tt
+
+
+def long_token_times(rel, seek: int, segs):
+    """wm_op_long_token_times (host only): rel = the window-relative float32 times of a window's generated ids (eot
+    dropped), segs = long_segments' (first, count, start, end) of those ids -> float64 array, one time per id a segment keeps."""
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(rel, np.float32).reshape(-1))
+    sg = (WmSegment * max(1, len(segs)))(*[WmSegment(int(s[0]), int(s[1]), float(s[2]), float(s[3])) for s in segs])
+    out = np.zeros(max(1, a.size), np.float64)
+    n = C.c_int32()
+    check(lib().wm_op_long_token_times(a.ctypes.data_as(C.POINTER(C.c_float)) if a.size else None, a.size, int(seek), sg, len(segs),
+                                       out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
+    return out[:n.value].copy()
+
+
+def long_result(h, B: int, quality: bool = False, token_times: bool = False):
     """Reads and frees a wm_long_result handle of B utterances -> (per utterance {"sequence": [...], "segments": [{"start",
     "end", "tokens"}]}, {"windows", "stalled", "passes", "rows"}: windows decoded, windows that did not advance seek, passes
     run and rows those passes decoded; "longest_prompt", "row_passes": the longest decoder prompt a pass carried and how many
     passes went out as per-row passes).
     quality (a run with thresholds): every segment also carries its window's "avg_logprob" / "no_speech_prob", every
     utterance its window log "windows": [{"seek", "avg_logprob", "no_speech_prob", "skipped"}] in decode order, and the stats
-    "skipped_windows"."""
+    "skipped_windows".
+    token_times (a run with token timestamps): every utterance also carries "token_times", a float64 array parallel to
+    "sequence", and every segment "token_timestamps", its slice of that array."""
+    import numpy as np
     L = lib()
     try:
         out = []
@@ -318,6 +349,12 @@ def long_result(h, B: int, quality: bool = False):
             seq = list(toks[:n_tok.value])
             out.append({"sequence": seq, "segments": [{"start": s.start, "end": s.end, "tokens": seq[s.first:s.first + s.count]}
                                                       for s in segs[:n_seg.value]]})
+            if token_times:
+                tt = np.zeros(max(1, n_tok.value), np.float64)
+                check(L.wm_long_result_token_times(h, b, tt.ctypes.data_as(C.POINTER(C.c_double))))
+                out[-1]["token_times"] = tt[:n_tok.value]
+                for sg, s in zip(out[-1]["segments"], segs[:n_seg.value]):
+                    sg["token_timestamps"] = out[-1]["token_times"][s.first:s.first + s.count]
             if quality:
                 qa, qn = (C.c_float * max(1, n_seg.value))(), (C.c_float * max(1, n_seg.value))()
                 check(L.wm_long_result_quality(h, b, qa, qn))

@@ -5,6 +5,7 @@
 //   align_norm : per column j < F_b: z = (w - mean_r) / std_r (population std, over the R_b rows), width-7 median along the columns
 //                (reflect padding; skipped for F_b <= 3), mean over the heads                  -> M [B][L][T]
 //   align_dtw  : DTW over -M (one workgroup per utterance, anti-diagonal sweep, 2-bit trace), backtrace, jump times -> times
+//   align_window: a long-form window pass: the chain's ragged tables before it, the window's float64 times behind it
 //
 // Rows of an utterance: R_b = n_tokens[b] - n_prompt - 1 (the ids that were fed back; the last id has no row).  Nothing here reads
 // anything the host computed after the loop: n_tokens stays on the device.  Forced alignment gives every utterance its
@@ -317,6 +318,40 @@ __global__ __launch_bounds__(512) void align_dtw_kernel(AlignParams p) {
         }
         times[t] = v;
     }
+}
+
+// A long-form window pass: mode 0 makes the chain's ragged tables from the counts the loop left on the device, mode 1
+// turns the chain's [row][out_stride] times into each row's generated-id times at the window's offset.  The prompt length is clamped
+// to [0, n_prompt] and the launcher requires out_stride >= n_prompt + L + 1, so no table value can move an access out of its row.
+// grid (B), 256 threads
+__global__ __launch_bounds__(256) void align_window_kernel(AlignWindowParams p) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x;
+    int len = p.prompt_len ? p.prompt_len[r] : p.n_prompt;
+    len = len < 0 ? 0 : (len > p.n_prompt ? p.n_prompt : len);
+    int gen = p.n_tokens[r] - len;  // generated ids, the trailing eot included
+    gen = gen < 0 ? 0 : (gen > p.L + 1 ? p.L + 1 : gen);
+    if (p.mode == 0) {
+        if (threadIdx.x == 0) {
+            p.rows[r] = r < p.n_real && gen > 1 ? gen - 1 : 0;
+            p.row0[r] = len;
+        }
+        return;
+    }
+    const bool real = r < p.n_real;  // (a row without align rows has zeros from the chain: its one id, if any, sits at the offset)
+    const double off = (double)p.items[(size_t)r * 3 + 1] * 0.02 / 2;  // time_offset, as long_segments forms it
+    const float* t = p.times + (size_t)r * p.out_stride + len;
+    double* o = p.out + (size_t)r * (p.L + 1);
+    for (int i = threadIdx.x; i <= p.L; i += blockDim.x) o[i] = real && i < gen ? (double)t[i] + off : 0.0;
+}
+
+int launch_align_window(const AlignWindowParams& p, hipStream_t st) {
+    if (p.B <= 0 || p.n_real < 0 || p.n_real > p.B || p.L < 1 - p.mode || p.L > ALIGN_MAX_ROWS || p.n_prompt < 1 || p.out_stride < p.n_prompt + p.L + 1 ||
+        (p.mode != 0 && p.mode != 1))
+        return launch_refuse("align_window: bad shape");
+    if (!p.n_tokens || !p.items || !p.rows || !p.row0 || (p.mode == 1 && (!p.times || !p.out))) return launch_refuse("align_window: null table");
+    hipLaunchKernelGGL(align_window_kernel, dim3(p.B), dim3(256), 0, st, p);
+    return WM_LAUNCH_OK;
 }
 
 int launch_align_probs(const AlignParams& p, hipStream_t st) {

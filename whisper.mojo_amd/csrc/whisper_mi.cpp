@@ -211,6 +211,10 @@ struct ScoreAsk {  // a score pass, already validated by score_che
     const std::vector<int32_t>* cols = nullptr;
     bool lp = true;
 };
+struct WinAsk {  // the windows a long-form timestamp pass decodes
+    const int32_t* items;  // device [B][3]: (utterance, seek, frames) per row
+    int n_real;            // rows [n_real, B) repeat row 0: no align rows, zero times
+};
 // One pass: encoder, prefill, greedy loop (or the teacher-forced pass of `score`) for B utterances.  The entry points validate, fill
 // one of these and hand it to a driver (run_now / submit_slot); nothing in it is owned, it lives on the caller's stack.
 struct PassAsk {
@@ -226,6 +230,7 @@ struct PassAsk {
     NsAsk ns;
     LangAsk lang;
     const ScoreAsk* score = nullptr;
+    const WinAsk* win = nullptr;  // with cols: a long-form window pass whose times are finished on the device
 };
 static PassAsk lang_only_ask(const float* mel, int mel_on_device, int B, const int32_t* lang_ids, int n_lang, int sot) {
     PassAsk ask{mel, mel_on_device, B};
@@ -244,6 +249,7 @@ struct PassOut {  // where a pass's results go: the caller's buffers, null = not
     int rows_cap = 0, pack_stride = 0;
     int32_t* top_ids = nullptr;  // score / align passes
     float* sum_logprob = nullptr;
+    double* win_times = nullptr;  // a window pass (PassAsk::win): [B][max_loop + 1] times of the generated ids, offset included
 };
 enum class PassKind { transcribe, score, align };  // which wait family collects a slot's pass
 
@@ -419,6 +425,12 @@ struct wm_state {
         int stride = 0;
         std::vector<int32_t> h_rows, h_row0, h_map;
         DevBuf rows, row0, map;
+        // a long-form window pass (win = the pending pass is one): rows / row0 are made on the device from n_tokens and the
+        // prompt lengths, wtimes [B][L + 1] float64 is what the pass hands back.  wtimes is allocated by the first such pass.
+        bool win = false;
+        int n_real = 0;
+        const int32_t* items = nullptr;
+        DevBuf wtimes;
     } al;
     // per-row prompts of the pending pass (on = wm_transcribe_rows and its kin).  Buffers are allocated by the first such
     // pass: table [B][n_text_ctx] ids, len [B], key_lo [B] (first cache row of each utterance's own keys).
@@ -2192,7 +2204,7 @@ static int check_opts(wm_model* m, const wm_decode_opts* o, int B) {
     return 0;
 }
 
-static int align_setup(wm_model* m, wm_state* s, const wm_decode_opts* o, const std::vector<int32_t>* cols);
+static int align_setup(wm_model* m, wm_state* s, const wm_decode_opts* o, const std::vector<int32_t>* cols, const WinAsk* win);
 static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a);
 static int rows_setup(wm_model* m, wm_state* s, const RowPrompts* rows) {
     wm_state::Rows& rw = s->rw;
@@ -2235,6 +2247,8 @@ static int submit_on(wm_model* m, wm_state** slot, const PassAsk& ask) {
         return fail(WM_E_ARG, "the no-speech probe needs a log-prob pass, a vocabulary id and 1 <= n_init <= prompt length");
     if (lp && (cols || dec_lanes_for(B) != 1))  // (the entry points refuse both before anything is touched; kept for internal callers)
         return fail(WM_E_ARG, "log-probabilities need a single-lane decode state and a pass without token timestamps");
+    if ((ask.win && (!cols || ask.mel2)) || (rows && cols && !ask.win))  // (no entry point asks for either)
+        return fail(WM_E_ARG, "per-row prompts take token timestamps in a long-form window pass only, and a window pass runs alone");
     HIPCHK(hipSetDevice(m->device));
     const bool pair = ask.mel2 != nullptr;
     // a pass that was submitted and not yet waited for owns the slot's state: refuse BEFORE touching it (re-creating the
@@ -2334,7 +2348,7 @@ static int submit_on(wm_model* m, wm_state** slot, const PassAsk& ask) {
         return 0;
     }
     s->al.ragged = false;
-    WMCHK(align_setup(m, s, o, cols));
+    WMCHK(align_setup(m, s, o, cols, ask.win));
     WMCHK(transcribe_decode(m, s, o, ask.allow_poll));
     s->pending = true;
     s->synced = false;
@@ -2373,6 +2387,8 @@ static int wait_on(wm_model* m, wm_state* s, int row0, int rows, const PassOut& 
         HIPCHK(hipMemcpy2D(out.tokens, (size_t)total * 4, s->out_tokens.as<int>() + (size_t)row0 * s->out_stride, (size_t)s->out_stride * 4, (size_t)total * 4, rows,
                            hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(out.n_tokens, s->n_tokens.as<int>() + row0, (size_t)rows * 4, hipMemcpyDeviceToHost));
+        if (out.win_times)  // (the caller's pass was a window pass)
+            HIPCHK(hipMemcpy(out.win_times, (const double*)s->al.wtimes.p + (size_t)row0 * (s->al.L + 1), (size_t)rows * (s->al.L + 1) * 8, hipMemcpyDeviceToHost));
         if (out.token_times)
             HIPCHK(hipMemcpy2D(out.token_times, (size_t)total * 4, s->al.times.as<float>() + (size_t)row0 * s->out_stride, (size_t)s->out_stride * 4,
                                (size_t)total * 4, rows, hipMemcpyDeviceToHost));
@@ -2886,10 +2902,18 @@ static int align_buffers(wm_model* m, wm_state* s, size_t Lr, size_t times_strid
     return 0;
 }
 // Before the pass's graphs are (re)captured: size the timestamp buffers of state s and record what the pass asked for.
-static int align_setup(wm_model* m, wm_state* s, const wm_decode_opts* o, const std::vector<int32_t>* cols) {
+static int align_setup(wm_model* m, wm_state* s, const wm_decode_opts* o, const std::vector<int32_t>* cols, const WinAsk* win) {
     wm_state::Align& a = s->al;
     a.on = cols != nullptr;
+    a.win = a.on && win != nullptr;
     if (!a.on) return 0;
+    if (a.win) {  // the tables the window kernel fills, and what it hands back
+        a.items = win->items;
+        a.n_real = win->n_real;
+        WMCHK(grow(a.rows, (size_t)s->B * 4));
+        WMCHK(grow(a.row0, (size_t)s->B * 4));
+        WMCHK(grow(a.wtimes, (size_t)s->B * (o->max_loop + 1) * 8));
+    }
     a.pairs = m->align_pairs;
     a.L = o->max_loop;
     a.n_prompt = o->n_prompt;
@@ -2941,8 +2965,31 @@ static AlignParams align_params(wm_model* m, wm_state* s) {
         p.row0 = a.row0.as<int>();
         p.out_stride = a.stride;
         for (int b = 0; b < s->B; ++b) p.out_need = std::max(p.out_need, a.h_row0[b] + a.h_rows[b] + 1);
+    } else if (a.win) {  // a window pass: the same form, the tables made on the device (row0[b] <= n_prompt, rows[b] <= L)
+        p.n_tokens = nullptr;
+        p.rows = a.rows.as<int>();
+        p.row0 = a.row0.as<int>();
+        p.out_need = a.n_prompt + a.L + 1;
     }
     return p;
+}
+static AlignWindowParams align_window_params(wm_state* s, int mode) {
+    const wm_state::Align& a = s->al;
+    AlignWindowParams w{};
+    w.mode = mode;
+    w.B = s->B;
+    w.n_real = a.n_real;
+    w.L = a.L;
+    w.n_prompt = a.n_prompt;
+    w.out_stride = s->out_stride;
+    w.n_tokens = s->n_tokens.as<int>();
+    w.prompt_len = s->rw.on ? s->rw.len.as<int>() : nullptr;
+    w.items = a.items;
+    w.rows = a.rows.as<int>();
+    w.row0 = a.row0.as<int>();
+    w.times = a.times.as<float>();
+    w.out = (double*)a.wtimes.p;
+    return w;
 }
 
 // the post-loop kernels of a timestamp pass, on lane 0's stream behind the last step
@@ -2950,12 +2997,15 @@ static int enqueue_align(wm_model* m, wm_state* s) {
     hipStream_t st = s->lanes[0].st;
     if (s->al.L == 0) {  // max_loop 0: no row ever, every time is 0 (HF's early return)
         HIPCHK(hipMemsetAsync(s->al.times.p, 0, (size_t)s->B * (s->al.ragged ? s->al.stride : s->out_stride) * 4, st));
+        if (s->al.win) LCHK(launch_align_window(align_window_params(s, 1), st));  // the one id of each window, at its offset
         return 0;
     }
     const AlignParams p = align_params(m, s);
+    if (s->al.win) LCHK(launch_align_window(align_window_params(s, 0), st));  // rows / row0 from the loop's counts
     LCHK(launch_align_probs(p, st));
     LCHK(launch_align_norm(p, st));
     LCHK(launch_align_dtw(p, st));
+    if (s->al.win) LCHK(launch_align_window(align_window_params(s, 1), st));  // the window's result rows
     return 0;
 }
 
@@ -3401,6 +3451,7 @@ static int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
         for (DevBuf* p : {&sc.lp, &sc.top}) WMCHK(grow(*p, (size_t)B * a.stride * 4));
     }
     al.on = al.ragged = align;
+    al.win = false;
     if (align) {  // the buffers of a timestamp pass, sized by the longest row of THIS pass
         al.pairs = m->align_pairs;
         al.L = Lal;
@@ -3685,7 +3736,23 @@ struct wm_long_result {
     int skipped = 0;
     std::vector<std::vector<Window>> wins;
     std::vector<std::vector<float>> seg_avg, seg_nsp;
+    // token timestamps (tt = the run computed them): per utterance one time per id of `tokens`
+    bool tt = false;
+    std::vector<std::vector<double>> times;
 };
+
+// The times of one window's kept ids: win[i] is generated id i's time with the window's offset (what align_window_kernel wrote);
+// each segment takes its own slice, so the trailing eot and the ids behind the last kept segment leave no entry.
+static void long_slice_times(const double* win, const std::vector<wm_segment>& segs, std::vector<double>& out) {
+    for (const wm_segment& sg : segs) out.insert(out.end(), win + sg.first, win + sg.first + sg.count);
+}
+// align_window_kernel's arithmetic on the host, for wm_op_long_token_times: window-relative fp32 times -> float64 with time_offset
+static void long_window_times(const float* rel, int n, int64_t seek, std::vector<double>& win) {
+#pragma clang fp contract(off)
+    const double off = (double)seek * 0.02 / 2;
+    win.resize(n);
+    for (int i = 0; i < n; ++i) win[i] = (double)rel[i] + off;
+}
 
 // HF WhisperGenerationMixin._retrieve_segment (time_precision 0.02, time_precision_features 0.01, input_stride 2) on one window's
 // generated ids without the trailing eot.  Returns the seek advance in frames exactly as HF computes it (possibly 0).
@@ -3907,7 +3974,7 @@ static int long_check(wm_model* m, const wm_decode_opts* o, int B) {
 // seek 0 is gathered in groups of R rows and run through wm_detect_language's device path on state 0, the ids are read back once per
 // group, and from then on recording b's initial ids are opts->prompt with slot 1 replaced by its language: every pass is a per-row pass.
 static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int B, const wm_decode_opts* o, wm_long_result* res,
-                    const wm_long_opts* lo, const int32_t* lang_ids = nullptr, int n_lang = 0, int32_t* lang_out = nullptr) {
+                    const wm_long_opts* lo, const int32_t* lang_ids = nullptr, int n_lang = 0, int32_t* lang_out = nullptr, bool tt = false) {
     const wm_dims& c = m->cfg.dims;
     const bool plain = long_opts_plain(lo) && !lang_ids;
     // thresholds: every pass is a log-prob pass; with a no_speech_token it also carries the probe at the first of the
@@ -3936,11 +4003,26 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
     out.token_logprobs = quality ? lps.data() : nullptr;
     out.avg_logprob = quality ? avg.data() : nullptr;
     out.no_speech_prob = ns.token >= 0 ? nsp.data() : nullptr;
+    // token timestamps: every window pass carries the alignment capture and the chain; per state the columns kept per
+    // row (window frames / 2) and the window table the finishing kernel reads, per pass the times [R][max_loop + 1] it hands back
+    const int L1 = o->max_loop + 1;
+    std::vector<double> wt(tt ? (size_t)R * L1 : 0);
+    std::vector<int32_t> win_cols[2];
+    WinAsk win_ask[2];
+    out.win_times = tt ? wt.data() : nullptr;
+    res->tt = tt;
     auto collect = [&](int k) { return wait_on(m, L.st[k], 0, -1, out); };
     auto window_ask = [&](int k, const wm_decode_opts* opts) {  // a pass over state k's gathered windows
         PassAsk ask{L.win[k].as<float>(), 1, R, opts};
         ask.lp = quality;
         ask.ns = ns;
+        if (tt) {
+            win_cols[k].resize(R);
+            for (int r = 0; r < R; ++r) win_cols[k][r] = std::max(1, L.h_items[k][3 * r + 2] / 2);
+            win_ask[k] = WinAsk{L.items[k].as<int>(), n_items[k]};
+            ask.cols = &win_cols[k];
+            ask.win = &win_ask[k];
+        }
         return ask;
     };
     auto drain = [&]() {  // an error mid-run: let the other pass finish before returning
@@ -4082,6 +4164,7 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
                     res->seg_nsp[b].push_back(nsp[r]);
                 }
             }
+            if (tt) long_slice_times(wt.data() + (size_t)r * L1, segs, res->times[b]);
             seek[b] += adv;
             busy[b] = 0;
             ++res->windows;
@@ -4091,14 +4174,16 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
 }
 
 static int transcribe_long_impl(wm_model* m, const float* mel_dev, int T, const int32_t* nf, int B, const wm_decode_opts* o, wm_long_result** out,
-                                const wm_long_opts* lo, const int32_t* lang_ids = nullptr, int n_lang = 0, int32_t* lang_out = nullptr) {
+                                const wm_long_opts* lo, const int32_t* lang_ids = nullptr, int n_lang = 0, int32_t* lang_out = nullptr,
+                                bool tt = false) {
     wm_long_result* r = new wm_long_result();
+    r->times.resize(B);
     r->tokens.resize(B);
     r->segs.resize(B);
     r->wins.resize(B);
     r->seg_avg.resize(B);
     r->seg_nsp.resize(B);
-    const int rc = long_run(m, mel_dev, T, nf, B, o, r, lo, lang_ids, n_lang, lang_out);
+    const int rc = long_run(m, mel_dev, T, nf, B, o, r, lo, lang_ids, n_lang, lang_out, tt);
     (void)hipStreamSynchronize(m->stream);
     long_release(m);
     if (rc) {
@@ -4118,11 +4203,20 @@ static int long_lang_check(wm_model* m, const wm_decode_opts* o, int B, const in
     if (m->cfg.dims.n_text_ctx < o->n_prompt + 1 + o->max_loop) return fail(WM_E_ARG, "the decoder context is too short");
     return 0;
 }
+// the extra refusals of a long-form run with token timestamps, before anything is launched
+static int long_tt_check(wm_model* m, const wm_long_opts* lo) {
+    if (lo && (lo->use_logprob_threshold || lo->use_no_speech_threshold))
+        return fail(WM_E_ARG, "token timestamps do not combine with logprob_threshold / no_speech_threshold");
+    if (m->align_pairs.empty()) return fail(WM_E_STATE, "token timestamps need alignment heads (wm_set_alignment_heads)");
+    return 0;
+}
 static int long_mel_impl(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames, const wm_decode_opts* o,
-                         const wm_long_opts* lo, const int32_t* lang_ids, int n_lang, int32_t* lang_out, bool want_lang, wm_long_result** out) {
+                         const wm_long_opts* lo, const int32_t* lang_ids, int n_lang, int32_t* lang_out, bool want_lang, wm_long_result** out,
+                         bool tt = false) {
     if (!m || !mel || !out || T <= 0) return fail(WM_E_ARG, "bad argument");
     *out = nullptr;
     WMCHK(long_check(m, o, B));
+    if (tt) WMCHK(long_tt_check(m, lo));
     WMCHK(long_opts_check(lo, o->prompt, o->n_prompt, o->max_loop, m->cfg.dims.vocab, m->cfg.dims.n_text_ctx, std::min((B + 1) / 2, m->cfg.max_batch)));
     if (want_lang) WMCHK(long_lang_check(m, o, B, lang_ids, n_lang, lang_out));
     std::vector<int32_t> nf(B, T);
@@ -4139,7 +4233,7 @@ static int long_mel_impl(wm_model* m, const float* mel, int mel_on_device, int B
         HIPCHK(hipMemcpyAsync(m->lf.in_mel.p, mel, bytes, hipMemcpyHostToDevice, m->stream));
         dev = m->lf.in_mel.as<float>();
     }
-    return transcribe_long_impl(m, dev, T, nf.data(), B, o, out, lo, want_lang ? lang_ids : nullptr, n_lang, lang_out);
+    return transcribe_long_impl(m, dev, T, nf.data(), B, o, out, lo, want_lang ? lang_ids : nullptr, n_lang, lang_out, tt);
 }
 extern "C" int wm_transcribe_long_ex(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames,
                                      const wm_decode_opts* o, const wm_long_opts* lo, wm_long_result** out) {
@@ -4150,6 +4244,37 @@ extern "C" int wm_transcribe_long_lang(wm_model* m, const float* mel, int mel_on
                                        wm_long_result** out) {
     return long_mel_impl(m, mel, mel_on_device, B, T, n_frames, o, lo, lang_ids, n_lang, lang_out, true, out);
 }
+// lang_ids null: no language detection (lang_out is not written), else as wm_transcribe_long_lang
+extern "C" int wm_transcribe_long_tt(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames,
+                                     const wm_decode_opts* o, const wm_long_opts* lo, const int32_t* lang_ids, int n_lang, int32_t* lang_out,
+                                     int token_timestamps, wm_long_result** out) {
+    return long_mel_impl(m, mel, mel_on_device, B, T, n_frames, o, lo, lang_ids, n_lang, lang_out, lang_ids != nullptr, out, token_timestamps != 0);
+}
+extern "C" int wm_long_result_token_times(const wm_long_result* r, int b, double* times) {
+    if (!r || b < 0 || b >= (int)r->tokens.size()) return fail(WM_E_ARG, "bad argument");
+    if (!r->tt) return fail(WM_E_STATE, "this run had no token timestamps (wm_transcribe_long_tt)");
+    if (!times && !r->times[b].empty()) return fail(WM_E_ARG, "bad argument");
+    std::copy(r->times[b].begin(), r->times[b].end(), times);
+    return 0;
+}
+// Host only: what a timestamp window pass and the scheduler make of one window.  rel: the window-relative fp32 time of
+// each of its n generated ids (trailing eot dropped), segs: wm_op_long_segments' segments of those ids -> one float64 per kept id.
+extern "C" int wm_op_long_token_times(const float* rel, int n, int64_t seek, const wm_segment* segs, int n_segs, double* times, int32_t* n_times) {
+    if (n < 0 || (n > 0 && !rel) || seek < 0 || n_segs < 0 || (n_segs > 0 && !segs) || !n_times) return fail(WM_E_ARG, "bad argument");
+    size_t total = 0;
+    for (int i = 0; i < n_segs; ++i) {
+        if (segs[i].first < 0 || segs[i].count < 0 || segs[i].first + segs[i].count > n) return fail(WM_E_ARG, "segment %d outside the window's %d ids", i, n);
+        total += segs[i].count;
+    }
+    if (total > 0 && !times) return fail(WM_E_ARG, "bad argument");
+    std::vector<double> win, kept;
+    long_window_times(rel, n, seek, win);
+    long_slice_times(win.data(), std::vector<wm_segment>(segs, segs + n_segs), kept);
+    std::copy(kept.begin(), kept.end(), times);
+    *n_times = (int32_t)kept.size();
+    return 0;
+}
+
 extern "C" int wm_transcribe_long(wm_model* m, const float* mel, int mel_on_device, int B, int T, const int32_t* n_frames, const wm_decode_opts* o,
                                   wm_long_result** out) {
     return wm_transcribe_long_ex(m, mel, mel_on_device, B, T, n_frames, o, nullptr, out);
@@ -4160,10 +4285,11 @@ extern "C" int wm_transcribe_long_pcm(wm_model* m, const float* pcm, const int32
     return wm_transcribe_long_pcm_ex(m, pcm, n_samples, B, stride, o, nullptr, out);
 }
 static int long_pcm_impl(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o, const wm_long_opts* lo,
-                         const int32_t* lang_ids, int n_lang, int32_t* lang_out, bool want_lang, wm_long_result** out) {
+                         const int32_t* lang_ids, int n_lang, int32_t* lang_out, bool want_lang, wm_long_result** out, bool tt = false) {
     if (!m || !out) return fail(WM_E_ARG, "bad argument");
     *out = nullptr;
     WMCHK(long_check(m, o, B));
+    if (tt) WMCHK(long_tt_check(m, lo));
     WMCHK(long_opts_check(lo, o->prompt, o->n_prompt, o->max_loop, m->cfg.dims.vocab, m->cfg.dims.n_text_ctx, std::min((B + 1) / 2, m->cfg.max_batch)));
     if (want_lang) WMCHK(long_lang_check(m, o, B, lang_ids, n_lang, lang_out));
     std::vector<int32_t> nf(std::max(B, 0));
@@ -4173,7 +4299,7 @@ static int long_pcm_impl(wm_model* m, const float* pcm, const int32_t* n_samples
         long_release(m);
         return rc;
     }
-    return transcribe_long_impl(m, m->lf.mel.as<float>(), stride / FE_HOP, nf.data(), B, o, out, lo, want_lang ? lang_ids : nullptr, n_lang, lang_out);
+    return transcribe_long_impl(m, m->lf.mel.as<float>(), stride / FE_HOP, nf.data(), B, o, out, lo, want_lang ? lang_ids : nullptr, n_lang, lang_out, tt);
 }
 extern "C" int wm_transcribe_long_pcm_ex(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o,
                                          const wm_long_opts* lo, wm_long_result** out) {
@@ -4182,6 +4308,11 @@ extern "C" int wm_transcribe_long_pcm_ex(wm_model* m, const float* pcm, const in
 extern "C" int wm_transcribe_long_pcm_lang(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o,
                                            const wm_long_opts* lo, const int32_t* lang_ids, int n_lang, int32_t* lang_out, wm_long_result** out) {
     return long_pcm_impl(m, pcm, n_samples, B, stride, o, lo, lang_ids, n_lang, lang_out, true, out);
+}
+extern "C" int wm_transcribe_long_pcm_tt(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o,
+                                         const wm_long_opts* lo, const int32_t* lang_ids, int n_lang, int32_t* lang_out, int token_timestamps,
+                                         wm_long_result** out) {
+    return long_pcm_impl(m, pcm, n_samples, B, stride, o, lo, lang_ids, n_lang, lang_out, lang_ids != nullptr, out, token_timestamps != 0);
 }
 
 extern "C" int wm_long_result_sizes(const wm_long_result* r, int b, int32_t* n_tokens, int32_t* n_segments) {

@@ -433,6 +433,22 @@ int launch_align_probs(const AlignParams& p, hipStream_t st);  // WM_LAUNCH_*
 int launch_align_norm(const AlignParams& p, hipStream_t st);
 int launch_align_dtw(const AlignParams& p, hipStream_t st);
 size_t align_dtw_lds_bytes(int L, int T);  // dynamic LDS of align_dtw with the trace in LDS (0: does not fit, trace goes to global)
+// A long-form window pass with token timestamps: one kernel, launched on both sides of the chain.  Row r of the pass holds
+// window items[r] = (utterance, seek, frames) with n_tokens[r] ids, prompt_len[r] of them prompt (null: n_prompt for every row).
+//   mode 0, before the chain: rows[r] = n_tokens[r] - prompt_len[r] - 1 clamped to [0, L] (0 for the spare rows r >= n_real) and
+//           row0[r] = prompt_len[r]: the ragged tables the chain reads (AlignParams::rows / row0).
+//   mode 1, behind it: out[r][i], i in [0, L], = double(times[r][prompt_len[r] + i]) + double(seek_r) · 0.02 / 2 for the row's
+//           n_tokens[r] - prompt_len[r] generated ids, 0 past them and in the spare rows (L = 0 is allowed: no chain ran, times is 0).
+struct AlignWindowParams {
+    int mode, B, n_real, L, n_prompt, out_stride;  // rows of the pass, real ones, max_loop, longest prompt, columns of `times`
+    const int* n_tokens;    // [B]
+    const int* prompt_len;  // [B] or null
+    const int* items;       // [B][3]
+    int *rows, *row0;       // [B]
+    const float* times;     // [B][out_stride], the chain's output
+    double* out;            // [B][L + 1]
+};
+int launch_align_window(const AlignWindowParams& p, hipStream_t st);  // WM_LAUNCH_*
 
 // ---- log-mel front end (kernels_frontend.hip) ------------------------------------------------------------------------
 void launch_zero_tails(float* pcm, const int* len, int B, int N, hipStream_t st);

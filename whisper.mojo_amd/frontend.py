@@ -106,9 +106,10 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
                                timestamps=(50364, 50363, 50), return_stats: bool = False, prompt_ids=None,
                                condition_on_prev_tokens: bool = False, prompt_condition_type: str = "first-segment",
                                prev_sot_token: int = 50361, logprob_threshold=None, no_speech_threshold=None, no_speech_token=None,
-                               detect_language=None):
+                               detect_language=None, return_token_timestamps: bool = False):
     """Sequential long-form transcription of 16 kHz PCM of any length (HF generate's long-form path), the long
-    log-mel never leaving the GPU.  prompt_ids / condition_on_prev_tokens / prompt_condition_type / logprob_threshold /
+    log-mel never leaving the GPU.  return_token_timestamps: as Whisper.transcribe_long_form ("token_times" per recording,
+    "token_timestamps" per segment; not with the thresholds).  prompt_ids / condition_on_prev_tokens / prompt_condition_type / logprob_threshold /
     no_speech_threshold / no_speech_token / detect_language (then the detected ids [B] are returned as the last element): as
     Whisper.transcribe_long_form.  Returns per recording {"sequence": ids, "segments": [{"start", "end", "tokens"}]}."""
     lo, _keep2 = _lib.long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token, logprob_threshold,
@@ -117,6 +118,7 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
         raise ValueError(f"no_speech_token {no_speech_token} is not a vocabulary id")
     if timestamps is None:
         raise ValueError("long-form transcription needs the timestamp rules")
+    tt = _lib.long_tt_args(return_token_timestamps, logprob_threshold, no_speech_threshold)
     lang_list = None
     if detect_language is not None:
         lang_list = _lib.lang_args(detect_language, model.config.vocab_size)
@@ -129,6 +131,17 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
     opts, _keep = model._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
     h = C.c_void_p()
+    if tt:
+        lang = np.zeros(len(audios), np.int32)
+        _lib.check(_lib.lib().wm_transcribe_long_pcm_tt(model._h, buf.ctypes.data_as(fp), n.ctypes.data_as(ip), len(audios), stride,
+                                                        C.byref(opts), C.byref(lo),
+                                                        lang_list.ctypes.data_as(ip) if lang_list is not None else None,
+                                                        lang_list.size if lang_list is not None else 0, lang.ctypes.data_as(ip), 1,
+                                                        C.byref(h)))
+        out, stats = _lib.long_result(h, len(audios), False, True)
+        res = (out, stats) if return_stats else (out,)
+        res = res + (lang,) if lang_list is not None else res
+        return res if len(res) > 1 else out
     if lang_list is not None:
         lang = np.zeros(len(audios), np.int32)
         _lib.check(_lib.lib().wm_transcribe_long_pcm_lang(model._h, buf.ctypes.data_as(fp), n.ctypes.data_as(ip), len(audios), stride,

@@ -407,8 +407,12 @@ class Whisper:
                              condition_on_prev_tokens: bool = False, prompt_condition_type: str = "first-segment",
                              prev_sot_token: int = 50361, logprob_threshold: Optional[float] = None,
                              no_speech_threshold: Optional[float] = None, no_speech_token: Optional[int] = None,
-                             detect_language: Optional[Sequence[int]] = None):
+                             detect_language: Optional[Sequence[int]] = None, return_token_timestamps: bool = False):
         """Sequential long-form transcription (HF generate's long-form path, greedy).
+        return_token_timestamps (HF generate's option on its long-form path; needs set_alignment_heads): every utterance
+        also carries "token_times", a float64 array with the time in seconds of every id of "sequence", and every segment
+        "token_timestamps", its slice of it.  Works with prompt_ids, condition_on_prev_tokens and detect_language; ValueError with
+        logprob_threshold / no_speech_threshold.
         detect_language: a list of language ids (HF generate's language=None) — every recording's language is detected on
         its first window and replaces the second id of `prompt` for that recording; the call then also returns the detected ids
         [B] as its last element: (out, lang) or (out, stats, lang).
@@ -430,6 +434,7 @@ class Whisper:
         if no_speech_token is not None and int(no_speech_token) >= self.config.vocab_size:
             raise ValueError(f"no_speech_token {no_speech_token} is not a vocabulary id")
         quality = logprob_threshold is not None or no_speech_threshold is not None
+        tt = _lib.long_tt_args(return_token_timestamps, logprob_threshold, no_speech_threshold)
         lang_list = None
         if detect_language is not None:
             lang_list = _lib.lang_args(detect_language, self.config.vocab_size)
@@ -469,7 +474,7 @@ class Whisper:
                 return self.transcribe_long_form(t.float().numpy(), n_frames, prompt, eot, max_loop, suppress_tokens,
                                                  begin_suppress_tokens, timestamps, return_stats, prompt_ids, condition_on_prev_tokens,
                                                  prompt_condition_type, prev_sot_token, logprob_threshold, no_speech_threshold, no_speech_token,
-                                                 detect_language)
+                                                 detect_language, return_token_timestamps)
             keep = t.contiguous().float()
             torch.cuda.current_stream(keep.device).synchronize()  # the library reads it on its own HIP stream
             ptr, on_dev = C.c_void_p(keep.data_ptr()), 1
@@ -477,6 +482,15 @@ class Whisper:
         nf = self._frames_arg(n_frames, B)
         opts, _keep2 = self._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
         h = C.c_void_p()
+        if tt:  # one entry point with or without the language list
+            lang = np.zeros(B, np.int32)
+            _lib.check(_lib.lib().wm_transcribe_long_tt(self._h, ptr, on_dev, B, T, _ip(nf) if nf is not None else None, C.byref(opts),
+                                                        C.byref(lo), _ip(lang_list) if lang_list is not None else None,
+                                                        lang_list.size if lang_list is not None else 0, _ip(lang), 1, C.byref(h)))
+            out, stats = _lib.long_result(h, B, False, True)
+            res = (out, stats) if return_stats else (out,)
+            res = res + (lang,) if lang_list is not None else res
+            return res if len(res) > 1 else out
         if lang_list is not None:
             lang = np.zeros(B, np.int32)
             _lib.check(_lib.lib().wm_transcribe_long_lang(self._h, ptr, on_dev, B, T, _ip(nf) if nf is not None else None, C.byref(opts),
