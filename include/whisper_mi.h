@@ -289,6 +289,26 @@ int wm_score_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B,
                  const int32_t* ids_len, int ids_stride, const int32_t* context_len, float* token_logprobs, int32_t* top_ids, float* sum_logprob,
                  float* avg_logprob);
 
+/* ---- repetition processors -------------------------------------------------------------------------------------
+ * HF generate's repetition_penalty (RepetitionPenaltyLogitsProcessor) and no_repeat_ngram_size (NoRepeatNGramLogitsProcessor) for
+ * every greedy pass asked for from now on: wm_transcribe and its _submit / _rows / _lp / _lp_ns / _lang / _tt / _pcm forms and the
+ * wm_transcribe_long family (a model-wide setting, like the alignment heads; a submit that is held for a coalesce = 2 partner keeps the
+ * values in force when it was made, and pairs only with a submit made under the same values).  At every step, with hist the row's
+ * decoder ids so far (its own prompt, then what it generated) and z its fp32 logits, in this order and before the suppress masks, the
+ * timestamp rules, the arg-max and the log-prob sums:
+ *   1. every id t in hist, once: z[t] = z[t] * penalty if z[t] < 0, else z[t] / penalty;
+ *   2. with n = no_repeat_ngram_size >= 1 and len(hist) + 1 >= n: every id that follows an occurrence of hist's last n - 1 ids inside
+ *      hist is -inf (n = 1: every id of hist).
+ * Log-probs are those of the processed row: a banned id adds nothing to the normaliser, a penalised one exp of its penalised value.
+ * The no-speech probe, language detection, wm_score and wm_align read unprocessed logits.  A long-form window's pass sees that
+ * window's decoder ids only (a carried previous text included).  Both run on the device inside the captured step: two bit sets per
+ * row, kept by the step's arg-max launch and read by the logits kernel; a pass with both off launches exactly what it did before.
+ * penalty 1 and n 0 = off (the default).  WM_E_ARG: penalty <= 0 or not finite, n < 0 or n > 64.
+ * The setting PERSISTS until the next wm_set_repeat_options on the model: a caller that wants one pass processed sets the values
+ * before it and sets (1, 0) after it (the Python layer sets them on every greedy call).  It is read once, when a pass is asked
+ * for; like every call on a wm_model it is not synchronised — threads that share a model serialise set + submit themselves. */
+int wm_set_repeat_options(wm_model* m, float repetition_penalty, int no_repeat_ngram_size);
+
 /* ---- token-level timestamps ---------------------------------------------------------------------------------
  * When each id was spoken, with the semantics of HF generate(..., return_token_timestamps=True)
  * (WhisperGenerationMixin._extract_token_timestamps, time_precision 0.02, median_filter_width 7, num_input_ids = n_prompt): the
@@ -572,6 +592,18 @@ int wm_op_logits(float* logits, int32_t* ids, const float* x, const float* ln_g,
  * bit for bit. */
 int wm_op_logits_lp(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                     const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype);
+/* wm_op_logits / wm_op_logits_lp (logprob NULL / non-NULL) on the repetition-processor instantiation of the same kernel variant
+ * (DESIGN §29), with given sets: seen, ban [B][ceil(N / 32)], id t = bit (t & 31) of word t >> 5.  Row b's logits at the ids of seen[b]
+ * are multiplied (negative) or divided (else) by penalty, then those of ban[b] are -inf — before everything the mask, the ranges
+ * and the log-prob sums do.  `logits` are the processed values. */
+int wm_op_logits_processed(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                           const float* mask, const int32_t* ranges, int timestamp_begin, const uint32_t* seen, const uint32_t* ban,
+                           float penalty, int B, int N, int K, int dtype);
+/* The sets' bookkeeping alone: the init kernel on each row's prompt tokens[b][0 .. prompt_len[b]), then `steps` argmax launches, step
+ * s appending tokens[b][prompt_len[b] + s - 1] (a row past n_ids[b] has ended and does nothing).  seen, ban: host
+ * [steps + 1][B][ceil(vocab / 32)] — entry 0 after the init, entry s after step s.  1 <= prompt_len[b] <= n_ids[b] <= stride. */
+int wm_op_repeat_sets(uint32_t* seen, uint32_t* ban, const int32_t* tokens, const int32_t* prompt_len, const int32_t* n_ids, int B, int stride,
+                      int vocab, int ngram, int steps);
 /* The no-speech probe's launches on the kernel variant wm_op_logits_lp picks for (dtype, K, B): prob[b] = softmax(LN(x[b])·embᵀ)[token]
  * over all N columns, lse[b] the row's logsumexp.  prob, lse: [B]. */
 int wm_op_no_speech(float* prob, float* lse, const float* x, const float* ln_g, const float* ln_b, const float* emb, int B, int N, int K,

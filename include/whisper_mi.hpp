@@ -441,6 +441,12 @@ public:
         no_ts_ = no_timestamps_token;
         max_init_ = max_initial_timestamp_index;
     }
+    // HF generate's repetition_penalty / no_repeat_ngram_size for every transcribe / transcribe_long call from now on:
+    // 1.0 and 0 switch them off (the default).  Throws std::invalid_argument for a penalty <= 0 or an n outside [0, 64].
+    void set_repeat_options(float repetition_penalty, int no_repeat_ngram_size) {
+        need_model();
+        if (wm_set_repeat_options(model_, repetition_penalty, no_repeat_ngram_size) != WM_OK) throw std::invalid_argument(wm_last_error());
+    }
     const WhisperConfig& config() const { return cfg_; }
     wm_model* handle() const { return model_; }
 

@@ -37,6 +37,7 @@ SYMBOLS = [
     "wm_op_xattn_absorb",
     "wm_op_dec_linear_long",
     "wm_transcribe_long_tt", "wm_transcribe_long_pcm_tt", "wm_long_result_token_times", "wm_op_long_token_times",
+    "wm_set_repeat_options", "wm_op_logits_processed", "wm_op_repeat_sets",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -301,8 +302,30 @@ def lib():
     L.wm_synth_weights.restype = C.c_size_t
     L.wm_synth_mel_host.argtypes = [C.c_uint64, C.c_int, C.c_int, fp]
     L.wm_synth_mel_host.restype = None
+    up = C.POINTER(C.c_uint32)
+    L.wm_set_repeat_options.argtypes = [vp, C.c_float, C.c_int]
+    L.wm_op_logits_processed.argtypes = [fp, ip, fp, fp, fp, fp, fp, fp, ip, C.c_int, up, up, C.c_float] + [C.c_int] * 4
+    L.wm_op_repeat_sets.argtypes = [up, up, ip, ip, ip] + [C.c_int] * 5
     _lib = L
     return L
+
+
+REPEAT_NGRAM_MAX = 64  # wm_kernels.h REPEAT_NGRAM_MAX
+
+
+def repeat_args(repetition_penalty, no_repeat_ngram_size):
+    """Checks HF generate's repetition_penalty / no_repeat_ngram_size on the host (the library refuses the same with WM_E_ARG) ->
+    (penalty, n) as wm_set_repeat_options takes them: None means off (1.0 / 0)."""
+    p = 1.0 if repetition_penalty is None else float(repetition_penalty)
+    if not (p > 0.0) or p != p or p == float("inf"):
+        raise ValueError(f"repetition_penalty must be a finite float > 0 (got {repetition_penalty!r})")
+    n = 0 if no_repeat_ngram_size is None else no_repeat_ngram_size
+    if isinstance(n, bool) or int(n) != n:
+        raise ValueError(f"no_repeat_ngram_size must be an integer (got {no_repeat_ngram_size!r})")
+    n = int(n)
+    if n < 0 or n > REPEAT_NGRAM_MAX:
+        raise ValueError(f"no_repeat_ngram_size must lie in [0, {REPEAT_NGRAM_MAX}] (got {n})")
+    return p, n
 
 
 def long_tt_args(return_token_timestamps, logprob_threshold, no_speech_threshold):

@@ -564,6 +564,39 @@ __device__ __forceinline__ void logits_epilogue(const DecLinearParams& p, int CT
         }
     }
 }
+// RP (repetition processors): the lane's accumulators pass through the row's two bit sets first — penalty at the ids of
+// `seen`, -inf at the ids of `ban` — and the tail above sees the processed values: the logits store, the argmax candidates, the
+// timestamp partials and the log-prob sums.  A lane's four columns start at a multiple of four, so one word of each set covers them.
+// RP = false is the tail above and nothing else.
+template <int NRB, bool LP, bool RP>
+__device__ __forceinline__ void logits_epilogue_rp(const DecLinearParams& p, int CT, const f32x4 (&acc)[2][NRB], const int (&n0)[2],
+                                                   const bool (&have)[2], const float (&mk)[2][4], int row0, int nrows, int lane, int w,
+                                                   const LogitsScratch<NRB>& sc) {
+    if constexpr (RP) {
+        const int r16 = lane & 15, g = lane >> 4;
+        const float pen = p.rp_ctl->penalty;
+        f32x4 pa[2][NRB];
+#pragma unroll
+        for (int rb = 0; rb < NRB; ++rb) {
+            const size_t row = (size_t)(row0 + min(rb * 16 + r16, nrows - 1)) * p.rp_words;
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+                const int n = min(n0[nb] + g * 4, p.N - 1);  // (a tile past the vocabulary is not `have`: any word of the row will do)
+                const unsigned sw = p.rp_seen[row + (n >> 5)] >> (n & 31), bw = p.rp_ban[row + (n >> 5)] >> (n & 31);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float z = acc[nb][rb][r];
+                    if ((sw >> r) & 1u) z = z < 0.f ? z * pen : z / pen;
+                    if ((bw >> r) & 1u) z = -INFINITY;
+                    pa[nb][rb][r] = z;
+                }
+            }
+        }
+        logits_epilogue<NRB, LP>(p, CT, pa, n0, have, mk, row0, nrows, lane, w, sc);
+    } else {
+        logits_epilogue<NRB, LP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, sc);
+    }
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // Final LayerNorm + tied-embedding logits (whisper.mojo:156-166): logits[B, V] = LN(x)[B, d] · tok_emb[V, d]ᵀ.
@@ -572,7 +605,7 @@ __device__ __forceinline__ void logits_epilogue(const DecLinearParams& p, int CT
 // workgroup (LN statistics from a 4-thread-per-row sweep, everything in flight at once) and parked in LDS as MFMA
 // operands, so L2 sees x once per 128 columns; each wave then streams its 32 embedding rows straight from HBM into
 // registers (all k-steps in flight) and needs no cross-wave reduction.
-template <typename TW, int KD /* d_model/128 */, int NRB, bool LP = false>
+template <typename TW, int KD /* d_model/128 */, int NRB, bool LP = false, bool RP = false>
 __global__ __launch_bounds__(512) void dec_logits_kernel(DecLinearParams p, int CT) {
     // One workgroup = 8 waves = CT <= 16 column tiles of 16 vocabulary rows (wave w owns tiles w and w+8), all NRB*16
     // utterance rows.  CT is chosen by the launcher so that the whole vocabulary is ONE round of <= 256 workgroups
@@ -755,12 +788,12 @@ __global__ __launch_bounds__(512) void dec_logits_kernel(DecLinearParams p, int 
             __shared__ float s_ls[8][NRB * 16];
             sc.ls = s_ls;
         }
-        logits_epilogue<NRB, LP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, sc);
+        logits_epilogue_rp<NRB, LP, RP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, sc);
     } else {  // 128 rows: the 48 KB of scratch do not fit beside the activation image — overlay it once every wave is done reading
         __syncthreads();
         static_assert((LP ? LogitsScratch<NRB>::bytes_lp : LogitsScratch<NRB>::bytes) <= (size_t)NRB * 16 * PITCH * sizeof(TW),
                       "epilogue scratch must fit the activation image");
-        logits_epilogue<NRB, LP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
+        logits_epilogue_rp<NRB, LP, RP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
     }
     WM_LG_STAMP(4);
 }
@@ -808,7 +841,7 @@ __device__ __forceinline__ f32x4 mma_bf16(const bf16x8& a, const bf16x8& b, f32x
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-template <int KD /* d_model/128 */, int NRB, bool LP = false>
+template <int KD /* d_model/128 */, int NRB, bool LP = false, bool RP = false>
 __global__ __launch_bounds__(512) void dec_logits_split_kernel(DecLinearParams p, int CT) {
     // Geometry as dec_logits_kernel: 8 waves, wave w owns column tiles w and w + 8 of the workgroup's CT <= 16, all NRB*16 rows.
     constexpr int K = KD * 128;
@@ -976,7 +1009,7 @@ __global__ __launch_bounds__(512) void dec_logits_split_kernel(DecLinearParams p
     __syncthreads();  // every wave is past its last fragment read: the epilogue's scratch overlays the activation images
     static_assert((LP ? LogitsScratch<NRB>::bytes_lp : LogitsScratch<NRB>::bytes) <= (size_t)3 * IMG * sizeof(bf16),
                   "epilogue scratch must fit the activation images");
-    logits_epilogue<NRB, LP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
+    logits_epilogue_rp<NRB, LP, RP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
     WM_LG_STAMP(4);
 }
 #undef WM_LG_STAMP
@@ -988,7 +1021,7 @@ __global__ __launch_bounds__(512) void dec_logits_split_kernel(DecLinearParams p
 // LayerNorm statistics are summed in the same order (a thread carries the two partial sums of the two "virtual" threads the
 // 8-threads-per-row scheme gives its elements to), the k-steps accumulate in the same order — so the ids of a coalesced pass equal
 // the uncoalesced ones bit for bit.
-template <int KD /* d_model/128 */, bool LP = false>
+template <int KD /* d_model/128 */, bool LP = false, bool RP = false>
 __global__ __launch_bounds__(512) void dec_logits_split128_kernel(DecLinearParams p, int CT) {
     constexpr int NRB = 8, ROWS = 128;
     constexpr int K = KD * 128, KH = K / 2;  // columns per pass
@@ -1188,28 +1221,28 @@ __global__ __launch_bounds__(512) void dec_logits_split128_kernel(DecLinearParam
     __syncthreads();  // the epilogue's scratch overlays the activation images
     static_assert((LP ? LogitsScratch<NRB>::bytes_lp : LogitsScratch<NRB>::bytes) <= (size_t)3 * IMG * sizeof(bf16),
                   "epilogue scratch must fit the activation images");
-    logits_epilogue<NRB, LP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
+    logits_epilogue_rp<NRB, LP, RP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
     WM_LG_STAMP(4);
 }
 #undef WM_LG_STAMP
-template <int KD, bool LP = false> static int launch_dec_logits_split128_t(const DecLinearParams& p, hipStream_t st) {
+template <int KD, bool LP = false, bool RP = false> static int launch_dec_logits_split128_t(const DecLinearParams& p, hipStream_t st) {
     const size_t lds = (size_t)3 * 128 * (KD * 64 + 16) * sizeof(bf16) + (size_t)2 * KD * 128 * sizeof(float);
     if (lds > 48 * 1024)
-        if (const hipError_t e = ensure_dyn_lds<&dec_logits_split128_kernel<KD, LP>>((int)lds); e != hipSuccess)
+        if (const hipError_t e = ensure_dyn_lds<&dec_logits_split128_kernel<KD, LP, RP>>((int)lds); e != hipSuccess)
             return launch_hip_failed("logits kernel (split fp32, 128 rows): dynamic LDS attribute", e);
     const int ct = dec_logits_tiles_per_wg(p.N);
     dim3 grid(dec_logits_parts(p.N), (p.B + 127) / 128);
-    hipLaunchKernelGGL((dec_logits_split128_kernel<KD, LP>), grid, dim3(512), lds, st, p, ct);
+    hipLaunchKernelGGL((dec_logits_split128_kernel<KD, LP, RP>), grid, dim3(512), lds, st, p, ct);
     return WM_LAUNCH_OK;
 }
-template <int KD, int NRB, bool LP = false> static int launch_dec_logits_split_t(const DecLinearParams& p, hipStream_t st) {
+template <int KD, int NRB, bool LP = false, bool RP = false> static int launch_dec_logits_split_t(const DecLinearParams& p, hipStream_t st) {
     const size_t lds = (size_t)3 * NRB * 16 * (KD * 128 + 16) * sizeof(bf16) + (size_t)2 * KD * 128 * sizeof(float);
     if (lds > 48 * 1024)
-        if (const hipError_t e = ensure_dyn_lds<&dec_logits_split_kernel<KD, NRB, LP>>((int)lds); e != hipSuccess)
+        if (const hipError_t e = ensure_dyn_lds<&dec_logits_split_kernel<KD, NRB, LP, RP>>((int)lds); e != hipSuccess)
             return launch_hip_failed("logits kernel (split fp32): dynamic LDS attribute", e);
     const int ct = dec_logits_tiles_per_wg(p.N);
     dim3 grid(dec_logits_parts(p.N), (p.B + NRB * 16 - 1) / (NRB * 16));
-    hipLaunchKernelGGL((dec_logits_split_kernel<KD, NRB, LP>), grid, dim3(512), lds, st, p, ct);
+    hipLaunchKernelGGL((dec_logits_split_kernel<KD, NRB, LP, RP>), grid, dim3(512), lds, st, p, ct);
     return WM_LAUNCH_OK;
 }
 
@@ -1227,22 +1260,22 @@ int dec_logits_parts(int N) {
     const int tiles = (N + 15) / 16, ct = dec_logits_tiles_per_wg(N);
     return (tiles + ct - 1) / ct;
 }
-template <typename TW, int KD, int NRB, bool LP = false> static int launch_dec_logits_t(const DecLinearParams& p, hipStream_t st) {
+template <typename TW, int KD, int NRB, bool LP = false, bool RP = false> static int launch_dec_logits_t(const DecLinearParams& p, hipStream_t st) {
     constexpr size_t lds = (size_t)NRB * 16 * (KD * 128 + (sizeof(TW) == 2 ? 80 : 16 / sizeof(TW))) * sizeof(TW);
     // beside the image: gamma | beta (8·K bytes) and, up to 64 rows, the epilogue's scratch: 2 x 32 + 4 x 8 (+ 8 with log-probs)
     // floats / ints per row.  At 128 rows the scratch overlays the image.
     static_assert(lds + (size_t)8 * KD * 128 + (NRB <= 4 ? (size_t)NRB * 16 * 4 * (LP ? 104 : 96) : 0) <= 160 * 1024,
                   "activation image + static LDS must fit the 160 KB of a CU");
     if (lds > 48 * 1024)
-        if (const hipError_t e = ensure_dyn_lds<&dec_logits_kernel<TW, KD, NRB, LP>>((int)lds); e != hipSuccess)
+        if (const hipError_t e = ensure_dyn_lds<&dec_logits_kernel<TW, KD, NRB, LP, RP>>((int)lds); e != hipSuccess)
             return launch_hip_failed("logits kernel: dynamic LDS attribute", e);
     const int ct = dec_logits_tiles_per_wg(p.N);
     dim3 grid(dec_logits_parts(p.N), (p.B + NRB * 16 - 1) / (NRB * 16));
-    hipLaunchKernelGGL((dec_logits_kernel<TW, KD, NRB, LP>), grid, dim3(512), lds, st, p, ct);
+    hipLaunchKernelGGL((dec_logits_kernel<TW, KD, NRB, LP, RP>), grid, dim3(512), lds, st, p, ct);
     return WM_LAUNCH_OK;
 }
 // requires ln_g/ln_b, no bias/act/residual, K in {128, 384, 512, 768, 1024}, ldo % 4 == 0; amax_stride >= dec_logits_parts(N)
-template <typename TW, bool LP> static int launch_dec_logits_lp(const DecLinearParams& p, hipStream_t st) {
+template <typename TW, bool LP, bool RP> static int launch_dec_logits_lp(const DecLinearParams& p, hipStream_t st) {
     const int kd = p.K >> 7;
     if (p.B <= 0 || p.N <= 0) return launch_refuse("dec_logits: empty problem");
     if ((p.K & 127) != 0 || (kd != 1 && kd != 3 && kd != 4 && kd != 6 && kd != 8)) return launch_refuse("dec_logits: d_model must be 128, 384, 512, 768 or 1024");
@@ -1259,24 +1292,24 @@ template <typename TW, bool LP> static int launch_dec_logits_lp(const DecLinearP
         // WM_LOGITS_EXACT (developer build) forces the exact kernel for A/B runs.
         static const bool exact = wm_env("WM_LOGITS_EXACT") != nullptr;
         if (!exact && (kd == 1 || kd == 3)) {
-            if (p.B <= 16) return kd == 1 ? launch_dec_logits_split_t<1, 1, LP>(p, st) : launch_dec_logits_split_t<3, 1, LP>(p, st);
+            if (p.B <= 16) return kd == 1 ? launch_dec_logits_split_t<1, 1, LP, RP>(p, st) : launch_dec_logits_split_t<3, 1, LP, RP>(p, st);
             // more than 64 rows (coalesced batches): 128 rows per workgroup, the embedding streamed once per 128 (WM_LOGITS_NO128: A/B)
             static const bool no128 = wm_env("WM_LOGITS_NO128") != nullptr;
-            if (p.B > 64 && !no128) return kd == 1 ? launch_dec_logits_split128_t<1, LP>(p, st) : launch_dec_logits_split128_t<3, LP>(p, st);
-            return kd == 1 ? launch_dec_logits_split_t<1, 4, LP>(p, st) : launch_dec_logits_split_t<3, 4, LP>(p, st);
+            if (p.B > 64 && !no128) return kd == 1 ? launch_dec_logits_split128_t<1, LP, RP>(p, st) : launch_dec_logits_split128_t<3, LP, RP>(p, st);
+            return kd == 1 ? launch_dec_logits_split_t<1, 4, LP, RP>(p, st) : launch_dec_logits_split_t<3, 4, LP, RP>(p, st);
         }
     }
     if (p.B <= 16) {
-        if (kd == 1) return launch_dec_logits_t<TW, 1, 1, LP>(p, st);
-        if (kd == 3) return launch_dec_logits_t<TW, 3, 1, LP>(p, st);
-        if (kd == 6) return launch_dec_logits_t<TW, 6, 1, LP>(p, st);
-        if (kd == 8) return launch_dec_logits_t<TW, 8, 1, LP>(p, st);
-        return launch_dec_logits_t<TW, 4, 1, LP>(p, st);
+        if (kd == 1) return launch_dec_logits_t<TW, 1, 1, LP, RP>(p, st);
+        if (kd == 3) return launch_dec_logits_t<TW, 3, 1, LP, RP>(p, st);
+        if (kd == 6) return launch_dec_logits_t<TW, 6, 1, LP, RP>(p, st);
+        if (kd == 8) return launch_dec_logits_t<TW, 8, 1, LP, RP>(p, st);
+        return launch_dec_logits_t<TW, 4, 1, LP, RP>(p, st);
     }
     // d_model 1024: 32 rows per workgroup for every operand type (16-bit: 32 x 1104 x 2 = 69 KB image + 21 KB static; fp32:
     // 32 x 1028 x 4 = 129 KB + 21 KB; 64 rows of 16-bit would be 138 + 34 KB, past the 160).  More rows are more row blocks in grid.y.
-    if (kd == 8) return launch_dec_logits_t<TW, 8, 2, LP>(p, st);
-    if (kd == 6) return launch_dec_logits_t<TW, 6, sizeof(TW) == 4 ? 2 : 4, LP>(p, st);  // (16-bit, 64 rows: 106 KB image + 30 KB static)
+    if (kd == 8) return launch_dec_logits_t<TW, 8, 2, LP, RP>(p, st);
+    if (kd == 6) return launch_dec_logits_t<TW, 6, sizeof(TW) == 4 ? 2 : 4, LP, RP>(p, st);  // (16-bit, 64 rows: 106 KB image + 30 KB static)
 #ifdef WM_DEV
     if constexpr (sizeof(TW) == 2) {
         // Developer A/B (WM_LOGITS_128_16BIT): 128 rows per workgroup for 16-bit weights too.  Measured SLOWER than two 64-row
@@ -1285,19 +1318,24 @@ template <typename TW, bool LP> static int launch_dec_logits_lp(const DecLinearP
         // the rows behind one stream.  The fp32 form (80 MB per stream, MFMA-heavy) does gain: dec_logits_split128_kernel.
         static const bool on128 = wm_env("WM_LOGITS_128_16BIT") != nullptr;
         if (p.B > 64 && on128) {
-            if (kd == 1) return launch_dec_logits_t<TW, 1, 8, LP>(p, st);
-            if (kd == 3) return launch_dec_logits_t<TW, 3, 8, LP>(p, st);
-            return launch_dec_logits_t<TW, 4, 8, LP>(p, st);
+            if (kd == 1) return launch_dec_logits_t<TW, 1, 8, LP, RP>(p, st);
+            if (kd == 3) return launch_dec_logits_t<TW, 3, 8, LP, RP>(p, st);
+            return launch_dec_logits_t<TW, 4, 8, LP, RP>(p, st);
         }
     }
 #endif
-    if (kd == 1) return launch_dec_logits_t<TW, 1, 4, LP>(p, st);
-    if (kd == 3) return launch_dec_logits_t<TW, 3, 4, LP>(p, st);
-    return launch_dec_logits_t<TW, 4, 4, LP>(p, st);
+    if (kd == 1) return launch_dec_logits_t<TW, 1, 4, LP, RP>(p, st);
+    if (kd == 3) return launch_dec_logits_t<TW, 3, 4, LP, RP>(p, st);
+    return launch_dec_logits_t<TW, 4, 4, LP, RP>(p, st);
 }
 // p.lp_s null: exactly the kernels, grids and LDS of a pass without log-probabilities; non-null: the LP instantiation of the same variant
+// p.rp_seen likewise: null is the pass without the repetition processors, non-null the RP instantiation of the same variant
 template <typename TW> int launch_dec_logits(const DecLinearParams& p, hipStream_t st) {
-    return p.lp_s ? launch_dec_logits_lp<TW, true>(p, st) : launch_dec_logits_lp<TW, false>(p, st);
+    if (p.rp_seen) {
+        if (!p.rp_ban || !p.rp_ctl || p.rp_words < repeat_words(p.N)) return launch_refuse("dec_logits: the repetition processors need both sets of ceil(N / 32) words per row and their control block");
+        return p.lp_s ? launch_dec_logits_lp<TW, true, true>(p, st) : launch_dec_logits_lp<TW, false, true>(p, st);
+    }
+    return p.lp_s ? launch_dec_logits_lp<TW, true, false>(p, st) : launch_dec_logits_lp<TW, false, false>(p, st);
 }
 template int launch_dec_logits<float>(const DecLinearParams&, hipStream_t);
 template int launch_dec_logits<bf16>(const DecLinearParams&, hipStream_t);
@@ -2071,12 +2109,35 @@ __device__ __forceinline__ void argmax_partials(const float* pv, const int* pi, 
     best = mv;
     bidx = mi;
 }
-// LP: the log-probability instantiation (p.lp_s non-null); LP = false is the kernel without it, static LDS included
-template <bool LP>
+// Repetition processors: the ids that would complete an n-gram the history holds.  hist(i), i < L, is the row's history;
+// with n >= 2 and L >= n - 1, every position i with i + n - 1 < L whose n - 1 ids equal the last n - 1 names the id hist(i + n - 1).
+// One compare chain per position, the positions spread over the workgroup; SET: the ids' bits are set in `ban`, else cleared —
+// clearing walks the history the set was built from, so it costs what setting cost and no list of the set bits is kept.
+template <bool SET, typename H>
+__device__ __forceinline__ void repeat_ban_walk(unsigned* ban, int n, int L, H hist) {
+    if (n < 2 || L < n - 1) return;
+    const int s0 = L - (n - 1);
+    for (int i = threadIdx.x; i + n - 1 < L; i += blockDim.x) {
+        bool same = true;
+        for (int k = 0; k < n - 1 && same; ++k) same = hist(i + k) == hist(s0 + k);
+        if (same) {
+            const int t = hist(i + n - 1);
+            if (SET)
+                atomicOr(ban + (t >> 5), 1u << (t & 31));
+            else
+                atomicAnd(ban + (t >> 5), ~(1u << (t & 31)));
+        }
+    }
+}
+// LP: the log-probability instantiation (p.lp_s non-null); LP = false is the kernel without it, static LDS included.  RP: the
+// repetition processors' bookkeeping (p.rp_seen non-null), likewise.
+template <bool LP, bool RP = false>
 __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
     const int b = blockIdx.x;
     if (p.ts && b == 0 && threadIdx.x == 0) ts_put(p.ts, p.ts_id, 3);
     const int pos0 = p.emb_out ? p.pos[b] : 0;  // read before thread 0 advances it (the reductions below synchronise)
+    int rp_len = -1;  // RP: the row's history length before this id, -1 = the row stores nothing (read before thread 0 appends)
+    if constexpr (RP) rp_len = p.finished[b] ? -1 : p.n_tokens[b];
     if (p.host_progress && b == 0 && threadIdx.x == 0) {
         // finishes of EARLIER steps are complete (their launches ended); this step's may or may not be counted yet: a lower bound.
         // System-scope stores to pinned host memory: visible to the polling host without any stream synchronisation.
@@ -2182,17 +2243,48 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
             }
         }
     }
+    if constexpr (RP) {
+        // a row that stored its id: the history is out_tokens[b][0 .. rp_len) and the new id (every thread holds it; thread 0's store
+        // of it is not read here).  `ban` loses the bits of this step — the walk over the history without the new id that set them —
+        // and gains those of the next one.  n = 1 bans every id of the history: `ban` follows `seen` and nothing is ever cleared.
+        if (rp_len >= 0) {
+            const int n = p.rp_ctl->ngram;
+            unsigned* seen = p.rp_seen + (size_t)b * p.rp_words;
+            unsigned* ban = p.rp_ban + (size_t)b * p.rp_words;
+            const int* row = p.out_tokens + (size_t)b * p.out_stride;
+            const int L = rp_len;
+            auto hist = [&](int i) { return i < L ? row[i] : idx; };
+            if (threadIdx.x == 0) {
+                atomicOr(seen + (idx >> 5), 1u << (idx & 31));
+                if (n == 1) atomicOr(ban + (idx >> 5), 1u << (idx & 31));
+            }
+            repeat_ban_walk<false>(ban, n, L, hist);
+            __threadfence();
+            __syncthreads();  // every clear is done before the first set: an id banned at both steps stays banned
+            repeat_ban_walk<true>(ban, n, L + 1, hist);
+        }
+    }
     if (p.emb_out) {  // every thread holds idx: next step's embedding row (whisper.mojo:141-149)
         const float* te = p.emb_tok + (size_t)idx * p.d;
         const float* pe = p.emb_pos + (size_t)min(pos0 + (p.advance ? 1 : 0), p.max_pos) * p.d;
         for (int j = threadIdx.x; j < p.d; j += blockDim.x) p.emb_out[(size_t)b * p.d + j] = te[j] + pe[j];
     }
 }
-void launch_argmax_step(const ArgmaxParams& p, hipStream_t st) {
+int launch_argmax_step(const ArgmaxParams& p, hipStream_t st) {
+    if (p.rp_seen) {  // the sets' bookkeeping reads the row's history and rides the partials form: anything else is refused, not dropped
+        if (!p.out_tokens || !p.pval || !p.rp_ban || !p.rp_ctl || p.rp_words < repeat_words(p.V))
+            return launch_refuse("argmax_step: the repetition processors need the partials form, the id table, both sets and their control block");
+        if (p.lp_s)
+            hipLaunchKernelGGL((argmax_step_kernel<true, true>), dim3(p.B), dim3(256), 0, st, p);
+        else
+            hipLaunchKernelGGL((argmax_step_kernel<false, true>), dim3(p.B), dim3(256), 0, st, p);
+        return WM_LAUNCH_OK;
+    }
     if (p.lp_s && p.pval)
         hipLaunchKernelGGL(argmax_step_kernel<true>, dim3(p.B), dim3(256), 0, st, p);
     else
         hipLaunchKernelGGL(argmax_step_kernel<false>, dim3(p.B), dim3(p.pval ? 256 : 1024), 0, st, p);
+    return WM_LAUNCH_OK;
 }
 __global__ __launch_bounds__(1024) void argmax_plain_kernel(const float* t, int n, int* idx) {
     float best;
@@ -2277,6 +2369,28 @@ __global__ void init_tokens_rows_kernel(InitTokensParams p, RowPromptParams r) {
 }
 void launch_init_tokens_rows(const InitTokensParams& p, const RowPromptParams& r, hipStream_t st) {
     hipLaunchKernelGGL(init_tokens_rows_kernel, dim3((p.B + 255) / 256), dim3(256), 0, st, p, r);
+}
+// start of a pass with the repetition processors, one workgroup per row, behind the init-tokens launch: both sets
+// cleared, `seen` = the row's prompt, `ban` = what the prompt bans for the first generated id
+__global__ __launch_bounds__(256) void repeat_init_kernel(RepeatInitParams p) {
+    const int b = blockIdx.x;
+    if (b == 0 && threadIdx.x == 0) *p.ctl = RepeatCtl{p.penalty, p.ngram};
+    unsigned* seen = p.seen + (size_t)b * p.words;
+    unsigned* ban = p.ban + (size_t)b * p.words;
+    for (int i = threadIdx.x; i < p.words; i += blockDim.x) seen[i] = ban[i] = 0u;
+    __threadfence();
+    __syncthreads();
+    const int* row = p.out_tokens + (size_t)b * p.out_stride;
+    const int L = p.n_tokens[b];
+    for (int i = threadIdx.x; i < L; i += blockDim.x) {
+        const int t = row[i];
+        atomicOr(seen + (t >> 5), 1u << (t & 31));
+        if (p.ngram == 1) atomicOr(ban + (t >> 5), 1u << (t & 31));
+    }
+    repeat_ban_walk<true>(ban, p.ngram, L, [&](int i) { return row[i]; });
+}
+void launch_repeat_init(const RepeatInitParams& p, hipStream_t st) {
+    hipLaunchKernelGGL(repeat_init_kernel, dim3(p.B), dim3(256), 0, st, p);
 }
 // end of a per-row prefill: cache length Lmax for all, position len[b] + pos_delta per row
 __global__ void set_rows_step_kernel(StepCtl* ctl, int Lmax, int* pos, const int* len, int pos_delta, int B) {

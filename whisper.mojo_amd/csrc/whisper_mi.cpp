@@ -215,6 +215,12 @@ struct WinAsk {  // the windows a long-form timestamp pass decodes
     const int32_t* items;  // device [B][3]: (utterance, seek, frames) per row
     int n_real;            // rows [n_real, B) repeat row 0: no align rows, zero times
 };
+struct RepeatAsk {  // the repetition processors of a greedy pass, as wm_set_repeat_options left them when the pass was asked for
+    float penalty = 1.f;
+    int ngram = 0;
+    bool on() const { return penalty != 1.f || ngram > 0; }
+    bool operator==(const RepeatAsk& o) const { return penalty == o.penalty && ngram == o.ngram; }
+};
 // One pass: encoder, prefill, greedy loop (or the teacher-forced pass of `score`) for B utterances.  The entry points validate, fill
 // one of these and hand it to a driver (run_now / submit_slot); nothing in it is owned, it lives on the caller's stack.
 struct PassAsk {
@@ -231,6 +237,7 @@ struct PassAsk {
     LangAsk lang;
     const ScoreAsk* score = nullptr;
     const WinAsk* win = nullptr;  // with cols: a long-form window pass whose times are finished on the device
+    RepeatAsk rp;                 // filled by the drivers (run_now / submit_slot / the long-form scheduler) from the model's setting
 };
 static PassAsk lang_only_ask(const float* mel, int mel_on_device, int B, const int32_t* lang_ids, int n_lang, int sot) {
     PassAsk ask{mel, mel_on_device, B};
@@ -318,6 +325,7 @@ struct wm_model {
     bool pump_quit = false;
     // token-level timestamps: HF generation_config.alignment_heads, (layer, head) pairs in the caller's order; empty = off
     std::vector<int32_t> align_pairs;
+    RepeatAsk repeat;  // wm_set_repeat_options: what every greedy pass asked for from now on carries (a held submit keeps its own)
     struct AlignRef {  // where a slot's last timestamp pass left its alignment weights (wm_alignment_weights)
         wm_state* st = nullptr;
         int row0 = 0, rows = 0, gen = 0;
@@ -386,10 +394,11 @@ struct wm_state {
             bool operator==(const Cap& o) const { return buf == o.buf && L == o.L && n_prompt == o.n_prompt && pairs == o.pairs; }
         } cap;
         bool rows = false, lp = false;  // self-attention in the key-window form (rw.on); log-probabilities (lp.on)
+        bool rp = false;                // repetition processors (rp.on): the flag only — penalty and n-gram size are read on the device
         bool operator==(const StepKey& o) const {
             return eot == o.eot && ignore_eot == o.ignore_eot && rules.tb == o.rules.tb && rules.eos == o.rules.eos &&
                    rules.max_init == o.rules.max_init && rules.vocab == o.rules.vocab && shares_chip == o.shares_chip && cap == o.cap &&
-                   rows == o.rows && lp == o.lp;
+                   rows == o.rows && lp == o.lp && rp == o.rp;
         }
     };
     StepKey step, graph_step;
@@ -447,6 +456,14 @@ struct wm_state {
         DevBuf part_s, table, sum;
         std::vector<int32_t> n_prompt;  // [B] prompt length of each row of the pending pass
     } lp;
+    // repetition processors of the pending pass (on = the pass was asked for with wm_set_repeat_options in force): the
+    // rows' two bit sets [B][words] and the control block the kernels read (penalty, n-gram size).  Allocated by the first such pass.
+    struct Rp {
+        bool on = false;
+        RepeatAsk ask;
+        int words = 0;
+        DevBuf seen, ban, ctl;
+    } rp;
     // no-speech probe of the pending pass (on = wm_transcribe_lp_ns and its kin, always with lp.on): the residual rows
     // of the <|startoftranscript|> position [B][d], the probe's OWN sweep partials [B][npart] (the step's amax / lp_s partials and
     // the control block are not touched) and the results [B].  Part of the arena; runs outside the captured step graph.
@@ -976,7 +993,7 @@ extern "C" void wm_state_free(wm_state* s) {
                     &s->sc.slot, &s->sc.dst, &s->sc.len, &s->sc.ctx, &s->sc.lp, &s->sc.top, &s->sc.sum, &s->sc.avg,
                     &s->rw.table, &s->rw.len, &s->rw.key_lo, &s->lp.part_s, &s->lp.table, &s->lp.sum,
                     &s->ns.x, &s->ns.pmax, &s->ns.pidx, &s->ns.psum, &s->ns.prob, &s->ns.lse,
-                    &s->lg.x, &s->lg.ids, &s->lg.col, &s->lg.out, &s->lg.probs};
+                    &s->lg.x, &s->lg.ids, &s->lg.col, &s->lg.out, &s->lg.probs, &s->rp.seen, &s->rp.ban, &s->rp.ctl};
     for (DevBuf* b : bs) b->release();
     delete s;
 }
@@ -1584,6 +1601,27 @@ static void add_argmax_partials(DecLinearParams& p, wm_state* s, const DecView& 
         p.ts_s = lane_ptr<float>(s->ts_s, v, s->npart);
     }
     if (s->lp.on) p.lp_s = lane_ptr<float>(s->lp.part_s, v, s->npart);
+    if (s->rp.on) {  // repetition processors: the rows' sets, ahead of the mask and the ranges
+        p.rp_seen = lane_ptr<unsigned>(s->rp.seen, v, s->rp.words);
+        p.rp_ban = lane_ptr<unsigned>(s->rp.ban, v, s->rp.words);
+        p.rp_ctl = s->rp.ctl.as<RepeatCtl>();
+        p.rp_words = s->rp.words;
+    }
+}
+// start of a pass with the repetition processors, behind the lane's init-tokens launch
+static void repeat_init(wm_state* s, const DecView& v) {
+    RepeatInitParams r{};
+    r.seen = lane_ptr<unsigned>(s->rp.seen, v, s->rp.words);
+    r.ban = lane_ptr<unsigned>(s->rp.ban, v, s->rp.words);
+    r.words = s->rp.words;
+    r.B = v.nb;
+    r.ctl = s->rp.ctl.as<RepeatCtl>();
+    r.penalty = s->rp.ask.penalty;
+    r.ngram = s->rp.ask.ngram;
+    r.out_tokens = lane_ptr<int>(s->out_tokens, v, s->out_stride);
+    r.out_stride = s->out_stride;
+    r.n_tokens = lane_ptr<int>(s->n_tokens, v, 1);
+    launch_repeat_init(r, v.st);
 }
 // LN1 -> q | k,v appended to the cache   (layers.mojo:118-147)
 static DecLinearParams qkv_block(wm_model* m, wm_state* s, const DecView& v, int l, int P) {
@@ -1721,6 +1759,12 @@ static ArgmaxParams argmax_first_id(wm_model* m, wm_state* s, const DecView& v, 
         a.logprobs = lane_ptr<float>(s->lp.table, v, s->out_stride);
         a.lp_sum = lane_ptr<float>(s->lp.sum, v, 1);
     }
+    if (s->rp.on) {
+        a.rp_seen = lane_ptr<unsigned>(s->rp.seen, v, s->rp.words);
+        a.rp_ban = lane_ptr<unsigned>(s->rp.ban, v, s->rp.words);
+        a.rp_ctl = s->rp.ctl.as<RepeatCtl>();
+        a.rp_words = s->rp.words;
+    }
     a.eot = eot;
     a.ignore_eot = ignore_eot;
     return a;
@@ -1814,7 +1858,7 @@ static int loop_step(wm_model* m, wm_state* s, const DecView& v) {
     step.rules = &k.rules;  // (tb <= 0: off, as every reader of the rules checks)
     step.capture = true;
     WMCHK(decode_core(m, s, v, step));
-    launch_argmax_step(argmax_loop_step(m, s, v, k.eot, k.ignore_eot, &k.rules), v.st);
+    LCHK(launch_argmax_step(argmax_loop_step(m, s, v, k.eot, k.ignore_eot, &k.rules), v.st));
     return 0;
 }
 static void invalidate_step_graphs(wm_state* s) { s->graphs_valid = false; }  // the next greedy pass captures its step anew
@@ -2006,6 +2050,7 @@ static int prefill_rows(wm_model* m, wm_state* s, const DecView& v, InitTokensPa
     ip.tok_rows = s->tok_rows.as<int>();
     ip.pos_rows = s->pos_rows.as<int>();
     launch_init_tokens_rows(ip, RowPromptParams{rw.table.as<int>(), rw.len.as<int>(), rw.stride, Lmax, rw.key_lo.as<int>()}, v.st);
+    if (s->rp.on) repeat_init(s, v);  // each row's own prompt, a detected language included
     for (int t0 = 0; t0 < Lmax; t0 += wm_state::PREFILL_MAX) {
         const int P = std::min<int>(wm_state::PREFILL_MAX, Lmax - t0);
         if (t0) launch_set_step(v.ctl, t0, 1, nullptr, 0, nullptr, 0, v.nb, v.st);
@@ -2020,7 +2065,7 @@ static int prefill_rows(wm_model* m, wm_state* s, const DecView& v, InitTokensPa
         const int t_sot = Lmax - s->ns.n_init;
         if (s->ns.on && t_sot >= t0 && t_sot < t0 + P) ns_capture(m, s, v, (size_t)(t_sot - t0) * v.nb);
     }
-    launch_argmax_step(argmax_first_id(m, s, v, o->eot, o->ignore_eot, rp), v.st);
+    LCHK(launch_argmax_step(argmax_first_id(m, s, v, o->eot, o->ignore_eot, rp), v.st));
     trace_mark(v.st, "state %p lane %d prefill end", (void*)s, v.b0);
     launch_set_rows_step(v.ctl, Lmax, lane_ptr<int>(s->pos, v, 1), rw.len.as<int>(), o->pos_mode == WM_POS_REF ? -1 : 0, v.nb, v.st);
     return 0;
@@ -2051,6 +2096,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
     if (s->al.on) s->step.cap = wm_state::StepKey::Cap{s->al.cap.p, s->al.L, s->al.n_prompt, s->al.pairs};
     s->step.rows = s->rw.on;
     s->step.lp = s->lp.on;
+    s->step.rp = s->rp.on;
     const bool recapture = !s->graphs_valid || !(s->graph_step == s->step);
     const int first_pos = o->pos_mode == WM_POS_REF ? o->n_prompt - 1 : o->n_prompt;
     // logit masks (§8f rank 4): rebuilt only when the id lists change; always passed (all-zero = the reference's raw argmax)
@@ -2097,6 +2143,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
             WMCHK(prefill_rows(m, s, v, ip, o, rp));
         } else {
             launch_init_tokens(ip, v.st);
+            if (s->rp.on) repeat_init(s, v);
             // prefill (whisper.mojo:195, start_pos=0): the q_len = n_prompt causal block equals n_prompt single-token steps
             static const bool seq_prefill = wm_env("WM_SEQ_PREFILL") != nullptr;  // A/B: one pass per prompt position
             DecPass prompt;  // the last prompt position's logits, under the begin mask
@@ -2115,7 +2162,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
                     if (s->ns.on && i == o->n_prompt - s->ns.n_init) ns_capture(m, s, v, 0);
                 }
             }
-            launch_argmax_step(argmax_first_id(m, s, v, o->eot, o->ignore_eot, rp), v.st);  // :198-203
+            LCHK(launch_argmax_step(argmax_first_id(m, s, v, o->eot, o->ignore_eot, rp), v.st));  // :198-203
             trace_mark(v.st, "state %p lane %d prefill end", (void*)s, v.b0);
             // incremental steps: start_pos = current_len - 1 (reference, :217) or current_len (HF)
             launch_set_step(v.ctl, o->n_prompt, 1, lane_ptr<int>(s->pos, v, 1), first_pos, nullptr, 0, v.nb, v.st);
@@ -2275,6 +2322,14 @@ static int submit_on(wm_model* m, wm_state** slot, const PassAsk& ask) {
     }
     s->sc.on = false;
     s->sc.timed = s->sc.timed_al = false;
+    s->rp.on = ask.rp.on() && !score && !lang.only;  // greedy passes only: score / align are teacher-forced, detection reads raw logits
+    if (s->rp.on) {
+        s->rp.ask = ask.rp;
+        s->rp.words = repeat_words(c.vocab);
+        WMCHK(grow(s->rp.seen, (size_t)B * s->rp.words * 4));
+        WMCHK(grow(s->rp.ban, (size_t)B * s->rp.words * 4));
+        WMCHK(grow(s->rp.ctl, sizeof(RepeatCtl)));
+    }
     s->lp.on = lp;
     if (lp) {
         if (rows)
@@ -2454,6 +2509,7 @@ static bool pairs_with(const wm_model::Held& h, const PassAsk& b) {
     const wm_decode_opts &x = h.o, *o = b.opts;
     if (a.B != b.B || (a.cols != nullptr) != (b.cols != nullptr) || a.lp != b.lp || a.ns.token != b.ns.token || a.ns.n_init != b.ns.n_init)
         return false;
+    if (!(a.rp == b.rp)) return false;  // one control block per state: a pair shares (penalty, n-gram size)
     if (x.n_prompt != o->n_prompt || x.eot != o->eot || x.max_loop != o->max_loop || x.pos_mode != o->pos_mode || x.ignore_eot != o->ignore_eot ||
         x.n_suppress != (o->suppress_tokens ? o->n_suppress : 0) || x.n_begin_suppress != (o->begin_suppress_tokens ? o->n_begin_suppress : 0) ||
         x.timestamp_begin != o->timestamp_begin || x.no_timestamps_token != o->no_timestamps_token ||
@@ -2506,14 +2562,17 @@ static int slot0_ready(wm_model* m) {
 static int run_now(wm_model* m, PassAsk ask, const PassOut& out) {
     WMCHK(slot0_ready(m));
     ask.allow_poll = true;
+    ask.rp = m->repeat;
     WMCHK(submit_on(m, &m->cached, ask));
     record_pass(m, 0, ask, m->cached, 0, ask.B);
     return collect_pass(m, 0, out);
 }
 // Pipelined form of Whisper.transcribe for back-to-back batches: submit enqueues the encoder and the greedy loop on the slot's
 // stream and returns; the slot's wait blocks until its results are ready.  A pending slot is refused BEFORE a held submit is flushed.
-static int submit_slot(wm_model* m, int slot, const PassAsk& ask) {
+static int submit_slot(wm_model* m, int slot, const PassAsk& asked) {
     if (m->slot_ref[slot].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    PassAsk ask = asked;
+    ask.rp = m->repeat;  // the setting in force now: a held submit runs with it even if it changes before the partner arrives
     const int B = ask.B;
     // (a per-row, language or score / align pass is never held for a coalesce = 2 partner: it runs alone)
     const bool can_pair = !ask.rows && !ask.lang.ids && !ask.score && m->cfg.coalesce == 2 && B <= m->cfg.max_batch &&
@@ -2867,6 +2926,17 @@ extern "C" int wm_transcribe_wait_lang(wm_model* m, int slot, int32_t* tokens_ou
     out.lang_out = lang_out;
     out.lang_probs = lang_probs;
     return collect_slot(m, slot, PassKind::transcribe, out);
+}
+// ---- repetition processors -------------------------------------------------------------------------------------
+extern "C" int wm_set_repeat_options(wm_model* m, float repetition_penalty, int no_repeat_ngram_size) {
+    if (!m) return fail(WM_E_ARG, "bad argument");
+    if (!(repetition_penalty > 0.f) || !std::isfinite(repetition_penalty))
+        return fail(WM_E_ARG, "repetition_penalty must be a finite float > 0 (1 = off)");
+    if (no_repeat_ngram_size < 0 || no_repeat_ngram_size > REPEAT_NGRAM_MAX)
+        return fail(WM_E_ARG, "no_repeat_ngram_size %d outside [0, %d] (0 = off)", no_repeat_ngram_size, REPEAT_NGRAM_MAX);
+    m->repeat.penalty = repetition_penalty;
+    m->repeat.ngram = no_repeat_ngram_size;
+    return 0;
 }
 // ---- token-level timestamps ------------------------------------------------------------------------------------
 extern "C" int wm_set_alignment_heads(wm_model* m, const int32_t* layer_head_pairs, int n_pairs) {
@@ -4016,6 +4086,7 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
         PassAsk ask{L.win[k].as<float>(), 1, R, opts};
         ask.lp = quality;
         ask.ns = ns;
+        ask.rp = m->repeat;  // every window's pass sees its own decoder ids only, carried previous text included (HF's per-window generate)
         if (tt) {
             win_cols[k].resize(R);
             for (int r = 0; r < R; ++r) win_cols[k][r] = std::max(1, L.h_items[k][3 * r + 2] / 2);
@@ -5097,13 +5168,14 @@ extern "C" int wm_op_dec_linear_capmap(float* out, float* cap, const float* x, c
 // argmax_peek wire them: launch_dec_logits picks the kernel variant from (dtype, K, B), argmax_step reduces its partials.
 // logprob non-null: the LP instantiation of the same kernel variant, and the chosen ids' log-probabilities [B] (wm_op_logits_lp)
 static int op_logits(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
-                     const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
+                     const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype, const uint32_t* seen = nullptr,
+                     const uint32_t* ban = nullptr, float penalty = 1.f) {
     if (!logits || !ids || !x || !ln_g || !ln_b || !emb || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
     if (K != 128 && K != 384 && K != 512 && K != 768 && K != 1024) return fail(WM_E_ARG, "K must be 128, 384, 512, 768 or 1024 (the logits kernels' d_model)");
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
     if (ranges && (timestamp_begin <= 0 || timestamp_begin >= N)) return fail(WM_E_ARG, "ranges need 0 < timestamp_begin < N");
     TmpDev t;
-    t.bufs.reserve(20);
+    t.bufs.reserve(24);
     hipStream_t st = nullptr;
     const int ldo = (N + 3) / 4 * 4, npart = dec_logits_parts(N);  // the kernel stores whole float4 groups below ldo
     DevBuf &dx = t.add(), &g = t.add(), &be = t.add(), &w = t.add(), &mk = t.add(), &o = t.add(), &av = t.add(), &ai = t.add(),
@@ -5155,6 +5227,21 @@ static int op_logits(float* logits, int32_t* ids, float* logprob, const float* x
         p.ts_s = ts.as<float>();
     }
     if (logprob) p.lp_s = ls.as<float>();
+    if (seen) {  // wm_op_logits_processed: the rows' sets as given, the RP instantiation of the same kernel variant
+        DevBuf &ds = t.add(), &db = t.add(), &dc = t.add();
+        const size_t words = (size_t)repeat_words(N);
+        const RepeatCtl ctl{penalty, 0};
+        WMCHK(ds.alloc(B * words * 4));
+        WMCHK(db.alloc(B * words * 4));
+        WMCHK(dc.alloc(sizeof(ctl)));
+        HIPCHK(hipMemcpy(ds.p, seen, B * words * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(db.p, ban, B * words * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dc.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice));
+        p.rp_seen = ds.as<unsigned>();
+        p.rp_ban = db.as<unsigned>();
+        p.rp_ctl = dc.as<RepeatCtl>();
+        p.rp_words = (int)words;
+    }
     int lrc = 0;
     DISPATCH_DT(dtype, TT, lrc = launch_dec_logits<TT>(p, st));
     LCHK(lrc);
@@ -5195,6 +5282,96 @@ extern "C" int wm_op_logits_lp(float* logits, int32_t* ids, float* logprob, cons
                                const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
     if (!logprob) return fail(WM_E_ARG, "bad argument");
     return op_logits(logits, ids, logprob, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype);
+}
+// The same two launches with the repetition processors on given sets: seen / ban [B][ceil(N / 32)], bit (id & 31) of word
+// id >> 5.  logprob null: the instantiation without log-probabilities.
+extern "C" int wm_op_logits_processed(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b,
+                                      const float* emb, const float* mask, const int32_t* ranges, int timestamp_begin, const uint32_t* seen,
+                                      const uint32_t* ban, float penalty, int B, int N, int K, int dtype) {
+    if (!seen || !ban || !(penalty > 0.f)) return fail(WM_E_ARG, "bad argument");
+    return op_logits(logits, ids, logprob, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype, seen, ban, penalty);
+}
+// The sets' bookkeeping alone: repeat_init on each row's prompt tokens[b][0 .. prompt_len[b]), then one argmax launch per step that is
+// handed the row's next id of the table as its only candidate, so it appends exactly that id — rows end at n_ids[b] (a row past its
+// end is `finished` and does nothing).  seen / ban: [steps + 1][B][ceil(vocab / 32)], entry 0 after the init, entry s after step s.
+extern "C" int wm_op_repeat_sets(uint32_t* seen, uint32_t* ban, const int32_t* tokens, const int32_t* prompt_len, const int32_t* n_ids, int B,
+                                 int stride, int vocab, int ngram, int steps) {
+    if (!seen || !ban || !tokens || !prompt_len || !n_ids || B <= 0 || stride <= 0 || vocab <= 0 || steps < 0) return fail(WM_E_ARG, "bad argument");
+    if (ngram < 0 || ngram > REPEAT_NGRAM_MAX) return fail(WM_E_ARG, "no_repeat_ngram_size %d outside [0, %d]", ngram, REPEAT_NGRAM_MAX);
+    for (int b = 0; b < B; ++b) {
+        if (prompt_len[b] < 1 || prompt_len[b] > n_ids[b] || n_ids[b] > stride) return fail(WM_E_ARG, "row %d: need 1 <= prompt_len <= n_ids <= stride", b);
+        for (int i = 0; i < n_ids[b]; ++i)
+            if (tokens[(size_t)b * stride + i] < 0 || tokens[(size_t)b * stride + i] >= vocab) return fail(WM_E_ARG, "token id out of range");
+    }
+    TmpDev t;
+    t.bufs.reserve(12);
+    hipStream_t st = nullptr;
+    const size_t words = (size_t)repeat_words(vocab), set_bytes = (size_t)B * words * 4;
+    DevBuf &ds = t.add(), &db = t.add(), &dc = t.add(), &out = t.add(), &nt = t.add(), &fin = t.add(), &ctl = t.add(), &pv = t.add(), &pi = t.add(),
+           &nx = t.add(), &pos = t.add();
+    WMCHK(ds.alloc(set_bytes));
+    WMCHK(db.alloc(set_bytes));
+    WMCHK(dc.alloc(sizeof(RepeatCtl)));
+    WMCHK(out.alloc((size_t)B * stride * 4, true));
+    WMCHK(nt.alloc((size_t)B * 4));
+    WMCHK(fin.alloc((size_t)B * 4, true));
+    WMCHK(ctl.alloc(sizeof(StepCtl), true));
+    WMCHK(pv.alloc((size_t)B * 4, true));  // one partial per row: value 0, index = the id to append
+    WMCHK(pi.alloc((size_t)B * 4));
+    WMCHK(nx.alloc((size_t)B * 4));
+    WMCHK(pos.alloc((size_t)B * 4, true));
+    std::vector<int32_t> h_out((size_t)B * stride, 0), h_idx(B), h_fin(B);
+    for (int b = 0; b < B; ++b) std::copy(tokens + (size_t)b * stride, tokens + (size_t)b * stride + prompt_len[b], h_out.begin() + (size_t)b * stride);
+    HIPCHK(hipMemcpy(out.p, h_out.data(), h_out.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(nt.p, prompt_len, (size_t)B * 4, hipMemcpyHostToDevice));
+    RepeatInitParams r{};
+    r.seen = ds.as<unsigned>();
+    r.ban = db.as<unsigned>();
+    r.words = (int)words;
+    r.B = B;
+    r.ctl = dc.as<RepeatCtl>();
+    r.penalty = 1.f;
+    r.ngram = ngram;
+    r.out_tokens = out.as<int>();
+    r.out_stride = stride;
+    r.n_tokens = nt.as<int>();
+    launch_repeat_init(r, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(seen, ds.p, set_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ban, db.p, set_bytes, hipMemcpyDeviceToHost));
+    for (int s = 1; s <= steps; ++s) {
+        for (int b = 0; b < B; ++b) {
+            const int at = prompt_len[b] + s - 1;
+            h_fin[b] = at >= n_ids[b];
+            h_idx[b] = h_fin[b] ? 0 : tokens[(size_t)b * stride + at];
+        }
+        HIPCHK(hipMemcpy(pi.p, h_idx.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(fin.p, h_fin.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+        ArgmaxParams a{};
+        a.V = vocab;
+        a.B = B;
+        a.pval = pv.as<float>();
+        a.pidx = pi.as<int>();
+        a.npart = 1;
+        a.next = nx.as<int>();
+        a.out_tokens = out.as<int>();
+        a.out_stride = stride;
+        a.n_tokens = nt.as<int>();
+        a.finished = fin.as<int>();
+        a.ctl = ctl.as<StepCtl>();
+        a.pos = pos.as<int>();
+        a.eot = -1;
+        a.ignore_eot = 1;
+        a.rp_seen = ds.as<unsigned>();
+        a.rp_ban = db.as<unsigned>();
+        a.rp_ctl = dc.as<RepeatCtl>();
+        a.rp_words = (int)words;
+        LCHK(launch_argmax_step(a, st));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(seen + (size_t)s * B * words, ds.p, set_bytes, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ban + (size_t)s * B * words, db.p, set_bytes, hipMemcpyDeviceToHost));
+    }
+    return 0;
 }
 
 // The no-speech probe's launches on the kernel variant wm_op_logits_lp would pick for (dtype, K, B): the LP sweep with

@@ -128,6 +128,17 @@ __host__ __device__ inline void ts_next_ranges(TsState& st, const TsRules& r) { 
     }
 }
 
+// Repetition processors of the greedy loop (HF RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor).  Per
+// utterance two bit sets over the vocabulary, `words` 32-bit words each: `seen` = the ids of its decoder history (prompt + generated),
+// `ban` = the ids that would complete an n-gram the history already holds.  Set from the prompt by repeat_init, kept current by the
+// step's argmax launch, read by the logits epilogue.  The values live in device memory: one captured step serves any (penalty, ngram).
+struct RepeatCtl {
+    float penalty;  // 1 = off
+    int ngram;      // 0 = off
+};
+static const int REPEAT_NGRAM_MAX = 64;
+inline int repeat_words(int vocab) { return (vocab + 31) / 32; }
+
 struct DecLinearParams {
     const float* x;  // [B][ldx] fp32 activations
     int ldx;
@@ -183,6 +194,14 @@ struct DecLinearParams {
     // Row r stores to cap[(cap_map[r] * cap_nsel + cap_sel[h]) * 64 + (column % 64)]; ctl->len, cap_row_stride, cap_step0 and
     // cap_steps are not read
     const int* cap_map;
+    // dec_logits only — repetition processors (rp_seen null = off, needs rp_ban and rp_ctl): row b's logits at the ids of
+    // rp_seen[b] are multiplied (negative) or divided (else) by rp_ctl->penalty, then those of rp_ban[b] are -inf — before the logits
+    // store, the mask, the ranges and the log-prob sums.  Non-null selects the RP instantiation of the same kernel variant; null
+    // launches exactly the kernel, grid and LDS without it.
+    const unsigned* rp_seen;  // [B][rp_words]
+    const unsigned* rp_ban;
+    const RepeatCtl* rp_ctl;
+    int rp_words;
 };
 template <typename TW> int launch_dec_linear(const DecLinearParams& p, hipStream_t st);  // WM_LAUNCH_*
 bool dec_linear_supports_k(int K);  // K/32 k-steps must split into NW <= 16 waves x KPW <= 4 steps, or K = 3072 (the op hooks' answer)
@@ -293,8 +312,28 @@ struct ArgmaxParams {
     float* logprobs;    // [B][out_stride] or null: lp goes where the id goes in out_tokens (same guard: a finished row does not store)
     float* lp_sum;      // [B], with logprobs: running sum of the row's stored values
     float* lp_next;     // [B] or null: lp of next[b], stored unconditionally (op-level entry)
+    // repetition processors (rp_seen null = off, needs out_tokens): a row that stores its id also sets the id's bit in
+    // rp_seen[b], clears the bits rp_ban[b] held for this step and sets those of the next one from its history out_tokens[b]
+    unsigned* rp_seen;  // [B][rp_words]
+    unsigned* rp_ban;
+    const RepeatCtl* rp_ctl;
+    int rp_words;
 };
-void launch_argmax_step(const ArgmaxParams& p, hipStream_t st);
+int launch_argmax_step(const ArgmaxParams& p, hipStream_t st);  // WM_LAUNCH_*: refuses sets without the partials form or the id table
+// Start of a pass with the repetition processors, behind the init-tokens launch: writes ctl, clears both sets of the B rows, sets
+// `seen` from each row's prompt out_tokens[b][0 .. n_tokens[b]) and `ban` for the first generated id.
+struct RepeatInitParams {
+    unsigned* seen;  // [B][words]
+    unsigned* ban;
+    int words, B;
+    RepeatCtl* ctl;
+    float penalty;
+    int ngram;
+    const int* out_tokens;  // [B][out_stride]
+    int out_stride;
+    const int* n_tokens;  // [B]
+};
+void launch_repeat_init(const RepeatInitParams& p, hipStream_t st);
 struct InitTokensParams {
     int* out_tokens;
     int out_stride;

@@ -35,9 +35,12 @@ def log_mel(model, audios: Sequence[np.ndarray]) -> np.ndarray:
 
 
 def transcribe_audio(model, audios: Sequence[np.ndarray], prompt: Sequence[int] = PROMPT, eot: int = EOT,
-                     max_loop: int = MAX_LOOP, ignore_eot: bool = False, return_token_timestamps: bool = False):
+                     max_loop: int = MAX_LOOP, ignore_eot: bool = False, return_token_timestamps: bool = False,
+                     repetition_penalty=None, no_repeat_ngram_size=None):
     """PCM in, token ids out (the mel never leaves the GPU).  return_token_timestamps: (ids, times) with the time in seconds
-    each id was spoken (needs model.set_alignment_heads); the attention columns are cropped to each clip's real audio."""
+    each id was spoken (needs model.set_alignment_heads); the attention columns are cropped to each clip's real audio.
+    repetition_penalty / no_repeat_ngram_size: as Whisper.transcribe_batch."""
+    model._set_repeat(_lib.repeat_args(repetition_penalty, no_repeat_ngram_size))
     buf, n, stride = _pack(audios)
     p = np.asarray(prompt, np.int32)
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
@@ -106,12 +109,15 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
                                timestamps=(50364, 50363, 50), return_stats: bool = False, prompt_ids=None,
                                condition_on_prev_tokens: bool = False, prompt_condition_type: str = "first-segment",
                                prev_sot_token: int = 50361, logprob_threshold=None, no_speech_threshold=None, no_speech_token=None,
-                               detect_language=None, return_token_timestamps: bool = False):
+                               detect_language=None, return_token_timestamps: bool = False, repetition_penalty=None,
+                               no_repeat_ngram_size=None):
     """Sequential long-form transcription of 16 kHz PCM of any length (HF generate's long-form path), the long
-    log-mel never leaving the GPU.  return_token_timestamps: as Whisper.transcribe_long_form ("token_times" per recording,
-    "token_timestamps" per segment; not with the thresholds).  prompt_ids / condition_on_prev_tokens / prompt_condition_type / logprob_threshold /
+    log-mel never leaving the GPU.  repetition_penalty / no_repeat_ngram_size: as Whisper.transcribe_long_form.
+    return_token_timestamps: as Whisper.transcribe_long_form ("token_times" per recording, "token_timestamps" per segment; not with
+    the thresholds).  prompt_ids / condition_on_prev_tokens / prompt_condition_type / logprob_threshold /
     no_speech_threshold / no_speech_token / detect_language (then the detected ids [B] are returned as the last element): as
     Whisper.transcribe_long_form.  Returns per recording {"sequence": ids, "segments": [{"start", "end", "tokens"}]}."""
+    rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
     lo, _keep2 = _lib.long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token, logprob_threshold,
                                 no_speech_threshold, no_speech_token)
     if no_speech_token is not None and int(no_speech_token) >= model.config.vocab_size:
@@ -129,6 +135,7 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
     if buf.shape[1] < stride:
         buf = np.pad(buf, ((0, 0), (0, stride - buf.shape[1])))
     opts, _keep = model._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
+    model._set_repeat(rp)
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
     h = C.c_void_p()
     if tt:

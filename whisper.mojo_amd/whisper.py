@@ -207,6 +207,10 @@ class Whisper:
                                  tb, no_ts, max_init)
         return opts, (p, sup, bsup)
 
+    def _set_repeat(self, rp):
+        """wm_set_repeat_options with a call's (penalty, n): every greedy call sets them, so a call without the arguments runs with both off."""
+        _lib.check(_lib.lib().wm_set_repeat_options(self._h, rp[0], rp[1]))
+
     def set_alignment_heads(self, pairs: Sequence[Sequence[int]]):
         """(layer, head) pairs whose cross-attention aligns ids with audio (HF generation_config.alignment_heads, e.g.
         config.ALIGNMENT_HEADS_TINY); needed by return_token_timestamps.  An empty list switches the feature off."""
@@ -324,8 +328,14 @@ class Whisper:
                          begin_suppress_tokens: Sequence[int] = (), timestamps=None, return_token_timestamps: bool = False,
                          n_frames=None, prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False,
                          no_speech_token: Optional[int] = None, n_init: Optional[int] = None,
-                         detect_language: Optional[Sequence[int]] = None):
+                         detect_language: Optional[Sequence[int]] = None, repetition_penalty: Optional[float] = None,
+                         no_repeat_ngram_size: Optional[int] = None):
         """Batched Whisper.transcribe: one List[int] per utterance = prompt + generated ids (+ eot when hit).
+        repetition_penalty / no_repeat_ngram_size: HF generate's options of the same names, applied on the device at every
+        step to each row's own history (its prompt, then what it generated), before the suppress lists, the timestamp rules and
+        the log-prob sums: every id of the history has its logit multiplied (negative) or divided (else) by the penalty, once; every id
+        that would complete an n-gram the history already holds is -inf.  None / 1.0 / 0 = off.  They combine with every other option
+        here; no_speech_prob and detect_language read unprocessed logits, as in HF.  ValueError: penalty <= 0, n < 0, n > 64.
         detect_language: a list of language ids (tokenizer.language_ids) — HF generate's language=None: every utterance's
         language is detected on the device in the same pass and written over the second of its n_init initial ids (n_init: default
         the shared prompt's length, required with prompts=, >= 2); returns (ids, lang) or, with return_logprobs, (ids, (…the tuple
@@ -343,12 +353,14 @@ class Whisper:
         probability of that id under the raw logits at each row's <|startoftranscript|> position, prompt length - n_init; the second
         element becomes (token_logprobs, avg_logprob, no_speech_prob).  n_init: the number of initial ids (<|startoftranscript|>
         first); defaults to the shared prompt's length, required with prompts=."""
+        rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
         lang = None
         if detect_language is not None:
             lang = self._lang_args(detect_language, n_init, prompt, prompts, return_token_timestamps, no_speech_token, return_logprobs)
         ns = None if lang else self._ns_args(no_speech_token, n_init, prompt, prompts, return_logprobs)
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
+        self._set_repeat(rp)
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]
@@ -407,8 +419,11 @@ class Whisper:
                              condition_on_prev_tokens: bool = False, prompt_condition_type: str = "first-segment",
                              prev_sot_token: int = 50361, logprob_threshold: Optional[float] = None,
                              no_speech_threshold: Optional[float] = None, no_speech_token: Optional[int] = None,
-                             detect_language: Optional[Sequence[int]] = None, return_token_timestamps: bool = False):
+                             detect_language: Optional[Sequence[int]] = None, return_token_timestamps: bool = False,
+                             repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None):
         """Sequential long-form transcription (HF generate's long-form path, greedy).
+        repetition_penalty / no_repeat_ngram_size: as transcribe_batch.  Every window's pass sees that window's decoder
+        ids only — its prompt, a carried previous text included, then what it generates — as HF's per-window generate does.
         return_token_timestamps (HF generate's option on its long-form path; needs set_alignment_heads): every utterance
         also carries "token_times", a float64 array with the time in seconds of every id of "sequence", and every segment
         "token_timestamps", its slice of it.  Works with prompt_ids, condition_on_prev_tokens and detect_language; ValueError with
@@ -429,6 +444,7 @@ class Whisper:
         array's length).  timestamps: (timestamp_begin, no_timestamps_id, max_initial_timestamp_index | None), required.
         Returns per utterance {"sequence": ids, "segments": [{"start", "end", "tokens"}]} — HF's return_segments output with
         the padding-free sequences row; return_stats also returns {"windows", "stalled"}."""
+        rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
         lo, _keep3 = _lib.long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token, logprob_threshold,
                                     no_speech_threshold, no_speech_token)
         if no_speech_token is not None and int(no_speech_token) >= self.config.vocab_size:
@@ -474,13 +490,14 @@ class Whisper:
                 return self.transcribe_long_form(t.float().numpy(), n_frames, prompt, eot, max_loop, suppress_tokens,
                                                  begin_suppress_tokens, timestamps, return_stats, prompt_ids, condition_on_prev_tokens,
                                                  prompt_condition_type, prev_sot_token, logprob_threshold, no_speech_threshold, no_speech_token,
-                                                 detect_language, return_token_timestamps)
+                                                 detect_language, return_token_timestamps, repetition_penalty, no_repeat_ngram_size)
             keep = t.contiguous().float()
             torch.cuda.current_stream(keep.device).synchronize()  # the library reads it on its own HIP stream
             ptr, on_dev = C.c_void_p(keep.data_ptr()), 1
         B, T = int(keep.shape[0]), int(keep.shape[2])
         nf = self._frames_arg(n_frames, B)
         opts, _keep2 = self._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
+        self._set_repeat(rp)
         h = C.c_void_p()
         if tt:  # one entry point with or without the language list
             lang = np.zeros(B, np.int32)
@@ -515,20 +532,24 @@ class Whisper:
                           timestamps=None, return_token_timestamps: bool = False, n_frames=None,
                           prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False,
                           no_speech_token: Optional[int] = None, n_init: Optional[int] = None,
-                          detect_language: Optional[Sequence[int]] = None):
+                          detect_language: Optional[Sequence[int]] = None, repetition_penalty: Optional[float] = None,
+                          no_repeat_ngram_size: Optional[int] = None):
         """Pipelined form (wm_transcribe_submit): enqueue encoder + greedy loop for this batch on pipeline slot 0..7 and
         return at once; `transcribe_wait(slot)` collects the ids.  Submitting batch i+1 before waiting for batch i lets
         its encoder overlap batch i's decode.  return_token_timestamps / n_frames: as transcribe_batch; the matching
         transcribe_wait then returns (ids, times).  return_logprobs: as transcribe_batch; the matching transcribe_wait returns
         (ids, (token_logprobs, avg_logprob)).  no_speech_token / n_init: as transcribe_batch; the matching transcribe_wait returns
         (ids, (token_logprobs, avg_logprob, no_speech_prob)).  detect_language: as transcribe_batch; the matching transcribe_wait
-        returns what transcribe_batch returns."""
+        returns what transcribe_batch returns.  repetition_penalty / no_repeat_ngram_size: as transcribe_batch; the pass keeps the
+        values it was submitted with, and under coalesce = 2 it pairs only with a submit that carries the same values."""
+        rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
         lang = None
         if detect_language is not None:
             lang = self._lang_args(detect_language, n_init, prompt, prompts, return_token_timestamps, no_speech_token, return_logprobs)
         ns = None if lang else self._ns_args(no_speech_token, n_init, prompt, prompts, return_logprobs)
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
+        self._set_repeat(rp)
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]

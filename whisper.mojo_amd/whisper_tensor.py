@@ -233,11 +233,15 @@ def argmax(t) -> int:
     return int(idx.value)
 
 
-def logits_argmax(x, ln_g, ln_b, emb, dtype=DT_F32, mask=None, ranges=None, timestamp_begin: int = 0, return_logprobs: bool = False):
+def logits_argmax(x, ln_g, ln_b, emb, dtype=DT_F32, mask=None, ranges=None, timestamp_begin: int = 0, return_logprobs: bool = False,
+                  seen=None, ban=None, penalty: float = 1.0):
     """whisper.mojo:156-166 + the greedy argmax: (logits [B, N] = layer_norm(x)·embᵀ, ids [B]) on the decode step's logits kernel
     and fused argmax.  mask [N] additive (0 / -inf) on the argmax candidates; ranges [B, 4] = (text_lo, text_hi, ts_lo, ts_hi)
     with timestamp_begin > 0: the timestamp decision (wm_op_logits).  return_logprobs: (logits, ids, logprob [B]) from the log-prob
-    instantiation of the same kernels (wm_op_logits_lp): logits[id] - logsumexp over the candidates the mask and the ranges leave."""
+    instantiation of the same kernels (wm_op_logits_lp): logits[id] - logsumexp over the candidates the mask and the ranges leave.
+    seen / ban [B, ceil(N / 32)] uint32 (both or neither): the repetition-processor instantiation (wm_op_logits_processed, DESIGN
+    §29) — row b's logits at the ids of seen[b] times (negative) or over (else) `penalty`, those of ban[b] -inf, ahead of all of the
+    above; the returned logits are the processed ones."""
     f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
     x, emb, mask = f(x), f(emb), f(mask)
     g, b = f(ln_g).ravel(), f(ln_b).ravel()
@@ -255,6 +259,17 @@ def logits_argmax(x, ln_g, ln_b, emb, dtype=DT_F32, mask=None, ranges=None, time
     logits = np.zeros((B, N), np.float32)
     ids = np.zeros(B, np.int32)
     ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    if seen is not None or ban is not None:
+        words = (N + 31) // 32
+        sets = [np.ascontiguousarray(a, np.uint32) for a in (seen, ban) if a is not None]
+        if len(sets) != 2 or any(a.shape != (B, words) for a in sets):
+            raise ValueError("seen and ban must both be [B, ceil(N / 32)] uint32")
+        up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        lp = np.zeros(B, np.float32) if return_logprobs else None
+        _lib.check(_lib.lib().wm_op_logits_processed(_fp(logits), ip(ids), _fp(lp), _fp(x), _fp(g), _fp(b), _fp(emb),
+                                                     _fp(mask.ravel() if mask is not None else None), ip(rg), int(timestamp_begin),
+                                                     up(sets[0]), up(sets[1]), float(penalty), B, N, K, dtype))
+        return (logits, ids, lp) if return_logprobs else (logits, ids)
     if return_logprobs:
         lp = np.zeros(B, np.float32)
         _lib.check(_lib.lib().wm_op_logits_lp(_fp(logits), ip(ids), _fp(lp), _fp(x), _fp(g), _fp(b), _fp(emb),
@@ -390,3 +405,20 @@ def align_norm(weights, R, F, M=None):
     ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
     _lib.check(_lib.lib().wm_op_align_norm(_fp(M), _fp(w), n_tab, n_sel, L, T, ip(R), ip(F)))
     return M
+
+
+def repeat_sets(tokens, prompt_len, n_ids, vocab: int, ngram: int, steps: int):
+    """The repetition processors' bookkeeping alone (wm_op_repeat_sets): tokens [B, stride] int32, row b's prompt its first
+    prompt_len[b] ids and its history n_ids[b] ids in all -> (seen, ban), each [steps + 1, B, ceil(vocab / 32)] uint32: entry 0 behind the
+    init kernel, entry s behind the argmax launch that appended the row's id prompt_len[b] + s - 1 (a row past its end does nothing)."""
+    tok = np.ascontiguousarray(tokens, np.int32)
+    pl, nn = np.ascontiguousarray(prompt_len, np.int32).ravel(), np.ascontiguousarray(n_ids, np.int32).ravel()
+    if tok.ndim != 2 or pl.size != tok.shape[0] or nn.size != tok.shape[0]:
+        raise ValueError("tokens must be [B, stride], prompt_len and n_ids [B]")
+    B, stride = tok.shape
+    words = (vocab + 31) // 32
+    seen = np.zeros((steps + 1, B, words), np.uint32)
+    ban = np.zeros((steps + 1, B, words), np.uint32)
+    ip, up = (lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32)))
+    _lib.check(_lib.lib().wm_op_repeat_sets(up(seen), up(ban), ip(tok), ip(pl), ip(nn), B, stride, int(vocab), int(ngram), int(steps)))
+    return seen, ban
