@@ -514,6 +514,46 @@ void wm_long_result_free(wm_long_result* r);
 int wm_op_long_segments(const int32_t* ids, int n, int timestamp_begin, int64_t seek, int seek_num_frames, wm_segment* segs,
                         int32_t* n_segs, int32_t* advance);
 
+/* ---- chunked long-form transcription ------------------------------------------------------------------------
+ * HF's ASR pipeline with chunk_length_s / stride_length_s / batch_size: every recording is cut into overlapping chunks
+ * (pipelines/automatic_speech_recognition.py::chunk_iter), every chunk is decoded on its own — its own 30 s log-mel with its own clamp
+ * max, the decode options applying per chunk — in passes of up to max_batch rows that mix the chunks of all recordings, and each
+ * recording's id lists are stitched on the device as tokenization_whisper._find_longest_common_sequence(sequences) stitches them
+ * after _decode_asr's strip: every id >= first_special (50257 for the multilingual vocabulary: eot, language, task, timestamp ids) is
+ * dropped, a chunk that keeps no id is no operand.  Unlike wm_transcribe_long, a single recording fills whole batches.
+ *
+ * wm_chunk_table (host only): HF's list of chunks for R recordings of n_samples[r] samples, one row of six ints per chunk in
+ * recording order: (recording, start, len, stride_left_eff, stride_right_eff, is_last).  Step chunk_len - stride_left - stride_right;
+ * the first chunk of a recording has left stride 0 and the last right stride 0; a chunk is kept only if len > stride_left_eff; the walk
+ * ends at the first chunk with start + chunk_len >= n_samples[r].  table NULL (cap 0): only n_chunks is written.  WM_E_ARG: chunk_len
+ * <= stride_left + stride_right (HF raises for <, and for = in range()), chunk_len > window when window > 0 (the model's window in
+ * samples, 160 · 2 · n_audio_ctx); WM_E_SIZE: cap rows do not hold the table.
+ *
+ * wm_transcribe_chunked: pcm [R][stride] fp32 at 16 kHz, host or (pcm_on_device) device; n_samples[r] <= stride.  opts: as
+ * wm_transcribe, applied to every chunk; lang_ids non-NULL: every pass is a wm_transcribe_submit_lang pass (n_init = opts->n_prompt,
+ * the detected id sits in each chunk's ids); wm_set_repeat_options applies as always.  merged [R][cap], merged_len [R]: the stitched
+ * ids; cap >= (most chunks of one recording) · (n_prompt + 1 + max_loop), else WM_E_SIZE.  chunk_ids [n_chunks][n_prompt + 1 +
+ * max_loop] with chunk_n [n_chunks] (both or neither): every chunk's own ids, in table order, exactly what wm_transcribe_pcm of that
+ * chunk's samples returns.  n_passes (or NULL): passes submitted.  Between the upload of the PCM and the download of the merged ids
+ * only the chunk table and its recording offsets cross the bus: chunk_gather_kernel cuts the chunks on the device, each pass's ids go from its decode state
+ * into one packed device table (wm_transcribe_wait_device's rows), chunk_merge_kernel reads that table.  Uses the caller's slots 0..1
+ * (0..3 with coalesce = 2): WM_E_STATE while one of them holds a pass; a held coalesce submit is flushed first.  The scratch is
+ * released before the call returns.  Not here: token timestamps in chunked mode, HF's split at a language change. */
+int wm_chunk_table(const int32_t* n_samples, int R, int chunk_len, int stride_left, int stride_right, int window, int32_t* table, int cap,
+                   int32_t* n_chunks);
+int wm_transcribe_chunked(wm_model* m, const float* pcm, int pcm_on_device, const int32_t* n_samples, int R, int stride, int chunk_len,
+                          int stride_left, int stride_right, const wm_decode_opts* opts, const int32_t* lang_ids, int n_lang, int first_special,
+                          int32_t* merged, int32_t* merged_len, int cap, int32_t* chunk_ids, int32_t* chunk_n, int32_t* n_passes);
+/* Known-answer tests.  wm_op_chunk_gather: chunk_gather_kernel alone — out [n][N] (in and out: a cell the kernel does not store keeps
+ * the caller's value) = pcm [R][T_max] cut at items [n][3] = (recording, start, len), zero-padded past len.  WM_E_ARG: an item that
+ * leaves its recording or the row.
+ * wm_op_chunk_merge: chunk_merge_kernel alone — ids [n_rows][stride] with lens [n_rows]; recording r owns rows [rec_off[r],
+ * rec_off[r + 1]) (rec_off [n_rec + 1]); merged [n_rec][cap] (in and out), merged_len [n_rec].  stride <= 2048; cap must hold every
+ * recording's ids.  One launch for all recordings. */
+int wm_op_chunk_gather(float* out, const float* pcm, int R, int64_t T_max, const int32_t* items, int n, int N);
+int wm_op_chunk_merge(int32_t* merged, int32_t* merged_len, const int32_t* ids, const int32_t* lens, const int32_t* rec_off, int n_rows,
+                      int n_rec, int stride, int cap, int first_special);
+
 /* ---- op-level entry points (host pointers; known-answer tests only) ------------------------------------------
  * Same argument meaning as the reference ops: out-param first, caller-allocated. */
 /* matmul(C, A, B, bias)  whisper_tensor.mojo:151-246 : C[M,N] = A[M,K]·B[N,K]ᵀ (+bias[N], may be NULL).

@@ -430,6 +430,46 @@ public:
         check(rc);
         return out;
     }
+    // chunked long-form transcription (HF's ASR pipeline with chunk_length_s / stride_length_s): PCM [R][stride] at
+    // 16 kHz on the host, or (pcm_on_device) on the model's GPU, n_samples per recording; chunk_len / stride_left / stride_right in samples (strides < 0: chunk_len / 6).  Every chunk is
+    // decoded on its own in passes of max_batch rows; `sequence` is the recording's stitched ids, `chunks` (want_chunks) every chunk
+    // with its own ids.  lang_ids: every chunk's language is detected in its pass.
+    struct Chunk {
+        int32_t start, len, stride_left, stride_right;  // samples
+        std::vector<int> tokens;
+    };
+    struct ChunkedResult {
+        std::vector<int> sequence;
+        std::vector<Chunk> chunks;
+    };
+    std::vector<ChunkedResult> transcribe_chunked(const float* pcm, const std::vector<int32_t>& n_samples, int stride, int chunk_len = 480000,
+                                                  int stride_left = -1, int stride_right = -1, bool want_chunks = false, int max_loop = MAX_LOOP,
+                                                  const std::vector<int32_t>& lang_ids = {}, int32_t first_special = 50257,
+                                                  bool pcm_on_device = false) const {
+        need_model();
+        wm_decode_opts o = opts(max_loop, false);
+        const int R = (int)n_samples.size(), sl = stride_left < 0 ? chunk_len / 6 : stride_left, sr = stride_right < 0 ? chunk_len / 6 : stride_right;
+        int32_t n = 0;
+        check(wm_chunk_table(n_samples.data(), R, chunk_len, sl, sr, 0, nullptr, 0, &n));
+        std::vector<int32_t> tab((size_t)(n > 0 ? n : 1) * 6);
+        check(wm_chunk_table(n_samples.data(), R, chunk_len, sl, sr, 0, tab.data(), n, &n));
+        std::vector<int> per(R, 0);
+        for (int k = 0; k < n; ++k) ++per[tab[(size_t)k * 6]];
+        const int total = o.n_prompt + 1 + max_loop;
+        int cap = 1;
+        for (int v : per) cap = v * total > cap ? v * total : cap;
+        std::vector<int32_t> merged((size_t)R * cap), mlen(R), cids(want_chunks ? (size_t)(n > 0 ? n : 1) * total : 0), cn(want_chunks ? (n > 0 ? n : 1) : 0);
+        check(wm_transcribe_chunked(model_, pcm, pcm_on_device ? 1 : 0, n_samples.data(), R, stride, chunk_len, sl, sr, &o, lang_ids.empty() ? nullptr : lang_ids.data(),
+                                    (int)lang_ids.size(), first_special, merged.data(), mlen.data(), cap, want_chunks ? cids.data() : nullptr,
+                                    want_chunks ? cn.data() : nullptr, nullptr));
+        std::vector<ChunkedResult> out(R);
+        for (int r = 0; r < R; ++r) out[r].sequence.assign(merged.begin() + (size_t)r * cap, merged.begin() + (size_t)r * cap + mlen[r]);
+        for (int k = 0; want_chunks && k < n; ++k) {
+            const int32_t* t = &tab[(size_t)k * 6];
+            out[t[0]].chunks.push_back({t[1], t[2], t[3], t[4], std::vector<int>(cids.begin() + (size_t)k * total, cids.begin() + (size_t)k * total + cn[k])});
+        }
+        return out;
+    }
     // other prompts / stop ids (reduced test models have small vocabularies); defaults are the reference's
     void set_prompt(const std::vector<int32_t>& prompt, int32_t eot) {
         prompt_ = prompt;

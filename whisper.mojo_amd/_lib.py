@@ -38,6 +38,7 @@ SYMBOLS = [
     "wm_op_dec_linear_long",
     "wm_transcribe_long_tt", "wm_transcribe_long_pcm_tt", "wm_long_result_token_times", "wm_op_long_token_times",
     "wm_set_repeat_options", "wm_op_logits_processed", "wm_op_repeat_sets",
+    "wm_chunk_table", "wm_transcribe_chunked", "wm_op_chunk_gather", "wm_op_chunk_merge",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -306,8 +307,86 @@ def lib():
     L.wm_set_repeat_options.argtypes = [vp, C.c_float, C.c_int]
     L.wm_op_logits_processed.argtypes = [fp, ip, fp, fp, fp, fp, fp, fp, ip, C.c_int, up, up, C.c_float] + [C.c_int] * 4
     L.wm_op_repeat_sets.argtypes = [up, up, ip, ip, ip] + [C.c_int] * 5
+    L.wm_chunk_table.argtypes = [ip] + [C.c_int] * 5 + [ip, C.c_int, ip]
+    L.wm_transcribe_chunked.argtypes = [vp, vp, C.c_int, ip] + [C.c_int] * 5 + [C.POINTER(WmDecodeOpts), ip, C.c_int, C.c_int, ip, ip, C.c_int,
+                                                                               ip, ip, ip]
+    L.wm_op_chunk_gather.argtypes = [fp, fp, C.c_int, C.c_int64, ip, C.c_int, C.c_int]
+    L.wm_op_chunk_merge.argtypes = [ip] * 5 + [C.c_int] * 5
     _lib = L
     return L
+
+
+FIRST_SPECIAL = 50257  # the multilingual vocabulary's first special id (<|endoftext|>): what the chunked stitch strips from
+CHUNK_MERGE_MAX_IDS = 2048  # wm_kernels.h CHUNK_MERGE_MAX_IDS
+
+
+def chunk_strides(chunk_length_s, stride_length_s, sampling_rate=16000):
+    """HF AutomaticSpeechRecognitionPipeline.preprocess' seconds -> samples (Whisper: align_to = 1): (chunk_len, stride_left,
+    stride_right).  stride_length_s: None (chunk_length_s / 6 on both sides), one number, or (left, right)."""
+    if stride_length_s is None:
+        stride_length_s = chunk_length_s / 6
+    if isinstance(stride_length_s, (int, float)):
+        stride_length_s = [stride_length_s, stride_length_s]
+    if len(stride_length_s) != 2:
+        raise ValueError("stride_length_s is None, one number or (left, right)")
+    return (int(round(chunk_length_s * sampling_rate)), int(round(stride_length_s[0] * sampling_rate)),
+            int(round(stride_length_s[1] * sampling_rate)))
+
+
+def chunk_table(n_samples, chunk_len=480000, stride_left=None, stride_right=None, window=0):
+    """wm_chunk_table (host only): HF chunk_iter's chunks of recordings of n_samples[r] samples -> int32 array [n, 6] of
+    (recording, start, len, stride_left_eff, stride_right_eff, is_last).  The strides default to chunk_len // 6.  window > 0: the
+    model's window in samples, chunk_len beyond it is refused.  WhisperMiError (WM_E_ARG) where HF raises."""
+    import numpy as np
+    ns = np.ascontiguousarray(np.asarray(n_samples, np.int64).reshape(-1))
+    if ns.size < 1 or ns.min() < 0 or ns.max() >= 2 ** 31:
+        raise ValueError("n_samples needs one length in [0, 2^31) per recording")
+    ns = ns.astype(np.int32)
+    sl = chunk_len // 6 if stride_left is None else int(stride_left)
+    sr = chunk_len // 6 if stride_right is None else int(stride_right)
+    ip = C.POINTER(C.c_int32)
+    n = C.c_int32()
+    check(lib().wm_chunk_table(ns.ctypes.data_as(ip), ns.size, int(chunk_len), sl, sr, int(window), None, 0, C.byref(n)))
+    tab = np.zeros((max(1, n.value), 6), np.int32)
+    check(lib().wm_chunk_table(ns.ctypes.data_as(ip), ns.size, int(chunk_len), sl, sr, int(window), tab.ctypes.data_as(ip), n.value, C.byref(n)))
+    return tab[:n.value]
+
+
+def op_chunk_gather(pcm, items, N, fill=0.0):
+    """wm_op_chunk_gather: pcm [R, T_max] float32, items [(recording, start, len)] -> [n, N]; the output starts as `fill` everywhere, so
+    a cell the kernel does not store shows."""
+    import numpy as np
+    p = np.ascontiguousarray(pcm, np.float32)
+    it = np.ascontiguousarray(np.asarray(items, np.int32).reshape(-1, 3))
+    out = np.full((it.shape[0], int(N)), fill, np.float32)
+    check(lib().wm_op_chunk_gather(out.ctypes.data_as(C.POINTER(C.c_float)), p.ctypes.data_as(C.POINTER(C.c_float)), p.shape[0], p.shape[1],
+                                   it.ctypes.data_as(C.POINTER(C.c_int32)), it.shape[0], int(N)))
+    return out
+
+
+def op_chunk_merge(recordings, first_special=FIRST_SPECIAL, fill=-7):
+    """wm_op_chunk_merge: recordings = one list of id lists (chunks, in order) per recording -> one merged id list per recording, all
+    recordings in one launch.  Cells of the output past each length must still hold `fill` (AssertionError)."""
+    import numpy as np
+    rows = [np.asarray(ch, np.int32).reshape(-1) for rec in recordings for ch in rec]
+    off = np.zeros(len(recordings) + 1, np.int32)
+    off[1:] = np.cumsum([len(rec) for rec in recordings])
+    if not rows:
+        rows = [np.zeros(0, np.int32)]  # (the library wants one row; no recording owns it)
+    stride = max(1, max(r.size for r in rows))
+    ids = np.zeros((len(rows), stride), np.int32)
+    lens = np.asarray([r.size for r in rows], np.int32)
+    for k, r in enumerate(rows):
+        ids[k, :r.size] = r
+    cap = max(1, max([sum(len(ch) for ch in rec) for rec in recordings] + [1]))
+    merged = np.full((len(recordings), cap + 8), fill, np.int32)
+    mlen = np.zeros(len(recordings), np.int32)
+    ip = C.POINTER(C.c_int32)
+    check(lib().wm_op_chunk_merge(merged.ctypes.data_as(ip), mlen.ctypes.data_as(ip), ids.ctypes.data_as(ip), lens.ctypes.data_as(ip),
+                                  off.ctypes.data_as(ip), len(rows), len(recordings), stride, cap + 8, int(first_special)))
+    for r in range(len(recordings)):
+        assert (merged[r, mlen[r]:] == fill).all(), f"recording {r}: the kernel stored past its length"
+    return [merged[r, :mlen[r]].tolist() for r in range(len(recordings))]
 
 
 REPEAT_NGRAM_MAX = 64  # wm_kernels.h REPEAT_NGRAM_MAX

@@ -8,6 +8,8 @@
 // Long audio (wm_log_mel_long) runs the first three over chunks of frames at a frame offset t0 into a
 // [B][n_mels][F] log-mel, then mel_max_partial_kernel + mel_norm_long_kernel: a two-stage per-utterance max over the whole
 // spectrogram (no atomics) and a wide clamp / rescale pass.  window_gather_kernel cuts the encoder windows out of it.
+// Chunked long-form: chunk_gather_kernel cuts overlapping chunks of PCM out of long recordings, one 30 s front-end row
+// each, so that every chunk gets its own clamp max as HF's feature extractor gives it.
 #include "wm_kernels.h"
 
 namespace wm {
@@ -138,6 +140,24 @@ __global__ __launch_bounds__(256) void window_gather_kernel(const float* __restr
 }
 void launch_window_gather(const float* mel, const int* items, float* out, int rows, int n_mels, int F, int W, hipStream_t st) {
     hipLaunchKernelGGL(window_gather_kernel, dim3((W + 255) / 256, n_mels, rows), dim3(256), 0, st, mel, items, out, n_mels, F, W);
+}
+
+// Chunks of chunked long-form transcription: out[r][i] = pcm[rec][start + i] for i < len, 0 beyond, for
+// items[row0 + r] = (rec, start, len, ...) with `item_stride` ints per item.  pcm [R][T_max], out [rows][N].  The host guarantees
+// start + len <= T_max and len <= N; the kernel clamps both again.  Offsets are formed in size_t: R · T_max passes 2^31 for an hour.
+__global__ __launch_bounds__(256) void chunk_gather_kernel(const float* __restrict__ pcm, const int* __restrict__ items, int item_stride, int row0,
+                                                           float* __restrict__ out, size_t T_max, int N) {
+    const int r = blockIdx.y;
+    const int* it = items + (size_t)(row0 + r) * item_stride;
+    const size_t rec = (size_t)it[0], start = (size_t)it[1];
+    const int len = min(it[2], N);
+    const float* src = pcm + rec * T_max;
+    float* dst = out + (size_t)r * N;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) dst[i] = (i < len && start + i < T_max) ? src[start + i] : 0.f;
+}
+void launch_chunk_gather(const float* pcm, const int* items, int item_stride, int row0, float* out, int rows, size_t T_max, int N, hipStream_t st) {
+    const int gx = std::max(1, std::min(256, (N + 1023) / 1024));
+    hipLaunchKernelGGL(chunk_gather_kernel, dim3(gx, rows), dim3(256), 0, st, pcm, items, item_stride, row0, out, T_max, N);
 }
 
 }  // namespace wm

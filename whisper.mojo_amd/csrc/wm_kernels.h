@@ -498,6 +498,14 @@ void launch_mel_log(const float* spec, const float* fb, const int* band, float* 
 void launch_mel_norm_long(float* logmel, float* part, int B, size_t n, hipStream_t st);
 void launch_window_gather(const float* mel, const int* items, float* out, int rows, int n_mels, int F, int W, hipStream_t st);
 void launch_mel_norm(const float* logmel, float* out, int B, int n, hipStream_t st);
+// chunked long-form: rows [row0, row0 + rows) of the item table (item_stride ints each: recording, start, len, ...) cut
+// out of pcm [R][T_max] into out [rows][N], zero-padded past len
+void launch_chunk_gather(const float* pcm, const int* items, int item_stride, int row0, float* out, int rows, size_t T_max, int N, hipStream_t st);
+// the stitch (kernels_chunked.hip): packed rows [n][1 + stride] = (count, ids), recording r owning rows [rec_off[r], rec_off[r + 1]) ->
+// merged [n_rec][cap], merged_len [n_rec].  One workgroup per recording; LDS 2 · stride ints + 3 KB.  WM_LAUNCH_*
+static const int CHUNK_MERGE_MAX_IDS = 2048;
+int launch_chunk_merge(const int* rows, const int* rec_off, int n_rec, int stride, int first_special, int* merged, int* merged_len, int cap,
+                       hipStream_t st);
 
 // ---- small ops for the op-level C-ABI ----------------------------------------------------------------------------
 void launch_gelu(float* t, size_t n, int mode, hipStream_t st);

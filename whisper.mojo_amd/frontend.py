@@ -162,6 +162,90 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
     return (out, stats) if return_stats else out
 
 
+def transcribe_audio_chunked(model, audios, chunk_length_s: float = 30.0, stride_length_s=None, return_chunks: bool = False,
+                             prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP, suppress_tokens: Sequence[int] = (),
+                             begin_suppress_tokens: Sequence[int] = (), timestamps=None, detect_language=None, repetition_penalty=None,
+                             no_repeat_ngram_size=None, first_special: int = _lib.FIRST_SPECIAL, return_stats: bool = False, n_samples=None):
+    """Chunked long-form transcription of 16 kHz PCM of any length (HF's ASR pipeline with chunk_length_s / stride_length_s /
+    batch_size = max_batch): every recording is cut into overlapping chunks (HF chunk_iter), the chunks of all recordings
+    are decoded on their own in passes of up to max_batch rows, two passes in flight, and each recording's id lists are stitched on
+    the GPU (HF _find_longest_common_sequence after the strip of every id >= first_special).  One recording fills whole batches,
+    which transcribe_audio_long_form's sequential algorithm cannot.
+    audios: one 1-D float array or a list of them, or PCM that already is on the model's GPU: a torch float32 CUDA tensor [R, stride]
+    (or [stride]) with n_samples, the valid samples per row (None: the whole row) — it is not copied.  stride_length_s: None (chunk_length_s / 6), seconds, or (left, right).
+    prompt / eot / max_loop / suppress_tokens / begin_suppress_tokens / timestamps / detect_language / repetition_penalty /
+    no_repeat_ngram_size: as Whisper.transcribe_batch, applied to every chunk (HF's generate_kwargs); with detect_language the
+    detected id sits in each chunk's ids.  The no-timestamps prompt is the caller's choice; timestamp ids a chunk does emit are dropped
+    with the other specials.
+    Returns per recording {"sequence": merged ids} and, with return_chunks, "chunks": [(start_s, len_s, stride_left_s,
+    stride_right_s, ids)] with the ids exactly as transcribe_audio gives them for that chunk's samples alone.  A single array in, a
+    single dict out.  return_stats: also {"chunks", "passes"}.  tokenizer.decode_text(sequence) gives the text."""
+    dev = None
+    if not isinstance(audios, (np.ndarray, list, tuple)):
+        import torch
+        if isinstance(audios, torch.Tensor) and audios.is_cuda:
+            dev = audios
+    if dev is not None:
+        single = dev.dim() == 1
+        dev = (dev[None] if single else dev).contiguous().float()
+        if dev.dim() != 2 or dev.shape[0] < 1 or dev.shape[1] < 1:
+            raise ValueError("device PCM must be [R, stride] or [stride]")
+        n = np.full(dev.shape[0], dev.shape[1], np.int64) if n_samples is None else np.asarray(n_samples, np.int64).reshape(-1)
+        if n.size != dev.shape[0] or n.min() < 0 or n.max() > dev.shape[1]:
+            raise ValueError(f"n_samples needs one length in [0, {dev.shape[1]}] per row ({dev.shape[0]})")
+        n, stride, n_rec = n.astype(np.int32), int(dev.shape[1]), int(dev.shape[0])
+        import torch
+        torch.cuda.current_stream(dev.device).synchronize()  # the library reads it on its own HIP stream
+        pcm_ptr, on_dev = C.c_void_p(dev.data_ptr()), 1
+    else:
+        if n_samples is not None:
+            raise ValueError("n_samples goes with device PCM; host arrays carry their own lengths")
+        single = isinstance(audios, np.ndarray) and audios.ndim == 1
+        if single:
+            audios = [audios]
+        audios = [np.asarray(a, np.float32).reshape(-1) for a in audios]
+        if not audios:
+            raise ValueError("no recording")
+        buf, n, stride = _pack(audios)
+        n_rec = len(audios)
+        pcm_ptr, on_dev = buf.ctypes.data_as(C.c_void_p), 0
+    rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
+    lang_list = None
+    if detect_language is not None:
+        lang_list = _lib.lang_args(detect_language, model.config.vocab_size)
+        if len(prompt) < 2:
+            raise ValueError("detect_language needs at least two initial ids (<|startoftranscript|> and the language slot)")
+    if not 0 < int(first_special) <= model.config.vocab_size:
+        raise ValueError(f"first_special must lie in (0, vocab = {model.config.vocab_size}]")
+    chunk_len, sl, sr = _lib.chunk_strides(chunk_length_s, stride_length_s, SAMPLING_RATE)
+    tab = _lib.chunk_table(n, chunk_len, sl, sr, window=model.config.n_frames * HOP)
+    if model._h is None:
+        raise _lib.WhisperMiError("model not loaded")
+    opts, _keep = model._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
+    model._set_repeat(rp)
+    R, total = n_rec, len(prompt) + 1 + max_loop
+    per_rec = np.bincount(tab[:, 0], minlength=R) if len(tab) else np.zeros(R, np.int64)
+    cap = max(1, int(per_rec.max()) * total)
+    merged, mlen = np.zeros((R, cap), np.int32), np.zeros(R, np.int32)
+    cids = np.zeros((max(1, len(tab)), total), np.int32) if return_chunks else None
+    cn = np.zeros(max(1, len(tab)), np.int32) if return_chunks else None
+    passes = C.c_int32()
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    _lib.check(_lib.lib().wm_transcribe_chunked(
+        model._h, pcm_ptr, on_dev, n.ctypes.data_as(ip), R, stride, chunk_len, sl, sr, C.byref(opts),
+        lang_list.ctypes.data_as(ip) if lang_list is not None else None, lang_list.size if lang_list is not None else 0, int(first_special),
+        merged.ctypes.data_as(ip), mlen.ctypes.data_as(ip), cap, cids.ctypes.data_as(ip) if return_chunks else None,
+        cn.ctypes.data_as(ip) if return_chunks else None, C.byref(passes)))
+    out = [{"sequence": merged[r, :mlen[r]].tolist()} for r in range(R)]
+    if return_chunks:
+        for r in range(R):
+            out[r]["chunks"] = []
+        for k, (r, start, ln, esl, esr, _last) in enumerate(tab.tolist()):
+            out[r]["chunks"].append((start / SAMPLING_RATE, ln / SAMPLING_RATE, esl / SAMPLING_RATE, esr / SAMPLING_RATE, cids[k, :cn[k]].tolist()))
+    res = out[0] if single else out
+    return (res, {"chunks": int(len(tab)), "passes": int(passes.value)}) if return_stats else res
+
+
 # ---- decoding features the reference lacks (SURVEY §8f rank 4), host-level over the same C-ABI -----------------------
 HOP = 160  # samples per mel frame (WhisperFeatureExtractor hop_length)
 
