@@ -538,7 +538,7 @@ int wm_op_long_segments(const int32_t* ids, int n, int timestamp_begin, int64_t 
  * only the chunk table and its recording offsets cross the bus: chunk_gather_kernel cuts the chunks on the device, each pass's ids go from its decode state
  * into one packed device table (wm_transcribe_wait_device's rows), chunk_merge_kernel reads that table.  Uses the caller's slots 0..1
  * (0..3 with coalesce = 2): WM_E_STATE while one of them holds a pass; a held coalesce submit is flushed first.  The scratch is
- * released before the call returns.  Not here: token timestamps in chunked mode, HF's split at a language change. */
+ * released before the call returns.  Timestamps in chunked mode: wm_transcribe_chunked_ts below.  Not here: HF's split at a language change. */
 int wm_chunk_table(const int32_t* n_samples, int R, int chunk_len, int stride_left, int stride_right, int window, int32_t* table, int cap,
                    int32_t* n_chunks);
 int wm_transcribe_chunked(wm_model* m, const float* pcm, int pcm_on_device, const int32_t* n_samples, int R, int stride, int chunk_len,
@@ -553,6 +553,38 @@ int wm_transcribe_chunked(wm_model* m, const float* pcm, int pcm_on_device, cons
 int wm_op_chunk_gather(float* out, const float* pcm, int R, int64_t T_max, const int32_t* items, int n, int N);
 int wm_op_chunk_merge(int32_t* merged, int32_t* merged_len, const int32_t* ids, const int32_t* lens, const int32_t* rec_off, int n_rows,
                       int n_rec, int stride, int cap, int first_special);
+
+/* ---- chunked long-form transcription with timestamps ----------------------------------------------------------
+ * HF's ASR pipeline with chunk_length_s and return_timestamps = True (mode 1, segments) or "word" (mode 2): wm_transcribe_chunked's
+ * arguments and passes, stitched by tokenization_whisper._decode_asr's state machine instead of the plain merge — each chunk's ids are
+ * walked, timestamp ids inside a stride are skipped, a segment closes at an end timestamp, and the id lists a segment gathered over
+ * several chunks are merged by _find_longest_common_sequence (mode 2: a position counts only when the ids are equal and the left
+ * (start, end) pair <= the right pair).  Ids >= opts->timestamp_begin are timestamps, ids in [first_special, timestamp_begin) are
+ * ignored, every other id is text.  time_precision: seconds per timestamp id, 0 = the model's (window seconds / n_audio_ctx);
+ * segment_size is n_audio_ctx.  All times are float64, formed with Python's operations in Python's order and rounded as Python's
+ * round(x, 2), on the device.
+ * merged [R][cap], merged_len [R]: the segments' ids concatenated (cap as wm_transcribe_chunked).  n_seg [R]; seg_times [R][seg_cap][2]:
+ * start and end in seconds, NaN for HF's None; seg_range [R][seg_cap][2]: [begin, end) in merged.  WM_E_SIZE when a recording has
+ * more than seg_cap segments (n_seg holds the count; cap + 1 always suffices).  Mode 2: pairs [R][cap][2], the (start, end) of every
+ * merged id; every pass carries the alignment-head capture with n_frames = chunk samples / 160 (the ragged form of
+ * wm_transcribe_submit_tt) and its times are packed into one device table next to its ids, so nothing new crosses the bus between the
+ * PCM upload and the results; chunk_times [n_chunks][n_prompt + 1 + max_loop] (or NULL; with chunk_ids): every chunk's token times
+ * as wm_transcribe_wait_tt returns them.  WM_E_ARG: opts without the timestamp rule (timestamp_begin <= 0), mode 2 without alignment
+ * heads, with lang_ids or with a chunk shorter than 320 samples, mode outside {1, 2}.  Not here: the language fields and HF's split at
+ * a language change, _strip_prompt of a <|startofprev|> prompt, word grouping (host side: Tokenizer / tokenizer.collate_words).
+ * wm_op_chunk_segments: chunk_segments_kernel alone (a known-answer test) — ids [n_rows][stride] with lens [n_rows], strides
+ * [n_rows][3] = (len, stride_left, stride_right) in samples, times [n_rows][stride] aligned with the ids (mode 2) or NULL (mode 1);
+ * the outputs as above, all in and out: a cell the kernel does not store keeps the caller's value.  WM_E_SIZE: cap below a recording's
+ * ids (nothing is launched) or more segments than seg_cap (nothing is stored beyond it). */
+int wm_transcribe_chunked_ts(wm_model* m, const float* pcm, int pcm_on_device, const int32_t* n_samples, int R, int stride, int chunk_len,
+                             int stride_left, int stride_right, const wm_decode_opts* opts, const int32_t* lang_ids, int n_lang,
+                             int first_special, int mode, double time_precision, int32_t* merged, int32_t* merged_len, int cap,
+                             int32_t* n_seg, double* seg_times, int32_t* seg_range, int seg_cap, double* pairs, int32_t* chunk_ids,
+                             int32_t* chunk_n, float* chunk_times, int32_t* n_passes);
+int wm_op_chunk_segments(const int32_t* ids, const int32_t* lens, const int32_t* strides, const float* times, const int32_t* rec_off,
+                         int n_rows, int n_rec, int stride, int first_special, int timestamp_begin, double time_precision, int segment_size,
+                         int32_t* merged, int32_t* merged_len, int cap, int32_t* n_seg, double* seg_times, int32_t* seg_range, int seg_cap,
+                         double* pairs);
 
 /* ---- op-level entry points (host pointers; known-answer tests only) ------------------------------------------
  * Same argument meaning as the reference ops: out-param first, caller-allocated. */

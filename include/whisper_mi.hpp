@@ -19,6 +19,7 @@
 #include <sstream>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "whisper_mi.h"
@@ -467,6 +468,53 @@ public:
         for (int k = 0; want_chunks && k < n; ++k) {
             const int32_t* t = &tab[(size_t)k * 6];
             out[t[0]].chunks.push_back({t[1], t[2], t[3], t[4], std::vector<int>(cids.begin() + (size_t)k * total, cids.begin() + (size_t)k * total + cn[k])});
+        }
+        return out;
+    }
+    // ... with timestamps (set_timestamps first): HF's return_timestamps = true (word = false) or "word" (word = true, needs
+    // alignment heads).  `segments`: start / end in seconds (end NaN: no ending timestamp), the ids and, in word mode, the (start, end)
+    // of every id; `sequence` is the segments' ids concatenated.
+    struct ChunkSegment {
+        double start, end;
+        std::vector<int> tokens;
+        std::vector<std::pair<double, double>> token_timestamps;
+    };
+    struct ChunkedTsResult {
+        std::vector<int> sequence;
+        std::vector<ChunkSegment> segments;
+    };
+    std::vector<ChunkedTsResult> transcribe_chunked_ts(const float* pcm, const std::vector<int32_t>& n_samples, int stride, bool word,
+                                                       int chunk_len = 480000, int stride_left = -1, int stride_right = -1, int max_loop = MAX_LOOP,
+                                                       int32_t first_special = 50257, bool pcm_on_device = false, double time_precision = 0.0) const {
+        need_model();
+        wm_decode_opts o = opts(max_loop, false);
+        const int R = (int)n_samples.size(), sl = stride_left < 0 ? chunk_len / 6 : stride_left, sr = stride_right < 0 ? chunk_len / 6 : stride_right;
+        int32_t n = 0;
+        check(wm_chunk_table(n_samples.data(), R, chunk_len, sl, sr, 0, nullptr, 0, &n));
+        std::vector<int32_t> tab((size_t)(n > 0 ? n : 1) * 6);
+        check(wm_chunk_table(n_samples.data(), R, chunk_len, sl, sr, 0, tab.data(), n, &n));
+        std::vector<int> per(R, 0);
+        for (int k = 0; k < n; ++k) ++per[tab[(size_t)k * 6]];
+        const int total = o.n_prompt + 1 + max_loop;
+        int cap = 1;
+        for (int v : per) cap = v * total > cap ? v * total : cap;
+        const int seg_cap = cap + 1;
+        std::vector<int32_t> merged((size_t)R * cap), mlen(R), nseg(R), range((size_t)R * seg_cap * 2);
+        std::vector<double> times((size_t)R * seg_cap * 2), pairs(word ? (size_t)R * cap * 2 : 0);
+        check(wm_transcribe_chunked_ts(model_, pcm, pcm_on_device ? 1 : 0, n_samples.data(), R, stride, chunk_len, sl, sr, &o, nullptr, 0, first_special,
+                                       word ? 2 : 1, time_precision, merged.data(), mlen.data(), cap, nseg.data(), times.data(), range.data(), seg_cap,
+                                       word ? pairs.data() : nullptr, nullptr, nullptr, nullptr, nullptr));
+        std::vector<ChunkedTsResult> out(R);
+        for (int r = 0; r < R; ++r) {
+            const int32_t* ids = merged.data() + (size_t)r * cap;
+            out[r].sequence.assign(ids, ids + mlen[r]);
+            for (int k = 0; k < nseg[r]; ++k) {
+                const size_t at = ((size_t)r * seg_cap + k) * 2;
+                ChunkSegment sg{times[at], times[at + 1], std::vector<int>(ids + range[at], ids + range[at + 1]), {}};
+                for (int j = range[at]; word && j < range[at + 1]; ++j)
+                    sg.token_timestamps.emplace_back(pairs[((size_t)r * cap + j) * 2], pairs[((size_t)r * cap + j) * 2 + 1]);
+                out[r].segments.push_back(std::move(sg));
+            }
         }
         return out;
     }

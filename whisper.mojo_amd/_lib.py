@@ -39,6 +39,7 @@ SYMBOLS = [
     "wm_transcribe_long_tt", "wm_transcribe_long_pcm_tt", "wm_long_result_token_times", "wm_op_long_token_times",
     "wm_set_repeat_options", "wm_op_logits_processed", "wm_op_repeat_sets",
     "wm_chunk_table", "wm_transcribe_chunked", "wm_op_chunk_gather", "wm_op_chunk_merge",
+    "wm_transcribe_chunked_ts", "wm_op_chunk_segments",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -312,6 +313,10 @@ def lib():
                                                                                ip, ip, ip]
     L.wm_op_chunk_gather.argtypes = [fp, fp, C.c_int, C.c_int64, ip, C.c_int, C.c_int]
     L.wm_op_chunk_merge.argtypes = [ip] * 5 + [C.c_int] * 5
+    dp = C.POINTER(C.c_double)
+    L.wm_transcribe_chunked_ts.argtypes = [vp, vp, C.c_int, ip] + [C.c_int] * 5 + [C.POINTER(WmDecodeOpts), ip, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                                                  ip, ip, C.c_int, ip, dp, ip, C.c_int, dp, ip, ip, fp, ip]
+    L.wm_op_chunk_segments.argtypes = [ip, ip, ip, fp, ip] + [C.c_int] * 5 + [C.c_double, C.c_int, ip, ip, C.c_int, ip, dp, ip, C.c_int, dp]
     _lib = L
     return L
 
@@ -387,6 +392,64 @@ def op_chunk_merge(recordings, first_special=FIRST_SPECIAL, fill=-7):
     for r in range(len(recordings)):
         assert (merged[r, mlen[r]:] == fill).all(), f"recording {r}: the kernel stored past its length"
     return [merged[r, :mlen[r]].tolist() for r in range(len(recordings))]
+
+
+def op_chunk_segments(recordings, word, timestamp_begin, first_special, time_precision, segment_size, cap_extra=8, seg_cap=None, cap=None,
+                      fill=-7):
+    """wm_op_chunk_segments: recordings = per recording a list of chunks (ids, (len, stride_left, stride_right) in samples, token times
+    or None), all recordings in one launch -> per recording the segments [{"timestamp": (start, end | None), "ids", "token_timestamps"
+    (word)}].  Every output starts as a sentinel; cells past what a recording produced must still hold it (AssertionError).
+    cap / seg_cap: capacities to force (default: what the recording can need + cap_extra)."""
+    import numpy as np
+    chunks = [ch for rec in recordings for ch in rec]
+    off = np.zeros(len(recordings) + 1, np.int32)
+    off[1:] = np.cumsum([len(rec) for rec in recordings])
+    n_rows = max(1, len(chunks))
+    stride = max([1] + [len(ch[0]) for ch in chunks])
+    ids, lens = np.zeros((n_rows, stride), np.int32), np.zeros(n_rows, np.int32)
+    strides, times = np.zeros((n_rows, 3), np.int32), np.zeros((n_rows, stride), np.float32)
+    for k, (i, st, tt) in enumerate(chunks):
+        lens[k] = len(i)
+        ids[k, :len(i)] = i
+        strides[k] = st
+        if word:
+            times[k, :len(i)] = np.asarray(tt, np.float32)
+    R = len(recordings)
+    need = max([1] + [sum(len(ch[0]) for ch in rec) for rec in recordings])
+    cap = need + cap_extra if cap is None else int(cap)
+    seg_cap = need + 1 + cap_extra if seg_cap is None else int(seg_cap)
+    NAN_FILL = np.float64(-12345.5)
+    GUARD = 64  # cells behind every output that the library never hears of: a store past a capacity lands there
+    merged_g, segt_g = np.full(R * cap + GUARD, fill, np.int32), np.full(R * seg_cap * 2 + GUARD, NAN_FILL, np.float64)
+    segr_g, pairs_g = np.full(R * seg_cap * 2 + GUARD, fill, np.int32), np.full(R * cap * 2 + GUARD, NAN_FILL, np.float64)
+    merged, segt = merged_g[:R * cap].reshape(R, cap), segt_g[:R * seg_cap * 2].reshape(R, seg_cap, 2)
+    segr, pairs = segr_g[:R * seg_cap * 2].reshape(R, seg_cap, 2), pairs_g[:R * cap * 2].reshape(R, cap, 2)
+    mlen, nseg = np.zeros(R, np.int32), np.zeros(R, np.int32)
+    ip, dp, fp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_float)
+    rc = lib().wm_op_chunk_segments(ids.ctypes.data_as(ip), lens.ctypes.data_as(ip), strides.ctypes.data_as(ip), times.ctypes.data_as(fp) if word else None,
+                                    off.ctypes.data_as(ip), n_rows, R, stride, int(first_special), int(timestamp_begin), float(time_precision),
+                                    int(segment_size), merged.ctypes.data_as(ip), mlen.ctypes.data_as(ip), cap, nseg.ctypes.data_as(ip),
+                                    segt.ctypes.data_as(dp), segr.ctypes.data_as(ip), seg_cap, pairs.ctypes.data_as(dp) if word else None)
+    assert (merged_g[R * cap:] == fill).all() and (segr_g[R * seg_cap * 2:] == fill).all(), "a store past an output's capacity"
+    assert (segt_g[R * seg_cap * 2:] == NAN_FILL).all() and (pairs_g[R * cap * 2:] == NAN_FILL).all(), "a store past an output's capacity"
+    for r in range(R):  # also on a refusal: nothing was stored past what was produced
+        assert (merged[r, min(mlen[r], cap):] == fill).all(), f"recording {r}: ids stored past the length"
+        k = min(max(nseg[r], 0), seg_cap)
+        assert (segr[r, k:] == fill).all() and (segt[r, k:] == NAN_FILL).all(), f"recording {r}: segments stored past the count"
+        assert (pairs[r, min(mlen[r], cap) if word else 0:] == NAN_FILL).all(), f"recording {r}: pairs stored past the length"
+    check(rc)
+    out = []
+    for r in range(R):
+        m, segs = merged[r, :mlen[r]].tolist(), []
+        for k in range(nseg[r]):
+            (s, e), (b0, b1) = segt[r, k].tolist(), segr[r, k].tolist()
+            seg = {"timestamp": (None if s != s else s, None if e != e else e), "ids": m[b0:b1]}
+            if word:
+                seg["token_timestamps"] = [tuple(p) for p in pairs[r, b0:b1].tolist()]
+            segs.append(seg)
+        assert not segs or (segs and segr[r, nseg[r] - 1, 1] == mlen[r] and segr[r, 0, 0] == 0)
+        out.append(segs)
+    return out
 
 
 REPEAT_NGRAM_MAX = 64  # wm_kernels.h REPEAT_NGRAM_MAX

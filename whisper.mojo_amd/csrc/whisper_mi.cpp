@@ -254,6 +254,7 @@ struct PassOut {  // where a pass's results go: the caller's buffers, null = not
     float* lang_probs = nullptr;
     int32_t* dev_packed = nullptr;  // wm_transcribe_wait_device: the ids stay on the device, [rows_cap][1 + pack_stride]
     int rows_cap = 0, pack_stride = 0;
+    float* dev_times = nullptr;  // with dev_packed, a pass with token timestamps: its times stay on the device too, [rows_cap][pack_stride]
     int32_t* top_ids = nullptr;  // score / align passes
     float* sum_logprob = nullptr;
     double* win_times = nullptr;  // a window pass (PassAsk::win): [B][max_loop + 1] times of the generated ids, offset included
@@ -2437,6 +2438,9 @@ static int wait_on(wm_model* m, wm_state* s, int row0, int rows, const PassOut& 
         launch_pack_tokens(s->out_tokens.as<int>() + (size_t)row0 * s->out_stride, s->n_tokens.as<int>() + row0, s->out_stride, rows, out.rows_cap,
                            out.pack_stride, out.dev_packed, s->lanes[0].st);
         HIPCHK(hipGetLastError());
+        if (out.dev_times)
+            HIPCHK(hipMemcpy2DAsync(out.dev_times, (size_t)out.pack_stride * 4, s->al.times.as<float>() + (size_t)row0 * s->out_stride,
+                                    (size_t)s->out_stride * 4, (size_t)total * 4, rows, hipMemcpyDeviceToDevice, s->lanes[0].st));
         HIPCHK(hipStreamSynchronize(s->lanes[0].st));  // the caller's collective runs on another stream
     } else {
         HIPCHK(hipMemcpy2D(out.tokens, (size_t)total * 4, s->out_tokens.as<int>() + (size_t)row0 * s->out_stride, (size_t)s->out_stride * 4, (size_t)total * 4, rows,
@@ -2634,7 +2638,8 @@ static int collect_slot(wm_model* m, int slot, PassKind kind, const PassOut& out
         if (out.lang_out && !r.lang) return fail(WM_E_STATE, "this slot's pass was submitted without language detection (wm_transcribe_submit_lang)");
         if (out.no_speech_prob && !r.ns) return fail(WM_E_STATE, "this slot's pass was submitted without the no-speech probe (wm_transcribe_submit_lp_ns)");
         if (out.token_logprobs && !r.lp) return fail(WM_E_STATE, "this slot's pass was submitted without log-probabilities (wm_transcribe_submit_lp)");
-        if (out.token_times && !r.tt) return fail(WM_E_STATE, "this slot's pass was submitted without token timestamps (wm_transcribe_submit_tt)");
+        if ((out.token_times || out.dev_times) && !r.tt)
+            return fail(WM_E_STATE, "this slot's pass was submitted without token timestamps (wm_transcribe_submit_tt)");
         if (out.dev_packed && out.rows_cap < r.rows) return fail(WM_E_ARG, "rows_cap %d is smaller than the batch (%d)", out.rows_cap, r.rows);
         if (out.dev_packed && out.pack_stride < r.total)
             return fail(WM_E_ARG, "stride %d is smaller than the pass's ids per utterance (%d)", out.pack_stride, r.total);
@@ -3529,14 +3534,38 @@ extern "C" int wm_op_chunk_merge(int32_t* merged, int32_t* merged_len, const int
 // Chunks of all recordings fill passes of up to max_batch rows, in table order; passes alternate over the caller's slots 0..1 (0..3 under
 // coalesce = 2, where two submits make one pass), so two passes are in flight, each with a log-mel buffer of its own.  A pass's ids go
 // from its decode state into the packed table on the device (wm_transcribe_wait_device's rows); the stitch reads that table.
-extern "C" int wm_transcribe_chunked(wm_model* m, const float* pcm, int pcm_on_device, const int32_t* n_samples, int R, int stride, int chunk_len,
-                                     int stride_left, int stride_right, const wm_decode_opts* o, const int32_t* lang_ids, int n_lang, int first_special,
-                                     int32_t* merged, int32_t* merged_len, int cap, int32_t* chunk_ids, int32_t* chunk_n, int32_t* n_passes) {
+// The timestamp outputs of wm_transcribe_chunked_ts.  mode 0: none of this — wm_transcribe_chunked, which launches what it
+// always launched.  mode 1 (segments): chunk_segments_kernel stitches instead of chunk_merge_kernel.  mode 2 (word): every pass also
+// carries the alignment-head capture with per-row n_frames = len // 160, and its times are packed next to its ids.
+struct ChunkTs {
+    int mode = 0;
+    double time_precision = 0.0;
+    int32_t* n_seg = nullptr;
+    double* seg_times = nullptr;
+    int32_t* seg_range = nullptr;
+    int seg_cap = 0;
+    double* pairs = nullptr;
+    float* chunk_times = nullptr;
+};
+static int chunked_impl(wm_model* m, const float* pcm, int pcm_on_device, const int32_t* n_samples, int R, int stride, int chunk_len,
+                        int stride_left, int stride_right, const wm_decode_opts* o, const int32_t* lang_ids, int n_lang, int first_special,
+                        int32_t* merged, int32_t* merged_len, int cap, int32_t* chunk_ids, int32_t* chunk_n, int32_t* n_passes, const ChunkTs& ts) {
     if (!m || !pcm || !n_samples || R <= 0 || stride <= 0 || !merged || !merged_len || cap <= 0 || (!chunk_ids != !chunk_n) || first_special <= 0)
         return fail(WM_E_ARG, "bad argument");
     const wm_dims& c = m->cfg.dims;
     const int n_frames = 2 * c.n_audio_ctx, N = FE_HOP * n_frames;
     WMCHK(check_opts(m, o, 1));
+    const bool word = ts.mode == 2;
+    if (ts.mode) {  // everything is refused before anything is launched
+        if (ts.mode != 1 && ts.mode != 2) return fail(WM_E_ARG, "mode must be 1 (segments) or 2 (word)");
+        if (!ts.n_seg || !ts.seg_times || !ts.seg_range || ts.seg_cap <= 0 || (word && !ts.pairs) || (ts.chunk_times && (!word || !chunk_ids)))
+            return fail(WM_E_ARG, "bad argument");
+        if (o->timestamp_begin <= 0) return fail(WM_E_ARG, "chunked timestamps need the timestamp rule (opts->timestamp_begin)");
+        if (o->timestamp_begin < first_special) return fail(WM_E_ARG, "timestamp_begin %d lies below first_special %d", o->timestamp_begin, first_special);
+        if (word && m->align_pairs.empty()) return fail(WM_E_ARG, "word timestamps need alignment heads (wm_set_alignment_heads)");
+        if (word && lang_ids) return fail(WM_E_ARG, "word timestamps do not combine with language detection (a language pass carries no token timestamps)");
+        if (ts.time_precision < 0.0 || ts.time_precision != ts.time_precision) return fail(WM_E_ARG, "time_precision must be positive (0: the model's)");
+    }
     for (int r = 0; r < R; ++r)
         if (n_samples[r] < 0 || n_samples[r] > stride) return fail(WM_E_ARG, "n_samples[%d]=%d out of range", r, n_samples[r]);
     int32_t n = 0;
@@ -3551,6 +3580,12 @@ extern "C" int wm_transcribe_chunked(wm_model* m, const float* pcm, int pcm_on_d
     }
     const int total = o->n_prompt + 1 + o->max_loop;
     if ((int64_t)most * total > cap) return fail(WM_E_SIZE, "cap %d is smaller than %d chunks x %d ids of the longest recording", cap, most, total);
+    if (ts.mode && total > CHUNK_MERGE_MAX_IDS) return fail(WM_E_ARG, "more than %d ids per chunk", CHUNK_MERGE_MAX_IDS);
+    if (word)
+        for (int k = 0; k < n; ++k)
+            if (tab[(size_t)k * CHUNK_COLS + 2] < 2 * FE_HOP)
+                return fail(WM_E_ARG, "chunk %d has %d samples: word timestamps need two mel frames of audio per chunk", k, tab[(size_t)k * CHUNK_COLS + 2]);
+    if (ts.mode) std::fill(ts.n_seg, ts.n_seg + R, 0);
     const int PB = std::min(m->cfg.max_batch, std::max(n, 1));
     if (lang_ids) {  // what a _lang pass would refuse, before anything is launched
         WMCHK(lang_list_check(c.vocab, lang_ids, n_lang));
@@ -3568,8 +3603,18 @@ extern "C" int wm_transcribe_chunked(wm_model* m, const float* pcm, int pcm_on_d
         if (m->slot_ref[s].pending) return fail(WM_E_STATE, "slot %d still holds a pass that was not waited for (chunked transcription uses slots 0..%d)", s, NS - 1);
     hipStream_t st = m->stream;
     TmpDev tmp;
-    tmp.bufs.reserve(12);
+    tmp.bufs.reserve(20);
     DevBuf &d_pcm = tmp.add(), &d_tab = tmp.add(), &d_off = tmp.add(), &d_packed = tmp.add(), &d_merged = tmp.add(), &d_len = tmp.add();
+    DevBuf &d_times = tmp.add(), &d_nseg = tmp.add(), &d_segt = tmp.add(), &d_segr = tmp.add(), &d_pairs = tmp.add();
+    if (ts.mode) {
+        WMCHK(d_nseg.alloc((size_t)R * 4));
+        WMCHK(d_segt.alloc((size_t)R * ts.seg_cap * 2 * 8));
+        WMCHK(d_segr.alloc((size_t)R * ts.seg_cap * 2 * 4));
+    }
+    if (word) {
+        WMCHK(d_times.alloc((size_t)n * total * 4));
+        WMCHK(d_pairs.alloc((size_t)R * cap * 2 * 8));
+    }
     const float* dpcm = pcm;
     if (!pcm_on_device) {
         WMCHK(d_pcm.alloc((size_t)R * stride * 4));
@@ -3599,6 +3644,7 @@ extern "C" int wm_transcribe_chunked(wm_model* m, const float* pcm, int pcm_on_d
         out.dev_packed = d_packed.as<int32_t>() + (size_t)p.row0 * (1 + total);
         out.rows_cap = p.rows;
         out.pack_stride = total;
+        if (word) out.dev_times = d_times.as<float>() + (size_t)p.row0 * total;  // this pass's times, next to its ids
         return collect_slot(m, s, PassKind::transcribe, out);
     };
     int rc = 0, np = 0;
@@ -3610,7 +3656,16 @@ extern "C" int wm_transcribe_chunked(wm_model* m, const float* pcm, int pcm_on_d
             launch_chunk_gather(dpcm, d_tab.as<int>(), CHUNK_COLS, row0, m->fe.pcm.as<float>(), rows, (size_t)stride, N, st);
             rc = frontend_compute(m, rows, d_mel[s]->as<float>());
         }
-        if (!rc)
+        if (!rc && word) {  // the ragged form of §28: row b keeps (len // 160) // 2 encoder positions
+            std::vector<int32_t> nf(rows), cols;
+            for (int b = 0; b < rows; ++b) nf[b] = tab[(size_t)(row0 + b) * CHUNK_COLS + 2] / FE_HOP;
+            rc = align_cols(m, nf.data(), rows, cols);
+            if (!rc) {
+                PassAsk ask{d_mel[s]->as<float>(), 1, rows, o};
+                ask.cols = &cols;
+                rc = submit_slot(m, s, ask);
+            }
+        } else if (!rc)
             rc = lang_ids ? lang_entry(m, s, d_mel[s]->as<float>(), 1, rows, o, nullptr, nullptr, 0, false, -1, o->n_prompt, lang_ids, n_lang, PassOut())
                           : submit_slot(m, s, PassAsk{d_mel[s]->as<float>(), 1, rows, o});
         if (!rc) {
@@ -3631,17 +3686,133 @@ extern "C" int wm_transcribe_chunked(wm_model* m, const float* pcm, int pcm_on_d
         return rc;
     }
     if (n_passes) *n_passes = np;
-    LCHK(launch_chunk_merge(d_packed.as<int>(), d_off.as<int>(), R, total, first_special, d_merged.as<int>(), d_len.as<int>(), cap, st));
+    if (ts.mode) {
+        ChunkSegArgs a{};
+        a.rows = d_packed.as<int>();
+        a.rec_off = d_off.as<int>();
+        a.tab = d_tab.as<int>();
+        a.times = word ? d_times.as<float>() : nullptr;
+        a.tab_cols = CHUNK_COLS, a.tab_c0 = 2, a.stride = total, a.first_special = first_special, a.timestamp_begin = o->timestamp_begin;
+        a.segment_size = c.n_audio_ctx;
+        a.time_precision = ts.time_precision > 0.0 ? ts.time_precision : (double)N / 16000.0 / (double)c.n_audio_ctx;
+        a.merged = d_merged.as<int>(), a.merged_len = d_len.as<int>(), a.n_seg = d_nseg.as<int>();
+        a.seg_times = (double*)d_segt.p, a.seg_range = d_segr.as<int>(), a.pairs = word ? (double*)d_pairs.p : nullptr;
+        a.cap = cap, a.seg_cap = ts.seg_cap;
+        LCHK(launch_chunk_segments(a, R, st));
+        HIPCHK(hipMemcpyAsync(ts.n_seg, d_nseg.p, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+    } else {
+        LCHK(launch_chunk_merge(d_packed.as<int>(), d_off.as<int>(), R, total, first_special, d_merged.as<int>(), d_len.as<int>(), cap, st));
+    }
     HIPCHK(hipMemcpyAsync(merged_len, d_len.p, (size_t)R * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    for (int r = 0; r < R; ++r)
+    for (int r = 0; r < R && ts.mode; ++r)
+        if (ts.n_seg[r] > ts.seg_cap) return fail(WM_E_SIZE, "recording %d has %d segments, seg_cap is %d", r, ts.n_seg[r], ts.seg_cap);
+    for (int r = 0; r < R; ++r) {
         if (merged_len[r] > 0)
             HIPCHK(hipMemcpyAsync(merged + (size_t)r * cap, d_merged.as<int32_t>() + (size_t)r * cap, (size_t)merged_len[r] * 4, hipMemcpyDeviceToHost, st));
+        if (word && merged_len[r] > 0)
+            HIPCHK(hipMemcpyAsync(ts.pairs + (size_t)r * cap * 2, (const double*)d_pairs.p + (size_t)r * cap * 2, (size_t)merged_len[r] * 16, hipMemcpyDeviceToHost, st));
+        if (ts.mode && ts.n_seg[r] > 0) {
+            const size_t at = (size_t)r * ts.seg_cap * 2;
+            HIPCHK(hipMemcpyAsync(ts.seg_times + at, (const double*)d_segt.p + at, (size_t)ts.n_seg[r] * 16, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(ts.seg_range + at, d_segr.as<int32_t>() + at, (size_t)ts.n_seg[r] * 8, hipMemcpyDeviceToHost, st));
+        }
+    }
+    if (ts.chunk_times)
+        HIPCHK(hipMemcpyAsync(ts.chunk_times, d_times.p, (size_t)n * total * 4, hipMemcpyDeviceToHost, st));
     if (chunk_ids) {  // on request: every chunk's own ids, as wm_transcribe_pcm of that chunk's samples returns them
         HIPCHK(hipMemcpy2DAsync(chunk_n, 4, d_packed.p, (size_t)(1 + total) * 4, 4, n, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpy2DAsync(chunk_ids, (size_t)total * 4, d_packed.as<int32_t>() + 1, (size_t)(1 + total) * 4, (size_t)total * 4, n, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+extern "C" int wm_transcribe_chunked(wm_model* m, const float* pcm, int pcm_on_device, const int32_t* n_samples, int R, int stride, int chunk_len,
+                                     int stride_left, int stride_right, const wm_decode_opts* o, const int32_t* lang_ids, int n_lang, int first_special,
+                                     int32_t* merged, int32_t* merged_len, int cap, int32_t* chunk_ids, int32_t* chunk_n, int32_t* n_passes) {
+    return chunked_impl(m, pcm, pcm_on_device, n_samples, R, stride, chunk_len, stride_left, stride_right, o, lang_ids, n_lang, first_special, merged,
+                        merged_len, cap, chunk_ids, chunk_n, n_passes, ChunkTs());
+}
+extern "C" int wm_transcribe_chunked_ts(wm_model* m, const float* pcm, int pcm_on_device, const int32_t* n_samples, int R, int stride, int chunk_len,
+                                        int stride_left, int stride_right, const wm_decode_opts* o, const int32_t* lang_ids, int n_lang,
+                                        int first_special, int mode, double time_precision, int32_t* merged, int32_t* merged_len, int cap,
+                                        int32_t* n_seg, double* seg_times, int32_t* seg_range, int seg_cap, double* pairs, int32_t* chunk_ids,
+                                        int32_t* chunk_n, float* chunk_times, int32_t* n_passes) {
+    ChunkTs ts;
+    ts.mode = mode;
+    ts.time_precision = time_precision;
+    ts.n_seg = n_seg, ts.seg_times = seg_times, ts.seg_range = seg_range, ts.seg_cap = seg_cap, ts.pairs = pairs, ts.chunk_times = chunk_times;
+    if (mode != 1 && mode != 2) return fail(WM_E_ARG, "mode must be 1 (segments) or 2 (word)");
+    return chunked_impl(m, pcm, pcm_on_device, n_samples, R, stride, chunk_len, stride_left, stride_right, o, lang_ids, n_lang, first_special, merged,
+                        merged_len, cap, chunk_ids, chunk_n, n_passes, ts);
+}
+
+// chunk_segments_kernel alone: ids [n_rows][stride] with lens [n_rows], strides [n_rows][3] = (len, stride_left, stride_right) in samples,
+// times [n_rows][stride] (word mode) or NULL (segments mode).  The outputs are uploaded first, so a cell the kernel does not store
+// keeps the caller's value.
+extern "C" int wm_op_chunk_segments(const int32_t* ids, const int32_t* lens, const int32_t* strides, const float* times, const int32_t* rec_off,
+                                    int n_rows, int n_rec, int stride, int first_special, int timestamp_begin, double time_precision,
+                                    int segment_size, int32_t* merged, int32_t* merged_len, int cap, int32_t* n_seg, double* seg_times,
+                                    int32_t* seg_range, int seg_cap, double* pairs) {
+    if (!ids || !lens || !strides || !rec_off || !merged || !merged_len || !n_seg || !seg_times || !seg_range || n_rows <= 0 || n_rec <= 0 ||
+        stride <= 0 || cap <= 0 || seg_cap <= 0 || (times && !pairs))
+        return fail(WM_E_ARG, "bad argument");
+    if (rec_off[0] < 0 || rec_off[n_rec] > n_rows) return fail(WM_E_ARG, "rec_off leaves the %d rows", n_rows);
+    for (int r = 0; r < n_rec; ++r)
+        if (rec_off[r + 1] < rec_off[r]) return fail(WM_E_ARG, "rec_off must not decrease");
+    std::vector<int32_t> packed((size_t)n_rows * (1 + stride), 0);
+    for (int k = 0; k < n_rows; ++k) {
+        if (lens[k] < 0 || lens[k] > stride) return fail(WM_E_ARG, "lens[%d] = %d outside [0, %d]", k, lens[k], stride);
+        if (strides[3 * k] < 0 || strides[3 * k + 1] < 0 || strides[3 * k + 2] < 0) return fail(WM_E_ARG, "strides[%d] is negative", k);
+        packed[(size_t)k * (1 + stride)] = lens[k];
+        std::copy(ids + (size_t)k * stride, ids + (size_t)k * stride + lens[k], packed.begin() + (size_t)k * (1 + stride) + 1);
+    }
+    for (int r = 0; r < n_rec; ++r) {  // cap must hold the recording's ids even when nothing overlaps
+        int64_t sum = 0;
+        for (int k = rec_off[r]; k < rec_off[r + 1]; ++k) sum += lens[k];
+        if (sum > cap) return fail(WM_E_SIZE, "recording %d has %lld ids, cap is %d", r, (long long)sum, cap);
+    }
+    TmpDev tmp;
+    tmp.bufs.reserve(12);
+    DevBuf &dr = tmp.add(), &doff = tmp.add(), &dtab = tmp.add(), &dtt = tmp.add(), &dm = tmp.add(), &dl = tmp.add(), &dn = tmp.add(), &dst = tmp.add(),
+           &dsr = tmp.add(), &dp = tmp.add();
+    const size_t nm = (size_t)n_rec * cap, ns = (size_t)n_rec * seg_cap * 2;
+    WMCHK(dr.alloc(packed.size() * 4));
+    WMCHK(doff.alloc((size_t)(n_rec + 1) * 4));
+    WMCHK(dtab.alloc((size_t)n_rows * 3 * 4));
+    WMCHK(dm.alloc(nm * 4));
+    WMCHK(dl.alloc((size_t)n_rec * 4));
+    WMCHK(dn.alloc((size_t)n_rec * 4));
+    WMCHK(dst.alloc(ns * 8));
+    WMCHK(dsr.alloc(ns * 4));
+    HIPCHK(hipMemcpy(dr.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(doff.p, rec_off, (size_t)(n_rec + 1) * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dtab.p, strides, (size_t)n_rows * 3 * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dm.p, merged, nm * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dst.p, seg_times, ns * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dsr.p, seg_range, ns * 4, hipMemcpyHostToDevice));
+    if (times) {
+        WMCHK(dtt.alloc((size_t)n_rows * stride * 4));
+        WMCHK(dp.alloc(nm * 2 * 8));
+        HIPCHK(hipMemcpy(dtt.p, times, (size_t)n_rows * stride * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dp.p, pairs, nm * 2 * 8, hipMemcpyHostToDevice));
+    }
+    ChunkSegArgs a{};
+    a.rows = dr.as<int>(), a.rec_off = doff.as<int>(), a.tab = dtab.as<int>(), a.times = times ? dtt.as<float>() : nullptr;
+    a.tab_cols = 3, a.tab_c0 = 0, a.stride = stride, a.first_special = first_special, a.timestamp_begin = timestamp_begin;
+    a.segment_size = segment_size, a.time_precision = time_precision;
+    a.merged = dm.as<int>(), a.merged_len = dl.as<int>(), a.n_seg = dn.as<int>(), a.seg_times = (double*)dst.p, a.seg_range = dsr.as<int>();
+    a.pairs = times ? (double*)dp.p : nullptr;
+    a.cap = cap, a.seg_cap = seg_cap;
+    LCHK(launch_chunk_segments(a, n_rec, nullptr));
+    HIPCHK(hipMemcpy(merged, dm.p, nm * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(merged_len, dl.p, (size_t)n_rec * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(n_seg, dn.p, (size_t)n_rec * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(seg_times, dst.p, ns * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(seg_range, dsr.p, ns * 4, hipMemcpyDeviceToHost));
+    if (times) HIPCHK(hipMemcpy(pairs, dp.p, nm * 2 * 8, hipMemcpyDeviceToHost));
+    for (int r = 0; r < n_rec; ++r)
+        if (n_seg[r] > seg_cap) return fail(WM_E_SIZE, "recording %d has %d segments, seg_cap is %d", r, n_seg[r], seg_cap);
     return 0;
 }
 

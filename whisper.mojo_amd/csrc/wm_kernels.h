@@ -506,6 +506,23 @@ void launch_chunk_gather(const float* pcm, const int* items, int item_stride, in
 static const int CHUNK_MERGE_MAX_IDS = 2048;
 int launch_chunk_merge(const int* rows, const int* rec_off, int n_rec, int stride, int first_special, int* merged, int* merged_len, int cap,
                        hipStream_t st);
+// the stitch with timestamps: chunk_segments_kernel, one workgroup per recording; LDS 4 · stride ints + 3 KB.  WM_LAUNCH_*
+struct ChunkSegArgs {
+    const int* rows;      // [n_chunks][1 + stride]: (count, ids), the decoder prompt included
+    const int* rec_off;   // [n_rec + 1]
+    const int* tab;       // chunk k: tab[k * tab_cols + tab_c0 + 0 .. 2] = (len, stride_left, stride_right) in samples
+    const float* times;   // word mode: [n_chunks][stride] token times aligned with the ids; else null
+    int tab_cols, tab_c0, stride, first_special, timestamp_begin, segment_size;
+    double time_precision;
+    int* merged;          // [n_rec][cap]
+    int* merged_len;      // [n_rec]
+    int* n_seg;           // [n_rec]: the segments found, also when more than seg_cap
+    double* seg_times;    // [n_rec][seg_cap][2]: start, end (NaN = None)
+    int* seg_range;       // [n_rec][seg_cap][2]: [begin, end) in merged
+    double* pairs;        // word mode: [n_rec][cap][2]
+    int cap, seg_cap;
+};
+int launch_chunk_segments(const ChunkSegArgs& a, int n_rec, hipStream_t st);
 
 // ---- small ops for the op-level C-ABI ----------------------------------------------------------------------------
 void launch_gelu(float* t, size_t n, int mode, hipStream_t st);

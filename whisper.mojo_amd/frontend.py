@@ -165,7 +165,8 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
 def transcribe_audio_chunked(model, audios, chunk_length_s: float = 30.0, stride_length_s=None, return_chunks: bool = False,
                              prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP, suppress_tokens: Sequence[int] = (),
                              begin_suppress_tokens: Sequence[int] = (), timestamps=None, detect_language=None, repetition_penalty=None,
-                             no_repeat_ngram_size=None, first_special: int = _lib.FIRST_SPECIAL, return_stats: bool = False, n_samples=None):
+                             no_repeat_ngram_size=None, first_special: int = _lib.FIRST_SPECIAL, return_stats: bool = False, n_samples=None,
+                             return_timestamps=False, time_precision=None, tokenizer=None):
     """Chunked long-form transcription of 16 kHz PCM of any length (HF's ASR pipeline with chunk_length_s / stride_length_s /
     batch_size = max_batch): every recording is cut into overlapping chunks (HF chunk_iter), the chunks of all recordings
     are decoded on their own in passes of up to max_batch rows, two passes in flight, and each recording's id lists are stitched on
@@ -179,7 +180,24 @@ def transcribe_audio_chunked(model, audios, chunk_length_s: float = 30.0, stride
     with the other specials.
     Returns per recording {"sequence": merged ids} and, with return_chunks, "chunks": [(start_s, len_s, stride_left_s,
     stride_right_s, ids)] with the ids exactly as transcribe_audio gives them for that chunk's samples alone.  A single array in, a
-    single dict out.  return_stats: also {"chunks", "passes"}.  tokenizer.decode_text(sequence) gives the text."""
+    single dict out.  return_stats: also {"chunks", "passes"}.  tokenizer.decode_text(sequence) gives the text.
+    return_timestamps (needs timestamps=, the timestamp rule, and a prompt without the no-timestamps id): True — HF's
+    return_timestamps=True: every recording also carries "segments": [{"timestamp": (start_s, end_s | None), "ids": [...]}], cut at
+    the timestamp ids as _decode_asr cuts them (those inside a stride are skipped), each segment's ids merged over the chunks it
+    spans; "sequence" is then the segments' ids concatenated.  "word" — HF's return_timestamps="word" (needs set_alignment_heads; not
+    with detect_language): every pass also computes token times with n_frames = chunk samples // 160, every segment carries
+    "token_timestamps": [(start_s, end_s)] per id, the merge counts a position only when the left pair <= the right pair, and with
+    tokenizer= also "words" (tokenizer.collate_words); with return_chunks every chunk tuple ends with its token times.  "word" needs
+    two mel frames of audio in every chunk: a chunk shorter than 320 samples (the tail of a recording under stride_length_s=0, or a
+    recording shorter than 20 ms) makes the library refuse the whole call, where the other two modes accept it.
+    time_precision: seconds per timestamp id (None: window seconds / n_audio_ctx)."""
+    if not isinstance(return_timestamps, (bool, np.bool_)) and not (isinstance(return_timestamps, str) and return_timestamps == "word"):
+        raise ValueError('return_timestamps is False, True or "word"')  # 0 / 1 would pass an `in` test by equality: bools only
+    ts_mode = 2 if isinstance(return_timestamps, str) else 1 if return_timestamps else 0
+    if ts_mode and timestamps is None:
+        raise ValueError("return_timestamps needs timestamps=(timestamp_begin, no_timestamps_id, max_initial_timestamp_index)")
+    if ts_mode == 2 and detect_language is not None:
+        raise ValueError('return_timestamps="word" does not combine with detect_language')
     dev = None
     if not isinstance(audios, (np.ndarray, list, tuple)):
         import torch
@@ -231,17 +249,47 @@ def transcribe_audio_chunked(model, audios, chunk_length_s: float = 30.0, stride
     cn = np.zeros(max(1, len(tab)), np.int32) if return_chunks else None
     passes = C.c_int32()
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
-    _lib.check(_lib.lib().wm_transcribe_chunked(
-        model._h, pcm_ptr, on_dev, n.ctypes.data_as(ip), R, stride, chunk_len, sl, sr, C.byref(opts),
-        lang_list.ctypes.data_as(ip) if lang_list is not None else None, lang_list.size if lang_list is not None else 0, int(first_special),
-        merged.ctypes.data_as(ip), mlen.ctypes.data_as(ip), cap, cids.ctypes.data_as(ip) if return_chunks else None,
-        cn.ctypes.data_as(ip) if return_chunks else None, C.byref(passes)))
-    out = [{"sequence": merged[r, :mlen[r]].tolist()} for r in range(R)]
+    lang_ptr = lang_list.ctypes.data_as(ip) if lang_list is not None else None
+    n_lang = lang_list.size if lang_list is not None else 0
+    ctimes = None
+    if not ts_mode:
+        _lib.check(_lib.lib().wm_transcribe_chunked(
+            model._h, pcm_ptr, on_dev, n.ctypes.data_as(ip), R, stride, chunk_len, sl, sr, C.byref(opts), lang_ptr, n_lang, int(first_special),
+            merged.ctypes.data_as(ip), mlen.ctypes.data_as(ip), cap, cids.ctypes.data_as(ip) if return_chunks else None,
+            cn.ctypes.data_as(ip) if return_chunks else None, C.byref(passes)))
+        out = [{"sequence": merged[r, :mlen[r]].tolist()} for r in range(R)]
+    else:
+        dp = C.POINTER(C.c_double)
+        seg_cap = cap + 1  # a segment closes at a timestamp id, and one more may stay open
+        nseg, segt, segr = np.zeros(R, np.int32), np.zeros((R, seg_cap, 2), np.float64), np.zeros((R, seg_cap, 2), np.int32)
+        pairs = np.zeros((R, cap, 2), np.float64) if ts_mode == 2 else None
+        ctimes = np.zeros((max(1, len(tab)), total), np.float32) if return_chunks and ts_mode == 2 else None
+        _lib.check(_lib.lib().wm_transcribe_chunked_ts(
+            model._h, pcm_ptr, on_dev, n.ctypes.data_as(ip), R, stride, chunk_len, sl, sr, C.byref(opts), lang_ptr, n_lang, int(first_special),
+            ts_mode, 0.0 if time_precision is None else float(time_precision), merged.ctypes.data_as(ip), mlen.ctypes.data_as(ip), cap,
+            nseg.ctypes.data_as(ip), segt.ctypes.data_as(dp), segr.ctypes.data_as(ip), seg_cap, pairs.ctypes.data_as(dp) if pairs is not None else None,
+            cids.ctypes.data_as(ip) if return_chunks else None, cn.ctypes.data_as(ip) if return_chunks else None,
+            ctimes.ctypes.data_as(fp) if ctimes is not None else None, C.byref(passes)))
+        out = []
+        for r in range(R):
+            ids = merged[r, :mlen[r]].tolist()
+            segs = []
+            for k in range(nseg[r]):
+                (s, e), (b0, b1) = segt[r, k].tolist(), segr[r, k].tolist()
+                seg = {"timestamp": (None if s != s else s, None if e != e else e), "ids": ids[b0:b1]}
+                if pairs is not None:
+                    seg["token_timestamps"] = [tuple(p) for p in pairs[r, b0:b1].tolist()]
+                    if tokenizer is not None:
+                        from .tokenizer import collate_words
+                        seg["words"] = collate_words(tokenizer, seg["ids"], seg["token_timestamps"])
+                segs.append(seg)
+            out.append({"sequence": ids, "segments": segs})
     if return_chunks:
         for r in range(R):
             out[r]["chunks"] = []
         for k, (r, start, ln, esl, esr, _last) in enumerate(tab.tolist()):
-            out[r]["chunks"].append((start / SAMPLING_RATE, ln / SAMPLING_RATE, esl / SAMPLING_RATE, esr / SAMPLING_RATE, cids[k, :cn[k]].tolist()))
+            row = (start / SAMPLING_RATE, ln / SAMPLING_RATE, esl / SAMPLING_RATE, esr / SAMPLING_RATE, cids[k, :cn[k]].tolist())
+            out[r]["chunks"].append(row + (ctimes[k, :cn[k]].tolist(),) if ctimes is not None else row)
     res = out[0] if single else out
     return (res, {"chunks": int(len(tab)), "passes": int(passes.value)}) if return_stats else res
 

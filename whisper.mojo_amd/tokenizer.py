@@ -104,3 +104,68 @@ def language_ids(tokenizer: "Tokenizer" = None):
 def language_code(token_id: int, tokenizer: "Tokenizer" = None) -> str:
     """<|xx|> id -> "xx"; KeyError for an id that is no language token."""
     return language_ids(tokenizer)[1][int(token_id)]
+
+
+# ---- word grouping for word-level timestamps (DESIGN §31) --------------------------------------------------------------------------
+# A restatement of transformers' tokenization_whisper._collate_word_timestamps for the languages that are split on spaces:
+# _split_tokens_on_unicode (a word ends where the ids so far decode to complete UTF-8), _split_tokens_on_spaces, _merge_punctuations.
+UNICODE_SPLIT_LANGUAGES = {"chinese", "japanese", "thai", "lao", "myanmar", "cantonese", "zh", "ja", "th", "lo", "my", "yue"}
+_PREPEND_PUNCTUATIONS = "\"'“¡¿([{-"
+_APPEND_PUNCTUATIONS = "\"'.。,，!！?？:：”)]}、"
+_PUNCTUATION = "!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~"
+
+
+def _split_on_unicode(tokenizer: "Tokenizer", ids: Sequence[int]):
+    full = tokenizer.decode_text(ids)
+    bad = "�"
+    words, indices, cur, offset = [], [], [], 0
+    for k in range(len(ids)):
+        cur.append(k)
+        text = tokenizer.decode_text([ids[j] for j in cur])
+        if bad not in text or offset + text.index(bad) >= len(full) or full[offset + text.index(bad)] == bad:
+            words.append(text)
+            indices.append(cur)
+            cur = []
+            offset += len(text)
+    return words, indices
+
+
+def collate_words(tokenizer: "Tokenizer", ids: Sequence[int], pairs: Sequence[Sequence[float]], language: str = None,
+                  eos_token_id: int = 50257) -> List[dict]:
+    """ids of one segment and their (start, end) pairs -> [{"text": word, "timestamp": (start of its first id, end of its last)}],
+    as HF's _collate_word_timestamps groups them: a new word at an id that decodes with a leading space, at a punctuation mark and
+    at an id >= eos_token_id; then the prepended / appended punctuation marks join their neighbours.  NotImplementedError for the
+    languages HF splits on unicode points instead."""
+    if language is not None and language.lower() in UNICODE_SPLIT_LANGUAGES:
+        raise NotImplementedError(f"word grouping for {language!r} (split on unicode points) is not implemented")
+    ids = [int(t) for t in ids]
+    words, indices = [], []
+    for sub, idx in zip(*_split_on_unicode(tokenizer, ids)):
+        special = ids[idx[0]] >= eos_token_id
+        if special or sub.startswith(" ") or sub.strip() in _PUNCTUATION or not words:
+            words.append(sub)
+            indices.append(list(idx))
+        else:
+            words[-1] += sub
+            indices[-1].extend(idx)
+    i, j = len(words) - 2, len(words) - 1
+    while i >= 0:  # prepended marks go to the word that follows
+        if words[i].startswith(" ") and words[i].strip() in _PREPEND_PUNCTUATIONS:
+            words[j] = words[i] + words[j]
+            indices[j] = indices[i] + indices[j]
+            words[i], indices[i] = "", []
+        else:
+            j = i
+        i -= 1
+    i, j = 0, 1
+    while j < len(words):  # appended marks go to the word before
+        if not words[i].endswith(" ") and words[j] in _APPEND_PUNCTUATIONS:
+            words[i] += words[j]
+            indices[i] += indices[j]
+            words[j], indices[j] = "", []
+        else:
+            i = j
+        j += 1
+    words = [w for w in words if w]      # (HF filters the two lists separately; so does this)
+    indices = [x for x in indices if x]
+    return [{"text": w, "timestamp": (pairs[x[0]][0], pairs[x[-1]][1])} for w, x in zip(words, indices)]
