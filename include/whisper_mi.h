@@ -607,6 +607,24 @@ int wm_op_layer_norm(float* out, const float* inp, const float* gamma, const flo
  * so the guard row after the last comes back as it went in unless the kernel wrote it.  cols as wm_op_layer_norm.  Known-answer tests. */
 int wm_op_layer_norm_t(float* out_t, float* out_f, const float* inp, const float* gamma, const float* beta, int rows, int cols,
                        float eps, int dtype);
+/* One launch of the encoder's tiled GEMM kernels (gemm_nt_kernel, gemm_nt_lds_kernel) with every field of their shared epilogue:
+ *   C[b][m][n] = act(Σ_k A[b·strideA + m·lda + k]·W[n][k] + bias[n]) + pos[m][n] + residual[b·strideR + m·ldr + n]
+ * A: flat, a_len >= (batch-1)·strideA + (M-1)·lda + K elements (lda < K: overlapping rows, the implicit-GEMM conv form); W [N][K];
+ * bias [N], pos [M][N], residual (r_len elements) may each be NULL.  residual_in_place != 0: the residual is C itself (fp32 output
+ * only; residual must be NULL, ldr / strideR are taken from ldc / strideC).  act 0 / 1 (GELU, gelu_mode 0 tanh form, 1 erf).
+ * group_n > 0: column n goes to C + (n / group_n)·group_stride + m·ldc + n % group_n (the cross-K/V scatter), group_n % 64 == 0.
+ * dtype: operand rounding of A and W on upload; out_dtype: WM_F32 or dtype, 16-bit results are returned widened.
+ * C (c_len elements, flat) is in and out: the device buffer starts from the caller's values rounded to out_dtype, so whatever the
+ * kernel did not write (guard rows, gaps between batches or groups) comes back as it went in.
+ * kernel_ran receives the WM_GEMM_NT_* answer of the launcher's own dispatch query.  WM_E_ARG with nothing launched and C untouched:
+ * null / non-positive arguments, bad dtype / out_dtype, N % 128 or K % 32, lda / strideA not multiples of 8, ldc / strideC / ldr /
+ * strideR / group_stride not multiples of 4, a bad group_n, residual_in_place without fp32 output, a size that overflows a_len /
+ * c_len / r_len, or a shape that dispatches to the row-panel or full-row kernel.  Known-answer tests. */
+enum { WM_GEMM_NT_REFUSED = -1, WM_GEMM_NT_DIRECT = 0, WM_GEMM_NT_LDS = 1, WM_GEMM_NT_ROWPANEL = 2, WM_GEMM_NT_FULLROW = 3 };
+int wm_op_gemm_nt_epi(float* C, size_t c_len, const float* A, size_t a_len, const float* W, const float* bias, const float* pos,
+                      const float* residual, size_t r_len, int M, int N, int K, int batch, long long lda, long long strideA,
+                      long long ldc, long long strideC, long long ldr, long long strideR, int residual_in_place, int act, int gelu_mode,
+                      int group_n, long long group_stride, int dtype, int out_dtype, int* kernel_ran);
 /* The q_len == 1 path of MultiHeadAttention.forward over cached keys / values (layers.mojo:186-272): per utterance and head
  * s_j = (q·K_j)·0.125 (scale AFTER the dot product), running max from -1e10, p = exp(s - max), o = Σ p_j V_j / Σ p_j.
  * q, out [B, 64·n_heads] fp32; k, v [B, t, 64·n_heads] fp32 host rows, rounded to kv_dtype as the cache holds them.

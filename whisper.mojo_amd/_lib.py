@@ -40,6 +40,7 @@ SYMBOLS = [
     "wm_set_repeat_options", "wm_op_logits_processed", "wm_op_repeat_sets",
     "wm_chunk_table", "wm_transcribe_chunked", "wm_op_chunk_gather", "wm_op_chunk_merge",
     "wm_transcribe_chunked_ts", "wm_op_chunk_segments",
+    "wm_op_gemm_nt_epi",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -248,6 +249,8 @@ def lib():
     L.wm_op_layer_norm.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_float]
     L.wm_op_layer_norm_t.argtypes = [fp] * 5 + [C.c_int, C.c_int, C.c_float, C.c_int]
     L.wm_op_attention_batch.argtypes = [fp] * 4 + [C.c_int] * 4
+    L.wm_op_gemm_nt_epi.argtypes = ([fp, C.c_size_t, fp, C.c_size_t, fp, fp, fp, fp, C.c_size_t] + [C.c_int] * 4 + [C.c_longlong] * 6 +
+                                    [C.c_int] * 4 + [C.c_longlong, C.c_int, C.c_int, ip])
     L.wm_op_gelu.argtypes = [fp, C.c_size_t, C.c_int]
     L.wm_op_softmax_rows.argtypes = [fp, C.c_int, C.c_int]
     L.wm_op_conv1d_k3.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]

@@ -900,23 +900,40 @@ template <typename T> static int launch_fullrow(const GemmParams& p, int batch, 
     return launch_fullrow_t<T, false, false>(p, batch, st);
 }
 
+// Which kernel launch_gemm_nt<T, TO> (sizeof T = operand_bytes, sizeof TO = out_bytes) runs for these parameters, or GEMM_NT_REFUSED
+// with *why set.  Pure host arithmetic: launch_gemm_nt dispatches on this answer, so the two cannot drift apart.
 // Refusals (nothing is launched, WM_LAUNCH_BAD_SHAPE): a fused LayerNorm asked of a shape whose kernel cannot apply it — the result
 // would be a product of un-normalised rows / a missing operand copy — and shapes no kernel tiles (N % 128, K % 32).
-template <typename T, typename TO> int launch_gemm_nt(const GemmParams& p, int batch, hipStream_t st) {
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || batch <= 0) return launch_refuse("gemm_nt: empty problem");
-    if ((p.N & 127) != 0) return launch_refuse("gemm_nt: N must be a multiple of 128 (the dense kernels tile 128 output columns)");
-    if ((p.K & 31) != 0) return launch_refuse("gemm_nt: K must be a multiple of 32 (one MFMA k-step)");
-    if (p.ln_g && !rowpanel_ok((int)sizeof(T), p, batch))  // caller bug (see gemm_nt_fuses_layernorm)
-        return launch_refuse("gemm_nt: LayerNorm fused into the A load asked of a shape only the plain kernels take");
-    if constexpr (sizeof(T) == 2 && sizeof(TO) == 4) {
-        if (fullrow_ok(2, p)) return launch_fullrow<T>(p, batch, st);
-    }
-    if (p.lno_out) return launch_refuse("gemm_nt: LayerNorm of the output rows asked of a shape the full-row kernel does not take");
-    dim3 grid(p.N / 128, (p.M + 127) / 128, batch);
+int gemm_nt_kernel_for(int operand_bytes, int out_bytes, const GemmParams& p, int batch, const char** why) {
+    const char* dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || batch <= 0) return *why = "gemm_nt: empty problem", GEMM_NT_REFUSED;
+    if ((p.N & 127) != 0) return *why = "gemm_nt: N must be a multiple of 128 (the dense kernels tile 128 output columns)", GEMM_NT_REFUSED;
+    if ((p.K & 31) != 0) return *why = "gemm_nt: K must be a multiple of 32 (one MFMA k-step)", GEMM_NT_REFUSED;
+    if (p.ln_g && !rowpanel_ok(operand_bytes, p, batch))  // caller bug (see gemm_nt_fuses_layernorm)
+        return *why = "gemm_nt: LayerNorm fused into the A load asked of a shape only the plain kernels take", GEMM_NT_REFUSED;
+    if (operand_bytes == 2 && out_bytes == 4 && fullrow_ok(2, p)) return GEMM_NT_FULLROW;
+    if (p.lno_out) return *why = "gemm_nt: LayerNorm of the output rows asked of a shape the full-row kernel does not take", GEMM_NT_REFUSED;
     static const bool no_lds = wm_env("WM_GEMM_DIRECT") != nullptr;
+    if (operand_bytes == 2) {
+        if (rowpanel_ok(operand_bytes, p, batch)) return GEMM_NT_ROWPANEL;
+        if (!no_lds && (p.K & 63) == 0) return GEMM_NT_LDS;
+    }
+    return GEMM_NT_DIRECT;
+}
+
+template <typename T, typename TO> int launch_gemm_nt(const GemmParams& p, int batch, hipStream_t st) {
+    const char* why;
+    const int kern = gemm_nt_kernel_for((int)sizeof(T), (int)sizeof(TO), p, batch, &why);
+    if (kern == GEMM_NT_REFUSED) return launch_refuse(why);
+    if constexpr (sizeof(T) == 2 && sizeof(TO) == 4) {
+        if (kern == GEMM_NT_FULLROW) return launch_fullrow<T>(p, batch, st);
+    }
+    dim3 grid(p.N / 128, (p.M + 127) / 128, batch);
     if constexpr (sizeof(T) == 2) {
-        if (rowpanel_ok((int)sizeof(T), p, batch)) return launch_rowpanel<T, TO, 12>(p, st);
-        if (!no_lds && (p.K & 63) == 0) {
+        if (kern == GEMM_NT_ROWPANEL) return launch_rowpanel<T, TO, 12>(p, st);
+        if (kern == GEMM_NT_LDS) {
             static const bool no_remap = wm_env("WM_GEMM_NOXCD") != nullptr;
             GemmParams q = p;
             q.xcd_remap = !no_remap;

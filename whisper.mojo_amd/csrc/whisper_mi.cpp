@@ -5207,6 +5207,96 @@ extern "C" int wm_op_layer_norm_t(float* out_t, float* out_f, const float* inp, 
     return 0;
 }
 
+// One gemm_dispatch call with everything GemmParams offers the two tiled kernels (include/whisper_mi.h).  Device sizes: both kernels
+// read whole 128-row panels of A whatever M is, so A is allocated zero-filled up to the last panel row; bias, pos, residual and C are
+// touched at valid rows only (gemm_epilogue's valid[]), and the checks below hold every offset the epilogue can form inside the
+// caller's lengths, which are also the device lengths.
+extern "C" int wm_op_gemm_nt_epi(float* C, size_t c_len, const float* A, size_t a_len, const float* W, const float* bias, const float* pos,
+                                 const float* residual, size_t r_len, int M, int N, int K, int batch, long long lda, long long strideA,
+                                 long long ldc, long long strideC, long long ldr, long long strideR, int residual_in_place, int act,
+                                 int gelu_mode, int group_n, long long group_stride, int dtype, int out_dtype, int* kernel_ran) {
+    if (!C || !A || !W || !kernel_ran || M <= 0 || N <= 0 || K <= 0 || batch <= 0) return fail(WM_E_ARG, "bad argument");
+    if (M > (1 << 20) || N > (1 << 16) || K > (1 << 16) || batch > 1024) return fail(WM_E_ARG, "problem too large for the op hook");
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    if (out_dtype != WM_F32 && out_dtype != dtype) return fail(WM_E_ARG, "out_dtype must be WM_F32 or dtype");
+    if (N % 128 || K % 32) return fail(WM_E_ARG, "N must be a multiple of 128 and K of 32");
+    if ((act != 0 && act != 1) || (gelu_mode != 0 && gelu_mode != 1)) return fail(WM_E_ARG, "bad act / gelu_mode");
+    const long long LIM = 1ll << 40;  // keeps every product below int64
+    auto ld_ok = [&](long long v, int unit, bool zero_ok) { return (v > 0 || (zero_ok && v == 0)) && v < LIM && v % unit == 0; };
+    // 16-byte operand loads: 8 sixteen-bit or 4 fp32 elements (8 serves both); 16-byte fp32 / 8-byte 16-bit stores and addend loads: 4
+    if (!ld_ok(lda, 8, false) || !ld_ok(strideA, 8, true) || !ld_ok(ldc, 4, false) || !ld_ok(strideC, 4, true))
+        return fail(WM_E_ARG, "lda / strideA must be multiples of 8, ldc / strideC of 4");
+    if (batch > 1 && (strideA == 0 || strideC == 0)) return fail(WM_E_ARG, "batch > 1 needs strideA and strideC");
+    if (group_n < 0 || group_n % 64 || (group_n > 0 && (N % group_n || !ld_ok(group_stride, 4, false))))
+        return fail(WM_E_ARG, "group_n must be a multiple of 64 that divides N, with a group_stride that is a multiple of 4");
+    const int n_grp = group_n > 0 ? N / group_n : 1, row_w = group_n > 0 ? group_n : N;
+    if (ldc < row_w) return fail(WM_E_ARG, "ldc below the row width");
+    if (residual_in_place) {
+        if (out_dtype != WM_F32) return fail(WM_E_ARG, "residual_in_place needs fp32 output");
+        if (residual || group_n > 0) return fail(WM_E_ARG, "residual_in_place takes no separate residual and no column groups");
+        ldr = ldc;
+        strideR = strideC;
+    } else if (residual) {
+        if (!ld_ok(ldr, 4, false) || !ld_ok(strideR, 4, true) || ldr < N || (batch > 1 && strideR == 0))
+            return fail(WM_E_ARG, "ldr must be a multiple of 4 and >= N, strideR a multiple of 4");
+    }
+    const size_t Mp = ((size_t)M + 127) / 128 * 128;
+    const size_t a_need = (size_t)(batch - 1) * strideA + (size_t)(M - 1) * lda + K;
+    const size_t a_dev = (size_t)(batch - 1) * strideA + (Mp - 1) * (size_t)lda + K;
+    const size_t c_need = (size_t)(batch - 1) * strideC + (size_t)(n_grp - 1) * (group_n > 0 ? group_stride : 0) + (size_t)(M - 1) * ldc + row_w;
+    const size_t r_need = (size_t)(batch - 1) * strideR + (size_t)(M - 1) * ldr + N;
+    if (a_len < a_need || c_len < c_need || (residual && r_len < r_need)) return fail(WM_E_ARG, "a size overflows the caller's arrays");
+    if (a_len > ((size_t)1 << 31) || c_len > ((size_t)1 << 31) || r_len > ((size_t)1 << 31)) return fail(WM_E_ARG, "array too large for the op hook");
+    TmpDev t;
+    t.bufs.reserve(8);
+    DevBuf &a = t.add(), &w = t.add(), &c = t.add(), &b = t.add(), &ps = t.add(), &r = t.add();
+    GemmParams p{};
+    p.M = M;
+    p.N = N;
+    p.K = K;
+    p.lda = (long)lda;
+    p.ldw = K;
+    p.ldc = (long)ldc;
+    p.strideA = (long)strideA;
+    p.strideC = (long)strideC;
+    p.ldr = (long)ldr;
+    p.strideR = (long)strideR;
+    p.act = act;
+    p.gelu_mode = gelu_mode;
+    p.group_n = group_n;
+    p.group_stride = group_n > 0 ? (long)group_stride : 0;
+    // addend pointers decide the dispatch (the row-panel kernel takes none): non-null placeholders until the uploads below
+    p.bias = bias;
+    p.pos = pos;
+    p.residual = residual_in_place ? C : residual;
+    *kernel_ran = gemm_nt_kernel_for((int)dt_size(dtype), (int)dt_size(out_dtype), p, batch, nullptr);
+    // the device sizes above are worked out for the two tiled kernels only; the ring kernels have hooks of their own
+    if (*kernel_ran != wm::GEMM_NT_DIRECT && *kernel_ran != wm::GEMM_NT_LDS)
+        return fail(WM_E_ARG, "this shape dispatches to the row-panel / full-row kernel (wm_op_matmul_nt, wm_op_ln_matmul_nt, wm_op_mlp_block)");
+    {  // A: the caller's part, then zeros up to the end of the last 128-row panel
+        std::vector<float> Ap(std::max(a_dev, a_need), 0.f);
+        memcpy(Ap.data(), A, a_need * 4);
+        WMCHK(upload(a, Ap.data(), Ap.size(), dtype));
+    }
+    WMCHK(upload(w, W, (size_t)N * K, dtype));
+    WMCHK(upload(c, C, c_len, out_dtype));
+    if (bias) WMCHK(upload(b, bias, N, WM_F32));
+    if (pos) WMCHK(upload(ps, pos, (size_t)M * N, WM_F32));
+    if (residual && !residual_in_place) WMCHK(upload(r, residual, r_len, WM_F32));
+    p.A = a.p;
+    p.W = w.p;
+    p.C = c.p;
+    p.bias = bias ? b.as<float>() : nullptr;
+    p.pos = pos ? ps.as<float>() : nullptr;
+    p.residual = residual_in_place ? c.as<float>() : residual ? r.as<float>() : nullptr;
+    WMCHK(gemm_dispatch(dtype, out_dtype, p, batch, nullptr));
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned char> h(c_len * dt_size(out_dtype));
+    HIPCHK(hipMemcpy(h.data(), c.p, h.size(), hipMemcpyDeviceToHost));
+    widen_to_f32(h.data(), out_dtype, c_len, C);
+    return 0;
+}
+
 extern "C" int wm_op_mlp_block(float* x, const float* ln_g, const float* ln_b, const float* fc1_w, const float* fc1_b, const float* fc2_w,
                                const float* fc2_b, const float* next_g, const float* next_b, float* xn_out, int M, int d, int ffn,
                                int dtype, int gelu_mode) {

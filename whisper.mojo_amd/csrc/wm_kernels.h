@@ -81,6 +81,10 @@ struct GemmParams {
 bool gemm_nt_fuses_layernorm_out(int operand_bytes, const GemmParams& p);
 // true when launch_gemm_nt<T, *> takes the A-stationary row-panel kernel for these parameters (the only one that can fuse a LayerNorm)
 bool gemm_nt_fuses_layernorm(int operand_bytes, const GemmParams& p, int batch);
+// the kernel launch_gemm_nt<T, TO> runs for (sizeof T, sizeof TO, p, batch): the launcher dispatches on this very function.  why (may be
+// null) receives the refusal text.  The values are include/whisper_mi.h's WM_GEMM_NT_*.
+enum { GEMM_NT_REFUSED = -1, GEMM_NT_DIRECT = 0, GEMM_NT_LDS = 1, GEMM_NT_ROWPANEL = 2, GEMM_NT_FULLROW = 3 };
+int gemm_nt_kernel_for(int operand_bytes, int out_bytes, const GemmParams& p, int batch, const char** why);
 template <typename T> void launch_mel_transpose_pad(const float* mel, void* out, int B, int C, int L, int Cp, hipStream_t st);
 template <typename T, typename TO> int launch_gemm_nt(const GemmParams& p, int batch, hipStream_t st);  // WM_LAUNCH_*
 template <typename T>

@@ -199,6 +199,32 @@ def layer_norm_t(inp, gamma, beta, eps: float = 1e-5, dtype=DT_F32, out_t=None, 
     _lib.check(_lib.lib().wm_op_layer_norm_t(_fp(out_t), _fp(out_f), _fp(x), _fp(g), _fp(b), x.shape[0], x.shape[1], eps, dtype))
 
 
+GEMM_NT_KERNELS = {-1: "refused", 0: "direct", 1: "lds", 2: "rowpanel", 3: "fullrow"}  # whisper_mi.h WM_GEMM_NT_*
+
+
+def gemm_nt_epi(C_flat: np.ndarray, A_flat, W, M, lda=None, batch=1, strideA=0, ldc=None, strideC=0, bias=None, pos=None, residual=None,
+                ldr=0, strideR=0, residual_in_place=False, act=False, gelu_mode: int = GELU_TANH, group_n=0, group_stride=0, dtype=DT_F32,
+                out_dtype=DT_F32) -> str:
+    """One launch of the encoder's tiled GEMM with its whole epilogue (wm_op_gemm_nt_epi, whisper_mi.h): C_flat is the caller's flat
+    float32 array, in and out (cells the kernel does not write keep their values); A_flat a flat array of (batch-1)·strideA +
+    (M-1)·lda + K elements; W [N, K].  -> the kernel that ran, a name of GEMM_NT_KERNELS."""
+    f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32).ravel()
+    W = np.ascontiguousarray(W, np.float32)
+    N, K = W.shape
+    A_flat, bias, pos, residual = f(A_flat), f(bias), f(pos), f(residual)
+    _chk_out(C_flat, (C_flat.size,))
+    if bias is not None and bias.size != N:
+        raise ValueError("bias must have N elements")
+    if pos is not None and pos.size != M * N:
+        raise ValueError("pos must be [M, N]")
+    ran = C.c_int32(-1)
+    _lib.check(_lib.lib().wm_op_gemm_nt_epi(_fp(C_flat), C_flat.size, _fp(A_flat), A_flat.size, _fp(W), _fp(bias), _fp(pos), _fp(residual),
+                                            0 if residual is None else residual.size, M, N, K, batch, K if lda is None else lda, strideA,
+                                            N if ldc is None else ldc, strideC, ldr, strideR, int(bool(residual_in_place)), int(bool(act)),
+                                            gelu_mode, group_n, group_stride, dtype, out_dtype, C.byref(ran)))
+    return GEMM_NT_KERNELS[ran.value]
+
+
 def gelu(t: np.ndarray, mode: int = GELU_TANH):
     """whisper_tensor.mojo:288-308 — in place."""
     _chk_out(t, t.shape)
