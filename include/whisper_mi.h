@@ -586,6 +586,35 @@ int wm_op_chunk_segments(const int32_t* ids, const int32_t* lens, const int32_t*
                          int32_t* merged, int32_t* merged_len, int cap, int32_t* n_seg, double* seg_times, int32_t* seg_range, int seg_cap,
                          double* pairs);
 
+/* ---- PCM at any sample rate and as int16: resampling to 16 kHz on the device -----------------------------------
+ * Every audio entry above takes fp32 PCM at 16 kHz.  These turn rows of fp32 (WM_F32) or int16 (WM_I16, converted as x / 32768 in the
+ * same kernel) PCM at sr_in into that, by band-limited sinc interpolation exactly as torchaudio.functional.resample(x, sr_in, 16000)
+ * defines it with its defaults (lowpass_filter_width 6, rolloff 0.99, sinc_interp_hann).  With g = gcd(sr_in, 16000), orig = sr_in /
+ * g, nw = 16000 / g, base = min(orig, nw) · 0.99, width = ceil(6 · orig / base):
+ *   h[p][k] = sinc(t) · cos(pi t / 12)^2 · base / orig,  t = clamp((-p / nw + (k - width) / orig) · base, -6, 6),  0 <= p < nw,
+ *   0 <= k < 2 · width + orig, computed in float64 and rounded once to fp32;  y[j] = sum_k h[j % nw][k] · x[(j / nw) · orig - width + k]
+ *   with x zero outside the row, accumulated in fp32 in ascending k;  a row of n samples gives ceil(nw · n / orig).
+ * sr_in = 16000 is the identity (orig = nw = 1, width = 0, one tap of 1).  A row's values depend on that row's samples alone.
+ * WM_E_ARG, nothing launched: sr_in <= 0; orig or nw above 1024 (every common rate from 8 kHz to 192 kHz passes); in_dtype outside
+ * {WM_F32, WM_I16}; n_in[b] outside [0, stride_in]; B above 65535.  WM_E_SIZE, nothing launched: stride_out below the longest row's output,
+ * a row that resamples to 2^31 samples or more.
+ *
+ * wm_resample_len (host only): the output length of a row of n_in samples.
+ * wm_resample_pcm: in [B][stride_in] on the host or (in_on_device) the model's device -> out [B][stride_out] fp32 on the host or
+ * (out_on_device) the device, zero at and beyond n_out[b]; n_in and n_out [B] are host arrays.  Runs on the model's stream and returns
+ * when the result is there.  The table of a rate is built on first use and kept in the model.  stride_out <= 2^31 - 1.
+ * wm_op_resample (known-answer tests): resample_kernel alone on host rows; out is in and out — a cell at or beyond n_out[b] keeps the
+ * caller's value; n_out is what the kernel wrote.
+ * wm_op_resample_taps (host only): the table h [nw][2 · width + orig] into taps (cap floats; NULL with cap 0: only the three sizes);
+ * WM_E_SIZE when cap does not hold it. */
+enum { WM_I16 = 3 }; /* an input dtype of the resampling entries alone */
+int wm_resample_len(int64_t n_in, int sr_in, int64_t* n_out);
+int wm_resample_pcm(wm_model* m, const void* in, int in_dtype, int in_on_device, const int32_t* n_in, int B, int64_t stride_in, int sr_in,
+                    float* out, int out_on_device, int64_t stride_out, int32_t* n_out);
+int wm_op_resample(float* out, const void* in, int in_dtype, const int32_t* n_in, int B, int64_t stride_in, int sr_in, int64_t stride_out,
+                   int32_t* n_out);
+int wm_op_resample_taps(int sr_in, float* taps, int64_t cap, int* orig, int* nw, int* width);
+
 /* ---- op-level entry points (host pointers; known-answer tests only) ------------------------------------------
  * Same argument meaning as the reference ops: out-param first, caller-allocated. */
 /* matmul(C, A, B, bias)  whisper_tensor.mojo:151-246 : C[M,N] = A[M,K]·B[N,K]ᵀ (+bias[N], may be NULL).

@@ -431,6 +431,24 @@ public:
         check(rc);
         return out;
     }
+    // PCM at any sample rate, float (WM_F32) or int16_t (WM_I16, scaled by 1 / 32768), [B][stride] on the host with n_samples per row
+    // -> one float vector at 16 kHz per row, resampled on the GPU as torchaudio.functional.resample defines it: what every
+    // PCM entry above takes.  frontend.resample of the Python package.
+    std::vector<std::vector<float>> resample(const void* pcm, int in_dtype, const std::vector<int32_t>& n_samples, int64_t stride, int sampling_rate) const {
+        const int B = (int)n_samples.size();
+        int64_t longest = 1;
+        for (int32_t n : n_samples) {
+            int64_t v = 0;
+            check(wm_resample_len(n, sampling_rate, &v));
+            longest = v > longest ? v : longest;
+        }
+        std::vector<float> out((size_t)(B > 0 ? B : 1) * longest);
+        std::vector<int32_t> n_out(B > 0 ? B : 1);
+        check(wm_resample_pcm(model_, pcm, in_dtype, 0, n_samples.data(), B, stride, sampling_rate, out.data(), 0, longest, n_out.data()));
+        std::vector<std::vector<float>> rows(B);
+        for (int b = 0; b < B; ++b) rows[b].assign(out.begin() + (size_t)b * longest, out.begin() + (size_t)b * longest + n_out[b]);
+        return rows;
+    }
     // chunked long-form transcription (HF's ASR pipeline with chunk_length_s / stride_length_s): PCM [R][stride] at
     // 16 kHz on the host, or (pcm_on_device) on the model's GPU, n_samples per recording; chunk_len / stride_left / stride_right in samples (strides < 0: chunk_len / 6).  Every chunk is
     // decoded on its own in passes of max_batch rows; `sequence` is the recording's stitched ids, `chunks` (want_chunks) every chunk

@@ -41,6 +41,7 @@ SYMBOLS = [
     "wm_chunk_table", "wm_transcribe_chunked", "wm_op_chunk_gather", "wm_op_chunk_merge",
     "wm_transcribe_chunked_ts", "wm_op_chunk_segments",
     "wm_op_gemm_nt_epi",
+    "wm_resample_len", "wm_resample_pcm", "wm_op_resample", "wm_op_resample_taps",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -320,6 +321,11 @@ def lib():
     L.wm_transcribe_chunked_ts.argtypes = [vp, vp, C.c_int, ip] + [C.c_int] * 5 + [C.POINTER(WmDecodeOpts), ip, C.c_int, C.c_int, C.c_int, C.c_double,
                                                                                   ip, ip, C.c_int, ip, dp, ip, C.c_int, dp, ip, ip, fp, ip]
     L.wm_op_chunk_segments.argtypes = [ip, ip, ip, fp, ip] + [C.c_int] * 5 + [C.c_double, C.c_int, ip, ip, C.c_int, ip, dp, ip, C.c_int, dp]
+    i64 = C.c_int64
+    L.wm_resample_len.argtypes = [i64, C.c_int, C.POINTER(i64)]
+    L.wm_resample_pcm.argtypes = [vp, vp, C.c_int, C.c_int, ip, C.c_int, i64, C.c_int, vp, C.c_int, i64, ip]
+    L.wm_op_resample.argtypes = [fp, vp, C.c_int, ip, C.c_int, i64, C.c_int, i64, ip]
+    L.wm_op_resample_taps.argtypes = [C.c_int, fp, i64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -453,6 +459,58 @@ def op_chunk_segments(recordings, word, timestamp_begin, first_special, time_pre
         assert not segs or (segs and segr[r, nseg[r] - 1, 1] == mlen[r] and segr[r, 0, 0] == 0)
         out.append(segs)
     return out
+
+
+WM_F32, WM_I16 = 0, 3  # include/whisper_mi.h: the input dtypes of the resampling entries
+
+
+def resample_len(n_in, sr_in):
+    """wm_resample_len (host only): samples at 16 kHz of a row of n_in samples at sr_in."""
+    n = C.c_int64()
+    check(lib().wm_resample_len(int(n_in), int(sr_in), C.byref(n)))
+    return n.value
+
+
+def resample_taps(sr_in):
+    """wm_op_resample_taps (host only): (h [new, 2 * width + orig] float32, orig, new, width) of the sinc table for sr_in -> 16 kHz."""
+    import numpy as np
+    o, n, w = C.c_int(), C.c_int(), C.c_int()
+    check(lib().wm_op_resample_taps(int(sr_in), None, 0, C.byref(o), C.byref(n), C.byref(w)))
+    h = np.zeros((n.value, 2 * w.value + o.value), np.float32)
+    check(lib().wm_op_resample_taps(int(sr_in), h.ctypes.data_as(C.POINTER(C.c_float)), h.size, C.byref(o), C.byref(n), C.byref(w)))
+    return h, o.value, n.value, w.value
+
+
+def pack_pcm(rows):
+    """Rows of PCM -> ([B, stride] buffer, lengths [B] int32, dtype code): int16 when every row is np.int16, else float32 (an int16 row
+    among float rows is scaled by 1 / 32768 here, which is exact)."""
+    import numpy as np
+    rows = [np.asarray(r).reshape(-1) for r in rows]
+    if not rows:
+        raise ValueError("no recording")
+    i16 = all(r.dtype == np.int16 for r in rows)
+    n = np.asarray([r.size for r in rows], np.int64)
+    if n.max() >= 2 ** 31:
+        raise ValueError("a row has 2^31 samples or more")
+    buf = np.zeros((len(rows), max(1, int(n.max()))), np.int16 if i16 else np.float32)
+    for b, r in enumerate(rows):
+        buf[b, :r.size] = r if i16 or r.dtype != np.int16 else r.astype(np.float32) / 32768.0
+    return buf, n.astype(np.int32), WM_I16 if i16 else WM_F32
+
+
+def op_resample(rows, sr_in, fill=-7.0, stride_out=None, in_dtype=None):
+    """wm_op_resample: resample_kernel alone on rows of float32 or int16 PCM -> (out [B, stride_out] float32, n_out [B]); out starts as
+    `fill` everywhere, so a cell the kernel does not store shows.  stride_out: None = the longest row's output + 8."""
+    import numpy as np
+    buf, n, dt = pack_pcm(rows)
+    if stride_out is None:
+        stride_out = max(resample_len(int(v), sr_in) for v in n) + 8
+    out = np.full((len(rows), int(stride_out)), fill, np.float32)
+    n_out = np.full(len(rows), -1, np.int32)
+    ip = C.POINTER(C.c_int32)
+    check(lib().wm_op_resample(out.ctypes.data_as(C.POINTER(C.c_float)), buf.ctypes.data_as(C.c_void_p), dt if in_dtype is None else int(in_dtype),
+                               n.ctypes.data_as(ip), len(rows), buf.shape[1], int(sr_in), int(stride_out), n_out.ctypes.data_as(ip)))
+    return out, n_out
 
 
 REPEAT_NGRAM_MAX = 64  # wm_kernels.h REPEAT_NGRAM_MAX

@@ -10,6 +10,8 @@
 // spectrogram (no atomics) and a wide clamp / rescale pass.  window_gather_kernel cuts the encoder windows out of it.
 // Chunked long-form: chunk_gather_kernel cuts overlapping chunks of PCM out of long recordings, one 30 s front-end row
 // each, so that every chunk gets its own clamp max as HF's feature extractor gives it.
+// Any sample rate and int16 in: resample_kernel<TIN> turns [B][stride_in] PCM at sr_in into fp32 PCM at 16 kHz by
+// band-limited sinc interpolation (torchaudio.functional.resample's defaults), ahead of everything above.
 #include "wm_kernels.h"
 
 namespace wm {
@@ -158,6 +160,65 @@ __global__ __launch_bounds__(256) void chunk_gather_kernel(const float* __restri
 void launch_chunk_gather(const float* pcm, const int* items, int item_stride, int row0, float* out, int rows, size_t T_max, int N, hipStream_t st) {
     const int gx = std::max(1, std::min(256, (N + 1023) / 1024));
     hipLaunchKernelGGL(chunk_gather_kernel, dim3(gx, rows), dim3(256), 0, st, pcm, items, item_stride, row0, out, T_max, N);
+}
+
+// Polyphase sinc resampler: y[j] = sum_k h[j % nw][k] * x[(j / nw) * orig - width + k], x zero outside [0, n_in[b]).
+// One workgroup = `frames` input frames of one row = frames * nw consecutive outputs; the frames * orig + 2 * width input samples
+// they read are staged in LDS once (every global read predicated on the row's length, int16 widened by an exact / 32768 on the way).
+// The taps come compact and phase-minor from global memory: taps[q * nw + p] = h[p][lo[p] + q] for q < cnt[p], the non-zero span of
+// phase p, so that the lanes of a wave (consecutive outputs = consecutive phases) read consecutive floats.  One fmaf chain per output
+// in ascending k: a value depends on its own row's samples alone.  Sample indices are 64-bit: j * orig passes 2^31 within the hour.
+template <typename TIN> __device__ inline float pcm_to_f32(TIN v);
+template <> __device__ inline float pcm_to_f32<float>(float v) { return v; }
+template <> __device__ inline float pcm_to_f32<int16_t>(int16_t v) { return (float)v * (1.0f / 32768.0f); }
+
+template <typename TIN> __global__ __launch_bounds__(256) void resample_kernel(ResampleParams p) {
+    extern __shared__ float s_x[];
+    const int b = blockIdx.y;
+    const int64_t n = p.n_in[b];
+    const int64_t n_out = (n * p.nw + p.orig - 1) / p.orig;
+    if (blockIdx.x == 0 && threadIdx.x == 0) p.n_out[b] = (int)n_out;
+    const int64_t f0 = (int64_t)blockIdx.x * p.frames, j0 = f0 * p.nw;
+    if (j0 >= n_out) return;  // the whole workgroup: no barrier is left behind
+    const TIN* x = (const TIN*)p.x + (size_t)b * p.stride_in;
+    const int64_t i0 = f0 * p.orig - p.width;
+    const int span = p.frames * p.orig + 2 * p.width;
+    for (int s = threadIdx.x; s < span; s += 256) {
+        const int64_t i = i0 + s;
+        s_x[s] = (i >= 0 && i < n) ? pcm_to_f32<TIN>(x[i]) : 0.f;
+    }
+    __syncthreads();
+    float* y = p.y + (size_t)b * p.stride_out;
+    const int outs = p.frames * p.nw;
+    for (int jl = threadIdx.x; jl < outs; jl += 256) {
+        const int64_t j = j0 + jl;
+        if (j >= n_out) break;
+        const int il = jl / p.nw, ph = jl - il * p.nw;
+        const int lo = p.span[2 * ph], cnt = p.span[2 * ph + 1];  // lo + cnt <= 2 * width + orig: the reads stay inside the staged span
+        const float* xs = s_x + il * p.orig + lo;
+        const float* h = p.taps + ph;
+        float acc = 0.f;
+        for (int q = 0; q < cnt; ++q) acc = fmaf(h[(size_t)q * p.nw], xs[q], acc);
+        y[j] = acc;
+    }
+}
+int resample_frames(int orig, int nw, int width) {
+    const int by_out = std::max(1, 1024 / nw), by_lds = (8192 - 2 * width) / orig;  // <= 1024 outputs and, where a frame allows, <= 32 KB
+    return std::max(1, std::min(by_out, by_lds));
+}
+template <typename TIN> static int launch_resample_t(const ResampleParams& p, int B, int64_t max_n_out, hipStream_t st) {
+    const size_t lds = ((size_t)p.frames * p.orig + 2 * (size_t)p.width) * 4;
+    if (lds > 64 * 1024) return launch_refuse("resample: the input span of one frame does not fit in 64 KB of LDS");
+    const int64_t per = (int64_t)p.frames * p.nw, gx = std::max<int64_t>(1, (max_n_out + per - 1) / per);
+    if (gx > INT32_MAX || B > 65535) return launch_refuse("resample: more workgroups than a grid holds");
+    if (lds > 48 * 1024)
+        if (const hipError_t e = ensure_dyn_lds<&resample_kernel<TIN>>((int)lds); e != hipSuccess) return launch_hip_failed("resample LDS", e);
+    hipLaunchKernelGGL((resample_kernel<TIN>), dim3((unsigned)gx, B), dim3(256), lds, st, p);
+    return WM_LAUNCH_OK;
+}
+int launch_resample(const ResampleParams& p, bool in_i16, int B, int64_t max_n_out, hipStream_t st) {
+    if (B <= 0 || p.orig <= 0 || p.nw <= 0 || p.width < 0 || p.frames <= 0 || max_n_out < 0) return launch_refuse("resample: bad shape");
+    return in_i16 ? launch_resample_t<int16_t>(p, B, max_n_out, st) : launch_resample_t<float>(p, B, max_n_out, st);
 }
 
 }  // namespace wm

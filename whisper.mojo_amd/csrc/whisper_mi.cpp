@@ -288,6 +288,11 @@ struct wm_model {
         bool ready = false;
         int chunk = 16;  // utterances per DFT GEMM
         DevBuf window, dft, fb, band, pcm, lens, frames, spec, logtmp, mel;
+        struct Resampler {  // the sinc table of one input rate, built on first use and kept like the filter bank
+            int sr = 0, orig = 0, nw = 0, width = 0, frames = 0;
+            DevBuf taps, span;
+        };
+        std::vector<Resampler*> rs;
     } fe;
     static const int NSLOT = 8;
     wm_state* cached = nullptr;           // slot 0: the state behind wm_transcribe / wm_transcribe_submit(slot 0)
@@ -650,6 +655,11 @@ extern "C" void wm_model_free(wm_model* m) {
     {
         DevBuf* fb[] = {&m->fe.window, &m->fe.dft, &m->fe.fb, &m->fe.band, &m->fe.pcm, &m->fe.lens, &m->fe.frames, &m->fe.spec, &m->fe.logtmp, &m->fe.mel};
         for (DevBuf* b : fb) b->release();
+        for (auto* r : m->fe.rs) {
+            r->taps.release();
+            r->span.release();
+            delete r;
+        }
         DevBuf* lb[] = {&m->lf.pcm, &m->lf.lens, &m->lf.frames, &m->lf.spec, &m->lf.part, &m->lf.mel, &m->lf.in_mel,
                         &m->lf.win[0], &m->lf.win[1], &m->lf.items[0], &m->lf.items[1]};
         for (DevBuf* b : lb) b->release();
@@ -3437,6 +3447,220 @@ extern "C" int wm_transcribe_pcm_tt(wm_model* m, const float* pcm, const int32_t
     PassAsk ask{m->fe.mel.as<float>(), 1, B, o};
     ask.cols = &cols;
     return run_now(m, ask, PassOut{tokens_out, n_tokens, token_times});
+}
+
+// ---- any sample rate and int16 in: resampling to 16 kHz on the GPU --------------------------------------------------
+// torchaudio.functional.resample(x, sr_in, 16000) with its defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99): the
+// taps are computed in float64 and rounded once; sr_in = 16000 is the identity (one tap of 1, as torchaudio returns its input).
+static const int RS_RATE = 16000, RS_MAX_RATIO = 1024;
+static int resample_ratio(int sr_in, int* orig, int* nw, int* width) {
+    if (sr_in <= 0) return fail(WM_E_ARG, "sr_in = %d must be positive", sr_in);
+    int a = sr_in, b = RS_RATE;
+    while (b) {
+        const int t = a % b;
+        a = b, b = t;
+    }
+    const int64_t o = sr_in / a, n = RS_RATE / a;
+    if (o > RS_MAX_RATIO || n > RS_MAX_RATIO)
+        return fail(WM_E_ARG, "sr_in = %d: the reduced ratio %lld / %lld has a term above %d", sr_in, (long long)o, (long long)n, RS_MAX_RATIO);
+    *orig = (int)o, *nw = (int)n;
+    const double base = (double)std::min(o, n) * 0.99;
+    *width = sr_in == RS_RATE ? 0 : (int)std::ceil(6.0 * (double)o / base);
+    return 0;
+}
+// h [nw][2 * width + orig]
+static void resample_taps_host(int orig, int nw, int width, std::vector<float>& h) {
+    const int K = 2 * width + orig;
+    h.assign((size_t)nw * K, 0.f);
+    if (width == 0) {
+        h[0] = 1.f;
+        return;
+    }
+    const double PI = 3.14159265358979323846, base = (double)std::min(orig, nw) * 0.99, scale = base / (double)orig;
+    for (int p = 0; p < nw; ++p)
+        for (int k = 0; k < K; ++k) {
+            double t = (-(double)p / (double)nw + (double)(k - width) / (double)orig) * base;
+            t = std::min(6.0, std::max(-6.0, t));
+            const double pt = PI * t, s = t == 0.0 ? 1.0 : std::sin(pt) / pt, c = std::cos(pt / 12.0);
+            h[(size_t)p * K + k] = (float)(s * (c * c) * scale);
+        }
+}
+static int resample_len(int64_t n_in, int orig, int nw, int64_t* n_out) {
+    if (n_in < 0) return fail(WM_E_ARG, "n_in = %lld is negative", (long long)n_in);
+    if (n_in > INT64_MAX / RS_MAX_RATIO - RS_MAX_RATIO) return fail(WM_E_SIZE, "n_in = %lld: the output length leaves 64 bits", (long long)n_in);
+    *n_out = (n_in * nw + orig - 1) / orig;
+    return 0;
+}
+extern "C" int wm_resample_len(int64_t n_in, int sr_in, int64_t* n_out) {
+    if (!n_out) return fail(WM_E_ARG, "bad argument");
+    int orig, nw, width;
+    WMCHK(resample_ratio(sr_in, &orig, &nw, &width));
+    return resample_len(n_in, orig, nw, n_out);
+}
+extern "C" int wm_op_resample_taps(int sr_in, float* taps, int64_t cap, int* orig, int* nw, int* width) {
+    if (!orig || !nw || !width || cap < 0 || (cap > 0 && !taps)) return fail(WM_E_ARG, "bad argument");
+    WMCHK(resample_ratio(sr_in, orig, nw, width));
+    if (!taps) return 0;
+    const int64_t need = (int64_t)*nw * (2 * *width + *orig);
+    if (cap < need) return fail(WM_E_SIZE, "cap = %lld is smaller than the table of %lld taps", (long long)cap, (long long)need);
+    std::vector<float> h;
+    resample_taps_host(*orig, *nw, *width, h);
+    memcpy(taps, h.data(), h.size() * 4);
+    return 0;
+}
+// the table of one sr_in on the device, in the layout resample_kernel reads (wm_kernels.h ResampleParams)
+static int resampler_build(wm_model::Frontend::Resampler& r, int sr_in) {
+    WMCHK(resample_ratio(sr_in, &r.orig, &r.nw, &r.width));
+    std::vector<float> h;
+    resample_taps_host(r.orig, r.nw, r.width, h);
+    const int K = 2 * r.width + r.orig;
+    std::vector<int32_t> span(2 * (size_t)r.nw, 0);
+    int most = 1;
+    for (int p = 0; p < r.nw; ++p) {
+        int lo = K, hi = 0;
+        for (int k = 0; k < K; ++k)
+            if (h[(size_t)p * K + k] != 0.f) lo = std::min(lo, k), hi = k + 1;
+        if (lo < hi) span[2 * p] = lo, span[2 * p + 1] = hi - lo;
+        most = std::max(most, span[2 * p + 1]);
+    }
+    std::vector<float> compact((size_t)most * r.nw, 0.f);
+    for (int p = 0; p < r.nw; ++p)
+        for (int q = 0; q < span[2 * p + 1]; ++q) compact[(size_t)q * r.nw + p] = h[(size_t)p * K + span[2 * p] + q];
+    WMCHK(r.taps.alloc(compact.size() * 4));
+    WMCHK(r.span.alloc(span.size() * 4));
+    HIPCHK(hipMemcpy(r.taps.p, compact.data(), compact.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(r.span.p, span.data(), span.size() * 4, hipMemcpyHostToDevice));
+    r.frames = resample_frames(r.orig, r.nw, r.width);
+    r.sr = sr_in;
+    return 0;
+}
+// what both entries refuse before anything is launched; n_out [B] and the longest row's output length
+static int resample_check(const void* in, int in_dtype, const int32_t* n_in, int B, int64_t stride_in, int sr_in, const void* out, int64_t stride_out,
+                          int32_t* n_out, int64_t* longest) {
+    if (!in || !out || !n_in || !n_out || B <= 0 || stride_in <= 0 || stride_out <= 0) return fail(WM_E_ARG, "bad argument");
+    int orig, nw, width;
+    WMCHK(resample_ratio(sr_in, &orig, &nw, &width));
+    if (in_dtype != WM_F32 && in_dtype != WM_I16) return fail(WM_E_ARG, "in_dtype = %d is neither WM_F32 nor WM_I16", in_dtype);
+    if (B > 65535) return fail(WM_E_ARG, "B = %d rows exceed 65535", B);
+    *longest = 0;
+    for (int b = 0; b < B; ++b) {
+        if (n_in[b] < 0 || n_in[b] > stride_in) return fail(WM_E_ARG, "n_in[%d] = %d outside [0, stride_in = %lld]", b, n_in[b], (long long)stride_in);
+        int64_t n = 0;
+        WMCHK(resample_len(n_in[b], orig, nw, &n));
+        if (n > INT32_MAX) return fail(WM_E_SIZE, "row %d resamples to %lld samples, more than 2^31 - 1", b, (long long)n);
+        *longest = std::max(*longest, n);
+    }
+    if (*longest > stride_out) return fail(WM_E_SIZE, "stride_out = %lld is smaller than the longest row's %lld samples", (long long)stride_out, (long long)*longest);
+    for (int b = 0; b < B; ++b) n_out[b] = (int32_t)(((int64_t)n_in[b] * nw + orig - 1) / orig);
+    return 0;
+}
+static int resample_launch(const wm_model::Frontend::Resampler& r, const void* d_in, int in_dtype, const int* d_nin, int B, int64_t stride_in, float* d_out,
+                           int64_t stride_out, int* d_nout, int64_t longest, hipStream_t st) {
+    ResampleParams p{};
+    p.x = d_in, p.y = d_out, p.n_in = d_nin, p.n_out = d_nout;
+    p.stride_in = (size_t)stride_in, p.stride_out = (size_t)stride_out;
+    p.taps = r.taps.as<float>(), p.span = r.span.as<int>();
+    p.orig = r.orig, p.nw = r.nw, p.width = r.width, p.frames = r.frames;
+    LCHK(launch_resample(p, in_dtype == WM_I16, B, longest, st));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+extern "C" int wm_op_resample(float* out, const void* in, int in_dtype, const int32_t* n_in, int B, int64_t stride_in, int sr_in, int64_t stride_out,
+                              int32_t* n_out) {
+    if (!n_out) return fail(WM_E_ARG, "bad argument");
+    int64_t longest = 0;
+    std::vector<int32_t> no(std::max(B, 1));
+    WMCHK(resample_check(in, in_dtype, n_in, B, stride_in, sr_in, out, stride_out, no.data(), &longest));
+    wm_model::Frontend::Resampler r;
+    TmpDev tmp;
+    tmp.bufs.reserve(8);
+    DevBuf &din = tmp.add(), &dout = tmp.add(), &dni = tmp.add(), &dno = tmp.add();
+    const size_t es = in_dtype == WM_I16 ? 2 : 4, nin = (size_t)B * stride_in, nout = (size_t)B * stride_out;
+    int rc = resampler_build(r, sr_in);
+    if (!rc) rc = din.alloc(nin * es);
+    if (!rc) rc = dout.alloc(nout * 4);
+    if (!rc) rc = dni.alloc((size_t)B * 4);
+    if (!rc) rc = dno.alloc((size_t)B * 4);
+    auto run = [&]() -> int {
+        HIPCHK(hipMemcpy(din.p, in, nin * es, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dout.p, out, nout * 4, hipMemcpyHostToDevice));  // in and out: a cell the kernel does not store keeps the caller's value
+        HIPCHK(hipMemcpy(dni.p, n_in, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dno.p, n_out, (size_t)B * 4, hipMemcpyHostToDevice));
+        WMCHK(resample_launch(r, din.p, in_dtype, dni.as<int>(), B, stride_in, dout.as<float>(), stride_out, dno.as<int>(), longest, nullptr));
+        HIPCHK(hipMemcpy(out, dout.p, nout * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(n_out, dno.p, (size_t)B * 4, hipMemcpyDeviceToHost));  // what the kernel computed, not the host's copy
+        return 0;
+    };
+    if (!rc) rc = run();
+    r.taps.release();
+    r.span.release();
+    return rc;
+}
+static int resampler_get(wm_model* m, int sr_in, wm_model::Frontend::Resampler** out) {
+    for (auto* r : m->fe.rs)
+        if (r->sr == sr_in) {
+            *out = r;
+            return 0;
+        }
+    auto* r = new wm_model::Frontend::Resampler();
+    const int rc = resampler_build(*r, sr_in);
+    if (rc) {
+        r->taps.release();
+        r->span.release();
+        delete r;
+        return rc;
+    }
+    m->fe.rs.push_back(r);
+    *out = r;
+    return 0;
+}
+extern "C" int wm_resample_pcm(wm_model* m, const void* in, int in_dtype, int in_on_device, const int32_t* n_in, int B, int64_t stride_in, int sr_in,
+                               float* out, int out_on_device, int64_t stride_out, int32_t* n_out) {
+    if (!m) return fail(WM_E_ARG, "null model");
+    if (!n_out) return fail(WM_E_ARG, "bad argument");
+    int64_t longest = 0;
+    std::vector<int32_t> no(std::max(B, 1));
+    WMCHK(resample_check(in, in_dtype, n_in, B, stride_in, sr_in, out, stride_out, no.data(), &longest));
+    if (stride_out > INT32_MAX) return fail(WM_E_SIZE, "stride_out = %lld exceeds 2^31 - 1", (long long)stride_out);
+    HIPCHK(hipSetDevice(m->device));
+    wm_model::Frontend::Resampler* r = nullptr;
+    WMCHK(resampler_get(m, sr_in, &r));
+    hipStream_t st = m->stream;
+    TmpDev tmp;
+    tmp.bufs.reserve(8);
+    DevBuf &din = tmp.add(), &dout = tmp.add(), &dni = tmp.add(), &dno = tmp.add();
+    const size_t es = in_dtype == WM_I16 ? 2 : 4, nin = (size_t)B * stride_in, nout = (size_t)B * stride_out;
+    auto run = [&]() -> int {
+        const void* d_in = in;
+        float* d_out = out;
+        if (!in_on_device) {
+            WMCHK(din.alloc(nin * es));
+            HIPCHK(hipMemcpyAsync(din.p, in, nin * es, hipMemcpyHostToDevice, st));
+            d_in = din.p;
+        }
+        if (!out_on_device) {
+            WMCHK(dout.alloc(nout * 4));
+            d_out = dout.as<float>();
+        }
+        WMCHK(dni.alloc((size_t)B * 4));
+        WMCHK(dno.alloc((size_t)B * 4));
+        HIPCHK(hipMemcpyAsync(dni.p, n_in, (size_t)B * 4, hipMemcpyHostToDevice, st));
+        WMCHK(resample_launch(*r, d_in, in_dtype, dni.as<int>(), B, stride_in, d_out, stride_out, dno.as<int>(), longest, st));
+        launch_zero_tails(d_out, dno.as<int>(), B, (int)stride_out, st);  // the model path hands on rows that are zero past their length
+        HIPCHK(hipGetLastError());
+        if (!out_on_device) HIPCHK(hipMemcpyAsync(out, dout.p, nout * 4, hipMemcpyDeviceToHost, st));
+        return 0;
+    };
+    const int rc = run();
+    const std::string err = g_err;
+    const hipError_t e = hipStreamSynchronize(st);  // the scratch is released on return, and no[] is the caller's from here
+    if (rc) {
+        g_err = err;
+        return rc;
+    }
+    if (e != hipSuccess) return fail(WM_E_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    std::copy(no.begin(), no.begin() + B, n_out);
+    return 0;
 }
 
 // ---- chunked long-form transcription -----------------------------------------------------------------------------

@@ -505,6 +505,21 @@ void launch_mel_norm(const float* logmel, float* out, int B, int n, hipStream_t 
 // chunked long-form: rows [row0, row0 + rows) of the item table (item_stride ints each: recording, start, len, ...) cut
 // out of pcm [R][T_max] into out [rows][N], zero-padded past len
 void launch_chunk_gather(const float* pcm, const int* items, int item_stride, int row0, float* out, int rows, size_t T_max, int N, hipStream_t st);
+// any sample rate / int16 -> fp32 16 kHz: resample_kernel.  x [B][stride_in] float or int16 with n_in[b] samples ->
+// y [B][stride_out] and n_out[b] = ceil(nw * n_in[b] / orig); cells of y at or beyond n_out[b] are not stored.  taps: compact and
+// phase-minor, taps[q * nw + p] = h[p][lo[p] + q]; span [nw][2] = (lo, cnt), each phase's non-zero taps.  frames = resample_frames().
+struct ResampleParams {
+    const void* x;
+    float* y;
+    const int* n_in;
+    int* n_out;
+    size_t stride_in, stride_out;
+    const float* taps;
+    const int* span;
+    int orig, nw, width, frames;
+};
+int resample_frames(int orig, int nw, int width);  // input frames per workgroup
+int launch_resample(const ResampleParams& p, bool in_i16, int B, int64_t max_n_out, hipStream_t st);  // WM_LAUNCH_*
 // the stitch (kernels_chunked.hip): packed rows [n][1 + stride] = (count, ids), recording r owning rows [rec_off[r], rec_off[r + 1]) ->
 // merged [n_rec][cap], merged_len [n_rec].  One workgroup per recording; LDS 2 · stride ints + 3 KB.  WM_LAUNCH_*
 static const int CHUNK_MERGE_MAX_IDS = 2048;

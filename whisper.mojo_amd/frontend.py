@@ -23,9 +23,54 @@ def _pack(audios: Sequence[np.ndarray]):
     return buf, n, stride
 
 
-def log_mel(model, audios: Sequence[np.ndarray]) -> np.ndarray:
+def _is_16k_f32(audios, sampling_rate) -> bool:
+    """True for what every entry took before resampling existed: 16 kHz and no int16 row.  That input takes the old path untouched."""
+    if isinstance(sampling_rate, bool) or int(sampling_rate) != sampling_rate:
+        raise ValueError(f"sampling_rate must be an integer (got {sampling_rate!r})")
+    if int(sampling_rate) <= 0:
+        raise ValueError(f"sampling_rate must be positive (got {sampling_rate})")
+    return int(sampling_rate) == SAMPLING_RATE and not any(isinstance(a, np.ndarray) and a.dtype == np.int16 for a in audios)
+
+
+def _resample(model, audios, sampling_rate, on_device: bool):
+    """wm_resample_pcm (DESIGN §33): rows of float32 or int16 PCM at sampling_rate -> 16 kHz float32 [B, stride] with lengths [B];
+    on_device: a torch CUDA tensor on the model's GPU (the samples stay there), else a numpy array."""
+    if model._h is None:
+        raise _lib.WhisperMiError("model not loaded")
+    buf, n, dt = _lib.pack_pcm(audios)
+    stride = max(1, max(_lib.resample_len(int(v), sampling_rate) for v in n))
+    n_out = np.zeros(len(n), np.int32)
+    if on_device:
+        import torch
+        out = torch.empty((len(n), stride), dtype=torch.float32, device=f"cuda:{model.device}")
+        torch.cuda.current_stream(out.device).synchronize()
+        ptr = C.c_void_p(out.data_ptr())
+    else:
+        out = np.empty((len(n), stride), np.float32)
+        ptr = out.ctypes.data_as(C.c_void_p)
+    ip = C.POINTER(C.c_int32)
+    _lib.check(_lib.lib().wm_resample_pcm(model._h, buf.ctypes.data_as(C.c_void_p), dt, 0, n.ctypes.data_as(ip), len(n), buf.shape[1],
+                                          int(sampling_rate), ptr, int(on_device), stride, n_out.ctypes.data_as(ip)))
+    return out, n_out
+
+
+def resample(model, audios: Sequence[np.ndarray], sampling_rate: int) -> List[np.ndarray]:
+    """PCM at any sample rate, float32 or np.int16 (scaled by 1 / 32768), -> a list of float32 arrays at 16 kHz, resampled on the GPU
+    by band-limited sinc interpolation as torchaudio.functional.resample(x, sampling_rate, 16000) defines it.  What every
+    audio entry does with sampling_rate= / int16 input before anything else."""
+    _is_16k_f32(audios, sampling_rate)
+    out, n = _resample(model, audios, sampling_rate, False)
+    return [out[b, :n[b]].copy() for b in range(len(n))]
+
+
+def _at_16k(model, audios, sampling_rate):
+    return audios if _is_16k_f32(audios, sampling_rate) else resample(model, audios, sampling_rate)
+
+
+def log_mel(model, audios: Sequence[np.ndarray], sampling_rate: int = SAMPLING_RATE) -> np.ndarray:
     """audios: list of 1-D float arrays at 16 kHz (any lengths; padded / trimmed to 30 s like WhisperProcessor) ->
-    [B, n_mels, 2*n_audio_ctx] float32."""
+    [B, n_mels, 2*n_audio_ctx] float32.  sampling_rate / np.int16 rows: resampled on the GPU first (resample)."""
+    audios = _at_16k(model, audios, sampling_rate)
     buf, n, stride = _pack(audios)
     cfg = model.config
     out = np.empty((len(audios), cfg.n_mels, cfg.n_frames), np.float32)
@@ -36,11 +81,12 @@ def log_mel(model, audios: Sequence[np.ndarray]) -> np.ndarray:
 
 def transcribe_audio(model, audios: Sequence[np.ndarray], prompt: Sequence[int] = PROMPT, eot: int = EOT,
                      max_loop: int = MAX_LOOP, ignore_eot: bool = False, return_token_timestamps: bool = False,
-                     repetition_penalty=None, no_repeat_ngram_size=None):
-    """PCM in, token ids out (the mel never leaves the GPU).  return_token_timestamps: (ids, times) with the time in seconds
+                     repetition_penalty=None, no_repeat_ngram_size=None, sampling_rate: int = SAMPLING_RATE):
+    """PCM in, token ids out (the mel never leaves the GPU).  sampling_rate / np.int16 rows: resampled on the GPU first (resample).  return_token_timestamps: (ids, times) with the time in seconds
     each id was spoken (needs model.set_alignment_heads); the attention columns are cropped to each clip's real audio.
     repetition_penalty / no_repeat_ngram_size: as Whisper.transcribe_batch."""
     model._set_repeat(_lib.repeat_args(repetition_penalty, no_repeat_ngram_size))
+    audios = _at_16k(model, audios, sampling_rate)
     buf, n, stride = _pack(audios)
     p = np.asarray(prompt, np.int32)
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
@@ -58,8 +104,11 @@ def transcribe_audio(model, audios: Sequence[np.ndarray], prompt: Sequence[int] 
     return [toks[b, :cnt[b]].tolist() for b in range(len(audios))]
 
 
-def score_audio(model, audios: Sequence[np.ndarray], ids, context_len=None, return_top_ids: bool = False):
-    """PCM in, Whisper.score out (wm_score_pcm: the mel never leaves the GPU).  Arguments and result as Whisper.score."""
+def score_audio(model, audios: Sequence[np.ndarray], ids, context_len=None, return_top_ids: bool = False,
+                sampling_rate: int = SAMPLING_RATE):
+    """PCM in, Whisper.score out (wm_score_pcm: the mel never leaves the GPU).  Arguments and result as Whisper.score.
+    sampling_rate / np.int16 rows: resampled on the GPU first (resample)."""
+    audios = _at_16k(model, audios, sampling_rate)
     buf, n, stride = _pack(audios)
     B = len(audios)
     tab, lens, ctx = _lib.score_args(ids, context_len, B, model.config.vocab_size, model.config.n_text_ctx, model.max_batch)
@@ -73,9 +122,12 @@ def score_audio(model, audios: Sequence[np.ndarray], ids, context_len=None, retu
     return model._score_out(tab, lens, lps, top, sm, avg, return_top_ids)
 
 
-def align_audio(model, audios: Sequence[np.ndarray], ids, context_len=None, return_logprobs: bool = False):
+def align_audio(model, audios: Sequence[np.ndarray], ids, context_len=None, return_logprobs: bool = False,
+                sampling_rate: int = SAMPLING_RATE):
     """PCM in, Whisper.align out (wm_align_pcm: the mel never leaves the GPU; n_frames from the clip lengths, as
-    transcribe_audio(return_token_timestamps=True)).  Arguments and result as Whisper.align."""
+    transcribe_audio(return_token_timestamps=True)).  Arguments and result as Whisper.align.
+    sampling_rate / np.int16 rows: resampled on the GPU first (resample); the frame counts are those of the 16 kHz samples."""
+    audios = _at_16k(model, audios, sampling_rate)
     buf, n, stride = _pack(audios)
     B = len(audios)
     tab, lens, ctx, _ = _lib.align_args(ids, context_len, None, B, model.config.vocab_size, model.config.n_text_ctx, model.max_batch,
@@ -89,9 +141,11 @@ def align_audio(model, audios: Sequence[np.ndarray], ids, context_len=None, retu
     return model._align_out(0, tab, lens, ctx, times, lp)
 
 
-def log_mel_long(model, audios: Sequence[np.ndarray]):
+def log_mel_long(model, audios: Sequence[np.ndarray], sampling_rate: int = SAMPLING_RATE):
     """Log-mel of audio of any length, HF WhisperFeatureExtractor(truncation=False, padding="longest",
-    return_attention_mask=True): (features [B, n_mels, longest // 160] float32, n_frames [B] = the mask's ones)."""
+    return_attention_mask=True): (features [B, n_mels, longest // 160] float32, n_frames [B] = the mask's ones).
+    sampling_rate / np.int16 rows: resampled on the GPU first (resample); longest counts 16 kHz samples."""
+    audios = _at_16k(model, audios, sampling_rate)
     buf, n, stride = _pack(audios)
     stride = max(stride, 201)
     if buf.shape[1] < stride:
@@ -110,9 +164,10 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
                                condition_on_prev_tokens: bool = False, prompt_condition_type: str = "first-segment",
                                prev_sot_token: int = 50361, logprob_threshold=None, no_speech_threshold=None, no_speech_token=None,
                                detect_language=None, return_token_timestamps: bool = False, repetition_penalty=None,
-                               no_repeat_ngram_size=None):
+                               no_repeat_ngram_size=None, sampling_rate: int = SAMPLING_RATE):
     """Sequential long-form transcription of 16 kHz PCM of any length (HF generate's long-form path), the long
-    log-mel never leaving the GPU.  repetition_penalty / no_repeat_ngram_size: as Whisper.transcribe_long_form.
+    log-mel never leaving the GPU.  sampling_rate / np.int16 rows: resampled on the GPU first (resample; the 16 kHz samples pass
+    through host memory); all times are seconds of audio.  repetition_penalty / no_repeat_ngram_size: as Whisper.transcribe_long_form.
     return_token_timestamps: as Whisper.transcribe_long_form ("token_times" per recording, "token_timestamps" per segment; not with
     the thresholds).  prompt_ids / condition_on_prev_tokens / prompt_condition_type / logprob_threshold /
     no_speech_threshold / no_speech_token / detect_language (then the detected ids [B] are returned as the last element): as
@@ -130,6 +185,7 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
         lang_list = _lib.lang_args(detect_language, model.config.vocab_size)
         if len(prompt) < 2:
             raise ValueError("detect_language needs at least two initial ids (<|startoftranscript|> and the language slot)")
+    audios = _at_16k(model, audios, sampling_rate)
     buf, n, stride = _pack(audios)
     stride = max(stride, 201)
     if buf.shape[1] < stride:
@@ -166,7 +222,7 @@ def transcribe_audio_chunked(model, audios, chunk_length_s: float = 30.0, stride
                              prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP, suppress_tokens: Sequence[int] = (),
                              begin_suppress_tokens: Sequence[int] = (), timestamps=None, detect_language=None, repetition_penalty=None,
                              no_repeat_ngram_size=None, first_special: int = _lib.FIRST_SPECIAL, return_stats: bool = False, n_samples=None,
-                             return_timestamps=False, time_precision=None, tokenizer=None):
+                             return_timestamps=False, time_precision=None, tokenizer=None, sampling_rate: int = SAMPLING_RATE):
     """Chunked long-form transcription of 16 kHz PCM of any length (HF's ASR pipeline with chunk_length_s / stride_length_s /
     batch_size = max_batch): every recording is cut into overlapping chunks (HF chunk_iter), the chunks of all recordings
     are decoded on their own in passes of up to max_batch rows, two passes in flight, and each recording's id lists are stitched on
@@ -190,7 +246,10 @@ def transcribe_audio_chunked(model, audios, chunk_length_s: float = 30.0, stride
     tokenizer= also "words" (tokenizer.collate_words); with return_chunks every chunk tuple ends with its token times.  "word" needs
     two mel frames of audio in every chunk: a chunk shorter than 320 samples (the tail of a recording under stride_length_s=0, or a
     recording shorter than 20 ms) makes the library refuse the whole call, where the other two modes accept it.
-    time_precision: seconds per timestamp id (None: window seconds / n_audio_ctx)."""
+    time_precision: seconds per timestamp id (None: window seconds / n_audio_ctx).
+    sampling_rate / np.int16 host arrays: the raw samples go up once, are resampled to 16 kHz on the GPU and stay there
+    (the device-PCM path below); chunk_length_s, stride_length_s and every returned time are seconds of audio.  Device PCM is 16 kHz
+    float32 already."""
     if not isinstance(return_timestamps, (bool, np.bool_)) and not (isinstance(return_timestamps, str) and return_timestamps == "word"):
         raise ValueError('return_timestamps is False, True or "word"')  # 0 / 1 would pass an `in` test by equality: bools only
     ts_mode = 2 if isinstance(return_timestamps, str) else 1 if return_timestamps else 0
@@ -198,11 +257,24 @@ def transcribe_audio_chunked(model, audios, chunk_length_s: float = 30.0, stride
         raise ValueError("return_timestamps needs timestamps=(timestamp_begin, no_timestamps_id, max_initial_timestamp_index)")
     if ts_mode == 2 and detect_language is not None:
         raise ValueError('return_timestamps="word" does not combine with detect_language')
-    dev = None
+    dev, was_single = None, None
     if not isinstance(audios, (np.ndarray, list, tuple)):
         import torch
         if isinstance(audios, torch.Tensor) and audios.is_cuda:
             dev = audios
+    if dev is not None and int(sampling_rate) != SAMPLING_RATE:
+        raise ValueError("device PCM is 16 kHz float32; sampling_rate goes with host arrays")
+    if dev is None:
+        if n_samples is not None:
+            raise ValueError("n_samples goes with device PCM; host arrays carry their own lengths")
+        single = isinstance(audios, np.ndarray) and audios.ndim == 1
+        if single:
+            audios = [audios]
+        if not len(audios):
+            raise ValueError("no recording")
+        if not _is_16k_f32(audios, sampling_rate):
+            dev, n_samples = _resample(model, audios, sampling_rate, True)
+            was_single = single
     if dev is not None:
         single = dev.dim() == 1
         dev = (dev[None] if single else dev).contiguous().float()
@@ -215,15 +287,9 @@ def transcribe_audio_chunked(model, audios, chunk_length_s: float = 30.0, stride
         import torch
         torch.cuda.current_stream(dev.device).synchronize()  # the library reads it on its own HIP stream
         pcm_ptr, on_dev = C.c_void_p(dev.data_ptr()), 1
+        single = was_single if was_single is not None else single
     else:
-        if n_samples is not None:
-            raise ValueError("n_samples goes with device PCM; host arrays carry their own lengths")
-        single = isinstance(audios, np.ndarray) and audios.ndim == 1
-        if single:
-            audios = [audios]
         audios = [np.asarray(a, np.float32).reshape(-1) for a in audios]
-        if not audios:
-            raise ValueError("no recording")
         buf, n, stride = _pack(audios)
         n_rec = len(audios)
         pcm_ptr, on_dev = buf.ctypes.data_as(C.c_void_p), 0

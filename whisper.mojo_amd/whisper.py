@@ -520,7 +520,7 @@ class Whisper:
         return (out, stats) if return_stats else out
 
     def transcribe_chunked(self, pcm, chunk_length_s: float = 30.0, stride_length_s=None, return_chunks: bool = False, return_timestamps=False,
-                           **decode_options):
+                           sampling_rate: int = 16000, **decode_options):
         """Chunked long-form transcription (HF's ASR pipeline with chunk_length_s / stride_length_s): pcm — one 1-D array
         of 16 kHz samples, a list of them, or a CUDA tensor [R, stride] with n_samples= — is cut into overlapping chunks, the chunks of all recordings fill passes of max_batch
         rows, and every recording's ids are stitched on the GPU.  decode_options: prompt, eot, max_loop, suppress_tokens,
@@ -528,10 +528,10 @@ class Whisper:
         chunk) and first_special.  -> per recording {"sequence": ids, "chunks": [(start_s, len_s, stride_l_s, stride_r_s, ids_k)]
         (with return_chunks)}; see frontend.transcribe_audio_chunked.  return_timestamps: False, True (HF's segments: "segments":
         [{"timestamp": (start, end | None), "ids"}]) or "word" (also "token_timestamps" per segment, "words" with tokenizer=;
-        DESIGN §31)."""
+        DESIGN §31).  sampling_rate / np.int16 host arrays: resampled to 16 kHz on the GPU, where the samples stay."""
         from . import frontend
         return frontend.transcribe_audio_chunked(self, pcm, chunk_length_s, stride_length_s, return_chunks, return_timestamps=return_timestamps,
-                                                 **decode_options)
+                                                 sampling_rate=sampling_rate, **decode_options)
 
     def alignment_weights(self, slot: int = 0) -> np.ndarray:
         """The alignment heads' cross-attention probabilities of the slot's last timestamp pass (slot 0: transcribe_batch),
