@@ -309,6 +309,28 @@ int wm_score_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B,
  * for; like every call on a wm_model it is not synchronised — threads that share a model serialise set + submit themselves. */
 int wm_set_repeat_options(wm_model* m, float repetition_penalty, int no_repeat_ngram_size);
 
+/* ---- sequence bias and bad words ---------------------------------------------------------------------------------
+ * HF generate's sequence_bias (SequenceBiasLogitsProcessor) and bad_words_ids (NoBadWordsLogitsProcessor), given as ids, for every
+ * greedy pass asked for from now on — the passes wm_set_repeat_options names, with the same rules: model-wide, it persists until the
+ * next call, a submit held for a coalesce = 2 partner keeps the table in force when it was made and pairs only with a submit made
+ * under the same table, and replacing the table changes no pass that was already asked for.
+ * Sequence q of sequence_bias is ids[offsets[q] .. offsets[q + 1]) with bias[q]; bad word q is bad_ids[bad_offsets[q] ..
+ * bad_offsets[q + 1]).  At every step, with hist the row's decoder ids so far and z its fp32 logits:
+ *   1. a bias vector starts at 0; every length-1 sequence sets its id's entry; then, in the caller's order, every sequence s with
+ *      2 <= len(s) <= len(hist) whose first len(s) - 1 ids are hist's last adds its bias to the entry of its last id (sequences that
+ *      end in the same id are summed in that order, in fp32, as HF sums them); z += bias;
+ *   2. repetition_penalty and no_repeat_ngram_size (wm_set_repeat_options) on the biased row;
+ *   3. bad words: the same matching, -inf in place of the sum; a length-1 bad word equal to the pass's eot is dropped (HF's filter);
+ *   4. the suppress masks, the timestamp rules, the arg-max and the log-prob sums see the processed row.
+ * The no-speech probe, language detection, wm_score and wm_align read unprocessed logits; a long-form window's or a chunk's pass sees
+ * that pass's decoder ids only.  It runs on the device inside the captured step: the step's arg-max launch matches every sequence
+ * against the row's new history tail, the logits kernel reads the row's hits; a pass with both lists empty launches exactly what it
+ * did before.  n_seq = n_bad = 0 switches it off (the default; the pointers may be NULL).
+ * WM_E_ARG, with the setting unchanged: an id outside the vocabulary, a sequence of 0 or more than 32 ids, more than 1024 sequences
+ * over the two lists, a duplicate sequence within a list, a bias that is NaN or +inf (-inf is allowed), offsets that do not start at 0. */
+int wm_set_sequence_bias(wm_model* m, const int32_t* ids, const int32_t* offsets, const float* bias, int n_seq, const int32_t* bad_ids,
+                         const int32_t* bad_offsets, int n_bad);
+
 /* ---- token-level timestamps ---------------------------------------------------------------------------------
  * When each id was spoken, with the semantics of HF generate(..., return_token_timestamps=True)
  * (WhisperGenerationMixin._extract_token_timestamps, time_precision 0.02, median_filter_width 7, num_input_ids = n_prompt): the
@@ -723,6 +745,23 @@ int wm_op_logits_processed(float* logits, int32_t* ids, float* logprob, const fl
  * [steps + 1][B][ceil(vocab / 32)] — entry 0 after the init, entry s after step s.  1 <= prompt_len[b] <= n_ids[b] <= stride. */
 int wm_op_repeat_sets(uint32_t* seen, uint32_t* ban, const int32_t* tokens, const int32_t* prompt_len, const int32_t* n_ids, int B, int stride,
                       int vocab, int ngram, int steps);
+/* wm_op_logits_processed on the sequence-bias instantiation of the same kernel variant, with given hit state: hit
+ * [B][ceil(N / 32)] (id t = bit (t & 31) of word t >> 5), the slots' ids slot_id [n_slots] (ascending, 1 <= n_slots <= 1024) and per
+ * row and slot the summed bias slot_bias [B][n_slots] and slot_flags [B][n_slots] (bit 0: on, bit 1: a ban).  Where row b's bit of id t
+ * is set, t's slot adds its bias before the penalty, or makes the value -inf when it carries a ban. */
+int wm_op_logits_seq_bias(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                          const float* mask, const int32_t* ranges, int timestamp_begin, const uint32_t* seen, const uint32_t* ban, float penalty,
+                          const uint32_t* hit, const int32_t* slot_id, int n_slots, const float* slot_bias, const int32_t* slot_flags, int B,
+                          int N, int K, int dtype);
+/* The hit state's bookkeeping alone, as wm_op_repeat_sets runs the sets': the table is built from the two lists as
+ * wm_set_sequence_bias builds it (same refusals), the init kernel runs on each row's prompt, then `steps` argmax launches append the
+ * rows' ids.  Out: slot_id [n_seq + n_bad] and *n_slots (one slot per distinct last id, ascending); hit [steps + 1][B][ceil(vocab /
+ * 32)]; slot_bias, slot_flags [steps + 1][B][n_seq + n_bad], the first *n_slots of each row written — entry 0 after the init, entry s
+ * after step s.  eot: the id whose length-1 bad word is dropped, -1 = none. */
+int wm_op_seq_bias_hits(uint32_t* hit, float* slot_bias, int32_t* slot_flags, int32_t* slot_id, int32_t* n_slots, const int32_t* tokens,
+                        const int32_t* prompt_len, const int32_t* n_ids, int B, int stride, int vocab, int eot, const int32_t* seq_ids,
+                        const int32_t* seq_off, const float* seq_bias, int n_seq, const int32_t* bad_ids, const int32_t* bad_off, int n_bad,
+                        int steps);
 /* The no-speech probe's launches on the kernel variant wm_op_logits_lp picks for (dtype, K, B): prob[b] = softmax(LN(x[b])·embᵀ)[token]
  * over all N columns, lse[b] the row's logsumexp.  prob, lse: [B]. */
 int wm_op_no_speech(float* prob, float* lse, const float* x, const float* ln_g, const float* ln_b, const float* emb, int B, int N, int K,

@@ -553,6 +553,27 @@ public:
         need_model();
         if (wm_set_repeat_options(model_, repetition_penalty, no_repeat_ngram_size) != WM_OK) throw std::invalid_argument(wm_last_error());
     }
+    // HF generate's sequence_bias / bad_words_ids, as ids, for every transcribe / transcribe_long call from now on: each
+    // bias entry is (ids, bias), each bad word a list of ids; two empty lists switch them off (the default).  Throws
+    // std::invalid_argument for what wm_set_sequence_bias refuses.
+    void set_sequence_bias(const std::vector<std::pair<std::vector<int32_t>, float>>& sequence_bias,
+                           const std::vector<std::vector<int32_t>>& bad_words_ids) {
+        need_model();
+        std::vector<int32_t> ids, off{0}, bids, boff{0};
+        std::vector<float> bias;
+        for (const auto& s : sequence_bias) {
+            ids.insert(ids.end(), s.first.begin(), s.first.end());
+            off.push_back((int32_t)ids.size());
+            bias.push_back(s.second);
+        }
+        for (const auto& s : bad_words_ids) {
+            bids.insert(bids.end(), s.begin(), s.end());
+            boff.push_back((int32_t)bids.size());
+        }
+        if (wm_set_sequence_bias(model_, ids.data(), off.data(), bias.data(), (int)sequence_bias.size(), bids.data(), boff.data(),
+                                 (int)bad_words_ids.size()) != WM_OK)
+            throw std::invalid_argument(wm_last_error());
+    }
     const WhisperConfig& config() const { return cfg_; }
     wm_model* handle() const { return model_; }
 

@@ -38,6 +38,7 @@ SYMBOLS = [
     "wm_op_dec_linear_long",
     "wm_transcribe_long_tt", "wm_transcribe_long_pcm_tt", "wm_long_result_token_times", "wm_op_long_token_times",
     "wm_set_repeat_options", "wm_op_logits_processed", "wm_op_repeat_sets",
+    "wm_set_sequence_bias", "wm_op_logits_seq_bias", "wm_op_seq_bias_hits",
     "wm_chunk_table", "wm_transcribe_chunked", "wm_op_chunk_gather", "wm_op_chunk_merge",
     "wm_transcribe_chunked_ts", "wm_op_chunk_segments",
     "wm_op_gemm_nt_epi",
@@ -312,6 +313,9 @@ def lib():
     L.wm_set_repeat_options.argtypes = [vp, C.c_float, C.c_int]
     L.wm_op_logits_processed.argtypes = [fp, ip, fp, fp, fp, fp, fp, fp, ip, C.c_int, up, up, C.c_float] + [C.c_int] * 4
     L.wm_op_repeat_sets.argtypes = [up, up, ip, ip, ip] + [C.c_int] * 5
+    L.wm_set_sequence_bias.argtypes = [vp, ip, ip, fp, C.c_int, ip, ip, C.c_int]
+    L.wm_op_logits_seq_bias.argtypes = [fp, ip, fp, fp, fp, fp, fp, fp, ip, C.c_int, up, up, C.c_float, up, ip, C.c_int, fp, ip] + [C.c_int] * 4
+    L.wm_op_seq_bias_hits.argtypes = [up, fp, ip, ip, ip, ip, ip, ip] + [C.c_int] * 4 + [ip, ip, fp, C.c_int, ip, ip, C.c_int, C.c_int]
     L.wm_chunk_table.argtypes = [ip] + [C.c_int] * 5 + [ip, C.c_int, ip]
     L.wm_transcribe_chunked.argtypes = [vp, vp, C.c_int, ip] + [C.c_int] * 5 + [C.POINTER(WmDecodeOpts), ip, C.c_int, C.c_int, ip, ip, C.c_int,
                                                                                ip, ip, ip]
@@ -529,6 +533,65 @@ def repeat_args(repetition_penalty, no_repeat_ngram_size):
     if n < 0 or n > REPEAT_NGRAM_MAX:
         raise ValueError(f"no_repeat_ngram_size must lie in [0, {REPEAT_NGRAM_MAX}] (got {n})")
     return p, n
+
+
+SEQ_BIAS_MAX, SEQ_BIAS_LEN_MAX = 1024, 32  # wm_kernels.h
+
+
+def seq_bias_args(sequence_bias, bad_words_ids, vocab):
+    """Checks HF generate's sequence_bias ({(ids...): bias} or [[[ids...], bias], ...]) and bad_words_ids ([[ids...], ...]) on the
+    host (the library refuses the same with WM_E_ARG) -> None when both are empty, else (key, [ids, offsets, bias, n_seq, bad_ids,
+    bad_offsets, n_bad]) as wm_set_sequence_bias takes them; key is hashable and equal for equal lists in equal order."""
+    import numpy as np
+    if sequence_bias is None:
+        seqs = []
+    elif isinstance(sequence_bias, dict):
+        seqs = list(sequence_bias.items())
+    else:
+        seqs = [(s[0], s[1]) for s in sequence_bias]
+    bad = [] if bad_words_ids is None else list(bad_words_ids)
+    out = []
+    for what, items in (("sequence_bias", [s for s, _ in seqs]), ("bad_words_ids", bad)):
+        had = set()
+        for s in items:
+            try:
+                t = tuple(s)
+            except TypeError:
+                raise ValueError(f"{what}: every sequence is a list of ids (got {s!r})")
+            if not 1 <= len(t) <= SEQ_BIAS_LEN_MAX:
+                raise ValueError(f"{what}: a sequence has 1..{SEQ_BIAS_LEN_MAX} ids (got {len(t)})")
+            for i in t:
+                if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= int(i) < vocab:
+                    raise ValueError(f"{what}: id {i!r} is not an integer inside the vocabulary of {vocab}")
+            t = tuple(int(i) for i in t)
+            if t in had:
+                raise ValueError(f"{what}: sequence {list(t)} is given twice")
+            had.add(t)
+            out.append(t)
+    n_seq, n_bad = len(seqs), len(bad)
+    if n_seq + n_bad > SEQ_BIAS_MAX:
+        raise ValueError(f"at most {SEQ_BIAS_MAX} sequences over sequence_bias and bad_words_ids together (got {n_seq + n_bad})")
+    bias = []
+    for _, b in seqs:
+        if isinstance(b, bool) or not isinstance(b, (int, float, np.integer, np.floating)):
+            raise ValueError(f"sequence_bias: a bias is a float (got {b!r})")
+        b = float(np.float32(b))
+        if b != b or b == float("inf"):
+            raise ValueError("sequence_bias: a bias is a finite float or -inf")
+        bias.append(b)
+    if n_seq + n_bad == 0:
+        return None
+
+    def pack(ts):
+        ids = np.asarray([i for t in ts for i in t], np.int32)
+        off = np.concatenate([[0], np.cumsum([len(t) for t in ts])]).astype(np.int32)
+        return ids, off
+
+    ids, off = pack(out[:n_seq])
+    bids, boff = pack(out[n_seq:])
+    key = (tuple(out[:n_seq]), tuple(np.float32(b).tobytes() for b in bias), tuple(out[n_seq:]))
+    return key, [ids if n_seq else None, off if n_seq else None, np.asarray(bias, np.float32) if n_seq else None, n_seq,
+                 bids if n_bad else None, boff if n_bad else None, n_bad]
 
 
 def long_tt_args(return_token_timestamps, logprob_threshold, no_speech_threshold):

@@ -568,24 +568,40 @@ __device__ __forceinline__ void logits_epilogue(const DecLinearParams& p, int CT
 // `seen`, -inf at the ids of `ban` — and the tail above sees the processed values: the logits store, the argmax candidates, the
 // timestamp partials and the log-prob sums.  A lane's four columns start at a multiple of four, so one word of each set covers them.
 // RP = false is the tail above and nothing else.
-template <int NRB, bool LP, bool RP>
+// SB (sequence bias / bad words; needs RP): a third word per column group, the row's `hit` bits.  Where one is set the
+// table's id -> slot map names the row's SeqSlot: its summed bias is added BEFORE the penalty, and a ban makes the value -inf at once
+// — bit for bit what HF's later `+ -inf` leaves, since the penalty (p > 0) and the n-gram ban keep -inf, and it frees the flag's
+// register across the rest (the 128-row fp32 kernel has none to spare).
+template <int NRB, bool LP, bool RP, bool SB = false>
 __device__ __forceinline__ void logits_epilogue_rp(const DecLinearParams& p, int CT, const f32x4 (&acc)[2][NRB], const int (&n0)[2],
                                                    const bool (&have)[2], const float (&mk)[2][4], int row0, int nrows, int lane, int w,
                                                    const LogitsScratch<NRB>& sc) {
+    static_assert(RP || !SB, "the sequence bias rides the repetition processors' instantiation");
     if constexpr (RP) {
         const int r16 = lane & 15, g = lane >> 4;
         const float pen = p.rp_ctl->penalty;
+        const int* slot_of = nullptr;  // SB: the table's id -> slot map, one uniform load for the whole epilogue
+        if constexpr (SB) slot_of = p.sb_ctl->slot_of;
         f32x4 pa[2][NRB];
 #pragma unroll
         for (int rb = 0; rb < NRB; ++rb) {
-            const size_t row = (size_t)(row0 + min(rb * 16 + r16, nrows - 1)) * p.rp_words;
+            const size_t urow = (size_t)(row0 + min(rb * 16 + r16, nrows - 1));
+            const size_t row = urow * p.rp_words;
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
                 const int n = min(n0[nb] + g * 4, p.N - 1);  // (a tile past the vocabulary is not `have`: any word of the row will do)
                 const unsigned sw = p.rp_seen[row + (n >> 5)] >> (n & 31), bw = p.rp_ban[row + (n >> 5)] >> (n & 31);
+                unsigned hw = 0u;
+                if constexpr (SB) hw = (p.sb_hit[row + (n >> 5)] >> (n & 31)) & 15u;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float z = acc[nb][rb][r];
+                    if constexpr (SB) {
+                        if ((hw >> r) & 1u) {  // (a set bit is an id below N that has a slot)
+                            const SeqSlot e = p.sb_val[urow * SEQ_BIAS_MAX + slot_of[n + r]];
+                            z = (e.flags & 2) ? -INFINITY : z + e.bias;
+                        }
+                    }
                     if ((sw >> r) & 1u) z = z < 0.f ? z * pen : z / pen;
                     if ((bw >> r) & 1u) z = -INFINITY;
                     pa[nb][rb][r] = z;
@@ -605,7 +621,7 @@ __device__ __forceinline__ void logits_epilogue_rp(const DecLinearParams& p, int
 // workgroup (LN statistics from a 4-thread-per-row sweep, everything in flight at once) and parked in LDS as MFMA
 // operands, so L2 sees x once per 128 columns; each wave then streams its 32 embedding rows straight from HBM into
 // registers (all k-steps in flight) and needs no cross-wave reduction.
-template <typename TW, int KD /* d_model/128 */, int NRB, bool LP = false, bool RP = false>
+template <typename TW, int KD /* d_model/128 */, int NRB, bool LP = false, bool RP = false, bool SB = false>
 __global__ __launch_bounds__(512) void dec_logits_kernel(DecLinearParams p, int CT) {
     // One workgroup = 8 waves = CT <= 16 column tiles of 16 vocabulary rows (wave w owns tiles w and w+8), all NRB*16
     // utterance rows.  CT is chosen by the launcher so that the whole vocabulary is ONE round of <= 256 workgroups
@@ -788,12 +804,12 @@ __global__ __launch_bounds__(512) void dec_logits_kernel(DecLinearParams p, int 
             __shared__ float s_ls[8][NRB * 16];
             sc.ls = s_ls;
         }
-        logits_epilogue_rp<NRB, LP, RP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, sc);
+        logits_epilogue_rp<NRB, LP, RP, SB>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, sc);
     } else {  // 128 rows: the 48 KB of scratch do not fit beside the activation image — overlay it once every wave is done reading
         __syncthreads();
         static_assert((LP ? LogitsScratch<NRB>::bytes_lp : LogitsScratch<NRB>::bytes) <= (size_t)NRB * 16 * PITCH * sizeof(TW),
                       "epilogue scratch must fit the activation image");
-        logits_epilogue_rp<NRB, LP, RP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
+        logits_epilogue_rp<NRB, LP, RP, SB>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
     }
     WM_LG_STAMP(4);
 }
@@ -841,7 +857,7 @@ __device__ __forceinline__ f32x4 mma_bf16(const bf16x8& a, const bf16x8& b, f32x
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-template <int KD /* d_model/128 */, int NRB, bool LP = false, bool RP = false>
+template <int KD /* d_model/128 */, int NRB, bool LP = false, bool RP = false, bool SB = false>
 __global__ __launch_bounds__(512) void dec_logits_split_kernel(DecLinearParams p, int CT) {
     // Geometry as dec_logits_kernel: 8 waves, wave w owns column tiles w and w + 8 of the workgroup's CT <= 16, all NRB*16 rows.
     constexpr int K = KD * 128;
@@ -1009,7 +1025,7 @@ __global__ __launch_bounds__(512) void dec_logits_split_kernel(DecLinearParams p
     __syncthreads();  // every wave is past its last fragment read: the epilogue's scratch overlays the activation images
     static_assert((LP ? LogitsScratch<NRB>::bytes_lp : LogitsScratch<NRB>::bytes) <= (size_t)3 * IMG * sizeof(bf16),
                   "epilogue scratch must fit the activation images");
-    logits_epilogue_rp<NRB, LP, RP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
+    logits_epilogue_rp<NRB, LP, RP, SB>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
     WM_LG_STAMP(4);
 }
 #undef WM_LG_STAMP
@@ -1021,7 +1037,7 @@ __global__ __launch_bounds__(512) void dec_logits_split_kernel(DecLinearParams p
 // LayerNorm statistics are summed in the same order (a thread carries the two partial sums of the two "virtual" threads the
 // 8-threads-per-row scheme gives its elements to), the k-steps accumulate in the same order — so the ids of a coalesced pass equal
 // the uncoalesced ones bit for bit.
-template <int KD /* d_model/128 */, bool LP = false, bool RP = false>
+template <int KD /* d_model/128 */, bool LP = false, bool RP = false, bool SB = false>
 __global__ __launch_bounds__(512) void dec_logits_split128_kernel(DecLinearParams p, int CT) {
     constexpr int NRB = 8, ROWS = 128;
     constexpr int K = KD * 128, KH = K / 2;  // columns per pass
@@ -1221,28 +1237,28 @@ __global__ __launch_bounds__(512) void dec_logits_split128_kernel(DecLinearParam
     __syncthreads();  // the epilogue's scratch overlays the activation images
     static_assert((LP ? LogitsScratch<NRB>::bytes_lp : LogitsScratch<NRB>::bytes) <= (size_t)3 * IMG * sizeof(bf16),
                   "epilogue scratch must fit the activation images");
-    logits_epilogue_rp<NRB, LP, RP>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
+    logits_epilogue_rp<NRB, LP, RP, SB>(p, CT, acc, n0, have, mk, row0, nrows, lane, w, LogitsScratch<NRB>::carve(smem_raw));
     WM_LG_STAMP(4);
 }
 #undef WM_LG_STAMP
-template <int KD, bool LP = false, bool RP = false> static int launch_dec_logits_split128_t(const DecLinearParams& p, hipStream_t st) {
+template <int KD, bool LP = false, bool RP = false, bool SB = false> static int launch_dec_logits_split128_t(const DecLinearParams& p, hipStream_t st) {
     const size_t lds = (size_t)3 * 128 * (KD * 64 + 16) * sizeof(bf16) + (size_t)2 * KD * 128 * sizeof(float);
     if (lds > 48 * 1024)
-        if (const hipError_t e = ensure_dyn_lds<&dec_logits_split128_kernel<KD, LP, RP>>((int)lds); e != hipSuccess)
+        if (const hipError_t e = ensure_dyn_lds<&dec_logits_split128_kernel<KD, LP, RP, SB>>((int)lds); e != hipSuccess)
             return launch_hip_failed("logits kernel (split fp32, 128 rows): dynamic LDS attribute", e);
     const int ct = dec_logits_tiles_per_wg(p.N);
     dim3 grid(dec_logits_parts(p.N), (p.B + 127) / 128);
-    hipLaunchKernelGGL((dec_logits_split128_kernel<KD, LP, RP>), grid, dim3(512), lds, st, p, ct);
+    hipLaunchKernelGGL((dec_logits_split128_kernel<KD, LP, RP, SB>), grid, dim3(512), lds, st, p, ct);
     return WM_LAUNCH_OK;
 }
-template <int KD, int NRB, bool LP = false, bool RP = false> static int launch_dec_logits_split_t(const DecLinearParams& p, hipStream_t st) {
+template <int KD, int NRB, bool LP = false, bool RP = false, bool SB = false> static int launch_dec_logits_split_t(const DecLinearParams& p, hipStream_t st) {
     const size_t lds = (size_t)3 * NRB * 16 * (KD * 128 + 16) * sizeof(bf16) + (size_t)2 * KD * 128 * sizeof(float);
     if (lds > 48 * 1024)
-        if (const hipError_t e = ensure_dyn_lds<&dec_logits_split_kernel<KD, NRB, LP, RP>>((int)lds); e != hipSuccess)
+        if (const hipError_t e = ensure_dyn_lds<&dec_logits_split_kernel<KD, NRB, LP, RP, SB>>((int)lds); e != hipSuccess)
             return launch_hip_failed("logits kernel (split fp32): dynamic LDS attribute", e);
     const int ct = dec_logits_tiles_per_wg(p.N);
     dim3 grid(dec_logits_parts(p.N), (p.B + NRB * 16 - 1) / (NRB * 16));
-    hipLaunchKernelGGL((dec_logits_split_kernel<KD, NRB, LP, RP>), grid, dim3(512), lds, st, p, ct);
+    hipLaunchKernelGGL((dec_logits_split_kernel<KD, NRB, LP, RP, SB>), grid, dim3(512), lds, st, p, ct);
     return WM_LAUNCH_OK;
 }
 
@@ -1260,22 +1276,22 @@ int dec_logits_parts(int N) {
     const int tiles = (N + 15) / 16, ct = dec_logits_tiles_per_wg(N);
     return (tiles + ct - 1) / ct;
 }
-template <typename TW, int KD, int NRB, bool LP = false, bool RP = false> static int launch_dec_logits_t(const DecLinearParams& p, hipStream_t st) {
+template <typename TW, int KD, int NRB, bool LP = false, bool RP = false, bool SB = false> static int launch_dec_logits_t(const DecLinearParams& p, hipStream_t st) {
     constexpr size_t lds = (size_t)NRB * 16 * (KD * 128 + (sizeof(TW) == 2 ? 80 : 16 / sizeof(TW))) * sizeof(TW);
     // beside the image: gamma | beta (8·K bytes) and, up to 64 rows, the epilogue's scratch: 2 x 32 + 4 x 8 (+ 8 with log-probs)
     // floats / ints per row.  At 128 rows the scratch overlays the image.
     static_assert(lds + (size_t)8 * KD * 128 + (NRB <= 4 ? (size_t)NRB * 16 * 4 * (LP ? 104 : 96) : 0) <= 160 * 1024,
                   "activation image + static LDS must fit the 160 KB of a CU");
     if (lds > 48 * 1024)
-        if (const hipError_t e = ensure_dyn_lds<&dec_logits_kernel<TW, KD, NRB, LP, RP>>((int)lds); e != hipSuccess)
+        if (const hipError_t e = ensure_dyn_lds<&dec_logits_kernel<TW, KD, NRB, LP, RP, SB>>((int)lds); e != hipSuccess)
             return launch_hip_failed("logits kernel: dynamic LDS attribute", e);
     const int ct = dec_logits_tiles_per_wg(p.N);
     dim3 grid(dec_logits_parts(p.N), (p.B + NRB * 16 - 1) / (NRB * 16));
-    hipLaunchKernelGGL((dec_logits_kernel<TW, KD, NRB, LP, RP>), grid, dim3(512), lds, st, p, ct);
+    hipLaunchKernelGGL((dec_logits_kernel<TW, KD, NRB, LP, RP, SB>), grid, dim3(512), lds, st, p, ct);
     return WM_LAUNCH_OK;
 }
 // requires ln_g/ln_b, no bias/act/residual, K in {128, 384, 512, 768, 1024}, ldo % 4 == 0; amax_stride >= dec_logits_parts(N)
-template <typename TW, bool LP, bool RP> static int launch_dec_logits_lp(const DecLinearParams& p, hipStream_t st) {
+template <typename TW, bool LP, bool RP, bool SB> static int launch_dec_logits_lp(const DecLinearParams& p, hipStream_t st) {
     const int kd = p.K >> 7;
     if (p.B <= 0 || p.N <= 0) return launch_refuse("dec_logits: empty problem");
     if ((p.K & 127) != 0 || (kd != 1 && kd != 3 && kd != 4 && kd != 6 && kd != 8)) return launch_refuse("dec_logits: d_model must be 128, 384, 512, 768 or 1024");
@@ -1292,24 +1308,24 @@ template <typename TW, bool LP, bool RP> static int launch_dec_logits_lp(const D
         // WM_LOGITS_EXACT (developer build) forces the exact kernel for A/B runs.
         static const bool exact = wm_env("WM_LOGITS_EXACT") != nullptr;
         if (!exact && (kd == 1 || kd == 3)) {
-            if (p.B <= 16) return kd == 1 ? launch_dec_logits_split_t<1, 1, LP, RP>(p, st) : launch_dec_logits_split_t<3, 1, LP, RP>(p, st);
+            if (p.B <= 16) return kd == 1 ? launch_dec_logits_split_t<1, 1, LP, RP, SB>(p, st) : launch_dec_logits_split_t<3, 1, LP, RP, SB>(p, st);
             // more than 64 rows (coalesced batches): 128 rows per workgroup, the embedding streamed once per 128 (WM_LOGITS_NO128: A/B)
             static const bool no128 = wm_env("WM_LOGITS_NO128") != nullptr;
-            if (p.B > 64 && !no128) return kd == 1 ? launch_dec_logits_split128_t<1, LP, RP>(p, st) : launch_dec_logits_split128_t<3, LP, RP>(p, st);
-            return kd == 1 ? launch_dec_logits_split_t<1, 4, LP, RP>(p, st) : launch_dec_logits_split_t<3, 4, LP, RP>(p, st);
+            if (p.B > 64 && !no128) return kd == 1 ? launch_dec_logits_split128_t<1, LP, RP, SB>(p, st) : launch_dec_logits_split128_t<3, LP, RP, SB>(p, st);
+            return kd == 1 ? launch_dec_logits_split_t<1, 4, LP, RP, SB>(p, st) : launch_dec_logits_split_t<3, 4, LP, RP, SB>(p, st);
         }
     }
     if (p.B <= 16) {
-        if (kd == 1) return launch_dec_logits_t<TW, 1, 1, LP, RP>(p, st);
-        if (kd == 3) return launch_dec_logits_t<TW, 3, 1, LP, RP>(p, st);
-        if (kd == 6) return launch_dec_logits_t<TW, 6, 1, LP, RP>(p, st);
-        if (kd == 8) return launch_dec_logits_t<TW, 8, 1, LP, RP>(p, st);
-        return launch_dec_logits_t<TW, 4, 1, LP, RP>(p, st);
+        if (kd == 1) return launch_dec_logits_t<TW, 1, 1, LP, RP, SB>(p, st);
+        if (kd == 3) return launch_dec_logits_t<TW, 3, 1, LP, RP, SB>(p, st);
+        if (kd == 6) return launch_dec_logits_t<TW, 6, 1, LP, RP, SB>(p, st);
+        if (kd == 8) return launch_dec_logits_t<TW, 8, 1, LP, RP, SB>(p, st);
+        return launch_dec_logits_t<TW, 4, 1, LP, RP, SB>(p, st);
     }
     // d_model 1024: 32 rows per workgroup for every operand type (16-bit: 32 x 1104 x 2 = 69 KB image + 21 KB static; fp32:
     // 32 x 1028 x 4 = 129 KB + 21 KB; 64 rows of 16-bit would be 138 + 34 KB, past the 160).  More rows are more row blocks in grid.y.
-    if (kd == 8) return launch_dec_logits_t<TW, 8, 2, LP, RP>(p, st);
-    if (kd == 6) return launch_dec_logits_t<TW, 6, sizeof(TW) == 4 ? 2 : 4, LP, RP>(p, st);  // (16-bit, 64 rows: 106 KB image + 30 KB static)
+    if (kd == 8) return launch_dec_logits_t<TW, 8, 2, LP, RP, SB>(p, st);
+    if (kd == 6) return launch_dec_logits_t<TW, 6, sizeof(TW) == 4 ? 2 : 4, LP, RP, SB>(p, st);  // (16-bit, 64 rows: 106 KB image + 30 KB static)
 #ifdef WM_DEV
     if constexpr (sizeof(TW) == 2) {
         // Developer A/B (WM_LOGITS_128_16BIT): 128 rows per workgroup for 16-bit weights too.  Measured SLOWER than two 64-row
@@ -1318,24 +1334,29 @@ template <typename TW, bool LP, bool RP> static int launch_dec_logits_lp(const D
         // the rows behind one stream.  The fp32 form (80 MB per stream, MFMA-heavy) does gain: dec_logits_split128_kernel.
         static const bool on128 = wm_env("WM_LOGITS_128_16BIT") != nullptr;
         if (p.B > 64 && on128) {
-            if (kd == 1) return launch_dec_logits_t<TW, 1, 8, LP, RP>(p, st);
-            if (kd == 3) return launch_dec_logits_t<TW, 3, 8, LP, RP>(p, st);
-            return launch_dec_logits_t<TW, 4, 8, LP, RP>(p, st);
+            if (kd == 1) return launch_dec_logits_t<TW, 1, 8, LP, RP, SB>(p, st);
+            if (kd == 3) return launch_dec_logits_t<TW, 3, 8, LP, RP, SB>(p, st);
+            return launch_dec_logits_t<TW, 4, 8, LP, RP, SB>(p, st);
         }
     }
 #endif
-    if (kd == 1) return launch_dec_logits_t<TW, 1, 4, LP, RP>(p, st);
-    if (kd == 3) return launch_dec_logits_t<TW, 3, 4, LP, RP>(p, st);
-    return launch_dec_logits_t<TW, 4, 4, LP, RP>(p, st);
+    if (kd == 1) return launch_dec_logits_t<TW, 1, 4, LP, RP, SB>(p, st);
+    if (kd == 3) return launch_dec_logits_t<TW, 3, 4, LP, RP, SB>(p, st);
+    return launch_dec_logits_t<TW, 4, 4, LP, RP, SB>(p, st);
 }
 // p.lp_s null: exactly the kernels, grids and LDS of a pass without log-probabilities; non-null: the LP instantiation of the same variant
 // p.rp_seen likewise: null is the pass without the repetition processors, non-null the RP instantiation of the same variant
 template <typename TW> int launch_dec_logits(const DecLinearParams& p, hipStream_t st) {
     if (p.rp_seen) {
         if (!p.rp_ban || !p.rp_ctl || p.rp_words < repeat_words(p.N)) return launch_refuse("dec_logits: the repetition processors need both sets of ceil(N / 32) words per row and their control block");
-        return p.lp_s ? launch_dec_logits_lp<TW, true, true>(p, st) : launch_dec_logits_lp<TW, false, true>(p, st);
+        if (p.sb_hit) {  // sequence bias / bad words: the SB instantiation of the same variant
+            if (!p.sb_val || !p.sb_ctl) return launch_refuse("dec_logits: the sequence bias needs the rows' slots and the control block");
+            return p.lp_s ? launch_dec_logits_lp<TW, true, true, true>(p, st) : launch_dec_logits_lp<TW, false, true, true>(p, st);
+        }
+        return p.lp_s ? launch_dec_logits_lp<TW, true, true, false>(p, st) : launch_dec_logits_lp<TW, false, true, false>(p, st);
     }
-    return p.lp_s ? launch_dec_logits_lp<TW, true, false>(p, st) : launch_dec_logits_lp<TW, false, false>(p, st);
+    if (p.sb_hit) return launch_refuse("dec_logits: the sequence bias needs the repetition processors' sets (penalty 1, n-gram 0 = no-ops)");
+    return p.lp_s ? launch_dec_logits_lp<TW, true, false, false>(p, st) : launch_dec_logits_lp<TW, false, false, false>(p, st);
 }
 template int launch_dec_logits<float>(const DecLinearParams&, hipStream_t);
 template int launch_dec_logits<bf16>(const DecLinearParams&, hipStream_t);
@@ -2129,9 +2150,53 @@ __device__ __forceinline__ void repeat_ban_walk(unsigned* ban, int n, int L, H h
         }
     }
 }
+// Sequence bias / bad words: a row's slots and bits for its NEXT step.  hist(i), i < L, is the row's history.  Pass 1, the
+// sequences spread over the workgroup: sequence q of m ids matches when m = 1 (a length-1 ban of the eot is dropped), or when
+// 2 <= m <= L and its first m - 1 ids are the history's last m - 1 (m <= L, not m - 1 <= L: HF's own `continue`) — a compare chain of at
+// most 31 ids.  Pass 2, the slots spread over the workgroup: ONE thread walks its slot's sequences in table order and adds the matching
+// biases, so the fp32 sum is HF's whichever thread matched what; it rewrites the SeqSlot and touches the id's bit only where the slot
+// goes on or off, so nothing is swept.  FRESH: the bits were just cleared and no slot is on yet (the init kernel).
+template <bool FRESH, typename H>
+__device__ __forceinline__ void seq_bias_update(const SeqBiasCtl& c, unsigned* hit, SeqSlot* val, int L, H hist) {
+    __shared__ unsigned char s_match[SEQ_BIAS_MAX];
+    const int n_seq = min(c.n_seq, SEQ_BIAS_MAX), n_slots = min(c.n_slots, SEQ_BIAS_MAX);
+    for (int q = threadIdx.x; q < n_seq; q += blockDim.x) {
+        const int o = c.off[q], m = c.off[q + 1] - o;
+        bool same;
+        if (m == 1) {
+            same = !(c.ban[q] && c.ids[o] == c.eot);
+        } else {
+            same = m <= L;
+            for (int k = 0; k < m - 1 && same; ++k) same = hist(L - (m - 1) + k) == c.ids[o + k];
+        }
+        s_match[q] = same;
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < n_slots; s += blockDim.x) {
+        float sum = 0.f;
+        int flags = 0;
+        for (int q = c.slot_off[s]; q < c.slot_off[s + 1]; ++q) {
+            if (!s_match[q]) continue;
+            flags |= 1;
+            if (c.ban[q])
+                flags |= 2;
+            else
+                sum += c.bias[q];
+        }
+        const int was = FRESH ? 0 : val[s].flags;
+        val[s] = SeqSlot{sum, flags};
+        if ((flags ^ was) & 1) {
+            const int t = c.slot_id[s];
+            if (flags & 1)
+                atomicOr(hit + (t >> 5), 1u << (t & 31));
+            else
+                atomicAnd(hit + (t >> 5), ~(1u << (t & 31)));
+        }
+    }
+}
 // LP: the log-probability instantiation (p.lp_s non-null); LP = false is the kernel without it, static LDS included.  RP: the
-// repetition processors' bookkeeping (p.rp_seen non-null), likewise.
-template <bool LP, bool RP = false>
+// repetition processors' bookkeeping (p.rp_seen non-null), likewise.  SB: the sequence-bias bookkeeping (p.sb_hit non-null, needs RP).
+template <bool LP, bool RP = false, bool SB = false>
 __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
     const int b = blockIdx.x;
     if (p.ts && b == 0 && threadIdx.x == 0) ts_put(p.ts, p.ts_id, 3);
@@ -2262,6 +2327,8 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
             __threadfence();
             __syncthreads();  // every clear is done before the first set: an id banned at both steps stays banned
             repeat_ban_walk<true>(ban, n, L + 1, hist);
+            if constexpr (SB)
+                seq_bias_update<false>(*p.sb_ctl, p.sb_hit + (size_t)b * p.rp_words, p.sb_val + (size_t)b * SEQ_BIAS_MAX, L + 1, hist);
         }
     }
     if (p.emb_out) {  // every thread holds idx: next step's embedding row (whisper.mojo:141-149)
@@ -2274,12 +2341,21 @@ int launch_argmax_step(const ArgmaxParams& p, hipStream_t st) {
     if (p.rp_seen) {  // the sets' bookkeeping reads the row's history and rides the partials form: anything else is refused, not dropped
         if (!p.out_tokens || !p.pval || !p.rp_ban || !p.rp_ctl || p.rp_words < repeat_words(p.V))
             return launch_refuse("argmax_step: the repetition processors need the partials form, the id table, both sets and their control block");
+        if (p.sb_hit) {
+            if (!p.sb_val || !p.sb_ctl) return launch_refuse("argmax_step: the sequence bias needs the rows' slots and the control block");
+            if (p.lp_s)
+                hipLaunchKernelGGL((argmax_step_kernel<true, true, true>), dim3(p.B), dim3(256), 0, st, p);
+            else
+                hipLaunchKernelGGL((argmax_step_kernel<false, true, true>), dim3(p.B), dim3(256), 0, st, p);
+            return WM_LAUNCH_OK;
+        }
         if (p.lp_s)
             hipLaunchKernelGGL((argmax_step_kernel<true, true>), dim3(p.B), dim3(256), 0, st, p);
         else
             hipLaunchKernelGGL((argmax_step_kernel<false, true>), dim3(p.B), dim3(256), 0, st, p);
         return WM_LAUNCH_OK;
     }
+    if (p.sb_hit) return launch_refuse("argmax_step: the sequence bias needs the repetition processors' sets");
     if (p.lp_s && p.pval)
         hipLaunchKernelGGL(argmax_step_kernel<true>, dim3(p.B), dim3(256), 0, st, p);
     else
@@ -2391,6 +2467,28 @@ __global__ __launch_bounds__(256) void repeat_init_kernel(RepeatInitParams p) {
 }
 void launch_repeat_init(const RepeatInitParams& p, hipStream_t st) {
     hipLaunchKernelGGL(repeat_init_kernel, dim3(p.B), dim3(256), 0, st, p);
+}
+// start of a pass with sequence bias / bad words, one workgroup per row, behind the init-tokens launch: the control
+// block, the row's bits cleared, its slots and bits for the first generated id from its prompt
+__global__ __launch_bounds__(256) void seq_bias_init_kernel(SeqBiasInitParams p) {
+    const int b = blockIdx.x;
+    // A state with several decode lanes launches this once per lane, each on its own stream, and every launch writes the state's one
+    // control block: the same table and eot, so the same bytes, and no kernel of the pass reads it before its own lane's init.
+    if (b == 0 && threadIdx.x == 0) *p.ctl = p.table;
+    unsigned* hit = p.hit + (size_t)b * p.words;
+    for (int i = threadIdx.x; i < p.words; i += blockDim.x) hit[i] = 0u;
+    __threadfence();
+    __syncthreads();
+    const int* row = p.out_tokens + (size_t)b * p.out_stride;
+    seq_bias_update<true>(p.table, hit, p.val + (size_t)b * SEQ_BIAS_MAX, p.n_tokens[b], [&](int i) { return row[i]; });
+}
+int launch_seq_bias_init(const SeqBiasInitParams& p, hipStream_t st) {
+    const SeqBiasCtl& t = p.table;
+    if (!p.hit || !p.val || !p.ctl || !p.out_tokens || !p.n_tokens || p.B <= 0 || p.words <= 0 || t.n_seq < 1 || t.n_seq > SEQ_BIAS_MAX ||
+        t.n_slots < 1 || t.n_slots > t.n_seq || !t.ids || !t.off || !t.bias || !t.ban || !t.slot_id || !t.slot_off || !t.slot_of)
+        return launch_refuse("seq_bias_init: 1 .. SEQ_BIAS_MAX sequences in at most as many slots, and every table");
+    hipLaunchKernelGGL(seq_bias_init_kernel, dim3(p.B), dim3(256), 0, st, p);
+    return WM_LAUNCH_OK;
 }
 // end of a per-row prefill: cache length Lmax for all, position len[b] + pos_delta per row
 __global__ void set_rows_step_kernel(StepCtl* ctl, int Lmax, int* pos, const int* len, int pos_delta, int B) {

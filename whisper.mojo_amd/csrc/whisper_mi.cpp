@@ -17,7 +17,9 @@
 #include <cstring>
 #include <atomic>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
+#include <set>
 #include <thread>
 #include <string>
 #include <unordered_set>
@@ -215,11 +217,33 @@ struct WinAsk {  // the windows a long-form timestamp pass decodes
     const int32_t* items;  // device [B][3]: (utterance, seek, frames) per row
     int n_real;            // rows [n_real, B) repeat row 0: no align rows, zero times
 };
-struct RepeatAsk {  // the repetition processors of a greedy pass, as wm_set_repeat_options left them when the pass was asked for
+// One table of wm_set_sequence_bias: both lists validated, grouped by last id and copied to the device.  Immutable once
+// built; the model, a held submit and a state's pending pass each hold a reference, so replacing the model's table changes none of them.
+struct SeqTable {
+    int gen = 0;  // the model's count of tables built: what a PassAsk carries and what pairs two submits
+    int device = 0;  // where the buffers live: the last reference may drop while another device is current
+    int n_seq = 0, n_slots = 0;
+    DevBuf ids, off, bias, ban, slot_id, slot_off, slot_of;
+    SeqTable() = default;
+    SeqTable(const SeqTable&) = delete;
+    SeqTable& operator=(const SeqTable&) = delete;
+    ~SeqTable() {
+        int cur = -1;
+        const bool moved = hipGetDevice(&cur) == hipSuccess && cur != device && hipSetDevice(device) == hipSuccess;
+        for (DevBuf* b : {&ids, &off, &bias, &ban, &slot_id, &slot_off, &slot_of}) b->release();
+        if (moved) (void)hipSetDevice(cur);
+    }
+    SeqBiasCtl ctl(int eot) const {
+        return SeqBiasCtl{n_seq, n_slots, eot, ids.as<int>(), off.as<int>(), bias.as<float>(), ban.as<int>(), slot_id.as<int>(), slot_off.as<int>(), slot_of.as<int>()};
+    }
+};
+struct RepeatAsk {  // the logits processors of a greedy pass, as wm_set_repeat_options / wm_set_sequence_bias left them when the pass was asked for
     float penalty = 1.f;
     int ngram = 0;
-    bool on() const { return penalty != 1.f || ngram > 0; }
-    bool operator==(const RepeatAsk& o) const { return penalty == o.penalty && ngram == o.ngram; }
+    std::shared_ptr<const SeqTable> sb;  // sequence bias / bad words: null = off
+    int sb_gen() const { return sb ? sb->gen : 0; }
+    bool on() const { return penalty != 1.f || ngram > 0 || sb; }
+    bool operator==(const RepeatAsk& o) const { return penalty == o.penalty && ngram == o.ngram && sb_gen() == o.sb_gen(); }
 };
 // One pass: encoder, prefill, greedy loop (or the teacher-forced pass of `score`) for B utterances.  The entry points validate, fill
 // one of these and hand it to a driver (run_now / submit_slot); nothing in it is owned, it lives on the caller's stack.
@@ -331,7 +355,8 @@ struct wm_model {
     bool pump_quit = false;
     // token-level timestamps: HF generation_config.alignment_heads, (layer, head) pairs in the caller's order; empty = off
     std::vector<int32_t> align_pairs;
-    RepeatAsk repeat;  // wm_set_repeat_options: what every greedy pass asked for from now on carries (a held submit keeps its own)
+    RepeatAsk repeat;  // wm_set_repeat_options / wm_set_sequence_bias: what every greedy pass asked for from now on carries (a held submit keeps its own)
+    int seq_gen = 0;   // tables built so far by wm_set_sequence_bias
     struct AlignRef {  // where a slot's last timestamp pass left its alignment weights (wm_alignment_weights)
         wm_state* st = nullptr;
         int row0 = 0, rows = 0, gen = 0;
@@ -401,10 +426,11 @@ struct wm_state {
         } cap;
         bool rows = false, lp = false;  // self-attention in the key-window form (rw.on); log-probabilities (lp.on)
         bool rp = false;                // repetition processors (rp.on): the flag only — penalty and n-gram size are read on the device
+        bool sb = false;                // sequence bias / bad words (rp.sb): the flag only — the table is reached through the control block
         bool operator==(const StepKey& o) const {
             return eot == o.eot && ignore_eot == o.ignore_eot && rules.tb == o.rules.tb && rules.eos == o.rules.eos &&
                    rules.max_init == o.rules.max_init && rules.vocab == o.rules.vocab && shares_chip == o.shares_chip && cap == o.cap &&
-                   rows == o.rows && lp == o.lp && rp == o.rp;
+                   rows == o.rows && lp == o.lp && rp == o.rp && sb == o.sb;
         }
     };
     StepKey step, graph_step;
@@ -469,6 +495,10 @@ struct wm_state {
         RepeatAsk ask;
         int words = 0;
         DevBuf seen, ban, ctl;
+        // sequence bias / bad words (sb = ask.sb non-null, always with on): the rows' hit bits [B][words], their slots
+        // [B][SEQ_BIAS_MAX] and the control block that names the table.  Allocated by the first such pass.
+        bool sb = false;
+        DevBuf hit, val, sbctl;
     } rp;
     // no-speech probe of the pending pass (on = wm_transcribe_lp_ns and its kin, always with lp.on): the residual rows
     // of the <|startoftranscript|> position [B][d], the probe's OWN sweep partials [B][npart] (the step's amax / lp_s partials and
@@ -1004,7 +1034,7 @@ extern "C" void wm_state_free(wm_state* s) {
                     &s->sc.slot, &s->sc.dst, &s->sc.len, &s->sc.ctx, &s->sc.lp, &s->sc.top, &s->sc.sum, &s->sc.avg,
                     &s->rw.table, &s->rw.len, &s->rw.key_lo, &s->lp.part_s, &s->lp.table, &s->lp.sum,
                     &s->ns.x, &s->ns.pmax, &s->ns.pidx, &s->ns.psum, &s->ns.prob, &s->ns.lse,
-                    &s->lg.x, &s->lg.ids, &s->lg.col, &s->lg.out, &s->lg.probs, &s->rp.seen, &s->rp.ban, &s->rp.ctl};
+                    &s->lg.x, &s->lg.ids, &s->lg.col, &s->lg.out, &s->lg.probs, &s->rp.seen, &s->rp.ban, &s->rp.ctl, &s->rp.hit, &s->rp.val, &s->rp.sbctl};
     for (DevBuf* b : bs) b->release();
     delete s;
 }
@@ -1617,6 +1647,11 @@ static void add_argmax_partials(DecLinearParams& p, wm_state* s, const DecView& 
         p.rp_ban = lane_ptr<unsigned>(s->rp.ban, v, s->rp.words);
         p.rp_ctl = s->rp.ctl.as<RepeatCtl>();
         p.rp_words = s->rp.words;
+        if (s->rp.sb) {
+            p.sb_hit = lane_ptr<unsigned>(s->rp.hit, v, s->rp.words);
+            p.sb_val = lane_ptr<SeqSlot>(s->rp.val, v, SEQ_BIAS_MAX);
+            p.sb_ctl = s->rp.sbctl.as<SeqBiasCtl>();
+        }
     }
 }
 // start of a pass with the repetition processors, behind the lane's init-tokens launch
@@ -1633,6 +1668,21 @@ static void repeat_init(wm_state* s, const DecView& v) {
     r.out_stride = s->out_stride;
     r.n_tokens = lane_ptr<int>(s->n_tokens, v, 1);
     launch_repeat_init(r, v.st);
+}
+// start of a pass with sequence bias / bad words, behind the lane's init-tokens launch; eot: the pass's, whose length-1 ban is dropped
+static int seq_bias_init(wm_state* s, const DecView& v, int eot) {
+    SeqBiasInitParams r{};
+    r.hit = lane_ptr<unsigned>(s->rp.hit, v, s->rp.words);
+    r.val = lane_ptr<SeqSlot>(s->rp.val, v, SEQ_BIAS_MAX);
+    r.words = s->rp.words;
+    r.B = v.nb;
+    r.ctl = s->rp.sbctl.as<SeqBiasCtl>();
+    r.table = s->rp.ask.sb->ctl(eot);
+    r.out_tokens = lane_ptr<int>(s->out_tokens, v, s->out_stride);
+    r.out_stride = s->out_stride;
+    r.n_tokens = lane_ptr<int>(s->n_tokens, v, 1);
+    LCHK(launch_seq_bias_init(r, v.st));
+    return 0;
 }
 // LN1 -> q | k,v appended to the cache   (layers.mojo:118-147)
 static DecLinearParams qkv_block(wm_model* m, wm_state* s, const DecView& v, int l, int P) {
@@ -1775,6 +1825,11 @@ static ArgmaxParams argmax_first_id(wm_model* m, wm_state* s, const DecView& v, 
         a.rp_ban = lane_ptr<unsigned>(s->rp.ban, v, s->rp.words);
         a.rp_ctl = s->rp.ctl.as<RepeatCtl>();
         a.rp_words = s->rp.words;
+        if (s->rp.sb) {
+            a.sb_hit = lane_ptr<unsigned>(s->rp.hit, v, s->rp.words);
+            a.sb_val = lane_ptr<SeqSlot>(s->rp.val, v, SEQ_BIAS_MAX);
+            a.sb_ctl = s->rp.sbctl.as<SeqBiasCtl>();
+        }
     }
     a.eot = eot;
     a.ignore_eot = ignore_eot;
@@ -2062,6 +2117,7 @@ static int prefill_rows(wm_model* m, wm_state* s, const DecView& v, InitTokensPa
     ip.pos_rows = s->pos_rows.as<int>();
     launch_init_tokens_rows(ip, RowPromptParams{rw.table.as<int>(), rw.len.as<int>(), rw.stride, Lmax, rw.key_lo.as<int>()}, v.st);
     if (s->rp.on) repeat_init(s, v);  // each row's own prompt, a detected language included
+    if (s->rp.sb) WMCHK(seq_bias_init(s, v, o->eot));
     for (int t0 = 0; t0 < Lmax; t0 += wm_state::PREFILL_MAX) {
         const int P = std::min<int>(wm_state::PREFILL_MAX, Lmax - t0);
         if (t0) launch_set_step(v.ctl, t0, 1, nullptr, 0, nullptr, 0, v.nb, v.st);
@@ -2108,6 +2164,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
     s->step.rows = s->rw.on;
     s->step.lp = s->lp.on;
     s->step.rp = s->rp.on;
+    s->step.sb = s->rp.sb;
     const bool recapture = !s->graphs_valid || !(s->graph_step == s->step);
     const int first_pos = o->pos_mode == WM_POS_REF ? o->n_prompt - 1 : o->n_prompt;
     // logit masks (§8f rank 4): rebuilt only when the id lists change; always passed (all-zero = the reference's raw argmax)
@@ -2155,6 +2212,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
         } else {
             launch_init_tokens(ip, v.st);
             if (s->rp.on) repeat_init(s, v);
+            if (s->rp.sb) WMCHK(seq_bias_init(s, v, o->eot));
             // prefill (whisper.mojo:195, start_pos=0): the q_len = n_prompt causal block equals n_prompt single-token steps
             static const bool seq_prefill = wm_env("WM_SEQ_PREFILL") != nullptr;  // A/B: one pass per prompt position
             DecPass prompt;  // the last prompt position's logits, under the begin mask
@@ -2341,6 +2399,14 @@ static int submit_on(wm_model* m, wm_state** slot, const PassAsk& ask) {
         WMCHK(grow(s->rp.ban, (size_t)B * s->rp.words * 4));
         WMCHK(grow(s->rp.ctl, sizeof(RepeatCtl)));
     }
+    s->rp.sb = s->rp.on && ask.rp.sb;
+    if (s->rp.sb) {
+        WMCHK(grow(s->rp.hit, (size_t)B * s->rp.words * 4));
+        WMCHK(grow(s->rp.val, (size_t)B * SEQ_BIAS_MAX * sizeof(SeqSlot)));
+        WMCHK(grow(s->rp.sbctl, sizeof(SeqBiasCtl)));
+    } else {
+        s->rp.ask.sb.reset();  // (a pass without the table holds no reference to one)
+    }
     s->lp.on = lp;
     if (lp) {
         if (rows)
@@ -2523,7 +2589,7 @@ static bool pairs_with(const wm_model::Held& h, const PassAsk& b) {
     const wm_decode_opts &x = h.o, *o = b.opts;
     if (a.B != b.B || (a.cols != nullptr) != (b.cols != nullptr) || a.lp != b.lp || a.ns.token != b.ns.token || a.ns.n_init != b.ns.n_init)
         return false;
-    if (!(a.rp == b.rp)) return false;  // one control block per state: a pair shares (penalty, n-gram size)
+    if (!(a.rp == b.rp)) return false;  // one control block per state: a pair shares (penalty, n-gram size) and the sequence-bias table
     if (x.n_prompt != o->n_prompt || x.eot != o->eot || x.max_loop != o->max_loop || x.pos_mode != o->pos_mode || x.ignore_eot != o->ignore_eot ||
         x.n_suppress != (o->suppress_tokens ? o->n_suppress : 0) || x.n_begin_suppress != (o->begin_suppress_tokens ? o->n_begin_suppress : 0) ||
         x.timestamp_begin != o->timestamp_begin || x.no_timestamps_token != o->no_timestamps_token ||
@@ -2951,6 +3017,93 @@ extern "C" int wm_set_repeat_options(wm_model* m, float repetition_penalty, int 
         return fail(WM_E_ARG, "no_repeat_ngram_size %d outside [0, %d] (0 = off)", no_repeat_ngram_size, REPEAT_NGRAM_MAX);
     m->repeat.penalty = repetition_penalty;
     m->repeat.ngram = no_repeat_ngram_size;
+    return 0;
+}
+// ---- sequence bias and bad words ---------------------------------------------------------------------------------
+// Validates both lists and builds the device table: the sequences grouped by last id (ascending), inside a group the length-1 bias
+// first, then the bias sequences in the caller's order, then the bans — the order one thread sums a group in.  Nothing is allocated
+// before every argument has passed.  slot_ids (optional): the groups' ids for the op hook.
+static int build_seq_table(std::shared_ptr<SeqTable>& out, int vocab, const int32_t* ids, const int32_t* off, const float* bias, int n_seq,
+                           const int32_t* bad_ids, const int32_t* bad_off, int n_bad, std::vector<int32_t>* slot_ids = nullptr) {
+    if (n_seq < 0 || n_bad < 0 || (n_seq > 0 && (!ids || !off || !bias)) || (n_bad > 0 && (!bad_ids || !bad_off))) return fail(WM_E_ARG, "bad argument");
+    if ((long long)n_seq + n_bad > SEQ_BIAS_MAX) return fail(WM_E_ARG, "%d + %d sequences: at most %d over the two lists", n_seq, n_bad, SEQ_BIAS_MAX);
+    struct Ent {
+        const int32_t* p;
+        int len, ban, order;
+        float bias;
+    };
+    std::vector<Ent> es;
+    for (int list = 0; list < 2; ++list) {
+        const int n = list ? n_bad : n_seq;
+        const int32_t *id = list ? bad_ids : ids, *o = list ? bad_off : off;
+        const char* what = list ? "bad_words_ids" : "sequence_bias";
+        std::set<std::vector<int32_t>> had;
+        if (n > 0 && o[0] != 0) return fail(WM_E_ARG, "%s: offsets start at 0", what);
+        for (int q = 0; q < n; ++q) {
+            const long long len = (long long)o[q + 1] - o[q];
+            if (len < 1 || len > SEQ_BIAS_LEN_MAX) return fail(WM_E_ARG, "%s: sequence %d has %lld ids, need 1..%d", what, q, len, SEQ_BIAS_LEN_MAX);
+            for (int k = 0; k < (int)len; ++k)
+                if (id[o[q] + k] < 0 || id[o[q] + k] >= vocab) return fail(WM_E_ARG, "%s: sequence %d holds id %d outside the vocabulary of %d", what, q, id[o[q] + k], vocab);
+            if (!had.insert(std::vector<int32_t>(id + o[q], id + o[q + 1])).second) return fail(WM_E_ARG, "%s: sequence %d is a duplicate", what, q);
+            if (!list && !(std::isfinite(bias[q]) || (std::isinf(bias[q]) && bias[q] < 0.f)))
+                return fail(WM_E_ARG, "sequence_bias: the bias of sequence %d must be a finite float or -inf", q);
+            es.push_back(Ent{id + o[q], (int)len, list, (int)es.size(), list ? -INFINITY : bias[q]});
+        }
+    }
+    out.reset();
+    if (es.empty()) return 0;
+    std::sort(es.begin(), es.end(), [](const Ent& a, const Ent& b) {
+        const int la = a.p[a.len - 1], lb = b.p[b.len - 1];
+        if (la != lb) return la < lb;
+        if (a.ban != b.ban) return a.ban < b.ban;
+        const int ra = !a.ban && a.len == 1 ? 0 : 1, rb = !b.ban && b.len == 1 ? 0 : 1;  // HF sets the length-1 biases before it adds the others
+        if (ra != rb) return ra < rb;
+        return a.order < b.order;
+    });
+    std::vector<int32_t> h_ids, h_off{0}, h_ban, h_sid, h_soff;
+    std::vector<float> h_bias;
+    for (size_t q = 0; q < es.size(); ++q) {
+        const Ent& e = es[q];
+        if (q == 0 || es[q - 1].p[es[q - 1].len - 1] != e.p[e.len - 1]) {
+            h_sid.push_back(e.p[e.len - 1]);
+            h_soff.push_back((int32_t)q);
+        }
+        h_ids.insert(h_ids.end(), e.p, e.p + e.len);
+        h_off.push_back((int32_t)h_ids.size());
+        h_ban.push_back(e.ban);
+        h_bias.push_back(e.bias);
+    }
+    h_soff.push_back((int32_t)es.size());
+    auto t = std::make_shared<SeqTable>();
+    (void)hipGetDevice(&t->device);  // (the callers have made the model's device current)
+    t->n_seq = (int)es.size();
+    t->n_slots = (int)h_sid.size();
+    auto up = [](DevBuf& d, const void* src, size_t bytes) -> int {
+        WMCHK(d.alloc(bytes));
+        HIPCHK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+        return 0;
+    };
+    WMCHK(up(t->ids, h_ids.data(), h_ids.size() * 4));
+    WMCHK(up(t->off, h_off.data(), h_off.size() * 4));
+    WMCHK(up(t->bias, h_bias.data(), h_bias.size() * 4));
+    WMCHK(up(t->ban, h_ban.data(), h_ban.size() * 4));
+    WMCHK(up(t->slot_id, h_sid.data(), h_sid.size() * 4));
+    WMCHK(up(t->slot_off, h_soff.data(), h_soff.size() * 4));
+    std::vector<int32_t> h_of((size_t)vocab, -1);
+    for (size_t k = 0; k < h_sid.size(); ++k) h_of[h_sid[k]] = (int32_t)k;
+    WMCHK(up(t->slot_of, h_of.data(), h_of.size() * 4));
+    if (slot_ids) *slot_ids = h_sid;
+    out = std::move(t);
+    return 0;
+}
+extern "C" int wm_set_sequence_bias(wm_model* m, const int32_t* ids, const int32_t* offsets, const float* bias, int n_seq, const int32_t* bad_ids,
+                                    const int32_t* bad_offsets, int n_bad) {
+    if (!m) return fail(WM_E_ARG, "bad argument");
+    HIPCHK(hipSetDevice(m->device));
+    std::shared_ptr<SeqTable> t;
+    WMCHK(build_seq_table(t, m->cfg.dims.vocab, ids, offsets, bias, n_seq, bad_ids, bad_offsets, n_bad));
+    if (t) t->gen = ++m->seq_gen;
+    m->repeat.sb = std::move(t);  // a held submit and a pending pass keep the table they were asked for with
     return 0;
 }
 // ---- token-level timestamps ------------------------------------------------------------------------------------
@@ -5873,13 +6026,14 @@ extern "C" int wm_op_dec_linear_capmap(float* out, float* cap, const float* x, c
 // logprob non-null: the LP instantiation of the same kernel variant, and the chosen ids' log-probabilities [B] (wm_op_logits_lp)
 static int op_logits(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                      const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype, const uint32_t* seen = nullptr,
-                     const uint32_t* ban = nullptr, float penalty = 1.f) {
+                     const uint32_t* ban = nullptr, float penalty = 1.f, const uint32_t* hit = nullptr, const int32_t* slot_id = nullptr,
+                     int n_slots = 0, const float* slot_bias = nullptr, const int32_t* slot_flags = nullptr) {
     if (!logits || !ids || !x || !ln_g || !ln_b || !emb || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
     if (K != 128 && K != 384 && K != 512 && K != 768 && K != 1024) return fail(WM_E_ARG, "K must be 128, 384, 512, 768 or 1024 (the logits kernels' d_model)");
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
     if (ranges && (timestamp_begin <= 0 || timestamp_begin >= N)) return fail(WM_E_ARG, "ranges need 0 < timestamp_begin < N");
     TmpDev t;
-    t.bufs.reserve(24);
+    t.bufs.reserve(28);
     hipStream_t st = nullptr;
     const int ldo = (N + 3) / 4 * 4, npart = dec_logits_parts(N);  // the kernel stores whole float4 groups below ldo
     DevBuf &dx = t.add(), &g = t.add(), &be = t.add(), &w = t.add(), &mk = t.add(), &o = t.add(), &av = t.add(), &ai = t.add(),
@@ -5945,6 +6099,29 @@ static int op_logits(float* logits, int32_t* ids, float* logprob, const float* x
         p.rp_ban = db.as<unsigned>();
         p.rp_ctl = dc.as<RepeatCtl>();
         p.rp_words = (int)words;
+        if (hit) {  // wm_op_logits_seq_bias: the rows' hit bits and slots as given, the SB instantiation of the same kernel variant
+            DevBuf &dh = t.add(), &dv = t.add(), &di = t.add(), &dt = t.add();
+            std::vector<int32_t> h_of((size_t)N, -1);
+            for (int k = 0; k < n_slots; ++k) h_of[slot_id[k]] = k;
+            std::vector<SeqSlot> h((size_t)B * SEQ_BIAS_MAX, SeqSlot{0.f, 0});
+            for (int b = 0; b < B; ++b)
+                for (int k = 0; k < n_slots; ++k) h[(size_t)b * SEQ_BIAS_MAX + k] = SeqSlot{slot_bias[(size_t)b * n_slots + k], slot_flags[(size_t)b * n_slots + k]};
+            SeqBiasCtl sc{};
+            sc.n_slots = n_slots;
+            sc.eot = -1;
+            WMCHK(dh.alloc(B * words * 4));
+            WMCHK(dv.alloc(h.size() * sizeof(SeqSlot)));
+            WMCHK(di.alloc((size_t)N * 4));
+            WMCHK(dt.alloc(sizeof(sc)));
+            sc.slot_of = di.as<int>();
+            HIPCHK(hipMemcpy(dh.p, hit, B * words * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(dv.p, h.data(), h.size() * sizeof(SeqSlot), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(di.p, h_of.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(dt.p, &sc, sizeof(sc), hipMemcpyHostToDevice));
+            p.sb_hit = dh.as<unsigned>();
+            p.sb_val = dv.as<SeqSlot>();
+            p.sb_ctl = dt.as<SeqBiasCtl>();
+        }
     }
     int lrc = 0;
     DISPATCH_DT(dtype, TT, lrc = launch_dec_logits<TT>(p, st));
@@ -6074,6 +6251,146 @@ extern "C" int wm_op_repeat_sets(uint32_t* seen, uint32_t* ban, const int32_t* t
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpy(seen + (size_t)s * B * words, ds.p, set_bytes, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(ban + (size_t)s * B * words, db.p, set_bytes, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+// The same two launches with sequence bias / bad words on given hit state: hit [B][ceil(N / 32)], the slots' ids
+// (ascending) and, per row and slot, the summed bias and the flags (bit 0 on, bit 1 ban).  seen / ban / penalty as above.
+extern "C" int wm_op_logits_seq_bias(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b,
+                                     const float* emb, const float* mask, const int32_t* ranges, int timestamp_begin, const uint32_t* seen,
+                                     const uint32_t* ban, float penalty, const uint32_t* hit, const int32_t* slot_id, int n_slots,
+                                     const float* slot_bias, const int32_t* slot_flags, int B, int N, int K, int dtype) {
+    if (!seen || !ban || !(penalty > 0.f) || !hit || !slot_id || !slot_bias || !slot_flags || n_slots < 1 || n_slots > SEQ_BIAS_MAX)
+        return fail(WM_E_ARG, "bad argument");
+    for (int k = 0; k < n_slots; ++k)
+        if (slot_id[k] < 0 || slot_id[k] >= N || (k && slot_id[k] <= slot_id[k - 1])) return fail(WM_E_ARG, "slot ids must ascend inside the vocabulary");
+    // the kernel looks a set bit's slot up without a check (the drivers set a bit only for a slot's id): refuse any other bit here
+    if (B > 0 && N > 0) {
+        std::vector<char> is_slot((size_t)N, 0);
+        for (int k = 0; k < n_slots; ++k) is_slot[slot_id[k]] = 1;
+        const int words = repeat_words(N);
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t < words * 32; ++t)
+                if ((hit[(size_t)b * words + (t >> 5)] >> (t & 31) & 1u) && (t >= N || !is_slot[t])) return fail(WM_E_ARG, "row %d: hit bit %d has no slot", b, t);
+    }
+    return op_logits(logits, ids, logprob, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype, seen, ban, penalty, hit, slot_id, n_slots,
+                     slot_bias, slot_flags);
+}
+// The hit state's bookkeeping alone, as wm_op_repeat_sets runs the sets': seq_bias_init on each row's prompt, then one argmax launch
+// per step that appends the row's next id of the table.  The table is built from the two lists as wm_set_sequence_bias builds it (same
+// refusals).  slot_id [n_seq + n_bad] and *n_slots: the table's slots; hit [steps + 1][B][ceil(vocab / 32)], slot_bias / slot_flags
+// [steps + 1][B][n_seq + n_bad] (the first *n_slots of each row are written) — entry 0 after the init, entry s after step s.
+extern "C" int wm_op_seq_bias_hits(uint32_t* hit, float* slot_bias, int32_t* slot_flags, int32_t* slot_id, int32_t* n_slots, const int32_t* tokens,
+                                   const int32_t* prompt_len, const int32_t* n_ids, int B, int stride, int vocab, int eot, const int32_t* seq_ids,
+                                   const int32_t* seq_off, const float* seq_bias, int n_seq, const int32_t* bad_ids, const int32_t* bad_off, int n_bad,
+                                   int steps) {
+    if (!hit || !slot_bias || !slot_flags || !slot_id || !n_slots || !tokens || !prompt_len || !n_ids || B <= 0 || stride <= 0 || vocab <= 0 || steps < 0)
+        return fail(WM_E_ARG, "bad argument");
+    for (int b = 0; b < B; ++b) {
+        if (prompt_len[b] < 1 || prompt_len[b] > n_ids[b] || n_ids[b] > stride) return fail(WM_E_ARG, "row %d: need 1 <= prompt_len <= n_ids <= stride", b);
+        for (int i = 0; i < n_ids[b]; ++i)
+            if (tokens[(size_t)b * stride + i] < 0 || tokens[(size_t)b * stride + i] >= vocab) return fail(WM_E_ARG, "token id out of range");
+    }
+    std::shared_ptr<SeqTable> tab;
+    std::vector<int32_t> sid;
+    WMCHK(build_seq_table(tab, vocab, seq_ids, seq_off, seq_bias, n_seq, bad_ids, bad_off, n_bad, &sid));
+    if (!tab) return fail(WM_E_ARG, "both lists are empty");
+    const int cap = n_seq + n_bad, ns = tab->n_slots;
+    *n_slots = ns;
+    std::copy(sid.begin(), sid.end(), slot_id);
+    TmpDev t;
+    t.bufs.reserve(16);
+    hipStream_t st = nullptr;
+    const size_t words = (size_t)repeat_words(vocab), set_bytes = (size_t)B * words * 4;
+    DevBuf &ds = t.add(), &db = t.add(), &dc = t.add(), &dh = t.add(), &dv = t.add(), &dsc = t.add(), &out = t.add(), &nt = t.add(), &fin = t.add(),
+           &ctl = t.add(), &pv = t.add(), &pi = t.add(), &nx = t.add(), &pos = t.add();
+    WMCHK(ds.alloc(set_bytes));
+    WMCHK(db.alloc(set_bytes));
+    WMCHK(dc.alloc(sizeof(RepeatCtl)));
+    WMCHK(dh.alloc(set_bytes));
+    WMCHK(dv.alloc((size_t)B * SEQ_BIAS_MAX * sizeof(SeqSlot), true));
+    WMCHK(dsc.alloc(sizeof(SeqBiasCtl)));
+    WMCHK(out.alloc((size_t)B * stride * 4, true));
+    WMCHK(nt.alloc((size_t)B * 4));
+    WMCHK(fin.alloc((size_t)B * 4, true));
+    WMCHK(ctl.alloc(sizeof(StepCtl), true));
+    WMCHK(pv.alloc((size_t)B * 4, true));  // one partial per row: value 0, index = the id to append
+    WMCHK(pi.alloc((size_t)B * 4));
+    WMCHK(nx.alloc((size_t)B * 4));
+    WMCHK(pos.alloc((size_t)B * 4, true));
+    std::vector<int32_t> h_out((size_t)B * stride, 0), h_idx(B), h_fin(B);
+    for (int b = 0; b < B; ++b) std::copy(tokens + (size_t)b * stride, tokens + (size_t)b * stride + prompt_len[b], h_out.begin() + (size_t)b * stride);
+    HIPCHK(hipMemcpy(out.p, h_out.data(), h_out.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(nt.p, prompt_len, (size_t)B * 4, hipMemcpyHostToDevice));
+    RepeatInitParams r{};
+    r.seen = ds.as<unsigned>();
+    r.ban = db.as<unsigned>();
+    r.words = (int)words;
+    r.B = B;
+    r.ctl = dc.as<RepeatCtl>();
+    r.penalty = 1.f;
+    r.ngram = 0;
+    r.out_tokens = out.as<int>();
+    r.out_stride = stride;
+    r.n_tokens = nt.as<int>();
+    launch_repeat_init(r, st);
+    SeqBiasInitParams q{};
+    q.hit = dh.as<unsigned>();
+    q.val = dv.as<SeqSlot>();
+    q.words = (int)words;
+    q.B = B;
+    q.ctl = dsc.as<SeqBiasCtl>();
+    q.table = tab->ctl(eot);
+    q.out_tokens = out.as<int>();
+    q.out_stride = stride;
+    q.n_tokens = nt.as<int>();
+    LCHK(launch_seq_bias_init(q, st));
+    HIPCHK(hipGetLastError());
+    std::vector<SeqSlot> h_val((size_t)B * SEQ_BIAS_MAX);
+    auto fetch = [&](int s) -> int {
+        HIPCHK(hipMemcpy(hit + (size_t)s * B * words, dh.p, set_bytes, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h_val.data(), dv.p, h_val.size() * sizeof(SeqSlot), hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b)
+            for (int k = 0; k < ns; ++k) {
+                slot_bias[((size_t)s * B + b) * cap + k] = h_val[(size_t)b * SEQ_BIAS_MAX + k].bias;
+                slot_flags[((size_t)s * B + b) * cap + k] = h_val[(size_t)b * SEQ_BIAS_MAX + k].flags;
+            }
+        return 0;
+    };
+    WMCHK(fetch(0));
+    for (int s = 1; s <= steps; ++s) {
+        for (int b = 0; b < B; ++b) {
+            const int at = prompt_len[b] + s - 1;
+            h_fin[b] = at >= n_ids[b];
+            h_idx[b] = h_fin[b] ? 0 : tokens[(size_t)b * stride + at];
+        }
+        HIPCHK(hipMemcpy(pi.p, h_idx.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(fin.p, h_fin.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+        ArgmaxParams a{};
+        a.V = vocab;
+        a.B = B;
+        a.pval = pv.as<float>();
+        a.pidx = pi.as<int>();
+        a.npart = 1;
+        a.next = nx.as<int>();
+        a.out_tokens = out.as<int>();
+        a.out_stride = stride;
+        a.n_tokens = nt.as<int>();
+        a.finished = fin.as<int>();
+        a.ctl = ctl.as<StepCtl>();
+        a.pos = pos.as<int>();
+        a.eot = -1;
+        a.ignore_eot = 1;
+        a.rp_seen = ds.as<unsigned>();
+        a.rp_ban = db.as<unsigned>();
+        a.rp_ctl = dc.as<RepeatCtl>();
+        a.rp_words = (int)words;
+        a.sb_hit = dh.as<unsigned>();
+        a.sb_val = dv.as<SeqSlot>();
+        a.sb_ctl = dsc.as<SeqBiasCtl>();
+        LCHK(launch_argmax_step(a, st));
+        HIPCHK(hipGetLastError());
+        WMCHK(fetch(s));
     }
     return 0;
 }

@@ -143,6 +143,31 @@ struct RepeatCtl {
 static const int REPEAT_NGRAM_MAX = 64;
 inline int repeat_words(int vocab) { return (vocab + 31) / 32; }
 
+// Sequence bias and bad words of the greedy loop (HF SequenceBiasLogitsProcessor, NoBadWordsLogitsProcessor).  The model's
+// table: the sequences of both lists, grouped by their LAST id into `slots` (ascending id; inside a slot the length-1 bias entry first,
+// then the bias sequences in the caller's order, then the bans), so one thread sums a slot's biases in HF's order.  Per utterance, for
+// the NEXT step: one SeqSlot per slot — the summed bias of the sequences whose prefix ends its history, whether one of them is a ban —
+// and a bit set over the vocabulary, `words` 32-bit words, with the bit of every slot that is on.  Built from the prompt by
+// seq_bias_init, kept current by the step's argmax launch (a bit is touched only where a slot goes on or off), read by the logits
+// epilogue.  The kernels reach the table through the state's control block, so one captured step serves any table.
+static const int SEQ_BIAS_MAX = 1024;     // sequences over the two lists together (so at most as many slots)
+static const int SEQ_BIAS_LEN_MAX = 32;   // ids per sequence
+struct SeqSlot {
+    float bias;  // sum over the slot's matching bias sequences, in table order
+    int flags;   // bit 0: on (a sequence of the slot matches: the id's bit is set); bit 1: a ban matches
+};
+struct SeqBiasCtl {
+    int n_seq, n_slots;
+    int eot;              // a length-1 ban of this id is dropped (HF's filter); -1 = none
+    const int* ids;       // flattened sequences, table order
+    const int* off;       // [n_seq + 1]
+    const float* bias;    // [n_seq] (a ban's is not read)
+    const int* ban;       // [n_seq] != 0: a bad word
+    const int* slot_id;   // [n_slots] ascending
+    const int* slot_off;  // [n_slots + 1] into the sequences
+    const int* slot_of;   // [vocab] id -> slot, -1 = none (the epilogue's lookup at a set bit)
+};
+
 struct DecLinearParams {
     const float* x;  // [B][ldx] fp32 activations
     int ldx;
@@ -206,6 +231,12 @@ struct DecLinearParams {
     const unsigned* rp_ban;
     const RepeatCtl* rp_ctl;
     int rp_words;
+    // dec_logits only — sequence bias / bad words (sb_hit null = off, needs the rp_* fields: penalty 1 and n-gram 0 are
+    // exact no-ops): where row b's bit in sb_hit[b] is set, the slot of that id adds its bias BEFORE the penalty and, with a ban,
+    // sets -inf AFTER the n-gram ban.  Non-null selects the SB instantiation of the same kernel variant.
+    const unsigned* sb_hit;  // [B][rp_words]
+    const SeqSlot* sb_val;   // [B][SEQ_BIAS_MAX]
+    const SeqBiasCtl* sb_ctl;
 };
 template <typename TW> int launch_dec_linear(const DecLinearParams& p, hipStream_t st);  // WM_LAUNCH_*
 bool dec_linear_supports_k(int K);  // K/32 k-steps must split into NW <= 16 waves x KPW <= 4 steps, or K = 3072 (the op hooks' answer)
@@ -322,6 +353,11 @@ struct ArgmaxParams {
     unsigned* rp_ban;
     const RepeatCtl* rp_ctl;
     int rp_words;
+    // sequence bias / bad words (sb_hit null = off, needs the rp_* fields): a row that stores its id also matches every
+    // sequence's prefix against its new history tail and rewrites its slots and the bits of the slots that went on or off
+    unsigned* sb_hit;  // [B][rp_words]
+    SeqSlot* sb_val;   // [B][SEQ_BIAS_MAX]
+    const SeqBiasCtl* sb_ctl;
 };
 int launch_argmax_step(const ArgmaxParams& p, hipStream_t st);  // WM_LAUNCH_*: refuses sets without the partials form or the id table
 // Start of a pass with the repetition processors, behind the init-tokens launch: writes ctl, clears both sets of the B rows, sets
@@ -338,6 +374,19 @@ struct RepeatInitParams {
     const int* n_tokens;  // [B]
 };
 void launch_repeat_init(const RepeatInitParams& p, hipStream_t st);
+// Start of a pass with sequence bias / bad words, behind the init-tokens launch: writes ctl, clears the B rows' bits and builds their
+// slots and bits for the first generated id from each row's prompt out_tokens[b][0 .. n_tokens[b]).
+struct SeqBiasInitParams {
+    unsigned* hit;  // [B][words]
+    SeqSlot* val;   // [B][SEQ_BIAS_MAX]
+    int words, B;
+    SeqBiasCtl* ctl;
+    SeqBiasCtl table;       // what ctl becomes
+    const int* out_tokens;  // [B][out_stride]
+    int out_stride;
+    const int* n_tokens;  // [B]
+};
+int launch_seq_bias_init(const SeqBiasInitParams& p, hipStream_t st);  // WM_LAUNCH_*
 struct InitTokensParams {
     int* out_tokens;
     int out_stride;

@@ -81,11 +81,13 @@ def log_mel(model, audios: Sequence[np.ndarray], sampling_rate: int = SAMPLING_R
 
 def transcribe_audio(model, audios: Sequence[np.ndarray], prompt: Sequence[int] = PROMPT, eot: int = EOT,
                      max_loop: int = MAX_LOOP, ignore_eot: bool = False, return_token_timestamps: bool = False,
-                     repetition_penalty=None, no_repeat_ngram_size=None, sampling_rate: int = SAMPLING_RATE):
+                     repetition_penalty=None, no_repeat_ngram_size=None, sampling_rate: int = SAMPLING_RATE, sequence_bias=None,
+                     bad_words_ids=None):
     """PCM in, token ids out (the mel never leaves the GPU).  sampling_rate / np.int16 rows: resampled on the GPU first (resample).  return_token_timestamps: (ids, times) with the time in seconds
     each id was spoken (needs model.set_alignment_heads); the attention columns are cropped to each clip's real audio.
     repetition_penalty / no_repeat_ngram_size: as Whisper.transcribe_batch."""
-    model._set_repeat(_lib.repeat_args(repetition_penalty, no_repeat_ngram_size))
+    model._set_repeat(_lib.repeat_args(repetition_penalty, no_repeat_ngram_size),
+                      _lib.seq_bias_args(sequence_bias, bad_words_ids, model.config.vocab_size))  # (as Whisper.transcribe_batch, DESIGN §34)
     audios = _at_16k(model, audios, sampling_rate)
     buf, n, stride = _pack(audios)
     p = np.asarray(prompt, np.int32)
@@ -164,7 +166,7 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
                                condition_on_prev_tokens: bool = False, prompt_condition_type: str = "first-segment",
                                prev_sot_token: int = 50361, logprob_threshold=None, no_speech_threshold=None, no_speech_token=None,
                                detect_language=None, return_token_timestamps: bool = False, repetition_penalty=None,
-                               no_repeat_ngram_size=None, sampling_rate: int = SAMPLING_RATE):
+                               no_repeat_ngram_size=None, sampling_rate: int = SAMPLING_RATE, sequence_bias=None, bad_words_ids=None):
     """Sequential long-form transcription of 16 kHz PCM of any length (HF generate's long-form path), the long
     log-mel never leaving the GPU.  sampling_rate / np.int16 rows: resampled on the GPU first (resample; the 16 kHz samples pass
     through host memory); all times are seconds of audio.  repetition_penalty / no_repeat_ngram_size: as Whisper.transcribe_long_form.
@@ -173,6 +175,7 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
     no_speech_threshold / no_speech_token / detect_language (then the detected ids [B] are returned as the last element): as
     Whisper.transcribe_long_form.  Returns per recording {"sequence": ids, "segments": [{"start", "end", "tokens"}]}."""
     rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
+    sb = _lib.seq_bias_args(sequence_bias, bad_words_ids, model.config.vocab_size)  # (as Whisper.transcribe_batch, DESIGN §34)
     lo, _keep2 = _lib.long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token, logprob_threshold,
                                 no_speech_threshold, no_speech_token)
     if no_speech_token is not None and int(no_speech_token) >= model.config.vocab_size:
@@ -191,7 +194,7 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
     if buf.shape[1] < stride:
         buf = np.pad(buf, ((0, 0), (0, stride - buf.shape[1])))
     opts, _keep = model._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
-    model._set_repeat(rp)
+    model._set_repeat(rp, sb)
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
     h = C.c_void_p()
     if tt:
@@ -222,7 +225,8 @@ def transcribe_audio_chunked(model, audios, chunk_length_s: float = 30.0, stride
                              prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP, suppress_tokens: Sequence[int] = (),
                              begin_suppress_tokens: Sequence[int] = (), timestamps=None, detect_language=None, repetition_penalty=None,
                              no_repeat_ngram_size=None, first_special: int = _lib.FIRST_SPECIAL, return_stats: bool = False, n_samples=None,
-                             return_timestamps=False, time_precision=None, tokenizer=None, sampling_rate: int = SAMPLING_RATE):
+                             return_timestamps=False, time_precision=None, tokenizer=None, sampling_rate: int = SAMPLING_RATE,
+                             sequence_bias=None, bad_words_ids=None):
     """Chunked long-form transcription of 16 kHz PCM of any length (HF's ASR pipeline with chunk_length_s / stride_length_s /
     batch_size = max_batch): every recording is cut into overlapping chunks (HF chunk_iter), the chunks of all recordings
     are decoded on their own in passes of up to max_batch rows, two passes in flight, and each recording's id lists are stitched on
@@ -294,6 +298,7 @@ def transcribe_audio_chunked(model, audios, chunk_length_s: float = 30.0, stride
         n_rec = len(audios)
         pcm_ptr, on_dev = buf.ctypes.data_as(C.c_void_p), 0
     rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
+    sb = _lib.seq_bias_args(sequence_bias, bad_words_ids, model.config.vocab_size)  # (as Whisper.transcribe_batch)
     lang_list = None
     if detect_language is not None:
         lang_list = _lib.lang_args(detect_language, model.config.vocab_size)
@@ -306,7 +311,7 @@ def transcribe_audio_chunked(model, audios, chunk_length_s: float = 30.0, stride
     if model._h is None:
         raise _lib.WhisperMiError("model not loaded")
     opts, _keep = model._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
-    model._set_repeat(rp)
+    model._set_repeat(rp, sb)
     R, total = n_rec, len(prompt) + 1 + max_loop
     per_rec = np.bincount(tab[:, 0], minlength=R) if len(tab) else np.zeros(R, np.int64)
     cap = max(1, int(per_rec.max()) * total)

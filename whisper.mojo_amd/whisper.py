@@ -150,6 +150,7 @@ class Whisper:
         self._h = None
         self._caches = weakref.WeakSet()  # live KVCaches of the loaded model
         self._n_align = 0  # alignment heads set on the loaded model (set_alignment_heads)
+        self._sb_key = None  # the lists of the sequence-bias table set on the loaded model (_set_repeat); None = no table
         self._score_pending = {}  # slot -> (id table, lengths, mel keep-alive) of a submitted score pass (score_submit / score_wait)
         self._align_pending = {}  # slot -> (id table, lengths, context lengths, logprobs asked, keep-alives) of a submitted align pass
         self.encoder = WhisperEncoder(self)
@@ -168,6 +169,7 @@ class Whisper:
         _lib.check(_lib.lib().wm_model_load_memory(_fp(w), w.size, C.byref(cfg), self.device, C.byref(h)))
         self._h = h
         self._n_align = 0
+        self._sb_key = None  # a freshly loaded model has no sequence-bias table
 
     def load_file(self, path: str):
         self.close()
@@ -176,9 +178,11 @@ class Whisper:
         _lib.check(_lib.lib().wm_model_load(path.encode(), C.byref(cfg), self.device, C.byref(h)))
         self._h = h
         self._n_align = 0
+        self._sb_key = None  # a freshly loaded model has no sequence-bias table
 
     def close(self):
         h, self._h = self._h, None
+        self._sb_key = None
         if h:
             for c in list(self._caches):
                 c._invalidate()
@@ -207,9 +211,18 @@ class Whisper:
                                  tb, no_ts, max_init)
         return opts, (p, sup, bsup)
 
-    def _set_repeat(self, rp):
-        """wm_set_repeat_options with a call's (penalty, n): every greedy call sets them, so a call without the arguments runs with both off."""
+    def _set_repeat(self, rp, sb=None):
+        """wm_set_repeat_options with a call's (penalty, n) and wm_set_sequence_bias with its lists (sb: _lib.seq_bias_args, None =
+        off): every greedy call sets them, so a call without the arguments runs with all of them off.  The table is rebuilt only
+        when the lists differ from the last call's."""
         _lib.check(_lib.lib().wm_set_repeat_options(self._h, rp[0], rp[1]))
+        key = None if sb is None else sb[0]
+        if key != self._sb_key:
+            ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+            a = [None, None, None, 0, None, None, 0] if sb is None else sb[1]
+            q = lambda x, t: None if x is None else x.ctypes.data_as(t)
+            _lib.check(_lib.lib().wm_set_sequence_bias(self._h, q(a[0], ip), q(a[1], ip), q(a[2], fp), a[3], q(a[4], ip), q(a[5], ip), a[6]))
+            self._sb_key = key
 
     def set_alignment_heads(self, pairs: Sequence[Sequence[int]]):
         """(layer, head) pairs whose cross-attention aligns ids with audio (HF generation_config.alignment_heads, e.g.
@@ -329,8 +342,14 @@ class Whisper:
                          n_frames=None, prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False,
                          no_speech_token: Optional[int] = None, n_init: Optional[int] = None,
                          detect_language: Optional[Sequence[int]] = None, repetition_penalty: Optional[float] = None,
-                         no_repeat_ngram_size: Optional[int] = None):
+                         no_repeat_ngram_size: Optional[int] = None, sequence_bias=None, bad_words_ids=None):
         """Batched Whisper.transcribe: one List[int] per utterance = prompt + generated ids (+ eot when hit).
+        sequence_bias / bad_words_ids: HF generate's options of the same names, given as ids.  sequence_bias is a dict
+        {(ids...): bias} or a list of [[ids...], bias]: a length-1 sequence always adds its bias to that id's logit; a longer one adds it
+        to its last id when the row's history (its prompt, then what it generated) ends with the ids before it.  bad_words_ids is a
+        list of id lists with bias -inf (an [eot] entry is dropped, as HF drops it).  Order: sequence_bias, repetition_penalty,
+        no_repeat_ngram_size, bad_words_ids, then the suppress lists, the timestamp rules and the log-prob sums.  At most 1024
+        sequences of 1..32 ids over both; a bias is finite or -inf; None / empty = off.  ValueError otherwise.
         repetition_penalty / no_repeat_ngram_size: HF generate's options of the same names, applied on the device at every
         step to each row's own history (its prompt, then what it generated), before the suppress lists, the timestamp rules and
         the log-prob sums: every id of the history has its logit multiplied (negative) or divided (else) by the penalty, once; every id
@@ -354,13 +373,14 @@ class Whisper:
         element becomes (token_logprobs, avg_logprob, no_speech_prob).  n_init: the number of initial ids (<|startoftranscript|>
         first); defaults to the shared prompt's length, required with prompts=."""
         rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
+        sb = _lib.seq_bias_args(sequence_bias, bad_words_ids, self.config.vocab_size)
         lang = None
         if detect_language is not None:
             lang = self._lang_args(detect_language, n_init, prompt, prompts, return_token_timestamps, no_speech_token, return_logprobs)
         ns = None if lang else self._ns_args(no_speech_token, n_init, prompt, prompts, return_logprobs)
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
-        self._set_repeat(rp)
+        self._set_repeat(rp, sb)
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]
@@ -420,8 +440,10 @@ class Whisper:
                              prev_sot_token: int = 50361, logprob_threshold: Optional[float] = None,
                              no_speech_threshold: Optional[float] = None, no_speech_token: Optional[int] = None,
                              detect_language: Optional[Sequence[int]] = None, return_token_timestamps: bool = False,
-                             repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None):
+                             repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                             sequence_bias=None, bad_words_ids=None):
         """Sequential long-form transcription (HF generate's long-form path, greedy).
+        sequence_bias / bad_words_ids: as transcribe_batch, matched against each window's own decoder ids.
         repetition_penalty / no_repeat_ngram_size: as transcribe_batch.  Every window's pass sees that window's decoder
         ids only — its prompt, a carried previous text included, then what it generates — as HF's per-window generate does.
         return_token_timestamps (HF generate's option on its long-form path; needs set_alignment_heads): every utterance
@@ -445,6 +467,7 @@ class Whisper:
         Returns per utterance {"sequence": ids, "segments": [{"start", "end", "tokens"}]} — HF's return_segments output with
         the padding-free sequences row; return_stats also returns {"windows", "stalled"}."""
         rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
+        sb = _lib.seq_bias_args(sequence_bias, bad_words_ids, self.config.vocab_size)
         lo, _keep3 = _lib.long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token, logprob_threshold,
                                     no_speech_threshold, no_speech_token)
         if no_speech_token is not None and int(no_speech_token) >= self.config.vocab_size:
@@ -490,14 +513,15 @@ class Whisper:
                 return self.transcribe_long_form(t.float().numpy(), n_frames, prompt, eot, max_loop, suppress_tokens,
                                                  begin_suppress_tokens, timestamps, return_stats, prompt_ids, condition_on_prev_tokens,
                                                  prompt_condition_type, prev_sot_token, logprob_threshold, no_speech_threshold, no_speech_token,
-                                                 detect_language, return_token_timestamps, repetition_penalty, no_repeat_ngram_size)
+                                                 detect_language, return_token_timestamps, repetition_penalty, no_repeat_ngram_size,
+                                                 sequence_bias, bad_words_ids)
             keep = t.contiguous().float()
             torch.cuda.current_stream(keep.device).synchronize()  # the library reads it on its own HIP stream
             ptr, on_dev = C.c_void_p(keep.data_ptr()), 1
         B, T = int(keep.shape[0]), int(keep.shape[2])
         nf = self._frames_arg(n_frames, B)
         opts, _keep2 = self._opts(prompt, eot, max_loop, False, suppress_tokens, begin_suppress_tokens, timestamps)
-        self._set_repeat(rp)
+        self._set_repeat(rp, sb)
         h = C.c_void_p()
         if tt:  # one entry point with or without the language list
             lang = np.zeros(B, np.int32)
@@ -524,7 +548,7 @@ class Whisper:
         """Chunked long-form transcription (HF's ASR pipeline with chunk_length_s / stride_length_s): pcm — one 1-D array
         of 16 kHz samples, a list of them, or a CUDA tensor [R, stride] with n_samples= — is cut into overlapping chunks, the chunks of all recordings fill passes of max_batch
         rows, and every recording's ids are stitched on the GPU.  decode_options: prompt, eot, max_loop, suppress_tokens,
-        begin_suppress_tokens, timestamps, detect_language, repetition_penalty, no_repeat_ngram_size (as transcribe_batch, per
+        begin_suppress_tokens, timestamps, detect_language, repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids (as transcribe_batch, per
         chunk) and first_special.  -> per recording {"sequence": ids, "chunks": [(start_s, len_s, stride_l_s, stride_r_s, ids_k)]
         (with return_chunks)}; see frontend.transcribe_audio_chunked.  return_timestamps: False, True (HF's segments: "segments":
         [{"timestamp": (start, end | None), "ids"}]) or "word" (also "token_timestamps" per segment, "words" with tokenizer=;
@@ -547,7 +571,7 @@ class Whisper:
                           prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False,
                           no_speech_token: Optional[int] = None, n_init: Optional[int] = None,
                           detect_language: Optional[Sequence[int]] = None, repetition_penalty: Optional[float] = None,
-                          no_repeat_ngram_size: Optional[int] = None):
+                          no_repeat_ngram_size: Optional[int] = None, sequence_bias=None, bad_words_ids=None):
         """Pipelined form (wm_transcribe_submit): enqueue encoder + greedy loop for this batch on pipeline slot 0..7 and
         return at once; `transcribe_wait(slot)` collects the ids.  Submitting batch i+1 before waiting for batch i lets
         its encoder overlap batch i's decode.  return_token_timestamps / n_frames: as transcribe_batch; the matching
@@ -555,15 +579,17 @@ class Whisper:
         (ids, (token_logprobs, avg_logprob)).  no_speech_token / n_init: as transcribe_batch; the matching transcribe_wait returns
         (ids, (token_logprobs, avg_logprob, no_speech_prob)).  detect_language: as transcribe_batch; the matching transcribe_wait
         returns what transcribe_batch returns.  repetition_penalty / no_repeat_ngram_size: as transcribe_batch; the pass keeps the
-        values it was submitted with, and under coalesce = 2 it pairs only with a submit that carries the same values."""
+        values it was submitted with, and under coalesce = 2 it pairs only with a submit that carries the same values.
+        sequence_bias / bad_words_ids: as transcribe_batch, kept and paired likewise (the same lists as the previous call = the same table)."""
         rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
+        sb = _lib.seq_bias_args(sequence_bias, bad_words_ids, self.config.vocab_size)
         lang = None
         if detect_language is not None:
             lang = self._lang_args(detect_language, n_init, prompt, prompts, return_token_timestamps, no_speech_token, return_logprobs)
         ns = None if lang else self._ns_args(no_speech_token, n_init, prompt, prompts, return_logprobs)
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
-        self._set_repeat(rp)
+        self._set_repeat(rp, sb)
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]

@@ -260,14 +260,17 @@ def argmax(t) -> int:
 
 
 def logits_argmax(x, ln_g, ln_b, emb, dtype=DT_F32, mask=None, ranges=None, timestamp_begin: int = 0, return_logprobs: bool = False,
-                  seen=None, ban=None, penalty: float = 1.0):
+                  seen=None, ban=None, penalty: float = 1.0, hit=None, slot_id=None, slot_bias=None, slot_flags=None):
     """whisper.mojo:156-166 + the greedy argmax: (logits [B, N] = layer_norm(x)·embᵀ, ids [B]) on the decode step's logits kernel
     and fused argmax.  mask [N] additive (0 / -inf) on the argmax candidates; ranges [B, 4] = (text_lo, text_hi, ts_lo, ts_hi)
     with timestamp_begin > 0: the timestamp decision (wm_op_logits).  return_logprobs: (logits, ids, logprob [B]) from the log-prob
     instantiation of the same kernels (wm_op_logits_lp): logits[id] - logsumexp over the candidates the mask and the ranges leave.
     seen / ban [B, ceil(N / 32)] uint32 (both or neither): the repetition-processor instantiation (wm_op_logits_processed, DESIGN
     §29) — row b's logits at the ids of seen[b] times (negative) or over (else) `penalty`, those of ban[b] -inf, ahead of all of the
-    above; the returned logits are the processed ones."""
+    above; the returned logits are the processed ones.  hit [B, ceil(N / 32)] uint32 with slot_id [S] (ascending ids), slot_bias
+    [B, S] float32 and slot_flags [B, S] int32 (bit 0 on, bit 1 ban), beside seen / ban: the sequence-bias instantiation
+    (wm_op_logits_seq_bias) — where row b's hit bit of an id is set its slot's bias is added ahead of the penalty, or the
+    value is -inf under a ban."""
     f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
     x, emb, mask = f(x), f(emb), f(mask)
     g, b = f(ln_g).ravel(), f(ln_b).ravel()
@@ -292,6 +295,17 @@ def logits_argmax(x, ln_g, ln_b, emb, dtype=DT_F32, mask=None, ranges=None, time
             raise ValueError("seen and ban must both be [B, ceil(N / 32)] uint32")
         up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
         lp = np.zeros(B, np.float32) if return_logprobs else None
+        if hit is not None:
+            hw = np.ascontiguousarray(hit, np.uint32)
+            sid = np.ascontiguousarray(slot_id, np.int32).ravel()
+            sbias, sflags = np.ascontiguousarray(slot_bias, np.float32), np.ascontiguousarray(slot_flags, np.int32)
+            if hw.shape != (B, words) or sbias.shape != (B, sid.size) or sflags.shape != (B, sid.size):
+                raise ValueError("hit must be [B, ceil(N / 32)], slot_bias and slot_flags [B, len(slot_id)]")
+            _lib.check(_lib.lib().wm_op_logits_seq_bias(_fp(logits), ip(ids), _fp(lp), _fp(x), _fp(g), _fp(b), _fp(emb),
+                                                        _fp(mask.ravel() if mask is not None else None), ip(rg), int(timestamp_begin),
+                                                        up(sets[0]), up(sets[1]), float(penalty), up(hw), ip(sid), int(sid.size), _fp(sbias),
+                                                        ip(sflags), B, N, K, dtype))
+            return (logits, ids, lp) if return_logprobs else (logits, ids)
         _lib.check(_lib.lib().wm_op_logits_processed(_fp(logits), ip(ids), _fp(lp), _fp(x), _fp(g), _fp(b), _fp(emb),
                                                      _fp(mask.ravel() if mask is not None else None), ip(rg), int(timestamp_begin),
                                                      up(sets[0]), up(sets[1]), float(penalty), B, N, K, dtype))
@@ -448,3 +462,27 @@ def repeat_sets(tokens, prompt_len, n_ids, vocab: int, ngram: int, steps: int):
     ip, up = (lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32)))
     _lib.check(_lib.lib().wm_op_repeat_sets(up(seen), up(ban), ip(tok), ip(pl), ip(nn), B, stride, int(vocab), int(ngram), int(steps)))
     return seen, ban
+
+
+def seq_bias_hits(tokens, prompt_len, n_ids, vocab: int, sequence_bias, bad_words_ids, steps: int, eot: int = -1):
+    """The sequence-bias bookkeeping alone (wm_op_seq_bias_hits): tokens / prompt_len / n_ids as repeat_sets, the two lists
+    as transcribe_batch takes them -> (slot_id [S], hit [steps + 1, B, ceil(vocab / 32)] uint32, slot_bias [steps + 1, B, S] float32,
+    slot_flags [steps + 1, B, S] int32): entry 0 behind the init kernel, entry s behind the argmax launch of step s."""
+    tok = np.ascontiguousarray(tokens, np.int32)
+    pl, nn = np.ascontiguousarray(prompt_len, np.int32).ravel(), np.ascontiguousarray(n_ids, np.int32).ravel()
+    if tok.ndim != 2 or pl.size != tok.shape[0] or nn.size != tok.shape[0]:
+        raise ValueError("tokens must be [B, stride], prompt_len and n_ids [B]")
+    sb = _lib.seq_bias_args(sequence_bias, bad_words_ids, vocab)
+    if sb is None:
+        raise ValueError("both lists are empty")
+    a = sb[1]
+    B, stride = tok.shape
+    words, cap = (vocab + 31) // 32, a[3] + a[6]
+    hit = np.zeros((steps + 1, B, words), np.uint32)
+    sbias, sflags = np.zeros((steps + 1, B, cap), np.float32), np.zeros((steps + 1, B, cap), np.int32)
+    sid, ns = np.zeros(cap, np.int32), np.zeros(1, np.int32)
+    ip, up = (lambda x: None if x is None else x.ctypes.data_as(C.POINTER(C.c_int32))), (lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32)))
+    _lib.check(_lib.lib().wm_op_seq_bias_hits(up(hit), _fp(sbias), ip(sflags), ip(sid), ip(ns), ip(tok), ip(pl), ip(nn), B, stride, int(vocab),
+                                              int(eot), ip(a[0]), ip(a[1]), _fp(a[2]), a[3], ip(a[4]), ip(a[5]), a[6], int(steps)))
+    S = int(ns[0])
+    return sid[:S].copy(), hit, sbias[:, :, :S].copy(), sflags[:, :, :S].copy()
