@@ -25,13 +25,13 @@
 #include <unordered_set>
 #include <vector>
 
-#include "wm_kernels.h"
+#include "wm_host.h"
 
 using namespace wm;
 
 // ------------------------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
-static int fail(int code, const char* fmt, ...) {
+int fail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -40,26 +40,14 @@ static int fail(int code, const char* fmt, ...) {
     g_err = buf;
     return code;
 }
-#define HIPCHK(expr)                                                                                     \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return fail(WM_E_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-#define WMCHK(expr)            \
-    do {                       \
-        int rc_ = (expr);      \
-        if (rc_ != 0) return rc_; \
-    } while (0)
 
 extern "C" const char* wm_last_error(void) { return g_err.c_str(); }
 extern "C" int wm_abi_version(void) { return WM_ABI_VERSION; }
 
-// a launcher's status (wm_kernels.h WM_LAUNCH_*) as a C-ABI status: a refused shape is the caller's argument error
-static int launch_rc(int st) {
+int launch_rc(int st) {
     if (st == wm::WM_LAUNCH_OK) return 0;
     return fail(st == wm::WM_LAUNCH_HIP ? WM_E_HIP : WM_E_ARG, "%s", wm::launch_last_refusal());
 }
-#define LCHK(expr) WMCHK(launch_rc(expr))
 
 // Developer timeline (WM_TRACE_EVENTS=1): HIP events recorded on the library's streams at pass / phase boundaries and
 // printed, sorted on the GPU clock, when the model is freed.  The profiler serialises concurrent queues; events do not.
@@ -102,63 +90,11 @@ static void trace_dump() {
     for (auto& r : rows) fprintf(stderr, "[wm-trace] %10.3f ms  %s\n", r.first, r.second.c_str());
 }
 
-static size_t dt_size(int dt) { return dt == WM_F32 ? 4 : 2; }
 static int dec_dtype(const wm_config& c) { return c.decoder_fp32 ? WM_F32 : c.compute_dtype; }  // operand dtype of the decoder
-static inline uint16_t f32_to_bf16_host(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static inline uint16_t f32_to_f16_host(float f) {
-    _Float16 h = (_Float16)f;
-    uint16_t u;
-    memcpy(&u, &h, 2);
-    return u;
-}
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int alloc(size_t n, bool zero = false) {
-        release();  // re-allocation never leaks the previous block
-        bytes = n ? n : 16;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) return fail(WM_E_HIP, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
-        if (zero) {
-            // hipMemset on device memory is asynchronous to the host and runs on the null stream, which the library's
-            // non-blocking streams do not wait for: finish it here, or the first kernels on a fresh buffer can race the
-            // zeroing (seen once in ~6 runs of the eight-slot test as a wrong token row)
-            e = hipMemset(p, 0, bytes);
-            if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-            if (e != hipSuccess) return fail(WM_E_HIP, "hipMemset: %s", hipGetErrorString(e));
-        }
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    template <typename T> T* as() const { return (T*)p; }
-};
 
 static int grow(DevBuf& b, size_t bytes) { return b.p && b.bytes >= bytes ? 0 : b.alloc(bytes); }
 
-// scratch of an op-level entry point, released on return
-struct TmpDev {
-    std::vector<DevBuf> bufs;
-    ~TmpDev() {
-        for (auto& b : bufs) b.release();
-    }
-    DevBuf& add() {
-        bufs.emplace_back();
-        return bufs.back();
-    }
-};
-
-// host fp32 -> device buffer in dtype dt
-static int upload(DevBuf& b, const float* h, size_t n, int dt) {
+int upload(DevBuf& b, const float* h, size_t n, int dt) {
     WMCHK(b.alloc(n * dt_size(dt)));
     if (dt == WM_F32) {
         HIPCHK(hipMemcpy(b.p, h, n * 4, hipMemcpyHostToDevice));
@@ -216,26 +152,6 @@ struct ScoreAsk {  // a score pass, already validated by score_che
 struct WinAsk {  // the windows a long-form timestamp pass decodes
     const int32_t* items;  // device [B][3]: (utterance, seek, frames) per row
     int n_real;            // rows [n_real, B) repeat row 0: no align rows, zero times
-};
-// One table of wm_set_sequence_bias: both lists validated, grouped by last id and copied to the device.  Immutable once
-// built; the model, a held submit and a state's pending pass each hold a reference, so replacing the model's table changes none of them.
-struct SeqTable {
-    int gen = 0;  // the model's count of tables built: what a PassAsk carries and what pairs two submits
-    int device = 0;  // where the buffers live: the last reference may drop while another device is current
-    int n_seq = 0, n_slots = 0;
-    DevBuf ids, off, bias, ban, slot_id, slot_off, slot_of;
-    SeqTable() = default;
-    SeqTable(const SeqTable&) = delete;
-    SeqTable& operator=(const SeqTable&) = delete;
-    ~SeqTable() {
-        int cur = -1;
-        const bool moved = hipGetDevice(&cur) == hipSuccess && cur != device && hipSetDevice(device) == hipSuccess;
-        for (DevBuf* b : {&ids, &off, &bias, &ban, &slot_id, &slot_off, &slot_of}) b->release();
-        if (moved) (void)hipSetDevice(cur);
-    }
-    SeqBiasCtl ctl(int eot) const {
-        return SeqBiasCtl{n_seq, n_slots, eot, ids.as<int>(), off.as<int>(), bias.as<float>(), ban.as<int>(), slot_id.as<int>(), slot_off.as<int>(), slot_of.as<int>()};
-    }
 };
 struct RepeatAsk {  // the logits processors of a greedy pass, as wm_set_repeat_options / wm_set_sequence_bias left them when the pass was asked for
     float penalty = 1.f;
@@ -538,24 +454,9 @@ struct wm_state {
 };
 
 // ------------------------------------------------------------------------------------------------------------
-#define DISPATCH_DT(dt, T, ...)              \
-    do {                                     \
-        if ((dt) == WM_F32) {                \
-            typedef float T;                 \
-            __VA_ARGS__;                     \
-        } else if ((dt) == WM_BF16) {        \
-            typedef wm::bf16 T;              \
-            __VA_ARGS__;                     \
-        } else {                             \
-            typedef wm::f16 T;               \
-            __VA_ARGS__;                     \
-        }                                    \
-    } while (0)
-
-static int gemm_dispatch(int dt_in, int dt_out, const GemmParams& p, int batch, hipStream_t st);
 // C = LN(x) W^T (+ epilogue of p): p.A names the scratch for the normalised rows.  The A-stationary GEMM normalises the fp32 rows
 // while it loads them (no LayerNorm launch, no 16-bit copy through HBM); every other shape runs layernorm_rows first.
-static int ln_then_gemm(int dt_in, int dt_out, GemmParams p, const float* x, const float* g, const float* b, hipStream_t st) {
+int ln_then_gemm(int dt_in, int dt_out, GemmParams p, const float* x, const float* g, const float* b, hipStream_t st) {
     if (gemm_nt_fuses_layernorm(dt_in == WM_F32 ? 4 : 2, p, 1)) {
         p.A = x;
         p.ln_g = g;
@@ -566,7 +467,7 @@ static int ln_then_gemm(int dt_in, int dt_out, GemmParams p, const float* x, con
     return gemm_dispatch(dt_in, dt_out, p, 1, st);
 }
 // 0 or a WM_E_* status with wm_last_error set (a shape the kernels refuse: nothing was launched)
-static int gemm_dispatch(int dt_in, int dt_out, const GemmParams& p, int batch, hipStream_t st) {
+int gemm_dispatch(int dt_in, int dt_out, const GemmParams& p, int batch, hipStream_t st) {
     int rc;
     if (dt_in == WM_F32) {
         rc = launch_gemm_nt<float, float>(p, batch, st);
@@ -642,7 +543,7 @@ static AttnW read_attn(Reader& r, size_t d) {
     return a;
 }
 // [co][ci][3] -> [co][3][ci_pad]   (transpose_conv_weights, whisper_tensor.mojo:358-364, plus channel padding)
-static std::vector<float> conv_relayout(const float* w, int co, int ci, int cip) {
+std::vector<float> conv_relayout(const float* w, int co, int ci, int cip) {
     std::vector<float> o((size_t)co * 3 * cip, 0.f);
     for (int a = 0; a < co; ++a)
         for (int c = 0; c < ci; ++c)
@@ -1225,7 +1126,6 @@ extern "C" int wm_state_len(const wm_state* s) { return state_is_live(s) ? s->ho
 
 // ---- encoder: whisper.mojo:71-99 ------------------------------------------------------------------------------------
 static void* off_bytes(const DevBuf& b, size_t bytes) { return (char*)b.p + bytes; }
-static const float ATTN_SCALE = 1.0f / sqrtf(64.0f);  // every attention here has heads of 64 columns
 
 static int cross_kv_chunk(wm_model* m, wm_state* s, int c0, int bc, hipStream_t st) {
     // cross K/V for utterances [c0, c0+bc) from enc_t (rows 0..bc*T): layers.mojo:150-154, all layers in one GEMM
@@ -1456,12 +1356,12 @@ extern "C" int wm_state_set_encoder_output(wm_model* m, wm_state* s, const float
 }
 
 // ---- one decode step for all B utterances: whisper.mojo:130-167 with L_tgt = 1 ------------------------------------
-static int dec_linear_dispatch(int dt, const DecLinearParams& p, hipStream_t st) {
+int dec_linear_dispatch(int dt, const DecLinearParams& p, hipStream_t st) {
     int rc = 0;
     DISPATCH_DT(dt, TT, rc = launch_dec_linear<TT>(p, st));
     return launch_rc(rc);
 }
-static int attn_decode_dispatch(int dt, const AttnDecParams& p, hipStream_t st, const int* key_lo = nullptr) {
+int attn_decode_dispatch(int dt, const AttnDecParams& p, hipStream_t st, const int* key_lo) {
     int rc = 0;
     DISPATCH_DT(dt, TT, rc = launch_attn_decode<TT>(p, st, key_lo));
     return launch_rc(rc);
@@ -1476,12 +1376,6 @@ struct DecView {
 static DecView whole_batch(wm_model* m, wm_state* s) { return DecView{0, s->B, m->stream, s->ctl.as<StepCtl>()}; }
 template <typename T> static T* lane_ptr(const DevBuf& buf, const DecView& v, size_t stride) { return buf.as<T>() + (size_t)v.b0 * stride; }  // view v's rows
 
-// What a sweep over the tied embedding reads: the final LayerNorm and the embedding in the decoder's operand dtype
-struct VocabHead {
-    const float *ln_g, *ln_b;
-    const void* emb;
-    int vocab, d_model;
-};
 static VocabHead vocab_head(const wm_model* m) {
     return VocabHead{m->dec_ln_g.as<float>(), m->dec_ln_b.as<float>(), dec_dtype(m->cfg) == WM_F32 ? m->tok_emb_f.p : m->tok_emb_t.p,
                      m->cfg.dims.vocab, m->cfg.dims.d_model};
@@ -1571,8 +1465,8 @@ struct DecPass {
     bool key_window = true;         // false: no per-row key windows even on a per-row pass (the language pass, §19)
 };
 // What every linear launch of a decoder pass sets (ln_g null: no LayerNorm prologue); each block's special part is added by name below
-static DecLinearParams linear_block(const float* x, const float* ln_g, const float* ln_b, const void* W, const float* bias, int N, int K, int B,
-                                 float* out, int ldo) {
+DecLinearParams linear_block(const float* x, const float* ln_g, const float* ln_b, const void* W, const float* bias, int N, int K, int B,
+                             float* out, int ldo) {
     DecLinearParams p{};
     p.x = x;
     p.ldx = K;
@@ -2033,8 +1927,8 @@ static void ns_capture(wm_model* m, wm_state* s, const DecView& v, size_t row_of
     const size_t d = m->cfg.dims.d_model;
     launch_no_speech_capture(lane_ptr<float>(s->dx, v, d) + row_off * d, lane_ptr<float>(s->ns.x, v, d), v.nb, (int)d, v.st);
 }
-static int ns_sweep(int T, const float* x, const VocabHead& h, int B, int npart, float* pmax, int* pidx, float* psum, int token, float* prob,
-                    float* lse, hipStream_t st) {
+int ns_sweep(int T, const float* x, const VocabHead& h, int B, int npart, float* pmax, int* pidx, float* psum, int token, float* prob,
+             float* lse, hipStream_t st) {
     DecLinearParams p = linear_block(x, h.ln_g, h.ln_b, h.emb, nullptr, h.vocab, h.d_model, B, nullptr, (h.vocab + 3) / 4 * 4);
     p.amax_val = pmax;
     p.amax_idx = pidx;
@@ -2912,7 +2806,7 @@ extern "C" int wm_transcribe_wait_lp_ns(wm_model* m, int slot, int32_t* tokens_o
 }
 // ---- language detection ----------------------------------------------------------------------------------------------
 // Everything is refused before anything is launched.
-static int lang_list_check(int vocab, const int32_t* lang_ids, int n_lang) {
+int lang_list_check(int vocab, const int32_t* lang_ids, int n_lang) {
     if (n_lang < 1 || n_lang > LANG_DETECT_MAX) return fail(WM_E_ARG, "n_lang = %d outside [1, %d]", n_lang, LANG_DETECT_MAX);
     if (!lang_ids) return fail(WM_E_ARG, "bad argument");
     for (int i = 0; i < n_lang; ++i) {
@@ -3023,8 +2917,8 @@ extern "C" int wm_set_repeat_options(wm_model* m, float repetition_penalty, int 
 // Validates both lists and builds the device table: the sequences grouped by last id (ascending), inside a group the length-1 bias
 // first, then the bias sequences in the caller's order, then the bans — the order one thread sums a group in.  Nothing is allocated
 // before every argument has passed.  slot_ids (optional): the groups' ids for the op hook.
-static int build_seq_table(std::shared_ptr<SeqTable>& out, int vocab, const int32_t* ids, const int32_t* off, const float* bias, int n_seq,
-                           const int32_t* bad_ids, const int32_t* bad_off, int n_bad, std::vector<int32_t>* slot_ids = nullptr) {
+int build_seq_table(std::shared_ptr<SeqTable>& out, int vocab, const int32_t* ids, const int32_t* off, const float* bias, int n_seq,
+                    const int32_t* bad_ids, const int32_t* bad_off, int n_bad, std::vector<int32_t>* slot_ids) {
     if (n_seq < 0 || n_bad < 0 || (n_seq > 0 && (!ids || !off || !bias)) || (n_bad > 0 && (!bad_ids || !bad_off))) return fail(WM_E_ARG, "bad argument");
     if ((long long)n_seq + n_bad > SEQ_BIAS_MAX) return fail(WM_E_ARG, "%d + %d sequences: at most %d over the two lists", n_seq, n_bad, SEQ_BIAS_MAX);
     struct Ent {
@@ -3275,15 +3169,13 @@ extern "C" int wm_op_token_times(float* times, const float* weights, int n_sel, 
         return 0;
     }
     TmpDev t;
-    t.bufs.reserve(8);
     DevBuf &probs = t.add(), &mean = t.add(), &sd = t.add(), &M = t.add(), &tr = t.add(), &tm = t.add(), &nt = t.add();
     WMCHK(upload(probs, weights, (size_t)n_sel * R * F, WM_F32));
     WMCHK(mean.alloc((size_t)n_sel * F * 4));
     WMCHK(sd.alloc((size_t)n_sel * F * 4));
     WMCHK(M.alloc((size_t)R * F * 4));
     WMCHK(tm.alloc((size_t)total * 4));
-    WMCHK(nt.alloc(4));
-    HIPCHK(hipMemcpy(nt.p, &total, 4, hipMemcpyHostToDevice));
+    WMCHK(upload_bytes(nt, &total, 4));
     AlignParams p{};
     p.B = 1;
     p.L = R;
@@ -3322,17 +3214,13 @@ extern "C" int wm_op_token_times_rows(float* times, const float* weights, int n_
     }
     if (out_stride < need) return fail(WM_E_ARG, "out_stride %d is smaller than max(row0 + R + 1) = %d", out_stride, need);
     TmpDev t;
-    t.bufs.reserve(10);
     DevBuf &probs = t.add(), &mean = t.add(), &sd = t.add(), &M = t.add(), &tr = t.add(), &tm = t.add(), &dr = t.add(), &df = t.add(), &d0 = t.add();
     WMCHK(upload(probs, weights, (size_t)n_tab * n_sel * L * T, WM_F32));
     WMCHK(mean.alloc((size_t)n_tab * n_sel * T * 4));
     WMCHK(sd.alloc((size_t)n_tab * n_sel * T * 4));
     WMCHK(M.alloc((size_t)n_tab * L * T * 4));
     WMCHK(tm.alloc((size_t)n_tab * out_stride * 4));
-    for (auto pr : {std::make_pair(&dr, R), std::make_pair(&df, F), std::make_pair(&d0, row0)}) {
-        WMCHK(pr.first->alloc((size_t)n_tab * 4));
-        HIPCHK(hipMemcpy(pr.first->p, pr.second, (size_t)n_tab * 4, hipMemcpyHostToDevice));
-    }
+    for (auto pr : {std::make_pair(&dr, R), std::make_pair(&df, F), std::make_pair(&d0, row0)}) WMCHK(upload_bytes(*pr.first, pr.second, (size_t)n_tab * 4));
     AlignParams p{};
     p.B = n_tab;
     p.L = L;
@@ -3376,12 +3264,10 @@ extern "C" int wm_op_align_probs(float* probs, const float* q, const float* kv, 
         if (layer_head_pairs[2 * k] < 0 || layer_head_pairs[2 * k] >= n_layers || layer_head_pairs[2 * k + 1] < 0 || layer_head_pairs[2 * k + 1] >= d / 64)
             return fail(WM_E_ARG, "pair %d: layer in [0, %d), head in [0, %d)", k, n_layers, d / 64);
     TmpDev t;
-    t.bufs.reserve(8);
     DevBuf &cap = t.add(), &keys = t.add(), &wk = t.add(), &kh = t.add(), &pr = t.add(), &dr = t.add();
     WMCHK(upload(cap, q, (size_t)B * L * n_sel * 64, WM_F32));
     WMCHK(upload(pr, probs, (size_t)B * n_sel * L * T, WM_F32));
-    WMCHK(dr.alloc((size_t)B * 4));
-    HIPCHK(hipMemcpy(dr.p, rows, (size_t)B * 4, hipMemcpyHostToDevice));
+    WMCHK(upload_bytes(dr, rows, (size_t)B * 4));
     AlignParams p{};
     p.cap = cap.as<float>();
     p.B = B;
@@ -3422,16 +3308,12 @@ extern "C" int wm_op_align_norm(float* M, const float* weights, int n_tab, int n
     for (int b = 0; b < n_tab; ++b)
         if (R[b] < 0 || R[b] > L || F[b] < 1 || F[b] > T) return fail(WM_E_ARG, "table %d: R in [0, L], F in [1, T]", b);
     TmpDev t;
-    t.bufs.reserve(8);
     DevBuf &probs = t.add(), &mean = t.add(), &sd = t.add(), &dm = t.add(), &dr = t.add(), &df = t.add();
     WMCHK(upload(probs, weights, (size_t)n_tab * n_sel * L * T, WM_F32));
     WMCHK(upload(dm, M, (size_t)n_tab * L * T, WM_F32));
     WMCHK(mean.alloc((size_t)n_tab * n_sel * T * 4));
     WMCHK(sd.alloc((size_t)n_tab * n_sel * T * 4));
-    for (auto pr : {std::make_pair(&dr, R), std::make_pair(&df, F)}) {
-        WMCHK(pr.first->alloc((size_t)n_tab * 4));
-        HIPCHK(hipMemcpy(pr.first->p, pr.second, (size_t)n_tab * 4, hipMemcpyHostToDevice));
-    }
+    for (auto pr : {std::make_pair(&dr, R), std::make_pair(&df, F)}) WMCHK(upload_bytes(*pr.first, pr.second, (size_t)n_tab * 4));
     AlignParams p{};
     p.B = n_tab;
     p.L = L;
@@ -3726,19 +3608,14 @@ extern "C" int wm_op_resample(float* out, const void* in, int in_dtype, const in
     WMCHK(resample_check(in, in_dtype, n_in, B, stride_in, sr_in, out, stride_out, no.data(), &longest));
     wm_model::Frontend::Resampler r;
     TmpDev tmp;
-    tmp.bufs.reserve(8);
     DevBuf &din = tmp.add(), &dout = tmp.add(), &dni = tmp.add(), &dno = tmp.add();
     const size_t es = in_dtype == WM_I16 ? 2 : 4, nin = (size_t)B * stride_in, nout = (size_t)B * stride_out;
     int rc = resampler_build(r, sr_in);
-    if (!rc) rc = din.alloc(nin * es);
-    if (!rc) rc = dout.alloc(nout * 4);
-    if (!rc) rc = dni.alloc((size_t)B * 4);
-    if (!rc) rc = dno.alloc((size_t)B * 4);
     auto run = [&]() -> int {
-        HIPCHK(hipMemcpy(din.p, in, nin * es, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dout.p, out, nout * 4, hipMemcpyHostToDevice));  // in and out: a cell the kernel does not store keeps the caller's value
-        HIPCHK(hipMemcpy(dni.p, n_in, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dno.p, n_out, (size_t)B * 4, hipMemcpyHostToDevice));
+        WMCHK(upload_bytes(din, in, nin * es));
+        WMCHK(upload_bytes(dout, out, nout * 4));  // in and out: a cell the kernel does not store keeps the caller's value
+        WMCHK(upload_bytes(dni, n_in, (size_t)B * 4));
+        WMCHK(upload_bytes(dno, n_out, (size_t)B * 4));
         WMCHK(resample_launch(r, din.p, in_dtype, dni.as<int>(), B, stride_in, dout.as<float>(), stride_out, dno.as<int>(), longest, nullptr));
         HIPCHK(hipMemcpy(out, dout.p, nout * 4, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(n_out, dno.p, (size_t)B * 4, hipMemcpyDeviceToHost));  // what the kernel computed, not the host's copy
@@ -3780,7 +3657,6 @@ extern "C" int wm_resample_pcm(wm_model* m, const void* in, int in_dtype, int in
     WMCHK(resampler_get(m, sr_in, &r));
     hipStream_t st = m->stream;
     TmpDev tmp;
-    tmp.bufs.reserve(8);
     DevBuf &din = tmp.add(), &dout = tmp.add(), &dni = tmp.add(), &dno = tmp.add();
     const size_t es = in_dtype == WM_I16 ? 2 : 4, nin = (size_t)B * stride_in, nout = (size_t)B * stride_out;
     auto run = [&]() -> int {
@@ -3860,14 +3736,10 @@ extern "C" int wm_op_chunk_gather(float* out, const float* pcm, int R, int64_t T
             return fail(WM_E_ARG, "item %d = (%d, %d, %d) leaves pcm [%d][%lld] or the row of %d samples", k, t[0], t[1], t[2], R, (long long)T_max, N);
     }
     TmpDev tmp;
-    tmp.bufs.reserve(12);
     DevBuf &dp = tmp.add(), &di = tmp.add(), &dout = tmp.add();
-    WMCHK(dp.alloc((size_t)R * T_max * 4));
-    WMCHK(di.alloc((size_t)n * 3 * 4));
-    WMCHK(dout.alloc((size_t)n * N * 4));
-    HIPCHK(hipMemcpy(dp.p, pcm, (size_t)R * T_max * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(di.p, items, (size_t)n * 3 * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dout.p, out, (size_t)n * N * 4, hipMemcpyHostToDevice));  // in and out: a store the kernel misses keeps the caller's value
+    WMCHK(upload_bytes(dp, pcm, (size_t)R * T_max * 4));
+    WMCHK(upload_bytes(di, items, (size_t)n * 3 * 4));
+    WMCHK(upload_bytes(dout, out, (size_t)n * N * 4));  // in and out: a store the kernel misses keeps the caller's value
     launch_chunk_gather(dp.as<float>(), di.as<int>(), 3, 0, dout.as<float>(), n, (size_t)T_max, N, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out, dout.p, (size_t)n * N * 4, hipMemcpyDeviceToHost));
@@ -3893,15 +3765,11 @@ extern "C" int wm_op_chunk_merge(int32_t* merged, int32_t* merged_len, const int
         if (sum > cap) return fail(WM_E_ARG, "recording %d has %lld ids, cap is %d", r, (long long)sum, cap);
     }
     TmpDev tmp;
-    tmp.bufs.reserve(12);
     DevBuf &dr = tmp.add(), &doff = tmp.add(), &dm = tmp.add(), &dl = tmp.add();
-    WMCHK(dr.alloc(packed.size() * 4));
-    WMCHK(doff.alloc((size_t)(n_rec + 1) * 4));
-    WMCHK(dm.alloc((size_t)n_rec * cap * 4));
+    WMCHK(upload_bytes(dr, packed.data(), packed.size() * 4));
+    WMCHK(upload_bytes(doff, rec_off, (size_t)(n_rec + 1) * 4));
+    WMCHK(upload_bytes(dm, merged, (size_t)n_rec * cap * 4));  // in and out, as wm_op_chunk_gather
     WMCHK(dl.alloc((size_t)n_rec * 4));
-    HIPCHK(hipMemcpy(dr.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(doff.p, rec_off, (size_t)(n_rec + 1) * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dm.p, merged, (size_t)n_rec * cap * 4, hipMemcpyHostToDevice));  // in and out, as wm_op_chunk_gather
     LCHK(launch_chunk_merge(dr.as<int>(), doff.as<int>(), n_rec, stride, first_special, dm.as<int>(), dl.as<int>(), cap, nullptr));
     HIPCHK(hipMemcpy(merged, dm.p, (size_t)n_rec * cap * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(merged_len, dl.p, (size_t)n_rec * 4, hipMemcpyDeviceToHost));
@@ -3980,7 +3848,6 @@ static int chunked_impl(wm_model* m, const float* pcm, int pcm_on_device, const 
         if (m->slot_ref[s].pending) return fail(WM_E_STATE, "slot %d still holds a pass that was not waited for (chunked transcription uses slots 0..%d)", s, NS - 1);
     hipStream_t st = m->stream;
     TmpDev tmp;
-    tmp.bufs.reserve(20);
     DevBuf &d_pcm = tmp.add(), &d_tab = tmp.add(), &d_off = tmp.add(), &d_packed = tmp.add(), &d_merged = tmp.add(), &d_len = tmp.add();
     DevBuf &d_times = tmp.add(), &d_nseg = tmp.add(), &d_segt = tmp.add(), &d_segr = tmp.add(), &d_pairs = tmp.add();
     if (ts.mode) {
@@ -4150,29 +4017,20 @@ extern "C" int wm_op_chunk_segments(const int32_t* ids, const int32_t* lens, con
         if (sum > cap) return fail(WM_E_SIZE, "recording %d has %lld ids, cap is %d", r, (long long)sum, cap);
     }
     TmpDev tmp;
-    tmp.bufs.reserve(12);
     DevBuf &dr = tmp.add(), &doff = tmp.add(), &dtab = tmp.add(), &dtt = tmp.add(), &dm = tmp.add(), &dl = tmp.add(), &dn = tmp.add(), &dst = tmp.add(),
            &dsr = tmp.add(), &dp = tmp.add();
     const size_t nm = (size_t)n_rec * cap, ns = (size_t)n_rec * seg_cap * 2;
-    WMCHK(dr.alloc(packed.size() * 4));
-    WMCHK(doff.alloc((size_t)(n_rec + 1) * 4));
-    WMCHK(dtab.alloc((size_t)n_rows * 3 * 4));
-    WMCHK(dm.alloc(nm * 4));
+    WMCHK(upload_bytes(dr, packed.data(), packed.size() * 4));
+    WMCHK(upload_bytes(doff, rec_off, (size_t)(n_rec + 1) * 4));
+    WMCHK(upload_bytes(dtab, strides, (size_t)n_rows * 3 * 4));
+    WMCHK(upload_bytes(dm, merged, nm * 4));
     WMCHK(dl.alloc((size_t)n_rec * 4));
     WMCHK(dn.alloc((size_t)n_rec * 4));
-    WMCHK(dst.alloc(ns * 8));
-    WMCHK(dsr.alloc(ns * 4));
-    HIPCHK(hipMemcpy(dr.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(doff.p, rec_off, (size_t)(n_rec + 1) * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dtab.p, strides, (size_t)n_rows * 3 * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dm.p, merged, nm * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dst.p, seg_times, ns * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dsr.p, seg_range, ns * 4, hipMemcpyHostToDevice));
+    WMCHK(upload_bytes(dst, seg_times, ns * 8));
+    WMCHK(upload_bytes(dsr, seg_range, ns * 4));
     if (times) {
-        WMCHK(dtt.alloc((size_t)n_rows * stride * 4));
-        WMCHK(dp.alloc(nm * 2 * 8));
-        HIPCHK(hipMemcpy(dtt.p, times, (size_t)n_rows * stride * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dp.p, pairs, nm * 2 * 8, hipMemcpyHostToDevice));
+        WMCHK(upload_bytes(dtt, times, (size_t)n_rows * stride * 4));
+        WMCHK(upload_bytes(dp, pairs, nm * 2 * 8));
     }
     ChunkSegArgs a{};
     a.rows = dr.as<int>(), a.rec_off = doff.as<int>(), a.tab = dtab.as<int>(), a.times = times ? dtt.as<float>() : nullptr;
@@ -4513,29 +4371,25 @@ extern "C" int wm_align_phases(wm_model* m, int slot, float* ms) {
 extern "C" int wm_op_score_logits(float* logprob, int32_t* top_id, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                                   const int32_t* target, int M, int N, int K, int dtype) {
     if (!logprob || !top_id || !x || !ln_g || !ln_b || !emb || !target || M <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
-    if (K != 128 && K != 384 && K != 512 && K != 768 && K != 1024) return fail(WM_E_ARG, "K must be 128, 384, 512, 768 or 1024 (the logits kernels' d_model)");
+    WMCHK(vocab_k_check(K));
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
     for (int r = 0; r < M; ++r)
         if (target[r] >= N) return fail(WM_E_ARG, "target[%d] = %d is not a vocabulary id", r, target[r]);
     TmpDev t;
-    t.bufs.reserve(16);
     const size_t parts = score_parts(N, dtype);
-    DevBuf &dx = t.add(), &g = t.add(), &be = t.add(), &w = t.add(), &a = t.add(), &pm = t.add(), &ps = t.add(), &pi = t.add(), &zt = t.add(),
-           &tg = t.add(), &lp = t.add(), &top = t.add();
-    WMCHK(upload(dx, x, (size_t)M * K, WM_F32));
-    WMCHK(upload(g, ln_g, K, WM_F32));
-    WMCHK(upload(be, ln_b, K, WM_F32));
-    WMCHK(upload(w, emb, (size_t)N * K, dtype));
+    const float* dx;
+    VocabHead vh;
+    WMCHK(upload_vocab_head(t, x, ln_g, ln_b, emb, M, N, K, dtype, &dx, &vh));
+    DevBuf &a = t.add(), &pm = t.add(), &ps = t.add(), &pi = t.add(), &zt = t.add(), &tg = t.add(), &lp = t.add(), &top = t.add();
     WMCHK(a.alloc(score_operand_bytes(M, K, dtype)));
     for (DevBuf* p : {&pm, &ps, &pi}) WMCHK(p->alloc((size_t)M * parts * 4, true));
     for (DevBuf* p : {&zt, &lp, &top}) WMCHK(p->alloc((size_t)M * 4, true));
-    WMCHK(tg.alloc((size_t)M * 4));
-    HIPCHK(hipMemcpy(tg.p, target, (size_t)M * 4, hipMemcpyHostToDevice));
+    WMCHK(upload_bytes(tg, target, (size_t)M * 4));
     ScoreParams q{};
-    q.x = dx.as<float>();
-    q.ln_g = g.as<float>();
-    q.ln_b = be.as<float>();
-    q.emb = w.p;
+    q.x = dx;
+    q.ln_g = vh.ln_g;
+    q.ln_b = vh.ln_b;
+    q.emb = vh.emb;
     q.a = a.p;
     q.target = tg.as<int>();
     q.M = M;
@@ -5421,1198 +5275,5 @@ extern "C" int wm_bench_kernel(wm_model* m, wm_state* s, int which, int reps, fl
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     *avg_us = ms * 1000.0f / (float)reps;
-    return 0;
-}
-
-// ---- op-level entry points (whisper_tensor.mojo) --------------------------------------------------------------------------
-
-extern "C" int wm_op_matmul_nt(float* C, const float* A, const float* Bm, const float* bias, int M, int N, int K, int dtype) {
-    if (!C || !A || !Bm || M <= 0 || N <= 0 || K <= 0) return fail(WM_E_ARG, "bad argument");
-    if (K % 32) return fail(WM_E_ARG, "K must be a multiple of 32");
-    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
-    TmpDev t;
-    t.bufs.reserve(8);
-    hipStream_t st = nullptr;
-    if (N % 128 == 0) {  // dense path: the encoder GEMM kernel
-        const size_t Mp = ((size_t)M + 127) / 128 * 128;
-        std::vector<float> Ap(Mp * K, 0.f);
-        memcpy(Ap.data(), A, (size_t)M * K * 4);
-        DevBuf &a = t.add(), &w = t.add(), &c = t.add(), &b = t.add();
-        WMCHK(upload(a, Ap.data(), Ap.size(), dtype));
-        WMCHK(upload(w, Bm, (size_t)N * K, dtype));
-        WMCHK(c.alloc((size_t)M * N * 4));
-        if (bias) WMCHK(upload(b, bias, N, WM_F32));
-        GemmParams p{};
-        p.A = a.p;
-        p.W = w.p;
-        p.C = c.p;
-        p.M = M;
-        p.N = N;
-        p.K = K;
-        p.lda = K;
-        p.ldw = K;
-        p.ldc = N;
-        p.bias = bias ? b.as<float>() : nullptr;
-        WMCHK(gemm_dispatch(dtype, WM_F32, p, 1, st));
-        HIPCHK(hipMemcpy(C, c.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-    } else {  // skinny path: the decode-step linear kernel
-        const int Np = (N + 15) / 16 * 16;
-        // the kernel splits K over NW <= 16 waves, <= 4 k-steps of 32 each: zero-pad K to the next such size
-        auto splittable = [](int k) {
-            const int ks = k / 32;
-            for (int c = 16; c >= 1; --c)
-                if (ks % c == 0 && ks / c <= 4) return true;
-            return false;
-        };
-        int Kp = (K + 127) / 128 * 128;
-        while (Kp <= 2048 && !splittable(Kp)) Kp += 128;  // (bounded: no K above 2048 splits, and an unbounded search overflowed)
-        if (Kp > 2048) return fail(WM_E_ARG, "K too large for the skinny path (<= 2048)");
-        std::vector<float> Apad((size_t)M * Kp, 0.f), Bpad((size_t)N * Kp, 0.f);
-        for (int i = 0; i < M; ++i) memcpy(&Apad[(size_t)i * Kp], A + (size_t)i * K, (size_t)K * 4);
-        for (int i = 0; i < N; ++i) memcpy(&Bpad[(size_t)i * Kp], Bm + (size_t)i * K, (size_t)K * 4);
-        K = Kp;
-        DevBuf &a = t.add(), &w = t.add(), &c = t.add(), &b = t.add();
-        WMCHK(upload(a, Apad.data(), Apad.size(), WM_F32));
-        WMCHK(upload(w, Bpad.data(), Bpad.size(), dtype));
-        WMCHK(c.alloc((size_t)M * Np * 4));
-        if (bias) WMCHK(upload(b, bias, N, WM_F32));
-        DecLinearParams p{};
-        p.x = a.as<float>();
-        p.ldx = K;
-        p.W = w.p;
-        p.N = N;
-        p.K = K;
-        p.B = M;
-        p.bias = bias ? b.as<float>() : nullptr;
-        p.out = c.as<float>();
-        p.ldo = Np;
-        WMCHK(dec_linear_dispatch(dtype, p, st));
-        HIPCHK(hipMemcpy2D(C, (size_t)N * 4, c.p, (size_t)Np * 4, (size_t)N * 4, M, hipMemcpyDeviceToHost));
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// C = layer_norm(A, ln_g, ln_b) · Bᵀ (+ bias): the LN -> projection pair of ResidualAttentionBlock.forward (layers.mojo:449-455,
-// 489-497) on the encoder's kernels.  require_fused != 0 demands the ONE-kernel form (LayerNorm applied while the row-panel GEMM
-// loads its fp32 A rows): a shape that kernel does not take is refused by the launcher — WM_E_ARG, nothing launched, C untouched.
-extern "C" int wm_op_ln_matmul_nt(float* C, const float* A, const float* ln_g, const float* ln_b, const float* Bm, const float* bias,
-                                  int M, int N, int K, int dtype, int require_fused) {
-    if (!C || !A || !ln_g || !ln_b || !Bm || M <= 0 || N <= 0 || K <= 0) return fail(WM_E_ARG, "bad argument");
-    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
-    if (K % 128 || K > 1024) return fail(WM_E_ARG, "K must be a multiple of 128 and <= 1024 (layer_norm rows)");
-    TmpDev t;
-    t.bufs.reserve(8);
-    hipStream_t st = nullptr;
-    const size_t Mp = ((size_t)M + 127) / 128 * 128;
-    std::vector<float> Ap(Mp * K, 0.f);
-    memcpy(Ap.data(), A, (size_t)M * K * 4);
-    DevBuf &x = t.add(), &xn = t.add(), &w = t.add(), &c = t.add(), &b = t.add(), &g = t.add(), &be = t.add();
-    WMCHK(upload(x, Ap.data(), Ap.size(), WM_F32));
-    WMCHK(xn.alloc(Mp * K * dt_size(dtype), true));
-    WMCHK(upload(w, Bm, (size_t)N * K, dtype));
-    WMCHK(c.alloc((size_t)M * N * 4));
-    WMCHK(upload(g, ln_g, K, WM_F32));
-    WMCHK(upload(be, ln_b, K, WM_F32));
-    if (bias) WMCHK(upload(b, bias, N, WM_F32));
-    GemmParams p{};
-    p.A = xn.p;
-    p.W = w.p;
-    p.C = c.p;
-    p.M = M;
-    p.N = N;
-    p.K = K;
-    p.lda = K;
-    p.ldw = K;
-    p.ldc = N;
-    p.bias = bias ? b.as<float>() : nullptr;
-    if (require_fused) {  // handed to the launcher as asked: it either fuses or refuses
-        p.A = x.p;
-        p.ln_g = g.as<float>();
-        p.ln_b = be.as<float>();
-        WMCHK(gemm_dispatch(dtype, WM_F32, p, 1, st));
-    } else {
-        WMCHK(ln_then_gemm(dtype, WM_F32, p, x.as<float>(), g.as<float>(), be.as<float>(), st));
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(C, c.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int wm_op_layer_norm(float* out, const float* inp, const float* gamma, const float* beta, int rows, int cols, float eps) {
-    if (!out || !inp || !gamma || !beta || rows <= 0 || cols <= 0) return fail(WM_E_ARG, "bad argument");
-    if (cols % 128 || cols > 1024) return fail(WM_E_ARG, "cols must be a multiple of 128 and <= 1024");
-    TmpDev t;
-    t.bufs.reserve(8);
-    DevBuf &x = t.add(), &g = t.add(), &b = t.add(), &o = t.add();
-    WMCHK(upload(x, inp, (size_t)rows * cols, WM_F32));
-    WMCHK(upload(g, gamma, cols, WM_F32));
-    WMCHK(upload(b, beta, cols, WM_F32));
-    WMCHK(o.alloc((size_t)rows * cols * 4));
-    launch_layernorm_rows<float>(x.as<float>(), g.as<float>(), b.as<float>(), nullptr, o.as<float>(), rows, cols, eps, nullptr);
-    HIPCHK(hipMemcpy(out, o.p, (size_t)rows * cols * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-static void widen_to_f32(const void* src, int dtype, size_t n, float* dst);
-// launch_layernorm_rows<T> with the operand-dtype store (out_t, returned widened), the fp32 store (out_f), or both — the launches the
-// base / small encoder makes before every projection.  out_t / out_f hold rows + 1 rows, in and out: the device buffers start from the
-// caller's values, so the guard row (and anything else the kernel did not write) comes back as it went in.  Known-answer tests.
-extern "C" int wm_op_layer_norm_t(float* out_t, float* out_f, const float* inp, const float* gamma, const float* beta, int rows, int cols,
-                                  float eps, int dtype) {
-    if ((!out_t && !out_f) || !inp || !gamma || !beta || rows <= 0 || cols <= 0) return fail(WM_E_ARG, "bad argument");
-    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
-    if (cols % 128 || cols > 1024) return fail(WM_E_ARG, "cols must be a multiple of 128 and <= 1024");
-    const size_t n = (size_t)rows * cols, ng = n + cols;
-    TmpDev t;
-    t.bufs.reserve(8);
-    DevBuf &x = t.add(), &g = t.add(), &b = t.add(), &ot = t.add(), &of = t.add();
-    WMCHK(upload(x, inp, n, WM_F32));
-    WMCHK(upload(g, gamma, cols, WM_F32));
-    WMCHK(upload(b, beta, cols, WM_F32));
-    if (out_t) WMCHK(upload(ot, out_t, ng, dtype));
-    if (out_f) WMCHK(upload(of, out_f, ng, WM_F32));
-    DISPATCH_DT(dtype, TT, launch_layernorm_rows<TT>(x.as<float>(), g.as<float>(), b.as<float>(), out_t ? ot.p : nullptr,
-                                                     out_f ? of.as<float>() : nullptr, rows, cols, eps, nullptr));
-    HIPCHK(hipGetLastError());
-    if (out_t) {
-        std::vector<unsigned char> h(ng * dt_size(dtype));
-        HIPCHK(hipMemcpy(h.data(), ot.p, h.size(), hipMemcpyDeviceToHost));
-        widen_to_f32(h.data(), dtype, ng, out_t);
-    }
-    if (out_f) HIPCHK(hipMemcpy(out_f, of.p, ng * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// One gemm_dispatch call with everything GemmParams offers the two tiled kernels (include/whisper_mi.h).  Device sizes: both kernels
-// read whole 128-row panels of A whatever M is, so A is allocated zero-filled up to the last panel row; bias, pos, residual and C are
-// touched at valid rows only (gemm_epilogue's valid[]), and the checks below hold every offset the epilogue can form inside the
-// caller's lengths, which are also the device lengths.
-extern "C" int wm_op_gemm_nt_epi(float* C, size_t c_len, const float* A, size_t a_len, const float* W, const float* bias, const float* pos,
-                                 const float* residual, size_t r_len, int M, int N, int K, int batch, long long lda, long long strideA,
-                                 long long ldc, long long strideC, long long ldr, long long strideR, int residual_in_place, int act,
-                                 int gelu_mode, int group_n, long long group_stride, int dtype, int out_dtype, int* kernel_ran) {
-    if (!C || !A || !W || !kernel_ran || M <= 0 || N <= 0 || K <= 0 || batch <= 0) return fail(WM_E_ARG, "bad argument");
-    if (M > (1 << 20) || N > (1 << 16) || K > (1 << 16) || batch > 1024) return fail(WM_E_ARG, "problem too large for the op hook");
-    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
-    if (out_dtype != WM_F32 && out_dtype != dtype) return fail(WM_E_ARG, "out_dtype must be WM_F32 or dtype");
-    if (N % 128 || K % 32) return fail(WM_E_ARG, "N must be a multiple of 128 and K of 32");
-    if ((act != 0 && act != 1) || (gelu_mode != 0 && gelu_mode != 1)) return fail(WM_E_ARG, "bad act / gelu_mode");
-    const long long LIM = 1ll << 40;  // keeps every product below int64
-    auto ld_ok = [&](long long v, int unit, bool zero_ok) { return (v > 0 || (zero_ok && v == 0)) && v < LIM && v % unit == 0; };
-    // 16-byte operand loads: 8 sixteen-bit or 4 fp32 elements (8 serves both); 16-byte fp32 / 8-byte 16-bit stores and addend loads: 4
-    if (!ld_ok(lda, 8, false) || !ld_ok(strideA, 8, true) || !ld_ok(ldc, 4, false) || !ld_ok(strideC, 4, true))
-        return fail(WM_E_ARG, "lda / strideA must be multiples of 8, ldc / strideC of 4");
-    if (batch > 1 && (strideA == 0 || strideC == 0)) return fail(WM_E_ARG, "batch > 1 needs strideA and strideC");
-    if (group_n < 0 || group_n % 64 || (group_n > 0 && (N % group_n || !ld_ok(group_stride, 4, false))))
-        return fail(WM_E_ARG, "group_n must be a multiple of 64 that divides N, with a group_stride that is a multiple of 4");
-    const int n_grp = group_n > 0 ? N / group_n : 1, row_w = group_n > 0 ? group_n : N;
-    if (ldc < row_w) return fail(WM_E_ARG, "ldc below the row width");
-    if (residual_in_place) {
-        if (out_dtype != WM_F32) return fail(WM_E_ARG, "residual_in_place needs fp32 output");
-        if (residual || group_n > 0) return fail(WM_E_ARG, "residual_in_place takes no separate residual and no column groups");
-        ldr = ldc;
-        strideR = strideC;
-    } else if (residual) {
-        if (!ld_ok(ldr, 4, false) || !ld_ok(strideR, 4, true) || ldr < N || (batch > 1 && strideR == 0))
-            return fail(WM_E_ARG, "ldr must be a multiple of 4 and >= N, strideR a multiple of 4");
-    }
-    const size_t Mp = ((size_t)M + 127) / 128 * 128;
-    const size_t a_need = (size_t)(batch - 1) * strideA + (size_t)(M - 1) * lda + K;
-    const size_t a_dev = (size_t)(batch - 1) * strideA + (Mp - 1) * (size_t)lda + K;
-    const size_t c_need = (size_t)(batch - 1) * strideC + (size_t)(n_grp - 1) * (group_n > 0 ? group_stride : 0) + (size_t)(M - 1) * ldc + row_w;
-    const size_t r_need = (size_t)(batch - 1) * strideR + (size_t)(M - 1) * ldr + N;
-    if (a_len < a_need || c_len < c_need || (residual && r_len < r_need)) return fail(WM_E_ARG, "a size overflows the caller's arrays");
-    if (a_len > ((size_t)1 << 31) || c_len > ((size_t)1 << 31) || r_len > ((size_t)1 << 31)) return fail(WM_E_ARG, "array too large for the op hook");
-    TmpDev t;
-    t.bufs.reserve(8);
-    DevBuf &a = t.add(), &w = t.add(), &c = t.add(), &b = t.add(), &ps = t.add(), &r = t.add();
-    GemmParams p{};
-    p.M = M;
-    p.N = N;
-    p.K = K;
-    p.lda = (long)lda;
-    p.ldw = K;
-    p.ldc = (long)ldc;
-    p.strideA = (long)strideA;
-    p.strideC = (long)strideC;
-    p.ldr = (long)ldr;
-    p.strideR = (long)strideR;
-    p.act = act;
-    p.gelu_mode = gelu_mode;
-    p.group_n = group_n;
-    p.group_stride = group_n > 0 ? (long)group_stride : 0;
-    // addend pointers decide the dispatch (the row-panel kernel takes none): non-null placeholders until the uploads below
-    p.bias = bias;
-    p.pos = pos;
-    p.residual = residual_in_place ? C : residual;
-    *kernel_ran = gemm_nt_kernel_for((int)dt_size(dtype), (int)dt_size(out_dtype), p, batch, nullptr);
-    // the device sizes above are worked out for the two tiled kernels only; the ring kernels have hooks of their own
-    if (*kernel_ran != wm::GEMM_NT_DIRECT && *kernel_ran != wm::GEMM_NT_LDS)
-        return fail(WM_E_ARG, "this shape dispatches to the row-panel / full-row kernel (wm_op_matmul_nt, wm_op_ln_matmul_nt, wm_op_mlp_block)");
-    {  // A: the caller's part, then zeros up to the end of the last 128-row panel
-        std::vector<float> Ap(std::max(a_dev, a_need), 0.f);
-        memcpy(Ap.data(), A, a_need * 4);
-        WMCHK(upload(a, Ap.data(), Ap.size(), dtype));
-    }
-    WMCHK(upload(w, W, (size_t)N * K, dtype));
-    WMCHK(upload(c, C, c_len, out_dtype));
-    if (bias) WMCHK(upload(b, bias, N, WM_F32));
-    if (pos) WMCHK(upload(ps, pos, (size_t)M * N, WM_F32));
-    if (residual && !residual_in_place) WMCHK(upload(r, residual, r_len, WM_F32));
-    p.A = a.p;
-    p.W = w.p;
-    p.C = c.p;
-    p.bias = bias ? b.as<float>() : nullptr;
-    p.pos = pos ? ps.as<float>() : nullptr;
-    p.residual = residual_in_place ? c.as<float>() : residual ? r.as<float>() : nullptr;
-    WMCHK(gemm_dispatch(dtype, out_dtype, p, batch, nullptr));
-    HIPCHK(hipGetLastError());
-    std::vector<unsigned char> h(c_len * dt_size(out_dtype));
-    HIPCHK(hipMemcpy(h.data(), c.p, h.size(), hipMemcpyDeviceToHost));
-    widen_to_f32(h.data(), out_dtype, c_len, C);
-    return 0;
-}
-
-extern "C" int wm_op_mlp_block(float* x, const float* ln_g, const float* ln_b, const float* fc1_w, const float* fc1_b, const float* fc2_w,
-                               const float* fc2_b, const float* next_g, const float* next_b, float* xn_out, int M, int d, int ffn,
-                               int dtype, int gelu_mode) {
-    if (!x || !ln_g || !ln_b || !fc1_w || !fc1_b || !fc2_w || !fc2_b || M <= 0) return fail(WM_E_ARG, "bad argument");
-    if (d <= 0 || d % 128 || d > 1024 || ffn <= 0 || ffn % 128) return fail(WM_E_ARG, "d and ffn must be multiples of 128 (d <= 1024)");
-    if (dtype < 0 || dtype > 2 || (gelu_mode != 0 && gelu_mode != 1)) return fail(WM_E_ARG, "bad dtype / gelu_mode");
-    const bool want_next = next_g && next_b && xn_out;
-    if (!want_next && (next_g || next_b || xn_out)) return fail(WM_E_ARG, "next_g, next_b and xn_out go together");
-    TmpDev t;
-    t.bufs.reserve(16);
-    hipStream_t st = nullptr;
-    const size_t Mp = ((size_t)M + 127) / 128 * 128, ts = dt_size(dtype);  // the tile kernels read whole 128-row panels
-    DevBuf &dx = t.add(), &xn = t.add(), &hid = t.add(), &g1 = t.add(), &b1 = t.add(), &w1 = t.add(), &bb1 = t.add(), &w2 = t.add(),
-           &bb2 = t.add(), &g2 = t.add(), &b2 = t.add();
-    std::vector<float> xp(Mp * d, 0.f);
-    memcpy(xp.data(), x, (size_t)M * d * 4);
-    WMCHK(upload(dx, xp.data(), xp.size(), WM_F32));
-    WMCHK(xn.alloc(Mp * d * ts, true));
-    WMCHK(hid.alloc(Mp * ffn * ts, true));
-    WMCHK(upload(g1, ln_g, d, WM_F32));
-    WMCHK(upload(b1, ln_b, d, WM_F32));
-    WMCHK(upload(w1, fc1_w, (size_t)ffn * d, dtype));
-    WMCHK(upload(bb1, fc1_b, ffn, WM_F32));
-    WMCHK(upload(w2, fc2_w, (size_t)d * ffn, dtype));
-    WMCHK(upload(bb2, fc2_b, d, WM_F32));
-    if (want_next) {
-        WMCHK(upload(g2, next_g, d, WM_F32));
-        WMCHK(upload(b2, next_b, d, WM_F32));
-    }
-    GemmParams f1{};
-    f1.A = xn.p;
-    f1.W = w1.p;
-    f1.C = hid.p;
-    f1.M = M;
-    f1.N = ffn;
-    f1.K = d;
-    f1.lda = d;
-    f1.ldw = d;
-    f1.ldc = ffn;
-    f1.bias = bb1.as<float>();
-    f1.act = 1;
-    f1.gelu_mode = gelu_mode;
-    WMCHK(ln_then_gemm(dtype, dtype, f1, dx.as<float>(), g1.as<float>(), b1.as<float>(), st));
-    GemmParams f2{};
-    f2.A = hid.p;
-    f2.W = w2.p;
-    f2.C = dx.p;
-    f2.M = M;
-    f2.N = d;
-    f2.K = ffn;
-    f2.lda = ffn;
-    f2.ldw = ffn;
-    f2.ldc = d;
-    f2.bias = bb2.as<float>();
-    f2.residual = dx.as<float>();
-    f2.ldr = d;
-    bool fused_next = false;
-    if (want_next && gemm_nt_fuses_layernorm_out(dtype == WM_F32 ? 4 : 2, f2)) {
-        f2.lno_g = g2.as<float>();
-        f2.lno_b = b2.as<float>();
-        f2.lno_out = xn.p;
-        fused_next = true;
-    }
-    WMCHK(gemm_dispatch(dtype, WM_F32, f2, 1, st));
-    if (want_next && !fused_next)
-        DISPATCH_DT(dtype, TT, launch_layernorm_rows<TT>(dx.as<float>(), g2.as<float>(), b2.as<float>(), xn.p, nullptr, M, d, 1e-5f, st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(x, dx.p, (size_t)M * d * 4, hipMemcpyDeviceToHost));
-    if (want_next) {  // the operand rows as the next GEMM reads them, widened on the host
-        const size_t n = (size_t)M * d;
-        std::vector<unsigned char> h(n * ts);
-        HIPCHK(hipMemcpy(h.data(), xn.p, h.size(), hipMemcpyDeviceToHost));
-        widen_to_f32(h.data(), dtype, n, xn_out);
-    }
-    return 0;
-}
-
-// widen n operand-dtype values on the host (known-answer entry points only)
-static void widen_to_f32(const void* src, int dtype, size_t n, float* dst) {
-    if (dtype == WM_F32) {
-        memcpy(dst, src, n * 4);
-        return;
-    }
-    const uint16_t* h = static_cast<const uint16_t*>(src);
-    for (size_t i = 0; i < n; ++i) {
-        if (dtype == WM_BF16) {
-            const uint32_t u = (uint32_t)h[i] << 16;
-            memcpy(&dst[i], &u, 4);
-        } else {
-            _Float16 hv;
-            memcpy(&hv, &h[i], 2);
-            dst[i] = (float)hv;
-        }
-    }
-}
-
-extern "C" int wm_op_attention_batch(float* out, const float* q, const float* k, const float* v, int B, int n_ctx, int n_heads, int dtype) {
-    if (!out || !q || !k || !v || B <= 0 || n_ctx <= 0 || n_heads <= 0 || n_heads > 64) return fail(WM_E_ARG, "bad argument");
-    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
-    const size_t d = (size_t)n_heads * 64, rows = (size_t)B * n_ctx, n = rows * d;
-    std::vector<float> packed(3 * n);  // the fused projection layout the kernel reads: row = [q | k | v], utterances back to back
-    for (size_t t = 0; t < rows; ++t) {
-        memcpy(&packed[t * 3 * d], q + t * d, d * 4);
-        memcpy(&packed[t * 3 * d + d], k + t * d, d * 4);
-        memcpy(&packed[t * 3 * d + 2 * d], v + t * d, d * 4);
-    }
-    TmpDev t;
-    t.bufs.reserve(4);
-    DevBuf &qkv = t.add(), &o = t.add();
-    WMCHK(upload(qkv, packed.data(), packed.size(), dtype));
-    WMCHK(o.alloc(n * dt_size(dtype), true));
-    DISPATCH_DT(dtype, TT, launch_flash_attn_enc<TT>(qkv.p, o.p, B, n_heads, n_ctx, 0.125f, nullptr));
-    HIPCHK(hipGetLastError());
-    std::vector<unsigned char> h(n * dt_size(dtype));
-    HIPCHK(hipMemcpy(h.data(), o.p, h.size(), hipMemcpyDeviceToHost));
-    widen_to_f32(h.data(), dtype, n, out);
-    return 0;
-}
-extern "C" int wm_op_attention(float* out, const float* q, const float* k, const float* v, int n_ctx, int n_heads, int dtype) {
-    return wm_op_attention_batch(out, q, k, v, 1, n_ctx, n_heads, dtype);
-}
-
-static int op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
-                               int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo, bool with_lo);
-extern "C" int wm_op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
-                                      int n_chunks, int out_dtype, int q_B, int len, int nq) {
-    return op_attention_cached(out, q, k, v, B, t, n_heads, kv_dtype, n_chunks, out_dtype, q_B, len, nq, nullptr, false);
-}
-extern "C" int wm_op_attention_cached_lo(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
-                                         int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo) {
-    return op_attention_cached(out, q, k, v, B, t, n_heads, kv_dtype, n_chunks, out_dtype, q_B, len, nq, key_lo, true);
-}
-static int op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
-                               int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo, bool with_lo) {
-    if (with_lo && (!key_lo || n_chunks != 1 || nq != 0)) return fail(WM_E_ARG, "key_lo belongs to the single-workgroup forms (n_chunks = 1, nq = 0)");
-    if (!out || !q || !k || !v || B <= 0 || t <= 0 || n_heads <= 0 || n_heads > 16) return fail(WM_E_ARG, "bad argument");
-    if (kv_dtype < 0 || kv_dtype > 2 || out_dtype < 0 || out_dtype > 2) return fail(WM_E_ARG, "bad dtype");
-    if (n_chunks < 1 || (n_chunks > 1 && (n_chunks < (t + 511) / 512 || n_chunks > (t + 31) / 32)))
-        return fail(WM_E_ARG, "n_chunks must be 1, or between ceil(t/512) and ceil(t/32)");
-    if (n_chunks == 1 && t > 512) return fail(WM_E_ARG, "the single-workgroup form serves up to 512 keys (the text context)");
-    if (n_chunks > 64) return fail(WM_E_ARG, "the merge takes up to 64 chunks");
-    if (q_B < 0 || (q_B > 0 && B % q_B)) return fail(WM_E_ARG, "prefill rows are position-major: B must be P * q_B");
-    if (nq != 0 && (nq != 4 || n_chunks == 1 || q_B == 0 || B != 4 * q_B))
-        return fail(WM_E_ARG, "nq must be 0, or 4 with the chunked form and B = 4 * q_B rows");
-    const int P = q_B > 0 ? B / q_B : 1, n_utt = q_B > 0 ? q_B : B;  // k, v hold n_utt utterances of t rows
-    if (n_chunks > 1 && len >= 0) return fail(WM_E_ARG, "len belongs to the single-workgroup form (the chunked form sweeps all t rows)");
-    if (n_chunks == 1 && len < 0 && P > 1) return fail(WM_E_ARG, "the causal prefill form needs len >= 0");
-    if (n_chunks == 1 && len >= 0 && len + P > t) return fail(WM_E_ARG, "the cache must hold len + P rows");
-    const size_t d = (size_t)n_heads * 64, n = (size_t)B * d;
-    TmpDev tmp;
-    tmp.bufs.reserve(8);
-    DevBuf &dq = tmp.add(), &dk = tmp.add(), &dv = tmp.add(), &po = tmp.add(), &pml = tmp.add(), &o = tmp.add(), &ctl = tmp.add(), &dlo = tmp.add();
-    if (with_lo) {
-        for (int u = 0; u < n_utt; ++u)
-            if (key_lo[u] < 0 || key_lo[u] > t) return fail(WM_E_ARG, "key_lo[%d] = %d outside [0, %d]", u, key_lo[u], t);
-        WMCHK(dlo.alloc((size_t)n_utt * 4));
-        HIPCHK(hipMemcpy(dlo.p, key_lo, (size_t)n_utt * 4, hipMemcpyHostToDevice));
-    }
-    WMCHK(upload(dq, q, n, WM_F32));
-    WMCHK(upload(dk, k, (size_t)n_utt * t * d, kv_dtype));
-    WMCHK(upload(dv, v, (size_t)n_utt * t * d, kv_dtype));
-    WMCHK(o.alloc(n * dt_size(out_dtype), true));
-    AttnDecParams a{};
-    a.q = dq.as<float>();
-    a.K = dk.p;
-    a.V = dv.p;
-    a.batch_stride = (long)((size_t)t * d);
-    a.scale = 0.125f;
-    a.H = n_heads;
-    a.d = (int)d;
-    a.B = B;
-    a.q_B = q_B;
-    a.nq = nq;
-    if (n_chunks > 1) {
-        WMCHK(po.alloc((size_t)B * n_chunks * d * 4, true));
-        WMCHK(pml.alloc((size_t)B * n_chunks * n_heads * 2 * 4, true));
-        a.n_keys = t;
-        a.nsplit = n_chunks;
-        a.part_o = po.as<float>();
-        a.part_ml = pml.as<float>();
-        WMCHK(attn_decode_dispatch(kv_dtype, a, nullptr));
-        launch_attn_combine(po.as<float>(), pml.as<float>(), o.p, out_dtype, B, n_chunks, n_heads, (int)d, nullptr);
-    } else {
-        StepCtl h{};
-        // the kernel sweeps len + 1 rows (position p of a prefill: len + 1 + p): the cache as it stands after this step's row was appended
-        h.len = len >= 0 ? len : t - 1;
-        WMCHK(ctl.alloc(sizeof(StepCtl)));
-        HIPCHK(hipMemcpy(ctl.p, &h, sizeof h, hipMemcpyHostToDevice));
-        a.n_keys = -1;
-        a.ctl = ctl.as<StepCtl>();
-        a.nsplit = 1;
-        a.direct_out = o.as<float>();
-        a.out_dtype = out_dtype;
-        WMCHK(attn_decode_dispatch(kv_dtype, a, nullptr, with_lo ? dlo.as<int>() : nullptr));
-    }
-    HIPCHK(hipGetLastError());
-    std::vector<unsigned char> h(n * dt_size(out_dtype));
-    HIPCHK(hipMemcpy(h.data(), o.p, h.size(), hipMemcpyDeviceToHost));
-    widen_to_f32(h.data(), out_dtype, n, out);
-    return 0;
-}
-
-// One launch_dec_linear as decode_core wires it: LN1 -> QKV with the cache append, the XT out-projections with the residual in place,
-// LNx -> cross q with the alignment-head capture, LN2 -> fc1 + GELU stored in operand dtype, fc2.
-// cap_map non-null: the capture by row map, cap is [cap_dst][cap_nsel][64] and len / cap_step0 / cap_steps are not used
-static int op_dec_linear(float* out, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
-                         const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
-                         float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
-                         const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel, const int32_t* cap_map = nullptr, int cap_dst = 0,
-                         bool k_long = false) {
-    if (!out || !x || !W || B <= 0 || N <= 0 || K <= 0) return fail(WM_E_ARG, "bad argument");
-    if (dtype < 0 || dtype > 2 || (gelu_mode != 0 && gelu_mode != 1)) return fail(WM_E_ARG, "bad dtype / gelu_mode");
-    if (k_long) {  // wm_op_dec_linear_long: the K-long form alone (16 waves walking groups of k-steps), which has no LayerNorm prologue
-        if (!dec_linear_long_supports_k(K)) return fail(WM_E_ARG, "K must be 3072 or 4096 (the K-long form of the skinny linear)");
-        if (ln_g || ln_b) return fail(WM_E_ARG, "the K-long form has no LayerNorm prologue");
-    } else if (!dec_linear_supports_k(K)) return fail(WM_E_ARG, "K must be a multiple of 32 whose k-steps split over <= 16 waves x <= 4 steps (K <= 2048), or 3072");
-    if (!ln_g != !ln_b) return fail(WM_E_ARG, "ln_g and ln_b go together");
-    if (ln_g && x_is_t) return fail(WM_E_ARG, "the LayerNorm prologue reads fp32 rows (no x_is_t)");
-    if (!kcache != !vcache) return fail(WM_E_ARG, "kcache and vcache go together");
-    if (out_is_t && (residual || kcache)) return fail(WM_E_ARG, "out_is_t is the plain store (no residual, no cache append)");
-    const int d = N / 3;
-    if (kcache) {
-        if (N % 3 || d % 64 || kv_dtype < 0 || kv_dtype > 2 || n_utt <= 0 || cap_rows <= 0 || len < 0)
-            return fail(WM_E_ARG, "QKV mode needs N = 3 * d_model (d_model % 64 == 0), a kv_dtype and a cache [n_utt][cap_rows][d_model]");
-        if (residual) return fail(WM_E_ARG, "QKV mode has no residual");
-        if (kv_B < 0 || (kv_B > 0 ? (kv_B > n_utt || B % kv_B || len + B / kv_B > cap_rows) : (B > n_utt || len + 1 > cap_rows)))
-            return fail(WM_E_ARG, "rows must be P * kv_B with kv_B <= n_utt and len + P <= cap_rows, or <= n_utt with len < cap_rows");
-    }
-    if (cap && cap_map) {
-        if (!cap_sel || cap_dst <= 0 || cap_nsel <= 0 || cap_nsel > 32 || N % 64 || N > 2048 || kcache)
-            return fail(WM_E_ARG, "capture by row map needs cap_sel, cap_dst > 0, N = 64 * heads <= 2048, 1 <= cap_nsel <= 32 (and no cache)");
-        for (int h = 0; h < 32; ++h)
-            if (cap_sel[h] >= cap_nsel || (cap_sel[h] >= 0 && h >= N / 64)) return fail(WM_E_ARG, "cap_sel names a slot >= cap_nsel or a head >= N / 64");
-        for (int r = 0; r < B; ++r)
-            if (cap_map[r] < -1 || cap_map[r] >= cap_dst) return fail(WM_E_ARG, "cap_map[%d] = %d outside [-1, cap_dst = %d)", r, cap_map[r], cap_dst);
-    } else if (cap) {
-        if (!cap_sel || len < 0 || cap_steps <= 0 || cap_nsel <= 0 || cap_nsel > 32 || N % 64 || N > 2048 || (kcache && cap))
-            return fail(WM_E_ARG, "capture needs cap_sel, len >= 0, N = 64 * heads <= 2048, 1 <= cap_nsel <= 32, cap_steps > 0 (and no cache)");
-        for (int h = 0; h < 32; ++h)
-            if (cap_sel[h] >= cap_nsel || (cap_sel[h] >= 0 && h >= N / 64)) return fail(WM_E_ARG, "cap_sel names a slot >= cap_nsel or a head >= N / 64");
-    }
-    TmpDev t;
-    t.bufs.reserve(12);
-    hipStream_t st = nullptr;
-    // the kernel stores whole 16-column tiles (and loads the residual the same way): rows padded to 16 columns
-    const int wout = kcache ? d : N, ldo = (wout + 15) / 16 * 16;
-    const int odt = out_is_t ? dtype : WM_F32;
-    const size_t ncache = kcache ? (size_t)n_utt * cap_rows * d : 0;
-    const size_t ncap = !cap ? 0 : cap_map ? (size_t)cap_dst * cap_nsel * 64 : (size_t)B * cap_steps * cap_nsel * 64;
-    DevBuf &dx = t.add(), &w = t.add(), &b = t.add(), &g = t.add(), &be = t.add(), &o = t.add(), &r = t.add(), &kc = t.add(), &vc = t.add(),
-           &ctl = t.add(), &cp = t.add(), &cm = t.add();
-    WMCHK(upload(dx, x, (size_t)B * K, x_is_t ? dtype : WM_F32));
-    WMCHK(upload(w, W, (size_t)N * K, dtype));
-    if (bias) WMCHK(upload(b, bias, N, WM_F32));
-    if (ln_g) {
-        WMCHK(upload(g, ln_g, K, WM_F32));
-        WMCHK(upload(be, ln_b, K, WM_F32));
-    }
-    WMCHK(o.alloc((size_t)B * ldo * dt_size(odt), true));
-    const bool in_place = residual == out;
-    if (residual) {
-        DevBuf& dst = in_place ? o : r;
-        if (!in_place) WMCHK(r.alloc((size_t)B * ldo * 4, true));
-        HIPCHK(hipMemcpy2D(dst.p, (size_t)ldo * 4, residual, (size_t)N * 4, (size_t)N * 4, B, hipMemcpyHostToDevice));
-    }
-    DecLinearParams p = linear_block(dx.as<float>(), ln_g ? g.as<float>() : nullptr, ln_g ? be.as<float>() : nullptr, w.p, bias ? b.as<float>() : nullptr,
-                                     N, K, B, o.as<float>(), ldo);
-    p.x_is_t = x_is_t;
-    p.out_is_t = out_is_t;
-    p.act = act != 0;
-    p.gelu_mode = gelu_mode;
-    p.residual = residual ? (in_place ? o.as<float>() : r.as<float>()) : nullptr;
-    p.ldr = ldo;
-    if (kcache || (cap && !cap_map)) {
-        StepCtl h{};
-        h.len = len;
-        WMCHK(ctl.alloc(sizeof(StepCtl)));
-        HIPCHK(hipMemcpy(ctl.p, &h, sizeof h, hipMemcpyHostToDevice));
-        p.ctl = ctl.as<StepCtl>();
-    }
-    if (kcache) {
-        WMCHK(upload(kc, kcache, ncache, kv_dtype));
-        WMCHK(upload(vc, vcache, ncache, kv_dtype));
-        p.kcache = kc.p;
-        p.vcache = vc.p;
-        p.kv_batch_stride = (long)((size_t)cap_rows * d);
-        p.d_model = d;
-        p.kv_dtype = kv_dtype;
-        p.kv_B = kv_B;
-    }
-    if (cap) {
-        WMCHK(upload(cp, cap, ncap, WM_F32));
-        p.cap = cp.as<float>();
-        p.cap_row_stride = (long)cap_steps * cap_nsel * 64;
-        p.cap_step0 = cap_step0;
-        p.cap_steps = cap_steps;
-        p.cap_nsel = cap_nsel;
-        memcpy(p.cap_sel, cap_sel, 32);
-        if (cap_map) {
-            WMCHK(cm.alloc((size_t)B * 4));
-            HIPCHK(hipMemcpy(cm.p, cap_map, (size_t)B * 4, hipMemcpyHostToDevice));
-            p.cap_map = cm.as<int>();
-        }
-    }
-    WMCHK(dec_linear_dispatch(dtype, p, st));
-    HIPCHK(hipGetLastError());
-    {
-        const size_t es = dt_size(odt);
-        std::vector<unsigned char> h((size_t)B * wout * es);
-        HIPCHK(hipMemcpy2D(h.data(), (size_t)wout * es, o.p, (size_t)ldo * es, (size_t)wout * es, B, hipMemcpyDeviceToHost));
-        widen_to_f32(h.data(), odt, (size_t)B * wout, out);
-    }
-    if (kcache) {
-        std::vector<unsigned char> h(ncache * dt_size(kv_dtype));
-        HIPCHK(hipMemcpy(h.data(), kc.p, h.size(), hipMemcpyDeviceToHost));
-        widen_to_f32(h.data(), kv_dtype, ncache, kcache);
-        HIPCHK(hipMemcpy(h.data(), vc.p, h.size(), hipMemcpyDeviceToHost));
-        widen_to_f32(h.data(), kv_dtype, ncache, vcache);
-    }
-    if (cap) HIPCHK(hipMemcpy(cap, cp.p, ncap * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-extern "C" int wm_op_dec_linear(float* out, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
-                                const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
-                                float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
-                                const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel) {
-    return op_dec_linear(out, x, W, bias, ln_g, ln_b, residual, B, N, K, dtype, x_is_t, out_is_t, act, gelu_mode, kcache, vcache, n_utt, cap_rows,
-                         kv_dtype, kv_B, len, cap, cap_sel, cap_step0, cap_steps, cap_nsel);
-}
-// The K-long form of the same launch (fc2 of d_model 768 / 1024): K = 3072 or 4096, no LayerNorm prologue.  wm_op_dec_linear keeps
-// refusing K = 4096; K = 3072 runs the same kernel through either hook.
-extern "C" int wm_op_dec_linear_long(float* out, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
-                                     const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
-                                     float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
-                                     const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel) {
-    return op_dec_linear(out, x, W, bias, ln_g, ln_b, residual, B, N, K, dtype, x_is_t, out_is_t, act, gelu_mode, kcache, vcache, n_utt, cap_rows,
-                         kv_dtype, kv_B, len, cap, cap_sel, cap_step0, cap_steps, cap_nsel, nullptr, 0, true);
-}
-// LNx -> cross q as an align pass wires it: B input rows, cap [cap_dst][cap_nsel][64] in and out, cap_map [B] in [-1, cap_dst)
-extern "C" int wm_op_dec_linear_capmap(float* out, float* cap, const float* x, const float* W, const float* bias, const float* ln_g,
-                                       const float* ln_b, int B, int N, int K, int dtype, const int8_t* cap_sel, int cap_nsel,
-                                       const int32_t* cap_map, int cap_dst) {
-    if (!cap || !cap_map) return fail(WM_E_ARG, "bad argument");
-    return op_dec_linear(out, x, W, bias, ln_g, ln_b, nullptr, B, N, K, dtype, 0, 0, 0, 0, nullptr, nullptr, 0, 0, 0, 0, 0, cap, cap_sel, 0, 0,
-                         cap_nsel, cap_map, cap_dst);
-}
-
-// The decode step's final LayerNorm + tied-embedding logits and its fused argmax, wired as decode_core (Logits::full) and
-// argmax_peek wire them: launch_dec_logits picks the kernel variant from (dtype, K, B), argmax_step reduces its partials.
-// logprob non-null: the LP instantiation of the same kernel variant, and the chosen ids' log-probabilities [B] (wm_op_logits_lp)
-static int op_logits(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
-                     const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype, const uint32_t* seen = nullptr,
-                     const uint32_t* ban = nullptr, float penalty = 1.f, const uint32_t* hit = nullptr, const int32_t* slot_id = nullptr,
-                     int n_slots = 0, const float* slot_bias = nullptr, const int32_t* slot_flags = nullptr) {
-    if (!logits || !ids || !x || !ln_g || !ln_b || !emb || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
-    if (K != 128 && K != 384 && K != 512 && K != 768 && K != 1024) return fail(WM_E_ARG, "K must be 128, 384, 512, 768 or 1024 (the logits kernels' d_model)");
-    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
-    if (ranges && (timestamp_begin <= 0 || timestamp_begin >= N)) return fail(WM_E_ARG, "ranges need 0 < timestamp_begin < N");
-    TmpDev t;
-    t.bufs.reserve(28);
-    hipStream_t st = nullptr;
-    const int ldo = (N + 3) / 4 * 4, npart = dec_logits_parts(N);  // the kernel stores whole float4 groups below ldo
-    DevBuf &dx = t.add(), &g = t.add(), &be = t.add(), &w = t.add(), &mk = t.add(), &o = t.add(), &av = t.add(), &ai = t.add(),
-           &tst = t.add(), &tv = t.add(), &ti = t.add(), &tm = t.add(), &ts = t.add(), &nx = t.add(), &ls = t.add(), &ln = t.add();
-    WMCHK(upload(dx, x, (size_t)B * K, WM_F32));
-    WMCHK(upload(g, ln_g, K, WM_F32));
-    WMCHK(upload(be, ln_b, K, WM_F32));
-    WMCHK(upload(w, emb, (size_t)N * K, dtype));
-    if (mask) WMCHK(upload(mk, mask, N, WM_F32));
-    WMCHK(o.alloc((size_t)B * ldo * 4, true));
-    WMCHK(av.alloc((size_t)B * npart * 4, true));
-    WMCHK(ai.alloc((size_t)B * npart * 4, true));
-    WMCHK(nx.alloc((size_t)B * 4, true));
-    if (logprob) {
-        WMCHK(ls.alloc((size_t)B * npart * 4, true));
-        WMCHK(ln.alloc((size_t)B * 4, true));
-    }
-    TsRules rules{};
-    if (ranges) {
-        std::vector<TsState> h(B);
-        for (int b = 0; b < B; ++b) {
-            h[b] = TsState{};
-            h[b].n_gen = 1;
-            h[b].t_last = -1;
-            h[b].text_lo = ranges[4 * b];
-            h[b].text_hi = ranges[4 * b + 1];
-            h[b].ts_lo = ranges[4 * b + 2];
-            h[b].ts_hi = ranges[4 * b + 3];
-        }
-        WMCHK(tst.alloc((size_t)B * sizeof(TsState)));
-        HIPCHK(hipMemcpy(tst.p, h.data(), (size_t)B * sizeof(TsState), hipMemcpyHostToDevice));
-        for (DevBuf* d : {&tv, &ti, &tm, &ts}) WMCHK(d->alloc((size_t)B * npart * 4, true));
-        rules.tb = timestamp_begin;
-        rules.eos = timestamp_begin;
-        rules.max_init = -1;
-        rules.vocab = N;
-    }
-    DecLinearParams p = linear_block(dx.as<float>(), g.as<float>(), be.as<float>(), w.p, nullptr, N, K, B, o.as<float>(), ldo);
-    p.amax_val = av.as<float>();
-    p.amax_idx = ai.as<int>();
-    p.amax_stride = npart;
-    p.amax_mask = mask ? mk.as<float>() : nullptr;
-    if (ranges) {
-        p.ts_state = tst.as<TsState>();
-        p.ts_begin = timestamp_begin;
-        p.ts_val = tv.as<float>();
-        p.ts_idx = ti.as<int>();
-        p.ts_m = tm.as<float>();
-        p.ts_s = ts.as<float>();
-    }
-    if (logprob) p.lp_s = ls.as<float>();
-    if (seen) {  // wm_op_logits_processed: the rows' sets as given, the RP instantiation of the same kernel variant
-        DevBuf &ds = t.add(), &db = t.add(), &dc = t.add();
-        const size_t words = (size_t)repeat_words(N);
-        const RepeatCtl ctl{penalty, 0};
-        WMCHK(ds.alloc(B * words * 4));
-        WMCHK(db.alloc(B * words * 4));
-        WMCHK(dc.alloc(sizeof(ctl)));
-        HIPCHK(hipMemcpy(ds.p, seen, B * words * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(db.p, ban, B * words * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dc.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice));
-        p.rp_seen = ds.as<unsigned>();
-        p.rp_ban = db.as<unsigned>();
-        p.rp_ctl = dc.as<RepeatCtl>();
-        p.rp_words = (int)words;
-        if (hit) {  // wm_op_logits_seq_bias: the rows' hit bits and slots as given, the SB instantiation of the same kernel variant
-            DevBuf &dh = t.add(), &dv = t.add(), &di = t.add(), &dt = t.add();
-            std::vector<int32_t> h_of((size_t)N, -1);
-            for (int k = 0; k < n_slots; ++k) h_of[slot_id[k]] = k;
-            std::vector<SeqSlot> h((size_t)B * SEQ_BIAS_MAX, SeqSlot{0.f, 0});
-            for (int b = 0; b < B; ++b)
-                for (int k = 0; k < n_slots; ++k) h[(size_t)b * SEQ_BIAS_MAX + k] = SeqSlot{slot_bias[(size_t)b * n_slots + k], slot_flags[(size_t)b * n_slots + k]};
-            SeqBiasCtl sc{};
-            sc.n_slots = n_slots;
-            sc.eot = -1;
-            WMCHK(dh.alloc(B * words * 4));
-            WMCHK(dv.alloc(h.size() * sizeof(SeqSlot)));
-            WMCHK(di.alloc((size_t)N * 4));
-            WMCHK(dt.alloc(sizeof(sc)));
-            sc.slot_of = di.as<int>();
-            HIPCHK(hipMemcpy(dh.p, hit, B * words * 4, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(dv.p, h.data(), h.size() * sizeof(SeqSlot), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(di.p, h_of.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(dt.p, &sc, sizeof(sc), hipMemcpyHostToDevice));
-            p.sb_hit = dh.as<unsigned>();
-            p.sb_val = dv.as<SeqSlot>();
-            p.sb_ctl = dt.as<SeqBiasCtl>();
-        }
-    }
-    int lrc = 0;
-    DISPATCH_DT(dtype, TT, lrc = launch_dec_logits<TT>(p, st));
-    LCHK(lrc);
-    ArgmaxParams a{};
-    if (logprob) {
-        a.lp_s = ls.as<float>();
-        a.lp_next = ln.as<float>();
-    }
-    if (ranges) {
-        a.ts_state = tst.as<TsState>();
-        a.rules = rules;
-        a.ts_val = tv.as<float>();
-        a.ts_idx = ti.as<int>();
-        a.ts_m = tm.as<float>();
-        a.ts_s = ts.as<float>();
-        a.ts_part0 = timestamp_begin / dec_logits_ids_per_part(N);
-    }
-    a.logits = o.as<float>();
-    a.ldl = ldo;
-    a.V = N;
-    a.B = B;
-    a.pval = av.as<float>();
-    a.pidx = ai.as<int>();
-    a.npart = npart;
-    a.next = nx.as<int>();
-    launch_argmax_step(a, st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy2D(logits, (size_t)N * 4, o.p, (size_t)ldo * 4, (size_t)N * 4, B, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ids, nx.p, (size_t)B * 4, hipMemcpyDeviceToHost));
-    if (logprob) HIPCHK(hipMemcpy(logprob, ln.p, (size_t)B * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-extern "C" int wm_op_logits(float* logits, int32_t* ids, const float* x, const float* ln_g, const float* ln_b, const float* emb,
-                            const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
-    return op_logits(logits, ids, nullptr, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype);
-}
-extern "C" int wm_op_logits_lp(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
-                               const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
-    if (!logprob) return fail(WM_E_ARG, "bad argument");
-    return op_logits(logits, ids, logprob, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype);
-}
-// The same two launches with the repetition processors on given sets: seen / ban [B][ceil(N / 32)], bit (id & 31) of word
-// id >> 5.  logprob null: the instantiation without log-probabilities.
-extern "C" int wm_op_logits_processed(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b,
-                                      const float* emb, const float* mask, const int32_t* ranges, int timestamp_begin, const uint32_t* seen,
-                                      const uint32_t* ban, float penalty, int B, int N, int K, int dtype) {
-    if (!seen || !ban || !(penalty > 0.f)) return fail(WM_E_ARG, "bad argument");
-    return op_logits(logits, ids, logprob, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype, seen, ban, penalty);
-}
-// The sets' bookkeeping alone: repeat_init on each row's prompt tokens[b][0 .. prompt_len[b]), then one argmax launch per step that is
-// handed the row's next id of the table as its only candidate, so it appends exactly that id — rows end at n_ids[b] (a row past its
-// end is `finished` and does nothing).  seen / ban: [steps + 1][B][ceil(vocab / 32)], entry 0 after the init, entry s after step s.
-extern "C" int wm_op_repeat_sets(uint32_t* seen, uint32_t* ban, const int32_t* tokens, const int32_t* prompt_len, const int32_t* n_ids, int B,
-                                 int stride, int vocab, int ngram, int steps) {
-    if (!seen || !ban || !tokens || !prompt_len || !n_ids || B <= 0 || stride <= 0 || vocab <= 0 || steps < 0) return fail(WM_E_ARG, "bad argument");
-    if (ngram < 0 || ngram > REPEAT_NGRAM_MAX) return fail(WM_E_ARG, "no_repeat_ngram_size %d outside [0, %d]", ngram, REPEAT_NGRAM_MAX);
-    for (int b = 0; b < B; ++b) {
-        if (prompt_len[b] < 1 || prompt_len[b] > n_ids[b] || n_ids[b] > stride) return fail(WM_E_ARG, "row %d: need 1 <= prompt_len <= n_ids <= stride", b);
-        for (int i = 0; i < n_ids[b]; ++i)
-            if (tokens[(size_t)b * stride + i] < 0 || tokens[(size_t)b * stride + i] >= vocab) return fail(WM_E_ARG, "token id out of range");
-    }
-    TmpDev t;
-    t.bufs.reserve(12);
-    hipStream_t st = nullptr;
-    const size_t words = (size_t)repeat_words(vocab), set_bytes = (size_t)B * words * 4;
-    DevBuf &ds = t.add(), &db = t.add(), &dc = t.add(), &out = t.add(), &nt = t.add(), &fin = t.add(), &ctl = t.add(), &pv = t.add(), &pi = t.add(),
-           &nx = t.add(), &pos = t.add();
-    WMCHK(ds.alloc(set_bytes));
-    WMCHK(db.alloc(set_bytes));
-    WMCHK(dc.alloc(sizeof(RepeatCtl)));
-    WMCHK(out.alloc((size_t)B * stride * 4, true));
-    WMCHK(nt.alloc((size_t)B * 4));
-    WMCHK(fin.alloc((size_t)B * 4, true));
-    WMCHK(ctl.alloc(sizeof(StepCtl), true));
-    WMCHK(pv.alloc((size_t)B * 4, true));  // one partial per row: value 0, index = the id to append
-    WMCHK(pi.alloc((size_t)B * 4));
-    WMCHK(nx.alloc((size_t)B * 4));
-    WMCHK(pos.alloc((size_t)B * 4, true));
-    std::vector<int32_t> h_out((size_t)B * stride, 0), h_idx(B), h_fin(B);
-    for (int b = 0; b < B; ++b) std::copy(tokens + (size_t)b * stride, tokens + (size_t)b * stride + prompt_len[b], h_out.begin() + (size_t)b * stride);
-    HIPCHK(hipMemcpy(out.p, h_out.data(), h_out.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(nt.p, prompt_len, (size_t)B * 4, hipMemcpyHostToDevice));
-    RepeatInitParams r{};
-    r.seen = ds.as<unsigned>();
-    r.ban = db.as<unsigned>();
-    r.words = (int)words;
-    r.B = B;
-    r.ctl = dc.as<RepeatCtl>();
-    r.penalty = 1.f;
-    r.ngram = ngram;
-    r.out_tokens = out.as<int>();
-    r.out_stride = stride;
-    r.n_tokens = nt.as<int>();
-    launch_repeat_init(r, st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(seen, ds.p, set_bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ban, db.p, set_bytes, hipMemcpyDeviceToHost));
-    for (int s = 1; s <= steps; ++s) {
-        for (int b = 0; b < B; ++b) {
-            const int at = prompt_len[b] + s - 1;
-            h_fin[b] = at >= n_ids[b];
-            h_idx[b] = h_fin[b] ? 0 : tokens[(size_t)b * stride + at];
-        }
-        HIPCHK(hipMemcpy(pi.p, h_idx.data(), (size_t)B * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(fin.p, h_fin.data(), (size_t)B * 4, hipMemcpyHostToDevice));
-        ArgmaxParams a{};
-        a.V = vocab;
-        a.B = B;
-        a.pval = pv.as<float>();
-        a.pidx = pi.as<int>();
-        a.npart = 1;
-        a.next = nx.as<int>();
-        a.out_tokens = out.as<int>();
-        a.out_stride = stride;
-        a.n_tokens = nt.as<int>();
-        a.finished = fin.as<int>();
-        a.ctl = ctl.as<StepCtl>();
-        a.pos = pos.as<int>();
-        a.eot = -1;
-        a.ignore_eot = 1;
-        a.rp_seen = ds.as<unsigned>();
-        a.rp_ban = db.as<unsigned>();
-        a.rp_ctl = dc.as<RepeatCtl>();
-        a.rp_words = (int)words;
-        LCHK(launch_argmax_step(a, st));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(seen + (size_t)s * B * words, ds.p, set_bytes, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ban + (size_t)s * B * words, db.p, set_bytes, hipMemcpyDeviceToHost));
-    }
-    return 0;
-}
-// The same two launches with sequence bias / bad words on given hit state: hit [B][ceil(N / 32)], the slots' ids
-// (ascending) and, per row and slot, the summed bias and the flags (bit 0 on, bit 1 ban).  seen / ban / penalty as above.
-extern "C" int wm_op_logits_seq_bias(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b,
-                                     const float* emb, const float* mask, const int32_t* ranges, int timestamp_begin, const uint32_t* seen,
-                                     const uint32_t* ban, float penalty, const uint32_t* hit, const int32_t* slot_id, int n_slots,
-                                     const float* slot_bias, const int32_t* slot_flags, int B, int N, int K, int dtype) {
-    if (!seen || !ban || !(penalty > 0.f) || !hit || !slot_id || !slot_bias || !slot_flags || n_slots < 1 || n_slots > SEQ_BIAS_MAX)
-        return fail(WM_E_ARG, "bad argument");
-    for (int k = 0; k < n_slots; ++k)
-        if (slot_id[k] < 0 || slot_id[k] >= N || (k && slot_id[k] <= slot_id[k - 1])) return fail(WM_E_ARG, "slot ids must ascend inside the vocabulary");
-    // the kernel looks a set bit's slot up without a check (the drivers set a bit only for a slot's id): refuse any other bit here
-    if (B > 0 && N > 0) {
-        std::vector<char> is_slot((size_t)N, 0);
-        for (int k = 0; k < n_slots; ++k) is_slot[slot_id[k]] = 1;
-        const int words = repeat_words(N);
-        for (int b = 0; b < B; ++b)
-            for (int t = 0; t < words * 32; ++t)
-                if ((hit[(size_t)b * words + (t >> 5)] >> (t & 31) & 1u) && (t >= N || !is_slot[t])) return fail(WM_E_ARG, "row %d: hit bit %d has no slot", b, t);
-    }
-    return op_logits(logits, ids, logprob, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype, seen, ban, penalty, hit, slot_id, n_slots,
-                     slot_bias, slot_flags);
-}
-// The hit state's bookkeeping alone, as wm_op_repeat_sets runs the sets': seq_bias_init on each row's prompt, then one argmax launch
-// per step that appends the row's next id of the table.  The table is built from the two lists as wm_set_sequence_bias builds it (same
-// refusals).  slot_id [n_seq + n_bad] and *n_slots: the table's slots; hit [steps + 1][B][ceil(vocab / 32)], slot_bias / slot_flags
-// [steps + 1][B][n_seq + n_bad] (the first *n_slots of each row are written) — entry 0 after the init, entry s after step s.
-extern "C" int wm_op_seq_bias_hits(uint32_t* hit, float* slot_bias, int32_t* slot_flags, int32_t* slot_id, int32_t* n_slots, const int32_t* tokens,
-                                   const int32_t* prompt_len, const int32_t* n_ids, int B, int stride, int vocab, int eot, const int32_t* seq_ids,
-                                   const int32_t* seq_off, const float* seq_bias, int n_seq, const int32_t* bad_ids, const int32_t* bad_off, int n_bad,
-                                   int steps) {
-    if (!hit || !slot_bias || !slot_flags || !slot_id || !n_slots || !tokens || !prompt_len || !n_ids || B <= 0 || stride <= 0 || vocab <= 0 || steps < 0)
-        return fail(WM_E_ARG, "bad argument");
-    for (int b = 0; b < B; ++b) {
-        if (prompt_len[b] < 1 || prompt_len[b] > n_ids[b] || n_ids[b] > stride) return fail(WM_E_ARG, "row %d: need 1 <= prompt_len <= n_ids <= stride", b);
-        for (int i = 0; i < n_ids[b]; ++i)
-            if (tokens[(size_t)b * stride + i] < 0 || tokens[(size_t)b * stride + i] >= vocab) return fail(WM_E_ARG, "token id out of range");
-    }
-    std::shared_ptr<SeqTable> tab;
-    std::vector<int32_t> sid;
-    WMCHK(build_seq_table(tab, vocab, seq_ids, seq_off, seq_bias, n_seq, bad_ids, bad_off, n_bad, &sid));
-    if (!tab) return fail(WM_E_ARG, "both lists are empty");
-    const int cap = n_seq + n_bad, ns = tab->n_slots;
-    *n_slots = ns;
-    std::copy(sid.begin(), sid.end(), slot_id);
-    TmpDev t;
-    t.bufs.reserve(16);
-    hipStream_t st = nullptr;
-    const size_t words = (size_t)repeat_words(vocab), set_bytes = (size_t)B * words * 4;
-    DevBuf &ds = t.add(), &db = t.add(), &dc = t.add(), &dh = t.add(), &dv = t.add(), &dsc = t.add(), &out = t.add(), &nt = t.add(), &fin = t.add(),
-           &ctl = t.add(), &pv = t.add(), &pi = t.add(), &nx = t.add(), &pos = t.add();
-    WMCHK(ds.alloc(set_bytes));
-    WMCHK(db.alloc(set_bytes));
-    WMCHK(dc.alloc(sizeof(RepeatCtl)));
-    WMCHK(dh.alloc(set_bytes));
-    WMCHK(dv.alloc((size_t)B * SEQ_BIAS_MAX * sizeof(SeqSlot), true));
-    WMCHK(dsc.alloc(sizeof(SeqBiasCtl)));
-    WMCHK(out.alloc((size_t)B * stride * 4, true));
-    WMCHK(nt.alloc((size_t)B * 4));
-    WMCHK(fin.alloc((size_t)B * 4, true));
-    WMCHK(ctl.alloc(sizeof(StepCtl), true));
-    WMCHK(pv.alloc((size_t)B * 4, true));  // one partial per row: value 0, index = the id to append
-    WMCHK(pi.alloc((size_t)B * 4));
-    WMCHK(nx.alloc((size_t)B * 4));
-    WMCHK(pos.alloc((size_t)B * 4, true));
-    std::vector<int32_t> h_out((size_t)B * stride, 0), h_idx(B), h_fin(B);
-    for (int b = 0; b < B; ++b) std::copy(tokens + (size_t)b * stride, tokens + (size_t)b * stride + prompt_len[b], h_out.begin() + (size_t)b * stride);
-    HIPCHK(hipMemcpy(out.p, h_out.data(), h_out.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(nt.p, prompt_len, (size_t)B * 4, hipMemcpyHostToDevice));
-    RepeatInitParams r{};
-    r.seen = ds.as<unsigned>();
-    r.ban = db.as<unsigned>();
-    r.words = (int)words;
-    r.B = B;
-    r.ctl = dc.as<RepeatCtl>();
-    r.penalty = 1.f;
-    r.ngram = 0;
-    r.out_tokens = out.as<int>();
-    r.out_stride = stride;
-    r.n_tokens = nt.as<int>();
-    launch_repeat_init(r, st);
-    SeqBiasInitParams q{};
-    q.hit = dh.as<unsigned>();
-    q.val = dv.as<SeqSlot>();
-    q.words = (int)words;
-    q.B = B;
-    q.ctl = dsc.as<SeqBiasCtl>();
-    q.table = tab->ctl(eot);
-    q.out_tokens = out.as<int>();
-    q.out_stride = stride;
-    q.n_tokens = nt.as<int>();
-    LCHK(launch_seq_bias_init(q, st));
-    HIPCHK(hipGetLastError());
-    std::vector<SeqSlot> h_val((size_t)B * SEQ_BIAS_MAX);
-    auto fetch = [&](int s) -> int {
-        HIPCHK(hipMemcpy(hit + (size_t)s * B * words, dh.p, set_bytes, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(h_val.data(), dv.p, h_val.size() * sizeof(SeqSlot), hipMemcpyDeviceToHost));
-        for (int b = 0; b < B; ++b)
-            for (int k = 0; k < ns; ++k) {
-                slot_bias[((size_t)s * B + b) * cap + k] = h_val[(size_t)b * SEQ_BIAS_MAX + k].bias;
-                slot_flags[((size_t)s * B + b) * cap + k] = h_val[(size_t)b * SEQ_BIAS_MAX + k].flags;
-            }
-        return 0;
-    };
-    WMCHK(fetch(0));
-    for (int s = 1; s <= steps; ++s) {
-        for (int b = 0; b < B; ++b) {
-            const int at = prompt_len[b] + s - 1;
-            h_fin[b] = at >= n_ids[b];
-            h_idx[b] = h_fin[b] ? 0 : tokens[(size_t)b * stride + at];
-        }
-        HIPCHK(hipMemcpy(pi.p, h_idx.data(), (size_t)B * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(fin.p, h_fin.data(), (size_t)B * 4, hipMemcpyHostToDevice));
-        ArgmaxParams a{};
-        a.V = vocab;
-        a.B = B;
-        a.pval = pv.as<float>();
-        a.pidx = pi.as<int>();
-        a.npart = 1;
-        a.next = nx.as<int>();
-        a.out_tokens = out.as<int>();
-        a.out_stride = stride;
-        a.n_tokens = nt.as<int>();
-        a.finished = fin.as<int>();
-        a.ctl = ctl.as<StepCtl>();
-        a.pos = pos.as<int>();
-        a.eot = -1;
-        a.ignore_eot = 1;
-        a.rp_seen = ds.as<unsigned>();
-        a.rp_ban = db.as<unsigned>();
-        a.rp_ctl = dc.as<RepeatCtl>();
-        a.rp_words = (int)words;
-        a.sb_hit = dh.as<unsigned>();
-        a.sb_val = dv.as<SeqSlot>();
-        a.sb_ctl = dsc.as<SeqBiasCtl>();
-        LCHK(launch_argmax_step(a, st));
-        HIPCHK(hipGetLastError());
-        WMCHK(fetch(s));
-    }
-    return 0;
-}
-
-// The no-speech probe's launches on the kernel variant wm_op_logits_lp would pick for (dtype, K, B): the LP sweep with
-// no mask and no ranges, then no_speech_finish_kernel.  prob[b] = softmax(logits[b])[token], lse[b] = logsumexp(logits[b]).
-extern "C" int wm_op_no_speech(float* prob, float* lse, const float* x, const float* ln_g, const float* ln_b, const float* emb, int B, int N, int K,
-                               int dtype, int token) {
-    if (!prob || !lse || !x || !ln_g || !ln_b || !emb || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
-    if (K != 128 && K != 384 && K != 512 && K != 768 && K != 1024) return fail(WM_E_ARG, "K must be 128, 384, 512, 768 or 1024 (the logits kernels' d_model)");
-    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
-    if (token < 0 || token >= N) return fail(WM_E_ARG, "token %d is not a vocabulary id", token);
-    TmpDev t;
-    t.bufs.reserve(12);
-    const int npart = dec_logits_parts(N);
-    DevBuf &dx = t.add(), &g = t.add(), &be = t.add(), &w = t.add(), &pm = t.add(), &pi = t.add(), &ps = t.add(), &pr = t.add(), &ls = t.add();
-    WMCHK(upload(dx, x, (size_t)B * K, WM_F32));
-    WMCHK(upload(g, ln_g, K, WM_F32));
-    WMCHK(upload(be, ln_b, K, WM_F32));
-    WMCHK(upload(w, emb, (size_t)N * K, dtype));
-    for (DevBuf* d : {&pm, &pi, &ps}) WMCHK(d->alloc((size_t)B * npart * 4, true));
-    WMCHK(pr.alloc((size_t)B * 4, true));
-    WMCHK(ls.alloc((size_t)B * 4, true));
-    WMCHK(ns_sweep(dtype, dx.as<float>(), VocabHead{g.as<float>(), be.as<float>(), w.p, N, K}, B, npart, pm.as<float>(), pi.as<int>(), ps.as<float>(),
-                   token, pr.as<float>(), ls.as<float>(), nullptr));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(prob, pr.p, (size_t)B * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(lse, ls.p, (size_t)B * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// lang_detect_kernel alone, launched as the language pass launches it (no patch).
-extern "C" int wm_op_lang_detect(int32_t* lang_out, float* probs, const float* x, const float* ln_g, const float* ln_b, const float* emb,
-                                 const int32_t* lang_ids, int n_lang, int B, int N, int K, int dtype) {
-    if (!lang_out || !x || !ln_g || !ln_b || !emb || !lang_ids || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
-    if (K != 128 && K != 384 && K != 512 && K != 768 && K != 1024) return fail(WM_E_ARG, "K must be 128, 384, 512, 768 or 1024 (the logits kernels' d_model)");
-    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
-    WMCHK(lang_list_check(N, lang_ids, n_lang));
-    TmpDev t;
-    t.bufs.reserve(8);
-    DevBuf &dx = t.add(), &g = t.add(), &be = t.add(), &w = t.add(), &li = t.add(), &lo = t.add(), &pr = t.add();
-    WMCHK(upload(dx, x, (size_t)B * K, WM_F32));
-    WMCHK(upload(g, ln_g, K, WM_F32));
-    WMCHK(upload(be, ln_b, K, WM_F32));
-    WMCHK(upload(w, emb, (size_t)N * K, dtype));
-    WMCHK(li.alloc((size_t)n_lang * 4));
-    HIPCHK(hipMemcpy(li.p, lang_ids, (size_t)n_lang * 4, hipMemcpyHostToDevice));
-    WMCHK(lo.alloc((size_t)B * 4, true));
-    WMCHK(pr.alloc((size_t)B * n_lang * 4, true));
-    LangDetectParams q{};
-    q.x = dx.as<float>();
-    q.ldx = K;
-    q.ln_g = g.as<float>();
-    q.ln_b = be.as<float>();
-    q.emb = w.p;
-    q.lang_ids = li.as<int>();
-    q.n_lang = n_lang;
-    q.K = K;
-    q.B = B;
-    q.lang_out = lo.as<int>();
-    q.probs = pr.as<float>();
-    DISPATCH_DT(dtype, TT, launch_lang_detect<TT>(q, nullptr));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(lang_out, lo.p, (size_t)B * 4, hipMemcpyDeviceToHost));
-    if (probs) HIPCHK(hipMemcpy(probs, pr.p, (size_t)B * n_lang * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// The absorbed cross-attention of m->xattn models, wired as launch_cross_attn + cross_attn_merge wire it: absorb, X sweep, merge.
-extern "C" int wm_op_xattn(float* out, const float* q, const float* Wk, const float* Wv, const float* bv, const float* X, int rows,
-                           int q_B, int n_utt, int n_keys, int n_heads, int nsplit, int out_dtype) {
-    if (!out || !q || !Wk || !Wv || !bv || !X || rows <= 0 || n_utt <= 0 || n_keys <= 0) return fail(WM_E_ARG, "bad argument");
-    if (n_heads < 1 || n_heads > 8 || nsplit < 1 || nsplit > 64) return fail(WM_E_ARG, "needs 1 <= n_heads <= 8, 1 <= nsplit <= 64");
-    if (out_dtype != WM_F32 && out_dtype != WM_BF16) return fail(WM_E_ARG, "out_dtype must be WM_F32 or WM_BF16");
-    if (q_B < 0 || (q_B > 0 ? (q_B > n_utt || rows % q_B) : rows > n_utt))
-        return fail(WM_E_ARG, "rows must be P * q_B with q_B <= n_utt (prefill), or <= n_utt (q_B == 0)");
-    const size_t d = (size_t)n_heads * 64;
-    TmpDev t;
-    t.bufs.reserve(12);
-    hipStream_t st = nullptr;
-    DevBuf &dq = t.add(), &wk = t.add(), &wv = t.add(), &b = t.add(), &dx = t.add(), &qs = t.add(), &py = t.add(), &pml = t.add(),
-           &o = t.add();
-    WMCHK(upload(dq, q, (size_t)rows * d, WM_F32));
-    WMCHK(upload(wk, Wk, d * d, WM_BF16));
-    WMCHK(upload(wv, Wv, d * d, WM_BF16));
-    WMCHK(upload(b, bv, d, WM_F32));
-    WMCHK(upload(dx, X, (size_t)n_utt * n_keys * d, WM_BF16));
-    WMCHK(qs.alloc((size_t)rows * 3 * n_heads * d * 2, true));
-    WMCHK(py.alloc((size_t)rows * nsplit * n_heads * d * 4, true));
-    WMCHK(pml.alloc((size_t)rows * nsplit * n_heads * 2 * 4, true));
-    WMCHK(o.alloc((size_t)rows * d * dt_size(out_dtype), true));
-    XAttnParams x{};
-    x.q = dq.as<float>();
-    x.Wk = wk.p;
-    x.Wv = wv.p;
-    x.bv = b.as<float>();
-    x.X = dx.p;
-    x.x_stride = (long)((size_t)n_keys * d);
-    x.n_keys = n_keys;
-    x.nsplit = nsplit;
-    x.H = n_heads;
-    x.d = (int)d;
-    x.rows = rows;
-    x.q_B = q_B;
-    x.scale = ATTN_SCALE;
-    x.qs = qs.p;
-    x.part_y = py.as<float>();
-    x.part_ml = pml.as<float>();
-    x.out = o.p;
-    x.out_dtype = out_dtype;
-    LCHK(launch_xattn_absorb(x, st));
-    LCHK(launch_xattn(x, st));
-    LCHK(launch_xattn_merge(x, st));
-    HIPCHK(hipGetLastError());
-    const size_t n = (size_t)rows * d;
-    std::vector<unsigned char> h(n * dt_size(out_dtype));
-    HIPCHK(hipMemcpy(h.data(), o.p, h.size(), hipMemcpyDeviceToHost));
-    widen_to_f32(h.data(), out_dtype, n, out);
-    return 0;
-}
-
-// xattn_absorb_kernel alone: the three bf16 images of q' as the X sweep reads them
-extern "C" int wm_op_xattn_absorb(float* images, const float* q, const float* Wk, int rows, int n_heads, int late_loads) {
-    if (!images || !q || !Wk || rows <= 0) return fail(WM_E_ARG, "bad argument");
-    if (n_heads < 1 || n_heads > 8) return fail(WM_E_ARG, "needs 1 <= n_heads <= 8");
-    const size_t d = (size_t)n_heads * 64, n = (size_t)rows * 3 * n_heads * d;
-    TmpDev t;
-    t.bufs.reserve(4);
-    DevBuf &dq = t.add(), &wk = t.add(), &qs = t.add();
-    WMCHK(upload(dq, q, (size_t)rows * d, WM_F32));
-    WMCHK(upload(wk, Wk, d * d, WM_BF16));
-    WMCHK(qs.alloc(n * 2, true));
-    XAttnParams x{};
-    x.q = dq.as<float>();
-    x.Wk = wk.p;
-    x.n_keys = 1;  // (not read by the absorb; the launch check wants a key)
-    x.nsplit = 1;
-    x.H = n_heads;
-    x.d = (int)d;
-    x.rows = rows;
-    x.scale = ATTN_SCALE;
-    x.qs = qs.p;
-    LCHK(launch_xattn_absorb(x, nullptr, late_loads != 0));
-    HIPCHK(hipGetLastError());
-    std::vector<unsigned char> h(n * 2);
-    HIPCHK(hipMemcpy(h.data(), qs.p, h.size(), hipMemcpyDeviceToHost));
-    widen_to_f32(h.data(), WM_BF16, n, images);
-    return 0;
-}
-
-extern "C" int wm_op_gelu(float* tt, size_t n, int mode) {
-    if (!tt || (mode != 0 && mode != 1)) return fail(WM_E_ARG, "bad argument");
-    if (n == 0) return 0;
-    TmpDev t;
-    t.bufs.reserve(2);
-    DevBuf& x = t.add();
-    WMCHK(upload(x, tt, n, WM_F32));
-    launch_gelu(x.as<float>(), n, mode, nullptr);
-    HIPCHK(hipMemcpy(tt, x.p, n * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int wm_op_softmax_rows(float* tt, int rows, int cols) {
-    if (!tt || rows <= 0 || cols <= 0) return fail(WM_E_ARG, "bad argument");
-    TmpDev t;
-    t.bufs.reserve(2);
-    DevBuf& x = t.add();
-    WMCHK(upload(x, tt, (size_t)rows * cols, WM_F32));
-    launch_softmax_rows(x.as<float>(), rows, cols, nullptr);
-    HIPCHK(hipMemcpy(tt, x.p, (size_t)rows * cols * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int wm_op_argmax(const float* tt, int n, int32_t* idx) {
-    if (!tt || !idx || n <= 0) return fail(WM_E_ARG, "bad argument");
-    TmpDev t;
-    t.bufs.reserve(2);
-    DevBuf &x = t.add(), &o = t.add();
-    WMCHK(upload(x, tt, n, WM_F32));
-    WMCHK(o.alloc(4));
-    launch_argmax_plain(x.as<float>(), n, o.as<int>(), nullptr);
-    HIPCHK(hipMemcpy(idx, o.p, 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int wm_op_conv1d_k3(float* out, const float* inp, const float* weight, const float* bias, int C_in, int L_in,
-                               int C_out, int stride, int out_T, int dtype) {
-    if (!out || !inp || !weight || !bias || C_in <= 0 || L_in <= 0 || C_out <= 0) return fail(WM_E_ARG, "bad argument");
-    if (stride != 1 && stride != 2) return fail(WM_E_ARG, "stride must be 1 or 2");
-    if (C_out % 128) return fail(WM_E_ARG, "C_out must be a multiple of 128");
-    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
-    const int Cp = (C_in + 31) / 32 * 32;
-    const int L_out = (L_in + 2 - 3) / stride + 1;
-    TmpDev t;
-    t.bufs.reserve(8);
-    DevBuf &x = t.add(), &xt = t.add(), &w = t.add(), &b = t.add(), &o = t.add(), &o2 = t.add();
-    WMCHK(upload(x, inp, (size_t)C_in * L_in, WM_F32));
-    WMCHK(xt.alloc(((size_t)L_in + 2 + 512) * Cp * dt_size(dtype), true));
-    auto wr = conv_relayout(weight, C_out, C_in, Cp);
-    WMCHK(upload(w, wr.data(), wr.size(), dtype));
-    WMCHK(upload(b, bias, C_out, WM_F32));
-    WMCHK(o.alloc((size_t)L_out * C_out * 4));
-    DISPATCH_DT(dtype, TT, launch_mel_transpose_pad<TT>(x.as<float>(), xt.p, 1, C_in, L_in, Cp, nullptr));
-    GemmParams p{};
-    p.A = xt.p;
-    p.W = w.p;
-    p.C = o.p;
-    p.M = L_out;
-    p.N = C_out;
-    p.K = 3 * Cp;
-    p.lda = (long)stride * Cp;
-    p.ldw = 3 * Cp;
-    p.ldc = C_out;
-    p.bias = b.as<float>();
-    WMCHK(gemm_dispatch(dtype, WM_F32, p, 1, nullptr));
-    if (out_T) {
-        HIPCHK(hipMemcpy(out, o.p, (size_t)L_out * C_out * 4, hipMemcpyDeviceToHost));
-    } else {
-        WMCHK(o2.alloc((size_t)L_out * C_out * 4));
-        launch_transpose_f32(o.as<float>(), o2.as<float>(), L_out, C_out, nullptr);
-        HIPCHK(hipMemcpy(out, o2.p, (size_t)L_out * C_out * 4, hipMemcpyDeviceToHost));
-    }
-    HIPCHK(hipGetLastError());
     return 0;
 }

@@ -1,0 +1,1109 @@
+// wm_ops.cpp — the wm_op_* test hooks of include/whisper_mi.h: each uploads host fp32 arrays, launches one or two kernels exactly as
+// the runtime (whisper_mi.cpp) wires them, and copies the result back, for the float64 and known-answer tests.  Hooks that need the
+// static helpers of a subsystem (alignment, resampling, chunking, scoring) stay next to them in whisper_mi.cpp.
+#include "wm_host.h"
+
+using namespace wm;
+
+// ---- the hooks' transfers, each written once (wm_host.h) ------------------------------------------------------------------
+int upload_bytes(DevBuf& b, const void* h, size_t n) {
+    WMCHK(b.alloc(n));
+    HIPCHK(hipMemcpy(b.p, h, n, hipMemcpyHostToDevice));
+    return 0;
+}
+int upload_padded(DevBuf& b, const float* h, size_t n, size_t n_dev, int dt) {
+    std::vector<float> padded(std::max(n, n_dev), 0.f);
+    memcpy(padded.data(), h, n * 4);
+    return upload(b, padded.data(), padded.size(), dt);
+}
+// widen n operand-dtype values on the host
+static void widen_to_f32(const void* src, int dtype, size_t n, float* dst) {
+    if (dtype == WM_F32) {
+        memcpy(dst, src, n * 4);
+        return;
+    }
+    const uint16_t* h = static_cast<const uint16_t*>(src);
+    for (size_t i = 0; i < n; ++i) {
+        if (dtype == WM_BF16) {
+            const uint32_t u = (uint32_t)h[i] << 16;
+            memcpy(&dst[i], &u, 4);
+        } else {
+            _Float16 hv;
+            memcpy(&hv, &h[i], 2);
+            dst[i] = (float)hv;
+        }
+    }
+}
+int download_f32(float* dst, const DevBuf& b, size_t n, int dt) {
+    std::vector<unsigned char> h(n * dt_size(dt));
+    HIPCHK(hipMemcpy(h.data(), b.p, h.size(), hipMemcpyDeviceToHost));
+    widen_to_f32(h.data(), dt, n, dst);
+    return 0;
+}
+int download_f32_rows(float* dst, const DevBuf& b, size_t rows, size_t cols, size_t ld, int dt) {
+    const size_t es = dt_size(dt);
+    std::vector<unsigned char> h(rows * cols * es);
+    HIPCHK(hipMemcpy2D(h.data(), cols * es, b.p, ld * es, cols * es, rows, hipMemcpyDeviceToHost));
+    widen_to_f32(h.data(), dt, rows * cols, dst);
+    return 0;
+}
+int vocab_k_check(int K) {
+    if (K != 128 && K != 384 && K != 512 && K != 768 && K != 1024) return fail(WM_E_ARG, "K must be 128, 384, 512, 768 or 1024 (the logits kernels' d_model)");
+    return 0;
+}
+int upload_vocab_head(TmpDev& t, const float* x, const float* ln_g, const float* ln_b, const float* emb, int B, int N, int K, int dtype,
+                      const float** dx, VocabHead* h) {
+    DevBuf &x_d = t.add(), &g = t.add(), &be = t.add(), &w = t.add();
+    WMCHK(upload(x_d, x, (size_t)B * K, WM_F32));
+    WMCHK(upload(g, ln_g, K, WM_F32));
+    WMCHK(upload(be, ln_b, K, WM_F32));
+    WMCHK(upload(w, emb, (size_t)N * K, dtype));
+    *dx = x_d.as<float>();
+    *h = VocabHead{g.as<float>(), be.as<float>(), w.p, N, K};
+    return 0;
+}
+
+// ---- op-level entry points (whisper_tensor.mojo) --------------------------------------------------------------------------
+
+extern "C" int wm_op_matmul_nt(float* C, const float* A, const float* Bm, const float* bias, int M, int N, int K, int dtype) {
+    if (!C || !A || !Bm || M <= 0 || N <= 0 || K <= 0) return fail(WM_E_ARG, "bad argument");
+    if (K % 32) return fail(WM_E_ARG, "K must be a multiple of 32");
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    TmpDev t;
+    hipStream_t st = nullptr;
+    if (N % 128 == 0) {  // dense path: the encoder GEMM kernel
+        DevBuf &a = t.add(), &w = t.add(), &c = t.add(), &b = t.add();
+        WMCHK(upload_padded(a, A, (size_t)M * K, panel_rows(M) * K, dtype));
+        WMCHK(upload(w, Bm, (size_t)N * K, dtype));
+        WMCHK(c.alloc((size_t)M * N * 4));
+        if (bias) WMCHK(upload(b, bias, N, WM_F32));
+        GemmParams p{};
+        p.A = a.p;
+        p.W = w.p;
+        p.C = c.p;
+        p.M = M;
+        p.N = N;
+        p.K = K;
+        p.lda = K;
+        p.ldw = K;
+        p.ldc = N;
+        p.bias = bias ? b.as<float>() : nullptr;
+        WMCHK(gemm_dispatch(dtype, WM_F32, p, 1, st));
+        HIPCHK(hipMemcpy(C, c.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+    } else {  // skinny path: the decode-step linear kernel
+        const int Np = (N + 15) / 16 * 16;
+        // the kernel splits K over NW <= 16 waves, <= 4 k-steps of 32 each: zero-pad K to the next such size
+        auto splittable = [](int k) {
+            const int ks = k / 32;
+            for (int c = 16; c >= 1; --c)
+                if (ks % c == 0 && ks / c <= 4) return true;
+            return false;
+        };
+        int Kp = (K + 127) / 128 * 128;
+        while (Kp <= 2048 && !splittable(Kp)) Kp += 128;  // (bounded: no K above 2048 splits, and an unbounded search overflowed)
+        if (Kp > 2048) return fail(WM_E_ARG, "K too large for the skinny path (<= 2048)");
+        std::vector<float> Apad((size_t)M * Kp, 0.f), Bpad((size_t)N * Kp, 0.f);
+        for (int i = 0; i < M; ++i) memcpy(&Apad[(size_t)i * Kp], A + (size_t)i * K, (size_t)K * 4);
+        for (int i = 0; i < N; ++i) memcpy(&Bpad[(size_t)i * Kp], Bm + (size_t)i * K, (size_t)K * 4);
+        K = Kp;
+        DevBuf &a = t.add(), &w = t.add(), &c = t.add(), &b = t.add();
+        WMCHK(upload(a, Apad.data(), Apad.size(), WM_F32));
+        WMCHK(upload(w, Bpad.data(), Bpad.size(), dtype));
+        WMCHK(c.alloc((size_t)M * Np * 4));
+        if (bias) WMCHK(upload(b, bias, N, WM_F32));
+        DecLinearParams p{};
+        p.x = a.as<float>();
+        p.ldx = K;
+        p.W = w.p;
+        p.N = N;
+        p.K = K;
+        p.B = M;
+        p.bias = bias ? b.as<float>() : nullptr;
+        p.out = c.as<float>();
+        p.ldo = Np;
+        WMCHK(dec_linear_dispatch(dtype, p, st));
+        WMCHK(download_f32_rows(C, c, M, N, Np, WM_F32));
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// C = layer_norm(A, ln_g, ln_b) · Bᵀ (+ bias): the LN -> projection pair of ResidualAttentionBlock.forward (layers.mojo:449-455,
+// 489-497) on the encoder's kernels.  require_fused != 0 demands the ONE-kernel form (LayerNorm applied while the row-panel GEMM
+// loads its fp32 A rows): a shape that kernel does not take is refused by the launcher — WM_E_ARG, nothing launched, C untouched.
+extern "C" int wm_op_ln_matmul_nt(float* C, const float* A, const float* ln_g, const float* ln_b, const float* Bm, const float* bias,
+                                  int M, int N, int K, int dtype, int require_fused) {
+    if (!C || !A || !ln_g || !ln_b || !Bm || M <= 0 || N <= 0 || K <= 0) return fail(WM_E_ARG, "bad argument");
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    if (K % 128 || K > 1024) return fail(WM_E_ARG, "K must be a multiple of 128 and <= 1024 (layer_norm rows)");
+    TmpDev t;
+    hipStream_t st = nullptr;
+    const size_t Mp = panel_rows(M);
+    DevBuf &x = t.add(), &xn = t.add(), &w = t.add(), &c = t.add(), &b = t.add(), &g = t.add(), &be = t.add();
+    WMCHK(upload_padded(x, A, (size_t)M * K, Mp * K, WM_F32));
+    WMCHK(xn.alloc(Mp * K * dt_size(dtype), true));
+    WMCHK(upload(w, Bm, (size_t)N * K, dtype));
+    WMCHK(c.alloc((size_t)M * N * 4));
+    WMCHK(upload(g, ln_g, K, WM_F32));
+    WMCHK(upload(be, ln_b, K, WM_F32));
+    if (bias) WMCHK(upload(b, bias, N, WM_F32));
+    GemmParams p{};
+    p.A = xn.p;
+    p.W = w.p;
+    p.C = c.p;
+    p.M = M;
+    p.N = N;
+    p.K = K;
+    p.lda = K;
+    p.ldw = K;
+    p.ldc = N;
+    p.bias = bias ? b.as<float>() : nullptr;
+    if (require_fused) {  // handed to the launcher as asked: it either fuses or refuses
+        p.A = x.p;
+        p.ln_g = g.as<float>();
+        p.ln_b = be.as<float>();
+        WMCHK(gemm_dispatch(dtype, WM_F32, p, 1, st));
+    } else {
+        WMCHK(ln_then_gemm(dtype, WM_F32, p, x.as<float>(), g.as<float>(), be.as<float>(), st));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(C, c.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int wm_op_layer_norm(float* out, const float* inp, const float* gamma, const float* beta, int rows, int cols, float eps) {
+    if (!out || !inp || !gamma || !beta || rows <= 0 || cols <= 0) return fail(WM_E_ARG, "bad argument");
+    if (cols % 128 || cols > 1024) return fail(WM_E_ARG, "cols must be a multiple of 128 and <= 1024");
+    TmpDev t;
+    DevBuf &x = t.add(), &g = t.add(), &b = t.add(), &o = t.add();
+    WMCHK(upload(x, inp, (size_t)rows * cols, WM_F32));
+    WMCHK(upload(g, gamma, cols, WM_F32));
+    WMCHK(upload(b, beta, cols, WM_F32));
+    WMCHK(o.alloc((size_t)rows * cols * 4));
+    launch_layernorm_rows<float>(x.as<float>(), g.as<float>(), b.as<float>(), nullptr, o.as<float>(), rows, cols, eps, nullptr);
+    HIPCHK(hipMemcpy(out, o.p, (size_t)rows * cols * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// launch_layernorm_rows<T> with the operand-dtype store (out_t, returned widened), the fp32 store (out_f), or both — the launches the
+// base / small encoder makes before every projection.  out_t / out_f hold rows + 1 rows, in and out: the device buffers start from the
+// caller's values, so the guard row (and anything else the kernel did not write) comes back as it went in.  Known-answer tests.
+extern "C" int wm_op_layer_norm_t(float* out_t, float* out_f, const float* inp, const float* gamma, const float* beta, int rows, int cols,
+                                  float eps, int dtype) {
+    if ((!out_t && !out_f) || !inp || !gamma || !beta || rows <= 0 || cols <= 0) return fail(WM_E_ARG, "bad argument");
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    if (cols % 128 || cols > 1024) return fail(WM_E_ARG, "cols must be a multiple of 128 and <= 1024");
+    const size_t n = (size_t)rows * cols, ng = n + cols;
+    TmpDev t;
+    DevBuf &x = t.add(), &g = t.add(), &b = t.add(), &ot = t.add(), &of = t.add();
+    WMCHK(upload(x, inp, n, WM_F32));
+    WMCHK(upload(g, gamma, cols, WM_F32));
+    WMCHK(upload(b, beta, cols, WM_F32));
+    if (out_t) WMCHK(upload(ot, out_t, ng, dtype));
+    if (out_f) WMCHK(upload(of, out_f, ng, WM_F32));
+    DISPATCH_DT(dtype, TT, launch_layernorm_rows<TT>(x.as<float>(), g.as<float>(), b.as<float>(), out_t ? ot.p : nullptr,
+                                                     out_f ? of.as<float>() : nullptr, rows, cols, eps, nullptr));
+    HIPCHK(hipGetLastError());
+    if (out_t) WMCHK(download_f32(out_t, ot, ng, dtype));
+    if (out_f) HIPCHK(hipMemcpy(out_f, of.p, ng * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// One gemm_dispatch call with everything GemmParams offers the two tiled kernels (include/whisper_mi.h).  Device sizes: both kernels
+// read whole 128-row panels of A whatever M is, so A is allocated zero-filled up to the last panel row; bias, pos, residual and C are
+// touched at valid rows only (gemm_epilogue's valid[]), and the checks below hold every offset the epilogue can form inside the
+// caller's lengths, which are also the device lengths.
+extern "C" int wm_op_gemm_nt_epi(float* C, size_t c_len, const float* A, size_t a_len, const float* W, const float* bias, const float* pos,
+                                 const float* residual, size_t r_len, int M, int N, int K, int batch, long long lda, long long strideA,
+                                 long long ldc, long long strideC, long long ldr, long long strideR, int residual_in_place, int act,
+                                 int gelu_mode, int group_n, long long group_stride, int dtype, int out_dtype, int* kernel_ran) {
+    if (!C || !A || !W || !kernel_ran || M <= 0 || N <= 0 || K <= 0 || batch <= 0) return fail(WM_E_ARG, "bad argument");
+    if (M > (1 << 20) || N > (1 << 16) || K > (1 << 16) || batch > 1024) return fail(WM_E_ARG, "problem too large for the op hook");
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    if (out_dtype != WM_F32 && out_dtype != dtype) return fail(WM_E_ARG, "out_dtype must be WM_F32 or dtype");
+    if (N % 128 || K % 32) return fail(WM_E_ARG, "N must be a multiple of 128 and K of 32");
+    if ((act != 0 && act != 1) || (gelu_mode != 0 && gelu_mode != 1)) return fail(WM_E_ARG, "bad act / gelu_mode");
+    const long long LIM = 1ll << 40;  // keeps every product below int64
+    auto ld_ok = [&](long long v, int unit, bool zero_ok) { return (v > 0 || (zero_ok && v == 0)) && v < LIM && v % unit == 0; };
+    // 16-byte operand loads: 8 sixteen-bit or 4 fp32 elements (8 serves both); 16-byte fp32 / 8-byte 16-bit stores and addend loads: 4
+    if (!ld_ok(lda, 8, false) || !ld_ok(strideA, 8, true) || !ld_ok(ldc, 4, false) || !ld_ok(strideC, 4, true))
+        return fail(WM_E_ARG, "lda / strideA must be multiples of 8, ldc / strideC of 4");
+    if (batch > 1 && (strideA == 0 || strideC == 0)) return fail(WM_E_ARG, "batch > 1 needs strideA and strideC");
+    if (group_n < 0 || group_n % 64 || (group_n > 0 && (N % group_n || !ld_ok(group_stride, 4, false))))
+        return fail(WM_E_ARG, "group_n must be a multiple of 64 that divides N, with a group_stride that is a multiple of 4");
+    const int n_grp = group_n > 0 ? N / group_n : 1, row_w = group_n > 0 ? group_n : N;
+    if (ldc < row_w) return fail(WM_E_ARG, "ldc below the row width");
+    if (residual_in_place) {
+        if (out_dtype != WM_F32) return fail(WM_E_ARG, "residual_in_place needs fp32 output");
+        if (residual || group_n > 0) return fail(WM_E_ARG, "residual_in_place takes no separate residual and no column groups");
+        ldr = ldc;
+        strideR = strideC;
+    } else if (residual) {
+        if (!ld_ok(ldr, 4, false) || !ld_ok(strideR, 4, true) || ldr < N || (batch > 1 && strideR == 0))
+            return fail(WM_E_ARG, "ldr must be a multiple of 4 and >= N, strideR a multiple of 4");
+    }
+    const size_t Mp = panel_rows(M);
+    const size_t a_need = (size_t)(batch - 1) * strideA + (size_t)(M - 1) * lda + K;
+    const size_t a_dev = (size_t)(batch - 1) * strideA + (Mp - 1) * (size_t)lda + K;
+    const size_t c_need = (size_t)(batch - 1) * strideC + (size_t)(n_grp - 1) * (group_n > 0 ? group_stride : 0) + (size_t)(M - 1) * ldc + row_w;
+    const size_t r_need = (size_t)(batch - 1) * strideR + (size_t)(M - 1) * ldr + N;
+    if (a_len < a_need || c_len < c_need || (residual && r_len < r_need)) return fail(WM_E_ARG, "a size overflows the caller's arrays");
+    if (a_len > ((size_t)1 << 31) || c_len > ((size_t)1 << 31) || r_len > ((size_t)1 << 31)) return fail(WM_E_ARG, "array too large for the op hook");
+    TmpDev t;
+    DevBuf &a = t.add(), &w = t.add(), &c = t.add(), &b = t.add(), &ps = t.add(), &r = t.add();
+    GemmParams p{};
+    p.M = M;
+    p.N = N;
+    p.K = K;
+    p.lda = (long)lda;
+    p.ldw = K;
+    p.ldc = (long)ldc;
+    p.strideA = (long)strideA;
+    p.strideC = (long)strideC;
+    p.ldr = (long)ldr;
+    p.strideR = (long)strideR;
+    p.act = act;
+    p.gelu_mode = gelu_mode;
+    p.group_n = group_n;
+    p.group_stride = group_n > 0 ? (long)group_stride : 0;
+    // addend pointers decide the dispatch (the row-panel kernel takes none): non-null placeholders until the uploads below
+    p.bias = bias;
+    p.pos = pos;
+    p.residual = residual_in_place ? C : residual;
+    *kernel_ran = gemm_nt_kernel_for((int)dt_size(dtype), (int)dt_size(out_dtype), p, batch, nullptr);
+    // the device sizes above are worked out for the two tiled kernels only; the ring kernels have hooks of their own
+    if (*kernel_ran != wm::GEMM_NT_DIRECT && *kernel_ran != wm::GEMM_NT_LDS)
+        return fail(WM_E_ARG, "this shape dispatches to the row-panel / full-row kernel (wm_op_matmul_nt, wm_op_ln_matmul_nt, wm_op_mlp_block)");
+    WMCHK(upload_padded(a, A, a_need, a_dev, dtype));  // A: the caller's part, then zeros up to the end of the last 128-row panel
+    WMCHK(upload(w, W, (size_t)N * K, dtype));
+    WMCHK(upload(c, C, c_len, out_dtype));
+    if (bias) WMCHK(upload(b, bias, N, WM_F32));
+    if (pos) WMCHK(upload(ps, pos, (size_t)M * N, WM_F32));
+    if (residual && !residual_in_place) WMCHK(upload(r, residual, r_len, WM_F32));
+    p.A = a.p;
+    p.W = w.p;
+    p.C = c.p;
+    p.bias = bias ? b.as<float>() : nullptr;
+    p.pos = pos ? ps.as<float>() : nullptr;
+    p.residual = residual_in_place ? c.as<float>() : residual ? r.as<float>() : nullptr;
+    WMCHK(gemm_dispatch(dtype, out_dtype, p, batch, nullptr));
+    HIPCHK(hipGetLastError());
+    return download_f32(C, c, c_len, out_dtype);
+}
+
+extern "C" int wm_op_mlp_block(float* x, const float* ln_g, const float* ln_b, const float* fc1_w, const float* fc1_b, const float* fc2_w,
+                               const float* fc2_b, const float* next_g, const float* next_b, float* xn_out, int M, int d, int ffn,
+                               int dtype, int gelu_mode) {
+    if (!x || !ln_g || !ln_b || !fc1_w || !fc1_b || !fc2_w || !fc2_b || M <= 0) return fail(WM_E_ARG, "bad argument");
+    if (d <= 0 || d % 128 || d > 1024 || ffn <= 0 || ffn % 128) return fail(WM_E_ARG, "d and ffn must be multiples of 128 (d <= 1024)");
+    if (dtype < 0 || dtype > 2 || (gelu_mode != 0 && gelu_mode != 1)) return fail(WM_E_ARG, "bad dtype / gelu_mode");
+    const bool want_next = next_g && next_b && xn_out;
+    if (!want_next && (next_g || next_b || xn_out)) return fail(WM_E_ARG, "next_g, next_b and xn_out go together");
+    TmpDev t;
+    hipStream_t st = nullptr;
+    const size_t Mp = panel_rows(M), ts = dt_size(dtype);  // the tile kernels read whole 128-row panels
+    DevBuf &dx = t.add(), &xn = t.add(), &hid = t.add(), &g1 = t.add(), &b1 = t.add(), &w1 = t.add(), &bb1 = t.add(), &w2 = t.add(),
+           &bb2 = t.add(), &g2 = t.add(), &b2 = t.add();
+    WMCHK(upload_padded(dx, x, (size_t)M * d, Mp * d, WM_F32));
+    WMCHK(xn.alloc(Mp * d * ts, true));
+    WMCHK(hid.alloc(Mp * ffn * ts, true));
+    WMCHK(upload(g1, ln_g, d, WM_F32));
+    WMCHK(upload(b1, ln_b, d, WM_F32));
+    WMCHK(upload(w1, fc1_w, (size_t)ffn * d, dtype));
+    WMCHK(upload(bb1, fc1_b, ffn, WM_F32));
+    WMCHK(upload(w2, fc2_w, (size_t)d * ffn, dtype));
+    WMCHK(upload(bb2, fc2_b, d, WM_F32));
+    if (want_next) {
+        WMCHK(upload(g2, next_g, d, WM_F32));
+        WMCHK(upload(b2, next_b, d, WM_F32));
+    }
+    GemmParams f1{};
+    f1.A = xn.p;
+    f1.W = w1.p;
+    f1.C = hid.p;
+    f1.M = M;
+    f1.N = ffn;
+    f1.K = d;
+    f1.lda = d;
+    f1.ldw = d;
+    f1.ldc = ffn;
+    f1.bias = bb1.as<float>();
+    f1.act = 1;
+    f1.gelu_mode = gelu_mode;
+    WMCHK(ln_then_gemm(dtype, dtype, f1, dx.as<float>(), g1.as<float>(), b1.as<float>(), st));
+    GemmParams f2{};
+    f2.A = hid.p;
+    f2.W = w2.p;
+    f2.C = dx.p;
+    f2.M = M;
+    f2.N = d;
+    f2.K = ffn;
+    f2.lda = ffn;
+    f2.ldw = ffn;
+    f2.ldc = d;
+    f2.bias = bb2.as<float>();
+    f2.residual = dx.as<float>();
+    f2.ldr = d;
+    bool fused_next = false;
+    if (want_next && gemm_nt_fuses_layernorm_out(dtype == WM_F32 ? 4 : 2, f2)) {
+        f2.lno_g = g2.as<float>();
+        f2.lno_b = b2.as<float>();
+        f2.lno_out = xn.p;
+        fused_next = true;
+    }
+    WMCHK(gemm_dispatch(dtype, WM_F32, f2, 1, st));
+    if (want_next && !fused_next)
+        DISPATCH_DT(dtype, TT, launch_layernorm_rows<TT>(dx.as<float>(), g2.as<float>(), b2.as<float>(), xn.p, nullptr, M, d, 1e-5f, st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(x, dx.p, (size_t)M * d * 4, hipMemcpyDeviceToHost));
+    if (want_next) WMCHK(download_f32(xn_out, xn, (size_t)M * d, dtype));  // the operand rows as the next GEMM reads them, widened on the host
+    return 0;
+}
+
+extern "C" int wm_op_attention_batch(float* out, const float* q, const float* k, const float* v, int B, int n_ctx, int n_heads, int dtype) {
+    if (!out || !q || !k || !v || B <= 0 || n_ctx <= 0 || n_heads <= 0 || n_heads > 64) return fail(WM_E_ARG, "bad argument");
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    const size_t d = (size_t)n_heads * 64, rows = (size_t)B * n_ctx, n = rows * d;
+    std::vector<float> packed(3 * n);  // the fused projection layout the kernel reads: row = [q | k | v], utterances back to back
+    for (size_t t = 0; t < rows; ++t) {
+        memcpy(&packed[t * 3 * d], q + t * d, d * 4);
+        memcpy(&packed[t * 3 * d + d], k + t * d, d * 4);
+        memcpy(&packed[t * 3 * d + 2 * d], v + t * d, d * 4);
+    }
+    TmpDev t;
+    DevBuf &qkv = t.add(), &o = t.add();
+    WMCHK(upload(qkv, packed.data(), packed.size(), dtype));
+    WMCHK(o.alloc(n * dt_size(dtype), true));
+    DISPATCH_DT(dtype, TT, launch_flash_attn_enc<TT>(qkv.p, o.p, B, n_heads, n_ctx, 0.125f, nullptr));
+    HIPCHK(hipGetLastError());
+    return download_f32(out, o, n, dtype);
+}
+extern "C" int wm_op_attention(float* out, const float* q, const float* k, const float* v, int n_ctx, int n_heads, int dtype) {
+    return wm_op_attention_batch(out, q, k, v, 1, n_ctx, n_heads, dtype);
+}
+
+static int op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
+                               int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo, bool with_lo);
+extern "C" int wm_op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
+                                      int n_chunks, int out_dtype, int q_B, int len, int nq) {
+    return op_attention_cached(out, q, k, v, B, t, n_heads, kv_dtype, n_chunks, out_dtype, q_B, len, nq, nullptr, false);
+}
+extern "C" int wm_op_attention_cached_lo(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
+                                         int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo) {
+    return op_attention_cached(out, q, k, v, B, t, n_heads, kv_dtype, n_chunks, out_dtype, q_B, len, nq, key_lo, true);
+}
+static int op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
+                               int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo, bool with_lo) {
+    if (with_lo && (!key_lo || n_chunks != 1 || nq != 0)) return fail(WM_E_ARG, "key_lo belongs to the single-workgroup forms (n_chunks = 1, nq = 0)");
+    if (!out || !q || !k || !v || B <= 0 || t <= 0 || n_heads <= 0 || n_heads > 16) return fail(WM_E_ARG, "bad argument");
+    if (kv_dtype < 0 || kv_dtype > 2 || out_dtype < 0 || out_dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    if (n_chunks < 1 || (n_chunks > 1 && (n_chunks < (t + 511) / 512 || n_chunks > (t + 31) / 32)))
+        return fail(WM_E_ARG, "n_chunks must be 1, or between ceil(t/512) and ceil(t/32)");
+    if (n_chunks == 1 && t > 512) return fail(WM_E_ARG, "the single-workgroup form serves up to 512 keys (the text context)");
+    if (n_chunks > 64) return fail(WM_E_ARG, "the merge takes up to 64 chunks");
+    if (q_B < 0 || (q_B > 0 && B % q_B)) return fail(WM_E_ARG, "prefill rows are position-major: B must be P * q_B");
+    if (nq != 0 && (nq != 4 || n_chunks == 1 || q_B == 0 || B != 4 * q_B))
+        return fail(WM_E_ARG, "nq must be 0, or 4 with the chunked form and B = 4 * q_B rows");
+    const int P = q_B > 0 ? B / q_B : 1, n_utt = q_B > 0 ? q_B : B;  // k, v hold n_utt utterances of t rows
+    if (n_chunks > 1 && len >= 0) return fail(WM_E_ARG, "len belongs to the single-workgroup form (the chunked form sweeps all t rows)");
+    if (n_chunks == 1 && len < 0 && P > 1) return fail(WM_E_ARG, "the causal prefill form needs len >= 0");
+    if (n_chunks == 1 && len >= 0 && len + P > t) return fail(WM_E_ARG, "the cache must hold len + P rows");
+    const size_t d = (size_t)n_heads * 64, n = (size_t)B * d;
+    TmpDev tmp;
+    DevBuf &dq = tmp.add(), &dk = tmp.add(), &dv = tmp.add(), &po = tmp.add(), &pml = tmp.add(), &o = tmp.add(), &ctl = tmp.add(), &dlo = tmp.add();
+    if (with_lo) {
+        for (int u = 0; u < n_utt; ++u)
+            if (key_lo[u] < 0 || key_lo[u] > t) return fail(WM_E_ARG, "key_lo[%d] = %d outside [0, %d]", u, key_lo[u], t);
+        WMCHK(upload_bytes(dlo, key_lo, (size_t)n_utt * 4));
+    }
+    WMCHK(upload(dq, q, n, WM_F32));
+    WMCHK(upload(dk, k, (size_t)n_utt * t * d, kv_dtype));
+    WMCHK(upload(dv, v, (size_t)n_utt * t * d, kv_dtype));
+    WMCHK(o.alloc(n * dt_size(out_dtype), true));
+    AttnDecParams a{};
+    a.q = dq.as<float>();
+    a.K = dk.p;
+    a.V = dv.p;
+    a.batch_stride = (long)((size_t)t * d);
+    a.scale = 0.125f;
+    a.H = n_heads;
+    a.d = (int)d;
+    a.B = B;
+    a.q_B = q_B;
+    a.nq = nq;
+    if (n_chunks > 1) {
+        WMCHK(po.alloc((size_t)B * n_chunks * d * 4, true));
+        WMCHK(pml.alloc((size_t)B * n_chunks * n_heads * 2 * 4, true));
+        a.n_keys = t;
+        a.nsplit = n_chunks;
+        a.part_o = po.as<float>();
+        a.part_ml = pml.as<float>();
+        WMCHK(attn_decode_dispatch(kv_dtype, a, nullptr));
+        launch_attn_combine(po.as<float>(), pml.as<float>(), o.p, out_dtype, B, n_chunks, n_heads, (int)d, nullptr);
+    } else {
+        StepCtl h{};
+        // the kernel sweeps len + 1 rows (position p of a prefill: len + 1 + p): the cache as it stands after this step's row was appended
+        h.len = len >= 0 ? len : t - 1;
+        WMCHK(upload_bytes(ctl, &h, sizeof h));
+        a.n_keys = -1;
+        a.ctl = ctl.as<StepCtl>();
+        a.nsplit = 1;
+        a.direct_out = o.as<float>();
+        a.out_dtype = out_dtype;
+        WMCHK(attn_decode_dispatch(kv_dtype, a, nullptr, with_lo ? dlo.as<int>() : nullptr));
+    }
+    HIPCHK(hipGetLastError());
+    return download_f32(out, o, n, out_dtype);
+}
+
+// One launch_dec_linear as decode_core wires it: LN1 -> QKV with the cache append, the XT out-projections with the residual in place,
+// LNx -> cross q with the alignment-head capture, LN2 -> fc1 + GELU stored in operand dtype, fc2.
+// cap_map non-null: the capture by row map, cap is [cap_dst][cap_nsel][64] and len / cap_step0 / cap_steps are not used
+static int op_dec_linear(float* out, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
+                         const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
+                         float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
+                         const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel, const int32_t* cap_map = nullptr, int cap_dst = 0,
+                         bool k_long = false) {
+    if (!out || !x || !W || B <= 0 || N <= 0 || K <= 0) return fail(WM_E_ARG, "bad argument");
+    if (dtype < 0 || dtype > 2 || (gelu_mode != 0 && gelu_mode != 1)) return fail(WM_E_ARG, "bad dtype / gelu_mode");
+    if (k_long) {  // wm_op_dec_linear_long: the K-long form alone (16 waves walking groups of k-steps), which has no LayerNorm prologue
+        if (!dec_linear_long_supports_k(K)) return fail(WM_E_ARG, "K must be 3072 or 4096 (the K-long form of the skinny linear)");
+        if (ln_g || ln_b) return fail(WM_E_ARG, "the K-long form has no LayerNorm prologue");
+    } else if (!dec_linear_supports_k(K)) return fail(WM_E_ARG, "K must be a multiple of 32 whose k-steps split over <= 16 waves x <= 4 steps (K <= 2048), or 3072");
+    if (!ln_g != !ln_b) return fail(WM_E_ARG, "ln_g and ln_b go together");
+    if (ln_g && x_is_t) return fail(WM_E_ARG, "the LayerNorm prologue reads fp32 rows (no x_is_t)");
+    if (!kcache != !vcache) return fail(WM_E_ARG, "kcache and vcache go together");
+    if (out_is_t && (residual || kcache)) return fail(WM_E_ARG, "out_is_t is the plain store (no residual, no cache append)");
+    const int d = N / 3;
+    if (kcache) {
+        if (N % 3 || d % 64 || kv_dtype < 0 || kv_dtype > 2 || n_utt <= 0 || cap_rows <= 0 || len < 0)
+            return fail(WM_E_ARG, "QKV mode needs N = 3 * d_model (d_model % 64 == 0), a kv_dtype and a cache [n_utt][cap_rows][d_model]");
+        if (residual) return fail(WM_E_ARG, "QKV mode has no residual");
+        if (kv_B < 0 || (kv_B > 0 ? (kv_B > n_utt || B % kv_B || len + B / kv_B > cap_rows) : (B > n_utt || len + 1 > cap_rows)))
+            return fail(WM_E_ARG, "rows must be P * kv_B with kv_B <= n_utt and len + P <= cap_rows, or <= n_utt with len < cap_rows");
+    }
+    if (cap && cap_map) {
+        if (!cap_sel || cap_dst <= 0 || cap_nsel <= 0 || cap_nsel > 32 || N % 64 || N > 2048 || kcache)
+            return fail(WM_E_ARG, "capture by row map needs cap_sel, cap_dst > 0, N = 64 * heads <= 2048, 1 <= cap_nsel <= 32 (and no cache)");
+        for (int h = 0; h < 32; ++h)
+            if (cap_sel[h] >= cap_nsel || (cap_sel[h] >= 0 && h >= N / 64)) return fail(WM_E_ARG, "cap_sel names a slot >= cap_nsel or a head >= N / 64");
+        for (int r = 0; r < B; ++r)
+            if (cap_map[r] < -1 || cap_map[r] >= cap_dst) return fail(WM_E_ARG, "cap_map[%d] = %d outside [-1, cap_dst = %d)", r, cap_map[r], cap_dst);
+    } else if (cap) {
+        if (!cap_sel || len < 0 || cap_steps <= 0 || cap_nsel <= 0 || cap_nsel > 32 || N % 64 || N > 2048 || (kcache && cap))
+            return fail(WM_E_ARG, "capture needs cap_sel, len >= 0, N = 64 * heads <= 2048, 1 <= cap_nsel <= 32, cap_steps > 0 (and no cache)");
+        for (int h = 0; h < 32; ++h)
+            if (cap_sel[h] >= cap_nsel || (cap_sel[h] >= 0 && h >= N / 64)) return fail(WM_E_ARG, "cap_sel names a slot >= cap_nsel or a head >= N / 64");
+    }
+    TmpDev t;
+    hipStream_t st = nullptr;
+    // the kernel stores whole 16-column tiles (and loads the residual the same way): rows padded to 16 columns
+    const int wout = kcache ? d : N, ldo = (wout + 15) / 16 * 16;
+    const int odt = out_is_t ? dtype : WM_F32;
+    const size_t ncache = kcache ? (size_t)n_utt * cap_rows * d : 0;
+    const size_t ncap = !cap ? 0 : cap_map ? (size_t)cap_dst * cap_nsel * 64 : (size_t)B * cap_steps * cap_nsel * 64;
+    DevBuf &dx = t.add(), &w = t.add(), &b = t.add(), &g = t.add(), &be = t.add(), &o = t.add(), &r = t.add(), &kc = t.add(), &vc = t.add(),
+           &ctl = t.add(), &cp = t.add(), &cm = t.add();
+    WMCHK(upload(dx, x, (size_t)B * K, x_is_t ? dtype : WM_F32));
+    WMCHK(upload(w, W, (size_t)N * K, dtype));
+    if (bias) WMCHK(upload(b, bias, N, WM_F32));
+    if (ln_g) {
+        WMCHK(upload(g, ln_g, K, WM_F32));
+        WMCHK(upload(be, ln_b, K, WM_F32));
+    }
+    WMCHK(o.alloc((size_t)B * ldo * dt_size(odt), true));
+    const bool in_place = residual == out;
+    if (residual) {
+        DevBuf& dst = in_place ? o : r;
+        if (!in_place) WMCHK(r.alloc((size_t)B * ldo * 4, true));
+        HIPCHK(hipMemcpy2D(dst.p, (size_t)ldo * 4, residual, (size_t)N * 4, (size_t)N * 4, B, hipMemcpyHostToDevice));
+    }
+    DecLinearParams p = linear_block(dx.as<float>(), ln_g ? g.as<float>() : nullptr, ln_g ? be.as<float>() : nullptr, w.p, bias ? b.as<float>() : nullptr,
+                                     N, K, B, o.as<float>(), ldo);
+    p.x_is_t = x_is_t;
+    p.out_is_t = out_is_t;
+    p.act = act != 0;
+    p.gelu_mode = gelu_mode;
+    p.residual = residual ? (in_place ? o.as<float>() : r.as<float>()) : nullptr;
+    p.ldr = ldo;
+    if (kcache || (cap && !cap_map)) {
+        StepCtl h{};
+        h.len = len;
+        WMCHK(upload_bytes(ctl, &h, sizeof h));
+        p.ctl = ctl.as<StepCtl>();
+    }
+    if (kcache) {
+        WMCHK(upload(kc, kcache, ncache, kv_dtype));
+        WMCHK(upload(vc, vcache, ncache, kv_dtype));
+        p.kcache = kc.p;
+        p.vcache = vc.p;
+        p.kv_batch_stride = (long)((size_t)cap_rows * d);
+        p.d_model = d;
+        p.kv_dtype = kv_dtype;
+        p.kv_B = kv_B;
+    }
+    if (cap) {
+        WMCHK(upload(cp, cap, ncap, WM_F32));
+        p.cap = cp.as<float>();
+        p.cap_row_stride = (long)cap_steps * cap_nsel * 64;
+        p.cap_step0 = cap_step0;
+        p.cap_steps = cap_steps;
+        p.cap_nsel = cap_nsel;
+        memcpy(p.cap_sel, cap_sel, 32);
+        if (cap_map) {
+            WMCHK(upload_bytes(cm, cap_map, (size_t)B * 4));
+            p.cap_map = cm.as<int>();
+        }
+    }
+    WMCHK(dec_linear_dispatch(dtype, p, st));
+    HIPCHK(hipGetLastError());
+    WMCHK(download_f32_rows(out, o, B, wout, ldo, odt));
+    if (kcache) {
+        WMCHK(download_f32(kcache, kc, ncache, kv_dtype));
+        WMCHK(download_f32(vcache, vc, ncache, kv_dtype));
+    }
+    if (cap) HIPCHK(hipMemcpy(cap, cp.p, ncap * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int wm_op_dec_linear(float* out, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
+                                const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
+                                float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
+                                const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel) {
+    return op_dec_linear(out, x, W, bias, ln_g, ln_b, residual, B, N, K, dtype, x_is_t, out_is_t, act, gelu_mode, kcache, vcache, n_utt, cap_rows,
+                         kv_dtype, kv_B, len, cap, cap_sel, cap_step0, cap_steps, cap_nsel);
+}
+// The K-long form of the same launch (fc2 of d_model 768 / 1024): K = 3072 or 4096, no LayerNorm prologue.  wm_op_dec_linear keeps
+// refusing K = 4096; K = 3072 runs the same kernel through either hook.
+extern "C" int wm_op_dec_linear_long(float* out, const float* x, const float* W, const float* bias, const float* ln_g, const float* ln_b,
+                                     const float* residual, int B, int N, int K, int dtype, int x_is_t, int out_is_t, int act, int gelu_mode,
+                                     float* kcache, float* vcache, int n_utt, int cap_rows, int kv_dtype, int kv_B, int len, float* cap,
+                                     const int8_t* cap_sel, int cap_step0, int cap_steps, int cap_nsel) {
+    return op_dec_linear(out, x, W, bias, ln_g, ln_b, residual, B, N, K, dtype, x_is_t, out_is_t, act, gelu_mode, kcache, vcache, n_utt, cap_rows,
+                         kv_dtype, kv_B, len, cap, cap_sel, cap_step0, cap_steps, cap_nsel, nullptr, 0, true);
+}
+// LNx -> cross q as an align pass wires it: B input rows, cap [cap_dst][cap_nsel][64] in and out, cap_map [B] in [-1, cap_dst)
+extern "C" int wm_op_dec_linear_capmap(float* out, float* cap, const float* x, const float* W, const float* bias, const float* ln_g,
+                                       const float* ln_b, int B, int N, int K, int dtype, const int8_t* cap_sel, int cap_nsel,
+                                       const int32_t* cap_map, int cap_dst) {
+    if (!cap || !cap_map) return fail(WM_E_ARG, "bad argument");
+    return op_dec_linear(out, x, W, bias, ln_g, ln_b, nullptr, B, N, K, dtype, 0, 0, 0, 0, nullptr, nullptr, 0, 0, 0, 0, 0, cap, cap_sel, 0, 0,
+                         cap_nsel, cap_map, cap_dst);
+}
+
+// The decode step's final LayerNorm + tied-embedding logits and its fused argmax, wired as decode_core (Logits::full) and
+// argmax_peek wire them: launch_dec_logits picks the kernel variant from (dtype, K, B), argmax_step reduces its partials.
+// logprob non-null: the LP instantiation of the same kernel variant, and the chosen ids' log-probabilities [B] (wm_op_logits_lp)
+static int op_logits(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                     const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype, const uint32_t* seen = nullptr,
+                     const uint32_t* ban = nullptr, float penalty = 1.f, const uint32_t* hit = nullptr, const int32_t* slot_id = nullptr,
+                     int n_slots = 0, const float* slot_bias = nullptr, const int32_t* slot_flags = nullptr) {
+    if (!logits || !ids || !x || !ln_g || !ln_b || !emb || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
+    WMCHK(vocab_k_check(K));
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    if (ranges && (timestamp_begin <= 0 || timestamp_begin >= N)) return fail(WM_E_ARG, "ranges need 0 < timestamp_begin < N");
+    TmpDev t;
+    hipStream_t st = nullptr;
+    const int ldo = (N + 3) / 4 * 4, npart = dec_logits_parts(N);  // the kernel stores whole float4 groups below ldo
+    const float* dx;
+    VocabHead vh;
+    WMCHK(upload_vocab_head(t, x, ln_g, ln_b, emb, B, N, K, dtype, &dx, &vh));
+    DevBuf &mk = t.add(), &o = t.add(), &av = t.add(), &ai = t.add(), &tst = t.add(), &tv = t.add(), &ti = t.add(), &tm = t.add(), &ts = t.add(),
+           &nx = t.add(), &ls = t.add(), &ln = t.add();
+    if (mask) WMCHK(upload(mk, mask, N, WM_F32));
+    WMCHK(o.alloc((size_t)B * ldo * 4, true));
+    WMCHK(av.alloc((size_t)B * npart * 4, true));
+    WMCHK(ai.alloc((size_t)B * npart * 4, true));
+    WMCHK(nx.alloc((size_t)B * 4, true));
+    if (logprob) {
+        WMCHK(ls.alloc((size_t)B * npart * 4, true));
+        WMCHK(ln.alloc((size_t)B * 4, true));
+    }
+    TsRules rules{};
+    if (ranges) {
+        std::vector<TsState> h(B);
+        for (int b = 0; b < B; ++b) {
+            h[b] = TsState{};
+            h[b].n_gen = 1;
+            h[b].t_last = -1;
+            h[b].text_lo = ranges[4 * b];
+            h[b].text_hi = ranges[4 * b + 1];
+            h[b].ts_lo = ranges[4 * b + 2];
+            h[b].ts_hi = ranges[4 * b + 3];
+        }
+        WMCHK(upload_bytes(tst, h.data(), (size_t)B * sizeof(TsState)));
+        for (DevBuf* d : {&tv, &ti, &tm, &ts}) WMCHK(d->alloc((size_t)B * npart * 4, true));
+        rules.tb = timestamp_begin;
+        rules.eos = timestamp_begin;
+        rules.max_init = -1;
+        rules.vocab = N;
+    }
+    DecLinearParams p = linear_block(dx, vh.ln_g, vh.ln_b, vh.emb, nullptr, N, K, B, o.as<float>(), ldo);
+    p.amax_val = av.as<float>();
+    p.amax_idx = ai.as<int>();
+    p.amax_stride = npart;
+    p.amax_mask = mask ? mk.as<float>() : nullptr;
+    if (ranges) {
+        p.ts_state = tst.as<TsState>();
+        p.ts_begin = timestamp_begin;
+        p.ts_val = tv.as<float>();
+        p.ts_idx = ti.as<int>();
+        p.ts_m = tm.as<float>();
+        p.ts_s = ts.as<float>();
+    }
+    if (logprob) p.lp_s = ls.as<float>();
+    if (seen) {  // wm_op_logits_processed: the rows' sets as given, the RP instantiation of the same kernel variant
+        DevBuf &ds = t.add(), &db = t.add(), &dc = t.add();
+        const size_t words = (size_t)repeat_words(N);
+        const RepeatCtl ctl{penalty, 0};
+        WMCHK(upload_bytes(ds, seen, B * words * 4));
+        WMCHK(upload_bytes(db, ban, B * words * 4));
+        WMCHK(upload_bytes(dc, &ctl, sizeof(ctl)));
+        p.rp_seen = ds.as<unsigned>();
+        p.rp_ban = db.as<unsigned>();
+        p.rp_ctl = dc.as<RepeatCtl>();
+        p.rp_words = (int)words;
+        if (hit) {  // wm_op_logits_seq_bias: the rows' hit bits and slots as given, the SB instantiation of the same kernel variant
+            DevBuf &dh = t.add(), &dv = t.add(), &di = t.add(), &dt = t.add();
+            std::vector<int32_t> h_of((size_t)N, -1);
+            for (int k = 0; k < n_slots; ++k) h_of[slot_id[k]] = k;
+            std::vector<SeqSlot> h((size_t)B * SEQ_BIAS_MAX, SeqSlot{0.f, 0});
+            for (int b = 0; b < B; ++b)
+                for (int k = 0; k < n_slots; ++k) h[(size_t)b * SEQ_BIAS_MAX + k] = SeqSlot{slot_bias[(size_t)b * n_slots + k], slot_flags[(size_t)b * n_slots + k]};
+            SeqBiasCtl sc{};
+            sc.n_slots = n_slots;
+            sc.eot = -1;
+            WMCHK(upload_bytes(dh, hit, B * words * 4));
+            WMCHK(upload_bytes(dv, h.data(), h.size() * sizeof(SeqSlot)));
+            WMCHK(upload_bytes(di, h_of.data(), (size_t)N * 4));
+            sc.slot_of = di.as<int>();
+            WMCHK(upload_bytes(dt, &sc, sizeof(sc)));
+            p.sb_hit = dh.as<unsigned>();
+            p.sb_val = dv.as<SeqSlot>();
+            p.sb_ctl = dt.as<SeqBiasCtl>();
+        }
+    }
+    int lrc = 0;
+    DISPATCH_DT(dtype, TT, lrc = launch_dec_logits<TT>(p, st));
+    LCHK(lrc);
+    ArgmaxParams a{};
+    if (logprob) {
+        a.lp_s = ls.as<float>();
+        a.lp_next = ln.as<float>();
+    }
+    if (ranges) {
+        a.ts_state = tst.as<TsState>();
+        a.rules = rules;
+        a.ts_val = tv.as<float>();
+        a.ts_idx = ti.as<int>();
+        a.ts_m = tm.as<float>();
+        a.ts_s = ts.as<float>();
+        a.ts_part0 = timestamp_begin / dec_logits_ids_per_part(N);
+    }
+    a.logits = o.as<float>();
+    a.ldl = ldo;
+    a.V = N;
+    a.B = B;
+    a.pval = av.as<float>();
+    a.pidx = ai.as<int>();
+    a.npart = npart;
+    a.next = nx.as<int>();
+    launch_argmax_step(a, st);
+    HIPCHK(hipGetLastError());
+    WMCHK(download_f32_rows(logits, o, B, N, ldo, WM_F32));
+    HIPCHK(hipMemcpy(ids, nx.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    if (logprob) HIPCHK(hipMemcpy(logprob, ln.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int wm_op_logits(float* logits, int32_t* ids, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                            const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
+    return op_logits(logits, ids, nullptr, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype);
+}
+extern "C" int wm_op_logits_lp(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                               const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype) {
+    if (!logprob) return fail(WM_E_ARG, "bad argument");
+    return op_logits(logits, ids, logprob, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype);
+}
+// The same two launches with the repetition processors on given sets: seen / ban [B][ceil(N / 32)], bit (id & 31) of word
+// id >> 5.  logprob null: the instantiation without log-probabilities.
+extern "C" int wm_op_logits_processed(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b,
+                                      const float* emb, const float* mask, const int32_t* ranges, int timestamp_begin, const uint32_t* seen,
+                                      const uint32_t* ban, float penalty, int B, int N, int K, int dtype) {
+    if (!seen || !ban || !(penalty > 0.f)) return fail(WM_E_ARG, "bad argument");
+    return op_logits(logits, ids, logprob, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype, seen, ban, penalty);
+}
+// Forced-token replay, shared by wm_op_repeat_sets and wm_op_seq_bias_hits: repeat_init on each row's prompt tokens[b][0 ..
+// prompt_len[b]), then one argmax launch per step that is handed the row's next id of the table as its only candidate, so it appends
+// exactly that id — rows end at n_ids[b] (a row past its end is `finished` and does nothing).
+static int replay_rows_check(const int32_t* tokens, const int32_t* prompt_len, const int32_t* n_ids, int B, int stride, int vocab) {
+    for (int b = 0; b < B; ++b) {
+        if (prompt_len[b] < 1 || prompt_len[b] > n_ids[b] || n_ids[b] > stride) return fail(WM_E_ARG, "row %d: need 1 <= prompt_len <= n_ids <= stride", b);
+        for (int i = 0; i < n_ids[b]; ++i)
+            if (tokens[(size_t)b * stride + i] < 0 || tokens[(size_t)b * stride + i] >= vocab) return fail(WM_E_ARG, "token id out of range");
+    }
+    return 0;
+}
+// extra: the hook's own fields of every step's ArgmaxParams.  init(r): the hook's launch behind repeat_init, on the same prompt
+// buffers.  fetch(s, seen, ban): copies entry s out — 0 after the init, s after step s.
+template <typename Init, typename Fetch>
+static int replay_forced(TmpDev& t, const int32_t* tokens, const int32_t* prompt_len, const int32_t* n_ids, int B, int stride, int vocab, int ngram,
+                         int steps, const ArgmaxParams& extra, Init init, Fetch fetch) {
+    hipStream_t st = nullptr;
+    const size_t words = (size_t)repeat_words(vocab), set_bytes = (size_t)B * words * 4;
+    DevBuf &ds = t.add(), &db = t.add(), &dc = t.add(), &out = t.add(), &nt = t.add(), &fin = t.add(), &ctl = t.add(), &pv = t.add(), &pi = t.add(),
+           &nx = t.add(), &pos = t.add();
+    WMCHK(ds.alloc(set_bytes));
+    WMCHK(db.alloc(set_bytes));
+    WMCHK(dc.alloc(sizeof(RepeatCtl)));
+    WMCHK(fin.alloc((size_t)B * 4, true));
+    WMCHK(ctl.alloc(sizeof(StepCtl), true));
+    WMCHK(pv.alloc((size_t)B * 4, true));  // one partial per row: value 0, index = the id to append
+    WMCHK(pi.alloc((size_t)B * 4));
+    WMCHK(nx.alloc((size_t)B * 4));
+    WMCHK(pos.alloc((size_t)B * 4, true));
+    std::vector<int32_t> h_out((size_t)B * stride, 0), h_idx(B), h_fin(B);
+    for (int b = 0; b < B; ++b) std::copy(tokens + (size_t)b * stride, tokens + (size_t)b * stride + prompt_len[b], h_out.begin() + (size_t)b * stride);
+    WMCHK(upload_bytes(out, h_out.data(), h_out.size() * 4));
+    WMCHK(upload_bytes(nt, prompt_len, (size_t)B * 4));
+    RepeatInitParams r{};
+    r.seen = ds.as<unsigned>();
+    r.ban = db.as<unsigned>();
+    r.words = (int)words;
+    r.B = B;
+    r.ctl = dc.as<RepeatCtl>();
+    r.penalty = 1.f;
+    r.ngram = ngram;
+    r.out_tokens = out.as<int>();
+    r.out_stride = stride;
+    r.n_tokens = nt.as<int>();
+    launch_repeat_init(r, st);
+    WMCHK(init(r));
+    HIPCHK(hipGetLastError());
+    WMCHK(fetch(0, ds, db));
+    for (int s = 1; s <= steps; ++s) {
+        for (int b = 0; b < B; ++b) {
+            const int at = prompt_len[b] + s - 1;
+            h_fin[b] = at >= n_ids[b];
+            h_idx[b] = h_fin[b] ? 0 : tokens[(size_t)b * stride + at];
+        }
+        HIPCHK(hipMemcpy(pi.p, h_idx.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(fin.p, h_fin.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+        ArgmaxParams a = extra;
+        a.V = vocab;
+        a.B = B;
+        a.pval = pv.as<float>();
+        a.pidx = pi.as<int>();
+        a.npart = 1;
+        a.next = nx.as<int>();
+        a.out_tokens = out.as<int>();
+        a.out_stride = stride;
+        a.n_tokens = nt.as<int>();
+        a.finished = fin.as<int>();
+        a.ctl = ctl.as<StepCtl>();
+        a.pos = pos.as<int>();
+        a.eot = -1;
+        a.ignore_eot = 1;
+        a.rp_seen = ds.as<unsigned>();
+        a.rp_ban = db.as<unsigned>();
+        a.rp_ctl = dc.as<RepeatCtl>();
+        a.rp_words = (int)words;
+        LCHK(launch_argmax_step(a, st));
+        HIPCHK(hipGetLastError());
+        WMCHK(fetch(s, ds, db));
+    }
+    return 0;
+}
+// The sets' bookkeeping alone, replayed.  seen / ban: [steps + 1][B][ceil(vocab / 32)], entry 0 after the init, entry s after step s.
+extern "C" int wm_op_repeat_sets(uint32_t* seen, uint32_t* ban, const int32_t* tokens, const int32_t* prompt_len, const int32_t* n_ids, int B,
+                                 int stride, int vocab, int ngram, int steps) {
+    if (!seen || !ban || !tokens || !prompt_len || !n_ids || B <= 0 || stride <= 0 || vocab <= 0 || steps < 0) return fail(WM_E_ARG, "bad argument");
+    if (ngram < 0 || ngram > REPEAT_NGRAM_MAX) return fail(WM_E_ARG, "no_repeat_ngram_size %d outside [0, %d]", ngram, REPEAT_NGRAM_MAX);
+    WMCHK(replay_rows_check(tokens, prompt_len, n_ids, B, stride, vocab));
+    TmpDev t;
+    const size_t set_words = (size_t)B * repeat_words(vocab);
+    auto fetch = [&](int s, const DevBuf& ds, const DevBuf& db) -> int {
+        HIPCHK(hipMemcpy(seen + s * set_words, ds.p, set_words * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ban + s * set_words, db.p, set_words * 4, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    return replay_forced(t, tokens, prompt_len, n_ids, B, stride, vocab, ngram, steps, ArgmaxParams{}, [](const RepeatInitParams&) { return 0; }, fetch);
+}
+// The same two launches with sequence bias / bad words on given hit state: hit [B][ceil(N / 32)], the slots' ids
+// (ascending) and, per row and slot, the summed bias and the flags (bit 0 on, bit 1 ban).  seen / ban / penalty as above.
+extern "C" int wm_op_logits_seq_bias(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b,
+                                     const float* emb, const float* mask, const int32_t* ranges, int timestamp_begin, const uint32_t* seen,
+                                     const uint32_t* ban, float penalty, const uint32_t* hit, const int32_t* slot_id, int n_slots,
+                                     const float* slot_bias, const int32_t* slot_flags, int B, int N, int K, int dtype) {
+    if (!seen || !ban || !(penalty > 0.f) || !hit || !slot_id || !slot_bias || !slot_flags || n_slots < 1 || n_slots > SEQ_BIAS_MAX)
+        return fail(WM_E_ARG, "bad argument");
+    for (int k = 0; k < n_slots; ++k)
+        if (slot_id[k] < 0 || slot_id[k] >= N || (k && slot_id[k] <= slot_id[k - 1])) return fail(WM_E_ARG, "slot ids must ascend inside the vocabulary");
+    // the kernel looks a set bit's slot up without a check (the drivers set a bit only for a slot's id): refuse any other bit here
+    if (B > 0 && N > 0) {
+        std::vector<char> is_slot((size_t)N, 0);
+        for (int k = 0; k < n_slots; ++k) is_slot[slot_id[k]] = 1;
+        const int words = repeat_words(N);
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t < words * 32; ++t)
+                if ((hit[(size_t)b * words + (t >> 5)] >> (t & 31) & 1u) && (t >= N || !is_slot[t])) return fail(WM_E_ARG, "row %d: hit bit %d has no slot", b, t);
+    }
+    return op_logits(logits, ids, logprob, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype, seen, ban, penalty, hit, slot_id, n_slots,
+                     slot_bias, slot_flags);
+}
+// The hit state's bookkeeping alone, as wm_op_repeat_sets runs the sets': seq_bias_init on each row's prompt, then one argmax launch
+// per step that appends the row's next id of the table.  The table is built from the two lists as wm_set_sequence_bias builds it (same
+// refusals).  slot_id [n_seq + n_bad] and *n_slots: the table's slots; hit [steps + 1][B][ceil(vocab / 32)], slot_bias / slot_flags
+// [steps + 1][B][n_seq + n_bad] (the first *n_slots of each row are written) — entry 0 after the init, entry s after step s.
+extern "C" int wm_op_seq_bias_hits(uint32_t* hit, float* slot_bias, int32_t* slot_flags, int32_t* slot_id, int32_t* n_slots, const int32_t* tokens,
+                                   const int32_t* prompt_len, const int32_t* n_ids, int B, int stride, int vocab, int eot, const int32_t* seq_ids,
+                                   const int32_t* seq_off, const float* seq_bias, int n_seq, const int32_t* bad_ids, const int32_t* bad_off, int n_bad,
+                                   int steps) {
+    if (!hit || !slot_bias || !slot_flags || !slot_id || !n_slots || !tokens || !prompt_len || !n_ids || B <= 0 || stride <= 0 || vocab <= 0 || steps < 0)
+        return fail(WM_E_ARG, "bad argument");
+    WMCHK(replay_rows_check(tokens, prompt_len, n_ids, B, stride, vocab));
+    std::shared_ptr<SeqTable> tab;
+    std::vector<int32_t> sid;
+    WMCHK(build_seq_table(tab, vocab, seq_ids, seq_off, seq_bias, n_seq, bad_ids, bad_off, n_bad, &sid));
+    if (!tab) return fail(WM_E_ARG, "both lists are empty");
+    const int cap = n_seq + n_bad, ns = tab->n_slots;
+    *n_slots = ns;
+    std::copy(sid.begin(), sid.end(), slot_id);
+    TmpDev t;
+    const size_t words = (size_t)repeat_words(vocab), set_bytes = (size_t)B * words * 4;
+    DevBuf &dh = t.add(), &dv = t.add(), &dsc = t.add();
+    WMCHK(dh.alloc(set_bytes));
+    WMCHK(dv.alloc((size_t)B * SEQ_BIAS_MAX * sizeof(SeqSlot), true));
+    WMCHK(dsc.alloc(sizeof(SeqBiasCtl)));
+    ArgmaxParams extra{};
+    extra.sb_hit = dh.as<unsigned>();
+    extra.sb_val = dv.as<SeqSlot>();
+    extra.sb_ctl = dsc.as<SeqBiasCtl>();
+    auto init = [&](const RepeatInitParams& r) -> int {
+        SeqBiasInitParams q{};
+        q.hit = dh.as<unsigned>();
+        q.val = dv.as<SeqSlot>();
+        q.words = (int)words;
+        q.B = B;
+        q.ctl = dsc.as<SeqBiasCtl>();
+        q.table = tab->ctl(eot);
+        q.out_tokens = r.out_tokens;
+        q.out_stride = stride;
+        q.n_tokens = r.n_tokens;
+        LCHK(launch_seq_bias_init(q, nullptr));
+        return 0;
+    };
+    std::vector<SeqSlot> h_val((size_t)B * SEQ_BIAS_MAX);
+    auto fetch = [&](int s, const DevBuf&, const DevBuf&) -> int {
+        HIPCHK(hipMemcpy(hit + (size_t)s * B * words, dh.p, set_bytes, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h_val.data(), dv.p, h_val.size() * sizeof(SeqSlot), hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b)
+            for (int k = 0; k < ns; ++k) {
+                slot_bias[((size_t)s * B + b) * cap + k] = h_val[(size_t)b * SEQ_BIAS_MAX + k].bias;
+                slot_flags[((size_t)s * B + b) * cap + k] = h_val[(size_t)b * SEQ_BIAS_MAX + k].flags;
+            }
+        return 0;
+    };
+    return replay_forced(t, tokens, prompt_len, n_ids, B, stride, vocab, 0, steps, extra, init, fetch);
+}
+
+// The no-speech probe's launches on the kernel variant wm_op_logits_lp would pick for (dtype, K, B): the LP sweep with
+// no mask and no ranges, then no_speech_finish_kernel.  prob[b] = softmax(logits[b])[token], lse[b] = logsumexp(logits[b]).
+extern "C" int wm_op_no_speech(float* prob, float* lse, const float* x, const float* ln_g, const float* ln_b, const float* emb, int B, int N, int K,
+                               int dtype, int token) {
+    if (!prob || !lse || !x || !ln_g || !ln_b || !emb || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
+    WMCHK(vocab_k_check(K));
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    if (token < 0 || token >= N) return fail(WM_E_ARG, "token %d is not a vocabulary id", token);
+    TmpDev t;
+    const int npart = dec_logits_parts(N);
+    const float* dx;
+    VocabHead vh;
+    WMCHK(upload_vocab_head(t, x, ln_g, ln_b, emb, B, N, K, dtype, &dx, &vh));
+    DevBuf &pm = t.add(), &pi = t.add(), &ps = t.add(), &pr = t.add(), &ls = t.add();
+    for (DevBuf* d : {&pm, &pi, &ps}) WMCHK(d->alloc((size_t)B * npart * 4, true));
+    WMCHK(pr.alloc((size_t)B * 4, true));
+    WMCHK(ls.alloc((size_t)B * 4, true));
+    WMCHK(ns_sweep(dtype, dx, vh, B, npart, pm.as<float>(), pi.as<int>(), ps.as<float>(), token, pr.as<float>(), ls.as<float>(), nullptr));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(prob, pr.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lse, ls.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// lang_detect_kernel alone, launched as the language pass launches it (no patch).
+extern "C" int wm_op_lang_detect(int32_t* lang_out, float* probs, const float* x, const float* ln_g, const float* ln_b, const float* emb,
+                                 const int32_t* lang_ids, int n_lang, int B, int N, int K, int dtype) {
+    if (!lang_out || !x || !ln_g || !ln_b || !emb || !lang_ids || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
+    WMCHK(vocab_k_check(K));
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    WMCHK(lang_list_check(N, lang_ids, n_lang));
+    TmpDev t;
+    const float* dx;
+    VocabHead vh;
+    WMCHK(upload_vocab_head(t, x, ln_g, ln_b, emb, B, N, K, dtype, &dx, &vh));
+    DevBuf &li = t.add(), &lo = t.add(), &pr = t.add();
+    WMCHK(upload_bytes(li, lang_ids, (size_t)n_lang * 4));
+    WMCHK(lo.alloc((size_t)B * 4, true));
+    WMCHK(pr.alloc((size_t)B * n_lang * 4, true));
+    LangDetectParams q{};
+    q.x = dx;
+    q.ldx = K;
+    q.ln_g = vh.ln_g;
+    q.ln_b = vh.ln_b;
+    q.emb = vh.emb;
+    q.lang_ids = li.as<int>();
+    q.n_lang = n_lang;
+    q.K = K;
+    q.B = B;
+    q.lang_out = lo.as<int>();
+    q.probs = pr.as<float>();
+    DISPATCH_DT(dtype, TT, launch_lang_detect<TT>(q, nullptr));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(lang_out, lo.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    if (probs) HIPCHK(hipMemcpy(probs, pr.p, (size_t)B * n_lang * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The absorbed cross-attention of m->xattn models, wired as launch_cross_attn + cross_attn_merge wire it: absorb, X sweep, merge.
+extern "C" int wm_op_xattn(float* out, const float* q, const float* Wk, const float* Wv, const float* bv, const float* X, int rows,
+                           int q_B, int n_utt, int n_keys, int n_heads, int nsplit, int out_dtype) {
+    if (!out || !q || !Wk || !Wv || !bv || !X || rows <= 0 || n_utt <= 0 || n_keys <= 0) return fail(WM_E_ARG, "bad argument");
+    if (n_heads < 1 || n_heads > 8 || nsplit < 1 || nsplit > 64) return fail(WM_E_ARG, "needs 1 <= n_heads <= 8, 1 <= nsplit <= 64");
+    if (out_dtype != WM_F32 && out_dtype != WM_BF16) return fail(WM_E_ARG, "out_dtype must be WM_F32 or WM_BF16");
+    if (q_B < 0 || (q_B > 0 ? (q_B > n_utt || rows % q_B) : rows > n_utt))
+        return fail(WM_E_ARG, "rows must be P * q_B with q_B <= n_utt (prefill), or <= n_utt (q_B == 0)");
+    const size_t d = (size_t)n_heads * 64;
+    TmpDev t;
+    hipStream_t st = nullptr;
+    DevBuf &dq = t.add(), &wk = t.add(), &wv = t.add(), &b = t.add(), &dx = t.add(), &qs = t.add(), &py = t.add(), &pml = t.add(),
+           &o = t.add();
+    WMCHK(upload(dq, q, (size_t)rows * d, WM_F32));
+    WMCHK(upload(wk, Wk, d * d, WM_BF16));
+    WMCHK(upload(wv, Wv, d * d, WM_BF16));
+    WMCHK(upload(b, bv, d, WM_F32));
+    WMCHK(upload(dx, X, (size_t)n_utt * n_keys * d, WM_BF16));
+    WMCHK(qs.alloc((size_t)rows * 3 * n_heads * d * 2, true));
+    WMCHK(py.alloc((size_t)rows * nsplit * n_heads * d * 4, true));
+    WMCHK(pml.alloc((size_t)rows * nsplit * n_heads * 2 * 4, true));
+    WMCHK(o.alloc((size_t)rows * d * dt_size(out_dtype), true));
+    XAttnParams x{};
+    x.q = dq.as<float>();
+    x.Wk = wk.p;
+    x.Wv = wv.p;
+    x.bv = b.as<float>();
+    x.X = dx.p;
+    x.x_stride = (long)((size_t)n_keys * d);
+    x.n_keys = n_keys;
+    x.nsplit = nsplit;
+    x.H = n_heads;
+    x.d = (int)d;
+    x.rows = rows;
+    x.q_B = q_B;
+    x.scale = ATTN_SCALE;
+    x.qs = qs.p;
+    x.part_y = py.as<float>();
+    x.part_ml = pml.as<float>();
+    x.out = o.p;
+    x.out_dtype = out_dtype;
+    LCHK(launch_xattn_absorb(x, st));
+    LCHK(launch_xattn(x, st));
+    LCHK(launch_xattn_merge(x, st));
+    HIPCHK(hipGetLastError());
+    return download_f32(out, o, (size_t)rows * d, out_dtype);
+}
+
+// xattn_absorb_kernel alone: the three bf16 images of q' as the X sweep reads them
+extern "C" int wm_op_xattn_absorb(float* images, const float* q, const float* Wk, int rows, int n_heads, int late_loads) {
+    if (!images || !q || !Wk || rows <= 0) return fail(WM_E_ARG, "bad argument");
+    if (n_heads < 1 || n_heads > 8) return fail(WM_E_ARG, "needs 1 <= n_heads <= 8");
+    const size_t d = (size_t)n_heads * 64, n = (size_t)rows * 3 * n_heads * d;
+    TmpDev t;
+    DevBuf &dq = t.add(), &wk = t.add(), &qs = t.add();
+    WMCHK(upload(dq, q, (size_t)rows * d, WM_F32));
+    WMCHK(upload(wk, Wk, d * d, WM_BF16));
+    WMCHK(qs.alloc(n * 2, true));
+    XAttnParams x{};
+    x.q = dq.as<float>();
+    x.Wk = wk.p;
+    x.n_keys = 1;  // (not read by the absorb; the launch check wants a key)
+    x.nsplit = 1;
+    x.H = n_heads;
+    x.d = (int)d;
+    x.rows = rows;
+    x.scale = ATTN_SCALE;
+    x.qs = qs.p;
+    LCHK(launch_xattn_absorb(x, nullptr, late_loads != 0));
+    HIPCHK(hipGetLastError());
+    return download_f32(images, qs, n, WM_BF16);
+}
+
+extern "C" int wm_op_gelu(float* tt, size_t n, int mode) {
+    if (!tt || (mode != 0 && mode != 1)) return fail(WM_E_ARG, "bad argument");
+    if (n == 0) return 0;
+    TmpDev t;
+    DevBuf& x = t.add();
+    WMCHK(upload(x, tt, n, WM_F32));
+    launch_gelu(x.as<float>(), n, mode, nullptr);
+    HIPCHK(hipMemcpy(tt, x.p, n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int wm_op_softmax_rows(float* tt, int rows, int cols) {
+    if (!tt || rows <= 0 || cols <= 0) return fail(WM_E_ARG, "bad argument");
+    TmpDev t;
+    DevBuf& x = t.add();
+    WMCHK(upload(x, tt, (size_t)rows * cols, WM_F32));
+    launch_softmax_rows(x.as<float>(), rows, cols, nullptr);
+    HIPCHK(hipMemcpy(tt, x.p, (size_t)rows * cols * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int wm_op_argmax(const float* tt, int n, int32_t* idx) {
+    if (!tt || !idx || n <= 0) return fail(WM_E_ARG, "bad argument");
+    TmpDev t;
+    DevBuf &x = t.add(), &o = t.add();
+    WMCHK(upload(x, tt, n, WM_F32));
+    WMCHK(o.alloc(4));
+    launch_argmax_plain(x.as<float>(), n, o.as<int>(), nullptr);
+    HIPCHK(hipMemcpy(idx, o.p, 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int wm_op_conv1d_k3(float* out, const float* inp, const float* weight, const float* bias, int C_in, int L_in,
+                               int C_out, int stride, int out_T, int dtype) {
+    if (!out || !inp || !weight || !bias || C_in <= 0 || L_in <= 0 || C_out <= 0) return fail(WM_E_ARG, "bad argument");
+    if (stride != 1 && stride != 2) return fail(WM_E_ARG, "stride must be 1 or 2");
+    if (C_out % 128) return fail(WM_E_ARG, "C_out must be a multiple of 128");
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    const int Cp = (C_in + 31) / 32 * 32;
+    const int L_out = (L_in + 2 - 3) / stride + 1;
+    TmpDev t;
+    DevBuf &x = t.add(), &xt = t.add(), &w = t.add(), &b = t.add(), &o = t.add(), &o2 = t.add();
+    WMCHK(upload(x, inp, (size_t)C_in * L_in, WM_F32));
+    WMCHK(xt.alloc(((size_t)L_in + 2 + 512) * Cp * dt_size(dtype), true));
+    auto wr = conv_relayout(weight, C_out, C_in, Cp);
+    WMCHK(upload(w, wr.data(), wr.size(), dtype));
+    WMCHK(upload(b, bias, C_out, WM_F32));
+    WMCHK(o.alloc((size_t)L_out * C_out * 4));
+    DISPATCH_DT(dtype, TT, launch_mel_transpose_pad<TT>(x.as<float>(), xt.p, 1, C_in, L_in, Cp, nullptr));
+    GemmParams p{};
+    p.A = xt.p;
+    p.W = w.p;
+    p.C = o.p;
+    p.M = L_out;
+    p.N = C_out;
+    p.K = 3 * Cp;
+    p.lda = (long)stride * Cp;
+    p.ldw = 3 * Cp;
+    p.ldc = C_out;
+    p.bias = b.as<float>();
+    WMCHK(gemm_dispatch(dtype, WM_F32, p, 1, nullptr));
+    if (out_T) {
+        HIPCHK(hipMemcpy(out, o.p, (size_t)L_out * C_out * 4, hipMemcpyDeviceToHost));
+    } else {
+        WMCHK(o2.alloc((size_t)L_out * C_out * 4));
+        launch_transpose_f32(o.as<float>(), o2.as<float>(), L_out, C_out, nullptr);
+        HIPCHK(hipMemcpy(out, o2.p, (size_t)L_out * C_out * 4, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
