@@ -309,6 +309,29 @@ int wm_score_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B,
  * for; like every call on a wm_model it is not synchronised — threads that share a model serialise set + submit themselves. */
 int wm_set_repeat_options(wm_model* m, float repetition_penalty, int no_repeat_ngram_size);
 
+/* ---- top-k alternatives per generated id ---------------------------------------------------------------------------
+ * HF generate(output_scores=True) followed by log_softmax(scores).topk(k) per step, for every log-prob pass asked for from now on
+ * (wm_transcribe_lp / _lp_ns / _lang with log-probs, their submit forms and wm_transcribe_rows' log-prob kin), under the rules of
+ * wm_set_repeat_options: model-wide, it persists until the next call, a submit held for a coalesce = 2 partner keeps the value in
+ * force when it was made and pairs only with a submit made under the same value.  Passes without log-probs, wm_score, wm_align and
+ * wm_detect_language ignore it; the long-form and chunked entries refuse to run while it is non-zero (WM_E_ARG).
+ * At every generated position the candidates are what all processors leave for the row — the set the log-prob normalises over:
+ * admissible text and admissible timestamps, the timestamps alone when the rule forces one, everything the masks leave with the
+ * rules off; after sequence_bias, repetition_penalty, no_repeat_ngram_size, bad words, the suppress lists and the timestamp rules.
+ * The k with the largest score come back in descending score, equal scores lowest id first (the arg-max's rule), each with
+ * score - logsumexp over the same set.  Rank 0 is the id the pass emitted and its log-prob is bit for bit token_logprobs' value (a
+ * step whose candidates are all -inf: id 0, -inf).  A rank with no finite candidate left holds id -1 and -inf, never NaN.
+ * It runs on the device inside the captured step: the logits kernel also stores its processed rows, the step's arg-max launch
+ * leaves each row's ranges and normaliser, and one selection launch behind it keeps the k best; a pass with top_k 0 launches
+ * exactly what it did before.  0 = off (the default), 1..8; WM_E_ARG otherwise.
+ *
+ * wm_transcribe_top_k: the alternatives of the log-prob pass this slot collected last (slot 0: the synchronous entries), until the
+ * slot's state runs another pass: top_ids, top_logprobs [B][n_prompt + 1 + max_loop][k] in the layout of tokens_out (for a
+ * per-row-prompt pass: [B][prompt_stride + 1 + max_loop][k]), k the value the pass was asked for under.  Prompt positions and
+ * positions past a row's n_tokens hold id -1 and log-prob 0.  WM_E_STATE: no such pass. */
+int wm_set_top_k(wm_model* m, int top_k);
+int wm_transcribe_top_k(wm_model* m, int slot, int32_t* top_ids, float* top_logprobs);
+
 /* ---- sequence bias and bad words ---------------------------------------------------------------------------------
  * HF generate's sequence_bias (SequenceBiasLogitsProcessor) and bad_words_ids (NoBadWordsLogitsProcessor), given as ids, for every
  * greedy pass asked for from now on — the passes wm_set_repeat_options names, with the same rules: model-wide, it persists until the
@@ -740,6 +763,12 @@ int wm_op_logits_lp(float* logits, int32_t* ids, float* logprob, const float* x,
 int wm_op_logits_processed(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                            const float* mask, const int32_t* ranges, int timestamp_begin, const uint32_t* seen, const uint32_t* ban,
                            float penalty, int B, int N, int K, int dtype);
+/* wm_op_logits_lp with the top-k alternatives: the top-k instantiation of the arg-max launch and the selection launch
+ * behind it, as a decode step runs them.  top_ids, top_lp [B][top_k], 1 <= top_k <= 8: the rule of wm_set_top_k on the row's
+ * candidates (mask, ranges); rank 0 equals (ids, logprob).  seen / ban (both or NULL, with penalty): as wm_op_logits_processed. */
+int wm_op_logits_topk(float* logits, int32_t* ids, float* logprob, int32_t* top_ids, float* top_lp, int top_k, const float* x,
+                      const float* ln_g, const float* ln_b, const float* emb, const float* mask, const int32_t* ranges, int timestamp_begin,
+                      const uint32_t* seen, const uint32_t* ban, float penalty, int B, int N, int K, int dtype);
 /* The sets' bookkeeping alone: the init kernel on each row's prompt tokens[b][0 .. prompt_len[b]), then `steps` argmax launches, step
  * s appending tokens[b][prompt_len[b] + s - 1] (a row past n_ids[b] has ended and does nothing).  seen, ban: host
  * [steps + 1][B][ceil(vocab / 32)] — entry 0 after the init, entry s after step s.  1 <= prompt_len[b] <= n_ids[b] <= stride. */

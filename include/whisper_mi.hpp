@@ -104,13 +104,13 @@ public:
     // whisper.load(loader)  (whisper.mojo:180-182, main.mojo:16-17)
     void load(const WeightLoader& loader) {
         check_abi();
-        if (model_) wm_model_free(model_), model_ = nullptr;
+        if (model_) wm_model_free(model_), model_ = nullptr, top_k_ = 0;
         check(wm_model_load(loader.filename().c_str(), &wcfg_, device_, &model_));
     }
     // weights already in memory (flat fp32, the file's order)
     void load(const float* weights, size_t n_floats) {
         check_abi();
-        if (model_) wm_model_free(model_), model_ = nullptr;
+        if (model_) wm_model_free(model_), model_ = nullptr, top_k_ = 0;
         check(wm_model_load_memory(weights, n_floats, &wcfg_, device_, &model_));
     }
 
@@ -553,6 +553,37 @@ public:
         need_model();
         if (wm_set_repeat_options(model_, repetition_penalty, no_repeat_ngram_size) != WM_OK) throw std::invalid_argument(wm_last_error());
     }
+    // Top-k alternatives for every log-prob call (transcribe_batch_lp and its kin) from now on: 0 = off (the default),
+    // 1..8.  After such a call top_k() returns, per utterance and per GENERATED position, the k (id, log-prob) candidates in
+    // descending score — rank 0 the emitted id with token_logprobs' value; (-1, -inf) where no finite candidate is left.
+    // prompt_len: the prompt lengths the call ran with (one entry = the shared prompt's).  Throws std::invalid_argument for what
+    // wm_set_top_k refuses; the long-form calls refuse to run while it is non-zero.
+    void set_top_k(int k) {
+        need_model();
+        if (wm_set_top_k(model_, k) != WM_OK) throw std::invalid_argument(wm_last_error());
+        top_k_ = k;
+    }
+    struct TopK {
+        std::vector<int32_t> ids;  // [positions][k]
+        std::vector<float> logprobs;
+    };
+    std::vector<TopK> top_k(const std::vector<std::vector<int>>& result, const std::vector<int>& prompt_len, int max_loop = MAX_LOOP) const {
+        need_model();
+        const int B = (int)result.size(), k = top_k_;
+        int lmax = 0;
+        for (int v : prompt_len) lmax = std::max(lmax, v);
+        const size_t stride = (size_t)lmax + 1 + max_loop;
+        std::vector<int32_t> ids((size_t)B * stride * std::max(k, 1));
+        std::vector<float> lps(ids.size());
+        check(wm_transcribe_top_k(model_, 0, ids.data(), lps.data()));
+        std::vector<TopK> out(B);
+        for (int b = 0; b < B; ++b) {
+            const size_t p0 = (size_t)prompt_len[prompt_len.size() == 1 ? 0 : b], p1 = std::max(p0, result[b].size());
+            out[b].ids.assign(ids.begin() + (b * stride + p0) * k, ids.begin() + (b * stride + p1) * k);
+            out[b].logprobs.assign(lps.begin() + (b * stride + p0) * k, lps.begin() + (b * stride + p1) * k);
+        }
+        return out;
+    }
     // HF generate's sequence_bias / bad_words_ids, as ids, for every transcribe / transcribe_long call from now on: each
     // bias entry is (ids, bias), each bad word a list of ids; two empty lists switch them off (the default).  Throws
     // std::invalid_argument for what wm_set_sequence_bias refuses.
@@ -641,6 +672,7 @@ private:
     wm_config wcfg_{};
     int device_ = 0;
     wm_model* model_ = nullptr;
+    int top_k_ = 0;  // what set_top_k set on model_
     struct Pend {
         int B, stride;
     };

@@ -43,6 +43,7 @@ SYMBOLS = [
     "wm_transcribe_chunked_ts", "wm_op_chunk_segments",
     "wm_op_gemm_nt_epi",
     "wm_resample_len", "wm_resample_pcm", "wm_op_resample", "wm_op_resample_taps",
+    "wm_set_top_k", "wm_transcribe_top_k", "wm_op_logits_topk",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -313,6 +314,9 @@ def lib():
     L.wm_set_repeat_options.argtypes = [vp, C.c_float, C.c_int]
     L.wm_op_logits_processed.argtypes = [fp, ip, fp, fp, fp, fp, fp, fp, ip, C.c_int, up, up, C.c_float] + [C.c_int] * 4
     L.wm_op_repeat_sets.argtypes = [up, up, ip, ip, ip] + [C.c_int] * 5
+    L.wm_set_top_k.argtypes = [vp, C.c_int]
+    L.wm_transcribe_top_k.argtypes = [vp, C.c_int, ip, fp]
+    L.wm_op_logits_topk.argtypes = [fp, ip, fp, ip, fp, C.c_int, fp, fp, fp, fp, fp, ip, C.c_int, up, up, C.c_float] + [C.c_int] * 4
     L.wm_set_sequence_bias.argtypes = [vp, ip, ip, fp, C.c_int, ip, ip, C.c_int]
     L.wm_op_logits_seq_bias.argtypes = [fp, ip, fp, fp, fp, fp, fp, fp, ip, C.c_int, up, up, C.c_float, up, ip, C.c_int, fp, ip] + [C.c_int] * 4
     L.wm_op_seq_bias_hits.argtypes = [up, fp, ip, ip, ip, ip, ip, ip] + [C.c_int] * 4 + [ip, ip, fp, C.c_int, ip, ip, C.c_int, C.c_int]
@@ -533,6 +537,24 @@ def repeat_args(repetition_penalty, no_repeat_ngram_size):
     if n < 0 or n > REPEAT_NGRAM_MAX:
         raise ValueError(f"no_repeat_ngram_size must lie in [0, {REPEAT_NGRAM_MAX}] (got {n})")
     return p, n
+
+
+TOPK_MAX = 8  # wm_kernels.h TOPK_MAX
+
+
+def top_k_arg(top_k, return_logprobs):
+    """Checks top_k on the host (the library refuses the same with WM_E_ARG) -> k as wm_set_top_k takes it: None means off (0).
+    ValueError: not an integer of [1, 8], or without return_logprobs (the alternatives' log-probs share the chosen id's normaliser)."""
+    if top_k is None:
+        return 0
+    if isinstance(top_k, bool) or int(top_k) != top_k:
+        raise ValueError(f"top_k must be an integer (got {top_k!r})")
+    k = int(top_k)
+    if k < 1 or k > TOPK_MAX:
+        raise ValueError(f"top_k must lie in [1, {TOPK_MAX}] (got {k})")
+    if not return_logprobs:
+        raise ValueError("top_k needs return_logprobs=True")
+    return k
 
 
 SEQ_BIAS_MAX, SEQ_BIAS_LEN_MAX = 1024, 32  # wm_kernels.h

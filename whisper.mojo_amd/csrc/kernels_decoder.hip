@@ -2196,8 +2196,10 @@ __device__ __forceinline__ void seq_bias_update(const SeqBiasCtl& c, unsigned* h
 }
 // LP: the log-probability instantiation (p.lp_s non-null); LP = false is the kernel without it, static LDS included.  RP: the
 // repetition processors' bookkeeping (p.rp_seen non-null), likewise.  SB: the sequence-bias bookkeeping (p.sb_hit non-null, needs RP).
-template <bool LP, bool RP = false, bool SB = false>
+// TK (top-k alternatives; p.tk_rows non-null, needs LP): thread 0 also leaves the row's TopkRow for the selection launch.
+template <bool LP, bool RP = false, bool SB = false, bool TK = false>
 __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
+    static_assert(LP || !TK, "the top-k alternatives ride the log-prob instantiation");
     const int b = blockIdx.x;
     if (p.ts && b == 0 && threadIdx.x == 0) ts_put(p.ts, p.ts_id, 3);
     const int pos0 = p.emb_out ? p.pos[b] : 0;  // read before thread 0 advances it (the reductions below synchronise)
@@ -2235,6 +2237,12 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
         }
         if (!p.ts_state && txt_s > 0.f) lp = -logf(txt_s);  // best - (best + log sum); every candidate -inf: stays -inf, never NaN
     }
+    TopkRow tk{};  // TK, thread 0: rules off — everything the mask leaves, against (best, log of the text sum)
+    if constexpr (TK) {
+        tk.hi0 = p.V;
+        tk.ref = best;
+        tk.logz = txt_s > 0.f ? logf(txt_s) : 0.f;
+    }
     if (p.ts_state) {
         // Timestamp rules, the decision (HF WhisperTimeStampLogitsProcessor rule 5 + the final argmax): (best, idx) is the best
         // admissible text id; if the admissible timestamps' probability mass exceeds it — logsumexp(ts) > best, the softmax
@@ -2270,6 +2278,23 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
                     if (tot > 0.f) lp = (best - mn) - logf(tot);
                 }
             }
+            if constexpr (TK) {  // this step's ranges, before the history moves on; the pair the branch above normalised with
+                const TsState cur = p.ts_state[b];
+                tk.lo1 = cur.ts_lo;
+                tk.hi1 = cur.ts_hi;
+                if (forced) {
+                    tk.lo0 = tk.hi0 = 0;
+                    tk.ref = tm;
+                    tk.logz = logf(tsum);
+                } else {
+                    const float mn = fmaxf(best, tm);
+                    const float tot = (txt_s > 0.f ? txt_s * expf(best - mn) : 0.f) + (tsum > 0.f ? tsum * expf(tm - mn) : 0.f);
+                    tk.lo0 = cur.text_lo;
+                    tk.hi0 = cur.text_hi;
+                    tk.ref = mn;
+                    tk.logz = tot > 0.f ? logf(tot) : 0.f;
+                }
+            }
             if ((unsigned)pick >= (unsigned)p.V) pick = 0;
             TsState st = p.ts_state[b];
             const int is_ts = pick >= p.rules.tb;
@@ -2291,6 +2316,12 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
     if (threadIdx.x == 0) {
         p.next[b] = idx;
         if (LP && p.lp_next) p.lp_next[b] = lp;
+        if constexpr (TK) {  // the entry beside the id's: same guard as out_tokens (read before this step's count and finish)
+            tk.slot = !p.out_tokens ? b : p.finished[b] ? -1 : b * p.out_stride + p.n_tokens[b];
+            tk.id0 = idx;
+            tk.lp0 = lp;
+            p.tk_rows[b] = tk;
+        }
         if (p.advance) {  // current_len += 1 (layers.mojo:143), position += 1: nothing else in this launch reads them
             p.pos[b] += 1;
             if (b == 0) p.ctl->len += 1;
@@ -2338,6 +2369,19 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
     }
 }
 int launch_argmax_step(const ArgmaxParams& p, hipStream_t st) {
+    if (p.tk_rows) {  // the top-k instantiations: the log-prob ones plus the row's TopkRow, nothing else differs
+        if (!p.lp_s || !p.pval) return launch_refuse("argmax_step: the top-k alternatives need the log-prob form");
+        if (p.sb_hit && (!p.rp_seen || !p.sb_val || !p.sb_ctl)) return launch_refuse("argmax_step: the sequence bias needs the repetition processors' sets, the rows' slots and the control block");
+        if (p.rp_seen && (!p.out_tokens || !p.rp_ban || !p.rp_ctl || p.rp_words < repeat_words(p.V)))
+            return launch_refuse("argmax_step: the repetition processors need the partials form, the id table, both sets and their control block");
+        if (p.sb_hit)
+            hipLaunchKernelGGL((argmax_step_kernel<true, true, true, true>), dim3(p.B), dim3(256), 0, st, p);
+        else if (p.rp_seen)
+            hipLaunchKernelGGL((argmax_step_kernel<true, true, false, true>), dim3(p.B), dim3(256), 0, st, p);
+        else
+            hipLaunchKernelGGL((argmax_step_kernel<true, false, false, true>), dim3(p.B), dim3(256), 0, st, p);
+        return WM_LAUNCH_OK;
+    }
     if (p.rp_seen) {  // the sets' bookkeeping reads the row's history and rides the partials form: anything else is refused, not dropped
         if (!p.out_tokens || !p.pval || !p.rp_ban || !p.rp_ctl || p.rp_words < repeat_words(p.V))
             return launch_refuse("argmax_step: the repetition processors need the partials form, the id table, both sets and their control block");
@@ -2360,6 +2404,115 @@ int launch_argmax_step(const ArgmaxParams& p, hipStream_t st) {
         hipLaunchKernelGGL(argmax_step_kernel<true>, dim3(p.B), dim3(256), 0, st, p);
     else
         hipLaunchKernelGGL(argmax_step_kernel<false>, dim3(p.B), dim3(p.pval ? 256 : 1024), 0, st, p);
+    return WM_LAUNCH_OK;
+}
+// Top-k alternatives, the selection: one workgroup of 4 waves per row.  A thread keeps the TOPK_MAX best of the ids
+// threadIdx.x, + 256, ... (ascending, so strict '>' keeps the lowest id among equals) as a sorted list in registers; a wave pops its
+// lanes' heads TOPK_MAX times (a butterfly arg-max per pop: value, then lowest id), thread 0 merges the 4 waves' lists from LDS the
+// same way.  Every order is fixed by values and ids alone: a row's result does not depend on the batch it sits in.
+__device__ __forceinline__ bool topk_before(float v, int i, float v2, int i2) { return v > v2 || (v == v2 && i < i2); }
+__global__ __launch_bounds__(256) void topk_select_kernel(TopkSelectParams p) {
+    constexpr int K = TOPK_MAX;
+    const int b = blockIdx.x;
+    const TopkRow row = p.rows[b];
+    if (row.slot < 0) return;  // (block-uniform) a finished row stores nothing
+    __shared__ float s_v[4][K];
+    __shared__ int s_i[4][K];
+    const float* z = p.logits + (size_t)b * p.ldl;
+    float lv[K];
+    int li[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        lv[j] = -INFINITY;
+        li[j] = 0x7fffffff;
+    }
+    for (int n = threadIdx.x; n < p.V; n += 256) {
+        if (!((n >= row.lo0 && n < row.hi0) || (n >= row.lo1 && n < row.hi1))) continue;
+        const float v = z[n] + (p.mask ? p.mask[n] : 0.f);
+        if (v > lv[K - 1] && v < INFINITY) {  // (NaN and -inf fail the compare; n only grows: an equal value never displaces)
+            lv[K - 1] = v;
+            li[K - 1] = n;
+#pragma unroll
+            for (int j = K - 1; j > 0; --j)
+                if (lv[j] > lv[j - 1]) {
+                    const float tv = lv[j];
+                    const int ti = li[j];
+                    lv[j] = lv[j - 1];
+                    li[j] = li[j - 1];
+                    lv[j - 1] = tv;
+                    li[j - 1] = ti;
+                }
+        }
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int r = 0; r < K; ++r) {
+        float bv = lv[0];
+        int bi = li[0];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float v2 = __shfl_xor(bv, o, 64);
+            const int i2 = __shfl_xor(bi, o, 64);
+            if (topk_before(v2, i2, bv, bi)) {
+                bv = v2;
+                bi = i2;
+            }
+        }
+        if (bv > -INFINITY && bi == li[0]) {  // ids are unique: exactly the lane that held the winner pops it
+#pragma unroll
+            for (int j = 0; j < K - 1; ++j) {
+                lv[j] = lv[j + 1];
+                li[j] = li[j + 1];
+            }
+            lv[K - 1] = -INFINITY;
+            li[K - 1] = 0x7fffffff;
+        }
+        if (lane == 0) {
+            s_v[w][r] = bv;
+            s_i[w][r] = bv > -INFINITY ? bi : 0x7fffffff;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int head[4] = {0, 0, 0, 0};
+        int* oi = p.ids + (size_t)row.slot * p.k;
+        float* ol = p.lps + (size_t)row.slot * p.k;
+        // rank 0: the id the step emitted, with the log-prob it stored (id 0 / -inf when nothing was finite).  The merged stream then
+        // fills ranks 1.. and passes over the emitted id BY ID wherever it stands: an id is neither listed twice nor lost when the
+        // arg-max's winner is not the stream's head (a +inf score, which the sweep leaves out)
+        oi[0] = row.id0;
+        ol[0] = row.lp0;
+        for (int r = 1; r < p.k;) {
+            float bv = -INFINITY;
+            int bi = 0x7fffffff, bw = -1;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (head[q] >= K) continue;
+                const float v2 = s_v[q][head[q]];
+                const int i2 = s_i[q][head[q]];
+                if (topk_before(v2, i2, bv, bi)) {
+                    bv = v2;
+                    bi = i2;
+                    bw = q;
+                }
+            }
+            if (bw >= 0) {
+                head[bw] += 1;  // (every turn moves a head or r: at most 4 K + k turns)
+                if (bi == row.id0) continue;
+                oi[r] = bi;
+                ol[r] = (bv - row.ref) - row.logz;
+            } else {
+                oi[r] = -1;
+                ol[r] = -INFINITY;
+            }
+            ++r;
+        }
+    }
+}
+int launch_topk_select(const TopkSelectParams& p, hipStream_t st) {
+    if (!p.logits || !p.rows || !p.ids || !p.lps || p.B <= 0 || p.V <= 0 || p.ldl < p.V) return launch_refuse("topk_select: bad argument");
+    if (p.k < 1 || p.k > TOPK_MAX) return launch_refuse("topk_select: k must be 1..8");
+    hipLaunchKernelGGL(topk_select_kernel, dim3(p.B), dim3(256), 0, st, p);
     return WM_LAUNCH_OK;
 }
 __global__ __launch_bounds__(1024) void argmax_plain_kernel(const float* t, int n, int* idx) {

@@ -178,6 +178,7 @@ struct PassAsk {
     const ScoreAsk* score = nullptr;
     const WinAsk* win = nullptr;  // with cols: a long-form window pass whose times are finished on the device
     RepeatAsk rp;                 // filled by the drivers (run_now / submit_slot / the long-form scheduler) from the model's setting
+    int top_k = 0;                // top-k alternatives of a greedy log-prob pass, filled by run_now / submit_slot likewise; 0 = off
 };
 static PassAsk lang_only_ask(const float* mel, int mel_on_device, int B, const int32_t* lang_ids, int n_lang, int sot) {
     PassAsk ask{mel, mel_on_device, B};
@@ -273,10 +274,15 @@ struct wm_model {
     std::vector<int32_t> align_pairs;
     RepeatAsk repeat;  // wm_set_repeat_options / wm_set_sequence_bias: what every greedy pass asked for from now on carries (a held submit keeps its own)
     int seq_gen = 0;   // tables built so far by wm_set_sequence_bias
+    int top_k = 0;     // wm_set_top_k: what every log-prob pass asked for from now on carries (a held submit keeps its own)
     struct AlignRef {  // where a slot's last timestamp pass left its alignment weights (wm_alignment_weights)
         wm_state* st = nullptr;
         int row0 = 0, rows = 0, gen = 0;
     } align_ref[8];
+    struct TopkRef {  // where a slot's last collected log-prob pass left its top-k tables (wm_transcribe_top_k)
+        wm_state* st = nullptr;
+        int row0 = 0, rows = 0, total = 0, k = 0, gen = 0;
+    } topk_ref[8];
     // sequential long-form decoding: the long log-mel and its scratch (frames / spec hold one chunk of frames, the
     // rest grows with the audio), and two internal decode states, apart from the caller's slots, with each one's gathered
     // windows and work items
@@ -343,10 +349,11 @@ struct wm_state {
         bool rows = false, lp = false;  // self-attention in the key-window form (rw.on); log-probabilities (lp.on)
         bool rp = false;                // repetition processors (rp.on): the flag only — penalty and n-gram size are read on the device
         bool sb = false;                // sequence bias / bad words (rp.sb): the flag only — the table is reached through the control block
+        int top_k = 0;                  // top-k alternatives (tk.k): the logits store, the argmax instantiation and the selection launch
         bool operator==(const StepKey& o) const {
             return eot == o.eot && ignore_eot == o.ignore_eot && rules.tb == o.rules.tb && rules.eos == o.rules.eos &&
                    rules.max_init == o.rules.max_init && rules.vocab == o.rules.vocab && shares_chip == o.shares_chip && cap == o.cap &&
-                   rows == o.rows && lp == o.lp && rp == o.rp && sb == o.sb;
+                   rows == o.rows && lp == o.lp && rp == o.rp && sb == o.sb && top_k == o.top_k;
         }
     };
     StepKey step, graph_step;
@@ -404,6 +411,13 @@ struct wm_state {
         DevBuf part_s, table, sum;
         std::vector<int32_t> n_prompt;  // [B] prompt length of each row of the pending pass
     } lp;
+    // top-k alternatives of the pending pass (k > 0 = a log-prob pass asked for with wm_set_top_k in force): each step's
+    // TopkRow per row, and the [B][out_stride][k] id / log-prob tables beside out_tokens (sized for k = TOPK_MAX; entries of generated
+    // positions only are ever written).  Part of the arena.  gen counts the state's passes of any kind.
+    struct Tk {
+        int k = 0, gen = 0;
+        DevBuf rows, ids, lps;
+    } tk;
     // repetition processors of the pending pass (on = the pass was asked for with wm_set_repeat_options in force): the
     // rows' two bit sets [B][words] and the control block the kernels read (penalty, n-gram size).  Allocated by the first such pass.
     struct Rp {
@@ -909,6 +923,8 @@ extern "C" void wm_state_free(wm_state* s) {
         if (r.st == s) r = wm_model::SlotRef{};
     for (auto& r : s->m->align_ref)
         if (r.st == s) r = wm_model::AlignRef{};
+    for (auto& r : s->m->topk_ref)
+        if (r.st == s) r = wm_model::TopkRef{};
     (void)hipSetDevice(s->m->device);
     // nothing of this state may still be running when its graphs, streams and arenas go away (a submitted pass that was
     // never waited for, or the model stream's last wm_decode_step)
@@ -933,7 +949,7 @@ extern "C" void wm_state_free(wm_state* s) {
                     &s->al.cap, &s->al.kh, &s->al.probs, &s->al.mean, &s->al.stdv, &s->al.M, &s->al.trace, &s->al.times, &s->al.ncols,
                     &s->al.rows, &s->al.row0, &s->al.map, &s->sc.rows, &s->sc.a, &s->sc.pmax, &s->sc.psum, &s->sc.pidx, &s->sc.ztgt, &s->sc.target,
                     &s->sc.slot, &s->sc.dst, &s->sc.len, &s->sc.ctx, &s->sc.lp, &s->sc.top, &s->sc.sum, &s->sc.avg,
-                    &s->rw.table, &s->rw.len, &s->rw.key_lo, &s->lp.part_s, &s->lp.table, &s->lp.sum,
+                    &s->rw.table, &s->rw.len, &s->rw.key_lo, &s->lp.part_s, &s->lp.table, &s->lp.sum, &s->tk.rows, &s->tk.ids, &s->tk.lps,
                     &s->ns.x, &s->ns.pmax, &s->ns.pidx, &s->ns.psum, &s->ns.prob, &s->ns.lse,
                     &s->lg.x, &s->lg.ids, &s->lg.col, &s->lg.out, &s->lg.probs, &s->rp.seen, &s->rp.ban, &s->rp.ctl, &s->rp.hit, &s->rp.val, &s->rp.sbctl};
     for (DevBuf* b : bs) b->release();
@@ -1049,6 +1065,9 @@ static int state_new(wm_model* m, int B, wm_state** out, bool pair) {
     A(s->lp.part_s, (size_t)B * s->npart * 4, true);
     A(s->lp.table, (size_t)B * s->out_stride * 4, true);
     A(s->lp.sum, (size_t)B * 4, true);
+    A(s->tk.rows, (size_t)B * sizeof(TopkRow), true);
+    A(s->tk.ids, (size_t)B * s->out_stride * TOPK_MAX * 4, true);
+    A(s->tk.lps, (size_t)B * s->out_stride * TOPK_MAX * 4, true);
     A(s->ns.x, (size_t)B * d * 4, true);
     A(s->ns.pmax, (size_t)B * s->npart * 4, true);
     A(s->ns.pidx, (size_t)B * s->npart * 4, true);
@@ -1663,8 +1682,8 @@ static int decode_core(wm_model* m, wm_state* s, const DecView& v, const DecPass
     if (a.logits != Logits::none) {  // final LN + tied-embedding logits (whisper.mojo:156-166), no bias, rows of the last position
         const VocabHead h = vocab_head(m);
         DecLinearParams p = linear_block(dx + (size_t)(P - 1) * v.nb * d, h.ln_g, h.ln_b, h.emb, nullptr, h.vocab, h.d_model, v.nb,
-                                      a.logits == Logits::full ? lane_ptr<float>(s->logits, v, m->Vpad) : nullptr, m->Vpad);
-        add_argmax_partials(p, s, v, a.mask, a.rules);
+                                      a.logits == Logits::full || s->tk.k > 0 ? lane_ptr<float>(s->logits, v, m->Vpad) : nullptr, m->Vpad);
+        add_argmax_partials(p, s, v, a.mask, a.rules);  // (top-k alternatives: the selection launch reads the stored, processed rows)
         p.ts = (long long*)m->ts_buf.p;
         p.ts_id = s->trace_id;
         int lrc = 0;
@@ -1713,6 +1732,7 @@ static ArgmaxParams argmax_first_id(wm_model* m, wm_state* s, const DecView& v, 
         a.lp_s = lane_ptr<float>(s->lp.part_s, v, s->npart);
         a.logprobs = lane_ptr<float>(s->lp.table, v, s->out_stride);
         a.lp_sum = lane_ptr<float>(s->lp.sum, v, 1);
+        if (s->tk.k > 0) a.tk_rows = lane_ptr<TopkRow>(s->tk.rows, v, 1);
     }
     if (s->rp.on) {
         a.rp_seen = lane_ptr<unsigned>(s->rp.seen, v, s->rp.words);
@@ -1728,6 +1748,23 @@ static ArgmaxParams argmax_first_id(wm_model* m, wm_state* s, const DecView& v, 
     a.eot = eot;
     a.ignore_eot = ignore_eot;
     return a;
+}
+// Top-k alternatives: the selection launch behind an argmax launch that recorded an id — the k best of each row's stored
+// logits under `mask` and the ranges the argmax left in the row's TopkRow, into the tables' entry beside the id.  k = 0: nothing.
+static int topk_select(wm_model* m, wm_state* s, const DecView& v, const float* mask) {
+    if (s->tk.k <= 0) return 0;
+    TopkSelectParams q{};
+    q.logits = lane_ptr<float>(s->logits, v, m->Vpad);
+    q.ldl = m->Vpad;
+    q.V = m->cfg.dims.vocab;
+    q.B = v.nb;
+    q.mask = mask;
+    q.rows = lane_ptr<TopkRow>(s->tk.rows, v, 1);
+    q.k = s->tk.k;
+    q.ids = lane_ptr<int>(s->tk.ids, v, (size_t)s->out_stride * s->tk.k);
+    q.lps = lane_ptr<float>(s->tk.lps, v, (size_t)s->out_stride * s->tk.k);
+    LCHK(launch_topk_select(q, v.st));
+    return 0;
 }
 // a step of the greedy loop: also advances the cache length, reports progress to the host and writes the next step's input row
 static ArgmaxParams argmax_loop_step(wm_model* m, wm_state* s, const DecView& v, int eot, int ignore_eot, const TsRules* rules) {
@@ -1819,6 +1856,7 @@ static int loop_step(wm_model* m, wm_state* s, const DecView& v) {
     step.capture = true;
     WMCHK(decode_core(m, s, v, step));
     LCHK(launch_argmax_step(argmax_loop_step(m, s, v, k.eot, k.ignore_eot, &k.rules), v.st));
+    if (k.top_k > 0) WMCHK(topk_select(m, s, v, step.mask));
     return 0;
 }
 static void invalidate_step_graphs(wm_state* s) { s->graphs_valid = false; }  // the next greedy pass captures its step anew
@@ -2027,6 +2065,7 @@ static int prefill_rows(wm_model* m, wm_state* s, const DecView& v, InitTokensPa
         if (s->ns.on && t_sot >= t0 && t_sot < t0 + P) ns_capture(m, s, v, (size_t)(t_sot - t0) * v.nb);
     }
     LCHK(launch_argmax_step(argmax_first_id(m, s, v, o->eot, o->ignore_eot, rp), v.st));
+    WMCHK(topk_select(m, s, v, s->mask_begin.as<float>()));
     trace_mark(v.st, "state %p lane %d prefill end", (void*)s, v.b0);
     launch_set_rows_step(v.ctl, Lmax, lane_ptr<int>(s->pos, v, 1), rw.len.as<int>(), o->pos_mode == WM_POS_REF ? -1 : 0, v.nb, v.st);
     return 0;
@@ -2059,6 +2098,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
     s->step.lp = s->lp.on;
     s->step.rp = s->rp.on;
     s->step.sb = s->rp.sb;
+    s->step.top_k = s->tk.k;
     const bool recapture = !s->graphs_valid || !(s->graph_step == s->step);
     const int first_pos = o->pos_mode == WM_POS_REF ? o->n_prompt - 1 : o->n_prompt;
     // logit masks (§8f rank 4): rebuilt only when the id lists change; always passed (all-zero = the reference's raw argmax)
@@ -2126,6 +2166,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
                 }
             }
             LCHK(launch_argmax_step(argmax_first_id(m, s, v, o->eot, o->ignore_eot, rp), v.st));  // :198-203
+            WMCHK(topk_select(m, s, v, prompt.mask));
             trace_mark(v.st, "state %p lane %d prefill end", (void*)s, v.b0);
             // incremental steps: start_pos = current_len - 1 (reference, :217) or current_len (HF)
             launch_set_step(v.ctl, o->n_prompt, 1, lane_ptr<int>(s->pos, v, 1), first_pos, nullptr, 0, v.nb, v.st);
@@ -2302,6 +2343,8 @@ static int submit_on(wm_model* m, wm_state** slot, const PassAsk& ask) {
         s->rp.ask.sb.reset();  // (a pass without the table holds no reference to one)
     }
     s->lp.on = lp;
+    s->tk.k = lp && !score && !lang.only ? ask.top_k : 0;  // the alternatives of a greedy log-prob pass; every other pass ignores the setting
+    s->tk.gen += 1;
     if (lp) {
         if (rows)
             s->lp.n_prompt.assign(rows->len, rows->len + B);
@@ -2472,6 +2515,7 @@ static int collect_pass(wm_model* m, int slot, const PassOut& out) {
     if (!rc && transcribe) m->last_steps[slot] = s->last_steps;
     const bool weights = !rc && (r.tt || r.kind == PassKind::align);
     m->align_ref[slot] = weights ? wm_model::AlignRef{s, r.row0, r.rows, s->al.gen} : wm_model::AlignRef();
+    m->topk_ref[slot] = !rc && transcribe && r.lp && s->tk.k > 0 ? wm_model::TopkRef{s, r.row0, r.rows, r.total, s->tk.k, s->tk.gen} : wm_model::TopkRef();
     r = wm_model::SlotRef();
     return rc;
 }
@@ -2483,6 +2527,7 @@ static bool pairs_with(const wm_model::Held& h, const PassAsk& b) {
     const wm_decode_opts &x = h.o, *o = b.opts;
     if (a.B != b.B || (a.cols != nullptr) != (b.cols != nullptr) || a.lp != b.lp || a.ns.token != b.ns.token || a.ns.n_init != b.ns.n_init)
         return false;
+    if (a.top_k != b.top_k) return false;  // one step graph per state: a pair shares the top-k setting
     if (!(a.rp == b.rp)) return false;  // one control block per state: a pair shares (penalty, n-gram size) and the sequence-bias table
     if (x.n_prompt != o->n_prompt || x.eot != o->eot || x.max_loop != o->max_loop || x.pos_mode != o->pos_mode || x.ignore_eot != o->ignore_eot ||
         x.n_suppress != (o->suppress_tokens ? o->n_suppress : 0) || x.n_begin_suppress != (o->begin_suppress_tokens ? o->n_begin_suppress : 0) ||
@@ -2537,6 +2582,7 @@ static int run_now(wm_model* m, PassAsk ask, const PassOut& out) {
     WMCHK(slot0_ready(m));
     ask.allow_poll = true;
     ask.rp = m->repeat;
+    ask.top_k = m->top_k;
     WMCHK(submit_on(m, &m->cached, ask));
     record_pass(m, 0, ask, m->cached, 0, ask.B);
     return collect_pass(m, 0, out);
@@ -2547,6 +2593,7 @@ static int submit_slot(wm_model* m, int slot, const PassAsk& asked) {
     if (m->slot_ref[slot].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
     PassAsk ask = asked;
     ask.rp = m->repeat;  // the setting in force now: a held submit runs with it even if it changes before the partner arrives
+    ask.top_k = m->top_k;
     const int B = ask.B;
     // (a per-row, language or score / align pass is never held for a coalesce = 2 partner: it runs alone)
     const bool can_pair = !ask.rows && !ask.lang.ids && !ask.score && m->cfg.coalesce == 2 && B <= m->cfg.max_batch &&
@@ -2911,6 +2958,34 @@ extern "C" int wm_set_repeat_options(wm_model* m, float repetition_penalty, int 
         return fail(WM_E_ARG, "no_repeat_ngram_size %d outside [0, %d] (0 = off)", no_repeat_ngram_size, REPEAT_NGRAM_MAX);
     m->repeat.penalty = repetition_penalty;
     m->repeat.ngram = no_repeat_ngram_size;
+    return 0;
+}
+// ---- top-k alternatives ----------------------------------------------------------------------------------------
+extern "C" int wm_set_top_k(wm_model* m, int top_k) {
+    if (!m) return fail(WM_E_ARG, "bad argument");
+    if (top_k < 0 || top_k > TOPK_MAX) return fail(WM_E_ARG, "top_k %d outside [0, %d] (0 = off)", top_k, TOPK_MAX);
+    m->top_k = top_k;
+    return 0;
+}
+extern "C" int wm_transcribe_top_k(wm_model* m, int slot, int32_t* top_ids, float* top_logprobs) {
+    if (!m || !top_ids || !top_logprobs || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");
+    const wm_model::TopkRef& r = m->topk_ref[slot];
+    if (!r.st || !state_is_live(r.st) || r.st->tk.gen != r.gen || (r.st->pending && r.st->synced == false))
+        return fail(WM_E_STATE, "no collected log-prob pass with top_k on this slot (wm_set_top_k; or its state has run another pass since)");
+    wm_state* s = r.st;
+    HIPCHK(hipSetDevice(m->device));
+    const size_t k = r.k, row = (size_t)r.total * k, pitch = (size_t)s->out_stride * k;
+    HIPCHK(hipMemcpy2D(top_ids, row * 4, s->tk.ids.as<int>() + (size_t)r.row0 * pitch, pitch * 4, row * 4, r.rows, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(top_logprobs, row * 4, s->tk.lps.as<float>() + (size_t)r.row0 * pitch, pitch * 4, row * 4, r.rows, hipMemcpyDeviceToHost));
+    std::vector<int32_t> n(r.rows);
+    HIPCHK(hipMemcpy(n.data(), s->n_tokens.as<int>() + r.row0, (size_t)r.rows * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < r.rows; ++b)  // prompt and tail positions were never written: id -1, log-prob 0, as the log-prob table's 0
+        for (int i = 0; i < r.total; ++i)
+            if (i < s->lp.n_prompt[r.row0 + b] || i >= n[b])
+                for (size_t j = 0; j < k; ++j) {
+                    top_ids[b * row + i * k + j] = -1;
+                    top_logprobs[b * row + i * k + j] = 0.f;
+                }
     return 0;
 }
 // ---- sequence bias and bad words ---------------------------------------------------------------------------------
@@ -3800,6 +3875,8 @@ static int chunked_impl(wm_model* m, const float* pcm, int pcm_on_device, const 
     const wm_dims& c = m->cfg.dims;
     const int n_frames = 2 * c.n_audio_ctx, N = FE_HOP * n_frames;
     WMCHK(check_opts(m, o, 1));
+    if (m->top_k > 0)  // (the stitched result has no place for them yet)
+        return fail(WM_E_ARG, "top-k alternatives (wm_set_top_k) are not available in chunked transcription: set top_k to 0");
     const bool word = ts.mode == 2;
     if (ts.mode) {  // everything is refused before anything is launched
         if (ts.mode != 1 && ts.mode != 2) return fail(WM_E_ARG, "mode must be 1 (segments) or 2 (word)");
@@ -4667,6 +4744,8 @@ static int long_check(wm_model* m, const wm_decode_opts* o, int B) {
 static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int B, const wm_decode_opts* o, wm_long_result* res,
                     const wm_long_opts* lo, const int32_t* lang_ids = nullptr, int n_lang = 0, int32_t* lang_out = nullptr, bool tt = false) {
     const wm_dims& c = m->cfg.dims;
+    if (m->top_k > 0)  // (no entry of the long-form result carries them yet)
+        return fail(WM_E_ARG, "top-k alternatives (wm_set_top_k) are not available in long-form transcription: set top_k to 0");
     const bool plain = long_opts_plain(lo) && !lang_ids;
     // thresholds: every pass is a log-prob pass; with a no_speech_token it also carries the probe at the first of the
     // o->n_prompt initial ids.  A window is skipped iff avg_logprob < logprob_threshold and no_speech_prob > no_speech_threshold.

@@ -305,6 +305,17 @@ int launch_xattn_merge(const XAttnParams& p, hipStream_t st);
 
 void launch_dec_embed(const float* tok_emb, const float* pos_emb, const int* tok, const int* pos, float* x, int B, int d,
                       hipStream_t st);
+// Top-k alternatives: what argmax_step leaves per row for the selection launch behind it — where the row's entries go,
+// the id it emitted with its log-prob, the candidate ranges the step's processors left (read BEFORE the timestamp history moves on; a
+// forced timestamp leaves no text range) and the normaliser as the pair the log-prob was formed from: lp = (value - ref) - logz.
+static const int TOPK_MAX = 8;
+struct TopkRow {
+    int slot;  // entry of the [..][k] tables, -1: the row stores nothing (finished)
+    int id0;
+    float lp0;
+    int lo0, hi0, lo1, hi1;  // candidates: ids of [lo0, hi0) ∪ [lo1, hi1)
+    float ref, logz;
+};
 // argmax over logits rows (lowest index wins) + greedy-loop bookkeeping
 struct ArgmaxParams {
     const float* logits;
@@ -358,8 +369,24 @@ struct ArgmaxParams {
     unsigned* sb_hit;  // [B][rp_words]
     SeqSlot* sb_val;   // [B][SEQ_BIAS_MAX]
     const SeqBiasCtl* sb_ctl;
+    // top-k alternatives (tk_rows null = off, needs lp_s): the row's TopkRow for the selection launch behind this one
+    TopkRow* tk_rows;  // [B]
 };
 int launch_argmax_step(const ArgmaxParams& p, hipStream_t st);  // WM_LAUNCH_*: refuses sets without the partials form or the id table
+// Top-k alternatives, the selection launch: one workgroup per row sweeps the step's stored, processed logits row under
+// the mask and the ranges of rows[b], keeps the k best (value descending, lowest id first among equals) and stores ids and
+// log-probs (value - ref) - logz at table entry rows[b].slot (none when it is negative).  Rank 0 is rows[b]'s own (id0, lp0); a rank
+// without a finite candidate holds (-1, -inf).
+struct TopkSelectParams {
+    const float* logits;  // [B][ldl]: what the logits kernel stored (behind the repetition processors and the sequence bias)
+    int ldl, V, B;
+    const float* mask;    // [V] additive (0 / -inf) or null: the mask the step's argmax ran under
+    const TopkRow* rows;  // [B]
+    int k;                // 1..TOPK_MAX
+    int* ids;             // [entries][k]
+    float* lps;           // [entries][k]
+};
+int launch_topk_select(const TopkSelectParams& p, hipStream_t st);  // WM_LAUNCH_*
 // Start of a pass with the repetition processors, behind the init-tokens launch: writes ctl, clears both sets of the B rows, sets
 // `seen` from each row's prompt out_tokens[b][0 .. n_tokens[b]) and `ban` for the first generated id.
 struct RepeatInitParams {

@@ -596,8 +596,10 @@ extern "C" int wm_op_dec_linear_capmap(float* out, float* cap, const float* x, c
 static int op_logits(float* logits, int32_t* ids, float* logprob, const float* x, const float* ln_g, const float* ln_b, const float* emb,
                      const float* mask, const int32_t* ranges, int timestamp_begin, int B, int N, int K, int dtype, const uint32_t* seen = nullptr,
                      const uint32_t* ban = nullptr, float penalty = 1.f, const uint32_t* hit = nullptr, const int32_t* slot_id = nullptr,
-                     int n_slots = 0, const float* slot_bias = nullptr, const int32_t* slot_flags = nullptr) {
+                     int n_slots = 0, const float* slot_bias = nullptr, const int32_t* slot_flags = nullptr, int top_k = 0,
+                     int32_t* top_ids = nullptr, float* top_lp = nullptr) {
     if (!logits || !ids || !x || !ln_g || !ln_b || !emb || B <= 0 || N <= 0) return fail(WM_E_ARG, "bad argument");
+    if (top_k && (top_k < 1 || top_k > TOPK_MAX || !logprob || !top_ids || !top_lp)) return fail(WM_E_ARG, "top_k must be 1..%d, with the log-prob outputs", TOPK_MAX);
     WMCHK(vocab_k_check(K));
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
     if (ranges && (timestamp_begin <= 0 || timestamp_begin >= N)) return fail(WM_E_ARG, "ranges need 0 < timestamp_begin < N");
@@ -690,6 +692,13 @@ static int op_logits(float* logits, int32_t* ids, float* logprob, const float* x
         a.lp_s = ls.as<float>();
         a.lp_next = ln.as<float>();
     }
+    DevBuf &kr = t.add(), &ki = t.add(), &kl = t.add();  // wm_op_logits_topk: the rows' TopkRow and the [B][k] tables (slot = row)
+    if (top_k) {
+        WMCHK(kr.alloc((size_t)B * sizeof(TopkRow), true));
+        WMCHK(ki.alloc((size_t)B * top_k * 4, true));
+        WMCHK(kl.alloc((size_t)B * top_k * 4, true));
+        a.tk_rows = kr.as<TopkRow>();
+    }
     if (ranges) {
         a.ts_state = tst.as<TsState>();
         a.rules = rules;
@@ -707,9 +716,26 @@ static int op_logits(float* logits, int32_t* ids, float* logprob, const float* x
     a.pidx = ai.as<int>();
     a.npart = npart;
     a.next = nx.as<int>();
-    launch_argmax_step(a, st);
+    LCHK(launch_argmax_step(a, st));
+    if (top_k) {  // the selection launch as topk_select wires it behind the step's argmax
+        TopkSelectParams q{};
+        q.logits = o.as<float>();
+        q.ldl = ldo;
+        q.V = N;
+        q.B = B;
+        q.mask = p.amax_mask;
+        q.rows = kr.as<TopkRow>();
+        q.k = top_k;
+        q.ids = ki.as<int>();
+        q.lps = kl.as<float>();
+        LCHK(launch_topk_select(q, st));
+    }
     HIPCHK(hipGetLastError());
     WMCHK(download_f32_rows(logits, o, B, N, ldo, WM_F32));
+    if (top_k) {
+        HIPCHK(hipMemcpy(top_ids, ki.p, (size_t)B * top_k * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(top_lp, kl.p, (size_t)B * top_k * 4, hipMemcpyDeviceToHost));
+    }
     HIPCHK(hipMemcpy(ids, nx.p, (size_t)B * 4, hipMemcpyDeviceToHost));
     if (logprob) HIPCHK(hipMemcpy(logprob, ln.p, (size_t)B * 4, hipMemcpyDeviceToHost));
     return 0;
@@ -730,6 +756,15 @@ extern "C" int wm_op_logits_processed(float* logits, int32_t* ids, float* logpro
                                       const uint32_t* ban, float penalty, int B, int N, int K, int dtype) {
     if (!seen || !ban || !(penalty > 0.f)) return fail(WM_E_ARG, "bad argument");
     return op_logits(logits, ids, logprob, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype, seen, ban, penalty);
+}
+// The same launches with the top-k alternatives: the TK instantiation of argmax_step and the selection launch behind it, on
+// arbitrary rows, masks and ranges; seen / ban (both or neither, with penalty) add the repetition processors.  top_ids / top_lp [B][k].
+extern "C" int wm_op_logits_topk(float* logits, int32_t* ids, float* logprob, int32_t* top_ids, float* top_lp, int top_k, const float* x,
+                                 const float* ln_g, const float* ln_b, const float* emb, const float* mask, const int32_t* ranges,
+                                 int timestamp_begin, const uint32_t* seen, const uint32_t* ban, float penalty, int B, int N, int K, int dtype) {
+    if (!logprob || !top_ids || !top_lp || top_k < 1 || (!seen != !ban) || (seen && !(penalty > 0.f))) return fail(WM_E_ARG, "bad argument");
+    return op_logits(logits, ids, logprob, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype, seen, ban, penalty, nullptr, nullptr, 0,
+                     nullptr, nullptr, top_k, top_ids, top_lp);
 }
 // Forced-token replay, shared by wm_op_repeat_sets and wm_op_seq_bias_hits: repeat_init on each row's prompt tokens[b][0 ..
 // prompt_len[b]), then one argmax launch per step that is handed the row's next id of the table as its only candidate, so it appends

@@ -211,11 +211,12 @@ class Whisper:
                                  tb, no_ts, max_init)
         return opts, (p, sup, bsup)
 
-    def _set_repeat(self, rp, sb=None):
-        """wm_set_repeat_options with a call's (penalty, n) and wm_set_sequence_bias with its lists (sb: _lib.seq_bias_args, None =
-        off): every greedy call sets them, so a call without the arguments runs with all of them off.  The table is rebuilt only
-        when the lists differ from the last call's."""
+    def _set_repeat(self, rp, sb=None, top_k=0):
+        """wm_set_repeat_options with a call's (penalty, n), wm_set_sequence_bias with its lists (sb: _lib.seq_bias_args, None =
+        off) and wm_set_top_k with its k: every greedy call sets them, so a call without the arguments runs with all of them off.
+        The table is rebuilt only when the lists differ from the last call's."""
         _lib.check(_lib.lib().wm_set_repeat_options(self._h, rp[0], rp[1]))
+        _lib.check(_lib.lib().wm_set_top_k(self._h, top_k))
         key = None if sb is None else sb[0]
         if key != self._sb_key:
             ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
@@ -336,14 +337,33 @@ class Whisper:
     def _split_times(times, n, B):
         return [times[b, :n[b]].tolist() for b in range(B)]
 
+    def _top_k(self, slot, k, plens):
+        """wm_transcribe_top_k of the log-prob pass just collected on `slot` -> (top_ids, top_logprobs): per utterance an int32 /
+        float32 array [generated ids, k], the row's prompt (plens[b] ids) cut off."""
+        B, total = self.last_tokens.shape
+        n = self.last_counts
+        ids, lps = np.zeros((B, total, k), np.int32), np.zeros((B, total, k), np.float32)
+        _lib.check(_lib.lib().wm_transcribe_top_k(self._h, slot, _ip(ids), _fp(lps)))
+        return ([ids[b, plens[b]:max(n[b], plens[b])].copy() for b in range(B)],
+                [lps[b, plens[b]:max(n[b], plens[b])].copy() for b in range(B)])
+
+    @staticmethod
+    def _plens(prompt, prompts, B):
+        return [len(prompt)] * B if prompts is None else [len(r) for r in prompts]
+
     def transcribe_batch(self, mel, prompt: Sequence[int] = PROMPT, eot: int = EOT, max_loop: int = MAX_LOOP,
                          ignore_eot: bool = False, suppress_tokens: Sequence[int] = (),
                          begin_suppress_tokens: Sequence[int] = (), timestamps=None, return_token_timestamps: bool = False,
                          n_frames=None, prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False,
                          no_speech_token: Optional[int] = None, n_init: Optional[int] = None,
                          detect_language: Optional[Sequence[int]] = None, repetition_penalty: Optional[float] = None,
-                         no_repeat_ngram_size: Optional[int] = None, sequence_bias=None, bad_words_ids=None):
+                         no_repeat_ngram_size: Optional[int] = None, sequence_bias=None, bad_words_ids=None, top_k: Optional[int] = None):
         """Batched Whisper.transcribe: one List[int] per utterance = prompt + generated ids (+ eot when hit).
+        top_k (1..8, needs return_logprobs): the result gets one more, last element (top_ids, top_logprobs) — per
+        utterance an int32 / float32 array [generated ids, k]: at every generated position the k candidates with the largest
+        processed score (HF generate(output_scores=True), then log_softmax(scores).topk(k)), descending, equal scores lowest id
+        first, over the set the log-probs normalise over.  Rank 0 is the emitted id with token_logprobs' value; a rank with no finite
+        candidate left holds id -1 and -inf.  Not in the long-form and chunked calls.
         sequence_bias / bad_words_ids: HF generate's options of the same names, given as ids.  sequence_bias is a dict
         {(ids...): bias} or a list of [[ids...], bias]: a length-1 sequence always adds its bias to that id's logit; a longer one adds it
         to its last id when the row's history (its prompt, then what it generated) ends with the ids before it.  bad_words_ids is a
@@ -372,6 +392,17 @@ class Whisper:
         probability of that id under the raw logits at each row's <|startoftranscript|> position, prompt length - n_init; the second
         element becomes (token_logprobs, avg_logprob, no_speech_prob).  n_init: the number of initial ids (<|startoftranscript|>
         first); defaults to the shared prompt's length, required with prompts=."""
+        k = _lib.top_k_arg(top_k, return_logprobs)
+        res = self._transcribe_batch(mel, prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps,
+                                     return_token_timestamps, n_frames, prompts, return_logprobs, no_speech_token, n_init, detect_language,
+                                     repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, k)
+        # the alternatives rode the call's log-prob pass: its tables are fetched once the pass is collected
+        return res + (self._top_k(0, k, self._plens(prompt, prompts, len(res[0]))),) if k else res
+
+    def _transcribe_batch(self, mel, prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps,
+                          return_token_timestamps, n_frames, prompts, return_logprobs, no_speech_token, n_init, detect_language,
+                          repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, k):
+        """transcribe_batch without the top-k tables; k: what wm_set_top_k gets for the pass (0 = off)"""
         rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
         sb = _lib.seq_bias_args(sequence_bias, bad_words_ids, self.config.vocab_size)
         lang = None
@@ -380,7 +411,7 @@ class Whisper:
         ns = None if lang else self._ns_args(no_speech_token, n_init, prompt, prompts, return_logprobs)
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
-        self._set_repeat(rp, sb)
+        self._set_repeat(rp, sb, k)
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]
@@ -441,8 +472,9 @@ class Whisper:
                              no_speech_threshold: Optional[float] = None, no_speech_token: Optional[int] = None,
                              detect_language: Optional[Sequence[int]] = None, return_token_timestamps: bool = False,
                              repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-                             sequence_bias=None, bad_words_ids=None):
+                             sequence_bias=None, bad_words_ids=None, top_k: Optional[int] = None):
         """Sequential long-form transcription (HF generate's long-form path, greedy).
+        top_k: refused here (ValueError) — the top-k alternatives of transcribe_batch have no place in this result yet.
         sequence_bias / bad_words_ids: as transcribe_batch, matched against each window's own decoder ids.
         repetition_penalty / no_repeat_ngram_size: as transcribe_batch.  Every window's pass sees that window's decoder
         ids only — its prompt, a carried previous text included, then what it generates — as HF's per-window generate does.
@@ -466,6 +498,8 @@ class Whisper:
         array's length).  timestamps: (timestamp_begin, no_timestamps_id, max_initial_timestamp_index | None), required.
         Returns per utterance {"sequence": ids, "segments": [{"start", "end", "tokens"}]} — HF's return_segments output with
         the padding-free sequences row; return_stats also returns {"windows", "stalled"}."""
+        if top_k is not None:
+            raise ValueError("top_k is not available in long-form transcription (use transcribe_batch on 30 s windows)")
         rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
         sb = _lib.seq_bias_args(sequence_bias, bad_words_ids, self.config.vocab_size)
         lo, _keep3 = _lib.long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token, logprob_threshold,
@@ -571,7 +605,7 @@ class Whisper:
                           prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False,
                           no_speech_token: Optional[int] = None, n_init: Optional[int] = None,
                           detect_language: Optional[Sequence[int]] = None, repetition_penalty: Optional[float] = None,
-                          no_repeat_ngram_size: Optional[int] = None, sequence_bias=None, bad_words_ids=None):
+                          no_repeat_ngram_size: Optional[int] = None, sequence_bias=None, bad_words_ids=None, top_k: Optional[int] = None):
         """Pipelined form (wm_transcribe_submit): enqueue encoder + greedy loop for this batch on pipeline slot 0..7 and
         return at once; `transcribe_wait(slot)` collects the ids.  Submitting batch i+1 before waiting for batch i lets
         its encoder overlap batch i's decode.  return_token_timestamps / n_frames: as transcribe_batch; the matching
@@ -580,19 +614,23 @@ class Whisper:
         (ids, (token_logprobs, avg_logprob, no_speech_prob)).  detect_language: as transcribe_batch; the matching transcribe_wait
         returns what transcribe_batch returns.  repetition_penalty / no_repeat_ngram_size: as transcribe_batch; the pass keeps the
         values it was submitted with, and under coalesce = 2 it pairs only with a submit that carries the same values.
-        sequence_bias / bad_words_ids: as transcribe_batch, kept and paired likewise (the same lists as the previous call = the same table)."""
+        sequence_bias / bad_words_ids: as transcribe_batch, kept and paired likewise (the same lists as the previous call = the same table).
+        top_k: as transcribe_batch, kept and paired likewise; the matching transcribe_wait returns the extra last element."""
         rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
         sb = _lib.seq_bias_args(sequence_bias, bad_words_ids, self.config.vocab_size)
+        k = _lib.top_k_arg(top_k, return_logprobs)
         lang = None
         if detect_language is not None:
             lang = self._lang_args(detect_language, n_init, prompt, prompts, return_token_timestamps, no_speech_token, return_logprobs)
         ns = None if lang else self._ns_args(no_speech_token, n_init, prompt, prompts, return_logprobs)
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
-        self._set_repeat(rp, sb)
+        self._set_repeat(rp, sb, k)
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]
+        self._pending_top_k = getattr(self, "_pending_top_k", {})
+        self._pending_top_k[slot] = (k, self._plens(prompt, prompts, B)) if k else None
         if lang:
             total, tag = self._lang_call(slot, ptr, on_dev, B, opts, p, prompts, max_loop, lang, return_logprobs, no_speech_token)
             self._pending = getattr(self, "_pending", {})
@@ -628,6 +666,11 @@ class Whisper:
         self._pending[slot] = (B, len(p) + 1 + max_loop, keep, (max_loop, self._n_align) if return_token_timestamps else None)
 
     def transcribe_wait(self, slot: int = 0):
+        top = getattr(self, "_pending_top_k", {}).pop(slot, None)
+        res = self._transcribe_wait(slot)
+        return res + (self._top_k(slot, *top),) if top else res
+
+    def _transcribe_wait(self, slot):
         B, total, _keep, tt = self._pending.pop(slot)
         if isinstance(tt, tuple) and tt and tt[0] == "lang":
             return self._lang_collect(slot, B, total, tt[1], tt[2], tt[3],

@@ -320,6 +320,45 @@ def logits_argmax(x, ln_g, ln_b, emb, dtype=DT_F32, mask=None, ranges=None, time
     return logits, ids
 
 
+def logits_topk(x, ln_g, ln_b, emb, k, dtype=DT_F32, mask=None, ranges=None, timestamp_begin: int = 0, seen=None, ban=None,
+                penalty: float = 1.0):
+    """logits_argmax(return_logprobs=True) with the top-k alternatives (wm_op_logits_topk): (logits [B, N], ids [B],
+    logprob [B], top_ids [B, k] int32, top_logprobs [B, k] float32) from the decode step's logits kernel, the top-k instantiation of
+    its arg-max launch and the selection launch behind it.  Per row the k candidates the mask and the ranges leave with the largest
+    logit, descending, equal logits lowest id first, each with logit - logsumexp over those candidates (a forced timestamp: over the
+    admissible timestamps alone); rank 0 equals (ids, logprob); a rank with no finite candidate left holds (-1, -inf).  mask, ranges,
+    timestamp_begin, seen / ban / penalty: as logits_argmax.  1 <= k <= 8."""
+    f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    x, emb, mask = f(x), f(emb), f(mask)
+    g, b = f(ln_g).ravel(), f(ln_b).ravel()
+    if x.ndim != 2 or emb.ndim != 2 or emb.shape[1] != x.shape[1] or g.size != x.shape[1] or b.size != x.shape[1]:
+        raise ValueError("x must be [B, K], emb [N, K], ln_g / ln_b [K]")
+    B, K = x.shape
+    N = emb.shape[0]
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= 8:
+        raise ValueError("k must be an integer of [1, 8]")
+    if mask is not None and mask.size != N:
+        raise ValueError("mask must have N elements")
+    rg = None
+    if ranges is not None:
+        rg = np.ascontiguousarray(ranges, np.int32)
+        if rg.shape != (B, 4):
+            raise ValueError("ranges must be [B, 4]")
+    sets = [None, None]
+    if seen is not None or ban is not None:
+        sets = [np.ascontiguousarray(a, np.uint32) for a in (seen, ban) if a is not None]
+        if len(sets) != 2 or any(a.shape != (B, (N + 31) // 32) for a in sets):
+            raise ValueError("seen and ban must both be [B, ceil(N / 32)] uint32")
+    ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    up = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint32))
+    logits, ids, lp = np.zeros((B, N), np.float32), np.zeros(B, np.int32), np.zeros(B, np.float32)
+    top_ids, top_lp = np.zeros((B, int(k)), np.int32), np.zeros((B, int(k)), np.float32)
+    _lib.check(_lib.lib().wm_op_logits_topk(_fp(logits), ip(ids), _fp(lp), ip(top_ids), _fp(top_lp), int(k), _fp(x), _fp(g), _fp(b), _fp(emb),
+                                            _fp(mask.ravel() if mask is not None else None), ip(rg), int(timestamp_begin), up(sets[0]),
+                                            up(sets[1]), float(penalty), B, N, K, dtype))
+    return logits, ids, lp, top_ids, top_lp
+
+
 def score_logits(x, ln_g, ln_b, emb, target, dtype=DT_F32):
     """The score pass's vocabulary side alone (wm_op_score_logits): (logprob [M], top_id [M]) with logprob[r] =
     z[r][target[r]] - logsumexp(z[r]) over z = layer_norm(x)·embᵀ (0 where target[r] < 0) and top_id[r] = argmax z[r], lowest id on
