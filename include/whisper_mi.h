@@ -660,6 +660,30 @@ int wm_op_resample(float* out, const void* in, int in_dtype, const int32_t* n_in
                    int32_t* n_out);
 int wm_op_resample_taps(int sr_in, float* taps, int64_t cap, int* orig, int* nw, int* width);
 
+/* ---- the log-mel front end one stage at a time (known-answer tests) ----------------------------------------------
+ * Each hook launches its kernel through the launcher wm_log_mel / wm_log_mel_long use, on host arrays.  The DFT stage between frames
+ * and mel_log is wm_op_matmul_nt(M, 512, 416, WM_F32) with the basis below as B: the same launcher and kernel.  WM_E_ARG, nothing
+ * launched: a null pointer, a size outside the ranges given, an offset or an item that leaves its array.
+ * wm_op_fe_tables (host only, no HIP call): the tables of a model with n_mels filters (1..128), computed in float64 and rounded once —
+ *   window [400] the periodic Hann window; dft [512][416] the real-DFT basis, row k = cos(2 pi k n / 400), row 256 + k = -sin(...),
+ *   k < 201, n < 400, every other entry 0; fb [201][n_mels] the slaney mel filters; band [n_mels][2] = [lo, hi), the bins outside which
+ *   filter m is 0.
+ * wm_op_fe_frames: frames_kernel — out [B][n][416] = the reflect-padded, windowed frames t0 .. t0 + n of pcm [B][N], columns 400..415
+ *   zero.  N > 200, t0 + n <= N / 160.  n_samples [B] or NULL: given, zero_tails_kernel first zeroes pcm[b][n_samples[b]..N) as the
+ *   runtime does after its upload.  out holds B * n + 1 rows and is in and out: the guard row keeps the caller's values.
+ * wm_op_fe_mel_log: mel_log_kernel — spec [B][n][512] (re at k, im at 256 + k) -> logmel[b][m][t_out + t] = log10(max(sum_k fb[k][m]
+ *   (re^2 + im^2), 1e-10)); logmel [B][n_mels][out_frames] is in and out, t_out + n <= out_frames: columns outside [t_out, t_out + n)
+ *   keep the caller's values.
+ * wm_op_fe_mel_norm: per row of n values y = (max(x, max(x) - 8) + 4) / 4.  long_mode 0: mel_norm_kernel; 1: the two-stage
+ *   mel_max_partial_kernel + mel_norm_long_kernel of long audio.  logmel, out [B][n].
+ * wm_op_window_gather: window_gather_kernel — out[r][m][t] = mel[b][m][seek + t] for t < len, 0 for len <= t < W, for items [rows][3]
+ *   = (b, seek, len), len <= W, seek + len <= F.  mel [B][n_mels][F]; out [rows][n_mels][W], in and out. */
+int wm_op_fe_tables(int n_mels, float* window, float* dft, float* fb, int32_t* band);
+int wm_op_fe_frames(float* out, const float* pcm, const int32_t* n_samples, int B, int N, int n, int t0);
+int wm_op_fe_mel_log(float* logmel, const float* spec, int B, int n, int n_mels, int out_frames, int t_out);
+int wm_op_fe_mel_norm(float* out, const float* logmel, int B, int64_t n, int long_mode);
+int wm_op_window_gather(float* out, const float* mel, const int32_t* items, int rows, int B, int n_mels, int F, int W);
+
 /* ---- op-level entry points (host pointers; known-answer tests only) ------------------------------------------
  * Same argument meaning as the reference ops: out-param first, caller-allocated. */
 /* matmul(C, A, B, bias)  whisper_tensor.mojo:151-246 : C[M,N] = A[M,K]·B[N,K]ᵀ (+bias[N], may be NULL).

@@ -205,3 +205,49 @@ def test_errors_empty_and_pending_slot(hip, micro_cfg, micro_weights):
         mc.transcribe_long_form(mels, timestamps=ts, **kw)
     assert mc.transcribe_wait(0) == want
     mc.close()
+
+
+def log_mel_long_raw(m, buf, n):
+    """wm_log_mel_long on rows that are already padded to one stride -> (mel [B, n_mels, stride // 160], n_frames [B])"""
+    from whisper_mojo_amd import _lib
+    B, stride = buf.shape
+    out = np.empty((B, m.config.n_mels, stride // 160), np.float32)
+    nf = np.zeros(B, np.int32)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    _lib.check(_lib.lib().wm_log_mel_long(m._h, buf.ctypes.data_as(fp), n.ctypes.data_as(ip), B, stride, out.ctypes.data_as(fp),
+                                          nf.ctypes.data_as(ip)))
+    return out, nf
+
+
+@pytest.mark.parametrize("B,F", [(96, 1000), (33, 1473)])
+def test_log_mel_long_across_frame_chunk_seams(hip, micro_cfg, micro_weights, B, F):
+    """The long path runs frames / DFT / mel over chunks of nt frames of all rows at once: B = 96 rows of 1000 frames take chunks of 480
+    (seams at 480 and 960), B = 33 rows of 1473 frames chunks of 1440 and a last one of 33.  A row alone takes one chunk, and has to
+    give the same bits."""
+    from oracle import logmel_oracle as lo
+    from test_frontend_ref import long_chunk_frames
+    nt = long_chunk_frames(F, B)
+    assert nt < F and long_chunk_frames(F, 1) >= F, "the case no longer crosses a chunk seam"
+    assert (nt, F % nt) == {96: (480, 40), 33: (1440, 33)}[B]
+    stride = 160 * F
+    m = make_model(micro_cfg, micro_weights, max_batch=2)
+    distinct = [lo.synth_audio(60 + k, stride) for k in range(4)]
+    buf = np.stack([distinct[b % 4] for b in range(B)])
+    n = np.full(B, stride, np.int32)
+    short = {5: stride - 1, B // 2: 160 * (F // 2) + 7, B - 1: 1234}  # the samples behind a length stay in the buffer
+    for b, v in short.items():
+        n[b] = v
+    mel, nf = log_mel_long_raw(m, buf, n)
+    assert mel.shape == (B, micro_cfg.n_mels, F)
+    assert nf.tolist() == [min(-(-int(v) // 160), F) for v in n]
+    for b in (0, B // 2, B - 1):
+        alone, nf1 = log_mel_long_raw(m, buf[b:b + 1], n[b:b + 1])
+        assert nf1[0] == nf[b]
+        assert np.array_equal(alone[0].view(np.uint32), mel[b].view(np.uint32)), b
+    for b in list(range(4)) + sorted(short):  # the four recordings and the three shortened rows
+        err = np.abs(mel[b] - lo.log_mel(buf[b, :n[b]], n_frames=F, n_mels=micro_cfg.n_mels))
+        assert err.max() < 2e-3 and err.mean() < 1e-4, (b, int(n[b]), err.max(), err.mean())
+    for b in range(4, B):  # every copy of a recording equals the first
+        if b not in short:
+            assert np.array_equal(mel[b].view(np.uint32), mel[b % 4].view(np.uint32)), b
+    m.close()

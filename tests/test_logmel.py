@@ -118,3 +118,34 @@ def test_long_form_and_language_id(micro_cfg, micro_weights):
     assert np.abs(p - rp).max() < 1e-4
     ids, pb = frontend.detect_language(m, np.stack([mel, mel]), sot=7, lang_first=100, lang_last=131)
     assert ids.tolist() == [lid, lid] and np.allclose(pb[0], p) and np.allclose(pb[1], p)
+
+
+@pytest.mark.gpu
+def test_gpu_front_end_across_the_16_utterance_group(micro_cfg, micro_weights):
+    """The 30 s path runs its frames / DFT / mel kernels over groups of 16 utterances: 35 clips take three groups, the last of three
+    rows.  Every row equals its clip computed alone, bit for bit where the groups meet and end, and the oracle within the bounds above."""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from oracle import logmel_oracle as lo
+    from whisper_mojo_amd import frontend
+    from whisper_mojo_amd.loader import WeightLoader
+    from whisper_mojo_amd.whisper import Whisper
+    B = 35
+    m = Whisper(micro_cfg, max_batch=B)
+    m.load(WeightLoader.from_array(micro_weights))
+    win = micro_cfg.n_frames * frontend.HOP
+    # full window, short, nothing, one sample, over-long, odd lengths; row 34 is empty, rows 0 / 16 / 32 are full windows of other seeds
+    lengths = [[win, 5000, 0, 1, win + 4000, 12345, win - 1, 20000][i % 8] for i in range(B)]
+    lengths[34] = 0
+    assert {0, 1, win}.issubset(lengths) and max(lengths) > win
+    audios = [lo.synth_audio(100 + i, n) for i, n in enumerate(lengths)]
+    mels = frontend.log_mel(m, audios)
+    assert mels.shape == (B, micro_cfg.n_mels, micro_cfg.n_frames)
+    for b in (0, 15, 16, 31, 32, 34):
+        alone = frontend.log_mel(m, [audios[b]])[0]
+        assert np.array_equal(alone.view(np.uint32), mels[b].view(np.uint32)), b
+    for b, a in enumerate(audios):
+        err = np.abs(mels[b] - lo.log_mel(a, n_frames=micro_cfg.n_frames, n_mels=micro_cfg.n_mels))
+        assert err.max() < 2e-3 and err.mean() < 1e-4, (b, lengths[b], err.max(), err.mean())
+    m.close()

@@ -44,6 +44,7 @@ SYMBOLS = [
     "wm_op_gemm_nt_epi",
     "wm_resample_len", "wm_resample_pcm", "wm_op_resample", "wm_op_resample_taps",
     "wm_set_top_k", "wm_transcribe_top_k", "wm_op_logits_topk",
+    "wm_op_fe_tables", "wm_op_fe_frames", "wm_op_fe_mel_log", "wm_op_fe_mel_norm", "wm_op_window_gather",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -334,6 +335,11 @@ def lib():
     L.wm_resample_pcm.argtypes = [vp, vp, C.c_int, C.c_int, ip, C.c_int, i64, C.c_int, vp, C.c_int, i64, ip]
     L.wm_op_resample.argtypes = [fp, vp, C.c_int, ip, C.c_int, i64, C.c_int, i64, ip]
     L.wm_op_resample_taps.argtypes = [C.c_int, fp, i64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.wm_op_fe_tables.argtypes = [C.c_int, fp, fp, fp, ip]
+    L.wm_op_fe_frames.argtypes = [fp, fp, ip] + [C.c_int] * 4
+    L.wm_op_fe_mel_log.argtypes = [fp, fp] + [C.c_int] * 5
+    L.wm_op_fe_mel_norm.argtypes = [fp, fp, C.c_int, i64, C.c_int]
+    L.wm_op_window_gather.argtypes = [fp, fp, ip] + [C.c_int] * 5
     _lib = L
     return L
 

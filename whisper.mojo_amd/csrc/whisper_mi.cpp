@@ -3429,13 +3429,19 @@ static const int FE_NFFT = 400, FE_HOP = 160, FE_NFREQ = 201;
 static double hz_to_mel_slaney(double f) { return f >= 1000.0 ? 15.0 + std::log(f / 1000.0) * (27.0 / std::log(6.4)) : 3.0 * f / 200.0; }
 static double mel_to_hz_slaney(double m) { return m >= 15.0 ? 1000.0 * std::exp(std::log(6.4) / 27.0 * (m - 15.0)) : 200.0 * m / 3.0; }
 
-static int frontend_init(wm_model* m) {
-    if (m->fe.ready) return 0;
-    const wm_dims& c = m->cfg.dims;
-    const int n_mels = c.n_mels, n_frames = 2 * c.n_audio_ctx, N = FE_HOP * n_frames, maxB = m->cfg.max_batch;
-    const double PI = 3.14159265358979323846;
-    std::vector<float> window(FE_NFFT), dft((size_t)512 * 416, 0.f), fb((size_t)FE_NFREQ * n_mels, 0.f);
-    for (int n = 0; n < FE_NFFT; ++n) window[n] = (float)(0.5 - 0.5 * std::cos(2.0 * PI * n / FE_NFFT));  // periodic Hann
+// The front end's four tables for n_mels filters, built once on the host in float64 and rounded once: the periodic Hann window [400],
+// the real-DFT basis [512][416] (cos at row k, -sin at row 256 + k, k < 201; every other entry 0), the slaney filter bank
+// [201][n_mels] and, per filter, the interval [lo, hi) of bins outside which it is 0 (band [n_mels][2]; an empty filter gives 0, 0).
+static const double FE_PI = 3.14159265358979323846;
+static void frontend_window(std::vector<float>& window) {
+    window.assign(FE_NFFT, 0.f);
+    for (int n = 0; n < FE_NFFT; ++n) window[n] = (float)(0.5 - 0.5 * std::cos(2.0 * FE_PI * n / FE_NFFT));  // periodic Hann
+}
+static void frontend_tables(int n_mels, std::vector<float>& window, std::vector<float>& dft, std::vector<float>& fb, std::vector<int>& band) {
+    const double PI = FE_PI;
+    frontend_window(window);
+    dft.assign((size_t)512 * 416, 0.f);
+    fb.assign((size_t)FE_NFREQ * n_mels, 0.f);
     for (int k = 0; k < FE_NFREQ; ++k)
         for (int n = 0; n < FE_NFFT; ++n) {
             const double ang = 2.0 * PI * (double)((k * n) % FE_NFFT) / FE_NFFT;
@@ -3446,7 +3452,7 @@ static int frontend_init(wm_model* m) {
     std::vector<double> ff(n_mels + 2);
     const double m0 = hz_to_mel_slaney(0.0), m1 = hz_to_mel_slaney(8000.0);
     for (int i = 0; i < n_mels + 2; ++i) ff[i] = mel_to_hz_slaney(m0 + (m1 - m0) * i / (n_mels + 1));
-    std::vector<int> band(2 * n_mels);
+    band.assign(2 * (size_t)n_mels, 0);
     for (int mm = 0; mm < n_mels; ++mm) {
         int lo = FE_NFREQ, hi = 0;
         const double enorm = 2.0 / (ff[mm + 2] - ff[mm]);
@@ -3463,6 +3469,15 @@ static int frontend_init(wm_model* m) {
         band[2 * mm] = lo < hi ? lo : 0;
         band[2 * mm + 1] = lo < hi ? hi : 0;
     }
+}
+
+static int frontend_init(wm_model* m) {
+    if (m->fe.ready) return 0;
+    const wm_dims& c = m->cfg.dims;
+    const int n_mels = c.n_mels, n_frames = 2 * c.n_audio_ctx, N = FE_HOP * n_frames, maxB = m->cfg.max_batch;
+    std::vector<float> window, dft, fb;
+    std::vector<int> band;
+    frontend_tables(n_mels, window, dft, fb, band);
     WMCHK(upload(m->fe.window, window.data(), window.size(), WM_F32));
     WMCHK(upload(m->fe.dft, dft.data(), dft.size(), WM_F32));
     WMCHK(upload(m->fe.fb, fb.data(), fb.size(), WM_F32));
@@ -3534,6 +3549,97 @@ extern "C" int wm_log_mel(wm_model* m, const float* pcm, const int32_t* n_sample
     if (mel_out) HIPCHK(hipMemcpyAsync(mel_out, m->fe.mel.p, (size_t)B * c.n_mels * 2 * c.n_audio_ctx * 4, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     return 0;
+}
+
+// ---- the front end's stages one at a time (known-answer tests; include/whisper_mi.h) -- each through the launcher the runtime uses
+static const int FE_MAX_MELS = 128, FE_MAX_GRID_Y = 65535;
+extern "C" int wm_op_fe_tables(int n_mels, float* window, float* dft, float* fb, int32_t* band) {
+    if (!window || !dft || !fb || !band || n_mels < 1 || n_mels > FE_MAX_MELS) return fail(WM_E_ARG, "bad argument (1 <= n_mels <= %d)", FE_MAX_MELS);
+    std::vector<float> w, d, f;
+    std::vector<int> bd;
+    frontend_tables(n_mels, w, d, f, bd);
+    memcpy(window, w.data(), w.size() * 4);
+    memcpy(dft, d.data(), d.size() * 4);
+    memcpy(fb, f.data(), f.size() * 4);
+    memcpy(band, bd.data(), bd.size() * 4);
+    return 0;
+}
+extern "C" int wm_op_fe_frames(float* out, const float* pcm, const int32_t* n_samples, int B, int N, int n, int t0) {
+    if (!out || !pcm || B <= 0 || B > FE_MAX_GRID_Y || N <= 200 || n <= 0 || t0 < 0)
+        return fail(WM_E_ARG, "bad argument (B >= 1, N > 200, n >= 1, t0 >= 0)");
+    if ((int64_t)t0 + n > N / FE_HOP)
+        return fail(WM_E_ARG, "frames [%d, %lld) leave the %d frames of %d samples", t0, (long long)t0 + n, N / FE_HOP, N);
+    if (n_samples)
+        for (int b = 0; b < B; ++b)
+            if (n_samples[b] < 0 || n_samples[b] > N) return fail(WM_E_ARG, "n_samples[%d]=%d out of range", b, n_samples[b]);
+    std::vector<float> window;
+    frontend_window(window);
+    TmpDev tmp;
+    DevBuf &dp = tmp.add(), &dl = tmp.add(), &dw = tmp.add(), &dout = tmp.add();
+    const size_t n_out = ((size_t)B * n + 1) * 416;  // one guard row behind the last frame
+    WMCHK(upload(dp, pcm, (size_t)B * N, WM_F32));
+    WMCHK(upload(dw, window.data(), window.size(), WM_F32));
+    WMCHK(upload(dout, out, n_out, WM_F32));  // in and out: what the kernel does not store keeps the caller's value
+    if (n_samples) {
+        WMCHK(upload_bytes(dl, n_samples, (size_t)B * 4));
+        launch_zero_tails(dp.as<float>(), dl.as<int>(), B, N, nullptr);
+    }
+    launch_frames(dp.as<float>(), dout.as<float>(), dw.as<float>(), B, N, n, FE_HOP, nullptr, t0);
+    HIPCHK(hipGetLastError());
+    return download_f32(out, dout, n_out, WM_F32);
+}
+extern "C" int wm_op_fe_mel_log(float* logmel, const float* spec, int B, int n, int n_mels, int out_frames, int t_out) {
+    if (!logmel || !spec || B <= 0 || B > FE_MAX_GRID_Y || n <= 0 || n_mels < 1 || n_mels > FE_MAX_MELS || t_out < 0)
+        return fail(WM_E_ARG, "bad argument (B >= 1, n >= 1, 1 <= n_mels <= %d, t_out >= 0)", FE_MAX_MELS);
+    if (out_frames <= 0 || (int64_t)t_out + n > out_frames)
+        return fail(WM_E_ARG, "frames [%d, %lld) leave the row of %d", t_out, (long long)t_out + n, out_frames);
+    std::vector<float> window, dft, fb;
+    std::vector<int> band;
+    frontend_tables(n_mels, window, dft, fb, band);
+    TmpDev tmp;
+    DevBuf &ds = tmp.add(), &df = tmp.add(), &db = tmp.add(), &dout = tmp.add();
+    const size_t n_out = (size_t)B * n_mels * out_frames;
+    WMCHK(upload(ds, spec, (size_t)B * n * 512, WM_F32));
+    WMCHK(upload(df, fb.data(), fb.size(), WM_F32));
+    WMCHK(upload_bytes(db, band.data(), band.size() * 4));
+    WMCHK(upload(dout, logmel, n_out, WM_F32));  // in and out
+    launch_mel_log(ds.as<float>(), df.as<float>(), db.as<int>(), dout.as<float>(), B, n, n_mels, nullptr, out_frames, t_out);
+    HIPCHK(hipGetLastError());
+    return download_f32(logmel, dout, n_out, WM_F32);
+}
+extern "C" int wm_op_fe_mel_norm(float* out, const float* logmel, int B, int64_t n, int long_mode) {
+    if (!out || !logmel || B <= 0 || B > FE_MAX_GRID_Y || n <= 0 || (long_mode != 0 && long_mode != 1)) return fail(WM_E_ARG, "bad argument");
+    if (n > INT32_MAX) return fail(WM_E_ARG, "n = %lld exceeds 2^31 - 1", (long long)n);
+    TmpDev tmp;
+    DevBuf &dx = tmp.add(), &dy = tmp.add(), &dpart = tmp.add();
+    WMCHK(upload(dx, logmel, (size_t)B * n, WM_F32));
+    if (long_mode) {
+        WMCHK(dpart.alloc((size_t)B * 256 * 4));
+        launch_mel_norm_long(dx.as<float>(), dpart.as<float>(), B, (size_t)n, nullptr);  // in place
+    } else {
+        WMCHK(dy.alloc((size_t)B * n * 4));
+        launch_mel_norm(dx.as<float>(), dy.as<float>(), B, (int)n, nullptr);
+    }
+    HIPCHK(hipGetLastError());
+    return download_f32(out, long_mode ? dx : dy, (size_t)B * n, WM_F32);
+}
+extern "C" int wm_op_window_gather(float* out, const float* mel, const int32_t* items, int rows, int B, int n_mels, int F, int W) {
+    if (!out || !mel || !items || rows <= 0 || rows > FE_MAX_GRID_Y || B <= 0 || n_mels < 1 || n_mels > FE_MAX_MELS || F <= 0 || W <= 0)
+        return fail(WM_E_ARG, "bad argument");
+    for (int r = 0; r < rows; ++r) {
+        const int32_t* t = items + 3 * (size_t)r;
+        if (t[0] < 0 || t[0] >= B || t[1] < 0 || t[2] < 0 || t[2] > W || (int64_t)t[1] + t[2] > F)
+            return fail(WM_E_ARG, "item %d = (%d, %d, %d) leaves mel [%d][%d][%d] or the window of %d frames", r, t[0], t[1], t[2], B, n_mels, F, W);
+    }
+    TmpDev tmp;
+    DevBuf &dm = tmp.add(), &di = tmp.add(), &dout = tmp.add();
+    const size_t n_out = (size_t)rows * n_mels * W;
+    WMCHK(upload(dm, mel, (size_t)B * n_mels * F, WM_F32));
+    WMCHK(upload_bytes(di, items, (size_t)rows * 3 * 4));
+    WMCHK(upload(dout, out, n_out, WM_F32));  // in and out
+    launch_window_gather(dm.as<float>(), di.as<int>(), dout.as<float>(), rows, n_mels, F, W, nullptr);
+    HIPCHK(hipGetLastError());
+    return download_f32(out, dout, n_out, WM_F32);
 }
 
 extern "C" int wm_transcribe_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B, int stride, const wm_decode_opts* o,

@@ -525,3 +525,67 @@ def seq_bias_hits(tokens, prompt_len, n_ids, vocab: int, sequence_bias, bad_word
                                               int(eot), ip(a[0]), ip(a[1]), _fp(a[2]), a[3], ip(a[4]), ip(a[5]), a[6], int(steps)))
     S = int(ns[0])
     return sid[:S].copy(), hit, sbias[:, :, :S].copy(), sflags[:, :, :S].copy()
+
+
+def fe_tables(n_mels: int):
+    """The front end's tables (wm_op_fe_tables, host only): (window [400], dft [512, 416], fb [201, n_mels], band [n_mels, 2])."""
+    window, dft = np.zeros(400, np.float32), np.zeros((512, 416), np.float32)
+    fb, band = np.zeros((201, max(1, int(n_mels))), np.float32), np.zeros((max(1, int(n_mels)), 2), np.int32)
+    _lib.check(_lib.lib().wm_op_fe_tables(int(n_mels), _fp(window), _fp(dft), _fp(fb), band.ctypes.data_as(C.POINTER(C.c_int32))))
+    return window, dft, fb, band
+
+
+def fe_frames(pcm, n: int, t0: int = 0, n_samples=None, fill: float = 0.0):
+    """frames_kernel alone (wm_op_fe_frames): pcm [B, N] -> (frames [B, n, 416] of frames t0 .. t0 + n, guard [416]); n_samples [B]:
+    zero_tails_kernel runs first.  Everything starts as `fill`; guard is the row behind the last frame, which no kernel may store."""
+    p = np.ascontiguousarray(pcm, np.float32)
+    if p.ndim != 2:
+        raise ValueError("pcm must be [B, N]")
+    B, N = p.shape
+    ns = None
+    if n_samples is not None:
+        ns = np.ascontiguousarray(np.asarray(n_samples, np.int32).reshape(-1))
+        if ns.size != B:
+            raise ValueError(f"n_samples needs one entry per row ({B})")
+    out = np.full((B * max(0, int(n)) + 1, 416), fill, np.float32)
+    _lib.check(_lib.lib().wm_op_fe_frames(_fp(out), _fp(p), None if ns is None else ns.ctypes.data_as(C.POINTER(C.c_int32)), B, N, int(n), int(t0)))
+    return out[:-1].reshape(B, int(n), 416), out[-1]
+
+
+def fe_mel_log(spec, n_mels: int, out_frames=None, t_out: int = 0, logmel=None):
+    """mel_log_kernel alone (wm_op_fe_mel_log): spec [B, n, 512] -> logmel [B, n_mels, out_frames] (in and out; None: zeros), frames
+    written at columns [t_out, t_out + n).  out_frames None: n."""
+    s = np.ascontiguousarray(spec, np.float32)
+    if s.ndim != 3 or s.shape[2] != 512:
+        raise ValueError("spec must be [B, n, 512]")
+    B, n, _ = s.shape
+    F = n if out_frames is None else int(out_frames)
+    if logmel is None:
+        logmel = np.zeros((B, max(1, int(n_mels)), max(1, F)), np.float32)
+    _chk_out(logmel, (B, max(1, int(n_mels)), max(1, F)))
+    _lib.check(_lib.lib().wm_op_fe_mel_log(_fp(logmel), _fp(s), B, n, int(n_mels), F, int(t_out)))
+    return logmel
+
+
+def fe_mel_norm(logmel, long_mode: bool = False):
+    """The clamp / rescale of the log-mel (wm_op_fe_mel_norm): rows [B, n] -> (max(x, rowmax - 8) + 4) / 4.  long_mode: the two-stage
+    kernels of long audio, else mel_norm_kernel."""
+    x = np.ascontiguousarray(logmel, np.float32)
+    if x.ndim != 2:
+        raise ValueError("logmel must be [B, n]")
+    out = np.empty_like(x)
+    _lib.check(_lib.lib().wm_op_fe_mel_norm(_fp(out), _fp(x), x.shape[0], x.shape[1], int(bool(long_mode))))
+    return out
+
+
+def window_gather(mel, items, W: int, fill: float = 0.0):
+    """window_gather_kernel alone (wm_op_window_gather): mel [B, n_mels, F], items [(b, seek, len)] -> [rows, n_mels, W]; the output
+    starts as `fill`, so a cell the kernel does not store shows."""
+    m = np.ascontiguousarray(mel, np.float32)
+    it = np.ascontiguousarray(np.asarray(items, np.int32).reshape(-1, 3))
+    if m.ndim != 3:
+        raise ValueError("mel must be [B, n_mels, F]")
+    out = np.full((max(1, it.shape[0]), m.shape[1], max(1, int(W))), fill, np.float32)
+    _lib.check(_lib.lib().wm_op_window_gather(_fp(out), _fp(m), it.ctypes.data_as(C.POINTER(C.c_int32)), it.shape[0], m.shape[0], m.shape[1],
+                                              m.shape[2], int(W)))
+    return out
