@@ -11,8 +11,10 @@ CSRC="$ROOT/whisper.mojo_amd/csrc"
 PROBE="$ROOT/tools/micro/asan_exit_probe"
 SANFLAGS="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-omit-frame-pointer"
 if [ "${1:-build}" = build ]; then
+  # the library's sources as build.py lists them: no copy of the list to fall behind
+  SRCS=$(cd "$ROOT/whisper.mojo_amd" && python3 -c 'import sys; sys.path.insert(0, "."); import build; print(" ".join(build.SOURCES))')
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Wall -Wno-unused-function -ffp-contract=on $SANFLAGS \
-    -I "$ROOT/include" -x hip "$CSRC/whisper_mi.cpp" "$CSRC/kernels_encoder.hip" "$CSRC/kernels_decoder.hip" "$CSRC/kernels_frontend.hip" \
+    -I "$ROOT/include" -x hip $(for s in $SRCS; do echo "$CSRC/$s"; done) \
     -x hip "$ROOT/examples/main.cpp" -o "$EXE"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -std=c++17 $SANFLAGS -x hip "$ROOT/tools/micro/asan_exit_probe.hip" -o "$PROBE"
   echo "built $EXE and $PROBE"
@@ -47,7 +49,7 @@ else
       if [ $probe_sig -eq 1 ] && [ "$(grep -c 'AddressSanitizer: CHECK failed' "$log")" = 1 ] && grep -q "$SIG" "$log" && \
          [ "$(grep -n '^Done\.$' "$log" | cut -d: -f1)" -lt "$(grep -n 'CHECK failed' "$log" | cut -d: -f1)" ] && \
          grep -q "Quarantine.*Recycle" "$log" && grep -q "__cxa_finalize\|AsanThread::Destroy" "$log" && \
-         ! grep -q "whisper_mi.cpp\|kernels_.*\.hip\|main.cpp" "$log"; then
+         ! grep -q "whisper_mi\.cpp\|wm_[a-z]*\.cpp\|kernels_.*\.hip\|main\.cpp" "$log"; then
         echo "[tolerated] exit-time device-allocator CHECK of the sanitizer runtime (the bare probe shows it too); exit code $rc"
       else
         bad=1

@@ -21,9 +21,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libwhispermi.so")
 LIB_DEV = os.path.join(CSRC, "libwhispermi_dev.so")
-SOURCES = ["whisper_mi.cpp", "wm_ops.cpp", "kernels_encoder.hip", "kernels_decoder.hip", "kernels_frontend.hip", "kernels_align.hip", "kernels_score.hip",
-           "kernels_chunked.hip"]
-HEADERS = ["wm_device.h", "wm_kernels.h", "wm_host.h", "../../include/whisper_mi.h", "../../include/wm_synth.h"]
+SOURCES = ["whisper_mi.cpp", "wm_align.cpp", "wm_frontend.cpp", "wm_chunked.cpp", "wm_score.cpp", "wm_long.cpp", "wm_bench.cpp", "wm_ops.cpp",
+           "kernels_encoder.hip", "kernels_decoder.hip", "kernels_frontend.hip", "kernels_align.hip", "kernels_score.hip", "kernels_chunked.hip"]
+HEADERS = ["wm_device.h", "wm_kernels.h", "wm_host.h", "wm_runtime.h", "../../include/whisper_mi.h", "../../include/wm_synth.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=on"]
 

@@ -1,4 +1,5 @@
-// wm_host.h — what the two host sources share: whisper_mi.cpp (the runtime) and wm_ops.cpp (the wm_op_* test hooks).
+// wm_host.h — what every host source shares: the runtime's sources (whisper_mi.cpp and the subsystems behind wm_runtime.h, which
+// includes this) and wm_ops.cpp (the wm_op_* test hooks), which needs no more than this.
 // Internal to the library: everything declared here has hidden visibility, so none of it reaches the dynamic symbol table.
 #pragma once
 #include "../../include/whisper_mi.h"

@@ -1,6 +1,6 @@
 // wm_ops.cpp — the wm_op_* test hooks of include/whisper_mi.h: each uploads host fp32 arrays, launches one or two kernels exactly as
 // the runtime (whisper_mi.cpp) wires them, and copies the result back, for the float64 and known-answer tests.  Hooks that need the
-// static helpers of a subsystem (alignment, the front end, resampling, chunking, scoring) stay next to them in whisper_mi.cpp.
+// static helpers of a subsystem (alignment, the front end, resampling, chunking, scoring, long-form) live in that subsystem's source.
 #include "wm_host.h"
 
 using namespace wm;
