@@ -332,6 +332,33 @@ int wm_set_repeat_options(wm_model* m, float repetition_penalty, int no_repeat_n
 int wm_set_top_k(wm_model* m, int top_k);
 int wm_transcribe_top_k(wm_model* m, int slot, int32_t* top_ids, float* top_logprobs);
 
+/* ---- phrase-list constraint ----------------------------------------------------------------------------------------
+ * "The answer is one of these phrases": HF generate's prefix_allowed_tokens_fn (PrefixConstrainedLogitsProcessor) with the function
+ * replaced by a trie of token ids, for every greedy pass asked for from now on — the passes wm_set_repeat_options names, with the
+ * rules of wm_set_sequence_bias: model-wide, it persists until the next call, a held coalesce = 2 submit keeps its table and pairs
+ * only with a submit made under the same one, and replacing the table changes no pass that was already asked for.
+ * Phrase q is ids[offsets[q] .. offsets[q + 1]).  free_from: ids >= free_from (the timestamp ids, say) are always allowed and never
+ * move a row through the trie; < 0 = none.  At every step, with gen the ids row b generated behind its own prompt:
+ *   1. walk = gen without the ids >= free_from; node = where walk leads from the trie's root, or the dead node if it leaves the trie;
+ *   2. allowed = the ids of the node's child edges, the pass's eot if a phrase ends at the node, and every id >= free_from (the dead
+ *      node: the eot and the free ids) — never empty;
+ *   3. every other id is -inf, where bad words act: behind sequence_bias, repetition_penalty and no_repeat_ngram_size, ahead of the
+ *      suppress lists, the timestamp rules, the arg-max, the log-prob sums and the top-k selection.
+ * The no-speech probe, language detection, wm_score and wm_align read unprocessed logits.  It runs on the device inside the captured
+ * step: the step's arg-max launch moves the row's node and rewrites the row's ban set, which the logits kernel of the repetition
+ * processors reads; a pass without a table launches exactly what it did before.  ids = NULL, n_phrases = 0 clears the table.
+ * WM_E_ARG, with the setting unchanged: n_phrases = 0 with ids given, an empty phrase, an id outside the vocabulary or >= free_from,
+ * a duplicate phrase, more than 4096 phrases, a phrase of more than 64 ids, more than 65536 trie nodes (root and dead node included),
+ * offsets that do not start at 0.  A pass whose eot is an id of a phrase is refused with WM_E_ARG when it is asked for; the
+ * long-form and chunked entries refuse to run while a table is set.
+ *
+ * wm_transcribe_constraint_match: for the B rows of the constrained pass this slot collected last (slot 0: the synchronous
+ * entries), until the slot's state runs another pass: the index of the phrase that ended at the row's node when it emitted the eot
+ * and stopped, -1 if it ended otherwise (the loop ran out, ignore_eot, the dead node, a node where no phrase ends).  WM_E_STATE: no
+ * such pass. */
+int wm_set_constraint(wm_model* m, const int32_t* ids, const int32_t* offsets, int n_phrases, int free_from);
+int wm_transcribe_constraint_match(wm_model* m, int slot, int32_t* out, int B);
+
 /* ---- sequence bias and bad words ---------------------------------------------------------------------------------
  * HF generate's sequence_bias (SequenceBiasLogitsProcessor) and bad_words_ids (NoBadWordsLogitsProcessor), given as ids, for every
  * greedy pass asked for from now on — the passes wm_set_repeat_options names, with the same rules: model-wide, it persists until the
@@ -815,6 +842,15 @@ int wm_op_seq_bias_hits(uint32_t* hit, float* slot_bias, int32_t* slot_flags, in
                         const int32_t* prompt_len, const int32_t* n_ids, int B, int stride, int vocab, int eot, const int32_t* seq_ids,
                         const int32_t* seq_off, const float* seq_bias, int n_seq, const int32_t* bad_ids, const int32_t* bad_off, int n_bad,
                         int steps);
+/* The phrase-list constraint's bookkeeping alone, replayed likewise: the table is built from the phrases as
+ * wm_set_constraint builds it (same refusals; eot: allowed where a phrase ends, refused inside a phrase), the init kernels run on each
+ * row's prompt with no_repeat_ngram_size = ngram, then `steps` argmax launches append the rows' ids.  Out: node [steps + 1][B], the
+ * rows' trie nodes (the root is 0, nodes are numbered as the phrases first reach them, the dead node is the last), and mask
+ * [steps + 1][B][ceil(vocab / 32)], the rows' ban words: the complement of the node's allowed set with the n-gram bans on top, bits
+ * past the vocabulary clear — entry 0 after the init, entry s after step s. */
+int wm_op_constraint_states(int32_t* node, uint32_t* mask, const int32_t* tokens, const int32_t* prompt_len, const int32_t* n_ids, int B,
+                            int stride, int vocab, int eot, int ngram, const int32_t* ids, const int32_t* offsets, int n_phrases, int free_from,
+                            int steps);
 /* The no-speech probe's launches on the kernel variant wm_op_logits_lp picks for (dtype, K, B): prob[b] = softmax(LN(x[b])·embᵀ)[token]
  * over all N columns, lse[b] the row's logsumexp.  prob, lse: [B]. */
 int wm_op_no_speech(float* prob, float* lse, const float* x, const float* ln_g, const float* ln_b, const float* emb, int B, int N, int K,

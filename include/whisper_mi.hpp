@@ -605,6 +605,69 @@ public:
                                  (int)bad_words_ids.size()) != WM_OK)
             throw std::invalid_argument(wm_last_error());
     }
+    // Phrase-list constraint for every transcribe call from now on: the generated ids of every row, without the ids >=
+    // free_from (< 0: none), are confined to one of the phrases followed by eot.  An empty list switches it off (the default; the C
+    // entry wants NULL for that, which is what this passes).  Throws std::invalid_argument for what wm_set_constraint refuses; the
+    // long-form calls refuse to run while it is set.  After a call, constraint_match(B) returns per row the index of the phrase it
+    // stood on when it emitted eot, or -1.
+    void set_constraint(const std::vector<std::vector<int32_t>>& phrases, int free_from = -1) {
+        need_model();
+        std::vector<int32_t> ids, off{0};
+        for (const auto& s : phrases) {
+            ids.insert(ids.end(), s.begin(), s.end());
+            off.push_back((int32_t)ids.size());
+        }
+        const bool none = phrases.empty();
+        if (wm_set_constraint(model_, none ? nullptr : ids.data(), none ? nullptr : off.data(), (int)phrases.size(), free_from) != WM_OK)
+            throw std::invalid_argument(wm_last_error());
+    }
+    std::vector<int32_t> constraint_match(int B, int slot = 0) const {
+        need_model();
+        std::vector<int32_t> out((size_t)B);
+        check(wm_transcribe_constraint_match(model_, slot, out.data(), B));
+        return out;
+    }
+    // The trie wm_set_constraint builds from the phrases, flattened as the library flattens it: node v's child edges are edge_id /
+    // edge_next [edge_off[v], edge_off[v + 1]), ids ascending; terminal[v] is the index of the phrase that ends at v or -1.  Node 0 is
+    // the root, nodes are numbered in the order the phrases, in the caller's order and id by id, first reach them, and the last node
+    // is the dead node (no edges, no phrase).  Host code only — for callers that want to walk the trie themselves (which ids may
+    // follow a prefix), and checked against the Python host's builder.  Throws std::invalid_argument for a duplicate phrase.
+    struct ConstraintTrie {
+        std::vector<int32_t> edge_off, edge_id, edge_next, terminal;
+    };
+    static ConstraintTrie constraint_trie(const std::vector<std::vector<int32_t>>& phrases) {
+        std::vector<std::vector<std::pair<int32_t, int32_t>>> kids(1);  // per node: (id, child), ascending by id
+        ConstraintTrie t;
+        t.terminal.assign(1, -1);
+        for (size_t q = 0; q < phrases.size(); ++q) {
+            int32_t v = 0;
+            for (int32_t id : phrases[q]) {
+                auto it = std::lower_bound(kids[v].begin(), kids[v].end(), std::make_pair(id, (int32_t)-1));
+                if (it != kids[v].end() && it->first == id) {
+                    v = it->second;
+                } else {
+                    const int32_t nv = (int32_t)kids.size();
+                    kids[v].insert(it, std::make_pair(id, nv));
+                    kids.emplace_back();
+                    t.terminal.push_back(-1);
+                    v = nv;
+                }
+            }
+            if (t.terminal[v] >= 0) throw std::invalid_argument("constraint: a phrase is given twice");
+            t.terminal[v] = (int32_t)q;
+        }
+        kids.emplace_back();  // the dead node
+        t.terminal.push_back(-1);
+        t.edge_off.push_back(0);
+        for (const auto& e : kids) {
+            for (const auto& pr : e) {
+                t.edge_id.push_back(pr.first);
+                t.edge_next.push_back(pr.second);
+            }
+            t.edge_off.push_back((int32_t)t.edge_id.size());
+        }
+        return t;
+    }
     const WhisperConfig& config() const { return cfg_; }
     wm_model* handle() const { return model_; }
 

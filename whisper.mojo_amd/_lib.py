@@ -44,6 +44,7 @@ SYMBOLS = [
     "wm_op_gemm_nt_epi",
     "wm_resample_len", "wm_resample_pcm", "wm_op_resample", "wm_op_resample_taps",
     "wm_set_top_k", "wm_transcribe_top_k", "wm_op_logits_topk",
+    "wm_set_constraint", "wm_transcribe_constraint_match", "wm_op_constraint_states",
     "wm_op_fe_tables", "wm_op_fe_frames", "wm_op_fe_mel_log", "wm_op_fe_mel_norm", "wm_op_window_gather",
 ]
 
@@ -315,6 +316,9 @@ def lib():
     L.wm_set_repeat_options.argtypes = [vp, C.c_float, C.c_int]
     L.wm_op_logits_processed.argtypes = [fp, ip, fp, fp, fp, fp, fp, fp, ip, C.c_int, up, up, C.c_float] + [C.c_int] * 4
     L.wm_op_repeat_sets.argtypes = [up, up, ip, ip, ip] + [C.c_int] * 5
+    L.wm_set_constraint.argtypes = [vp, ip, ip, C.c_int, C.c_int]
+    L.wm_transcribe_constraint_match.argtypes = [vp, C.c_int, ip, C.c_int]
+    L.wm_op_constraint_states.argtypes = [ip, up, ip, ip, ip] + [C.c_int] * 5 + [ip, ip] + [C.c_int] * 3
     L.wm_set_top_k.argtypes = [vp, C.c_int]
     L.wm_transcribe_top_k.argtypes = [vp, C.c_int, ip, fp]
     L.wm_op_logits_topk.argtypes = [fp, ip, fp, ip, fp, C.c_int, fp, fp, fp, fp, fp, ip, C.c_int, up, up, C.c_float] + [C.c_int] * 4
@@ -561,6 +565,90 @@ def top_k_arg(top_k, return_logprobs):
     if not return_logprobs:
         raise ValueError("top_k needs return_logprobs=True")
     return k
+
+
+CONSTRAINT_PHRASES_MAX, CONSTRAINT_LEN_MAX, CONSTRAINT_NODES_MAX = 4096, 64, 65536  # wm_kernels.h
+
+
+def constraint_trie(phrases):
+    """The trie of a list of phrases (id tuples), flattened as wm_set_constraint flattens it -> (edge_off [n + 1],
+    edge_id, edge_next, terminal [n]) int32: node v's child edges are edge_id / edge_next [edge_off[v] : edge_off[v + 1]], ids
+    ascending; terminal[v] = the index of the phrase that ends at v, or -1.  Node 0 is the root, nodes are numbered in the order the
+    phrases, taken in the caller's order and id by id, first reach them, and the last node is the dead node: no edges, no phrase.
+    ValueError: a duplicate phrase, more than CONSTRAINT_NODES_MAX nodes."""
+    import numpy as np
+    kids, term = [{}], [-1]
+    for q, ph in enumerate(phrases):
+        v = 0
+        for t in ph:
+            nxt = kids[v].get(t)
+            if nxt is None:
+                if len(kids) + 2 > CONSTRAINT_NODES_MAX:
+                    raise ValueError(f"constraint: more than {CONSTRAINT_NODES_MAX} trie nodes")
+                nxt = kids[v][t] = len(kids)
+                kids.append({})
+                term.append(-1)
+            v = nxt
+        if term[v] >= 0:
+            raise ValueError(f"constraint: phrase {list(ph)} is given twice")
+        term[v] = q
+    kids.append({})
+    term.append(-1)
+    off, eid, enx = [0], [], []
+    for k in kids:
+        for t in sorted(k):
+            eid.append(t)
+            enx.append(k[t])
+        off.append(len(eid))
+    return np.asarray(off, np.int32), np.asarray(eid, np.int32), np.asarray(enx, np.int32), np.asarray(term, np.int32)
+
+
+def constraint_args(constraint, free_from, vocab, eot, timestamps=None):
+    """Checks constraint= (a list of phrases, each a non-empty list of ids) and free_from= on the host (the library refuses the same
+    with WM_E_ARG) -> None when constraint is None, else (key, [ids, offsets, n_phrases, free_from]) as wm_set_constraint takes them;
+    key is hashable and equal for equal phrases in equal order under an equal free_from.  free_from None: the first timestamp id
+    when the timestamp rules are on, else no free ids (-1)."""
+    import numpy as np
+    if constraint is None:
+        if free_from is not None:
+            raise ValueError("free_from without constraint")
+        return None
+    try:
+        items = list(constraint)
+    except TypeError:
+        raise ValueError(f"constraint: a list of phrases, each a list of ids (got {constraint!r})")
+    if not items:
+        raise ValueError("constraint: an empty list of phrases (use None for off)")
+    if len(items) > CONSTRAINT_PHRASES_MAX:
+        raise ValueError(f"constraint: at most {CONSTRAINT_PHRASES_MAX} phrases (got {len(items)})")
+    if free_from is None:
+        ff = int(timestamps[0]) if timestamps is not None else -1
+    else:
+        if isinstance(free_from, bool) or not isinstance(free_from, (int, np.integer)):
+            raise ValueError(f"free_from must be an id (got {free_from!r})")
+        ff = int(free_from)
+    if ff < 0 or ff > vocab:
+        ff = vocab
+    out = []
+    for s in items:
+        try:
+            t = tuple(s)
+        except TypeError:
+            raise ValueError(f"constraint: every phrase is a list of ids (got {s!r})")
+        if not 1 <= len(t) <= CONSTRAINT_LEN_MAX:
+            raise ValueError(f"constraint: a phrase has 1..{CONSTRAINT_LEN_MAX} ids (got {len(t)})")
+        for i in t:
+            if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= int(i) < vocab:
+                raise ValueError(f"constraint: id {i!r} is not an integer inside the vocabulary of {vocab}")
+            if int(i) == int(eot):
+                raise ValueError(f"constraint: a phrase holds the eot {eot}")
+            if int(i) >= ff:
+                raise ValueError(f"constraint: a phrase holds the free id {int(i)} (free_from {ff})")
+        out.append(tuple(int(i) for i in t))
+    constraint_trie(out)  # a duplicate phrase, too many nodes
+    ids = np.asarray([i for t in out for i in t], np.int32)
+    off = np.concatenate([[0], np.cumsum([len(t) for t in out])]).astype(np.int32)
+    return (tuple(out), ff), [ids, off, len(out), ff]
 
 
 SEQ_BIAS_MAX, SEQ_BIAS_LEN_MAX = 1024, 32  # wm_kernels.h

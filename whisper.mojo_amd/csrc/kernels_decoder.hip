@@ -2194,12 +2194,58 @@ __device__ __forceinline__ void seq_bias_update(const SeqBiasCtl& c, unsigned* h
         }
     }
 }
+// Phrase-list constraint: the trie node a row reaches from `node` along id t.  An id >= free_from is free and leaves the
+// node where it is; otherwise the workgroup compares t with the node's edges (ids are distinct inside a node: at most one thread
+// finds it) and the row moves to that child, or to the dead node, which has no edges and so keeps every later id.
+__device__ __forceinline__ int constraint_advance(const ConstraintCtl& c, int node, int t) {
+    __shared__ int s_next;
+    if (t >= c.free_from) return node;  // (uniform over the workgroup: every thread holds the same t)
+    if (threadIdx.x == 0) s_next = c.dead;
+    __syncthreads();
+    for (int e = c.edge_off[node] + (int)threadIdx.x; e < c.edge_off[node + 1]; e += blockDim.x)
+        if (c.edge_id[e] == t) s_next = c.edge_next[e];
+    __syncthreads();
+    return s_next;
+}
+// The row's `ban` set for its NEXT step under the constraint: all `words` words rewritten.  First the complement of the node's allowed
+// set — every id below min(free_from, V) banned, bits past V clear as the other sets keep them, then the bits of the node's edges and,
+// where a phrase ends or the row has left the trie, of the eot cleared again — and behind a barrier the n-gram bans on top: the walk over the history for n >= 2,
+// the ids of `seen` for n = 1 (`seen` already holds the history's last id).  hist(i), i < L, is the row's history.
+template <typename H>
+__device__ __forceinline__ void constraint_rewrite(const ConstraintCtl& c, unsigned* ban, const unsigned* seen, int words, int V, int node, int n,
+                                                   int L, H hist) {
+    const int lim = min(max(c.free_from, 0), V);
+    for (int w = threadIdx.x; w < words; w += blockDim.x) {
+        const int lo = w * 32;
+        ban[w] = lo + 32 <= lim ? 0xffffffffu : lo >= lim ? 0u : (1u << (lim - lo)) - 1u;
+    }
+    __threadfence();
+    __syncthreads();
+    for (int e = c.edge_off[node] + (int)threadIdx.x; e < c.edge_off[node + 1]; e += blockDim.x) {
+        const int t = c.edge_id[e];
+        if ((unsigned)t < (unsigned)V) atomicAnd(ban + (t >> 5), ~(1u << (t & 31)));
+    }
+    // (the eot ends a phrase, and it is the dead node's way out: its allowed set is the eot and the free ids, never empty)
+    if (threadIdx.x == 0 && (c.terminal[node] >= 0 || node == c.dead) && (unsigned)c.eot < (unsigned)V)
+        atomicAnd(ban + (c.eot >> 5), ~(1u << (c.eot & 31)));
+    __threadfence();
+    __syncthreads();  // every allowed id is cleared before the first n-gram ban is set: an allowed id the n-gram bans stays banned
+    if (n == 1) {
+        for (int w = threadIdx.x; w < words; w += blockDim.x)
+            if (const unsigned sw = seen[w]) atomicOr(ban + w, sw);  // (an atomic like every other update of the set behind its first store)
+    } else {
+        repeat_ban_walk<true>(ban, n, L, hist);
+    }
+}
 // LP: the log-probability instantiation (p.lp_s non-null); LP = false is the kernel without it, static LDS included.  RP: the
 // repetition processors' bookkeeping (p.rp_seen non-null), likewise.  SB: the sequence-bias bookkeeping (p.sb_hit non-null, needs RP).
 // TK (top-k alternatives; p.tk_rows non-null, needs LP): thread 0 also leaves the row's TopkRow for the selection launch.
-template <bool LP, bool RP = false, bool SB = false, bool TK = false>
-__global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
+// CT (phrase-list constraint; p.ct_node non-null, needs RP): the row's trie node moves and its `ban` set is rewritten.
+// The body of both kernels below: argmax_step_kernel is CT = false under the names it always had, argmax_step_ct_kernel CT = true.
+template <bool LP, bool RP, bool SB, bool TK, bool CT, typename P>
+__device__ __forceinline__ void argmax_step_body(const P p) {  // (by value, as the kernels took it: a reference costs the log-prob ones an SGPR)
     static_assert(LP || !TK, "the top-k alternatives ride the log-prob instantiation");
+    static_assert(RP || !CT, "the constraint writes the repetition processors' ban set");
     const int b = blockIdx.x;
     if (p.ts && b == 0 && threadIdx.x == 0) ts_put(p.ts, p.ts_id, 3);
     const int pos0 = p.emb_out ? p.pos[b] : 0;  // read before thread 0 advances it (the reductions below synchronise)
@@ -2350,14 +2396,28 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
             const int* row = p.out_tokens + (size_t)b * p.out_stride;
             const int L = rp_len;
             auto hist = [&](int i) { return i < L ? row[i] : idx; };
-            if (threadIdx.x == 0) {
-                atomicOr(seen + (idx >> 5), 1u << (idx & 31));
-                if (n == 1) atomicOr(ban + (idx >> 5), 1u << (idx & 31));
+            if constexpr (CT) {
+                // the constrained row: its node moves along the new id, and the whole set is written again for the new node — the
+                // constraint's words first, the n-gram bans of the next step on top — so nothing of this step has to be cleared
+                const ConstraintCtl c = *p.ct_ctl;
+                if (threadIdx.x == 0) atomicOr(seen + (idx >> 5), 1u << (idx & 31));
+                const int node = p.ct_node[b];
+                const int to = constraint_advance(c, node, idx);
+                if (threadIdx.x == 0) {
+                    if (!p.ignore_eot && idx == p.eot) p.ct_match[b] = c.terminal[node];  // the row ends here: the phrase it stood on
+                    p.ct_node[b] = to;
+                }
+                constraint_rewrite(c, ban, seen, p.rp_words, p.V, to, n, L + 1, hist);
+            } else {
+                if (threadIdx.x == 0) {
+                    atomicOr(seen + (idx >> 5), 1u << (idx & 31));
+                    if (n == 1) atomicOr(ban + (idx >> 5), 1u << (idx & 31));
+                }
+                repeat_ban_walk<false>(ban, n, L, hist);
+                __threadfence();
+                __syncthreads();  // every clear is done before the first set: an id banned at both steps stays banned
+                repeat_ban_walk<true>(ban, n, L + 1, hist);
             }
-            repeat_ban_walk<false>(ban, n, L, hist);
-            __threadfence();
-            __syncthreads();  // every clear is done before the first set: an id banned at both steps stays banned
-            repeat_ban_walk<true>(ban, n, L + 1, hist);
             if constexpr (SB)
                 seq_bias_update<false>(*p.sb_ctl, p.sb_hit + (size_t)b * p.rp_words, p.sb_val + (size_t)b * SEQ_BIAS_MAX, L + 1, hist);
         }
@@ -2367,6 +2427,32 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
         const float* pe = p.emb_pos + (size_t)min(pos0 + (p.advance ? 1 : 0), p.max_pos) * p.d;
         for (int j = threadIdx.x; j < p.d; j += blockDim.x) p.emb_out[(size_t)b * p.d + j] = te[j] + pe[j];
     }
+}
+template <bool LP, bool RP = false, bool SB = false, bool TK = false>
+__global__ __launch_bounds__(1024) void argmax_step_kernel(ArgmaxParams p) {
+    argmax_step_body<LP, RP, SB, TK, false>(p);
+}
+template <bool LP, bool SB, bool TK>
+__global__ __launch_bounds__(256) void argmax_step_ct_kernel(ArgmaxCtParams p) {
+    argmax_step_body<LP, true, SB, TK, true>(p);
+}
+template <bool LP, bool SB, bool TK> static void launch_argmax_constrained(const ArgmaxCtParams& p, hipStream_t st) {
+    hipLaunchKernelGGL((argmax_step_ct_kernel<LP, SB, TK>), dim3(p.B), dim3(256), 0, st, p);
+}
+// the constraint's instantiations: the repetition processors' ones (with or without the rest) plus the trie walk
+int launch_argmax_step_ct(const ArgmaxCtParams& p, hipStream_t st) {
+    if (!p.ct_node || !p.ct_match || !p.ct_ctl) return launch_refuse("argmax_step: the constraint needs the rows' nodes, their matches and the control block");
+    if (!p.rp_seen || !p.out_tokens || !p.pval || !p.rp_ban || !p.rp_ctl || p.rp_words < repeat_words(p.V))
+        return launch_refuse("argmax_step: the constraint needs the repetition processors' partials form, the id table, both sets and their control block");
+    if (p.sb_hit && (!p.sb_val || !p.sb_ctl)) return launch_refuse("argmax_step: the sequence bias needs the rows' slots and the control block");
+    if (p.tk_rows && !p.lp_s) return launch_refuse("argmax_step: the top-k alternatives need the log-prob form");
+    if (p.tk_rows)
+        p.sb_hit ? launch_argmax_constrained<true, true, true>(p, st) : launch_argmax_constrained<true, false, true>(p, st);
+    else if (p.lp_s)
+        p.sb_hit ? launch_argmax_constrained<true, true, false>(p, st) : launch_argmax_constrained<true, false, false>(p, st);
+    else
+        p.sb_hit ? launch_argmax_constrained<false, true, false>(p, st) : launch_argmax_constrained<false, false, false>(p, st);
+    return WM_LAUNCH_OK;
 }
 int launch_argmax_step(const ArgmaxParams& p, hipStream_t st) {
     if (p.tk_rows) {  // the top-k instantiations: the log-prob ones plus the row's TopkRow, nothing else differs
@@ -2641,6 +2727,30 @@ int launch_seq_bias_init(const SeqBiasInitParams& p, hipStream_t st) {
         t.n_slots < 1 || t.n_slots > t.n_seq || !t.ids || !t.off || !t.bias || !t.ban || !t.slot_id || !t.slot_off || !t.slot_of)
         return launch_refuse("seq_bias_init: 1 .. SEQ_BIAS_MAX sequences in at most as many slots, and every table");
     hipLaunchKernelGGL(seq_bias_init_kernel, dim3(p.B), dim3(256), 0, st, p);
+    return WM_LAUNCH_OK;
+}
+// start of a pass with a phrase-list constraint, one workgroup per row, behind the repeat-init launch that cleared the
+// sets and filled `seen` from the prompt: the control block, the row on the root with no match, and the root's allowed set,
+// complemented, over the row's `ban` with the prompt's n-gram bans set again on top
+__global__ __launch_bounds__(256) void constraint_init_kernel(ConstraintInitParams p) {
+    const int b = blockIdx.x;
+    // (several decode lanes: every lane's launch writes the state's one control block with the same bytes, as seq_bias_init_kernel does)
+    if (b == 0 && threadIdx.x == 0) *p.ctl = p.table;
+    if (threadIdx.x == 0) {
+        p.node[b] = 0;
+        p.match[b] = -1;
+    }
+    const int* row = p.out_tokens + (size_t)b * p.out_stride;
+    constraint_rewrite(p.table, p.ban + (size_t)b * p.words, p.seen + (size_t)b * p.words, p.words, p.vocab, 0, p.ngram, p.n_tokens[b],
+                       [&](int i) { return row[i]; });
+}
+int launch_constraint_init(const ConstraintInitParams& p, hipStream_t st) {
+    const ConstraintCtl& t = p.table;
+    if (!p.ban || !p.seen || !p.node || !p.match || !p.ctl || !p.out_tokens || !p.n_tokens || p.B <= 0 || p.vocab <= 0 ||
+        p.words < repeat_words(p.vocab) || t.n_nodes < 2 || t.n_nodes > CONSTRAINT_NODES_MAX || t.dead < 1 || t.dead >= t.n_nodes || !t.edge_off ||
+        !t.edge_id || !t.edge_next || !t.terminal)
+        return launch_refuse("constraint_init: 2 .. CONSTRAINT_NODES_MAX nodes with a dead node among them, every table and ceil(vocab / 32) words per row");
+    hipLaunchKernelGGL(constraint_init_kernel, dim3(p.B), dim3(256), 0, st, p);
     return WM_LAUNCH_OK;
 }
 // end of a per-row prefill: cache length Lmax for all, position len[b] + pos_delta per row

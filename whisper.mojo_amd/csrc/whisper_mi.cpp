@@ -571,6 +571,8 @@ extern "C" void wm_state_free(wm_state* s) {
         if (r.st == s) r = wm_model::AlignRef{};
     for (auto& r : s->m->topk_ref)
         if (r.st == s) r = wm_model::TopkRef{};
+    for (auto& r : s->m->ct_ref)
+        if (r.st == s) r = wm_model::ConstraintRef{};
     (void)hipSetDevice(s->m->device);
     // nothing of this state may still be running when its graphs, streams and arenas go away (a submitted pass that was
     // never waited for, or the model stream's last wm_decode_step)
@@ -597,7 +599,8 @@ extern "C" void wm_state_free(wm_state* s) {
                     &s->sc.slot, &s->sc.dst, &s->sc.len, &s->sc.ctx, &s->sc.lp, &s->sc.top, &s->sc.sum, &s->sc.avg,
                     &s->rw.table, &s->rw.len, &s->rw.key_lo, &s->lp.part_s, &s->lp.table, &s->lp.sum, &s->tk.rows, &s->tk.ids, &s->tk.lps,
                     &s->ns.x, &s->ns.pmax, &s->ns.pidx, &s->ns.psum, &s->ns.prob, &s->ns.lse,
-                    &s->lg.x, &s->lg.ids, &s->lg.col, &s->lg.out, &s->lg.probs, &s->rp.seen, &s->rp.ban, &s->rp.ctl, &s->rp.hit, &s->rp.val, &s->rp.sbctl};
+                    &s->lg.x, &s->lg.ids, &s->lg.col, &s->lg.out, &s->lg.probs, &s->rp.seen, &s->rp.ban, &s->rp.ctl, &s->rp.hit, &s->rp.val, &s->rp.sbctl,
+                    &s->rp.node, &s->rp.match, &s->rp.ctctl};
     for (DevBuf* b : bs) b->release();
     delete s;
 }
@@ -1219,6 +1222,25 @@ static int seq_bias_init(wm_state* s, const DecView& v, int eot) {
     LCHK(launch_seq_bias_init(r, v.st));
     return 0;
 }
+// start of a pass with a phrase-list constraint, behind repeat_init (and seq_bias_init); eot: the pass's, allowed where a phrase ends
+static int constraint_init(wm_model* m, wm_state* s, const DecView& v, int eot) {
+    ConstraintInitParams r{};
+    r.ban = lane_ptr<unsigned>(s->rp.ban, v, s->rp.words);
+    r.seen = lane_ptr<unsigned>(s->rp.seen, v, s->rp.words);
+    r.words = s->rp.words;
+    r.B = v.nb;
+    r.vocab = m->cfg.dims.vocab;
+    r.node = lane_ptr<int>(s->rp.node, v, 1);
+    r.match = lane_ptr<int>(s->rp.match, v, 1);
+    r.ctl = s->rp.ctctl.as<ConstraintCtl>();
+    r.table = s->rp.ask.ct->ctl(eot);
+    r.ngram = s->rp.ask.ngram;
+    r.out_tokens = lane_ptr<int>(s->out_tokens, v, s->out_stride);
+    r.out_stride = s->out_stride;
+    r.n_tokens = lane_ptr<int>(s->n_tokens, v, 1);
+    LCHK(launch_constraint_init(r, v.st));
+    return 0;
+}
 // LN1 -> q | k,v appended to the cache   (layers.mojo:118-147)
 DecLinearParams qkv_block(wm_model* m, wm_state* s, const DecView& v, int l, int P) {
     const wm_dims& c = m->cfg.dims;
@@ -1371,6 +1393,17 @@ static ArgmaxParams argmax_first_id(wm_model* m, wm_state* s, const DecView& v, 
     a.ignore_eot = ignore_eot;
     return a;
 }
+// The argmax launch that records an id (a = argmax_first_id / argmax_loop_step): under a phrase-list constraint the instantiation
+// that also moves the rows' trie nodes, else the launch as it always was.
+static int launch_argmax_id(wm_state* s, const DecView& v, const ArgmaxParams& a) {
+    if (!s->rp.ct) return launch_argmax_step(a, v.st);
+    ArgmaxCtParams c{};
+    static_cast<ArgmaxParams&>(c) = a;
+    c.ct_node = lane_ptr<int>(s->rp.node, v, 1);
+    c.ct_match = lane_ptr<int>(s->rp.match, v, 1);
+    c.ct_ctl = s->rp.ctctl.as<ConstraintCtl>();
+    return launch_argmax_step_ct(c, v.st);
+}
 // Top-k alternatives: the selection launch behind an argmax launch that recorded an id — the k best of each row's stored
 // logits under `mask` and the ranges the argmax left in the row's TopkRow, into the tables' entry beside the id.  k = 0: nothing.
 static int topk_select(wm_model* m, wm_state* s, const DecView& v, const float* mask) {
@@ -1477,7 +1510,7 @@ static int loop_step(wm_model* m, wm_state* s, const DecView& v) {
     step.rules = &k.rules;  // (tb <= 0: off, as every reader of the rules checks)
     step.capture = true;
     WMCHK(decode_core(m, s, v, step));
-    LCHK(launch_argmax_step(argmax_loop_step(m, s, v, k.eot, k.ignore_eot, &k.rules), v.st));
+    LCHK(launch_argmax_id(s, v, argmax_loop_step(m, s, v, k.eot, k.ignore_eot, &k.rules)));
     if (k.top_k > 0) WMCHK(topk_select(m, s, v, step.mask));
     return 0;
 }
@@ -1670,6 +1703,7 @@ static int prefill_rows(wm_model* m, wm_state* s, const DecView& v, InitTokensPa
     launch_init_tokens_rows(ip, RowPromptParams{rw.table.as<int>(), rw.len.as<int>(), rw.stride, Lmax, rw.key_lo.as<int>()}, v.st);
     if (s->rp.on) repeat_init(s, v);  // each row's own prompt, a detected language included
     if (s->rp.sb) WMCHK(seq_bias_init(s, v, o->eot));
+    if (s->rp.ct) WMCHK(constraint_init(m, s, v, o->eot));
     for (int t0 = 0; t0 < Lmax; t0 += wm_state::PREFILL_MAX) {
         const int P = std::min<int>(wm_state::PREFILL_MAX, Lmax - t0);
         if (t0) launch_set_step(v.ctl, t0, 1, nullptr, 0, nullptr, 0, v.nb, v.st);
@@ -1684,7 +1718,7 @@ static int prefill_rows(wm_model* m, wm_state* s, const DecView& v, InitTokensPa
         const int t_sot = Lmax - s->ns.n_init;
         if (s->ns.on && t_sot >= t0 && t_sot < t0 + P) ns_capture(m, s, v, (size_t)(t_sot - t0) * v.nb);
     }
-    LCHK(launch_argmax_step(argmax_first_id(m, s, v, o->eot, o->ignore_eot, rp), v.st));
+    LCHK(launch_argmax_id(s, v, argmax_first_id(m, s, v, o->eot, o->ignore_eot, rp)));
     WMCHK(topk_select(m, s, v, s->mask_begin.as<float>()));
     trace_mark(v.st, "state %p lane %d prefill end", (void*)s, v.b0);
     launch_set_rows_step(v.ctl, Lmax, lane_ptr<int>(s->pos, v, 1), rw.len.as<int>(), o->pos_mode == WM_POS_REF ? -1 : 0, v.nb, v.st);
@@ -1718,6 +1752,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
     s->step.lp = s->lp.on;
     s->step.rp = s->rp.on;
     s->step.sb = s->rp.sb;
+    s->step.ct = s->rp.ct;
     s->step.top_k = s->tk.k;
     const bool recapture = !s->graphs_valid || !(s->graph_step == s->step);
     const int first_pos = o->pos_mode == WM_POS_REF ? o->n_prompt - 1 : o->n_prompt;
@@ -1767,6 +1802,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
             launch_init_tokens(ip, v.st);
             if (s->rp.on) repeat_init(s, v);
             if (s->rp.sb) WMCHK(seq_bias_init(s, v, o->eot));
+            if (s->rp.ct) WMCHK(constraint_init(m, s, v, o->eot));
             // prefill (whisper.mojo:195, start_pos=0): the q_len = n_prompt causal block equals n_prompt single-token steps
             static const bool seq_prefill = wm_env("WM_SEQ_PREFILL") != nullptr;  // A/B: one pass per prompt position
             DecPass prompt;  // the last prompt position's logits, under the begin mask
@@ -1785,7 +1821,7 @@ static int transcribe_decode(wm_model* m, wm_state* s, const wm_decode_opts* o, 
                     if (s->ns.on && i == o->n_prompt - s->ns.n_init) ns_capture(m, s, v, 0);
                 }
             }
-            LCHK(launch_argmax_step(argmax_first_id(m, s, v, o->eot, o->ignore_eot, rp), v.st));  // :198-203
+            LCHK(launch_argmax_id(s, v, argmax_first_id(m, s, v, o->eot, o->ignore_eot, rp)));  // :198-203
             WMCHK(topk_select(m, s, v, prompt.mask));
             trace_mark(v.st, "state %p lane %d prefill end", (void*)s, v.b0);
             // incremental steps: start_pos = current_len - 1 (reference, :217) or current_len (HF)
@@ -1960,6 +1996,15 @@ int submit_on(wm_model* m, wm_state** slot, const PassAsk& ask) {
     } else {
         s->rp.ask.sb.reset();  // (a pass without the table holds no reference to one)
     }
+    s->rp.ct = s->rp.on && ask.rp.ct;
+    s->rp.ct_gen += 1;
+    if (s->rp.ct) {
+        WMCHK(grow(s->rp.node, (size_t)B * 4));
+        WMCHK(grow(s->rp.match, (size_t)B * 4));
+        WMCHK(grow(s->rp.ctctl, sizeof(ConstraintCtl)));
+    } else {
+        s->rp.ask.ct.reset();
+    }
     s->lp.on = lp;
     s->tk.k = lp && !score && !lang.only ? ask.top_k : 0;  // the alternatives of a greedy log-prob pass; every other pass ignores the setting
     s->tk.gen += 1;
@@ -2133,6 +2178,7 @@ static int collect_pass(wm_model* m, int slot, const PassOut& out) {
     const bool weights = !rc && (r.tt || r.kind == PassKind::align);
     m->align_ref[slot] = weights ? wm_model::AlignRef{s, r.row0, r.rows, s->al.gen} : wm_model::AlignRef();
     m->topk_ref[slot] = !rc && transcribe && r.lp && s->tk.k > 0 ? wm_model::TopkRef{s, r.row0, r.rows, r.total, s->tk.k, s->tk.gen} : wm_model::TopkRef();
+    m->ct_ref[slot] = !rc && transcribe && s->rp.ct ? wm_model::ConstraintRef{s, r.row0, r.rows, s->rp.ct_gen} : wm_model::ConstraintRef();
     r = wm_model::SlotRef();
     return rc;
 }
@@ -2145,7 +2191,7 @@ static bool pairs_with(const wm_model::Held& h, const PassAsk& b) {
     if (a.B != b.B || (a.cols != nullptr) != (b.cols != nullptr) || a.lp != b.lp || a.ns.token != b.ns.token || a.ns.n_init != b.ns.n_init)
         return false;
     if (a.top_k != b.top_k) return false;  // one step graph per state: a pair shares the top-k setting
-    if (!(a.rp == b.rp)) return false;  // one control block per state: a pair shares (penalty, n-gram size) and the sequence-bias table
+    if (!(a.rp == b.rp)) return false;  // one control block per state: a pair shares (penalty, n-gram size), the sequence-bias table and the constraint's
     if (x.n_prompt != o->n_prompt || x.eot != o->eot || x.max_loop != o->max_loop || x.pos_mode != o->pos_mode || x.ignore_eot != o->ignore_eot ||
         x.n_suppress != (o->suppress_tokens ? o->n_suppress : 0) || x.n_begin_suppress != (o->begin_suppress_tokens ? o->n_begin_suppress : 0) ||
         x.timestamp_begin != o->timestamp_begin || x.no_timestamps_token != o->no_timestamps_token ||
@@ -2195,7 +2241,15 @@ static int slot0_ready(wm_model* m) {
     if (m->slot_ref[0].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
     return 0;
 }
+// A greedy pass under the model's constraint table: its eot must not be an id of a phrase (the eot is what ends a phrase).  Checked
+// before anything is flushed, held or launched.
+static int constraint_check(const wm_model* m, const PassAsk& ask) {
+    if (!m->repeat.ct || !ask.opts || ask.score || ask.lang.only) return 0;
+    if (m->repeat.ct->holds(ask.opts->eot)) return fail(WM_E_ARG, "constraint: a phrase holds the pass's eot %d", ask.opts->eot);
+    return 0;
+}
 int run_now(wm_model* m, PassAsk ask, const PassOut& out) {
+    WMCHK(constraint_check(m, ask));
     WMCHK(slot0_ready(m));
     ask.allow_poll = true;
     ask.rp = m->repeat;
@@ -2208,6 +2262,7 @@ int run_now(wm_model* m, PassAsk ask, const PassOut& out) {
 // stream and returns; the slot's wait blocks until its results are ready.  A pending slot is refused BEFORE a held submit is flushed.
 int submit_slot(wm_model* m, int slot, const PassAsk& asked) {
     if (m->slot_ref[slot].pending) return fail(WM_E_STATE, "this slot still holds a pass that was not waited for");
+    WMCHK(constraint_check(m, asked));
     PassAsk ask = asked;
     ask.rp = m->repeat;  // the setting in force now: a held submit runs with it even if it changes before the partner arrives
     ask.top_k = m->top_k;
@@ -2574,6 +2629,90 @@ extern "C" int wm_set_repeat_options(wm_model* m, float repetition_penalty, int 
         return fail(WM_E_ARG, "no_repeat_ngram_size %d outside [0, %d] (0 = off)", no_repeat_ngram_size, REPEAT_NGRAM_MAX);
     m->repeat.penalty = repetition_penalty;
     m->repeat.ngram = no_repeat_ngram_size;
+    return 0;
+}
+// ---- phrase-list constraint ----------------------------------------------------------------------------------------
+// Validates the phrases, builds their trie and flattens it to CSR on the device.  Nodes are numbered in the order the phrases, taken
+// in the caller's order and id by id, first reach them; the root is 0 and the dead node comes last.  Nothing is allocated before every
+// argument has passed.  free_from < 0 or >= vocab: no free ids.
+int build_constraint_table(std::shared_ptr<ConstraintTable>& out, int vocab, const int32_t* ids, const int32_t* off, int n_phrases, int free_from) {
+    if (n_phrases < 0 || (n_phrases > 0 && (!ids || !off))) return fail(WM_E_ARG, "bad argument");
+    out.reset();
+    if (n_phrases == 0) return 0;
+    if (n_phrases > CONSTRAINT_PHRASES_MAX) return fail(WM_E_ARG, "constraint: %d phrases, at most %d", n_phrases, CONSTRAINT_PHRASES_MAX);
+    if (off[0] != 0) return fail(WM_E_ARG, "constraint: offsets start at 0");
+    const int ff = free_from < 0 || free_from > vocab ? vocab : free_from;
+    std::vector<std::vector<std::pair<int32_t, int32_t>>> kids(1);  // per node: (id, child), kept ascending by id
+    std::vector<int32_t> term(1, -1);
+    for (int q = 0; q < n_phrases; ++q) {
+        const long long len = (long long)off[q + 1] - off[q];
+        if (len < 1 || len > CONSTRAINT_LEN_MAX) return fail(WM_E_ARG, "constraint: phrase %d has %lld ids, need 1..%d", q, len, CONSTRAINT_LEN_MAX);
+        int v = 0;
+        for (int k = 0; k < (int)len; ++k) {
+            const int32_t t = ids[off[q] + k];
+            if (t < 0 || t >= vocab) return fail(WM_E_ARG, "constraint: phrase %d holds id %d outside the vocabulary of %d", q, t, vocab);
+            if (t >= ff) return fail(WM_E_ARG, "constraint: phrase %d holds the free id %d (free_from %d)", q, t, ff);
+            auto& e = kids[v];
+            auto it = std::lower_bound(e.begin(), e.end(), std::make_pair(t, (int32_t)-1));
+            if (it != e.end() && it->first == t) {
+                v = it->second;
+            } else {
+                if ((long long)kids.size() + 2 > CONSTRAINT_NODES_MAX)
+                    return fail(WM_E_ARG, "constraint: more than %d trie nodes", CONSTRAINT_NODES_MAX);
+                const int32_t nv = (int32_t)kids.size();
+                e.insert(it, std::make_pair(t, nv));  // (kids grows below: e is not used again)
+                kids.emplace_back();
+                term.push_back(-1);
+                v = nv;
+            }
+        }
+        if (term[v] >= 0) return fail(WM_E_ARG, "constraint: phrase %d is a duplicate of phrase %d", q, term[v]);
+        term[v] = q;
+    }
+    kids.emplace_back();  // the dead node
+    term.push_back(-1);
+    std::vector<int32_t> h_off{0}, h_id, h_next;
+    for (const auto& e : kids) {
+        for (const auto& pr : e) {
+            h_id.push_back(pr.first);
+            h_next.push_back(pr.second);
+        }
+        h_off.push_back((int32_t)h_id.size());
+    }
+    auto t = std::make_shared<ConstraintTable>();
+    (void)hipGetDevice(&t->device);  // (the callers have made the model's device current)
+    t->n_nodes = (int)kids.size();
+    t->dead = t->n_nodes - 1;
+    t->n_phrases = n_phrases;
+    t->free_from = ff;
+    t->ids = h_id;
+    std::sort(t->ids.begin(), t->ids.end());
+    t->ids.erase(std::unique(t->ids.begin(), t->ids.end()), t->ids.end());
+    WMCHK(upload_bytes(t->edge_off, h_off.data(), h_off.size() * 4));
+    WMCHK(upload_bytes(t->edge_id, h_id.data(), h_id.size() * 4));
+    WMCHK(upload_bytes(t->edge_next, h_next.data(), h_next.size() * 4));
+    WMCHK(upload_bytes(t->terminal, term.data(), term.size() * 4));
+    out = std::move(t);
+    return 0;
+}
+extern "C" int wm_set_constraint(wm_model* m, const int32_t* ids, const int32_t* offsets, int n_phrases, int free_from) {
+    if (!m) return fail(WM_E_ARG, "bad argument");
+    if (n_phrases == 0 && ids) return fail(WM_E_ARG, "constraint: an empty list of phrases (pass NULL to switch the constraint off)");
+    HIPCHK(hipSetDevice(m->device));
+    std::shared_ptr<ConstraintTable> t;
+    WMCHK(build_constraint_table(t, m->cfg.dims.vocab, ids, offsets, n_phrases, free_from));
+    if (t) t->gen = ++m->ct_gen;
+    m->repeat.ct = std::move(t);  // a held submit and a pending pass keep the table they were asked for with
+    return 0;
+}
+extern "C" int wm_transcribe_constraint_match(wm_model* m, int slot, int32_t* out, int B) {
+    if (!m || !out || slot < 0 || slot > 7) return fail(WM_E_ARG, "bad argument");
+    const wm_model::ConstraintRef& r = m->ct_ref[slot];
+    if (!r.st || !state_is_live(r.st) || r.st->rp.ct_gen != r.gen)
+        return fail(WM_E_STATE, "no collected pass under a constraint on this slot (wm_set_constraint; or its state has run another pass since)");
+    if (B != r.rows) return fail(WM_E_ARG, "constraint_match: the pass had %d rows, not %d", r.rows, B);
+    HIPCHK(hipSetDevice(m->device));
+    HIPCHK(hipMemcpy(out, r.st->rp.match.as<int>() + r.row0, (size_t)B * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 // ---- top-k alternatives ----------------------------------------------------------------------------------------

@@ -111,6 +111,8 @@ static int chunked_impl(wm_model* m, const float* pcm, int pcm_on_device, const 
     WMCHK(check_opts(m, o, 1));
     if (m->top_k > 0)  // (the stitched result has no place for them yet)
         return fail(WM_E_ARG, "top-k alternatives (wm_set_top_k) are not available in chunked transcription: set top_k to 0");
+    if (m->repeat.ct)  // (the window and chunk schedulers do not carry the rows' trie nodes yet)
+        return fail(WM_E_ARG, "the phrase-list constraint (wm_set_constraint) is not available in chunked transcription: clear it first");
     const bool word = ts.mode == 2;
     if (ts.mode) {  // everything is refused before anything is launched
         if (ts.mode != 1 && ts.mode != 2) return fail(WM_E_ARG, "mode must be 1 (segments) or 2 (word)");

@@ -145,6 +145,28 @@ struct SeqTable {
         return wm::SeqBiasCtl{n_seq, n_slots, eot, ids.as<int>(), off.as<int>(), bias.as<float>(), ban.as<int>(), slot_id.as<int>(), slot_off.as<int>(), slot_of.as<int>()};
     }
 };
+// One table of wm_set_constraint: the phrases validated, their trie flattened to CSR and copied to the device.  Immutable
+// and reference counted exactly as SeqTable is.  ids: the distinct ids of all phrases, ascending — what a pass's eot is checked against.
+struct ConstraintTable {
+    int gen = 0;     // the model's count of tables built: what pairs two submits
+    int device = 0;  // where the buffers live
+    int n_nodes = 0, dead = 0, n_phrases = 0, free_from = 0;
+    std::vector<int32_t> ids;
+    DevBuf edge_off, edge_id, edge_next, terminal;
+    ConstraintTable() = default;
+    ConstraintTable(const ConstraintTable&) = delete;
+    ConstraintTable& operator=(const ConstraintTable&) = delete;
+    ~ConstraintTable() {
+        int cur = -1;
+        const bool moved = hipGetDevice(&cur) == hipSuccess && cur != device && hipSetDevice(device) == hipSuccess;
+        for (DevBuf* b : {&edge_off, &edge_id, &edge_next, &terminal}) b->release();
+        if (moved) (void)hipSetDevice(cur);
+    }
+    bool holds(int id) const { return std::binary_search(ids.begin(), ids.end(), id); }
+    wm::ConstraintCtl ctl(int eot) const {
+        return wm::ConstraintCtl{n_nodes, dead, eot, free_from, edge_off.as<int>(), edge_id.as<int>(), edge_next.as<int>(), terminal.as<int>()};
+    }
+};
 // What a sweep over the tied embedding reads: the final LayerNorm and the embedding in the decoder's operand dtype
 struct VocabHead {
     const float *ln_g, *ln_b;
@@ -165,6 +187,7 @@ int ns_sweep(int T, const float* x, const VocabHead& h, int B, int npart, float*
 int lang_list_check(int vocab, const int32_t* lang_ids, int n_lang);
 int build_seq_table(std::shared_ptr<SeqTable>& out, int vocab, const int32_t* ids, const int32_t* off, const float* bias, int n_seq,
                     const int32_t* bad_ids, const int32_t* bad_off, int n_bad, std::vector<int32_t>* slot_ids = nullptr);
+int build_constraint_table(std::shared_ptr<ConstraintTable>& out, int vocab, const int32_t* ids, const int32_t* off, int n_phrases, int free_from);
 std::vector<float> conv_relayout(const float* w, int co, int ci, int cip);
 // the vocabulary head of a hook (wm_ops.cpp): the K the logits kernels take, and x [B][K] fp32 + ln_g, ln_b + emb [N][K] in dtype on the device
 int vocab_k_check(int K);

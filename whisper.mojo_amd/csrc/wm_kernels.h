@@ -168,6 +168,26 @@ struct SeqBiasCtl {
     const int* slot_of;   // [vocab] id -> slot, -1 = none (the epilogue's lookup at a set bit)
 };
 
+// Phrase-list constraint of the greedy loop (HF PrefixConstrainedLogitsProcessor over a trie of token ids).  The model's
+// table: the trie of the phrases flattened to CSR — node v's child edges are edge_id / edge_next [edge_off[v] .. edge_off[v + 1]), ids
+// ascending; terminal[v] is the index of the phrase that ends at v or -1.  Node 0 is the root; node `dead` has no edges and no phrase:
+// where a walk leaves the trie it stays.  Per utterance: the node its generated ids have reached (ids >= free_from do not move it).
+// The allowed set of a node — its edges' ids, eot where a phrase ends, every id >= free_from — is written, complemented, over the
+// row's whole `ban` set of the repetition processors, the n-gram bans OR-ed on top: the logits epilogue reads nothing new.  Built by
+// constraint_init, kept current by the step's argmax launch, reached through the state's control block like the sequence-bias table.
+static const int CONSTRAINT_PHRASES_MAX = 4096;  // phrases of a table
+static const int CONSTRAINT_LEN_MAX = 64;        // ids per phrase
+static const int CONSTRAINT_NODES_MAX = 65536;   // trie nodes, the root and the dead node included
+struct ConstraintCtl {
+    int n_nodes, dead;
+    int eot;        // allowed where a phrase ends; the pass's
+    int free_from;  // ids >= this are always allowed and never move the node; the vocabulary size = none
+    const int* edge_off;   // [n_nodes + 1]
+    const int* edge_id;    // [edges] ascending inside a node
+    const int* edge_next;  // [edges]
+    const int* terminal;   // [n_nodes] phrase index or -1
+};
+
 struct DecLinearParams {
     const float* x;  // [B][ldx] fp32 activations
     int ldx;
@@ -373,6 +393,16 @@ struct ArgmaxParams {
     TopkRow* tk_rows;  // [B]
 };
 int launch_argmax_step(const ArgmaxParams& p, hipStream_t st);  // WM_LAUNCH_*: refuses sets without the partials form or the id table
+// The same launch under a phrase-list constraint (needs the rp_* fields): a row that stores its id moves its trie node
+// along that id (ids >= free_from stay put, an id without an edge goes to the dead node) and rewrites rp_ban[b] as the complement of
+// the new node's allowed set with the n-gram bans on top; a row that stores the eot and ends leaves its node's phrase in ct_match.
+// A struct of its own, so the kernels of launch_argmax_step keep the argument block they always had.
+struct ArgmaxCtParams : ArgmaxParams {
+    int* ct_node;   // [B]
+    int* ct_match;  // [B]
+    const ConstraintCtl* ct_ctl;
+};
+int launch_argmax_step_ct(const ArgmaxCtParams& p, hipStream_t st);  // WM_LAUNCH_*
 // Top-k alternatives, the selection launch: one workgroup per row sweeps the step's stored, processed logits row under
 // the mask and the ranges of rows[b], keeps the k best (value descending, lowest id first among equals) and stores ids and
 // log-probs (value - ref) - logz at table entry rows[b].slot (none when it is negative).  Rank 0 is rows[b]'s own (id0, lp0); a rank
@@ -414,6 +444,23 @@ struct SeqBiasInitParams {
     const int* n_tokens;  // [B]
 };
 int launch_seq_bias_init(const SeqBiasInitParams& p, hipStream_t st);  // WM_LAUNCH_*
+// Start of a pass with a phrase-list constraint, behind the repeat-init launch (and the sequence-bias one): writes ctl, puts every row
+// on the root with no match, and rewrites the row's `ban` as the complement of the root's allowed set with the n-gram bans of its
+// prompt out_tokens[b][0 .. n_tokens[b]) on top (ngram = 1: the ids of `seen`).
+struct ConstraintInitParams {
+    unsigned* ban;         // [B][words]
+    const unsigned* seen;  // [B][words]
+    int words, B, vocab;
+    int* node;   // [B]
+    int* match;  // [B]
+    ConstraintCtl* ctl;
+    ConstraintCtl table;  // what ctl becomes
+    int ngram;
+    const int* out_tokens;  // [B][out_stride]
+    int out_stride;
+    const int* n_tokens;  // [B]
+};
+int launch_constraint_init(const ConstraintInitParams& p, hipStream_t st);  // WM_LAUNCH_*
 struct InitTokensParams {
     int* out_tokens;
     int out_stride;

@@ -198,6 +198,8 @@ static int long_run(wm_model* m, const float* mel, int T, const int32_t* nf, int
     const wm_dims& c = m->cfg.dims;
     if (m->top_k > 0)  // (no entry of the long-form result carries them yet)
         return fail(WM_E_ARG, "top-k alternatives (wm_set_top_k) are not available in long-form transcription: set top_k to 0");
+    if (m->repeat.ct)  // (the window and chunk schedulers do not carry the rows' trie nodes yet)
+        return fail(WM_E_ARG, "the phrase-list constraint (wm_set_constraint) is not available in long-form transcription: clear it first");
     const bool plain = long_opts_plain(lo) && !lang_ids;
     // thresholds: every pass is a log-prob pass; with a no_speech_token it also carries the probe at the first of the
     // o->n_prompt initial ids.  A window is skipped iff avg_logprob < logprob_threshold and no_speech_prob > no_speech_threshold.

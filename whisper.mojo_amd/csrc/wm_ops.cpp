@@ -3,6 +3,8 @@
 // static helpers of a subsystem (alignment, the front end, resampling, chunking, scoring, long-form) live in that subsystem's source.
 #include "wm_host.h"
 
+#include <type_traits>
+
 using namespace wm;
 
 // ---- the hooks' transfers, each written once (wm_host.h) ------------------------------------------------------------------
@@ -766,7 +768,7 @@ extern "C" int wm_op_logits_topk(float* logits, int32_t* ids, float* logprob, in
     return op_logits(logits, ids, logprob, x, ln_g, ln_b, emb, mask, ranges, timestamp_begin, B, N, K, dtype, seen, ban, penalty, nullptr, nullptr, 0,
                      nullptr, nullptr, top_k, top_ids, top_lp);
 }
-// Forced-token replay, shared by wm_op_repeat_sets and wm_op_seq_bias_hits: repeat_init on each row's prompt tokens[b][0 ..
+// Forced-token replay, shared by wm_op_repeat_sets, wm_op_seq_bias_hits and wm_op_constraint_states: repeat_init on each row's prompt tokens[b][0 ..
 // prompt_len[b]), then one argmax launch per step that is handed the row's next id of the table as its only candidate, so it appends
 // exactly that id — rows end at n_ids[b] (a row past its end is `finished` and does nothing).
 static int replay_rows_check(const int32_t* tokens, const int32_t* prompt_len, const int32_t* n_ids, int B, int stride, int vocab) {
@@ -777,11 +779,11 @@ static int replay_rows_check(const int32_t* tokens, const int32_t* prompt_len, c
     }
     return 0;
 }
-// extra: the hook's own fields of every step's ArgmaxParams.  init(r): the hook's launch behind repeat_init, on the same prompt
+// extra: the hook's own fields of every step's ArgmaxParams (ArgmaxCtParams: the constrained launch).  init(r): the hook's launch behind repeat_init, on the same prompt
 // buffers.  fetch(s, seen, ban): copies entry s out — 0 after the init, s after step s.
-template <typename Init, typename Fetch>
+template <typename Params, typename Init, typename Fetch>
 static int replay_forced(TmpDev& t, const int32_t* tokens, const int32_t* prompt_len, const int32_t* n_ids, int B, int stride, int vocab, int ngram,
-                         int steps, const ArgmaxParams& extra, Init init, Fetch fetch) {
+                         int steps, const Params& extra, Init init, Fetch fetch) {
     hipStream_t st = nullptr;
     const size_t words = (size_t)repeat_words(vocab), set_bytes = (size_t)B * words * 4;
     DevBuf &ds = t.add(), &db = t.add(), &dc = t.add(), &out = t.add(), &nt = t.add(), &fin = t.add(), &ctl = t.add(), &pv = t.add(), &pi = t.add(),
@@ -822,7 +824,7 @@ static int replay_forced(TmpDev& t, const int32_t* tokens, const int32_t* prompt
         }
         HIPCHK(hipMemcpy(pi.p, h_idx.data(), (size_t)B * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(fin.p, h_fin.data(), (size_t)B * 4, hipMemcpyHostToDevice));
-        ArgmaxParams a = extra;
+        Params a = extra;
         a.V = vocab;
         a.B = B;
         a.pval = pv.as<float>();
@@ -841,7 +843,10 @@ static int replay_forced(TmpDev& t, const int32_t* tokens, const int32_t* prompt
         a.rp_ban = db.as<unsigned>();
         a.rp_ctl = dc.as<RepeatCtl>();
         a.rp_words = (int)words;
-        LCHK(launch_argmax_step(a, st));
+        if constexpr (std::is_same<Params, ArgmaxCtParams>::value)
+            LCHK(launch_argmax_step_ct(a, st));
+        else
+            LCHK(launch_argmax_step(a, st));
         HIPCHK(hipGetLastError());
         WMCHK(fetch(s, ds, db));
     }
@@ -938,6 +943,55 @@ extern "C" int wm_op_seq_bias_hits(uint32_t* hit, float* slot_bias, int32_t* slo
         return 0;
     };
     return replay_forced(t, tokens, prompt_len, n_ids, B, stride, vocab, 0, steps, extra, init, fetch);
+}
+// The phrase-list constraint's bookkeeping alone, replayed likewise: constraint_init behind the repeat init on each row's
+// prompt, then one argmax launch per step that appends the row's next id of the table.  The table is built from the phrases as
+// wm_set_constraint builds it (same refusals; eot: allowed where a phrase ends, refused inside one).  node [steps + 1][B] and mask
+// [steps + 1][B][ceil(vocab / 32)], the rows' `ban` words — entry 0 after the init, entry s after step s.
+extern "C" int wm_op_constraint_states(int32_t* node, uint32_t* mask, const int32_t* tokens, const int32_t* prompt_len, const int32_t* n_ids, int B,
+                                       int stride, int vocab, int eot, int ngram, const int32_t* ids, const int32_t* offsets, int n_phrases,
+                                       int free_from, int steps) {
+    if (!node || !mask || !tokens || !prompt_len || !n_ids || B <= 0 || stride <= 0 || vocab <= 0 || steps < 0) return fail(WM_E_ARG, "bad argument");
+    if (ngram < 0 || ngram > REPEAT_NGRAM_MAX) return fail(WM_E_ARG, "no_repeat_ngram_size %d outside [0, %d]", ngram, REPEAT_NGRAM_MAX);
+    WMCHK(replay_rows_check(tokens, prompt_len, n_ids, B, stride, vocab));
+    std::shared_ptr<ConstraintTable> tab;
+    WMCHK(build_constraint_table(tab, vocab, ids, offsets, n_phrases, free_from));
+    if (!tab) return fail(WM_E_ARG, "the list of phrases is empty");
+    if (tab->holds(eot)) return fail(WM_E_ARG, "constraint: a phrase holds the eot %d", eot);
+    TmpDev t;
+    const size_t words = (size_t)repeat_words(vocab), set_bytes = (size_t)B * words * 4;
+    DevBuf &dn = t.add(), &dm = t.add(), &dcc = t.add();
+    WMCHK(dn.alloc((size_t)B * 4, true));
+    WMCHK(dm.alloc((size_t)B * 4, true));
+    WMCHK(dcc.alloc(sizeof(ConstraintCtl)));
+    ArgmaxCtParams extra{};
+    extra.ct_node = dn.as<int>();
+    extra.ct_match = dm.as<int>();
+    extra.ct_ctl = dcc.as<ConstraintCtl>();
+    auto init = [&](const RepeatInitParams& r) -> int {
+        ConstraintInitParams q{};
+        q.ban = r.ban;
+        q.seen = r.seen;
+        q.words = (int)words;
+        q.B = B;
+        q.vocab = vocab;
+        q.node = dn.as<int>();
+        q.match = dm.as<int>();
+        q.ctl = dcc.as<ConstraintCtl>();
+        q.table = tab->ctl(eot);
+        q.ngram = ngram;
+        q.out_tokens = r.out_tokens;
+        q.out_stride = stride;
+        q.n_tokens = r.n_tokens;
+        LCHK(launch_constraint_init(q, nullptr));
+        return 0;
+    };
+    auto fetch = [&](int s, const DevBuf&, const DevBuf& db) -> int {
+        HIPCHK(hipMemcpy(node + (size_t)s * B, dn.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(mask + (size_t)s * B * words, db.p, set_bytes, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    return replay_forced(t, tokens, prompt_len, n_ids, B, stride, vocab, ngram, steps, extra, init, fetch);
 }
 
 // The no-speech probe's launches on the kernel variant wm_op_logits_lp would pick for (dtype, K, B): the LP sweep with

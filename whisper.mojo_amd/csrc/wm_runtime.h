@@ -59,9 +59,11 @@ struct RepeatAsk {  // the logits processors of a greedy pass (DESIGN §29, §34
     float penalty = 1.f;
     int ngram = 0;
     std::shared_ptr<const SeqTable> sb;  // sequence bias / bad words: null = off
+    std::shared_ptr<const ConstraintTable> ct;  // phrase-list constraint: null = off
     int sb_gen() const { return sb ? sb->gen : 0; }
-    bool on() const { return penalty != 1.f || ngram > 0 || sb; }
-    bool operator==(const RepeatAsk& o) const { return penalty == o.penalty && ngram == o.ngram && sb_gen() == o.sb_gen(); }
+    int ct_gen() const { return ct ? ct->gen : 0; }
+    bool on() const { return penalty != 1.f || ngram > 0 || sb || ct; }
+    bool operator==(const RepeatAsk& o) const { return penalty == o.penalty && ngram == o.ngram && sb_gen() == o.sb_gen() && ct_gen() == o.ct_gen(); }
 };
 // One pass: encoder, prefill, greedy loop (or the teacher-forced pass of `score`) for B utterances.  The entry points validate, fill
 // one of these and hand it to a driver (run_now / submit_slot); nothing in it is owned, it lives on the caller's stack.
@@ -176,6 +178,7 @@ struct wm_model {
     std::vector<int32_t> align_pairs;
     RepeatAsk repeat;  // wm_set_repeat_options / wm_set_sequence_bias: what every greedy pass asked for from now on carries (a held submit keeps its own)
     int seq_gen = 0;   // tables built so far by wm_set_sequence_bias
+    int ct_gen = 0;    // ... by wm_set_constraint
     int top_k = 0;     // wm_set_top_k: what every log-prob pass asked for from now on carries (a held submit keeps its own)
     struct AlignRef {  // where a slot's last timestamp pass left its alignment weights (wm_alignment_weights)
         wm_state* st = nullptr;
@@ -185,6 +188,10 @@ struct wm_model {
         wm_state* st = nullptr;
         int row0 = 0, rows = 0, total = 0, k = 0, gen = 0;
     } topk_ref[8];
+    struct ConstraintRef {  // where a slot's last collected constrained pass left its matches (wm_transcribe_constraint_match)
+        wm_state* st = nullptr;
+        int row0 = 0, rows = 0, gen = 0;
+    } ct_ref[8];
     // sequential long-form decoding: the long log-mel and its scratch (frames / spec hold one chunk of frames, the
     // rest grows with the audio), and two internal decode states, apart from the caller's slots, with each one's gathered
     // windows and work items
@@ -251,11 +258,12 @@ struct wm_state {
         bool rows = false, lp = false;  // self-attention in the key-window form (rw.on); log-probabilities (lp.on)
         bool rp = false;                // repetition processors (rp.on): the flag only — penalty and n-gram size are read on the device
         bool sb = false;                // sequence bias / bad words (rp.sb): the flag only — the table is reached through the control block
+        bool ct = false;                // phrase-list constraint (rp.ct): the flag only, likewise
         int top_k = 0;                  // top-k alternatives (tk.k): the logits store, the argmax instantiation and the selection launch
         bool operator==(const StepKey& o) const {
             return eot == o.eot && ignore_eot == o.ignore_eot && rules.tb == o.rules.tb && rules.eos == o.rules.eos &&
                    rules.max_init == o.rules.max_init && rules.vocab == o.rules.vocab && shares_chip == o.shares_chip && cap == o.cap &&
-                   rows == o.rows && lp == o.lp && rp == o.rp && sb == o.sb && top_k == o.top_k;
+                   rows == o.rows && lp == o.lp && rp == o.rp && sb == o.sb && ct == o.ct && top_k == o.top_k;
         }
     };
     StepKey step, graph_step;
@@ -331,6 +339,11 @@ struct wm_state {
         // [B][SEQ_BIAS_MAX] and the control block that names the table.  Allocated by the first such pass.
         bool sb = false;
         DevBuf hit, val, sbctl;
+        // phrase-list constraint (ct = ask.ct non-null, always with on): the rows' trie nodes [B], the phrase each row
+        // ended on [B] and the control block that names the table.  Allocated by the first such pass.
+        bool ct = false;
+        int ct_gen = 0;  // counts the passes of this state: a ConstraintRef of another pass is stale
+        DevBuf node, match, ctctl;
     } rp;
     // no-speech probe of the pending pass (on = wm_transcribe_lp_ns and its kin, always with lp.on): the residual rows
     // of the <|startoftranscript|> position [B][d], the probe's OWN sweep partials [B][npart] (the step's amax / lp_s partials and

@@ -82,17 +82,20 @@ def log_mel(model, audios: Sequence[np.ndarray], sampling_rate: int = SAMPLING_R
 def transcribe_audio(model, audios: Sequence[np.ndarray], prompt: Sequence[int] = PROMPT, eot: int = EOT,
                      max_loop: int = MAX_LOOP, ignore_eot: bool = False, return_token_timestamps: bool = False,
                      repetition_penalty=None, no_repeat_ngram_size=None, sampling_rate: int = SAMPLING_RATE, sequence_bias=None,
-                     bad_words_ids=None, return_logprobs: bool = False, top_k=None):
-    """PCM in, token ids out (the mel never leaves the GPU).  return_logprobs / top_k: as Whisper.transcribe_batch, whose result this
-    then is; the log-mel of such a call is made on the GPU by log_mel and handed to transcribe_batch from host memory.  sampling_rate / np.int16 rows: resampled on the GPU first (resample).  return_token_timestamps: (ids, times) with the time in seconds
+                     bad_words_ids=None, return_logprobs: bool = False, top_k=None, constraint=None, free_from=None):
+    """PCM in, token ids out (the mel never leaves the GPU).  return_logprobs / top_k / constraint / free_from: as
+    Whisper.transcribe_batch, whose result this then is (constraint_match last); the log-mel of such a call is made on the
+    GPU by log_mel and handed to transcribe_batch from host memory.  sampling_rate / np.int16 rows: resampled on the GPU first (resample).  return_token_timestamps: (ids, times) with the time in seconds
     each id was spoken (needs model.set_alignment_heads); the attention columns are cropped to each clip's real audio.
     repetition_penalty / no_repeat_ngram_size: as Whisper.transcribe_batch."""
     k = _lib.top_k_arg(top_k, return_logprobs)
-    if return_logprobs:
+    _lib.constraint_args(constraint, free_from, model.config.vocab_size, eot)  # (refused before any GPU work)
+    if return_logprobs or constraint is not None:
         return model.transcribe_batch(log_mel(model, audios, sampling_rate), prompt, eot, max_loop, ignore_eot,
-                                      return_token_timestamps=return_token_timestamps, return_logprobs=True,
+                                      return_token_timestamps=return_token_timestamps, return_logprobs=return_logprobs,
                                       repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-                                      sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, top_k=k or None)
+                                      sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, top_k=k or None, constraint=constraint,
+                                      free_from=free_from)
     model._set_repeat(_lib.repeat_args(repetition_penalty, no_repeat_ngram_size),
                       _lib.seq_bias_args(sequence_bias, bad_words_ids, model.config.vocab_size))  # (as Whisper.transcribe_batch, DESIGN §34)
     audios = _at_16k(model, audios, sampling_rate)
@@ -174,8 +177,8 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
                                prev_sot_token: int = 50361, logprob_threshold=None, no_speech_threshold=None, no_speech_token=None,
                                detect_language=None, return_token_timestamps: bool = False, repetition_penalty=None,
                                no_repeat_ngram_size=None, sampling_rate: int = SAMPLING_RATE, sequence_bias=None, bad_words_ids=None,
-                               top_k=None):
-    """top_k: refused here (ValueError), as in Whisper.transcribe_long_form.
+                               top_k=None, constraint=None, free_from=None):
+    """top_k, constraint / free_from: refused here (ValueError), as in Whisper.transcribe_long_form.
     Sequential long-form transcription of 16 kHz PCM of any length (HF generate's long-form path), the long
     log-mel never leaving the GPU.  sampling_rate / np.int16 rows: resampled on the GPU first (resample; the 16 kHz samples pass
     through host memory); all times are seconds of audio.  repetition_penalty / no_repeat_ngram_size: as Whisper.transcribe_long_form.
@@ -185,6 +188,8 @@ def transcribe_audio_long_form(model, audios: Sequence[np.ndarray], prompt: Sequ
     Whisper.transcribe_long_form.  Returns per recording {"sequence": ids, "segments": [{"start", "end", "tokens"}]}."""
     if top_k is not None:
         raise ValueError("top_k is not available in long-form transcription (use transcribe_batch on 30 s windows)")
+    if constraint is not None or free_from is not None:
+        raise ValueError("constraint is not available in long-form transcription (use transcribe_batch on 30 s windows)")
     rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
     sb = _lib.seq_bias_args(sequence_bias, bad_words_ids, model.config.vocab_size)  # (as Whisper.transcribe_batch, DESIGN §34)
     lo, _keep2 = _lib.long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token, logprob_threshold,
@@ -237,8 +242,10 @@ def transcribe_audio_chunked(model, audios, chunk_length_s: float = 30.0, stride
                              begin_suppress_tokens: Sequence[int] = (), timestamps=None, detect_language=None, repetition_penalty=None,
                              no_repeat_ngram_size=None, first_special: int = _lib.FIRST_SPECIAL, return_stats: bool = False, n_samples=None,
                              return_timestamps=False, time_precision=None, tokenizer=None, sampling_rate: int = SAMPLING_RATE,
-                             sequence_bias=None, bad_words_ids=None, top_k=None):
-    """top_k: refused here (ValueError) — the top-k alternatives of Whisper.transcribe_batch have no place in the stitched
+                             sequence_bias=None, bad_words_ids=None, top_k=None, constraint=None, free_from=None):
+    """constraint / free_from: refused here (ValueError) — the chunk scheduler does not carry Whisper.transcribe_batch's phrase-list
+    constraint yet.
+    top_k: refused here (ValueError) — the top-k alternatives of Whisper.transcribe_batch have no place in the stitched
     result yet.
     Chunked long-form transcription of 16 kHz PCM of any length (HF's ASR pipeline with chunk_length_s / stride_length_s /
     batch_size = max_batch): every recording is cut into overlapping chunks (HF chunk_iter), the chunks of all recordings
@@ -269,6 +276,8 @@ def transcribe_audio_chunked(model, audios, chunk_length_s: float = 30.0, stride
     float32 already."""
     if top_k is not None:
         raise ValueError("top_k is not available in chunked transcription (use transcribe_batch on the chunks)")
+    if constraint is not None or free_from is not None:
+        raise ValueError("constraint is not available in chunked transcription (use transcribe_batch on the chunks)")
     if not isinstance(return_timestamps, (bool, np.bool_)) and not (isinstance(return_timestamps, str) and return_timestamps == "word"):
         raise ValueError('return_timestamps is False, True or "word"')  # 0 / 1 would pass an `in` test by equality: bools only
     ts_mode = 2 if isinstance(return_timestamps, str) else 1 if return_timestamps else 0

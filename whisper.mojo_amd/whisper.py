@@ -151,6 +151,7 @@ class Whisper:
         self._caches = weakref.WeakSet()  # live KVCaches of the loaded model
         self._n_align = 0  # alignment heads set on the loaded model (set_alignment_heads)
         self._sb_key = None  # the lists of the sequence-bias table set on the loaded model (_set_repeat); None = no table
+        self._ct_key = None  # the phrases of the constraint table set on the loaded model, likewise
         self._score_pending = {}  # slot -> (id table, lengths, mel keep-alive) of a submitted score pass (score_submit / score_wait)
         self._align_pending = {}  # slot -> (id table, lengths, context lengths, logprobs asked, keep-alives) of a submitted align pass
         self.encoder = WhisperEncoder(self)
@@ -170,6 +171,7 @@ class Whisper:
         self._h = h
         self._n_align = 0
         self._sb_key = None  # a freshly loaded model has no sequence-bias table
+        self._ct_key = None  # ... and no constraint table
 
     def load_file(self, path: str):
         self.close()
@@ -179,10 +181,11 @@ class Whisper:
         self._h = h
         self._n_align = 0
         self._sb_key = None  # a freshly loaded model has no sequence-bias table
+        self._ct_key = None  # ... and no constraint table
 
     def close(self):
         h, self._h = self._h, None
-        self._sb_key = None
+        self._sb_key = self._ct_key = None
         if h:
             for c in list(self._caches):
                 c._invalidate()
@@ -211,10 +214,11 @@ class Whisper:
                                  tb, no_ts, max_init)
         return opts, (p, sup, bsup)
 
-    def _set_repeat(self, rp, sb=None, top_k=0):
+    def _set_repeat(self, rp, sb=None, top_k=0, ct=None):
         """wm_set_repeat_options with a call's (penalty, n), wm_set_sequence_bias with its lists (sb: _lib.seq_bias_args, None =
-        off) and wm_set_top_k with its k: every greedy call sets them, so a call without the arguments runs with all of them off.
-        The table is rebuilt only when the lists differ from the last call's."""
+        off), wm_set_top_k with its k and wm_set_constraint with its phrases (ct: _lib.constraint_args, None = off): every greedy
+        call sets them, so a call without the arguments runs with all of them off.  A table is rebuilt only when its lists differ
+        from the last call's."""
         _lib.check(_lib.lib().wm_set_repeat_options(self._h, rp[0], rp[1]))
         _lib.check(_lib.lib().wm_set_top_k(self._h, top_k))
         key = None if sb is None else sb[0]
@@ -224,6 +228,26 @@ class Whisper:
             q = lambda x, t: None if x is None else x.ctypes.data_as(t)
             _lib.check(_lib.lib().wm_set_sequence_bias(self._h, q(a[0], ip), q(a[1], ip), q(a[2], fp), a[3], q(a[4], ip), q(a[5], ip), a[6]))
             self._sb_key = key
+        key = None if ct is None else ct[0]
+        if key != self._ct_key:
+            ip = C.POINTER(C.c_int32)
+            if ct is None:
+                _lib.check(_lib.lib().wm_set_constraint(self._h, None, None, 0, -1))
+            else:
+                ids, off, n, ff = ct[1]
+                _lib.check(_lib.lib().wm_set_constraint(self._h, ids.ctypes.data_as(ip), off.ctypes.data_as(ip), n, ff))
+            self._ct_key = key
+
+    def _constraint_match(self, slot, B):
+        """constraint_match of the constrained pass the slot collected last (wm_transcribe_constraint_match): int32 [B]"""
+        out = np.zeros(B, np.int32)
+        _lib.check(_lib.lib().wm_transcribe_constraint_match(self._h, slot, _ip(out), B))
+        return out
+
+    @staticmethod
+    def _with_last(res, last):
+        """a call's result with one more, last element"""
+        return res + (last,) if isinstance(res, tuple) else (res, last)
 
     def set_alignment_heads(self, pairs: Sequence[Sequence[int]]):
         """(layer, head) pairs whose cross-attention aligns ids with audio (HF generation_config.alignment_heads, e.g.
@@ -357,8 +381,18 @@ class Whisper:
                          n_frames=None, prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False,
                          no_speech_token: Optional[int] = None, n_init: Optional[int] = None,
                          detect_language: Optional[Sequence[int]] = None, repetition_penalty: Optional[float] = None,
-                         no_repeat_ngram_size: Optional[int] = None, sequence_bias=None, bad_words_ids=None, top_k: Optional[int] = None):
+                         no_repeat_ngram_size: Optional[int] = None, sequence_bias=None, bad_words_ids=None, top_k: Optional[int] = None,
+                         constraint=None, free_from: Optional[int] = None):
         """Batched Whisper.transcribe: one List[int] per utterance = prompt + generated ids (+ eot when hit).
+        constraint: a list of phrases, each a non-empty list of ids — every row's generated ids, without the free ids,
+        are confined to one of the phrases followed by eot (HF generate's prefix_allowed_tokens_fn over a trie of the phrases).
+        free_from: ids >= it (the timestamps) are always allowed and do not move a row through the trie; default the first timestamp
+        id with timestamps=, else none.  At every step the ids outside the row's allowed set — the ids that continue a phrase from
+        where the row stands, eot where a phrase ends, the free ids — are -inf, where bad_words_ids acts; log-probs and top-k see the
+        allowed set only.  The result gets one more, last element constraint_match, int32 [B]: the index of the phrase the row stood
+        on when it emitted eot, -1 if it ended otherwise.  At most 4096 phrases of 1..64 ids inside the vocabulary, below free_from
+        and without eot, no duplicates, at most 65536 trie nodes; None = off, an empty list is a ValueError.  Not in the long-form and
+        chunked calls.
         top_k (1..8, needs return_logprobs): the result gets one more, last element (top_ids, top_logprobs) — per
         utterance an int32 / float32 array [generated ids, k]: at every generated position the k candidates with the largest
         processed score (HF generate(output_scores=True), then log_softmax(scores).topk(k)), descending, equal scores lowest id
@@ -393,16 +427,22 @@ class Whisper:
         element becomes (token_logprobs, avg_logprob, no_speech_prob).  n_init: the number of initial ids (<|startoftranscript|>
         first); defaults to the shared prompt's length, required with prompts=."""
         k = _lib.top_k_arg(top_k, return_logprobs)
+        ct = _lib.constraint_args(constraint, free_from, self.config.vocab_size, eot, timestamps)
         res = self._transcribe_batch(mel, prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps,
                                      return_token_timestamps, n_frames, prompts, return_logprobs, no_speech_token, n_init, detect_language,
-                                     repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, k)
+                                     repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, k, ct)
         # the alternatives rode the call's log-prob pass: its tables are fetched once the pass is collected
-        return res + (self._top_k(0, k, self._plens(prompt, prompts, len(res[0]))),) if k else res
+        if k:
+            res = res + (self._top_k(0, k, self._plens(prompt, prompts, len(res[0]))),)
+        if ct:  # the rows' matches, likewise
+            res = self._with_last(res, self._constraint_match(0, len(res[0]) if isinstance(res, tuple) else len(res)))
+        return res
 
     def _transcribe_batch(self, mel, prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps,
                           return_token_timestamps, n_frames, prompts, return_logprobs, no_speech_token, n_init, detect_language,
-                          repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, k):
-        """transcribe_batch without the top-k tables; k: what wm_set_top_k gets for the pass (0 = off)"""
+                          repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, k, ct=None):
+        """transcribe_batch without the top-k tables and the constraint's matches; k: what wm_set_top_k gets for the pass (0 = off),
+        ct: what wm_set_constraint gets (_lib.constraint_args, None = off)"""
         rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
         sb = _lib.seq_bias_args(sequence_bias, bad_words_ids, self.config.vocab_size)
         lang = None
@@ -411,7 +451,7 @@ class Whisper:
         ns = None if lang else self._ns_args(no_speech_token, n_init, prompt, prompts, return_logprobs)
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
-        self._set_repeat(rp, sb, k)
+        self._set_repeat(rp, sb, k, ct)
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]
@@ -472,8 +512,10 @@ class Whisper:
                              no_speech_threshold: Optional[float] = None, no_speech_token: Optional[int] = None,
                              detect_language: Optional[Sequence[int]] = None, return_token_timestamps: bool = False,
                              repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
-                             sequence_bias=None, bad_words_ids=None, top_k: Optional[int] = None):
+                             sequence_bias=None, bad_words_ids=None, top_k: Optional[int] = None, constraint=None, free_from=None):
         """Sequential long-form transcription (HF generate's long-form path, greedy).
+        constraint / free_from: refused here (ValueError) — the window scheduler does not carry transcribe_batch's phrase-list
+        constraint yet.
         top_k: refused here (ValueError) — the top-k alternatives of transcribe_batch have no place in this result yet.
         sequence_bias / bad_words_ids: as transcribe_batch, matched against each window's own decoder ids.
         repetition_penalty / no_repeat_ngram_size: as transcribe_batch.  Every window's pass sees that window's decoder
@@ -500,6 +542,8 @@ class Whisper:
         the padding-free sequences row; return_stats also returns {"windows", "stalled"}."""
         if top_k is not None:
             raise ValueError("top_k is not available in long-form transcription (use transcribe_batch on 30 s windows)")
+        if constraint is not None or free_from is not None:
+            raise ValueError("constraint is not available in long-form transcription (use transcribe_batch on 30 s windows)")
         rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
         sb = _lib.seq_bias_args(sequence_bias, bad_words_ids, self.config.vocab_size)
         lo, _keep3 = _lib.long_opts(prompt_ids, condition_on_prev_tokens, prompt_condition_type, prev_sot_token, logprob_threshold,
@@ -605,7 +649,8 @@ class Whisper:
                           prompts: Optional[Sequence[Sequence[int]]] = None, return_logprobs: bool = False,
                           no_speech_token: Optional[int] = None, n_init: Optional[int] = None,
                           detect_language: Optional[Sequence[int]] = None, repetition_penalty: Optional[float] = None,
-                          no_repeat_ngram_size: Optional[int] = None, sequence_bias=None, bad_words_ids=None, top_k: Optional[int] = None):
+                          no_repeat_ngram_size: Optional[int] = None, sequence_bias=None, bad_words_ids=None, top_k: Optional[int] = None,
+                          constraint=None, free_from: Optional[int] = None):
         """Pipelined form (wm_transcribe_submit): enqueue encoder + greedy loop for this batch on pipeline slot 0..7 and
         return at once; `transcribe_wait(slot)` collects the ids.  Submitting batch i+1 before waiting for batch i lets
         its encoder overlap batch i's decode.  return_token_timestamps / n_frames: as transcribe_batch; the matching
@@ -615,22 +660,27 @@ class Whisper:
         returns what transcribe_batch returns.  repetition_penalty / no_repeat_ngram_size: as transcribe_batch; the pass keeps the
         values it was submitted with, and under coalesce = 2 it pairs only with a submit that carries the same values.
         sequence_bias / bad_words_ids: as transcribe_batch, kept and paired likewise (the same lists as the previous call = the same table).
-        top_k: as transcribe_batch, kept and paired likewise; the matching transcribe_wait returns the extra last element."""
+        top_k: as transcribe_batch, kept and paired likewise; the matching transcribe_wait returns the extra last element.
+        constraint / free_from: as transcribe_batch, kept and paired like the sequence-bias table; the matching transcribe_wait
+        returns constraint_match as its last element."""
         rp = _lib.repeat_args(repetition_penalty, no_repeat_ngram_size)
         sb = _lib.seq_bias_args(sequence_bias, bad_words_ids, self.config.vocab_size)
         k = _lib.top_k_arg(top_k, return_logprobs)
+        ct = _lib.constraint_args(constraint, free_from, self.config.vocab_size, eot, timestamps)
         lang = None
         if detect_language is not None:
             lang = self._lang_args(detect_language, n_init, prompt, prompts, return_token_timestamps, no_speech_token, return_logprobs)
         ns = None if lang else self._ns_args(no_speech_token, n_init, prompt, prompts, return_logprobs)
         if self._h is None:
             raise _lib.WhisperMiError("model not loaded")
-        self._set_repeat(rp, sb, k)
+        self._set_repeat(rp, sb, k, ct)
         ptr, on_dev, B, keep = _mel_arg(mel, self.config)
         opts, keep2 = self._opts(prompt, eot, max_loop, ignore_eot, suppress_tokens, begin_suppress_tokens, timestamps)
         p = keep2[0]
         self._pending_top_k = getattr(self, "_pending_top_k", {})
         self._pending_top_k[slot] = (k, self._plens(prompt, prompts, B)) if k else None
+        self._pending_ct = getattr(self, "_pending_ct", {})
+        self._pending_ct[slot] = B if ct else None
         if lang:
             total, tag = self._lang_call(slot, ptr, on_dev, B, opts, p, prompts, max_loop, lang, return_logprobs, no_speech_token)
             self._pending = getattr(self, "_pending", {})
@@ -667,8 +717,11 @@ class Whisper:
 
     def transcribe_wait(self, slot: int = 0):
         top = getattr(self, "_pending_top_k", {}).pop(slot, None)
+        ct = getattr(self, "_pending_ct", {}).pop(slot, None)
         res = self._transcribe_wait(slot)
-        return res + (self._top_k(slot, *top),) if top else res
+        if top:
+            res = res + (self._top_k(slot, *top),)
+        return self._with_last(res, self._constraint_match(slot, ct)) if ct else res
 
     def _transcribe_wait(self, slot):
         B, total, _keep, tt = self._pending.pop(slot)
@@ -822,6 +875,10 @@ class Whisper:
         rows, width = int(packed.shape[0]), int(packed.shape[1])
         if not packed.is_cuda or packed.dtype.itemsize != 4 or not packed.is_contiguous():
             raise ValueError("packed must be a contiguous int32 CUDA tensor")
+        import torch
+        # the library writes `packed` on its own HIP stream: whatever torch still has queued on the buffer (the fill that made it)
+        # must have run, or it lands on top of the packed rows
+        torch.cuda.current_stream(packed.device).synchronize()
         _lib.check(_lib.lib().wm_transcribe_wait_device(self._h, slot, C.c_void_p(packed.data_ptr()), rows, width - 1))
         self.last_tokens = self.last_counts = None
 

@@ -589,3 +589,24 @@ def window_gather(mel, items, W: int, fill: float = 0.0):
     _lib.check(_lib.lib().wm_op_window_gather(_fp(out), _fp(m), it.ctypes.data_as(C.POINTER(C.c_int32)), it.shape[0], m.shape[0], m.shape[1],
                                               m.shape[2], int(W)))
     return out
+
+
+def constraint_states(tokens, prompt_len, n_ids, vocab: int, phrases, steps: int, eot: int = -1, free_from=None, ngram: int = 0):
+    """The phrase-list constraint's bookkeeping alone (wm_op_constraint_states): tokens / prompt_len / n_ids as
+    repeat_sets, phrases as transcribe_batch's constraint= -> (node [steps + 1, B] int32, mask [steps + 1, B, ceil(vocab / 32)] uint32,
+    the rows' ban words): entry 0 behind the init kernels, entry s behind the argmax launch of step s."""
+    tok = np.ascontiguousarray(tokens, np.int32)
+    pl, nn = np.ascontiguousarray(prompt_len, np.int32).ravel(), np.ascontiguousarray(n_ids, np.int32).ravel()
+    if tok.ndim != 2 or pl.size != tok.shape[0] or nn.size != tok.shape[0]:
+        raise ValueError("tokens must be [B, stride], prompt_len and n_ids [B]")
+    ct = _lib.constraint_args(phrases, free_from, vocab, eot)
+    if ct is None:
+        raise ValueError("the list of phrases is empty")
+    ids, off, n, ff = ct[1]
+    B, stride = tok.shape
+    node = np.zeros((steps + 1, B), np.int32)
+    mask = np.zeros((steps + 1, B, (vocab + 31) // 32), np.uint32)
+    ip, up = (lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))), (lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32)))
+    _lib.check(_lib.lib().wm_op_constraint_states(ip(node), up(mask), ip(tok), ip(pl), ip(nn), B, stride, int(vocab), int(eot), int(ngram),
+                                                  ip(ids), ip(off), n, ff, int(steps)))
+    return node, mask
