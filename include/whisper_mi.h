@@ -289,6 +289,38 @@ int wm_score_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int B,
                  const int32_t* ids_len, int ids_stride, const int32_t* context_len, float* token_logprobs, int32_t* top_ids, float* sum_logprob,
                  float* avg_logprob);
 
+/* ---- n-best scoring ---------------------------------------------------------------------------------------------
+ * Several candidate transcripts per clip on ONE encoder run: mel holds U clips (as wm_score takes it), clip u has n_cand[u] >= 1
+ * candidates, and the R = sum n_cand[u] id rows — ids, ids_len, ids_stride, context_len exactly as wm_score takes and validates them —
+ * are grouped by clip in the caller's order (clip 0's candidates first).  The encoder and the cross-K/V projection run over the U
+ * clips, the decoder over the R rows; each row's cross-attention reads its clip's encoder output through a row map.
+ * Per row: token_logprobs, top_ids (or NULL) [R][ids_stride], sum_logprob, avg_logprob [R] are what wm_score writes for the same rows
+ * with each clip's mel repeated n_cand[u] times, bit for bit.
+ * Per clip, computed on the device with key[c] = sum_logprob of the clip's candidate c (normalize != 0: avg_logprob) and row0[u] =
+ * n_cand[0] + .. + n_cand[u - 1]:
+ *   order [R]: entries [row0[u], row0[u] + n_cand[u]) hold the candidate indices 0 .. n_cand[u] - 1 sorted by key descending, equal
+ *     keys lower index first;   best [U] = order[row0[u]];
+ *   posterior [R]: exp(key_c - M_u) / sum_j exp(key_j - M_u) over the clip's candidates, M_u the clip's largest key, the sum in
+ *     ascending candidate order (fp32, expf): with normalize = 0 the model's posterior over the candidate list.  A clip's results do
+ *     not depend on the other clips of the call.
+ * WM_E_ARG, nothing launched: everything wm_score refuses, per row; U < 1 or an n_cand[u] < 1; R over max_batch; a multi-lane decode
+ * state.  State rules as wm_score: never coalesced, slot 0's state for the synchronous forms, no usable pass afterwards; the
+ * wm_transcribe_wait, wm_score_wait, wm_align_wait and wm_score_nbest_wait families refuse each other's passes with WM_E_STATE (the
+ * pass stays pending).  The next pass of any kind on the state clears the row map.  wm_score_phases serves the pass (its merge
+ * phase includes the ranking launch). */
+int wm_score_nbest(wm_model* m, const float* mel, int mel_on_device, int U, const int32_t* n_cand, int normalize, int pos_mode,
+                   const int32_t* ids, const int32_t* ids_len, int ids_stride, const int32_t* context_len, float* token_logprobs,
+                   int32_t* top_ids, float* sum_logprob, float* avg_logprob, int32_t* order, int32_t* best, float* posterior);
+int wm_score_nbest_submit(wm_model* m, int slot, const float* mel, int mel_on_device, int U, const int32_t* n_cand, int normalize, int pos_mode,
+                          const int32_t* ids, const int32_t* ids_len, int ids_stride, const int32_t* context_len);
+int wm_score_nbest_wait(wm_model* m, int slot, float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob, int32_t* order,
+                        int32_t* best, float* posterior);
+/* PCM in (the layout of wm_log_mel, U rows): front end + wm_score_nbest without the mel leaving the GPU */
+int wm_score_nbest_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int U, int stride, const int32_t* n_cand, int normalize,
+                       int pos_mode, const int32_t* ids, const int32_t* ids_len, int ids_stride, const int32_t* context_len,
+                       float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob, int32_t* order, int32_t* best,
+                       float* posterior);
+
 /* ---- repetition processors -------------------------------------------------------------------------------------
  * HF generate's repetition_penalty (RepetitionPenaltyLogitsProcessor) and no_repeat_ngram_size (NoRepeatNGramLogitsProcessor) for
  * every greedy pass asked for from now on: wm_transcribe and its _submit / _rows / _lp / _lp_ns / _lang / _tt / _pcm forms and the
@@ -768,6 +800,11 @@ int wm_op_attention_cached(float* out, const float* q, const float* k, const flo
  * bit for bit. */
 int wm_op_attention_cached_lo(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
                               int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo);
+/* wm_op_attention_cached's chunked forms (n_chunks >= 2; nq = 0 or 4) with K/V by row map: k, v hold n_utt clips of t
+ * rows, and the query row in batch slot b — of q_B slots, or of B when q_B == 0 — attends over clip utt_of[b] (0 <= utt_of[b] < n_utt,
+ * else WM_E_ARG).  Equal bit for bit to wm_op_attention_cached on k[utt_of], v[utt_of]. */
+int wm_op_attention_cached_map(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
+                               int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* utt_of, int n_utt);
 /* One launch of the decode step's skinny linear, out[B, N] = epi(pro(x)[B, K]·W[N, K]ᵀ + bias), wired as a decode step wires its six
  * per-layer launches.  W is rounded to dtype on upload.  pro: ln_g / ln_b [K] non-NULL: LayerNorm (eps 1e-5) of the fp32 rows x;
  * x_is_t != 0 (no LayerNorm): x is uploaded in dtype, as the producer kernel leaves it.  epi: + bias [N] (or NULL); act != 0: GELU
@@ -876,6 +913,13 @@ int wm_op_score_logits(float* logprob, int32_t* top_id, const float* x, const fl
  * 1 <= nsplit <= 64 (chunks of ceil(n_keys / nsplit) keys; trailing chunks may be empty).  Known-answer tests. */
 int wm_op_xattn(float* out, const float* q, const float* Wk, const float* Wv, const float* bv, const float* x, int rows, int q_B,
                 int n_utt, int n_keys, int n_heads, int nsplit, int out_dtype);
+/* wm_op_xattn with X by row map: utt(r) = utt_of[r % q_B] when q_B > 0 else utt_of[r]; utt_of holds q_B (or rows) entries
+ * of [0, n_utt), else WM_E_ARG; any number of rows may share a clip.  Equal bit for bit to wm_op_xattn on x[utt_of]. */
+int wm_op_xattn_map(float* out, const float* q, const float* Wk, const float* Wv, const float* bv, const float* x, int rows, int q_B,
+                    int n_utt, int n_keys, int n_heads, int nsplit, int out_dtype, const int32_t* utt_of);
+/* The n-best ranking launch alone: key [R = sum n_cand] fp32 grouped by clip, n_cand [U] >= 1; order, posterior [R] and
+ * best [U] as wm_score_nbest defines them.  A non-finite key is refused with WM_E_ARG (NaN keys have no rank).  Known-answer tests. */
+int wm_op_score_rank(int32_t* order, int32_t* best, float* posterior, const float* key, const int32_t* n_cand, int U);
 /* The first launch of wm_op_xattn alone: q'[r, h] = (0.125·q_h[r])·Wk_h as the X sweep reads it, three bf16 images whose sum is the
  * fp32 product (x = hi + mid + lo by truncation).  images [rows, 3, n_heads, 64·n_heads], widened to fp32; q [rows, 64·n_heads] fp32;
  * Wk [64·n_heads, 64·n_heads] rounded to bf16 on upload.  late_loads != 0: the loop that requests its Wk rows after q is staged

@@ -248,6 +248,72 @@ public:
         }
         return r;
     }
+    // Several candidate transcripts per clip on one encoder run (wm_score_nbest): candidates[u] = clip u's id rows, each as
+    // a row of score(); context_len: per candidate ROW, clip by clip (empty = 1).  Rows are flattened clip by clip; rows, order and
+    // posterior of clip u are entries [row0[u], row0[u] + n_cand[u]) of the flat results.  order: candidate indices by sum_logprob
+    // (normalize: avg_logprob) descending, equal keys lower index first; best[u] = the first of them; posterior: softmax of the keys
+    // over the clip's candidates.
+    struct NbestResult {
+        ScoreResult rows;  // per candidate row, as score() on the clip's mel repeated
+        std::vector<int32_t> n_cand, row0, order, best;
+        std::vector<float> posterior;
+    };
+    // The flat table of an n-best call, built on the host alone (tests/cpp/nbest_check.cpp): rows clip by clip, zero-padded to the
+    // longest; throws std::invalid_argument on a wrong clip count, an empty clip or a wrong number of context lengths.
+    struct NbestTable {
+        int R = 0, stride = 2;
+        std::vector<int32_t> tab, len, n_cand, row0, utt_of;
+    };
+    static NbestTable nbest_table(int U, const std::vector<std::vector<std::vector<int32_t>>>& candidates, const std::vector<int32_t>& context_len) {
+        if (U < 1 || (int)candidates.size() != U) throw std::invalid_argument("score_candidates: one candidate list per clip");
+        NbestTable t;
+        for (int u = 0; u < U; ++u) {
+            const auto& c = candidates[u];
+            if (c.empty()) throw std::invalid_argument("score_candidates: every clip needs at least one candidate");
+            t.row0.push_back(t.R);
+            t.n_cand.push_back((int32_t)c.size());
+            t.R += (int)c.size();
+            for (const auto& row : c) {
+                t.stride = std::max(t.stride, (int)row.size());
+                t.utt_of.push_back(u);
+            }
+        }
+        if (!context_len.empty() && (int)context_len.size() != t.R) throw std::invalid_argument("score_candidates: one context_len per candidate row");
+        t.tab.assign((size_t)t.R * t.stride, 0);
+        for (const auto& c : candidates)
+            for (const auto& row : c) {
+                std::copy(row.begin(), row.end(), t.tab.begin() + t.len.size() * (size_t)t.stride);
+                t.len.push_back((int32_t)row.size());
+            }
+        return t;
+    }
+    NbestResult score_candidates(const float* mels, int U, const std::vector<std::vector<std::vector<int32_t>>>& candidates,
+                                 const std::vector<int32_t>& context_len = {}, bool normalize = false, bool want_top_ids = false) const {
+        need_model();
+        const NbestTable t = nbest_table(U, candidates, context_len);
+        const int R = t.R, stride = t.stride;
+        const std::vector<int32_t>&tab = t.tab, &len = t.len;
+        std::vector<int32_t> top((size_t)R * stride);
+        NbestResult r;
+        r.n_cand = t.n_cand;
+        r.row0 = t.row0;
+        std::vector<float> lp((size_t)R * stride);
+        r.rows.sum_logprob.assign(R, 0.f);
+        r.rows.avg_logprob.assign(R, 0.f);
+        r.order.assign(R, -1);
+        r.best.assign(U, -1);
+        r.posterior.assign(R, 0.f);
+        check(wm_score_nbest(model_, mels, 0, U, r.n_cand.data(), normalize ? 1 : 0, WM_POS_REF, tab.data(), len.data(), stride,
+                             context_len.empty() ? nullptr : context_len.data(), lp.data(), want_top_ids ? top.data() : nullptr,
+                             r.rows.sum_logprob.data(), r.rows.avg_logprob.data(), r.order.data(), r.best.data(), r.posterior.data()));
+        r.rows.token_logprobs.assign(R, {});
+        if (want_top_ids) r.rows.top_ids.assign(R, {});
+        for (int b = 0; b < R; ++b) {
+            r.rows.token_logprobs[b].assign(lp.begin() + (size_t)b * stride, lp.begin() + (size_t)b * stride + len[b]);
+            if (want_top_ids) r.rows.top_ids[b].assign(top.begin() + (size_t)b * stride, top.begin() + (size_t)b * stride + len[b]);
+        }
+        return r;
+    }
     // When each id of a given transcript was spoken (wm_align): ids / context_len as score(); n_frames: per row the mel frames
     // of real audio (empty = the whole window).  Returns per row one time per id: 0 for the context, then HF's _extract_token_timestamps
     // over the teacher-forced cross-attentions.  scores (optional): what score() returns for the same inputs, from the same pass.

@@ -46,6 +46,8 @@ SYMBOLS = [
     "wm_set_top_k", "wm_transcribe_top_k", "wm_op_logits_topk",
     "wm_set_constraint", "wm_transcribe_constraint_match", "wm_op_constraint_states",
     "wm_op_fe_tables", "wm_op_fe_frames", "wm_op_fe_mel_log", "wm_op_fe_mel_norm", "wm_op_window_gather",
+    "wm_score_nbest", "wm_score_nbest_submit", "wm_score_nbest_wait", "wm_score_nbest_pcm",
+    "wm_op_attention_cached_map", "wm_op_xattn_map", "wm_op_score_rank",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -160,6 +162,39 @@ def score_args(ids, context_len, B, vocab, n_text_ctx, max_batch):
     return tab, lens, ctx
 
 
+def nbest_args(candidates, context_len, U, vocab, n_text_ctx, max_batch):
+    """Checks an n-best score call's arguments on the host (the library refuses the same with WM_E_ARG) -> (table
+    [R, stride] int32, lengths [R], context lengths [R], n_cand [U], utt_of [R], row0 [U]).  candidates: per clip a non-empty list of
+    id lists (each as a row of score_args); the R = sum n_cand rows are flattened clip by clip in the caller's order.  context_len:
+    None (= 1), one number, one per row (flat, [R]), or per clip a list with one entry per candidate."""
+    import numpy as np
+    try:
+        clips = [list(c) for c in candidates]
+    except TypeError:
+        raise ValueError("candidates: one list of id lists per clip")
+    if U < 1 or len(clips) != U:
+        raise ValueError(f"{len(clips)} candidate lists for {U} clips (at least one clip)")
+    n_cand = np.asarray([len(c) for c in clips], np.int32)
+    if n_cand.min() < 1:
+        raise ValueError("every clip needs at least one candidate")
+    R = int(n_cand.sum())
+    if R > max_batch:
+        raise ValueError(f"{R} candidates in all exceed max_batch = {max_batch}")
+    if context_len is not None and not np.isscalar(context_len):
+        cl = list(context_len)
+        if len(cl) == U and all(not np.isscalar(c) for c in cl):  # per clip, one entry per candidate
+            if any(len(c) != n for c, n in zip(cl, n_cand)):
+                raise ValueError("context_len per clip needs one entry per candidate")
+            cl = [v for c in cl for v in c]
+        if len(cl) != R:
+            raise ValueError(f"context_len needs one entry per candidate row ({R}), got {len(cl)}")
+        context_len = cl
+    tab, lens, ctx = score_args([r for c in clips for r in c], context_len, R, vocab, n_text_ctx, max_batch)
+    row0 = (np.cumsum(n_cand) - n_cand).astype(np.int32)
+    utt_of = np.repeat(np.arange(U, dtype=np.int32), n_cand)
+    return tab, lens, ctx, n_cand, utt_of, row0
+
+
 def align_args(ids, context_len, n_frames, B, vocab, n_text_ctx, max_batch, n_audio_ctx):
     """Checks an align call's arguments on the host (the library refuses the same with WM_E_ARG) -> (table, lengths, context
     lengths, n_frames [B] int32 or None).  ids / context_len: as score_args; n_frames: None (every column) or one count of real mel
@@ -249,6 +284,7 @@ def lib():
     L.wm_op_ln_matmul_nt.argtypes = [fp] * 6 + [C.c_int] * 5
     L.wm_op_attention.argtypes = [fp] * 4 + [C.c_int] * 3
     L.wm_op_attention_cached.argtypes = [fp] * 4 + [C.c_int] * 9
+    L.wm_op_attention_cached_map.argtypes = [fp] * 4 + [C.c_int] * 9 + [ip, C.c_int]
     L.wm_op_dec_linear.argtypes = [fp] * 7 + [C.c_int] * 8 + [fp, fp] + [C.c_int] * 5 + [fp, C.POINTER(C.c_int8)] + [C.c_int] * 3
     L.wm_op_dec_linear_long.argtypes = L.wm_op_dec_linear.argtypes
     L.wm_op_layer_norm.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_float]
@@ -291,6 +327,11 @@ def lib():
     L.wm_score_wait.argtypes = [vp, C.c_int, fp, ip, fp, fp]
     L.wm_score_pcm.argtypes = [vp, fp, ip, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip, fp, ip, fp, fp]
     L.wm_score_phases.argtypes = [vp, C.c_int, fp]
+    L.wm_score_nbest.argtypes = [vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, ip, ip, C.c_int, ip, fp, ip, fp, fp, ip, ip, fp]
+    L.wm_score_nbest_submit.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, ip, ip, C.c_int, ip]
+    L.wm_score_nbest_wait.argtypes = [vp, C.c_int, fp, ip, fp, fp, ip, ip, fp]
+    L.wm_score_nbest_pcm.argtypes = [vp, fp, ip, C.c_int, C.c_int, ip, C.c_int, C.c_int, ip, ip, C.c_int, ip, fp, ip, fp, fp, ip, ip, fp]
+    L.wm_op_score_rank.argtypes = [ip, ip, fp, fp, ip, C.c_int]
     L.wm_op_score_logits.argtypes = [fp, ip, fp, fp, fp, fp, ip] + [C.c_int] * 4
     L.wm_align.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip, ip, fp, fp, fp, fp]
     L.wm_align_submit.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip, ip, C.c_int]
@@ -305,6 +346,7 @@ def lib():
     L.wm_long_result_windows.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_int64), fp, fp, ip]
     L.wm_long_result_skip_stats.argtypes = [vp, ip]
     L.wm_op_xattn.argtypes = [fp] * 6 + [C.c_int] * 7
+    L.wm_op_xattn_map.argtypes = [fp] * 6 + [C.c_int] * 7 + [ip]
     L.wm_op_xattn_absorb.argtypes = [fp] * 3 + [C.c_int] * 3
     L.wm_bench_kernel.argtypes = [vp, vp, C.c_int, C.c_int, fp]
     L.wm_bench_bytes.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double)]

@@ -23,7 +23,7 @@ LIB = os.path.join(CSRC, "libwhispermi.so")
 LIB_DEV = os.path.join(CSRC, "libwhispermi_dev.so")
 SOURCES = ["whisper_mi.cpp", "wm_align.cpp", "wm_frontend.cpp", "wm_chunked.cpp", "wm_score.cpp", "wm_long.cpp", "wm_bench.cpp", "wm_ops.cpp",
            "kernels_encoder.hip", "kernels_decoder.hip", "kernels_frontend.hip", "kernels_align.hip", "kernels_score.hip", "kernels_chunked.hip"]
-HEADERS = ["wm_device.h", "wm_kernels.h", "wm_host.h", "wm_runtime.h", "../../include/whisper_mi.h", "../../include/wm_synth.h"]
+HEADERS = ["wm_device.h", "wm_kernels.h", "wm_host.h", "wm_runtime.h", "xattn_sweep.inc", "../../include/whisper_mi.h", "../../include/wm_synth.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=on"]
 

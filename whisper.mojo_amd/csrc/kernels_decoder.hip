@@ -1378,8 +1378,10 @@ template int launch_dec_logits<f16>(const DecLinearParams&, hipStream_t);
 // are aligned at the END of the longest prompt, so a shorter prompt has dead cache rows in front.  The sweep starts AT key_lo (row
 // slot r takes keys key_lo + r, key_lo + r + RPS, ...): a row's arithmetic is what it would be alone with its own unpadded prompt.
 // An empty window (a dead prefill slot) stores zeros.  LO = false is the kernel as it always was.
-template <typename TKV, int LPH, bool FAST, bool NT, int U, int NQ, bool LO>
-__device__ __forceinline__ void attn_decode_body(const AttnDecParams& p, const int* __restrict__ key_lo) {
+// MAP (n-best scoring; cross-attention forms only): the K/V this workgroup reads are those of utt_of[bq] instead of bq —
+// several query rows share one clip's K/V.  Queries, outputs and every sum are the row's own: MAP = false is the kernel as it always was.
+template <typename TKV, int LPH, bool FAST, bool NT, int U, int NQ, bool LO, bool MAP = false>
+__device__ __forceinline__ void attn_decode_body(const AttnDecParams& p, const int* __restrict__ key_lo, const int* __restrict__ utt_of = nullptr) {
     // NQ > 1 (prompt prefill, cross-attention): the workgroup of utterance b serves the NQ query rows t * B + b from ONE
     // sweep of that utterance's K/V chunk — each cache row is read once for all prompt positions.
     constexpr int EPL = 64 / LPH;  // elements per lane
@@ -1389,7 +1391,8 @@ __device__ __forceinline__ void attn_decode_body(const AttnDecParams& p, const i
     if (p.ts && NT && b == 0 && split == 0 && threadIdx.x == 0) ts_put(p.ts, p.ts_id, 0);
     const int LPR = p.H * LPH;
     const int RPS = p.rps;  // key rows swept per step = active threads / LPR
-    const int bk = (NQ == 1 && p.q_B > 0) ? b % p.q_B : b;  // utterance whose K/V this workgroup reads
+    const int bq = (NQ == 1 && p.q_B > 0) ? b % p.q_B : b;  // the row's slot in the batch
+    const int bk = MAP ? utt_of[bq] : bq;  // utterance whose K/V this workgroup reads
     const int len = p.n_keys >= 0 ? p.n_keys : p.ctl->len + 1 + ((NQ == 1 && p.q_B > 0) ? b / p.q_B : 0);  // (scalar chain kernarg -> ctl -> len: the loop bounds need it before any K/V row is requested)
     const int qstride = NQ > 1 ? p.q_B : 0;  // query / output row of position t: b + t * qstride
     const int lo = LO ? key_lo[bk] : 0;
@@ -1531,7 +1534,13 @@ template <typename TKV, int LPH, bool FAST, int U>
 __global__ __launch_bounds__(512) void attn_decode_lo_kernel(AttnDecParams p, const int* __restrict__ key_lo) {
     attn_decode_body<TKV, LPH, FAST, false, U, 1, true>(p, key_lo);
 }
-template <typename TKV> int launch_attn_decode(const AttnDecParams& p, hipStream_t st, const int* key_lo) {
+// the cross-attention forms (nq = 4 or one query per workgroup) with the K/V of utt_of[slot].  Never the non-temporal loads of the
+// forms it mirrors: the rows of one clip re-read its K/V, so the stream is not read-once (loads only: the arithmetic is the same).
+template <typename TKV, int LPH, bool FAST, int U, int NQ>
+__global__ __launch_bounds__(512) void attn_decode_map_kernel(AttnDecParams p, const int* __restrict__ utt_of) {
+    attn_decode_body<TKV, LPH, FAST, false, U, NQ, false, true>(p, nullptr, utt_of);
+}
+template <typename TKV> int launch_attn_decode(const AttnDecParams& p, hipStream_t st, const int* key_lo, const int* utt_of) {
     constexpr int LPH = sizeof(TKV) == 4 ? 16 : 8;
     constexpr bool FAST = sizeof(TKV) == 2;
     const int LPR = p.H * LPH;
@@ -1552,6 +1561,20 @@ template <typename TKV> int launch_attn_decode(const AttnDecParams& p, hipStream
     if (key_lo) {  // per-row prompts: the self-attention forms with a key window
         if (p.n_keys >= 0 || !p.direct_out || p.nq > 1) return launch_refuse("attn_decode: key_lo belongs to the single-workgroup self-attention forms");
         hipLaunchKernelGGL((attn_decode_lo_kernel<TKV, LPH, FAST, 4>), grid, block, 0, st, q, key_lo);
+        return WM_LAUNCH_OK;
+    }
+    if (utt_of) {  // n-best scoring: the chunked cross-attention forms, K/V by row map (same grid, block and U as the forms below)
+        if (p.n_keys < 0 || p.direct_out) return launch_refuse("attn_decode: utt_of belongs to the chunked cross-attention forms");
+        if (p.nq == 4) {
+            hipLaunchKernelGGL((attn_decode_map_kernel<TKV, LPH, FAST, 4, 4>), dim3(p.nsplit, p.q_B), block, 0, st, q, utt_of);
+            return WM_LAUNCH_OK;
+        }
+        static const int map_pad_env = wm_env("WM_ATTN_LDS_PAD") ? atoi(wm_env("WM_ATTN_LDS_PAD")) : -1;  // dev A/B override, as below
+        const int map_pad = map_pad_env >= 0 ? map_pad_env : p.lds_pad;
+        if (map_pad > 40 * 1024)
+            if (const hipError_t e = ensure_dyn_lds<&attn_decode_map_kernel<TKV, LPH, FAST, 4, 1>>(map_pad); e != hipSuccess)
+                return launch_hip_failed("attn_decode: dynamic LDS attribute", e);
+        hipLaunchKernelGGL((attn_decode_map_kernel<TKV, LPH, FAST, 4, 1>), grid, block, map_pad, st, q, utt_of);
         return WM_LAUNCH_OK;
     }
     static const bool nt_off = wm_env("WM_NO_NT") != nullptr;
@@ -1593,9 +1616,9 @@ template <typename TKV> int launch_attn_decode(const AttnDecParams& p, hipStream
     }
     return WM_LAUNCH_OK;
 }
-template int launch_attn_decode<float>(const AttnDecParams&, hipStream_t, const int*);
-template int launch_attn_decode<bf16>(const AttnDecParams&, hipStream_t, const int*);
-template int launch_attn_decode<f16>(const AttnDecParams&, hipStream_t, const int*);
+template int launch_attn_decode<float>(const AttnDecParams&, hipStream_t, const int*, const int*);
+template int launch_attn_decode<bf16>(const AttnDecParams&, hipStream_t, const int*, const int*);
+template int launch_attn_decode<f16>(const AttnDecParams&, hipStream_t, const int*, const int*);
 
 // merge the key-chunk partials: out[b][h*64+e] = Σ_s w_s·o_s / Σ_s w_s·l_s,  w_s = exp(m_s − max m).
 // One wave per (utterance, head): lane s owns chunk s's (m, l) — one exp per chunk, not per element — and the
@@ -1736,172 +1759,18 @@ __device__ __forceinline__ void wave_lds_fence() {  // this wave's LDS writes / 
 
 template <int H, bool NT>
 __global__ __launch_bounds__(256, 2) void xattn_kernel(XAttnParams p) {
-    constexpr int D = 64 * H, NKS = D / 32, NDB = D / 16;
-    constexpr int XP = D + 16;  // row pitch (elements): 32·H + 8 dwords, so the 8 rows of one transposed read hit disjoint banks
-    __shared__ __attribute__((aligned(16))) bf16 sQ[3 * (H + 1) * XP];  // q' images; row H of each image is zero
-    __shared__ __attribute__((aligned(16))) bf16 sX[4 * 16 * XP];        // per wave: the parked 16-key tile; at the end: Y of 4 waves
-    __shared__ float sML[4][H][2];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r16 = lane & 15, g = lane >> 4;
-    const int split = blockIdx.x, row = blockIdx.y;
-    const int utt = p.q_B > 0 ? row % p.q_B : row;
-    const int len = p.n_keys, chunk = (len + p.nsplit - 1) / p.nsplit;
-    const int j0 = split * chunk, j1 = min(len, j0 + chunk);
-    const int hq = r16 < H ? r16 : H;
-    const bf16* X = (const bf16*)p.X + (size_t)utt * p.x_stride;
-    bf16* park = sX + w * 16 * XP;
-    const int ntile = j1 > j0 ? (j1 - j0 + 15) / 16 : 0;
-
-    auto load = [&](bf16x8 (&xr)[NKS], int t) {
-        const int key = max(min(j0 + 16 * t + r16, j1 - 1), 0);
-        const bf16* src = X + (size_t)key * D + g * 8;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            if (NT)
-                xr[ks] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(src + ks * 32));
-            else
-                xr[ks] = *reinterpret_cast<const bf16x8*>(src + ks * 32);
-        }
-    };
-    // the wave's first X tile is requested before anything else: the q' staging and its barrier run under that round trip
-    bf16x8 xa[NKS], xb[NKS];
-    if (w < ntile) load(xa, w);
-    {  // q' images -> sQ: a thread owns one 16-byte column of every RPP-th (image, head) row, so its index split is done once
-        constexpr int C8 = D / 8, RPP = 256 / C8;
-        static_assert(RPP >= 3, "the three zero rows are filled by the first three row slots");
-        const bf16x8* src = (const bf16x8*)((const bf16*)p.qs + (size_t)row * 3 * H * D);
-        const int sr = threadIdx.x / C8, sc = threadIdx.x % C8;
-        if (sr < RPP) {
-#pragma unroll
-            for (int rr = sr; rr < 3 * H; rr += RPP) {
-                const int img = rr / H, hh = rr - img * H;
-                *reinterpret_cast<bf16x8*>(&sQ[(img * (H + 1) + hh) * XP + sc * 8]) = src[rr * C8 + sc];
-            }
-            if (sr < 3) *reinterpret_cast<bf16x8*>(&sQ[(sr * (H + 1) + H) * XP + sc * 8]) = bf16x8{};
-        }
-    }
-    __syncthreads();
-    f32x4 y[NDB];
-#pragma unroll
-    for (int db = 0; db < NDB; ++db) y[db] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run = -1e10f, l_run = 0.f;
-    auto consume = [&](const bf16x8 (&xr)[NKS], int t) {
-        // one accumulator per q' term: three independent MFMA chains of NKS instead of one dependent chain of 3·NKS
-        f32x4 sk[3] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const bf16x8 qf = *reinterpret_cast<const bf16x8*>(&sQ[(k * (H + 1) + hq) * XP + ks * 32 + g * 8]);
-                sk[k] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xr[ks], qf, sk[k], 0, 0, 0);
-            }
-        const f32x4 s = (sk[0] + sk[1]) + sk[2];
-        // lane (head r16, group g) holds the scores of keys 4g..4g+3 of the tile
-        const int kb = j0 + 16 * t + 4 * g;
-        float sc[4], bm = -1e30f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            sc[r] = kb + r < j1 ? s[r] : -1e30f;
-            bm = fmaxf(bm, sc[r]);
-        }
-        bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
-        bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-        const float m_new = fmaxf(m_run, bm);
-        const float alpha = expf(m_run - m_new);
-        float pe[4], ps = 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            pe[r] = expf(sc[r] - m_new);
-            ps += pe[r];
-        }
-        ps += __shfl_xor(ps, 16, 64);
-        ps += __shfl_xor(ps, 32, 64);
-        l_run = l_run * alpha + ps;
-        m_run = m_new;
-        typedef __attribute__((ext_vector_type(4))) unsigned short u16x4;
-        u16x4 ph, pm, pl;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            unsigned short a, b, c;
-            split3_1(pe[r], a, b, c);
-            ph[r] = a;
-            pm[r] = b;
-            pl[r] = c;
-        }
-        const bf16x4 fh = __builtin_bit_cast(bf16x4, ph), fm = __builtin_bit_cast(bf16x4, pm), fl = __builtin_bit_cast(bf16x4, pl);
-        wave_lds_fence();  // the previous tile's transposed reads are done
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) *reinterpret_cast<bf16x8*>(&park[r16 * XP + ks * 32 + g * 8]) = xr[ks];
-        wave_lds_fence();
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) {
-            const bf16x4 xt = lds_tr16_bf16(&park[(4 * g + (r16 >> 2)) * XP + db * 16 + (r16 & 3) * 4]);
-            f32x4 a = y[db] * alpha;
-            a = mma16_bf16(xt, fh, a);
-            a = mma16_bf16(xt, fm, a);
-            y[db] = mma16_bf16(xt, fl, a);
-        }
-    };
-
-    if (w < ntile) {
-        int t = w;
-        while (true) {
-            const bool more1 = t + 4 < ntile;
-            if (more1) load(xb, t + 4);
-            consume(xa, t);
-            t += 4;
-            if (!more1) break;
-            const bool more2 = t + 4 < ntile;
-            if (more2) load(xa, t + 4);
-            consume(xb, t);
-            t += 4;
-            if (!more2) break;
-        }
-    }
-    // merge the four waves (as attn_decode_kernel merges its row slots), write the chunk's partial
-    __syncthreads();
-    float* sY = reinterpret_cast<float*>(sX);  // [4][H][D]
-    if (r16 < H) {
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sY[(w * H + r16) * D + db * 16 + 4 * g + r] = y[db][r];
-        if (g == 0) {
-            sML[w][r16][0] = m_run;
-            sML[w][r16][1] = l_run;
-        }
-    }
-    __syncthreads();
-    const size_t prow = (size_t)row * p.nsplit + split;
-    // the four waves' weights of a head: once per head (they were one expf per wave and output element), then 16-byte combines
-    __shared__ float sWg[4][H];
-    if (threadIdx.x < H) {
-        const int h = threadIdx.x;
-        float M = -1e10f;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) M = fmaxf(M, sML[v][h][0]);
-        float L = 0.f;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const float wgt = sML[v][h][1] > 0.f ? expf(sML[v][h][0] - M) : 0.f;
-            L += wgt * sML[v][h][1];
-            sWg[v][h] = wgt;
-        }
-        p.part_ml[(prow * H + h) * 2] = M;
-        p.part_ml[(prow * H + h) * 2 + 1] = L;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x * 4; i < H * D; i += 256 * 4) {
-        const int h = i / D;
-        f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const float wgt = sWg[v][h];
-            const f32x4 yv = *reinterpret_cast<const f32x4*>(&sY[v * H * D + i]);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] += wgt * yv[k];
-        }
-        *reinterpret_cast<f32x4*>(p.part_y + prow * H * D + i) = o;
-    }
+#define XATTN_UTT(slot) slot
+#include "xattn_sweep.inc"
+#undef XATTN_UTT
+}
+// The same sweep with X by row map (n-best scoring): the row in batch slot b sweeps the X of clip utt_of[b].  Rows of one
+// clip re-read its X, so never the non-temporal form.
+template <int H>
+__global__ __launch_bounds__(256, 2) void xattn_map_kernel(XAttnParams p, const int* __restrict__ utt_of) {
+    constexpr bool NT = false;
+#define XATTN_UTT(slot) utt_of[slot]
+#include "xattn_sweep.inc"
+#undef XATTN_UTT
 }
 
 // Merge the chunk partials of one head (exactly attn_combine_kernel's weights) and apply Wv_h: out[row][h*64+e] =
@@ -2009,27 +1878,29 @@ int launch_xattn_absorb(const XAttnParams& p, hipStream_t st, bool late_loads) {
         hipLaunchKernelGGL(xattn_absorb_kernel<true>, grid, block, 0, st, p);
     return WM_LAUNCH_OK;
 }
-template <int H> static void launch_xattn_h(const XAttnParams& p, hipStream_t st) {
+template <int H> static void launch_xattn_h(const XAttnParams& p, hipStream_t st, const int* utt_of) {
     // X is re-read by every layer of the step (147 MB for 128 rows: inside the 256 MB Infinity Cache).  WM_XATTN_NT (developer
     // build): non-temporal loads for A/B.
     static const bool nt = wm_env("WM_XATTN_NT") != nullptr;
     const dim3 grid(p.nsplit, p.rows), block(256);
-    if (nt)
+    if (utt_of)  // n-best scoring: X by row map (rows of one clip re-read its X: never the non-temporal form)
+        hipLaunchKernelGGL((xattn_map_kernel<H>), grid, block, 0, st, p, utt_of);
+    else if (nt)
         hipLaunchKernelGGL((xattn_kernel<H, true>), grid, block, 0, st, p);
     else
         hipLaunchKernelGGL((xattn_kernel<H, false>), grid, block, 0, st, p);
 }
-int launch_xattn(const XAttnParams& p, hipStream_t st) {
+int launch_xattn(const XAttnParams& p, hipStream_t st, const int* utt_of) {
     if (const int rc = xattn_check(p)) return rc;
     switch (p.H) {
-        case 1: launch_xattn_h<1>(p, st); break;
-        case 2: launch_xattn_h<2>(p, st); break;
-        case 3: launch_xattn_h<3>(p, st); break;
-        case 4: launch_xattn_h<4>(p, st); break;
-        case 5: launch_xattn_h<5>(p, st); break;
-        case 6: launch_xattn_h<6>(p, st); break;
-        case 7: launch_xattn_h<7>(p, st); break;
-        default: launch_xattn_h<8>(p, st); break;
+        case 1: launch_xattn_h<1>(p, st, utt_of); break;
+        case 2: launch_xattn_h<2>(p, st, utt_of); break;
+        case 3: launch_xattn_h<3>(p, st, utt_of); break;
+        case 4: launch_xattn_h<4>(p, st, utt_of); break;
+        case 5: launch_xattn_h<5>(p, st, utt_of); break;
+        case 6: launch_xattn_h<6>(p, st, utt_of); break;
+        case 7: launch_xattn_h<7>(p, st, utt_of); break;
+        default: launch_xattn_h<8>(p, st, utt_of); break;
     }
     return WM_LAUNCH_OK;
 }

@@ -387,6 +387,35 @@ void launch_score_sums(const float* logprob, int stride, const int* len, const i
     hipLaunchKernelGGL(score_sums_kernel, dim3((B + 127) / 128), dim3(128), 0, st, logprob, stride, len, ctx, sum, avg, B);
 }
 
+// n-best scoring: one workgroup per clip.  Candidate c of the clip (key[row0 + c]) gets
+//   rank_c = #{j : key_j > key_c or (key_j == key_c and j < c)}   — a permutation of 0 .. n - 1, so order[row0 + rank_c] = c has no
+//   write conflict: no sort network, no atomics —
+//   posterior_c = expf(key_c - M) / Σ_j expf(key_j - M),  M = the clip's largest key, the sum in ascending j.
+// Every thread walks the clip's keys itself (n <= max_batch values, wave-uniform loads): no LDS, no barrier, and the same sum in
+// every thread, whatever the other clips of the launch hold.  Keys are finite or -inf below a finite maximum (log-prob sums); a NaN
+// key compares false everywhere, so NaN candidates would all take rank 0 and leave other order entries unwritten — every store
+// still lands inside the clip's rows, and wm_op_score_rank refuses such keys.
+__global__ __launch_bounds__(64) void score_rank_kernel(ScoreRankParams p) {
+    const int u = blockIdx.x, r0 = p.row0[u], n = p.n_cand[u];
+    const float* key = p.key + r0;
+    float M = key[0];
+    for (int j = 1; j < n; ++j) M = fmaxf(M, key[j]);
+    float S = 0.f;
+    for (int j = 0; j < n; ++j) S += expf(key[j] - M);
+    for (int c = threadIdx.x; c < n; c += blockDim.x) {
+        const float kc = key[c];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) {
+            const float kj = key[j];
+            rank += (kj > kc || (kj == kc && j < c)) ? 1 : 0;
+        }
+        p.order[r0 + rank] = c;
+        if (rank == 0) p.best[u] = c;
+        p.posterior[r0 + c] = expf(kc - M) / S;
+    }
+}
+void launch_score_rank(const ScoreRankParams& p, int U, hipStream_t st) { hipLaunchKernelGGL(score_rank_kernel, dim3(U), dim3(64), 0, st, p); }
+
 template <typename TW, int KD, bool SPLIT> static int score_run(const ScoreParams& q, hipStream_t st, hipEvent_t* ev) {
     using C = ScoreCfg<TW, KD, SPLIT>;
     hipLaunchKernelGGL((score_ln_kernel<TW, KD, SPLIT>), dim3((q.M + 31) / 32), dim3(256), 0, st, q.x, q.ln_g, q.ln_b, q.a, q.M);

@@ -1028,9 +1028,9 @@ int dec_linear_dispatch(int dt, const DecLinearParams& p, hipStream_t st) {
     DISPATCH_DT(dt, TT, rc = launch_dec_linear<TT>(p, st));
     return launch_rc(rc);
 }
-int attn_decode_dispatch(int dt, const AttnDecParams& p, hipStream_t st, const int* key_lo) {
+int attn_decode_dispatch(int dt, const AttnDecParams& p, hipStream_t st, const int* key_lo, const int* utt_of) {
     int rc = 0;
-    DISPATCH_DT(dt, TT, rc = launch_attn_decode<TT>(p, st, key_lo));
+    DISPATCH_DT(dt, TT, rc = launch_attn_decode<TT>(p, st, key_lo, utt_of));
     return launch_rc(rc);
 }
 
@@ -1073,10 +1073,12 @@ int cross_attn_merge(wm_model* m, wm_state* s, int l, const DecView& v, int P, v
 }
 
 int launch_cross_attn(wm_model* m, wm_state* s, int l, const DecView& v, int P) {
+    // an n-best score pass (single lane: v.b0 == 0): the row in slot b reads the X or K/V of clip utt_of[b]
+    const int* utt_of = s->nb.on ? s->nb.utt_of.as<int>() : nullptr;
     if (m->xattn) {
         const XAttnParams x = xattn_params(m, s, l, v, P);
         WMCHK(launch_rc(launch_xattn_absorb(x, v.st)));
-        return launch_rc(launch_xattn(x, v.st));
+        return launch_rc(launch_xattn(x, v.st, utt_of));
     }
     const wm_dims& c = m->cfg.dims;
     const size_t d = c.d_model, ks = dt_size(m->cfg.kv_dtype);
@@ -1105,7 +1107,7 @@ int launch_cross_attn(wm_model* m, wm_state* s, int l, const DecView& v, int P) 
     // static) = two per CU.  fp32 K/V (12 KB static): ONE per CU measured best with four 128-row passes in flight — pipelined ms per
     // 64-clip pass: pad 0 (four per CU) 28.2, 20 KB 28.4, 34 KB (three) 27.8, 42 / 50 / 60 KB (two) 27.3 / 27.5 / 27.4, 90 KB (one) 27.05
     a.lds_pad = s->shares_chip ? (m->cfg.kv_dtype == WM_F32 ? 90000 : 34 * 1024) : 0;
-    return attn_decode_dispatch(m->cfg.kv_dtype, a, v.st);
+    return attn_decode_dispatch(m->cfg.kv_dtype, a, v.st, nullptr, utt_of);
 }
 
 // What every linear launch of a decoder pass sets (ln_g null: no LayerNorm prologue); each block's special part is added by name below
@@ -1944,6 +1946,7 @@ int submit_on(wm_model* m, wm_state** slot, const PassAsk& ask) {
     const NsAsk& ns = ask.ns;
     const LangAsk& lang = ask.lang;
     const ScoreAsk* score = ask.score;
+    const int n_enc = score && score->n_utt > 0 ? score->n_utt : B;  // clips the encoder runs over: an n-best pass has fewer than rows
     if (score && (ask.mel2 || cols || rows || lp || ns.token >= 0 || lang.ids || dec_lanes_for(B) != 1))  // (refused by the entry points first)
         return fail(WM_E_ARG, "a score pass runs alone on a single-lane decode state");
     if (lang.ids && (ask.mel2 || cols || dec_lanes_for(B) != 1 || (!lang.only && !rows)))  // (refused by the entry points first)
@@ -1979,6 +1982,7 @@ int submit_on(wm_model* m, wm_state** slot, const PassAsk& ask) {
         for (int b = 0; b < B; ++b) s->lg.h_col[b] = rows ? rows->len[b] - lang.n_init + 1 : 0;
     }
     s->sc.on = false;
+    s->nb.on = false;  // the row-to-clip map of an n-best pass serves that pass alone
     s->sc.timed = s->sc.timed_al = false;
     s->rp.on = ask.rp.on() && !score && !lang.only;  // greedy passes only: score / align are teacher-forced, detection reads raw logits
     if (s->rp.on) {
@@ -2029,7 +2033,7 @@ int submit_on(wm_model* m, wm_state** slot, const PassAsk& ask) {
         HIPCHK(hipStreamWaitEvent(est, s->enc_done, 0));
     }
     const size_t mel_floats = (size_t)c.n_mels * 2 * c.n_audio_ctx;  // per utterance
-    const int B1 = pair ? B / 2 : B;
+    const int B1 = pair ? B / 2 : n_enc;
     const float* mel_dev = ask.mel;
     if (!ask.mel_on_device) {
         HIPCHK(hipMemcpyAsync(s->mel_dev.p, ask.mel, (size_t)B1 * mel_floats * 4, hipMemcpyHostToDevice, est));
@@ -2049,7 +2053,7 @@ int submit_on(wm_model* m, wm_state** slot, const PassAsk& ask) {
     }
     const auto tt0 = std::chrono::steady_clock::now();
     trace_mark(est, "state %p encoder start", (void*)s);
-    WMCHK(run_encoder(m, s, mel_dev, B, est, mel2_dev, B1, false));
+    WMCHK(run_encoder(m, s, mel_dev, pair ? B : n_enc, est, mel2_dev, B1, false));
     trace_mark(est, "state %p encoder end", (void*)s);
     s->enc_stream = est;
     s->has_enc = s->has_cross = true;
@@ -2159,7 +2163,7 @@ static void record_pass(wm_model* m, int slot, const PassAsk& a, wm_state* st, i
     r.st = st;
     r.row0 = row0;
     r.rows = rows;
-    r.kind = !a.score ? PassKind::transcribe : a.score->cols ? PassKind::align : PassKind::score;
+    r.kind = !a.score ? PassKind::transcribe : a.score->cols ? PassKind::align : a.score->n_utt > 0 ? PassKind::nbest : PassKind::score;
     r.total = a.score ? a.score->stride : a.opts->n_prompt + 1 + a.opts->max_loop;
     r.tt = a.cols != nullptr;
     r.lp = a.score ? a.score->lp : a.lp;
@@ -2318,6 +2322,7 @@ int collect_slot(wm_model* m, int slot, PassKind kind, const PassOut& out) {
     if (!r.pending) return fail(WM_E_STATE, "nothing was submitted on this slot");
     if (r.kind != kind) {
         if (r.kind == PassKind::score) return fail(WM_E_STATE, "this slot holds a score pass (collect it with wm_score_wait)");
+        if (r.kind == PassKind::nbest) return fail(WM_E_STATE, "this slot holds an n-best score pass (collect it with wm_score_nbest_wait)");
         if (r.kind == PassKind::align) return fail(WM_E_STATE, "this slot holds an align pass (collect it with wm_align_wait)");
         return fail(WM_E_STATE, "this slot holds a transcribe pass (collect it with wm_transcribe_wait)");
     }

@@ -179,7 +179,7 @@ struct VocabHead {
 int gemm_dispatch(int dt_in, int dt_out, const wm::GemmParams& p, int batch, hipStream_t st);
 int ln_then_gemm(int dt_in, int dt_out, wm::GemmParams p, const float* x, const float* g, const float* b, hipStream_t st);
 int dec_linear_dispatch(int dt, const wm::DecLinearParams& p, hipStream_t st);
-int attn_decode_dispatch(int dt, const wm::AttnDecParams& p, hipStream_t st, const int* key_lo = nullptr);
+int attn_decode_dispatch(int dt, const wm::AttnDecParams& p, hipStream_t st, const int* key_lo = nullptr, const int* utt_of = nullptr);
 wm::DecLinearParams linear_block(const float* x, const float* ln_g, const float* ln_b, const void* W, const float* bias, int N, int K, int B,
                                  float* out, int ldo);
 int ns_sweep(int T, const float* x, const VocabHead& h, int B, int npart, float* pmax, int* pidx, float* psum, int token, float* prob, float* lse,

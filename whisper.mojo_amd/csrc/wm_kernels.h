@@ -294,7 +294,9 @@ struct AttnDecParams {
 };
 // key_lo non-null (per-row prompts; single-workgroup self-attention forms only): [utterances], utterance u sweeps the keys
 // [key_lo[u], len + 1 (+ t)) — a separate kernel; with key_lo null exactly the launch it always was
-template <typename TKV> int launch_attn_decode(const AttnDecParams& p, hipStream_t st, const int* key_lo = nullptr);  // WM_LAUNCH_*
+// utt_of non-null (n-best scoring; chunked cross-attention forms only): [q_B, or B when q_B == 0] device ints, the row in
+// batch slot b reads the K/V of utterance utt_of[b] — separate kernels likewise
+template <typename TKV> int launch_attn_decode(const AttnDecParams& p, hipStream_t st, const int* key_lo = nullptr, const int* utt_of = nullptr);  // WM_LAUNCH_*
 void launch_attn_combine(const float* part_o, const float* part_ml, void* out, int out_dtype, int B, int nsplit, int H, int d,
                          hipStream_t st, long long* ts = nullptr, int ts_id = 0);
 
@@ -320,7 +322,7 @@ struct XAttnParams {
 };
 // late_loads: the absorb loop that requests its Wk rows after the q staging, as it was; same images bit for bit (op tests, A/B)
 int launch_xattn_absorb(const XAttnParams& p, hipStream_t st, bool late_loads = false);  // WM_LAUNCH_*
-int launch_xattn(const XAttnParams& p, hipStream_t st);
+int launch_xattn(const XAttnParams& p, hipStream_t st, const int* utt_of = nullptr);  // utt_of: as launch_attn_decode's, X of utt_of[slot]
 int launch_xattn_merge(const XAttnParams& p, hipStream_t st);
 
 void launch_dec_embed(const float* tok_emb, const float* pos_emb, const int* tok, const int* pos, float* x, int B, int d,
@@ -554,6 +556,17 @@ template <typename TW> int launch_score(const ScoreParams& p, hipStream_t st, hi
 // rows[r] -> out[dst[r]] for the n_rows rows of a prefill chunk whose dst[r] >= 0 (d floats each)
 void launch_score_collect(const float* rows, float* out, const int* dst, int n_rows, int d, hipStream_t st);
 void launch_score_sums(const float* logprob, int stride, const int* len, const int* ctx, float* sum, float* avg, int B, hipStream_t st);
+// n-best scoring: per clip u the candidates row0[u] .. row0[u] + n_cand[u] of key [R] are ranked (descending, equal keys
+// lower index first) and turned into a posterior, one workgroup per clip.  order / posterior [R], best [U].
+struct ScoreRankParams {
+    const float* key;  // [R]
+    const int* row0;   // [U]
+    const int* n_cand;  // [U]
+    int* order;
+    int* best;
+    float* posterior;
+};
+void launch_score_rank(const ScoreRankParams& p, int U, hipStream_t st);
 // rows of the gather buffer of SURVEY §8e: dst[r] = [n_tokens[r], ids of row r zero-padded to `stride`] for r < rows; rows in
 // [rows, rows_cap) are zeroed (ragged shards gather a fixed row count per rank)
 void launch_pack_tokens(const int* out_tokens, const int* n_tokens, int out_stride, int rows, int rows_cap, int stride, int* dst, hipStream_t st);

@@ -385,7 +385,8 @@ extern "C" int wm_op_attention(float* out, const float* q, const float* k, const
 }
 
 static int op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
-                               int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo, bool with_lo);
+                               int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo, bool with_lo,
+                               const int32_t* utt_of = nullptr, int n_map_utt = 0);
 extern "C" int wm_op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
                                       int n_chunks, int out_dtype, int q_B, int len, int nq) {
     return op_attention_cached(out, q, k, v, B, t, n_heads, kv_dtype, n_chunks, out_dtype, q_B, len, nq, nullptr, false);
@@ -394,8 +395,16 @@ extern "C" int wm_op_attention_cached_lo(float* out, const float* q, const float
                                          int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo) {
     return op_attention_cached(out, q, k, v, B, t, n_heads, kv_dtype, n_chunks, out_dtype, q_B, len, nq, key_lo, true);
 }
+// The chunked cross-attention forms with K/V by row map: k, v hold n_utt clips of t rows, the row in batch slot b (of q_B
+// slots, or of B when q_B == 0) reads clip utt_of[b].
+extern "C" int wm_op_attention_cached_map(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
+                                          int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* utt_of, int n_utt) {
+    if (!utt_of || n_utt < 1 || n_chunks < 2) return fail(WM_E_ARG, "the map belongs to the chunked forms (n_chunks >= 2) and needs n_utt >= 1 clips");
+    return op_attention_cached(out, q, k, v, B, t, n_heads, kv_dtype, n_chunks, out_dtype, q_B, len, nq, nullptr, false, utt_of, n_utt);
+}
 static int op_attention_cached(float* out, const float* q, const float* k, const float* v, int B, int t, int n_heads, int kv_dtype,
-                               int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo, bool with_lo) {
+                               int n_chunks, int out_dtype, int q_B, int len, int nq, const int32_t* key_lo, bool with_lo,
+                               const int32_t* utt_of, int n_map_utt) {
     if (with_lo && (!key_lo || n_chunks != 1 || nq != 0)) return fail(WM_E_ARG, "key_lo belongs to the single-workgroup forms (n_chunks = 1, nq = 0)");
     if (!out || !q || !k || !v || B <= 0 || t <= 0 || n_heads <= 0 || n_heads > 16) return fail(WM_E_ARG, "bad argument");
     if (kv_dtype < 0 || kv_dtype > 2 || out_dtype < 0 || out_dtype > 2) return fail(WM_E_ARG, "bad dtype");
@@ -406,13 +415,20 @@ static int op_attention_cached(float* out, const float* q, const float* k, const
     if (q_B < 0 || (q_B > 0 && B % q_B)) return fail(WM_E_ARG, "prefill rows are position-major: B must be P * q_B");
     if (nq != 0 && (nq != 4 || n_chunks == 1 || q_B == 0 || B != 4 * q_B))
         return fail(WM_E_ARG, "nq must be 0, or 4 with the chunked form and B = 4 * q_B rows");
-    const int P = q_B > 0 ? B / q_B : 1, n_utt = q_B > 0 ? q_B : B;  // k, v hold n_utt utterances of t rows
+    const int P = q_B > 0 ? B / q_B : 1, n_slots = q_B > 0 ? q_B : B;
+    const int n_utt = utt_of ? n_map_utt : n_slots;  // k, v hold n_utt utterances of t rows
     if (n_chunks > 1 && len >= 0) return fail(WM_E_ARG, "len belongs to the single-workgroup form (the chunked form sweeps all t rows)");
     if (n_chunks == 1 && len < 0 && P > 1) return fail(WM_E_ARG, "the causal prefill form needs len >= 0");
     if (n_chunks == 1 && len >= 0 && len + P > t) return fail(WM_E_ARG, "the cache must hold len + P rows");
     const size_t d = (size_t)n_heads * 64, n = (size_t)B * d;
     TmpDev tmp;
     DevBuf &dq = tmp.add(), &dk = tmp.add(), &dv = tmp.add(), &po = tmp.add(), &pml = tmp.add(), &o = tmp.add(), &ctl = tmp.add(), &dlo = tmp.add();
+    DevBuf& dmap = tmp.add();
+    if (utt_of) {
+        for (int b = 0; b < n_slots; ++b)
+            if (utt_of[b] < 0 || utt_of[b] >= n_utt) return fail(WM_E_ARG, "utt_of[%d] = %d outside [0, %d)", b, utt_of[b], n_utt);
+        WMCHK(upload_bytes(dmap, utt_of, (size_t)n_slots * 4));
+    }
     if (with_lo) {
         for (int u = 0; u < n_utt; ++u)
             if (key_lo[u] < 0 || key_lo[u] > t) return fail(WM_E_ARG, "key_lo[%d] = %d outside [0, %d]", u, key_lo[u], t);
@@ -440,7 +456,7 @@ static int op_attention_cached(float* out, const float* q, const float* k, const
         a.nsplit = n_chunks;
         a.part_o = po.as<float>();
         a.part_ml = pml.as<float>();
-        WMCHK(attn_decode_dispatch(kv_dtype, a, nullptr));
+        WMCHK(attn_decode_dispatch(kv_dtype, a, nullptr, nullptr, utt_of ? dmap.as<int>() : nullptr));
         launch_attn_combine(po.as<float>(), pml.as<float>(), o.p, out_dtype, B, n_chunks, n_heads, (int)d, nullptr);
     } else {
         StepCtl h{};
@@ -1053,12 +1069,28 @@ extern "C" int wm_op_lang_detect(int32_t* lang_out, float* probs, const float* x
 }
 
 // The absorbed cross-attention of m->xattn models, wired as launch_cross_attn + cross_attn_merge wire it: absorb, X sweep, merge.
+static int op_xattn(float* out, const float* q, const float* Wk, const float* Wv, const float* bv, const float* X, int rows, int q_B, int n_utt,
+                    int n_keys, int n_heads, int nsplit, int out_dtype, const int32_t* utt_of);
 extern "C" int wm_op_xattn(float* out, const float* q, const float* Wk, const float* Wv, const float* bv, const float* X, int rows,
                            int q_B, int n_utt, int n_keys, int n_heads, int nsplit, int out_dtype) {
+    return op_xattn(out, q, Wk, Wv, bv, X, rows, q_B, n_utt, n_keys, n_heads, nsplit, out_dtype, nullptr);
+}
+// X by row map: X holds n_utt clips, the row in batch slot b (of q_B slots, or of `rows` when q_B == 0) sweeps clip utt_of[b]
+extern "C" int wm_op_xattn_map(float* out, const float* q, const float* Wk, const float* Wv, const float* bv, const float* X, int rows,
+                               int q_B, int n_utt, int n_keys, int n_heads, int nsplit, int out_dtype, const int32_t* utt_of) {
+    if (!utt_of) return fail(WM_E_ARG, "bad argument");
+    return op_xattn(out, q, Wk, Wv, bv, X, rows, q_B, n_utt, n_keys, n_heads, nsplit, out_dtype, utt_of);
+}
+static int op_xattn(float* out, const float* q, const float* Wk, const float* Wv, const float* bv, const float* X, int rows, int q_B, int n_utt,
+                    int n_keys, int n_heads, int nsplit, int out_dtype, const int32_t* utt_of) {
     if (!out || !q || !Wk || !Wv || !bv || !X || rows <= 0 || n_utt <= 0 || n_keys <= 0) return fail(WM_E_ARG, "bad argument");
     if (n_heads < 1 || n_heads > 8 || nsplit < 1 || nsplit > 64) return fail(WM_E_ARG, "needs 1 <= n_heads <= 8, 1 <= nsplit <= 64");
     if (out_dtype != WM_F32 && out_dtype != WM_BF16) return fail(WM_E_ARG, "out_dtype must be WM_F32 or WM_BF16");
-    if (q_B < 0 || (q_B > 0 ? (q_B > n_utt || rows % q_B) : rows > n_utt))
+    if (utt_of) {  // any number of rows per clip: the map alone says which
+        if (q_B < 0 || (q_B > 0 && rows % q_B)) return fail(WM_E_ARG, "rows must be P * q_B (prefill)");
+        for (int b = 0, n = q_B > 0 ? q_B : rows; b < n; ++b)
+            if (utt_of[b] < 0 || utt_of[b] >= n_utt) return fail(WM_E_ARG, "utt_of[%d] = %d outside [0, %d)", b, utt_of[b], n_utt);
+    } else if (q_B < 0 || (q_B > 0 ? (q_B > n_utt || rows % q_B) : rows > n_utt))
         return fail(WM_E_ARG, "rows must be P * q_B with q_B <= n_utt (prefill), or <= n_utt (q_B == 0)");
     const size_t d = (size_t)n_heads * 64;
     TmpDev t;
@@ -1074,6 +1106,8 @@ extern "C" int wm_op_xattn(float* out, const float* q, const float* Wk, const fl
     WMCHK(py.alloc((size_t)rows * nsplit * n_heads * d * 4, true));
     WMCHK(pml.alloc((size_t)rows * nsplit * n_heads * 2 * 4, true));
     WMCHK(o.alloc((size_t)rows * d * dt_size(out_dtype), true));
+    DevBuf& dmap = t.add();
+    if (utt_of) WMCHK(upload_bytes(dmap, utt_of, (size_t)(q_B > 0 ? q_B : rows) * 4));
     XAttnParams x{};
     x.q = dq.as<float>();
     x.Wk = wk.p;
@@ -1094,7 +1128,7 @@ extern "C" int wm_op_xattn(float* out, const float* q, const float* Wk, const fl
     x.out = o.p;
     x.out_dtype = out_dtype;
     LCHK(launch_xattn_absorb(x, st));
-    LCHK(launch_xattn(x, st));
+    LCHK(launch_xattn(x, st, utt_of ? dmap.as<int>() : nullptr));
     LCHK(launch_xattn_merge(x, st));
     HIPCHK(hipGetLastError());
     return download_f32(out, o, (size_t)rows * d, out_dtype);

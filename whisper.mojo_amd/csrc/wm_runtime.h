@@ -50,6 +50,11 @@ struct ScoreAsk {  // a score pass, already validated by score_che
     // an align pass: cols non-null = the columns kept per row (align_cols); lp = the vocabulary side runs too
     const std::vector<int32_t>* cols = nullptr;
     bool lp = true;
+    // an n-best pass: n_utt > 0 = the rows are the candidates of n_utt clips, n_cand[u] consecutive rows each; the mel
+    // holds n_utt clips.  normalize: rank by avg_logprob instead of sum_logprob
+    int n_utt = 0;
+    const int32_t* n_cand = nullptr;  // host [n_utt]
+    bool normalize = false;
 };
 struct WinAsk {  // the windows a long-form timestamp pass decodes
     const int32_t* items;  // device [B][3]: (utterance, seek, frames) per row
@@ -102,9 +107,11 @@ struct PassOut {  // where a pass's results go: the caller's buffers, null = not
     float* dev_times = nullptr;  // with dev_packed, a pass with token timestamps: its times stay on the device too, [rows_cap][pack_stride]
     int32_t* top_ids = nullptr;  // score / align passes
     float* sum_logprob = nullptr;
+    int32_t *order = nullptr, *best = nullptr;  // an n-best score pass: [rows], [clips], [rows]
+    float* posterior = nullptr;
     double* win_times = nullptr;  // a window pass (PassAsk::win): [B][max_loop + 1] times of the generated ids, offset included
 };
-enum class PassKind { transcribe, score, align };  // which wait family collects a slot's pass
+enum class PassKind { transcribe, score, align, nbest };  // which wait family collects a slot's pass
 
 struct wm_model {
     wm_config cfg;
@@ -380,6 +387,15 @@ struct wm_state {
         bool timed = false;  // a completed pass's marks are all recorded
         bool timed_al = false;  // ... and it was an align pass: ev[6] too
     } sc;
+    // n-best scoring (on = the pending pass is an n-best score pass): utt_of [B] = the clip each row's cross-attention
+    // reads, row0 / n_cand [U] = each clip's rows, and the ranking's results.  Allocated by the first n-best pass of the state, never
+    // in state_new; every pass clears `on` before it reads anything.
+    struct Nbest {
+        bool on = false;
+        int U = 0;
+        DevBuf utt_of, row0, n_cand, order, best, post;
+        std::vector<int32_t> h_utt_of, h_row0, h_n_cand;
+    } nb;
 };
 
 // A view of `nb` utterances starting at b0, decoding on stream st under control block ctl.

@@ -1,5 +1,5 @@
 // wm_score.cpp — transcript scoring and forced alignment: the teacher-forced pass, its collection, the
-// wm_score* and wm_align* entries, and wm_op_score_logits.
+// wm_score*, wm_score_nbest*  and wm_align* entries, and wm_op_score_logits / wm_op_score_rank.
 #include "wm_runtime.h"
 
 // ---- transcript scoring --------------------------------------------------------------------------------------------
@@ -96,6 +96,21 @@ int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
         for (DevBuf* p : {&sc.len, &sc.ctx, &sc.sum, &sc.avg}) WMCHK(grow(*p, (size_t)B * 4));
         for (DevBuf* p : {&sc.lp, &sc.top}) WMCHK(grow(*p, (size_t)B * a.stride * 4));
     }
+    // an n-best pass: row r's cross-attention reads clip utt_of[r]; the ranking runs per clip over rows row0 .. + n_cand
+    wm_state::Nbest& nb = s->nb;
+    const bool nbest = a.n_utt > 0;
+    if (nbest) {
+        nb.U = a.n_utt;
+        nb.h_n_cand.assign(a.n_cand, a.n_cand + a.n_utt);
+        nb.h_row0.assign(a.n_utt, 0);
+        nb.h_utt_of.assign(B, 0);
+        for (int u = 0, r = 0; u < a.n_utt; ++u) {
+            nb.h_row0[u] = r;
+            for (int k = 0; k < a.n_cand[u]; ++k) nb.h_utt_of[r++] = u;
+        }
+        for (DevBuf* p : {&nb.utt_of, &nb.order, &nb.post}) WMCHK(grow(*p, (size_t)B * 4));
+        for (DevBuf* p : {&nb.row0, &nb.n_cand, &nb.best}) WMCHK(grow(*p, (size_t)a.n_utt * 4));
+    }
     al.on = al.ragged = align;
     al.win = false;
     if (align) {  // the buffers of a timestamp pass, sized by the longest row of THIS pass
@@ -113,6 +128,7 @@ int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
     s->rw.on = true;  // the prefill's self-attention sweeps each row's own key window
     s->rw.Lmax = Lmax;
     sc.on = true;
+    nb.on = nbest;
     const wm_state::Lane& ln = s->lanes[0];
     const DecView v{ln.b0, ln.nb, ln.st, ln.ctl};
     HIPCHK(hipEventRecord(s->enc_done, s->enc_stream ? s->enc_stream : m->stream));
@@ -129,6 +145,11 @@ int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
         HIPCHK(up(sc.ctx, sc.h_ctx));
         HIPCHK(hipMemsetAsync(sc.lp.p, 0, (size_t)B * a.stride * 4, v.st));     // logprob[b][0] and the tails: 0
         HIPCHK(hipMemsetAsync(sc.top.p, 0xff, (size_t)B * a.stride * 4, v.st));  // top_id[b][0] and the tails: -1
+    }
+    if (nbest) {
+        HIPCHK(up(nb.utt_of, nb.h_utt_of));
+        HIPCHK(up(nb.row0, nb.h_row0));
+        HIPCHK(up(nb.n_cand, nb.h_n_cand));
     }
     if (align) {  // (the host vectors outlive the copies: the state is not reused before this pass is waited for)
         HIPCHK(up(al.map, al.h_map));
@@ -175,6 +196,9 @@ int score_pass(wm_model* m, wm_state* s, const ScoreAsk& a) {
     DISPATCH_DT(T, TT, lrc = launch_score<TT>(q, v.st, sc.ev + 3));
     LCHK(lrc);
     launch_score_sums(sc.lp.as<float>(), a.stride, sc.len.as<int>(), sc.ctx.as<int>(), sc.sum.as<float>(), sc.avg.as<float>(), B, v.st);
+    if (nbest)  // ranking and posterior per clip, behind the sums on the same stream
+        launch_score_rank(ScoreRankParams{a.normalize ? sc.avg.as<float>() : sc.sum.as<float>(), nb.row0.as<int>(), nb.n_cand.as<int>(),
+                                          nb.order.as<int>(), nb.best.as<int>(), nb.post.as<float>()}, nb.U, v.st);
     HIPCHK(hipEventRecord(sc.ev[5], v.st));
     }
     if (align) {  // the align chain on the lane's stream, before the pass's completion event
@@ -198,6 +222,8 @@ int score_collect(wm_model* m, wm_state* s, const PassOut& out) {
     s->sc.on = false;
     s->rw.on = false;
     s->al.on = false;
+    const bool nbest = s->nb.on;
+    s->nb.on = false;
     HIPCHK(e);
     s->sc.timed = true;
     s->sc.timed_al = align;
@@ -208,6 +234,11 @@ int score_collect(wm_model* m, wm_state* s, const PassOut& out) {
     if (out.top_ids) HIPCHK(hipMemcpy(out.top_ids, s->sc.top.p, n, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out.sum_logprob, s->sc.sum.p, (size_t)s->B * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out.avg_logprob, s->sc.avg.p, (size_t)s->B * 4, hipMemcpyDeviceToHost));
+    if (nbest && out.order) {  // (the n-best entries ask for the three together)
+        HIPCHK(hipMemcpy(out.order, s->nb.order.p, (size_t)s->B * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out.best, s->nb.best.p, (size_t)s->nb.U * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out.posterior, s->nb.post.p, (size_t)s->B * 4, hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 // the request and the outputs of a checked score / align call (a: the caller's ScoreAsk, alive for the call)
@@ -251,6 +282,103 @@ extern "C" int wm_score_pcm(wm_model* m, const float* pcm, const int32_t* n_samp
     WMCHK(frontend_run(m, pcm, n_samples, B, stride));  // same stream order as the encoder: no host sync
     const ScoreAsk a{ids, ids_len, context_len, ids_stride, pos_mode};
     return run_now(m, score_ask(m->fe.mel.as<float>(), 1, B, a), score_out(nullptr, token_logprobs, top_ids, sum_logprob, avg_logprob));
+}
+
+// ---- n-best scoring -------------------------------------------------------------------------------------------------
+// U clips, n_cand[u] candidate rows each (R rows in all, grouped by clip): the encoder and the cross-K/V projection run over the U
+// clips, the decoder over the R rows, each row's cross-attention reading its clip's X or K/V by row map; per row exactly what wm_score
+// gives with the clip's mel repeated, per clip a ranking and a posterior made on the device.  Everything is refused before anything is
+// launched; *R_out = Σ n_cand.
+static int nbest_check(wm_model* m, int U, const int32_t* n_cand, int pos_mode, const int32_t* ids, const int32_t* ids_len, int ids_stride,
+                       const int32_t* context_len, int* R_out) {
+    if (!m || !n_cand || U < 1) return fail(WM_E_ARG, "bad argument (U >= 1 clips, n_cand[U])");
+    long R = 0;
+    for (int u = 0; u < U; ++u) {
+        if (n_cand[u] < 1) return fail(WM_E_ARG, "n_cand[%d] = %d: every clip needs at least one candidate", u, n_cand[u]);
+        R += n_cand[u];
+        if (R > m->cfg.max_batch) return fail(WM_E_ARG, "%d clips hold more than max_batch %d candidates", U, m->cfg.max_batch);
+    }
+    WMCHK(score_check(m, (int)R, pos_mode, ids, ids_len, ids_stride, context_len));
+    *R_out = (int)R;
+    return 0;
+}
+static ScoreAsk nbest_ask(int U, const int32_t* n_cand, int normalize, int pos_mode, const int32_t* ids, const int32_t* ids_len, int ids_stride,
+                          const int32_t* context_len) {
+    ScoreAsk a{ids, ids_len, context_len, ids_stride, pos_mode};
+    a.n_utt = U;
+    a.n_cand = n_cand;
+    a.normalize = normalize != 0;
+    return a;
+}
+static PassOut nbest_out(float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob, int32_t* order, int32_t* best,
+                         float* posterior) {
+    PassOut out = score_out(nullptr, token_logprobs, top_ids, sum_logprob, avg_logprob);
+    out.order = order;
+    out.best = best;
+    out.posterior = posterior;
+    return out;
+}
+extern "C" int wm_score_nbest(wm_model* m, const float* mel, int mel_on_device, int U, const int32_t* n_cand, int normalize, int pos_mode,
+                              const int32_t* ids, const int32_t* ids_len, int ids_stride, const int32_t* context_len, float* token_logprobs,
+                              int32_t* top_ids, float* sum_logprob, float* avg_logprob, int32_t* order, int32_t* best, float* posterior) {
+    if (!m || !mel || !token_logprobs || !sum_logprob || !avg_logprob || !order || !best || !posterior) return fail(WM_E_ARG, "bad argument");
+    int R = 0;
+    WMCHK(nbest_check(m, U, n_cand, pos_mode, ids, ids_len, ids_stride, context_len, &R));
+    const ScoreAsk a = nbest_ask(U, n_cand, normalize, pos_mode, ids, ids_len, ids_stride, context_len);
+    return run_now(m, score_ask(mel, mel_on_device, R, a), nbest_out(token_logprobs, top_ids, sum_logprob, avg_logprob, order, best, posterior));
+}
+extern "C" int wm_score_nbest_submit(wm_model* m, int slot, const float* mel, int mel_on_device, int U, const int32_t* n_cand, int normalize,
+                                     int pos_mode, const int32_t* ids, const int32_t* ids_len, int ids_stride, const int32_t* context_len) {
+    if (!m || !mel || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument (slot must be 0..7)");
+    int R = 0;
+    WMCHK(nbest_check(m, U, n_cand, pos_mode, ids, ids_len, ids_stride, context_len, &R));
+    const ScoreAsk a = nbest_ask(U, n_cand, normalize, pos_mode, ids, ids_len, ids_stride, context_len);
+    return submit_slot(m, slot, score_ask(mel, mel_on_device, R, a));
+}
+extern "C" int wm_score_nbest_wait(wm_model* m, int slot, float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob,
+                                   int32_t* order, int32_t* best, float* posterior) {
+    if (!m || !token_logprobs || !sum_logprob || !avg_logprob || !order || !best || !posterior || slot < 0 || slot >= wm_model::NSLOT)
+        return fail(WM_E_ARG, "bad argument");
+    return collect_slot(m, slot, PassKind::nbest, nbest_out(token_logprobs, top_ids, sum_logprob, avg_logprob, order, best, posterior));
+}
+extern "C" int wm_score_nbest_pcm(wm_model* m, const float* pcm, const int32_t* n_samples, int U, int stride, const int32_t* n_cand,
+                                  int normalize, int pos_mode, const int32_t* ids, const int32_t* ids_len, int ids_stride,
+                                  const int32_t* context_len, float* token_logprobs, int32_t* top_ids, float* sum_logprob, float* avg_logprob,
+                                  int32_t* order, int32_t* best, float* posterior) {
+    if (!m || !token_logprobs || !sum_logprob || !avg_logprob || !order || !best || !posterior) return fail(WM_E_ARG, "bad argument");
+    int R = 0;
+    WMCHK(nbest_check(m, U, n_cand, pos_mode, ids, ids_len, ids_stride, context_len, &R));
+    WMCHK(frontend_run(m, pcm, n_samples, U, stride));  // same stream order as the encoder: no host sync
+    const ScoreAsk a = nbest_ask(U, n_cand, normalize, pos_mode, ids, ids_len, ids_stride, context_len);
+    return run_now(m, score_ask(m->fe.mel.as<float>(), 1, R, a),
+                   nbest_out(token_logprobs, top_ids, sum_logprob, avg_logprob, order, best, posterior));
+}
+// The ranking launch alone on host keys: known-answer tests.
+extern "C" int wm_op_score_rank(int32_t* order, int32_t* best, float* posterior, const float* key, const int32_t* n_cand, int U) {
+    if (!order || !best || !posterior || !key || !n_cand || U < 1) return fail(WM_E_ARG, "bad argument");
+    std::vector<int32_t> row0(U);
+    long R = 0;
+    for (int u = 0; u < U; ++u) {
+        if (n_cand[u] < 1) return fail(WM_E_ARG, "n_cand[%d] = %d: every clip needs at least one candidate", u, n_cand[u]);
+        row0[u] = (int32_t)R;
+        R += n_cand[u];
+        if (R > (1 << 20)) return fail(WM_E_ARG, "more than 2^20 candidates");
+    }
+    for (long r = 0; r < R; ++r)
+        if (!std::isfinite(key[r])) return fail(WM_E_ARG, "key[%ld] is not finite (the counting rank needs comparable keys)", r);
+    TmpDev t;
+    DevBuf &dk = t.add(), &d0 = t.add(), &dn = t.add(), &dor = t.add(), &db = t.add(), &dp = t.add();
+    WMCHK(upload_bytes(dk, key, (size_t)R * 4));
+    WMCHK(upload_bytes(d0, row0.data(), (size_t)U * 4));
+    WMCHK(upload_bytes(dn, n_cand, (size_t)U * 4));
+    for (DevBuf* p : {&dor, &dp}) WMCHK(p->alloc((size_t)R * 4, true));
+    WMCHK(db.alloc((size_t)U * 4, true));
+    launch_score_rank(ScoreRankParams{dk.as<float>(), d0.as<int>(), dn.as<int>(), dor.as<int>(), db.as<int>(), dp.as<float>()}, U, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(order, dor.p, (size_t)R * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(best, db.p, (size_t)U * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(posterior, dp.p, (size_t)R * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 extern "C" int wm_score_phases(wm_model* m, int slot, float* ms) {
     if (!m || !ms || slot < 0 || slot >= wm_model::NSLOT) return fail(WM_E_ARG, "bad argument");

@@ -134,6 +134,27 @@ def score_audio(model, audios: Sequence[np.ndarray], ids, context_len=None, retu
     return model._score_out(tab, lens, lps, top, sm, avg, return_top_ids)
 
 
+def score_audio_candidates(model, audios: Sequence[np.ndarray], candidates, context_len=None, normalize: bool = False,
+                           return_top_ids: bool = False, sampling_rate: int = SAMPLING_RATE):
+    """PCM in, Whisper.score_candidates out (wm_score_nbest_pcm: the mel never leaves the GPU).  Arguments and result as
+    Whisper.score_candidates.  sampling_rate / np.int16 rows: resampled on the GPU first (resample)."""
+    audios = _at_16k(model, audios, sampling_rate)
+    buf, n, stride = _pack(audios)
+    U = len(audios)
+    args = _lib.nbest_args(candidates, context_len, U, model.config.vocab_size, model.config.n_text_ctx, model.max_batch)
+    tab, lens, ctx, n_cand = args[:4]
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    bufs = model._nbest_bufs(tab, U)
+    lps, top, sm, avg, order, best, post = bufs
+    _lib.check(_lib.lib().wm_score_nbest_pcm(model._h, buf.ctypes.data_as(fp), n.ctypes.data_as(ip), U, stride, n_cand.ctypes.data_as(ip),
+                                             int(bool(normalize)), model.pos_mode, tab.ctypes.data_as(ip), lens.ctypes.data_as(ip),
+                                             tab.shape[1], ctx.ctypes.data_as(ip), lps.ctypes.data_as(fp),
+                                             top.ctypes.data_as(ip) if return_top_ids else None, sm.ctypes.data_as(fp),
+                                             avg.ctypes.data_as(fp), order.ctypes.data_as(ip), best.ctypes.data_as(ip),
+                                             post.ctypes.data_as(fp)))
+    return model._nbest_out(args, bufs, return_top_ids)
+
+
 def align_audio(model, audios: Sequence[np.ndarray], ids, context_len=None, return_logprobs: bool = False,
                 sampling_rate: int = SAMPLING_RATE):
     """PCM in, Whisper.align out (wm_align_pcm: the mel never leaves the GPU; n_frames from the clip lengths, as

@@ -152,6 +152,7 @@ class Whisper:
         self._n_align = 0  # alignment heads set on the loaded model (set_alignment_heads)
         self._sb_key = None  # the lists of the sequence-bias table set on the loaded model (_set_repeat); None = no table
         self._ct_key = None  # the phrases of the constraint table set on the loaded model, likewise
+        self._nbest_pending = {}  # slot -> (arguments, mel keep-alive) of a submitted n-best score pass (score_candidates_submit / _wait)
         self._score_pending = {}  # slot -> (id table, lengths, mel keep-alive) of a submitted score pass (score_submit / score_wait)
         self._align_pending = {}  # slot -> (id table, lengths, context lengths, logprobs asked, keep-alives) of a submitted align pass
         self.encoder = WhisperEncoder(self)
@@ -192,6 +193,7 @@ class Whisper:
             self._caches.clear()
             self._pending = {}
             self._score_pending = {}
+            self._nbest_pending = {}
             self._align_pending = {}
             _lib.lib().wm_model_free(h)  # also frees every state (KVCache arena, pipeline slot) created on it
 
@@ -803,6 +805,71 @@ class Whisper:
         _lib.check(_lib.lib().wm_score_wait(self._h, slot, _fp(lps), _ip(top) if return_top_ids else None, _fp(sm), _fp(avg)))
         del pend[slot]  # only a collected pass leaves the table
         return self._score_out(tab, lens, lps, top, sm, avg, return_top_ids)
+
+    # ---- n-best scoring -----------------------------------------------------------------------------------------
+    def _nbest_args(self, mel, candidates, context_len):
+        ptr, on_dev, U, keep = _mel_arg(mel, self.config)
+        args = _lib.nbest_args(candidates, context_len, U, self.config.vocab_size, self.config.n_text_ctx, self.max_batch)
+        if self._h is None:
+            raise _lib.WhisperMiError("model not loaded")
+        return ptr, on_dev, U, keep, args
+
+    @staticmethod
+    def _nbest_bufs(tab, U):
+        R = tab.shape[0]
+        return (np.zeros(tab.shape, np.float32), np.full(tab.shape, -1, np.int32), np.zeros(R, np.float32), np.zeros(R, np.float32),
+                np.full(R, -1, np.int32), np.full(U, -1, np.int32), np.zeros(R, np.float32))
+
+    def _nbest_out(self, args, bufs, return_top_ids):
+        tab, lens, _ctx, n_cand, _utt_of, row0 = args
+        lps, top, sm, avg, order, best, post = bufs
+        out = []
+        for u, (r0, n) in enumerate(zip(row0.tolist(), n_cand.tolist())):
+            d = dict(token_logprobs=[lps[r, :lens[r]].tolist() for r in range(r0, r0 + n)], sum_logprob=sm[r0:r0 + n].copy(),
+                     avg_logprob=avg[r0:r0 + n].copy(), order=order[r0:r0 + n].tolist(), best=int(best[u]), posterior=post[r0:r0 + n].copy())
+            if return_top_ids:
+                d["top_ids"] = [top[r, :lens[r]].tolist() for r in range(r0, r0 + n)]
+            out.append(d)
+        return out
+
+    def score_candidates(self, mel, candidates, context_len=None, normalize: bool = False, return_top_ids: bool = False):
+        """Several candidate transcripts per clip on one encoder run (wm_score_nbest): mel [U, n_mels, frames]; candidates: per clip
+        a list of id lists, each as a row of score(); context_len: None (= 1), a number, one per candidate row (flat, clip by clip) or
+        per clip a list.  -> one dict per clip: token_logprobs / sum_logprob / avg_logprob (/ top_ids) per candidate — bit for bit what
+        score() gives for the candidate with the clip's mel repeated — and, made on the device over key = sum_logprob (normalize:
+        avg_logprob): order (candidate indices, key descending, equal keys lower index first), best = order[0], posterior (softmax
+        of the keys over the clip's candidates).  At most max_batch candidates in all."""
+        ptr, on_dev, U, keep, args = self._nbest_args(mel, candidates, context_len)
+        tab, lens, ctx, n_cand = args[:4]
+        bufs = self._nbest_bufs(tab, U)
+        lps, top, sm, avg, order, best, post = bufs
+        _lib.check(_lib.lib().wm_score_nbest(self._h, ptr, on_dev, U, _ip(n_cand), int(bool(normalize)), self.pos_mode, _ip(tab), _ip(lens),
+                                             tab.shape[1], _ip(ctx), _fp(lps), _ip(top) if return_top_ids else None, _fp(sm), _fp(avg),
+                                             _ip(order), _ip(best), _fp(post)))
+        return self._nbest_out(args, bufs, return_top_ids)
+
+    def score_candidates_submit(self, mel, candidates, slot: int = 0, context_len=None, normalize: bool = False):
+        """Pipelined score_candidates on one of the eight slots; collect with score_candidates_wait.  Everything is validated before
+        the call and the slot's record is written only once the library accepted the pass."""
+        ptr, on_dev, U, keep, args = self._nbest_args(mel, candidates, context_len)
+        if not 0 <= int(slot) < 8:
+            raise ValueError("slot must be 0..7")
+        tab, lens, ctx, n_cand = args[:4]
+        _lib.check(_lib.lib().wm_score_nbest_submit(self._h, slot, ptr, on_dev, U, _ip(n_cand), int(bool(normalize)), self.pos_mode, _ip(tab),
+                                                    _ip(lens), tab.shape[1], _ip(ctx)))
+        self._nbest_pending[slot] = (args, U, keep)
+
+    def score_candidates_wait(self, slot: int = 0, return_top_ids: bool = False):
+        pend = self._nbest_pending
+        if slot not in pend:
+            raise _lib.WhisperMiError(f"no n-best score pass was submitted on slot {slot}")
+        args, U, _keep = pend[slot]
+        bufs = self._nbest_bufs(args[0], U)
+        lps, top, sm, avg, order, best, post = bufs
+        _lib.check(_lib.lib().wm_score_nbest_wait(self._h, slot, _fp(lps), _ip(top) if return_top_ids else None, _fp(sm), _fp(avg), _ip(order),
+                                                  _ip(best), _fp(post)))
+        del pend[slot]  # only a collected pass leaves the table
+        return self._nbest_out(args, bufs, return_top_ids)
 
     # ---- forced alignment (DESIGN §21) ---------------------------------------------------------------------------------------
     def _align_args(self, mel, ids, context_len, n_frames):

@@ -116,6 +116,32 @@ def attention_cached(out: np.ndarray, q, k, v, n_heads: int, kv_dtype=DT_F32, n_
                                                  q_B, len, nq))
 
 
+def _utt_map(utt_of, n_slots):
+    m = np.ascontiguousarray(np.asarray(utt_of, np.int32).reshape(-1))
+    if m.size != n_slots:
+        raise ValueError(f"utt_of needs one entry per batch slot ({n_slots}), got {m.size}")
+    return m
+
+
+def attention_cached_map(out: np.ndarray, q, k, v, utt_of, n_heads: int, kv_dtype=DT_F32, n_chunks: int = 2, out_dtype=DT_F32,
+                         q_B: int = 0, nq: int = 0):
+    """attention_cached's chunked forms (n_chunks >= 2) with K/V by row map (wm_op_attention_cached_map): k / v
+    [n_utt, t, d], utt_of [q_B, or B when q_B == 0]: the query row in batch slot b attends over clip utt_of[b]."""
+    f = lambda a: np.ascontiguousarray(a, np.float32)
+    q, k, v = f(q), f(k), f(v)
+    if q.ndim != 2 or q.shape[1] != 64 * n_heads or k.ndim != 3 or k.shape[2] != q.shape[1] or v.shape != k.shape:
+        raise ValueError("q must be [B, 64 * n_heads], k and v [n_utt, t, 64 * n_heads]")
+    B = q.shape[0]
+    if q_B < 0 or (q_B > 0 and B % q_B):
+        raise ValueError("prefill rows are position-major: q must be [P * q_B, d]")
+    if n_chunks < 2:
+        raise ValueError("the map belongs to the chunked forms (n_chunks >= 2)")
+    m = _utt_map(utt_of, q_B if q_B > 0 else B)
+    _chk_out(out, q.shape)
+    _lib.check(_lib.lib().wm_op_attention_cached_map(_fp(out), _fp(q), _fp(k), _fp(v), B, k.shape[1], n_heads, kv_dtype, n_chunks, out_dtype,
+                                                     q_B, -1, nq, m.ctypes.data_as(C.POINTER(C.c_int32)), k.shape[0]))
+
+
 def dec_linear(x, W, bias=None, ln=None, residual=None, in_place: bool = False, dtype=DT_F32, x_is_t: bool = False, out_is_t: bool = False,
                act: bool = False, gelu_mode: int = GELU_TANH, kv=None, kv_dtype=DT_F32, kv_B: int = 0, len: int = 0, cap=None,
                cap_sel=None, cap_step0: int = 0, _hook: str = "wm_op_dec_linear"):
@@ -421,6 +447,35 @@ def xattn(out: np.ndarray, q, Wk, Wv, bv, x, n_heads: int, nsplit: int, q_B: int
     _chk_out(out, q.shape)
     _lib.check(_lib.lib().wm_op_xattn(_fp(out), _fp(q), _fp(Wk), _fp(Wv), _fp(bv), _fp(x), q.shape[0], q_B, x.shape[0], x.shape[1],
                                       n_heads, nsplit, out_dtype))
+
+
+def xattn_map(out: np.ndarray, q, Wk, Wv, bv, x, utt_of, n_heads: int, nsplit: int, q_B: int = 0, out_dtype=DT_F32):
+    """xattn with X by row map (wm_op_xattn_map): utt_of [q_B, or rows when q_B == 0]; the row in batch slot b attends
+    over x[utt_of[b]]."""
+    f = lambda a: np.ascontiguousarray(a, np.float32)
+    q, Wk, Wv, bv, x = f(q), f(Wk), f(Wv), f(bv).ravel(), f(x)
+    d = 64 * n_heads
+    if q.ndim != 2 or q.shape[1] != d or Wk.shape != (d, d) or Wv.shape != (d, d) or bv.size != d or x.ndim != 3 or x.shape[2] != d:
+        raise ValueError("q must be [rows, 64 * n_heads], Wk / Wv [d, d], bv [d], x [n_utt, n_keys, d]")
+    if q_B < 0 or (q_B > 0 and q.shape[0] % q_B):
+        raise ValueError("prefill rows are position-major: q must be [P * q_B, d]")
+    m = _utt_map(utt_of, q_B if q_B > 0 else q.shape[0])
+    _chk_out(out, q.shape)
+    _lib.check(_lib.lib().wm_op_xattn_map(_fp(out), _fp(q), _fp(Wk), _fp(Wv), _fp(bv), _fp(x), q.shape[0], q_B, x.shape[0], x.shape[1],
+                                          n_heads, nsplit, out_dtype, m.ctypes.data_as(C.POINTER(C.c_int32))))
+
+
+def score_rank(key, n_cand):
+    """The n-best ranking launch alone (wm_op_score_rank): key [R] fp32 grouped by clip, n_cand [U] >= 1 with
+    sum n_cand = R -> (order [R] int32, best [U] int32, posterior [R] fp32)."""
+    key = np.ascontiguousarray(np.asarray(key, np.float32).reshape(-1))
+    n = np.ascontiguousarray(np.asarray(n_cand, np.int32).reshape(-1))
+    if n.size < 1 or n.min() < 1 or int(n.sum()) != key.size:
+        raise ValueError("n_cand needs one count >= 1 per clip, summing to the number of keys")
+    order, best, post = np.full(key.size, -1, np.int32), np.full(n.size, -1, np.int32), np.zeros(key.size, np.float32)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    _lib.check(_lib.lib().wm_op_score_rank(ip(order), ip(best), _fp(post), _fp(key), ip(n), n.size))
+    return order, best, post
 
 
 def xattn_absorb(q, Wk, n_heads: int, late_loads: bool = False) -> np.ndarray:
