@@ -782,6 +782,21 @@ int wm_op_gemm_nt_epi(float* C, size_t c_len, const float* A, size_t a_len, cons
                       const float* residual, size_t r_len, int M, int N, int K, int batch, long long lda, long long strideA,
                       long long ldc, long long strideC, long long ldr, long long strideR, int residual_in_place, int act, int gelu_mode,
                       int group_n, long long group_stride, int dtype, int out_dtype, int* kernel_ran);
+/* wm_op_gemm_nt_epi for the shapes the launcher gives to the two ring kernels — gemm_nt_rowpanel_kernel (16-bit operands, K = 384,
+ * N <= 3072, batch 1, no pos / residual) and gemm_nt_fullrow_kernel (16-bit operands, N = 384, K % 128 == 0, fp32 output) — with the
+ * LayerNorms they carry.  Every argument of wm_op_gemm_nt_epi means the same here, and:
+ *   ln_g, ln_b [K], both or neither: A holds the fp32 residual rows (not rounded to dtype) and the row-panel kernel multiplies
+ *     round_dtype(LayerNorm(A row)·ln_g + ln_b).  Handed to the launcher as asked: a shape that cannot fuse is refused.
+ *   lno_g, lno_b [N], lno_out (lno_len elements), all or none: the full-row kernel also writes round_dtype(LayerNorm(C row)·lno_g +
+ *     lno_b) to lno_out, laid out like C (ldc, strideC).  lno_out is in and out like C: uploaded rounded to dtype, returned widened.
+ * WM_E_ARG with nothing launched and C / lno_out untouched: whatever wm_op_gemm_nt_epi refuses (but the ring shapes), a shape that
+ * dispatches to a tiled kernel, a LayerNorm the launcher refuses for the shape, ldc / strideC / group_stride not multiples of 8 where
+ * 16-bit rows are written (16-bit output, lno_out), lno_len below the extent of C, (M-1)·lda + K >= 2^31.  Known-answer tests. */
+int wm_op_gemm_nt_ring(float* C, size_t c_len, const float* A, size_t a_len, const float* W, const float* bias, const float* pos,
+                       const float* residual, size_t r_len, int M, int N, int K, int batch, long long lda, long long strideA,
+                       long long ldc, long long strideC, long long ldr, long long strideR, int residual_in_place, int act, int gelu_mode,
+                       int group_n, long long group_stride, int dtype, int out_dtype, const float* ln_g, const float* ln_b,
+                       const float* lno_g, const float* lno_b, float* lno_out, size_t lno_len, int* kernel_ran);
 /* The q_len == 1 path of MultiHeadAttention.forward over cached keys / values (layers.mojo:186-272): per utterance and head
  * s_j = (q·K_j)·0.125 (scale AFTER the dot product), running max from -1e10, p = exp(s - max), o = Σ p_j V_j / Σ p_j.
  * q, out [B, 64·n_heads] fp32; k, v [B, t, 64·n_heads] fp32 host rows, rounded to kv_dtype as the cache holds them.

@@ -43,6 +43,8 @@ import pytest
 from test_enc_ops_ref import DTYPE, SENTINEL, U, _rng, rnd
 
 KERN = ("direct", "lds")
+RING = ("rowpanel", "fullrow")  # the ring kernels (tests/test_enc_ring_gemm_ref.py): gelu_fast4 like the lds kernel
+EXTRA = {}  # case id -> case of a module that builds on this one; CASES below stays this module's own lists
 PAIRS = (("bf16", "bf16"), ("bf16", "f32"), ("f16", "f16"), ("f16", "f32"), ("f32", "f32"))
 EPIS = ("none", "bias", "bias_res", "bias_res_inplace", "bias_pos", "bias_pos_res")
 L_G = 1.13
@@ -94,6 +96,10 @@ def case_id(c):
         s += f"-g{c['group_n']}"
     if c["act"] is not None:
         s += f"-gelu{c['act']}"
+    if c.get("ldc_pad"):
+        s += f"-ldc+{c['ldc_pad']}"
+    if c.get("lno"):
+        s += "-lno"
     return s
 
 
@@ -171,7 +177,8 @@ def layout(c):
     """element counts and strides of the hook call: one guard row after the last row of every batch and of every column group"""
     M, N, K, B = c["M"], c["N"], c["K"], c["batch"]
     gn = c["group_n"]
-    ldc = gn if gn else N
+    row_w = gn if gn else N
+    ldc = row_w + c.get("ldc_pad", 0)  # ldc_pad: columns between the rows of C that the kernel must leave alone
     n_grp = N // gn if gn else 1
     group_stride = (M + 1) * ldc
     strideC = n_grp * group_stride
@@ -182,12 +189,27 @@ def layout(c):
         lda, strideA = K, M * K
     a_len = (B - 1) * strideA + (M - 1) * lda + K
     ldr, strideR = N + 8, M * (N + 8) + 16  # ldr > N, strideR != strideC
-    return dict(ldc=ldc, n_grp=n_grp, group_stride=group_stride, strideC=strideC, c_len=B * strideC, lda=lda, strideA=strideA, a_len=a_len,
+    return dict(ldc=ldc, row_w=row_w, n_grp=n_grp, group_stride=group_stride, strideC=strideC, c_len=B * strideC, lda=lda, strideA=strideA, a_len=a_len,
                 ldr=ldr, strideR=strideR, r_len=B * strideR)
+
+
+def cells(lay, base, M):
+    """the M rows of row_w columns at base, ldc apart, as an index into the flat C: a slice where the rows touch (val then ravelled)"""
+    if lay["ldc"] == lay["row_w"]:
+        return slice(base, base + M * lay["ldc"])
+    return base + np.arange(M)[:, None] * lay["ldc"] + np.arange(lay["row_w"])[None, :]
+
+
+def put(flat, lay, base, M, val):
+    flat[cells(lay, base, M)] = val if lay["ldc"] != lay["row_w"] or np.ndim(val) == 0 else np.asarray(val).reshape(-1)
 
 
 def _rows(flat, base, M, ld, width):
     return np.lib.stride_tricks.as_strided(flat[base:], (M, width), (ld * flat.itemsize, flat.itemsize), writeable=False)
+
+
+def _case(cid):
+    return CASES[cid] if cid in CASES else EXTRA[cid]
 
 
 def sweep_values(dt):
@@ -202,7 +224,7 @@ def sweep_values(dt):
 
 @functools.lru_cache(maxsize=None)
 def _operands(cid):
-    c = CASES[cid]
+    c = _case(cid)
     lay = layout(c)
     r = _rng(cid)
     M, N, K, B = c["M"], c["N"], c["K"], c["batch"]
@@ -214,7 +236,7 @@ def _operands(cid):
     elif c["pat"] == "sweep":
         z = sweep_values(dt)
         W = np.zeros((N, K), np.float32)
-        W[:, :64] = z.reshape(N, 64)  # z[m, n] = W[n, m] for m < 64; rows 64.. of the K = 96 variant read zero columns
+        W[:256, :64] = z.reshape(256, 64)  # z[m, n] = W[n, m] for m < 64, n < 256; rows 64.. of a deeper K read zero columns
         A = np.eye(M, K, dtype=np.float32).ravel()
         q = None
     else:
@@ -254,7 +276,7 @@ def c_init(c):
     if c["epi"].endswith("inplace"):
         res = operands(c)[4]
         for b in range(c["batch"]):
-            C0[b * lay["strideC"]:][:c["M"] * lay["ldc"]] = res[b].ravel()
+            put(C0, lay, b * lay["strideC"], c["M"], res[b])
     return C0
 
 
@@ -277,7 +299,7 @@ def gelu64(z, mode):
 def eps_gelu(z, y, mode, kern):
     """the module docstring's eps_g at z (float64), y = gelu64(z, mode)"""
     x, ay = np.asarray(z, np.float64), np.abs(y)
-    if kern == "lds" and mode == 0:
+    if kern != "direct" and mode == 0:
         e = x * (K1X + K2X * x * x)
         with np.errstate(divide="ignore", invalid="ignore"):
             sigma = np.clip(np.where(x != 0, 1.0 - y / x, 0.5), 0.0, 1.0)  # t / (1 + t) = 1 - y / x
@@ -296,7 +318,7 @@ def eps_gelu(z, y, mode, kern):
 @functools.lru_cache(maxsize=None)
 def _reference(cid):
     """-> (expected flat C in float64 with the untouched cells at the sentinel, bar per cell or None for an exact case)"""
-    c = CASES[cid]
+    c = _case(cid)
     lay = layout(c)
     A, W, bias, pos, res = operands(c)
     M, N, gn = c["M"], c["N"], c["group_n"]
@@ -321,11 +343,10 @@ def _reference(cid):
             d = 2.0 * d
         for g in range(lay["n_grp"]):
             base = b * lay["strideC"] + g * lay["group_stride"]
-            w = lay["ldc"]
             cols = slice(g * gn, (g + 1) * gn) if gn else slice(0, N)
-            want[base:base + M * w] = out[:, cols].ravel()
+            put(want, lay, base, M, out[:, cols])
             if bar is not None:
-                bar[base:base + M * w] = d[:, cols].ravel()
+                put(bar, lay, base, M, d[:, cols])
     want.setflags(write=False)
     return want, bar
 
@@ -340,7 +361,7 @@ def written_mask(c):
     for b in range(c["batch"]):
         for g in range(lay["n_grp"]):
             base = b * lay["strideC"] + g * lay["group_stride"]
-            m[base:base + c["M"] * lay["ldc"]] = True
+            put(m, lay, base, c["M"], True)
     return m
 
 
@@ -424,7 +445,7 @@ def restate(c):
         for g in range(lay["n_grp"]):
             base = b * lay["strideC"] + g * lay["group_stride"]
             cols = slice(g * gn, (g + 1) * gn) if gn else slice(0, N)
-            got[base:base + M * lay["ldc"]] = v[:, cols].ravel()
+            put(got, lay, base, M, v[:, cols])
     return got
 
 

@@ -41,7 +41,7 @@ SYMBOLS = [
     "wm_set_sequence_bias", "wm_op_logits_seq_bias", "wm_op_seq_bias_hits",
     "wm_chunk_table", "wm_transcribe_chunked", "wm_op_chunk_gather", "wm_op_chunk_merge",
     "wm_transcribe_chunked_ts", "wm_op_chunk_segments",
-    "wm_op_gemm_nt_epi",
+    "wm_op_gemm_nt_epi", "wm_op_gemm_nt_ring",
     "wm_resample_len", "wm_resample_pcm", "wm_op_resample", "wm_op_resample_taps",
     "wm_set_top_k", "wm_transcribe_top_k", "wm_op_logits_topk",
     "wm_set_constraint", "wm_transcribe_constraint_match", "wm_op_constraint_states",
@@ -292,6 +292,7 @@ def lib():
     L.wm_op_attention_batch.argtypes = [fp] * 4 + [C.c_int] * 4
     L.wm_op_gemm_nt_epi.argtypes = ([fp, C.c_size_t, fp, C.c_size_t, fp, fp, fp, fp, C.c_size_t] + [C.c_int] * 4 + [C.c_longlong] * 6 +
                                     [C.c_int] * 4 + [C.c_longlong, C.c_int, C.c_int, ip])
+    L.wm_op_gemm_nt_ring.argtypes = L.wm_op_gemm_nt_epi.argtypes[:-1] + [fp] * 5 + [C.c_size_t, ip]
     L.wm_op_gelu.argtypes = [fp, C.c_size_t, C.c_int]
     L.wm_op_softmax_rows.argtypes = [fp, C.c_int, C.c_int]
     L.wm_op_conv1d_k3.argtypes = [fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]

@@ -747,6 +747,11 @@ __global__ __launch_bounds__(512) void gemm_nt_fullrow_kernel(GemmParams p) {
     using N = std::false_type;
     WM_FR_TOP(8);  // half-stage 0 has landed (1 and 2 may be in flight)
     read_x(0, a0, wx);
+    // These first fragments are waited for here, not at step X(0)'s own wait: at K = 128 the loop below does not run, the two ways
+    // into the last group meet, and the compiler joins them with register copies of a0 / wx placed in front of that wait — copies of
+    // registers whose ds_read had not returned (wrong column blocks 2 wc + 1 at K = 128 with f16 operands).  One LDS latency per
+    // workgroup; every later read is requested and waited for inside one straight line of steps.
+    asm volatile("s_waitcnt lgkmcnt(0)" : WM_FR_HOLD_X(a0, wx)::"memory");
     // steady state: groups of four half-stages (two k64), every wait the same constant and every refill unconditional; then the
     // last group with its shorter queues.  Before the top of step h the DMAs outstanding are those of half-stages h+1 and h+2.
     int h = 0;

@@ -211,14 +211,25 @@ extern "C" int wm_op_layer_norm_t(float* out_t, float* out_f, const float* inp, 
     return 0;
 }
 
-// One gemm_dispatch call with everything GemmParams offers the two tiled kernels (include/whisper_mi.h).  Device sizes: both kernels
-// read whole 128-row panels of A whatever M is, so A is allocated zero-filled up to the last panel row; bias, pos, residual and C are
-// touched at valid rows only (gemm_epilogue's valid[]), and the checks below hold every offset the epilogue can form inside the
-// caller's lengths, which are also the device lengths.
-extern "C" int wm_op_gemm_nt_epi(float* C, size_t c_len, const float* A, size_t a_len, const float* W, const float* bias, const float* pos,
-                                 const float* residual, size_t r_len, int M, int N, int K, int batch, long long lda, long long strideA,
-                                 long long ldc, long long strideC, long long ldr, long long strideR, int residual_in_place, int act,
-                                 int gelu_mode, int group_n, long long group_stride, int dtype, int out_dtype, int* kernel_ran) {
+// One gemm_dispatch call with everything GemmParams offers (include/whisper_mi.h), behind wm_op_gemm_nt_epi (ring == false: the two
+// tiled kernels) and wm_op_gemm_nt_ring (ring == true: the row-panel and full-row kernels).
+// Device sizes, tiled kernels: both read whole 128-row panels of A whatever M is, so A is allocated zero-filled up to the last panel
+// row; bias, pos, residual and C are touched at valid rows only (gemm_epilogue's valid[]), and the checks below hold every offset the
+// epilogue can form inside the caller's lengths, which are also the device lengths.
+// Device sizes, ring kernels (read off kernels_encoder.hip): both clamp a row index >= M to M - 1 before they form any address —
+// gemm_nt_rowpanel_kernel `row = row < p.M ? row : p.M - 1` for its A fragments (16-bit, or the fp32 rows of the LNA form), the
+// full-row kernel `ar = ar < p.M ? ar : p.M - 1` for its A DMA and `mrow[i]` for residual, pos and the C row pointer — so A is read at
+// bz·strideA + row·lda + [0, K) with row < M only, residual at bz·strideR + row·ldr + [0, N), pos at row·N + [0, N), W at all N rows
+// of K, bias / ln_g / ln_b / lno_g / lno_b whole.  Stores are masked by row < M (`m >= p.M`, `mbase + row < p.M`, `valid`, `m < p.M`),
+// C at (group)·group_stride + bz·strideC + m·ldc + [0, row width), lno_out at bz·strideC + m·ldc + [0, N) in the operand type.  The
+// caller's lengths therefore cover both kernels; A is still zero-filled up to the end of the last 128-row panel, as upload_padded
+// callers do everywhere.  The full-row kernel forms its A offsets inside a batch in 32 bits: (M - 1)·lda + K must stay below 2^31
+// elements.  The 16-bit stores of both kernels are 16 bytes wide: ldc, strideC and group_stride are then multiples of 8.
+static int op_gemm_nt(bool ring, float* C, size_t c_len, const float* A, size_t a_len, const float* W, const float* bias, const float* pos,
+                      const float* residual, size_t r_len, int M, int N, int K, int batch, long long lda, long long strideA, long long ldc,
+                      long long strideC, long long ldr, long long strideR, int residual_in_place, int act, int gelu_mode, int group_n,
+                      long long group_stride, int dtype, int out_dtype, const float* ln_g, const float* ln_b, const float* lno_g,
+                      const float* lno_b, float* lno_out, size_t lno_len, int* kernel_ran) {
     if (!C || !A || !W || !kernel_ran || M <= 0 || N <= 0 || K <= 0 || batch <= 0) return fail(WM_E_ARG, "bad argument");
     if (M > (1 << 20) || N > (1 << 16) || K > (1 << 16) || batch > 1024) return fail(WM_E_ARG, "problem too large for the op hook");
     if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
@@ -251,8 +262,19 @@ extern "C" int wm_op_gemm_nt_epi(float* C, size_t c_len, const float* A, size_t 
     const size_t r_need = (size_t)(batch - 1) * strideR + (size_t)(M - 1) * ldr + N;
     if (a_len < a_need || c_len < c_need || (residual && r_len < r_need)) return fail(WM_E_ARG, "a size overflows the caller's arrays");
     if (a_len > ((size_t)1 << 31) || c_len > ((size_t)1 << 31) || r_len > ((size_t)1 << 31)) return fail(WM_E_ARG, "array too large for the op hook");
+    if ((ln_g != nullptr) != (ln_b != nullptr)) return fail(WM_E_ARG, "ln_g and ln_b go together");
+    const bool lno = lno_g || lno_b || lno_out;
+    if (lno && (!lno_g || !lno_b || !lno_out)) return fail(WM_E_ARG, "lno_g, lno_b and lno_out go together");
+    if (ring) {
+        if ((size_t)(M - 1) * lda + K >= ((size_t)1 << 31)) return fail(WM_E_ARG, "rows of one batch reach past 2^31 elements");
+        const bool wide = out_dtype != WM_F32 || lno;  // 16-byte stores of eight 16-bit elements
+        if (wide && (ldc % 8 || strideC % 8 || (group_n > 0 && group_stride % 8)))
+            return fail(WM_E_ARG, "16-bit rows need ldc / strideC / group_stride that are multiples of 8");
+        if (lno && (lno_len < c_need || lno_len > ((size_t)1 << 31))) return fail(WM_E_ARG, "lno_len does not hold the rows");
+    }
     TmpDev t;
-    DevBuf &a = t.add(), &w = t.add(), &c = t.add(), &b = t.add(), &ps = t.add(), &r = t.add();
+    DevBuf &a = t.add(), &w = t.add(), &c = t.add(), &b = t.add(), &ps = t.add(), &r = t.add(), &g1 = t.add(), &b1 = t.add(), &g2 = t.add(),
+           &b2 = t.add(), &lo = t.add();
     GemmParams p{};
     p.M = M;
     p.N = N;
@@ -272,25 +294,71 @@ extern "C" int wm_op_gemm_nt_epi(float* C, size_t c_len, const float* A, size_t 
     p.bias = bias;
     p.pos = pos;
     p.residual = residual_in_place ? C : residual;
-    *kernel_ran = gemm_nt_kernel_for((int)dt_size(dtype), (int)dt_size(out_dtype), p, batch, nullptr);
-    // the device sizes above are worked out for the two tiled kernels only; the ring kernels have hooks of their own
-    if (*kernel_ran != wm::GEMM_NT_DIRECT && *kernel_ran != wm::GEMM_NT_LDS)
+    p.ln_g = ln_g;  // handed to the launcher as asked: a shape that cannot fuse is refused
+    p.ln_b = ln_b;
+    p.lno_g = lno_g;
+    p.lno_b = lno_b;
+    p.lno_out = lno_out;
+    const char* why = "";
+    *kernel_ran = gemm_nt_kernel_for((int)dt_size(dtype), (int)dt_size(out_dtype), p, batch, &why);
+    if (*kernel_ran == wm::GEMM_NT_REFUSED) return fail(WM_E_ARG, why);
+    const bool is_ring = *kernel_ran == wm::GEMM_NT_ROWPANEL || *kernel_ran == wm::GEMM_NT_FULLROW;
+    // the tiled hook's device sizes are worked out for the two tiled kernels only; the ring kernels have a hook of their own
+    if (!ring && is_ring)
         return fail(WM_E_ARG, "this shape dispatches to the row-panel / full-row kernel (wm_op_matmul_nt, wm_op_ln_matmul_nt, wm_op_mlp_block)");
-    WMCHK(upload_padded(a, A, a_need, a_dev, dtype));  // A: the caller's part, then zeros up to the end of the last 128-row panel
+    if (ring && !is_ring) return fail(WM_E_ARG, "this shape dispatches to a tiled kernel (wm_op_gemm_nt_epi)");
+    // A: the caller's part, then zeros up to the end of the last 128-row panel (fp32 rows where the row-panel kernel normalises them)
+    WMCHK(upload_padded(a, A, a_need, a_dev, ln_g ? WM_F32 : dtype));
     WMCHK(upload(w, W, (size_t)N * K, dtype));
     WMCHK(upload(c, C, c_len, out_dtype));
     if (bias) WMCHK(upload(b, bias, N, WM_F32));
     if (pos) WMCHK(upload(ps, pos, (size_t)M * N, WM_F32));
     if (residual && !residual_in_place) WMCHK(upload(r, residual, r_len, WM_F32));
+    if (ln_g) {
+        WMCHK(upload(g1, ln_g, K, WM_F32));
+        WMCHK(upload(b1, ln_b, K, WM_F32));
+    }
+    if (lno) {  // the 16-bit rows start from the caller's values: what the kernel leaves alone comes back as it went in
+        WMCHK(upload(g2, lno_g, N, WM_F32));
+        WMCHK(upload(b2, lno_b, N, WM_F32));
+        WMCHK(upload(lo, lno_out, lno_len, dtype));
+    }
     p.A = a.p;
     p.W = w.p;
     p.C = c.p;
     p.bias = bias ? b.as<float>() : nullptr;
     p.pos = pos ? ps.as<float>() : nullptr;
     p.residual = residual_in_place ? c.as<float>() : residual ? r.as<float>() : nullptr;
+    p.ln_g = ln_g ? g1.as<float>() : nullptr;
+    p.ln_b = ln_g ? b1.as<float>() : nullptr;
+    p.lno_g = lno ? g2.as<float>() : nullptr;
+    p.lno_b = lno ? b2.as<float>() : nullptr;
+    p.lno_out = lno ? lo.p : nullptr;
     WMCHK(gemm_dispatch(dtype, out_dtype, p, batch, nullptr));
     HIPCHK(hipGetLastError());
+    if (lno) WMCHK(download_f32(lno_out, lo, lno_len, dtype));
     return download_f32(C, c, c_len, out_dtype);
+}
+
+extern "C" int wm_op_gemm_nt_epi(float* C, size_t c_len, const float* A, size_t a_len, const float* W, const float* bias, const float* pos,
+                                 const float* residual, size_t r_len, int M, int N, int K, int batch, long long lda, long long strideA,
+                                 long long ldc, long long strideC, long long ldr, long long strideR, int residual_in_place, int act,
+                                 int gelu_mode, int group_n, long long group_stride, int dtype, int out_dtype, int* kernel_ran) {
+    return op_gemm_nt(false, C, c_len, A, a_len, W, bias, pos, residual, r_len, M, N, K, batch, lda, strideA, ldc, strideC, ldr, strideR,
+                      residual_in_place, act, gelu_mode, group_n, group_stride, dtype, out_dtype, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                      kernel_ran);
+}
+
+// wm_op_gemm_nt_epi's twin for the shapes the launcher gives to gemm_nt_rowpanel_kernel and gemm_nt_fullrow_kernel, with the two
+// fused LayerNorms those kernels carry (op_gemm_nt's comment has the device-size argument).
+extern "C" int wm_op_gemm_nt_ring(float* C, size_t c_len, const float* A, size_t a_len, const float* W, const float* bias, const float* pos,
+                                  const float* residual, size_t r_len, int M, int N, int K, int batch, long long lda, long long strideA,
+                                  long long ldc, long long strideC, long long ldr, long long strideR, int residual_in_place, int act,
+                                  int gelu_mode, int group_n, long long group_stride, int dtype, int out_dtype, const float* ln_g,
+                                  const float* ln_b, const float* lno_g, const float* lno_b, float* lno_out, size_t lno_len, int* kernel_ran) {
+    return op_gemm_nt(true, C, c_len, A, a_len, W, bias, pos, residual, r_len, M, N, K, batch, lda, strideA, ldc, strideC, ldr, strideR,
+                      residual_in_place, act, gelu_mode, group_n, group_stride, dtype, out_dtype, ln_g, ln_b, lno_g, lno_b, lno_out, lno_len,
+                      kernel_ran);
 }
 
 extern "C" int wm_op_mlp_block(float* x, const float* ln_g, const float* ln_b, const float* fc1_w, const float* fc1_b, const float* fc2_w,

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .config import DT_F32, GELU_TANH
+from .config import DT_BF16, DT_F32, GELU_TANH
 
 
 def Tensor(rows: int, cols: int) -> np.ndarray:
@@ -248,6 +248,41 @@ def gemm_nt_epi(C_flat: np.ndarray, A_flat, W, M, lda=None, batch=1, strideA=0, 
                                             0 if residual is None else residual.size, M, N, K, batch, K if lda is None else lda, strideA,
                                             N if ldc is None else ldc, strideC, ldr, strideR, int(bool(residual_in_place)), int(bool(act)),
                                             gelu_mode, group_n, group_stride, dtype, out_dtype, C.byref(ran)))
+    return GEMM_NT_KERNELS[ran.value]
+
+
+def gemm_nt_ring(C_flat: np.ndarray, A_flat, W, M, lda=None, batch=1, strideA=0, ldc=None, strideC=0, bias=None, pos=None, residual=None,
+                 ldr=0, strideR=0, residual_in_place=False, act=False, gelu_mode: int = GELU_TANH, group_n=0, group_stride=0, dtype=DT_BF16,
+                 out_dtype=DT_F32, ln=None, lno=None, lno_out=None) -> str:
+    """gemm_nt_epi for the shapes that run on the encoder's row-panel and full-row kernels (wm_op_gemm_nt_ring, whisper_mi.h).  ln =
+    (gamma [K], beta [K]): A_flat holds fp32 residual rows which the row-panel kernel normalises while loading.  lno = (gamma [N],
+    beta [N]) with lno_out, the caller's flat float32 array laid out like C_flat, in and out: the full-row kernel's 16-bit LayerNorm
+    rows, widened.  -> the kernel that ran."""
+    f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32).ravel()
+    W = np.ascontiguousarray(W, np.float32)
+    N, K = W.shape
+    A_flat, bias, pos, residual = f(A_flat), f(bias), f(pos), f(residual)
+    _chk_out(C_flat, (C_flat.size,))
+    if bias is not None and bias.size != N:
+        raise ValueError("bias must have N elements")
+    if pos is not None and pos.size != M * N:
+        raise ValueError("pos must be [M, N]")
+    ln_g, ln_b = (None, None) if ln is None else (f(ln[0]), f(ln[1]))
+    lno_g, lno_b = (None, None) if lno is None else (f(lno[0]), f(lno[1]))
+    if ln is not None and (ln_g.size != K or ln_b.size != K):
+        raise ValueError("ln gamma / beta must have K elements")
+    if lno is not None and (lno_g.size != N or lno_b.size != N):
+        raise ValueError("lno gamma / beta must have N elements")
+    if (lno is None) != (lno_out is None):
+        raise ValueError("lno and lno_out go together")
+    if lno_out is not None:
+        _chk_out(lno_out, (lno_out.size,))
+    ran = C.c_int32(-1)
+    _lib.check(_lib.lib().wm_op_gemm_nt_ring(_fp(C_flat), C_flat.size, _fp(A_flat), A_flat.size, _fp(W), _fp(bias), _fp(pos), _fp(residual),
+                                             0 if residual is None else residual.size, M, N, K, batch, K if lda is None else lda, strideA,
+                                             N if ldc is None else ldc, strideC, ldr, strideR, int(bool(residual_in_place)), int(bool(act)),
+                                             gelu_mode, group_n, group_stride, dtype, out_dtype, _fp(ln_g), _fp(ln_b), _fp(lno_g), _fp(lno_b),
+                                             _fp(lno_out), 0 if lno_out is None else lno_out.size, C.byref(ran)))
     return GEMM_NT_KERNELS[ran.value]
 
 
