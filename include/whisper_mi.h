@@ -903,6 +903,50 @@ int wm_op_seq_bias_hits(uint32_t* hit, float* slot_bias, int32_t* slot_flags, in
 int wm_op_constraint_states(int32_t* node, uint32_t* mask, const int32_t* tokens, const int32_t* prompt_len, const int32_t* n_ids, int B,
                             int stride, int vocab, int eot, int ngram, const int32_t* ids, const int32_t* offsets, int n_phrases, int free_from,
                             int steps);
+/* The timestamp rules' state machine alone, replayed likewise.  Launches: the pass's real init (row_prompts == 0:
+ * launch_init_tokens on the prompt tokens[0][0 .. prompt_len[0]) that every row must share, at most 16 ids; else
+ * launch_init_tokens_rows on the ragged rows with Lmax = max prompt_len), launch_set_step / launch_set_rows_step (cache length Lmax,
+ * row positions), then `steps` launch_argmax_step with the rules on and `advance` set, step s handed tokens[b][prompt_len[b] + s - 1]
+ * as its only candidate (a text id as the text partial, a timestamp id as the timestamp partial), so the kernel's own decision picks
+ * it.  Out: states [steps + 1][B][8], each a TsState (n_gen, last_ts, pen_ts, t_last, text_lo, text_hi, ts_lo, ts_hi) — entry 0 after
+ * the init, entry s after step s; a row's entries count up to its own end n_ids[b] only (behind it the kernel moves the state of the
+ * finished row on as for id 0).  picks [steps][B]: the launches' `next`.  out_tokens [B][stride], n_tokens [B], pos [B], ctl [4]
+ * (len, n_finished, 2 pad words): the final values.  key_lo [B], tok_rows, pos_rows [Lmax][B]: with row_prompts, else NULL.
+ * WM_E_ARG, nothing launched: timestamp_begin <= 0 or >= vocab, eos outside [0, timestamp_begin], a bad row table (the rule of
+ * wm_op_repeat_sets), rows of a shared prompt that differ.  max_initial < 0: none. */
+int wm_op_ts_states(int32_t* states, int32_t* picks, int32_t* out_tokens, int32_t* n_tokens, int32_t* pos, int32_t* ctl, int32_t* key_lo,
+                    int32_t* tok_rows, int32_t* pos_rows, const int32_t* tokens, const int32_t* prompt_len, const int32_t* n_ids, int B, int stride,
+                    int vocab, int timestamp_begin, int eos, int max_initial, int steps, int row_prompts);
+/* The pass-control and data-movement kernels, one launch each, exactly the runtime's.  Every output array is in and out:
+ * it goes to the device with the caller's values and comes back whole, so a sentinel shows what the kernel left alone.  Arrays with
+ * B_held (rows_held) rows hold that many rows while the launch covers B (rows_cap): the rest is the guard.
+ *
+ * wm_op_init_tokens: launch_init_tokens (len NULL: prompt [n_prompt], 1 .. 16 ids) or launch_init_tokens_rows (prompt [B][row_stride],
+ * len [B] in [1, Lmax]).  out_tokens [B_held][out_stride], n_tokens, finished [B_held], ctl [4]; optional (NULL = the kernel gets a
+ * null pointer): tok_rows + pos_rows [rows_held][B] (required with len), ts_state [B_held][8] (with vocab, timestamp_begin, eos,
+ * max_initial as wm_op_ts_states), logprobs [B_held][out_stride] + lp_sum [B_held], key_lo [B_held] (with len only). */
+int wm_op_init_tokens(int32_t* out_tokens, int32_t* n_tokens, int32_t* finished, int32_t* ctl, int32_t* tok_rows, int32_t* pos_rows,
+                      int32_t* ts_state, float* logprobs, float* lp_sum, int32_t* key_lo, const int32_t* prompt, int n_prompt, const int32_t* len,
+                      int row_stride, int Lmax, int rows_held, int B, int B_held, int out_stride, int vocab, int timestamp_begin, int eos,
+                      int max_initial);
+/* launch_set_rows_step: ctl->len = Lmax, pos[b] = len[b] + pos_delta.  ctl [4], pos [B_held], len [B]. */
+int wm_op_set_rows_step(int32_t* ctl, int32_t* pos, const int32_t* len, int Lmax, int pos_delta, int B, int B_held);
+/* launch_set_step: pos[b] = pos_value and tok[b] = tok_value where the array is given, ctl->len = len when set_len != 0. */
+int wm_op_set_step(int32_t* ctl, int32_t* pos, int32_t* tok, int len, int set_len, int pos_value, int tok_value, int B, int B_held);
+/* launch_pack_tokens over rows_cap rows: dst[r] = [n, ids zero-padded to stride] with n = min(n_tokens[r], stride) for r < rows, zeros
+ * for rows <= r < rows_cap.  dst [rows_held][1 + stride], out_tokens [rows][out_stride], n_tokens [rows]. */
+int wm_op_pack_tokens(int32_t* dst, const int32_t* out_tokens, const int32_t* n_tokens, int out_stride, int rows, int rows_cap, int rows_held,
+                      int stride);
+/* launch_dec_embed: x[b] = tok_emb[tok[b]] + pos_emb[pos[b]] in fp32.  x [B_held][d], tok_emb [vocab][d], pos_emb [n_pos][d]; an id or
+ * a position outside its table is WM_E_ARG. */
+int wm_op_dec_embed(float* x, const float* tok_emb, const float* pos_emb, const int32_t* tok, const int32_t* pos, int B, int B_held, int d,
+                    int vocab, int n_pos);
+/* The two row copies.  dst NULL: launch_no_speech_capture, out[r] = rows[r] for r < n_rows; else launch_score_collect, out[dst[r]] =
+ * rows[r] where dst[r] >= 0 (dst [n_rows] in [-1, out_rows), else WM_E_ARG).  out [out_rows][d], rows [n_rows][d], d % 4 == 0. */
+int wm_op_rows_copy(float* out, const float* rows, const int32_t* dst, int n_rows, int out_rows, int d);
+/* launch_mel_transpose_pad on B clips: mel [B][C][L] fp32 -> image [B_held][L + 2][Cp] in dtype (Cp = C rounded up to 32), rounded to
+ * dtype on upload and widened on return: row t + 1 = frame t, rows 0 and L + 1 and channels >= C zero, clips behind B untouched. */
+int wm_op_mel_transpose_pad(float* image, const float* mel, int B, int B_held, int C, int L, int dtype);
 /* The no-speech probe's launches on the kernel variant wm_op_logits_lp picks for (dtype, K, B): prob[b] = softmax(LN(x[b])·embᵀ)[token]
  * over all N columns, lse[b] the row's logsumexp.  prob, lse: [B]. */
 int wm_op_no_speech(float* prob, float* lse, const float* x, const float* ln_g, const float* ln_b, const float* emb, int B, int N, int K,

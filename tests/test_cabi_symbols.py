@@ -19,7 +19,8 @@ def test_header_declares_the_boundary():
     for s in ("wm_model_load", "wm_transcribe", "wm_encode", "wm_decode_step", "wm_state_new", "wm_op_matmul_nt",
               "wm_op_layer_norm", "wm_op_gelu", "wm_op_softmax_rows", "wm_op_conv1d_k3", "wm_op_argmax",
               "wm_op_attention_batch", "wm_op_layer_norm_t", "wm_op_gemm_nt_epi", "wm_op_gemm_nt_ring", "wm_op_fe_tables", "wm_op_fe_frames", "wm_op_fe_mel_log",
-              "wm_op_fe_mel_norm", "wm_op_window_gather"):
+              "wm_op_fe_mel_norm", "wm_op_window_gather", "wm_op_ts_states", "wm_op_init_tokens", "wm_op_set_rows_step", "wm_op_set_step",
+              "wm_op_pack_tokens", "wm_op_dec_embed", "wm_op_rows_copy", "wm_op_mel_transpose_pad"):
         assert s in syms
 
 

@@ -48,6 +48,8 @@ SYMBOLS = [
     "wm_op_fe_tables", "wm_op_fe_frames", "wm_op_fe_mel_log", "wm_op_fe_mel_norm", "wm_op_window_gather",
     "wm_score_nbest", "wm_score_nbest_submit", "wm_score_nbest_wait", "wm_score_nbest_pcm",
     "wm_op_attention_cached_map", "wm_op_xattn_map", "wm_op_score_rank",
+    "wm_op_ts_states", "wm_op_init_tokens", "wm_op_set_rows_step", "wm_op_set_step", "wm_op_pack_tokens", "wm_op_dec_embed", "wm_op_rows_copy",
+    "wm_op_mel_transpose_pad",
 ]
 
 ABI_VERSION = 5  # include/whisper_mi.h WM_ABI_VERSION: the struct layouts below are this version's
@@ -387,6 +389,14 @@ def lib():
     L.wm_op_fe_mel_log.argtypes = [fp, fp] + [C.c_int] * 5
     L.wm_op_fe_mel_norm.argtypes = [fp, fp, C.c_int, i64, C.c_int]
     L.wm_op_window_gather.argtypes = [fp, fp, ip] + [C.c_int] * 5
+    L.wm_op_ts_states.argtypes = [ip] * 12 + [C.c_int] * 8
+    L.wm_op_init_tokens.argtypes = [ip] * 7 + [fp, fp, ip, ip, C.c_int, ip] + [C.c_int] * 10
+    L.wm_op_set_rows_step.argtypes = [ip, ip, ip] + [C.c_int] * 4
+    L.wm_op_set_step.argtypes = [ip, ip, ip] + [C.c_int] * 6
+    L.wm_op_pack_tokens.argtypes = [ip, ip, ip] + [C.c_int] * 5
+    L.wm_op_dec_embed.argtypes = [fp, fp, fp, ip, ip] + [C.c_int] * 5
+    L.wm_op_rows_copy.argtypes = [fp, fp, ip] + [C.c_int] * 3
+    L.wm_op_mel_transpose_pad.argtypes = [fp, fp] + [C.c_int] * 5
     _lib = L
     return L
 

@@ -1078,6 +1078,335 @@ extern "C" int wm_op_constraint_states(int32_t* node, uint32_t* mask, const int3
     return replay_forced(t, tokens, prompt_len, n_ids, B, stride, vocab, ngram, steps, extra, init, fetch);
 }
 
+// ---- the pass-control kernels and the timestamp rules' state machine ---------------------------------------------
+// The start of a pass on device buffers that already hold the caller's values: launch_init_tokens (len null: the shared prompt
+// prompt[0 .. n_prompt), at most 16 ids) or launch_init_tokens_rows (row b's prompt prompt[b * row_stride .. + len[b]), Lmax cache rows).
+// Shared by wm_op_init_tokens and wm_op_ts_states; the arguments are checked by the callers.
+struct InitDev {
+    int *out_tokens, *n_tokens, *finished, *tok_rows, *pos_rows, *key_lo;
+    StepCtl* ctl;
+    TsState* ts_state;
+    float *logprobs, *lp_sum;
+};
+static int op_launch_init(TmpDev& t, const InitDev& d, const int32_t* prompt, int n_prompt, const int32_t* len, int row_stride, int Lmax, int B,
+                          int out_stride, const TsRules& rules) {
+    InitTokensParams ip{};
+    ip.out_tokens = d.out_tokens;
+    ip.out_stride = out_stride;
+    ip.n_tokens = d.n_tokens;
+    ip.finished = d.finished;
+    ip.ctl = d.ctl;
+    ip.B = B;
+    ip.tok_rows = d.tok_rows;
+    ip.pos_rows = d.pos_rows;
+    ip.ts_state = d.ts_state;
+    ip.rules = rules;
+    ip.logprobs = d.logprobs;
+    ip.lp_sum = d.lp_sum;
+    if (!len) {
+        ip.n_prompt = n_prompt;
+        std::copy(prompt, prompt + n_prompt, ip.prompt);
+        launch_init_tokens(ip, nullptr);
+    } else {
+        DevBuf &tab = t.add(), &dl = t.add();
+        WMCHK(upload_bytes(tab, prompt, (size_t)B * row_stride * 4));
+        WMCHK(upload_bytes(dl, len, (size_t)B * 4));
+        launch_init_tokens_rows(ip, RowPromptParams{tab.as<int>(), dl.as<int>(), row_stride, Lmax, d.key_lo}, nullptr);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+static int ts_rules_check(int vocab, int timestamp_begin, int eos) {
+    if (timestamp_begin <= 0 || timestamp_begin >= vocab) return fail(WM_E_ARG, "timestamp rules need 0 < timestamp_begin < vocab");
+    if (eos < 0 || eos > timestamp_begin) return fail(WM_E_ARG, "timestamp rules need 0 <= eos <= timestamp_begin");
+    return 0;
+}
+// an in-and-out host array on the device, and back
+static int up_opt(DevBuf& b, const void* h, size_t bytes) { return h ? upload_bytes(b, h, bytes) : 0; }
+static int down_opt(void* h, const DevBuf& b, size_t bytes) {
+    if (h) HIPCHK(hipMemcpy(h, b.p, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// launch_init_tokens or launch_init_tokens_rows alone, one launch.  Every output array goes up with the caller's values and comes back
+// whole.  len null: the shared prompt; else the rows form.  The row arrays hold B_held >= B rows and tok_rows / pos_rows rows_held
+// position rows of B, so the caller sees what a thread past B or a slot past the prompt would have written.
+extern "C" int wm_op_init_tokens(int32_t* out_tokens, int32_t* n_tokens, int32_t* finished, int32_t* ctl, int32_t* tok_rows, int32_t* pos_rows,
+                                 int32_t* ts_state, float* logprobs, float* lp_sum, int32_t* key_lo, const int32_t* prompt, int n_prompt,
+                                 const int32_t* len, int row_stride, int Lmax, int rows_held, int B, int B_held, int out_stride, int vocab,
+                                 int timestamp_begin, int eos, int max_initial) {
+    if (!out_tokens || !n_tokens || !finished || !ctl || !prompt || B <= 0 || B_held < B || B_held > (1 << 20) || out_stride <= 0 || out_stride > (1 << 16))
+        return fail(WM_E_ARG, "bad argument");
+    if (!tok_rows != !pos_rows || !logprobs != !lp_sum) return fail(WM_E_ARG, "tok_rows and pos_rows go together, and so do logprobs and lp_sum");
+    int need_rows;
+    if (!len) {
+        if (n_prompt < 1 || n_prompt > 16 || n_prompt > out_stride) return fail(WM_E_ARG, "the shared prompt holds 1 .. 16 ids and fits out_stride");
+        if (key_lo) return fail(WM_E_ARG, "key_lo belongs to the rows form");
+        need_rows = n_prompt;
+    } else {
+        if (!tok_rows || !key_lo) return fail(WM_E_ARG, "the rows form needs tok_rows, pos_rows and key_lo");
+        if (row_stride <= 0 || row_stride > (1 << 16) || Lmax < 1 || Lmax > row_stride) return fail(WM_E_ARG, "the rows form needs 1 <= Lmax <= row_stride");
+        for (int b = 0; b < B; ++b)
+            if (len[b] < 1 || len[b] > Lmax || len[b] > out_stride) return fail(WM_E_ARG, "row %d: need 1 <= len <= Lmax and len <= out_stride", b);
+        need_rows = Lmax;
+    }
+    if (tok_rows && (rows_held < need_rows || rows_held > (1 << 16))) return fail(WM_E_ARG, "tok_rows / pos_rows hold fewer position rows than the prompt");
+    TsRules rules{};
+    if (ts_state) {
+        WMCHK(ts_rules_check(vocab, timestamp_begin, eos));
+        rules = TsRules{timestamp_begin, eos, max_initial, vocab};
+    }
+    TmpDev t;
+    DevBuf &o = t.add(), &nt = t.add(), &fin = t.add(), &dc = t.add(), &tr = t.add(), &pr = t.add(), &ts = t.add(), &lp = t.add(), &ls = t.add(),
+           &kl = t.add();
+    const size_t nb = (size_t)B_held * 4, no = (size_t)B_held * out_stride * 4, nr = (size_t)std::max(rows_held, 0) * B * 4;
+    WMCHK(upload_bytes(o, out_tokens, no));
+    WMCHK(upload_bytes(nt, n_tokens, nb));
+    WMCHK(upload_bytes(fin, finished, nb));
+    WMCHK(upload_bytes(dc, ctl, sizeof(StepCtl)));
+    WMCHK(up_opt(tr, tok_rows, nr));
+    WMCHK(up_opt(pr, pos_rows, nr));
+    WMCHK(up_opt(ts, ts_state, (size_t)B_held * sizeof(TsState)));
+    WMCHK(up_opt(lp, logprobs, no));
+    WMCHK(up_opt(ls, lp_sum, nb));
+    WMCHK(up_opt(kl, key_lo, nb));
+    InitDev d{o.as<int>(), nt.as<int>(), fin.as<int>(), tok_rows ? tr.as<int>() : nullptr, tok_rows ? pr.as<int>() : nullptr, kl.as<int>(),
+              dc.as<StepCtl>(), ts_state ? ts.as<TsState>() : nullptr, logprobs ? lp.as<float>() : nullptr, logprobs ? ls.as<float>() : nullptr};
+    WMCHK(op_launch_init(t, d, prompt, n_prompt, len, row_stride, Lmax, B, out_stride, rules));
+    WMCHK(down_opt(out_tokens, o, no));
+    WMCHK(down_opt(n_tokens, nt, nb));
+    WMCHK(down_opt(finished, fin, nb));
+    WMCHK(down_opt(ctl, dc, sizeof(StepCtl)));
+    WMCHK(down_opt(tok_rows, tr, nr));
+    WMCHK(down_opt(pos_rows, pr, nr));
+    WMCHK(down_opt(ts_state, ts, (size_t)B_held * sizeof(TsState)));
+    WMCHK(down_opt(logprobs, lp, no));
+    WMCHK(down_opt(lp_sum, ls, nb));
+    return down_opt(key_lo, kl, nb);
+}
+
+// Forced-token replay of the timestamp rules: the real init launch (row_prompts == 0: launch_init_tokens on the prompt all rows share;
+// else launch_init_tokens_rows on the ragged rows, Lmax = max prompt_len), the launch that ends the prefill (launch_set_step /
+// launch_set_rows_step: cache length and positions), then one launch_argmax_step per step with ts_state, rules and advance set.  Each
+// launch gets the row's next id as its only candidate — a text id (< timestamp_begin) as the one text partial with no timestamp mass
+// (ts_s = 0, ts_val = ts_m = -inf), a timestamp id as the one timestamp partial (value 0, mass 1) with no text candidate (index
+// INT_MAX, value -inf) — so the kernel's own decision block picks it and its own history update runs.  A row past n_ids[b] is
+// `finished` and gets no candidate: it stores nothing, but the kernel moves its state on as for id 0 (as the runtime's launch does
+// for a finished row), so a row's states count up to its own end only.
+extern "C" int wm_op_ts_states(int32_t* states, int32_t* picks, int32_t* out_tokens, int32_t* n_tokens, int32_t* pos, int32_t* ctl,
+                               int32_t* key_lo, int32_t* tok_rows, int32_t* pos_rows, const int32_t* tokens, const int32_t* prompt_len,
+                               const int32_t* n_ids, int B, int stride, int vocab, int timestamp_begin, int eos, int max_initial, int steps,
+                               int row_prompts) {
+    if (!states || !picks || !out_tokens || !n_tokens || !pos || !ctl || !tokens || !prompt_len || !n_ids || B <= 0 || B > (1 << 20) || stride <= 0 ||
+        stride > (1 << 16) || vocab <= 0 || steps < 0)
+        return fail(WM_E_ARG, "bad argument");
+    WMCHK(ts_rules_check(vocab, timestamp_begin, eos));
+    WMCHK(replay_rows_check(tokens, prompt_len, n_ids, B, stride, vocab));
+    int Lmax = 0;
+    for (int b = 0; b < B; ++b) Lmax = std::max(Lmax, prompt_len[b]);
+    if (row_prompts) {
+        if (!key_lo || !tok_rows || !pos_rows) return fail(WM_E_ARG, "row prompts need key_lo, tok_rows and pos_rows");
+    } else {
+        if (key_lo || tok_rows || pos_rows) return fail(WM_E_ARG, "key_lo, tok_rows and pos_rows belong to row prompts");
+        if (prompt_len[0] > 16) return fail(WM_E_ARG, "the shared prompt holds at most 16 ids");
+        for (int b = 1; b < B; ++b)
+            if (prompt_len[b] != prompt_len[0] || !std::equal(tokens, tokens + prompt_len[0], tokens + (size_t)b * stride))
+                return fail(WM_E_ARG, "row %d: the rows of a shared prompt start with the same ids", b);
+    }
+    const TsRules rules{timestamp_begin, eos, max_initial, vocab};
+    TmpDev t;
+    hipStream_t st = nullptr;
+    DevBuf &out = t.add(), &nt = t.add(), &fin = t.add(), &dc = t.add(), &tr = t.add(), &pr = t.add(), &ts = t.add(), &kl = t.add(), &dpos = t.add(),
+           &pv = t.add(), &pi = t.add(), &tv = t.add(), &ti = t.add(), &tm = t.add(), &tsum = t.add(), &nx = t.add(), &dlen = t.add();
+    const size_t nb = (size_t)B * 4, no = (size_t)B * stride * 4, nr = (size_t)Lmax * B * 4;
+    WMCHK(out.alloc(no, true));
+    for (DevBuf* d : {&nt, &fin, &dpos, &pv, &pi, &tv, &ti, &tm, &tsum, &nx}) WMCHK(d->alloc(nb, true));
+    WMCHK(dc.alloc(sizeof(StepCtl), true));
+    WMCHK(ts.alloc((size_t)B * sizeof(TsState), true));
+    if (row_prompts) {
+        WMCHK(tr.alloc(nr, true));
+        WMCHK(pr.alloc(nr, true));
+        WMCHK(kl.alloc(nb, true));
+        WMCHK(upload_bytes(dlen, prompt_len, nb));
+    }
+    InitDev d{out.as<int>(), nt.as<int>(), fin.as<int>(), row_prompts ? tr.as<int>() : nullptr, row_prompts ? pr.as<int>() : nullptr,
+              row_prompts ? kl.as<int>() : nullptr, dc.as<StepCtl>(), ts.as<TsState>(), nullptr, nullptr};
+    WMCHK(op_launch_init(t, d, tokens, prompt_len[0], row_prompts ? prompt_len : nullptr, stride, Lmax, B, stride, rules));
+    if (row_prompts)
+        launch_set_rows_step(dc.as<StepCtl>(), Lmax, dpos.as<int>(), dlen.as<int>(), 0, B, st);
+    else
+        launch_set_step(dc.as<StepCtl>(), Lmax, 1, dpos.as<int>(), Lmax, nullptr, 0, B, st);
+    HIPCHK(hipGetLastError());
+    const size_t sb = (size_t)B * sizeof(TsState);
+    static_assert(sizeof(TsState) == 32, "a TsState is eight ints");
+    HIPCHK(hipMemcpy(states, ts.p, sb, hipMemcpyDeviceToHost));
+    const float ninf = -INFINITY;
+    std::vector<int32_t> h_fin(B), h_pi(B), h_ti(B);
+    std::vector<float> h_pv(B), h_tv(B), h_ts(B);
+    for (int s = 1; s <= steps; ++s) {
+        for (int b = 0; b < B; ++b) {
+            const int at = prompt_len[b] + s - 1;
+            h_fin[b] = at >= n_ids[b];
+            const int id = h_fin[b] ? -1 : tokens[(size_t)b * stride + at];
+            const bool text = id >= 0 && id < timestamp_begin, stamp = id >= timestamp_begin;
+            h_pv[b] = text ? 0.f : ninf;
+            h_pi[b] = text ? id : 0x7fffffff;
+            h_tv[b] = stamp ? 0.f : ninf;  // the partial's value and its running maximum alike
+            h_ti[b] = stamp ? id : 0x7fffffff;
+            h_ts[b] = stamp ? 1.f : 0.f;
+        }
+        HIPCHK(hipMemcpy(fin.p, h_fin.data(), nb, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(pv.p, h_pv.data(), nb, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(pi.p, h_pi.data(), nb, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(tv.p, h_tv.data(), nb, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(tm.p, h_tv.data(), nb, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ti.p, h_ti.data(), nb, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(tsum.p, h_ts.data(), nb, hipMemcpyHostToDevice));
+        ArgmaxParams a{};
+        a.V = vocab;
+        a.B = B;
+        a.pval = pv.as<float>();
+        a.pidx = pi.as<int>();
+        a.npart = 1;
+        a.next = nx.as<int>();
+        a.out_tokens = out.as<int>();
+        a.out_stride = stride;
+        a.n_tokens = nt.as<int>();
+        a.finished = fin.as<int>();
+        a.ctl = dc.as<StepCtl>();
+        a.eot = -1;
+        a.ignore_eot = 1;
+        a.advance = 1;
+        a.pos = dpos.as<int>();
+        a.ts_state = ts.as<TsState>();
+        a.rules = rules;
+        a.ts_val = tv.as<float>();
+        a.ts_idx = ti.as<int>();
+        a.ts_m = tm.as<float>();
+        a.ts_s = tsum.as<float>();
+        a.ts_part0 = 0;
+        LCHK(launch_argmax_step(a, st));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(states + (size_t)s * B * 8, ts.p, sb, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(picks + (size_t)(s - 1) * B, nx.p, nb, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipMemcpy(out_tokens, out.p, no, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(n_tokens, nt.p, nb, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pos, dpos.p, nb, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ctl, dc.p, sizeof(StepCtl), hipMemcpyDeviceToHost));
+    if (row_prompts) {
+        HIPCHK(hipMemcpy(key_lo, kl.p, nb, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(tok_rows, tr.p, nr, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(pos_rows, pr.p, nr, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// launch_set_rows_step alone: ctl [4] and pos [B_held] in and out, len [B].
+extern "C" int wm_op_set_rows_step(int32_t* ctl, int32_t* pos, const int32_t* len, int Lmax, int pos_delta, int B, int B_held) {
+    if (!ctl || !pos || !len || B <= 0 || B_held < B || B_held > (1 << 20)) return fail(WM_E_ARG, "bad argument");
+    TmpDev t;
+    DevBuf &dc = t.add(), &dp = t.add(), &dl = t.add();
+    WMCHK(upload_bytes(dc, ctl, sizeof(StepCtl)));
+    WMCHK(upload_bytes(dp, pos, (size_t)B_held * 4));
+    WMCHK(upload_bytes(dl, len, (size_t)B * 4));
+    launch_set_rows_step(dc.as<StepCtl>(), Lmax, dp.as<int>(), dl.as<int>(), pos_delta, B, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(ctl, dc.p, sizeof(StepCtl), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pos, dp.p, (size_t)B_held * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+// launch_set_step alone: ctl [4] in and out; pos, tok [B_held] in and out, each may be null (the kernel then leaves that side alone).
+extern "C" int wm_op_set_step(int32_t* ctl, int32_t* pos, int32_t* tok, int len, int set_len, int pos_value, int tok_value, int B, int B_held) {
+    if (!ctl || B <= 0 || B_held < B || B_held > (1 << 20)) return fail(WM_E_ARG, "bad argument");
+    TmpDev t;
+    DevBuf &dc = t.add(), &dp = t.add(), &dt = t.add();
+    WMCHK(upload_bytes(dc, ctl, sizeof(StepCtl)));
+    WMCHK(up_opt(dp, pos, (size_t)B_held * 4));
+    WMCHK(up_opt(dt, tok, (size_t)B_held * 4));
+    launch_set_step(dc.as<StepCtl>(), len, set_len, pos ? dp.as<int>() : nullptr, pos_value, tok ? dt.as<int>() : nullptr, tok_value, B, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(ctl, dc.p, sizeof(StepCtl), hipMemcpyDeviceToHost));
+    WMCHK(down_opt(pos, dp, (size_t)B_held * 4));
+    return down_opt(tok, dt, (size_t)B_held * 4);
+}
+// launch_pack_tokens alone: dst [rows_held][1 + stride] in and out (rows_held >= rows_cap >= rows), out_tokens [rows][out_stride],
+// n_tokens [rows].  A row's min(n_tokens, stride) ids must lie inside its out_stride.
+extern "C" int wm_op_pack_tokens(int32_t* dst, const int32_t* out_tokens, const int32_t* n_tokens, int out_stride, int rows, int rows_cap,
+                                 int rows_held, int stride) {
+    if (!dst || !out_tokens || !n_tokens || out_stride <= 0 || stride <= 0 || stride > (1 << 16) || out_stride > (1 << 16) || rows < 0 || rows_cap < rows ||
+        rows_cap < 1 || rows_held < rows_cap || rows_held > (1 << 20))
+        return fail(WM_E_ARG, "bad argument");
+    for (int r = 0; r < rows; ++r)
+        if (n_tokens[r] < 0 || std::min(n_tokens[r], stride) > out_stride) return fail(WM_E_ARG, "row %d: its ids reach past out_stride", r);
+    TmpDev t;
+    DevBuf &dd = t.add(), &dout = t.add(), &dn = t.add();
+    WMCHK(upload_bytes(dd, dst, (size_t)rows_held * (1 + stride) * 4));
+    WMCHK(upload_bytes(dout, out_tokens, (size_t)std::max(rows, 1) * out_stride * 4));
+    WMCHK(upload_bytes(dn, n_tokens, (size_t)std::max(rows, 1) * 4));
+    launch_pack_tokens(dout.as<int>(), dn.as<int>(), out_stride, rows, rows_cap, stride, dd.as<int>(), nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(dst, dd.p, (size_t)rows_held * (1 + stride) * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+// launch_dec_embed alone: x [B_held][d] in and out, tok_emb [vocab][d], pos_emb [n_pos][d], tok / pos [B] inside their tables.
+extern "C" int wm_op_dec_embed(float* x, const float* tok_emb, const float* pos_emb, const int32_t* tok, const int32_t* pos, int B, int B_held, int d,
+                               int vocab, int n_pos) {
+    if (!x || !tok_emb || !pos_emb || !tok || !pos || B <= 0 || B_held < B || B_held > (1 << 20) || d <= 0 || d > (1 << 14) || vocab <= 0 || n_pos <= 0)
+        return fail(WM_E_ARG, "bad argument");
+    for (int b = 0; b < B; ++b)
+        if (tok[b] < 0 || tok[b] >= vocab || pos[b] < 0 || pos[b] >= n_pos) return fail(WM_E_ARG, "row %d: id or position outside its table", b);
+    TmpDev t;
+    DevBuf &dx = t.add(), &te = t.add(), &pe = t.add(), &dt = t.add(), &dp = t.add();
+    WMCHK(upload_bytes(dx, x, (size_t)B_held * d * 4));
+    WMCHK(upload_bytes(te, tok_emb, (size_t)vocab * d * 4));
+    WMCHK(upload_bytes(pe, pos_emb, (size_t)n_pos * d * 4));
+    WMCHK(upload_bytes(dt, tok, (size_t)B * 4));
+    WMCHK(upload_bytes(dp, pos, (size_t)B * 4));
+    launch_dec_embed(te.as<float>(), pe.as<float>(), dt.as<int>(), dp.as<int>(), dx.as<float>(), B, d, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(x, dx.p, (size_t)B_held * d * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+// The two row copies: dst null — launch_no_speech_capture, rows [n_rows][d] -> out[0 .. n_rows); else launch_score_collect, rows[r] ->
+// out[dst[r]] for dst[r] >= 0 (dst [n_rows] in [-1, out_rows)).  out [out_rows][d] in and out; d a multiple of 4 (16-byte copies).
+extern "C" int wm_op_rows_copy(float* out, const float* rows, const int32_t* dst, int n_rows, int out_rows, int d) {
+    if (!out || !rows || n_rows <= 0 || out_rows <= 0 || out_rows > (1 << 20) || n_rows > (1 << 20) || d <= 0 || d > (1 << 14) || d % 4)
+        return fail(WM_E_ARG, "bad argument (d must be a multiple of 4)");
+    if (!dst && out_rows < n_rows) return fail(WM_E_ARG, "the plain copy needs out_rows >= n_rows");
+    if (dst)
+        for (int r = 0; r < n_rows; ++r)
+            if (dst[r] < -1 || dst[r] >= out_rows) return fail(WM_E_ARG, "dst[%d] = %d outside [-1, %d)", r, dst[r], out_rows);
+    TmpDev t;
+    DevBuf &o = t.add(), &in = t.add(), &dd = t.add();
+    WMCHK(upload_bytes(o, out, (size_t)out_rows * d * 4));
+    WMCHK(upload_bytes(in, rows, (size_t)n_rows * d * 4));
+    if (dst) {
+        WMCHK(upload_bytes(dd, dst, (size_t)n_rows * 4));
+        launch_score_collect(in.as<float>(), o.as<float>(), dd.as<int>(), n_rows, d, nullptr);
+    } else {
+        launch_no_speech_capture(in.as<float>(), o.as<float>(), n_rows, d, nullptr);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, o.p, (size_t)out_rows * d * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+// launch_mel_transpose_pad<T> alone on B clips: mel [B][C][L] fp32 -> image [B_held][L + 2][Cp] in dtype, Cp = C rounded up to 32, in
+// (rounded to dtype on upload) and out (widened): the clips behind B are the guard.
+extern "C" int wm_op_mel_transpose_pad(float* image, const float* mel, int B, int B_held, int C_in, int L, int dtype) {
+    if (!image || !mel || B <= 0 || B_held < B || B_held > 64 || C_in <= 0 || C_in > 1024 || L <= 0 || L > (1 << 16)) return fail(WM_E_ARG, "bad argument");
+    if (dtype < 0 || dtype > 2) return fail(WM_E_ARG, "bad dtype");
+    const int Cp = (C_in + 31) / 32 * 32;
+    const size_t n = (size_t)B_held * (L + 2) * Cp;
+    TmpDev t;
+    DevBuf &x = t.add(), &xt = t.add();
+    WMCHK(upload(x, mel, (size_t)B * C_in * L, WM_F32));
+    WMCHK(upload(xt, image, n, dtype));
+    DISPATCH_DT(dtype, TT, launch_mel_transpose_pad<TT>(x.as<float>(), xt.p, B, C_in, L, Cp, nullptr));
+    HIPCHK(hipGetLastError());
+    return download_f32(image, xt, n, dtype);
+}
+
 // The no-speech probe's launches on the kernel variant wm_op_logits_lp would pick for (dtype, K, B): the LP sweep with
 // no mask and no ranges, then no_speech_finish_kernel.  prob[b] = softmax(logits[b])[token], lse[b] = logsumexp(logits[b]).
 extern "C" int wm_op_no_speech(float* prob, float* lse, const float* x, const float* ln_g, const float* ln_b, const float* emb, int B, int N, int K,

@@ -700,3 +700,143 @@ def constraint_states(tokens, prompt_len, n_ids, vocab: int, phrases, steps: int
     _lib.check(_lib.lib().wm_op_constraint_states(ip(node), up(mask), ip(tok), ip(pl), ip(nn), B, stride, int(vocab), int(eot), int(ngram),
                                                   ip(ids), ip(off), n, ff, int(steps)))
     return node, mask
+
+
+def _ip(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _chk_i32(a, shape, name):
+    if a is not None and (a.dtype != np.int32 or not a.flags.c_contiguous or a.shape != tuple(shape)):
+        raise ValueError(f"{name} must be a C-contiguous int32 array of shape {tuple(shape)}")
+
+
+def ts_states(tokens, prompt_len, n_ids, vocab: int, timestamp_begin: int, eos: int, max_initial=None, steps: int = 0, row_prompts: bool = False):
+    """The timestamp rules' state machine alone (wm_op_ts_states): tokens / prompt_len / n_ids as repeat_sets; the real init
+    launch (row_prompts: the ragged-rows form, else all rows share row 0's prompt), then one argmax launch per step that is handed the
+    row's next id as its only candidate -> dict: states [steps + 1, B, 8] (TsState: n_gen, last_ts, pen_ts, t_last, text_lo, text_hi,
+    ts_lo, ts_hi; entry 0 behind the init, entry s behind step s, a row's entries counting up to its own end), picks [steps, B], the final
+    out_tokens [B, stride], n_tokens [B], pos [B], ctl [4], and with row_prompts key_lo [B], tok_rows / pos_rows [Lmax, B]."""
+    tok = np.ascontiguousarray(tokens, np.int32)
+    pl, nn = np.ascontiguousarray(prompt_len, np.int32).ravel(), np.ascontiguousarray(n_ids, np.int32).ravel()
+    if tok.ndim != 2 or pl.size != tok.shape[0] or nn.size != tok.shape[0] or steps < 0:
+        raise ValueError("tokens must be [B, stride], prompt_len and n_ids [B]")
+    B, stride = tok.shape
+    Lmax = max(1, int(pl.max()))
+    r = dict(states=np.zeros((steps + 1, B, 8), np.int32), picks=np.zeros((steps, B), np.int32), out_tokens=np.zeros((B, stride), np.int32),
+             n_tokens=np.zeros(B, np.int32), pos=np.zeros(B, np.int32), ctl=np.zeros(4, np.int32))
+    if row_prompts:
+        r.update(key_lo=np.zeros(B, np.int32), tok_rows=np.zeros((Lmax, B), np.int32), pos_rows=np.zeros((Lmax, B), np.int32))
+    _lib.check(_lib.lib().wm_op_ts_states(_ip(r["states"]), _ip(r["picks"]), _ip(r["out_tokens"]), _ip(r["n_tokens"]), _ip(r["pos"]), _ip(r["ctl"]),
+                                          _ip(r.get("key_lo")), _ip(r.get("tok_rows")), _ip(r.get("pos_rows")), _ip(tok), _ip(pl), _ip(nn), B, stride,
+                                          int(vocab), int(timestamp_begin), int(eos), -1 if max_initial is None else int(max_initial), int(steps),
+                                          int(bool(row_prompts))))
+    return r
+
+
+def init_tokens(bufs, B: int, prompt=None, table=None, lens=None, Lmax: int = 0, ts=None):
+    """init_tokens_kernel (prompt: 1 .. 16 ids) or init_tokens_rows_kernel (table [B, stride] int32 with lens [B] and Lmax) alone
+    (wm_op_init_tokens), in place on the caller's sentinel-filled int32 / float32 arrays `bufs`: out_tokens [B_held, out_stride],
+    n_tokens, finished [B_held], ctl [4], and — each None or absent: the kernel gets a null pointer — tok_rows / pos_rows [rows_held, B],
+    ts_state [B_held, 8] (then ts = (vocab, timestamp_begin, eos, max_initial or None)), logprobs [B_held, out_stride] with lp_sum
+    [B_held], key_lo [B_held] (rows form)."""
+    g = bufs.get
+    out = g("out_tokens")
+    if out is None or out.ndim != 2:
+        raise ValueError("out_tokens must be [B_held, out_stride]")
+    Bh, stride = out.shape
+    _chk_i32(out, (Bh, stride), "out_tokens")
+    for k in ("n_tokens", "finished", "key_lo"):
+        _chk_i32(g(k), (Bh,), k)
+    _chk_i32(g("ctl"), (4,), "ctl")
+    _chk_i32(g("ts_state"), (Bh, 8), "ts_state")
+    rows_held = 0
+    if g("tok_rows") is not None:
+        rows_held = g("tok_rows").shape[0]
+        _chk_i32(g("tok_rows"), (rows_held, B), "tok_rows")
+        _chk_i32(g("pos_rows"), (rows_held, B), "pos_rows")
+    if g("logprobs") is not None:
+        _chk_out(g("logprobs"), (Bh, stride))
+        _chk_out(g("lp_sum"), (Bh,))
+    if g("n_tokens") is None or g("finished") is None or g("ctl") is None:
+        raise ValueError("n_tokens, finished and ctl are required")
+    vocab, tb, eos, mi = ts if ts is not None else (0, 0, 0, None)
+    if table is not None:
+        p = np.ascontiguousarray(table, np.int32)
+        ln = np.ascontiguousarray(lens, np.int32).ravel()
+        if p.ndim != 2 or p.shape[0] != B or ln.size != B:
+            raise ValueError("table must be [B, stride] and lens [B]")
+        n_prompt, row_stride = 0, p.shape[1]
+    else:
+        p, ln = np.ascontiguousarray(prompt, np.int32).ravel(), None
+        n_prompt, row_stride = p.size, 0
+    _lib.check(_lib.lib().wm_op_init_tokens(_ip(out), _ip(g("n_tokens")), _ip(g("finished")), _ip(g("ctl")), _ip(g("tok_rows")), _ip(g("pos_rows")),
+                                            _ip(g("ts_state")), _fp(g("logprobs")), _fp(g("lp_sum")), _ip(g("key_lo")), _ip(p), n_prompt, _ip(ln),
+                                            row_stride, int(Lmax), rows_held, int(B), Bh, stride, int(vocab), int(tb), int(eos),
+                                            -1 if mi is None else int(mi)))
+    return bufs
+
+
+def set_rows_step(ctl, pos, lens, Lmax: int, pos_delta: int, B: int):
+    """set_rows_step_kernel alone (wm_op_set_rows_step), in place: ctl [4], pos [B_held] int32; lens [B]."""
+    _chk_i32(ctl, (4,), "ctl")
+    _chk_i32(pos, (pos.shape[0],), "pos")
+    ln = np.ascontiguousarray(lens, np.int32).ravel()
+    if ln.size != B:
+        raise ValueError("lens must be [B]")
+    _lib.check(_lib.lib().wm_op_set_rows_step(_ip(ctl), _ip(pos), _ip(ln), int(Lmax), int(pos_delta), int(B), pos.shape[0]))
+
+
+def set_step(ctl, pos, tok, length: int, set_len: bool, pos_value: int, tok_value: int, B: int, B_held: int):
+    """set_step_kernel alone (wm_op_set_step), in place: ctl [4]; pos, tok [B_held] int32 or None."""
+    _chk_i32(ctl, (4,), "ctl")
+    _chk_i32(pos, (B_held,), "pos")
+    _chk_i32(tok, (B_held,), "tok")
+    _lib.check(_lib.lib().wm_op_set_step(_ip(ctl), _ip(pos), _ip(tok), int(length), int(bool(set_len)), int(pos_value), int(tok_value), int(B), int(B_held)))
+
+
+def pack_tokens(dst, out_tokens, n_tokens, rows: int, rows_cap: int, stride: int):
+    """pack_tokens_kernel alone (wm_op_pack_tokens), in place on dst [rows_held, 1 + stride] int32: out_tokens [rows, out_stride],
+    n_tokens [rows]."""
+    _chk_i32(dst, (dst.shape[0], 1 + stride), "dst")
+    o = np.ascontiguousarray(out_tokens, np.int32)
+    n = np.ascontiguousarray(n_tokens, np.int32).ravel()
+    if o.ndim != 2 or o.shape[0] < rows or n.size < rows:
+        raise ValueError("out_tokens must be [rows, out_stride] and n_tokens [rows]")
+    _lib.check(_lib.lib().wm_op_pack_tokens(_ip(dst), _ip(o), _ip(n), o.shape[1], int(rows), int(rows_cap), dst.shape[0], int(stride)))
+
+
+def dec_embed(x, tok_emb, pos_emb, tok, pos):
+    """dec_embed_kernel alone (wm_op_dec_embed), in place on x [B_held, d] float32: x[b] = tok_emb[tok[b]] + pos_emb[pos[b]], b < len(tok)."""
+    te, pe = np.ascontiguousarray(tok_emb, np.float32), np.ascontiguousarray(pos_emb, np.float32)
+    t, p = np.ascontiguousarray(tok, np.int32).ravel(), np.ascontiguousarray(pos, np.int32).ravel()
+    if te.ndim != 2 or pe.ndim != 2 or te.shape[1] != pe.shape[1] or t.size != p.size or x.ndim != 2:
+        raise ValueError("tok_emb [vocab, d], pos_emb [n_pos, d], tok and pos [B]")
+    _chk_out(x, (x.shape[0], te.shape[1]))
+    _lib.check(_lib.lib().wm_op_dec_embed(_fp(x), _fp(te), _fp(pe), _ip(t), _ip(p), t.size, x.shape[0], te.shape[1], te.shape[0], pe.shape[0]))
+
+
+def rows_copy(out, rows, dst=None):
+    """no_speech_capture_kernel (dst None: out[r] = rows[r]) or score_collect_kernel (out[dst[r]] = rows[r] where dst[r] >= 0) alone
+    (wm_op_rows_copy), in place on out [out_rows, d] float32."""
+    r = np.ascontiguousarray(rows, np.float32)
+    if r.ndim != 2 or out.ndim != 2:
+        raise ValueError("rows must be [n_rows, d] and out [out_rows, d]")
+    _chk_out(out, (out.shape[0], r.shape[1]))
+    d = None
+    if dst is not None:
+        d = np.ascontiguousarray(dst, np.int32).ravel()
+        if d.size != r.shape[0]:
+            raise ValueError("dst needs one entry per row")
+    _lib.check(_lib.lib().wm_op_rows_copy(_fp(out), _fp(r), _ip(d), r.shape[0], out.shape[0], r.shape[1]))
+
+
+def mel_transpose_pad(image, mel, dtype=DT_F32):
+    """mel_transpose_pad_kernel alone (wm_op_mel_transpose_pad), in place on image [B_held, L + 2, Cp] float32 (rounded to dtype on the
+    way in, widened on the way out): mel [B, C, L], Cp = C rounded up to 32."""
+    m = np.ascontiguousarray(mel, np.float32)
+    if m.ndim != 3 or image.ndim != 3:
+        raise ValueError("mel must be [B, C, L] and image [B_held, L + 2, Cp]")
+    B, Cc, L = m.shape
+    _chk_out(image, (image.shape[0], L + 2, (Cc + 31) // 32 * 32))
+    _lib.check(_lib.lib().wm_op_mel_transpose_pad(_fp(image), _fp(m), B, image.shape[0], Cc, L, dtype))
